@@ -10,9 +10,14 @@ A "step" is one training epoch over the rank's user shard: ceil(users/B) launche
 (B users per launch, batch rule of include/poi_hip.h with --batch-cap) plus, for N > 1, the per-epoch replica
 reconciliation (one RCCL all-reduce of the parameter deltas through the library's own communicator).  Users are
 sharded across ranks (total work fixed: strong scaling); every rank holds the full parameter replica.  Inputs are
-resident in HBM before the timed region.  Rank 0 prints ONE compact JSON line (emit(): the contract fields, roofline,
-roofline_gather_scatter, cpu_baseline, headline - under 6 KB) as the last line of stdout and writes the FULL record to --full-out
-(default gpurun_out/bench_full.json).  Map of main(): setup + timed region -> exact_mode -> evaluation -> per-kernel work model and
+resident in HBM before the timed region.
+
+A plain run does only what the headline needs: setup, warm-up, the --steps timed epochs, the outputs of the last timed
+epoch when --dump-outputs DIR is given (dump_outputs()), and ONE JSON line of contract fields (emit_plain()).  Everything
+else - per-kernel timings and rooflines, evaluation, exact mode, quality, secondary shapes, CPU baseline - runs only with
+--full: rank 0 then prints ONE compact JSON line (emit(): the contract fields, roofline, roofline_gather_scatter,
+cpu_baseline, headline - under 6 KB) as the last line of stdout and writes the FULL record to --full-out.
+Map of main(): setup + timed region -> dump -> (plain: emit_plain) -> exact_mode -> evaluation -> per-kernel work model and
 roofline blocks -> quality / reference schedule -> secondary shapes (foursquare, dd25, x1 subprocess, BPR-MF) -> launch_sweep ->
 multi_gpu.projection -> cpu_baseline -> emit.  Besides the contract fields the full record carries
   roofline / roofline_gather_scatter / kernels   live HIP-event timings of the timed region against gfx950 peaks
@@ -45,7 +50,7 @@ PROFILE_TAG = "r06"         # profiles/<tag>_pmc_traffic.json: committed rocprof
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=250, help="timed training epochs (default: a >= 2 s timed window)")
+    ap.add_argument("--steps", type=int, default=None, help="timed training epochs (default: 250, a >= 2 s timed window; x1: 20)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--shape", default="gowalla", choices=["tiny", "foursquare", "gowalla", "x1"],
                     help="x1 = one GPU's slice of BASELINE.json configs[4]: 10 M POIs, 125 k users (1 M / 8), dim 256, fp16 POI table")
@@ -87,7 +92,15 @@ def parse():
                     help="path of the FULL record (every block; ~25 KB of JSON).  Default gpurun_out/bench_full.json.  stdout's last line is the compact record")
     ap.add_argument("--replica-schedule", default="quality", choices=["quality", "throughput"],
                     help="N > 1: launches per replica and epoch - as many as the one-GPU run (quality, default) or ~--batch-users users each (plan_shard)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel timings and rooflines, evaluation, exact mode, quality, secondary shapes, CPU baseline "
+                         "(the --no-* options and --full-out apply to this mode)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed epoch computed to DIR/<name>.npy (dump_outputs)")
+    a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def full_out_path(a):
@@ -107,10 +120,7 @@ def emit(a, out):
         json.dump(out, f)
     r = out["roofline"]; g = out["roofline_gather_scatter"]; c = out.get("cpu_baseline")
     sub = lambda d, ks: None if d is None else {k: d.get(k) for k in ks if k in d}
-    cfg = out["config"]
-    compact = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
-    compact["config"] = {"workload": cfg["workload"], "batch_users_per_launch": cfg["batch_users_per_launch"], "batch_rule": "capped sum, cap %g" % cfg["batch_cap"],
-                         "parallelism": cfg["parallelism"], "replica_schedule": cfg.get("replica_schedule"), "table_storage": out.get("table_storage")}
+    compact = contract_fields(out)
     compact["roofline"] = sub(r, ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "launches", "avg_ms"))
     compact["roofline_gather_scatter"] = {
         "bound": "hbm", "kernels": g["kernels"], "ms_per_epoch": g["ms_per_epoch"], "achieved": g["achieved"], "peak": g["peak"], "unit": g["unit"], "frac": g["frac"],
@@ -138,6 +148,45 @@ def emit(a, out):
     assert len(line) < 6000, len(line)
     sys.stdout.flush()
     print(line, flush=True)
+
+
+def contract_fields(out):
+    """The contract fields of a record and its compact config: the whole result line of a plain run, the head of emit()'s."""
+    cfg = out["config"]
+    compact = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
+    compact["config"] = {"workload": cfg["workload"], "batch_users_per_launch": cfg["batch_users_per_launch"], "batch_rule": "capped sum, cap %g" % cfg["batch_cap"],
+                         "parallelism": cfg["parallelism"], "replica_schedule": cfg.get("replica_schedule"), "table_storage": out.get("table_storage")}
+    return compact
+
+
+def emit_plain(out, multi):
+    """Result line of a plain run (no --full): the contract fields, + for N > 1 the self-check's scalars (world size seen, replica checksums)."""
+    line = contract_fields(out)
+    if multi:
+        line["multi_gpu"] = {k: v for k, v in multi.items() if not isinstance(v, (dict, list))}
+    sys.stdout.flush()
+    print(json.dumps(line), flush=True)
+
+
+def dump_outputs(d, model, losses, seed=0):
+    """--dump-outputs DIR: what the timed path hands its caller after the last timed epoch, as .npy files - `losses`: the (n, 5) rows
+    [los, sur, upq, ls0, ls1] that the epoch's train_batch launches returned, in launch order; the trained parameters in their logical
+    layout (di, ui, wh, bi, vs, bs, wd, loss_weight); `lt`: a fixed, seeded sample of the POI table's rows (all of them when the table
+    fits in 32 MB of float32), their row ids in `lt_rows`.  float32, `lt_rows` float64; under 40 MB in all at every shape."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    arrs = {"losses": torch.cat(losses).float().cpu().numpy()}
+    t = model.lt.t
+    n_rows, width = t.shape
+    k = min(n_rows, (32 << 20) // (4 * width))
+    rows = np.arange(n_rows) if k == n_rows else np.sort(np.random.default_rng(seed).choice(n_rows, k, replace=False))
+    lt = t[torch.as_tensor(rows, device=t.device)].float().cpu().numpy()
+    arrs["lt"] = model.lt.unpad(lt) if model.lt.unpad else lt
+    for n in ("di", "ui", "wh", "bi", "vs", "bs", "wd", "loss_weight"):
+        arrs[n] = getattr(model, n).get_value()
+    for n, v in arrs.items():
+        np.save(os.path.join(d, n + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+    np.save(os.path.join(d, "lt_rows.npy"), rows.astype(np.float64))
 
 
 def step_flops(D, NB):
@@ -223,11 +272,13 @@ def main():
         a.local = 0.0; a.no_quality = True; a.no_secondary = True; a.no_cpu_baseline = True; a.no_exact = True; a.no_x1 = True
         a.eval_users = a.eval_users or 8192
         a.table_dtype = a.table_dtype or "f16"
-        if a.steps == 250:
+        if a.steps is None:
             a.steps = 20
         if a.batch_users == 12500:
             a.batch_users = 16384      # 512 recurrent tiles of 32 sequences: two full rounds of the 256 CUs (12500 -> 391 tiles: 1.5 rounds)
     a.table_dtype = a.table_dtype or "f32"
+    if a.steps is None:
+        a.steps = 250
     ds = pdata.make_synthetic(n_user, n_item, max_len, seed=20260928 + 2, local=a.local, dd=a.dd, ud_km=a.ud_km)
     lo, hi, B, batches = plan_shard(n_user, ds.lens, a.emulate_world or world, rank, a.batch_users, a.replica_schedule)
     tab = ds.shard(lo, hi)
@@ -261,6 +312,7 @@ def main():
             _, _, bk = make_batches(n_local, lens_local, B, seed=123 + k)
             epoch_orders.append(torch.as_tensor(np.concatenate(bk).astype(np.int32)).to(dev))
     epoch_no = [0]
+    last_losses = []        # the (n, 5) loss rows the launches of the model's latest epoch returned (--dump-outputs)
 
     def train_epoch(m=None, order_=None, B_=None, n_=None):
         m = m or model; B_ = B_ or B; n_ = n_ or n_local
@@ -269,9 +321,9 @@ def main():
             order_ = epoch_orders[k % len(epoch_orders)]
             if refresh and k > 0:
                 m.resample_negatives_device(7 * 1000003 + k)
-        for b0 in range(0, n_, B_):
-            m.train_batch(order_[b0:b0 + B_], sync=False)
+        outs = [m.train_batch(order_[b0:b0 + B_], sync=False) for b0 in range(0, n_, B_)]
         if m is model:
+            last_losses[:] = outs
             sync.end_epoch()
 
     def barrier():
@@ -293,9 +345,10 @@ def main():
     torch.cuda.synchronize(dev)
     for _ in range(a.warmup):
         train_epoch()
-    # live HIP-event timing INSIDE the timed region, on every (2 n_launch + 1)-th launch: each launch position of the epoch is sampled
+    # --full: live HIP-event timing INSIDE the timed region, on every (2 n_launch + 1)-th launch: each launch position of the epoch is sampled
     # in turn and the event pairs (~7 us of stream serialisation per kernel) stay below 1 % of the region
-    ctx.timing(True, period=2 * len(batches) + 1)
+    if a.full:
+        ctx.timing(True, period=2 * len(batches) + 1)
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
@@ -319,6 +372,28 @@ def main():
             if rank == 0:
                 print(json.dumps({"error": "multi-GPU self-check failed: " + "; ".join(bad), "multi_gpu": multi}), flush=True)
             sys.exit(3)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, last_losses)
+    # exact forward pass (te_xfwd.hip, default for dims 64 / 128 / 256 and float32 tables): see the work model below
+    xfwd = D in (64, 128, 256) and os.environ.get("POI_TE_XFWD", "1") != "0"
+    head = {"metric": "check-in sequences/sec training (Distance2Pre) + all-POI top-K eval users/sec",
+            "value": seq_per_s, "unit": "sequences/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32 (forward pass: int8 x 5 fixed point + f64 gates)" if xfwd else "f32", "table_storage": a.table_dtype, "data": "synthetic"}
+    head_config = {"workload": "synthetic %s-shape: %d POIs, %d users, seq<=%d, dim=%d, %d distance bins; one step = one "
+                               "Distance2Pre training epoch over all users" % (a.shape, n_item, n_user, max_len, D, ds.dist_num),
+                   "batch_users_per_launch": B, "batch_rule": "capped sum: a row touched by k sequences of a launch moves by min(k, %g)/k x the sum of "
+                                                              "their reference updates (include/poi_hip.h); see `quality` for what it learns" % a.batch_cap,
+                   "batch_cap": a.batch_cap, "local_transition_fraction": a.local,
+                   "parallelism": "user-shard x%d, per-epoch delta all-reduce" % world,
+                   "replica_schedule": a.replica_schedule if (world > 1 or a.emulate_world) else None, "launches_per_epoch_per_replica": len(batches)}
+    if not a.full:
+        if rank == 0:
+            emit_plain(dict(head, config=head_config), multi if world > 1 else None)
+        sync.close()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
     # N > 1 under the default (quality) schedule: the throughput schedule - one launch of ~--batch-users users per replica - timed beside it
     alt_schedule = None
     if (world > 1 or a.emulate_world) and a.replica_schedule == "quality":
@@ -527,7 +602,7 @@ def main():
                and 2 * (n_item + 1) <= B * max(model.max_len - 1, 1) + 192)
     # exact forward pass (te_xfwd.hip, default for dims 64 / 128 and float32 tables): te_gemm_ax and te_rec_fwd form their products from
     # five int8 digit planes per operand - 15 digit-pair MFMAs per product - and evaluate the gates in float64
-    xfwd = D in (64, 128, 256) and os.environ.get("POI_TE_XFWD", "1") != "0"      # (dim 256: te_gemmx<256> + te_rec_fwdd, float64 MFMA recurrence)
+    # (xfwd, set beside the contract fields; dim 256: te_gemmx<256> + te_rec_fwdd, float64 MFMA recurrence)
     if xfwd:
         fwd_tab = (os.environ.get("POI_TE_FWDTAB", "1") != "0" and 2 * (n_item + 1) <= B * max(model.max_len - 1, 1) + 192)
     # ... over the launch's step-input POIs only (abi.hip: forward_table_compact, launches of >= 1536 sequences on the regrouped path): rho rows per step
@@ -966,7 +1041,7 @@ def main():
         try:
             t0 = time.perf_counter()
             x1_path = os.path.join(os.path.dirname(full_out_path(a)), "bench_full_x1.json")
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--shape", "x1", "--steps", "8", "--warmup", "2", "--eval-steps", "2", "--full-out", x1_path],
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--shape", "x1", "--steps", "8", "--warmup", "2", "--eval-steps", "2", "--full", "--full-out", x1_path],
                                capture_output=True, text=True, timeout=300)
             j = json.load(open(x1_path))
             secondary_x1 = {"workload": j["config"]["workload"], "table_storage": j["table_storage"], "f16_rounding": j["config"].get("f16_rounding"),
@@ -1030,19 +1105,10 @@ def main():
         hbm["x1"] = {"frac_survey_8d": secondary_x1["gather_scatter"].get("frac"), "frac_bytes_moved": secondary_x1.get("gather_scatter_frac_bytes_moved"),
                      "ms_per_epoch": secondary_x1["gather_scatter"].get("ms_per_epoch")}
     if rank == 0:
-        out = {
-            "metric": "check-in sequences/sec training (Distance2Pre) + all-POI top-K eval users/sec",
-            "value": seq_per_s, "unit": "sequences/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32 (forward pass: int8 x 5 fixed point + f64 gates)" if xfwd else "f32", "table_storage": a.table_dtype, "data": "synthetic",
-            "config": {"workload": "synthetic %s-shape: %d POIs, %d users, seq<=%d, dim=%d, %d distance bins; one step = one "
-                                   "Distance2Pre training epoch over all users" % (a.shape, n_item, n_user, max_len, D, ds.dist_num),
-                       "batch_users_per_launch": B, "batch_rule": "capped sum: a row touched by k sequences of a launch moves by min(k, %g)/k x the sum of "
-                                                                  "their reference updates (include/poi_hip.h); see `quality` for what it learns" % a.batch_cap,
-                       "batch_cap": a.batch_cap, "local_transition_fraction": a.local,
-                       "parallelism": "user-shard x%d, per-epoch delta all-reduce" % world,
-                       "replica_schedule": a.replica_schedule if (world > 1 or a.emulate_world) else None, "launches_per_epoch_per_replica": len(batches),
-                       "f16_rounding": a.f16_rounding if a.table_dtype == "f16" else None,
+        out = dict(head)
+        out.update({
+            "config": dict(head_config,
+                       **{"f16_rounding": a.f16_rounding if a.table_dtype == "f16" else None,
                        "alpha": 0.01, "lambda": 0.001, "engine": "tile" if "te_rec_fwd" in kernels else "per-sequence",
                        "epoch_refresh": ("every epoch redraws its negatives + negative distance bins on the device (inside the clock) and takes a new shuffled "
                                          "user order (64 distinct orders drawn before the timed region, cycled): prog_bpr_gru_spatial.py:221-238") if refresh else
@@ -1054,7 +1120,7 @@ def main():
                                      "partial products, f32 accumulate; <=5.1e-6 of the f64 oracle, same bar as the f32 MFMA path -- "
                                      "tests/test_gpu_tile_engine.py): their `frac` entries under `kernels` are f32-equivalent flops over the f32 "
                                      "matrix peak; te_wgrad / te_head / te_gemm_dx use the f32 MFMA",
-                       "s_rows_per_step": rho},
+                       "s_rows_per_step": rho}),
             "timed_window_s": dt,
             "kernels": kernels, "quality": quality, "multi_gpu": multi, "secondary": secondary, "secondary_dd25": secondary_dd25, "launch_sweep": launch_sweep, "secondary_x1": secondary_x1, "secondary_bpr": secondary_bpr,
             "train_step_tflops": executed_flops / (train_kernel_ms * 1e-3) / 1e12 if train_kernel_ms > 0 else None,
@@ -1062,7 +1128,7 @@ def main():
             "reference_schedule": reference_schedule, "eval": eval_detail, "roofline_gather_scatter": hbm,
             "roofline": roofline, "cpu_baseline": cpu,
             "steady_window": steady, "exact_mode": exact_mode, "eval_users_per_s": eval_users_per_s,
-        }
+        })
         # compact recap LAST: a record that keeps only the tail of this line still holds every headline number
         out["headline"] = {
             "train_seq_per_s": seq_per_s, "ms_per_epoch": 1e3 * dt / a.steps, "steady_seq_per_s": steady and steady["seq_per_s"],

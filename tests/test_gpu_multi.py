@@ -281,7 +281,7 @@ def test_bench_two_ranks_end_to_end_on_one_gpu(tmp_path):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--same-device", "--shape", "foursquare", "--steps", "5", "--warmup", "1",
-           "--eval-steps", "1", "--no-quality", "--no-secondary", "--no-cpu-baseline", "--no-exact", "--no-x1", "--full-out", str(tmp_path / "full.json")]
+           "--eval-steps", "1", "--no-quality", "--no-secondary", "--no-cpu-baseline", "--no-exact", "--no-x1", "--full", "--full-out", str(tmp_path / "full.json")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     last = r.stdout.strip().splitlines()[-1]

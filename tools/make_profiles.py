@@ -42,7 +42,7 @@ try:
 except Exception:
     pass
 with open(os.path.join(P, tag + "_kernel_stats.md"), "w") as f:
-    f.write("# %s - rocprofv3 --kernel-trace --stats of `python bench.py --steps 2 --warmup 1 --eval-steps 2 --no-cpu-baseline --no-quality --no-secondary --no-exact --no-x1`\n\n" % tag)
+    f.write("# %s - rocprofv3 --kernel-trace --stats of `python bench.py --full --steps 2 --warmup 1 --eval-steps 2 --no-cpu-baseline --no-quality --no-secondary --no-exact --no-x1`\n\n" % tag)
     f.write("Gowalla-shape synthetic (100 k POIs, 50 k users, L <= 50, D = 128, 200 bins; 80 %% of the transitions local), one MI355X; 4 training\n"
             "epochs of 4 launches (12500 users each) + 3 evaluation passes.  Full CSV: `%s_kernel_stats.csv`.\n\n" % tag)
     f.write("| kernel | calls | total ms | avg us | % |\n|---|---|---|---|---|\n")
@@ -52,7 +52,7 @@ with open(os.path.join(P, tag + "_kernel_stats.md"), "w") as f:
         f.write("| `%s` | %s | %.3f | %.1f | %.2f |\n" % (short(r["Name"]), r["Calls"], float(r["TotalDurationNs"]) / 1e6,
                                                          float(r["AverageNs"]) / 1e3, float(r["Percentage"])))
     if bench:
-        f.write("\nLive HIP-event timings of the same build (`bench.py`, defaults): %.0f seq/s, %.2f ms/epoch, eval %.0f users/s.\n\n"
+        f.write("\nLive HIP-event timings of the same build (`bench.py --full`, defaults): %.0f seq/s, %.2f ms/epoch, eval %.0f users/s.\n\n"
                 % (bench["value"], bench["ms_per_step"], bench.get("eval_users_per_s") or 0))
         f.write("| timed region | ms/epoch | achieved | of peak |\n|---|---|---|---|\n")
         for k, v in bench["kernels"].items():
