@@ -47,7 +47,8 @@ extern "C" {
 /* 4 (round 4): new entry point poi_ctx_set_option. */
 /* 5 (round 5): new entry point poi_comm_available; poi_bpr_step's snapshot mode is sorted and atomic-free and accepts a half POI table; the exact
  * forward pass covers dim 256 (config X); option "hot_bins". */
-#define POI_ABI_VERSION 6
+/* 7: FPMC-LR - new entry points poi_fpmc_neighbor_counts / _fill, poi_fpmc_sample_negatives, poi_fpmc_step (existing entries unchanged). */
+#define POI_ABI_VERSION 7
 
 enum {
   POI_OK = 0,
@@ -115,7 +116,8 @@ int64_t poi_ctx_graph_replays(const poi_ctx* ctx);
 /* ABI 6.  Out-of-range ids in poi_bpr_step (the reference - a Theano gather, public/BPR.py:214-218 - raises IndexError): the kernels never touch
  * memory outside the tables; a triple with a user id outside [0, n_user) or a POI id outside [0, n_item] contributes NO gradient, its loss is NaN,
  * and it is counted on the device.  poi_ctx_take_bad_ids synchronises `stream`, returns the count since the last call and clears it - the Python
- * mirror raises IndexError from OboBpr.train / train_batch(sync=True), as the reference does. */
+ * mirror raises IndexError from OboBpr.train / train_batch(sync=True), as the reference does.  ABI 7: poi_fpmc_step counts its rejected
+ * transitions (an id outside its table, or i == j) in the same counter, one per transition. */
 int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -223,7 +225,7 @@ int poi_ctx_set_topk_filter(poi_ctx* ctx, int on);
 int poi_ctx_topk_filter_stats(poi_ctx* ctx, int64_t* users, int64_t* survivors, int64_t* tiles, int64_t* tiles_flagged);
 
 /* Batch rule cap (>= 1, see "Batch semantics" above); applies to poi_spatial_step / poi_gru_step / poi_bpr_step
- * (snapshot mode) launches with more than one sequence.  n_seq == 1 is the reference step for every cap.
+ * (snapshot mode) / poi_fpmc_step launches with more than one sequence.  n_seq == 1 is the reference step for every cap.
  * cap == 0 selects the MINI-BATCH rule of the reference's `Gru` class (public/GRU.py:395-498, cost :452-459): the launch is one
  * mini-batch - loss gradients averaged over its n sequences, L2 terms of every gathered row (all len_max positions of every
  * sequence, duplicates counted) summed: row -= alpha (G / n + lambda mult row); dense tensors: theta -= alpha (G / n + lambda theta).
@@ -382,6 +384,44 @@ int poi_sample_negatives(poi_ctx* ctx, const int32_t* off, const int32_t* p, int
                          const int32_t* tes_mask, int32_t len_tes, uint64_t seed, int32_t* q_out, int32_t* tes_q_out, void* stream);
 int poi_neg_dist_bins(poi_ctx* ctx, const int32_t* off, const int32_t* p, const int32_t* q, int32_t n_user, const double* coords,
                       const double* cphi, const double* thr, int32_t n_dist, double dd, int32_t* dq_out, void* stream);
+
+/* ---- FPMC-LR (ABI 7) - prog_fpmc_lr.py, public/FPMC_LR.py, public/Load_Data_fpmc_lr.py -----------------------------------
+ * Neighbour sets (fun_acquire_neighbors_for_each_poi, Load_Data_fpmc_lr.py:114-143): neighbours(i) = {k != i : cal_dis(i, k) <= UD},
+ * CSR over POI ids: row i = nbr[off[i] .. off[i+1]), int64 offsets (totals may pass 2^31).  coords (n_item, 2) float64 lat, lon;
+ * cphi (n_item) = cos(lat * pi / 180) with the reference's libm (data.cos_lat); lat_order (n_item) = the POI ids in ascending latitude
+ * (a stable argsort); c_ud = data.ud_threshold(UD): the smallest Haversine c at which 12742 asin(sqrt(c)) > UD, so that
+ * c < c_ud <=> dist <= UD for every c and no asin / sqrt runs on the device.  c is evaluated in float64 in cal_dis's operation order
+ * (as poi_dist_prob); a query scans only the latitude band that can hold neighbours.
+ * poi_fpmc_neighbor_counts writes off_out (n_item + 1) - off_out[n_item] is the total; the caller reads it, allocates nbr (or refuses)
+ * and calls poi_fpmc_neighbor_fill with the same arguments.  Row order: ascending position in lat_order; the output is deterministic. */
+int poi_fpmc_neighbor_counts(poi_ctx* ctx, const double* coords, const double* cphi, const int32_t* lat_order, int32_t n_item, double c_ud,
+                             int64_t* off_out, void* stream);
+int poi_fpmc_neighbor_fill(poi_ctx* ctx, const double* coords, const double* cphi, const int32_t* lat_order, int32_t n_item, double c_ud,
+                           const int64_t* off, int32_t* nbr_out, void* stream);
+/* Training negatives (prog_fpmc_lr.py:188-190, random.sample(negs[i+1], 1), redrawn every epoch): neg_out[t] = one uniform draw from
+ * neighbours(pos[t]), nbr[off[i] + floor(r cnt(i))], r from the counter-based RNG of poi_sample_negatives keyed on (seed, t): the same seed
+ * gives the same output.  A position outside [0, n_item) or a POI without neighbours gets -1 (which poi_fpmc_step rejects). */
+int poi_fpmc_sample_negatives(poi_ctx* ctx, const int64_t* nbr_off, const int32_t* nbr, int32_t n_item, const int32_t* pos, int64_t n,
+                              uint64_t seed, int32_t* neg_out, void* stream);
+/* Tables (FPMC_LR.py:52-59): ui (n_user, D); iu, ia, ai (n_item + 1, D) with a padding row.  Float32 only; D a multiple of 4, D <= 128 (the
+ * evaluation scores [ui | ai[last]] . [iu | ia] at width 2 D <= 256 with poi_score_all / poi_score_topk / poi_auc_preference). */
+typedef struct poi_fpmc_params {
+  float* ui; float* iu; float* ia; float* ai;
+  int32_t n_user; int32_t n_item; int32_t dim;
+} poi_fpmc_params;
+/* n transitions (u, a = POI at t-1, i = POI at t, j = negative), FPMC_LR.py:113-151:
+ *   x = ui[u].(iu[i] - iu[j]) + ai[a].(ia[i] - ia[j]),  s = sigmoid(-x),  loss_out[t] = log sigmoid(x)  (the driver sums it as is)
+ *   ui[u] += alpha (s (iu[i] - iu[j]) - lambda ui[u])    ai[a] += alpha (s (ia[i] - ia[j]) - lambda ai[a])
+ *   iu[i] += alpha (s ui[u] - lambda iu[i])               iu[j] += alpha (-s ui[u] - lambda iu[j])
+ *   ia[i] += alpha (s ai[a] - lambda ia[i])               ia[j] += alpha (-s ai[a] - lambda ia[j])
+ * every right-hand side at the launch-entry values; batch semantics above (poi_ctx_set_batch_cap), a row's touches within one table
+ * counted together (iu[r] as a positive and as a negative: k = 2); n == 1 is the reference step.  The 6 n touches are sorted by
+ * (table, row) and summed in a fixed order with no float atomics: identical launches give bitwise identical tables.  A transition with
+ * u outside [0, n_user), a / i / j outside [0, n_item], or i == j moves nothing (no gradient, no decay, no multiplicity), its loss is NaN
+ * and it is counted once (poi_ctx_take_bad_ids).  Timing names: "fpmc_nbr_count", "fpmc_nbr_fill", "fpmc_sample", "fpmc_fwd", "fpmc_sort",
+ * "fpmc_rows", "fpmc_commit". */
+int poi_fpmc_step(poi_ctx* ctx, const poi_fpmc_params* prm, const int32_t* u, const int32_t* a, const int32_t* i, const int32_t* j, int32_t n,
+                  float alpha, float lambda, float* loss_out, void* stream);
 
 /* ---- multi-GPU reconciliation (8e; new - the reference is single-process) ----------------------
  * Users are sharded across ranks, every rank trains on a full parameter replica with no data-path collective,

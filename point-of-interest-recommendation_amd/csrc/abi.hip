@@ -3,6 +3,7 @@
 #include "../../include/poi_hip.h"
 #include "poi_kernels.h"
 
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -79,6 +80,8 @@ struct poi_ctx {
   DevBuf uidx_stage, out_stage;
   // BPR
   DevBuf g_ux, cnt_ux, g_blt, cnt_blt;
+  // FPMC-LR step: sort buffers, per-transition sigmoid, window partial sums, new-row slots
+  DevBuf fp_ws;
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)
@@ -214,7 +217,7 @@ int poi_ctx_destroy(poi_ctx* c) {
   if (!c) return POI_OK;
   DevBuf* all[] = {&c->ex_ws, &c->ex_slab, &c->ex_glt, &c->ex_gdi, &c->ws, &c->slab, &c->te_ws, &c->hslab, &c->zrow, &c->g_lt, &c->mult_lt, &c->nseq_lt, &c->g_di, &c->mult_di, &c->nseq_di, &c->seg_s, &c->seg_e, &c->pmark, &c->xc, &c->kc_dev, &c->uidx_stage, &c->out_stage, &c->ptab, &c->iota, &c->xw, &c->xg, &c->xflag, &c->bad_ids,
                    &c->g_wd, &c->mult_wd, &c->nseq_wd, &c->ca_ws, &c->ca_slab, &c->ca_scr, &c->ca2, &c->g_ux, &c->cnt_ux, &c->g_blt, &c->cnt_blt, &c->cand_s, &c->cand_i, &c->items_pk, &c->gbound, &c->st,
-                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo};
+                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws};
   (void)hipDeviceSynchronize();
   c->tm.clear();
   drop_graphs(c);
@@ -817,6 +820,98 @@ int poi_bpr_step(poi_ctx* c, float* ux, float* lt, int32_t n_user, int32_t n_ite
     A.trail = fp;
   }
   HIPCHK(c, poi::launch_bpr(A, mode, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// FPMC-LR (fpmc.hip)
+static int fpmc_nbr_common(poi_ctx* c, const double* coords, const double* cphi, const int32_t* lat_order, int32_t n_item, double c_ud,
+                           const char* who, poi::FpmcNbrArgs& A) {
+  if (!c || !coords || !cphi || !lat_order) return fail(c, POI_EINVAL, "%s: NULL argument", who);
+  if (n_item <= 0) return fail(c, POI_EINVAL, "%s: n_item must be positive (got %d)", who, n_item);
+  if (!(c_ud >= 0.0)) return fail(c, POI_EINVAL, "%s: c_ud must be >= 0", who);
+  memset(&A, 0, sizeof A);
+  A.coords = coords; A.cphi = cphi; A.order = lat_order; A.n = n_item; A.c_ud = c_ud;
+  // c >= (1 - cos a) / 2 = sin^2(a / 2): a POI more than 2 asin(sqrt(c_ud)) away in latitude is never a neighbour (1e-6 relative margin)
+  A.band_deg = c_ud >= 1.0 ? 1e9 : 2.0 * asin(sqrt(c_ud)) / 0.017453292519943295 * (1.0 + 1e-6) + 1e-9;
+  return POI_OK;
+}
+
+int poi_fpmc_neighbor_counts(poi_ctx* c, const double* coords, const double* cphi, const int32_t* lat_order, int32_t n_item, double c_ud,
+                             int64_t* off_out, void* stream) {
+  poi::FpmcNbrArgs A;
+  int rc = fpmc_nbr_common(c, coords, cphi, lat_order, n_item, c_ud, "poi_fpmc_neighbor_counts", A);
+  if (rc) return rc;
+  if (!off_out) return fail(c, POI_EINVAL, "poi_fpmc_neighbor_counts: NULL argument");
+  A.off = (long long*)off_out;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->tm.begin("fpmc_nbr_count", (hipStream_t)stream);
+  HIPCHK(c, poi::launch_fpmc_neighbors(A, 0, (hipStream_t)stream));
+  c->tm.end((hipStream_t)stream);
+  return POI_OK;
+}
+
+int poi_fpmc_neighbor_fill(poi_ctx* c, const double* coords, const double* cphi, const int32_t* lat_order, int32_t n_item, double c_ud,
+                           const int64_t* off, int32_t* nbr_out, void* stream) {
+  poi::FpmcNbrArgs A;
+  int rc = fpmc_nbr_common(c, coords, cphi, lat_order, n_item, c_ud, "poi_fpmc_neighbor_fill", A);
+  if (rc) return rc;
+  if (!off || !nbr_out) return fail(c, POI_EINVAL, "poi_fpmc_neighbor_fill: NULL argument");
+  A.off = (long long*)off; A.nbr = nbr_out;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->tm.begin("fpmc_nbr_fill", (hipStream_t)stream);
+  HIPCHK(c, poi::launch_fpmc_neighbors(A, 1, (hipStream_t)stream));
+  c->tm.end((hipStream_t)stream);
+  return POI_OK;
+}
+
+int poi_fpmc_sample_negatives(poi_ctx* c, const int64_t* nbr_off, const int32_t* nbr, int32_t n_item, const int32_t* pos, int64_t n, uint64_t seed,
+                              int32_t* neg_out, void* stream) {
+  if (!c || !nbr_off || !nbr || !pos || !neg_out) return fail(c, POI_EINVAL, "poi_fpmc_sample_negatives: NULL argument");
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "poi_fpmc_sample_negatives: bad sizes");
+  if (n == 0) return POI_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->tm.begin("fpmc_sample", (hipStream_t)stream);
+  HIPCHK(c, poi::launch_fpmc_sample((const long long*)nbr_off, nbr, pos, n, n_item, seed, neg_out, (hipStream_t)stream));
+  c->tm.end((hipStream_t)stream);
+  return POI_OK;
+}
+
+int poi_fpmc_step(poi_ctx* c, const poi_fpmc_params* P, const int32_t* u, const int32_t* a, const int32_t* i, const int32_t* j, int32_t n,
+                  float alpha, float lambda, float* loss_out, void* stream) {
+  if (!c || !P || !P->ui || !P->iu || !P->ia || !P->ai || !u || !a || !i || !j || !loss_out) return fail(c, POI_EINVAL, "poi_fpmc_step: NULL argument");
+  if (is_f16(c, P->ui) || is_f16(c, P->iu) || is_f16(c, P->ia) || is_f16(c, P->ai)) return fail(c, POI_ENOTSUP, "FPMC-LR tables are float32 only");
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 128) return fail(c, POI_ENOTSUP, "FPMC-LR: dim must be a multiple of 4 in [4, 128] (got %d)", P->dim);
+  if (n < 0 || P->n_user <= 0 || P->n_item <= 0) return fail(c, POI_EINVAL, "poi_fpmc_step: bad sizes");
+  if ((int64_t)P->n_user + 3 * ((int64_t)P->n_item + 1) >= ((int64_t)1 << 31) - 1) return fail(c, POI_ENOTSUP, "FPMC-LR: n_user + 3 (n_item + 1) must stay below 2^31");
+  if ((int64_t)n * 6 >= ((int64_t)1 << 31) - 64) return fail(c, POI_ENOTSUP, "FPMC-LR: at most 2^31 / 6 transitions per launch");
+  if (c->batch_cap == 0.0f) return fail(c, POI_ENOTSUP, "the mini-batch rule (batch cap 0) applies to poi_gru_step / poi_spatial_step only");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::FpmcArgs A;
+  memset(&A, 0, sizeof A);
+  A.ui = P->ui; A.iu = P->iu; A.ia = P->ia; A.ai = P->ai; A.n_user = P->n_user; A.n_item = P->n_item; A.dim = P->dim;
+  A.u = u; A.a = a; A.i = i; A.j = j; A.n = n; A.alpha = alpha; A.lambda = lambda; A.bcap = c->batch_cap; A.loss = loss_out;
+  A.sentinel = P->n_user + 3 * (P->n_item + 1);
+  int rc;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  size_t ni = 0, nf = 0;
+  poi::fpmc_ws_sizes(n, P->dim, &ni, &nf);
+  if ((rc = ensure(c, c->fp_ws, sizeof(int) * ni + sizeof(float) * nf + 256, st))) return rc;
+  const size_t chunks = ((size_t)6 * n + 63) / 64 + 2, per = 6 * (size_t)n + 64;
+  int* ip = (int*)c->fp_ws.p;
+  A.keys0 = ip; A.keys1 = ip + per; A.vals0 = ip + 2 * per; A.vals1 = ip + 3 * per; ip += 4 * per;
+  A.hist = ip; ip += RS_HIST_INTS + RS_MAXBIN;
+  A.cnt = ip; ip += 64;
+  A.meta = (int4*)ip; ip += 4 * chunks;
+  float* fp = (float*)ip;
+  A.s = fp; fp += ((size_t)n + 64 + 3) & ~(size_t)3;
+  A.lead = fp; fp += chunks * (size_t)P->dim;
+  A.trail = fp; fp += chunks * (size_t)P->dim;
+  A.slot = fp;
+  HIPCHK(c, poi::launch_fpmc_step(A, c->num_cu, st, &c->tm));
   return POI_OK;
 }
 

@@ -180,12 +180,7 @@ __global__ __launch_bounds__(POI_BLOCK) void ulptai_kernel(const double* __restr
 // launch geometry.  The reference draws from Python's Mersenne Twister, whose stream cannot be
 // matched; the CONTRACT (support, exclusions, bins) is what the tests pin.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
+// (splitmix64: poi_common.h)
 __device__ __forceinline__ int draw_item(unsigned long long seed, unsigned long long pos, unsigned attempt, int n_item) {
   const unsigned long long r = splitmix64(splitmix64(seed ^ (pos * 0xD1342543DE82EF95ull)) + attempt);
   return (int)__umul64hi(r, (unsigned long long)n_item);      // floor(r / 2^64 * n_item): bias < 2^-47

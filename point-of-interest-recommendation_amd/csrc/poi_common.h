@@ -211,6 +211,14 @@ __device__ __forceinline__ double cos_small(double x) {
 }
 
 
+// Counter-based RNG of the negative samplers (misc.hip sample_neg, fpmc.hip): one splitmix64 round.
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
 // Distance bin of a Haversine `c` (public/Load_Data_by_length.py:32-39) through the exact host thresholds (data.bin_thresholds):
 // bin = #{t : c >= thr[t]}, thr ascending (LDS or global).  asin(x) ~ x at these distances, so int(sqrt(c) * 12742e3 / dd) is within
 // one bin of the answer; the thresholds then decide.

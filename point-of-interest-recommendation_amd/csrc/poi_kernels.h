@@ -344,6 +344,35 @@ struct BprArgs {
 hipError_t launch_bpr(BprArgs& A, int mode, int num_cu, hipStream_t st, Timing* tm);
 void bpr_ws_sizes(int n, int dim, size_t* n_int, size_t* n_float);
 
+// FPMC-LR (fpmc.hip)
+struct FpmcNbrArgs {
+  const double *coords, *cphi;      // (n, 2) lat, lon; cos(lat * pi / 180) per POI (data.cos_lat)
+  const int* order;                 // POI ids in ascending latitude
+  int n;
+  double c_ud, band_deg;            // neighbour <=> c < c_ud; latitude half-width of the scanned band (degrees)
+  long long* off;                   // (n + 1): counts pass writes the offsets; fill pass reads them
+  int* nbr;                         // fill pass output
+};
+hipError_t launch_fpmc_neighbors(FpmcNbrArgs& A, int fill, hipStream_t st);
+hipError_t launch_fpmc_sample(const long long* off, const int* nbr, const int* pos, long long n, int n_item, unsigned long long seed, int* out,
+                              hipStream_t st);
+struct FpmcArgs {
+  float *ui, *iu, *ia, *ai;         // (n_user, D), 3 x (n_item + 1, D)
+  int n_user, n_item, dim;
+  const int *u, *a, *i, *j;
+  int n;
+  float alpha, lambda, bcap;
+  float* loss;
+  int* bad;                         // device counter of rejected transitions (poi_ctx_take_bad_ids)
+  int sentinel;                     // key of a rejected transition's touches: n_user + 3 (n_item + 1), sorts last
+  int *keys0, *keys1, *vals0, *vals1, *hist, *cnt;      // radix sort of the 6 n touches
+  const int *ks, *vs;
+  int4* meta;                       // per 64-touch window: {opening run's touches, it goes on, closing run's touches, its key}
+  float *s, *lead, *trail, *slot;   // per transition sigmoid(-x); per-window partial sums; (6 n, D) new rows at a run's first position
+};
+hipError_t launch_fpmc_step(FpmcArgs& A, int num_cu, hipStream_t st, Timing* tm);
+void fpmc_ws_sizes(int n, int dim, size_t* n_int, size_t* n_float);
+
 // scoring / top-K
 struct ScoreArgs {
   const float *users, *items; int items_f16;      // items: float32, or IEEE half when items_f16

@@ -78,6 +78,64 @@ def cos_lat(coords):
     return np.fromiter(map(math.cos, lat.tolist()), np.float64, count=len(lat))
 
 
+def ud_threshold(ud_km):
+    """FPMC-LR neighbour radius as a Haversine `c` (public/Load_Data_fpmc_lr.py:25-34, 114-143: neighbour <=> cal_dis <= UD km): the
+    smallest float64 c with 12742 * asin(sqrt(c)) > ud_km, found by bisection on the float64 bit pattern with the scalar libm calls of
+    cal_dis (as bin_thresholds).  Then  neighbour <=> c < c_ud  for every c, and the device needs no asin / sqrt."""
+    import math
+    import struct
+
+    def far(c):
+        return EARTH_D * math.asin(math.sqrt(c)) > ud_km
+
+    def val(b):
+        return struct.unpack("<d", struct.pack("<q", b))[0]
+
+    lo, hi = 0, struct.unpack("<q", struct.pack("<d", 1.0))[0]      # far(val(lo)) is False for ud_km >= 0; far(1.0) unless ud_km >= 20015
+    if not far(val(hi)):
+        return np.inf
+    if far(val(lo)):
+        return 0.0
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if far(val(mid)):
+            hi = mid
+        else:
+            lo = mid
+    return val(hi)
+
+
+def fpmc_neighbors_host(coords, ud_km, block=2048):
+    """neighbours(i) = {k != i : cal_dis(i, k) <= ud_km} (public/Load_Data_fpmc_lr.py:114-143) as CSR: (off int64 (n+1), ids int32),
+    each row ascending.  The Haversine c in cal_dis's operation order (cos of the latitudes from cos_lat), compared with ud_threshold.
+    numpy's vectorised cos may differ from the scalar libm cos of the reference in the last bit, so every pair whose c lands within
+    1e-9 (relative) of the threshold is recomputed with math.cos: the sets equal the reference's on every input.  The CPU checker of
+    poi_fpmc_neighbor_counts / _fill."""
+    import math
+    xy = np.asarray(coords, np.float64)
+    n = len(xy)
+    c_ud = ud_threshold(ud_km)
+    cphi = cos_lat(xy)
+    lat, lon = xy[:, 0], xy[:, 1]
+    counts, ids = np.zeros(n, np.int64), []
+    for r0 in range(0, n, block):
+        r1 = min(n, r0 + block)
+        a = (lat[r0:r1, None] - lat[None, :]) * DEG
+        b = (lon[r0:r1, None] - lon[None, :]) * DEG
+        c = (1.0 - np.cos(a)) / 2 + cphi[r0:r1, None] * cphi[None, :] * (1.0 - np.cos(b)) / 2
+        near = np.abs(c - c_ud) <= 1e-9 * c_ud
+        for q, k in zip(*np.nonzero(near)):
+            i = r0 + int(q)
+            c[q, k] = (1.0 - math.cos((lat[i] - lat[k]) * DEG)) / 2 + cphi[i] * cphi[k] * (1.0 - math.cos((lon[i] - lon[k]) * DEG)) / 2
+        m = c < c_ud
+        m[np.arange(r1 - r0), np.arange(r0, r1)] = False
+        counts[r0:r1] = m.sum(axis=1)
+        ids.append(np.nonzero(m)[1].astype(np.int32))
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(counts, out=off[1:])
+    return off, (np.concatenate(ids) if ids else np.zeros(0, np.int32))
+
+
 def padded_to_csr(rows, lens):
     """Nested (U, LM) table + valid lengths -> (off int32 (U+1), flat int32)."""
     rows = np.asarray(rows)

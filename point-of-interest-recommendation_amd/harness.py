@@ -221,3 +221,53 @@ def cal_s(ds, p, device="cuda:0", out_root="./Lmdd", log=print):
     out = os.path.join(out_root, "%s_size%s_UD%s_dd%s_epoch%slast1" % (p["dataset"], p["latent_size"], p["UD"], p["dd"], p["load_epoch"]))
     np.save(out, sts)
     return out + ".npy", sts
+
+
+def fpmc_default_params():
+    """The in-source config of prog_fpmc_lr.py:55-73 (+ `batch`: transitions per launch - 1 is the reference's one-by-one training -, seed)."""
+    return dict(at_nums=[5, 10, 15, 20], epochs=200, latent_size=20, alpha=0.01, **{"lambda": 0.001}, UD=20, batch_size_train=1,
+                batch_size_test=32, batch=1, seed=123)
+
+
+def train_fpmc_lr(ds, p=None, device="cuda:0", log=print):
+    """train_valid_or_test of prog_fpmc_lr.py:149-216 on a PoiDataset: OboFpmc_lr over ds (neighbour sets within p['UD'] km built on the
+    device), then per epoch: new test negatives (epoch > 0), users shuffled, every transition (u, p[t-1], p[t], one neighbour of p[t]) trained
+    in launches of p['batch'] transitions, the sum_loss line (sum of log sigmoid, l2 = model.l2), AUC / top-K metrics into GlobalBest.
+    Returns (model, best, history)."""
+    p = dict(fpmc_default_params(), **(p or {}))
+    tab = ds.shard()
+    model = models.OboFpmc_lr(train=tab, test=None, alpha_lambda=[p["alpha"], p["lambda"]], n_user=ds.n_user, n_item=ds.n_item,
+                              n_size=p["latent_size"], device=device, seed=p.get("seed"), coords=ds.coords, ud_km=p["UD"])
+    best = GlobalBest(p["at_nums"])
+    U = ds.n_user
+    ses_tes = compute_start_end(U, p["batch_size_test"])
+    ses_auc = compute_start_end(U, p["batch_size_test"] * 10)
+    tes_p, tes_m = ds.tes_p.reshape(-1, 1), np.ones((U, 1), np.int32)
+    B = max(1, int(p.get("batch", 1)))
+    history = []
+    for epoch in range(p["epochs"]):
+        if epoch > 0:                                               # :171-174
+            model.resample_test_negatives_device(p.get("seed", 0) * 1000003 + epoch)
+        t0 = time.time()
+        order = np.random.default_rng(123 + epoch).permutation(U)   # :179-181
+        u, a, i, j = model.epoch_transitions(p.get("seed", 0) * 7919 + epoch, order)
+        n = u.numel()
+        loss = 0.0
+        if B == 1:                                                  # :182-190, one transition per call
+            hu, ha, hi, hj = (t.cpu().numpy() for t in (u, a, i, j))
+            for t in range(n):
+                loss += model.train(int(hu[t]), int(ha[t]), int(hi[t]), [int(hj[t])])
+        else:
+            parts = [model.train_batch(u[s:s + B], a[s:s + B], i[s:s + B], j[s:s + B], sync=False) for s in range(0, n, B)]
+            if model.ctx.take_bad_ids(model._stream().value):
+                raise IndexError("rejected transitions in epoch %d" % epoch)
+            loss = float(torch.cat(parts).double().sum().item()) if parts else 0.0
+        l2 = model.l2.eval()                                        # :191
+        t1 = time.time()
+        m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m)      # :199-201
+        t2 = time.time()
+        history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall={k: m["at"][k]["recall"] for k in p["at_nums"]},
+                            transitions=n, times=(t1 - t0, t2 - t1)))
+        log("epoch %d  sum_loss = %.3f = %.3f - %.3f  auc %.4f  recall@%d %.4f  time (train, test) %.2fs %.2fs"
+            % (epoch, loss + l2, loss, l2, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1))
+    return model, best, history

@@ -909,3 +909,215 @@ class OboBpr(MfBasic):
         lens = torch.as_tensor(np.diff(self._off_host.astype(np.int64))).to(self.device)
         u = torch.repeat_interleave(self._arange, lens)
         return u, self.p, self.q
+
+
+# =================================================================================================
+class OboFpmc_lr(_Base):
+    """public/FPMC_LR.py:27-166 (driver prog_fpmc_lr.py): FPMC with localized regions.  Four tables ui (n_user, D) and iu / ia / ai
+    (n_item + 1, D); a transition (u, a = POI at t-1, i = POI at t, j = negative among i's neighbours) moves six rows (poi_fpmc_step).
+
+    train: the reference's [tra_pois, tra_pois_negs, tra_last_poi] (tra_pois_negs is not read: the neighbour sets are built on the device from
+    `coords` and `ud_km`, fun_acquire_neighbors_for_each_poi) or a CsrTables (PoiDataset.shard()).  test: [tes_buys_masks, tes_masks,
+    tes_buys_neg_masks] (None with CsrTables).  n_size = D (a multiple of 4, <= 128).  Extra keywords: device, init (dict of float64 arrays
+    ui / iu / ia / ai), seed, coords ((n_item, 2) lat, lon - required), ud_km (UD, default 20 as prog_fpmc_lr.py:70), max_pairs (refuse neighbour
+    sets larger than this)."""
+
+    TABLES = ("ui", "iu", "ia", "ai")
+
+    def __init__(self, train, test, alpha_lambda, n_user, n_item, n_size, device="cuda:0", init=None, seed=None, coords=None, ud_km=20.0,
+                 max_pairs=1 << 31):
+        from .data import ud_threshold
+        self.n_user, self.n_item, self.dim = int(n_user), int(n_item), int(n_size)
+        if self.dim <= 0 or self.dim % 4 or self.dim > 128:
+            raise ValueError("OboFpmc_lr: n_size must be a multiple of 4 in [4, 128] (got %d)" % self.dim)
+        if coords is None:
+            raise ValueError("OboFpmc_lr needs coords= (the neighbour sets are built on the device from the POI coordinates)")
+        off, p, tes = self._host_tables(train, test)
+        lens = np.diff(off.astype(np.int64))
+        if len(lens) != self.n_user:
+            raise ValueError("OboFpmc_lr: %d train sequences for n_user = %d" % (len(lens), self.n_user))
+        if np.any(lens <= 0):           # PoiDataset.last_pois() would silently read the previous user's POI
+            raise ValueError("OboFpmc_lr: user(s) %s have an empty train sequence (no last POI)" % np.nonzero(lens <= 0)[0][:8].tolist())
+        for nm, t in (("train POIs", p), ("test POIs", tes[0]), ("test negatives", tes[2])):
+            self._check_ids(nm, t, self.n_item)
+        if p.size and p.max() >= self.n_item:
+            raise IndexError("train POIs must lie in [0, %d)" % self.n_item)
+        self._setup(device, alpha_lambda)
+        self.ud_km, self.c_ud = float(ud_km), float(ud_threshold(ud_km))
+        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+        self._off_host, self._lens = off, lens
+        self.off, self.p = i32(off), i32(p)
+        self.tes_buys_masks, self.tes_masks, self.tes_buys_neg_masks = i32(tes[0]), i32(tes[1]), i32(tes[2])
+        self._arange = torch.arange(self.n_user, dtype=torch.int32, device=self.device)
+        self.tra_last_poi = i32(p[off[1:].astype(np.int64) - 1])
+        xy = np.ascontiguousarray(coords, np.float64)
+        if xy.shape != (self.n_item, 2):
+            raise ValueError("coords must be (n_item, 2) lat, lon (got %s)" % (xy.shape,))
+        self.coords = torch.as_tensor(xy).to(self.device)
+        self._cphi = torch.as_tensor(cos_lat(xy)).to(self.device)
+        self.nbr_off, self.nbr = self.build_neighbors(max_pairs)
+        # transitions t = 1 .. len-1 of every user (prog_fpmc_lr.py:188-190): a target without a neighbour cannot be trained
+        # (random.sample(negs[i+1], 1) raises there too)
+        cnt = np.diff(self.nbr_off.cpu().numpy())
+        first = np.zeros(len(p), bool)
+        first[off[:-1].astype(np.int64)] = True
+        lonely = np.unique(p[~first][cnt[p[~first]] == 0])
+        if lonely.size:
+            raise ValueError("OboFpmc_lr: train target POI(s) %s have no neighbour within %g km" % (lonely[:8].tolist(), self.ud_km))
+        rng = np.random.default_rng(seed) if seed is not None else np.random
+        init = init or {}
+        shapes = dict(ui=(self.n_user, self.dim), iu=(self.n_item + 1, self.dim), ia=(self.n_item + 1, self.dim), ai=(self.n_item + 1, self.dim))
+        for k in ("ui", "iu", "ia", "ai"):                                                     # FPMC_LR.py:52-59
+            v = init[k] if k in init else rng.uniform(-0.5, 0.5, shapes[k])
+            t = self._dev(v)
+            if tuple(t.shape) != shapes[k]:
+                raise ValueError("init[%r] has shape %s, expected %s" % (k, tuple(t.shape), shapes[k]))
+            setattr(self, k, Shared(t))
+        self.params = [self.ui, self.iu, self.ai, self.ia]                                     # :61
+        self.l2 = _L2(self, ["ui", "iu", "ai", "ia"])                                          # :62-64
+        self._version, self._items_cat = 0, None
+
+    def _host_tables(self, train, test):
+        if isinstance(train, CsrTables):
+            off = np.ascontiguousarray(train.off, np.int32)
+            return off, np.ascontiguousarray(train.p, np.int32), (np.asarray(train.tes_p), np.asarray(train.tes_mask), np.asarray(train.tes_q))
+        tra_pois = train[0]
+        lens = np.array([len(s) for s in tra_pois], np.int64)
+        off = np.zeros(len(lens) + 1, np.int64)
+        np.cumsum(lens, out=off[1:])
+        p = np.array([x for s in tra_pois for x in s], np.int64).astype(np.int32) if off[-1] else np.zeros(0, np.int32)
+        return off.astype(np.int32), p, tuple(np.asarray(t) for t in test)
+
+    # ---- neighbour sets / negatives -----------------------------------------------------------
+    def build_neighbors(self, max_pairs=1 << 31):
+        """(off int64 (n_item + 1), ids int32) of neighbours(i) = {k != i : cal_dis(i, k) <= UD} on the device (Load_Data_fpmc_lr.py:114-143):
+        a count pass, then - if the total is at most max_pairs - the fill pass into a buffer of exactly that size."""
+        order = torch.argsort(self.coords[:, 0], stable=True).to(torch.int32).contiguous()
+        off = torch.empty(self.n_item + 1, dtype=torch.int64, device=self.device)
+        self.ctx.check(self.lib.poi_fpmc_neighbor_counts(self.ctx.handle, _ptr(self.coords), _ptr(self._cphi), _ptr(order), self.n_item, self.c_ud,
+                                                         _ptr(off), self._stream()))
+        total = int(off[-1].item())
+        if total > max_pairs:
+            raise _lib.PoiError("FPMC-LR neighbour sets hold %d pairs (%.1f per POI at UD = %g km), above the limit of %d"
+                                % (total, total / self.n_item, self.ud_km, max_pairs))
+        nbr = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)
+        self.ctx.check(self.lib.poi_fpmc_neighbor_fill(self.ctx.handle, _ptr(self.coords), _ptr(self._cphi), _ptr(order), self.n_item, self.c_ud,
+                                                       _ptr(off), _ptr(nbr), self._stream()))
+        return off, nbr
+
+    def sample_negatives(self, pos, seed):
+        """One uniform draw from neighbours(pos[t]) per entry (prog_fpmc_lr.py:190, random.sample(negs[i+1], 1)); device int32."""
+        pos = pos.to(self.device, torch.int32).contiguous()
+        out = torch.empty_like(pos)
+        self.ctx.check(self.lib.poi_fpmc_sample_negatives(self.ctx.handle, _ptr(self.nbr_off), _ptr(self.nbr), self.n_item, _ptr(pos), pos.numel(),
+                                                          int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out), self._stream()))
+        return out
+
+    def epoch_transitions(self, seed, order=None):
+        """All transitions of an epoch in the reference's order (prog_fpmc_lr.py:183-190: users in `order` - default 0..n_user-1 -, positions
+        t = 1 .. len-1, a = p[t-1], i = p[t]) with fresh negatives from the device sampler: device int32 tensors (u, a, i, j)."""
+        off = self._off_host.astype(np.int64)
+        users = np.arange(self.n_user) if order is None else np.asarray(order, np.int64)
+        lens = self._lens[users] - 1
+        starts = np.repeat(off[users] + 1 - np.concatenate(([0], np.cumsum(lens)[:-1])), lens)
+        pos = torch.as_tensor(starts + np.arange(int(lens.sum()))).to(self.device)
+        u = torch.as_tensor(np.repeat(users, lens).astype(np.int32)).to(self.device)
+        i = self.p.index_select(0, pos)
+        a = self.p.index_select(0, pos - 1)
+        return u, a, i, self.sample_negatives(i, seed)
+
+    def update_neg_masks(self, tes_buys_neg_masks):
+        """FPMC_LR.py:71-73: new test negatives every epoch."""
+        self._check_ids("test negatives", tes_buys_neg_masks, self.n_item)
+        self.tes_buys_neg_masks = self._dev(tes_buys_neg_masks, torch.int32)
+
+    def resample_test_negatives_device(self, seed):
+        """fun_random_neg_masks_tes (Load_Data_fpmc_lr.py:81-99) on the device: poi_sample_negatives' test output (the train draw it makes
+        alongside goes to a scratch buffer - FPMC-LR's train negatives come from the neighbour sets)."""
+        scratch = torch.empty_like(self.p)
+        tq = torch.empty_like(self.tes_buys_masks)
+        self.ctx.check(self.lib.poi_sample_negatives(self.ctx.handle, _ptr(self.off), _ptr(self.p), self.n_user, self.n_item,
+                                                     _ptr(self.tes_buys_masks), _ptr(self.tes_masks), self.tes_masks.shape[1],
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(scratch), _ptr(tq), self._stream()))
+        self.tes_buys_neg_masks = tq
+
+    # ---- training -----------------------------------------------------------------------------
+    def _fparams(self):
+        return _lib.FpmcParams(*[ctypes.c_void_p(getattr(self, k).t.data_ptr()) for k in ("ui", "iu", "ia", "ai")], self.n_user, self.n_item, self.dim)
+
+    def train(self, uidx, aidx, iidx, jidxs):
+        """seq_train(uidx, aidx, [iidx] + jidxs) (FPMC_LR.py:153-163) with the driver's one negative -> log sigmoid(x)."""
+        j = list(np.atleast_1d(np.asarray(jidxs)))
+        if len(j) != 1:
+            raise ValueError("OboFpmc_lr.train takes one negative per transition (prog_fpmc_lr.py:190); got %d" % len(j))
+        return float(self.train_batch([uidx], [aidx], [iidx], j)[0])
+
+    def train_batch(self, u, a, i, j, sync=True):
+        """A launch of n transitions (poi_fpmc_step, batch semantics of include/poi_hip.h) -> log sigmoid(x) per transition.  With sync, a
+        launch that held a transition with an id outside its table (or i == j) raises IndexError - those transitions moved nothing."""
+        conv = lambda v: v.to(self.device, torch.int32).contiguous() if isinstance(v, torch.Tensor) else \
+            torch.as_tensor(np.asarray(v, np.int64).astype(np.int32)).to(self.device)
+        u, a, i, j = conv(u), conv(a), conv(i), conv(j)
+        n = u.numel()
+        if not (a.numel() == i.numel() == j.numel() == n):
+            raise ValueError("u, a, i, j must have the same length")
+        loss = torch.empty(n, dtype=torch.float32, device=self.device)
+        P = self._fparams()
+        self.ctx.check(self.lib.poi_fpmc_step(self.ctx.handle, ctypes.byref(P), _ptr(u), _ptr(a), _ptr(i), _ptr(j), n, self.alpha_lambda[0],
+                                              self.alpha_lambda[1], _ptr(loss), self._stream()))
+        self._version += 1
+        if sync:
+            nb = self.ctx.take_bad_ids(self._stream().value)
+            if nb:
+                raise IndexError("%d transition(s) with an id outside its table or i == j in this launch: they moved nothing, their losses are NaN" % nb)
+        return loss.cpu().numpy() if sync else loss
+
+    # ---- evaluation (FPMC_LR.py:75-104): live tables, [ui | ai[last]] . [iu | ia] at width 2 D ----------------------------------------
+    @property
+    def kdim(self):
+        return 2 * self.dim
+
+    def _items(self):
+        """(n_item + 1, 2 D) item concatenation, rebuilt once after the tables moved (once per evaluation)."""
+        if self._items_cat is None or self._items_cat[0] != self._version:
+            self._items_cat = (self._version, torch.cat([self.iu.t, self.ia.t], 1).contiguous())
+        return self._items_cat[1]
+
+    def _users_rows(self, start_end):
+        ids, lo = self._ids(start_end)
+        last = self._rows(self.tra_last_poi, ids, lo)
+        return ids, torch.cat([self._rows(self.ui.t, ids, lo), self.ai.t.index_select(0, last.long())], 1).contiguous(), lo
+
+    def compute_sub_all_scores_device(self, start_end):
+        """FPMC_LR.py:76-82 -> (n, n_item) device tensor."""
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        out = torch.empty((n, self.n_item), dtype=torch.float32, device=self.device)
+        self.ctx.check(self.lib.poi_score_all(self.ctx.handle, _ptr(users), _ptr(self._items()), n, self.n_item, self.kdim, None, None,
+                                              _ptr(out), self._stream()))
+        return out
+
+    def compute_sub_topk(self, start_end, k, return_scores=False):
+        """Valuate.py:132-146 on the FPMC-LR scores through the fused top-K kernel: (n, k) int32 ids by descending score."""
+        if k > 32:
+            return self._topk_from_scores(start_end, k, return_scores)
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_scores else None
+        seed = self._seed_begin(lo, n, k)
+        self.ctx.check(self.lib.poi_score_topk(self.ctx.handle, _ptr(users), _ptr(self._items()), n, self.n_item, self.kdim, None, None, int(k),
+                                               _ptr(idx), _ptr(sc), self._stream()))
+        self._seed_end(seed, idx)
+        return (idx, sc) if return_scores else idx
+
+    def compute_sub_auc_preference(self, start_end):
+        """FPMC_LR.py:84-104 -> bool ndarray (n, len_tes)."""
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        ln = self.tes_masks.shape[1]
+        tp, tq, tm = (self._rows(t, ids, lo) for t in (self.tes_buys_masks, self.tes_buys_neg_masks, self.tes_masks))
+        out = torch.empty((n, ln), dtype=torch.uint8, device=self.device)
+        self.ctx.check(self.lib.poi_auc_preference(self.ctx.handle, _ptr(users), _ptr(self._items()), n, self.kdim, _ptr(tp), _ptr(tq), _ptr(tm),
+                                                   ln, _ptr(out), self._stream()))
+        return out.cpu().numpy().astype(bool)
