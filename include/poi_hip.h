@@ -48,7 +48,8 @@ extern "C" {
 /* 5 (round 5): new entry point poi_comm_available; poi_bpr_step's snapshot mode is sorted and atomic-free and accepts a half POI table; the exact
  * forward pass covers dim 256 (config X); option "hot_bins". */
 /* 7: FPMC-LR - new entry points poi_fpmc_neighbor_counts / _fill, poi_fpmc_sample_negatives, poi_fpmc_step (existing entries unchanged). */
-#define POI_ABI_VERSION 7
+/* 8: PRME - new entry points poi_prme_step, poi_prme_score_all, poi_prme_score_topk and poi_prme_params (existing entries unchanged). */
+#define POI_ABI_VERSION 8
 
 enum {
   POI_OK = 0,
@@ -117,7 +118,7 @@ int64_t poi_ctx_graph_replays(const poi_ctx* ctx);
  * memory outside the tables; a triple with a user id outside [0, n_user) or a POI id outside [0, n_item] contributes NO gradient, its loss is NaN,
  * and it is counted on the device.  poi_ctx_take_bad_ids synchronises `stream`, returns the count since the last call and clears it - the Python
  * mirror raises IndexError from OboBpr.train / train_batch(sync=True), as the reference does.  ABI 7: poi_fpmc_step counts its rejected
- * transitions (an id outside its table, or i == j) in the same counter, one per transition. */
+ * transitions (an id outside its table, or i == j) in the same counter, one per transition.  ABI 8: so does poi_prme_step. */
 int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -225,7 +226,7 @@ int poi_ctx_set_topk_filter(poi_ctx* ctx, int on);
 int poi_ctx_topk_filter_stats(poi_ctx* ctx, int64_t* users, int64_t* survivors, int64_t* tiles, int64_t* tiles_flagged);
 
 /* Batch rule cap (>= 1, see "Batch semantics" above); applies to poi_spatial_step / poi_gru_step / poi_bpr_step
- * (snapshot mode) / poi_fpmc_step launches with more than one sequence.  n_seq == 1 is the reference step for every cap.
+ * (snapshot mode) / poi_fpmc_step / poi_prme_step launches with more than one sequence.  n_seq == 1 is the reference step for every cap.
  * cap == 0 selects the MINI-BATCH rule of the reference's `Gru` class (public/GRU.py:395-498, cost :452-459): the launch is one
  * mini-batch - loss gradients averaged over its n sequences, L2 terms of every gathered row (all len_max positions of every
  * sequence, duplicates counted) summed: row -= alpha (G / n + lambda mult row); dense tensors: theta -= alpha (G / n + lambda theta).
@@ -422,6 +423,42 @@ typedef struct poi_fpmc_params {
  * "fpmc_rows", "fpmc_commit". */
 int poi_fpmc_step(poi_ctx* ctx, const poi_fpmc_params* prm, const int32_t* u, const int32_t* a, const int32_t* i, const int32_t* j, int32_t n,
                   float alpha, float lambda, float* loss_out, void* stream);
+
+/* ---- PRME (ABI 8) - prog_prme.py, public/PRME.py (public/PRPRM.py: the same maths), public/Load_Data_prme.py -------------------
+ * Tables (PRME.py:75-82): du (n_user, D); dp, ds (n_item + 1, D) with a padding row.  Float32 only; D a multiple of 4, D <= 128. */
+typedef struct poi_prme_params {
+  float* du; float* dp; float* ds;
+  int32_t n_user; int32_t n_item; int32_t dim;
+} poi_prme_params;
+/* n transitions (u, p = POI at i, q = negative, prev = POI at i-1, d = dist[i] float64 km, gap[i] minutes), replacing OboPrme.train
+ * (PRME.py:173-219, driver prog_prme.py:191-197):
+ *   far = gap > threshold,  w = (1 + d)^0.25,  a = far ? 1 : w cw,  b = far ? 0 : w (1 - cw)
+ *   x = a (|du-dp_q|^2 - |du-dp_p|^2) + b (|ds_q-ds_prev|^2 - |ds_p-ds_prev|^2),  loss_out[t] = log sigmoid(x),  g = sigmoid(-x)
+ *   du += alpha (2a g (dp_p - dp_q) - lambda du)          dp_p += alpha (2a g (du - dp_p) - lambda dp_p)
+ *   dp_q += alpha (-2a g (du - dp_q) - lambda dp_q)       dp_prev += alpha (-lambda dp_prev)
+ *   ds_p += alpha (-2b g (ds_p - ds_prev) - lambda ds_p)  ds_q += alpha (2b g (ds_q - ds_prev) - lambda ds_q)
+ *   ds_prev += alpha (2b g (ds_p - ds_q) - lambda ds_prev)
+ * every right-hand side at the launch-entry values.  A repeated row within one transition keeps the LAST occurrence in the order
+ * (p, q, prev) - Theano's set_subtensor: with p == prev, dp[p] moves by decay only and ds[p] takes the prev occurrence's update - and
+ * then counts as one touch.  Batch semantics above (poi_ctx_set_batch_cap); n == 1 is the reference step.  The 7 n touches are sorted by
+ * (table, row) and summed in a fixed order with no float atomics: identical launches give bitwise identical tables.  A transition with
+ * u outside [0, n_user), p / q / prev outside [0, n_item], p == q, or d not finite or < 0 moves nothing, its loss is NaN and it is
+ * counted once (poi_ctx_take_bad_ids).  Timing names: "prme_fwd", "prme_sort", "prme_rows", "prme_commit". */
+int poi_prme_step(poi_ctx* ctx, const poi_prme_params* prm, const int32_t* u, const int32_t* p, const int32_t* q, const int32_t* prev,
+                  const double* d, const int32_t* gap, int32_t n, float alpha, float lambda, int32_t threshold, float cw, float* loss_out,
+                  void* stream);
+/* Geo-weighted all-POI scores, replacing PrmeBasic.compute_sub_all_scores (PRME.py:117-139): prm holds the trained snapshots
+ * (du, dp with at least n_item rows, ds with n_item + 1); coords (n_item + 1, 2) float64 lat, lon, row n_item the pad POI (0, 0).
+ * Output row r is (users[r], query POI qpoi[r] in [0, n_item]); for a candidate j < n_item
+ *   out[r][j] = -(1 + cal_dis(qpoi[r], j))^0.25 (cw |du[users[r]] - dp[j]|^2 + (1 - cw) |ds[qpoi[r]] - ds[j]|^2)
+ * squared distances as float32 differences, the weight in float64 in cal_dis's operation order (Load_Data_prme.py:24-35).  A row with
+ * an id out of range is NaN.  poi_prme_score_all writes out (n_rows, n_item); poi_prme_score_topk the k <= 64 (k <= n_item) best ids per
+ * row, by descending score then ascending id (poi_score_topk's rule), and their scores when score_out is not NULL; a row with an id out
+ * of range gets ids -1.  Timing names: "prme_score_all", "prme_score_topk". */
+int poi_prme_score_all(poi_ctx* ctx, const poi_prme_params* prm, const double* coords, const int32_t* users, const int32_t* qpoi, int32_t n_rows,
+                       float cw, float* out, void* stream);
+int poi_prme_score_topk(poi_ctx* ctx, const poi_prme_params* prm, const double* coords, const int32_t* users, const int32_t* qpoi,
+                        int32_t n_rows, float cw, int32_t k, int32_t* idx_out, float* score_out, void* stream);
 
 /* ---- multi-GPU reconciliation (8e; new - the reference is single-process) ----------------------
  * Users are sharded across ranks, every rank trains on a full parameter replica with no data-path collective,

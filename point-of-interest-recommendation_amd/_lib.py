@@ -6,7 +6,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libpoi_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 BPR_SNAPSHOT, BPR_HOGWILD = 0, 1
 
@@ -26,6 +26,10 @@ class CarnnParams(ctypes.Structure):
 
 class FpmcParams(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("ui", "iu", "ia", "ai")] + [("n_user", c_int32), ("n_item", c_int32), ("dim", c_int32)]
+
+
+class PrmeParams(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("du", "dp", "ds")] + [("n_user", c_int32), ("n_item", c_int32), ("dim", c_int32)]
 
 
 class SyncSeg(ctypes.Structure):
@@ -102,6 +106,11 @@ SIGNATURES = {
     "poi_fpmc_sample_negatives": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, ctypes.c_uint64, c_void_p, c_void_p]),
     "poi_fpmc_step": (c_int, [c_void_p, POINTER(FpmcParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float, c_void_p,
                               c_void_p]),
+    "poi_prme_step": (c_int, [c_void_p, POINTER(PrmeParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float,
+                              c_float, c_int32, c_float, c_void_p, c_void_p]),
+    "poi_prme_score_all": (c_int, [c_void_p, POINTER(PrmeParams), c_void_p, c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p]),
+    "poi_prme_score_topk": (c_int, [c_void_p, POINTER(PrmeParams), c_void_p, c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p,
+                                    c_void_p]),
     "poi_delta_make": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_delta_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_comm_available": (c_int, []),
@@ -199,7 +208,7 @@ class Context:
         return dict(zip(("users", "survivors", "tiles", "tiles_flagged"), (x.value for x in v)))
 
     def take_bad_ids(self, stream=None):
-        """Out-of-range ids seen by poi_bpr_step (rejected transitions of poi_fpmc_step) since the last call (synchronises the stream, clears the counter)."""
+        """Out-of-range ids seen by poi_bpr_step (rejected transitions of poi_fpmc_step / poi_prme_step) since the last call (synchronises the stream, clears the counter)."""
         v = int(self.lib.poi_ctx_take_bad_ids(self.handle, ctypes.c_void_p(stream or 0)))
         if v < 0:
             self.check(v)

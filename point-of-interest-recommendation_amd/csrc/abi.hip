@@ -82,6 +82,8 @@ struct poi_ctx {
   DevBuf g_ux, cnt_ux, g_blt, cnt_blt;
   // FPMC-LR step: sort buffers, per-transition sigmoid, window partial sums, new-row slots
   DevBuf fp_ws;
+  // PRME step: the same layout for 7 touches per transition
+  DevBuf pr_ws;
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)
@@ -217,7 +219,7 @@ int poi_ctx_destroy(poi_ctx* c) {
   if (!c) return POI_OK;
   DevBuf* all[] = {&c->ex_ws, &c->ex_slab, &c->ex_glt, &c->ex_gdi, &c->ws, &c->slab, &c->te_ws, &c->hslab, &c->zrow, &c->g_lt, &c->mult_lt, &c->nseq_lt, &c->g_di, &c->mult_di, &c->nseq_di, &c->seg_s, &c->seg_e, &c->pmark, &c->xc, &c->kc_dev, &c->uidx_stage, &c->out_stage, &c->ptab, &c->iota, &c->xw, &c->xg, &c->xflag, &c->bad_ids,
                    &c->g_wd, &c->mult_wd, &c->nseq_wd, &c->ca_ws, &c->ca_slab, &c->ca_scr, &c->ca2, &c->g_ux, &c->cnt_ux, &c->g_blt, &c->cnt_blt, &c->cand_s, &c->cand_i, &c->items_pk, &c->gbound, &c->st,
-                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws};
+                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws};
   (void)hipDeviceSynchronize();
   c->tm.clear();
   drop_graphs(c);
@@ -913,6 +915,89 @@ int poi_fpmc_step(poi_ctx* c, const poi_fpmc_params* P, const int32_t* u, const 
   A.slot = fp;
   HIPCHK(c, poi::launch_fpmc_step(A, c->num_cu, st, &c->tm));
   return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// PRME (prme.hip)
+static int prme_check(poi_ctx* c, const poi_prme_params* P, const char* who) {
+  if (!c || !P || !P->du || !P->dp || !P->ds) return fail(c, POI_EINVAL, "%s: NULL argument", who);
+  if (is_f16(c, P->du) || is_f16(c, P->dp) || is_f16(c, P->ds)) return fail(c, POI_ENOTSUP, "PRME tables are float32 only");
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 128) return fail(c, POI_ENOTSUP, "PRME: dim must be a multiple of 4 in [4, 128] (got %d)", P->dim);
+  if (P->n_user <= 0 || P->n_item <= 0) return fail(c, POI_EINVAL, "%s: bad sizes", who);
+  return POI_OK;
+}
+
+int poi_prme_step(poi_ctx* c, const poi_prme_params* P, const int32_t* u, const int32_t* p, const int32_t* q, const int32_t* prev,
+                  const double* d, const int32_t* gap, int32_t n, float alpha, float lambda, int32_t threshold, float cw, float* loss_out,
+                  void* stream) {
+  int rc = prme_check(c, P, "poi_prme_step");
+  if (rc) return rc;
+  if (!u || !p || !q || !prev || !d || !gap || !loss_out) return fail(c, POI_EINVAL, "poi_prme_step: NULL argument");
+  if (n < 0) return fail(c, POI_EINVAL, "poi_prme_step: bad sizes");
+  if ((int64_t)P->n_user + 2 * ((int64_t)P->n_item + 1) >= ((int64_t)1 << 31) - 1) return fail(c, POI_ENOTSUP, "PRME: n_user + 2 (n_item + 1) must stay below 2^31");
+  if ((int64_t)n * 7 >= ((int64_t)1 << 31) - 64) return fail(c, POI_ENOTSUP, "PRME: at most 2^31 / 7 transitions per launch");
+  if (c->batch_cap == 0.0f) return fail(c, POI_ENOTSUP, "the mini-batch rule (batch cap 0) applies to poi_gru_step / poi_spatial_step only");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::PrmeArgs A;
+  memset(&A, 0, sizeof A);
+  A.du = P->du; A.dp = P->dp; A.ds = P->ds; A.n_user = P->n_user; A.n_item = P->n_item; A.dim = P->dim;
+  A.u = u; A.p = p; A.q = q; A.prev = prev; A.d = d; A.gap = gap; A.n = n; A.thd = threshold;
+  A.alpha = alpha; A.lambda = lambda; A.bcap = c->batch_cap; A.cw = cw; A.loss = loss_out;
+  A.sentinel = P->n_user + 2 * (P->n_item + 1);
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  size_t ni = 0, nf = 0;
+  poi::prme_ws_sizes(n, P->dim, &ni, &nf);
+  if ((rc = ensure(c, c->pr_ws, sizeof(int) * ni + sizeof(float) * nf + 256, st))) return rc;
+  const size_t chunks = ((size_t)7 * n + 63) / 64 + 2, per = 7 * (size_t)n + 64, nt = ((size_t)n + 64 + 3) & ~(size_t)3;
+  int* ip = (int*)c->pr_ws.p;
+  A.keys0 = ip; A.keys1 = ip + per; A.vals0 = ip + 2 * per; A.vals1 = ip + 3 * per; ip += 4 * per;
+  A.hist = ip; ip += RS_HIST_INTS + RS_MAXBIN;
+  A.cnt = ip; ip += 64;
+  A.meta = (int4*)ip; ip += 4 * chunks;
+  float* fp = (float*)ip;
+  A.ga = fp; fp += nt;
+  A.gb = fp; fp += nt;
+  A.lead = fp; fp += chunks * (size_t)P->dim;
+  A.trail = fp; fp += chunks * (size_t)P->dim;
+  A.slot = fp;
+  HIPCHK(c, poi::launch_prme_step(A, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+static int prme_score_common(poi_ctx* c, const poi_prme_params* P, const double* coords, const int32_t* users, const int32_t* qpoi, int32_t n_rows,
+                             float cw, int32_t k, float* out, int32_t* idx_out, float* score_out, void* stream) {
+  const char* who = k > 0 ? "poi_prme_score_topk" : "poi_prme_score_all";
+  int rc = prme_check(c, P, who);
+  if (rc) return rc;
+  if (!coords || !users || !qpoi || (k > 0 ? !idx_out : !out)) return fail(c, POI_EINVAL, "%s: NULL argument", who);
+  if (n_rows < 0) return fail(c, POI_EINVAL, "%s: n_rows < 0", who);
+  if (k > 0 && (k > 64 || k > P->n_item)) return fail(c, POI_EINVAL, "%s: k must lie in [1, min(64, n_item)] (got %d)", who, k);
+  if (n_rows == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::PrmeScoreArgs A;
+  memset(&A, 0, sizeof A);
+  A.du = P->du; A.dp = P->dp; A.ds = P->ds; A.coords = coords; A.users = users; A.qpoi = qpoi;
+  A.n_rows = n_rows; A.n_user = P->n_user; A.n_item = P->n_item; A.dim = P->dim; A.k = k > 0 ? k : 0; A.cw = cw;
+  A.out = out; A.idx_out = idx_out; A.sc_out = score_out;
+  c->tm.begin(k > 0 ? "prme_score_topk" : "prme_score_all", st);
+  HIPCHK(c, poi::launch_prme_score(A, st));
+  c->tm.end(st);
+  return POI_OK;
+}
+
+int poi_prme_score_all(poi_ctx* c, const poi_prme_params* P, const double* coords, const int32_t* users, const int32_t* qpoi, int32_t n_rows,
+                       float cw, float* out, void* stream) {
+  return prme_score_common(c, P, coords, users, qpoi, n_rows, cw, 0, out, nullptr, nullptr, stream);
+}
+
+int poi_prme_score_topk(poi_ctx* c, const poi_prme_params* P, const double* coords, const int32_t* users, const int32_t* qpoi,
+                        int32_t n_rows, float cw, int32_t k, int32_t* idx_out, float* score_out, void* stream) {
+  if (k <= 0) return fail(c, POI_EINVAL, "poi_prme_score_topk: k must be positive (got %d)", k);
+  return prme_score_common(c, P, coords, users, qpoi, n_rows, cw, k, nullptr, idx_out, score_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

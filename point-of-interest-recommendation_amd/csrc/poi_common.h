@@ -211,6 +211,30 @@ __device__ __forceinline__ double cos_small(double x) {
 }
 
 
+// Top-K tie rule of the scoring kernels (score_topk.hip, prme.hip): higher score first, then the lower index.
+__device__ __forceinline__ bool better(float s, int i, float ps, int pi) {
+  return (s > ps) || (s == ps && i < pi);
+}
+
+// 64-lane bitonic sort, best (highest score, then lowest index) first.
+__device__ __forceinline__ void wave_sort_desc(float& s, int& idx) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const float ps = __shfl_xor(s, j, 64);
+      const int pi = __shfl_xor(idx, j, 64);
+      const bool up = ((lane & k) == 0);
+      const bool lower = ((lane & j) == 0);
+      const bool mine = better(s, idx, ps, pi);
+      const bool keep = (up == lower) ? mine : !mine;
+      if (!keep) { s = ps; idx = pi; }
+    }
+  }
+}
+
+
 // Counter-based RNG of the negative samplers (misc.hip sample_neg, fpmc.hip): one splitmix64 round.
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
   x += 0x9E3779B97F4A7C15ull;

@@ -373,6 +373,35 @@ struct FpmcArgs {
 hipError_t launch_fpmc_step(FpmcArgs& A, int num_cu, hipStream_t st, Timing* tm);
 void fpmc_ws_sizes(int n, int dim, size_t* n_int, size_t* n_float);
 
+// PRME (prme.hip)
+struct PrmeArgs {
+  float *du, *dp, *ds;              // (n_user, D), 2 x (n_item + 1, D)
+  int n_user, n_item, dim;
+  const int *u, *p, *q, *prev, *gap;
+  const double* d;
+  int n, thd;
+  float alpha, lambda, bcap, cw;
+  float* loss;
+  int* bad;                         // device counter of rejected transitions (poi_ctx_take_bad_ids)
+  int sentinel;                     // key of a lost occurrence / a rejected transition's touches: n_user + 2 (n_item + 1), sorts last
+  int *keys0, *keys1, *vals0, *vals1, *hist, *cnt;      // radix sort of the 7 n touches
+  const int *ks, *vs;
+  int4* meta;                       // per 64-touch window: {opening run's touches, it goes on, closing run's touches, its key}
+  float *ga, *gb, *lead, *trail, *slot;   // per transition 2 a g, 2 b g; per-window partial sums; (7 n, D) new rows at a run's first position
+};
+hipError_t launch_prme_step(PrmeArgs& A, int num_cu, hipStream_t st, Timing* tm);
+void prme_ws_sizes(int n, int dim, size_t* n_int, size_t* n_float);
+struct PrmeScoreArgs {
+  const float *du, *dp, *ds;        // (n_user, D), (>= n_item, D), (n_item + 1, D)
+  const double* coords;             // (n_item + 1, 2) lat, lon (row n_item: the pad POI)
+  const int *users, *qpoi;          // per output row: user, query POI in [0, n_item]
+  int n_rows, n_user, n_item, dim, k;      // k > 0: fused top-K
+  float cw;
+  float* out;                       // (n_rows, n_item) when k == 0
+  int* idx_out; float* sc_out;      // (n_rows, k) when k > 0 (sc_out may be NULL)
+};
+hipError_t launch_prme_score(PrmeScoreArgs& A, hipStream_t st);
+
 // scoring / top-K
 struct ScoreArgs {
   const float *users, *items; int items_f16;      // items: float32, or IEEE half when items_f16

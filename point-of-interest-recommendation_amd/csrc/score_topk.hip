@@ -23,27 +23,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define TK_CAP 80   // candidate slots per user per wave (>= K + 32; compaction when cnt > TK_CAP - 32).
                     // 4 waves x 32 users x 80 x 6 B = 61 KB per workgroup (+ 16 KB of A fragments: two workgroups per CU)
 
-__device__ __forceinline__ bool better(float s, int i, float ps, int pi) {
-  return (s > ps) || (s == ps && i < pi);
-}
-
-// 64-lane bitonic sort, best (highest score, then lowest index) first.
-__device__ __forceinline__ void wave_sort_desc(float& s, int& idx) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const float ps = __shfl_xor(s, j, 64);
-      const int pi = __shfl_xor(idx, j, 64);
-      const bool up = ((lane & k) == 0);
-      const bool lower = ((lane & j) == 0);
-      const bool mine = better(s, idx, ps, pi);
-      const bool keep = (up == lower) ? mine : !mine;
-      if (!keep) { s = ps; idx = pi; }
-    }
-  }
-}
+// better() / wave_sort_desc(): poi_common.h (shared with prme.hip)
 
 struct WaveTopk {   // LDS state of one wavefront
   float cs[32][TK_CAP];

@@ -444,3 +444,137 @@ def shard_users(n_user, world_size, rank, lens=None):
     for i in range(1, len(bounds)):
         bounds[i] = max(bounds[i], bounds[i - 1])
     return bounds[rank], bounds[rank + 1]
+
+
+# ---- PRME (public/Load_Data_prme.py) ----------------------------------------------------------------------------------------------
+PRME_R = 6378.137                    # Load_Data_prme.py:25
+
+
+def prme_cal_dis(lat1, lon1, lat2, lon2):
+    """public/Load_Data_prme.py:24-35, vectorised in the same float64 operation order (rad(x) = x * pi / 180, sin^2 of the halves)."""
+    rad = lambda x: np.multiply(np.asarray(x, np.float64), np.pi) / 180.0
+    rl1, rl2 = rad(lat1), rad(lat2)
+    a = rl1 - rl2
+    b = rad(lon1) - rad(lon2)
+    s = 2 * np.arcsin(np.sqrt(np.power(np.sin(a / 2), 2) + np.cos(rl1) * np.cos(rl2) * np.power(np.sin(b / 2), 2)))
+    return s * PRME_R
+
+
+@dataclasses.dataclass
+class PrmeDataset:
+    """The tables prog_prme.py's Params builds (load_data + fun_data_pois_masks + the two negative draws), train side CSR-packed."""
+    n_user: int
+    n_item: int
+    coords: np.ndarray          # (n_item + 1, 2) float64 lat, lon; row n_item = (0, 0) (`location`)
+    off: np.ndarray             # (n_user + 1,) int32 train offsets
+    tra_p: np.ndarray           # flat int32 train POIs
+    tra_d: np.ndarray           # flat float64 km from the previous check-in (0 at a sequence's first check-in)
+    tra_gap: np.ndarray         # flat int32 minutes since the previous check-in (0 at the first)
+    tes_p: np.ndarray           # (n_user, len_tes) int32, padded with n_item
+    tes_mask: np.ndarray        # (n_user, len_tes) int32
+    tra_q: np.ndarray = None    # flat int32 train negatives (fun_random_neg_masks_tra)
+    tes_q: np.ndarray = None    # (n_user, len_tes) test negatives (fun_random_neg_masks_tes), n_item on padding
+
+    @property
+    def lens(self):
+        return np.diff(np.asarray(self.off, np.int64))
+
+    def resample_negatives(self, rng):
+        """prog_prme.py:179-182: train negatives outside the user's train list, test negatives outside train and test lists."""
+        self.tra_q = random_neg_tra(rng, self.n_item, self.off, self.tra_p)
+        m = np.asarray(self.tes_mask).astype(bool)
+        tes_off = np.zeros(self.n_user + 1, np.int64)
+        np.cumsum(m.sum(axis=1), out=tes_off[1:])
+        flat = np.asarray(self.tes_p)[m]
+        q = np.full(self.tes_p.shape, self.n_item, np.int32)
+        q[m] = random_neg_tes(rng, self.n_item, self.off, self.tra_p, tes_off, flat)
+        self.tes_q = q
+
+    def last_pois(self):
+        return np.asarray(self.tra_p)[np.asarray(self.off, np.int64)[1:] - 1]
+
+
+def _prme_from_lists(seqs, times, cods, split, seed, where="input"):
+    """Shared body of load_prme_sequence_file / make_prme_synthetic: per-user lists of raw POI keys, float times (minutes) and (lat, lon)."""
+    s0, s1 = float(split[0]), float(split[1])
+    alias, coord_of = {}, {}
+    for upois, ucods in zip(seqs, cods):
+        for s_, c_ in zip(upois, ucods):
+            coord_of[s_] = c_                                             # :55-56, the last occurrence in the whole file
+    tra, tes, tra_d, tra_g = [], [], [], []
+    for upois, ut, ucods in zip(seqs, times, cods):
+        le = len(upois)
+        if not (len(ut) == len(ucods) == le):
+            raise ValueError("%s: a user with %d POIs, %d times and %d coordinates" % (where, le, len(ut), len(ucods)))
+        i1, i2 = int(le * s0), int(le * s1)                               # :66-68
+        t = np.asarray(ut, np.float64)
+        gap = np.zeros(le, np.float64)
+        gap[1:] = t[1:] - t[:-1]
+        if np.any(gap != np.round(gap)) or np.any(np.abs(gap) >= 2 ** 31):
+            raise ValueError("%s: check-in time gaps must be whole minutes (the reference's gap is a Theano iscalar)" % where)
+        c = np.asarray(ucods, np.float64).reshape(-1, 2)
+        dist = np.zeros(le, np.float64)
+        if le > 1:
+            dist[1:] = prme_cal_dis(c[1:, 0], c[1:, 1], c[:-1, 0], c[:-1, 1])      # :73-79
+        tra.append(upois[:i1]); tes.append(upois[i1:i2])
+        tra_d.append(dist[:i1]); tra_g.append(gap[:i1].astype(np.int32))
+    for utra, utes in zip(tra, tes):                                      # :102-105: numbering over the kept check-ins
+        for s_ in list(utra) + list(utes):
+            if s_ not in alias:
+                alias[s_] = len(alias)
+    dropped = [s_ for s_ in coord_of if s_ not in alias]
+    if dropped:                                                           # the reference: KeyError at cordi_new[aliases_dict[i]]
+        raise KeyError("%s: POI(s) %s occur only in the check-ins the split %s drops" % (where, dropped[:8], list(split)))
+    n_user, n_item = len(seqs), len(alias)
+    coords = np.zeros((n_item + 1, 2), np.float64)
+    for s_, a_ in alias.items():
+        coords[a_] = coord_of[s_]
+    lens = np.array([len(x) for x in tra], np.int64)
+    off = np.zeros(n_user + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    tl = np.array([len(x) for x in tes], np.int64)
+    lt = int(tl.max()) if n_user else 0
+    tes_p = np.full((n_user, lt), n_item, np.int32)
+    for k, x in enumerate(tes):
+        tes_p[k, :len(x)] = [alias[s_] for s_ in x]
+    tes_mask = (np.arange(lt)[None, :] < tl[:, None]).astype(np.int32)
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if len(xs) and off[-1] else np.zeros(0, dt)
+    ds = PrmeDataset(n_user=n_user, n_item=n_item, coords=coords, off=off.astype(np.int32),
+                     tra_p=cat([np.fromiter((alias[s_] for s_ in x), np.int32, count=len(x)) for x in tra], np.int32),
+                     tra_d=cat(tra_d, np.float64), tra_gap=cat(tra_g, np.int32), tes_p=tes_p, tes_mask=tes_mask)
+    ds.resample_negatives(np.random.default_rng(seed))
+    return ds, alias
+
+
+def load_prme_sequence_file(path, split=(0.8, 1.0), seed=0, return_aliases=False):
+    """The reference's PRME loading (public/Load_Data_prme.py:38-120 load_data, fun_data_pois_masks, fun_random_neg_masks_tra / _tes as
+    prog_prme.py:67-77 calls them) on the ETL's sequence file, into a PrmeDataset:
+      * fractional split: train = pois[0:int(le*s0)], test = pois[int(le*s0):int(le*s1)] (test mode (0.8, 1.0), valid mode (0.6, 0.8));
+      * gap[j] = t[j] - t[j-1] in minutes (must be whole: the reference's Theano iscalar) and dist[j] = cal_dis(c[j], c[j-1]) from the
+        per-check-in coordinates, both 0 at j = 0;
+      * n_item counts the distinct POIs of the kept check-ins; a POI seen only in the dropped tail raises KeyError, as the reference does;
+      * a POI's coordinate is the one of its last occurrence in the whole file; coords gets a pad row n_item = (0, 0).
+    Aliases: order of first appearance among the kept check-ins (train lists, then test lists, user by user) instead of the reference's
+    set() iteration order - a relabelling of the same data.  Negatives are drawn from `seed` with the rules of poi_sample_negatives."""
+    import pandas as pd
+    tab = pd.read_csv(path, sep=" ")
+    seqs = [str(s).split("/") for s in tab["u_pois"]]
+    times = [[float(v) for v in str(s).split("/")] for s in tab["u_times"]]
+    cods = [[tuple(float(v) for v in c.split(",")) for c in str(s).split("/")] for s in tab["u_coordinates"]]
+    ds, alias = _prme_from_lists(seqs, times, cods, split, seed, where=str(path))
+    return (ds, alias) if return_aliases else ds
+
+
+def make_prme_synthetic(n_user, n_item, max_len, seed, far_frac=0.3, threshold=360, split=(0.8, 1.0), **kw):
+    """make_synthetic's check-ins (lengths, popularity, optional locality `local=`) with check-in times whose gaps exceed `threshold`
+    minutes with probability far_frac (else uniform in [1, threshold]), split and numbered as load_prme_sequence_file does."""
+    base = make_synthetic(n_user, n_item, max_len, seed, **kw)
+    rng = np.random.default_rng(seed + 1)
+    off = np.asarray(base.off, np.int64)
+    seqs, times, cods = [], [], []
+    for u in range(n_user):
+        s = np.concatenate([base.tra_p[off[u]:off[u + 1]], base.tes_p[u:u + 1]])
+        g = np.where(rng.random(len(s)) < far_frac, rng.integers(threshold + 1, 10 * threshold, len(s)), rng.integers(1, threshold + 1, len(s)))
+        g[0] = 0
+        seqs.append(s.tolist()); times.append(np.cumsum(g).astype(np.float64).tolist()); cods.append([tuple(base.coords[i]) for i in s])
+    return _prme_from_lists(seqs, times, cods, split, seed, where="make_prme_synthetic")[0]

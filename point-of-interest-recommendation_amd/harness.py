@@ -271,3 +271,54 @@ def train_fpmc_lr(ds, p=None, device="cuda:0", log=print):
         log("epoch %d  sum_loss = %.3f = %.3f - %.3f  auc %.4f  recall@%d %.4f  time (train, test) %.2fs %.2fs"
             % (epoch, loss + l2, loss, l2, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1))
     return model, best, history
+
+
+def prme_default_params():
+    """The in-source config of prog_prme.py:44-63 (+ `batch`: transitions per launch - 1 is the reference's one-by-one training -, seed)."""
+    return dict(mode="test", split=[0.8, 1.0], at_nums=[5, 10, 15, 20], epochs=100, threshold=360, component_weight=0.2, latent_size=20,
+                alpha=0.01, **{"lambda": 0.001}, mini_batch=0, prme=0, batch_size_train=1, batch_size_test=20, batch=1, seed=123)
+
+
+def train_prme(ds, p=None, device="cuda:0", log=print):
+    """train_valid_or_test of prog_prme.py:151-232 on a data.PrmeDataset: OboPrme (OboPRPRM with p['prme'] = 1), then per epoch: new
+    negatives on the device (epoch > 0), users shuffled, every transition (u, [tra[i], neg[i], tra[i-1]], dist[i], gap[i]) trained in launches
+    of p['batch'], the sum_loss line (sum of log sigmoid + l2), update_trained_items, AUC (always 0, as the reference) and top-K metrics into
+    GlobalBest.  Returns (model, best, history)."""
+    p = dict(prme_default_params(), **(p or {}))
+    cls = models.OboPRPRM if p.get("prme", 0) else models.OboPrme
+    model = cls(train=ds, test=None, alpha_lambda=[p["alpha"], p["lambda"]], threshold=p["threshold"], component_weight=p["component_weight"],
+                cordi=ds.coords, n_user=ds.n_user, n_item=ds.n_item, n_size=p["latent_size"], device=device, seed=p.get("seed"))
+    best = GlobalBest(p["at_nums"])
+    U = ds.n_user
+    ses_tes = compute_start_end(U, p["batch_size_test"])
+    ses_auc = compute_start_end(U, p["batch_size_test"] * 10)
+    tes_p, tes_m = np.asarray(ds.tes_p), np.asarray(ds.tes_mask)
+    B = max(1, int(p.get("batch", 1)))
+    history = []
+    for epoch in range(p["epochs"]):
+        if epoch > 0:                                               # :179-182
+            model.resample_negatives_device(p.get("seed", 0) * 1000003 + epoch)
+        t0 = time.time()
+        order = np.random.default_rng(123 + epoch).permutation(U)   # :188-190
+        u, pp, q, pv, d, g = model.epoch_transitions(None, order)
+        n = u.numel()
+        loss = 0.0
+        if B == 1:                                                  # :191-197, one transition per call
+            hu, hp, hq, hv, hd, hg = (t.cpu().numpy() for t in (u, pp, q, pv, d, g))
+            for t in range(n):
+                loss += model.train(int(hu[t]), [int(hp[t]), int(hq[t]), int(hv[t])], float(hd[t]), int(hg[t]))
+        else:
+            parts = [model.train_batch(u[s:s + B], pp[s:s + B], q[s:s + B], pv[s:s + B], d[s:s + B], g[s:s + B], sync=False) for s in range(0, n, B)]
+            if model.ctx.take_bad_ids(model._stream().value):
+                raise IndexError("rejected transitions in epoch %d" % epoch)
+            loss = float(torch.cat(parts).double().sum().item()) if parts else 0.0
+        l2 = model.l2.eval()                                        # :199
+        t1 = time.time()
+        model.update_trained_items()                                # :208
+        m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m)      # :213-214
+        t2 = time.time()
+        history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall={k: m["at"][k]["recall"] for k in p["at_nums"]},
+                            transitions=n, times=(t1 - t0, t2 - t1)))
+        log("epoch %d  sum_loss = %.3f = %.3f + %.3f  auc %.4f  recall@%d %.4f  time (train, test) %.2fs %.2fs"
+            % (epoch, loss + l2, loss, l2, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1))
+    return model, best, history

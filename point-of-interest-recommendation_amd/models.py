@@ -1121,3 +1121,209 @@ class OboFpmc_lr(_Base):
         self.ctx.check(self.lib.poi_auc_preference(self.ctx.handle, _ptr(users), _ptr(self._items()), n, self.kdim, _ptr(tp), _ptr(tq), _ptr(tm),
                                                    ln, _ptr(out), self._stream()))
         return out.cpu().numpy().astype(bool)
+
+
+# =================================================================================================
+class OboPrme(_Base):
+    """public/PRME.py:38-219 (driver prog_prme.py): PRME, a pairwise metric embedding with a geographical weight.  Three tables du
+    (n_user, D), dp / ds (n_item + 1, D); a transition (u, [p, q, prev], d, gap) moves up to seven rows (poi_prme_step).  Scoring reads the
+    `trained_*` snapshots taken by update_trained_items and ranks all POIs by a weighted squared Euclidean distance (poi_prme_score_all /
+    poi_prme_score_topk).
+
+    train: the reference's [tra_pois_masks, tra_all_times, tra_all_dists, tra_masks, tra_pois_neg_masks] or a data.PrmeDataset (then test is
+    None).  test: [tes_pois_masks, tes_all_times, tes_all_dists, tes_masks, tes_pois_neg_masks] (times / dists are not read).  cordi:
+    (n_item + 1, 2) lat, lon with the pad row (`location` of load_data).  n_size = D, a multiple of 4 in [4, 128].  Extra keywords:
+    device, init (dict of float64 arrays du / dp / ds), seed."""
+
+    TABLES = ("du", "dp", "ds")
+
+    def __init__(self, train, test, alpha_lambda, threshold, component_weight, cordi, n_user, n_item, n_size, device="cuda:0", init=None,
+                 seed=None):
+        self.n_user, self.n_item, self.dim = int(n_user), int(n_item), int(n_size)
+        if self.dim <= 0 or self.dim % 4 or self.dim > 128:
+            raise ValueError("%s: n_size must be a multiple of 4 in [4, 128] (got %d)" % (type(self).__name__, self.dim))
+        self.thd, self.cw = int(threshold), float(np.float32(component_weight))
+        off, p, dist, gap, q, tes = self._host_tables(train, test)
+        lens = np.diff(off.astype(np.int64))
+        if len(lens) != self.n_user:
+            raise ValueError("%s: %d train sequences for n_user = %d" % (type(self).__name__, len(lens), self.n_user))
+        if np.any(lens <= 0):           # the scoring's query POI is the last train POI
+            raise ValueError("%s: user(s) %s have an empty train sequence (no last POI)" % (type(self).__name__, np.nonzero(lens <= 0)[0][:8].tolist()))
+        for nm, t in (("train POIs", p), ("train negatives", q), ("test POIs", tes[0]), ("test negatives", tes[2])):
+            self._check_ids(nm, t, self.n_item)
+        if p.max() >= self.n_item:
+            raise IndexError("train POIs must lie in [0, %d)" % self.n_item)
+        if not np.all(np.isfinite(dist)) or np.any(dist < 0):
+            raise ValueError("train distances must be finite and >= 0")
+        xy = np.ascontiguousarray(cordi, np.float64)
+        if xy.shape != (self.n_item + 1, 2):
+            raise ValueError("cordi must be (n_item + 1, 2) lat, lon with the pad row (got %s)" % (xy.shape,))
+        self._setup(device, alpha_lambda)
+        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+        self._off_host, self._lens = off, lens
+        self.off, self.p, self.q, self.gap = i32(off), i32(p), i32(q), i32(gap)
+        self.dist = torch.as_tensor(np.ascontiguousarray(dist, np.float64)).to(self.device)
+        self.tes_buys_masks, self.tes_masks, self.tes_buys_neg_masks = i32(tes[0]), i32(tes[1]), i32(tes[2])
+        self._arange = torch.arange(self.n_user, dtype=torch.int32, device=self.device)
+        self.tra_last_poi = i32(p[off[1:].astype(np.int64) - 1])
+        self.cordi = torch.as_tensor(xy).to(self.device)
+        rng = np.random.default_rng(seed) if seed is not None else np.random
+        init = init or {}
+        shapes = dict(ds=(self.n_item + 1, self.dim), dp=(self.n_item + 1, self.dim), du=(self.n_user, self.dim))
+        for k in ("ds", "dp", "du"):                                                          # PRME.py:75-78
+            v = init[k] if k in init else rng.uniform(-0.5, 0.5, shapes[k])
+            t = self._dev(v)
+            if tuple(t.shape) != shapes[k]:
+                raise ValueError("init[%r] has shape %s, expected %s" % (k, tuple(t.shape), shapes[k]))
+            setattr(self, k, Shared(t))
+        # trained_* (PRME.py:85-91): scoring reads these snapshots; update_trained_items refreshes them
+        self._trained = {k: getattr(self, k).t.clone() for k in self.TABLES}
+        self.params = [self.dp, self.ds, self.du]                                             # :163
+        self.l2 = _L2(self, ["dp", "ds", "du"])                                               # :165-168
+
+    def _host_tables(self, train, test):
+        from .data import PrmeDataset
+        if isinstance(train, PrmeDataset):
+            ds = train
+            q = ds.tra_q if ds.tra_q is not None else np.zeros_like(ds.tra_p)
+            tq = ds.tes_q if ds.tes_q is not None else np.full(ds.tes_p.shape, self.n_item, np.int32)
+            return (np.asarray(ds.off, np.int32), np.asarray(ds.tra_p, np.int32), np.asarray(ds.tra_d, np.float64), np.asarray(ds.tra_gap, np.int64),
+                    np.asarray(q, np.int32), (np.asarray(ds.tes_p), np.asarray(ds.tes_mask), np.asarray(tq)))
+        tra_pois, tra_times, tra_dists, tra_masks, tra_neg = (np.asarray(x) for x in train)
+        lens = np.asarray(tra_masks, np.int64).sum(axis=1)
+        m = np.arange(tra_pois.shape[1])[None, :] < lens[:, None]
+        off = np.zeros(len(lens) + 1, np.int64)
+        np.cumsum(lens, out=off[1:])
+        gap = np.asarray(tra_times, np.float64)[m]
+        if np.any(gap != np.round(gap)):
+            raise ValueError("check-in time gaps must be whole minutes (the reference's gap is a Theano iscalar)")
+        te = [np.asarray(test[0]), np.asarray(test[3]), np.asarray(test[4])]
+        return (off.astype(np.int32), tra_pois[m].astype(np.int32), np.asarray(tra_dists, np.float64)[m], gap.astype(np.int64),
+                tra_neg[m].astype(np.int32), tuple(te))
+
+    # ---- negatives ----------------------------------------------------------------------------
+    def update_neg_masks(self, tra_pois_neg_masks, tes_pois_neg_masks):
+        """PRME.py:93-96: new negatives every epoch (padded tables as the reference builds them)."""
+        tn = np.asarray(tra_pois_neg_masks)
+        m = np.arange(tn.shape[1])[None, :] < self._lens[:, None]
+        self._check_ids("train negatives", tn[m], self.n_item)
+        self._check_ids("test negatives", tes_pois_neg_masks, self.n_item)
+        self.q = self._dev(tn[m], torch.int32)
+        self.tes_buys_neg_masks = self._dev(tes_pois_neg_masks, torch.int32)
+
+    def resample_negatives_device(self, seed):
+        """fun_random_neg_masks_tra / _tes (Load_Data_prme.py:123-162, prog_prme.py:179-182) on the device: poi_sample_negatives."""
+        q = torch.empty_like(self.p)
+        tq = torch.empty_like(self.tes_buys_masks)
+        self.ctx.check(self.lib.poi_sample_negatives(self.ctx.handle, _ptr(self.off), _ptr(self.p), self.n_user, self.n_item,
+                                                     _ptr(self.tes_buys_masks), _ptr(self.tes_masks), self.tes_masks.shape[1],
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(q), _ptr(tq), self._stream()))
+        self.q, self.tes_buys_neg_masks = q, tq
+
+    def epoch_transitions(self, seed=None, order=None):
+        """All transitions of an epoch in the driver's order (prog_prme.py:189-197: users in `order` - default 0..n_user-1 -, positions
+        i = 1 .. len-1): device tensors (u, p, q, prev, d, gap) with p = tra[i], q = neg[i], prev = tra[i-1], d = dist[i], gap = gap[i].
+        With a seed the negatives are redrawn on the device first (resample_negatives_device)."""
+        if seed is not None:
+            self.resample_negatives_device(seed)
+        off = self._off_host.astype(np.int64)
+        users = np.arange(self.n_user) if order is None else np.asarray(order, np.int64)
+        lens = self._lens[users] - 1
+        starts = np.repeat(off[users] + 1 - np.concatenate(([0], np.cumsum(lens)[:-1])), lens)
+        pos = torch.as_tensor(starts + np.arange(int(lens.sum()))).to(self.device)
+        u = torch.as_tensor(np.repeat(users, lens).astype(np.int32)).to(self.device)
+        return (u, self.p.index_select(0, pos), self.q.index_select(0, pos), self.p.index_select(0, pos - 1), self.dist.index_select(0, pos),
+                self.gap.index_select(0, pos))
+
+    # ---- training -----------------------------------------------------------------------------
+    def _pparams(self, tabs):
+        return _lib.PrmeParams(*[ctypes.c_void_p(tabs[k].data_ptr()) for k in ("du", "dp", "ds")], self.n_user, self.n_item, self.dim)
+
+    def train(self, u_idx, pq_idx, ad_idx, t_idx):
+        """OboPrme.train(u_idx, [p, q, prev], dist, gap) (PRME.py:216-219) -> log sigmoid(Dq - Dp)."""
+        pq = list(np.asarray(pq_idx).reshape(-1))
+        if len(pq) != 3:
+            raise ValueError("pq_idx must be [p, q, prev] (got %d ids)" % len(pq))
+        return float(self.train_batch([u_idx], [pq[0]], [pq[1]], [pq[2]], [ad_idx], [t_idx])[0])
+
+    def train_batch(self, u, p, q, prev, d, gap, sync=True):
+        """A launch of n transitions (poi_prme_step, batch semantics of include/poi_hip.h) -> log sigmoid(x) per transition.  With sync, a
+        launch that held a rejected transition (an id outside its table, p == q, d not finite or < 0) raises IndexError - those moved
+        nothing."""
+        conv = lambda v, dt, npdt: v.to(self.device, dt).contiguous() if isinstance(v, torch.Tensor) else \
+            torch.as_tensor(np.asarray(v, npdt)).to(dt).to(self.device)
+        u, p, q, prev, gap = (conv(v, torch.int32, np.int64) for v in (u, p, q, prev, gap))
+        d = conv(d, torch.float64, np.float64)
+        n = u.numel()
+        if not (p.numel() == q.numel() == prev.numel() == d.numel() == gap.numel() == n):
+            raise ValueError("u, p, q, prev, d, gap must have the same length")
+        loss = torch.empty(n, dtype=torch.float32, device=self.device)
+        P = self._pparams({k: getattr(self, k).t for k in self.TABLES})
+        self.ctx.check(self.lib.poi_prme_step(self.ctx.handle, ctypes.byref(P), _ptr(u), _ptr(p), _ptr(q), _ptr(prev), _ptr(d), _ptr(gap), n,
+                                              self.alpha_lambda[0], self.alpha_lambda[1], self.thd, self.cw, _ptr(loss), self._stream()))
+        if sync:
+            nb = self.ctx.take_bad_ids(self._stream().value)
+            if nb:
+                raise IndexError("%d rejected transition(s) in this launch (an id outside its table, p == q, or a bad distance): they moved "
+                                 "nothing, their losses are NaN" % nb)
+        return loss.cpu().numpy() if sync else loss
+
+    def update_trained_items(self):
+        """PRME.py:98-106: the scoring snapshots trained_du / trained_dp / trained_ds <- the live tables."""
+        for k in self.TABLES:
+            self._trained[k].copy_(getattr(self, k).t)
+
+    # ---- evaluation ---------------------------------------------------------------------------
+    def score_rows_device(self, users, qpoi, k=None):
+        """Arbitrary (user, query POI) rows against all POIs: (n_rows, n_item) scores, or with k the fused top-K (ids, scores)."""
+        users = users.to(self.device, torch.int32).contiguous()
+        qpoi = qpoi.to(self.device, torch.int32).contiguous()
+        n = users.numel()
+        P = self._pparams(self._trained)
+        if k is None:
+            out = torch.empty((n, self.n_item), dtype=torch.float32, device=self.device)
+            self.ctx.check(self.lib.poi_prme_score_all(self.ctx.handle, ctypes.byref(P), _ptr(self.cordi), _ptr(users), _ptr(qpoi), n, self.cw,
+                                                       _ptr(out), self._stream()))
+            return out
+        if not 0 < int(k) <= min(64, self.n_item):
+            raise ValueError("k must lie in [1, min(64, n_item)] (got %d)" % int(k))
+        idx = torch.empty((n, int(k)), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, int(k)), dtype=torch.float32, device=self.device)
+        self.ctx.check(self.lib.poi_prme_score_topk(self.ctx.handle, ctypes.byref(P), _ptr(self.cordi), _ptr(users), _ptr(qpoi), n, self.cw, int(k),
+                                                    _ptr(idx), _ptr(sc), self._stream()))
+        return idx, sc
+
+    def _query_rows(self, start_end):
+        """The reference's rows of one batch (PRME.py:118-120): per user, the last train POI, then the test POIs 0 .. Lb-2 (pad POI beyond
+        the user's list), Lb = the batch's longest test list -> (users, qpoi, Lb) device tensors, user-major."""
+        ids, lo = self._ids(start_end)
+        tm = self._rows(self.tes_masks, ids, lo)
+        lb = max(1, int(tm.sum(1).max().item())) if ids.numel() else 1
+        tp = self._rows(self.tes_buys_masks, ids, lo)[:, :lb - 1]
+        q = torch.cat([self._rows(self.tra_last_poi, ids, lo).view(-1, 1), tp], 1)
+        return ids.repeat_interleave(lb), q.reshape(-1).contiguous(), lb
+
+    def compute_sub_all_scores_device(self, start_end):
+        """PRME.py:117-139 -> (n * Lb, n_item) device tensor, user-major."""
+        users, qpoi, _ = self._query_rows(start_end)
+        return self.score_rows_device(users, qpoi)
+
+    def compute_sub_all_scores(self, start_end):
+        return self.compute_sub_all_scores_device(start_end).cpu().numpy()
+
+    def compute_sub_topk(self, start_end, k, return_scores=False):
+        """Per-user ranking for the metrics: row 0 (query = the last train POI) of each user through the fused top-K -> (n, k) int32 ids.
+        (The reference's evaluator zips its n * Lb rows with the n users' test lists; here every user is ranked from its row 0 - see
+        INTEGRATION.md.)"""
+        ids, lo = self._ids(start_end)
+        idx, sc = self.score_rows_device(ids, self._rows(self.tra_last_poi, ids, lo), k)
+        return (idx, sc) if return_scores else idx
+
+    def compute_sub_auc_preference(self, start_end):
+        """PRME.py:141-159 returns zeros (the AUC code is commented out there): AUC is always 0."""
+        ids, _ = self._ids(start_end)
+        return np.zeros((ids.numel(), self.tes_masks.shape[1]), bool)
+
+
+class OboPRPRM(OboPrme):
+    """public/PRPRM.py: the same model as OboPrme under another class name (prog_prme.py's 'prme' flag 1)."""
