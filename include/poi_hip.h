@@ -49,7 +49,8 @@ extern "C" {
  * forward pass covers dim 256 (config X); option "hot_bins". */
 /* 7: FPMC-LR - new entry points poi_fpmc_neighbor_counts / _fill, poi_fpmc_sample_negatives, poi_fpmc_step (existing entries unchanged). */
 /* 8: PRME - new entry points poi_prme_step, poi_prme_score_all, poi_prme_score_topk and poi_prme_params (existing entries unchanged). */
-#define POI_ABI_VERSION 8
+/* 9: new entry point poi_ctx_last_plan (existing entries unchanged). */
+#define POI_ABI_VERSION 9
 
 enum {
   POI_OK = 0,
@@ -120,6 +121,14 @@ int64_t poi_ctx_graph_replays(const poi_ctx* ctx);
  * mirror raises IndexError from OboBpr.train / train_batch(sync=True), as the reference does.  ABI 7: poi_fpmc_step counts its rejected
  * transitions (an id outside its table, or i == j) in the same counter, one per transition.  ABI 8: so does poi_prme_step. */
 int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
+/* ABI 9.  The plan the last poi_spatial_step / poi_gru_step on this context took, one named value at a time:
+ * "tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", "fwd_tab", "xft", "xcomp", "head_split", "efuse",
+ * "early_bins", "fork", and "hyb_fwd_seq" / "hyb_fwd_wg" / "hyb_bwd_seq" / "hyb_bwd_wg" (TeArgs.hyb_dev; synchronises the
+ * launch stream; -1 when hyb == 0).  POI_EINVAL for an unknown key, or before any training launch.  The flags are host fields set
+ * where the launch decides them (a graph replay records the plan of the launch it replays); "tile" == 0: the per-sequence or the exact
+ * engine ran and every other flag is 0.  The hyb_* values live in the tile engine's workspace: POI_EINVAL once a later tile-engine
+ * launch (poi_gru_predict included) may have reused it. */
+int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
  * poi_gru_predict; `items` of poi_score_all / poi_score_topk* / poi_auc_preference; `x` of poi_sumsq) reads / writes it as half.

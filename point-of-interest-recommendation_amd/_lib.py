@@ -6,7 +6,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libpoi_hip.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 BPR_SNAPSHOT, BPR_HOGWILD = 0, 1
 
@@ -58,6 +58,7 @@ SIGNATURES = {
     "poi_ctx_set_topk_filter": (c_int, [c_void_p, c_int]),
     "poi_ctx_topk_filter_stats": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "poi_ctx_graph_replays": (c_int64, [c_void_p]),
+    "poi_ctx_last_plan": (c_int, [c_void_p, c_char_p, POINTER(c_int64)]),
     "poi_ctx_take_bad_ids": (c_int64, [c_void_p, c_void_p]),
     "poi_ctx_register_f16": (c_int, [c_void_p, c_void_p, c_int64]),
     "poi_ctx_unregister_f16": (c_int, [c_void_p, c_void_p]),
@@ -163,6 +164,11 @@ def load():
     return lib
 
 
+# keys of poi_ctx_last_plan (include/poi_hip.h)
+PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", "fwd_tab", "xft", "xcomp", "head_split", "efuse", "early_bins",
+             "fork", "hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg")
+
+
 class Context:
     """Owns one poi_ctx (device scratch + error text) bound to a HIP device."""
 
@@ -216,6 +222,15 @@ class Context:
 
     def graph_replays(self):
         return int(self.lib.poi_ctx_graph_replays(self.handle))
+
+    def last_plan(self, key=None):
+        """The plan the last poi_spatial_step / poi_gru_step on this context took (poi_ctx_last_plan): the value of `key` (one of
+        PLAN_KEYS), or a dict of every key when key is None.  The hyb_* keys synchronise the launch stream."""
+        if key is None:
+            return {k: self.last_plan(k) for k in PLAN_KEYS}
+        v = c_int64(0)
+        self.check(self.lib.poi_ctx_last_plan(self.handle, key.encode(), ctypes.byref(v)))
+        return int(v.value)
 
     def set_batch_cap(self, cap):
         """Batch rule cap (include/poi_hip.h, poi_ctx_set_batch_cap): 1 = mean rule, 0 = the mini-batch rule of public/GRU.py:395-498."""

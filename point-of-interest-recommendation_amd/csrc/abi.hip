@@ -70,7 +70,7 @@ struct poi_ctx {
   // hipGraph replay of the tile engine's training launch (poi_ctx_set_graph): ~40 kernels on two streams become one graph launch.
   // A launch is captured the second time its key (every pointer / size / scalar the kernels receive) is seen; the caller's uidx /
   // out are staged through context buffers so that the key does not depend on them.
-  struct StepGraph { std::vector<uint64_t> key; hipGraph_t graph; hipGraphExec_t exec; uint64_t stamp; };
+  struct StepGraph { std::vector<uint64_t> key; hipGraph_t graph; hipGraphExec_t exec; uint64_t stamp; int fork; };      // fork: the plan record of a replay
   std::vector<StepGraph> graphs;
   std::vector<uint64_t> seen_key;
   int graph_mode = 0;       // off by default (no gain measured on ROCm 7.0: DESIGN.md section 5); POI_GRAPH=1 / poi_ctx_set_graph enable
@@ -78,6 +78,10 @@ struct poi_ctx {
   uint64_t graph_stamp = 0, graph_replays = 0, graph_captures = 0;
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
+  // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  LastPlan plan = {};
+  uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR
   DevBuf g_ux, cnt_ux, g_blt, cnt_blt;
   // FPMC-LR step: sort buffers, per-transition sigmoid, window partial sums, new-row slots
@@ -260,6 +264,7 @@ static void fill_args(poi::SeqArgs& A, const poi_gru_params* P, const poi_seq_ta
 static int te_setup(poi_ctx* c, poi::TeArgs& A, const poi_gru_params* P, const poi_seq_tables* T, const int32_t* uidx, int n,
                     bool predict, bool spatial, hipStream_t st) {
   memset(&A, 0, sizeof A);
+  ++c->te_ws_gen;
   const int n_dist = spatial ? P->n_dist : -1;            // the plain GRU has no distance-bin table: zero rows
   const int D = P->dim, NBP = poi::te_nbp(n_dist);
   A.lt = P->lt; A.di = P->di; A.ui = P->ui; A.wh = P->wh; A.bi = P->bi; A.vs = P->vs; A.bs = P->bs; A.wd = P->wd; A.lw = P->lw;
@@ -465,6 +470,7 @@ static int seq_step(poi_ctx* c, const poi_gru_params* P, const poi_seq_tables* T
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(c, hipSetDevice(c->device));
   c->tm.tick();
+  c->plan = poi_ctx::LastPlan{}; c->plan.valid = 1;      // (the per-sequence / exact engines: every flag 0)
   if (c->engine == 4) return exact_step(c, P, T, uidx, n, alpha, lambda, out, st, spatial);
   const int D = P->dim, XW = spatial ? 2 * D : D, NB = spatial ? P->n_dist + 1 : 0;
   int grid = c->num_cu * c->wg_per_cu;
@@ -529,6 +535,12 @@ static int seq_step(poi_ctx* c, const poi_gru_params* P, const poi_seq_tables* T
     A.kc_dev = E.kc_dev;                 // (dense_apply reads te_wgrad's K-chunk counts from the device)
     // one sequence (the reference schedule): the whole step in five kernels (tile_engine.hip, te_one_*)
     const bool one = n == 1 && c->one_path && E.rec1 && !E.lt_f16 && poi::te_one_supported(D, spatial, T->max_len);
+    {
+      poi_ctx::LastPlan& R = c->plan;
+      R.tile = 1; R.one = one; R.rec1 = E.rec1; R.xrec1 = E.xrec1; R.hyb = E.hyb; R.bintab = E.bintab; R.ppoi = E.ppoi; R.listed = E.urow != nullptr;
+      R.fwd_tab = E.fwd_tab; R.xft = E.xft; R.xcomp = E.xcomp; R.head_split = E.head_split; R.efuse = one ? 0 : E.efuse; R.early_bins = E.early_bins;
+      R.hyb_dev = E.hyb_dev; R.st = st; R.ws_gen = c->te_ws_gen;      // (fork: launch_te_scatter)
+    }
     // captured: a replay re-issues the launch id this launch got when it was captured - atomicMax against whatever a LATER launch left in xflag
     // would keep the newer id and lose this replay's NaN flag.  The captured sequence therefore starts by clearing the flag: only
     // its own pack kernels can raise it to its own id (they run behind ev_start, i.e. behind this node).
@@ -545,7 +557,7 @@ static int seq_step(poi_ctx* c, const poi_gru_params* P, const poi_seq_tables* T
         e = poi::launch_dense_apply(A, spatial, n_slab, n_slab, alpha, lambda, E.side, &c->tm);
         if (e == hipSuccess) e = hipEventRecord(E.ev_slots, E.side);
       }
-      if (e == hipSuccess) e = poi::launch_te_scatter(E, alpha, lambda, c->num_cu, s, &c->tm);
+      if (e == hipSuccess) e = poi::launch_te_scatter(E, alpha, lambda, c->num_cu, s, &c->tm, &c->plan.fork);
       if (e == hipSuccess && !dense_side) e = poi::launch_dense_apply(A, spatial, n_slab, n_slab, alpha, lambda, s, &c->tm);
       return e;
     };
@@ -610,11 +622,12 @@ static int seq_step(poi_ctx* c, const poi_gru_params* P, const poi_seq_tables* T
         (void)hipGraphExecDestroy(c->graphs[lru].exec); (void)hipGraphDestroy(c->graphs[lru].graph);
         c->graphs.erase(c->graphs.begin() + lru);
       }
-      c->graphs.push_back(poi_ctx::StepGraph{key, graph, exec, 0});
+      c->graphs.push_back(poi_ctx::StepGraph{key, graph, exec, 0, c->plan.fork});
       g = &c->graphs.back();
       ++c->graph_captures;
     }
     g->stamp = ++c->graph_stamp;
+    c->plan.fork = g->fork;
     HIPCHK(c, hipGraphLaunch(g->exec, st));
     ++c->graph_replays;
     HIPCHK(c, hipMemcpyAsync(out, c->out_stage.p, out_bytes, hipMemcpyDeviceToDevice, st));
@@ -1394,6 +1407,33 @@ int poi_ctx_set_graph(poi_ctx* c, int on, int min_n, int max_n) {
 }
 
 int64_t poi_ctx_graph_replays(const poi_ctx* c) { return c ? (int64_t)c->graph_replays : POI_EINVAL; }
+
+int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
+  if (!c || !key || !value) return fail(c, POI_EINVAL, "poi_ctx_last_plan: NULL argument");
+  const poi_ctx::LastPlan& R = c->plan;
+  if (!R.valid) return fail(c, POI_EINVAL, "poi_ctx_last_plan: no training launch on this context yet");
+  static const struct { const char* name; int poi_ctx::LastPlan::*f; } flags[] = {
+      {"tile", &poi_ctx::LastPlan::tile}, {"one", &poi_ctx::LastPlan::one}, {"rec1", &poi_ctx::LastPlan::rec1}, {"xrec1", &poi_ctx::LastPlan::xrec1},
+      {"hyb", &poi_ctx::LastPlan::hyb}, {"bintab", &poi_ctx::LastPlan::bintab}, {"ppoi", &poi_ctx::LastPlan::ppoi}, {"listed", &poi_ctx::LastPlan::listed},
+      {"fwd_tab", &poi_ctx::LastPlan::fwd_tab}, {"xft", &poi_ctx::LastPlan::xft}, {"xcomp", &poi_ctx::LastPlan::xcomp},
+      {"head_split", &poi_ctx::LastPlan::head_split}, {"efuse", &poi_ctx::LastPlan::efuse}, {"early_bins", &poi_ctx::LastPlan::early_bins},
+      {"fork", &poi_ctx::LastPlan::fork}};
+  for (const auto& e : flags)
+    if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
+  static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev
+  for (int i = 0; i < 4; ++i) {
+    if (strcmp(key, hyb_keys[i])) continue;
+    if (!R.hyb) { *value = -1; return POI_OK; }
+    if (R.ws_gen != c->te_ws_gen) return fail(c, POI_EINVAL, "poi_ctx_last_plan(\"%s\"): a later tile-engine launch may have reused the workspace", key);
+    int v[4];
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(R.st));
+    HIPCHK(c, hipMemcpy(v, R.hyb_dev, sizeof v, hipMemcpyDeviceToHost));
+    *value = v[i];
+    return POI_OK;
+  }
+  return fail(c, POI_EINVAL, "poi_ctx_last_plan: unknown key \"%s\"", key);
+}
 int64_t poi_ctx_take_bad_ids(poi_ctx* c, void* stream) {
   if (!c) return POI_EINVAL;
   if (!c->bad_ids.p) return 0;

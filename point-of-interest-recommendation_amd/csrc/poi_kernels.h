@@ -241,7 +241,7 @@ hipError_t launch_te_passign(TeArgs& A, hipStream_t st);
 hipError_t launch_te_hot_reduce(TeArgs& A, int num_cu, hipStream_t st);      // chunk sums of the hot rows (te_scatter.hip); early on the side stream when TeArgs.hot_early
 hipError_t launch_te_dprep(TeArgs& A, hipStream_t st);        // chunk offsets of the distance-bin chain (behind the slot sort; launch_te_bins expects them)      // S rows of the per-POI regrouping (behind the slot sort)
 int te_wgrad_ui_jobs(int D, int n_dist, bool spatial, bool bintab);
-hipError_t launch_te_scatter(TeArgs& A, float alpha, float lambda, int num_cu, hipStream_t st, Timing* tm);
+hipError_t launch_te_scatter(TeArgs& A, float alpha, float lambda, int num_cu, hipStream_t st, Timing* tm, int* forked = nullptr);      // forked: the plan record (poi_ctx_last_plan "fork")
 hipError_t launch_te_bins(TeArgs& A, float alpha, float lambda, int num_cu, hipStream_t sb, Timing* tm);      // te_scatter.hip: per-bin sums of DA -> d di, d ui[:, D:]
 int te_nbp(int n_dist);
 void launch_te_iota(int* buf, int n, hipStream_t st);

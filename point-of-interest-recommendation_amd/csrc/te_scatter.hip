@@ -910,7 +910,7 @@ hipError_t launch_te_bins(TeArgs& A, float alpha, float lambda, int num_cu, hipS
 }
 
 template <int D>
-static hipError_t te_scatter_t(TeArgs& A, float alpha, float lambda, int num_cu, hipStream_t st, Timing* tm) {
+static hipError_t te_scatter_t(TeArgs& A, float alpha, float lambda, int num_cu, hipStream_t st, Timing* tm, int* forked) {
   const int R = A.n_item + 1 + A.n_dist + 1;
   int grid = (R + 3) / 4;
   if (grid > num_cu * 32) grid = num_cu * 32;
@@ -923,6 +923,7 @@ static hipError_t te_scatter_t(TeArgs& A, float alpha, float lambda, int num_cu,
   // Timing: forked regions OVERLAP the main stream's and stretch each other; `te_tail` spans this function's fork to join.
   const bool early = A.bintab && A.early_bins;
   const bool fork = !early && A.bintab && A.side && !(A.dbg & 1) && A.n_seq >= 2048;
+  if (forked) *forked = fork ? 1 : 0;
   hipStream_t sb = fork ? A.side : st;
   const long tail = tm->span_begin("te_tail", st);
   if (fork && (hipEventRecord(A.ev_bwd, st) != hipSuccess || hipStreamWaitEvent(sb, A.ev_bwd, 0) != hipSuccess)) return hipGetLastError();
@@ -952,10 +953,10 @@ hipError_t launch_te_hot_reduce(TeArgs& A, int num_cu, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_te_scatter(TeArgs& A, float alpha, float lambda, int num_cu, hipStream_t st, Timing* tm) {
-  if (A.dim == 64) return te_scatter_t<64>(A, alpha, lambda, num_cu, st, tm);
-  if (A.dim == 128) return te_scatter_t<128>(A, alpha, lambda, num_cu, st, tm);
-  if (A.dim == 256) return te_scatter_t<256>(A, alpha, lambda, num_cu, st, tm);
+hipError_t launch_te_scatter(TeArgs& A, float alpha, float lambda, int num_cu, hipStream_t st, Timing* tm, int* forked) {
+  if (A.dim == 64) return te_scatter_t<64>(A, alpha, lambda, num_cu, st, tm, forked);
+  if (A.dim == 128) return te_scatter_t<128>(A, alpha, lambda, num_cu, st, tm, forked);
+  if (A.dim == 256) return te_scatter_t<256>(A, alpha, lambda, num_cu, st, tm, forked);
   return hipErrorInvalidValue;
 }
 

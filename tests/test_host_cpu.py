@@ -39,6 +39,20 @@ def test_argument_counts_match_header(lib):
         assert len(params) == len(args), (name, params, len(args))
 
 
+def test_last_plan_keys_match_header():
+    """ABI 9: the keys poi_ctx_last_plan documents are the binding's PLAN_KEYS, and abi.hip answers every one of them."""
+    hdr = open(os.path.join(ROOT, "include", "poi_hip.h")).read()
+    assert re.search(r"#define POI_ABI_VERSION 9\b", hdr) and poi_amd._lib.ABI_VERSION == 9
+    doc = hdr[hdr.index("/* ABI 9."):hdr.index("int poi_ctx_last_plan(")]
+    keys = list(dict.fromkeys(re.findall(r'"([a-z0-9_]+)"', doc)))
+    assert keys and tuple(keys) == poi_amd._lib.PLAN_KEYS, keys
+    src = open(os.path.join(ROOT, "point-of-interest-recommendation_amd", "csrc", "abi.hip")).read()
+    body = src[src.index("int poi_ctx_last_plan("):]
+    body = body[:body.index("\n}\n")]
+    for k in keys:
+        assert '"%s"' % k in body, k
+
+
 def test_models_refuse_to_run_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -148,10 +148,10 @@ def test_synthetic_builder_gap_fraction():
     assert ds.coords.shape == (ds.n_item + 1, 2) and np.all(ds.coords[-1] == 0)
 
 
-# ---- ABI 8 ------------------------------------------------------------------------------------------------------------------------
-def test_abi8_declarations_match_signatures():
+# ---- ABI 8 entries (unchanged in ABI 9) --------------------------------------------------------------------------------------------
+def test_abi8_declarations_match_signatures_in_abi9():
     hdr = open(os.path.join(ROOT, "include", "poi_hip.h")).read()
-    assert poi_amd._lib.ABI_VERSION == 8 and re.search(r"#define POI_ABI_VERSION 8\b", hdr)
+    assert poi_amd._lib.ABI_VERSION == 9 and re.search(r"#define POI_ABI_VERSION 9\b", hdr)
     assert re.search(r"typedef struct poi_prme_params \{\s*float\* du; float\* dp; float\* ds;\s*int32_t n_user; int32_t n_item; int32_t dim;", hdr)
     assert [f[0] for f in poi_amd._lib.PrmeParams._fields_] == ["du", "dp", "ds", "n_user", "n_item", "dim"]
     for name, nargs in (("poi_prme_step", 15), ("poi_prme_score_all", 9), ("poi_prme_score_topk", 11)):
