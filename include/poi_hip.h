@@ -50,6 +50,8 @@ extern "C" {
 /* 7: FPMC-LR - new entry points poi_fpmc_neighbor_counts / _fill, poi_fpmc_sample_negatives, poi_fpmc_step (existing entries unchanged). */
 /* 8: PRME - new entry points poi_prme_step, poi_prme_score_all, poi_prme_score_topk and poi_prme_params (existing entries unchanged). */
 /* 9: new entry point poi_ctx_last_plan (existing entries unchanged). */
+/* additive to 9: GeoIE - new entry points poi_geoie_step, poi_geoie_pair_distances, poi_geoie_user_vectors and poi_geoie_params (existing
+ * entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -468,6 +470,50 @@ int poi_prme_score_all(poi_ctx* ctx, const poi_prme_params* prm, const double* c
                        float cw, float* out, void* stream);
 int poi_prme_score_topk(poi_ctx* ctx, const poi_prme_params* prm, const double* coords, const int32_t* users, const int32_t* qpoi,
                         int32_t n_rows, float cw, int32_t k, int32_t* idx_out, float* score_out, void* stream);
+
+/* ---- GeoIE (additive to ABI 9) - prog_geoie.py, public/GeoIE.py, public/Load_Data_GeoIE.py -----------------------------------------
+ * Tables (GeoIE.py:65-78): g, h, z (n_item + 1, D) with a padding row, t (n_user, D); ab = {a, b} float64 on the device (the launches
+ * chain without a host sync).  Float32 tables only; D a multiple of 4, D <= 128 (scoring: [t | m] . [z | h] at width 2 D <= 256). */
+typedef struct poi_geoie_params {
+  float* g; float* h; float* t; float* z; double* ab;
+  int32_t n_user; int32_t n_item; int32_t dim;
+} poi_geoie_params;
+/* One launch of n users (users[k], rows of the training CSR off / p / q: positions off[u] .. off[u+1]-1 of the flat POIs p and negatives
+ * q; coords (n_item, 2) float64 lat, lon; cphi (n_item) = cos(lat * pi / 180), data.cos_lat), replacing GeoIE.seq_train
+ * (GeoIE.py:129-188, driver prog_geoie.py:160-185, distances of Load_Data_GeoIE.py:143-156).  For user u with POIs p_0 .. p_{L-1} and
+ * negatives q_0 .. q_{L-1}, rows i = 0 .. L-2, columns j <= i:
+ *   dp_ij = float32(cal_dis(p_j, p_{i+1})),  dq_ij = float32(cal_dis(p_j, q_{i+1}))  (float64 in cal_dis's operation order),
+ *   f(d) = a max(d, d_min)^b (float64),  sp_i - sq_i = (1 / (i + 1)) sum_j (g[p_j].h[p_{i+1}] f(dp_ij) - g[p_j].h[q_{i+1}] f(dq_ij)),
+ *   loss_out[k] = sum_i log sigmoid(sp_i - sq_i),  cost = -loss + lambda / 2 (|g[p_0..p_{L-2}]|^2 + |h, z at p_{1..}, q_{1..}|^2)
+ * (every gathered occurrence counts); every gathered row moves by -alpha d cost / d row with the user's full accumulated gradient, and
+ * a, b by -alpha d cost / d (a, b): t never moves, z by L2 decay only, a and b get no decay.  Undefined cases of the reference (f(0) with
+ * b <= 0) follow DESIGN.md section 11: a pair at max(d, d_min) = 0 with b > 0 contributes f = 0 and df/db = 0; a user with an id out of
+ * range (users[k] outside [0, n_user), a POI or negative outside [0, n_item)), or with any non-finite value - max(d, d_min) = 0 with
+ * b <= 0 included - is REJECTED: it moves nothing (rows, a, b), its loss is NaN, it counts in no k and is counted once
+ * (poi_ctx_take_bad_ids).  A user with L < 2 has no rows: loss 0, not counted.  Batch semantics above (poi_ctx_set_batch_cap): every
+ * user at the launch-entry values, a row touched by k users moves by min(k, cap) / k times their summed updates, a and b are touched by
+ * every accepted user with rows; n == 1 is the reference step.  The 5 touches per row (g[p_i], h and z at p_{i+1}, q_{i+1}) are sorted
+ * by (table, row) and summed in a fixed order with no float atomics: identical launches give bitwise identical g, h, z, a, b.
+ * n_rows = sum over the launch of max(L - 1, 0), known to the host (scratch is sized from it; no device-to-host sync); a launch whose
+ * rows do not add up to it moves nothing and rejects every user.  Timing names: "geoie_plan", "geoie_row", "geoie_col", "geoie_user",
+ * "geoie_sort", "geoie_rows", "geoie_commit", "geoie_ab". */
+int poi_geoie_step(poi_ctx* ctx, const poi_geoie_params* prm, const int32_t* off, const int32_t* p, const int32_t* q, const double* coords,
+                   const double* cphi, const int32_t* users, int32_t n, int64_t n_rows, float alpha, float lambda, double d_min,
+                   float* loss_out, void* stream);
+/* The float32 dp / dq of a launch (fun_compute_dist_neg, Load_Data_GeoIE.py:143-156, without the zero padding) in packed lower-triangular
+ * order: user k (launch order) starts at P_k = sum_{k' < k} R_k' (R_k' + 1) / 2, R = max(L - 1, 0), and its pair (i, j <= i) is at
+ * P_k + i (i + 1) / 2 + j.  n_pairs = the host's total.  NaN for a pair with an id out of range, and everywhere when the totals do not
+ * match.  Timing name: "geoie_pairs". */
+int poi_geoie_pair_distances(poi_ctx* ctx, const int32_t* off, const int32_t* p, const int32_t* q, int32_t n_user, int32_t n_item,
+                             const double* coords, const double* cphi, const int32_t* users, int32_t n, int64_t n_rows, int64_t n_pairs,
+                             float* dp_out, float* dq_out, void* stream);
+/* User side of GeoIE.compute_sub_all_scores (GeoIE.py:117-127): out (n_user, 2 D) row u = [t[u] | m_u], m_u = (sum_{j < L_u} g[p_j]) / nH_u,
+ * a float64 sum in sequence order.  norm 0 ("reference"): nH_u = sum_j p_j + (len_max - L_u) n_item, the reference's sum of the padded
+ * id row (tra_buys_masks, not the mask); norm 1 ("count"): nH_u = L_u (m_u = 0 for L_u = 0).  Scores s[u, k] = t[u].z[k] + m_u.h[k] then
+ * come from poi_score_all / poi_score_topk with items [z | h] at width 2 D.  A POI id outside [0, n_item] makes the row's m NaN.
+ * Timing name: "geoie_uvec". */
+int poi_geoie_user_vectors(poi_ctx* ctx, const poi_geoie_params* prm, const int32_t* off, const int32_t* p, int32_t n_user, int32_t len_max,
+                           int32_t norm, float* out, void* stream);
 
 /* ---- multi-GPU reconciliation (8e; new - the reference is single-process) ----------------------
  * Users are sharded across ranks, every rank trains on a full parameter replica with no data-path collective,

@@ -32,6 +32,10 @@ class PrmeParams(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("du", "dp", "ds")] + [("n_user", c_int32), ("n_item", c_int32), ("dim", c_int32)]
 
 
+class GeoieParams(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("g", "h", "t", "z", "ab")] + [("n_user", c_int32), ("n_item", c_int32), ("dim", c_int32)]
+
+
 class SyncSeg(ctypes.Structure):
     _fields_ = [("cur", c_void_p), ("rows", c_int64), ("width", c_int64), ("rule", c_int32), ("dtype", c_int32)]
 
@@ -112,6 +116,11 @@ SIGNATURES = {
     "poi_prme_score_all": (c_int, [c_void_p, POINTER(PrmeParams), c_void_p, c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p]),
     "poi_prme_score_topk": (c_int, [c_void_p, POINTER(PrmeParams), c_void_p, c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p,
                                     c_void_p]),
+    "poi_geoie_step": (c_int, [c_void_p, POINTER(GeoieParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64,
+                               c_float, c_float, c_double, c_void_p, c_void_p]),
+    "poi_geoie_pair_distances": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                         c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "poi_geoie_user_vectors": (c_int, [c_void_p, POINTER(GeoieParams), c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "poi_delta_make": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_delta_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_comm_available": (c_int, []),

@@ -88,6 +88,8 @@ struct poi_ctx {
   DevBuf fp_ws;
   // PRME step: the same layout for 7 touches per transition
   DevBuf pr_ws;
+  // GeoIE step / pair distances: plan, per-row and per-user values, touch gradients, sort buffers, new-row slots
+  DevBuf ge_ws;
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)
@@ -223,7 +225,7 @@ int poi_ctx_destroy(poi_ctx* c) {
   if (!c) return POI_OK;
   DevBuf* all[] = {&c->ex_ws, &c->ex_slab, &c->ex_glt, &c->ex_gdi, &c->ws, &c->slab, &c->te_ws, &c->hslab, &c->zrow, &c->g_lt, &c->mult_lt, &c->nseq_lt, &c->g_di, &c->mult_di, &c->nseq_di, &c->seg_s, &c->seg_e, &c->pmark, &c->xc, &c->kc_dev, &c->uidx_stage, &c->out_stage, &c->ptab, &c->iota, &c->xw, &c->xg, &c->xflag, &c->bad_ids,
                    &c->g_wd, &c->mult_wd, &c->nseq_wd, &c->ca_ws, &c->ca_slab, &c->ca_scr, &c->ca2, &c->g_ux, &c->cnt_ux, &c->g_blt, &c->cnt_blt, &c->cand_s, &c->cand_i, &c->items_pk, &c->gbound, &c->st,
-                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws};
+                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws};
   (void)hipDeviceSynchronize();
   c->tm.clear();
   drop_graphs(c);
@@ -1011,6 +1013,113 @@ int poi_prme_score_topk(poi_ctx* c, const poi_prme_params* P, const double* coor
                         int32_t n_rows, float cw, int32_t k, int32_t* idx_out, float* score_out, void* stream) {
   if (k <= 0) return fail(c, POI_EINVAL, "poi_prme_score_topk: k must be positive (got %d)", k);
   return prme_score_common(c, P, coords, users, qpoi, n_rows, cw, k, nullptr, idx_out, score_out, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// GeoIE (geoie.hip)
+static int geoie_check(poi_ctx* c, const poi_geoie_params* P, const char* who) {
+  if (!c || !P || !P->g || !P->h || !P->t || !P->z || !P->ab) return fail(c, POI_EINVAL, "%s: NULL argument", who);
+  if (is_f16(c, P->g) || is_f16(c, P->h) || is_f16(c, P->t) || is_f16(c, P->z)) return fail(c, POI_ENOTSUP, "GeoIE tables are float32 only");
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 128) return fail(c, POI_ENOTSUP, "GeoIE: dim must be a multiple of 4 in [4, 128] (got %d)", P->dim);
+  if (P->n_user <= 0 || P->n_item <= 0) return fail(c, POI_EINVAL, "%s: bad sizes", who);
+  return POI_OK;
+}
+
+// carve the GeoIE workspace for a launch of n users and P rows (256-byte aligned pieces); pairs: also the pair offsets
+static int geoie_workspace(poi_ctx* c, poi::GeoieArgs& A, int n, int P, int dim, bool pairs, hipStream_t st) {
+  const size_t chunks = ((size_t)5 * P + 63) / 64 + 2, T = 5 * (size_t)P + 64;
+  const size_t sizes[] = {
+      sizeof(int) * ((size_t)n + 1), sizeof(int) * ((size_t)n + 1), sizeof(int) * ((size_t)n + 1), sizeof(long long) * ((size_t)n + 1),
+      sizeof(int) * ((size_t)n + 1), sizeof(int) * 8, sizeof(int) * ((size_t)P + 1), sizeof(float) * ((size_t)P + 1),
+      sizeof(double) * ((size_t)P + 1) * 3, sizeof(double) * ((size_t)n + 1) * 2, pairs ? 0 : sizeof(float) * 3 * (size_t)P * dim,
+      pairs ? 0 : sizeof(int) * T * 4, sizeof(int) * ((size_t)RS_HIST_INTS + RS_MAXBIN + 64), pairs ? 0 : sizeof(int4) * chunks * 2,
+      pairs ? 0 : sizeof(float) * chunks * dim * 2, pairs ? 0 : sizeof(float) * 5 * (size_t)P * dim};
+  size_t total = 0;
+  for (size_t s : sizes) total += (s + 255) & ~(size_t)255;
+  int rc = ensure(c, c->ge_ws, total + 256, st);
+  if (rc) return rc;
+  char* b = (char*)c->ge_ws.p;
+  size_t i = 0;
+  auto take = [&]() { char* r = b; b += (sizes[i++] + 255) & ~(size_t)255; return (void*)r; };
+  A.rowoff = (int*)take(); A.troff = (int*)take(); A.tcoff = (int*)take(); A.pairoff = (long long*)take();
+  A.ubad = (int*)take(); A.tot = (int*)take(); A.tuser = (int*)take(); A.coef = (float*)take();
+  A.rloss = (double*)take(); A.rda = A.rloss + (P + 1); A.rdb = A.rda + (P + 1);
+  A.uda = (double*)take(); A.udb = A.uda + (n + 1);
+  A.G = (float*)take();
+  int* kv = (int*)take();
+  A.keys0 = kv; A.keys1 = kv + T; A.vals0 = kv + 2 * T; A.vals1 = kv + 3 * T;
+  int* hc = (int*)take();
+  A.hist = hc; A.cnt = hc + RS_HIST_INTS + RS_MAXBIN;
+  A.meta = (int4*)take(); A.meta2 = A.meta + chunks;
+  A.lead = (float*)take(); A.trail = A.lead + chunks * dim;
+  A.slot = (float*)take();
+  if (!pairs) A.pairoff = nullptr;
+  return POI_OK;
+}
+
+int poi_geoie_step(poi_ctx* c, const poi_geoie_params* P, const int32_t* off, const int32_t* p, const int32_t* q, const double* coords,
+                   const double* cphi, const int32_t* users, int32_t n, int64_t n_rows, float alpha, float lambda, double d_min,
+                   float* loss_out, void* stream) {
+  int rc = geoie_check(c, P, "poi_geoie_step");
+  if (rc) return rc;
+  if (!off || !p || !q || !coords || !cphi || !users || !loss_out) return fail(c, POI_EINVAL, "poi_geoie_step: NULL argument");
+  if (n < 0 || n_rows < 0) return fail(c, POI_EINVAL, "poi_geoie_step: bad sizes");
+  if (!(d_min >= 0.0)) return fail(c, POI_EINVAL, "poi_geoie_step: d_min must be >= 0");
+  if (3 * ((int64_t)P->n_item + 1) >= ((int64_t)1 << 31) - 1) return fail(c, POI_ENOTSUP, "GeoIE: 3 (n_item + 1) must stay below 2^31");
+  if (n_rows * 5 >= ((int64_t)1 << 31) - 64) return fail(c, POI_ENOTSUP, "GeoIE: at most 2^31 / 5 rows per launch");
+  if (c->batch_cap == 0.0f) return fail(c, POI_ENOTSUP, "the mini-batch rule (batch cap 0) applies to poi_gru_step / poi_spatial_step only");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::GeoieArgs A;
+  memset(&A, 0, sizeof A);
+  A.g = P->g; A.h = P->h; A.t = P->t; A.z = P->z; A.ab = P->ab; A.n_user = P->n_user; A.n_item = P->n_item; A.dim = P->dim;
+  A.off = off; A.p = p; A.q = q; A.users = users; A.coords = coords; A.cphi = cphi;
+  A.n = n; A.P = (int)n_rows; A.n_pairs = -1; A.d_min = d_min;
+  A.alpha = alpha; A.lambda = lambda; A.bcap = c->batch_cap; A.loss = loss_out;
+  A.sentinel = 3 * (P->n_item + 1);
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  if ((rc = geoie_workspace(c, A, n, (int)n_rows, P->dim, false, st))) return rc;
+  HIPCHK(c, poi::launch_geoie_step(A, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_geoie_pair_distances(poi_ctx* c, const int32_t* off, const int32_t* p, const int32_t* q, int32_t n_user, int32_t n_item,
+                             const double* coords, const double* cphi, const int32_t* users, int32_t n, int64_t n_rows, int64_t n_pairs,
+                             float* dp_out, float* dq_out, void* stream) {
+  if (!c || !off || !p || !q || !coords || !cphi || !users || !dp_out || !dq_out) return fail(c, POI_EINVAL, "poi_geoie_pair_distances: NULL argument");
+  if (n < 0 || n_rows < 0 || n_pairs < 0 || n_user <= 0 || n_item <= 0 || n_rows >= ((int64_t)1 << 31) / 5)
+    return fail(c, POI_EINVAL, "poi_geoie_pair_distances: bad sizes");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::GeoieArgs A;
+  memset(&A, 0, sizeof A);
+  A.n_user = n_user; A.n_item = n_item; A.off = off; A.p = p; A.q = q; A.users = users; A.coords = coords; A.cphi = cphi;
+  A.n = n; A.P = (int)n_rows; A.n_pairs = n_pairs; A.dp_out = dp_out; A.dq_out = dq_out;
+  int rc = geoie_workspace(c, A, n, (int)n_rows, 4, true, st);
+  if (rc) return rc;
+  c->tm.begin("geoie_pairs", st);
+  HIPCHK(c, poi::launch_geoie_pairs(A, c->num_cu, st));
+  c->tm.end(st);
+  return POI_OK;
+}
+
+int poi_geoie_user_vectors(poi_ctx* c, const poi_geoie_params* P, const int32_t* off, const int32_t* p, int32_t n_user, int32_t len_max,
+                           int32_t norm, float* out, void* stream) {
+  int rc = geoie_check(c, P, "poi_geoie_user_vectors");
+  if (rc) return rc;
+  if (!off || !p || !out) return fail(c, POI_EINVAL, "poi_geoie_user_vectors: NULL argument");
+  if (n_user < 0 || n_user > P->n_user || len_max < 0) return fail(c, POI_EINVAL, "poi_geoie_user_vectors: bad sizes");
+  if (norm != 0 && norm != 1) return fail(c, POI_EINVAL, "poi_geoie_user_vectors: norm must be 0 (reference) or 1 (count)");
+  if (n_user == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->tm.begin("geoie_uvec", st);
+  HIPCHK(c, poi::launch_geoie_uvec(P->g, P->t, off, p, n_user, P->n_item, P->dim, len_max, norm, out, c->num_cu, st));
+  c->tm.end(st);
+  return POI_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -402,6 +402,38 @@ struct PrmeScoreArgs {
 };
 hipError_t launch_prme_score(PrmeScoreArgs& A, hipStream_t st);
 
+// GeoIE (geoie.hip)
+struct GeoieArgs {
+  float *g, *h, *t, *z;             // (n_item + 1, D) x 3, t (n_user, D)
+  double* ab;                       // a, b on the device
+  int n_user, n_item, dim;
+  const int *off, *p, *q, *users;   // training CSR (n_user + 1 offsets), launch users (n)
+  const double *coords, *cphi;      // (n_item, 2) lat, lon; cos(lat * pi / 180) per POI
+  int n, P;                         // launch users, host total of rows sum max(L - 1, 0)
+  long long n_pairs;                // host total of pairs (poi_geoie_pair_distances), -1 in the step
+  double d_min;
+  float alpha, lambda, bcap;
+  float* loss;                      // (n) per user
+  int* bad;                         // device counter of rejected users (poi_ctx_take_bad_ids)
+  int sentinel;                     // key of a rejected user's touches: 3 (n_item + 1), sorts last
+  int *rowoff, *troff, *tcoff;      // (n + 1) exclusive scans of rows, row-pass tiles, column-pass tiles
+  long long* pairoff;               // (n + 1) pairs (pair distances only)
+  int *ubad, *tot;                  // per-user rejection flag; {rows, row tiles, column tiles, -, totals mismatch}
+  int* tuser;                       // (P) launch user of a row
+  float* coef;                      // (P) sigmoid(-diff_i) / (i + 1)
+  double *rloss, *rda, *rdb, *uda, *udb;      // per row / per user: loss, d cost / d a, d cost / d b
+  float* G;                         // (3 P, D) loss gradients of the g touches [0, P) and the h touches [P, 3 P)
+  int *keys0, *keys1, *vals0, *vals1, *hist, *cnt;      // radix sort of the 5 P touches
+  const int *ks, *vs;
+  int4 *meta, *meta2;               // per 64-touch window: {opening run's touches, it goes on, closing run's touches, its key}; {users of both}
+  float *lead, *trail, *slot;       // per-window partial sums; (5 P, D) new rows at a run's first position
+  float *dp_out, *dq_out;           // packed pair distances
+};
+hipError_t launch_geoie_step(GeoieArgs& A, int num_cu, hipStream_t st, Timing* tm);
+hipError_t launch_geoie_pairs(GeoieArgs& A, int num_cu, hipStream_t st);
+hipError_t launch_geoie_uvec(const float* g, const float* t, const int* off, const int* p, int n_user, int n_item, int dim, int len_max,
+                             int norm, float* out, int num_cu, hipStream_t st);
+
 // scoring / top-K
 struct ScoreArgs {
   const float *users, *items; int items_f16;      // items: float32, or IEEE half when items_f16

@@ -578,3 +578,39 @@ def make_prme_synthetic(n_user, n_item, max_len, seed, far_frac=0.3, threshold=3
         g[0] = 0
         seqs.append(s.tolist()); times.append(np.cumsum(g).astype(np.float64).tolist()); cods.append([tuple(base.coords[i]) for i in s])
     return _prme_from_lists(seqs, times, cods, split, seed, where="make_prme_synthetic")[0]
+
+
+# ---- GeoIE (public/Load_Data_GeoIE.py) --------------------------------------------------------------------------------------------
+# The data are load_sequence_file's / make_synthetic's PoiDataset: the same split (train = upois[:split], held-out upois[split]), the same
+# coordinates (a POI's last occurrence in the file) and the same negatives rule (fun_random_neg_masks_tra) as Load_Data_GeoIE.load_data.
+def geoie_cal_dis(lat1, lon1, lat2, lon2):
+    """cal_dis of Load_Data_GeoIE.py:28-42, vectorised in its float64 operation order (km)."""
+    lat1, lon1, lat2, lon2 = (np.asarray(v, np.float64) for v in (lat1, lon1, lat2, lon2))
+    a = (lat1 - lat2) * DEG
+    b = (lon1 - lon2) * DEG
+    c = (1.0 - np.cos(a)) / 2 + np.cos(lat1 * DEG) * np.cos(lat2 * DEG) * (1.0 - np.cos(b)) / 2
+    return EARTH_D * np.arcsin(np.sqrt(c))
+
+
+def geoie_pair_distances(coords, off, p, q, users=None):
+    """fun_compute_dist_neg (Load_Data_GeoIE.py:143-156) without its zero padding, in poi_geoie_pair_distances' packed order: for each user
+    of `users` (default all, in order) and each row i = 0 .. L-2, the float32 distances of p_0 .. p_i to p_{i+1} (dp) and to q_{i+1} (dq).
+    Returns (dp, dq, pair offsets per user (len(users) + 1, int64), rows per user)."""
+    xy = np.asarray(coords, np.float64)
+    off = np.asarray(off, np.int64)
+    p, q = np.asarray(p, np.int64), np.asarray(q, np.int64)
+    users = np.arange(len(off) - 1) if users is None else np.asarray(users, np.int64)
+    rows = np.maximum(off[users + 1] - off[users] - 1, 0)
+    poff = np.zeros(len(users) + 1, np.int64)
+    np.cumsum(rows * (rows + 1) // 2, out=poff[1:])
+    dp, dq = np.empty(int(poff[-1]), np.float32), np.empty(int(poff[-1]), np.float32)
+    for k, u in enumerate(users):
+        R = int(rows[k])
+        if R == 0:
+            continue
+        s = p[off[u]:off[u + 1]]
+        ii, jj = np.tril_indices(R)
+        src, tp, tq = xy[s[jj]], xy[s[ii + 1]], xy[q[off[u] + ii + 1]]
+        dp[poff[k]:poff[k + 1]] = geoie_cal_dis(src[:, 0], src[:, 1], tp[:, 0], tp[:, 1])
+        dq[poff[k]:poff[k + 1]] = geoie_cal_dis(src[:, 0], src[:, 1], tq[:, 0], tq[:, 1])
+    return dp, dq, poff, rows

@@ -322,3 +322,51 @@ def train_prme(ds, p=None, device="cuda:0", log=print):
         log("epoch %d  sum_loss = %.3f = %.3f + %.3f  auc %.4f  recall@%d %.4f  time (train, test) %.2fs %.2fs"
             % (epoch, loss + l2, loss, l2, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1))
     return model, best, history
+
+
+def geoie_default_params():
+    """The in-source config of prog_geoie.py:46-63 (+ `batch`: users per launch - 1 is the reference's one-by-one training -, seed, d_min (km,
+    0 = the reference) and score_norm ("reference" | "count"))."""
+    return dict(dataset="Foursquare.txt", mode="test", load_epoch=0, save_per_epoch=100, split=-1, at_nums=[5, 10, 15, 20], epochs=101,
+                latent_size=20, alpha=0.01, **{"lambda": 0.001}, mini_batch=0, GeoIE=1, batch_size_train=1, batch_size_test=5, batch=1, seed=123,
+                d_min=0.0, score_norm="reference")
+
+
+def train_geoie(ds, p=None, device="cuda:0", log=print):
+    """train_valid_or_test of prog_geoie.py:138-236 on a PoiDataset: OboGeoIE over ds, then per epoch: new negatives on the device (epoch > 0),
+    users shuffled, launches of p['batch'] users, the sum_loss line (sum of log sigmoid + l2), update_trained, AUC (always 0, as the
+    reference) and top-K metrics into GlobalBest.  The history records a, b and the users rejected in the epoch (logged, not raised: they
+    depend on data and parameters; their losses are left out of the sum).  Returns (model, best, history)."""
+    p = dict(geoie_default_params(), **(p or {}))
+    model = models.OboGeoIE(train=ds.shard(), test=None, alpha_lambda=[p["alpha"], p["lambda"]], n_user=ds.n_user, n_item=ds.n_item,
+                            n_in=p["latent_size"], n_hidden=p["latent_size"], coords=ds.coords, device=device, seed=p.get("seed"),
+                            d_min=p["d_min"], score_norm=p["score_norm"])
+    best = GlobalBest(p["at_nums"])
+    U = ds.n_user
+    ses_tes = compute_start_end(U, p["batch_size_test"])
+    ses_auc = compute_start_end(U, p["batch_size_test"] * 10)
+    tes_p, tes_m = ds.tes_p.reshape(-1, 1), np.ones((U, 1), np.int32)
+    B = max(1, int(p.get("batch", 1)))
+    history = []
+    for epoch in range(p["epochs"]):
+        if epoch > 0:                                               # :162-167
+            model.resample_negatives_device(p.get("seed", 0) * 1000003 + epoch)
+        t0 = time.time()
+        order = np.random.default_rng(123 + epoch).permutation(U)   # :175-177
+        model.ctx.take_bad_ids(model._stream().value)
+        parts = [model.train_batch(order[s:s + B], sync=False) for s in range(0, U, B)]      # :178-185 (B = 1: one user per call)
+        rejected = model.ctx.take_bad_ids(model._stream().value)
+        model.rejected += rejected
+        losses = torch.cat(parts).double() if parts else torch.zeros(0, dtype=torch.float64)
+        loss = float(torch.nan_to_num(losses, nan=0.0).sum().item())
+        l2 = model.l2.eval()                                        # :186
+        a, b = float(model.ab[0].item()), float(model.ab[1].item())
+        t1 = time.time()
+        model.update_trained()                                      # :200
+        m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m)      # :204-206
+        t2 = time.time()
+        history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall={k: m["at"][k]["recall"] for k in p["at_nums"]},
+                            a=a, b=b, rejected=rejected, times=(t1 - t0, t2 - t1)))
+        log("epoch %d  sum_loss = %.3f = %.3f + %.3f  a %.6f  b %.6f  rejected users %d  auc %.4f  recall@%d %.4f  time (train, test) %.2fs %.2fs"
+            % (epoch, loss + l2, loss, l2, a, b, rejected, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1))
+    return model, best, history

@@ -1327,3 +1327,206 @@ class OboPrme(_Base):
 
 class OboPRPRM(OboPrme):
     """public/PRPRM.py: the same model as OboPrme under another class name (prog_prme.py's 'prme' flag 1)."""
+
+
+# =================================================================================================
+class _GeoieL2:
+    """model.l2 of GeoIE.py:92-98: 0.5 lambda (|g|^2 + |h|^2 + |t|^2 + |z|^2 + a^2 + b^2)."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def eval(self):
+        m = self.model
+        acc = torch.zeros(1, dtype=torch.float64, device=m.device)
+        for n in m.TABLES:
+            t = getattr(m, n).t
+            m.ctx.check(m.lib.poi_sumsq(m.ctx.handle, _ptr(t), t.numel(), _ptr(acc), m._stream()))
+        return 0.5 * m.alpha_lambda[1] * (float(acc.item()) + float((m.ab ** 2).sum().item()))
+
+
+class OboGeoIE(_Base):
+    """public/GeoIE.py:46-194 (driver prog_geoie.py): GeoIE, a pairwise geo-influence model.  Tables g (geo-influence), h (geo-susceptibility),
+    z (POI preference) (n_item + 1, D) and t (user preference) (n_user, D); the power law f(d) = a d^b with a, b float64 on the device.  A step of
+    one user is a masked all-pairs interaction over the user's whole train sequence (poi_geoie_step); scoring reads the trained_* snapshots
+    taken by update_trained: s[u, k] = t[u].z[k] + m_u.h[k] (poi_geoie_user_vectors + poi_score_all / poi_score_topk at width 2 D).
+
+    train: a CsrTables (PoiDataset.shard(); test is then None) or the reference's [tra_buys_masks, tra_buys_neg_masks, tra_count, tra_masks]
+    with test = [tes_buys_masks, tes_buys_neg_masks].  coords (n_item, 2) lat, lon - required (the distances are computed on the device).
+    n_hidden = D, a multiple of 4 in [4, 128].  Extra keywords: device, init (dict of float64 arrays g / h / t / z and scalars a / b), seed,
+    d_min (km; pairs use max(d, d_min), 0 = the reference), score_norm ("reference": the reference's divisor - the sum of the padded id row -,
+    "count": the sequence length)."""
+
+    TABLES = ("g", "h", "t", "z")
+
+    def __init__(self, train, test, alpha_lambda, n_user, n_item, n_in, n_hidden, coords=None, device="cuda:0", init=None, seed=None,
+                 d_min=0.0, score_norm="reference"):
+        self.n_user, self.n_item, self.dim = int(n_user), int(n_item), int(n_hidden)
+        if self.dim <= 0 or self.dim % 4 or self.dim > 128:
+            raise ValueError("OboGeoIE: n_hidden must be a multiple of 4 in [4, 128] (got %d)" % self.dim)
+        if coords is None:
+            raise ValueError("OboGeoIE needs coords= (the pair distances are computed on the device from the POI coordinates)")
+        if score_norm not in ("reference", "count"):
+            raise ValueError("score_norm must be 'reference' or 'count' (got %r)" % (score_norm,))
+        if not float(d_min) >= 0.0:
+            raise ValueError("d_min must be >= 0")
+        self.d_min, self.score_norm = float(d_min), score_norm
+        off, p, q, tes = self._host_tables(train, test)
+        lens = np.diff(off.astype(np.int64))
+        if len(lens) != self.n_user:
+            raise ValueError("OboGeoIE: %d train sequences for n_user = %d" % (len(lens), self.n_user))
+        for nm, t in (("test POIs", tes[0]), ("test negatives", tes[2])):
+            self._check_ids(nm, t, self.n_item)
+        for nm, t in (("train POIs", p), ("train negatives", q)):
+            if t.size and (t.min() < 0 or t.max() >= self.n_item):
+                raise IndexError("%s must lie in [0, %d)" % (nm, self.n_item))
+        xy = np.ascontiguousarray(coords, np.float64)
+        if xy.shape != (self.n_item, 2):
+            raise ValueError("coords must be (n_item, 2) lat, lon (got %s)" % (xy.shape,))
+        self._setup(device, alpha_lambda)
+        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+        self._off_host, self._lens = off, lens
+        self.len_max = int(lens.max()) if len(lens) else 0
+        self.off, self.p, self.q = i32(off), i32(p), i32(q)
+        self.tes_buys_masks, self.tes_masks, self.tes_buys_neg_masks = i32(tes[0]), i32(tes[1]), i32(tes[2])
+        self._arange = torch.arange(self.n_user, dtype=torch.int32, device=self.device)
+        self.coords = torch.as_tensor(xy).to(self.device)
+        self._cphi = torch.as_tensor(cos_lat(xy)).to(self.device)
+        rng = np.random.default_rng(seed) if seed is not None else np.random
+        init = init or {}
+        shapes = dict(g=(self.n_item + 1, self.dim), h=(self.n_item + 1, self.dim), t=(self.n_user, self.dim), z=(self.n_item + 1, self.dim))
+        vals = {}
+        for k in ("g", "h", "t", "z", "a", "b"):                                                # GeoIE.py:65-75
+            vals[k] = init[k] if k in init else (rng.uniform(-0.5, 0.5, shapes[k]) if k in shapes else rng.uniform(-0.5, 0.5))
+        for k in self.TABLES:
+            t = self._dev(vals[k])
+            if tuple(t.shape) != shapes[k]:
+                raise ValueError("init[%r] has shape %s, expected %s" % (k, tuple(t.shape), shapes[k]))
+            setattr(self, k, Shared(t))
+        self.ab = torch.tensor([float(vals["a"]), float(vals["b"])], dtype=torch.float64, device=self.device)
+        self.a, self.b = Shared(self.ab[0:1], scalar=True), Shared(self.ab[1:2], scalar=True)
+        self.params = [self.a, self.b]                                                         # :91
+        self.l2 = _GeoieL2(self)                                                               # :92-98
+        self._trained = {k: getattr(self, k).t.clone() for k in self.TABLES}                  # :81-88 (trained_*)
+        self._uvec = self._items_cat = None
+        self.rejected = 0
+
+    def _host_tables(self, train, test):
+        if isinstance(train, CsrTables):
+            return (np.ascontiguousarray(train.off, np.int32), np.ascontiguousarray(train.p, np.int32), np.ascontiguousarray(train.q, np.int32),
+                    (np.asarray(train.tes_p), np.asarray(train.tes_mask), np.asarray(train.tes_q)))
+        tra_buys, tra_neg, _, tra_masks = (np.asarray(x) for x in train)
+        lens = np.asarray(tra_masks, np.int64).sum(axis=1)
+        off, p = padded_to_csr(tra_buys, lens)
+        _, q = padded_to_csr(tra_neg, lens)
+        tes_p, tes_q = np.asarray(test[0]), np.asarray(test[1])
+        return off, p, q, (tes_p, (tes_p < self.n_item).astype(np.int32), tes_q)
+
+    # ---- negatives ----------------------------------------------------------------------------
+    def resample_negatives_device(self, seed):
+        """fun_random_neg_masks_tra (Load_Data_GeoIE.py:105-121, prog_geoie.py:162-163) - and the test negatives alongside - on the device:
+        poi_sample_negatives.  The distances follow on the device inside every step."""
+        q = torch.empty_like(self.p)
+        tq = torch.empty_like(self.tes_buys_masks)
+        self.ctx.check(self.lib.poi_sample_negatives(self.ctx.handle, _ptr(self.off), _ptr(self.p), self.n_user, self.n_item,
+                                                     _ptr(self.tes_buys_masks), _ptr(self.tes_masks), self.tes_masks.shape[1],
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(q), _ptr(tq), self._stream()))
+        self.q, self.tes_buys_neg_masks = q, tq
+
+    # ---- training -----------------------------------------------------------------------------
+    def _gparams(self, tabs):
+        return _lib.GeoieParams(*[ctypes.c_void_p(tabs[k].data_ptr()) for k in self.TABLES], ctypes.c_void_p(self.ab.data_ptr()),
+                                self.n_user, self.n_item, self.dim)
+
+    def train(self, uidx):
+        """GeoIE.train(uidx, dist_pos, dist_neg, msk) (GeoIE.py:190-194): the distances and the mask are built on the device -> loss."""
+        return float(self.train_batch([int(uidx)])[0])
+
+    def train_batch(self, uidxs, sync=True):
+        """A launch of users (poi_geoie_step, batch semantics of include/poi_hip.h) -> sum_i log sigmoid(sp_i - sq_i) per user.  A rejected user
+        (an id out of range, or a non-finite value - d_eff = 0 with b <= 0 included) moved nothing and has a NaN loss; with sync the count is
+        added to self.rejected (rejections depend on data and parameters: they are reported, not raised)."""
+        a = np.atleast_1d(np.asarray(uidxs.cpu().numpy() if isinstance(uidxs, torch.Tensor) else uidxs)).astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= self.n_user):
+            raise IndexError("user ids must lie in [0, %d) (found %d..%d)" % (self.n_user, int(a.min()), int(a.max())))
+        users = torch.as_tensor(a.astype(np.int32)).to(self.device)
+        n = int(a.size)
+        rows = int(np.maximum(self._lens[a] - 1, 0).sum()) if n else 0
+        loss = torch.empty(n, dtype=torch.float32, device=self.device)
+        P = self._gparams({k: getattr(self, k).t for k in self.TABLES})
+        self.ctx.check(self.lib.poi_geoie_step(self.ctx.handle, ctypes.byref(P), _ptr(self.off), _ptr(self.p), _ptr(self.q), _ptr(self.coords),
+                                               _ptr(self._cphi), _ptr(users), n, rows, self.alpha_lambda[0], self.alpha_lambda[1], self.d_min,
+                                               _ptr(loss), self._stream()))
+        if sync:
+            self.rejected += self.ctx.take_bad_ids(self._stream().value)
+        return loss.cpu().numpy() if sync else loss
+
+    def pair_distances(self, uidxs):
+        """poi_geoie_pair_distances of the users: packed float32 (dp, dq) device tensors (data.geoie_pair_distances' order)."""
+        a = np.atleast_1d(np.asarray(uidxs)).astype(np.int64)
+        rows = np.maximum(self._lens[a] - 1, 0)
+        npair = int((rows * (rows + 1) // 2).sum())
+        dp = torch.empty(max(npair, 1), dtype=torch.float32, device=self.device)
+        dq = torch.empty_like(dp)
+        users = torch.as_tensor(a.astype(np.int32)).to(self.device)
+        self.ctx.check(self.lib.poi_geoie_pair_distances(self.ctx.handle, _ptr(self.off), _ptr(self.p), _ptr(self.q), self.n_user, self.n_item,
+                                                         _ptr(self.coords), _ptr(self._cphi), _ptr(users), len(a), int(rows.sum()), npair,
+                                                         _ptr(dp), _ptr(dq), self._stream()))
+        return dp[:npair], dq[:npair]
+
+    def update_trained(self):
+        """GeoIE.py:104-112: the scoring snapshots trained_g / _h / _t / _z <- the live tables."""
+        for k in self.TABLES:
+            self._trained[k].copy_(getattr(self, k).t)
+        self._uvec = self._items_cat = None
+
+    # ---- evaluation (GeoIE.py:114-127) --------------------------------------------------------
+    @property
+    def kdim(self):
+        return 2 * self.dim
+
+    def user_vectors(self, norm=None):
+        """(n_user, 2 D) [trained_t[u] | m_u] (poi_geoie_user_vectors) for the snapshot; norm defaults to score_norm."""
+        norm = self.score_norm if norm is None else norm
+        out = torch.empty((self.n_user, 2 * self.dim), dtype=torch.float32, device=self.device)
+        P = self._gparams(self._trained)
+        self.ctx.check(self.lib.poi_geoie_user_vectors(self.ctx.handle, ctypes.byref(P), _ptr(self.off), _ptr(self.p), self.n_user, self.len_max,
+                                                       {"reference": 0, "count": 1}[norm], _ptr(out), self._stream()))
+        return out
+
+    def _items(self):
+        if self._items_cat is None:
+            self._items_cat = torch.cat([self._trained["z"], self._trained["h"]], 1).contiguous()
+        return self._items_cat
+
+    def _users_rows(self, start_end):
+        if self._uvec is None:
+            self._uvec = self.user_vectors()
+        ids, lo = self._ids(start_end)
+        return ids, self._rows(self._uvec, ids, lo).contiguous(), lo
+
+    def compute_sub_all_scores_device(self, start_end):
+        """GeoIE.py:117-127 -> (n, n_item) device tensor (the dead ulptai distances are not built)."""
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        out = torch.empty((n, self.n_item), dtype=torch.float32, device=self.device)
+        self.ctx.check(self.lib.poi_score_all(self.ctx.handle, _ptr(users), _ptr(self._items()), n, self.n_item, self.kdim, None, None,
+                                              _ptr(out), self._stream()))
+        return out
+
+    def compute_sub_topk(self, start_end, k, return_scores=False):
+        """Valuate.py:132-146 on the GeoIE scores through the fused top-K kernel: (n, k) int32 ids by descending score."""
+        if k > 32:
+            return self._topk_from_scores(start_end, k, return_scores)
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_scores else None
+        self.ctx.check(self.lib.poi_score_topk(self.ctx.handle, _ptr(users), _ptr(self._items()), n, self.n_item, self.kdim, None, None, int(k),
+                                               _ptr(idx), _ptr(sc), self._stream()))
+        return (idx, sc) if return_scores else idx
+
+    def compute_sub_auc_preference(self, start_end):
+        """GeoIE.py:114-115 returns zeros: AUC is always 0."""
+        ids, _ = self._ids(start_end)
+        return np.zeros((ids.numel(), self.tes_masks.shape[1]), bool)
