@@ -52,6 +52,8 @@ extern "C" {
 /* 9: new entry point poi_ctx_last_plan (existing entries unchanged). */
 /* additive to 9: GeoIE - new entry points poi_geoie_step, poi_geoie_pair_distances, poi_geoie_user_vectors and poi_geoie_params (existing
  * entries unchanged). */
+/* additive to 9: POI2Vec - new entry points poi_poi2vec_step, poi_poi2vec_scores, poi_poi2vec_topk and poi_poi2vec_params (existing
+ * entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -514,6 +516,64 @@ int poi_geoie_pair_distances(poi_ctx* ctx, const int32_t* off, const int32_t* p,
  * Timing name: "geoie_uvec". */
 int poi_geoie_user_vectors(poi_ctx* ctx, const poi_geoie_params* prm, const int32_t* off, const int32_t* p, int32_t n_user, int32_t len_max,
                            int32_t norm, float* out, void* stream);
+
+/* ---- POI2Vec (additive to ABI 9) - prog_poi2vec.py, public/POI2Vec.py, public/Load_Data_Poi2vec.py ----------------------------------
+ * Tables (POI2Vec.py:63-71): xu (n_user, D), wl (n_item + 1, D) whose last row is the zero pad row wl_m and never moves, pb (n_node, D),
+ * float32; D a multiple of 4 in [4, 128].  Tree tables (Load_Data_Poi2vec.py:96-130): routes (n_item + 1, 4, depth) int32 [leaf .. root],
+ * lrs (same shape) int8, probs (n_item + 1, 4) float32, row n_item = the pad row (routes[0], lrs[0], probs 0); rid (n_item + 1, 4) int32 =
+ * the left-to-right index of each route's leaf (bit d - 1 of it = the child taken at route position d: 0 left, lrs + 1; 1 right,
+ * lrs - 1); depth <= 31, the tree is perfect (n_node = 2^depth - 1). */
+typedef struct poi_poi2vec_params {
+  float* xu; float* wl; float* pb;
+  const int32_t* routes; const int8_t* lrs; const float* probs; const int32_t* rid;
+  int32_t n_user; int32_t n_item; int32_t n_node; int32_t depth; int32_t dim;
+} poi_poi2vec_params;
+/* One launch of n users, replacing Poi2vec.seq_train (POI2Vec.py:127-181, driver prog_poi2vec.py:160-164).  Data: CSR of CSR - user u's
+ * train positions are off[u] .. off[u+1]-1 of tgt (targets t_i); position x's context POIs are cidx[coff[x] .. coff[x+1]-1] (an id
+ * outside [0, n_item) is the reference's padding: it adds the zero row).  For a user with L >= 1 targets:
+ *   s_j = xu_u . wl_j (j < n_item),  log plu_j = s_j - logsumexp(s);   c_i = sum_{k in C_i} wl_k,  ind_i = ceil(|mean_d c_i|)
+ *   z_ird = pb[routes[t_i][r][d]] . c_i,  S_i = sum_r probs[t_i][r] prod_d (sigmoid(z_ird lrs[t_i][r][d]) ind_i),
+ *   paths_i = floor(1 - S_i) + S_i (ceil and floor carry no gradient; both are decided on float64 values),
+ *   loss_out[k] = upq = -(1 / L) sum_i (log plu_{t_i} + log paths_i),  cost = upq + lambda / 2 (|xu_u|^2 + |wl|^2)  (nothing on pb).
+ * wl moves by -alpha d cost / d wl: DENSE (the softmax term (softmax_j - count_j / L) xu_u and the decay of every row, plus the context
+ * term through c_i on the context rows); xu_u by -alpha d cost / d xu_u; pb by the reference's set_subtensor on pb[bidx]: PER OCCURRENCE
+ * new = old - alpha d cost / d (that occurrence), assigned in the flattened (i, r, d) order of the bidx padded to len_max, the last write
+ * on a node winning.  The padded positions i >= L route through routes[0] and write the old value back last: for a user with
+ * L < len_max no node on POI 0's four routes (the root among them) moves.  This is what CPU Theano computes.
+ * Batch semantics above (poi_ctx_set_batch_cap): every user at the launch-entry values; wl is touched by every accepted user (k = their
+ * number: it moves by min(k, cap) / k times their summed updates), an xu row by its user (k = its accepted occurrences in the launch), a
+ * pb row by the users whose collapsed write on it comes from a real position (a padding write is not a touch).  n == 1 at cap 1 is the
+ * reference step.  A user with an id out of range (users[k] outside [0, n_user), a target outside [0, n_item)), with L = 0 or with a
+ * non-finite loss (paths_i <= 0 included) is REJECTED: it moves nothing, its loss is NaN, it counts in no k and is counted once
+ * (poi_ctx_take_bad_ids); removing it from the launch leaves every other result bitwise equal.  No float atomics, every sum in launch
+ * order: identical launches give bitwise identical tables.  n_pos / n_ctx = the launch's totals of positions and context entries, known
+ * to the host (scratch is sized from them; no device-to-host sync); a launch whose totals do not match moves nothing and rejects every
+ * user.  Limits: at most 4096 users per launch; the collapse costs (4 L)^2 integer operations on one workgroup per user and the per-user
+ * sums run over L serially, so L is meant to stay within a few thousand; scratch is about 4 bytes x (256 n D + n n_item / 16) + 8 bytes x
+ * n_pos (4 depth + 2 D) + 20 bytes x (n_pos 4 depth + n_pos + n_ctx) (256 n D floats of dXU partial sums dominate: 512 MB at n = 4096,
+ * D = 128).  Timing names: "p2v_plan", "p2v_lse", "p2v_pos", "p2v_user", "p2v_sort", "p2v_pb", "p2v_dense",
+ * "p2v_sparse", "p2v_xu". */
+int poi_poi2vec_step(poi_ctx* ctx, const poi_poi2vec_params* prm, const int32_t* off, const int32_t* tgt, const int32_t* coff,
+                     const int32_t* cidx, const int32_t* users, int32_t n, int64_t n_pos, int64_t n_ctx, int32_t len_max, float alpha,
+                     float lambda, float* loss_out, void* stream);
+/* Poi2vecBasic.compute_sub_all_scores (POI2Vec.py:91-109) in factorised form.  Rows (user b, position t), b < n_batch, t < length, row
+ * r = b length + t with the explicit context row coff[r] .. coff[r+1]-1 of cidx (the caller picks the reference's train-table rows or
+ * the test contexts).  Per row: cl = sum of wl over the context; z_n = pb_n . cl for every node ONCE (float64), f = sigmoid(z_n lr)
+ * ceil(|z_n|); the product of f along each of the 2^(depth-1) distinct routes (leaf_nodes (n_leaf, depth) int32 [leaf .. root] of the
+ * leaf with left-to-right index l; lr from the bits of l); S_j = sum_r probs[j][r] product[rid[j][r]]; paths_j = floor(1 - S_j) + S_j;
+ * out[r][j] = paths_j plu[b][j], j < n_item, where plu = softmax of xu[users] . wl^T over the USERS of the batch (softmax_axis 0, the
+ * reference: POI2Vec.py:92, 183-186) or over the POIs (softmax_axis 1).  prm->xu / wl / pb are the snapshots to score.  A user id out of
+ * range gives NaN rows for that user only (its logits are left out of the softmax over the users).  Scratch: rows (n_node + n_leaf + D)
+ * float64 values + n_batch n_item floats.  Timing names: "p2v_sc_node", "p2v_sc_route", "p2v_sc_plu", "p2v_sc_out". */
+int poi_poi2vec_scores(poi_ctx* ctx, const poi_poi2vec_params* prm, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch,
+                       int32_t length, const int32_t* coff, const int32_t* cidx, int32_t softmax_axis, float* out, void* stream);
+/* The same scores reduced to the top k per row (k <= 64), fused into the score pass: a workgroup per row computes the scores on the fly
+ * (the row of scores is never stored) and keeps sorted candidate lists in LDS.  idx_out (rows, k) int32 by descending score, ties by
+ * ascending id, NaN scores last; score_out (rows, k) or NULL, bitwise the values poi_poi2vec_scores writes.  Timing name: "p2v_sc_topk"
+ * (in place of "p2v_sc_out"). */
+int poi_poi2vec_topk(poi_ctx* ctx, const poi_poi2vec_params* prm, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch,
+                     int32_t length, const int32_t* coff, const int32_t* cidx, int32_t softmax_axis, int32_t k, int32_t* idx_out,
+                     float* score_out, void* stream);
 
 /* ---- multi-GPU reconciliation (8e; new - the reference is single-process) ----------------------
  * Users are sharded across ranks, every rank trains on a full parameter replica with no data-path collective,

@@ -36,6 +36,10 @@ class GeoieParams(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("g", "h", "t", "z", "ab")] + [("n_user", c_int32), ("n_item", c_int32), ("dim", c_int32)]
 
 
+class Poi2vecParams(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("xu", "wl", "pb", "routes", "lrs", "probs", "rid")] + [(n, c_int32) for n in ("n_user", "n_item", "n_node", "depth", "dim")]
+
+
 class SyncSeg(ctypes.Structure):
     _fields_ = [("cur", c_void_p), ("rows", c_int64), ("width", c_int64), ("rule", c_int32), ("dtype", c_int32)]
 
@@ -121,6 +125,12 @@ SIGNATURES = {
     "poi_geoie_pair_distances": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                          c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "poi_geoie_user_vectors": (c_int, [c_void_p, POINTER(GeoieParams), c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "poi_poi2vec_step": (c_int, [c_void_p, POINTER(Poi2vecParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64,
+                                 c_int32, c_float, c_float, c_void_p, c_void_p]),
+    "poi_poi2vec_scores": (c_int, [c_void_p, POINTER(Poi2vecParams), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                   c_void_p]),
+    "poi_poi2vec_topk": (c_int, [c_void_p, POINTER(Poi2vecParams), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32,
+                                 c_void_p, c_void_p, c_void_p]),
     "poi_delta_make": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_delta_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_comm_available": (c_int, []),

@@ -90,6 +90,8 @@ struct poi_ctx {
   DevBuf pr_ws;
   // GeoIE step / pair distances: plan, per-row and per-user values, touch gradients, sort buffers, new-row slots
   DevBuf ge_ws;
+  // POI2Vec step / scoring scratch
+  DevBuf pv_ws, pv_sc;
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)
@@ -225,7 +227,7 @@ int poi_ctx_destroy(poi_ctx* c) {
   if (!c) return POI_OK;
   DevBuf* all[] = {&c->ex_ws, &c->ex_slab, &c->ex_glt, &c->ex_gdi, &c->ws, &c->slab, &c->te_ws, &c->hslab, &c->zrow, &c->g_lt, &c->mult_lt, &c->nseq_lt, &c->g_di, &c->mult_di, &c->nseq_di, &c->seg_s, &c->seg_e, &c->pmark, &c->xc, &c->kc_dev, &c->uidx_stage, &c->out_stage, &c->ptab, &c->iota, &c->xw, &c->xg, &c->xflag, &c->bad_ids,
                    &c->g_wd, &c->mult_wd, &c->nseq_wd, &c->ca_ws, &c->ca_slab, &c->ca_scr, &c->ca2, &c->g_ux, &c->cnt_ux, &c->g_blt, &c->cnt_blt, &c->cand_s, &c->cand_i, &c->items_pk, &c->gbound, &c->st,
-                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws};
+                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc};
   (void)hipDeviceSynchronize();
   c->tm.clear();
   drop_graphs(c);
@@ -1120,6 +1122,112 @@ int poi_geoie_user_vectors(poi_ctx* c, const poi_geoie_params* P, const int32_t*
   HIPCHK(c, poi::launch_geoie_uvec(P->g, P->t, off, p, n_user, P->n_item, P->dim, len_max, norm, out, c->num_cu, st));
   c->tm.end(st);
   return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// POI2Vec (poi2vec.hip)
+static int poi2vec_check(poi_ctx* c, const poi_poi2vec_params* P, const char* who) {
+  if (!c || !P || !P->xu || !P->wl || !P->pb || !P->routes || !P->lrs || !P->probs || !P->rid) return fail(c, POI_EINVAL, "%s: NULL argument", who);
+  if (is_f16(c, P->xu) || is_f16(c, P->wl) || is_f16(c, P->pb)) return fail(c, POI_ENOTSUP, "POI2Vec tables are float32 only");
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 128) return fail(c, POI_ENOTSUP, "POI2Vec: dim must be a multiple of 4 in [4, 128] (got %d)", P->dim);
+  if (P->depth < 1 || P->depth > 31) return fail(c, POI_ENOTSUP, "POI2Vec: depth must lie in [1, 31] (got %d)", P->depth);
+  if (P->n_user <= 0 || P->n_item <= 0 || (int64_t)P->n_node != ((int64_t)1 << P->depth) - 1)
+    return fail(c, POI_EINVAL, "%s: bad sizes (n_node must be 2^depth - 1)", who);
+  return POI_OK;
+}
+
+struct Carver {
+  char* base; size_t used = 0;
+  explicit Carver(void* p) : base((char*)p) {}
+  void* bytes(size_t b) { void* r = base ? (void*)(base + used) : nullptr; used += (b + 255) & ~(size_t)255; return r; }
+};
+
+static void poi2vec_carve(poi::P2vArgs& A, Carver& W, int n_slot) {
+  const size_t n = (size_t)A.n, P = (size_t)A.n_pos, R = 4 * (size_t)A.depth, D = (size_t)A.dim, E = P * R + 64, T = P + (size_t)A.n_ctx + 64;
+  A.ubad = (int*)W.bytes(sizeof(int) * (n + 1)); A.acc = (int*)W.bytes(sizeof(int) * (n + 1)); A.lpos = (int*)W.bytes(sizeof(int) * (n + 1)); A.lctx = (int*)W.bytes(sizeof(int) * (n + 1));
+  A.tot = (int*)W.bytes(sizeof(int) * (8)); A.cnt = (int*)W.bytes(sizeof(int) * (8));
+  A.pmax = (float*)W.bytes(sizeof(float) * (n * A.n_tile + 1)); A.psum = (double*)W.bytes(sizeof(double) * (n * A.n_tile + 1));
+  A.posval = (double*)W.bytes(sizeof(double) * (P + 1)); A.gz = (double*)W.bytes(sizeof(double) * (P * R + 1)); A.cbuf = (double*)W.bytes(sizeof(double) * (P * D + 1)); A.gcbuf = (double*)W.bytes(sizeof(double) * (P * D + 1));
+  A.lse = (double*)W.bytes(sizeof(double) * (n + 1)); A.tsum = (double*)W.bytes(sizeof(double) * (n * D + 1)); A.scale = (float*)W.bytes(sizeof(float) * (8)); A.dxu = (float*)W.bytes(sizeof(float) * ((size_t)n_slot * n * D + 1));
+  A.keys0 = (int*)W.bytes(sizeof(int) * (E)); A.keys1 = (int*)W.bytes(sizeof(int) * (E)); A.vals0 = (int*)W.bytes(sizeof(int) * (E)); A.vals1 = (int*)W.bytes(sizeof(int) * (E));
+  A.k2a = (int*)W.bytes(sizeof(int) * (T)); A.k2b = (int*)W.bytes(sizeof(int) * (T)); A.v2a = (int*)W.bytes(sizeof(int) * (T)); A.v2b = (int*)W.bytes(sizeof(int) * (T)); A.epos = (int*)W.bytes(sizeof(int) * (T));
+  A.hist = (int*)W.bytes(sizeof(int) * ((size_t)RS_HIST_INTS + RS_MAXBIN + 64));
+}
+
+int poi_poi2vec_step(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* off, const int32_t* tgt, const int32_t* coff, const int32_t* cidx,
+                     const int32_t* users, int32_t n, int64_t n_pos, int64_t n_ctx, int32_t len_max, float alpha, float lambda, float* loss_out,
+                     void* stream) {
+  int rc = poi2vec_check(c, P, "poi_poi2vec_step");
+  if (rc) return rc;
+  if (!off || !tgt || !coff || !cidx || !users || !loss_out) return fail(c, POI_EINVAL, "poi_poi2vec_step: NULL argument");
+  if (n < 0 || n_pos < 0 || n_ctx < 0 || len_max < 0) return fail(c, POI_EINVAL, "poi_poi2vec_step: bad sizes");
+  if (n > 4096) return fail(c, POI_ENOTSUP, "POI2Vec: at most 4096 users per launch (got %d)", n);
+  if (n_pos * 4 * P->depth >= ((int64_t)1 << 31) - 64 || n_pos + n_ctx >= ((int64_t)1 << 31) - 64)
+    return fail(c, POI_ENOTSUP, "POI2Vec: a launch's route occurrences (4 depth per position) and context entries must stay below 2^31");
+  if (c->batch_cap == 0.0f) return fail(c, POI_ENOTSUP, "the mini-batch rule (batch cap 0) applies to poi_gru_step / poi_spatial_step only");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::P2vArgs A;
+  memset(&A, 0, sizeof A);
+  A.xu = P->xu; A.wl = P->wl; A.pb = P->pb; A.routes = P->routes; A.lrs = (const signed char*)P->lrs; A.probs = P->probs; A.rid = P->rid;
+  A.n_user = P->n_user; A.n_item = P->n_item; A.n_node = P->n_node; A.depth = P->depth; A.dim = P->dim;
+  A.off = off; A.tgt = tgt; A.coff = coff; A.cidx = cidx; A.users = users;
+  A.n = n; A.n_pos = (int)n_pos; A.n_ctx = (int)n_ctx; A.len_max = len_max; A.n_tile = (P->n_item + 63) / 64;
+  A.alpha = alpha; A.lambda = lambda; A.bcap = c->batch_cap; A.loss = loss_out;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  const int n_slot = A.n_tile < 256 ? A.n_tile : 256;
+  Carver dry(nullptr);
+  poi2vec_carve(A, dry, n_slot);
+  if ((rc = ensure(c, c->pv_ws, dry.used + 256, st))) return rc;
+  Carver W(c->pv_ws.p);
+  poi2vec_carve(A, W, n_slot);
+  HIPCHK(c, poi::launch_poi2vec_step(A, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+static int poi2vec_score_common(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch,
+                                int32_t length, const int32_t* coff, const int32_t* cidx, int32_t axis, int32_t k, float* out, int32_t* idx_out,
+                                float* score_out, void* stream, const char* who) {
+  int rc = poi2vec_check(c, P, who);
+  if (rc) return rc;
+  if (!leaf_nodes || !users || !coff || !cidx) return fail(c, POI_EINVAL, "%s: NULL argument", who);
+  if (n_batch < 0 || length < 0 || (axis != 0 && axis != 1)) return fail(c, POI_EINVAL, "%s: bad sizes or softmax_axis", who);
+  if ((int64_t)n_batch * length >= ((int64_t)1 << 31) / 4) return fail(c, POI_ENOTSUP, "%s: too many rows", who);
+  if (n_batch == 0 || length == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::P2vScoreArgs A;
+  memset(&A, 0, sizeof A);
+  A.xu = P->xu; A.wl = P->wl; A.pb = P->pb; A.probs = P->probs; A.rid = P->rid; A.leaf_nodes = leaf_nodes; A.users = users; A.coff = coff; A.cidx = cidx;
+  A.n_user = P->n_user; A.n_item = P->n_item; A.n_node = P->n_node; A.depth = P->depth; A.dim = P->dim;
+  A.n_batch = n_batch; A.length = length; A.n_rows = n_batch * length; A.axis = axis; A.k = k;
+  const size_t rows = (size_t)A.n_rows, NL = (size_t)1 << (P->depth - 1);
+  for (int pass = 0; pass < 2; ++pass) {
+    Carver W(pass ? c->pv_sc.p : nullptr);
+    A.cl = (double*)W.bytes(sizeof(double) * (rows * P->dim)); A.zf = (double*)W.bytes(sizeof(double) * (rows * P->n_node)); A.rp = (double*)W.bytes(sizeof(double) * (rows * NL));
+    const size_t ns = (size_t)(axis == 0 ? P->n_item : n_batch);
+    A.ssum = (double*)W.bytes(sizeof(double) * (ns)); A.smax = (float*)W.bytes(sizeof(float) * (ns)); A.logit = (float*)W.bytes(sizeof(float) * ((size_t)n_batch * P->n_item));
+    A.out = out;                                     // NULL for the top-K: the scores are not stored
+    if (!pass && (rc = ensure(c, c->pv_sc, W.used + 256, st))) return rc;
+  }
+  A.idx_out = idx_out; A.score_out = score_out;
+  HIPCHK(c, poi::launch_poi2vec_scores(A, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_poi2vec_scores(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch, int32_t length,
+                       const int32_t* coff, const int32_t* cidx, int32_t softmax_axis, float* out, void* stream) {
+  if (c && !out) return fail(c, POI_EINVAL, "poi_poi2vec_scores: NULL argument");
+  return poi2vec_score_common(c, P, leaf_nodes, users, n_batch, length, coff, cidx, softmax_axis, 0, out, nullptr, nullptr, stream, "poi_poi2vec_scores");
+}
+
+int poi_poi2vec_topk(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch, int32_t length,
+                     const int32_t* coff, const int32_t* cidx, int32_t softmax_axis, int32_t k, int32_t* idx_out, float* score_out, void* stream) {
+  if (c && !idx_out) return fail(c, POI_EINVAL, "poi_poi2vec_topk: NULL argument");
+  if (c && P && (k < 1 || k > 64 || k > P->n_item)) return fail(c, POI_EINVAL, "poi_poi2vec_topk: k must lie in [1, min(64, n_item)]");
+  return poi2vec_score_common(c, P, leaf_nodes, users, n_batch, length, coff, cidx, softmax_axis, k, nullptr, idx_out, score_out, stream, "poi_poi2vec_topk");
 }
 
 // ---------------------------------------------------------------------------------------------

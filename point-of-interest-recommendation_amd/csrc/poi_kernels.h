@@ -434,6 +434,31 @@ hipError_t launch_geoie_pairs(GeoieArgs& A, int num_cu, hipStream_t st);
 hipError_t launch_geoie_uvec(const float* g, const float* t, const int* off, const int* p, int n_user, int n_item, int dim, int len_max,
                              int norm, float* out, int num_cu, hipStream_t st);
 
+// POI2Vec (poi2vec.hip)
+struct P2vArgs {
+  float *xu, *wl, *pb;              // (n_user, D), (n_item [+ pad], D), (n_node, D)
+  const int* routes; const signed char* lrs; const float* probs; const int* rid;      // (n_item + 1, 4, depth) x 2, (n_item + 1, 4) x 2
+  int n_user, n_item, n_node, depth, dim;
+  const int *off, *tgt, *coff, *cidx, *users;      // CSR of CSR: user -> positions -> context POIs; launch users (n)
+  int n, n_pos, n_ctx, len_max, n_tile;            // host totals of the launch's positions and context entries; 64-item tiles
+  float alpha, lambda, bcap;
+  float* loss;                      // (n) upq per user
+  int* bad;                         // device counter of rejected users (poi_ctx_take_bad_ids)
+  int *ubad, *acc, *lpos, *lctx, *tot, *cnt;       // per user: bad flag, accepted, position / context offsets; {mismatch, k}; sort counts
+  float* pmax; double* psum;        // (n, n_tile) per-tile max / sum of exp of the logits
+  double *posval, *gz, *cbuf, *gcbuf, *lse, *tsum; // per position: s_t + log paths, (4 depth) d / d z, c_i, d / d c_i; per user: lse, sum of target rows
+  float *scale, *dxu;               // alpha min(k, cap) / k; (slots, n, D) partial sums of dXU
+  int *keys0, *keys1, *vals0, *vals1, *k2a, *k2b, *v2a, *v2b, *epos, *hist;
+  const int *ks, *vs, *k2s, *v2s;
+};
+struct P2vScoreArgs {
+  const float *xu, *wl, *pb, *probs; const int *rid, *leaf_nodes, *users, *coff, *cidx;
+  int n_user, n_item, n_node, depth, dim, n_batch, length, n_rows, axis, k;
+  double *cl, *zf, *rp, *ssum; float *logit, *smax, *out, *score_out; int* idx_out;
+};
+hipError_t launch_poi2vec_step(P2vArgs& A, int num_cu, hipStream_t st, Timing* tm);
+hipError_t launch_poi2vec_scores(P2vScoreArgs& A, int num_cu, hipStream_t st, Timing* tm);
+
 // scoring / top-K
 struct ScoreArgs {
   const float *users, *items; int items_f16;      // items: float32, or IEEE half when items_f16

@@ -614,3 +614,221 @@ def geoie_pair_distances(coords, off, p, q, users=None):
         dp[poff[k]:poff[k + 1]] = geoie_cal_dis(src[:, 0], src[:, 1], tp[:, 0], tp[:, 1])
         dq[poff[k]:poff[k + 1]] = geoie_cal_dis(src[:, 0], src[:, 1], tq[:, 0], tq[:, 1])
     return dp, dq, poff, rows
+
+
+# ---- POI2Vec (public/Load_Data_Poi2vec.py) ----------------------------------------------------------------------------------------
+def poi2vec_region_tree(coords, theta):
+    """The binary region tree of Load_Data_Poi2vec.py:152-247 (Treenode.build / route / overlap) over POI coordinates (n_item, 2) lat, lon,
+    and the per-POI route tables of preprocess (:96-125).  Root box = (min lat, max lat, max lon, min lon); a node halves its longer side
+    (latitude when strictly longer, else longitude) while that side > 2 theta, else it is a leaf.  Node ids follow the constructor order:
+    root 0; a splitting node's children take the next two ids, then the left subtree is built before the right one.  Every level is built
+    at once here (all nodes of a level have the same size, so the tree is perfect: ValueError if the arithmetic says otherwise, or if the
+    box has an empty side), each node with the reference's own expressions for its bounds.
+    Returns a dict: n_node, n_leaf, depth, routes (n_item + 1, 4, depth) int32 [leaf, .., root], lrs (same shape, int8: 1 at the leaf, then
+    +1 / -1 for the left (lower latitude / upper longitude) / right child taken at each ancestor), probs (n_item + 1, 4) float32, rid
+    (n_item + 1, 4) int32 = the leaf's left-to-right index (its ancestor at level l is node_ids[l][rid >> (depth - 1 - l)]), node_ids (list
+    per level) and leaf_box (n_leaf, 4) left, right, up, down; row n_item is the pad row: routes[0], lrs[0], probs 0 (:128-130)."""
+    xy = np.asarray(coords, np.float64).reshape(-1, 2)
+    theta = float(theta)
+    if not theta > 0 or len(xy) == 0:
+        raise ValueError("poi2vec_region_tree: theta must be > 0 and coords non-empty")
+    L, R, U, Dn = (np.array([v]) for v in (xy[:, 0].min(), xy[:, 0].max(), xy[:, 1].max(), xy[:, 1].min()))
+    if not (R[0] > L[0] and U[0] > Dn[0]):
+        raise ValueError("poi2vec_region_tree: the bounding box of the coordinates has an empty side")
+    levels = []
+    while True:
+        lat_split = (R - L) > (U - Dn)                                     # :171
+        split = np.where(lat_split, (R - L) > 2 * theta, (U - Dn) > 2 * theta)
+        if split.any() != split.all() or (split.all() and lat_split.any() != lat_split.all()):
+            raise ValueError("poi2vec_region_tree: the nodes of level %d do not split alike (the tree is not perfect)" % len(levels))
+        levels.append(dict(L=L, R=R, U=U, D=Dn, lat=bool(lat_split[0]) if split[0] else None))
+        if not split[0]:
+            break
+        if len(levels) > 30:
+            raise ValueError("poi2vec_region_tree: more than 2^30 leaves")
+        n = len(L)
+        nl, nr, nu, nd = (np.empty(2 * n) for _ in range(4))
+        if lat_split[0]:                                                   # :174-176
+            nl[0::2], nr[0::2], nl[1::2], nr[1::2] = L, (L + R) / 2, (R + L) / 2, R
+            nu[0::2] = nu[1::2] = U; nd[0::2] = nd[1::2] = Dn
+        else:                                                              # :184-186
+            nl[0::2] = nl[1::2] = L; nr[0::2] = nr[1::2] = R
+            nu[0::2], nd[0::2], nu[1::2], nd[1::2] = U, (U + Dn) / 2, (U + Dn) / 2, Dn
+        L, R, U, Dn = nl, nr, nu, nd
+    depth = len(levels)
+    # numbering: a node with h levels below it and child counter c has children c, c + 1; its left child's counter is c + 2, its right
+    # child's c + 2 + (2^h - 2) (the left subtree below the left child holds 2^h - 2 nodes)
+    ids, cs = np.array([0], np.int64), np.array([1], np.int64)
+    node_ids = [ids]
+    for lv in range(depth - 1):
+        h = depth - 1 - lv
+        nid, ncs = np.empty(2 * len(ids), np.int64), np.empty(2 * len(ids), np.int64)
+        nid[0::2], nid[1::2] = cs, cs + 1
+        ncs[0::2], ncs[1::2] = cs + 2, cs + (1 << h)
+        ids, cs = nid, ncs
+        node_ids.append(ids)
+    n_leaf = 1 << (depth - 1)
+    n_node = 2 * n_leaf - 1
+    # routes of the 4 corners of every POI (:99-112)
+    n_item = len(xy)
+    lat, lon = xy[:, 0], xy[:, 1]
+    cl = np.stack([lat - 0.5 * theta, lat - 0.5 * theta, lat + 0.5 * theta, lat + 0.5 * theta], 1)
+    co = np.stack([lon - 0.5 * theta, lon + 0.5 * theta, lon - 0.5 * theta, lon + 0.5 * theta], 1)
+    k = np.zeros((n_item, 4), np.int64)
+    for lv in range(depth - 1):
+        ch = levels[lv + 1]
+        if levels[lv]["lat"]:
+            right = ch["R"][2 * k] < cl                                    # :213 left_child.right < latitude
+        else:
+            right = ch["D"][2 * k] > co                                    # :222 left_child.down > longitude
+        k = 2 * k + right
+    routes = np.empty((n_item + 1, 4, depth), np.int32)
+    lrs = np.ones((n_item + 1, 4, depth), np.int8)
+    for d in range(depth):
+        routes[:n_item, :, d] = node_ids[depth - 1 - d][k >> d]
+        if d >= 1:
+            lrs[:n_item, :, d] = 1 - 2 * ((k >> (d - 1)) & 1)
+    lf = levels[-1]
+    left = np.maximum(lat[:, None] - 0.5 * theta, lf["L"][k])              # :161-166
+    right = np.minimum(lat[:, None] + 0.5 * theta, lf["R"][k])
+    up = np.minimum(lon[:, None] + 0.5 * theta, lf["U"][k])
+    down = np.maximum(lon[:, None] - 0.5 * theta, lf["D"][k])
+    area = (right - left) * (up - down)
+    for r in range(1, 4):                                                  # :108-111: a route seen at an earlier corner counts once
+        seen = np.zeros(n_item, bool)
+        for r0 in range(r):
+            seen |= k[:, r0] == k[:, r]
+        area[seen, r] = 0
+    probs = np.zeros((n_item + 1, 4), np.float32)
+    probs[:n_item] = area / area.sum(axis=1, keepdims=True)
+    rid = np.empty((n_item + 1, 4), np.int32)
+    rid[:n_item] = k
+    routes[n_item], lrs[n_item], rid[n_item] = routes[0], lrs[0], rid[0]
+    return dict(n_node=int(n_node), n_leaf=int(n_leaf), depth=int(depth), routes=routes, lrs=lrs, probs=probs, rid=rid,
+                node_ids=[a.astype(np.int32) for a in node_ids],
+                leaf_box=np.stack([lf["L"], lf["R"], lf["U"], lf["D"]], 1), theta=theta)
+
+
+@dataclasses.dataclass
+class Poi2vecDataset:
+    """What Load_Data_Poi2vec.preprocess / load_data / fun_data_masks hand to prog_poi2vec.py, contexts as CSR of CSR instead of the table
+    padded to the longest context: user u's train positions are off[u] .. off[u+1]-1 of tra_t (targets); position x's context POIs are
+    tra_c[tra_coff[x] .. tra_coff[x+1]-1]; the same on the test side."""
+    n_user: int
+    n_item: int
+    n_node: int
+    depth: int
+    coords: np.ndarray          # (n_item, 2) float64 lat, lon
+    off: np.ndarray             # (n_user + 1,) int32
+    tra_t: np.ndarray           # flat int32 train targets
+    tra_coff: np.ndarray        # (n_pos + 1,) int32
+    tra_c: np.ndarray           # flat int32 train context POIs
+    tes_off: np.ndarray
+    tes_t: np.ndarray
+    tes_coff: np.ndarray
+    tes_c: np.ndarray
+    routes: np.ndarray          # (n_item + 1, 4, depth) int32
+    lrs: np.ndarray             # (n_item + 1, 4, depth) int8
+    probs: np.ndarray           # (n_item + 1, 4) float32
+    rid: np.ndarray             # (n_item + 1, 4) int32 left-to-right leaf index of each route
+    theta: float = 0.1
+
+    @property
+    def lens(self):
+        return np.diff(np.asarray(self.off, np.int64))
+
+    @property
+    def len_max(self):
+        return int(self.lens.max()) if self.n_user else 0
+
+    def tes_padded(self):
+        """(tes_target_masks, tes_masks) of fun_data_masks (Load_Data_Poi2vec.py:133-139): targets padded with n_item."""
+        tl = np.diff(np.asarray(self.tes_off, np.int64))
+        lt = int(tl.max()) if self.n_user else 0
+        mask = (np.arange(lt)[None, :] < tl[:, None]).astype(np.int32)
+        p = np.full((self.n_user, lt), self.n_item, np.int32)
+        p[mask.astype(bool)] = self.tes_t
+        return p, mask
+
+
+def poi2vec_contexts(times, time_threshold):
+    """Load_Data_Poi2vec.py:56-69 for one user: for check-in j the earlier check-ins k = j-1, j-2, .. while t_j - t_k < time_threshold
+    (stopping at the first that fails).  Returns the list of index lists (nearest first; only the multiset matters: contexts are summed)."""
+    out = []
+    for j in range(len(times)):
+        ctx = []
+        for k in range(j - 1, -1, -1):
+            if times[j] - times[k] < time_threshold:
+                ctx.append(k)
+            else:
+                break
+        out.append(ctx)
+    return out
+
+
+def _poi2vec_from_lists(seqs, times, cods, split, time_threshold, region_threshold, where="input"):
+    s1 = float(split[1])
+    alias, coord_of = {}, {}
+    for upois, ucods in zip(seqs, cods):
+        for s_, c_ in zip(upois, ucods):
+            if s_ not in alias:
+                alias[s_] = len(alias)                                     # every POI of the file (:45, :81-82)
+            coord_of[s_] = c_                                              # :43-44: the last occurrence in the file
+    n_user, n_item = len(seqs), len(alias)
+    coords = np.zeros((n_item, 2), np.float64)
+    for s_, a_ in alias.items():
+        coords[a_] = coord_of[s_]
+    sides = {"tra": ([0], [], [0], []), "tes": ([0], [], [0], [])}
+    for upois, ut in zip(seqs, times):
+        le = len(upois)
+        if len(ut) != le:
+            raise ValueError("%s: a user with %d POIs and %d times" % (where, le, len(ut)))
+        split1, split2 = int(le * s1 - 1), int(le * s1)                    # :56
+        ids = [alias[s_] for s_ in upois]
+        ctx = poi2vec_contexts(ut, time_threshold)
+        for name, idx in (("tra", list(range(le))[0:split1]), ("tes", list(range(le))[split1:split2])):
+            off, t, coff, c = sides[name]
+            for j in idx:
+                t.append(ids[j])
+                c.extend(ids[k] for k in ctx[j])
+                coff.append(len(c))
+            off.append(len(t))
+    tree = poi2vec_region_tree(coords, region_threshold)
+    i32 = lambda v: np.asarray(v, np.int32)
+    ds = Poi2vecDataset(n_user=n_user, n_item=n_item, n_node=tree["n_node"], depth=tree["depth"], coords=coords,
+                        off=i32(sides["tra"][0]), tra_t=i32(sides["tra"][1]), tra_coff=i32(sides["tra"][2]), tra_c=i32(sides["tra"][3]),
+                        tes_off=i32(sides["tes"][0]), tes_t=i32(sides["tes"][1]), tes_coff=i32(sides["tes"][2]), tes_c=i32(sides["tes"][3]),
+                        routes=tree["routes"], lrs=tree["lrs"], probs=tree["probs"], rid=tree["rid"], theta=float(region_threshold))
+    return ds, alias
+
+
+def load_poi2vec_sequence_file(path, split=(0.8, 1.0), time_threshold=360, region_threshold=0.1, return_aliases=False):
+    """Load_Data_Poi2vec.preprocess (:35-131) on the ETL's sequence file, into a Poi2vecDataset:
+      * split1 = int(le * split[1] - 1), split2 = int(le * split[1]); train targets [0:split1], test targets [split1:split2] (split[0] is
+        unused, as in the reference);
+      * n_item counts every POI of the file; a POI's coordinate is the one of its last occurrence;
+      * contexts: poi2vec_contexts on the integer check-in times; the tree and the route tables: poi2vec_region_tree.
+    Aliases: order of first appearance in the file instead of the reference's set() iteration order - a relabelling of the same data."""
+    import pandas as pd
+    tab = pd.read_csv(path, sep=" ")
+    seqs = [str(s).split("/") for s in tab["u_pois"]]
+    times = [[int(v) for v in str(s).split("/")] for s in tab["u_times"]]
+    cods = [[tuple(float(v) for v in c.split(",")) for c in str(s).split("/")] for s in tab["u_coordinates"]]
+    ds, alias = _poi2vec_from_lists(seqs, times, cods, split, time_threshold, region_threshold, where=str(path))
+    return (ds, alias) if return_aliases else ds
+
+
+def make_poi2vec_synthetic(n_user, n_item, max_len, seed, far_frac=0.3, time_threshold=360, region_threshold=0.1, split=(0.8, 1.0), **kw):
+    """make_prme_synthetic's check-ins and times (make_synthetic's lengths, popularity and optional locality `local=`; gaps above
+    time_threshold minutes with probability far_frac), split and numbered as load_poi2vec_sequence_file does."""
+    base = make_synthetic(n_user, n_item, max_len, seed, **kw)
+    rng = np.random.default_rng(seed + 1)
+    off = np.asarray(base.off, np.int64)
+    seqs, times, cods = [], [], []
+    for u in range(n_user):
+        s = np.concatenate([base.tra_p[off[u]:off[u + 1]], base.tes_p[u:u + 1]])
+        g = np.where(rng.random(len(s)) < far_frac, rng.integers(time_threshold + 1, 10 * time_threshold, len(s)),
+                     rng.integers(1, time_threshold + 1, len(s)))
+        g[0] = 0
+        seqs.append(s.tolist()); times.append(np.cumsum(g).astype(np.int64).tolist()); cods.append([tuple(base.coords[i]) for i in s])
+    return _poi2vec_from_lists(seqs, times, cods, split, time_threshold, region_threshold, where="make_poi2vec_synthetic")[0]

@@ -370,3 +370,86 @@ def train_geoie(ds, p=None, device="cuda:0", log=print):
         log("epoch %d  sum_loss = %.3f = %.3f + %.3f  a %.6f  b %.6f  rejected users %d  auc %.4f  recall@%d %.4f  time (train, test) %.2fs %.2fs"
             % (epoch, loss + l2, loss, l2, a, b, rejected, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1))
     return model, best, history
+
+
+def poi2vec_default_params():
+    """The in-source config of prog_poi2vec.py:46-66 (+ `batch`: users per launch - 1 is the reference's one-by-one training -, seed, and the
+    two scoring switches of models.OboPoi2vec, default = what the reference computes)."""
+    return dict(dataset="Gowalla.txt", mode="test", regionThreshold=0.1, timeThreshold=360, split=[0.8, 1.0], at_nums=[5, 10, 15, 20], epochs=100,
+                latent_size=20, initial_alpha=1, initial_loss=25000, alpha=0.01, **{"lambda": 0.001}, mini_batch=0, poi2vec=0,
+                batch_size_train=4, batch_size_test=25, batch=1, seed=123, softmax_axis="reference", eval_context="reference")
+
+
+def poi2vec_model(ds, p=None, device="cuda:0"):
+    """build_model_one_by_one of prog_poi2vec.py:92-113 on a data.Poi2vecDataset (alpha starts at initial_alpha)."""
+    p = dict(poi2vec_default_params(), **(p or {}))
+    return models.OboPoi2vec(train=ds, test=None, alpha_lambda=[p["initial_alpha"], p["lambda"]], n_user=ds.n_user, n_item=ds.n_item,
+                             n_node=ds.n_node, n_size=p["latent_size"], probs=ds.probs, routes=ds.routes, lrs=ds.lrs, device=device,
+                             seed=p.get("seed"), softmax_axis=p["softmax_axis"], eval_context=p["eval_context"])
+
+
+def poi2vec_recall(model, ds, p, at_nums):
+    """The top-K metrics of Valuate.py:132-191 over batches of p['batch_size_test'] users, batch by batch (with softmax_axis 'reference' the
+    scores depend on the batch: the ranges are not merged), accumulated on the device (poi_rank_metrics)."""
+    from .evaluate import device_rank_metrics
+    p = dict(poi2vec_default_params(), **(p or {}))
+    if model.tes_len_max != 1:
+        raise ValueError("the evaluation expects one test position per user (split [.., 1.0]); found %d" % model.tes_len_max)
+    tot = None
+    for se in compute_start_end(ds.n_user, p["batch_size_test"]):
+        m = device_rank_metrics(model, [se], at_nums)
+        if tot is None:
+            tot = {k: dict(hits=0.0, map=0.0, ndcg=0.0) for k in at_nums}
+        for k in at_nums:
+            tot[k]["hits"] += m[k]["hits"]; tot[k]["map"] += m[k]["map"] * model.n_user; tot[k]["ndcg"] += m[k]["ndcg"] * model.n_user
+    denom = float(model.tes_masks.sum().item())
+    out = {}
+    for k in at_nums:
+        rec, pre = tot[k]["hits"] / denom, tot[k]["hits"] / (k * model.n_user)
+        out[k] = dict(hits=tot[k]["hits"], recall=rec, precision=pre, f1=2.0 * rec * pre / (rec + pre) if rec + pre > 0 else 0.0,
+                      map=tot[k]["map"] / model.n_user, ndcg=tot[k]["ndcg"] / model.n_user)
+    return out
+
+
+def train_poi2vec(ds, p=None, device="cuda:0", log=print):
+    """train_valid_or_test of prog_poi2vec.py:138-207 on a data.Poi2vecDataset: OboPoi2vec at alpha = initial_alpha, then per epoch: users
+    shuffled, launches of p['batch'] users, the sum_loss line (sum of upq + l2), update_trained_params, AUC (always 0, as the reference)
+    and the top-K metrics into GlobalBest; after the epoch alpha is divided by 10 when the epoch loss rose above the previous one (the
+    first comparison is against initial_loss) and alpha >= 10 p['alpha'] (:196-199).  Rejected users are logged, not raised; their losses
+    are left out of the sum.  Returns (model, best, history)."""
+    p = dict(poi2vec_default_params(), **(p or {}))
+    model = poi2vec_model(ds, p, device)
+    best = GlobalBest(p["at_nums"])
+    U = ds.n_user
+    B = max(1, int(p.get("batch", 1)))
+    pre_loss, lr_min = float(p["initial_loss"]), float(p["alpha"])
+    history = []
+    for epoch in range(p["epochs"]):
+        t0 = time.time()
+        order = np.random.default_rng(123 + epoch).permutation(U)   # :158-161
+        model.ctx.take_bad_ids(model._stream().value)
+        parts = [model.train_batch(order[s:s + B], sync=False) for s in range(0, U, B)]      # :162-164 (B = 1: one user per call)
+        rejected = model.ctx.take_bad_ids(model._stream().value)
+        model.rejected += rejected
+        losses = torch.cat(parts).double() if parts else torch.zeros(0, dtype=torch.float64)
+        loss = float(torch.nan_to_num(losses, nan=0.0).sum().item())
+        l2 = model.l2.eval()                                        # :165
+        t1 = time.time()
+        model.update_trained_params()                               # :173
+        at = poi2vec_recall(model, ds, p, p["at_nums"])            # :178-180
+        for i, k in enumerate(p["at_nums"]):
+            for name, key in (("recall", "recall"), ("precis", "precision"), ("f1scor", "f1"), ("map", "map"), ("ndcg", "ndcg")):
+                cur = getattr(best, "best_" + name)
+                if at[k][key] > cur[i]:
+                    cur[i] = at[k][key]
+                    getattr(best, "best_epoch_" + name)[i] = epoch
+        t2 = time.time()
+        lr = model.alpha_lambda[0]
+        history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=0.0, recall={k: at[k]["recall"] for k in p["at_nums"]}, alpha=lr,
+                            rejected=rejected, times=(t1 - t0, t2 - t1)))
+        log("epoch %d  sum_loss = %.3f = %.3f + %.3f  alpha %g  rejected users %d  auc %.4f  recall@%d %.4f  time (train, test) %.2fs %.2fs"
+            % (epoch, loss + l2, loss, l2, lr, rejected, 0.0, p["at_nums"][-1], at[p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1))
+        if pre_loss < loss and lr >= lr_min * 10:                   # :196-198
+            model.alpha_lambda = [lr / 10, p["lambda"]]
+        pre_loss = loss
+    return model, best, history

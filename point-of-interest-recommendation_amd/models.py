@@ -1530,3 +1530,210 @@ class OboGeoIE(_Base):
         """GeoIE.py:114-115 returns zeros: AUC is always 0."""
         ids, _ = self._ids(start_end)
         return np.zeros((ids.numel(), self.tes_masks.shape[1]), bool)
+
+
+class OboPoi2vec(_Base):
+    """public/POI2Vec.py:36-181 (driver prog_poi2vec.py): POI2Vec.  Tables xu (n_user, D), wl (n_item + 1, D) - the last row is the zero pad
+    row wl_m and never moves; .wl exposes the first n_item rows - and pb (n_node, D).  A step of one user is a full softmax over all POIs
+    times a hierarchical softmax over the binary region tree (poi_poi2vec_step); scoring reads the trained_* snapshots taken by
+    update_trained_params through poi_poi2vec_scores / _topk (the n_node products per row once, not the reference's gather of pb[routes]).
+
+    train / test: a data.Poi2vecDataset as `train` (test is then None), or the reference's five tables [target_masks, context_masks, masks,
+    masks_cot, accum_lens] each (Load_Data_Poi2vec.fun_data_masks).  probs / routes / lrs: the (n_item + 1, ..) tables of the tree with the
+    pad row; they must come from a perfect binary tree (ValueError otherwise).  n_size = D, a multiple of 4 in [4, 128].  Extra keywords:
+    device, init (dict of float64 arrays xu / wl (n_item rows) / pb), seed, softmax_axis ("reference": plu is a softmax over the USERS of
+    the evaluation batch, as POI2Vec.py:92 computes it; "items": over the POIs), eval_context ("reference": the contexts of the evaluation
+    are read from the TRAIN table at the user's first rows, POI2Vec.py:94-95; "test": the test contexts)."""
+
+    TABLES = ("xu", "wl", "pb")
+
+    def __init__(self, train, test, alpha_lambda, n_user, n_item, n_node, n_size, probs, routes, lrs, device="cuda:0", init=None, seed=None,
+                 softmax_axis="reference", eval_context="reference"):
+        from .data import Poi2vecDataset
+        self.n_user, self.n_item, self.n_node, self.dim = int(n_user), int(n_item), int(n_node), int(n_size)
+        if self.dim <= 0 or self.dim % 4 or self.dim > 128:
+            raise ValueError("OboPoi2vec: n_size must be a multiple of 4 in [4, 128] (got %d)" % self.dim)
+        if softmax_axis not in ("reference", "items"):
+            raise ValueError("softmax_axis must be 'reference' or 'items' (got %r)" % (softmax_axis,))
+        if eval_context not in ("reference", "test"):
+            raise ValueError("eval_context must be 'reference' or 'test' (got %r)" % (eval_context,))
+        self.softmax_axis, self.eval_context = softmax_axis, eval_context
+        routes, lrs = np.ascontiguousarray(routes, np.int32), np.ascontiguousarray(lrs, np.int8)
+        probs = np.ascontiguousarray(probs, np.float32)
+        if routes.shape != lrs.shape or routes.ndim != 3 or routes.shape[:2] != (self.n_item + 1, 4) or probs.shape != (self.n_item + 1, 4):
+            raise ValueError("routes / lrs must be (n_item + 1, 4, depth) and probs (n_item + 1, 4)")
+        self.depth = int(routes.shape[2])
+        rid, leaf_nodes = self._route_ids(routes, lrs)
+        if isinstance(train, Poi2vecDataset):
+            tra = (train.off, train.tra_t, train.tra_coff, train.tra_c)
+            tes = (train.tes_off, train.tes_t, train.tes_coff, train.tes_c)
+        else:
+            tra, tes = self._from_masks(train), self._from_masks(test)
+        self._tra = tuple(np.ascontiguousarray(a, np.int32) for a in tra)
+        self._tes = tuple(np.ascontiguousarray(a, np.int32) for a in tes)
+        self._lens = np.diff(self._tra[0].astype(np.int64))
+        if len(self._lens) != self.n_user or len(self._tes[0]) != self.n_user + 1:
+            raise ValueError("OboPoi2vec: %d train sequences for n_user = %d" % (len(self._lens), self.n_user))
+        for nm, t in (("train targets", self._tra[1]), ("test targets", self._tes[1])):
+            if t.size and (t.min() < 0 or t.max() >= self.n_item):
+                raise IndexError("%s must lie in [0, %d)" % (nm, self.n_item))
+        self.len_max = int(self._lens.max()) if self.n_user else 0
+        self._ctx_lens = np.diff(self._tra[2].astype(np.int64))
+        self._setup(device, alpha_lambda)
+        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+        self.off, self.tgt, self.coff, self.cidx = (i32(a if a.size else np.zeros(1, np.int32)) for a in self._tra)
+        tl = np.diff(self._tes[0].astype(np.int64))
+        self.tes_len_max = int(tl.max()) if self.n_user else 0
+        msk = np.arange(self.tes_len_max)[None, :] < tl[:, None]
+        tes_p = np.full(msk.shape, self.n_item, np.int32)
+        tes_p[msk] = self._tes[1]
+        self.tes_masks, self.tes_buys_masks = i32(msk.astype(np.int32)), i32(tes_p)          # tes_masks / tes_target_masks
+        self._arange = torch.arange(self.n_user, dtype=torch.int32, device=self.device)
+        self.routes, self.rid, self.leaf_nodes = i32(routes), i32(rid), i32(leaf_nodes)
+        self.lrs = torch.as_tensor(lrs).to(self.device)
+        self.probs = torch.as_tensor(probs).to(self.device)
+        rng = np.random.default_rng(seed) if seed is not None else np.random
+        init = init or {}
+        shapes = dict(xu=(self.n_user, self.dim), wl=(self.n_item, self.dim), pb=(self.n_node, self.dim))
+        for k in self.TABLES:                                                                  # POI2Vec.py:63-71
+            v = np.asarray(init[k], np.float64) if k in init else rng.uniform(-0.5, 0.5, shapes[k])
+            if tuple(v.shape) != shapes[k]:
+                raise ValueError("init[%r] has shape %s, expected %s" % (k, tuple(v.shape), shapes[k]))
+            if k == "wl":
+                v = np.concatenate([v, np.zeros((1, self.dim))])                               # wl_m (:67, 134)
+            setattr(self, "_" + k, self._dev(v))
+        self.xu, self.pb = Shared(self._xu), Shared(self._pb)
+        self.wl = Shared(self._wl[:self.n_item])
+        self.params = [self.wl]                                                                # :114
+        self.l2 = _L2(self, ["xu", "pb", "wl"])                                                # :115-122
+        self._trained = {k: getattr(self, "_" + k).clone() for k in self.TABLES}              # :73-79 (trained_users / _items / _branch)
+        self.rejected = 0
+
+    def _route_ids(self, routes, lrs):
+        """Left-to-right leaf index of every route from its lrs (bit d - 1 = the child taken at route position d), and the node list of
+        each leaf; checks that the tables describe one perfect binary tree."""
+        dep = self.depth
+        if dep < 1 or dep > 31 or self.n_node != (1 << dep) - 1:
+            raise ValueError("OboPoi2vec: n_node = %d is not 2^depth - 1 for depth %d (the tree must be perfect)" % (self.n_node, dep))
+        if routes.min() < 0 or routes.max() >= self.n_node or not np.all(np.abs(lrs) == 1) or not np.all(lrs[:, :, 0] == 1):
+            raise ValueError("OboPoi2vec: routes must lie in [0, n_node) and lrs be +1 / -1 (+1 at the leaf)")
+        rid = np.zeros(routes.shape[:2], np.int64)
+        for d in range(1, dep):
+            rid |= ((1 - lrs[:, :, d].astype(np.int64)) // 2) << (d - 1)
+        leaf_nodes = np.full((1 << (dep - 1), dep), -1, np.int64)
+        leaf_nodes[rid.reshape(-1)] = routes.reshape(-1, dep)
+        if not np.array_equal(leaf_nodes[rid.reshape(-1)], routes.reshape(-1, dep)):
+            raise ValueError("OboPoi2vec: two routes with the same turns list different nodes (not one binary tree)")
+        leaf_nodes[leaf_nodes < 0] = 0                                                         # leaves no POI reaches: never gathered
+        return rid.astype(np.int32), leaf_nodes.astype(np.int32)
+
+    def _from_masks(self, tabs):
+        """fun_data_masks' five tables -> CSR of CSR (ids >= n_item are padding)."""
+        target_masks, context_masks, masks, masks_cot, accum = (np.asarray(x) for x in tabs)
+        lens = np.asarray(masks, np.int64).reshape(len(accum), -1).sum(axis=1)
+        off, t = padded_to_csr(np.asarray(target_masks).reshape(len(accum), -1), lens)
+        clens = np.asarray(masks_cot, np.int64).sum(axis=1)
+        coff, c = padded_to_csr(context_masks, clens)
+        return off, t, coff, c
+
+    # ---- training -----------------------------------------------------------------------------
+    def _pparams(self, tabs):
+        return _lib.Poi2vecParams(*[ctypes.c_void_p(tabs[k].data_ptr()) for k in self.TABLES], _ptr(self.routes), _ptr(self.lrs), _ptr(self.probs),
+                                  _ptr(self.rid), self.n_user, self.n_item, self.n_node, self.depth, self.dim)
+
+    def _live(self):
+        return {k: getattr(self, "_" + k) for k in self.TABLES}
+
+    def train(self, uidx):
+        """Poi2vec.train(uidx) (POI2Vec.py:180-181) -> upq."""
+        return float(self.train_batch([int(uidx)])[0])
+
+    def train_batch(self, uidxs, sync=True):
+        """A launch of users (poi_poi2vec_step, batch semantics of include/poi_hip.h) -> upq per user.  A rejected user (no train target, a
+        non-finite loss) moved nothing and has a NaN loss; with sync the count is added to self.rejected."""
+        a = np.atleast_1d(np.asarray(uidxs.cpu().numpy() if isinstance(uidxs, torch.Tensor) else uidxs)).astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= self.n_user):
+            raise IndexError("user ids must lie in [0, %d) (found %d..%d)" % (self.n_user, int(a.min()), int(a.max())))
+        return self._launch(a, sync)
+
+    def _launch(self, a, sync=True):
+        n = int(a.size)
+        ok = a[(a >= 0) & (a < self.n_user)]
+        off, coff = self._tra[0].astype(np.int64), self._tra[2].astype(np.int64)
+        n_pos = int(self._lens[ok].sum()) if ok.size else 0
+        n_ctx = int((coff[off[ok + 1]] - coff[off[ok]]).sum()) if ok.size else 0
+        users = torch.as_tensor(a.astype(np.int32)).to(self.device)
+        loss = torch.empty(n, dtype=torch.float32, device=self.device)
+        P = self._pparams(self._live())
+        self.ctx.check(self.lib.poi_poi2vec_step(self.ctx.handle, ctypes.byref(P), _ptr(self.off), _ptr(self.tgt), _ptr(self.coff), _ptr(self.cidx),
+                                                 _ptr(users), n, n_pos, n_ctx, self.len_max, self.alpha_lambda[0], self.alpha_lambda[1],
+                                                 _ptr(loss), self._stream()))
+        if sync:
+            self.rejected += self.ctx.take_bad_ids(self._stream().value)
+        return loss.cpu().numpy() if sync else loss
+
+    def update_trained_params(self):
+        """POI2Vec.py:81-89: trained_users / trained_items / trained_branch <- the live tables."""
+        for k in self.TABLES:
+            self._trained[k].copy_(getattr(self, "_" + k))
+
+    # ---- evaluation (POI2Vec.py:91-112) -------------------------------------------------------
+    def _eval_rows(self, a, length=None, eval_context=None):
+        """The context rows (CSR on the device) of the evaluation rows (user, t), t < length = the longest test sequence of the batch (:93)."""
+        mode = self.eval_context if eval_context is None else eval_context
+        tl = np.diff(self._tes[0].astype(np.int64))[a]
+        length = int(tl.max()) if length is None and len(a) else int(length or 0)
+        src = self._tra if mode == "reference" else self._tes
+        off, coff, c = src[0].astype(np.int64), src[2].astype(np.int64), src[3]
+        rows = []
+        for u in a:
+            for t in range(length):
+                x = off[u] + t
+                if x >= off[u + 1]:
+                    if mode == "reference":                                                    # :94-95 would read the next user's rows
+                        raise ValueError("eval_context='reference': user %d has %d train positions, the evaluation reads %d" % (u, off[u + 1] - off[u], length))
+                    rows.append(c[0:0])
+                else:
+                    rows.append(c[coff[x]:coff[x + 1]])
+        rc = np.zeros(len(rows) + 1, np.int32)
+        np.cumsum([len(r) for r in rows], out=rc[1:])
+        flat = np.concatenate(rows).astype(np.int32) if len(rows) and rc[-1] else np.zeros(1, np.int32)
+        return length, torch.as_tensor(rc).to(self.device), torch.as_tensor(flat).to(self.device)
+
+    def _score_call(self, start_end, k=None, return_scores=False, softmax_axis=None, eval_context=None, length=None):
+        a = np.atleast_1d(np.asarray(start_end.cpu().numpy() if isinstance(start_end, torch.Tensor) else start_end)).astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= self.n_user):
+            raise IndexError("user ids must lie in [0, %d) (found %d..%d)" % (self.n_user, int(a.min()), int(a.max())))
+        axis = {"reference": 0, "items": 1}[self.softmax_axis if softmax_axis is None else softmax_axis]
+        length, rc, flat = self._eval_rows(a, length, eval_context)
+        users = torch.as_tensor(a.astype(np.int32)).to(self.device)
+        rows = len(a) * length
+        P = self._pparams(self._trained)
+        if k is None:
+            out = torch.empty((rows, self.n_item), dtype=torch.float32, device=self.device)
+            self.ctx.check(self.lib.poi_poi2vec_scores(self.ctx.handle, ctypes.byref(P), _ptr(self.leaf_nodes), _ptr(users), len(a), length, _ptr(rc),
+                                                       _ptr(flat), axis, _ptr(out), self._stream()))
+            return out
+        idx = torch.empty((rows, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((rows, k), dtype=torch.float32, device=self.device) if return_scores else None
+        self.ctx.check(self.lib.poi_poi2vec_topk(self.ctx.handle, ctypes.byref(P), _ptr(self.leaf_nodes), _ptr(users), len(a), length, _ptr(rc),
+                                                 _ptr(flat), axis, int(k), _ptr(idx), _ptr(sc), self._stream()))
+        return (idx, sc) if return_scores else idx
+
+    def compute_sub_all_scores_device(self, start_end, **kw):
+        """POI2Vec.py:91-109 -> (n_batch * length, n_item) device tensor, rows ordered (user, position)."""
+        return self._score_call(start_end, **kw)
+
+    def compute_sub_all_scores(self, start_end, **kw):
+        return self.compute_sub_all_scores_device(start_end, **kw).cpu().numpy()
+
+    def compute_sub_topk(self, start_end, k, return_scores=False, **kw):
+        """Valuate.py:132-146 on the POI2Vec scores: (n_batch * length, k) int32 ids by descending score (ties: ascending id)."""
+        if not 1 <= int(k) <= min(64, self.n_item):
+            raise _lib.PoiError("top-K supports 1 <= k <= min(64, n_item) (got %d)" % k)
+        return self._score_call(start_end, k=int(k), return_scores=return_scores, **kw)
+
+    def compute_sub_auc_preference(self, start_end):
+        """POI2Vec.py:111-112 returns zeros: AUC is always 0."""
+        ids, _ = self._ids(start_end)
+        return np.zeros((ids.numel(), self.tes_masks.shape[1]), bool)
