@@ -369,18 +369,27 @@ def carnn_forward_cost(P, p, q, dp, dq, mask, lam):
     return los + 0.5 * lam * l2, los
 
 
-def carnn_step(P, p, q, dp, dq, mask, alpha, lam):
-    """One ``OboCARNN.seq_train(uidx)`` (public/CA_RNN.py:105-170).  Returns (P_new, los); P is not modified
-    (Theano `updates`: everything evaluated at the old values).  Backward hand-derived, checked against an independent
-    float64 autograd of carnn_forward_cost (tests/test_oracle_autograd.py)."""
+def _carnn_seq_grads(P, p, q, dp, dq, mask, lam):
+    """Forward and backward pass of ONE sequence of ``OboCARNN.seq_train`` (public/CA_RNN.py:105-156) on its padded rows, with the
+    gradients held sparsely: -> (R, g_lt, S, g_wd, g_M, los) with R = unique(p U q) (:123-125), S = unique(dp U dq) (:127-129),
+    g_lt (len(R), D) and g_wd (len(S), H, D) the gradients of the cost - loss plus the L2 term of every gathered row / matrix of all LM
+    positions, multiplicity-weighted (:147) - with respect to those rows and matrices, and g_M the loss gradient of M (no L2 term).
+    Shared by carnn_step and carnn_batch_step.  Every sum runs in the order of the dense formulation (one accumulator per row, steps
+    backwards, then the L2 terms of p, q / dp, dq in position order), so scattering the result gives the same bits.  The arithmetic runs
+    in the dtype of P's arrays (float64 in every check; float32 to measure what that precision costs a long sequence).  Backward
+    hand-derived, checked against an independent float64 autograd of carnn_forward_cost (tests/test_oracle_autograd.py)."""
     p, q, dp, dq = (np.asarray(v, np.int64) for v in (p, q, dp, dq))
     lt, M, wd = P['lt'], P['M'], P['wd']
+    dt = lt.dtype
     D = lt.shape[1]
     L = int(np.sum(mask))
     ns = max(L - 1, 0)
+    R = np.unique(np.concatenate((p, q)))                    # :123-125
+    S = np.unique(np.concatenate((dp, dq)))                  # :127-129
+    ip, iq, idp, idq = np.searchsorted(R, p), np.searchsorted(R, q), np.searchsorted(S, dp), np.searchsorted(S, dq)
     xps, xqs = lt[p], lt[q]
-    hs = np.zeros((ns + 1, D)); hs[0] = P['h0']
-    mp = np.zeros((ns, D)); mq = np.zeros((ns, D)); vp = np.zeros((ns, D)); vq = np.zeros((ns, D)); ys = np.zeros(ns)
+    hs = np.zeros((ns + 1, D), dt); hs[0] = P['h0']
+    mp = np.zeros((ns, D), dt); mq = np.zeros((ns, D), dt); vp = np.zeros((ns, D), dt); vq = np.zeros((ns, D), dt); ys = np.zeros(ns, dt)
     tot = 0.0
     for t in range(ns):
         hs[t + 1] = sigmoid(M @ xps[t] + wd[dp[t]] @ hs[t])
@@ -390,36 +399,117 @@ def carnn_step(P, p, q, dp, dq, mask, alpha, lam):
         ys[t] = vp[t] @ mp[t] - vq[t] @ mq[t]
         tot += log_sigmoid(ys[t])
     los = -tot
-    g_M = np.zeros_like(M); g_lt = np.zeros_like(lt); g_wd = np.zeros_like(wd)
-    dh_next = np.zeros(D)
+    g_M = np.zeros_like(M); g_lt = np.zeros((len(R), D), dt); g_wd = np.zeros((len(S),) + wd.shape[1:], dt)
+    dh_next = np.zeros(D, dt)
+    o1, o2 = np.empty_like(M), np.empty_like(M)              # the rank-one terms, built in place (no temporaries of H x D per product)
+
+    def outer(a, b, out):
+        return np.multiply(a[:, None], b[None, :], out=out)
+
+    def acc(view, x, op=np.add):                             # view (+|-)= x on a matrix of g_wd, without writing the view back onto itself
+        op(view, x, out=view)
     for t in range(ns - 1, -1, -1):
         h, hp = hs[t + 1], hs[t]
         a, b = dp[t + 1], dq[t + 1]
         g = -sigmoid(-ys[t])                                 # d cost / d (yp - yq)
         dh = dh_next + g * (wd[a].T @ mp[t] - wd[b].T @ mq[t])
-        g_wd[a] += g * np.outer(mp[t], h)
-        g_wd[b] -= g * np.outer(mq[t], h)
-        g_M += g * (np.outer(vp[t], xps[t + 1]) - np.outer(vq[t], xqs[t + 1]))
-        g_lt[p[t + 1]] += g * (M.T @ vp[t])
-        g_lt[q[t + 1]] -= g * (M.T @ vq[t])
+        acc(g_wd[idp[t + 1]], np.multiply(g, outer(mp[t], h, o1), out=o1))           # += g * np.outer(mp[t], h)
+        acc(g_wd[idq[t + 1]], np.multiply(g, outer(mq[t], h, o1), out=o1), np.subtract)      # -= g * np.outer(mq[t], h)
+        g_M += np.multiply(g, np.subtract(outer(vp[t], xps[t + 1], o1), outer(vq[t], xqs[t + 1], o2), out=o1), out=o1)
+        g_lt[ip[t + 1]] += g * (M.T @ vp[t])
+        g_lt[iq[t + 1]] -= g * (M.T @ vq[t])
         da = dh * h * (1.0 - h)
-        g_M += np.outer(da, xps[t])
-        g_lt[p[t]] += M.T @ da
-        g_wd[dp[t]] += np.outer(da, hp)
+        g_M += outer(da, xps[t], o1)
+        g_lt[ip[t]] += M.T @ da
+        acc(g_wd[idp[t]], outer(da, hp, o1))
         dh_next = wd[dp[t]].T @ da
-    # L2 over ALL LM gathered rows / matrices, multiplicity-weighted (:147)
-    np.add.at(g_lt, p, lam * xps)
-    np.add.at(g_lt, q, lam * xqs)
-    np.add.at(g_wd, dp, lam * wd[dp])
-    np.add.at(g_wd, dq, lam * wd[dq])
+    # L2 over ALL LM gathered rows / matrices, multiplicity-weighted (:147): one term per position, p then q / dp then dq, in position
+    # order (what np.add.at(g, index, lam * rows) does, without gathering LM whole matrices first)
+    for idx, src, tab in ((ip, p, lt), (iq, q, lt)):
+        for i, r in zip(idx, src):
+            g_lt[i] += lam * tab[r]
+    for idx, src in ((idp, dp), (idq, dq)):
+        for i, r in zip(idx, src):
+            acc(g_wd[i], np.multiply(lam, wd[r], out=o1))
+    return R, g_lt, S, g_wd, g_M, los
+
+
+def carnn_step(P, p, q, dp, dq, mask, alpha, lam):
+    """One ``OboCARNN.seq_train(uidx)`` (public/CA_RNN.py:105-170).  Returns (P_new, los); P is not modified
+    (Theano `updates`: everything evaluated at the old values).  Forward and backward in _carnn_seq_grads."""
+    lt, M, wd = P['lt'], P['M'], P['wd']
+    R, g_lt, S, g_wd, g_M, los = _carnn_seq_grads(P, p, q, dp, dq, mask, lam)
     N = dict(P)
     N['M'] = M - alpha * (g_M + lam * M)                     # :151-152
-    R = np.unique(np.concatenate((p, q)))                    # :123-125
-    S = np.unique(np.concatenate((dp, dq)))                  # :127-129
-    lt_new = lt.copy(); lt_new[R] = lt[R] - alpha * g_lt[R]  # :153,155
-    wd_new = wd.copy(); wd_new[S] = wd[S] - alpha * g_wd[S]  # :154,156
+    lt_new = lt.copy(); lt_new[R] = lt[R] - alpha * g_lt     # :153,155
+    wd_new = wd.copy(); wd_new[S] = wd[S] - alpha * g_wd     # :154,156
     N['lt'], N['wd'] = lt_new, wd_new
     return N, los                                            # :163
+
+
+def _carnn_rows(tables, n_item, n_dist):
+    """u -> the five padded rows (p, q, dp, dq, mask) of user u.  tables: the padded tables (p_rows, q_rows, dp_rows, dq_rows, masks),
+    or CSR tables (attributes off, p, q, dp, dq, len_max) padded here as the reference pads them: POIs with n_item, bins with n_dist."""
+    if hasattr(tables, "off"):
+        off, LM = np.asarray(tables.off, np.int64), int(tables.len_max)
+        flat = [np.asarray(v, np.int64) for v in (tables.p, tables.q, tables.dp, tables.dq)]
+
+        def rows(u):
+            a, b = off[u], off[u + 1]
+            out = [np.concatenate((v[a:b], np.full(LM - (b - a), pad, np.int64))) for v, pad in zip(flat, (n_item, n_item, n_dist, n_dist))]
+            return out + [(np.arange(LM) < b - a).astype(np.int64)]
+        return rows
+    pm, qm, dpm, dqm, mm = (np.asarray(v) for v in tables)
+    return lambda u: [pm[u], qm[u], dpm[u], dqm[u], mm[u]]
+
+
+def carnn_batch_step(P, tables, users, alpha, lam, threads=1, block=32):
+    """One launch of ``users`` under the batch rule of include/poi_hip.h: every sequence's reference update (carnn_step) is evaluated at
+    P; every lt row and every interval matrix then moves by the mean of the updates of the sequences that touch it, M by the mean over
+    the launch.  Equal to carnn_step per sequence + tests/gpu_util.batch_mean_update, without a dense table per sequence: a sequence
+    hands over its touched rows / matrices only (_carnn_seq_grads), and they are added in sequence order whatever `threads` (<= 16
+    workers compute the sequences of a block side by side; the sums stay in the calling thread), so the result is deterministic.
+    -> (P_new, losses (n,), touched lt rows (bool mask), touched interval matrices (bool mask))."""
+    from concurrent.futures import ThreadPoolExecutor
+    lt, M, wd = P['lt'], P['M'], P['wd']
+    rows = _carnn_rows(tables, lt.shape[0] - 1, wd.shape[0] - 1)
+    users = [int(u) for u in np.asarray(users).ravel()]
+    n = len(users)
+
+    def one(u):
+        R, g_lt, S, g_wd, g_M, los = _carnn_seq_grads(P, *rows(u), lam)
+        # the sequence's own update of its rows, as carnn_step writes it: (old - alpha * g) - old, built in place in g
+        for g, old in ((g_lt, lt[R]), (g_wd, wd[S])):
+            g *= alpha
+            np.subtract(old, g, out=g)
+            g -= old
+        return R, g_lt, S, g_wd, (M - alpha * (g_M + lam * M)) - M, los
+
+    acc_lt, cnt_lt = np.zeros_like(lt), np.zeros(lt.shape[0], np.int64)
+    acc_wd, cnt_wd = np.zeros_like(wd), np.zeros(wd.shape[0], np.int64)
+    acc_M = np.zeros_like(M)
+    losses = np.empty(n)
+    blocks = [users[i:i + block] for i in range(0, n, block)]
+    with ThreadPoolExecutor(max(1, min(16, int(threads)))) as ex:
+        # one block of sequences is computed while the previous one is added up: at most two blocks of sparse results are alive
+        nxt = [ex.submit(one, u) for u in blocks[0]] if blocks else []
+        k = 0
+        for bi in range(len(blocks)):
+            cur, nxt = nxt, ([ex.submit(one, u) for u in blocks[bi + 1]] if bi + 1 < len(blocks) else [])
+            for f in cur:
+                R, d_lt, S, d_wd, d_M, losses[k] = f.result()
+                acc_lt[R] += d_lt; cnt_lt[R] += 1
+                acc_wd[S] += d_wd; cnt_wd[S] += 1
+                acc_M += d_M
+                k += 1
+    N = dict(P)
+    t_lt, t_wd = cnt_lt > 0, cnt_wd > 0
+    lt_new = lt.copy(); lt_new[t_lt] = lt[t_lt] + acc_lt[t_lt] / cnt_lt[t_lt, None]
+    wd_new = wd.copy(); wd_new[t_wd] = wd[t_wd] + acc_wd[t_wd] / cnt_wd[t_wd, None, None]
+    N['lt'], N['wd'] = lt_new, wd_new
+    if n:
+        N['M'] = M + acc_M / n
+    return N, losses, t_lt, t_wd
 
 
 def carnn_predict(P, items, dists, p_rows, d_rows, masks):
