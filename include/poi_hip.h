@@ -54,6 +54,8 @@ extern "C" {
  * entries unchanged). */
 /* additive to 9: POI2Vec - new entry points poi_poi2vec_step, poi_poi2vec_scores, poi_poi2vec_topk and poi_poi2vec_params (existing
  * entries unchanged). */
+/* additive to 9: mini-batch Lstm / Rnn - new entry points poi_cell_step, poi_cell_predict and poi_cell_params, option "cell_grid", plan
+ * keys for them (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -131,7 +133,9 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * launch stream; -1 when hyb == 0).  POI_EINVAL for an unknown key, or before any training launch.  The flags are host fields set
  * where the launch decides them (a graph replay records the plan of the launch it replays); "tile" == 0: the per-sequence or the exact
  * engine ran and every other flag is 0.  The hyb_* values live in the tile engine's workspace: POI_EINVAL once a later tile-engine
- * launch (poi_gru_predict included) may have reused it. */
+ * launch (poi_gru_predict included) may have reused it.
+ * Additive to 9: "cell_kernel" and "cell_grid" - the gate-block count (POI_CELL_RNN / POI_CELL_LSTM) of the recurrent kernel and the
+ * workgroups of its persistent grid when the last training launch was a poi_cell_step, 0 otherwise. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -192,7 +196,9 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *       tiles (4.5 / 2.9 us per step) on the other CUs; the split is chosen on the device from the launch's own lengths.  A 1563-sequence launch is 98
  *       tiles - 158 CUs idle behind the longest tile's 49-step chain: 678 -> 632 us.  Every sequence still goes through one of the two kernel
  *       families that hold it to the oracle on their own; a sequence's values depend on which one (inside the bars), identical launches are bitwise
- *       identical.  "hybrid_force" n (tests): n leading sequences per workgroup whatever the cost model says. */
+ *       identical.  "hybrid_force" n (tests): n leading sequences per workgroup whatever the cost model says;
+ *   "cell_grid" n (default 0 = no cap): poi_cell_step / poi_cell_predict run their recurrent kernel on at most n workgroups (the persistent
+ *       grid is min(sequences, 512) otherwise) - bitwise the same result for every n. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -574,6 +580,34 @@ int poi_poi2vec_scores(poi_ctx* ctx, const poi_poi2vec_params* prm, const int32_
 int poi_poi2vec_topk(poi_ctx* ctx, const poi_poi2vec_params* prm, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch,
                      int32_t length, const int32_t* coff, const int32_t* cidx, int32_t softmax_axis, int32_t k, int32_t* idx_out,
                      float* score_out, void* stream);
+
+/* ---- mini-batch Lstm / Rnn (additive to ABI 9) - public/GRU.py:502-657 (Lstm), :661-809 (Rnn) ---------------------------------------
+ * The baselines the reference's papers compare against, as one kernel family templated on the number of gate blocks.  lt (n_item + 1, D);
+ * Lstm: ui, wh (4, D, D), bi (4, D), gates i, f, g, o (GRU.py:562-567); Rnn: ui, wh (D, D), bi (D), h = sigmoid(ui x + wh h + bi)
+ * (:720-722).  h0 = c0 = 0, never trained.  Float32 tables only; D a multiple of 4 up to 256 at its native width.
+ * poi_cell_step replaces seq_train(start_end) (GRU.py:525-605, :682-760): the launch is ONE mini-batch of n_seq users - the rule
+ * poi_ctx_set_batch_cap(0) documents for `Gru`, always (the batch cap is ignored):
+ *   u_t = h_{t-1} . (lt[p_t] - lt[q_t]), t = 0 .. L-1;  out[k] = -sum_t log sigmoid(u_t)  (the reference returns their sum, :600)
+ *   cost = sum_k out[k] / n + lambda / 2 (|lt[p]|^2 + |lt[q]|^2 over all n x len_max gathered positions, pad rows and duplicates
+ *          counted, + |ui|^2 + |wh|^2 + |bi|^2)                                          (:582-588, :737-743)
+ *   dense: theta -= alpha (G / n + lambda theta);  every row of unique(p U q): row -= alpha (G_row / n + lambda mult row), mult = its
+ *   count over all len_max positions of all n users (the pad row n_item included), every right-hand side at the launch-entry values.
+ * A user runs exactly L-1 cell steps: the reference scans to the batch's longest L and feeds pad rows to shorter users, but those steps
+ * carry no loss and nothing reads them.  Float64 gate sums, states, BPTT and gradient sums, rounded once at the write-back; alpha /
+ * lambda as their shortest decimals (engine 4's rule).  No float atomics: the row touches are sorted and summed in a fixed order and
+ * the dense gradients are chunk partials added in chunk order - identical launches give bitwise identical tables, on any grid.
+ * A launch with a user id outside [0, n_user), a POI or negative outside [0, n_item] or a length outside [1, max_len] moves NOTHING:
+ * the offending users' losses are NaN and they are counted (poi_ctx_take_bad_ids).  Scratch grows with n_seq x max_len position rows
+ * (8 (G + 3) D + 8 D bytes each).  Timing names: "cell_plan", "cell_rec", "cell_wgrad", "cell_sort", "cell_rows", "cell_commit".
+ * poi_cell_predict replaces seq_predict(start_end) (:610-657, :765-809): the cell over all L positions of the snapshot prm->lt,
+ * hts (n, D) row out_row[k] (or k when out_row is NULL) = h_{L-1} of uidx[k]; a user with an id out of range gets a NaN row and is
+ * counted.  Timing name: "cell_predict". */
+enum { POI_CELL_RNN = 1, POI_CELL_LSTM = 4 };            /* = number of gate blocks */
+typedef struct poi_cell_params { float* lt; float* ui; float* wh; float* bi; int32_t n_item; int32_t dim; int32_t cell; } poi_cell_params;
+int poi_cell_step(poi_ctx* ctx, const poi_cell_params* prm, const poi_seq_tables* tab, const int32_t* uidx, int32_t n_seq,
+                  float alpha, float lambda, float* out /* n_seq: -sum_t log sigmoid(u_t) per user */, void* stream);
+int poi_cell_predict(poi_ctx* ctx, const poi_cell_params* prm, const poi_seq_tables* tab, const int32_t* uidx, const int32_t* out_row,
+                     int32_t n, float* hts, void* stream);   /* prm->lt = the snapshot */
 
 /* ---- multi-GPU reconciliation (8e; new - the reference is single-process) ----------------------
  * Users are sharded across ranks, every rank trains on a full parameter replica with no data-path collective,

@@ -40,6 +40,13 @@ class Poi2vecParams(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("xu", "wl", "pb", "routes", "lrs", "probs", "rid")] + [(n, c_int32) for n in ("n_user", "n_item", "n_node", "depth", "dim")]
 
 
+class CellParams(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("lt", "ui", "wh", "bi")] + [("n_item", c_int32), ("dim", c_int32), ("cell", c_int32)]
+
+
+CELL_RNN, CELL_LSTM = 1, 4          # POI_CELL_*: the number of gate blocks
+
+
 class SyncSeg(ctypes.Structure):
     _fields_ = [("cur", c_void_p), ("rows", c_int64), ("width", c_int64), ("rule", c_int32), ("dtype", c_int32)]
 
@@ -131,6 +138,8 @@ SIGNATURES = {
                                    c_void_p]),
     "poi_poi2vec_topk": (c_int, [c_void_p, POINTER(Poi2vecParams), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32,
                                  c_void_p, c_void_p, c_void_p]),
+    "poi_cell_step": (c_int, [c_void_p, POINTER(CellParams), POINTER(SeqTables), c_void_p, c_int32, c_float, c_float, c_void_p, c_void_p]),
+    "poi_cell_predict": (c_int, [c_void_p, POINTER(CellParams), POINTER(SeqTables), c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "poi_delta_make": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_delta_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_comm_available": (c_int, []),
@@ -185,7 +194,7 @@ def load():
 
 # keys of poi_ctx_last_plan (include/poi_hip.h)
 PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", "fwd_tab", "xft", "xcomp", "head_split", "efuse", "early_bins",
-             "fork", "hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg")
+             "fork", "hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg", "cell_kernel", "cell_grid")
 
 
 class Context:
@@ -275,7 +284,7 @@ class Context:
 
     def set_option(self, name, value):
         """Named tuning switch of the tile engine (poi_ctx_set_option: "forward_table_compact", "forward_table_compact_min", "head_split",
-        "early_bins", "hot_bins", "hybrid", "hybrid_min", "hybrid_max", "hybrid_force")."""
+        "early_bins", "hot_bins", "hybrid", "hybrid_min", "hybrid_max", "hybrid_force"; "cell_grid" of poi_cell_step)."""
         self.check(self.lib.poi_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def set_small_launch(self, max_sequences=1800):

@@ -79,7 +79,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR
@@ -92,6 +92,9 @@ struct poi_ctx {
   DevBuf ge_ws;
   // POI2Vec step / scoring scratch
   DevBuf pv_ws, pv_sc;
+  // mini-batch Lstm / Rnn: packed weights, per-position-row state, sort buffers, chunk partials, new-row slots
+  DevBuf cell_ws;
+  int cell_grid = 0;        // option "cell_grid": cap of the recurrent kernel's persistent grid (0: none)
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)
@@ -227,7 +230,7 @@ int poi_ctx_destroy(poi_ctx* c) {
   if (!c) return POI_OK;
   DevBuf* all[] = {&c->ex_ws, &c->ex_slab, &c->ex_glt, &c->ex_gdi, &c->ws, &c->slab, &c->te_ws, &c->hslab, &c->zrow, &c->g_lt, &c->mult_lt, &c->nseq_lt, &c->g_di, &c->mult_di, &c->nseq_di, &c->seg_s, &c->seg_e, &c->pmark, &c->xc, &c->kc_dev, &c->uidx_stage, &c->out_stage, &c->ptab, &c->iota, &c->xw, &c->xg, &c->xflag, &c->bad_ids,
                    &c->g_wd, &c->mult_wd, &c->nseq_wd, &c->ca_ws, &c->ca_slab, &c->ca_scr, &c->ca2, &c->g_ux, &c->cnt_ux, &c->g_blt, &c->cnt_blt, &c->cand_s, &c->cand_i, &c->items_pk, &c->gbound, &c->st,
-                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc};
+                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->cell_ws};
   (void)hipDeviceSynchronize();
   c->tm.clear();
   drop_graphs(c);
@@ -1125,6 +1128,87 @@ int poi_geoie_user_vectors(poi_ctx* c, const poi_geoie_params* P, const int32_t*
 }
 
 // ---------------------------------------------------------------------------------------------
+// mini-batch Lstm / Rnn (cells.hip)
+static int cell_check(poi_ctx* c, const poi_cell_params* P, const poi_seq_tables* T, bool need_q, const char* who) {
+  if (!c || !P || !T) return fail(c, POI_EINVAL, "%s: NULL ctx/params/tables", who);
+  if (P->cell != POI_CELL_RNN && P->cell != POI_CELL_LSTM) return fail(c, POI_EINVAL, "%s: cell must be POI_CELL_RNN or POI_CELL_LSTM (got %d)", who, P->cell);
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, P->dim);
+  if (!P->lt || !P->ui || !P->wh || !P->bi) return fail(c, POI_EINVAL, "%s: lt/ui/wh/bi must be non-NULL", who);
+  if (is_f16(c, P->lt)) return fail(c, POI_ENOTSUP, "%s: float32 tables only", who);
+  if (P->n_item <= 0 || (int64_t)P->n_item + 2 >= ((int64_t)1 << 31)) return fail(c, POI_EINVAL, "%s: bad n_item", who);
+  if (!T->off || !T->p || (need_q && !T->q)) return fail(c, POI_EINVAL, "%s: tables off/p/q must be non-NULL", who);
+  if (T->n_user <= 0 || T->max_len <= 0 || T->len_max < T->max_len) return fail(c, POI_EINVAL, "%s: tables need n_user > 0 and 0 < max_len <= len_max", who);
+  return POI_OK;
+}
+
+static void cell_fill(poi::CellArgs& A, const poi_cell_params* P, const poi_seq_tables* T, const int32_t* uidx, int n) {
+  memset(&A, 0, sizeof A);
+  A.lt = P->lt; A.ui = P->ui; A.wh = P->wh; A.bi = P->bi; A.n_item = P->n_item; A.dim = P->dim; A.G = P->cell;
+  A.off = T->off; A.p = T->p; A.q = T->q; A.n_user = T->n_user; A.len_max = T->len_max; A.max_len = T->max_len;
+  A.uidx = uidx; A.n_seq = n;
+}
+
+int poi_cell_step(poi_ctx* c, const poi_cell_params* P, const poi_seq_tables* T, const int32_t* uidx, int32_t n, float alpha, float lambda,
+                  float* out, void* stream) {
+  int rc = cell_check(c, P, T, true, "poi_cell_step");
+  if (rc) return rc;
+  if (!uidx || !out || n < 0) return fail(c, POI_EINVAL, "poi_cell_step: uidx/out NULL or n < 0");
+  if (n == 0) return POI_OK;
+  const size_t R = (size_t)n * (size_t)T->max_len, E = 2 * R + 1;
+  if (E >= ((size_t)1 << 31) - 128) return fail(c, POI_ENOTSUP, "poi_cell_step: n_seq x max_len must stay below 2^30");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->tm.tick();
+  poi::CellArgs A;
+  cell_fill(A, P, T, uidx, n);
+  A.out = out; A.alpha = shortest_decimal(alpha); A.lambda = shortest_decimal(lambda);
+  A.grid = poi::cell_grid(n, c->cell_grid); A.ch_rows = poi::cell_chunk_rows(n, T->max_len);
+  c->plan = poi_ctx::LastPlan{}; c->plan.valid = 1; c->plan.cell_kernel = P->cell; c->plan.cell_grid = A.grid;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  const size_t D = (size_t)P->dim, NO = (size_t)P->cell * D, Rp = R + 8, Ep = E + 64, chunks = (E + 63) / 64 + 2;
+  const size_t n_f4 = 4 * NO * (D / 4) + chunks;                                         // packed weights, meta
+  const size_t n_dbl = Rp * (3 * D + NO + 1) + (size_t)CELL_DENSE_CHUNKS * NO * (2 * D + 1) + 2 * chunks * D;
+  const size_t n_i32 = Ep * D + 4 * Ep + Rp + 2 * ((size_t)n + 8) + 64 + chunks + RS_HIST_INTS + RS_MAXBIN;
+  if ((rc = ensure(c, c->cell_ws, 16 * n_f4 + 8 * n_dbl + 4 * n_i32 + 256, st))) return rc;
+  float4* f4 = (float4*)c->cell_ws.p;
+  A.uiP = f4; f4 += NO * (D / 4); A.whP = f4; f4 += NO * (D / 4); A.uiT = f4; f4 += NO * (D / 4); A.whT = f4; f4 += NO * (D / 4);
+  A.meta = (int4*)f4; f4 += chunks;
+  double* dp = (double*)f4;
+  A.H = dp; dp += Rp * D; A.ACT = dp; dp += Rp * NO; A.CS = dp; dp += Rp * D; A.DX = dp; dp += Rp * D; A.gam = dp; dp += Rp;
+  A.dpart = dp; dp += (size_t)CELL_DENSE_CHUNKS * NO * (2 * D + 1);
+  A.lead = dp; dp += chunks * D; A.trail = dp; dp += chunks * D;
+  A.slot = (float*)dp;
+  int* ip = (int*)(A.slot + Ep * D);
+  A.keys0 = ip; ip += Ep; A.keys1 = ip; ip += Ep; A.vals0 = ip; ip += Ep; A.vals1 = ip; ip += Ep;
+  A.rowp = ip; ip += Rp; A.slen = ip; ip += n + 8; A.poff = ip; ip += n + 8; A.cnt = ip; ip += 64; A.mm = ip; ip += chunks;
+  A.hist = ip;
+  HIPCHK(c, poi::launch_cell_step(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_cell_predict(poi_ctx* c, const poi_cell_params* P, const poi_seq_tables* T, const int32_t* uidx, const int32_t* out_row, int32_t n,
+                     float* hts, void* stream) {
+  int rc = cell_check(c, P, T, false, "poi_cell_predict");
+  if (rc) return rc;
+  if (!uidx || !hts || n < 0) return fail(c, POI_EINVAL, "poi_cell_predict: uidx/hts NULL or n < 0");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::CellArgs A;
+  cell_fill(A, P, T, uidx, n);
+  A.out_row = out_row; A.hts = hts; A.grid = poi::cell_grid(n, c->cell_grid);
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  const size_t D = (size_t)P->dim, NO = (size_t)P->cell * D;
+  if ((rc = ensure(c, c->cell_ws, 16 * 4 * NO * (D / 4) + 256, st))) return rc;
+  float4* f4 = (float4*)c->cell_ws.p;
+  A.uiP = f4; f4 += NO * (D / 4); A.whP = f4; f4 += NO * (D / 4); A.uiT = f4; f4 += NO * (D / 4); A.whT = f4;
+  HIPCHK(c, poi::launch_cell_predict(A, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // POI2Vec (poi2vec.hip)
 static int poi2vec_check(poi_ctx* c, const poi_poi2vec_params* P, const char* who) {
   if (!c || !P || !P->xu || !P->wl || !P->pb || !P->routes || !P->lrs || !P->probs || !P->rid) return fail(c, POI_EINVAL, "%s: NULL argument", who);
@@ -1557,7 +1641,8 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
   if (!c || !name) return fail(c, POI_EINVAL, "poi_ctx_set_option: null argument");
   struct Opt { const char* name; int* p; int lo, hi; };
   const Opt opts[] = {{"forward_table_compact", &c->xcomp, 0, 1}, {"forward_table_compact_min", &c->xcomp_min, 0, 1 << 30}, {"head_split", &c->head3, 0, 1},
-                      {"early_bins", &c->early_bins, 0, 1}, {"hot_bins", &c->hot_bins, 0, 1}, {"hybrid", &c->hybrid, 0, 1}, {"hybrid_min", &c->hyb_min, 0, 1 << 30}, {"hybrid_max", &c->hyb_max, 0, 1 << 30}, {"hybrid_force", &c->hyb_force, 0, 1 << 30}};
+                      {"early_bins", &c->early_bins, 0, 1}, {"hot_bins", &c->hot_bins, 0, 1}, {"hybrid", &c->hybrid, 0, 1}, {"hybrid_min", &c->hyb_min, 0, 1 << 30}, {"hybrid_max", &c->hyb_max, 0, 1 << 30}, {"hybrid_force", &c->hyb_force, 0, 1 << 30},
+                      {"cell_grid", &c->cell_grid, 0, 1 << 30}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);
@@ -1634,7 +1719,7 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"hyb", &poi_ctx::LastPlan::hyb}, {"bintab", &poi_ctx::LastPlan::bintab}, {"ppoi", &poi_ctx::LastPlan::ppoi}, {"listed", &poi_ctx::LastPlan::listed},
       {"fwd_tab", &poi_ctx::LastPlan::fwd_tab}, {"xft", &poi_ctx::LastPlan::xft}, {"xcomp", &poi_ctx::LastPlan::xcomp},
       {"head_split", &poi_ctx::LastPlan::head_split}, {"efuse", &poi_ctx::LastPlan::efuse}, {"early_bins", &poi_ctx::LastPlan::early_bins},
-      {"fork", &poi_ctx::LastPlan::fork}};
+      {"fork", &poi_ctx::LastPlan::fork}, {"cell_kernel", &poi_ctx::LastPlan::cell_kernel}, {"cell_grid", &poi_ctx::LastPlan::cell_grid}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

@@ -459,6 +459,37 @@ struct P2vScoreArgs {
 hipError_t launch_poi2vec_step(P2vArgs& A, int num_cu, hipStream_t st, Timing* tm);
 hipError_t launch_poi2vec_scores(P2vScoreArgs& A, int num_cu, hipStream_t st, Timing* tm);
 
+// Mini-batch Lstm / Rnn cells (cells.hip)
+#define CELL_NT 256               // threads of the recurrent workgroup (one sequence per workgroup)
+#define CELL_GRID_MAX 512         // bound of the persistent recurrent grid: device-independent (two workgroups per CU on 256 CUs)
+#define CELL_DENSE_CHUNKS 64      // row chunks of the dense-gradient contraction (partials added in chunk order)
+#define CELL_PART 1024            // LDS doubles for the split contractions' partial sums
+struct CellArgs {
+  float *lt, *ui, *wh, *bi;         // (n_item + 1, D); (G, D, D) x 2; (G, D)
+  int n_item, dim, G;               // G = gate blocks: 1 Rnn, 4 Lstm (POI_CELL_*)
+  const int *off, *p, *q;
+  int n_user, len_max, max_len;
+  const int *uidx, *out_row;
+  int n_seq;
+  float *out, *hts;                 // train: loss per sequence; predict: (n, D)
+  double alpha, lambda;
+  int grid, ch_rows;                // workgroups of the recurrent kernel; position rows per dense-gradient chunk
+  int* bad;                         // device counter of rejected sequences (poi_ctx_take_bad_ids)
+  int *slen, *poff, *cnt, *rowp;    // per sequence: L (0: rejected), first position row; cnt = {entries, rows, pad multiplicity, rejected}; per row: p_t
+  int *keys0, *keys1, *vals0, *vals1, *hist;      // radix sort of the 2 P + 1 row entries
+  const int *ks, *vs;
+  float4 *uiP, *whP, *uiT, *whT;    // weights packed for the forward / backward contractions (cell_pack_kernel)
+  double *H, *ACT, *CS, *DX, *gam;  // per position row (see cells.hip)
+  double *dpart, *lead, *trail;     // dense-gradient chunk partials; per 64-entry window: partial sum of its opening / closing run
+  int4* meta; int* mm;              // per window: {opening run's multiplicity, it goes on, closing run's entries, its row}; closing run's multiplicity
+  float* slot;                      // (2 P + 1, D) new rows at a run's first sorted position
+};
+size_t cell_lds_bytes(int D, int G);
+int cell_grid(int n_seq, int cap);
+int cell_chunk_rows(int n_seq, int max_len);
+hipError_t launch_cell_step(CellArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_cell_predict(CellArgs& A, hipStream_t st, Timing* tm);
+
 // scoring / top-K
 struct ScoreArgs {
   const float *users, *items; int items_f16;      // items: float32, or IEEE half when items_f16

@@ -201,6 +201,63 @@ def train_valid_or_test(ds, p, device="cuda:0", log=print):
     return model, best, history
 
 
+def minibatch_default_params():
+    """Config of the mini-batch classes of public/GRU.py (`Gru` :395, `Lstm` :502, `Rnn` :661).  The reference has no driver for them
+    (its `main`, :813-814, is a stub): the values are default_params()'s with a train batch; `cell` picks the class - "gru", "lstm"
+    or "rnn".  The batch cost averages the loss gradients over the batch, so a batch of B users moves 1 / B as far per user as the
+    one-by-one drivers do at the same alpha."""
+    return dict(at_nums=[5, 10, 15, 20], epochs=3, latent_size=20, alpha=0.01, **{"lambda": 0.001}, cell="lstm",
+                batch_size_train=16, batch_size_test=32, seed=123, dataset="synthetic", UD=40, dd=200)
+
+
+MINIBATCH_CELLS = {"gru": "Gru", "lstm": "Lstm", "rnn": "Rnn"}
+
+
+def train_minibatch(ds, p=None, device="cuda:0", log=print):
+    """train_valid_or_test's epoch for the mini-batch classes: negative refresh -> shuffled users in batches of p["batch_size_train"]
+    (one SGD step each) -> snapshot -> predict -> update_trained_users -> evaluate.  -> (model, best, history)."""
+    q = minibatch_default_params()
+    q.update(p or {})
+    p = q
+    if p["cell"] not in MINIBATCH_CELLS:
+        raise ValueError("p['cell'] must be one of %s (got %r)" % (sorted(MINIBATCH_CELLS), p["cell"]))
+    if ds is None or isinstance(ds, str):
+        if isinstance(ds, str):
+            p = dict(p, dataset=ds)
+        ds = load_dataset(p)
+    size = p["latent_size"]
+    model = getattr(models, MINIBATCH_CELLS[p["cell"]])(train=ds.shard(), test=None, alpha_lambda=[p["alpha"], p["lambda"]], n_user=ds.n_user,
+                                                        n_item=ds.n_item, n_in=size, n_hidden=size, device=device, seed=p.get("seed"))
+    best = GlobalBest(p["at_nums"])
+    U, B = ds.n_user, max(1, int(p["batch_size_train"]))
+    ses_tes = compute_start_end(U, p["batch_size_test"])
+    ses_auc = compute_start_end(U, p["batch_size_test"] * 10)
+    ses_pred = compute_start_end(U, max(int(p["batch_size_test"]), 16384))
+    tes_p, tes_m = ds.tes_p.reshape(-1, 1), np.ones((U, 1), np.int32)
+    history = []
+    for epoch in range(p["epochs"]):
+        if epoch > 0:
+            model.resample_negatives_device(p.get("seed", 0) * 1000003 + epoch)
+        t0 = time.time()
+        order = np.random.default_rng(123 + epoch).permutation(U).astype(np.int32)
+        outs = [model.train_batch(order[b0:b0 + B], sync=False) for b0 in range(0, U, B)]
+        loss = float(torch.cat(outs).double().sum().item())
+        if model.ctx.take_bad_ids(model._stream().value):
+            raise IndexError("an index table holds an id outside the model's tables")
+        l2 = model.l2.eval()
+        t1 = time.time()
+        model.update_trained_items()
+        model.update_trained_users(torch.cat([model.predict_device(se) for se in ses_pred]))
+        t2 = time.time()
+        m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m)
+        t3 = time.time()
+        history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall=[m["at"][k]["recall"] for k in p["at_nums"]],
+                            times=(t1 - t0, t2 - t1, t3 - t2)))
+        log("epoch %d  sum_loss = %.3f = %.3f + %.3f  auc %.4f  recall@%d %.4f  time (train, user, test) %.2fs %.2fs %.2fs"
+            % (epoch, loss + l2, loss, l2, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1, t3 - t2))
+    return model, best, history
+
+
 def cal_s(ds, p, device="cuda:0", out_root="./Lmdd", log=print):
     """Mode 's' of the reference driver (prog_bpr_gru_spatial.py:337-362): build the Distance2Pre model, load the checkpoint of
     p['load_epoch'], snapshot the tables, predict every user and save the (n_user, n_dist + 1) bin probabilities `sts` with np.save under

@@ -2,6 +2,7 @@
 
 Class / method names, argument meaning and return shapes follow the Theano classes the drivers call:
     OboSpatialGru  public/GRU_Spatial.py:42-292      OboGru  public/GRU.py:301-389 (+ GruBasic :32-205)
+    Gru / Lstm / Rnn  public/GRU.py:395-498 / :502-657 / :661-809 (the mini-batch classes)
     OboBpr         public/BPR.py:191-241 (+ MfBasic :28-134)
 so that prog_bpr_gru_spatial.py's epoch loop and public/Valuate.py's evaluator run against them
 unchanged in shape.  State lives in torch ROCm tensors (device-memory containers only); every piece of
@@ -484,6 +485,86 @@ class Gru(OboGru):
         """public/GRU.py:476-481: lt rows scaled to unit L2 norm (never called by the reference's drivers)."""
         t = self.lt.t.float()
         self.lt.t.copy_((t / t.pow(2).sum(dim=1, keepdim=True).sqrt()).to(self.lt.t.dtype))
+
+
+class _CellModel(GruBasic):
+    """Shared host side of the mini-batch `Lstm` / `Rnn` (poi_cell_step / poi_cell_predict, csrc/cells.hip): `train(idxs)` takes a LIST
+    of users and makes ONE SGD step on the batch cost; predict / scoring / AUC / top-K are GruBasic's.  The tables are stored at the
+    model's own dim: a sigmoid unit cannot be zero-padded (sigmoid(0) != 0)."""
+
+    _pad_ok = False
+    _cell = None            # _lib.CELL_RNN | _lib.CELL_LSTM
+    _gates = ()             # leading axis of ui / wh / bi
+
+    def __init__(self, train, test, alpha_lambda, n_user, n_item, n_in, n_hidden, **kw):
+        if kw.get("table_dtype", "f32") != "f32":
+            raise ValueError("%s stores float32 tables only (table_dtype=%r)" % (type(self).__name__, kw["table_dtype"]))
+        init = dict(kw.pop("init", None) or {})
+        own = {k: init.pop(k) for k in ("ui", "wh", "bi", "c0") if k in init}
+        kw["pad_dim"] = False
+        super().__init__(train, test, alpha_lambda, n_user, n_item, n_in, n_hidden, init=init, **kw)
+        D, g, seed = self.dim, self._gates, kw.get("seed")
+        rng = np.random.default_rng(seed + 1) if seed is not None else np.random
+        val = lambda k, shape, draw: np.asarray(own[k], np.float64).reshape(shape) if k in own else draw(shape)
+        u = lambda shape: rng.uniform(-0.5, 0.5, shape)
+        self.ui = Shared(self._dev(val("ui", g + (D, D), u)))                              # GRU.py:507 / :666
+        self.wh = Shared(self._dev(val("wh", g + (D, D), u)))                              # :508 / :667
+        self.bi = Shared(self._dev(val("bi", g + (D,), np.zeros)))                         # :510 / :668
+        if self._cell == _lib.CELL_LSTM:
+            self.c0 = Shared(self._dev(val("c0", (D,), np.zeros)))                         # :509 never trained
+        self.params = [self.ui, self.wh, self.bi]                                          # :516 / :673
+        self.l2 = _L2(self, ["lt", "ui", "wh", "bi"])                                      # :517-521 / :674-678
+
+    def _cparams(self, snapshot=False):
+        P = _lib.CellParams()
+        P.lt = (self.trained_items if snapshot else self.lt).t.data_ptr()
+        P.ui, P.wh, P.bi = self.ui.t.data_ptr(), self.wh.t.data_ptr(), self.bi.t.data_ptr()
+        P.n_item, P.dim, P.cell = self.n_item, self.dim, self._cell
+        return P
+
+    def train(self, idxs):
+        """seq_train(start_end) -> the batch's summed loss -upq (GRU.py:600, :755)."""
+        return float(np.sum(self.train_batch(idxs), dtype=np.float64))
+
+    def train_batch(self, idxs, sync=True):
+        """One mini-batch step on the users `idxs` -> their losses (numpy, or the device tensor with sync=False).  An id out of range in
+        the index tables raises IndexError and the launch moves nothing (checked with sync=True; the counter stays readable through
+        ctx.take_bad_ids() otherwise)."""
+        ids, _ = self._ids(idxs)
+        n = ids.numel()
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        P, T = self._cparams(), self._tables()
+        self.ctx.check(self.lib.poi_cell_step(self.ctx.handle, ctypes.byref(P), ctypes.byref(T), _ptr(ids), n,
+                                              self.alpha_lambda[0], self.alpha_lambda[1], _ptr(out), self._stream()))
+        if not sync:
+            return out
+        bad = self.ctx.take_bad_ids(self._stream().value)
+        if bad:
+            raise IndexError("%d user(s) of the batch hold an id outside the tables: the launch moved nothing" % bad)
+        return out.cpu().numpy()
+
+    def predict_device(self, idxs):
+        ids, out_row = self._by_length(idxs)
+        n = ids.numel()
+        hts = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+        P, T = self._cparams(snapshot=True), self._tables()
+        self.ctx.check(self.lib.poi_cell_predict(self.ctx.handle, ctypes.byref(P), ctypes.byref(T), _ptr(ids), _ptr(out_row), n, _ptr(hts),
+                                                 self._stream()))
+        return hts
+
+
+class Lstm(_CellModel):
+    """public/GRU.py:502-657 - the mini-batch LSTM baseline: gates i, f, g, o, cell state c; ui, wh (4, D, D), bi (4, D), c0 (D)."""
+
+    _cell = _lib.CELL_LSTM
+    _gates = (4,)
+
+
+class Rnn(_CellModel):
+    """public/GRU.py:661-809 - the mini-batch sigmoid RNN baseline: h = sigmoid(ui x + wh h + bi); ui, wh (D, D), bi (D)."""
+
+    _cell = _lib.CELL_RNN
+    _gates = ()
 
 
 class OboSpatialGru(GruBasic):
