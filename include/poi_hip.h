@@ -56,6 +56,8 @@ extern "C" {
  * entries unchanged). */
 /* additive to 9: mini-batch Lstm / Rnn - new entry points poi_cell_step, poi_cell_predict and poi_cell_params, option "cell_grid", plan
  * keys for them (existing entries unchanged). */
+/* additive to 9: online sessions - new entry points poi_session_advance and poi_session_sts, option "session_tile_min", plan keys
+ * "session_path" / "session_tiles" / "session_tile_min" (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -135,7 +137,9 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * engine ran and every other flag is 0.  The hyb_* values live in the tile engine's workspace: POI_EINVAL once a later tile-engine
  * launch (poi_gru_predict included) may have reused it.
  * Additive to 9: "cell_kernel" and "cell_grid" - the gate-block count (POI_CELL_RNN / POI_CELL_LSTM) of the recurrent kernel and the
- * workgroups of its persistent grid when the last training launch was a poi_cell_step, 0 otherwise. */
+ * workgroups of its persistent grid when the last training launch was a poi_cell_step, 0 otherwise.
+ * Additive to 9: "session_path", "session_tiles", "session_tile_min" - written by poi_session_advance (which leaves the other keys as they
+ * are and also makes the plan readable). */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -197,6 +201,7 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *       tiles - 158 CUs idle behind the longest tile's 49-step chain: 678 -> 632 us.  Every sequence still goes through one of the two kernel
  *       families that hold it to the oracle on their own; a sequence's values depend on which one (inside the bars), identical launches are bitwise
  *       identical.  "hybrid_force" n (tests): n leading sequences per workgroup whatever the cost model says;
+ *   "session_tile_min" n (default 512): poi_session_advance calls of at least n events take the 16-event tile kernel.
  *   "cell_grid" n (default 0 = no cap): poi_cell_step / poi_cell_predict run their recurrent kernel on at most n workgroups (the persistent
  *       grid is min(sequences, 512) otherwise) - bitwise the same result for every n. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
@@ -608,6 +613,38 @@ int poi_cell_step(poi_ctx* ctx, const poi_cell_params* prm, const poi_seq_tables
                   float alpha, float lambda, float* out /* n_seq: -sum_t log sigmoid(u_t) per user */, void* stream);
 int poi_cell_predict(poi_ctx* ctx, const poi_cell_params* prm, const poi_seq_tables* tab, const int32_t* uidx, const int32_t* out_row,
                      int32_t n, float* hts, void* stream);   /* prm->lt = the snapshot */
+
+/* ---- online sessions (additive to 9; new - the reference can only rerun whole training sequences) ----------------------------------
+ * Per-slot recurrent state of the GRU family (OboSpatialGru, OboGru, Gru: one cell) kept on the device and advanced ONE check-in at a
+ * time.  State of slot s, owned by the caller: h (n_slot, D) FLOAT64 (one rounding less per step than a float32 state; 8 D bytes per
+ * slot), sts (n_slot, n_dist + 1) float32 (spatial only), last_poi (n_slot) int32 with -1 = no check-in yet, steps (n_slot) int32.
+ * poi_session_advance applies n events (slot[i], poi[i]) - the cell step of seq_predict (public/GRU_Spatial.py:231-288,
+ * public/GRU.py:154-202) on the snapshots prm->lt / prm->di:
+ *   d      = n_dist if last_poi[s] < 0, else bin(coords[j], coords[last_poi[s]])  (data.dist_pos_bins: same argument order, cphi / thr)
+ *   x      = [lt[j] | di[d]]  (spatial)  or  lt[j]  (plain: prm->di / vs / bs NULL, n_dist 0; coords / cphi / thr / sts may be NULL)
+ *   z, r   = sigmoid(ui[0:2] x + wh[0:2] h + bi[0:2]);  c = tanh(ui[2] x + wh[2] (r * h) + bi[2])
+ *   h[s]   = (1 - z) * h + z * c;  last_poi[s] = j;  steps[s] += 1;  sts[s] = softmax(vs h[s] + bs)  (spatial)
+ * so a zeroed slot (h = 0, last_poi = -1) advanced through p[0 .. L-1] holds what poi_gru_predict returns for that training row.
+ * The update is in place; hts_out (n, D) / sts_out (n, n_dist + 1) are optional float32 copies of the new rows.  dd in metres.
+ * Tables are float32, the POI snapshot may be a registered half table; a half di, or more than 4095 bins: POI_ENOTSUP.  Products,
+ * gate sums and the softmax are float64.  No atomics touch a result and every sum has a fixed order: identical calls give bitwise
+ * identical state.
+ * Repeated slots: a slot named by MORE THAN ONE event of a call is refused - every event of it is treated as a bad id - because
+ * the events of a call run concurrently.  Split such a batch into successive calls that keep each slot's order (models.Session.advance).
+ * Bad ids: a slot outside [0, n_slot) or a POI outside [0, n_item) leaves the state untouched, gives NaN rows in hts_out / sts_out
+ * and is counted (poi_ctx_take_bad_ids).
+ * Two launch regimes: below "session_tile_min" events (poi_ctx_set_option, default 512) one workgroup per event streams the weights
+ * from L2 (latency bound: live traffic); from there on 16 events per workgroup run on the float64 matrix cores (replay / bulk; needs
+ * D % 16 == 0 and the tile's LDS, else the event path serves every size).  poi_ctx_last_plan: "session_path" (0 event, 1 tile),
+ * "session_tiles" (workgroups of the tile kernel, 0 on the event path), "session_tile_min" (the switch point in force).
+ * Timing names: "session_advance", "session_sts".
+ * poi_session_sts: the head alone - sts_out (n, n_dist + 1) row i = softmax(vs h[slot[i]] + bs), for state seeded from outside
+ * (poi_gru_predict rows, a checkpoint); a slot out of range gives a NaN row and is counted. */
+int poi_session_advance(poi_ctx* ctx, const poi_gru_params* prm, const double* coords, const double* cphi, const double* thr, double dd,
+                        double* h, float* sts, int32_t* last_poi, int32_t* steps, int32_t n_slot, const int32_t* slot,
+                        const int32_t* poi, int32_t n, float* hts_out, float* sts_out, void* stream);
+int poi_session_sts(poi_ctx* ctx, const poi_gru_params* prm, const double* h, int32_t n_slot, const int32_t* slot, int32_t n,
+                    float* sts_out, void* stream);
 
 /* ---- multi-GPU reconciliation (8e; new - the reference is single-process) ----------------------
  * Users are sharded across ranks, every rank trains on a full parameter replica with no data-path collective,

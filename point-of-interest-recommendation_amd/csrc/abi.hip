@@ -79,7 +79,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR
@@ -95,6 +95,9 @@ struct poi_ctx {
   // mini-batch Lstm / Rnn: packed weights, per-position-row state, sort buffers, chunk partials, new-row slots
   DevBuf cell_ws;
   int cell_grid = 0;        // option "cell_grid": cap of the recurrent kernel's persistent grid (0: none)
+  // online sessions: per-slot claims of the repeated-slot check
+  DevBuf sess_owner;
+  int sess_tile_min = 512;  // option "session_tile_min": poi_session_advance calls of at least this many events take the tile kernel
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)
@@ -1209,6 +1212,76 @@ int poi_cell_predict(poi_ctx* c, const poi_cell_params* P, const poi_seq_tables*
 }
 
 // ---------------------------------------------------------------------------------------------
+// online sessions (session.hip)
+// ---------------------------------------------------------------------------------------------
+static int session_check(poi_ctx* c, const poi_gru_params* P, bool spatial, const char* who) {
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, P->dim);
+  if (P->n_item <= 0) return fail(c, POI_EINVAL, "%s: n_item must be positive", who);
+  if (spatial && (!P->di || !P->vs || !P->bs || P->n_dist <= 0)) return fail(c, POI_EINVAL, "%s: the spatial cell needs di / vs / bs and n_dist > 0", who);
+  if (!spatial && (P->di || P->vs || P->bs || P->n_dist != 0)) return fail(c, POI_EINVAL, "%s: the plain cell takes di / vs / bs NULL and n_dist 0", who);
+  if (spatial && P->n_dist + 1 > 4096) return fail(c, POI_ENOTSUP, "%s: at most 4095 distance bins", who);
+  if (spatial && is_f16(c, P->di)) return fail(c, POI_ENOTSUP, "%s: the distance table must be float32 (only the POI snapshot may be a half table)", who);
+  return POI_OK;
+}
+
+static void session_fill(poi_ctx* c, poi::SessArgs& A, const poi_gru_params* P, bool spatial) {
+  A = poi::SessArgs{};
+  A.lt = P->lt; A.lt_f16 = is_f16(c, P->lt);
+  A.di = P->di; A.ui = P->ui; A.wh = P->wh; A.bi = P->bi; A.vs = P->vs; A.bs = P->bs;
+  A.n_item = P->n_item; A.n_dist = spatial ? P->n_dist : 0; A.dim = P->dim; A.xw = spatial ? 2 * P->dim : P->dim; A.spatial = spatial ? 1 : 0;
+}
+
+int poi_session_advance(poi_ctx* c, const poi_gru_params* P, const double* coords, const double* cphi, const double* thr, double dd,
+                        double* h, float* sts, int32_t* last_poi, int32_t* steps, int32_t n_slot, const int32_t* slot,
+                        const int32_t* poi, int32_t n, float* hts_out, float* sts_out, void* stream) {
+  if (!c || !P) return fail(c, POI_EINVAL, "poi_session_advance: NULL ctx/params");
+  if (!P->lt || !P->ui || !P->wh || !P->bi) return fail(c, POI_EINVAL, "poi_session_advance: lt/ui/wh/bi must be non-NULL");
+  const bool spatial = P->di != nullptr || P->n_dist != 0;
+  int rc = session_check(c, P, spatial, "poi_session_advance");
+  if (rc) return rc;
+  if (spatial && (!coords || !cphi || !thr || !sts || !(dd > 0))) return fail(c, POI_EINVAL, "poi_session_advance: the spatial cell needs coords / cphi / thr / sts and dd > 0");
+  if (!h || !last_poi || !steps || n_slot <= 0) return fail(c, POI_EINVAL, "poi_session_advance: h / last_poi / steps NULL or n_slot <= 0");
+  if (!slot || !poi || n < 0) return fail(c, POI_EINVAL, "poi_session_advance: slot / poi NULL or n < 0");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::SessArgs A;
+  session_fill(c, A, P, spatial);
+  A.coords = coords; A.cphi = cphi; A.thr = thr; A.dd = dd;
+  A.h = h; A.sts = sts; A.last_poi = last_poi; A.steps = steps; A.n_slot = n_slot;
+  A.slot = slot; A.poi = poi; A.n = n; A.hts_out = hts_out; A.sts_out = sts_out;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  const int tile = n >= c->sess_tile_min && poi::sess_tile_supported(A.dim, A.xw, A.n_dist + 1, A.spatial);
+  // repeated slots: one event needs no check, small event launches scan the call inside the kernel, everything else claims the slots
+  if (n > 1 && (tile || n > SESS_SCAN_MAX)) {
+    if ((rc = ensure(c, c->sess_owner, sizeof(int) * (size_t)n_slot, st))) return rc;
+    A.owner = (int*)c->sess_owner.p;
+  }
+  c->plan.valid = 1; c->plan.session_path = tile; c->plan.session_tiles = tile ? (n + 15) / 16 : 0; c->plan.session_tile_min = c->sess_tile_min;
+  HIPCHK(c, poi::launch_session(A, tile, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_session_sts(poi_ctx* c, const poi_gru_params* P, const double* h, int32_t n_slot, const int32_t* slot, int32_t n, float* sts_out,
+                    void* stream) {
+  if (!c || !P) return fail(c, POI_EINVAL, "poi_session_sts: NULL ctx/params");
+  int rc = session_check(c, P, true, "poi_session_sts");
+  if (rc) return rc;
+  if (!h || !slot || !sts_out || n < 0 || n_slot <= 0) return fail(c, POI_EINVAL, "poi_session_sts: h / slot / sts_out NULL, n < 0 or n_slot <= 0");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::SessArgs A;
+  session_fill(c, A, P, true);
+  A.h = const_cast<double*>(h); A.n_slot = n_slot; A.slot = slot; A.n = n; A.sts_out = sts_out; A.head_only = 1;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  HIPCHK(c, poi::launch_session(A, 0, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // POI2Vec (poi2vec.hip)
 static int poi2vec_check(poi_ctx* c, const poi_poi2vec_params* P, const char* who) {
   if (!c || !P || !P->xu || !P->wl || !P->pb || !P->routes || !P->lrs || !P->probs || !P->rid) return fail(c, POI_EINVAL, "%s: NULL argument", who);
@@ -1642,7 +1715,7 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
   struct Opt { const char* name; int* p; int lo, hi; };
   const Opt opts[] = {{"forward_table_compact", &c->xcomp, 0, 1}, {"forward_table_compact_min", &c->xcomp_min, 0, 1 << 30}, {"head_split", &c->head3, 0, 1},
                       {"early_bins", &c->early_bins, 0, 1}, {"hot_bins", &c->hot_bins, 0, 1}, {"hybrid", &c->hybrid, 0, 1}, {"hybrid_min", &c->hyb_min, 0, 1 << 30}, {"hybrid_max", &c->hyb_max, 0, 1 << 30}, {"hybrid_force", &c->hyb_force, 0, 1 << 30},
-                      {"cell_grid", &c->cell_grid, 0, 1 << 30}};
+                      {"cell_grid", &c->cell_grid, 0, 1 << 30}, {"session_tile_min", &c->sess_tile_min, 1, 1 << 30}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);
@@ -1719,7 +1792,9 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"hyb", &poi_ctx::LastPlan::hyb}, {"bintab", &poi_ctx::LastPlan::bintab}, {"ppoi", &poi_ctx::LastPlan::ppoi}, {"listed", &poi_ctx::LastPlan::listed},
       {"fwd_tab", &poi_ctx::LastPlan::fwd_tab}, {"xft", &poi_ctx::LastPlan::xft}, {"xcomp", &poi_ctx::LastPlan::xcomp},
       {"head_split", &poi_ctx::LastPlan::head_split}, {"efuse", &poi_ctx::LastPlan::efuse}, {"early_bins", &poi_ctx::LastPlan::early_bins},
-      {"fork", &poi_ctx::LastPlan::fork}, {"cell_kernel", &poi_ctx::LastPlan::cell_kernel}, {"cell_grid", &poi_ctx::LastPlan::cell_grid}};
+      {"fork", &poi_ctx::LastPlan::fork}, {"cell_kernel", &poi_ctx::LastPlan::cell_kernel}, {"cell_grid", &poi_ctx::LastPlan::cell_grid},
+      {"session_path", &poi_ctx::LastPlan::session_path}, {"session_tiles", &poi_ctx::LastPlan::session_tiles},
+      {"session_tile_min", &poi_ctx::LastPlan::session_tile_min}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

@@ -490,6 +490,27 @@ int cell_chunk_rows(int n_seq, int max_len);
 hipError_t launch_cell_step(CellArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_cell_predict(CellArgs& A, hipStream_t st, Timing* tm);
 
+// Online sessions (session.hip): per-slot recurrent state advanced one check-in at a time
+#define SESS_TILE_LDS_MAX (152 * 1024)      // dynamic LDS the tile kernel may ask for (opt-in per device)
+#define SESS_EVENT_GRID_MAX 16384           // workgroups of the event kernel (it strides over larger launches)
+#define SESS_SCAN_MAX 256                   // event path: up to this many events a workgroup scans the call's slots for repeats itself
+struct SessArgs {
+  const void* lt; int lt_f16;               // POI snapshot: float32, or IEEE half when lt_f16
+  const float *di, *ui, *wh, *bi, *vs, *bs; // di / vs / bs null: the plain cell
+  int n_item, n_dist, dim, xw, spatial;     // xw = D or 2 D columns of ui
+  const double *coords, *cphi, *thr; double dd;
+  double* h; float* sts; int *last_poi, *steps; int n_slot;      // the state, updated in place
+  const int *slot, *poi; int n;
+  float *hts_out, *sts_out;                 // optional (n, D) / (n, n_dist + 1) copies of the new rows (NaN rows: rejected events)
+  int* bad;                                 // device counter of rejected events (poi_ctx_take_bad_ids)
+  int* owner;                               // (n_slot) scratch of the repeated-slot check, or null: the event kernel scans the call
+  int head_only;                            // poi_session_sts: softmax(vs . h[slot] + bs) to sts_out, nothing else
+};
+size_t sess_tile_lds(int D, int xw, int NB, int spatial);
+size_t sess_event_lds(int D, int xw, int NB, int spatial);
+bool sess_tile_supported(int D, int xw, int NB, int spatial);
+hipError_t launch_session(SessArgs& A, int tile, hipStream_t st, Timing* tm);
+
 // scoring / top-K
 struct ScoreArgs {
   const float *users, *items; int items_f16;      // items: float32, or IEEE half when items_f16

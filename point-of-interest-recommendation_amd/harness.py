@@ -510,3 +510,17 @@ def train_poi2vec(ds, p=None, device="cuda:0", log=print):
             model.alpha_lambda = [lr / 10, p["lambda"]]
         pre_loss = loss
     return model, best, history
+
+
+def serve_replay(model, ds=None, k=20):
+    """Online use of a trained GRU-family model (models.Session): seed every user's state from the training rows (`load_history`),
+    advance every user by their first held-out test POI as if it had just been checked in, and recommend the next top-k from the new
+    state.  `ds` is the data set the model was built from (its tables already live in the model; accepted for symmetry with the
+    train_* drivers).  Returns (session, (n_user, k) int32 device indices)."""
+    s = model.session()
+    s.load_history()
+    users = np.arange(model.n_user)
+    tes = model.tes_buys_masks[:, 0].cpu().numpy()
+    ok = (model.tes_masks[:, 0].cpu().numpy() > 0) & (tes < model.n_item)
+    s.advance(users[ok], tes[ok])
+    return s, s.recommend(users, k)

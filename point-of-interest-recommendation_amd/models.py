@@ -426,6 +426,10 @@ class GruBasic(_Base):
         T.n_user, T.len_max, T.max_len = self.n_user, self.len_max, self.max_len
         return T
 
+    def session(self, n_slot=None):
+        """Online state for this model (Session): per-slot h / last POI advanced one check-in at a time, top-K from it."""
+        return Session(self, n_slot)
+
     def predict(self, idxs):
         """public/GRU.py:204-205 -> hts ndarray (n, D)."""
         return np.ascontiguousarray(self.predict_device(idxs)[:, :self.dim].cpu().numpy())
@@ -911,6 +915,249 @@ class OboCARNN(GruBasic):
     def compute_sub_topk(self, start_end, k, return_scores=False):
         """Valuate.py:132-146 on the CA-RNN scores: the (n, n_item) rows stay on the device, poi_topk selects."""
         return self._topk_from_scores(start_end, k, return_scores)
+
+
+# =================================================================================================
+class Session:
+    """Online sessions of the GRU family (OboSpatialGru, OboGru, Gru): per-slot recurrent state on the device, advanced ONE check-in at a
+    time (poi_session_advance, include/poi_hip.h) and ranked with the model's own scoring rule.  A slot holds h (kdim float64; `state`
+    shows the logical dim), last_poi (-1: none yet), steps and - spatial - sts.  A fresh slot advanced through p[0 .. L-1] holds exactly
+    what `predict` returns for a user whose training row is that sequence: every step reads the evaluation SNAPSHOTS trained_items /
+    trained_dists as they are at the call, so a session follows update_trained_items() / update_trained_dists() and never changes a model
+    parameter."""
+
+    def __init__(self, model, n_slot=None):
+        if not isinstance(model, GruBasic) or isinstance(model, (_CellModel, OboCARNN)):
+            raise _lib.PoiError("Session covers the GRU family (OboSpatialGru, OboGru, Gru): %s is out of scope" % type(model).__name__)
+        if model.spatial and model.coords is None:
+            raise _lib.PoiError("session on the spatial model needs coords= at construction")
+        self.m = m = model
+        self.spatial = bool(model.spatial)
+        self.n_slot = int(m.n_user if n_slot is None else n_slot)
+        if self.n_slot <= 0:
+            raise ValueError("n_slot must be positive")
+        dev = m.device
+        self.h = torch.zeros((self.n_slot, m.kdim), dtype=torch.float64, device=dev)
+        self.last_poi = torch.full((self.n_slot,), -1, dtype=torch.int32, device=dev)
+        self.steps = torch.zeros(self.n_slot, dtype=torch.int32, device=dev)
+        self.nb = m.n_dist + 1 if self.spatial else 0
+        self.sts = torch.zeros((self.n_slot, self.nb), dtype=torch.float32, device=dev) if self.spatial else None
+
+    # ---- ids ------------------------------------------------------------------------------------
+    def _host_ids(self, name, ids, hi):
+        a = np.atleast_1d(np.asarray(ids)).astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= hi):
+            raise IndexError("%s must lie in [0, %d) (found %d..%d)" % (name, hi, int(a.min()), int(a.max())))
+        return a
+
+    def _slot_tensor(self, slots):
+        """int64 device tensor of slot ids (host ids are range-checked; slots=None: every slot)."""
+        if slots is None:
+            return torch.arange(self.n_slot, device=self.m.device)
+        if isinstance(slots, torch.Tensor):
+            return slots.to(self.m.device).long().reshape(-1)
+        return torch.as_tensor(self._host_ids("slots", slots, self.n_slot)).to(self.m.device)
+
+    def _i32(self, a):
+        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.m.device)
+
+    # ---- state ----------------------------------------------------------------------------------
+    def reset(self, slots=None):
+        """h = h0 = 0, last_poi = -1, steps = 0 (every slot, or the given ones)."""
+        if slots is None:
+            self.h.zero_(); self.last_poi.fill_(-1); self.steps.zero_()
+            if self.spatial:
+                self.sts.zero_()
+            return
+        ids = self._slot_tensor(slots)
+        self.h[ids] = 0.0; self.last_poi[ids] = -1; self.steps[ids] = 0
+        if self.spatial:
+            self.sts[ids] = 0.0
+
+    def load_history(self, users=None):
+        """Seed slot u from user u's training row of the model's own tables: h and sts are the rows `predict_device` returns (what the
+        evaluation path ranks with), last_poi the last train POI, steps the length."""
+        m = self.m
+        a = np.arange(m.n_user) if users is None else self._host_ids("users", users, min(m.n_user, self.n_slot))
+        if a.size and a.max() >= self.n_slot:
+            raise IndexError("users must lie in [0, %d): the session has that many slots" % self.n_slot)
+        out = m.predict_device(a)
+        ids = torch.as_tensor(a).to(m.device)
+        hts, sts = out if self.spatial else (out, None)
+        self.h[ids] = hts.double()
+        last = torch.as_tensor(m._off_host[1:].astype(np.int64)[a] - 1).to(m.device)
+        self.last_poi[ids] = m.p.index_select(0, last)
+        self.steps[ids] = torch.as_tensor(np.asarray(m._lens)[a].astype(np.int32)).to(m.device)
+        if self.spatial:
+            self.sts[ids] = sts
+
+    def seed(self, slots, h, last_poi, steps=None):
+        """State from outside (a checkpoint, another model's rows): h (n, dim) or (n, kdim), last_poi (n) with -1 = none; sts is
+        recomputed through the head (poi_session_sts)."""
+        m = self.m
+        ids = self._slot_tensor(slots)
+        n = ids.numel()
+        ht = h if isinstance(h, torch.Tensor) else torch.as_tensor(np.asarray(h, np.float64))
+        self.h[ids] = m._pad_cols(ht.to(m.device, torch.float64).reshape(n, -1))
+        lp = self._host_ids("last_poi + 1", np.asarray(last_poi, np.int64) + 1, m.n_item + 1) - 1
+        self.last_poi[ids] = self._i32(lp)
+        self.steps[ids] = self._i32(np.zeros(n) if steps is None else steps)
+        if self.spatial and n:
+            P = m._params(snapshot=True)
+            out = torch.empty((n, self.nb), dtype=torch.float32, device=m.device)
+            sl = ids.int().contiguous()
+            m.ctx.check(m.lib.poi_session_sts(m.ctx.handle, ctypes.byref(P), _ptr(self.h), self.n_slot, _ptr(sl), n, _ptr(out), m._stream()))
+            self.sts[ids] = out
+
+    def state(self, slots=None):
+        """Host copies at the logical dim: dict(h (n, dim) float64, last_poi, steps[, sts])."""
+        ids = self._slot_tensor(slots)
+        out = dict(h=np.ascontiguousarray(self.h.index_select(0, ids)[:, :self.m.dim].cpu().numpy()),
+                   last_poi=self.last_poi.index_select(0, ids).cpu().numpy(), steps=self.steps.index_select(0, ids).cpu().numpy())
+        if self.spatial:
+            out["sts"] = self.sts.index_select(0, ids).cpu().numpy()
+        return out
+
+    # ---- advance --------------------------------------------------------------------------------
+    def _launch(self, slot_ptr, poi_ptr, n, hts_out=None, sts_out=None):
+        m = self.m
+        P = m._params(snapshot=True)
+        sp = self.spatial
+        m.ctx.check(m.lib.poi_session_advance(m.ctx.handle, ctypes.byref(P), _ptr(m.coords if sp else None), _ptr(m._cphi if sp else None),
+                                              _ptr(m._binthr if sp else None), m.dd * 1000.0 if sp else 0.0, _ptr(self.h), _ptr(self.sts),
+                                              _ptr(self.last_poi), _ptr(self.steps), self.n_slot, ctypes.c_void_p(slot_ptr),
+                                              ctypes.c_void_p(poi_ptr), int(n), _ptr(hts_out), _ptr(sts_out), m._stream()))
+
+    def _raise_bad(self):
+        bad = self.m.ctx.take_bad_ids(self.m._stream().value)
+        if bad:
+            raise IndexError("%d event(s) named a slot outside [0, %d), a POI outside [0, %d) or - in a device batch - a slot more than once: "
+                             "those slots were left untouched" % (bad, self.n_slot, self.m.n_item))
+
+    def advance(self, slots, pois, sync=True, return_state=False):
+        """Apply the check-ins (slots[i], pois[i]).  Host arrays are range-checked first (IndexError, nothing moves) and may name a slot
+        several times: the batch is split into successive launches that keep each slot's order.  Device tensors are one launch and are
+        checked by the kernel: a bad id or a repeated slot leaves that slot untouched and raises IndexError (with sync=True; otherwise
+        the count stays readable through ctx.take_bad_ids()).  return_state: (hts (n, kdim)[, sts (n, n_dist + 1)]) float32 device rows
+        of the new state, in the order of the call."""
+        m = self.m
+        dev_in = isinstance(slots, torch.Tensor) or isinstance(pois, torch.Tensor)
+        if dev_in:
+            st = slots if isinstance(slots, torch.Tensor) else self._i32(self._host_ids("slots", slots, self.n_slot))
+            pt = pois if isinstance(pois, torch.Tensor) else self._i32(self._host_ids("pois", pois, m.n_item))
+            st = st.to(m.device, torch.int32).contiguous().reshape(-1); pt = pt.to(m.device, torch.int32).contiguous().reshape(-1)
+            rounds = [None]
+        else:
+            s = self._host_ids("slots", slots, self.n_slot)
+            j = self._host_ids("pois", pois, m.n_item)
+            st, pt = self._i32(s), self._i32(j)
+            rounds = [None]
+            if len(s) > 1 and len(np.unique(s)) < len(s):
+                order = np.argsort(s, kind="stable")
+                ss, pos = s[order], np.arange(len(s))
+                first = np.maximum.accumulate(np.where(np.r_[True, ss[1:] != ss[:-1]], pos, 0))
+                rank = np.empty(len(s), np.int64)
+                rank[order] = pos - first                     # occurrence number of the event within its slot
+                rounds = [np.nonzero(rank == r)[0] for r in range(int(rank.max()) + 1)]
+        if st.numel() != pt.numel():
+            raise ValueError("slots and pois must have the same length (%d vs %d)" % (st.numel(), pt.numel()))
+        n = st.numel()
+        hts = torch.empty((n, m.kdim), dtype=torch.float32, device=m.device) if return_state else None
+        sts = torch.empty((n, self.nb), dtype=torch.float32, device=m.device) if return_state and self.spatial else None
+        for sel in rounds:
+            if sel is None:
+                self._launch(st.data_ptr(), pt.data_ptr(), n, hts, sts)
+                continue
+            it = torch.as_tensor(sel).to(m.device)
+            s_r, p_r = st.index_select(0, it), pt.index_select(0, it)
+            h_r = torch.empty((len(sel), m.kdim), dtype=torch.float32, device=m.device) if return_state else None
+            t_r = torch.empty((len(sel), self.nb), dtype=torch.float32, device=m.device) if sts is not None else None
+            self._launch(s_r.data_ptr(), p_r.data_ptr(), len(sel), h_r, t_r)
+            if return_state:
+                hts[it] = h_r
+                if sts is not None:
+                    sts[it] = t_r
+        if sync:
+            self._raise_bad()
+        if return_state:
+            return (hts, sts) if self.spatial else hts
+
+    def replay(self, off, p_flat, slots=None, sync=True):
+        """Advance through CSR sequences (the layout of data.padded_to_csr): sequence k = p_flat[off[k] : off[k + 1]] goes to slots[k]
+        (default k).  The events are laid out step-major on the device once; launch t then carries the slots whose sequence is longer
+        than t, straight from that layout - no host round trip per step beyond the launch."""
+        m = self.m
+        off = np.asarray(off.cpu() if isinstance(off, torch.Tensor) else off, np.int64)
+        p = np.asarray(p_flat.cpu() if isinstance(p_flat, torch.Tensor) else p_flat, np.int64)
+        lens = np.diff(off)
+        nseq = len(lens)
+        sl = np.arange(nseq) if slots is None else np.atleast_1d(np.asarray(slots)).astype(np.int64)
+        if len(sl) != nseq:
+            raise ValueError("replay: %d sequences but %d slots" % (nseq, len(sl)))
+        self._host_ids("slots", sl, self.n_slot)
+        if len(np.unique(sl)) != nseq:
+            raise ValueError("replay: every sequence needs a slot of its own")
+        if nseq == 0 or lens.max() <= 0:
+            return
+        self._host_ids("pois", p[off[0]:off[-1]], m.n_item)
+        order = np.argsort(-lens, kind="stable")
+        lo, so, st0 = lens[order], sl[order], off[:-1][order]
+        L = int(lo[0])
+        cnt = [int(np.searchsorted(-lo, -t, side="left")) for t in range(L)]      # sequences longer than t (lo is descending)
+        s_sm = np.concatenate([so[:c] for c in cnt])
+        p_sm = np.concatenate([p[st0[:c] + t] for t, c in enumerate(cnt)])
+        sd, pd = self._i32(s_sm), self._i32(p_sm)
+        pos = 0
+        for c in cnt:
+            self._launch(sd.data_ptr() + 4 * pos, pd.data_ptr() + 4 * pos, c)
+            pos += c
+        if sync:
+            self._raise_bad()
+
+    # ---- recommend ------------------------------------------------------------------------------
+    def recommend(self, slots, k, return_scores=False):
+        """(n, k) int32 device indices by descending score, ties by ascending index: h . trained_items[:-1]^T, plus - spatial -
+        wd * sts[bin(last_poi, .)] for bins below n_dist.  A slot without a check-in has no distance term."""
+        m = self.m
+        ids = self._slot_tensor(slots)
+        n, k = ids.numel(), int(k)
+        users = self.h.index_select(0, ids).float().contiguous()
+        idx = torch.empty((n, k), dtype=torch.int32, device=m.device)
+        sc = torch.empty((n, k), dtype=torch.float32, device=m.device) if return_scores else None
+        wd = st = lp = None
+        if self.spatial:
+            pad = ((n + 31) // 32) * 32                  # whole 32-row tiles must be readable, column n_dist ("too far") is zero
+            lpr = self.last_poi.index_select(0, ids)
+            st = torch.zeros((pad, self.nb), dtype=torch.float32, device=m.device)
+            st[:n] = self.sts.index_select(0, ids) * (lpr >= 0).float()[:, None]
+            st[:, m.n_dist] = 0.0
+            lp = lpr.clamp(min=0).contiguous()
+            wd = m.wd.t
+        if k <= 32:
+            if self.spatial:
+                m.ctx.check(m.lib.poi_score_topk_geo(m.ctx.handle, _ptr(users), _ptr(m.trained_items.t), n, m.n_item, m.kdim, _ptr(wd), _ptr(st),
+                                                     _ptr(m.coords), _ptr(m._cphi), _ptr(m._binthr), _ptr(lp), m.n_dist, m.dd * 1000.0, k,
+                                                     _ptr(idx), _ptr(sc), m._stream()))
+            else:
+                m.ctx.check(m.lib.poi_score_topk(m.ctx.handle, _ptr(users), _ptr(m.trained_items.t), n, m.n_item, m.kdim, None, None, k,
+                                                 _ptr(idx), _ptr(sc), m._stream()))
+            return (idx, sc) if return_scores else idx
+        if k > 64:
+            raise _lib.PoiError("top-K supports k <= 64 (got %d)" % k)
+        step = max(1, min(n, (1 << 28) // max(m.n_item, 1)))      # explicit score rows, <= 1 GiB at a time, + poi_topk
+        for o in range(0, n, step):
+            c = min(step, n - o)
+            prob = None
+            if self.spatial:
+                prob = torch.empty((c, m.n_item), dtype=torch.float32, device=m.device)
+                m.ctx.check(m.lib.poi_dist_prob(m.ctx.handle, _ptr(m.coords), _ptr(m._cphi), _ptr(m._binthr), _ptr(lp[o:o + c]), _ptr(st[o:o + c]), c,
+                                                m.n_item, m.n_dist, m.dd * 1000.0, _ptr(prob), m._stream()))
+            full = torch.empty((c, m.n_item), dtype=torch.float32, device=m.device)
+            m.ctx.check(m.lib.poi_score_all(m.ctx.handle, _ptr(users[o:o + c]), _ptr(m.trained_items.t), c, m.n_item, m.kdim, _ptr(wd), _ptr(prob),
+                                            _ptr(full), m._stream()))
+            m.ctx.check(m.lib.poi_topk(m.ctx.handle, _ptr(full), c, m.n_item, k, ctypes.c_void_p(idx.data_ptr() + 4 * o * k),
+                                       ctypes.c_void_p(sc.data_ptr() + 4 * o * k) if sc is not None else None, m._stream()))
+        return (idx, sc) if return_scores else idx
 
 
 # =================================================================================================
