@@ -58,6 +58,8 @@ extern "C" {
  * keys for them (existing entries unchanged). */
 /* additive to 9: online sessions - new entry points poi_session_advance and poi_session_sts, option "session_tile_min", plan keys
  * "session_path" / "session_tiles" / "session_tile_min" (existing entries unchanged). */
+/* additive to 9: VBPR - new entry points poi_vbpr_step, poi_vbpr_items, poi_vbpr_users and poi_vbpr_params, option "vbpr_grid" (existing
+ * entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -203,7 +205,9 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *       identical.  "hybrid_force" n (tests): n leading sequences per workgroup whatever the cost model says;
  *   "session_tile_min" n (default 512): poi_session_advance calls of at least n events take the 16-event tile kernel.
  *   "cell_grid" n (default 0 = no cap): poi_cell_step / poi_cell_predict run their recurrent kernel on at most n workgroups (the persistent
- *       grid is min(sequences, 512) otherwise) - bitwise the same result for every n. */
+ *       grid is min(sequences, 512) otherwise) - bitwise the same result for every n.
+ *   "vbpr_grid" n (default 0 = no cap): every kernel of poi_vbpr_step / poi_vbpr_items runs on at most n workgroups - bitwise the same
+ *       result for every n (tests). */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -613,6 +617,42 @@ int poi_cell_step(poi_ctx* ctx, const poi_cell_params* prm, const poi_seq_tables
                   float alpha, float lambda, float* out /* n_seq: -sum_t log sigmoid(u_t) per user */, void* stream);
 int poi_cell_predict(poi_ctx* ctx, const poi_cell_params* prm, const poi_seq_tables* tab, const int32_t* uidx, const int32_t* out_row,
                      int32_t n, float* hts, void* stream);   /* prm->lt = the snapshot */
+
+/* ---- VBPR (additive to ABI 9) - OboVBpr, public/BPR.py:245-335 ------------------------------------------------------------------------
+ * BPR-MF with a fixed per-item feature table and a trained dense projection.  Float32 tables on the device: ux, ue (n_user, D);
+ * lt (n_item + 1, D); ei (D, F); fi (n_item + 1, F), never written, row n_item the (zero) pad row.  D = dim a multiple of 4 up to 128,
+ * F = n_img a multiple of 4 up to 4096, every table 16-byte aligned (else POI_ENOTSUP / POI_EINVAL).
+ * poi_vbpr_step replaces bpr_train(uidx, [p, q]) (:268-319) for n triples, every right-hand side at the launch-entry values:
+ *   d = fi[p] - fi[q];  v = ei d;  x = ux[u] . (lt[p] - lt[q]) + ue[u] . v;  g = -sigmoid(-x);  loss_out[i] = -log sigmoid(x)
+ *   ux[u] -= alpha (g (lt[p] - lt[q]) + lambda ux[u])      ue[u] -= alpha (g v + lambda ue[u])
+ *   lt[p] -= alpha (g ux[u] + lambda lt[p])                lt[q] -= alpha (-g ux[u] + lambda lt[q])
+ *   ei    -= alpha (g ue[u] (x) d + lambda_ev ei)
+ * Launches of n > 1 triples follow "Batch semantics" above: a row of ux / ue / lt touched by k triples moves by min(k, cap) / k of their
+ * summed updates; ei, touched by all n_acc accepted triples, by min(n_acc, cap) / n_acc of -alpha (sum_i g_i ue[u_i] (x) d_i + n_acc
+ * lambda_ev ei).  n == 1 is the reference step for every cap; batch cap 0: POI_ENOTSUP.
+ * Arithmetic: both matrix products over the gathered differences - V = Dmat ei^T and d ei = G^T Dmat - run on the FLOAT64 matrix cores
+ * (v_mfma_f64_16x16x4_f64) from the float32 tables, as do x, g, the loss and the ei step; the row sums of ux / ue / lt are float32.  The
+ * n x F difference matrix is never stored; a triple's two feature rows are read twice per step.  No float atomics: the 4 n row touches
+ * are sorted by (table, row) and summed run by run; d ei is summed as row-chunk partials over the ACCEPTED triples in launch order (at
+ * most 64 chunks of 64 ceil(ceil(n / 64) / 64) triples: a function of n alone) added in chunk order.  Identical launches give bitwise
+ * identical tables on any grid ("vbpr_grid").
+ * Bad ids: a triple with u outside [0, n_user), p or q outside [0, n_item], or p == q moves nothing, has loss NaN and is counted once
+ * (poi_ctx_take_bad_ids).  Removing it from the launch leaves every row of ux / ue / lt and every loss bitwise equal, and ei too whenever
+ * both launches have the same chunk length (always up to 4096 triples).
+ * Scratch (context-owned, grows with the launch): 8 n_chunk D F + 20 n D + ~60 n bytes.  No device-to-host sync inside a launch.
+ * Timing names: "vbpr_fwd", "vbpr_wgrad", "vbpr_sort", "vbpr_rows", "vbpr_commit".
+ * poi_vbpr_items (update_trained_items, :321-329): items_out (n_item + 1, 2 D) = [lt | fi ei^T], the product on the same MFMA written
+ * straight into the right half.  Timing name: "vbpr_items".
+ * poi_vbpr_users (:331-335): users_out (n_user, 2 D) = [ux | ue].  Timing name: "vbpr_users".
+ * Scoring, top-K and AUC on the two outputs: poi_score_all / poi_score_topk / poi_auc_preference with dim = 2 D. */
+typedef struct poi_vbpr_params {
+  float* ux; float* lt; float* ue; float* ei; const float* fi;
+  int32_t n_user; int32_t n_item; int32_t dim; int32_t n_img;
+} poi_vbpr_params;
+int poi_vbpr_step(poi_ctx* ctx, const poi_vbpr_params* prm, const int32_t* uidx, const int32_t* p, const int32_t* q, int32_t n, float alpha,
+                  float lambda, float lambda_ev, float* loss_out /* n */, void* stream);
+int poi_vbpr_items(poi_ctx* ctx, const poi_vbpr_params* prm, float* items_out, void* stream);
+int poi_vbpr_users(poi_ctx* ctx, const poi_vbpr_params* prm, float* users_out, void* stream);
 
 /* ---- online sessions (additive to 9; new - the reference can only rerun whole training sequences) ----------------------------------
  * Per-slot recurrent state of the GRU family (OboSpatialGru, OboGru, Gru: one cell) kept on the device and advanced ONE check-in at a

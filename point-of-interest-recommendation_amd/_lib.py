@@ -44,6 +44,10 @@ class CellParams(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("lt", "ui", "wh", "bi")] + [("n_item", c_int32), ("dim", c_int32), ("cell", c_int32)]
 
 
+class VbprParams(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("ux", "lt", "ue", "ei", "fi")] + [(n, c_int32) for n in ("n_user", "n_item", "dim", "n_img")]
+
+
 CELL_RNN, CELL_LSTM = 1, 4          # POI_CELL_*: the number of gate blocks
 
 
@@ -140,6 +144,9 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p]),
     "poi_cell_step": (c_int, [c_void_p, POINTER(CellParams), POINTER(SeqTables), c_void_p, c_int32, c_float, c_float, c_void_p, c_void_p]),
     "poi_cell_predict": (c_int, [c_void_p, POINTER(CellParams), POINTER(SeqTables), c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "poi_vbpr_step": (c_int, [c_void_p, POINTER(VbprParams), c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p]),
+    "poi_vbpr_items": (c_int, [c_void_p, POINTER(VbprParams), c_void_p, c_void_p]),
+    "poi_vbpr_users": (c_int, [c_void_p, POINTER(VbprParams), c_void_p, c_void_p]),
     "poi_session_advance": (c_int, [c_void_p, POINTER(GruParams), c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                     c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "poi_session_sts": (c_int, [c_void_p, POINTER(GruParams), c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),

@@ -95,6 +95,9 @@ struct poi_ctx {
   // mini-batch Lstm / Rnn: packed weights, per-position-row state, sort buffers, chunk partials, new-row slots
   DevBuf cell_ws;
   int cell_grid = 0;        // option "cell_grid": cap of the recurrent kernel's persistent grid (0: none)
+  // VBPR step: dense-gradient chunk partials, sort buffers, per-triple values, window partial sums, new-row slots
+  DevBuf vb_ws;
+  int vbpr_grid = 0;        // option "vbpr_grid": cap of the workgroups of every VBPR kernel (0: none)
   // online sessions: per-slot claims of the repeated-slot check
   DevBuf sess_owner;
   int sess_tile_min = 512;  // option "session_tile_min": poi_session_advance calls of at least this many events take the tile kernel
@@ -233,7 +236,7 @@ int poi_ctx_destroy(poi_ctx* c) {
   if (!c) return POI_OK;
   DevBuf* all[] = {&c->ex_ws, &c->ex_slab, &c->ex_glt, &c->ex_gdi, &c->ws, &c->slab, &c->te_ws, &c->hslab, &c->zrow, &c->g_lt, &c->mult_lt, &c->nseq_lt, &c->g_di, &c->mult_di, &c->nseq_di, &c->seg_s, &c->seg_e, &c->pmark, &c->xc, &c->kc_dev, &c->uidx_stage, &c->out_stage, &c->ptab, &c->iota, &c->xw, &c->xg, &c->xflag, &c->bad_ids,
                    &c->g_wd, &c->mult_wd, &c->nseq_wd, &c->ca_ws, &c->ca_slab, &c->ca_scr, &c->ca2, &c->g_ux, &c->cnt_ux, &c->g_blt, &c->cnt_blt, &c->cand_s, &c->cand_i, &c->items_pk, &c->gbound, &c->st,
-                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->cell_ws};
+                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->cell_ws, &c->vb_ws};
   (void)hipDeviceSynchronize();
   c->tm.clear();
   drop_graphs(c);
@@ -845,6 +848,84 @@ int poi_bpr_step(poi_ctx* c, float* ux, float* lt, int32_t n_user, int32_t n_ite
     A.trail = fp;
   }
   HIPCHK(c, poi::launch_bpr(A, mode, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// VBPR (vbpr.hip)
+static int vbpr_check(poi_ctx* c, const poi_vbpr_params* P, const char* who, poi::VbprArgs& A) {
+  if (!c || !P) return fail(c, POI_EINVAL, "%s: NULL ctx/params", who);
+  if (!P->ux || !P->lt || !P->ue || !P->ei || !P->fi) return fail(c, POI_EINVAL, "%s: ux/lt/ue/ei/fi must be non-NULL", who);
+  if (is_f16(c, P->ux) || is_f16(c, P->lt) || is_f16(c, P->ue) || is_f16(c, P->ei) || is_f16(c, P->fi)) return fail(c, POI_ENOTSUP, "VBPR tables are float32 only");
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 128) return fail(c, POI_ENOTSUP, "VBPR: dim must be a multiple of 4 in [4, 128] (got %d)", P->dim);
+  if (P->n_img <= 0 || P->n_img % 4 != 0 || P->n_img > 4096) return fail(c, POI_ENOTSUP, "VBPR: n_img must be a multiple of 4 in [4, 4096] (got %d)", P->n_img);
+  if (((uintptr_t)P->fi | (uintptr_t)P->ei | (uintptr_t)P->ux | (uintptr_t)P->ue | (uintptr_t)P->lt) & 15) return fail(c, POI_EINVAL, "%s: the tables must be 16-byte aligned", who);
+  if (P->n_user <= 0 || P->n_item <= 0) return fail(c, POI_EINVAL, "%s: bad sizes", who);
+  if (2 * (int64_t)P->n_user + (int64_t)P->n_item + 1 >= ((int64_t)1 << 31) - 1) return fail(c, POI_ENOTSUP, "VBPR: 2 n_user + n_item + 1 must stay below 2^31");
+  memset(&A, 0, sizeof A);
+  A.ux = P->ux; A.lt = P->lt; A.ue = P->ue; A.ei = P->ei; A.fi = P->fi;
+  A.n_user = P->n_user; A.n_item = P->n_item; A.dim = P->dim; A.n_img = P->n_img;
+  A.sentinel = 2 * P->n_user + P->n_item + 1;
+  A.grid_cap = c->vbpr_grid;
+  return POI_OK;
+}
+
+int poi_vbpr_step(poi_ctx* c, const poi_vbpr_params* P, const int32_t* uidx, const int32_t* p, const int32_t* q, int32_t n, float alpha,
+                  float lambda, float lambda_ev, float* loss_out, void* stream) {
+  poi::VbprArgs A;
+  int rc = vbpr_check(c, P, "poi_vbpr_step", A);
+  if (rc) return rc;
+  if (!uidx || !p || !q || !loss_out) return fail(c, POI_EINVAL, "poi_vbpr_step: NULL argument");
+  if (n < 0) return fail(c, POI_EINVAL, "poi_vbpr_step: bad sizes");
+  if ((int64_t)n * 4 >= ((int64_t)1 << 31) - 64) return fail(c, POI_ENOTSUP, "VBPR: at most 2^31 / 4 triples per launch");
+  if (c->batch_cap == 0.0f) return fail(c, POI_ENOTSUP, "the mini-batch rule (batch cap 0) applies to poi_gru_step / poi_spatial_step only");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  A.uidx = uidx; A.p = p; A.q = q; A.n = n; A.alpha = alpha; A.lambda = lambda; A.lambda_ev = lambda_ev; A.bcap = c->batch_cap; A.loss = loss_out;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  poi::vbpr_chunking(n, &A.ch_rows, &A.n_chunk);
+  size_t ni = 0, nf = 0, nd = 0;
+  poi::vbpr_ws_sizes(n, P->dim, P->n_img, &ni, &nf, &nd);
+  if ((rc = ensure(c, c->vb_ws, sizeof(double) * nd + sizeof(int) * ni + sizeof(float) * nf + 512, st))) return rc;
+  const size_t chunks = ((size_t)4 * n + 63) / 64 + 2, per = 4 * (size_t)n + 64, nt = ((size_t)n + 64 + 3) & ~(size_t)3;
+  A.dpart = (double*)c->vb_ws.p;
+  int* ip = (int*)(A.dpart + ((nd + 1) & ~(size_t)1));      // (16-byte aligned behind the float64 partials)
+  A.keys0 = ip; A.keys1 = ip + per; A.vals0 = ip + 2 * per; A.vals1 = ip + 3 * per; ip += 4 * per;
+  A.hist = ip; ip += RS_HIST_INTS + RS_MAXBIN;
+  A.cnt = ip; ip += 64;
+  A.meta = (int4*)ip; ip += 4 * chunks;
+  A.okf = ip; ip += nt;
+  A.ord = ip; ip += nt;
+  float* fp = (float*)ip;
+  A.g = fp; fp += nt;
+  A.V = fp; fp += (size_t)n * P->dim;
+  A.lead = fp; fp += chunks * (size_t)P->dim;
+  A.trail = fp; fp += chunks * (size_t)P->dim;
+  A.slot = fp;
+  HIPCHK(c, poi::launch_vbpr_step(A, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_vbpr_items(poi_ctx* c, const poi_vbpr_params* P, float* items_out, void* stream) {
+  poi::VbprArgs A;
+  int rc = vbpr_check(c, P, "poi_vbpr_items", A);
+  if (rc) return rc;
+  if (!items_out) return fail(c, POI_EINVAL, "poi_vbpr_items: NULL argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  A.out = items_out; A.n_rows = P->n_item + 1;
+  HIPCHK(c, poi::launch_vbpr_items(A, c->num_cu, (hipStream_t)stream, &c->tm));
+  return POI_OK;
+}
+
+int poi_vbpr_users(poi_ctx* c, const poi_vbpr_params* P, float* users_out, void* stream) {
+  poi::VbprArgs A;
+  int rc = vbpr_check(c, P, "poi_vbpr_users", A);
+  if (rc) return rc;
+  if (!users_out) return fail(c, POI_EINVAL, "poi_vbpr_users: NULL argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, poi::launch_vbpr_users(P->ux, P->ue, P->n_user, P->dim, users_out, c->num_cu, (hipStream_t)stream, &c->tm));
   return POI_OK;
 }
 
@@ -1715,7 +1796,7 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
   struct Opt { const char* name; int* p; int lo, hi; };
   const Opt opts[] = {{"forward_table_compact", &c->xcomp, 0, 1}, {"forward_table_compact_min", &c->xcomp_min, 0, 1 << 30}, {"head_split", &c->head3, 0, 1},
                       {"early_bins", &c->early_bins, 0, 1}, {"hot_bins", &c->hot_bins, 0, 1}, {"hybrid", &c->hybrid, 0, 1}, {"hybrid_min", &c->hyb_min, 0, 1 << 30}, {"hybrid_max", &c->hyb_max, 0, 1 << 30}, {"hybrid_force", &c->hyb_force, 0, 1 << 30},
-                      {"cell_grid", &c->cell_grid, 0, 1 << 30}, {"session_tile_min", &c->sess_tile_min, 1, 1 << 30}};
+                      {"cell_grid", &c->cell_grid, 0, 1 << 30}, {"vbpr_grid", &c->vbpr_grid, 0, 1 << 30}, {"session_tile_min", &c->sess_tile_min, 1, 1 << 30}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);

@@ -490,6 +490,35 @@ int cell_chunk_rows(int n_seq, int max_len);
 hipError_t launch_cell_step(CellArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_cell_predict(CellArgs& A, hipStream_t st, Timing* tm);
 
+// VBPR (vbpr.hip)
+#define VBPR_DENSE_CHUNKS 64      // at most this many row chunks of the dense-gradient contraction (partials added in chunk order)
+struct VbprArgs {
+  float *ux, *lt, *ue, *ei;         // (n_user, D), (n_item + 1, D), (n_user, D), (D, F)
+  const float* fi;                  // (n_item + 1, F), never written
+  int n_user, n_item, dim, n_img;
+  const int *uidx, *p, *q;
+  int n;
+  float alpha, lambda, lambda_ev, bcap;
+  float* loss;
+  int* bad;                         // device counter of rejected triples (poi_ctx_take_bad_ids)
+  int sentinel;                     // key of a rejected triple's touches: 2 n_user + n_item + 1, sorts last
+  int *keys0, *keys1, *vals0, *vals1, *hist, *cnt;      // radix sort of the 4 n touches; cnt = {4 n, accepted triples}
+  const int *ks, *vs;
+  int4* meta;                       // per 64-touch window: {opening run's touches, it goes on, closing run's touches, its key}
+  int *okf, *ord;                   // per triple: accepted; accepted triples in launch order
+  float *g, *V;                     // per triple: d loss / d x; ei (fi[p] - fi[q])
+  float *lead, *trail, *slot;       // per-window partial sums; (4 n, D) new rows at a run's first sorted position
+  double* dpart;                    // (n_chunk, D, F) partial sums of d ei
+  int ch_rows, n_chunk;             // accepted triples per chunk, chunks: vbpr_chunking(n)
+  int grid_cap;                     // option "vbpr_grid": at most this many workgroups per kernel (0: none)
+  float* out; int n_rows;           // items: (n_rows, 2 D) output over the n_rows = n_item + 1 table rows
+};
+void vbpr_chunking(int n, int* ch_rows, int* n_chunk);
+void vbpr_ws_sizes(int n, int dim, int n_img, size_t* n_int, size_t* n_float, size_t* n_double);
+hipError_t launch_vbpr_step(VbprArgs& A, int num_cu, hipStream_t st, Timing* tm);
+hipError_t launch_vbpr_items(VbprArgs& A, int num_cu, hipStream_t st, Timing* tm);
+hipError_t launch_vbpr_users(const float* ux, const float* ue, int n_user, int dim, float* out, int num_cu, hipStream_t st, Timing* tm);
+
 // Online sessions (session.hip): per-slot recurrent state advanced one check-in at a time
 #define SESS_TILE_LDS_MAX (152 * 1024)      // dynamic LDS the tile kernel may ask for (opt-in per device)
 #define SESS_EVENT_GRID_MAX 16384           // workgroups of the event kernel (it strides over larger launches)

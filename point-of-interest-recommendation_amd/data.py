@@ -832,3 +832,21 @@ def make_poi2vec_synthetic(n_user, n_item, max_len, seed, far_frac=0.3, time_thr
         g[0] = 0
         seqs.append(s.tolist()); times.append(np.cumsum(g).astype(np.int64).tolist()); cods.append([tuple(base.coords[i]) for i in s])
     return _poi2vec_from_lists(seqs, times, cods, split, time_threshold, region_threshold, where="make_poi2vec_synthetic")[0]
+
+
+# ---- VBPR (public/BPR.py:245-335) ----------------------------------------------------------------------------------------------------
+def synthetic_features(n_item, n_img, seed, scale=None):
+    """(n_item + 1, n_img) float32 item features shaped like the post-ReLU CNN activations the reference's VBPR was written for (nothing in
+    the reference loads a feature file): non-negative, about half of the entries zero, a few latent "styles" shared between items, row
+    n_item the zero pad row.  scale multiplies the rows (None: unit scale, entries ~ |N(0, 1)|; 1 / sqrt(n_img) keeps ei . d of order 1)."""
+    rng = np.random.default_rng(seed)
+    n_style = max(2, min(16, n_item))
+    styles = rng.standard_normal((n_style, n_img))
+    mix = rng.dirichlet(np.full(n_style, 0.3), n_item)
+    x = mix @ styles + 0.7 * rng.standard_normal((n_item, n_img))
+    x = np.maximum(x, 0.0)
+    if scale is not None:
+        x = x * float(scale)
+    out = np.zeros((n_item + 1, n_img), np.float32)
+    out[:n_item] = x
+    return out

@@ -381,6 +381,70 @@ def train_prme(ds, p=None, device="cuda:0", log=print):
     return model, best, history
 
 
+def vbpr_default_params():
+    """Config of OboVBpr (public/BPR.py:245-335) in the shape of default_params(): the reference has no driver that builds it (nothing
+    there loads a feature file).  `launch`: triples per launch (1 = the reference's one-by-one training); `cap`: the batch rule's cap for
+    launches of more than one triple; n_img / fea_scale: the synthetic feature table (data.synthetic_features) used when the dataset
+    brings none (ds.fea_img)."""
+    return dict(at_nums=[5, 10, 15, 20], epochs=3, latent_size=20, alpha=0.01, **{"lambda": 0.001}, lambda_ev=0.001, fea_random_zero=0.0,
+                n_img=1024, fea_scale=None, launch=4096, cap=8.0, batch_size_test=32, seed=123, dataset="synthetic", UD=40, dd=200)
+
+
+def train_vbpr(ds, p=None, device="cuda:0", log=print):
+    """The flag-0 epoch of prog_bpr_gru_spatial.py:219-303 for OboVBpr: new negatives on the device (epoch > 0) -> the epoch's triples
+    shuffled -> launches of p["launch"] triples -> sum_loss line -> update_trained_items / _users -> AUC and top-K metrics on the
+    device.  -> (model, best, history)."""
+    from . import data as pdata
+    q = vbpr_default_params()
+    q.update(p or {})
+    p = q
+    if ds is None or isinstance(ds, str):
+        if isinstance(ds, str):
+            p = dict(p, dataset=ds)
+        ds = load_dataset(p)
+    fea = getattr(ds, "fea_img", None)
+    if fea is None:
+        fea = pdata.synthetic_features(ds.n_item, p["n_img"], p.get("seed", 0), p.get("fea_scale"))
+    size = p["latent_size"]
+    model = models.OboVBpr(train=ds.shard(), test=None, alpha_lambda=[p["alpha"], p["lambda"], p["lambda_ev"], p["fea_random_zero"]],
+                           n_user=ds.n_user, n_item=ds.n_item, n_in=size, n_hidden=size, n_img=fea.shape[1], fea_img=fea, device=device,
+                           seed=p.get("seed"))
+    best = GlobalBest(p["at_nums"])
+    U, B = ds.n_user, max(1, int(p["launch"]))
+    ses_tes = compute_start_end(U, p["batch_size_test"])
+    ses_auc = compute_start_end(U, p["batch_size_test"] * 10)
+    tes_p, tes_m = ds.tes_p.reshape(-1, 1), np.ones((U, 1), np.int32)
+    history = []
+    model.ctx.set_batch_cap(float(p["cap"]))
+    try:
+        for epoch in range(p["epochs"]):
+            if epoch > 0:
+                model.resample_negatives_device(p.get("seed", 0) * 1000003 + epoch)
+            t0 = time.time()
+            u, pp, qq = model.epoch_triples()
+            gen = torch.Generator(device="cpu").manual_seed(123 + epoch)
+            order = torch.randperm(u.numel(), generator=gen).to(model.device)
+            u, pp, qq = (t.index_select(0, order).contiguous() for t in (u, pp, qq))
+            outs = [model.train_batch(u[s:s + B], pp[s:s + B], qq[s:s + B], sync=False) for s in range(0, u.numel(), B)]
+            loss = float(torch.cat(outs).double().sum().item())
+            if model.ctx.take_bad_ids(model._stream().value):
+                raise IndexError("an index table holds an id outside the model's tables, or a negative equal to its positive")
+            l2 = model.l2.eval()
+            t1 = time.time()
+            model.update_trained_items()
+            model.update_trained_users()
+            t2 = time.time()
+            m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m)
+            t3 = time.time()
+            history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall=[m["at"][k]["recall"] for k in p["at_nums"]],
+                                times=(t1 - t0, t2 - t1, t3 - t2)))
+            log("epoch %d  sum_loss = %.3f = %.3f + %.3f  auc %.4f  recall@%d %.4f  time (train, user, test) %.2fs %.2fs %.2fs"
+                % (epoch, loss + l2, loss, l2, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1, t3 - t2))
+    finally:
+        model.ctx.set_batch_cap(1.0)
+    return model, best, history
+
+
 def geoie_default_params():
     """The in-source config of prog_geoie.py:46-63 (+ `batch`: users per launch - 1 is the reference's one-by-one training -, seed, d_min (km,
     0 = the reference) and score_norm ("reference" | "count"))."""

@@ -3,7 +3,7 @@
 Class / method names, argument meaning and return shapes follow the Theano classes the drivers call:
     OboSpatialGru  public/GRU_Spatial.py:42-292      OboGru  public/GRU.py:301-389 (+ GruBasic :32-205)
     Gru / Lstm / Rnn  public/GRU.py:395-498 / :502-657 / :661-809 (the mini-batch classes)
-    OboBpr         public/BPR.py:191-241 (+ MfBasic :28-134)
+    OboBpr         public/BPR.py:191-241 (+ MfBasic :28-134)      OboVBpr  public/BPR.py:245-335
 so that prog_bpr_gru_spatial.py's epoch loop and public/Valuate.py's evaluator run against them
 unchanged in shape.  State lives in torch ROCm tensors (device-memory containers only); every piece of
 arithmetic is a HIP kernel reached through ctypes.  There is no CPU path: without the library or a GPU
@@ -1237,6 +1237,103 @@ class OboBpr(MfBasic):
         lens = torch.as_tensor(np.diff(self._off_host.astype(np.int64))).to(self.device)
         u = torch.repeat_interleave(self._arange, lens)
         return u, self.p, self.q
+
+
+
+class _VbprL2:
+    """model.l2 of OboVBpr (public/BPR.py:259-265): 0.5 lambda (|ux|^2 + |lt|^2 + |ue|^2) + 0.5 lambda_ev |ei|^2."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def eval(self):
+        m = self.model
+        out = 0.0
+        for names, lam in ((("ux", "lt", "ue"), m.alpha_lambda[1]), (("ei",), m.lambda_ev)):
+            acc = torch.zeros(1, dtype=torch.float64, device=m.device)
+            for n in names:
+                t = getattr(m, n).t
+                m.ctx.check(m.lib.poi_sumsq(m.ctx.handle, _ptr(t), t.numel(), _ptr(acc), m._stream()))
+            out += 0.5 * lam * float(acc.item())
+        return out
+
+
+class OboVBpr(MfBasic):
+    """public/BPR.py:245-335: BPR-MF plus a fixed per-item feature table fi (n_item + 1, n_img) and a trained projection ei (n_in, n_img).
+    alpha_lambda = [alpha, lambda, lambda_ev(, fea_random_zero: accepted, unused - the train graph never corrupts features)].
+    fea_img: (n_item + 1, n_img) with a zero pad row, or (n_item, n_img) - the pad row is appended.  Float32 tables only."""
+
+    def __init__(self, train, test, alpha_lambda, n_user, n_item, n_in, n_hidden, n_img, fea_img, device="cuda:0", init=None, seed=None):
+        if len(alpha_lambda) < 3:
+            raise ValueError("OboVBpr: alpha_lambda = [alpha, lambda, lambda_ev(, fea_random_zero)]")
+        super().__init__(train, test, alpha_lambda, n_user, n_item, n_in, n_hidden, device=device, init=init, seed=seed)
+        self.lambda_ev = float(alpha_lambda[2])
+        self.n_img = int(n_img)
+        if self.dim % 4 or self.dim > 128 or self.n_img % 4 or not 0 < self.n_img <= 4096:
+            raise _lib.PoiError("OboVBpr: n_in must be a multiple of 4 up to 128 and n_img a multiple of 4 up to 4096 (got %d, %d)" % (self.dim, self.n_img))
+        fea = fea_img if isinstance(fea_img, torch.Tensor) else np.asarray(fea_img)
+        if fea.ndim != 2 or fea.shape[1] != self.n_img or fea.shape[0] not in (self.n_item, self.n_item + 1):
+            raise ValueError("fea_img must be (n_item, n_img) or (n_item + 1, n_img); got %s" % (tuple(fea.shape),))
+        fi = self._dev(fea)
+        if fi.shape[0] == self.n_item:
+            fi = torch.cat([fi, torch.zeros((1, self.n_img), dtype=torch.float32, device=self.device)]).contiguous()
+        self.fi = Shared(fi)                                                               # BPR.py:249, never trained
+        rng = np.random.default_rng(int(seed) + 1) if seed is not None else np.random      # (its own stream: MfBasic drew ux / lt from `seed`)
+        u = lambda *s: rng.uniform(-0.5, 0.5, s)
+        init = init or {}
+        g = lambda k, v: (init[k] if isinstance(init[k], torch.Tensor) else np.asarray(init[k], np.float64)) if k in init else v()
+        self.mi = Shared(self._dev(g("mi", lambda: u(self.n_item + 1, self.dim))))         # :252 (set by update_trained_items)
+        self.ue = Shared(self._dev(g("ue", lambda: u(self.n_user, self.dim))))             # :253
+        self.ei = Shared(self._dev(g("ei", lambda: u(self.dim, self.n_img))))              # :254
+        self.kdim = 2 * self.dim
+        self.trained_items = Shared(torch.zeros((self.n_item + 1, self.kdim), dtype=torch.float32, device=self.device))
+        self.trained_users = Shared(torch.zeros((self.n_user, self.kdim), dtype=torch.float32, device=self.device))
+        self.params = [self.ux, self.lt, self.ue, self.ei]                                 # :258
+        self.l2 = _VbprL2(self)
+
+    def _vparams(self):
+        return _lib.VbprParams(self.ux.t.data_ptr(), self.lt.t.data_ptr(), self.ue.t.data_ptr(), self.ei.t.data_ptr(), self.fi.t.data_ptr(),
+                               self.n_user, self.n_item, self.dim, self.n_img)
+
+    def train(self, u_idx, pq_idx):
+        """bpr_train(uidx, [p, q]) -> -log sigmoid(x)  (public/BPR.py:312-319)."""
+        return float(self.train_batch([u_idx], [pq_idx[0]], [pq_idx[1]])[0])
+
+    def train_batch(self, uidx, p, q, sync=True):
+        """One launch of n triples under the batch rule (include/poi_hip.h); n == 1 is the reference step.  sync=True returns the host
+        losses and raises IndexError when a triple was rejected (an id outside its table, or p == q: the reference's gather raises on
+        the former); sync=False returns the device losses (NaN for rejected triples) and leaves the count to ctx.take_bad_ids()."""
+        conv = lambda v: v.to(self.device, torch.int32).contiguous() if isinstance(v, torch.Tensor) else \
+            torch.as_tensor(np.asarray(v, np.int32)).to(self.device)
+        u, pp, qq = conv(uidx), conv(p), conv(q)
+        n = u.numel()
+        if pp.numel() != n or qq.numel() != n:
+            raise ValueError("uidx, p and q must have the same length")
+        loss = torch.empty(n, dtype=torch.float32, device=self.device)
+        P = self._vparams()
+        self.ctx.check(self.lib.poi_vbpr_step(self.ctx.handle, ctypes.byref(P), _ptr(u), _ptr(pp), _ptr(qq), n, self.alpha_lambda[0],
+                                              self.alpha_lambda[1], self.lambda_ev, _ptr(loss), self._stream()))
+        if sync:
+            nb = self.ctx.take_bad_ids(self._stream().value)
+            if nb:
+                raise IndexError("%d triple(s) with an id outside the user / POI tables or p == q in this launch: they moved nothing, their losses are NaN" % nb)
+        return loss.cpu().numpy() if sync else loss
+
+    def epoch_triples(self):
+        """All (user, pos_t, neg_t) triples of the train tables in the reference's order - device int32 tensors."""
+        lens = torch.as_tensor(np.diff(self._off_host.astype(np.int64))).to(self.device)
+        return torch.repeat_interleave(self._arange, lens), self.p, self.q
+
+    def update_trained_items(self):
+        """public/BPR.py:321-329: trained_items = [lt | fi ei^T] (the product on the device's matrix cores), mi = its right half."""
+        P = self._vparams()
+        self.ctx.check(self.lib.poi_vbpr_items(self.ctx.handle, ctypes.byref(P), _ptr(self.trained_items.t), self._stream()))
+        self.mi.t.copy_(self.trained_items.t[:, self.dim:])
+
+    def update_trained_users(self):
+        """public/BPR.py:331-335: trained_users = [ux | ue]."""
+        P = self._vparams()
+        self.ctx.check(self.lib.poi_vbpr_users(self.ctx.handle, ctypes.byref(P), _ptr(self.trained_users.t), self._stream()))
 
 
 # =================================================================================================
