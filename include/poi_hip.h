@@ -60,6 +60,9 @@ extern "C" {
  * "session_path" / "session_tiles" / "session_tile_min" (existing entries unchanged). */
 /* additive to 9: VBPR - new entry points poi_vbpr_step, poi_vbpr_items, poi_vbpr_users and poi_vbpr_params, option "vbpr_grid" (existing
  * entries unchanged). */
+/* additive to 9: restricted recommendation - new entry point poi_score_topk_near (public/Valuate.py:132-146 over the candidate sets of
+ * public/Load_Data_fpmc_lr.py:114-143), options "near_split_max" / "near_grid", plan keys "near_path" / "near_splits" / "near_split_max"
+ * (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -141,7 +144,8 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * Additive to 9: "cell_kernel" and "cell_grid" - the gate-block count (POI_CELL_RNN / POI_CELL_LSTM) of the recurrent kernel and the
  * workgroups of its persistent grid when the last training launch was a poi_cell_step, 0 otherwise.
  * Additive to 9: "session_path", "session_tiles", "session_tile_min" - written by poi_session_advance (which leaves the other keys as they
- * are and also makes the plan readable). */
+ * are and also makes the plan readable).
+ * Additive to 9: "near_path", "near_splits", "near_split_max" - written by poi_score_topk_near in the same way. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -207,7 +211,11 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *   "cell_grid" n (default 0 = no cap): poi_cell_step / poi_cell_predict run their recurrent kernel on at most n workgroups (the persistent
  *       grid is min(sequences, 512) otherwise) - bitwise the same result for every n.
  *   "vbpr_grid" n (default 0 = no cap): every kernel of poi_vbpr_step / poi_vbpr_items runs on at most n workgroups - bitwise the same
- *       result for every n (tests). */
+ *       result for every n (tests).
+ *   "near_split_max" n (default 256): poi_score_topk_near calls of at most n rows cut every row's band into slices, a workgroup each, and
+ *       merge the slices' lists (0: never); larger calls run one workgroup per row;
+ *   "near_grid" n (default 0 = by the row count and the CUs; at most 64): slices per row on that split path - bitwise the same result for
+ *       every n and on either path. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -685,6 +693,37 @@ int poi_session_advance(poi_ctx* ctx, const poi_gru_params* prm, const double* c
                         const int32_t* poi, int32_t n, float* hts_out, float* sts_out, void* stream);
 int poi_session_sts(poi_ctx* ctx, const poi_gru_params* prm, const double* h, int32_t n_slot, const int32_t* slot, int32_t n,
                     float* sts_out, void* stream);
+
+/* ---- restricted recommendation (additive to 9): top-K within a radius of an anchor POI, skipping listed POIs ---------------------------
+ * public/Valuate.py:132-146 ranks over every POI; FPMC-LR defines its candidates as the POIs within UD km of the last check-in
+ * (public/Load_Data_fpmc_lr.py:114-143).  This entry ranks over
+ *   C(r) = { j in [0, n_item) : (anchor[r] < 0 or c(anchor[r], j) < c_r or j == anchor[r]) and j not in ex[ex_off[r] .. ex_off[r + 1]) }
+ * only: it gathers the candidates' item rows, applies the score rule below and keeps a top-K.
+ *   c        the float64 Haversine term in cal_dis's operation order from coords / cphi, exactly as poi_fpmc_neighbor_* and poi_dist_prob
+ *            evaluate it; c_r = data.ud_threshold(r km), so that c < c_r <=> dist <= r km.  c_r = +inf, or anchor[r] == -1, means no
+ *            radius test for the call or the row.  The anchor itself is a candidate unless it is excluded.
+ *   band     lat_order = the stable argsort of latitude that the FPMC-LR neighbour entries take; a row with a radius walks only the
+ *            latitude band that can hold candidates (a conservative superset - the exact test alone decides).
+ *   ex       per-row exclusion lists: ex_off (n + 1) ascending offsets into ex, ids ascending and unique within a row; both NULL = none.
+ *   score    users[r] . items[j] in float32, one fixed summation order per pair that does not depend on how the band is cut; with
+ *            wd / sts / thr non-NULL plus wd * sts[r][bin] for bin < n_dist, the bin from the same c through thr (data.bin_thresholds, dd
+ *            in metres) - the rule of poi_score_topk_geo.  A row with anchor[r] == -1 has no distance term.  sts is (n, n_dist + 1) and is
+ *            read for exactly n rows.  items may be a registered half table; rows >= n_item (the padding row) are never read.
+ *   outputs  idx_out (n, k), k <= 32, by descending score, ties by ascending id; a row with fewer than k candidates is filled with -1 ids
+ *            and -inf scores (score_out (n, k) or NULL); count_out (n) or NULL = |C(r)|, not clipped to k.
+ *   bad rows an anchor outside [-1, n_item) or an exclusion id outside [0, n_item): the row is all -1 / -inf / count 0 and is counted
+ *            (poi_ctx_take_bad_ids).
+ * coords / cphi / anchor may be NULL when there is neither a radius nor a distance term, lat_order when there is no radius.
+ * dim: a multiple of 4, up to 256.  No float atomics: identical calls give bitwise identical outputs, and so do different grids.
+ * Two launch regimes: calls of at most "near_split_max" rows (poi_ctx_set_option, default 256: live traffic) cut each row's band into
+ * slices, one workgroup each, and merge the slices' lists in a second kernel; larger calls run one workgroup per row.
+ * poi_ctx_last_plan: "near_path" (0 row, 1 split), "near_splits" (slices per row, 0 on the row path), "near_split_max" (the switch point
+ * in force).  Timing name: "score_topk_near". */
+int poi_score_topk_near(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                        const double* coords, const double* cphi, const int32_t* lat_order, const int32_t* anchor, double c_r,
+                        const int32_t* ex_off, const int32_t* ex,
+                        const float* wd, const float* sts, const double* thr, int32_t n_dist, double dd,
+                        int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
 
 /* ---- multi-GPU reconciliation (8e; new - the reference is single-process) ----------------------
  * Users are sharded across ranks, every rank trains on a full parameter replica with no data-path collective,

@@ -150,6 +150,8 @@ SIGNATURES = {
     "poi_session_advance": (c_int, [c_void_p, POINTER(GruParams), c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                     c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "poi_session_sts": (c_int, [c_void_p, POINTER(GruParams), c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "poi_score_topk_near": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_delta_make": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_delta_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_comm_available": (c_int, []),
@@ -204,7 +206,8 @@ def load():
 
 # keys of poi_ctx_last_plan (include/poi_hip.h)
 PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", "fwd_tab", "xft", "xcomp", "head_split", "efuse", "early_bins",
-             "fork", "hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg", "cell_kernel", "cell_grid", "session_path", "session_tiles", "session_tile_min")
+             "fork", "hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg", "cell_kernel", "cell_grid", "session_path", "session_tiles", "session_tile_min",
+             "near_path", "near_splits", "near_split_max")
 
 
 class Context:
@@ -294,7 +297,8 @@ class Context:
 
     def set_option(self, name, value):
         """Named tuning switch of the tile engine (poi_ctx_set_option: "forward_table_compact", "forward_table_compact_min", "head_split",
-        "early_bins", "hot_bins", "hybrid", "hybrid_min", "hybrid_max", "hybrid_force"; "cell_grid" of poi_cell_step; "session_tile_min" of poi_session_advance)."""
+        "early_bins", "hot_bins", "hybrid", "hybrid_min", "hybrid_max", "hybrid_force"; "cell_grid" of poi_cell_step; "session_tile_min" of poi_session_advance;
+        "near_split_max" / "near_grid" of poi_score_topk_near)."""
         self.check(self.lib.poi_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def set_small_launch(self, max_sequences=1800):

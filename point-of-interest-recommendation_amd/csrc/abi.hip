@@ -79,7 +79,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR
@@ -101,6 +101,10 @@ struct poi_ctx {
   // online sessions: per-slot claims of the repeated-slot check
   DevBuf sess_owner;
   int sess_tile_min = 512;  // option "session_tile_min": poi_session_advance calls of at least this many events take the tile kernel
+  // restricted top-K (near.hip): per (row, slice) partial lists of the split path
+  DevBuf near_ws;
+  int near_split_max = 256; // option "near_split_max": poi_score_topk_near calls of at most this many rows split each row's band over several workgroups
+  int near_grid = 0;        // option "near_grid": workgroups per row on the split path (0: by the row count and the CUs)
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)
@@ -931,6 +935,9 @@ int poi_vbpr_users(poi_ctx* c, const poi_vbpr_params* P, float* users_out, void*
 
 // ---------------------------------------------------------------------------------------------
 // FPMC-LR (fpmc.hip)
+// c >= (1 - cos a) / 2 = sin^2(a / 2): a POI more than 2 asin(sqrt(c)) away in latitude is never within the radius (1e-6 relative margin)
+static double lat_band_deg(double c) { return c >= 1.0 ? 1e9 : 2.0 * asin(sqrt(c)) / 0.017453292519943295 * (1.0 + 1e-6) + 1e-9; }
+
 static int fpmc_nbr_common(poi_ctx* c, const double* coords, const double* cphi, const int32_t* lat_order, int32_t n_item, double c_ud,
                            const char* who, poi::FpmcNbrArgs& A) {
   if (!c || !coords || !cphi || !lat_order) return fail(c, POI_EINVAL, "%s: NULL argument", who);
@@ -938,8 +945,7 @@ static int fpmc_nbr_common(poi_ctx* c, const double* coords, const double* cphi,
   if (!(c_ud >= 0.0)) return fail(c, POI_EINVAL, "%s: c_ud must be >= 0", who);
   memset(&A, 0, sizeof A);
   A.coords = coords; A.cphi = cphi; A.order = lat_order; A.n = n_item; A.c_ud = c_ud;
-  // c >= (1 - cos a) / 2 = sin^2(a / 2): a POI more than 2 asin(sqrt(c_ud)) away in latitude is never a neighbour (1e-6 relative margin)
-  A.band_deg = c_ud >= 1.0 ? 1e9 : 2.0 * asin(sqrt(c_ud)) / 0.017453292519943295 * (1.0 + 1e-6) + 1e-9;
+  A.band_deg = lat_band_deg(c_ud);
   return POI_OK;
 }
 
@@ -1670,6 +1676,55 @@ int poi_score_topk_geo(poi_ctx* c, const float* users, const float* items, int32
   return score_common(c, users, items, n, n_item, dim, wd, nullptr, nullptr, k, idx_out, score_out, stream, &U);
 }
 
+// ---------------------------------------------------------------------------------------------
+// restricted top-K (near.hip)
+int poi_score_topk_near(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const double* coords,
+                        const double* cphi, const int32_t* lat_order, const int32_t* anchor, double c_r, const int32_t* ex_off, const int32_t* ex,
+                        const float* wd, const float* sts, const double* thr, int32_t n_dist, double dd, int32_t k, int32_t* idx_out,
+                        float* score_out, int32_t* count_out, void* stream) {
+  if (!c || !users || !items || !idx_out) return fail(c, POI_EINVAL, "poi_score_topk_near: NULL ctx / users / items / idx_out");
+  if (k <= 0 || k > NEAR_K_MAX) return fail(c, POI_ENOTSUP, "poi_score_topk_near supports 1 <= k <= %d (got %d)", NEAR_K_MAX, k);
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_score_topk_near: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "poi_score_topk_near: n < 0 or n_item <= 0");
+  if (!(c_r >= 0.0)) return fail(c, POI_EINVAL, "poi_score_topk_near: c_r must be >= 0 (+inf: no radius test)");
+  const bool radius = c_r < HUGE_VAL, geo = wd != nullptr;
+  if ((ex_off == nullptr) != (ex == nullptr)) return fail(c, POI_EINVAL, "poi_score_topk_near: ex_off and ex go together");
+  if (geo != (sts != nullptr) || geo != (thr != nullptr)) return fail(c, POI_EINVAL, "poi_score_topk_near: wd, sts and thr go together");
+  if (geo && (n_dist <= 0 || !(dd > 0))) return fail(c, POI_EINVAL, "poi_score_topk_near: the distance term needs n_dist > 0 and dd > 0");
+  if ((radius || geo) && (!coords || !cphi || !anchor)) return fail(c, POI_EINVAL, "poi_score_topk_near: a radius or a distance term needs coords / cphi / anchor");
+  if (radius && !lat_order) return fail(c, POI_EINVAL, "poi_score_topk_near: a radius needs lat_order");
+  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "poi_score_topk_near: users must be float32");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::NearArgs A = {};
+  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
+  A.n = n; A.n_item = n_item; A.dim = dim; A.k = k;
+  A.coords = coords; A.cphi = cphi; A.order = lat_order; A.anchor = anchor; A.c_r = c_r; A.band_deg = radius ? lat_band_deg(c_r) : 0.0;
+  A.ex_off = ex_off; A.ex = ex;
+  A.wd = wd; A.sts = sts; A.thr = thr; A.n_dist = geo ? n_dist : 0; A.bin_scale = geo ? (float)(12742.0 * 1000.0 / dd) : 0.f;
+  A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
+  int rc;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  // few rows (live traffic): every row's band is cut into slices so that the call fills the CUs; many rows: one workgroup per row
+  const int split = n <= c->near_split_max;
+  A.n_split = 1;
+  if (split) {
+    int s = c->near_grid > 0 ? c->near_grid : 4 * c->num_cu / n;
+    if (c->near_grid <= 0 && s < 2) s = 2;
+    A.n_split = s > NEAR_SPLIT_LIMIT ? NEAR_SPLIT_LIMIT : s;
+    const size_t lists = (size_t)n * A.n_split;
+    if ((rc = ensure(c, c->near_ws, lists * (NEAR_K_MAX * (sizeof(float) + sizeof(int)) + sizeof(int)), st))) return rc;
+    A.part_s = (float*)c->near_ws.p;
+    A.part_i = (int*)(A.part_s + lists * NEAR_K_MAX);
+    A.part_cnt = A.part_i + lists * NEAR_K_MAX;
+  }
+  c->plan.valid = 1; c->plan.near_path = split; c->plan.near_splits = split ? A.n_split : 0; c->plan.near_split_max = c->near_split_max;
+  HIPCHK(c, poi::launch_near(A, st, &c->tm));
+  return POI_OK;
+}
+
 int poi_topk(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, int32_t k, int32_t* idx_out, float* score_out,
              void* stream) {
   if (!c || !scores || !idx_out) return fail(c, POI_EINVAL, "poi_topk: NULL argument");
@@ -1796,7 +1851,8 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
   struct Opt { const char* name; int* p; int lo, hi; };
   const Opt opts[] = {{"forward_table_compact", &c->xcomp, 0, 1}, {"forward_table_compact_min", &c->xcomp_min, 0, 1 << 30}, {"head_split", &c->head3, 0, 1},
                       {"early_bins", &c->early_bins, 0, 1}, {"hot_bins", &c->hot_bins, 0, 1}, {"hybrid", &c->hybrid, 0, 1}, {"hybrid_min", &c->hyb_min, 0, 1 << 30}, {"hybrid_max", &c->hyb_max, 0, 1 << 30}, {"hybrid_force", &c->hyb_force, 0, 1 << 30},
-                      {"cell_grid", &c->cell_grid, 0, 1 << 30}, {"vbpr_grid", &c->vbpr_grid, 0, 1 << 30}, {"session_tile_min", &c->sess_tile_min, 1, 1 << 30}};
+                      {"cell_grid", &c->cell_grid, 0, 1 << 30}, {"vbpr_grid", &c->vbpr_grid, 0, 1 << 30}, {"session_tile_min", &c->sess_tile_min, 1, 1 << 30},
+                      {"near_split_max", &c->near_split_max, 0, 1 << 30}, {"near_grid", &c->near_grid, 0, NEAR_SPLIT_LIMIT}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);
@@ -1875,7 +1931,8 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"head_split", &poi_ctx::LastPlan::head_split}, {"efuse", &poi_ctx::LastPlan::efuse}, {"early_bins", &poi_ctx::LastPlan::early_bins},
       {"fork", &poi_ctx::LastPlan::fork}, {"cell_kernel", &poi_ctx::LastPlan::cell_kernel}, {"cell_grid", &poi_ctx::LastPlan::cell_grid},
       {"session_path", &poi_ctx::LastPlan::session_path}, {"session_tiles", &poi_ctx::LastPlan::session_tiles},
-      {"session_tile_min", &poi_ctx::LastPlan::session_tile_min}};
+      {"session_tile_min", &poi_ctx::LastPlan::session_tile_min}, {"near_path", &poi_ctx::LastPlan::near_path},
+      {"near_splits", &poi_ctx::LastPlan::near_splits}, {"near_split_max", &poi_ctx::LastPlan::near_split_max}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

@@ -28,18 +28,6 @@ namespace poi {
 #define NB_Q 4          // queries per block of the neighbour passes (one wave each)
 #define NB_TILE 256     // band candidates staged in LDS per round
 
-// first position k of the latitude order with lat(order[k]) > v (strict) or >= v
-template <bool STRICT>
-__device__ int lat_bound(const double* coords, const int* order, int n, double v) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int m = (lo + hi) >> 1;
-    const double x = coords[2 * (size_t)order[m]];
-    if (STRICT ? x <= v : x < v) lo = m + 1; else hi = m;
-  }
-  return lo;
-}
-
 template <bool FILL>
 __global__ __launch_bounds__(256) void fpmc_nbr_kernel(FpmcNbrArgs A) {
   __shared__ double s_lat[NB_TILE], s_lon[NB_TILE], s_cp[NB_TILE];
@@ -59,7 +47,6 @@ __global__ __launch_bounds__(256) void fpmc_nbr_kernel(FpmcNbrArgs A) {
   const int b0 = s_band[0], b1 = s_band[1];
   long long count = 0;
   const long long base = (FILL && active) ? A.off[qi] : 0;
-  const double pr = 0.017453292519943295;
   for (int t0 = b0; t0 < b1; t0 += NB_TILE) {
     __syncthreads();
     const int k = t0 + threadIdx.x;
@@ -75,13 +62,7 @@ __global__ __launch_bounds__(256) void fpmc_nbr_kernel(FpmcNbrArgs A) {
       const int l = l0 + lane;
       bool hit = false;
       if (l < m) {
-        double c;
-        {
-#pragma clang fp contract(off)
-          const double a = (lat1 - s_lat[l]) * pr;
-          const double b = (lon1 - s_lon[l]) * pr;
-          c = (1.0 - cos_small(a)) / 2 + c1 * s_cp[l] * (1.0 - cos_small(b)) / 2;
-        }
+        const double c = haversine_c(lat1, lon1, c1, s_lat[l], s_lon[l], s_cp[l]);
         hit = c < A.c_ud && s_id[l] != qi;
       }
       const unsigned long long bal = __ballot(hit);

@@ -210,6 +210,27 @@ __device__ __forceinline__ double cos_small(double x) {
   return cos(x);
 }
 
+// The Haversine term `c` of cal_dis (public/Load_Data_by_length.py:32-35) in float64 in its operation order, cos(lat) of both points
+// from the host (data.cos_lat): what the exact thresholds (data.bin_thresholds, data.ud_threshold) are compared with.
+__device__ __forceinline__ double haversine_c(double lat1, double lon1, double cp1, double lat2, double lon2, double cp2) {
+#pragma clang fp contract(off)
+  const double pr = 0.017453292519943295;
+  const double a = (lat1 - lat2) * pr;
+  const double b = (lon1 - lon2) * pr;
+  return (1.0 - cos_small(a)) / 2 + cp1 * cp2 * (1.0 - cos_small(b)) / 2;
+}
+
+// first position k of the latitude order with lat(order[k]) > v (strict) or >= v
+template <bool STRICT>
+__device__ __forceinline__ int lat_bound(const double* coords, const int* order, int n, double v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int m = (lo + hi) >> 1;
+    const double x = coords[2 * (size_t)order[m]];
+    if (STRICT ? x <= v : x < v) lo = m + 1; else hi = m;
+  }
+  return lo;
+}
 
 // Top-K tie rule of the scoring kernels (score_topk.hip, prme.hip): higher score first, then the lower index.
 __device__ __forceinline__ bool better(float s, int i, float ps, int pi) {

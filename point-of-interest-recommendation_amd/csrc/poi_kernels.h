@@ -540,6 +540,23 @@ size_t sess_event_lds(int D, int xw, int NB, int spatial);
 bool sess_tile_supported(int D, int xw, int NB, int spatial);
 hipError_t launch_session(SessArgs& A, int tile, hipStream_t st, Timing* tm);
 
+// Restricted top-K (near.hip): candidates within a radius of an anchor POI, minus a per-row exclusion list
+#define NEAR_K_MAX 32                       // list length (one half wave)
+#define NEAR_SPLIT_LIMIT 64                 // workgroups a row's band may be split over
+struct NearArgs {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim, k;
+  const double *coords, *cphi; const int* order;             // null when no row has a radius test or a distance term
+  const int* anchor; double c_r, band_deg;                    // c_r = +inf: no radius test
+  const int *ex_off, *ex;                                     // per-row exclusion lists (ascending ids), or both null
+  const float *wd, *sts; const double* thr; int n_dist; float bin_scale;      // distance term, or wd null
+  int n_split;                                                // workgroups per row (1 on the row path)
+  float* part_s; int *part_i, *part_cnt;                      // split path: (n, n_split, NEAR_K_MAX) partial lists, (n, n_split) counts
+  int* idx_out; float* score_out; int* count_out;             // score_out / count_out may be null
+  int* bad;                                                   // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+hipError_t launch_near(NearArgs& A, hipStream_t st, Timing* tm);
+
 // scoring / top-K
 struct ScoreArgs {
   const float *users, *items; int items_f16;      // items: float32, or IEEE half when items_f16

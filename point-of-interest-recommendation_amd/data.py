@@ -136,6 +136,49 @@ def fpmc_neighbors_host(coords, ud_km, block=2048):
     return off, (np.concatenate(ids) if ids else np.zeros(0, np.int32))
 
 
+def train_exclusion_csr(off, p_flat, n_item):
+    """Every user's DISTINCT train POIs as a CSR (off int64 (n_user + 1), ids int32), ids ascending within a row: the exclude="train"
+    lists of compute_sub_topk_near.  A padding id (>= n_item) never is a candidate and is dropped."""
+    off = np.asarray(off, np.int64)
+    p = np.asarray(p_flat, np.int64)
+    n_user = len(off) - 1
+    user = np.repeat(np.arange(n_user), np.diff(off))
+    keep = (p >= 0) & (p < n_item)
+    key = np.unique(user[keep] * (n_item + 1) + p[keep])                 # sorted by (user, POI), duplicates dropped
+    eo = np.zeros(n_user + 1, np.int64)
+    np.cumsum(np.bincount(key // (n_item + 1), minlength=n_user), out=eo[1:])
+    if eo[-1] >= 1 << 31:
+        raise ValueError("the train exclusion lists hold %d ids: above 2^31" % eo[-1])
+    return eo, (key % (n_item + 1)).astype(np.int32)
+
+
+def last_exclusion_csr(anchor):
+    """exclude="last" as a CSR: row r lists anchor[r] alone; a row without an anchor (-1) excludes nothing."""
+    a = np.asarray(anchor, np.int64).reshape(-1)
+    off = np.zeros(len(a) + 1, np.int64)
+    np.cumsum(a >= 0, out=off[1:])
+    return off, a[a >= 0].astype(np.int32)
+
+
+def check_exclusion_csr(off, ids, n, n_item):
+    """Range- and order-check host exclusion lists for n rows -> (off int32 (n + 1), ids int32).  off ascends from 0 to len(ids)
+    (ValueError); ids lie in [0, n_item) (IndexError) and are strictly ascending - sorted, unique - within every row (ValueError): the
+    kernel finds an id by binary search."""
+    off = np.asarray(off, np.int64).reshape(-1)
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    if len(off) != n + 1 or off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0):
+        raise ValueError("exclude=(off, ids): off must hold n + 1 = %d ascending offsets from 0 to len(ids) = %d" % (n + 1, len(ids)))
+    if ids.size and (ids.min() < 0 or ids.max() >= n_item):
+        raise IndexError("exclude ids must lie in [0, %d) (found %d..%d)" % (n_item, int(ids.min()), int(ids.max())))
+    if ids.size > 1:
+        inner = np.ones(len(ids) - 1, bool)
+        cut = off[1:-1]
+        inner[cut[(cut > 0) & (cut < len(ids))] - 1] = False               # neighbours that belong to two rows
+        if np.any((np.diff(ids) <= 0) & inner):
+            raise ValueError("exclude ids must be strictly ascending (sorted, unique) within every row")
+    return off.astype(np.int32), ids.astype(np.int32)
+
+
 def padded_to_csr(rows, lens):
     """Nested (U, LM) table + valid lengths -> (off int32 (U+1), flat int32)."""
     rows = np.asarray(rows)

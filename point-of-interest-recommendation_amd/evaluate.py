@@ -65,8 +65,11 @@ def coalesce_ranges(starts_ends, target=65536):
     return out
 
 
-def device_rank_metrics(model, starts_ends_tes, at_nums):
-    """Fused top-K + metric accumulation on the device: only (len(at_nums), 3) doubles reach the host."""
+def device_rank_metrics(model, starts_ends_tes, at_nums, within_km=None, exclude=None):
+    """Fused top-K + metric accumulation on the device: only (len(at_nums), 3) doubles reach the host.
+    within_km / exclude (model.compute_sub_topk_near; cut-offs <= 32): rank over the POIs within that radius of the user's last train
+    POI, minus the exclusion lists - the restricted-candidate protocol of the FPMC-LR paper.  A row with fewer candidates than the
+    cut-off carries -1 ids, which poi_rank_metrics counts as misses (an id equals no test POI)."""
     import ctypes
     import torch
     at_nums = list(at_nums)
@@ -77,7 +80,10 @@ def device_rank_metrics(model, starts_ends_tes, at_nums):
     at = torch.as_tensor(np.asarray(at_nums, np.int32)).to(model.device)
     for se in coalesce_ranges(starts_ends_tes):
         ids, lo = model._ids(se)
-        idx = model.compute_sub_topk(se, kmax)
+        if within_km is None and exclude is None:
+            idx = model.compute_sub_topk(se, kmax)
+        else:
+            idx = model.compute_sub_topk_near(se, kmax, within_km=within_km, exclude=exclude)
         tp, tm = model._rows(model.tes_buys_masks, ids, lo), model._rows(model.tes_masks, ids, lo)
         model.ctx.check(model.lib.poi_rank_metrics(model.ctx.handle, idx.data_ptr(), idx.shape[0], kmax, tp.data_ptr(), tm.data_ptr(),
                                                    tm.shape[1], at.data_ptr(), len(at_nums), acc.data_ptr(), model._stream()))

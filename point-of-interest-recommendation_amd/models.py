@@ -307,6 +307,169 @@ class _Base:
         return (idx, sc) if return_scores else idx
 
 
+    # ---- restricted recommendation (poi_score_topk_near): top-K within a radius of an anchor POI, skipping listed POIs -----------------
+    _near_ok = True         # False: the model ranks by a score rule of its own (CA-RNN, PRME, GeoIE, POI2Vec)
+
+    def set_coords(self, coords):
+        """POI coordinates ((n_item, 2) lat, lon) for a model constructed without them (the MfBasic family, plain GruBasic): uploads
+        coords, cos(lat) (data.cos_lat) and the stable latitude order that the radius test of compute_sub_topk_near / Session.recommend
+        walks.  Models that were given coords= at construction need no call: they build the latitude order at first use."""
+        xy = np.ascontiguousarray(coords.cpu().numpy() if isinstance(coords, torch.Tensor) else coords, np.float64)
+        if xy.shape != (self.n_item, 2):
+            raise ValueError("coords must be (n_item, 2) lat, lon (got %s)" % (xy.shape,))
+        self.coords = torch.as_tensor(xy).to(self.device)
+        self._cphi = torch.as_tensor(cos_lat(xy)).to(self.device)
+        self._lat_order = None
+        if getattr(self, "spatial", False):
+            self._binthr = self._dev(bin_thresholds(self.dd * 1000.0, self.n_dist), torch.float64)
+
+    def _near_geo(self, radius):
+        """(coords, cphi, lat_order | None) on the device; the order is built once."""
+        if getattr(self, "coords", None) is None:
+            raise _lib.PoiError("%s holds no POI coordinates: call set_coords(coords) first" % type(self).__name__)
+        if radius and getattr(self, "_lat_order", None) is None:
+            self._lat_order = torch.argsort(self.coords[:, 0], stable=True).to(torch.int32).contiguous()
+        return self.coords, self._cphi, (self._lat_order if radius else None)
+
+    def _near_radius(self, within_km):
+        """within_km -> the Haversine threshold c_r (data.ud_threshold; None / inf: no radius test)."""
+        from .data import ud_threshold
+        if within_km is None:
+            return float("inf")
+        r = float(within_km)
+        if not r >= 0.0:
+            raise ValueError("within_km must be >= 0 (got %r)" % (within_km,))
+        cache = self.__dict__.setdefault("_near_thr", {})
+        if r not in cache:
+            cache[r] = float(ud_threshold(r))
+        return cache[r]
+
+    def _near_items(self):
+        return self.trained_items.t
+
+    def _near_term(self, ids, lo):
+        """(wd, sts rows (n, n_dist + 1), thr, n_dist, dd in metres) of the model's distance term, or None."""
+        return None
+
+    def _last_train_poi(self):
+        """(n_user) int32 device: every user's last train POI (-1 for an empty train row)."""
+        t = self.__dict__.get("_near_last")
+        if t is None:
+            off = self._off_host.astype(np.int64)
+            t = self.p.index_select(0, torch.as_tensor(np.maximum(off[1:] - 1, 0)).to(self.device)).clone()
+            t[torch.as_tensor(off[1:] == off[:-1]).to(self.device)] = -1
+            self._near_last = t
+        return t
+
+    def train_exclusion(self):
+        """Every user's DISTINCT train POIs as a sorted CSR (off (n_user + 1) int32, ids int32) on the device - built once (the train
+        tables do not change) and cached: the exclude="train" lists."""
+        t = self.__dict__.get("_near_train")
+        if t is None:
+            from .data import train_exclusion_csr
+            eo, key = train_exclusion_csr(self._off_host, self.p.cpu().numpy(), self.n_item)
+            i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+            t = self._near_train = (i32(eo), i32(key))
+        return t
+
+    def _near_exclusion(self, exclude, n, anchor, ids=None, lo=None, kinds=("train", "last")):
+        """exclude -> (ex_off (n + 1), ex) int32 device tensors, or (None, None)."""
+        if exclude is None:
+            return None, None
+        if isinstance(exclude, str):
+            if exclude not in kinds:
+                raise ValueError("exclude must be None, %s or a pair (off, ids) (got %r)" % (", ".join(repr(k) for k in kinds), exclude))
+            if exclude == "last":                               # the anchor alone (a row without one excludes nothing)
+                has = (anchor >= 0)
+                eo = torch.zeros(n + 1, dtype=torch.int32, device=self.device)
+                eo[1:] = torch.cumsum(has.int(), 0)
+                ex = anchor[has].contiguous()
+                return eo, (ex if ex.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+            eo, ex = self.train_exclusion()
+            if lo is not None:                                  # a contiguous user range: its offsets index the cached ids as they are
+                return eo[lo:lo + n + 1], ex
+            u = ids.long()
+            beg, ln = eo[u].long(), (eo[u + 1] - eo[u]).long()
+            no = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+            no[1:] = torch.cumsum(ln, 0)
+            pos = torch.arange(int(no[-1].item()), device=self.device) - torch.repeat_interleave(no[:-1] - beg, ln)
+            return no.int(), (ex[pos].contiguous() if pos.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+        off, lst = exclude
+        if isinstance(off, torch.Tensor) and isinstance(lst, torch.Tensor):      # device lists are checked by the kernel
+            if off.numel() != n + 1:
+                raise ValueError("exclude=(off, ids): off must hold n + 1 = %d offsets" % (n + 1))
+            lst = lst.to(self.device, torch.int32).contiguous()
+            return off.to(self.device, torch.int32).contiguous(), (lst if lst.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+        off = off.cpu().numpy() if isinstance(off, torch.Tensor) else off
+        lst = lst.cpu().numpy() if isinstance(lst, torch.Tensor) else lst
+        from .data import check_exclusion_csr
+        eo, ex = (torch.as_tensor(v).to(self.device) for v in check_exclusion_csr(off, lst, n, self.n_item))
+        return eo, (ex if ex.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+
+    def _near_launch(self, users, items, anchor, c_r, ex, term, k, return_scores, return_counts, sync):
+        """One poi_score_topk_near call -> idx[, scores][, counts] (device tensors)."""
+        n, k = users.shape[0], int(k)
+        radius = c_r < float("inf")
+        coords = cphi = order = None
+        if radius or term is not None:
+            coords, cphi, order = self._near_geo(radius)
+        wd, sts, thr, n_dist, dd_m = term if term is not None else (None, None, None, 0, 0.0)
+        idx = torch.empty((n, max(k, 0)), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, max(k, 0)), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        self.ctx.check(self.lib.poi_score_topk_near(self.ctx.handle, _ptr(users), _ptr(items), n, self.n_item, self.kdim, _ptr(coords), _ptr(cphi),
+                                                    _ptr(order), _ptr(anchor), c_r, _ptr(ex[0]), _ptr(ex[1]), _ptr(wd), _ptr(sts), _ptr(thr),
+                                                    int(n_dist), float(dd_m), k, _ptr(idx), _ptr(sc), _ptr(cnt), self._stream()))
+        if sync:
+            bad = self.ctx.take_bad_ids(self._stream().value)
+            if bad:
+                raise IndexError("%d row(s) with an anchor outside [-1, %d) or an exclusion id outside [0, %d): their lists are all -1"
+                                 % (bad, self.n_item, self.n_item))
+        out = (idx,) + ((sc,) if return_scores else ()) + ((cnt,) if return_counts else ())
+        return out if len(out) > 1 else idx
+
+    def _near_anchor(self, anchor, n, default):
+        """anchor argument -> (n) int32 device tensor; host arrays are range-checked ([-1, n_item), -1 = no anchor) before any launch."""
+        if anchor is None:
+            return default()
+        if isinstance(anchor, torch.Tensor):
+            t = anchor.to(self.device, torch.int32).contiguous().reshape(-1)
+        else:
+            a = np.atleast_1d(np.asarray(anchor)).astype(np.int64)
+            if a.size and (a.min() < -1 or a.max() >= self.n_item):
+                raise IndexError("anchor ids must lie in [-1, %d) (found %d..%d)" % (self.n_item, int(a.min()), int(a.max())))
+            t = torch.as_tensor(a.astype(np.int32)).to(self.device)
+        if t.numel() != n:
+            raise ValueError("anchor must hold one POI per row (%d vs %d)" % (t.numel(), n))
+        return t
+
+    def compute_sub_topk_near(self, start_end, k, within_km=None, exclude=None, anchor=None, return_scores=False, return_counts=False, sync=True):
+        """compute_sub_topk over RESTRICTED candidates (include/poi_hip.h, poi_score_topk_near): the POIs within `within_km` km of the
+        row's anchor (cal_dis <= within_km, exactly; None: no radius; default anchor: the user's last train POI; anchor -1: no radius
+        for that row), minus the row's exclusion list - None, "train" (the user's distinct train POIs), "last" (the anchor) or a pair
+        (off, ids) of CSR lists, ids ascending and unique per row.  Returns (n, k) int32 ids by descending score (k <= 32), ties by
+        ascending id, -1 where a row has fewer than k candidates (scores -inf); with return_counts the candidate count of every row.
+        The score is the model's own: users . items at kdim, plus the spatial model's distance term taken at the anchor.  With
+        within_km=None and exclude=None this is compute_sub_topk.  Host arguments are checked before the launch; device tensors are
+        checked by the kernel: an offending row comes out all -1 and - with sync - raises IndexError (sync=False leaves the count to
+        ctx.take_bad_ids())."""
+        if not self._near_ok:
+            raise _lib.PoiError("%s ranks by a score rule of its own, not users . items: compute_sub_topk_near does not cover it" % type(self).__name__)
+        if within_km is None and exclude is None and anchor is None:
+            out = self.compute_sub_topk(start_end, k, return_scores)
+            if return_counts:
+                n = (out[0] if return_scores else out).shape[0]
+                cnt = torch.full((n,), self.n_item, dtype=torch.int32, device=self.device)
+                out = (out + (cnt,)) if return_scores else (out, cnt)
+            return out
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        anc = self._near_anchor(anchor, n, lambda: self._rows(self._last_train_poi(), ids, lo))
+        ex = self._near_exclusion(exclude, n, anc, ids, lo)
+        return self._near_launch(users, self._near_items(), anc, self._near_radius(within_km), ex, self._near_term(ids, lo), k,
+                                 return_scores, return_counts, sync)
+
+
 # =================================================================================================
 class GruBasic(_Base):
     """public/GRU.py:32-205."""
@@ -736,6 +899,12 @@ class OboSpatialGru(GruBasic):
         self._seed_end(seed, idx)
         return (idx, sc) if return_scores else idx
 
+    def _near_term(self, ids, lo):
+        if self.prob is not None or self.trained_sus is None:
+            raise _lib.PoiError("compute_sub_topk_near on the spatial model takes its distance term from the bin probabilities: "
+                                "call update_trained_sus (a dense update_prob matrix is not covered)")
+        return self.wd.t, self._rows(self._sus_masked, ids, lo), self._binthr, self.n_dist, self.dd * 1000.0
+
     def _prob_rows(self, ids, lo):
         if self.prob is not None:
             return self.wd.t, self._rows(self.prob, ids, lo)
@@ -819,6 +988,8 @@ class OboCARNN(GruBasic):
     matrices wd[(n_dist+1), H, D], input matrix M (H, D), sigmoid RNN, BPR.  Same ctor as the reference; `ulptai` (the
     reference's U x N usrs_last_poi_to_all_intervals matrix) is accepted for signature compatibility but never
     uploaded: with coords= the scoring kernel computes those bins on the fly (bit-identical, tested)."""
+
+    _near_ok = False
 
     spatial = True          # has distance-bin tables (negatives refresh computes dq)
     _pad_ok = False
@@ -1115,12 +1286,22 @@ class Session:
             self._raise_bad()
 
     # ---- recommend ------------------------------------------------------------------------------
-    def recommend(self, slots, k, return_scores=False):
+    def recommend(self, slots, k, return_scores=False, within_km=None, exclude=None, return_counts=False, sync=True):
         """(n, k) int32 device indices by descending score, ties by ascending index: h . trained_items[:-1]^T, plus - spatial -
-        wd * sts[bin(last_poi, .)] for bins below n_dist.  A slot without a check-in has no distance term."""
+        wd * sts[bin(last_poi, .)] for bins below n_dist.  A slot without a check-in has no distance term.
+        within_km / exclude / return_counts rank over restricted candidates instead (poi_score_topk_near, k <= 32): the POIs within
+        within_km km of the slot's last_poi (a slot without a check-in ignores the radius), minus exclude = "last" (the last_poi) or CSR
+        lists (off, ids); -1 ids where fewer than k candidates remain.  Plain models need set_coords() for a radius.  The defaults
+        keep the unrestricted path."""
         m = self.m
         ids = self._slot_tensor(slots)
         n, k = ids.numel(), int(k)
+        if within_km is not None or exclude is not None or return_counts:
+            users = self.h.index_select(0, ids).float().contiguous()
+            anc = self.last_poi.index_select(0, ids).contiguous()
+            term = (m.wd.t, self.sts.index_select(0, ids).contiguous(), m._binthr, m.n_dist, m.dd * 1000.0) if self.spatial else None
+            ex = m._near_exclusion(exclude, n, anc, kinds=("last",))
+            return m._near_launch(users, m.trained_items.t, anc, m._near_radius(within_km), ex, term, k, return_scores, return_counts, sync)
         users = self.h.index_select(0, ids).float().contiguous()
         idx = torch.empty((n, k), dtype=torch.int32, device=m.device)
         sc = torch.empty((n, k), dtype=torch.float32, device=m.device) if return_scores else None
@@ -1536,6 +1717,17 @@ class OboFpmc_lr(_Base):
         self._seed_end(seed, idx)
         return (idx, sc) if return_scores else idx
 
+    def _near_items(self):
+        return self._items()
+
+    def _last_train_poi(self):
+        return self.tra_last_poi
+
+    def compute_sub_topk_near(self, start_end, k, within_km=None, exclude=None, anchor=None, **kw):
+        """The restricted-candidate protocol of the FPMC-LR paper: within_km defaults to the model's own UD (ud_km), so that a row's
+        candidates are neighbours(last POI) + the last POI itself; within_km=float("inf") lifts the radius."""
+        return super().compute_sub_topk_near(start_end, k, self.ud_km if within_km is None else within_km, exclude, anchor, **kw)
+
     def compute_sub_auc_preference(self, start_end):
         """FPMC_LR.py:84-104 -> bool ndarray (n, len_tes)."""
         ids, users, lo = self._users_rows(start_end)
@@ -1559,6 +1751,8 @@ class OboPrme(_Base):
     None).  test: [tes_pois_masks, tes_all_times, tes_all_dists, tes_masks, tes_pois_neg_masks] (times / dists are not read).  cordi:
     (n_item + 1, 2) lat, lon with the pad row (`location` of load_data).  n_size = D, a multiple of 4 in [4, 128].  Extra keywords:
     device, init (dict of float64 arrays du / dp / ds), seed."""
+
+    _near_ok = False
 
     TABLES = ("du", "dp", "ds")
 
@@ -1782,6 +1976,8 @@ class OboGeoIE(_Base):
     d_min (km; pairs use max(d, d_min), 0 = the reference), score_norm ("reference": the reference's divisor - the sum of the padded id row -,
     "count": the sequence length)."""
 
+    _near_ok = False
+
     TABLES = ("g", "h", "t", "z")
 
     def __init__(self, train, test, alpha_lambda, n_user, n_item, n_in, n_hidden, coords=None, device="cuda:0", init=None, seed=None,
@@ -1969,6 +2165,8 @@ class OboPoi2vec(_Base):
     device, init (dict of float64 arrays xu / wl (n_item rows) / pb), seed, softmax_axis ("reference": plu is a softmax over the USERS of
     the evaluation batch, as POI2Vec.py:92 computes it; "items": over the POIs), eval_context ("reference": the contexts of the evaluation
     are read from the TRAIN table at the user's first rows, POI2Vec.py:94-95; "test": the test contexts)."""
+
+    _near_ok = False
 
     TABLES = ("xu", "wl", "pb")
 
