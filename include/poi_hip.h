@@ -63,6 +63,8 @@ extern "C" {
 /* additive to 9: restricted recommendation - new entry point poi_score_topk_near (public/Valuate.py:132-146 over the candidate sets of
  * public/Load_Data_fpmc_lr.py:114-143), options "near_split_max" / "near_grid", plan keys "near_path" / "near_splits" / "near_split_max"
  * (existing entries unchanged). */
+/* additive to 9: exact target ranks - new entry points poi_score_rank and poi_rank_scores, option "rank_grid", plan key "rank_splits",
+ * timing names "score_rank" / "rank_scores" (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -145,7 +147,8 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * workgroups of its persistent grid when the last training launch was a poi_cell_step, 0 otherwise.
  * Additive to 9: "session_path", "session_tiles", "session_tile_min" - written by poi_session_advance (which leaves the other keys as they
  * are and also makes the plan readable).
- * Additive to 9: "near_path", "near_splits", "near_split_max" - written by poi_score_topk_near in the same way. */
+ * Additive to 9: "near_path", "near_splits", "near_split_max" - written by poi_score_topk_near in the same way.
+ * Additive to 9: "rank_splits" - written by poi_score_rank in the same way. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -215,7 +218,9 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *   "near_split_max" n (default 256): poi_score_topk_near calls of at most n rows cut every row's band into slices, a workgroup each, and
  *       merge the slices' lists (0: never); larger calls run one workgroup per row;
  *   "near_grid" n (default 0 = by the row count and the CUs; at most 64): slices per row on that split path - bitwise the same result for
- *       every n and on either path. */
+ *       every n and on either path.
+ *   "rank_grid" n (default 0 = by the row count and the CUs): poi_score_rank splits the item range of a 32-row tile over at most n
+ *       wavefronts (never fewer than ceil(item tiles / 65535)) - identical ranks for every n. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -724,6 +729,40 @@ int poi_score_topk_near(poi_ctx* ctx, const float* users, const float* items, in
                         const int32_t* ex_off, const int32_t* ex,
                         const float* wd, const float* sts, const double* thr, int32_t n_dist, double dd,
                         int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+
+/* ---- exact target ranks (additive to 9): where given POIs stand among ALL POIs ------------------------------------------------------------
+ * public/Valuate.py knows a held-out POI only through a top-K list (:132-146) or one sampled negative (:113-118).  These entries give
+ * its exact rank, from which MRR, mean / median rank, recall at any cut-off and the AUC over all negatives follow, without an
+ * (n, n_item) score matrix.
+ *   C(r)            = [0, n_item) minus ex[ex_off[r] .. ex_off[r + 1])
+ *   rank_out[r][i]  = |{ j in C(r), j != t : s(r, j) > s(r, t) or (s(r, j) == s(r, t) and j < t) }|   for t = tgt[r][i], tmask[r][i] != 0,
+ *                     t in C(r): the tie rule of every top-K entry, i.e. the 0-based position of t in an endless poi_score_topk list.
+ *   count_out[r]    = |C(r)| (n), or NULL.
+ *   -1              for a masked position (tmask 0: tgt is not read as an id), for an excluded target, and for a target outside
+ *                   [0, n_item), which is also counted (poi_ctx_take_bad_ids).
+ *   s(r, j)         users[r] . items[j] in float32 on the f32 matrix pipe (exact products, one fixed k order); with wd non-NULL plus
+ *                   wd * sts[r][bin(last_poi[r], j)] for bin < n_dist - the arguments and the rule of poi_score_topk_geo (sts (n, n_dist + 1)
+ *                   is read for exactly n rows).  wd NULL: the plain score; sts / coords / cphi / thr / last_poi are then ignored.
+ *                   A target's own score comes from the same product routine and k order as the streamed scores, so a POI whose item row
+ *                   equals the target's ties bit for bit and the index decides.  score_out (n, len_t) or NULL: s(r, t), -inf where the
+ *                   rank is -1.
+ *   tgt, tmask      (n, len_t) int32, 1 <= len_t <= 8 (larger: POI_ENOTSUP).
+ *   ex              as poi_score_topk_near: ex_off (n + 1) ascending offsets into ex, ids ascending and unique within a row, both NULL =
+ *                   none.  A row whose list is not ascending or leaves [0, n_item) is rejected: ranks -1, count 0, counted once.
+ *   items           float32 or a registered half table; rows >= n_item (the padding row) are never read.  dim: a multiple of 4, <= 256.
+ * Two kernels: the targets' scores (which also set rank_out to 0 / -1), then the tile walk of the fused top-K with a compare-and-count
+ * epilogue; the item range of a 32-row tile is split over up to "rank_grid" wavefronts and every (row, target) receives integer
+ * atomic adds only - identical calls and different grids give identical ranks.  poi_ctx_last_plan "rank_splits": the split taken.
+ * Timing name: "score_rank".  n = 0 is a no-op. */
+int poi_score_rank(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                   const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                   int32_t n_dist, double dd,
+                   const int32_t* tgt, const int32_t* tmask, int32_t len_t, const int32_t* ex_off, const int32_t* ex,
+                   int32_t* rank_out, float* score_out, int32_t* count_out, void* stream);
+/* The same definition on explicit score rows scores (n, n_item) - the counterpart of poi_topk for models whose score is not
+ * users . items, and an independent check of the counting.  NaN scores count as below every target.  Timing name: "rank_scores". */
+int poi_rank_scores(poi_ctx* ctx, const float* scores, int32_t n, int32_t n_item, const int32_t* tgt, const int32_t* tmask, int32_t len_t,
+                    const int32_t* ex_off, const int32_t* ex, int32_t* rank_out, int32_t* count_out, void* stream);
 
 /* ---- multi-GPU reconciliation (8e; new - the reference is single-process) ----------------------
  * Users are sharded across ranks, every rank trains on a full parameter replica with no data-path collective,

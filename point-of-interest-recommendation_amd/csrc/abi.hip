@@ -79,7 +79,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR
@@ -105,6 +105,9 @@ struct poi_ctx {
   DevBuf near_ws;
   int near_split_max = 256; // option "near_split_max": poi_score_topk_near calls of at most this many rows split each row's band over several workgroups
   int near_grid = 0;        // option "near_grid": workgroups per row on the split path (0: by the row count and the CUs)
+  // exact target ranks (rank.hip): the targets' scores and ids, pass 1 -> pass 2
+  DevBuf rank_ws;
+  int rank_grid = 0;        // option "rank_grid": cap of the item ranges a 32-row tile is split into (0: by the row count and the CUs)
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)
@@ -240,7 +243,7 @@ int poi_ctx_destroy(poi_ctx* c) {
   if (!c) return POI_OK;
   DevBuf* all[] = {&c->ex_ws, &c->ex_slab, &c->ex_glt, &c->ex_gdi, &c->ws, &c->slab, &c->te_ws, &c->hslab, &c->zrow, &c->g_lt, &c->mult_lt, &c->nseq_lt, &c->g_di, &c->mult_di, &c->nseq_di, &c->seg_s, &c->seg_e, &c->pmark, &c->xc, &c->kc_dev, &c->uidx_stage, &c->out_stage, &c->ptab, &c->iota, &c->xw, &c->xg, &c->xflag, &c->bad_ids,
                    &c->g_wd, &c->mult_wd, &c->nseq_wd, &c->ca_ws, &c->ca_slab, &c->ca_scr, &c->ca2, &c->g_ux, &c->cnt_ux, &c->g_blt, &c->cnt_blt, &c->cand_s, &c->cand_i, &c->items_pk, &c->gbound, &c->st,
-                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->cell_ws, &c->vb_ws};
+                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->cell_ws, &c->vb_ws, &c->rank_ws};
   (void)hipDeviceSynchronize();
   c->tm.clear();
   drop_graphs(c);
@@ -1725,6 +1728,71 @@ int poi_score_topk_near(poi_ctx* c, const float* users, const float* items, int3
   return POI_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// exact target ranks (rank.hip)
+static int rank_check(poi_ctx* c, const char* who, int32_t n, int32_t n_item, const int32_t* tgt, const int32_t* tmask, int32_t len_t,
+                      const int32_t* ex_off, const int32_t* ex, const int32_t* rank_out) {
+  if (!tgt || !tmask || !rank_out) return fail(c, POI_EINVAL, "%s: NULL tgt / tmask / rank_out", who);
+  if (len_t <= 0 || len_t > RANK_LT_MAX) return fail(c, POI_ENOTSUP, "%s supports 1 <= len_t <= %d (got %d)", who, RANK_LT_MAX, len_t);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "%s: n < 0 or n_item <= 0", who);
+  if ((ex_off == nullptr) != (ex == nullptr)) return fail(c, POI_EINVAL, "%s: ex_off and ex go together", who);
+  return POI_OK;
+}
+
+int poi_score_rank(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                   const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                   const int32_t* tgt, const int32_t* tmask, int32_t len_t, const int32_t* ex_off, const int32_t* ex, int32_t* rank_out,
+                   float* score_out, int32_t* count_out, void* stream) {
+  if (!c || !users || !items) return fail(c, POI_EINVAL, "poi_score_rank: NULL ctx / users / items");
+  int rc;
+  if ((rc = rank_check(c, "poi_score_rank", n, n_item, tgt, tmask, len_t, ex_off, ex, rank_out))) return rc;
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_score_rank: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  const bool geo = wd != nullptr;
+  if (geo && (!sts || !coords || !cphi || !thr || !last_poi)) return fail(c, POI_EINVAL, "poi_score_rank: the distance term needs sts / coords / cphi / thr / last_poi");
+  if (geo && (n_dist <= 0 || !(dd > 0))) return fail(c, POI_EINVAL, "poi_score_rank: the distance term needs n_dist > 0 and dd > 0");
+  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "poi_score_rank: users must be float32");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::RankArgs A = {};
+  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
+  A.n = n; A.n_item = n_item; A.dim = dim; A.len_t = len_t;
+  if (geo) { A.wd = wd; A.sts = sts; A.coords = coords; A.cphi = cphi; A.thr = thr; A.last_poi = last_poi; A.n_dist = n_dist; A.bin_scale = (float)(12742.0 * 1000.0 / dd); }
+  A.tgt = tgt; A.tmask = tmask; A.ex_off = ex_off; A.ex = ex;
+  A.rank_out = rank_out; A.score_out = score_out; A.count_out = count_out;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
+  if ((rc = ensure(c, c->rank_ws, sizeof(poi::RankTgt) * (size_t)n_utile * 32 * RANK_LT_MAX, st))) return rc;
+  A.tl = (poi::RankTgt*)c->rank_ws.p;
+  // item ranges per 32-row tile, one wave each: 8 waves per CU over the call, at least 8 tiles per range; "rank_grid" caps it; the 16-bit
+  // per-lane counters set the floor
+  int want = (c->num_cu * 8 + n_utile - 1) / n_utile;
+  if (want > ntile / 8) want = ntile / 8;
+  if (c->rank_grid > 0 && want > c->rank_grid) want = c->rank_grid;
+  if (want < 1) want = 1;
+  if (want < (ntile + RANK_TILES_MAX - 1) / RANK_TILES_MAX) want = (ntile + RANK_TILES_MAX - 1) / RANK_TILES_MAX;
+  A.n_split = want;
+  c->plan.valid = 1; c->plan.rank_splits = want;
+  HIPCHK(c, poi::launch_rank(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_rank_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, const int32_t* tgt, const int32_t* tmask, int32_t len_t,
+                    const int32_t* ex_off, const int32_t* ex, int32_t* rank_out, int32_t* count_out, void* stream) {
+  if (!c || !scores) return fail(c, POI_EINVAL, "poi_rank_scores: NULL ctx / scores");
+  int rc;
+  if ((rc = rank_check(c, "poi_rank_scores", n, n_item, tgt, tmask, len_t, ex_off, ex, rank_out))) return rc;
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  c->tm.begin("rank_scores", st);
+  HIPCHK(c, poi::launch_rank_scores(scores, n, n_item, tgt, tmask, len_t, ex_off, ex, rank_out, count_out, (int*)c->bad_ids.p, st));
+  c->tm.end(st);
+  return POI_OK;
+}
+
 int poi_topk(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, int32_t k, int32_t* idx_out, float* score_out,
              void* stream) {
   if (!c || !scores || !idx_out) return fail(c, POI_EINVAL, "poi_topk: NULL argument");
@@ -1852,7 +1920,8 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
   const Opt opts[] = {{"forward_table_compact", &c->xcomp, 0, 1}, {"forward_table_compact_min", &c->xcomp_min, 0, 1 << 30}, {"head_split", &c->head3, 0, 1},
                       {"early_bins", &c->early_bins, 0, 1}, {"hot_bins", &c->hot_bins, 0, 1}, {"hybrid", &c->hybrid, 0, 1}, {"hybrid_min", &c->hyb_min, 0, 1 << 30}, {"hybrid_max", &c->hyb_max, 0, 1 << 30}, {"hybrid_force", &c->hyb_force, 0, 1 << 30},
                       {"cell_grid", &c->cell_grid, 0, 1 << 30}, {"vbpr_grid", &c->vbpr_grid, 0, 1 << 30}, {"session_tile_min", &c->sess_tile_min, 1, 1 << 30},
-                      {"near_split_max", &c->near_split_max, 0, 1 << 30}, {"near_grid", &c->near_grid, 0, NEAR_SPLIT_LIMIT}};
+                      {"near_split_max", &c->near_split_max, 0, 1 << 30}, {"near_grid", &c->near_grid, 0, NEAR_SPLIT_LIMIT},
+                      {"rank_grid", &c->rank_grid, 0, 1 << 30}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);
@@ -1932,7 +2001,8 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"fork", &poi_ctx::LastPlan::fork}, {"cell_kernel", &poi_ctx::LastPlan::cell_kernel}, {"cell_grid", &poi_ctx::LastPlan::cell_grid},
       {"session_path", &poi_ctx::LastPlan::session_path}, {"session_tiles", &poi_ctx::LastPlan::session_tiles},
       {"session_tile_min", &poi_ctx::LastPlan::session_tile_min}, {"near_path", &poi_ctx::LastPlan::near_path},
-      {"near_splits", &poi_ctx::LastPlan::near_splits}, {"near_split_max", &poi_ctx::LastPlan::near_split_max}};
+      {"near_splits", &poi_ctx::LastPlan::near_splits}, {"near_split_max", &poi_ctx::LastPlan::near_split_max},
+      {"rank_splits", &poi_ctx::LastPlan::rank_splits}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

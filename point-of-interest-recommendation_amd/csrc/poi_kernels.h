@@ -557,6 +557,26 @@ struct NearArgs {
 };
 hipError_t launch_near(NearArgs& A, hipStream_t st, Timing* tm);
 
+// Exact rank of target POIs among all POIs (rank.hip)
+#define RANK_LT_MAX 8                       // targets per row
+#define RANK_TILES_MAX 65535                // item tiles one wave may walk: its per-lane counters are 16 bits wide
+struct RankTgt { float s; int id; };        // a target's score and id; (+inf, -1): not ranked
+struct RankArgs {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim, len_t;
+  const float *wd, *sts; const double *coords, *cphi, *thr; const int* last_poi; int n_dist; float bin_scale;      // distance term, or wd null
+  const int *tgt, *tmask;                                     // (n, len_t)
+  const int *ex_off, *ex;                                     // per-row exclusion lists (ascending ids), or both null
+  int n_split;                                                // item ranges (one per wave) of a 32-row tile
+  int t_off;                                                  // first target slot of this walk (pass 2 takes up to 4 per launch)
+  RankTgt* tl;                                                // workspace (32-row tiles, RANK_LT_MAX): pass 1 -> pass 2
+  int* rank_out; float* score_out; int* count_out;            // score_out / count_out may be null
+  int* bad;                                                   // device counter of rejected targets / rows (poi_ctx_take_bad_ids)
+};
+hipError_t launch_rank(const RankArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_rank_scores(const float* scores, int n, int n_item, const int* tgt, const int* tmask, int len_t, const int* ex_off,
+                              const int* ex, int* rank_out, int* count_out, int* bad, hipStream_t st);
+
 // scoring / top-K
 struct ScoreArgs {
   const float *users, *items; int items_f16;      // items: float32, or IEEE half when items_f16

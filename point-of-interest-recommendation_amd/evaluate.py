@@ -98,6 +98,73 @@ def device_rank_metrics(model, starts_ends_tes, at_nums, within_km=None, exclude
     return out
 
 
+def rank_summary(ranks, counts, at_nums, n_user=None):
+    """The formulas of full_rank_metrics on host arrays: ranks (n, len_t) with -1 = not ranked, counts (n) ranked POIs per row.
+    hits / recall / ndcg agree with rank_metrics on a list built from the same ranks (a target at rank < k is a hit at position rank;
+    distinct valid targets of a row have distinct ranks)."""
+    ranks = np.asarray(ranks, np.int64)
+    counts = np.asarray(counts, np.int64)
+    ok = ranks >= 0
+    denom = float(ok.sum())
+    r = ranks[ok].astype(np.float64)
+    c = np.broadcast_to(counts[:, None], ranks.shape)[ok].astype(np.float64)
+    n_user = len(ranks) if n_user is None else n_user
+    n_test = ok.sum(axis=1)
+    out = dict(n=denom, mrr=float((1.0 / (r + 1.0)).sum() / denom) if denom else 0.0, mean_rank=float(r.mean()) if denom else 0.0,
+               median_rank=float(np.sort(r)[(len(r) - 1) // 2]) if denom else 0.0,
+               auc_full=float(np.where(c > 1, 1.0 - r / np.maximum(c - 1.0, 1.0), 1.0).sum() / denom) if denom else 0.0, at={})
+    for k in at_nums:
+        hit = ok & (ranks < k)
+        disc = np.where(hit, 1.0 / np.log2(np.maximum(ranks, 0) + 2.0), 0.0)
+        ideal = np.array([(1.0 / np.log2(np.arange(min(int(t), k)) + 2.0)).sum() for t in n_test])
+        ndcg = np.where(hit.any(axis=1), disc.sum(axis=1) / np.maximum(ideal, 1e-300), 0.0)
+        hits = float(hit.sum())
+        out["at"][k] = dict(hits=hits, recall=hits / denom if denom else 0.0, ndcg=float(ndcg.sum() / n_user))
+    return out
+
+
+def full_rank_metrics(model, starts_ends_tes, at_nums, exclude=None):
+    """Metrics from the EXACT rank of every held-out POI among all POIs (model.compute_sub_target_rank): independent of the negative
+    sampler and of any list length.  Returns dict(n, mrr, mean_rank, median_rank (the lower median), auc_full = mean of
+    1 - rank / (count - 1) - the share of the other ranked POIs that score below the target -, at = {k: dict(hits, recall, ndcg)}) for
+    any ascending cut-offs 1 <= k <= n_item; recall / ndcg follow rank_metrics' definitions.  exclude as compute_sub_target_rank (a
+    target that is excluded is not ranked and leaves every mean).  The reductions are torch ops on the device; scalars reach the host."""
+    import torch
+    at_nums = list(at_nums)
+    if any(b <= a for a, b in zip(at_nums, at_nums[1:])) or (at_nums and (at_nums[0] <= 0 or at_nums[-1] > model.n_item)):
+        raise ValueError("at_nums must be strictly ascending cut-offs in [1, n_item] (got %r)" % (at_nums,))
+    dev = model.device
+    f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
+    acc = f64(4)                                  # valid positions, sum 1 / (rank + 1), sum rank, sum auc term
+    hits, ndcg = f64(len(at_nums)), f64(len(at_nums))
+    lt = model.tes_masks.shape[1]
+    disc_cum = torch.cat([f64(1), torch.cumsum(1.0 / torch.log2(torch.arange(lt, device=dev, dtype=torch.float64) + 2.0), 0)])      # ideal DCG of m hits
+    kept = []
+    for se in coalesce_ranges(starts_ends_tes):
+        rank, cnt = model.compute_sub_target_rank(se, exclude=exclude, return_counts=True)
+        ok = rank >= 0
+        r = rank.double()
+        c = cnt.double()[:, None].expand_as(r)
+        acc += torch.stack([ok.sum().double(), torch.where(ok, 1.0 / (r + 1.0), f64(1)).sum(), torch.where(ok, r, f64(1)).sum(),
+                            torch.where(ok, torch.where(c > 1, 1.0 - r / (c - 1.0).clamp(min=1.0), f64(1) + 1.0), f64(1)).sum()])
+        n_test = ok.sum(1)
+        for i, k in enumerate(at_nums):
+            hit = ok & (rank < k)
+            dcg = torch.where(hit, 1.0 / torch.log2(r.clamp(min=0) + 2.0), f64(1)).sum(1)
+            ideal = disc_cum[n_test.clamp(max=min(k, lt))]
+            hits[i] += hit.sum(); ndcg[i] += torch.where(hit.any(1), dcg / ideal.clamp(min=1e-300), f64(1)).sum()
+        kept.append(rank[ok])
+    allr = torch.cat(kept) if kept else torch.zeros(0, dtype=torch.int32, device=dev)
+    med = float(torch.sort(allr)[0][(allr.numel() - 1) // 2].item()) if allr.numel() else 0.0
+    a, h, g = acc.cpu().numpy(), hits.cpu().numpy(), ndcg.cpu().numpy()
+    n = float(a[0])
+    out = dict(n=n, mrr=float(a[1] / n) if n else 0.0, mean_rank=float(a[2] / n) if n else 0.0, median_rank=med,
+               auc_full=float(a[3] / n) if n else 0.0, at={})
+    for i, k in enumerate(at_nums):
+        out["at"][k] = dict(hits=float(h[i]), recall=float(h[i] / n) if n else 0.0, ndcg=float(g[i]) / model.n_user)
+    return out
+
+
 def fun_predict_auc_recall_map_ndcg(p, model, best, epoch, starts_ends_auc, starts_ends_tes, tes_buys_masks, tes_masks, on_device=True):
     """Same signature and side effects on `best` as public/Valuate.py:103-191; returns the metrics too.
     With on_device (default) the ranks never leave the GPU; on_device=False downloads them and uses the

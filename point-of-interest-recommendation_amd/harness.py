@@ -119,6 +119,22 @@ def load_checkpoint(model, path):
     model.load_params(read_checkpoint(path))
 
 
+def evaluate_epoch(p, model, best, epoch, starts_ends_auc, starts_ends_tes, tes_buys_masks, tes_masks, full_rank=False):
+    """The epoch's evaluation of every driver: fun_predict_auc_recall_map_ndcg, plus - with full_rank=True (p["full_rank"]; off by
+    default) - the exact-rank metrics of evaluate.full_rank_metrics (mrr, mean / median rank, auc_full, recall at p["full_rank_at"],
+    default [20, 100, 1000] clipped to n_item) under the key "full_rank", which the epoch record then carries."""
+    m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, starts_ends_auc, starts_ends_tes, tes_buys_masks, tes_masks)
+    if full_rank:
+        from .evaluate import full_rank_metrics
+        at = sorted(set(min(int(k), model.n_item) for k in p.get("full_rank_at", [20, 100, 1000])))
+        m["full_rank"] = full_rank_metrics(model, starts_ends_tes, at)
+    return m
+
+
+def _full_rank(m):
+    return {"full_rank": m["full_rank"]} if "full_rank" in m else {}
+
+
 def train_valid_or_test(ds, p, device="cuda:0", log=print):
     if ds is None or isinstance(ds, str):                          # a sequence file: BASELINE.json configs[0] through the product
         if isinstance(ds, str):
@@ -190,9 +206,9 @@ def train_valid_or_test(ds, p, device="cuda:0", log=print):
             model.update_trained_users(torch.cat(hs))
             model.update_trained_sus(torch.cat(ss))
         t2 = time.time()
-        m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m)
+        m = evaluate_epoch(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m, full_rank=bool(p.get("full_rank", False)))
         t3 = time.time()
-        history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall=[m["at"][k]["recall"] for k in p["at_nums"]],
+        history.append(dict(_full_rank(m), epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall=[m["at"][k]["recall"] for k in p["at_nums"]],
                             times=(t1 - t0, t2 - t1, t3 - t2)))
         log("epoch %d  sum_loss = %.3f = %.3f + %.3f  auc %.4f  recall@%d %.4f  time (train, user, test) %.2fs %.2fs %.2fs"
             % (epoch, loss + l2, loss, l2, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1, t3 - t2))
@@ -249,9 +265,9 @@ def train_minibatch(ds, p=None, device="cuda:0", log=print):
         model.update_trained_items()
         model.update_trained_users(torch.cat([model.predict_device(se) for se in ses_pred]))
         t2 = time.time()
-        m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m)
+        m = evaluate_epoch(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m, full_rank=bool(p.get("full_rank", False)))
         t3 = time.time()
-        history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall=[m["at"][k]["recall"] for k in p["at_nums"]],
+        history.append(dict(_full_rank(m), epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall=[m["at"][k]["recall"] for k in p["at_nums"]],
                             times=(t1 - t0, t2 - t1, t3 - t2)))
         log("epoch %d  sum_loss = %.3f = %.3f + %.3f  auc %.4f  recall@%d %.4f  time (train, user, test) %.2fs %.2fs %.2fs"
             % (epoch, loss + l2, loss, l2, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1, t3 - t2))
@@ -321,9 +337,9 @@ def train_fpmc_lr(ds, p=None, device="cuda:0", log=print):
             loss = float(torch.cat(parts).double().sum().item()) if parts else 0.0
         l2 = model.l2.eval()                                        # :191
         t1 = time.time()
-        m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m)      # :199-201
+        m = evaluate_epoch(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m, full_rank=bool(p.get("full_rank", False)))      # :199-201
         t2 = time.time()
-        history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall={k: m["at"][k]["recall"] for k in p["at_nums"]},
+        history.append(dict(_full_rank(m), epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall={k: m["at"][k]["recall"] for k in p["at_nums"]},
                             transitions=n, times=(t1 - t0, t2 - t1)))
         log("epoch %d  sum_loss = %.3f = %.3f - %.3f  auc %.4f  recall@%d %.4f  time (train, test) %.2fs %.2fs"
             % (epoch, loss + l2, loss, l2, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1))
@@ -372,9 +388,9 @@ def train_prme(ds, p=None, device="cuda:0", log=print):
         l2 = model.l2.eval()                                        # :199
         t1 = time.time()
         model.update_trained_items()                                # :208
-        m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m)      # :213-214
+        m = evaluate_epoch(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m, full_rank=bool(p.get("full_rank", False)))      # :213-214
         t2 = time.time()
-        history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall={k: m["at"][k]["recall"] for k in p["at_nums"]},
+        history.append(dict(_full_rank(m), epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall={k: m["at"][k]["recall"] for k in p["at_nums"]},
                             transitions=n, times=(t1 - t0, t2 - t1)))
         log("epoch %d  sum_loss = %.3f = %.3f + %.3f  auc %.4f  recall@%d %.4f  time (train, test) %.2fs %.2fs"
             % (epoch, loss + l2, loss, l2, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1))
@@ -434,9 +450,9 @@ def train_vbpr(ds, p=None, device="cuda:0", log=print):
             model.update_trained_items()
             model.update_trained_users()
             t2 = time.time()
-            m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m)
+            m = evaluate_epoch(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m, full_rank=bool(p.get("full_rank", False)))
             t3 = time.time()
-            history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall=[m["at"][k]["recall"] for k in p["at_nums"]],
+            history.append(dict(_full_rank(m), epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall=[m["at"][k]["recall"] for k in p["at_nums"]],
                                 times=(t1 - t0, t2 - t1, t3 - t2)))
             log("epoch %d  sum_loss = %.3f = %.3f + %.3f  auc %.4f  recall@%d %.4f  time (train, user, test) %.2fs %.2fs %.2fs"
                 % (epoch, loss + l2, loss, l2, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1, t3 - t2))
@@ -484,9 +500,9 @@ def train_geoie(ds, p=None, device="cuda:0", log=print):
         a, b = float(model.ab[0].item()), float(model.ab[1].item())
         t1 = time.time()
         model.update_trained()                                      # :200
-        m = fun_predict_auc_recall_map_ndcg(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m)      # :204-206
+        m = evaluate_epoch(p, model, best, epoch, ses_auc, ses_tes, tes_p, tes_m, full_rank=bool(p.get("full_rank", False)))      # :204-206
         t2 = time.time()
-        history.append(dict(epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall={k: m["at"][k]["recall"] for k in p["at_nums"]},
+        history.append(dict(_full_rank(m), epoch=epoch, loss=loss, l2=l2, auc=m["auc"], recall={k: m["at"][k]["recall"] for k in p["at_nums"]},
                             a=a, b=b, rejected=rejected, times=(t1 - t0, t2 - t1)))
         log("epoch %d  sum_loss = %.3f = %.3f + %.3f  a %.6f  b %.6f  rejected users %d  auc %.4f  recall@%d %.4f  time (train, test) %.2fs %.2fs"
             % (epoch, loss + l2, loss, l2, a, b, rejected, m["auc"], p["at_nums"][-1], m["at"][p["at_nums"][-1]]["recall"], t1 - t0, t2 - t1))

@@ -469,6 +469,135 @@ class _Base:
         return self._near_launch(users, self._near_items(), anc, self._near_radius(within_km), ex, self._near_term(ids, lo), k,
                                  return_scores, return_counts, sync)
 
+    # ---- exact target ranks (poi_score_rank / poi_rank_scores): where the held-out POIs stand among ALL POIs ---------------------------
+    _rank_fused = True      # False: the model's score is not users . items - explicit score rows + poi_rank_scores
+
+    def _rank_term(self, ids, lo):
+        """(wd, sts rows (n, n_dist + 1), last POI rows (n)) of the model's distance term, or None."""
+        return None
+
+    def _rank_targets(self, targets, n, ids=None, lo=None):
+        """targets -> (tgt, tmask) int32 device tensors (n, len_t): None = the model's test rows, an (n, len_t) array of POI ids (all
+        valid), or a pair (ids, mask)."""
+        if targets is None:
+            tgt, tm = self._rows(self.tes_buys_masks, ids, lo), self._rows(self.tes_masks, ids, lo)
+        else:
+            tgt, tm = targets if isinstance(targets, tuple) and len(targets) == 2 else (targets, None)
+            tgt = self._dev(tgt, torch.int32).reshape(n, -1)
+            tm = torch.ones_like(tgt) if tm is None else self._dev(tm, torch.int32).reshape(n, -1)
+        if tgt.shape != tm.shape:
+            raise ValueError("targets and their mask must have the same shape (%s vs %s)" % (tuple(tgt.shape), tuple(tm.shape)))
+        if not 1 <= tgt.shape[1] <= 8:
+            raise _lib.PoiError("target ranks support 1 .. 8 targets per row (got %d)" % tgt.shape[1])
+        return tgt.contiguous(), tm.contiguous()
+
+    def _rank_out(self, rank, sc, cnt, return_scores, return_counts, sync):
+        if sync:
+            bad = self.ctx.take_bad_ids(self._stream().value)
+            if bad:
+                raise IndexError("%d target(s) outside [0, %d) or row(s) with a malformed exclusion list: their ranks are -1" % (bad, self.n_item))
+        out = (rank,) + ((sc,) if return_scores else ()) + ((cnt,) if return_counts else ())
+        return out if len(out) > 1 else rank
+
+    def _rank_launch(self, users, items, term, tgt, tm, ex, return_scores, return_counts, sync):
+        """One poi_score_rank call -> rank[, scores][, counts] (device tensors)."""
+        n, lt = users.shape[0], tgt.shape[1]
+        rank = torch.empty((n, lt), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, lt), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        wd = sts = lp = coords = cphi = thr = None
+        n_dist, dd_m = 0, 0.0
+        if term is not None:
+            wd, sts, lp = term
+            coords, cphi, thr, n_dist, dd_m = self.coords, self._cphi, self._binthr, self.n_dist, self.dd * 1000.0
+        self.ctx.check(self.lib.poi_score_rank(self.ctx.handle, _ptr(users), _ptr(items), n, self.n_item, self.kdim, _ptr(wd), _ptr(sts), _ptr(coords),
+                                               _ptr(cphi), _ptr(thr), _ptr(lp), int(n_dist), float(dd_m), _ptr(tgt), _ptr(tm), lt, _ptr(ex[0]), _ptr(ex[1]),
+                                               _ptr(rank), _ptr(sc), _ptr(cnt), self._stream()))
+        return self._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
+
+    def _rank_score_rows(self, a):
+        """Fallback models: (score rows (m, n_item) ranked by descending value, rows per user) for the users `a`."""
+        return self.compute_sub_all_scores_device(a), 1
+
+    def _rank_from_scores(self, start_end, exclude, targets, return_scores, return_counts, sync):
+        """Explicit score rows, a bounded number of users at a time, + poi_rank_scores."""
+        a = start_end if isinstance(start_end, torch.Tensor) else np.atleast_1d(np.asarray(start_end))
+        n = len(a)
+        ids, lo = self._ids(a)
+        tgt, tm = self._rank_targets(targets, n, ids, lo)
+        ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+        lt = tgt.shape[1]
+        rank = torch.full((n, lt), -1, dtype=torch.int32, device=self.device)
+        sc = torch.full((n, lt), float("-inf"), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        step = self._rank_chunk(n)
+        for o in range(0, n, step):
+            c = min(step, n - o)
+            full, per = self._rank_score_rows(a[o:o + c])
+            t_c, m_c = tgt[o:o + c], tm[o:o + c]
+            eo = ex[0][o:o + c + 1].contiguous() if ex[0] is not None else None
+            if per == 1:
+                r_c = torch.empty((c, lt), dtype=torch.int32, device=self.device)
+                k_c = torch.empty(c, dtype=torch.int32, device=self.device) if cnt is not None else None
+                self.ctx.check(self.lib.poi_rank_scores(self.ctx.handle, _ptr(full), c, self.n_item, _ptr(t_c.contiguous()), _ptr(m_c.contiguous()), lt,
+                                                        _ptr(eo), _ptr(ex[1]), _ptr(r_c), _ptr(k_c), self._stream()))
+            else:
+                # rows (user, position): position t ranks the user's t-th target; positions beyond `per` stay -1
+                w = min(per, lt)
+                t_r = torch.zeros((c, per), dtype=torch.int32, device=self.device); m_r = torch.zeros_like(t_r)
+                t_r[:, :w] = t_c[:, :w]; m_r[:, :w] = m_c[:, :w]
+                if eo is not None:                               # every position of a user shares the user's list
+                    b, l = eo[:-1].long(), (eo[1:] - eo[:-1]).long()
+                    l_r = l.repeat_interleave(per)
+                    o_r = torch.zeros(c * per + 1, dtype=torch.int64, device=self.device); o_r[1:] = torch.cumsum(l_r, 0)
+                    pos = torch.arange(int(o_r[-1].item()), device=self.device) - torch.repeat_interleave(o_r[:-1] - b.repeat_interleave(per), l_r)
+                    e_r = (o_r.int(), ex[1][pos].contiguous() if pos.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+                else:
+                    e_r = (None, None)
+                r_r = torch.empty((c * per, 1), dtype=torch.int32, device=self.device)
+                k_r = torch.empty(c * per, dtype=torch.int32, device=self.device) if cnt is not None else None
+                self.ctx.check(self.lib.poi_rank_scores(self.ctx.handle, _ptr(full), c * per, self.n_item, _ptr(t_r.reshape(-1, 1)), _ptr(m_r.reshape(-1, 1)), 1,
+                                                        _ptr(e_r[0]), _ptr(e_r[1]), _ptr(r_r), _ptr(k_r), self._stream()))
+                r_c = torch.full((c, lt), -1, dtype=torch.int32, device=self.device)
+                r_c[:, :w] = r_r.view(c, per)[:, :w]
+                k_c = k_r.view(c, per)[:, 0] if k_r is not None else None
+                full = full.view(c, per, self.n_item)
+            rank[o:o + c] = r_c
+            if cnt is not None:
+                cnt[o:o + c] = k_c
+            if sc is not None:
+                ok = r_c >= 0
+                g = t_c.long().clamp(0, self.n_item - 1)
+                if per == 1:
+                    v = full.gather(1, g)
+                else:
+                    w = min(per, lt)
+                    v = torch.full((c, lt), float("-inf"), dtype=torch.float32, device=self.device)
+                    v[:, :w] = full[:, :w].gather(2, g[:, :w, None])[:, :, 0]
+                sc[o:o + c] = torch.where(ok, v, torch.full_like(v, float("-inf")))
+        return self._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
+
+    def _rank_chunk(self, n):
+        return max(1, min(n, (1 << 28) // max(self.n_item, 1)))      # <= 1 GiB of score rows at a time
+
+    def compute_sub_target_rank(self, start_end, exclude=None, targets=None, return_scores=False, return_counts=False, sync=True):
+        """Exact 0-based rank of each target POI among ALL POIs under the model's own score (include/poi_hip.h, poi_score_rank): the
+        number of POIs with a higher score, or an equal score and a lower id - the position the target would have in an endless
+        compute_sub_topk list.  targets: None = the rows' test POIs (tes_buys_masks / tes_masks), an (n, len_t <= 8) array of POI ids, or
+        a pair (ids, mask).  exclude: None, "train" (the user's distinct train POIs leave the ranking) or CSR lists (off, ids), as
+        compute_sub_topk_near.  Returns (n, len_t) int32 on the device, -1 for a masked position, an excluded target or a target outside
+        [0, n_item) (which - with sync - raises IndexError); with return_scores the targets' scores, with return_counts the number of
+        ranked POIs per row.  No (n, n_item) matrix is built for the models that score by users . items; CA-RNN, PRME and POI2Vec go
+        through their own score rows, a bounded number of users at a time, and poi_rank_scores."""
+        if not self._rank_fused:
+            return self._rank_from_scores(start_end, exclude, targets, return_scores, return_counts, sync)
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        tgt, tm = self._rank_targets(targets, n, ids, lo)
+        ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+        items = self._items() if hasattr(self, "_items") else self.trained_items.t
+        return self._rank_launch(users, items, self._rank_term(ids, lo), tgt, tm, ex, return_scores, return_counts, sync)
+
 
 # =================================================================================================
 class GruBasic(_Base):
@@ -905,6 +1034,18 @@ class OboSpatialGru(GruBasic):
                                 "call update_trained_sus (a dense update_prob matrix is not covered)")
         return self.wd.t, self._rows(self._sus_masked, ids, lo), self._binthr, self.n_dist, self.dd * 1000.0
 
+    def _rank_term(self, ids, lo):
+        """The rows of sts and last train POI that _topk_geo ranks with; a model without bin probabilities ranks by the plain score, as
+        its compute_sub_topk does."""
+        if self.prob is not None:
+            raise _lib.PoiError("compute_sub_target_rank on the spatial model takes its distance term from the bin probabilities: "
+                                "call update_trained_sus (a dense update_prob matrix is not covered)")
+        if self.trained_sus is None:
+            return None
+        if self.coords is None:
+            raise _lib.PoiError("update_trained_sus needs coords= at construction")
+        return self.wd.t, self._rows(self._sus_masked, ids, lo).contiguous(), self._rows(self._last_poi, ids, lo).contiguous()
+
     def _prob_rows(self, ids, lo):
         if self.prob is not None:
             return self.wd.t, self._rows(self.prob, ids, lo)
@@ -1086,6 +1227,8 @@ class OboCARNN(GruBasic):
     def compute_sub_topk(self, start_end, k, return_scores=False):
         """Valuate.py:132-146 on the CA-RNN scores: the (n, n_item) rows stay on the device, poi_topk selects."""
         return self._topk_from_scores(start_end, k, return_scores)
+
+    _rank_fused = False
 
 
 # =================================================================================================
@@ -1339,6 +1482,25 @@ class Session:
             m.ctx.check(m.lib.poi_topk(m.ctx.handle, _ptr(full), c, m.n_item, k, ctypes.c_void_p(idx.data_ptr() + 4 * o * k),
                                        ctypes.c_void_p(sc.data_ptr() + 4 * o * k) if sc is not None else None, m._stream()))
         return (idx, sc) if return_scores else idx
+
+
+    def rank_of(self, slots, pois, exclude=None, return_scores=False, return_counts=False, sync=True):
+        """Exact 0-based rank of pois[i] (one POI per slot, or (n, len_t <= 8)) among all POIs under the slot's CURRENT state - the score
+        rule of `recommend` (h . trained_items[:-1]^T, plus the spatial distance term at last_poi; none before the first check-in):
+        model.compute_sub_target_rank through the session's h / sts / last_poi.  exclude: None, "last" or CSR lists (off, ids)."""
+        m = self.m
+        ids = self._slot_tensor(slots)
+        n = ids.numel()
+        users = self.h.index_select(0, ids).float().contiguous()
+        lpr = self.last_poi.index_select(0, ids).contiguous()
+        tgt, tm = m._rank_targets(pois.reshape(n, -1) if isinstance(pois, torch.Tensor) else np.asarray(pois).reshape(n, -1), n)
+        term = None
+        if self.spatial:
+            st = (self.sts.index_select(0, ids) * (lpr >= 0).float()[:, None]).contiguous()
+            st[:, m.n_dist] = 0.0
+            term = (m.wd.t, st, lpr.clamp(min=0).contiguous())
+        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
+        return m._rank_launch(users, m.trained_items.t, term, tgt, tm, ex, return_scores, return_counts, sync)
 
 
 # =================================================================================================
@@ -1938,6 +2100,13 @@ class OboPrme(_Base):
         idx, sc = self.score_rows_device(ids, self._rows(self.tra_last_poi, ids, lo), k)
         return (idx, sc) if return_scores else idx
 
+    _rank_fused = False
+
+    def _rank_score_rows(self, a):
+        """The rows compute_sub_topk ranks: every user from its row 0 (query = the last train POI)."""
+        ids, lo = self._ids(a)
+        return self.score_rows_device(ids, self._rows(self.tra_last_poi, ids, lo)), 1
+
     def compute_sub_auc_preference(self, start_end):
         """PRME.py:141-159 returns zeros (the AUC code is commented out there): AUC is always 0."""
         ids, _ = self._ids(start_end)
@@ -2355,6 +2524,16 @@ class OboPoi2vec(_Base):
         if not 1 <= int(k) <= min(64, self.n_item):
             raise _lib.PoiError("top-K supports 1 <= k <= min(64, n_item) (got %d)" % k)
         return self._score_call(start_end, k=int(k), return_scores=return_scores, **kw)
+
+    _rank_fused = False
+
+    def _rank_score_rows(self, a):
+        """The rows compute_sub_topk ranks: (user, position) for position < the longest test sequence of the users."""
+        full = self._score_call(a)
+        return full, (full.shape[0] // max(len(a), 1) if len(a) else 1)
+
+    def _rank_chunk(self, n):
+        return max(n, 1)                          # the reference softmax runs over the USERS of a call: the call is not cut
 
     def compute_sub_auc_preference(self, start_end):
         """POI2Vec.py:111-112 returns zeros: AUC is always 0."""
