@@ -65,6 +65,8 @@ extern "C" {
  * (existing entries unchanged). */
 /* additive to 9: exact target ranks - new entry points poi_score_rank and poi_rank_scores, option "rank_grid", plan key "rank_splits",
  * timing names "score_rank" / "rank_scores" (existing entries unchanged). */
+/* additive to 9: fold-in for the factorisation family - new entry point poi_foldin_bpr, timing name "foldin"; no new option or plan key
+ * (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -763,6 +765,33 @@ int poi_score_rank(poi_ctx* ctx, const float* users, const float* items, int32_t
  * users . items, and an independent check of the counting.  NaN scores count as below every target.  Timing name: "rank_scores". */
 int poi_rank_scores(poi_ctx* ctx, const float* scores, int32_t n, int32_t n_item, const int32_t* tgt, const int32_t* tmask, int32_t len_t,
                     const int32_t* ex_off, const int32_t* ex, int32_t* rank_out, int32_t* count_out, void* stream);
+
+/* ---- fold-in (additive to 9): a user row of OboBpr / OboVBpr for a check-in history the model never trained on -------------------------------
+ * The factorisation family's only user representation is a trained row of ux (and ue).  Fold-in freezes the item side and runs the
+ * model's own per-check-in SGD rule - public/BPR.py:216-230 (OboBpr.bpr_train: the ux[u] part of the update) and :287-306 (OboVBpr:
+ * usr and use are regularised with the same lambda, :294-304, so [ux[u] | ue[u]] moves exactly like one BPR-MF user row against
+ * [lt | fi ei^T]) - on one fresh row over that history.  For new user r with history p[off[r] .. off[r + 1]):
+ *   w = w0[r] (zeros when w0 is NULL);  for e = 0 .. epochs - 1, for t in history order:
+ *     d = Y[p_t] - Y[q_{e,t}],   x = w . d,   loss[r][e] += -log sigmoid(x)   (x before the update),
+ *     w = w - alpha (-sigmoid(-x) d + lambda w)
+ *   Y = items (n_item + 1, dim), float32 or a registered half table (the evaluation snapshot trained_items: dim = D for OboBpr, 2 D for
+ *   OboVBpr); q_{e,t} = q[e * q_epoch_stride + off[r] + t] - q_epoch_stride = 0 reuses one draw for every epoch, the usual value is the
+ *   total number of check-ins off[n].  Ids lie in [0, n_item] (the padding row is a legal id, as in poi_bpr_step).
+ * Arithmetic: the running w, the dot product, the sigmoid and the loss are float64 (alpha and lambda are taken at their float values) and
+ * are rounded to float32 once, at the end - the choice poi_session_advance makes for h.  Every sum has one fixed order (per lane its
+ * columns ascending, then a fixed tree over 16 lanes); no atomics touch a result.  A user's output bits depend on its own history,
+ * negatives and w0 alone: not on the other users of the call, on its position in the call or on the grid.
+ * Edge cases: epochs = 0 or an empty history returns w0[r] (zeros without w0) and losses 0; p_t == q_t is legal (d = 0: only the decay
+ * acts).  A user with off[r + 1] < off[r], off[r] < 0 or an id outside [0, n_item] among the ids it reads is a bad user: a NaN row, NaN
+ * losses, counted once (poi_ctx_take_bad_ids), and nothing else moves.  The offsets themselves must lie inside p / q (the caller's
+ * contract, as for every CSR argument).
+ * w_out (n, dim) may alias w0; loss_out (n, epochs) or NULL.  dim: a multiple of 4, up to 256.  n = 0 is a no-op.
+ * One kernel: a 16-lane row of a wave per user, the rows and ids of the next steps in flight while a step computes (foldin.hip).
+ * Timing name: "foldin". */
+int poi_foldin_bpr(poi_ctx* ctx, const float* items, int32_t n_item, int32_t dim,
+                   const int32_t* off, const int32_t* p, const int32_t* q, int64_t q_epoch_stride,
+                   int32_t n, int32_t epochs, float alpha, float lambda,
+                   const float* w0, float* w_out, float* loss_out, void* stream);
 
 /* ---- multi-GPU reconciliation (8e; new - the reference is single-process) ----------------------
  * Users are sharded across ranks, every rank trains on a full parameter replica with no data-path collective,

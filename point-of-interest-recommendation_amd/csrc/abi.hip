@@ -1793,6 +1793,32 @@ int poi_rank_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, 
   return POI_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// fold-in of new users (foldin.hip)
+int poi_foldin_bpr(poi_ctx* c, const float* items, int32_t n_item, int32_t dim, const int32_t* off, const int32_t* p, const int32_t* q,
+                   int64_t q_epoch_stride, int32_t n, int32_t epochs, float alpha, float lambda, const float* w0, float* w_out,
+                   float* loss_out, void* stream) {
+  if (!c || !items || !w_out) return fail(c, POI_EINVAL, "poi_foldin_bpr: NULL ctx / items / w_out");
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_foldin_bpr: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  if (n < 0 || n_item <= 0 || epochs < 0 || q_epoch_stride < 0) return fail(c, POI_EINVAL, "poi_foldin_bpr: n < 0, n_item <= 0, epochs < 0 or q_epoch_stride < 0");
+  if (n == 0) return POI_OK;
+  if (!off || !p || !q) return fail(c, POI_EINVAL, "poi_foldin_bpr: NULL off / p / q");
+  if ((w0 && is_f16(c, w0)) || is_f16(c, w_out)) return fail(c, POI_ENOTSUP, "poi_foldin_bpr: w0 / w_out must be float32");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::FoldinArgs A = {};
+  A.items = items; A.items_f16 = is_f16(c, items);
+  A.n = n; A.n_item = n_item; A.dim = dim; A.epochs = epochs;
+  A.off = off; A.p = p; A.q = q; A.q_epoch_stride = q_epoch_stride;
+  A.alpha = alpha; A.lambda = lambda;
+  A.w0 = w0; A.w_out = w_out; A.loss_out = loss_out;
+  int rc;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  HIPCHK(c, poi::launch_foldin(A, st, &c->tm));
+  return POI_OK;
+}
+
 int poi_topk(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, int32_t k, int32_t* idx_out, float* score_out,
              void* stream) {
   if (!c || !scores || !idx_out) return fail(c, POI_EINVAL, "poi_topk: NULL argument");

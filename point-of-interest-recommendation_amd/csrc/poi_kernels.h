@@ -577,6 +577,18 @@ hipError_t launch_rank(const RankArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_rank_scores(const float* scores, int n, int n_item, const int* tgt, const int* tmask, int len_t, const int* ex_off,
                               const int* ex, int* rank_out, int* count_out, int* bad, hipStream_t st);
 
+// Fold-in of new users for the factorisation family (foldin.hip)
+#define FOLDIN_USERS_PER_WAVE 4             // one 16-lane DPP row per user
+struct FoldinArgs {
+  const void* items; int items_f16;                           // (n_item + 1, dim) float32 or IEEE half
+  int n, n_item, dim, epochs;
+  const int *off, *p, *q; long long q_epoch_stride;           // history CSR (n + 1), positives, negatives of epoch e at q + e * q_epoch_stride
+  float alpha, lambda;
+  const float* w0; float* w_out; float* loss_out;             // (n, dim) or null; (n, dim), may alias w0; (n, epochs) or null
+  int* bad;                                                   // device counter of rejected users (poi_ctx_take_bad_ids)
+};
+hipError_t launch_foldin(const FoldinArgs& A, hipStream_t st, Timing* tm);
+
 // scoring / top-K
 struct ScoreArgs {
   const float *users, *items; int items_f16;      // items: float32, or IEEE half when items_f16

@@ -129,6 +129,21 @@ def full_rank_metrics(model, starts_ends_tes, at_nums, exclude=None):
     1 - rank / (count - 1) - the share of the other ranked POIs that score below the target -, at = {k: dict(hits, recall, ndcg)}) for
     any ascending cut-offs 1 <= k <= n_item; recall / ndcg follow rank_metrics' definitions.  exclude as compute_sub_target_rank (a
     target that is excluded is not ranked and leaves every mean).  The reductions are torch ops on the device; scalars reach the host."""
+    batches = (model.compute_sub_target_rank(se, exclude=exclude, return_counts=True) for se in coalesce_ranges(starts_ends_tes))
+    return _metrics_of_ranks(model, batches, at_nums, model.tes_masks.shape[1], model.n_user)
+
+
+def foldin_rank_metrics(model, histories, targets, at_nums, exclude="history", **fold_in_kwargs):
+    """full_rank_metrics for HELD-OUT users of the factorisation family (strong generalisation): every history is folded in
+    (model.rank_new: fold_in, then the exact rank of its targets among all POIs) and the same reductions run on those ranks.  targets:
+    (n, len_t <= 8) POI ids or a pair (ids, mask); exclude: "history" (default), None or CSR lists.  Returns the keys of
+    full_rank_metrics; ndcg is averaged over the n histories."""
+    rank, cnt = model.rank_new(histories, targets, exclude=exclude, return_counts=True, **fold_in_kwargs)
+    return _metrics_of_ranks(model, [(rank, cnt)], at_nums, rank.shape[1], rank.shape[0])
+
+
+def _metrics_of_ranks(model, batches, at_nums, lt, n_user):
+    """The reductions of full_rank_metrics over (rank (n, lt), count (n)) device batches."""
     import torch
     at_nums = list(at_nums)
     if any(b <= a for a, b in zip(at_nums, at_nums[1:])) or (at_nums and (at_nums[0] <= 0 or at_nums[-1] > model.n_item)):
@@ -137,11 +152,9 @@ def full_rank_metrics(model, starts_ends_tes, at_nums, exclude=None):
     f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
     acc = f64(4)                                  # valid positions, sum 1 / (rank + 1), sum rank, sum auc term
     hits, ndcg = f64(len(at_nums)), f64(len(at_nums))
-    lt = model.tes_masks.shape[1]
     disc_cum = torch.cat([f64(1), torch.cumsum(1.0 / torch.log2(torch.arange(lt, device=dev, dtype=torch.float64) + 2.0), 0)])      # ideal DCG of m hits
     kept = []
-    for se in coalesce_ranges(starts_ends_tes):
-        rank, cnt = model.compute_sub_target_rank(se, exclude=exclude, return_counts=True)
+    for rank, cnt in batches:
         ok = rank >= 0
         r = rank.double()
         c = cnt.double()[:, None].expand_as(r)
@@ -161,7 +174,7 @@ def full_rank_metrics(model, starts_ends_tes, at_nums, exclude=None):
     out = dict(n=n, mrr=float(a[1] / n) if n else 0.0, mean_rank=float(a[2] / n) if n else 0.0, median_rank=med,
                auc_full=float(a[3] / n) if n else 0.0, at={})
     for i, k in enumerate(at_nums):
-        out["at"][k] = dict(hits=float(h[i]), recall=float(h[i] / n) if n else 0.0, ndcg=float(g[i]) / model.n_user)
+        out["at"][k] = dict(hits=float(h[i]), recall=float(h[i] / n) if n else 0.0, ndcg=float(g[i]) / n_user)
     return out
 
 

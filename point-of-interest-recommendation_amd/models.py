@@ -1545,6 +1545,156 @@ class MfBasic(_Base):
         """public/BPR.py:71-74 (no argument: copies ux)."""
         self.trained_users.t.copy_(self.ux.t)
 
+    # ---- fold-in (poi_foldin_bpr): user rows for check-in histories the model never trained on -----------------------------------------
+    # The recurrent models serve an unseen user through a Session slot; this family's only user representation is a trained row, so a
+    # new user gets one by running the model's own per-check-in rule on a fresh row against the frozen evaluation snapshot
+    # trained_items (width kdim: [lt | fi ei^T] for OboVBpr).  Nothing here changes a parameter or a snapshot.  Not covered: FPMC-LR
+    # (its transition term has no user parameter), PRME / GeoIE / POI2Vec (rules of their own), the recurrent models (Session).
+    def _foldin_csr(self, histories):
+        """histories -> (off (n + 1), p) int32 device tensors, n, total.  A tuple (off, p_flat) is a CSR, anything else a list of id
+        sequences.  Host data is checked here (IndexError / ValueError before any launch); of a device CSR only the offsets' range is
+        checked (one sync: they address memory), its ids and the order of its offsets are left to the kernel."""
+        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+        if isinstance(histories, tuple) and len(histories) == 2:
+            off, p = histories
+            if isinstance(off, torch.Tensor) and isinstance(p, torch.Tensor) and p.is_cuda:
+                off = off.to(self.device, torch.int32).contiguous().reshape(-1)
+                p = p.to(self.device, torch.int32).contiguous().reshape(-1)
+                if off.numel() < 1:
+                    raise ValueError("histories=(off, p_flat): off must hold n + 1 offsets")
+                lo, hi, first, last = (int(v) for v in torch.stack([off.min(), off.max(), off[0], off[-1]]).cpu())
+                if lo < 0 or hi > p.numel():
+                    raise IndexError("histories=(off, p_flat): offsets must lie in [0, %d] (found %d..%d)" % (p.numel(), lo, hi))
+                if first != 0 or last != p.numel():
+                    raise ValueError("histories=(off, p_flat): off must run from 0 to len(p_flat)")
+                return off, (p if p.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)), off.numel() - 1, p.numel()
+            off = np.asarray(off.cpu() if isinstance(off, torch.Tensor) else off).astype(np.int64).reshape(-1)
+            p = np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p).astype(np.int64).reshape(-1)
+            if off.size < 1 or off[0] != 0 or off[-1] != p.size or np.any(np.diff(off) < 0):
+                raise ValueError("histories=(off, p_flat): off must ascend from 0 to len(p_flat)")
+        else:
+            seqs = [np.asarray(h, np.int64).reshape(-1) for h in histories]
+            off = np.zeros(len(seqs) + 1, np.int64)
+            off[1:] = np.cumsum([len(s) for s in seqs])
+            p = np.concatenate(seqs) if seqs else np.zeros(0, np.int64)
+        if p.size >= (1 << 31):
+            raise ValueError("fold_in: at most 2^31 - 1 check-ins per call")
+        self._check_ids("fold_in histories", p, self.n_item)
+        return i32(off), i32(p if p.size else [0]), len(off) - 1, int(p.size)
+
+    def fold_in(self, histories, negatives=None, epochs=10, alpha=None, lam=None, init="zeros", seed=0, return_loss=False, sync=True):
+        """User rows for NEW check-in histories (include/poi_hip.h, poi_foldin_bpr): the item side stays frozen and the model's own
+        per-check-in SGD rule (public/BPR.py:216-230, :287-306) runs `epochs` times over each history on one fresh row, against the
+        evaluation snapshot trained_items.  Returns an (n, kdim) float32 device tensor - rows to rank with exactly like trained_users
+        rows ([ux | ue] layout for OboVBpr); with return_loss also the (n, epochs) summed -log sigmoid of every epoch.
+        histories: a list of POI id sequences, or a tuple (off, p_flat) CSR of host arrays or device tensors; ids in [0, n_item].
+        negatives: None = drawn on the device, once per epoch (poi_sample_negatives on the history CSR: uniform over [0, n_item), redrawn
+        while the draw is in the user's own history; epoch e is seeded seed + e - a history must not hold every POI), or an explicit flat
+        array of `total` ids (one draw reused by every epoch) or epochs x total ids (epoch-major).
+        alpha / lam: default to the model's alpha_lambda[0:2].  init: "zeros", "mean" (the mean row of trained_users) or an (n, kdim) array.
+        Host arrays are range-checked before any launch (IndexError).  Device tensors are checked by the kernel: an offending user's row
+        and losses are NaN, the other users are untouched, and - with sync - IndexError is raised (sync=False leaves the count to
+        ctx.take_bad_ids()).  A user's row does not depend on the other users of the call."""
+        off, p, n, total = self._foldin_csr(histories)
+        epochs = int(epochs)
+        if epochs < 0:
+            raise ValueError("epochs must be >= 0 (got %d)" % epochs)
+        alpha = self.alpha_lambda[0] if alpha is None else float(alpha)
+        lam = self.alpha_lambda[1] if lam is None else float(lam)
+        if isinstance(init, str):
+            if init not in ("zeros", "mean"):
+                raise ValueError("init must be 'zeros', 'mean' or an (n, kdim) array (got %r)" % (init,))
+            w0 = None if init == "zeros" else self.trained_users.t.mean(0, keepdim=True).expand(n, self.kdim).contiguous()
+        else:
+            w0 = self._dev(init).reshape(-1, self.kdim)
+            if w0.shape[0] != n:
+                raise ValueError("init must hold one row per history (%d vs %d)" % (w0.shape[0], n))
+        if negatives is None:
+            q = torch.empty(max(epochs * total, 1), dtype=torch.int32, device=self.device)
+            stride = total
+            for e in range(epochs if total else 0):
+                self.ctx.check(self.lib.poi_sample_negatives(self.ctx.handle, _ptr(off), _ptr(p), n, self.n_item, None, None, 0,
+                                                             (int(seed) + e) & 0xFFFFFFFFFFFFFFFF, ctypes.c_void_p(q.data_ptr() + 4 * e * total),
+                                                             None, self._stream()))
+        else:
+            if isinstance(negatives, torch.Tensor) and negatives.is_cuda:
+                q = negatives.to(self.device, torch.int32).contiguous().reshape(-1)
+            else:
+                qh = np.asarray(negatives.cpu() if isinstance(negatives, torch.Tensor) else negatives).astype(np.int64).reshape(-1)
+                self._check_ids("fold_in negatives", qh, self.n_item)
+                q = torch.as_tensor(qh.astype(np.int32)).to(self.device)
+            if q.numel() == total:
+                stride = 0
+            elif q.numel() == epochs * total:
+                stride = total
+            else:
+                raise ValueError("negatives must hold total = %d or epochs x total = %d ids (got %d)" % (total, epochs * total, q.numel()))
+            if not q.numel():
+                q = torch.zeros(1, dtype=torch.int32, device=self.device)
+        w = torch.empty((n, self.kdim), dtype=torch.float32, device=self.device)
+        loss = torch.empty((n, epochs), dtype=torch.float32, device=self.device) if return_loss else None
+        self.ctx.check(self.lib.poi_foldin_bpr(self.ctx.handle, _ptr(self.trained_items.t), self.n_item, self.kdim, _ptr(off), _ptr(p), _ptr(q), stride,
+                                               n, epochs, alpha, lam, _ptr(w0), _ptr(w), _ptr(loss), self._stream()))
+        if sync:
+            bad = self.ctx.take_bad_ids(self._stream().value)
+            if bad:
+                raise IndexError("%d history(ies) with an id outside [0, %d] or descending offsets: their rows and losses are NaN" % (bad, self.n_item))
+        return (w, loss) if return_loss else w
+
+    def _foldin_exclusion(self, exclude, off, p, n, total):
+        """exclude -> (ex_off, ex): "history" = every history's distinct POIs, ascending (the padding id n_item is no candidate and
+        is dropped); None or a CSR pair as compute_sub_topk_near."""
+        if not isinstance(exclude, str):
+            return self._near_exclusion(exclude, n, None)
+        if exclude != "history":
+            raise ValueError("exclude must be None, 'history' or a pair (off, ids) (got %r)" % (exclude,))
+        o = off.long()
+        row = torch.repeat_interleave(torch.arange(n, device=self.device), o[1:] - o[:-1])
+        ids = p[:total].long()
+        keys = torch.unique((row * (self.n_item + 1) + ids)[ids < self.n_item])             # sorted: by row, then by id
+        eo = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        eo[1:] = torch.cumsum(torch.bincount(keys // (self.n_item + 1), minlength=n), 0)
+        ex = (keys % (self.n_item + 1)).int()
+        return eo.int(), (ex if ex.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+
+    def _foldin_rows(self, histories, kw):
+        """(folded rows, off, p, n, total) for the ranking entries; the histories are checked with a sync whatever `sync` says - the
+        exclusion lists below are built from them."""
+        if kw.get("return_loss"):
+            raise ValueError("return_loss belongs to fold_in")
+        off, p, n, total = csr = self._foldin_csr(histories)
+        return (self.fold_in((off, p[:total]), **dict(kw, sync=True)),) + csr
+
+    def recommend_new(self, histories, k, exclude="history", within_km=None, anchor="last", return_scores=False, return_counts=False,
+                      sync=True, **fold_in_kwargs):
+        """Top-k for NEW users: fold_in(histories, **fold_in_kwargs), then the restricted ranking of compute_sub_topk_near
+        (poi_score_topk_near) on the folded rows.  exclude: "history" (each history's distinct POIs leave the candidates), None or a CSR
+        pair (off, ids); within_km: only POIs within that many km of the anchor (needs set_coords; None: no radius, no coordinates
+        needed); anchor: "last" (each history's last POI; an empty history has none: no radius for it), or one POI id per row (-1: none).
+        Returns (n, k) int32 ids, k <= 32, -1 where a row has fewer than k candidates[, scores][, candidate counts]."""
+        w, off, p, n, total = self._foldin_rows(histories, fold_in_kwargs)
+        if isinstance(anchor, str):
+            if anchor != "last":
+                raise ValueError("anchor must be 'last' or one POI id per row (got %r)" % (anchor,))
+            o = off.long()
+            anc = torch.where(o[1:] > o[:-1], p[(o[1:] - 1).clamp(min=0)], torch.full((n,), -1, dtype=torch.int32, device=self.device))
+            anc = torch.where(anc >= self.n_item, torch.full_like(anc, -1), anc).contiguous()      # (the padding id has no coordinates)
+        else:
+            if anchor is None and within_km is not None:
+                raise ValueError("within_km needs an anchor: 'last' or one POI id per row")
+            anc = self._near_anchor(anchor, n, lambda: None)
+        ex = self._foldin_exclusion(exclude, off, p, n, total)
+        return self._near_launch(w, self.trained_items.t, anc, self._near_radius(within_km), ex, None, k, return_scores, return_counts, sync)
+
+    def rank_new(self, histories, targets, exclude="history", return_scores=False, return_counts=False, sync=True, **fold_in_kwargs):
+        """Exact 0-based rank of `targets` ((n, len_t <= 8) POI ids, or a pair (ids, mask)) among all POIs for NEW users:
+        fold_in(histories, **fold_in_kwargs), then poi_score_rank on the folded rows, as compute_sub_target_rank.  exclude: "history",
+        None or a CSR pair (off, ids); an excluded target is not ranked (-1)."""
+        w, off, p, n, total = self._foldin_rows(histories, fold_in_kwargs)
+        tgt, tm = self._rank_targets(targets, n)
+        ex = self._foldin_exclusion(exclude, off, p, n, total)
+        return self._rank_launch(w, self.trained_items.t, None, tgt, tm, ex, return_scores, return_counts, sync)
+
 
 class OboBpr(MfBasic):
     """public/BPR.py:191-241."""
