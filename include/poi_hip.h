@@ -346,13 +346,20 @@ int poi_score_all(poi_ctx* ctx, const float* users, const float* items, int32_t 
 
 /* ---- a8+a9 fused: scoring + top-K - public/Valuate.py:91-100,132-146 -----------------------
  * Same score definition as poi_score_all; the (n, n_item) matrix is never materialised.
- * idx_out (n, k) int32 sorted by descending score, ties by ascending index; score_out (n, k) or NULL. */
+ * idx_out (n, k) int32 sorted by descending score, ties by ascending index; score_out (n, k) or NULL.
+ * An item whose score is -inf or NaN is never selected (every comparison is `score > threshold`, from -inf): a row with fewer than k
+ * selectable items ends in -1 ids and -inf scores, as poi_score_topk_near states it.  The same holds for poi_score_topk_ulptai and
+ * poi_score_topk_geo, one- and two-stage.  A K-th best of exactly +0.0 is a score like any other (ties at zero are kept); how a -0.0
+ * score ranks against +0.0 scores is NOT specified (the candidate lists order -0.0 below +0.0, the merge treats them as equal).
+ * tests: tests/test_gpu_topk_adversarial.py (planted ties, plateaus across item ranges, short rows, NaN). */
 int poi_score_topk(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item,
                    int32_t dim, const float* wd, const float* prob, int32_t k,
                    int32_t* idx_out, float* score_out, void* stream);
 
 /* ---- a9 alone: top-K of a given score matrix, k <= 64 (checks the selection independently of the GEMM; also the path for
- * cut-offs beyond the fused kernels' k <= 32, e.g. at_nums = [5, 10, 15, 20, 30, 50] of public/Valuate.py:126) */
+ * cut-offs beyond the fused kernels' k <= 32, e.g. at_nums = [5, 10, 15, 20, 30, 50] of public/Valuate.py:126).
+ * Order and short rows as poi_score_topk: descending score, ties by ascending index; -inf and NaN entries are never selected, and a
+ * row with fewer than k selectable entries ends in -1 ids and -inf scores. */
 int poi_topk(poi_ctx* ctx, const float* scores, int32_t n, int32_t n_item, int32_t k,
              int32_t* idx_out, float* score_out, void* stream);
 

@@ -237,6 +237,15 @@ __device__ __forceinline__ bool better(float s, int i, float ps, int pi) {
   return (s > ps) || (s == ps && i < pi);
 }
 
+// Order-mapped bound (score_topk.hip f2ord: larger float <=> larger uint) one step BELOW the order-mapped score o, for consumers that keep
+// `score > bound`: a score equal to the K-th best still passes.  One step below +0.0 is -0.0, which COMPARES EQUAL to +0.0 - a bound
+// published from a K-th best of zero dropped every tie at zero in the other item ranges - so a step that lands on a zero or a subnormal
+// (which a flushing compare would treat as zero) goes on to -FLT_MIN: any lower value is still a bound.  Callers check o > 1.
+__device__ __forceinline__ unsigned tie_bound_below(unsigned o) {
+  const unsigned b = o - 1u;                               // ord(-FLT_MIN) = 0x7F7FFFFF, ord(-0.0) = 0x7FFFFFFF, ord(+0.0) = 0x80000000, ord(FLT_MIN) = 0x80800000
+  return (b > 0x7F7FFFFFu && b < 0x80800000u) ? 0x7F7FFFFFu : b;
+}
+
 // 64-lane bitonic sort, best (highest score, then lowest index) first.
 __device__ __forceinline__ void wave_sort_desc(float& s, int& idx) {
   const int lane = lane_id();

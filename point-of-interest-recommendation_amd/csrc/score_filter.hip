@@ -365,7 +365,7 @@ __global__ __launch_bounds__(256) void sf_select_kernel(ScoreArgs A, int k) {
   const float thr = kth - slack;
   if (lane == 0 && thr > -INFINITY) {
     const unsigned o = sf_f2ord(thr);
-    if (o > 1u && o - 1u > A.gbound[u]) A.gbound[u] = o - 1u;
+    if (o > 1u && tie_bound_below(o) > A.gbound[u]) A.gbound[u] = tie_bound_below(o);
   }
 }
 
@@ -687,6 +687,9 @@ __global__ __launch_bounds__(256) void score_rescore_kernel(ScoreArgs A) {
       if (lane >= K) {
         if (c < n) { sc = A.surv_sc[base0 + c]; idx = A.surv_idx[base0 + c]; }
         else { sc = -INFINITY; idx = INT_MAX; }
+        // a NaN survives the filter on purpose; here it must not enter the sort - it compares false both ways, so the network would
+        // duplicate one neighbour and lose another - and, like -inf, is never selected (the one-stage kernels' `score > threshold`)
+        if (!(sc > -INFINITY)) { sc = -INFINITY; idx = INT_MAX; }
       }
       sf_wave_sort_desc(sc, idx);
     }
@@ -841,7 +844,7 @@ __global__ __launch_bounds__(256) void topk_bound_kernel(const float* __restrict
   const float s = score_k[(size_t)u * k + (k - 1)];
   if (!(s > -INFINITY)) return;                 // fewer than K items in the subset (or NaN): no bound
   const unsigned o = sf_f2ord(s);
-  if (o > 1u && o - 1u > gbound[u]) gbound[u] = o - 1u;
+  if (o > 1u && tie_bound_below(o) > gbound[u]) gbound[u] = tie_bound_below(o);      // (never -0.0: a flagged tile's one-stage kernel compares `score > bound`)
 }
 hipError_t launch_topk_bound(const float* score_k, int n, int k, unsigned* gbound, hipStream_t st) {
   hipLaunchKernelGGL(topk_bound_kernel, dim3((n + 255) / 256), dim3(256), 0, st, score_k, n, k, gbound);

@@ -94,11 +94,12 @@ __device__ __forceinline__ void compact_user(WaveTopk& T, int i, int K, unsigned
     T.cnt[i] = K;
     T.thr[i] = kth;
     // Any subset's K-th best score bounds the global K-th best from below: publish (kth - 1 ulp, so
-    // that `score > bound` keeps ties) for the waves that scan other item ranges of the same user,
+    // that `score > bound` keeps ties - tie_bound_below, poi_common.h: never -0.0) for the waves that scan other item ranges of the same user,
     // but only when it improves on the bound last seen (keeps atomic traffic on hot words low).
     if (gbound && dbg != 4) {
       const unsigned o = f2ord(kth);
-      if (o > 1u && o - 1u > T.gseen[i]) { atomicMax(gbound, o - 1u); T.gseen[i] = o - 1u; }
+      const unsigned b = tie_bound_below(o);
+      if (o > 1u && b > T.gseen[i]) { atomicMax(gbound, b); T.gseen[i] = b; }
     }
   }
   wave_fence();
@@ -207,7 +208,7 @@ __global__ __launch_bounds__(POI_BLOCK) void topk_seed_kernel(ScoreArgs A, const
   if (at && lane == 0) {
     const float tau = readlane_f(lb, __builtin_ctzll(at));
     const unsigned o = f2ord(tau);
-    if (o > 1u) A.gbound[u] = o - 1u;           // (as compact_user publishes: `score > bound` keeps ties)
+    if (o > 1u) A.gbound[u] = tie_bound_below(o);      // (as compact_user publishes: `score > bound` keeps ties)
   }
 }
 
