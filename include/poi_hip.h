@@ -67,6 +67,8 @@ extern "C" {
  * timing names "score_rank" / "rank_scores" (existing entries unchanged). */
 /* additive to 9: fold-in for the factorisation family - new entry point poi_foldin_bpr, timing name "foldin"; no new option or plan key
  * (existing entries unchanged). */
+/* additive to 9: fold-in for the successive-POI models - new entry points poi_foldin_terms_fpmc, poi_foldin_terms_prme and poi_foldin_pair,
+ * timing names "foldin_terms" and "foldin_pair"; no new option or plan key (existing entries, poi_foldin_bpr included, unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -799,6 +801,55 @@ int poi_foldin_bpr(poi_ctx* ctx, const float* items, int32_t n_item, int32_t dim
                    const int32_t* off, const int32_t* p, const int32_t* q, int64_t q_epoch_stride,
                    int32_t n, int32_t epochs, float alpha, float lambda,
                    const float* w0, float* w_out, float* loss_out, void* stream);
+
+/* ---- fold-in for the successive-POI models (additive to 9): a row of OboFpmc_lr's ui or of OboPrme's du for an unseen history --------------
+ * FPMC-LR and PRME represent a user by one trained row.  With the item side frozen, each model's per-transition rule on that row is
+ * poi_foldin_bpr's chain with two per-step scalars that do not depend on the row, a weight a and an offset c.  A history
+ * p[off[r] .. off[r + 1]) of length L has the transitions t = 1 .. L - 1 with prev = p[t - 1], target p[t] and negative
+ * q_{e,t} = q[e * q_epoch_stride + off[r] + t]; position 0 is no step.
+ *   FPMC-LR (public/FPMC_LR.py:113-140, the ui part of the update, one negative per transition as the driver draws):
+ *     c = ai[prev] . (ia[p_t] - ia[q]),   x = w . (iu[p_t] - iu[q]) + c,   w -= alpha (-sigmoid(-x) (iu[p_t] - iu[q]) + lambda w)
+ *   PRME (public/PRME.py:173-214, the du part):
+ *     far = gap_t > thd,  wgt = (1 + d_t)^0.25,  a = far ? 1 : wgt cw,  b = far ? 0 : wgt (1 - cw)
+ *     c = b (|ds[q] - ds[prev]|^2 - |ds[p_t] - ds[prev]|^2),   x = a (|w - dp[q]|^2 - |w - dp[p_t]|^2) + c
+ *     w += alpha (sigmoid(-x) 2 a (dp[p_t] - dp[q]) - lambda w)
+ *   loss[r][e] += -log sigmoid(x) in both.  The reference's PRME step returns +log sigmoid(x) (as poi_prme_step does); fold-in keeps
+ *   poi_foldin_bpr's sign for both models.  The reference's last-wins collapse of repeated rows concerns dp / ds only and does not
+ *   touch the du row: p_t == q and p_t == prev are legal here, nothing but w moves.
+ * Arithmetic: the running row, x, the sigmoid and the loss are float64 and are rounded to float32 once, at the end; alpha and lambda
+ * enter at their float values, cw too.  Gathered rows are float32.  Every sum has one fixed order (per lane its columns ascending, then
+ * a fixed tree over 16 lanes); no atomics touch a result; no output depends on the grid.
+ *
+ * The terms pass writes the scalars, float64, at the CSR position: c_out[e * q_epoch_stride + pos] (one epoch's worth when
+ * q_epoch_stride = 0), a_out[pos] once per position; the first position of a history is written as 0.  total = the number of check-ins
+ * (the length of p; off[n] for a well-formed CSR).  d_t is dist[pos] (float64 km) or, with dist NULL, cal_dis(cordi[p_t], cordi[prev]) in
+ * float64 in cal_dis's operation order (cordi (n_item + 1, 2) lat, lon with the pad row, as poi_prme_score_all).  gap[pos]: minutes.
+ * A negative id of -1 means "no negative exists" (poi_fpmc_sample_negatives emits it for a target without neighbours): the step is
+ * skipped - no update, no decay, no loss - and its c is 0.  An entry with any other id outside [0, n_item], or with a distance that is
+ * negative or not finite, becomes NaN; bad ids are not counted here - the chain counts its user.  With descending offsets the entries at
+ * positions that two histories claim are unspecified.  Timing name: "foldin_terms". */
+int poi_foldin_terms_fpmc(poi_ctx* ctx, const poi_fpmc_params* prm, const int32_t* off, const int32_t* p, const int32_t* q,
+                          int64_t q_epoch_stride, int32_t n, int64_t total, int32_t epochs, double* c_out, void* stream);
+int poi_foldin_terms_prme(poi_ctx* ctx, const poi_prme_params* prm, const double* cordi, const int32_t* off, const int32_t* p, const int32_t* q,
+                          int64_t q_epoch_stride, const int32_t* gap, const double* dist, int32_t n, int64_t total, int32_t epochs,
+                          int32_t threshold, float cw, double* a_out, double* c_out, void* stream);
+/* The chain.  items (n_item + 1, dim) float32: iu for FPMC-LR, dp for PRME.  form: POI_FOLDIN_DOT x = w . d + c, gradient direction d;
+ * POI_FOLDIN_METRIC x = a (|w - y_q|^2 - |w - y_p|^2) + c, evaluated as a sum of d (2 w - y_p - y_q), gradient direction 2 a d;
+ * d = y_p - y_q.  first (0 or 1): the first position of a history that is a step.  a (per position) NULL means 1 and is not read in
+ * the dot form, c NULL means 0; c of epoch e lies at c + e * c_epoch_stride.  With a = c = NULL, first = 0 and valid ids the dot form
+ * performs poi_foldin_bpr's operations in its order: the same bits.
+ * For new user r: w = w0[r] (zeros when w0 is NULL), then epochs x (L - first) steps in history order.  L <= first or epochs = 0
+ * returns w0[r] and losses 0.  A step whose negative is -1 is skipped.  A user with off[r + 1] < off[r], off[r] < 0, any other id
+ * outside [0, n_item] among the ids it reads (with first = 1 its first check-in included) or a term that is not finite is a bad user:
+ * a NaN row, NaN losses, counted once (poi_ctx_take_bad_ids), and nothing else moves.  A user's output bits depend on its own history,
+ * negatives, terms and w0 alone.  w_out (n, dim) may alias w0; loss_out (n, epochs) or NULL.  dim: a multiple of 4, up to 256.  n = 0 is
+ * a no-op.  One kernel: a 16-lane row of a wave per user, the rows, ids and terms of the next steps in flight while a step computes
+ * (foldin_seq.hip).  Timing name: "foldin_pair". */
+enum { POI_FOLDIN_DOT = 0, POI_FOLDIN_METRIC = 1 };
+int poi_foldin_pair(poi_ctx* ctx, const float* items, int32_t n_item, int32_t dim, int32_t form, int32_t first,
+                    const int32_t* off, const int32_t* p, const int32_t* q, int64_t q_epoch_stride,
+                    const double* a, const double* c, int64_t c_epoch_stride, int32_t n, int32_t epochs, float alpha, float lambda,
+                    const float* w0, float* w_out, float* loss_out, void* stream);
 
 /* ---- multi-GPU reconciliation (8e; new - the reference is single-process) ----------------------
  * Users are sharded across ranks, every rank trains on a full parameter replica with no data-path collective,

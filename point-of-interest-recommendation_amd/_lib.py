@@ -48,6 +48,7 @@ class VbprParams(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("ux", "lt", "ue", "ei", "fi")] + [(n, c_int32) for n in ("n_user", "n_item", "dim", "n_img")]
 
 
+FOLDIN_DOT, FOLDIN_METRIC = 0, 1    # POI_FOLDIN_*: the form of poi_foldin_pair
 CELL_RNN, CELL_LSTM = 1, 4          # POI_CELL_*: the number of gate blocks
 
 
@@ -157,6 +158,11 @@ SIGNATURES = {
     "poi_rank_scores": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_foldin_bpr": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float, c_float,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_foldin_terms_fpmc": (c_int, [c_void_p, POINTER(FpmcParams), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p]),
+    "poi_foldin_terms_prme": (c_int, [c_void_p, POINTER(PrmeParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64,
+                                      c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
+    "poi_foldin_pair": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                c_int32, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_delta_make": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_delta_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "poi_comm_available": (c_int, []),

@@ -1819,6 +1819,82 @@ int poi_foldin_bpr(poi_ctx* c, const float* items, int32_t n_item, int32_t dim, 
   return POI_OK;
 }
 
+// fold-in for the successive-POI models (foldin_seq.hip): the per-step scalars, then the generalised chain
+static int foldin_terms_common(poi_ctx* c, const char* who, const int32_t* off, const int32_t* p, const int32_t* q, int64_t q_epoch_stride, int32_t n,
+                               int64_t total, int32_t epochs, const double* c_out, poi::FoldinTermsArgs& A) {
+  if (n < 0 || total < 0 || epochs < 0 || q_epoch_stride < 0) return fail(c, POI_EINVAL, "%s: n < 0, total < 0, epochs < 0 or q_epoch_stride < 0", who);
+  if (total >= ((int64_t)1 << 31)) return fail(c, POI_ENOTSUP, "%s: at most 2^31 - 1 check-ins per call", who);
+  if (q_epoch_stride != 0 && q_epoch_stride < total) return fail(c, POI_EINVAL, "%s: q_epoch_stride must be 0 or at least total", who);
+  if (n == 0 || total == 0 || epochs == 0) return POI_OK;
+  if (!off || !p || !q || !c_out) return fail(c, POI_EINVAL, "%s: NULL off / p / q / c_out", who);
+  A.off = off; A.p = p; A.q = q; A.q_epoch_stride = q_epoch_stride; A.n = n; A.total = total;
+  A.n_epoch = q_epoch_stride ? epochs : 1;
+  return POI_OK;
+}
+
+int poi_foldin_terms_fpmc(poi_ctx* c, const poi_fpmc_params* P, const int32_t* off, const int32_t* p, const int32_t* q, int64_t q_epoch_stride,
+                          int32_t n, int64_t total, int32_t epochs, double* c_out, void* stream) {
+  if (!c || !P || !P->ia || !P->ai) return fail(c, POI_EINVAL, "poi_foldin_terms_fpmc: NULL ctx / params / ia / ai");
+  if (is_f16(c, P->ia) || is_f16(c, P->ai)) return fail(c, POI_ENOTSUP, "FPMC-LR tables are float32 only");
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 256) return fail(c, POI_ENOTSUP, "poi_foldin_terms_fpmc: dim must be a multiple of 4 in [4, 256] (got %d)", P->dim);
+  if (P->n_item <= 0) return fail(c, POI_EINVAL, "poi_foldin_terms_fpmc: n_item <= 0");
+  poi::FoldinTermsArgs A = {};
+  int rc = foldin_terms_common(c, "poi_foldin_terms_fpmc", off, p, q, q_epoch_stride, n, total, epochs, c_out, A);
+  if (rc || !A.off) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  A.tab_pq = P->ia; A.tab_prev = P->ai; A.n_item = P->n_item; A.dim = P->dim; A.c_out = c_out;
+  HIPCHK(c, poi::launch_foldin_terms(A, false, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_foldin_terms_prme(poi_ctx* c, const poi_prme_params* P, const double* cordi, const int32_t* off, const int32_t* p, const int32_t* q,
+                          int64_t q_epoch_stride, const int32_t* gap, const double* dist, int32_t n, int64_t total, int32_t epochs, int32_t threshold,
+                          float cw, double* a_out, double* c_out, void* stream) {
+  if (!c || !P || !P->ds) return fail(c, POI_EINVAL, "poi_foldin_terms_prme: NULL ctx / params / ds");
+  if (is_f16(c, P->ds)) return fail(c, POI_ENOTSUP, "PRME tables are float32 only");
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 256) return fail(c, POI_ENOTSUP, "poi_foldin_terms_prme: dim must be a multiple of 4 in [4, 256] (got %d)", P->dim);
+  if (P->n_item <= 0) return fail(c, POI_EINVAL, "poi_foldin_terms_prme: n_item <= 0");
+  poi::FoldinTermsArgs A = {};
+  int rc = foldin_terms_common(c, "poi_foldin_terms_prme", off, p, q, q_epoch_stride, n, total, epochs, c_out, A);
+  if (rc || !A.off) return rc;
+  if (!gap || !a_out || (!dist && !cordi)) return fail(c, POI_EINVAL, "poi_foldin_terms_prme: NULL gap / a_out, or neither dist nor cordi");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  A.tab_pq = P->ds; A.tab_prev = P->ds; A.n_item = P->n_item; A.dim = P->dim; A.c_out = c_out; A.a_out = a_out;
+  A.gap = gap; A.dist = dist; A.cordi = cordi; A.thd = threshold; A.cw = cw;
+  HIPCHK(c, poi::launch_foldin_terms(A, true, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_foldin_pair(poi_ctx* c, const float* items, int32_t n_item, int32_t dim, int32_t form, int32_t first, const int32_t* off, const int32_t* p,
+                    const int32_t* q, int64_t q_epoch_stride, const double* a, const double* cterm, int64_t c_epoch_stride, int32_t n, int32_t epochs,
+                    float alpha, float lambda, const float* w0, float* w_out, float* loss_out, void* stream) {
+  if (!c || !items || !w_out) return fail(c, POI_EINVAL, "poi_foldin_pair: NULL ctx / items / w_out");
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_foldin_pair: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  if (form != FOLDIN_FORM_DOT && form != FOLDIN_FORM_METRIC) return fail(c, POI_EINVAL, "poi_foldin_pair: form must be POI_FOLDIN_DOT or POI_FOLDIN_METRIC (got %d)", form);
+  if (first != 0 && first != 1) return fail(c, POI_EINVAL, "poi_foldin_pair: first must be 0 or 1 (got %d)", first);
+  if (n < 0 || n_item <= 0 || epochs < 0 || q_epoch_stride < 0 || c_epoch_stride < 0)
+    return fail(c, POI_EINVAL, "poi_foldin_pair: n < 0, n_item <= 0, epochs < 0 or a negative epoch stride");
+  if (n == 0) return POI_OK;
+  if (!off || !p || !q) return fail(c, POI_EINVAL, "poi_foldin_pair: NULL off / p / q");
+  if (is_f16(c, items) || (w0 && is_f16(c, w0)) || is_f16(c, w_out)) return fail(c, POI_ENOTSUP, "poi_foldin_pair: items / w0 / w_out must be float32");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::FoldinPairArgs A = {};
+  A.items = items; A.n = n; A.n_item = n_item; A.dim = dim; A.epochs = epochs; A.form = form; A.first = first;
+  A.off = off; A.p = p; A.q = q; A.q_epoch_stride = q_epoch_stride;
+  A.a = form == FOLDIN_FORM_METRIC ? a : nullptr; A.c = cterm; A.c_epoch_stride = c_epoch_stride;
+  A.alpha = alpha; A.lambda = lambda;
+  A.w0 = w0; A.w_out = w_out; A.loss_out = loss_out;
+  int rc;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  A.dummy = (const double*)c->bad_ids.p + 4;      // (bytes 32 .. 39 of the counter's buffer: never written)
+  HIPCHK(c, poi::launch_foldin_pair(A, st, &c->tm));
+  return POI_OK;
+}
+
 int poi_topk(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, int32_t k, int32_t* idx_out, float* score_out,
              void* stream) {
   if (!c || !scores || !idx_out) return fail(c, POI_EINVAL, "poi_topk: NULL argument");

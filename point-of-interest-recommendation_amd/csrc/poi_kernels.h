@@ -589,6 +589,30 @@ struct FoldinArgs {
 };
 hipError_t launch_foldin(const FoldinArgs& A, hipStream_t st, Timing* tm);
 
+// Fold-in of new users for the successive-POI models (foldin_seq.hip): the per-step scalars a / c, then the generalised chain
+#define FOLDIN_FORM_DOT 0                   // x = w . d + c                                   (FPMC-LR's ui against iu)
+#define FOLDIN_FORM_METRIC 1                // x = a (|w - y_q|^2 - |w - y_p|^2) + c           (PRME's du against dp)
+struct FoldinTermsArgs {
+  const float *tab_pq, *tab_prev;                             // FPMC-LR: ia, ai;  PRME: ds, ds   (n_item + 1, dim) float32
+  int n, n_item, dim, n_epoch;                                // n_epoch: epochs with their own negatives (1 when q_epoch_stride = 0)
+  long long total;                                            // check-ins of the call (length of p)
+  const int *off, *p, *q; long long q_epoch_stride;
+  const int* gap; const double *dist, *cordi; int thd; float cw;      // PRME only; dist or cordi
+  double *a_out, *c_out;                                      // a_out (total), PRME only; c_out at the stride of q
+};
+hipError_t launch_foldin_terms(const FoldinTermsArgs& A, bool prme, int num_cu, hipStream_t st, Timing* tm);
+struct FoldinPairArgs {
+  const float* items;                                         // (n_item + 1, dim) float32
+  int n, n_item, dim, epochs, form, first;
+  const int *off, *p, *q; long long q_epoch_stride;
+  const double *a, *c; long long c_epoch_stride;              // per-position weight (metric form) and offset, or null (1 and 0)
+  const double* dummy;                                        // 8 readable bytes: where the loads of absent a / c and of steps past the end go
+  float alpha, lambda;
+  const float* w0; float* w_out; float* loss_out;
+  int* bad;
+};
+hipError_t launch_foldin_pair(const FoldinPairArgs& A, hipStream_t st, Timing* tm);
+
 // scoring / top-K
 struct ScoreArgs {
   const float *users, *items; int items_f16;      // items: float32, or IEEE half when items_f16

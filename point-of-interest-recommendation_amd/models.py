@@ -141,6 +141,85 @@ class _Base:
         if a.size and (a.min() < 0 or a.max() > hi):
             raise IndexError("%s: ids must lie in [0, %d] (found %d..%d)" % (name, hi, int(a.min()), int(a.max())))
 
+    # ---- fold-in glue shared by MfBasic and the successive-POI models -------------------------------------------------------------
+    def _foldin_csr(self, histories):
+        """histories -> (off (n + 1), p) int32 device tensors, n, total.  A tuple (off, p_flat) is a CSR, anything else a list of id
+        sequences.  Host data is checked here (IndexError / ValueError before any launch); of a device CSR only the offsets' range is
+        checked (one sync: they address memory), its ids and the order of its offsets are left to the kernel."""
+        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+        if isinstance(histories, tuple) and len(histories) == 2:
+            off, p = histories
+            if isinstance(off, torch.Tensor) and isinstance(p, torch.Tensor) and p.is_cuda:
+                off = off.to(self.device, torch.int32).contiguous().reshape(-1)
+                p = p.to(self.device, torch.int32).contiguous().reshape(-1)
+                if off.numel() < 1:
+                    raise ValueError("histories=(off, p_flat): off must hold n + 1 offsets")
+                lo, hi, first, last = (int(v) for v in torch.stack([off.min(), off.max(), off[0], off[-1]]).cpu())
+                if lo < 0 or hi > p.numel():
+                    raise IndexError("histories=(off, p_flat): offsets must lie in [0, %d] (found %d..%d)" % (p.numel(), lo, hi))
+                if first != 0 or last != p.numel():
+                    raise ValueError("histories=(off, p_flat): off must run from 0 to len(p_flat)")
+                return off, (p if p.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)), off.numel() - 1, p.numel()
+            off = np.asarray(off.cpu() if isinstance(off, torch.Tensor) else off).astype(np.int64).reshape(-1)
+            p = np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p).astype(np.int64).reshape(-1)
+            if off.size < 1 or off[0] != 0 or off[-1] != p.size or np.any(np.diff(off) < 0):
+                raise ValueError("histories=(off, p_flat): off must ascend from 0 to len(p_flat)")
+        else:
+            seqs = [np.asarray(h, np.int64).reshape(-1) for h in histories]
+            off = np.zeros(len(seqs) + 1, np.int64)
+            off[1:] = np.cumsum([len(s) for s in seqs])
+            p = np.concatenate(seqs) if seqs else np.zeros(0, np.int64)
+        if p.size >= (1 << 31):
+            raise ValueError("fold_in: at most 2^31 - 1 check-ins per call")
+        self._check_ids("fold_in histories", p, self.n_item)
+        return i32(off), i32(p if p.size else [0]), len(off) - 1, int(p.size)
+
+    def _foldin_exclusion(self, exclude, off, p, n, total):
+        """exclude -> (ex_off, ex): "history" = every history's distinct POIs, ascending (the padding id n_item is no candidate and
+        is dropped); None or a CSR pair as compute_sub_topk_near."""
+        if not isinstance(exclude, str):
+            return self._near_exclusion(exclude, n, None)
+        if exclude != "history":
+            raise ValueError("exclude must be None, 'history' or a pair (off, ids) (got %r)" % (exclude,))
+        o = off.long()
+        row = torch.repeat_interleave(torch.arange(n, device=self.device), o[1:] - o[:-1])
+        ids = p[:total].long()
+        keys = torch.unique((row * (self.n_item + 1) + ids)[ids < self.n_item])             # sorted: by row, then by id
+        eo = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        eo[1:] = torch.cumsum(torch.bincount(keys // (self.n_item + 1), minlength=n), 0)
+        ex = (keys % (self.n_item + 1)).int()
+        return eo.int(), (ex if ex.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+
+    def _foldin_init(self, init, n, dim, mean_of):
+        """init -> the (n, dim) start rows on the device, or None for zeros: "zeros", "mean" (the mean row of `mean_of`) or an array."""
+        if isinstance(init, str):
+            if init not in ("zeros", "mean"):
+                raise ValueError("init must be 'zeros', 'mean' or an (n, kdim) array (got %r)" % (init,))
+            return None if init == "zeros" else mean_of.mean(0, keepdim=True).expand(n, dim).contiguous()
+        w0 = self._dev(init).reshape(-1, dim)
+        if w0.shape[0] != n:
+            raise ValueError("init must hold one row per history (%d vs %d)" % (w0.shape[0], n))
+        return w0
+
+    def _foldin_given_negatives(self, negatives, total, epochs, lo=0):
+        """Explicit negatives -> (q int32 device, q_epoch_stride): `total` ids (one draw for every epoch) or epochs x total, epoch-major.
+        Host arrays are range-checked ([lo, n_item]) before any launch; device tensors are left to the kernel."""
+        if isinstance(negatives, torch.Tensor) and negatives.is_cuda:
+            q = negatives.to(self.device, torch.int32).contiguous().reshape(-1)
+        else:
+            qh = np.asarray(negatives.cpu() if isinstance(negatives, torch.Tensor) else negatives).astype(np.int64).reshape(-1)
+            self._check_ids("fold_in negatives", qh if lo == 0 else qh[qh != -1], self.n_item)
+            q = torch.as_tensor(qh.astype(np.int32)).to(self.device)
+        if q.numel() == total:
+            stride = 0
+        elif q.numel() == epochs * total:
+            stride = total
+        else:
+            raise ValueError("negatives must hold total = %d or epochs x total = %d ids (got %d)" % (total, epochs * total, q.numel()))
+        if not q.numel():
+            q = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return q, stride
+
     def _load_tables(self, train, test):
         self._csr = train if isinstance(train, CsrTables) else None
         if self._csr is not None:
@@ -1548,40 +1627,9 @@ class MfBasic(_Base):
     # ---- fold-in (poi_foldin_bpr): user rows for check-in histories the model never trained on -----------------------------------------
     # The recurrent models serve an unseen user through a Session slot; this family's only user representation is a trained row, so a
     # new user gets one by running the model's own per-check-in rule on a fresh row against the frozen evaluation snapshot
-    # trained_items (width kdim: [lt | fi ei^T] for OboVBpr).  Nothing here changes a parameter or a snapshot.  Not covered: FPMC-LR
-    # (its transition term has no user parameter), PRME / GeoIE / POI2Vec (rules of their own), the recurrent models (Session).
-    def _foldin_csr(self, histories):
-        """histories -> (off (n + 1), p) int32 device tensors, n, total.  A tuple (off, p_flat) is a CSR, anything else a list of id
-        sequences.  Host data is checked here (IndexError / ValueError before any launch); of a device CSR only the offsets' range is
-        checked (one sync: they address memory), its ids and the order of its offsets are left to the kernel."""
-        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
-        if isinstance(histories, tuple) and len(histories) == 2:
-            off, p = histories
-            if isinstance(off, torch.Tensor) and isinstance(p, torch.Tensor) and p.is_cuda:
-                off = off.to(self.device, torch.int32).contiguous().reshape(-1)
-                p = p.to(self.device, torch.int32).contiguous().reshape(-1)
-                if off.numel() < 1:
-                    raise ValueError("histories=(off, p_flat): off must hold n + 1 offsets")
-                lo, hi, first, last = (int(v) for v in torch.stack([off.min(), off.max(), off[0], off[-1]]).cpu())
-                if lo < 0 or hi > p.numel():
-                    raise IndexError("histories=(off, p_flat): offsets must lie in [0, %d] (found %d..%d)" % (p.numel(), lo, hi))
-                if first != 0 or last != p.numel():
-                    raise ValueError("histories=(off, p_flat): off must run from 0 to len(p_flat)")
-                return off, (p if p.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)), off.numel() - 1, p.numel()
-            off = np.asarray(off.cpu() if isinstance(off, torch.Tensor) else off).astype(np.int64).reshape(-1)
-            p = np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p).astype(np.int64).reshape(-1)
-            if off.size < 1 or off[0] != 0 or off[-1] != p.size or np.any(np.diff(off) < 0):
-                raise ValueError("histories=(off, p_flat): off must ascend from 0 to len(p_flat)")
-        else:
-            seqs = [np.asarray(h, np.int64).reshape(-1) for h in histories]
-            off = np.zeros(len(seqs) + 1, np.int64)
-            off[1:] = np.cumsum([len(s) for s in seqs])
-            p = np.concatenate(seqs) if seqs else np.zeros(0, np.int64)
-        if p.size >= (1 << 31):
-            raise ValueError("fold_in: at most 2^31 - 1 check-ins per call")
-        self._check_ids("fold_in histories", p, self.n_item)
-        return i32(off), i32(p if p.size else [0]), len(off) - 1, int(p.size)
-
+    # trained_items (width kdim: [lt | fi ei^T] for OboVBpr).  Nothing here changes a parameter or a snapshot.  FPMC-LR and PRME
+    # fold in through _SeqFoldin (per-step scalars + the generalised chain).  Not covered: GeoIE / POI2Vec (rules of their own), the
+    # recurrent models (Session).
     def fold_in(self, histories, negatives=None, epochs=10, alpha=None, lam=None, init="zeros", seed=0, return_loss=False, sync=True):
         """User rows for NEW check-in histories (include/poi_hip.h, poi_foldin_bpr): the item side stays frozen and the model's own
         per-check-in SGD rule (public/BPR.py:216-230, :287-306) runs `epochs` times over each history on one fresh row, against the
@@ -1601,14 +1649,7 @@ class MfBasic(_Base):
             raise ValueError("epochs must be >= 0 (got %d)" % epochs)
         alpha = self.alpha_lambda[0] if alpha is None else float(alpha)
         lam = self.alpha_lambda[1] if lam is None else float(lam)
-        if isinstance(init, str):
-            if init not in ("zeros", "mean"):
-                raise ValueError("init must be 'zeros', 'mean' or an (n, kdim) array (got %r)" % (init,))
-            w0 = None if init == "zeros" else self.trained_users.t.mean(0, keepdim=True).expand(n, self.kdim).contiguous()
-        else:
-            w0 = self._dev(init).reshape(-1, self.kdim)
-            if w0.shape[0] != n:
-                raise ValueError("init must hold one row per history (%d vs %d)" % (w0.shape[0], n))
+        w0 = self._foldin_init(init, n, self.kdim, self.trained_users.t)
         if negatives is None:
             q = torch.empty(max(epochs * total, 1), dtype=torch.int32, device=self.device)
             stride = total
@@ -1617,20 +1658,7 @@ class MfBasic(_Base):
                                                              (int(seed) + e) & 0xFFFFFFFFFFFFFFFF, ctypes.c_void_p(q.data_ptr() + 4 * e * total),
                                                              None, self._stream()))
         else:
-            if isinstance(negatives, torch.Tensor) and negatives.is_cuda:
-                q = negatives.to(self.device, torch.int32).contiguous().reshape(-1)
-            else:
-                qh = np.asarray(negatives.cpu() if isinstance(negatives, torch.Tensor) else negatives).astype(np.int64).reshape(-1)
-                self._check_ids("fold_in negatives", qh, self.n_item)
-                q = torch.as_tensor(qh.astype(np.int32)).to(self.device)
-            if q.numel() == total:
-                stride = 0
-            elif q.numel() == epochs * total:
-                stride = total
-            else:
-                raise ValueError("negatives must hold total = %d or epochs x total = %d ids (got %d)" % (total, epochs * total, q.numel()))
-            if not q.numel():
-                q = torch.zeros(1, dtype=torch.int32, device=self.device)
+            q, stride = self._foldin_given_negatives(negatives, total, epochs)
         w = torch.empty((n, self.kdim), dtype=torch.float32, device=self.device)
         loss = torch.empty((n, epochs), dtype=torch.float32, device=self.device) if return_loss else None
         self.ctx.check(self.lib.poi_foldin_bpr(self.ctx.handle, _ptr(self.trained_items.t), self.n_item, self.kdim, _ptr(off), _ptr(p), _ptr(q), stride,
@@ -1640,22 +1668,6 @@ class MfBasic(_Base):
             if bad:
                 raise IndexError("%d history(ies) with an id outside [0, %d] or descending offsets: their rows and losses are NaN" % (bad, self.n_item))
         return (w, loss) if return_loss else w
-
-    def _foldin_exclusion(self, exclude, off, p, n, total):
-        """exclude -> (ex_off, ex): "history" = every history's distinct POIs, ascending (the padding id n_item is no candidate and
-        is dropped); None or a CSR pair as compute_sub_topk_near."""
-        if not isinstance(exclude, str):
-            return self._near_exclusion(exclude, n, None)
-        if exclude != "history":
-            raise ValueError("exclude must be None, 'history' or a pair (off, ids) (got %r)" % (exclude,))
-        o = off.long()
-        row = torch.repeat_interleave(torch.arange(n, device=self.device), o[1:] - o[:-1])
-        ids = p[:total].long()
-        keys = torch.unique((row * (self.n_item + 1) + ids)[ids < self.n_item])             # sorted: by row, then by id
-        eo = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
-        eo[1:] = torch.cumsum(torch.bincount(keys // (self.n_item + 1), minlength=n), 0)
-        ex = (keys % (self.n_item + 1)).int()
-        return eo.int(), (ex if ex.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
 
     def _foldin_rows(self, histories, kw):
         """(folded rows, off, p, n, total) for the ranking entries; the histories are checked with a sync whatever `sync` says - the
@@ -1830,7 +1842,89 @@ class OboVBpr(MfBasic):
 
 
 # =================================================================================================
-class OboFpmc_lr(_Base):
+class _SeqFoldin:
+    """Fold-in of the successive-POI models (include/poi_hip.h, poi_foldin_terms_* / poi_foldin_pair): OboFpmc_lr and OboPrme represent a
+    user by one trained row (ui[u], du[u]), so an unseen user gets one by running the model's own per-transition rule on a fresh row with
+    the item side frozen.  The terms pass writes each step's scalars a / c off the chain; the chain is poi_foldin_bpr's with them.
+    Nothing here changes a model parameter."""
+
+    def _foldin_positions(self, values, total, name, dtype):
+        """A per-check-in array of `total` entries -> a flat device tensor (entry 0 of every history is ignored)."""
+        if isinstance(values, torch.Tensor) and values.is_cuda:
+            t = values.to(self.device).reshape(-1)
+            if t.is_floating_point() and dtype == torch.int32 and bool((t != t.round()).any().item()):
+                raise ValueError("%s must be whole minutes (the reference's gap is a Theano iscalar)" % name)
+            t = t.to(dtype).contiguous()
+        else:
+            if isinstance(values, (list, tuple)) and len(values) and np.ndim(values[0]) > 0:
+                values = np.concatenate([np.asarray(v, np.float64).reshape(-1) for v in values])
+            h = np.asarray(values.cpu() if isinstance(values, torch.Tensor) else values, np.float64).reshape(-1)
+            if dtype == torch.int32:
+                if np.any(h != np.round(h)):
+                    raise ValueError("%s must be whole minutes (the reference's gap is a Theano iscalar)" % name)
+                t = torch.as_tensor(h.astype(np.int64).astype(np.int32)).to(self.device)
+            else:
+                if not np.all(np.isfinite(h)) or np.any(h < 0):
+                    raise ValueError("%s must be finite and >= 0" % name)
+                t = torch.as_tensor(h).to(self.device)
+        if t.numel() != total:
+            raise ValueError("%s must hold one entry per check-in (%d vs %d)" % (name, t.numel(), total))
+        return t if total else torch.zeros(1, dtype=dtype, device=self.device)
+
+    def _foldin_seq(self, csr, form, items, mean_of, draw, terms, negatives, epochs, alpha, lam, init, return_loss, sync):
+        """The shared body of fold_in: start rows, negatives (draw(e, out) fills epoch e's `total` ids), the terms pass
+        (terms(off, p, q, stride, n, total, epochs, c) -> a or None), the chain."""
+        off, p, n, total = csr
+        epochs = int(epochs)
+        if epochs < 0:
+            raise ValueError("epochs must be >= 0 (got %d)" % epochs)
+        alpha = self.alpha_lambda[0] if alpha is None else float(alpha)
+        lam = self.alpha_lambda[1] if lam is None else float(lam)
+        w0 = self._foldin_init(init, n, self.dim, mean_of)
+        if negatives is None:
+            q = torch.empty(max(epochs * total, 1), dtype=torch.int32, device=self.device)
+            stride = total
+            for e in range(epochs if total else 0):
+                draw(e, q[e * total:(e + 1) * total])
+        else:
+            q, stride = self._foldin_given_negatives(negatives, total, epochs, lo=-1)
+        c = torch.empty(max((epochs if stride else 1) * total, 1), dtype=torch.float64, device=self.device)
+        a = terms(off, p, q, stride, n, total, epochs, c)
+        w = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+        loss = torch.empty((n, epochs), dtype=torch.float32, device=self.device) if return_loss else None
+        self.ctx.check(self.lib.poi_foldin_pair(self.ctx.handle, _ptr(items), self.n_item, self.dim, form, 1, _ptr(off), _ptr(p), _ptr(q), stride,
+                                                _ptr(a), _ptr(c), stride, n, epochs, alpha, lam, _ptr(w0), _ptr(w), _ptr(loss), self._stream()))
+        if sync:
+            bad = self.ctx.take_bad_ids(self._stream().value)
+            if bad:
+                raise IndexError("%d history(ies) with an id outside [0, %d] (negatives: -1 skips the step), a bad distance or descending offsets: "
+                                 "their rows and losses are NaN" % (bad, self.n_item))
+        return (w, loss) if return_loss else w
+
+    def _foldin_last(self, off, p, n):
+        """Every history's last POI (n) int32; the ranking entries need one per history (it selects ai[last] / the query POI)."""
+        o = off.long()
+        if n and not bool((o[1:] > o[:-1]).all().item()):
+            raise ValueError("%s ranks a new user from its last check-in: every history needs at least one" % type(self).__name__)
+        last = p[(o[1:] - 1).clamp(min=0)].contiguous() if n else torch.zeros(0, dtype=torch.int32, device=self.device)
+        if n:
+            lo, hi = int(last.min().item()), int(last.max().item())
+            if lo < 0 or hi > self.n_item:
+                raise IndexError("fold_in histories: ids must lie in [0, %d] (found %d..%d)" % (self.n_item, lo, hi))
+        return last
+
+    def _foldin_rows(self, histories, kw, **extra):
+        """(folded rows, off, p, n, total, last POIs) for the ranking entries; the histories are checked with a sync whatever `sync`
+        says - the exclusion lists are built from them."""
+        if kw.get("return_loss"):
+            raise ValueError("return_loss belongs to fold_in")
+        off, p, n, total = self._foldin_csr(histories)
+        last = self._foldin_last(off, p, n)
+        w = self.fold_in((off, p[:total]), **dict(kw, sync=True, **extra))
+        return w, off, p, n, total, last
+
+
+class OboFpmc_lr(_SeqFoldin, _Base):
     """public/FPMC_LR.py:27-166 (driver prog_fpmc_lr.py): FPMC with localized regions.  Four tables ui (n_user, D) and iu / ia / ai
     (n_item + 1, D); a transition (u, a = POI at t-1, i = POI at t, j = negative among i's neighbours) moves six rows (poi_fpmc_step).
 
@@ -2040,6 +2134,60 @@ class OboFpmc_lr(_Base):
         candidates are neighbours(last POI) + the last POI itself; within_km=float("inf") lifts the radius."""
         return super().compute_sub_topk_near(start_end, k, self.ud_km if within_km is None else within_km, exclude, anchor, **kw)
 
+    # ---- fold-in: ui rows for check-in histories the model never trained on -------------------------------------------------------------
+    def fold_in(self, histories, negatives=None, epochs=10, alpha=None, lam=None, init="zeros", seed=0, return_loss=False, sync=True):
+        """Rows of ui for NEW check-in histories (include/poi_hip.h, poi_foldin_terms_fpmc + poi_foldin_pair): iu / ia / ai stay frozen and
+        the ui part of the model's own transition rule (public/FPMC_LR.py:113-140) runs `epochs` times over each history's transitions
+        t = 1 .. len - 1 on one fresh row.  Returns an (n, D) float32 device tensor[, the (n, epochs) summed -log sigmoid of every epoch].
+        histories: a list of POI id sequences or a CSR (off, p_flat), host or device; ids in [0, n_item].  negatives: None = drawn per
+        epoch from the targets' neighbour sets (sample_negatives(targets, seed + e); a target without a neighbour gets -1 and its step
+        is skipped), or `total` / epochs x total ids at the CSR positions (position 0 of a history is ignored; -1 skips the step).
+        alpha / lam: default to alpha_lambda[0:2].  init: "zeros", "mean" (the mean row of ui) or an (n, D) array.  Host data is checked
+        before any launch (IndexError); device data by the kernel: an offending history's row and losses are NaN, the others are
+        untouched, and - with sync - IndexError is raised (sync=False leaves the count to ctx.take_bad_ids())."""
+        csr = self._foldin_csr(histories)
+        P = self._fparams()
+
+        def draw(e, out):
+            out.copy_(self.sample_negatives(csr[1][:csr[3]], int(seed) + e))
+
+        def terms(off, p, q, stride, n, total, epochs, c):
+            self.ctx.check(self.lib.poi_foldin_terms_fpmc(self.ctx.handle, ctypes.byref(P), _ptr(off), _ptr(p), _ptr(q), stride, n, total, epochs,
+                                                          _ptr(c), self._stream()))
+            return None
+        return self._foldin_seq(csr, _lib.FOLDIN_DOT, self.iu.t, self.ui.t, draw, terms, negatives, epochs, alpha, lam, init, return_loss, sync)
+
+    def _foldin_users(self, w, last):
+        return torch.cat([w, self.ai.t.index_select(0, last.long())], 1).contiguous()
+
+    def recommend_new(self, histories, k, exclude="history", within_km=None, anchor="last", return_scores=False, return_counts=False,
+                      sync=True, **fold_in_kwargs):
+        """Top-k for NEW users: fold_in(histories, **fold_in_kwargs), then the rows [w | ai[last POI]] against [iu | ia] through the
+        restricted ranking of compute_sub_topk_near.  exclude: "history", None or a CSR pair (off, ids); within_km: only POIs within
+        that many km of the anchor (None: no radius; model.ud_km gives the paper's protocol); anchor: "last" (each history's last POI)
+        or one POI id per row (-1: none).  Every history needs at least one check-in.  Returns (n, k) int32 ids, k <= 32, -1 where a
+        row has fewer than k candidates[, scores][, candidate counts]."""
+        w, off, p, n, total, last = self._foldin_rows(histories, fold_in_kwargs)
+        if isinstance(anchor, str):
+            if anchor != "last":
+                raise ValueError("anchor must be 'last' or one POI id per row (got %r)" % (anchor,))
+            anc = torch.where(last >= self.n_item, torch.full_like(last, -1), last).contiguous()      # (the padding id has no coordinates)
+        else:
+            if anchor is None and within_km is not None:
+                raise ValueError("within_km needs an anchor: 'last' or one POI id per row")
+            anc = self._near_anchor(anchor, n, lambda: None)
+        ex = self._foldin_exclusion(exclude, off, p, n, total)
+        return self._near_launch(self._foldin_users(w, last), self._items(), anc, self._near_radius(within_km), ex, None, k, return_scores,
+                                 return_counts, sync)
+
+    def rank_new(self, histories, targets, exclude="history", return_scores=False, return_counts=False, sync=True, **fold_in_kwargs):
+        """Exact 0-based rank of `targets` ((n, len_t <= 8) POI ids, or a pair (ids, mask)) among all POIs for NEW users: fold_in, then
+        poi_score_rank on the rows [w | ai[last POI]], as compute_sub_target_rank.  exclude: "history", None or a CSR pair."""
+        w, off, p, n, total, last = self._foldin_rows(histories, fold_in_kwargs)
+        tgt, tm = self._rank_targets(targets, n)
+        ex = self._foldin_exclusion(exclude, off, p, n, total)
+        return self._rank_launch(self._foldin_users(w, last), self._items(), None, tgt, tm, ex, return_scores, return_counts, sync)
+
     def compute_sub_auc_preference(self, start_end):
         """FPMC_LR.py:84-104 -> bool ndarray (n, len_tes)."""
         ids, users, lo = self._users_rows(start_end)
@@ -2053,7 +2201,7 @@ class OboFpmc_lr(_Base):
 
 
 # =================================================================================================
-class OboPrme(_Base):
+class OboPrme(_SeqFoldin, _Base):
     """public/PRME.py:38-219 (driver prog_prme.py): PRME, a pairwise metric embedding with a geographical weight.  Three tables du
     (n_user, D), dp / ds (n_item + 1, D); a transition (u, [p, q, prev], d, gap) moves up to seven rows (poi_prme_step).  Scoring reads the
     `trained_*` snapshots taken by update_trained_items and ranks all POIs by a weighted squared Euclidean distance (poi_prme_score_all /
@@ -2256,6 +2404,129 @@ class OboPrme(_Base):
         """The rows compute_sub_topk ranks: every user from its row 0 (query = the last train POI)."""
         ids, lo = self._ids(a)
         return self.score_rows_device(ids, self._rows(self.tra_last_poi, ids, lo)), 1
+
+    # ---- fold-in: du rows for check-in histories the model never trained on -------------------------------------------------------------
+    def fold_in(self, histories, gaps, dists=None, negatives=None, epochs=10, alpha=None, lam=None, init="zeros", seed=0, return_loss=False,
+                sync=True):
+        """Rows of du for NEW check-in histories (include/poi_hip.h, poi_foldin_terms_prme + poi_foldin_pair): the du part of the model's
+        own transition rule (public/PRME.py:173-214) runs `epochs` times over each history's transitions t = 1 .. len - 1 on one fresh
+        row, against the trained_* snapshots.  Returns an (n, D) float32 device tensor[, the (n, epochs) summed -log sigmoid per epoch -
+        the reference's step returns +log sigmoid, fold-in keeps poi_foldin_bpr's sign].
+        histories: a list of POI id sequences or a CSR (off, p_flat).  gaps: whole minutes since the previous check-in, one per check-in
+        (a flat array or one sequence per history; entry 0 of a history is ignored; fractional gaps raise ValueError as the constructor
+        does).  dists: km from the previous check-in, likewise; None = cal_dis of `cordi` on the device.  negatives: None = drawn per
+        epoch with poi_sample_negatives on the history CSR (seed + e), or `total` / epochs x total ids at the CSR positions (-1 skips
+        the step).  init: "zeros", "mean" (the mean row of the trained du) or an (n, D) array.  Checks and the IndexError-after-sync
+        behaviour are OboFpmc_lr.fold_in's; a device distance that is negative or not finite makes a bad history too."""
+        csr = self._foldin_csr(histories)
+        total = csr[3]
+        gap = self._foldin_positions(gaps, total, "gaps", torch.int32)
+        dist = None if dists is None else self._foldin_positions(dists, total, "dists", torch.float64)
+        P = self._pparams(self._trained)
+
+        def draw(e, out):
+            self.ctx.check(self.lib.poi_sample_negatives(self.ctx.handle, _ptr(csr[0]), _ptr(csr[1]), csr[2], self.n_item, None, None, 0,
+                                                         (int(seed) + e) & 0xFFFFFFFFFFFFFFFF, _ptr(out), None, self._stream()))
+
+        def terms(off, p, q, stride, n, total, epochs, c):
+            a = torch.empty(max(total, 1), dtype=torch.float64, device=self.device)
+            self.ctx.check(self.lib.poi_foldin_terms_prme(self.ctx.handle, ctypes.byref(P), _ptr(self.cordi), _ptr(off), _ptr(p), _ptr(q), stride,
+                                                          _ptr(gap), _ptr(dist), n, total, epochs, self.thd, self.cw, _ptr(a), _ptr(c), self._stream()))
+            return a
+        return self._foldin_seq(csr, _lib.FOLDIN_METRIC, self._trained["dp"], self._trained["du"], draw, terms, negatives, epochs, alpha, lam, init,
+                                return_loss, sync)
+
+    def _foldin_score(self, w, last, o, c, k=None):
+        """Rows o .. o + c of the folded table `w` as the du table of a poi_prme_params, query POI = the history's last POI."""
+        P = _lib.PrmeParams(ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(self._trained["dp"].data_ptr()), ctypes.c_void_p(self._trained["ds"].data_ptr()),
+                            w.shape[0], self.n_item, self.dim)
+        users = torch.arange(o, o + c, dtype=torch.int32, device=self.device)
+        qp = last[o:o + c].contiguous()
+        if k is None:
+            out = torch.empty((c, self.n_item), dtype=torch.float32, device=self.device)
+            self.ctx.check(self.lib.poi_prme_score_all(self.ctx.handle, ctypes.byref(P), _ptr(self.cordi), _ptr(users), _ptr(qp), c, self.cw, _ptr(out),
+                                                       self._stream()))
+            return out
+        idx = torch.empty((c, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((c, k), dtype=torch.float32, device=self.device)
+        self.ctx.check(self.lib.poi_prme_score_topk(self.ctx.handle, ctypes.byref(P), _ptr(self.cordi), _ptr(users), _ptr(qp), c, self.cw, k, _ptr(idx),
+                                                    _ptr(sc), self._stream()))
+        return idx, sc
+
+    def _foldin_ex(self, exclude, off, p, n, total):
+        """_foldin_exclusion, with the ids of a caller's device lists checked here (no kernel of this path checks them)."""
+        eo, ex = self._foldin_exclusion(exclude, off, p, n, total)
+        if eo is not None and not isinstance(exclude, str):
+            cnt = int(eo[-1].item())
+            if eo.numel() != n + 1 or cnt > ex.numel() or bool((eo[1:] < eo[:-1]).any().item()) or int(eo[0].item()) != 0:
+                raise ValueError("exclude=(off, ids): off must ascend from 0 to len(ids)")
+            if cnt and (int(ex[:cnt].min().item()) < 0 or int(ex[:cnt].max().item()) >= self.n_item):
+                raise IndexError("exclude=(off, ids): ids must lie in [0, %d)" % self.n_item)
+        return eo, ex
+
+    def recommend_new(self, histories, gaps, k, exclude="history", return_scores=False, return_counts=False, sync=True, **fold_in_kwargs):
+        """Top-k for NEW users: fold_in(histories, gaps, **fold_in_kwargs), then the model's own geo-weighted score with the folded rows
+        as the du table and each history's last POI as the query POI.  exclude: "history" (each history's distinct POIs leave the
+        candidates), None or a CSR pair (off, ids).  Without an exclusion the fused top-K ranks (poi_prme_score_topk); with one, explicit
+        score rows - at most 1 GiB at a time - get -inf at the listed ids and go through poi_topk.  k <= min(64, n_item).  Returns (n, k)
+        int32 ids by descending score then ascending id, -1 where a row has fewer than k candidates[, scores][, candidate counts]."""
+        w, off, p, n, total, last = self._foldin_rows(histories, fold_in_kwargs, gaps=gaps)
+        k = int(k)
+        if not 0 < k <= min(64, self.n_item):
+            raise ValueError("k must lie in [1, min(64, n_item)] (got %d)" % k)
+        eo, ex = self._foldin_ex(exclude, off, p, n, total)
+        if eo is None:
+            idx, sc = self._foldin_score(w, last, 0, n, k) if n else (torch.empty((0, k), dtype=torch.int32, device=self.device),
+                                                                        torch.empty((0, k), dtype=torch.float32, device=self.device))
+            cnt = torch.full((n,), self.n_item, dtype=torch.int32, device=self.device)
+        else:
+            idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
+            sc = torch.empty((n, k), dtype=torch.float32, device=self.device)
+            eo64 = eo.long()
+            row = torch.repeat_interleave(torch.arange(n, device=self.device), eo64[1:] - eo64[:-1])
+            ids = ex[:row.numel()].long()
+            step = self._rank_chunk(n)
+            for o in range(0, n, step):
+                c = min(step, n - o)
+                full = self._foldin_score(w, last, o, c)
+                sel = (row >= o) & (row < o + c)
+                full[row[sel] - o, ids[sel]] = float("-inf")
+                self.ctx.check(self.lib.poi_topk(self.ctx.handle, _ptr(full), c, self.n_item, k, ctypes.c_void_p(idx.data_ptr() + 4 * o * k),
+                                                 ctypes.c_void_p(sc.data_ptr() + 4 * o * k), self._stream()))
+            idx = torch.where(sc == float("-inf"), torch.full_like(idx, -1), idx)
+            cnt = (self.n_item - (eo64[1:] - eo64[:-1])).int()
+        out = (idx,) + ((sc,) if return_scores else ()) + ((cnt,) if return_counts else ())
+        return out if len(out) > 1 else idx
+
+    def rank_new(self, histories, gaps=None, targets=None, exclude="history", return_scores=False, return_counts=False, sync=True, **fold_in_kwargs):
+        """Exact 0-based rank of `targets` ((n, len_t <= 8) POI ids, or a pair (ids, mask)) among all POIs for NEW users:
+        fold_in(histories, gaps, **fold_in_kwargs), explicit score rows (at most 1 GiB at a time) and poi_rank_scores.  exclude:
+        "history", None or a CSR pair (off, ids); an excluded target is not ranked (-1)."""
+        if gaps is None or targets is None:
+            raise ValueError("rank_new needs gaps and targets")
+        w, off, p, n, total, last = self._foldin_rows(histories, fold_in_kwargs, gaps=gaps)
+        tgt, tm = self._rank_targets(targets, n)
+        eo, ex = self._foldin_ex(exclude, off, p, n, total)
+        lt = tgt.shape[1]
+        rank = torch.empty((n, lt), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, lt), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        step = self._rank_chunk(n)
+        for o in range(0, n, step):
+            c = min(step, n - o)
+            full = self._foldin_score(w, last, o, c)
+            eo_c = eo[o:o + c + 1].contiguous() if eo is not None else None
+            r_c = torch.empty((c, lt), dtype=torch.int32, device=self.device)
+            k_c = torch.empty(c, dtype=torch.int32, device=self.device) if cnt is not None else None
+            self.ctx.check(self.lib.poi_rank_scores(self.ctx.handle, _ptr(full), c, self.n_item, _ptr(tgt[o:o + c].contiguous()),
+                                                    _ptr(tm[o:o + c].contiguous()), lt, _ptr(eo_c), _ptr(ex), _ptr(r_c), _ptr(k_c), self._stream()))
+            rank[o:o + c] = r_c
+            if cnt is not None:
+                cnt[o:o + c] = k_c
+            if sc is not None:
+                v = full.gather(1, tgt[o:o + c].long().clamp(0, self.n_item - 1))
+                sc[o:o + c] = torch.where(r_c >= 0, v, torch.full_like(v, float("-inf")))
+        return self._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
 
     def compute_sub_auc_preference(self, start_end):
         """PRME.py:141-159 returns zeros (the AUC code is commented out there): AUC is always 0."""
