@@ -69,6 +69,9 @@ extern "C" {
  * (existing entries unchanged). */
 /* additive to 9: fold-in for the successive-POI models - new entry points poi_foldin_terms_fpmc, poi_foldin_terms_prme and poi_foldin_pair,
  * timing names "foldin_terms" and "foldin_pair"; no new option or plan key (existing entries, poi_foldin_bpr included, unchanged). */
+/* additive to 9: online sessions of Lstm / Rnn / CA-RNN - new entry points poi_session_cell_advance and poi_session_carnn_advance,
+ * timing names "session_cell_advance" / "session_carnn_advance"; they read the option "session_tile_min" and write the plan keys
+ * "session_path" / "session_tiles" / "session_tile_min" as poi_session_advance does (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -709,6 +712,41 @@ int poi_session_advance(poi_ctx* ctx, const poi_gru_params* prm, const double* c
                         const int32_t* poi, int32_t n, float* hts_out, float* sts_out, void* stream);
 int poi_session_sts(poi_ctx* ctx, const poi_gru_params* prm, const double* h, int32_t n_slot, const int32_t* slot, int32_t n,
                     float* sts_out, void* stream);
+
+/* ---- online sessions of the baselines Lstm / Rnn / CA-RNN (additive to 9) ------------------------------------------------------------
+ * The same per-slot state, owned by the caller, for the three recurrent classes poi_session_advance does not cover: h (n_slot, D)
+ * FLOAT64, c (n_slot, D) FLOAT64 (the Lstm's cell state; NULL for POI_CELL_RNN), last_poi (n_slot) int32 with -1 = no check-in yet,
+ * steps (n_slot) int32.  There is no sts.  Both entries apply n events (slot[i], poi[i]) with j = poi[i], s = slot[i]; they are the cell
+ * steps of poi_cell_predict / poi_carnn_predict on the snapshots prm->lt (and prm->wd), so a zeroed slot (h = c = 0, last_poi = -1)
+ * advanced through p[0 .. L-1] holds what those entries return for that training row.
+ * poi_session_cell_advance (prm->cell = POI_CELL_RNN | POI_CELL_LSTM; public/GRU.py:720-722 and :562-567):
+ *   Rnn    h[s] = sigmoid(ui lt[j] + wh h[s] + bi)
+ *   Lstm   a = ui lt[j] + wh h[s] + bi  (four blocks of D rows);  i, f, o = sigmoid(a0), sigmoid(a1), sigmoid(a3);  g = tanh(a2)
+ *          c[s] = f * c[s] + i * g;  h[s] = o * tanh(c[s])
+ * poi_session_carnn_advance (public/CA_RNN.py:172-217, literally - the predict graph adds-then-sums):
+ *   d      = n_dist if last_poi[s] < 0, else bin(coords[j], coords[last_poi[s]])  (data.dist_pos_bins: the argument order, cphi and thr
+ *            of poi_session_advance; dd in metres)
+ *   h[s]   = sigmoid(M lt[j] + rowsum(wd[d]) + sum(h[s]))  with rowsum = the sum over the last axis of the (D, D) matrix wd[d] and
+ *            sum(h[s]) the scalar sum of the previous state
+ * All three: last_poi[s] = j; steps[s] += 1; the update is in place; hts_out (n, D) is an optional float32 copy of the new h rows.
+ * Precision: tables are float32 at the model's own dim (these classes are never stored padded; a registered half table: POI_ENOTSUP);
+ * every product, gate sum, sigmoid and tanh is float64.  No atomics touch a result and every sum has one fixed order: identical calls
+ * give bitwise identical state.  dim must be a multiple of 4 in [4, 256] - what poi_cell_predict and poi_carnn_predict accept - else
+ * POI_ENOTSUP; no row is read past its end.
+ * Repeated slots and bad ids: exactly as poi_session_advance - a slot named by more than one event of a call, a slot outside
+ * [0, n_slot) or a POI outside [0, n_item) leaves the state untouched, gives a NaN row in hts_out and is counted
+ * (poi_ctx_take_bad_ids).  Split a batch that repeats slots into successive calls (models.CellSession.advance does).
+ * Launch regimes: below "session_tile_min" events (default 512) one workgroup per event streams the weights from L2 - per event
+ * 8 D^2 bytes for Rnn and CA-RNN (ui + wh, or M + wd[d]), 32 D^2 for Lstm; from there on, with D % 16 == 0, 16 events per workgroup
+ * run on the float64 matrix cores and read the weights once per tile (CA-RNN: the row sums of all n_dist + 1 matrices are rewritten
+ * into context scratch by a pre-pass of every such call, so the entry follows a changed prm->wd without a cache).  Otherwise the event
+ * path serves every size.  poi_ctx_last_plan: "session_path", "session_tiles", "session_tile_min" as poi_session_advance writes them.
+ * Timing names: "session_cell_advance", "session_carnn_advance". */
+int poi_session_cell_advance(poi_ctx* ctx, const poi_cell_params* prm, double* h, double* c, int32_t* last_poi, int32_t* steps,
+                             int32_t n_slot, const int32_t* slot, const int32_t* poi, int32_t n, float* hts_out, void* stream);
+int poi_session_carnn_advance(poi_ctx* ctx, const poi_carnn_params* prm, const double* coords, const double* cphi, const double* thr,
+                              double dd, double* h, int32_t* last_poi, int32_t* steps, int32_t n_slot, const int32_t* slot,
+                              const int32_t* poi, int32_t n, float* hts_out, void* stream);
 
 /* ---- restricted recommendation (additive to 9): top-K within a radius of an anchor POI, skipping listed POIs ---------------------------
  * public/Valuate.py:132-146 ranks over every POI; FPMC-LR defines its candidates as the POIs within UD km of the last check-in

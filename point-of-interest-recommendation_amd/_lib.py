@@ -151,6 +151,10 @@ SIGNATURES = {
     "poi_session_advance": (c_int, [c_void_p, POINTER(GruParams), c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                     c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "poi_session_sts": (c_int, [c_void_p, POINTER(GruParams), c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "poi_session_cell_advance": (c_int, [c_void_p, POINTER(CellParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                         c_void_p]),
+    "poi_session_carnn_advance": (c_int, [c_void_p, POINTER(CarnnParams), c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int32,
+                                          c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "poi_score_topk_near": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_score_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -100,6 +100,7 @@ struct poi_ctx {
   int vbpr_grid = 0;        // option "vbpr_grid": cap of the workgroups of every VBPR kernel (0: none)
   // online sessions: per-slot claims of the repeated-slot check
   DevBuf sess_owner;
+  DevBuf sess_wrs;          // poi_session_carnn_advance, tile path: float64 row sums of the interval matrices, rewritten on every call
   int sess_tile_min = 512;  // option "session_tile_min": poi_session_advance calls of at least this many events take the tile kernel
   // restricted top-K (near.hip): per (row, slice) partial lists of the split path
   DevBuf near_ws;
@@ -243,7 +244,7 @@ int poi_ctx_destroy(poi_ctx* c) {
   if (!c) return POI_OK;
   DevBuf* all[] = {&c->ex_ws, &c->ex_slab, &c->ex_glt, &c->ex_gdi, &c->ws, &c->slab, &c->te_ws, &c->hslab, &c->zrow, &c->g_lt, &c->mult_lt, &c->nseq_lt, &c->g_di, &c->mult_di, &c->nseq_di, &c->seg_s, &c->seg_e, &c->pmark, &c->xc, &c->kc_dev, &c->uidx_stage, &c->out_stage, &c->ptab, &c->iota, &c->xw, &c->xg, &c->xflag, &c->bad_ids,
                    &c->g_wd, &c->mult_wd, &c->nseq_wd, &c->ca_ws, &c->ca_slab, &c->ca_scr, &c->ca2, &c->g_ux, &c->cnt_ux, &c->g_blt, &c->cnt_blt, &c->cand_s, &c->cand_i, &c->items_pk, &c->gbound, &c->st,
-                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->cell_ws, &c->vb_ws, &c->rank_ws};
+                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->cell_ws, &c->vb_ws, &c->rank_ws, &c->sess_wrs};
   (void)hipDeviceSynchronize();
   c->tm.clear();
   drop_graphs(c);
@@ -1369,6 +1370,63 @@ int poi_session_sts(poi_ctx* c, const poi_gru_params* P, const double* h, int32_
   A.bad = (int*)c->bad_ids.p;
   HIPCHK(c, poi::launch_session(A, 0, st, &c->tm));
   return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// online sessions of Lstm / Rnn / CA-RNN (session_cells.hip)
+// ---------------------------------------------------------------------------------------------
+static int session_cells_run(poi_ctx* c, poi::SessCellArgs& A, const char* who, void* stream) {
+  if (A.dim <= 0 || A.dim % 4 != 0 || A.dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, A.dim);
+  if (is_f16(c, A.lt)) return fail(c, POI_ENOTSUP, "%s: float32 tables only", who);
+  if (A.n_item <= 0) return fail(c, POI_EINVAL, "%s: n_item must be positive", who);
+  if (!A.h || !A.last_poi || !A.steps || A.n_slot <= 0) return fail(c, POI_EINVAL, "%s: h / last_poi / steps NULL or n_slot <= 0", who);
+  if (!A.slot || !A.poi || A.n < 0) return fail(c, POI_EINVAL, "%s: slot / poi NULL or n < 0", who);
+  if (A.n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  const int tile = A.n >= c->sess_tile_min && poi::sess_cell_tile_supported(A.G, A.dim);
+  // repeated slots: as poi_session_advance - one event needs no check, small event launches scan the call inside the kernel
+  if (A.n > 1 && (tile || A.n > SESS_SCAN_MAX)) {
+    if ((rc = ensure(c, c->sess_owner, sizeof(int) * (size_t)A.n_slot, st))) return rc;
+    A.owner = (int*)c->sess_owner.p;
+  }
+  if (tile && A.G == 0) {
+    if ((rc = ensure(c, c->sess_wrs, sizeof(double) * (size_t)(A.n_dist + 1) * A.dim, st))) return rc;
+    A.wrs = (const double*)c->sess_wrs.p;
+  }
+  c->plan.valid = 1; c->plan.session_path = tile; c->plan.session_tiles = tile ? (A.n + 15) / 16 : 0; c->plan.session_tile_min = c->sess_tile_min;
+  HIPCHK(c, poi::launch_session_cells(A, tile, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_session_cell_advance(poi_ctx* c, const poi_cell_params* P, double* h, double* cst, int32_t* last_poi, int32_t* steps, int32_t n_slot,
+                             const int32_t* slot, const int32_t* poi, int32_t n, float* hts_out, void* stream) {
+  if (!c || !P) return fail(c, POI_EINVAL, "poi_session_cell_advance: NULL ctx/params");
+  if (P->cell != POI_CELL_RNN && P->cell != POI_CELL_LSTM) return fail(c, POI_EINVAL, "poi_session_cell_advance: cell must be POI_CELL_RNN or POI_CELL_LSTM (got %d)", P->cell);
+  if (!P->lt || !P->ui || !P->wh || !P->bi) return fail(c, POI_EINVAL, "poi_session_cell_advance: lt/ui/wh/bi must be non-NULL");
+  if (P->cell == POI_CELL_LSTM && !cst) return fail(c, POI_EINVAL, "poi_session_cell_advance: the Lstm cell needs c");
+  poi::SessCellArgs A = poi::SessCellArgs{};
+  A.G = P->cell; A.lt = P->lt; A.ui = P->ui; A.wh = P->wh; A.bi = P->bi; A.n_item = P->n_item; A.dim = P->dim;
+  A.h = h; A.c = P->cell == POI_CELL_LSTM ? cst : nullptr; A.last_poi = last_poi; A.steps = steps; A.n_slot = n_slot;
+  A.slot = slot; A.poi = poi; A.n = n; A.hts_out = hts_out;
+  return session_cells_run(c, A, "poi_session_cell_advance", stream);
+}
+
+int poi_session_carnn_advance(poi_ctx* c, const poi_carnn_params* P, const double* coords, const double* cphi, const double* thr, double dd,
+                              double* h, int32_t* last_poi, int32_t* steps, int32_t n_slot, const int32_t* slot, const int32_t* poi, int32_t n,
+                              float* hts_out, void* stream) {
+  if (!c || !P) return fail(c, POI_EINVAL, "poi_session_carnn_advance: NULL ctx/params");
+  if (!P->lt || !P->wd || !P->M || P->n_dist <= 0) return fail(c, POI_EINVAL, "poi_session_carnn_advance: CA-RNN needs lt / wd / M and n_dist > 0");
+  if (!coords || !cphi || !thr || !(dd > 0)) return fail(c, POI_EINVAL, "poi_session_carnn_advance: coords / cphi / thr NULL or dd <= 0");
+  poi::SessCellArgs A = poi::SessCellArgs{};
+  A.G = 0; A.lt = P->lt; A.ui = P->M; A.wh = P->wd; A.n_item = P->n_item; A.n_dist = P->n_dist; A.dim = P->dim;
+  A.coords = coords; A.cphi = cphi; A.thr = thr; A.dd = dd;
+  A.h = h; A.last_poi = last_poi; A.steps = steps; A.n_slot = n_slot;
+  A.slot = slot; A.poi = poi; A.n = n; A.hts_out = hts_out;
+  return session_cells_run(c, A, "poi_session_carnn_advance", stream);
 }
 
 // ---------------------------------------------------------------------------------------------

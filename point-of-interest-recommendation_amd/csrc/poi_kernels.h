@@ -539,6 +539,26 @@ size_t sess_tile_lds(int D, int xw, int NB, int spatial);
 size_t sess_event_lds(int D, int xw, int NB, int spatial);
 bool sess_tile_supported(int D, int xw, int NB, int spatial);
 hipError_t launch_session(SessArgs& A, int tile, hipStream_t st, Timing* tm);
+// the repeated-slot claims alone (sess_claim_kernel + sess_mark_kernel): owner[s] = the one event that names slot s, or -1
+hipError_t launch_session_claims(const int* slot, int n, int n_slot, int* owner, hipStream_t st);
+
+// Online sessions of Lstm / Rnn / CA-RNN (session_cells.hip): the same state and launch regimes, templated on the cell
+struct SessCellArgs {
+  int G;                                    // gate blocks: 1 Rnn, 4 Lstm, 0 CA-RNN
+  const float *lt, *ui, *wh, *bi;           // cells: ui / wh (G D, D), bi (G D).  CA-RNN: ui = M (D, D), wh = wd (n_dist + 1, D, D), bi null
+  int n_item, n_dist, dim;                  // n_dist: CA-RNN only
+  const double *coords, *cphi, *thr; double dd;      // CA-RNN only
+  double *h, *c; int *last_poi, *steps; int n_slot;  // the state, updated in place (c: Lstm only)
+  const int *slot, *poi; int n;
+  float* hts_out;                           // optional (n, D) copy of the new rows (NaN rows: rejected events)
+  int* bad;                                 // device counter of rejected events (poi_ctx_take_bad_ids)
+  int* owner;                               // (n_slot) scratch of the repeated-slot check, or null: the event kernel scans the call
+  const double* wrs;                        // CA-RNN tile path: (n_dist + 1, D) float64 row sums of wd, written by the launch's pre-pass
+};
+size_t sess_cell_tile_lds(int G, int D);
+size_t sess_cell_event_lds(int G, int D);
+bool sess_cell_tile_supported(int G, int D);
+hipError_t launch_session_cells(SessCellArgs& A, int tile, hipStream_t st, Timing* tm);
 
 // Restricted top-K (near.hip): candidates within a radius of an anchor POI, minus a per-row exclusion list
 #define NEAR_K_MAX 32                       // list length (one half wave)

@@ -357,6 +357,14 @@ bool sess_tile_supported(int D, int xw, int NB, int spatial) {
   return D >= 16 && D % 16 == 0 && D <= 256 && sess_tile_lds(D, xw, NB, spatial) <= SESS_TILE_LDS_MAX;
 }
 
+hipError_t launch_session_claims(const int* slot, int n, int n_slot, int* owner, hipStream_t st) {
+  SessArgs A = SessArgs{};
+  A.slot = slot; A.n = n; A.n_slot = n_slot; A.owner = owner;
+  hipLaunchKernelGGL(sess_claim_kernel, dim3((n + 255) / 256), dim3(256), 0, st, A);
+  hipLaunchKernelGGL(sess_mark_kernel, dim3((n + 255) / 256), dim3(256), 0, st, A);
+  return hipGetLastError();
+}
+
 hipError_t launch_session(SessArgs& A, int tile, hipStream_t st, Timing* tm) {
   const int NB = A.n_dist + 1;
   tm->begin(A.head_only ? "session_sts" : "session_advance", st);

@@ -593,11 +593,12 @@ def train_poi2vec(ds, p=None, device="cuda:0", log=print):
 
 
 def serve_replay(model, ds=None, k=20):
-    """Online use of a trained GRU-family model (models.Session): seed every user's state from the training rows (`load_history`),
+    """Online use of a trained recurrent model (models.Session for the GRU family, models.CellSession - model.cell_session() - for Lstm,
+    Rnn and OboCARNN): seed every user's state from the training rows (`load_history`),
     advance every user by their first held-out test POI as if it had just been checked in, and recommend the next top-k from the new
     state.  `ds` is the data set the model was built from (its tables already live in the model; accepted for symmetry with the
     train_* drivers).  Returns (session, (n_user, k) int32 device indices)."""
-    s = model.session()
+    s = model.cell_session() if hasattr(model, "cell_session") else model.session()
     s.load_history()
     users = np.arange(model.n_user)
     tes = model.tes_buys_masks[:, 0].cpu().numpy()

@@ -897,6 +897,11 @@ class _CellModel(GruBasic):
         P.n_item, P.dim, P.cell = self.n_item, self.dim, self._cell
         return P
 
+    def cell_session(self, n_slot=None):
+        """Online state for this model (CellSession): per-slot h (and c) / last POI advanced one check-in at a time, top-K from it.
+        (`session()` stays the GRU family's entry and refuses this class.)"""
+        return CellSession(self, n_slot)
+
     def train(self, idxs):
         """seq_train(start_end) -> the batch's summed loss -upq (GRU.py:600, :755)."""
         return float(np.sum(self.train_batch(idxs), dtype=np.float64))
@@ -1266,6 +1271,11 @@ class OboCARNN(GruBasic):
         T.dp, T.dq = self.dp.data_ptr(), self.dq.data_ptr()
         return T
 
+    def cell_session(self, n_slot=None):
+        """Online state for this model (CellSession): per-slot h / last POI advanced one check-in at a time by the literal predict step,
+        ranked by compute_sub_all_scores' rule.  Needs coords= at construction.  (`session()` refuses this class.)"""
+        return CellSession(self, n_slot)
+
     def train(self, idx):
         """seq_train(uidx) -> los (public/CA_RNN.py:160-170,219-221)."""
         return float(self.train_batch(np.atleast_1d(idx))[0])
@@ -1321,7 +1331,8 @@ class Session:
 
     def __init__(self, model, n_slot=None):
         if not isinstance(model, GruBasic) or isinstance(model, (_CellModel, OboCARNN)):
-            raise _lib.PoiError("Session covers the GRU family (OboSpatialGru, OboGru, Gru): %s is out of scope" % type(model).__name__)
+            hint = " - use model.cell_session()" if isinstance(model, (_CellModel, OboCARNN)) else ""
+            raise _lib.PoiError("Session covers the GRU family (OboSpatialGru, OboGru, Gru): %s is out of scope%s" % (type(model).__name__, hint))
         if model.spatial and model.coords is None:
             raise _lib.PoiError("session on the spatial model needs coords= at construction")
         self.m = m = model
@@ -1580,6 +1591,180 @@ class Session:
             term = (m.wd.t, st, lpr.clamp(min=0).contiguous())
         ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
         return m._rank_launch(users, m.trained_items.t, term, tgt, tm, ex, return_scores, return_counts, sync)
+
+
+class CellSession(Session):
+    """Online sessions of the baselines `Lstm`, `Rnn` and `OboCARNN` (model.cell_session()): the slot bookkeeping, `advance`, `replay`
+    and the repeated-slot rule of `Session` over the cell steps of poi_session_cell_advance / poi_session_carnn_advance
+    (include/poi_hip.h).  A slot holds h (dim float64), c (Lstm only), last_poi (-1: none yet) and steps; there is no sts.  A fresh slot
+    advanced through p[0 .. L-1] holds what `predict` returns for a user whose training row is that sequence; every step reads the
+    evaluation snapshots as they are at the call (trained_items, and trained_dists for CA-RNN) and never changes a model parameter.
+    Lstm and Rnn rank as the plain GRU session does (h . trained_items[:-1]^T; within_km / exclude / return_counts after set_coords()).
+    CA-RNN ranks by its own rule (poi_carnn_score_all on the slots' h and last_poi + poi_topk / poi_rank_scores): a slot without a
+    check-in has no last POI and gets index -1 / a NaN score / rank -1, and within_km is refused as on the model itself."""
+
+    def __init__(self, model, n_slot=None):
+        if not isinstance(model, (_CellModel, OboCARNN)):
+            raise _lib.PoiError("CellSession covers Lstm, Rnn and OboCARNN: use model.session() for %s" % type(model).__name__)
+        self.carnn = isinstance(model, OboCARNN)
+        if self.carnn and model.coords is None:
+            raise _lib.PoiError("cell_session on OboCARNN needs coords= at construction (the interval of a check-in is computed on the device)")
+        self.m = m = model
+        self.lstm = not self.carnn and m._cell == _lib.CELL_LSTM
+        self.spatial = False                        # no sts and no distance term: the plain paths of Session
+        self.n_slot = int(m.n_user if n_slot is None else n_slot)
+        if self.n_slot <= 0:
+            raise ValueError("n_slot must be positive")
+        dev = m.device
+        self.h = torch.zeros((self.n_slot, m.dim), dtype=torch.float64, device=dev)
+        self.c = torch.zeros((self.n_slot, m.dim), dtype=torch.float64, device=dev) if self.lstm else None
+        self.last_poi = torch.full((self.n_slot,), -1, dtype=torch.int32, device=dev)
+        self.steps = torch.zeros(self.n_slot, dtype=torch.int32, device=dev)
+        self.nb, self.sts = 0, None
+
+    # ---- state ----------------------------------------------------------------------------------
+    def reset(self, slots=None):
+        """h = c = 0, last_poi = -1, steps = 0 (every slot, or the given ones)."""
+        super().reset(slots)
+        if self.lstm:
+            if slots is None:
+                self.c.zero_()
+            else:
+                self.c[self._slot_tensor(slots)] = 0.0
+
+    def load_history(self, users=None):
+        """Seed slot u from user u's training row of the model's own tables.  Rnn and CA-RNN take h from `predict_device` (the rows the
+        evaluation path ranks with).  poi_cell_predict does not return the Lstm's cell state, so an Lstm session REPLAYS the users'
+        training rows through the session kernels instead: its h then comes from them (float64 state, equal to predict_device's float32
+        rows within the test tolerance, not bitwise)."""
+        if not self.lstm:
+            return super().load_history(users)
+        m = self.m
+        a = np.arange(m.n_user) if users is None else self._host_ids("users", users, min(m.n_user, self.n_slot))
+        if a.size and a.max() >= self.n_slot:
+            raise IndexError("users must lie in [0, %d): the session has that many slots" % self.n_slot)
+        if len(np.unique(a)) != len(a):
+            a = np.unique(a)
+        if not a.size:
+            return
+        off, p = m._off_host.astype(np.int64), m.p.cpu().numpy()
+        lens = off[a + 1] - off[a]
+        sub = np.concatenate([p[off[u]:off[u + 1]] for u in a]) if lens.sum() else np.zeros(0, np.int64)
+        self.reset(a)
+        self.replay(np.concatenate(([0], np.cumsum(lens))), sub, slots=a)
+
+    def seed(self, slots, h, last_poi, steps=None, c=None):
+        """State from outside (a checkpoint, another model's rows): h (n, dim), last_poi (n) with -1 = none, c (n, dim) for an Lstm
+        (zeros when omitted; refused for the other cells)."""
+        if c is not None and not self.lstm:
+            raise ValueError("only an Lstm session holds a cell state c")
+        super().seed(slots, h, last_poi, steps)
+        if self.lstm:
+            ids = self._slot_tensor(slots)
+            if c is None:
+                self.c[ids] = 0.0
+            else:
+                ct = c if isinstance(c, torch.Tensor) else torch.as_tensor(np.asarray(c, np.float64))
+                self.c[ids] = ct.to(self.m.device, torch.float64).reshape(ids.numel(), -1)
+
+    def state(self, slots=None):
+        """Host copies: dict(h (n, dim) float64, last_poi, steps[, c (n, dim) float64 for an Lstm])."""
+        out = super().state(slots)
+        if self.lstm:
+            out["c"] = np.ascontiguousarray(self.c.index_select(0, self._slot_tensor(slots)).cpu().numpy())
+        return out
+
+    # ---- advance --------------------------------------------------------------------------------
+    def _launch(self, slot_ptr, poi_ptr, n, hts_out=None, sts_out=None):
+        m = self.m
+        P = m._cparams(snapshot=True)
+        if self.carnn:
+            m.ctx.check(m.lib.poi_session_carnn_advance(m.ctx.handle, ctypes.byref(P), _ptr(m.coords), _ptr(m._cphi), _ptr(m._binthr), m.dd * 1000.0,
+                                                        _ptr(self.h), _ptr(self.last_poi), _ptr(self.steps), self.n_slot, ctypes.c_void_p(slot_ptr),
+                                                        ctypes.c_void_p(poi_ptr), int(n), _ptr(hts_out), m._stream()))
+        else:
+            m.ctx.check(m.lib.poi_session_cell_advance(m.ctx.handle, ctypes.byref(P), _ptr(self.h), _ptr(self.c), _ptr(self.last_poi), _ptr(self.steps),
+                                                       self.n_slot, ctypes.c_void_p(slot_ptr), ctypes.c_void_p(poi_ptr), int(n), _ptr(hts_out),
+                                                       m._stream()))
+
+    # ---- ranking: CA-RNN's own rule ---------------------------------------------------------------
+    def _carnn_rows(self, slots):
+        """(n, users (n, dim) float32, last POI clamped to 0, has-a-check-in mask) of the slots."""
+        ids = self._slot_tensor(slots)
+        lpr = self.last_poi.index_select(0, ids)
+        return ids.numel(), self.h.index_select(0, ids).float().contiguous(), lpr.clamp(min=0).contiguous(), lpr >= 0
+
+    def _carnn_scores(self, users, lp, o, c):
+        m = self.m
+        full = torch.empty((c, m.n_item), dtype=torch.float32, device=m.device)
+        m.ctx.check(m.lib.poi_carnn_score_all(m.ctx.handle, _ptr(users[o:o + c]), _ptr(m.trained_items.t), _ptr(m.M.t), _ptr(m.trained_dists.t),
+                                              _ptr(m.coords), _ptr(m._cphi), _ptr(m._binthr), _ptr(lp[o:o + c]), c, m.n_item, m.n_dist, m.dim,
+                                              m.dd * 1000.0, _ptr(full), m._stream()))
+        return full
+
+    def recommend(self, slots, k, return_scores=False, within_km=None, exclude=None, return_counts=False, sync=True):
+        """(n, k) int32 device indices by descending score, ties by ascending index.  Lstm / Rnn: `Session.recommend`'s plain rule and
+        its restricted form.  CA-RNN: compute_sub_all_scores' rule on the slots' CURRENT h and last_poi (explicit score rows, <= 1 GiB
+        at a time, + poi_topk, k <= 64); a slot without a check-in gives -1 ids (NaN scores); within_km / exclude / return_counts are
+        not defined for its score rule and raise."""
+        if not self.carnn:
+            return super().recommend(slots, k, return_scores, within_km, exclude, return_counts, sync)
+        m = self.m
+        if within_km is not None or exclude is not None or return_counts:
+            raise _lib.PoiError("OboCARNN ranks by a score rule of its own: within_km / exclude / return_counts are not supported on its sessions")
+        k = int(k)
+        if k > 64:
+            raise _lib.PoiError("top-K supports k <= 64 (got %d)" % k)
+        n, users, lp, has = self._carnn_rows(slots)
+        idx = torch.empty((n, k), dtype=torch.int32, device=m.device)
+        sc = torch.empty((n, k), dtype=torch.float32, device=m.device) if return_scores else None
+        step = max(1, min(n, (1 << 28) // max(m.n_item, 1)))
+        for o in range(0, n, step):
+            c = min(step, n - o)
+            full = self._carnn_scores(users, lp, o, c)
+            m.ctx.check(m.lib.poi_topk(m.ctx.handle, _ptr(full), c, m.n_item, k, ctypes.c_void_p(idx.data_ptr() + 4 * o * k),
+                                       ctypes.c_void_p(sc.data_ptr() + 4 * o * k) if sc is not None else None, m._stream()))
+        idx = torch.where(has[:, None], idx, torch.full_like(idx, -1))
+        if sc is not None:
+            sc = torch.where(has[:, None], sc, torch.full_like(sc, float("nan")))
+        return (idx, sc) if return_scores else idx
+
+    def rank_of(self, slots, pois, exclude=None, return_scores=False, return_counts=False, sync=True):
+        """Exact 0-based rank of pois[i] (one POI per slot, or (n, len_t <= 8)) among all POIs under the slot's CURRENT state and the
+        score rule of `recommend`.  exclude: None, "last" or CSR lists (off, ids).  CA-RNN goes through its score rows and
+        poi_rank_scores; a slot without a check-in gives rank -1 (NaN score, count 0)."""
+        if not self.carnn:
+            return super().rank_of(slots, pois, exclude, return_scores, return_counts, sync)
+        m = self.m
+        n, users, lp, has = self._carnn_rows(slots)
+        tgt, tm = m._rank_targets(pois.reshape(n, -1) if isinstance(pois, torch.Tensor) else np.asarray(pois).reshape(n, -1), n)
+        lpr = torch.where(has, lp, torch.full_like(lp, -1))
+        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
+        lt = tgt.shape[1]
+        rank = torch.empty((n, lt), dtype=torch.int32, device=m.device)
+        sc = torch.empty((n, lt), dtype=torch.float32, device=m.device) if return_scores else None
+        cnt = torch.empty(n, dtype=torch.int32, device=m.device) if return_counts else None
+        step = max(1, min(n, (1 << 28) // max(m.n_item, 1)))
+        for o in range(0, n, step):
+            c = min(step, n - o)
+            full = self._carnn_scores(users, lp, o, c)
+            eo = ex[0][o:o + c + 1].contiguous() if ex[0] is not None else None
+            r_c = torch.empty((c, lt), dtype=torch.int32, device=m.device)
+            k_c = torch.empty(c, dtype=torch.int32, device=m.device) if cnt is not None else None
+            m.ctx.check(m.lib.poi_rank_scores(m.ctx.handle, _ptr(full), c, m.n_item, _ptr(tgt[o:o + c].contiguous()), _ptr(tm[o:o + c].contiguous()), lt,
+                                              _ptr(eo), _ptr(ex[1]), _ptr(r_c), _ptr(k_c), m._stream()))
+            rank[o:o + c] = r_c
+            if cnt is not None:
+                cnt[o:o + c] = k_c
+            if sc is not None:
+                v = full.gather(1, tgt[o:o + c].long().clamp(0, m.n_item - 1))
+                sc[o:o + c] = torch.where(r_c >= 0, v, torch.full_like(v, float("-inf")))
+        rank = torch.where(has[:, None], rank, torch.full_like(rank, -1))
+        if sc is not None:
+            sc = torch.where(has[:, None], sc, torch.full_like(sc, float("nan")))
+        if cnt is not None:
+            cnt = torch.where(has, cnt, torch.zeros_like(cnt))
+        return m._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
 
 
 # =================================================================================================
