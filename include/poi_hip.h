@@ -72,6 +72,9 @@ extern "C" {
 /* additive to 9: online sessions of Lstm / Rnn / CA-RNN - new entry points poi_session_cell_advance and poi_session_carnn_advance,
  * timing names "session_cell_advance" / "session_carnn_advance"; they read the option "session_tile_min" and write the plan keys
  * "session_path" / "session_tiles" / "session_tile_min" as poi_session_advance does (existing entries unchanged). */
+/* additive to 9: GeoIE scoring under the trained geo-influence law - new entry points poi_geoie_score_all_geo and poi_geoie_score_topk_geo,
+ * option "geoie_score_span", plan keys "geoie_score_span" / "geoie_score_splits", timing names "geoie_score_geo" / "geoie_topk_geo" (existing
+ * entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -155,7 +158,8 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * Additive to 9: "session_path", "session_tiles", "session_tile_min" - written by poi_session_advance (which leaves the other keys as they
  * are and also makes the plan readable).
  * Additive to 9: "near_path", "near_splits", "near_split_max" - written by poi_score_topk_near in the same way.
- * Additive to 9: "rank_splits" - written by poi_score_rank in the same way. */
+ * Additive to 9: "rank_splits" - written by poi_score_rank in the same way.
+ * Additive to 9: "geoie_score_span", "geoie_score_splits" - written by poi_geoie_score_all_geo / poi_geoie_score_topk_geo in the same way. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -558,6 +562,44 @@ int poi_geoie_pair_distances(poi_ctx* ctx, const int32_t* off, const int32_t* p,
  * Timing name: "geoie_uvec". */
 int poi_geoie_user_vectors(poi_ctx* ctx, const poi_geoie_params* prm, const int32_t* off, const int32_t* p, int32_t n_user, int32_t len_max,
                            int32_t norm, float* out, void* stream);
+/* Scoring under the TRAINED rule (additive to 9): the score poi_geoie_step optimises, against every POI.  The
+ * reference's scoring (GeoIE.py:117-127, poi_geoie_user_vectors above) drops the power law f; this is its commented-out line
+ * `gh = T.sum(gi * hj, 3) * self.f_d(self.trained_f, d) / n_H` without the (n_user, L, n_item) distance list: every distance is recomputed
+ * per pair and never stored.  For a history p_0 .. p_{L-1} (ids in [0, n_item)) and a candidate l in [0, n_item):
+ *   S(l) = tu . z[l] + (1 / L) sum_{k in distinct(p), ascending id} m_k (g[k] . h[l]) f(d_eff(k, l))
+ * m_k = occurrences of k in the history (revisits share one distance: each distinct POI is evaluated once);
+ * d = float32(cal_dis(k, l)) exactly as the step computes it (float64, cal_dis's operation order, cphi from the host, no contraction);
+ * d_eff = max(d, d_min); f = a exp(b ln d_eff) in float64, the step's arithmetic.  The two D-wide dot products are float32; the sum over
+ * k and the user term are accumulated in float64 in a fixed order per (history, candidate); the result is rounded once to float32.  The
+ * divisor is L - the step's 1 / (i + 1) with the whole history behind it; score_norm does not apply.  tu (n_rows, D) or NULL (= zero: a
+ * user the model never saw; t never moves in training, so a GeoIE user IS its history).
+ * Undefined cases (rules 2-4): a pair at d_eff = 0 contributes 0 when b > 0; when b <= 0 the candidate's score is
+ * NaN in the matrix, it is never selected by the top-K and counts below every target in poi_rank_scores - this happens exactly when the
+ * candidate coincides with a history POI and d_min = 0.  An empty history scores tu . z[l] alone.
+ *   off / p / mult  CSR of COMPACTED histories: p the distinct ids of a history in strictly ascending order, mult their multiplicities
+ *                   (NULL = 1 each), L = the sum of a row's mult
+ *   rows (n_rows)   the histories of the CSR to score, output row r <- history rows[r] (NULL = the identity); trusted like user ids
+ *   prm             the tables to score with (the caller's snapshots); t is not read
+ * A bad row - off[h + 1] < off[h], an id outside [0, n_item), ids not strictly ascending, a multiplicity < 1, or a malformed exclusion
+ * list - gets NaN scores (matrix) or -1 ids, -inf scores and count 0 (top-K), is counted once (poi_ctx_take_bad_ids), and its
+ * neighbours are untouched.  The bits of a row depend on its own history, tu and the tables only - not on the other rows of the call,
+ * the grid or the span size.  n_rows == 0 is a no-op.
+ * poi_geoie_score_all_geo writes out (n_rows, n_item).  Timing name: "geoie_score_geo".
+ * poi_geoie_score_topk_geo (1 <= k <= 32): idx_out (n_rows, k) by descending score, ties by ascending id; score_out (n_rows, k) or NULL,
+ * bitwise the matrix's values; ex_off (n_rows + 1) / ex per-row exclusion lists under poi_score_topk_near's contract (ids ascending and
+ * unique within a row, both NULL = none), skipped before the pair math; count_out (n_rows) or NULL = the selectable candidates of a row
+ * (not excluded, score neither NaN nor -inf); a row with fewer than k of them ends in -1 ids and -inf scores.  Timing name:
+ * "geoie_topk_geo".
+ * Both cut [0, n_item) into spans of "geoie_score_span" candidates (poi_ctx_set_option; 0 = default: about 4 workgroups per CU over the
+ * call, at least 256 candidates each; rounded up to a multiple of 16), one workgroup per (row, span); the top-K folds a row's span lists
+ * in a second small kernel.  Every span size gives bitwise the same lists and scores.  poi_ctx_last_plan: "geoie_score_span" (the span
+ * in force), "geoie_score_splits" (spans per row). */
+int poi_geoie_score_all_geo(poi_ctx* ctx, const poi_geoie_params* prm, const int32_t* off, const int32_t* p, const int32_t* mult, const float* tu,
+                            const int32_t* rows, int32_t n_rows, const double* coords, const double* cphi, double d_min, float* out,
+                            void* stream);
+int poi_geoie_score_topk_geo(poi_ctx* ctx, const poi_geoie_params* prm, const int32_t* off, const int32_t* p, const int32_t* mult, const float* tu,
+                             const int32_t* rows, int32_t n_rows, const double* coords, const double* cphi, double d_min, const int32_t* ex_off,
+                             const int32_t* ex, int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
 
 /* ---- POI2Vec (additive to ABI 9) - prog_poi2vec.py, public/POI2Vec.py, public/Load_Data_Poi2vec.py ----------------------------------
  * Tables (POI2Vec.py:63-71): xu (n_user, D), wl (n_item + 1, D) whose last row is the zero pad row wl_m and never moves, pb (n_node, D),

@@ -137,6 +137,10 @@ SIGNATURES = {
     "poi_geoie_pair_distances": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                          c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "poi_geoie_user_vectors": (c_int, [c_void_p, POINTER(GeoieParams), c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "poi_geoie_score_all_geo": (c_int, [c_void_p, POINTER(GeoieParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                        c_double, c_void_p, c_void_p]),
+    "poi_geoie_score_topk_geo": (c_int, [c_void_p, POINTER(GeoieParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                         c_double, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_poi2vec_step": (c_int, [c_void_p, POINTER(Poi2vecParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64,
                                  c_int32, c_float, c_float, c_void_p, c_void_p]),
     "poi_poi2vec_scores": (c_int, [c_void_p, POINTER(Poi2vecParams), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
@@ -222,7 +226,7 @@ def load():
 # keys of poi_ctx_last_plan (include/poi_hip.h)
 PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", "fwd_tab", "xft", "xcomp", "head_split", "efuse", "early_bins",
              "fork", "hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg", "cell_kernel", "cell_grid", "session_path", "session_tiles", "session_tile_min",
-             "near_path", "near_splits", "near_split_max", "rank_splits")
+             "near_path", "near_splits", "near_split_max", "rank_splits", "geoie_score_span", "geoie_score_splits")
 
 
 class Context:
@@ -313,7 +317,8 @@ class Context:
     def set_option(self, name, value):
         """Named tuning switch of the tile engine (poi_ctx_set_option: "forward_table_compact", "forward_table_compact_min", "head_split",
         "early_bins", "hot_bins", "hybrid", "hybrid_min", "hybrid_max", "hybrid_force"; "cell_grid" of poi_cell_step; "session_tile_min" of poi_session_advance;
-        "near_split_max" / "near_grid" of poi_score_topk_near; "rank_grid" of poi_score_rank)."""
+        "near_split_max" / "near_grid" of poi_score_topk_near; "rank_grid" of poi_score_rank; "geoie_score_span" of
+        poi_geoie_score_all_geo / poi_geoie_score_topk_geo)."""
         self.check(self.lib.poi_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def set_small_launch(self, max_sequences=1800):

@@ -79,7 +79,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR
@@ -106,6 +106,9 @@ struct poi_ctx {
   DevBuf near_ws;
   int near_split_max = 256; // option "near_split_max": poi_score_topk_near calls of at most this many rows split each row's band over several workgroups
   int near_grid = 0;        // option "near_grid": workgroups per row on the split path (0: by the row count and the CUs)
+  // GeoIE scoring under the trained rule (geoie_score.hip): per (row, span) partial lists of the top-K mode
+  DevBuf geo_ws;
+  int geo_span = 0;         // option "geoie_score_span": candidates per workgroup (0: by the row count and the CUs)
   // exact target ranks (rank.hip): the targets' scores and ids, pass 1 -> pass 2
   DevBuf rank_ws;
   int rank_grid = 0;        // option "rank_grid": cap of the item ranges a 32-row tile is split into (0: by the row count and the CUs)
@@ -244,7 +247,7 @@ int poi_ctx_destroy(poi_ctx* c) {
   if (!c) return POI_OK;
   DevBuf* all[] = {&c->ex_ws, &c->ex_slab, &c->ex_glt, &c->ex_gdi, &c->ws, &c->slab, &c->te_ws, &c->hslab, &c->zrow, &c->g_lt, &c->mult_lt, &c->nseq_lt, &c->g_di, &c->mult_di, &c->nseq_di, &c->seg_s, &c->seg_e, &c->pmark, &c->xc, &c->kc_dev, &c->uidx_stage, &c->out_stage, &c->ptab, &c->iota, &c->xw, &c->xg, &c->xflag, &c->bad_ids,
                    &c->g_wd, &c->mult_wd, &c->nseq_wd, &c->ca_ws, &c->ca_slab, &c->ca_scr, &c->ca2, &c->g_ux, &c->cnt_ux, &c->g_blt, &c->cnt_blt, &c->cand_s, &c->cand_i, &c->items_pk, &c->gbound, &c->st,
-                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->cell_ws, &c->vb_ws, &c->rank_ws, &c->sess_wrs};
+                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->cell_ws, &c->vb_ws, &c->rank_ws, &c->sess_wrs, &c->geo_ws};
   (void)hipDeviceSynchronize();
   c->tm.clear();
   drop_graphs(c);
@@ -1221,6 +1224,70 @@ int poi_geoie_user_vectors(poi_ctx* c, const poi_geoie_params* P, const int32_t*
   return POI_OK;
 }
 
+// scoring under the trained rule (geoie_score.hip): k == 0 writes the (n_rows, n_item) matrix, k > 0 the lists
+static int geoie_score_common(poi_ctx* c, const char* who, const poi_geoie_params* P, const int32_t* off, const int32_t* p, const int32_t* mult,
+                              const float* tu, const int32_t* rows, int32_t n_rows, const double* coords, const double* cphi, double d_min,
+                              float* out, const int32_t* ex_off, const int32_t* ex, int32_t k, int32_t* idx_out, float* score_out,
+                              int32_t* count_out, void* stream) {
+  int rc = geoie_check(c, P, who);
+  if (rc) return rc;
+  if (n_rows < 0) return fail(c, POI_EINVAL, "%s: n_rows < 0", who);
+  if (!(d_min >= 0.0)) return fail(c, POI_EINVAL, "%s: d_min must be >= 0", who);
+  if ((ex_off == nullptr) != (ex == nullptr)) return fail(c, POI_EINVAL, "%s: ex_off and ex go together", who);
+  if (tu && is_f16(c, tu)) return fail(c, POI_ENOTSUP, "%s: tu must be float32", who);
+  if (n_rows == 0) return POI_OK;
+  if (!off || !p || !coords || !cphi) return fail(c, POI_EINVAL, "%s: NULL off / p / coords / cphi", who);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::GeoScoreArgs A = {};
+  A.g = P->g; A.h = P->h; A.z = P->z; A.ab = P->ab; A.n_item = P->n_item; A.dim = P->dim;
+  A.off = off; A.p = p; A.mult = mult; A.rows = rows; A.tu = tu; A.n_rows = n_rows;
+  A.coords = coords; A.cphi = cphi; A.d_min = d_min;
+  A.out = out; A.k = k; A.ex_off = ex_off; A.ex = ex; A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  // candidates per workgroup: "geoie_score_span", or - so that a call of one history still fills the chip - about 4 workgroups per CU
+  // over the call, at least 256 candidates each
+  int64_t span = c->geo_span;
+  if (span <= 0) {
+    const int64_t want = ((int64_t)4 * c->num_cu + n_rows - 1) / n_rows;
+    span = ((int64_t)P->n_item + want - 1) / want;
+    if (span < 256) span = 256;
+  }
+  span = (span + 15) & ~(int64_t)15;
+  if (span > (int64_t)1 << 30) span = (int64_t)1 << 30;
+  A.span = (int)span;
+  A.n_split = (int)(((int64_t)P->n_item + span - 1) / span);
+  if ((int64_t)n_rows * A.n_split >= ((int64_t)1 << 31) - 1) return fail(c, POI_ENOTSUP, "%s: n_rows x spans per row must stay below 2^31", who);
+  if (k > 0 && A.n_split > 1) {
+    const size_t lists = (size_t)n_rows * A.n_split;
+    if ((rc = ensure(c, c->geo_ws, lists * (GEO_K_MAX * (sizeof(float) + sizeof(int)) + sizeof(int)), st))) return rc;
+    A.part_s = (float*)c->geo_ws.p;
+    A.part_i = (int*)(A.part_s + lists * GEO_K_MAX);
+    A.part_cnt = A.part_i + lists * GEO_K_MAX;
+  }
+  c->plan.valid = 1; c->plan.geoie_score_span = A.span; c->plan.geoie_score_splits = A.n_split;
+  HIPCHK(c, poi::launch_geoie_score(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_geoie_score_all_geo(poi_ctx* c, const poi_geoie_params* P, const int32_t* off, const int32_t* p, const int32_t* mult, const float* tu,
+                            const int32_t* rows, int32_t n_rows, const double* coords, const double* cphi, double d_min, float* out,
+                            void* stream) {
+  if (c && n_rows > 0 && !out) return fail(c, POI_EINVAL, "poi_geoie_score_all_geo: NULL out");
+  return geoie_score_common(c, "poi_geoie_score_all_geo", P, off, p, mult, tu, rows, n_rows, coords, cphi, d_min, out, nullptr, nullptr, 0, nullptr,
+                            nullptr, nullptr, stream);
+}
+
+int poi_geoie_score_topk_geo(poi_ctx* c, const poi_geoie_params* P, const int32_t* off, const int32_t* p, const int32_t* mult, const float* tu,
+                             const int32_t* rows, int32_t n_rows, const double* coords, const double* cphi, double d_min, const int32_t* ex_off,
+                             const int32_t* ex, int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out, void* stream) {
+  if (k <= 0 || k > GEO_K_MAX) return fail(c, POI_ENOTSUP, "poi_geoie_score_topk_geo supports 1 <= k <= %d (got %d)", GEO_K_MAX, k);
+  if (c && n_rows > 0 && !idx_out) return fail(c, POI_EINVAL, "poi_geoie_score_topk_geo: NULL idx_out");
+  return geoie_score_common(c, "poi_geoie_score_topk_geo", P, off, p, mult, tu, rows, n_rows, coords, cphi, d_min, nullptr, ex_off, ex, k, idx_out,
+                            score_out, count_out, stream);
+}
+
 // ---------------------------------------------------------------------------------------------
 // mini-batch Lstm / Rnn (cells.hip)
 static int cell_check(poi_ctx* c, const poi_cell_params* P, const poi_seq_tables* T, bool need_q, const char* who) {
@@ -2081,7 +2148,7 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
                       {"early_bins", &c->early_bins, 0, 1}, {"hot_bins", &c->hot_bins, 0, 1}, {"hybrid", &c->hybrid, 0, 1}, {"hybrid_min", &c->hyb_min, 0, 1 << 30}, {"hybrid_max", &c->hyb_max, 0, 1 << 30}, {"hybrid_force", &c->hyb_force, 0, 1 << 30},
                       {"cell_grid", &c->cell_grid, 0, 1 << 30}, {"vbpr_grid", &c->vbpr_grid, 0, 1 << 30}, {"session_tile_min", &c->sess_tile_min, 1, 1 << 30},
                       {"near_split_max", &c->near_split_max, 0, 1 << 30}, {"near_grid", &c->near_grid, 0, NEAR_SPLIT_LIMIT},
-                      {"rank_grid", &c->rank_grid, 0, 1 << 30}};
+                      {"rank_grid", &c->rank_grid, 0, 1 << 30}, {"geoie_score_span", &c->geo_span, 0, 1 << 30}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);
@@ -2162,7 +2229,8 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"session_path", &poi_ctx::LastPlan::session_path}, {"session_tiles", &poi_ctx::LastPlan::session_tiles},
       {"session_tile_min", &poi_ctx::LastPlan::session_tile_min}, {"near_path", &poi_ctx::LastPlan::near_path},
       {"near_splits", &poi_ctx::LastPlan::near_splits}, {"near_split_max", &poi_ctx::LastPlan::near_split_max},
-      {"rank_splits", &poi_ctx::LastPlan::rank_splits}};
+      {"rank_splits", &poi_ctx::LastPlan::rank_splits}, {"geoie_score_span", &poi_ctx::LastPlan::geoie_score_span},
+      {"geoie_score_splits", &poi_ctx::LastPlan::geoie_score_splits}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

@@ -20,7 +20,7 @@
 // geoie_keys + te_scatter's radix sort of the 5 touches per row keyed (table, row) over [g | h | z], the run sums of fpmc.hip / prme.hip
 // (64-touch windows joined across window boundaries) with k = the number of distinct users in a run, geoie_commit, geoie_ab.  No float
 // atomics: identical launches give bitwise identical tables and a, b.
-#include "poi_common.h"
+#include "geoie_pair.h"      // gi_dist, gi_f: shared with geoie_score.hip
 #include "poi_kernels.h"
 
 namespace poi {
@@ -29,30 +29,6 @@ namespace poi {
 #define GI_JT 64        // columns per LDS tile of geoie_row
 #define GI_TC 16        // columns per work item of geoie_col
 #define GI_IT 64        // rows per LDS tile of geoie_col
-
-// cal_dis of Load_Data_GeoIE.py:28-42 (FPMC-LR's): float64 in its operation order, cos(lat) from the host (cphi), rounded to float32
-// as the reference's fmatrix inputs dist_pos / dist_neg are
-__device__ __forceinline__ float gi_dist(double lat1, double lon1, double cp1, double lat2, double lon2, double cp2) {
-#pragma clang fp contract(off)
-  const double pr = 0.017453292519943295;
-  const double a = (lat1 - lat2) * pr;
-  const double b = (lon1 - lon2) * pr;
-  const double c = (1.0 - cos_small(a)) / 2 + cp1 * cp2 * (1.0 - cos_small(b)) / 2;
-  return (float)(12742 * asin(sqrt(c)));
-}
-
-// f = a d_eff^b and its a / b derivatives; `bad` for d_eff = 0 with b <= 0 (the reference's inf / NaN)
-__device__ __forceinline__ void gi_f(float d32, double dmin, double a, double b, double& f, double& fa, double& fb, bool& bad) {
-  double d = (double)d32;
-  if (d < dmin) d = dmin;
-  if (d == 0.0) {
-    f = 0.0; fa = 0.0; fb = 0.0;
-    if (!(b > 0.0)) bad = true;
-    return;
-  }
-  const double l = log(d), pw = exp(b * l);
-  f = a * pw; fa = pw; fb = f * l;
-}
 
 __device__ __forceinline__ int gi_id(int v, int hi) { return (unsigned)v < (unsigned)hi ? v : 0; }
 

@@ -434,6 +434,24 @@ hipError_t launch_geoie_pairs(GeoieArgs& A, int num_cu, hipStream_t st);
 hipError_t launch_geoie_uvec(const float* g, const float* t, const int* off, const int* p, int n_user, int n_item, int dim, int len_max,
                              int norm, float* out, int num_cu, hipStream_t st);
 
+// GeoIE scoring under the trained rule (geoie_score.hip)
+#define GEO_K_MAX 32                        // list length (one half wave)
+struct GeoScoreArgs {
+  const float *g, *h, *z; const double* ab; // (n_item + 1, D) x 3; a, b on the device
+  int n_item, dim;
+  const int *off, *p, *mult;                // compacted histories: CSR of distinct ascending ids, their multiplicities (null = 1 each)
+  const int* rows; const float* tu;         // (n_rows) histories of the CSR (null = identity); (n_rows, D) user rows (null = zero)
+  int n_rows;
+  const double *coords, *cphi; double d_min;
+  int span, n_split;                        // candidates per workgroup; workgroups per row = ceil(n_item / span)
+  float* out;                               // matrix mode (k == 0): (n_rows, n_item)
+  int k; const int *ex_off, *ex;            // top-K mode: per-row exclusion lists (null = none)
+  int* idx_out; float* score_out; int* count_out;             // score_out / count_out may be null
+  float* part_s; int *part_i, *part_cnt;    // n_split > 1: (n_rows, n_split, GEO_K_MAX) partial lists, (n_rows, n_split) counts
+  int* bad;                                 // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+hipError_t launch_geoie_score(GeoScoreArgs& A, hipStream_t st, Timing* tm);
+
 // POI2Vec (poi2vec.hip)
 struct P2vArgs {
   float *xu, *wl, *pb;              // (n_user, D), (n_item [+ pad], D), (n_node, D)

@@ -369,9 +369,9 @@ class _Base:
             filled[lo:lo + n] = True
 
 
-    def _topk_from_scores(self, start_end, k, return_scores=False):
+    def _topk_from_scores(self, start_end, k, return_scores=False, scores=None):
         """Cut-offs beyond the fused kernels' k <= 32 (e.g. at_nums = [5, 10, 15, 20, 30, 50], public/Valuate.py:126):
-        explicit score rows (compute_sub_all_scores_device, <= 1 GiB at a time) + poi_topk (k <= 64)."""
+        explicit score rows (compute_sub_all_scores_device or `scores`, <= 1 GiB at a time) + poi_topk (k <= 64)."""
         if k > 64:
             raise _lib.PoiError("top-K supports k <= 64 (got %d)" % k)
         a = start_end if isinstance(start_end, torch.Tensor) else np.atleast_1d(np.asarray(start_end))
@@ -380,7 +380,7 @@ class _Base:
         sc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_scores else None
         step = max(1, min(n, (1 << 28) // max(self.n_item, 1)))
         for o in range(0, n, step):
-            full = self.compute_sub_all_scores_device(a[o:o + step])
+            full = (scores or self.compute_sub_all_scores_device)(a[o:o + step])
             self.ctx.check(self.lib.poi_topk(self.ctx.handle, _ptr(full), full.shape[0], self.n_item, int(k), ctypes.c_void_p(idx.data_ptr() + 4 * o * k),
                                              ctypes.c_void_p(sc.data_ptr() + 4 * o * k) if sc is not None else None, self._stream()))
         return (idx, sc) if return_scores else idx
@@ -2743,20 +2743,25 @@ class OboGeoIE(_Base):
     """public/GeoIE.py:46-194 (driver prog_geoie.py): GeoIE, a pairwise geo-influence model.  Tables g (geo-influence), h (geo-susceptibility),
     z (POI preference) (n_item + 1, D) and t (user preference) (n_user, D); the power law f(d) = a d^b with a, b float64 on the device.  A step of
     one user is a masked all-pairs interaction over the user's whole train sequence (poi_geoie_step); scoring reads the trained_* snapshots
-    taken by update_trained: s[u, k] = t[u].z[k] + m_u.h[k] (poi_geoie_user_vectors + poi_score_all / poi_score_topk at width 2 D).
+    taken by update_trained.  Two score rules: "reference" - GeoIE.py:117-127, s[u, k] = t[u].z[k] + m_u.h[k]
+    (poi_geoie_user_vectors + poi_score_all / poi_score_topk at width 2 D), which drops the power law - and "geo", the rule the step trains:
+    s[u, l] = t[u].z[l] + (1 / L) sum_k m_k (g[k].h[l]) f(d(k, l)) over the user's distinct train POIs (poi_geoie_score_all_geo /
+    poi_geoie_score_topk_geo).  Under "geo" a user is its history, so unseen histories are served too: score_new / recommend_new / rank_new.
 
     train: a CsrTables (PoiDataset.shard(); test is then None) or the reference's [tra_buys_masks, tra_buys_neg_masks, tra_count, tra_masks]
     with test = [tes_buys_masks, tes_buys_neg_masks].  coords (n_item, 2) lat, lon - required (the distances are computed on the device).
     n_hidden = D, a multiple of 4 in [4, 128].  Extra keywords: device, init (dict of float64 arrays g / h / t / z and scalars a / b), seed,
     d_min (km; pairs use max(d, d_min), 0 = the reference), score_norm ("reference": the reference's divisor - the sum of the padded id row -,
-    "count": the sequence length)."""
+    "count": the sequence length; INTEGRATION.md - the "reference" rule only), score_rule ("reference" | "geo": the rule of the scoring
+    methods when they are called without rule=)."""
 
     _near_ok = False
 
     TABLES = ("g", "h", "t", "z")
+    RULES = ("reference", "geo")
 
     def __init__(self, train, test, alpha_lambda, n_user, n_item, n_in, n_hidden, coords=None, device="cuda:0", init=None, seed=None,
-                 d_min=0.0, score_norm="reference"):
+                 d_min=0.0, score_norm="reference", score_rule="reference"):
         self.n_user, self.n_item, self.dim = int(n_user), int(n_item), int(n_hidden)
         if self.dim <= 0 or self.dim % 4 or self.dim > 128:
             raise ValueError("OboGeoIE: n_hidden must be a multiple of 4 in [4, 128] (got %d)" % self.dim)
@@ -2764,9 +2769,11 @@ class OboGeoIE(_Base):
             raise ValueError("OboGeoIE needs coords= (the pair distances are computed on the device from the POI coordinates)")
         if score_norm not in ("reference", "count"):
             raise ValueError("score_norm must be 'reference' or 'count' (got %r)" % (score_norm,))
+        if score_rule not in self.RULES:
+            raise ValueError("score_rule must be 'reference' or 'geo' (got %r)" % (score_rule,))
         if not float(d_min) >= 0.0:
             raise ValueError("d_min must be >= 0")
-        self.d_min, self.score_norm = float(d_min), score_norm
+        self.d_min, self.score_norm, self.score_rule = float(d_min), score_norm, score_rule
         off, p, q, tes = self._host_tables(train, test)
         lens = np.diff(off.astype(np.int64))
         if len(lens) != self.n_user:
@@ -2804,7 +2811,7 @@ class OboGeoIE(_Base):
         self.params = [self.a, self.b]                                                         # :91
         self.l2 = _GeoieL2(self)                                                               # :92-98
         self._trained = {k: getattr(self, k).t.clone() for k in self.TABLES}                  # :81-88 (trained_*)
-        self._uvec = self._items_cat = None
+        self._uvec = self._items_cat = self._geo_train = None
         self.rejected = 0
 
     def _host_tables(self, train, test):
@@ -2874,7 +2881,7 @@ class OboGeoIE(_Base):
         """GeoIE.py:104-112: the scoring snapshots trained_g / _h / _t / _z <- the live tables."""
         for k in self.TABLES:
             self._trained[k].copy_(getattr(self, k).t)
-        self._uvec = self._items_cat = None
+        self._uvec = self._items_cat = self._geo_train = None
 
     # ---- evaluation (GeoIE.py:114-127) --------------------------------------------------------
     @property
@@ -2901,8 +2908,21 @@ class OboGeoIE(_Base):
         ids, lo = self._ids(start_end)
         return ids, self._rows(self._uvec, ids, lo).contiguous(), lo
 
-    def compute_sub_all_scores_device(self, start_end):
-        """GeoIE.py:117-127 -> (n, n_item) device tensor (the dead ulptai distances are not built)."""
+    def _rule(self, rule):
+        rule = self.score_rule if rule is None else rule
+        if rule not in self.RULES:
+            raise ValueError("rule must be 'reference' or 'geo' (got %r)" % (rule,))
+        return rule
+
+    def compute_sub_all_scores(self, start_end, rule=None):
+        return self.compute_sub_all_scores_device(start_end, rule).cpu().numpy()
+
+    def compute_sub_all_scores_device(self, start_end, rule=None):
+        """(n, n_item) device tensor: GeoIE.py:117-127 under "reference" (the dead ulptai distances are not built), the trained rule on the
+        users' train histories and trained_t under "geo"."""
+        if self._rule(rule) == "geo":
+            ids, lo = self._ids(start_end)
+            return self._geo_call(self._geo_train_csr(), ids, self._rows(self._trained["t"], ids, lo).contiguous(), ids.numel())
         ids, users, lo = self._users_rows(start_end)
         n = ids.numel()
         out = torch.empty((n, self.n_item), dtype=torch.float32, device=self.device)
@@ -2910,10 +2930,23 @@ class OboGeoIE(_Base):
                                               _ptr(out), self._stream()))
         return out
 
-    def compute_sub_topk(self, start_end, k, return_scores=False):
-        """Valuate.py:132-146 on the GeoIE scores through the fused top-K kernel: (n, k) int32 ids by descending score."""
+    def compute_sub_topk(self, start_end, k, return_scores=False, rule=None, exclude=None, return_counts=False):
+        """Valuate.py:132-146 on the GeoIE scores through the fused top-K kernels: (n, k) int32 ids by descending score.  Under "geo":
+        exclude = None, "train" (the user's distinct train POIs leave the candidates) or CSR lists (off, ids) as compute_sub_topk_near
+        (k <= 32), -1 / -inf where a row has fewer than k candidates, and with return_counts the candidate count of every row."""
+        rule = self._rule(rule)
+        if rule != "geo" and (exclude is not None or return_counts):
+            raise _lib.PoiError("exclude= / return_counts= belong to the 'geo' rule")
         if k > 32:
-            return self._topk_from_scores(start_end, k, return_scores)
+            if exclude is not None or return_counts:
+                raise _lib.PoiError("exclusion lists and candidate counts need k <= 32 (got %d)" % k)
+            return self._topk_from_scores(start_end, k, return_scores, scores=lambda a: self.compute_sub_all_scores_device(a, rule))
+        if rule == "geo":
+            ids, lo = self._ids(start_end)
+            n = ids.numel()
+            ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+            return self._geo_call(self._geo_train_csr(), ids, self._rows(self._trained["t"], ids, lo).contiguous(), n, int(k), ex, return_scores,
+                                  return_counts)
         ids, users, lo = self._users_rows(start_end)
         n = ids.numel()
         idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
@@ -2921,6 +2954,121 @@ class OboGeoIE(_Base):
         self.ctx.check(self.lib.poi_score_topk(self.ctx.handle, _ptr(users), _ptr(self._items()), n, self.n_item, self.kdim, None, None, int(k),
                                                _ptr(idx), _ptr(sc), self._stream()))
         return (idx, sc) if return_scores else idx
+
+    # ---- the trained rule (poi_geoie_score_all_geo / poi_geoie_score_topk_geo) ---------------------------------------
+    @property
+    def _rank_fused(self):
+        """Under "geo" the score is not users . items: compute_sub_target_rank goes through explicit score rows + poi_rank_scores."""
+        return self.score_rule != "geo"
+
+    def _rank_score_rows(self, a):
+        return self.compute_sub_all_scores_device(a), 1
+
+    def _geo_compact(self, off, p, n, total):
+        """A history CSR -> the compacted CSR of the scoring entries on the device: (off (n + 1), distinct ascending ids, multiplicities)
+        int32, built with torch ops.  The padding id n_item is no check-in and is dropped; any other id outside [0, n_item) is kept as an
+        invalid id, so the kernel rejects that row and no other."""
+        o = off.long()
+        row = torch.repeat_interleave(torch.arange(n, device=self.device), o[1:] - o[:-1])
+        ids = p[:total].long()
+        ids = torch.where((ids < 0) | (ids > self.n_item), torch.full_like(ids, self.n_item + 1), ids)
+        w = self.n_item + 2
+        keys, cnt = torch.unique((row * w + ids)[ids != self.n_item], return_counts=True)      # sorted: by row, then by id
+        co = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        co[1:] = torch.cumsum(torch.bincount(keys // w, minlength=n), 0)
+        pad = lambda t: t.int().contiguous() if t.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)
+        return co.int(), pad(keys % w), pad(cnt)
+
+    def _geo_train_csr(self):
+        """The compacted train histories: built once per snapshot and cached until update_trained."""
+        if self._geo_train is None:
+            self._geo_train = self._geo_compact(self.off, self.p, self.n_user, int(self._off_host[-1]))
+        return self._geo_train
+
+    def _geo_call(self, csr, rows, tu, n, k=None, ex=(None, None), return_scores=False, return_counts=False, sync=True, what="history"):
+        """One launch of the trained rule on rows `rows` (None: all) of a compacted CSR with the user rows tu ((n, D) or None = zero):
+        the (n, n_item) scores, or idx[, scores][, counts] for k."""
+        co, cp, cm = csr
+        P = self._gparams(self._trained)
+        if k is None:
+            out = torch.empty((n, self.n_item), dtype=torch.float32, device=self.device)
+            self.ctx.check(self.lib.poi_geoie_score_all_geo(self.ctx.handle, ctypes.byref(P), _ptr(co), _ptr(cp), _ptr(cm), _ptr(tu), _ptr(rows), n,
+                                                            _ptr(self.coords), _ptr(self._cphi), self.d_min, _ptr(out), self._stream()))
+        else:
+            if not 0 < k <= 32:
+                raise _lib.PoiError("the fused top-K of the 'geo' rule supports 1 <= k <= 32 (got %d)" % k)
+            idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
+            sc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_scores else None
+            cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+            self.ctx.check(self.lib.poi_geoie_score_topk_geo(self.ctx.handle, ctypes.byref(P), _ptr(co), _ptr(cp), _ptr(cm), _ptr(tu), _ptr(rows), n,
+                                                             _ptr(self.coords), _ptr(self._cphi), self.d_min, _ptr(ex[0]), _ptr(ex[1]), k,
+                                                             _ptr(idx), _ptr(sc), _ptr(cnt), self._stream()))
+            out = (idx,) + ((sc,) if return_scores else ()) + ((cnt,) if return_counts else ())
+            out = out if len(out) > 1 else idx
+        if sync:
+            bad = self.ctx.take_bad_ids(self._stream().value)
+            if bad:
+                raise IndexError("%d %s row(s) with an id outside [0, %d) or a malformed exclusion list: NaN scores / empty lists"
+                                 % (bad, what, self.n_item))
+        return out
+
+    # ---- unseen users: t never moves in training, so a GeoIE user is its history ------------------------------------------------------------
+    def _geo_new(self, histories, user_term):
+        off, p, n, total = self._foldin_csr(histories)
+        if n and bool((off[1:] < off[:-1]).any().item()):
+            raise ValueError("histories=(off, p_flat): off must ascend")
+        tu = None
+        if user_term is not None:
+            tu = self._dev(user_term).reshape(-1, self.dim)
+            if tu.shape[0] != n:
+                raise ValueError("user_term must hold one row per history (%d vs %d)" % (tu.shape[0], n))
+        clean = torch.where((p < 0) | (p > self.n_item), torch.full_like(p, self.n_item), p)      # (the exclusion lists skip invalid ids)
+        return self._geo_compact(off, p, n, total), off, clean, n, total, tu
+
+    def score_new(self, histories, user_term=None, sync=True):
+        """(n, n_item) device scores of NEW check-in histories (a list of POI id sequences or a CSR (off, p_flat)) under the trained rule
+        against the trained_* snapshots: no training, no user id.  user_term: None (tu = 0: an unseen user) or (n, D) rows standing in
+        for t[u].  The bits of a history's row do not depend on the other histories of the call.  A device CSR with an id outside
+        [0, n_item] gives a NaN row and - with sync - IndexError."""
+        csr, off, p, n, total, tu = self._geo_new(histories, user_term)
+        return self._geo_call(csr, None, tu, n, sync=sync)
+
+    def recommend_new(self, histories, k, exclude="history", return_scores=False, return_counts=False, user_term=None, sync=True):
+        """Top-k (k <= 32) for NEW histories under the trained rule (poi_geoie_score_topk_geo).  exclude: "history" (each history's distinct
+        POIs leave the candidates), None or a CSR pair (off, ids).  Returns (n, k) int32 ids by descending score, ties by ascending id,
+        -1 where a row has fewer than k candidates[, scores][, candidate counts]."""
+        csr, off, p, n, total, tu = self._geo_new(histories, user_term)
+        ex = self._foldin_exclusion(exclude, off, p, n, total)
+        return self._geo_call(csr, None, tu, n, int(k), ex, return_scores, return_counts, sync)
+
+    def rank_new(self, histories, targets, exclude="history", return_scores=False, return_counts=False, sync=True, user_term=None):
+        """Exact 0-based rank of `targets` ((n, len_t <= 8) POI ids, or a pair (ids, mask)) among all POIs for NEW histories: score rows
+        under the trained rule (at most 1 GiB at a time) + poi_rank_scores.  exclude: "history", None or a CSR pair (off, ids); an
+        excluded target is not ranked (-1); a NaN score counts below every target."""
+        csr, off, p, n, total, tu = self._geo_new(histories, user_term)
+        tgt, tm = self._rank_targets(targets, n)
+        eo, ex = self._foldin_exclusion(exclude, off, p, n, total)
+        lt = tgt.shape[1]
+        rank = torch.empty((n, lt), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, lt), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        step = self._rank_chunk(n)
+        for o in range(0, n, step):
+            c = min(step, n - o)
+            rows = torch.arange(o, o + c, dtype=torch.int32, device=self.device)
+            full = self._geo_call(csr, rows, tu[o:o + c].contiguous() if tu is not None else None, c, sync=sync)
+            eo_c = eo[o:o + c + 1].contiguous() if eo is not None else None
+            r_c = torch.empty((c, lt), dtype=torch.int32, device=self.device)
+            k_c = torch.empty(c, dtype=torch.int32, device=self.device) if cnt is not None else None
+            self.ctx.check(self.lib.poi_rank_scores(self.ctx.handle, _ptr(full), c, self.n_item, _ptr(tgt[o:o + c].contiguous()),
+                                                    _ptr(tm[o:o + c].contiguous()), lt, _ptr(eo_c), _ptr(ex), _ptr(r_c), _ptr(k_c), self._stream()))
+            rank[o:o + c] = r_c
+            if cnt is not None:
+                cnt[o:o + c] = k_c
+            if sc is not None:
+                v = full.gather(1, tgt[o:o + c].long().clamp(0, self.n_item - 1))
+                sc[o:o + c] = torch.where(r_c >= 0, v, torch.full_like(v, float("-inf")))
+        return self._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
 
     def compute_sub_auc_preference(self, start_end):
         """GeoIE.py:114-115 returns zeros: AUC is always 0."""
