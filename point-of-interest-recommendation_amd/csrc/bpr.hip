@@ -22,13 +22,6 @@
 
 namespace poi {
 
-template <int LPT>   // lanes per triple (16 / 32 / 64); float4 per lane per pass
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = LPT / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LPT);
-  return v;
-}
-
 // HOGWILD: in-place.  One pass: 3 rows in, 3 rows out.
 template <int LPT>
 __global__ __launch_bounds__(POI_BLOCK) void bpr_hogwild_kernel(BprArgs A) {
@@ -51,7 +44,7 @@ __global__ __launch_bounds__(POI_BLOCK) void bpr_hogwild_kernel(BprArgs A) {
       const float4 b = *reinterpret_cast<const float4*>(qr + j);
       dot += u.x * (a.x - b.x) + u.y * (a.y - b.y) + u.z * (a.z - b.z) + u.w * (a.w - b.w);
     }
-    dot = group_sum<LPT>(dot);
+    dot = xor_group_sum<LPT>(dot);
     const float g = -sigmoidf_(-dot);
     const float al = A.alpha, lm = A.lambda;
     for (int j = gl * 4; j < D; j += LPT * 4) {
@@ -194,7 +187,7 @@ __global__ __launch_bounds__(256) void bpr_chunk_kernel(BprArgs A) {
             float dot = 0.f;
 #pragma unroll
             for (int t = 0; t < NT; ++t) dot += dot4(ur.v[t], x[u].v[t]);
-            dot = group_sum<LPR>(dot);
+            dot = xor_group_sum<LPR>(dot);
             const bool bad = (unsigned)A.uidx[tri[u]] >= (unsigned)A.n_user || (unsigned)A.p[tri[u]] > (unsigned)A.n_item || (unsigned)A.q[tri[u]] > (unsigned)A.n_item;
             sg[u] = (ok[u] && !bad) ? -sigmoidf_(-dot) : 0.f;      // (a triple with an id outside its table moves nothing)
             if (ok[u] && gl == 0) { A.g[tri[u]] = sg[u]; A.loss[tri[u]] = bad ? __int_as_float(0x7fc00000) : -log_sigmoidf_(dot); }

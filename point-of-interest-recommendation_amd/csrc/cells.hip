@@ -26,10 +26,8 @@ namespace {
 
 constexpr int NT = CELL_NT;
 
-__device__ __forceinline__ double sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
-__device__ __forceinline__ double log_sigmoid_d(double x) { return x >= 0.0 ? -log1p(exp(-x)) : x - log1p(exp(x)); }
-
 // block sum in a fixed order: xor-butterfly inside each wave, the wave sums in wave order.  Contains barriers.
+// (local: NT / 64 waves summed left to right - not the (0 + 1) + (2 + 3) of session_common.h's block_sum_d)
 __device__ __forceinline__ double block_sum_d(double v, double* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -23,16 +23,10 @@ namespace poi {
 
 namespace {
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, false);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ double readlane_d(double v, int l) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
+// DPP + readlane reductions: another summation order (other bits) than the xor-butterfly wave_sum_d of session_common.h
 __device__ __forceinline__ double wave_sum_d(double v) {
   v += dpp_d<0xB1>(v);
   v += dpp_d<0x4E>(v);
@@ -62,8 +56,6 @@ __device__ __forceinline__ double block_max_d(double v, double* red) {
   return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
 }
 
-__device__ __forceinline__ double sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
-__device__ __forceinline__ double log_sigmoid_d(double x) { return x >= 0.0 ? -log1p(exp(-x)) : x - log1p(exp(x)); }
 __device__ __forceinline__ double dot4d(const float4 w, const double* x) {
   return fma((double)w.x, x[0], fma((double)w.y, x[1], fma((double)w.z, x[2], (double)w.w * x[3])));
 }

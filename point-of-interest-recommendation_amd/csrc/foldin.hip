@@ -32,26 +32,6 @@
 
 namespace poi {
 
-namespace {
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-// sum over the 16 lanes of a DPP row, the same bits in every lane of the row (wave_sum's four steps, poi_common.h)
-__device__ __forceinline__ double row_sum(double v) {
-  v += dpp_d<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_d<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dpp_d<0x141>(v);  // row_half_mirror
-  v += dpp_d<0x140>(v);  // row_mirror
-  return v;
-}
-
-}  // namespace
-
 template <int NJ, int K, bool F16>
 __global__ __launch_bounds__(64) void foldin_kernel(FoldinArgs A) {
   using elem_t = typename std::conditional<F16, __half, float>::type;

@@ -37,22 +37,6 @@ namespace poi {
 
 namespace {
 
-template <int CTRL>
-__device__ __forceinline__ double fs_dpp_d(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-// sum over the 16 lanes of a DPP row, the same bits in every lane of the row (foldin.hip's row_sum)
-__device__ __forceinline__ double fs_row_sum(double v) {
-  v += fs_dpp_d<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += fs_dpp_d<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += fs_dpp_d<0x141>(v);  // row_half_mirror
-  v += fs_dpp_d<0x140>(v);  // row_mirror
-  return v;
-}
-
 // cal_dis (Load_Data_prme.py:24-35) in float64 in its operation order: rad(x) = x pi / 180, sin^2 halves, R = 6378.137
 __device__ __forceinline__ double fs_cal_dis(double lat1, double lon1, double lat2, double lon2) {
 #pragma clang fp contract(off)
@@ -118,7 +102,7 @@ __global__ __launch_bounds__(256) void foldin_terms_kernel(FoldinTermsArgs A) {
         s = fma((double)yv.z, (double)yp.z - (double)yq.z, s); s = fma((double)yv.w, (double)yp.w - (double)yq.w, s);
       }
     }
-    s = fs_row_sum(s);
+    s = row_sum(s);
     if (gl == 0) *cdst = PRME ? b * s : s;
   }
 }
@@ -251,7 +235,7 @@ __global__ __launch_bounds__(64) void foldin_pair_kernel(FoldinPairArgs A) {
       for (int c = 0; c < NJ; ++c)
 #pragma unroll
         for (int i = 0; i < 4; ++i) x = METRIC ? fma(d[c][i], 2.0 * w[c][i] - sm[c][i], x) : fma(w[c][i], d[c][i], x);
-      x = fs_row_sum(x);
+      x = row_sum(x);
       x = METRIC ? fma(av, x, cv) : x + cv;
       // e = exp(-|x|):  sigmoid(-x) = x >= 0 ? e / (1 + e) : 1 / (1 + e),  -log sigmoid(x) = max(-x, 0) + log1p(e)
       const double e = exp(-fabs(x));

@@ -135,14 +135,6 @@ hipError_t launch_fpmc_sample(const long long* off, const int* nbr, const int* p
 // ---------------------------------------------------------------------------------------------
 // Step
 // ---------------------------------------------------------------------------------------------
-template <int L>
-__device__ __forceinline__ float fp_group_sum(float v) {
-#pragma unroll
-  for (int o = L / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, L);
-  return v;
-}
-__device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-
 // touch e of 6 n: kind e / n (0 ui[u], 1 ai[a], 2 iu[i], 3 iu[j], 4 ia[i], 5 ia[j]) of transition e % n
 __device__ __forceinline__ const float* fpmc_row(const FpmcArgs& A, int key) {
   const int D = A.dim, R = A.n_item + 1;
@@ -172,7 +164,7 @@ __global__ __launch_bounds__(256) void fpmc_fwd_kernel(FpmcArgs A) {
       const float4 da = sub4(ld4(A.ia + (size_t)i * D + c), ld4(A.ia + (size_t)j * D + c));
       dot += dot4(U, di) + dot4(Aa, da);
     }
-    dot = fp_group_sum<LPT>(dot);
+    dot = xor_group_sum<LPT>(dot);
     if (gl == 0) { A.s[t] = sigmoidf_(-dot); A.loss[t] = log_sigmoidf_(dot); }
     if (gl < 6) {
       const int nu = A.n_user;

@@ -11,51 +11,19 @@
 // coordinates, cos lat and m_k in LDS; a history of at most 64 distinct POIs is staged once per workgroup), and the 16 float64 partial
 // sums meet in an xor butterfly - one fixed order per (history, candidate), whatever the span, the grid or the other rows of the call.
 // Matrix mode writes the score.  Top-K mode (k <= 32) skips a row's excluded ids before the pair math, queues 64 scores per wave and folds
-// a full queue into the wave's sorted best 64 (near.hip's bitonic merge; a queue without an entry above the K-th best is dropped after one
+// a full queue into the wave's sorted best 64 (top64_merge, topk_list.h; a queue without an entry above the K-th best is dropped after one
 // ballot); the four waves' lists meet in LDS and, when a row has several spans, a one-wave kernel per row folds the spans' lists.  The
 // order (descending score, ascending id) is total, so every span size gives the same lists, and the scores are matrix mode's bits.
 // No float atomics; a bad row (offsets, an id outside [0, n_item), ids not strictly ascending, a multiplicity < 1, a malformed exclusion
 // list) gives NaN scores / an empty list and is counted once with one integer atomic.
 #include "geoie_pair.h"
 #include "poi_kernels.h"
+#include "topk_list.h"
 
 namespace poi {
 
 #define GS_NC 16        // candidates per round
 #define GS_KT 64        // history entries per LDS tile
-
-namespace {
-
-constexpr int PAD_ID = 0x7fffffff;      // an empty list entry: sorts behind every POI of the same score
-__device__ __forceinline__ float gs_neg_inf() { return -__builtin_huge_valf(); }
-__device__ __forceinline__ float gs_nan() { return __int_as_float(0x7fc00000); }
-
-// (cs, ci) sorted best-first over the lanes, (ns, ni) in any order -> the best 64 of the 128, sorted
-__device__ __forceinline__ void gs_merge(float& cs, int& ci, float ns, int ni) {
-  wave_sort_desc(ns, ni);
-  const float rs = __shfl(ns, 63 - lane_id(), 64);
-  const int ri = __shfl(ni, 63 - lane_id(), 64);
-  if (better(rs, ri, cs, ci)) { cs = rs; ci = ri; }
-  wave_sort_desc(cs, ci);
-}
-
-// wave 0 of a workgroup: lane l holds entry l of a sorted list
-__device__ __forceinline__ void gs_emit(const GeoScoreArgs& A, int r, int s, float sc, int id, int cnt) {
-  const int lane = lane_id();
-  if (A.n_split > 1) {
-    const size_t at = (size_t)r * A.n_split + s;
-    if (lane < GEO_K_MAX) { A.part_s[at * GEO_K_MAX + lane] = sc; A.part_i[at * GEO_K_MAX + lane] = id; }
-    if (lane == 0) A.part_cnt[at] = cnt;
-    return;
-  }
-  if (lane < A.k) {
-    A.idx_out[(size_t)r * A.k + lane] = id == PAD_ID ? -1 : id;
-    if (A.score_out) A.score_out[(size_t)r * A.k + lane] = id == PAD_ID ? gs_neg_inf() : sc;
-  }
-  if (lane == 0 && A.count_out) A.count_out[r] = cnt;
-}
-
-}  // namespace
 
 template <int MAXD, bool TOPK>
 __global__ __launch_bounds__(256) void geoie_score_kernel(GeoScoreArgs A) {
@@ -90,9 +58,9 @@ __global__ __launch_bounds__(256) void geoie_score_kernel(GeoScoreArgs A) {
   if (__syncthreads_or(bad)) {      // a rejected row: NaN scores / an empty list, counted once
     if (s == 0 && tid == 0) atomicAdd(A.bad, 1);
     if (TOPK) {
-      if (w == 0) gs_emit(A, r, s, gs_neg_inf(), PAD_ID, 0);
+      if (w == 0) list_emit<GEO_K_MAX>(A, A.n_split > 1, r, s, neg_inf(), PAD_ID, 0);
     } else {
-      for (int l = lo + tid; l < hi; l += 256) A.out[(size_t)r * NI + l] = gs_nan();
+      for (int l = lo + tid; l < hi; l += 256) A.out[(size_t)r * NI + l] = quiet_nan();
     }
     return;
   }
@@ -121,7 +89,7 @@ __global__ __launch_bounds__(256) void geoie_score_kernel(GeoScoreArgs A) {
     }
   };
   if (single && nh > 0) stage(0, nh);
-  float cs = gs_neg_inf(), q_s = gs_neg_inf();
+  float cs = neg_inf(), q_s = neg_inf();
   int ci = PAD_ID, q_id = PAD_ID, count = 0;      // the wave's best 64 so far, sorted over its lanes; its queue, one entry per lane
   for (int c0 = lo, round = 0; c0 < hi; c0 += GS_NC, ++round) {
     const int l = c0 + cg;
@@ -187,21 +155,21 @@ __global__ __launch_bounds__(256) void geoie_score_kernel(GeoScoreArgs A) {
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) { sum += __shfl_xor(sum, o, 64); tz += __shfl_xor(tz, o, 64); nn |= __shfl_xor(nn, o, 64); }
     const double v = (double)tz + (nh > 0 ? sum / Ld : 0.0);
-    const float sc = nn ? gs_nan() : (float)v;
+    const float sc = nn ? quiet_nan() : (float)v;
     if (!TOPK) {
       if (l16 == 0 && l < hi) A.out[(size_t)r * NI + l] = sc;
     } else {
-      const bool sel = active && sc > gs_neg_inf();      // NaN and -inf are never selected
+      const bool sel = active && sc > neg_inf();      // NaN and -inf are never selected
       count += sel && l16 == 0;
       // candidate g of this round was summed by lane group g: queue lane 4 (round & 15) + g takes it
-      const float vs = __shfl(sel ? sc : gs_neg_inf(), (lane & 3) << 4, 64);
+      const float vs = __shfl(sel ? sc : neg_inf(), (lane & 3) << 4, 64);
       const int vi = __shfl(sel ? l : PAD_ID, (lane & 3) << 4, 64);
       if ((lane >> 2) == (round & 15)) { q_s = vs; q_id = vi; }
       if ((round & 15) == 15 || c0 + GS_NC >= hi) {
         const float ts = __shfl(cs, A.k - 1, 64);
         const int ti = __shfl(ci, A.k - 1, 64);
-        if (__ballot(q_id != PAD_ID && better(q_s, q_id, ts, ti))) gs_merge(cs, ci, q_s, q_id);
-        q_s = gs_neg_inf(); q_id = PAD_ID;
+        if (__ballot(q_id != PAD_ID && better(q_s, q_id, ts, ti))) top64_merge(cs, ci, q_s, q_id);
+        q_s = neg_inf(); q_id = PAD_ID;
       }
     }
   }
@@ -216,31 +184,31 @@ __global__ __launch_bounds__(256) void geoie_score_kernel(GeoScoreArgs A) {
       float as = m_s[hw][ll], bs = m_s[2 + hw][ll];
       int ai = m_i[hw][ll], bi = m_i[2 + hw][ll];
       wave_sort_desc(as, ai);
-      gs_merge(as, ai, bs, bi);
-      gs_emit(A, r, s, as, ai, (m_cnt[0] + m_cnt[1]) + (m_cnt[2] + m_cnt[3]));
+      top64_merge(as, ai, bs, bi);
+      list_emit<GEO_K_MAX>(A, A.n_split > 1, r, s, as, ai, (m_cnt[0] + m_cnt[1]) + (m_cnt[2] + m_cnt[3]));
     }
   }
 }
 
-// several spans per row: one wave per row folds the row's span lists, two at a time, in span order
+// several spans per row: one wave per row folds the row's span lists, two at a time, in span order (near_merge_kernel's text: see there)
 __global__ __launch_bounds__(64) void geoie_score_merge_kernel(GeoScoreArgs A) {
   const int r = blockIdx.x, lane = lane_id(), S = A.n_split;
   const size_t base = (size_t)r * S;
-  float cs = gs_neg_inf();
+  float cs = neg_inf();
   int ci = PAD_ID, cnt = 0;
   for (int s0 = 0; s0 < S; s0 += 2) {
     const int sl = s0 + (lane >> 5);
     const size_t at = (base + sl) * GEO_K_MAX + (lane & (GEO_K_MAX - 1));
-    const float ns = sl < S ? A.part_s[at] : gs_neg_inf();
+    const float ns = sl < S ? A.part_s[at] : neg_inf();
     const int ni = sl < S ? A.part_i[at] : PAD_ID;
-    gs_merge(cs, ci, ns, ni);
+    top64_merge(cs, ci, ns, ni);
   }
   for (int s = lane; s < S; s += 64) cnt += A.part_cnt[base + s];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
   if (lane < A.k) {
     A.idx_out[(size_t)r * A.k + lane] = ci == PAD_ID ? -1 : ci;
-    if (A.score_out) A.score_out[(size_t)r * A.k + lane] = ci == PAD_ID ? gs_neg_inf() : cs;
+    if (A.score_out) A.score_out[(size_t)r * A.k + lane] = ci == PAD_ID ? neg_inf() : cs;
   }
   if (lane == 0 && A.count_out) A.count_out[r] = cnt;
 }

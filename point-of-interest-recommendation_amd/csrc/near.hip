@@ -13,7 +13,7 @@
 // candidates per lane group in flight, the user row in registers.
 //   score = users[r] . items[j]: per lane an fma chain over its columns in ascending order, then a 16-lane butterfly - one fixed order per
 //   pair, whatever the slice, the wave or the grid - plus wd * sts[r][bin] for bin < n_dist when the row has an anchor.
-// Each wave keeps its best 64 sorted over its lanes (bitonic: sort the batch, keep the better of cur[l] / new[63 - l], sort); a batch
+// Each wave keeps its best 64 sorted over its lanes (top64_merge, topk_list.h: sort the batch, keep the better of cur[l] / new[63 - l], sort); a batch
 // without an entry above the K-th best so far is dropped after one ballot.  The four waves' lists meet in LDS.  Row path: that list is
 // the answer.  Split path: it goes to a (row, slice) partial list and a one-wave merge kernel per row combines the slices.  The order
 // (descending score, ascending id) is total over distinct ids, so the result does not depend on how a band was cut: every grid gives the
@@ -23,13 +23,11 @@
 // row has an anchor, plus ~log2(list) exclusion ids for the positions inside the radius.
 #include "poi_common.h"
 #include "poi_kernels.h"
+#include "topk_list.h"
 
 namespace poi {
 
 namespace {
-
-constexpr int PAD_ID = 0x7fffffff;      // an empty list entry: sorts behind every POI of the same score
-__device__ __forceinline__ float neg_inf() { return -__builtin_huge_valf(); }
 
 // position of the t-th (0-based) set bit of m; m has more than t bits set
 __device__ __forceinline__ int nth_bit(unsigned long long m, int t) {
@@ -40,31 +38,6 @@ __device__ __forceinline__ int nth_bit(unsigned long long m, int t) {
     if (t >= c) { t -= c; pos += w; }
   }
   return pos;
-}
-
-// (cs, ci) sorted best-first over the lanes, (ns, ni) in any order -> the best 64 of the 128, sorted
-__device__ __forceinline__ void top64_merge(float& cs, int& ci, float ns, int ni) {
-  wave_sort_desc(ns, ni);
-  const float rs = __shfl(ns, 63 - lane_id(), 64);
-  const int ri = __shfl(ni, 63 - lane_id(), 64);
-  if (better(rs, ri, cs, ci)) { cs = rs; ci = ri; }
-  wave_sort_desc(cs, ci);
-}
-
-// wave 0 of a workgroup: lane l holds entry l of a sorted list
-__device__ __forceinline__ void near_emit(const NearArgs& A, int r, int s, float sc, int id, int cnt) {
-  const int lane = lane_id();
-  if (A.part_s) {
-    const size_t at = (size_t)r * A.n_split + s;
-    if (lane < NEAR_K_MAX) { A.part_s[at * NEAR_K_MAX + lane] = sc; A.part_i[at * NEAR_K_MAX + lane] = id; }
-    if (lane == 0) A.part_cnt[at] = cnt;
-    return;
-  }
-  if (lane < A.k) {
-    A.idx_out[(size_t)r * A.k + lane] = id == PAD_ID ? -1 : id;
-    if (A.score_out) A.score_out[(size_t)r * A.k + lane] = id == PAD_ID ? neg_inf() : sc;
-  }
-  if (lane == 0 && A.count_out) A.count_out[r] = cnt;
 }
 
 // scores the queue (lane l: candidate q_id, PAD_ID = none; m = entries in use) and folds it into the wave's list
@@ -119,7 +92,7 @@ __global__ __launch_bounds__(256) void near_kernel(NearArgs A) {
     for (int i = e0 + tid; i < e1; i += 256) bad |= (unsigned)A.ex[i] >= (unsigned)N;
   if (__syncthreads_or(bad)) {      // a rejected row: an empty list, counted once
     if (s == 0 && tid == 0) atomicAdd(A.bad, 1);
-    if (w == 0) near_emit(A, r, s, neg_inf(), PAD_ID, 0);
+    if (w == 0) list_emit<NEAR_K_MAX>(A, A.part_s != nullptr, r, s, neg_inf(), PAD_ID, 0);
     return;
   }
   const bool radius = anchor >= 0 && A.c_r < __builtin_huge_val();
@@ -190,11 +163,12 @@ __global__ __launch_bounds__(256) void near_kernel(NearArgs A) {
     int ai = m_i[hw][l], bi = m_i[2 + hw][l];
     wave_sort_desc(as, ai);
     top64_merge(as, ai, bs, bi);
-    near_emit(A, r, s, as, ai, (m_cnt[0] + m_cnt[1]) + (m_cnt[2] + m_cnt[3]));
+    list_emit<NEAR_K_MAX>(A, A.part_s != nullptr, r, s, as, ai, (m_cnt[0] + m_cnt[1]) + (m_cnt[2] + m_cnt[3]));
   }
 }
 
-// split path: one wave per row folds the row's slice lists, two at a time, in slice order
+// split path: one wave per row folds the row's slice lists, two at a time, in slice order.  (geoie_score_merge_kernel has the same text:
+// behind one shared device function the compiler ordered both kernels' instructions differently, so each keeps its own.)
 __global__ __launch_bounds__(64) void near_merge_kernel(NearArgs A) {
   const int r = blockIdx.x, lane = lane_id(), S = A.n_split;
   const size_t base = (size_t)r * S;

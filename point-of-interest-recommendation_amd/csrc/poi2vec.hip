@@ -22,6 +22,8 @@
 // user leaves every other result bitwise equal.
 #include "poi_common.h"
 #include "poi_kernels.h"
+#include "session_common.h"
+#include "topk_list.h"
 
 namespace poi {
 
@@ -29,11 +31,6 @@ namespace poi {
 #define P2V_UC 32          // users per chunk of the dense pass
 #define P2V_SLOTS 256      // dXU partial slots (independent of the launch size: the summation order must not depend on it)
 
-__device__ __forceinline__ double wave_all_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ float wave_all_max_f(float v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -103,7 +100,7 @@ __global__ __launch_bounds__(256) void p2v_lse_kernel(P2vArgs A) {
       float s = 0.f;
       for (int d = 0; d < D; ++d) s = fmaf(tile[d * 65 + i], x[d], s);
       const float m = wave_all_max_f(live ? s : -INFINITY);
-      const double e = wave_all_sum_d(live ? (double)__expf(s - m) : 0.0);
+      const double e = wave_sum_d(live ? (double)__expf(s - m) : 0.0);
       if (i == 0) { A.pmax[(size_t)b * A.n_tile + t] = m; A.psum[(size_t)b * A.n_tile + t] = e; }
     }
   }
@@ -130,16 +127,16 @@ __global__ __launch_bounds__(256) void p2v_pos_kernel(P2vArgs A) {
       if (d0 < D) c0 += (double)A.wl[(size_t)k * D + d0];
       if (d1 < D) c1 += (double)A.wl[(size_t)k * D + d1];
     }
-    const double mean = wave_all_sum_d(c0 + c1) / (double)D;
+    const double mean = wave_sum_d(c0 + c1) / (double)D;
     const double ind = ceil(fabs(mean));
     const float* xr = A.xu + (size_t)u * D;
     const float* wt = A.wl + (size_t)t * D;
-    const double st = wave_all_sum_d((d0 < D ? (double)xr[d0] * (double)wt[d0] : 0.0) + (d1 < D ? (double)xr[d1] * (double)wt[d1] : 0.0));
+    const double st = wave_sum_d((d0 < D ? (double)xr[d0] * (double)wt[d0] : 0.0) + (d1 < D ? (double)xr[d1] * (double)wt[d1] : 0.0));
     const int* rt = A.routes + (size_t)t * R;
     const signed char* lr = A.lrs + (size_t)t * R;
     for (int q = 0; q < R; ++q) {
       const float* pr = A.pb + (size_t)rt[q] * D;
-      const double z = wave_all_sum_d((d0 < D ? (double)pr[d0] * c0 : 0.0) + (d1 < D ? (double)pr[d1] * c1 : 0.0));
+      const double z = wave_sum_d((d0 < D ? (double)pr[d0] * c0 : 0.0) + (d1 < D ? (double)pr[d1] * c1 : 0.0));
       if (lane == 0) s_sg[w][q] = 1.0 / (1.0 + exp(-z * (double)lr[q]));
     }
     __builtin_amdgcn_wave_barrier();
@@ -660,31 +657,6 @@ __global__ __launch_bounds__(256) void p2v_sc_out_kernel(P2vScoreArgs A) {
   }
 }
 
-// merge a wave's 64 (unsorted) new candidates into its LDS list (sorted, best first; entries 0 .. K-1 exact): prme.hip's scheme - the
-// wave sorts only when one candidate beats the list's K-th entry, then the half-cleaner merge of two sorted lists
-__device__ __forceinline__ void p2v_merge(float* ls, int* li, float s, int i, int K) {
-  const int lane = lane_id();
-  const bool cand = better(s, i, ls[K - 1], li[K - 1]);
-  if (!__ballot(cand)) return;
-  if (!cand) { s = -INFINITY; i = 0x7fffffff; }
-  wave_sort_desc(s, i);
-  float rs = __shfl(s, 63 - lane, 64);
-  int ri = __shfl(i, 63 - lane, 64);
-  const float cs = ls[lane];
-  const int ci = li[lane];
-  if (better(cs, ci, rs, ri)) { rs = cs; ri = ci; }      // best 64 of the union: a bitonic sequence
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) {
-    const float ps = __shfl_xor(rs, j, 64);
-    const int pi = __shfl_xor(ri, j, 64);
-    const bool mine = better(rs, ri, ps, pi);
-    if (((lane & j) == 0) != mine) { rs = ps; ri = pi; }
-  }
-  __builtin_amdgcn_wave_barrier();
-  ls[lane] = rs; li[lane] = ri;
-  __builtin_amdgcn_wave_barrier();
-}
-
 // fused top-K (K <= 64): a workgroup per row computes the scores of its POIs on the fly - the row of scores is never stored - and each
 // wave keeps a sorted 64-entry list in LDS; the 4 lists are merged at the end.  Order: higher score, then lower id; a NaN score ranks
 // as -inf (last) and is reported as NaN.
@@ -694,13 +666,13 @@ __global__ __launch_bounds__(256) void p2v_sc_topk_kernel(P2vScoreArgs A) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int r = blockIdx.x; r < A.n_rows; r += gridDim.x) {
     __syncthreads();
-    s_ls[w][lane] = -INFINITY; s_li[w][lane] = 0x7fffffff;
+    s_ls[w][lane] = -INFINITY; s_li[w][lane] = PAD_ID;
     __builtin_amdgcn_wave_barrier();
     for (int j0 = 0; j0 < A.n_item; j0 += 256) {              // (wave-uniform trip count)
       const int j = j0 + threadIdx.x;
       float s = -INFINITY;
       if (j < A.n_item) { s = p2v_score(A, r, j); if (!(s == s)) s = -INFINITY; }
-      p2v_merge(s_ls[w], s_li[w], s, j < A.n_item ? j : 0x7fffffff, A.k);
+      lds_list_merge(s_ls[w], s_li[w], s, j < A.n_item ? j : PAD_ID, A.k);
     }
     __syncthreads();
     if (w == 0) {
@@ -721,7 +693,7 @@ __global__ __launch_bounds__(256) void p2v_sc_topk_kernel(P2vScoreArgs A) {
       }
       if (lane < A.k) {
         const size_t o = (size_t)r * A.k + lane;
-        const bool ok = i != 0x7fffffff;
+        const bool ok = i != PAD_ID;
         A.idx_out[o] = ok ? i : -1;
         if (A.score_out) A.score_out[o] = ok ? p2v_score(A, r, i) : __int_as_float(0x7fc00000);
       }

@@ -46,6 +46,48 @@ __device__ __forceinline__ float wave_sum_shfl(float v) {
   return v;
 }
 
+// One DPP step on a double (both halves moved by the same control).
+template <int CTRL>
+__device__ __forceinline__ double dpp_d(double v) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+// sum over the 16 lanes of a DPP row, the same bits in every lane of the row (wave_sum's four steps)
+__device__ __forceinline__ double row_sum(double v) {
+  v += dpp_d<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += dpp_d<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += dpp_d<0x141>(v);  // row_half_mirror
+  v += dpp_d<0x140>(v);  // row_mirror
+  return v;
+}
+// xor-butterfly sum over groups of L adjacent lanes (16 / 32 / 64), in every lane.  (tile_engine.hip's group_sum<N> is the DPP form: another order.)
+template <int L>
+__device__ __forceinline__ float xor_group_sum(float v) {
+#pragma unroll
+  for (int o = L / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, L);
+  return v;
+}
+
+// Orders this wavefront's LDS traffic only (LDS is in-order per wave; the waitcnt makes returned data
+// available, the clobber stops compiler reordering).  Deliberately NOT a memory fence: a wavefront-
+// scope __builtin_amdgcn_fence also drains vmcnt, i.e. waits for every outstanding global load /
+// atomic (the bounds score_topk.hip publishes), which costs microseconds per compaction.
+__device__ __forceinline__ void wave_fence() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also carries a release fence that
+// waits for every outstanding GLOBAL access of the wave (vmcnt(0)) - microseconds per barrier in loops
+// where global results are consumed only by later kernels (or loads are requested iterations ahead) and
+// just LDS tiles cross waves.  (Loads feeding ds_write are still waited for by the data dependence.)
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
 // Block-wide (256 threads) reductions; `red` is an LDS array of >= POI_NWAVE floats.  Contains barriers.
 __device__ __forceinline__ float block_sum(float v, float* red) {
   v = wave_sum(v);
@@ -116,6 +158,13 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __ex
 __device__ __forceinline__ float log_sigmoidf_(float x) {
   return x >= 0.f ? -log1pf(expf(-x)) : x - log1pf(expf(x));
 }
+
+__device__ __forceinline__ double sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
+__device__ __forceinline__ double log_sigmoid_d(double x) { return x >= 0.0 ? -log1p(exp(-x)) : x - log1p(exp(x)); }
+__device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+// what a rejected row is filled with / the score of an empty list entry
+__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
+__device__ __forceinline__ float neg_inf() { return -__builtin_huge_valf(); }
 
 // Row-parallel GEMV: out[r] = act(W1[r,:K1].x1 + W2[r,:K2].x2 + bias[r]) for r in [0, nrows).
 // One wavefront per row (4 rows in flight per wave), lanes stride the row in float4 (coalesced
@@ -237,7 +286,14 @@ __device__ __forceinline__ bool better(float s, int i, float ps, int pi) {
   return (s > ps) || (s == ps && i < pi);
 }
 
-// Order-mapped bound (score_topk.hip f2ord: larger float <=> larger uint) one step BELOW the order-mapped score o, for consumers that keep
+// Order-preserving map float -> uint (larger float <=> larger uint) and back.
+__device__ __forceinline__ unsigned f2ord(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
+
+// Order-mapped bound (f2ord) one step BELOW the order-mapped score o, for consumers that keep
 // `score > bound`: a score equal to the K-th best still passes.  One step below +0.0 is -0.0, which COMPARES EQUAL to +0.0 - a bound
 // published from a K-th best of zero dropped every tie at zero in the other item ranges - so a step that lands on a zero or a subnormal
 // (which a flushing compare would treat as zero) goes on to -FLT_MIN: any lower value is still a bound.  Callers check o > 1.

@@ -24,17 +24,10 @@
 // lists); at the end the block's 4 lists of a row are merged the same way.
 #include "poi_common.h"
 #include "poi_kernels.h"
-#include <limits.h>
+#include "topk_list.h"
 
 namespace poi {
 
-template <int L>
-__device__ __forceinline__ float pr_group_sum(float v) {
-#pragma unroll
-  for (int o = L / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, L);
-  return v;
-}
-__device__ __forceinline__ float4 pr_sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ float pr_sq4(float4 a, float4 b, float acc) {
   const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z, w = a.w - b.w;
   return fmaf(w, w, fmaf(z, z, fmaf(y, y, fmaf(x, x, acc))));
@@ -73,7 +66,7 @@ __global__ __launch_bounds__(256) void prme_fwd_kernel(PrmeArgs A) {
       const float4 Sp = ld4(A.ds + (size_t)p * D + c), Sq = ld4(A.ds + (size_t)q * D + c), Sv = ld4(A.ds + (size_t)pv * D + c);
       dpp = pr_sq4(U, Pp, dpp); dpq = pr_sq4(U, Pq, dpq); dsp = pr_sq4(Sp, Sv, dsp); dsq = pr_sq4(Sq, Sv, dsq);
     }
-    dpp = pr_group_sum<LPT>(dpp); dpq = pr_group_sum<LPT>(dpq); dsp = pr_group_sum<LPT>(dsp); dsq = pr_group_sum<LPT>(dsq);
+    dpp = xor_group_sum<LPT>(dpp); dpq = xor_group_sum<LPT>(dpq); dsp = xor_group_sum<LPT>(dsp); dsq = xor_group_sum<LPT>(dsq);
     const float x = (a * dpq + b * dsq) - (a * dpp + b * dsp);
     if (gl == 0) {
       const float g = sigmoidf_(-x);
@@ -98,16 +91,16 @@ __device__ __forceinline__ float4 prme_grad(const PrmeArgs& A, int e, int col) {
   if (kind <= 2) {
     s = A.ga[t];
     const float4 U = ld4(A.du + (size_t)A.u[t] * D + col);
-    if (kind == 0) v = pr_sub4(ld4(A.dp + (size_t)A.p[t] * D + col), ld4(A.dp + (size_t)A.q[t] * D + col));
-    else if (kind == 1) v = pr_sub4(U, ld4(A.dp + (size_t)A.p[t] * D + col));
-    else v = pr_sub4(ld4(A.dp + (size_t)A.q[t] * D + col), U);
+    if (kind == 0) v = sub4(ld4(A.dp + (size_t)A.p[t] * D + col), ld4(A.dp + (size_t)A.q[t] * D + col));
+    else if (kind == 1) v = sub4(U, ld4(A.dp + (size_t)A.p[t] * D + col));
+    else v = sub4(ld4(A.dp + (size_t)A.q[t] * D + col), U);
   } else {
     s = A.gb[t];
     const float4 Sp = ld4(A.ds + (size_t)A.p[t] * D + col), Sq = ld4(A.ds + (size_t)A.q[t] * D + col);
-    if (kind == 6) v = pr_sub4(Sp, Sq);
+    if (kind == 6) v = sub4(Sp, Sq);
     else {
       const float4 Sv = ld4(A.ds + (size_t)A.prev[t] * D + col);
-      v = kind == 4 ? pr_sub4(Sv, Sp) : pr_sub4(Sq, Sv);
+      v = kind == 4 ? sub4(Sv, Sp) : sub4(Sq, Sv);
     }
   }
   return make_float4(s * v.x, s * v.y, s * v.z, s * v.w);
@@ -267,30 +260,6 @@ __device__ __forceinline__ double pr_weight(double rl1, double ro1, double cl1, 
   return sqrt(sqrt(1 + s));
 }
 
-// merge a wave's 64 (unsorted) new candidates of one row into the row's LDS list (sorted, best first; entries 0 .. K-1 exact)
-__device__ __forceinline__ void pr_merge(float* ls, int* li, float s, int i, int K) {
-  const int lane = lane_id();
-  const bool cand = better(s, i, ls[K - 1], li[K - 1]);
-  if (!__ballot(cand)) return;
-  if (!cand) { s = -INFINITY; i = INT_MAX; }
-  wave_sort_desc(s, i);
-  float rs = __shfl(s, 63 - lane, 64);
-  int ri = __shfl(i, 63 - lane, 64);
-  const float cs = ls[lane];
-  const int ci = li[lane];
-  if (better(cs, ci, rs, ri)) { rs = cs; ri = ci; }      // best 64 of the union: a bitonic sequence
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) {
-    const float ps = __shfl_xor(rs, j, 64);
-    const int pi = __shfl_xor(ri, j, 64);
-    const bool mine = better(rs, ri, ps, pi);
-    if (((lane & j) == 0) != mine) { rs = ps; ri = pi; }
-  }
-  __builtin_amdgcn_wave_barrier();
-  ls[lane] = rs; li[lane] = ri;
-  __builtin_amdgcn_wave_barrier();
-}
-
 template <bool TOPK>
 __global__ __launch_bounds__(256) void prme_score_kernel(PrmeScoreArgs A) {
   __shared__ __align__(16) float s_u[PS_ROWS][PS_MAXD], s_s[PS_ROWS][PS_MAXD];
@@ -323,7 +292,7 @@ __global__ __launch_bounds__(256) void prme_score_kernel(PrmeScoreArgs A) {
     s_u[r][c] = vu; s_s[r][c] = vs;
   }
   if (TOPK) {
-    for (int x = tid; x < 4 * PS_ROWS * 64; x += 256) { (&s_ls[0][0][0])[x] = -INFINITY; (&s_li[0][0][0])[x] = INT_MAX; }
+    for (int x = tid; x < 4 * PS_ROWS * 64; x += 256) { (&s_ls[0][0][0])[x] = -INFINITY; (&s_li[0][0][0])[x] = PAD_ID; }
   }
   __syncthreads();
   const float cw = A.cw, cw1 = 1.f - A.cw;
@@ -354,7 +323,7 @@ __global__ __launch_bounds__(256) void prme_score_kernel(PrmeScoreArgs A) {
       if (!TOPK) {
         if (valid) A.out[(size_t)(row0 + r) * N + j] = sc;
       } else {
-        pr_merge(s_ls[w][r], s_li[w][r], valid && s_ok[r] ? sc : -INFINITY, valid && s_ok[r] ? j : INT_MAX, A.k);
+        lds_list_merge(s_ls[w][r], s_li[w][r], valid && s_ok[r] ? sc : -INFINITY, valid && s_ok[r] ? j : PAD_ID, A.k);
       }
     }
   }

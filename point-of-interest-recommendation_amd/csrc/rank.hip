@@ -35,12 +35,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// orders this wavefront's LDS traffic (as score_topk.hip: not a memory fence)
-__device__ __forceinline__ void wave_fence() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // row `row` of a (rows, D) table in fragment order: lane half h holds the k-columns 8m + 4h .. 8m + 4h + 3, one float4 per m
 template <int D8>
 __device__ __forceinline__ void load_frag(float4 (&f)[D8], const void* base, int f16, size_t row, int D, int h) {

@@ -28,9 +28,6 @@ namespace poi {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ float sf_ord2f(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
-__device__ __forceinline__ unsigned sf_f2ord(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-
 // Items -> IEEE half in the fragment order of v_mfma_f32_32x32x16_f16 + the two norms of the bound.
 //   P[(tile * KG + m) * 64 + lane] = 8 halfs items[32 tile + j][16 m + 8 h + e], e = 0..7, lane = 32 h + j        (KG = D / 16)
 //   inorm[item] = { |v|_2 (rounded up), 2^-25 * 1.01 * |v|_1 }; an item with a value outside the half range gets |v|_2 = +inf
@@ -149,7 +146,7 @@ __global__ __launch_bounds__(256, ((BINS == 3 || UT == 2) ? 2 : 3)) void score_f
     float pmax = 0.f;
     if (BINS) for (int b = 0; b < NB; ++b) pmax = fmaxf(pmax, fabsf(sts[tt * NB + b]));
     const unsigned g = urow < A.n ? A.gbound[urow] : 0u;
-    const float thr = g ? sf_ord2f(g) : -INFINITY;
+    const float thr = g ? ord2f(g) : -INFINITY;
     const float nu2 = sqrtf(n2_of(u)[tt]) * 1.000002f;
     constexpr float c1 = (9.765625e-4f * 1.0005f + (float)D * (2.38418579e-7f * 1.001f + 1.19209290e-7f) + 4.76837158e-7f) * 1.00001f;
     const float bu = n1_of(u)[tt] * (2.98023224e-8f * 1.01f) + 4.76837158e-7f * (fabsf(wd) * pmax + (g ? fabsf(thr) : 0.f)) + 1e-30f;
@@ -364,7 +361,7 @@ __global__ __launch_bounds__(256) void sf_select_kernel(ScoreArgs A, int k) {
   const float slack = 2.f * (n1 * (2.98023224e-8f * 1.01f) + 4.76837158e-7f * (fabsf(wd) * pmax + fabsf(kth))) + 1e-30f;
   const float thr = kth - slack;
   if (lane == 0 && thr > -INFINITY) {
-    const unsigned o = sf_f2ord(thr);
+    const unsigned o = f2ord(thr);
     if (o > 1u && tie_bound_below(o) > A.gbound[u]) A.gbound[u] = tie_bound_below(o);
   }
 }
@@ -414,7 +411,7 @@ __global__ __launch_bounds__(256) void sf_users_prep_kernel(ScoreArgs A, uint4* 
     float pmax = 0.f, mx = 0.f;
     for (int b = 0; b < NB; ++b) { const float p = srow[b]; pmax = fmaxf(pmax, fabsf(p)); mx = fmaxf(mx, wd * p); }
     const unsigned g = urow < A.n ? A.gbound[urow] : 0u;
-    const float thr = g ? sf_ord2f(g) : -INFINITY;
+    const float thr = g ? ord2f(g) : -INFINITY;
     const float nu2 = sqrtf(s_n2[t]) * 1.000002f;
     constexpr float c1 = (9.765625e-4f * 1.0005f + (float)D * (2.38418579e-7f * 1.001f + 1.19209290e-7f) + 4.76837158e-7f) * 1.00001f;
     const float bu = s_n1[t] * (2.98023224e-8f * 1.01f) + 4.76837158e-7f * (fabsf(wd) * pmax + (g ? fabsf(thr) : 0.f)) + 1e-30f;
@@ -432,15 +429,8 @@ __global__ __launch_bounds__(256) void sf_users_prep_kernel(ScoreArgs A, uint4* 
   if (t < 64 && __any(unseeded) && t == 0) A.tile_flag[ut] = 1;      // an unseeded user: the whole tile goes to the one-stage kernel
 }
 
-// Workgroup barrier that orders LDS traffic only (tile_engine.hip's lds_barrier): __syncthreads() also waits for every outstanding GLOBAL
-// load of the wave (vmcnt(0)) - here the user tile requested two iterations ahead, i.e. a full L2 round trip per iteration: 2.7 us per
-// 32 x 32 x 256 tile product instead of 0.5.
-__device__ __forceinline__ void sf_lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
+// The barriers of the loop are lds_barrier() (poi_common.h): __syncthreads() would also wait for the user tile requested two iterations
+// ahead, i.e. a full L2 round trip per iteration: 2.7 us per 32 x 32 x 256 tile product instead of 0.5.
 template <int D>
 __global__ __launch_bounds__(256, 2) void score_filter_items_kernel(ScoreArgs A, const uint4* __restrict__ upk, const float4* __restrict__ ub,
                                                                     const double* __restrict__ ugeo, int n_utile) {
@@ -458,7 +448,7 @@ __global__ __launch_bounds__(256, 2) void score_filter_items_kernel(ScoreArgs A,
   const float wd = A.wd ? A.wd[0] : 0.f;
   const float gscale = (float)(12742.0 * 1000.0 / A.dd);
   for (int i = t; i < A.n_dist; i += 256) s_geo[i] = A.thr[i];
-  // the next user tile is requested while the current one is multiplied (one register set; the barriers do not wait for it: sf_lds_barrier)
+  // the next user tile is requested while the current one is multiplied (one register set; the barriers do not wait for it: lds_barrier)
   // (native vector types: an array of HIP's uint4 struct captured by the lambdas stayed in scratch memory - a store, a vmcnt(0) and a
   // reload per iteration)
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -561,12 +551,13 @@ __global__ __launch_bounds__(256, 2) void score_filter_items_kernel(ScoreArgs A,
         }
       }
       put(buf ^ 1);
-      sf_lds_barrier();
+      lds_barrier();
     }
   }
 }
 
-// 64-lane bitonic sort, best (highest score, then lowest id) first - as score_topk.hip's merge
+// 64-lane bitonic sort, best (highest score, then lowest id) first: wave_sort_desc (poi_common.h) with better() written out.  Kept apart:
+// in score_rescore_kernel the compiler turns the two spellings into different code (this one keeps branches the shared one if-converts).
 __device__ __forceinline__ void sf_wave_sort_desc(float& s, int& idx) {
   const int lane = lane_id();
 #pragma unroll
@@ -843,7 +834,7 @@ __global__ __launch_bounds__(256) void topk_bound_kernel(const float* __restrict
   if (u >= n) return;
   const float s = score_k[(size_t)u * k + (k - 1)];
   if (!(s > -INFINITY)) return;                 // fewer than K items in the subset (or NaN): no bound
-  const unsigned o = sf_f2ord(s);
+  const unsigned o = f2ord(s);
   if (o > 1u && tie_bound_below(o) > gbound[u]) gbound[u] = tie_bound_below(o);      // (never -0.0: a flagged tile's one-stage kernel compares `score > bound`)
 }
 hipError_t launch_topk_bound(const float* score_k, int n, int k, unsigned* gbound, hipStream_t st) {

@@ -23,7 +23,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define TK_CAP 80   // candidate slots per user per wave (>= K + 32; compaction when cnt > TK_CAP - 32).
                     // 4 waves x 32 users x 80 x 6 B = 61 KB per workgroup (+ 16 KB of A fragments: two workgroups per CU)
 
-// better() / wave_sort_desc(): poi_common.h (shared with prme.hip)
+// better() / wave_sort_desc() / wave_fence() / f2ord() / ord2f(): poi_common.h
 
 struct WaveTopk {   // LDS state of one wavefront
   float cs[32][TK_CAP];
@@ -34,21 +34,6 @@ struct WaveTopk {   // LDS state of one wavefront
   unsigned gtmp[32];    // staging of a bound refresh
 };
 
-// Orders this wavefront's LDS traffic only (LDS is in-order per wave; the waitcnt makes returned data
-// available, the clobber stops compiler reordering).  Deliberately NOT a memory fence: a wavefront-
-// scope __builtin_amdgcn_fence also drains vmcnt, i.e. waits for every outstanding global load /
-// atomic (the published bounds below), which costs microseconds per compaction.
-__device__ __forceinline__ void wave_fence() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// Order-preserving map float -> uint (larger float <=> larger uint).
-__device__ __forceinline__ unsigned f2ord(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
 __device__ __forceinline__ int popc64(unsigned long long m) { return __builtin_popcountll(m); }
 
 // Keep the best K of user i's (unsorted, <= 128 entries) candidate list and raise its threshold to the

@@ -21,63 +21,14 @@
 // such a batch into successive calls (models.Session.advance does).
 #include "poi_common.h"
 #include "poi_kernels.h"
+#include "session_common.h"
 
 namespace poi {
 
 namespace {
 
-constexpr int RS = 17;      // LDS row stride of the k-major tiles (16 events + 1: the transposing copies stay conflict-free)
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double sess_sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }
-__device__ __forceinline__ float sess_nan() { return __int_as_float(0x7fc00000); }
 __device__ __forceinline__ float ld_tab(const void* base, size_t off, int f16) {
   return f16 ? __half2float(reinterpret_cast<const __half*>(base)[off]) : reinterpret_cast<const float*>(base)[off];
-}
-__device__ __forceinline__ int swz(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
-
-// data.dist_pos_bins: bin(coords[cur], coords[prev]) through the exact thresholds (the expression order of neg_dist_kernel)
-__device__ __forceinline__ int sess_bin(const SessArgs& A, int cur, int prev) {
-#pragma clang fp contract(off)
-  const double pr = 0.017453292519943295;
-  const double a = (A.coords[2 * cur] - A.coords[2 * prev]) * pr;
-  const double b = (A.coords[2 * cur + 1] - A.coords[2 * prev + 1]) * pr;
-  const double c = (1.0 - cos_small(a)) / 2 + A.cphi[cur] * A.cphi[prev] * (1.0 - cos_small(b)) / 2;
-  return bin_of_c(c, A.thr, A.n_dist, (float)(12742.0 * 1000.0 / A.dd));
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// block reductions of a 256-thread workgroup in a fixed order.  Contain barriers; `red` holds 4 doubles.
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if (lane_id() == 0) red[wave_id()] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ double block_max_d(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if (lane_id() == 0) red[wave_id()] = v;
-  __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-
-// this lane's share of w[0 .. K) . x (x: LDS doubles); the lanes stride the row in float4
-__device__ __forceinline__ double row_part(const float* __restrict__ w, int K, const double* x, int lane) {
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  for (int j = lane * 4; j < K; j += 256) {
-    const float4 v = ld4(w + j);
-    a0 = fma((double)v.x, x[j], a0); a1 = fma((double)v.y, x[j + 1], a1);
-    a2 = fma((double)v.z, x[j + 2], a2); a3 = fma((double)v.w, x[j + 3], a3);
-  }
-  return (a0 + a1) + (a2 + a3);
 }
 
 // softmax(vs . hs + bs) of one event by the whole workgroup: float32 rows to st (state, may be null) and out (may be null)
@@ -143,8 +94,8 @@ __global__ __launch_bounds__(256) void sess_event_kernel(SessArgs A) {
     }
     if (__syncthreads_or(bad)) {
       if (tid == 0) atomicAdd(A.bad, 1);
-      if (A.hts_out) for (int u = tid; u < D; u += 256) A.hts_out[(size_t)e * D + u] = sess_nan();
-      if (A.sts_out && A.spatial) for (int b = tid; b < NB; b += 256) A.sts_out[(size_t)e * NB + b] = sess_nan();
+      if (A.hts_out) for (int u = tid; u < D; u += 256) A.hts_out[(size_t)e * D + u] = quiet_nan();
+      if (A.sts_out && A.spatial) for (int b = tid; b < NB; b += 256) A.sts_out[(size_t)e * NB + b] = quiet_nan();
       continue;
     }
     double* hrow = A.h + (size_t)s * D;
@@ -156,7 +107,7 @@ __global__ __launch_bounds__(256) void sess_event_kernel(SessArgs A) {
       continue;
     }
     int d = A.n_dist;
-    if (A.spatial) { const int lp = A.last_poi[s]; if (lp >= 0) d = sess_bin(A, j, lp); }
+    if (A.spatial) { const int lp = A.last_poi[s]; if (lp >= 0) d = pos_bin(A, j, lp); }
     for (int u = tid; u < D; u += 256) {
       xs[u] = (double)ld_tab(A.lt, (size_t)j * D + u, A.lt_f16);
       if (A.spatial) xs[D + u] = (double)A.di[(size_t)d * D + u];
@@ -172,7 +123,7 @@ __global__ __launch_bounds__(256) void sess_event_kernel(SessArgs A) {
         const double a = wave_sum_d(acc[u]);
         const int o = o0 + u;
         if (lane == 0) {
-          const double v = sess_sigmoid(a + (double)A.bi[o]);
+          const double v = sigmoid_d(a + (double)A.bi[o]);
           if (o < D) zs[o] = v; else rh[o - D] = v * hs[o - D];
         }
       }
@@ -207,6 +158,7 @@ __global__ __launch_bounds__(256) void sess_event_kernel(SessArgs A) {
 // ---- tile path: 16 events per workgroup, float64 MFMA ---------------------------------------------------------------------------------
 namespace {
 // acc[q] += W_q[16 rows][K] . S[K][16 events]: wrow[q] = this lane's row of W_q at column 4 g; S k-major in LDS at the swizzled rows
+// (not merged with session_cells.hip's sc_mma, which prefetches the next k-block: unifying them would change one kernel's schedule)
 template <int NG, class T>
 __device__ __forceinline__ void sess_mma(f64x4 (&acc)[NG], const float* const (&wrow)[NG], int K, const T* sT, int i, int g) {
   for (int kq = 0; kq < (K >> 4); ++kq) {
@@ -253,7 +205,7 @@ __global__ __launch_bounds__(256) void sess_tile_kernel(SessArgs A, int r0_bytes
       if (bad) atomicAdd(A.bad, 1);
       else {
         ok = 1;
-        if (A.spatial) { const int lp = A.last_poi[s]; if (lp >= 0) d = sess_bin(A, j, lp); }
+        if (A.spatial) { const int lp = A.last_poi[s]; if (lp >= 0) d = pos_bin(A, j, lp); }
       }
     }
     s_slot[tid] = s; s_poi[tid] = j; s_d[tid] = d; s_ok[tid] = ok;
@@ -282,8 +234,8 @@ __global__ __launch_bounds__(256) void sess_tile_kernel(SessArgs A, int r0_bytes
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int unit = 16 * ut + g + 4 * r, at = swz(unit) * RS + i;
-        zr[t][r] = sess_sigmoid(acc[0][r] + (double)A.bi[unit]);
-        rhT[at] = sess_sigmoid(acc[1][r] + (double)A.bi[D + unit]) * hT[at];
+        zr[t][r] = sigmoid_d(acc[0][r] + (double)A.bi[unit]);
+        rhT[at] = sigmoid_d(acc[1][r] + (double)A.bi[D + unit]) * hT[at];
       }
     }
   }
@@ -312,7 +264,7 @@ __global__ __launch_bounds__(256) void sess_tile_kernel(SessArgs A, int r0_bytes
     if (e0 + e >= A.n) break;
     const double v = hT[swz(u) * RS + e];
     if (s_ok[e]) A.h[(size_t)s_slot[e] * D + u] = v;
-    if (A.hts_out) A.hts_out[(size_t)(e0 + e) * D + u] = s_ok[e] ? (float)v : sess_nan();
+    if (A.hts_out) A.hts_out[(size_t)(e0 + e) * D + u] = s_ok[e] ? (float)v : quiet_nan();
   }
   if (tid < 16 && s_ok[tid]) { A.last_poi[s_slot[tid]] = s_poi[tid]; A.steps[s_slot[tid]] += 1; }
   if (!A.spatial) return;
@@ -343,7 +295,7 @@ __global__ __launch_bounds__(256) void sess_tile_kernel(SessArgs A, int r0_bytes
       float* st = ok ? A.sts + (size_t)s_slot[e] * NB : nullptr;
       float* out = A.sts_out ? A.sts_out + (size_t)(e0 + e) * NB : nullptr;
       for (int b = q; b < NB; b += 16) {
-        const float v = ok ? (float)(exp(lg[b * RS + e] - m) / s) : sess_nan();
+        const float v = ok ? (float)(exp(lg[b * RS + e] - m) / s) : quiet_nan();
         if (st) st[b] = v;
         if (out) out[b] = v;
       }

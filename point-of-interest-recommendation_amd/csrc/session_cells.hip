@@ -20,54 +20,13 @@
 // Bad ids and repeated slots behave as in poi_session_advance: slot untouched, NaN hts_out row, counted (poi_ctx_take_bad_ids).
 #include "poi_common.h"
 #include "poi_kernels.h"
+#include "session_common.h"
 
 namespace poi {
 
 namespace {
 
-constexpr int RS = 17;      // LDS row stride of the k-major tiles (16 events + 1)
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double sc_sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }
-__device__ __forceinline__ float sc_nan() { return __int_as_float(0x7fc00000); }
-__device__ __forceinline__ int swz(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
-
-// data.dist_pos_bins: bin(coords[cur], coords[prev]) through the exact thresholds (sess_bin's expression)
-__device__ __forceinline__ int sc_bin(const SessCellArgs& A, int cur, int prev) {
-#pragma clang fp contract(off)
-  const double pr = 0.017453292519943295;
-  const double a = (A.coords[2 * cur] - A.coords[2 * prev]) * pr;
-  const double b = (A.coords[2 * cur + 1] - A.coords[2 * prev + 1]) * pr;
-  const double c = (1.0 - cos_small(a)) / 2 + A.cphi[cur] * A.cphi[prev] * (1.0 - cos_small(b)) / 2;
-  return bin_of_c(c, A.thr, A.n_dist, (float)(12742.0 * 1000.0 / A.dd));
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// block sum of a 256-thread workgroup in a fixed order.  Contains barriers; `red` holds 4 doubles.
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if (lane_id() == 0) red[wave_id()] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// this lane's share of w[0 .. K) . x (x: LDS doubles); the lanes stride the row in float4 (K % 4 == 0)
-__device__ __forceinline__ double row_part(const float* __restrict__ w, int K, const double* x, int lane) {
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  for (int j = lane * 4; j < K; j += 256) {
-    const float4 v = ld4(w + j);
-    a0 = fma((double)v.x, x[j], a0); a1 = fma((double)v.y, x[j + 1], a1);
-    a2 = fma((double)v.z, x[j + 2], a2); a3 = fma((double)v.w, x[j + 3], a3);
-  }
-  return (a0 + a1) + (a2 + a3);
-}
-// this lane's share of sum(w[0 .. K)), the same walk
+// this lane's share of sum(w[0 .. K)): row_part's walk
 __device__ __forceinline__ double row_sum_part(const float* __restrict__ w, int K, int lane) {
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
   for (int j = lane * 4; j < K; j += 256) {
@@ -78,7 +37,7 @@ __device__ __forceinline__ double row_sum_part(const float* __restrict__ w, int 
 }
 
 // acc[q] += W_q[16 rows][K] . S[K][16 events]: wrow[q] = this lane's row of W_q at column 4 g; S k-major in LDS at the swizzled rows
-// (sess_mma of session.hip: MFMA j of k-block kq contracts k = 16 kq + 4 g + j, stored at row swz(k) = 16 kq + 4 j + g)
+// (rows swz(k), session_common.h).  Not session.hip's sess_mma: this one keeps the next k-block's weights in flight - another schedule.
 template <int NG, class T>
 __device__ __forceinline__ void sc_mma(f64x4 (&acc)[NG], const float* (&wrow)[NG], int K, const T* sT, int i, int g) {
   const int nk = K >> 4;
@@ -140,13 +99,13 @@ __global__ __launch_bounds__(256) void sc_event_kernel(SessCellArgs A) {
     }
     if (__syncthreads_or(bad)) {
       if (tid == 0) atomicAdd(A.bad, 1);
-      if (A.hts_out) for (int u = tid; u < D; u += 256) A.hts_out[(size_t)e * D + u] = sc_nan();
+      if (A.hts_out) for (int u = tid; u < D; u += 256) A.hts_out[(size_t)e * D + u] = quiet_nan();
       continue;
     }
     double* hrow = A.h + (size_t)s * D;
     double* crow = G == 4 ? A.c + (size_t)s * D : nullptr;
     int d = 0;
-    if (G == 0) { const int lp = A.last_poi[s]; d = lp >= 0 ? sc_bin(A, j, lp) : A.n_dist; }
+    if (G == 0) { const int lp = A.last_poi[s]; d = lp >= 0 ? pos_bin(A, j, lp) : A.n_dist; }
     for (int u = tid; u < D; u += 256) {
       xs[u] = (double)A.lt[(size_t)j * D + u];
       hs[u] = hrow[u];
@@ -173,9 +132,9 @@ __global__ __launch_bounds__(256) void sc_event_kernel(SessCellArgs A) {
         const double a = wave_sum_d(acc[u]);
         const int o = o0 + u;
         if (lane == 0) {
-          if (G == 0) act[o] = sc_sigmoid(a + hsum);
+          if (G == 0) act[o] = sigmoid_d(a + hsum);
           else if (G == 4 && o >= 2 * D && o < 3 * D) act[o] = tanh(a + (double)A.bi[o]);
-          else act[o] = sc_sigmoid(a + (double)A.bi[o]);
+          else act[o] = sigmoid_d(a + (double)A.bi[o]);
         }
       }
     }
@@ -224,7 +183,7 @@ __global__ __launch_bounds__(256) void sc_tile_kernel(SessCellArgs A) {
       if (bad) atomicAdd(A.bad, 1);
       else {
         ok = 1;
-        if (G == 0) { const int lp = A.last_poi[s]; if (lp >= 0) d = sc_bin(A, j, lp); }
+        if (G == 0) { const int lp = A.last_poi[s]; if (lp >= 0) d = pos_bin(A, j, lp); }
       }
     }
     s_slot[tid] = s; s_poi[tid] = j; s_d[tid] = d; s_ok[tid] = ok;
@@ -267,12 +226,12 @@ __global__ __launch_bounds__(256) void sc_tile_kernel(SessCellArgs A) {
     for (int r = 0; r < 4; ++r) {
       const int unit = 16 * ut + g + 4 * r, at = swz(unit) * RS + i;
       if constexpr (G == 0) {
-        nT[at] = sc_sigmoid(acc[0][r] + A.wrs[(size_t)s_d[i] * D + unit] + s_hsum[i]);
+        nT[at] = sigmoid_d(acc[0][r] + A.wrs[(size_t)s_d[i] * D + unit] + s_hsum[i]);
       } else if constexpr (G == 1) {
-        nT[at] = sc_sigmoid(acc[0][r] + (double)A.bi[unit]);
+        nT[at] = sigmoid_d(acc[0][r] + (double)A.bi[unit]);
       } else {      // cT[at]: read and written by this lane only
-        const double ig = sc_sigmoid(acc[0][r] + (double)A.bi[unit]), fg = sc_sigmoid(acc[1][r] + (double)A.bi[D + unit]);
-        const double gg = tanh(acc[2][r] + (double)A.bi[2 * D + unit]), og = sc_sigmoid(acc[3][r] + (double)A.bi[3 * D + unit]);
+        const double ig = sigmoid_d(acc[0][r] + (double)A.bi[unit]), fg = sigmoid_d(acc[1][r] + (double)A.bi[D + unit]);
+        const double gg = tanh(acc[2][r] + (double)A.bi[2 * D + unit]), og = sigmoid_d(acc[3][r] + (double)A.bi[3 * D + unit]);
         const double cn = fg * cT[at] + ig * gg;
         cT[at] = cn;
         nT[at] = og * tanh(cn);
@@ -289,7 +248,7 @@ __global__ __launch_bounds__(256) void sc_tile_kernel(SessCellArgs A) {
       A.h[(size_t)s_slot[e] * D + u] = v;
       if (G == 4) A.c[(size_t)s_slot[e] * D + u] = cT[at];
     }
-    if (A.hts_out) A.hts_out[(size_t)(e0 + e) * D + u] = s_ok[e] ? (float)v : sc_nan();
+    if (A.hts_out) A.hts_out[(size_t)(e0 + e) * D + u] = s_ok[e] ? (float)v : quiet_nan();
   }
   if (tid < 16 && s_ok[tid]) { A.last_poi[s_slot[tid]] = s_poi[tid]; A.steps[s_slot[tid]] += 1; }
 }

@@ -34,11 +34,6 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 #define XS 5                       // signed base-256 digits per operand
 #define XQB (8 * XS - 2)           // |Q| <= 2^XQB: the leading digit stays inside [-64, 64] (+ carry)
 
-__device__ __forceinline__ void x_lds_barrier() {      // orders LDS traffic only (tile_engine.hip: lds_barrier)
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 __device__ __forceinline__ double x_pow2(int e) { return __longlong_as_double((long long)(1023 + e) << 52); }
 // exponent e with |m| < 2^e (m = 0 and subnormals: -126)
 __device__ __forceinline__ int x_exponent(float m) { return (int)((__float_as_uint(m) >> 23) & 255u) - 126; }
@@ -297,7 +292,7 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void te_gemmx_kernel(XGemm
       // tile j has landed when at most what was issued behind its request is outstanding: the 16 C stores of tile j - 1 (first tile: the
       // compiler has already waited for the row loads that followed the request - nothing younger is in flight)
       if (j == j0) x_wait_vm<0>(); else x_wait_vm<16>();
-      x_lds_barrier();                                         // every wave's pieces are in; the other slot (tile j - 1) has been read; s_rs is visible
+      lds_barrier();                                         // every wave's pieces are in; the other slot (tile j - 1) has been read; s_rs is visible
       if (j + 1 < j0 + tpg) request(j + 1, slot ^ 1);
       const uint4* cur = s_b[slot];
       i32x16 acc[NC];
@@ -334,7 +329,7 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void te_gemmx_kernel(XGemm
       }
     }
     x_wait_vm<0>();
-    x_lds_barrier();                                           // both slots and s_rs are free for the next item
+    lds_barrier();                                           // both slots and s_rs are free for the next item
   }
 }
 
@@ -485,7 +480,7 @@ __global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel(TeArgs A) {
       }
     }
     XP(2)
-    x_lds_barrier();
+    lds_barrier();
     XP(3)
     mma(ac, rrow, 2, std::integral_constant<int, 1>());
     XP(4)
@@ -508,7 +503,7 @@ __global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel(TeArgs A) {
       *reinterpret_cast<float4*>(A.H + row * D + u0) = make_float4(h4[0], h4[1], h4[2], h4[3]);
     }
     XP(6)
-    x_lds_barrier();
+    lds_barrier();
     XP(7)
   };
 
@@ -569,17 +564,11 @@ __global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel(TeArgs A) {
 // A 16-row tile step of te_rec_fwdx costs 3.6 us whether the tile holds 16 sequences or one (float64 gate math for 16 x 3 D values);
 // here a step is 96 FMAs + two gate values per thread: ~1 us.  Same inputs (gx, gate-major) and outputs as te_rec_fwdx.
 // -------------------------------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ double x_dpp(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, false), hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
 template <int N> __device__ __forceinline__ double x_group_sum(double v) {      // sum over N = 8 / 16 adjacent lanes, in every lane
-  v += x_dpp<0xB1>(v);                     // quad_perm [1,0,3,2]
-  v += x_dpp<0x4E>(v);                     // quad_perm [2,3,0,1]
-  v += x_dpp<0x141>(v);                    // row_half_mirror
-  if (N >= 16) v += x_dpp<0x140>(v);       // row_mirror
+  v += dpp_d<0xB1>(v);                     // quad_perm [1,0,3,2]
+  v += dpp_d<0x4E>(v);                     // quad_perm [2,3,0,1]
+  v += dpp_d<0x141>(v);                    // row_half_mirror
+  if (N >= 16) v += dpp_d<0x140>(v);       // row_mirror
   return v;
 }
 __device__ __forceinline__ double x_pick4(const double (&a)[4], int o) { return o == 0 ? a[0] : o == 1 ? a[1] : o == 2 ? a[2] : a[3]; }
@@ -663,7 +652,7 @@ __global__ __launch_bounds__(4 * D) void te_rec_fwd1x_kernel(TeArgs A) {
           *(st ? A.RH + row * D + jr : dR) = (float)rh;
         }
       }
-      x_lds_barrier();
+      lds_barrier();
       double b[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int i = 0; i < LC; i += 2) {
@@ -684,7 +673,7 @@ __global__ __launch_bounds__(4 * D) void te_rec_fwd1x_kernel(TeArgs A) {
           *(ownc ? A.H + row * D + jc : dH) = (float)hn;
         }
       }
-      x_lds_barrier();
+      lds_barrier();
       asm volatile("" : "+v"(nzr), "+v"(nc));      // the wait for the prefetch is counted HERE, behind this step's stores
       gzr = nzr; gcc = nc;
     }
@@ -844,7 +833,7 @@ __global__ __launch_bounds__(D * 2) void te_rec_fwdd_kernel(TeArgs A) {
       }
     }
     pre(gcc, 2, row, p1, z1);
-    x_lds_barrier();
+    lds_barrier();
     mma(ac1, rhT, 2, std::integral_constant<int, 1>());
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -863,7 +852,7 @@ __global__ __launch_bounds__(D * 2) void te_rec_fwdd_kernel(TeArgs A) {
         *reinterpret_cast<float4*>(A.H + row * D + ub[u]) = make_float4(h4[0], h4[1], h4[2], h4[3]);
       }
     }
-    x_lds_barrier();
+    lds_barrier();
   }
   if constexpr (PRED) {
     const int k = tile * 16 + i;

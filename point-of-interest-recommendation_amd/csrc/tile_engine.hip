@@ -39,15 +39,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also carries a release fence that
-// waits for every outstanding GLOBAL store / atomic of the wave (vmcnt(0)) - microseconds per barrier
-// in these loops, where global results are consumed only by later kernels and just LDS tiles cross
-// waves.  (Loads feeding ds_write are still waited for by the data dependence.)
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
+// lds_barrier(): poi_common.h
 // tanh on the hardware exp: 1 - 2 / (1 + e^{2x}); saturates correctly (e^{2x} -> inf gives 1, -> 0 gives -1);
 // absolute error ~1e-7, far inside the 1e-5 parity bar.  The library tanhf is a long branchy routine.
 // (v_rcp_f32, 1 ulp, instead of the IEEE division sequence: the gate math sits on the per-step latency chain)
