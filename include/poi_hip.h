@@ -75,6 +75,9 @@ extern "C" {
 /* additive to 9: GeoIE scoring under the trained geo-influence law - new entry points poi_geoie_score_all_geo and poi_geoie_score_topk_geo,
  * option "geoie_score_span", plan keys "geoie_score_span" / "geoie_score_splits", timing names "geoie_score_geo" / "geoie_topk_geo" (existing
  * entries unchanged). */
+/* additive to 9: fold-in for POI2Vec - new entry points poi_foldin_p2v, poi_foldin_p2v_span and poi_poi2vec_topk_ex, timing names
+ * "foldin_p2v_prep" / "foldin_p2v_pass" / "foldin_p2v_upd"; no new option or plan key (existing entries, poi_poi2vec_scores / _topk
+ * included, unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -658,6 +661,44 @@ int poi_poi2vec_scores(poi_ctx* ctx, const poi_poi2vec_params* prm, const int32_
 int poi_poi2vec_topk(poi_ctx* ctx, const poi_poi2vec_params* prm, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch,
                      int32_t length, const int32_t* coff, const int32_t* cidx, int32_t softmax_axis, int32_t k, int32_t* idx_out,
                      float* score_out, void* stream);
+
+/* poi_poi2vec_topk with per-row exclusion lists (additive to 9): ex_off (rows + 1) / ex are a CSR of ascending unique POI ids per output
+ * row (the contract of poi_score_topk_near's lists), or both NULL.  An excluded POI is never listed.  count_out (rows) or NULL: the
+ * number of POIs ranked, n_item minus the row's excluded ids.  A row with fewer than k candidates ends in id -1 with a NaN score (an empty
+ * list slot).  With ex_off = ex = count_out = NULL the call is poi_poi2vec_topk: the same bits. */
+int poi_poi2vec_topk_ex(poi_ctx* ctx, const poi_poi2vec_params* prm, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch,
+                        int32_t length, const int32_t* coff, const int32_t* cidx, int32_t softmax_axis, const int32_t* ex_off,
+                        const int32_t* ex, int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+
+/* ---- fold-in for POI2Vec (additive to 9): a row of xu for a check-in history the model never trained on ------------------------------------
+ * In Poi2vec.seq_train (public/POI2Vec.py:140-163) the geographic factor paths_i depends on wl, pb and the contexts, never on xu.  With
+ * the item side frozen the user row sees only the full softmax over all POIs.  For new user r with history t_i = tgt[off[r] .. off[r+1]),
+ * L = its length:
+ *   w = w0[r] (zeros when w0 is NULL);  for e = 0 .. epochs - 1:
+ *     s_j = w . wl_j  (j < n_item),   lse = logsumexp_j s_j,   plu = softmax_j s_j,
+ *     loss[r][e] = lse - (1/L) sum_i s_{t_i}                                     (at the values before the update),
+ *     w = w - alpha (sum_j plu_j wl_j - (1/L) sum_i wl_{t_i} + lambda w)         (one step per pass over the history)
+ *   This is the xu[u] part of poi_poi2vec_step for one user: from w0 = xu[u], one epoch gives that step's xu[u]; the loss is the
+ *   step's upq minus its mean log paths term, which does not depend on w.
+ *   wl: the evaluation snapshot, float32, at least n_item rows; the softmax runs over rows 0 .. n_item - 1 only - the zero pad row
+ *   n_item never enters it.  Ids lie in [0, n_item): the pad id is not a POI of the softmax and is rejected, as poi_poi2vec_step does.
+ *   A repeated target counts as often as it occurs.
+ * Arithmetic: the running w, the logits, the exponentials, every sum and the loss are float64 (alpha and lambda are taken at their
+ * float values); w is rounded to float32 once, at the end.  Every exponential has a running maximum subtracted: any finite w0 gives
+ * finite rows and losses.  No float atomics; partials are formed per span of P2V_FOLD_SPAN = poi_foldin_p2v_span() items and merged
+ * in span order.  A user's output bits depend on its own history and w0 alone: not on the other users of the call, on its position in
+ * the call, on n or on the grid.
+ * Edge cases: epochs = 0 or an empty history returns w0[r] (zeros without w0) and losses 0.  A user with off[r + 1] < off[r],
+ * off[r] < 0 or a target outside [0, n_item) is a bad user: a NaN row, NaN losses, counted once (poi_ctx_take_bad_ids), and nothing
+ * else moves.  The offsets themselves must lie inside tgt (the caller's contract).  n = 0 is a no-op.
+ * w_out (n, dim) may alias w0; loss_out (n, epochs) or NULL.  dim: a multiple of 4 in [4, 128].
+ * Scratch: 8 bytes x c (n_span (dim + 2) + 2 dim) + 4 c, n_span = ceil(n_item / span), for c = the users of a chunk: the call is cut
+ * into chunks of c = max(64, 64 MiB / (8 n_span (dim + 2)) rounded down to a multiple of 64) users, which changes no bit.
+ * Per epoch two kernels (foldin_p2v.hip): a pass over wl (16 users x 16 POIs per v_mfma_f64_16x16x4_f64 block, item tiles staged in
+ * LDS as float64) and a combine-and-update.  Timing names: "foldin_p2v_prep", "foldin_p2v_pass", "foldin_p2v_upd". */
+int poi_foldin_p2v(poi_ctx* ctx, const float* wl, int32_t n_item, int32_t dim, const int32_t* off, const int32_t* tgt, int32_t n,
+                   int32_t epochs, float alpha, float lambda, const float* w0, float* w_out, float* loss_out, void* stream);
+int poi_foldin_p2v_span(void);      /* the span of the partials (a compile-time constant; tests straddle it) */
 
 /* ---- mini-batch Lstm / Rnn (additive to ABI 9) - public/GRU.py:502-657 (Lstm), :661-809 (Rnn) ---------------------------------------
  * The baselines the reference's papers compare against, as one kernel family templated on the number of gate blocks.  lt (n_item + 1, D);

@@ -7,6 +7,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libpoi_hip.so")
 ABI_VERSION = 9
+P2V_FOLD_SPAN = 256        # items per softmax partial of poi_foldin_p2v (csrc/poi_kernels.h; checked against the library on load)
 
 BPR_SNAPSHOT, BPR_HOGWILD = 0, 1
 
@@ -147,6 +148,11 @@ SIGNATURES = {
                                    c_void_p]),
     "poi_poi2vec_topk": (c_int, [c_void_p, POINTER(Poi2vecParams), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32,
                                  c_void_p, c_void_p, c_void_p]),
+    "poi_poi2vec_topk_ex": (c_int, [c_void_p, POINTER(Poi2vecParams), c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                    c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_foldin_p2v": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p,
+                               c_void_p, c_void_p]),
+    "poi_foldin_p2v_span": (c_int, []),
     "poi_cell_step": (c_int, [c_void_p, POINTER(CellParams), POINTER(SeqTables), c_void_p, c_int32, c_float, c_float, c_void_p, c_void_p]),
     "poi_cell_predict": (c_int, [c_void_p, POINTER(CellParams), POINTER(SeqTables), c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "poi_vbpr_step": (c_int, [c_void_p, POINTER(VbprParams), c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p]),
@@ -219,6 +225,8 @@ def load():
         fn.argtypes = args
     if lib.poi_abi_version() != ABI_VERSION:
         raise PoiError("libpoi_hip.so ABI %d != binding %d" % (lib.poi_abi_version(), ABI_VERSION))
+    if lib.poi_foldin_p2v_span() != P2V_FOLD_SPAN:
+        raise PoiError("libpoi_hip.so folds POI2Vec in spans of %d, the binding expects %d" % (lib.poi_foldin_p2v_span(), P2V_FOLD_SPAN))
     _lib = lib
     return lib
 

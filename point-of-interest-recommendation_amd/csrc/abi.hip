@@ -92,6 +92,7 @@ struct poi_ctx {
   DevBuf ge_ws;
   // POI2Vec step / scoring scratch
   DevBuf pv_ws, pv_sc;
+  DevBuf pv_fold;           // poi_foldin_p2v: float64 running rows, mean target rows, per (user, span) softmax partials
   // mini-batch Lstm / Rnn: packed weights, per-position-row state, sort buffers, chunk partials, new-row slots
   DevBuf cell_ws;
   int cell_grid = 0;        // option "cell_grid": cap of the recurrent kernel's persistent grid (0: none)
@@ -247,7 +248,7 @@ int poi_ctx_destroy(poi_ctx* c) {
   if (!c) return POI_OK;
   DevBuf* all[] = {&c->ex_ws, &c->ex_slab, &c->ex_glt, &c->ex_gdi, &c->ws, &c->slab, &c->te_ws, &c->hslab, &c->zrow, &c->g_lt, &c->mult_lt, &c->nseq_lt, &c->g_di, &c->mult_di, &c->nseq_di, &c->seg_s, &c->seg_e, &c->pmark, &c->xc, &c->kc_dev, &c->uidx_stage, &c->out_stage, &c->ptab, &c->iota, &c->xw, &c->xg, &c->xflag, &c->bad_ids,
                    &c->g_wd, &c->mult_wd, &c->nseq_wd, &c->ca_ws, &c->ca_slab, &c->ca_scr, &c->ca2, &c->g_ux, &c->cnt_ux, &c->g_blt, &c->cnt_blt, &c->cand_s, &c->cand_i, &c->items_pk, &c->gbound, &c->st,
-                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->cell_ws, &c->vb_ws, &c->rank_ws, &c->sess_wrs, &c->geo_ws};
+                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->pv_fold, &c->cell_ws, &c->vb_ws, &c->rank_ws, &c->sess_wrs, &c->geo_ws};
   (void)hipDeviceSynchronize();
   c->tm.clear();
   drop_graphs(c);
@@ -1561,7 +1562,8 @@ int poi_poi2vec_step(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* off
 
 static int poi2vec_score_common(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch,
                                 int32_t length, const int32_t* coff, const int32_t* cidx, int32_t axis, int32_t k, float* out, int32_t* idx_out,
-                                float* score_out, void* stream, const char* who) {
+                                float* score_out, void* stream, const char* who, const int32_t* ex_off = nullptr, const int32_t* ex = nullptr,
+                                int32_t* count_out = nullptr) {
   int rc = poi2vec_check(c, P, who);
   if (rc) return rc;
   if (!leaf_nodes || !users || !coff || !cidx) return fail(c, POI_EINVAL, "%s: NULL argument", who);
@@ -1585,6 +1587,7 @@ static int poi2vec_score_common(poi_ctx* c, const poi_poi2vec_params* P, const i
     if (!pass && (rc = ensure(c, c->pv_sc, W.used + 256, st))) return rc;
   }
   A.idx_out = idx_out; A.score_out = score_out;
+  A.ex_off = ex_off; A.ex = ex; A.count_out = count_out;
   HIPCHK(c, poi::launch_poi2vec_scores(A, c->num_cu, st, &c->tm));
   return POI_OK;
 }
@@ -1600,6 +1603,58 @@ int poi_poi2vec_topk(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* lea
   if (c && !idx_out) return fail(c, POI_EINVAL, "poi_poi2vec_topk: NULL argument");
   if (c && P && (k < 1 || k > 64 || k > P->n_item)) return fail(c, POI_EINVAL, "poi_poi2vec_topk: k must lie in [1, min(64, n_item)]");
   return poi2vec_score_common(c, P, leaf_nodes, users, n_batch, length, coff, cidx, softmax_axis, k, nullptr, idx_out, score_out, stream, "poi_poi2vec_topk");
+}
+
+int poi_poi2vec_topk_ex(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch, int32_t length,
+                        const int32_t* coff, const int32_t* cidx, int32_t softmax_axis, const int32_t* ex_off, const int32_t* ex, int32_t k,
+                        int32_t* idx_out, float* score_out, int32_t* count_out, void* stream) {
+  if (c && !idx_out) return fail(c, POI_EINVAL, "poi_poi2vec_topk_ex: NULL argument");
+  if (c && ((ex_off == nullptr) != (ex == nullptr))) return fail(c, POI_EINVAL, "poi_poi2vec_topk_ex: ex_off and ex come together");
+  if (c && P && (k < 1 || k > 64 || k > P->n_item)) return fail(c, POI_EINVAL, "poi_poi2vec_topk_ex: k must lie in [1, min(64, n_item)]");
+  return poi2vec_score_common(c, P, leaf_nodes, users, n_batch, length, coff, cidx, softmax_axis, k, nullptr, idx_out, score_out, stream,
+                              "poi_poi2vec_topk_ex", ex_off, ex, count_out);
+}
+
+// fold-in of new users for POI2Vec (foldin_p2v.hip).  The partials grow with users x spans x (dim + 2): the call is cut into user
+// chunks that keep them within P2V_FOLD_PART_BYTES (a user's bits do not depend on the chunking)
+#define P2V_FOLD_PART_BYTES ((size_t)64 << 20)
+int poi_foldin_p2v_span(void) { return P2V_FOLD_SPAN; }
+
+int poi_foldin_p2v(poi_ctx* c, const float* wl, int32_t n_item, int32_t dim, const int32_t* off, const int32_t* tgt, int32_t n, int32_t epochs,
+                   float alpha, float lambda, const float* w0, float* w_out, float* loss_out, void* stream) {
+  if (!c || !wl || !w_out) return fail(c, POI_EINVAL, "poi_foldin_p2v: NULL ctx / wl / w_out");
+  if (dim <= 0 || dim % 4 != 0 || dim > 128) return fail(c, POI_ENOTSUP, "poi_foldin_p2v: dim must be a multiple of 4 in [4, 128] (got %d)", dim);
+  if (n < 0 || n_item <= 0 || epochs < 0) return fail(c, POI_EINVAL, "poi_foldin_p2v: n < 0, n_item <= 0 or epochs < 0");
+  if (n == 0) return POI_OK;
+  if (!off || !tgt) return fail(c, POI_EINVAL, "poi_foldin_p2v: NULL off / tgt");
+  if (is_f16(c, wl) || (w0 && is_f16(c, w0)) || is_f16(c, w_out)) return fail(c, POI_ENOTSUP, "poi_foldin_p2v: wl / w0 / w_out must be float32");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  const int n_span = (n_item + P2V_FOLD_SPAN - 1) / P2V_FOLD_SPAN;
+  const size_t per_user = sizeof(double) * (size_t)n_span * (size_t)(dim + 2);
+  size_t uc = P2V_FOLD_PART_BYTES / per_user / P2V_FOLD_USERS * P2V_FOLD_USERS;
+  if (uc < P2V_FOLD_USERS) uc = P2V_FOLD_USERS;
+  if (uc > (size_t)n) uc = (size_t)n;
+  for (int pass = 0; pass < 2; ++pass) {
+    Carver W(pass ? c->pv_fold.p : nullptr);
+    double* w = (double*)W.bytes(sizeof(double) * uc * dim);
+    double* tbar = (double*)W.bytes(sizeof(double) * uc * dim);
+    int* flag = (int*)W.bytes(sizeof(int) * uc);
+    double* part = (double*)W.bytes(per_user * uc);
+    if (!pass) { if ((rc = ensure(c, c->pv_fold, W.used + 256, st))) return rc; continue; }
+    for (size_t r0 = 0; r0 < (size_t)n; r0 += uc) {
+      poi::FoldP2vArgs A = {};
+      A.wl = wl; A.n_item = n_item; A.dim = dim; A.epochs = epochs; A.n_span = n_span;
+      A.n = (int)((size_t)n - r0 < uc ? (size_t)n - r0 : uc);
+      A.off = off + r0; A.tgt = tgt; A.alpha = alpha; A.lambda = lambda;
+      A.w0 = w0 ? w0 + r0 * dim : nullptr; A.w_out = w_out + r0 * dim; A.loss_out = loss_out ? loss_out + r0 * epochs : nullptr;
+      A.w = w; A.tbar = tbar; A.flag = flag; A.part = part; A.bad = (int*)c->bad_ids.p;
+      HIPCHK(c, poi::launch_foldin_p2v(A, st, &c->tm));
+    }
+  }
+  return POI_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

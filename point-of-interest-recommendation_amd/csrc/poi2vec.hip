@@ -663,17 +663,30 @@ __global__ __launch_bounds__(256) void p2v_sc_out_kernel(P2vScoreArgs A) {
 __global__ __launch_bounds__(256) void p2v_sc_topk_kernel(P2vScoreArgs A) {
   __shared__ float s_ls[4][64];
   __shared__ int s_li[4][64];
+  __shared__ int s_nex;                                       // POIs of the row its exclusion list removed
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int r = blockIdx.x; r < A.n_rows; r += gridDim.x) {
+    if (threadIdx.x == 0) s_nex = 0;                          // (wave 0 has read the previous row's count)
     __syncthreads();
     s_ls[w][lane] = -INFINITY; s_li[w][lane] = PAD_ID;
     __builtin_amdgcn_wave_barrier();
+    // exclusion list of the row (poi_poi2vec_topk_ex; ascending unique ids): an excluded POI enters the lists as an empty entry.  A
+    // malformed list (descending offsets) is taken as empty
+    const int e0 = A.ex ? A.ex_off[r] : 0, e1 = A.ex ? max(A.ex_off[r + 1], e0) : 0;
+    int n_ex = 0;
     for (int j0 = 0; j0 < A.n_item; j0 += 256) {              // (wave-uniform trip count)
       const int j = j0 + threadIdx.x;
+      bool on = j < A.n_item;
+      if (on && e1 > e0) {                                    // first entry >= j
+        int a = e0, b = e1;
+        while (a < b) { const int md = (a + b) >> 1; if (A.ex[md] < j) a = md + 1; else b = md; }
+        if (a < e1 && A.ex[a] == j) { on = false; ++n_ex; }
+      }
       float s = -INFINITY;
-      if (j < A.n_item) { s = p2v_score(A, r, j); if (!(s == s)) s = -INFINITY; }
-      lds_list_merge(s_ls[w], s_li[w], s, j < A.n_item ? j : PAD_ID, A.k);
+      if (on) { s = p2v_score(A, r, j); if (!(s == s)) s = -INFINITY; }
+      lds_list_merge(s_ls[w], s_li[w], s, on ? j : PAD_ID, A.k);
     }
+    if (n_ex) atomicAdd(&s_nex, n_ex);                        // (an integer count in LDS: order-free)
     __syncthreads();
     if (w == 0) {
       float s = s_ls[0][lane];
@@ -697,6 +710,7 @@ __global__ __launch_bounds__(256) void p2v_sc_topk_kernel(P2vScoreArgs A) {
         A.idx_out[o] = ok ? i : -1;
         if (A.score_out) A.score_out[o] = ok ? p2v_score(A, r, i) : __int_as_float(0x7fc00000);
       }
+      if (lane == 0 && A.count_out) A.count_out[r] = A.n_item - s_nex;
     }
   }
 }

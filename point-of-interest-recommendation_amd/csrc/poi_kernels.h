@@ -473,6 +473,7 @@ struct P2vScoreArgs {
   const float *xu, *wl, *pb, *probs; const int *rid, *leaf_nodes, *users, *coff, *cidx;
   int n_user, n_item, n_node, depth, dim, n_batch, length, n_rows, axis, k;
   double *cl, *zf, *rp, *ssum; float *logit, *smax, *out, *score_out; int* idx_out;
+  const int *ex_off, *ex; int* count_out;      // top-K only (poi_poi2vec_topk_ex): per-row exclusion lists, ascending unique ids; candidates ranked.  NULL otherwise
 };
 hipError_t launch_poi2vec_step(P2vArgs& A, int num_cu, hipStream_t st, Timing* tm);
 hipError_t launch_poi2vec_scores(P2vScoreArgs& A, int num_cu, hipStream_t st, Timing* tm);
@@ -650,6 +651,22 @@ struct FoldinPairArgs {
   int* bad;
 };
 hipError_t launch_foldin_pair(const FoldinPairArgs& A, hipStream_t st, Timing* tm);
+
+// Fold-in of new users for POI2Vec (foldin_p2v.hip): the xu[u] part of the step against the frozen wl, one softmax pass per epoch
+#define P2V_FOLD_SPAN 256                   // items per partial: a user's (max, sum, weighted row sum) partials are merged in span order
+#define P2V_FOLD_USERS 64                   // users per workgroup of the pass kernel (four 16-user MFMA tiles share a staged item tile)
+struct FoldP2vArgs {
+  const float* wl;                                            // (>= n_item, dim) float32: the softmax runs over rows 0 .. n_item - 1
+  int n, n_item, dim, epochs, n_span, epoch;                  // n_span = ceil(n_item / P2V_FOLD_SPAN); epoch: set per launch
+  const int *off, *tgt;                                       // history CSR (n + 1), targets
+  float alpha, lambda;
+  const float* w0; float* w_out; float* loss_out;             // (n, dim) or null; (n, dim), may alias w0; (n, epochs) or null
+  double *w, *tbar, *part; int* flag;                         // scratch: (n, dim) running rows, (n, dim) mean target rows,
+                                                              // (n, n_span, dim + 2) partials; per user 0 = live, 1 = bad, 2 = nothing to do
+  int* bad;                                                   // device counter of rejected users (poi_ctx_take_bad_ids)
+};
+size_t foldin_p2v_lds(int dim);
+hipError_t launch_foldin_p2v(FoldP2vArgs& A, hipStream_t st, Timing* tm);
 
 // scoring / top-K
 struct ScoreArgs {

@@ -809,6 +809,23 @@ def poi2vec_contexts(times, time_threshold):
     return out
 
 
+def poi2vec_next_context(pois, times, now, time_threshold):
+    """The loader's context rule (poi2vec_contexts, Load_Data_Poi2vec.py:56-69) applied to a QUERY at time `now` behind a history of
+    check-ins `pois` at `times`: the trailing check-ins k = L-1, L-2, .. while now - t_k < time_threshold, stopping at the first that
+    fails.  Returns their POI ids (nearest first) as an int64 array - what OboPoi2vec.score_new / recommend_new / rank_new take as one
+    row of contexts=.  Host only."""
+    pois, times = np.asarray(pois, np.int64).reshape(-1), np.asarray(times).reshape(-1)
+    if len(pois) != len(times):
+        raise ValueError("poi2vec_next_context: %d POIs and %d times" % (len(pois), len(times)))
+    out = []
+    for k in range(len(pois) - 1, -1, -1):
+        if now - times[k] < time_threshold:
+            out.append(int(pois[k]))
+        else:
+            break
+    return np.asarray(out, np.int64)
+
+
 def _poi2vec_from_lists(seqs, times, cods, split, time_threshold, region_threshold, where="input"):
     s1 = float(split[1])
     alias, coord_of = {}, {}

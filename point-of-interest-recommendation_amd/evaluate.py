@@ -134,10 +134,10 @@ def full_rank_metrics(model, starts_ends_tes, at_nums, exclude=None):
 
 
 def foldin_rank_metrics(model, histories, targets, at_nums, exclude="history", **fold_in_kwargs):
-    """full_rank_metrics for HELD-OUT users of the factorisation family and of the successive-POI models OboFpmc_lr / OboPrme (strong
-    generalisation): every history is folded in (model.rank_new: fold_in, then the exact rank of its targets among all POIs) and the
+    """full_rank_metrics for HELD-OUT users of the factorisation family, of the successive-POI models OboFpmc_lr / OboPrme and of
+    OboPoi2vec (strong generalisation): every history is folded in (model.rank_new: fold_in, then the exact rank of its targets among all POIs) and the
     same reductions run on those ranks.  targets: (n, len_t <= 8) POI ids or a pair (ids, mask); exclude: "history" (default), None or
-    CSR lists.  OboPrme's gaps= (and dists=) travel in fold_in_kwargs.  Returns the keys of full_rank_metrics; ndcg is averaged over
+    CSR lists.  OboPrme's gaps= (and dists=) and OboPoi2vec's contexts= travel in fold_in_kwargs.  Returns the keys of full_rank_metrics; ndcg is averaged over
     the n histories."""
     rank, cnt = model.rank_new(histories, targets=targets, exclude=exclude, return_counts=True, **fold_in_kwargs)
     return _metrics_of_ranks(model, [(rank, cnt)], at_nums, rank.shape[1], rank.shape[0])

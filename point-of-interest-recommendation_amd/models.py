@@ -1813,7 +1813,7 @@ class MfBasic(_Base):
     # The recurrent models serve an unseen user through a Session slot; this family's only user representation is a trained row, so a
     # new user gets one by running the model's own per-check-in rule on a fresh row against the frozen evaluation snapshot
     # trained_items (width kdim: [lt | fi ei^T] for OboVBpr).  Nothing here changes a parameter or a snapshot.  FPMC-LR and PRME
-    # fold in through _SeqFoldin (per-step scalars + the generalised chain).  Not covered: GeoIE / POI2Vec (rules of their own), the
+    # fold in through _SeqFoldin (per-step scalars + the generalised chain), POI2Vec through poi_foldin_p2v (OboPoi2vec.fold_in).  Not covered: the
     # recurrent models (Session).
     def fold_in(self, histories, negatives=None, epochs=10, alpha=None, lam=None, init="zeros", seed=0, return_loss=False, sync=True):
         """User rows for NEW check-in histories (include/poi_hip.h, poi_foldin_bpr): the item side stays frozen and the model's own
@@ -3288,6 +3288,163 @@ class OboPoi2vec(_Base):
 
     def _rank_chunk(self, n):
         return max(n, 1)                          # the reference softmax runs over the USERS of a call: the call is not cut
+
+    # ---- unseen users (poi_foldin_p2v) ---------------------------------------------------------------------------------
+    # paths_i of Poi2vec.seq_train (POI2Vec.py:140-163) depends on wl, pb and the contexts, never on xu: with the item side frozen the
+    # row of a new user sees the full softmax over the POIs alone, and one pass over its history is one gradient step of
+    #   logsumexp_j (w . wl_j) - (1/L) sum_i w . wl_{t_i} + (lambda / 2) |w|^2.
+    def fold_in(self, histories, epochs=10, alpha=None, lam=None, init="zeros", seed=0, return_loss=False, sync=True):
+        """User rows for NEW check-in histories (include/poi_hip.h, poi_foldin_p2v): the xu[u] part of the reference step
+        (POI2Vec.py:140-163) runs `epochs` times - one step per pass over the history - on one fresh row against the evaluation snapshot
+        of wl (update_trained_params).  Returns an (n, D) float32 device tensor - rows to score with exactly like trained xu rows; with
+        return_loss also the (n, epochs) losses logsumexp - mean target logit, each at the values before its epoch's update.  Changes no
+        parameter and no snapshot.
+        histories: a list of POI id sequences, or a tuple (off, p_flat) CSR of host arrays or device tensors; ids in [0, n_item) - the
+        padding id n_item is not a POI of the softmax and is refused.  alpha / lam: default to the model's alpha_lambda[0:2].
+        init: "zeros", "uniform" (the reference's uniform(-0.5, 0.5) rows, POI2Vec.py:63, drawn from `seed`) or an (n, D) array.
+        Host arrays are range-checked before any launch (IndexError).  Device tensors are checked by the kernel: an offending history's
+        row and losses are NaN, the others are untouched, and - with sync - IndexError is raised (sync=False leaves the count to
+        ctx.take_bad_ids()).  A history's row does not depend on the other histories of the call."""
+        off, p, n, total = self._foldin_csr(histories)
+        on_device = isinstance(histories, tuple) and len(histories) == 2 and isinstance(histories[1], torch.Tensor) and histories[1].is_cuda
+        if total and not on_device and int(p[:total].max()) >= self.n_item:
+            raise IndexError("fold_in histories: ids must lie in [0, %d) (the padding id is no POI of the softmax)" % self.n_item)
+        epochs = int(epochs)
+        if epochs < 0:
+            raise ValueError("epochs must be >= 0 (got %d)" % epochs)
+        alpha = self.alpha_lambda[0] if alpha is None else float(alpha)
+        lam = self.alpha_lambda[1] if lam is None else float(lam)
+        if isinstance(init, str):
+            if init not in ("zeros", "uniform"):
+                raise ValueError("init must be 'zeros', 'uniform' or an (n, D) array (got %r)" % (init,))
+            w0 = None if init == "zeros" else self._dev(np.random.default_rng(seed).uniform(-0.5, 0.5, (n, self.dim)))
+        else:
+            w0 = self._foldin_init(init, n, self.dim, None)
+        w = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+        loss = torch.empty((n, epochs), dtype=torch.float32, device=self.device) if return_loss else None
+        self.ctx.check(self.lib.poi_foldin_p2v(self.ctx.handle, _ptr(self._trained["wl"]), self.n_item, self.dim, _ptr(off), _ptr(p), n, epochs,
+                                               alpha, lam, _ptr(w0), _ptr(w), _ptr(loss), self._stream()))
+        if sync:
+            bad = self.ctx.take_bad_ids(self._stream().value)
+            if bad:
+                raise IndexError("%d history(ies) with an id outside [0, %d) or descending offsets: their rows and losses are NaN" % (bad, self.n_item))
+        return (w, loss) if return_loss else w
+
+    def _new_contexts(self, contexts, off, p, n):
+        """contexts -> the context CSR (rc (n + 1), flat) int32 on the device, one row per history: "last" (the history's last check-in),
+        "none" (empty rows: ind = 0, S = 0, paths = 1 - the score is plu alone) or a list of n id arrays."""
+        if isinstance(contexts, str):
+            if contexts not in ("last", "none"):
+                raise ValueError("contexts must be 'last', 'none' or one id array per history (got %r)" % (contexts,))
+            o = off.long()
+            has = (o[1:] > o[:-1]) if contexts == "last" else torch.zeros(n, dtype=torch.bool, device=self.device)
+            rc = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+            rc[1:] = torch.cumsum(has.long(), 0)
+            flat = p[(o[1:] - 1).clamp(min=0)][has]
+            pad = flat.int().contiguous() if flat.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)
+            return rc.int(), pad
+        rows = [np.asarray(c, np.int64).reshape(-1) for c in contexts]
+        if len(rows) != n:
+            raise ValueError("contexts must hold one id array per history (%d vs %d)" % (len(rows), n))
+        flat = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+        self._check_ids("contexts", flat, self.n_item)
+        rc = np.zeros(n + 1, np.int32)
+        np.cumsum([len(r) for r in rows], out=rc[1:])
+        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+        return i32(rc), i32(flat if flat.size else [0])
+
+    def _foldin_rows(self, histories, contexts, kw):
+        """(folded rows, context CSR, off, p, n, total); the histories are checked with a sync whatever `sync` says - the exclusion
+        lists and the default contexts are built from them."""
+        if kw.get("return_loss"):
+            raise ValueError("return_loss belongs to fold_in")
+        off, p, n, total = csr = self._foldin_csr(histories)
+        return (self.fold_in((off, p[:total]), **dict(kw, sync=True)), self._new_contexts(contexts, off, p, n)) + csr
+
+    def _new_params(self, w):
+        tabs = dict(self._trained, xu=w)
+        return _lib.Poi2vecParams(*[ctypes.c_void_p(tabs[k].data_ptr()) for k in self.TABLES], _ptr(self.routes), _ptr(self.lrs), _ptr(self.probs),
+                                  _ptr(self.rid), max(int(w.shape[0]), 1), self.n_item, self.n_node, self.depth, self.dim)
+
+    def _score_rows_new(self, w, rc, flat, o=0, c=None):
+        """poi_poi2vec_scores on rows o .. o + c of the folded rows: n_user = c, users = arange(c), length 1, softmax over the POIs."""
+        c = w.shape[0] - o if c is None else c
+        out = torch.empty((c, self.n_item), dtype=torch.float32, device=self.device)
+        if c:
+            wc = w[o:o + c].contiguous()
+            rcc = (rc[o:o + c + 1] - rc[o]).contiguous()
+            fl = flat[int(rc[o]):] if o else flat
+            fl = fl if fl.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)
+            users = torch.arange(c, dtype=torch.int32, device=self.device)
+            P = self._new_params(wc)
+            self.ctx.check(self.lib.poi_poi2vec_scores(self.ctx.handle, ctypes.byref(P), _ptr(self.leaf_nodes), _ptr(users), c, 1, _ptr(rcc),
+                                                       _ptr(fl.contiguous()), 1, _ptr(out), self._stream()))
+        return out
+
+    def score_new(self, histories, contexts="last", **fold_in_kwargs):
+        """(n, n_item) device scores paths_j plu_j of NEW histories: fold_in(histories, **fold_in_kwargs), then poi_poi2vec_scores with
+        the folded rows in the place of xu (one row per history, length 1).  plu is the softmax over the POIs, always: the reference's
+        softmax over the USERS of an evaluation batch (softmax_axis="reference") ties a row's scores to whoever shares its batch, which
+        is meaningless between unrelated new users.  contexts: "last" (each history's last check-in), "none" (an empty context: ind = 0,
+        S = 0, paths = 1 - the score is plu alone) or one id array per history (data.poi2vec_next_context builds one from timestamps)."""
+        w, (rc, flat), off, p, n, total = self._foldin_rows(histories, contexts, fold_in_kwargs)
+        return self._score_rows_new(w, rc, flat)
+
+    def recommend_new(self, histories, k, contexts="last", exclude="history", return_scores=False, return_counts=False, within_km=None,
+                      sync=True, **fold_in_kwargs):
+        """Top-k (k <= min(64, n_item)) for NEW histories: fold_in, then poi_poi2vec_topk_ex on the folded rows (score_new's scores, never
+        stored).  exclude: "history" (each history's distinct POIs leave the candidates), None or a CSR pair (off, ids) of ascending
+        unique ids per row.  Returns (n, k) int32 ids by descending score, ties by ascending id, -1 (score NaN) where a row has fewer
+        than k candidates[, scores][, candidate counts].  within_km is refused: POI2Vec has no restricted ranking."""
+        if within_km is not None:
+            raise _lib.PoiError("%s ranks by a score rule of its own, not users . items: compute_sub_topk_near does not cover it" % type(self).__name__)
+        if not 1 <= int(k) <= min(64, self.n_item):
+            raise _lib.PoiError("top-K supports 1 <= k <= min(64, n_item) (got %d)" % k)
+        w, (rc, flat), off, p, n, total = self._foldin_rows(histories, contexts, fold_in_kwargs)
+        eo, ex = self._foldin_exclusion(exclude, off, p, n, total)
+        idx = torch.empty((n, int(k)), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, int(k)), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        if n:
+            users = torch.arange(n, dtype=torch.int32, device=self.device)
+            P = self._new_params(w)
+            self.ctx.check(self.lib.poi_poi2vec_topk_ex(self.ctx.handle, ctypes.byref(P), _ptr(self.leaf_nodes), _ptr(users), n, 1, _ptr(rc),
+                                                        _ptr(flat), 1, _ptr(eo), _ptr(ex), int(k), _ptr(idx), _ptr(sc), _ptr(cnt), self._stream()))
+        if sync:
+            torch.cuda.current_stream(self.device).synchronize()
+        out = (idx,) + ((sc,) if return_scores else ()) + ((cnt,) if return_counts else ())
+        return out if len(out) > 1 else idx
+
+    def rank_new(self, histories, targets, contexts="last", exclude="history", return_scores=False, return_counts=False, within_km=None,
+                 sync=True, **fold_in_kwargs):
+        """Exact 0-based rank of `targets` ((n, len_t <= 8) POI ids, or a pair (ids, mask)) among all POIs for NEW histories: score_new's
+        rows (at most 1 GiB at a time) + poi_rank_scores.  exclude: "history", None or a CSR pair (off, ids); an excluded target is not
+        ranked (-1); a NaN score counts below every target."""
+        if within_km is not None:
+            raise _lib.PoiError("%s ranks by a score rule of its own, not users . items: compute_sub_topk_near does not cover it" % type(self).__name__)
+        w, (rc, flat), off, p, n, total = self._foldin_rows(histories, contexts, fold_in_kwargs)
+        tgt, tm = self._rank_targets(targets, n)
+        eo, ex = self._foldin_exclusion(exclude, off, p, n, total)
+        lt = tgt.shape[1]
+        rank = torch.empty((n, lt), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, lt), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        step = max(1, min(max(n, 1), (1 << 28) // max(self.n_item, 1)))
+        for o in range(0, n, step):
+            c = min(step, n - o)
+            full = self._score_rows_new(w, rc, flat, o, c)
+            eo_c = eo[o:o + c + 1].contiguous() if eo is not None else None
+            r_c = torch.empty((c, lt), dtype=torch.int32, device=self.device)
+            k_c = torch.empty(c, dtype=torch.int32, device=self.device) if cnt is not None else None
+            self.ctx.check(self.lib.poi_rank_scores(self.ctx.handle, _ptr(full), c, self.n_item, _ptr(tgt[o:o + c].contiguous()),
+                                                    _ptr(tm[o:o + c].contiguous()), lt, _ptr(eo_c), _ptr(ex), _ptr(r_c), _ptr(k_c), self._stream()))
+            rank[o:o + c] = r_c
+            if cnt is not None:
+                cnt[o:o + c] = k_c
+            if sc is not None:
+                v = full.gather(1, tgt[o:o + c].long().clamp(0, self.n_item - 1))
+                sc[o:o + c] = torch.where(r_c >= 0, v, torch.full_like(v, float("-inf")))
+        return self._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
 
     def compute_sub_auc_preference(self, start_end):
         """POI2Vec.py:111-112 returns zeros: AUC is always 0."""
