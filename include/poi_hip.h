@@ -78,6 +78,8 @@ extern "C" {
 /* additive to 9: fold-in for POI2Vec - new entry points poi_foldin_p2v, poi_foldin_p2v_span and poi_poi2vec_topk_ex, timing names
  * "foldin_p2v_prep" / "foldin_p2v_pass" / "foldin_p2v_upd"; no new option or plan key (existing entries, poi_poi2vec_scores / _topk
  * included, unchanged). */
+/* additive to 9: group recommendation - new entry points poi_group_topk and poi_group_topk_scores, options "group_split_max" / "group_grid",
+ * plan keys "group_path" / "group_splits" / "group_split_max", timing names "group_topk" / "group_topk_scores" (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -162,7 +164,8 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * are and also makes the plan readable).
  * Additive to 9: "near_path", "near_splits", "near_split_max" - written by poi_score_topk_near in the same way.
  * Additive to 9: "rank_splits" - written by poi_score_rank in the same way.
- * Additive to 9: "geoie_score_span", "geoie_score_splits" - written by poi_geoie_score_all_geo / poi_geoie_score_topk_geo in the same way. */
+ * Additive to 9: "geoie_score_span", "geoie_score_splits" - written by poi_geoie_score_all_geo / poi_geoie_score_topk_geo in the same way.
+ * Additive to 9: "group_path", "group_splits", "group_split_max" - written by poi_group_topk in the same way. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -234,7 +237,11 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *   "near_grid" n (default 0 = by the row count and the CUs; at most 64): slices per row on that split path - bitwise the same result for
  *       every n and on either path.
  *   "rank_grid" n (default 0 = by the row count and the CUs): poi_score_rank splits the item range of a 32-row tile over at most n
- *       wavefronts (never fewer than ceil(item tiles / 65535)) - identical ranks for every n. */
+ *       wavefronts (never fewer than ceil(item tiles / 65535)) - identical ranks for every n.
+ *   "group_split_max" n (default 256): poi_group_topk calls of at most n groups cut the item range into slices, a workgroup each, and merge
+ *       the slices' lists (0: never); larger calls run one workgroup per 8 groups;
+ *   "group_grid" n (default 0 = by the group count and the CUs; at most 64): slices on that split path - bitwise the same result for
+ *       every n and on either path. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -895,6 +902,50 @@ int poi_score_rank(poi_ctx* ctx, const float* users, const float* items, int32_t
  * users . items, and an independent check of the counting.  NaN scores count as below every target.  Timing name: "rank_scores". */
 int poi_rank_scores(poi_ctx* ctx, const float* scores, int32_t n, int32_t n_item, const int32_t* tgt, const int32_t* tmask, int32_t len_t,
                     const int32_t* ex_off, const int32_t* ex, int32_t* rank_out, int32_t* count_out, void* stream);
+
+/* ---- group recommendation (additive to 9): the top-K of an aggregate of the members' scores, for a party of users -----------------------
+ * Every other ranking entry answers for one user row.  A party - friends choosing a place, a family on a trip - is ranked by an
+ * aggregate of its members' scores, which is not the score of any single row: the minimum is not linear, and under the distance term
+ * every member stands at a last POI of their own.  These entries rank n_grp groups without the (members, n_item) score matrix.
+ *   users, g_off, g_mem   n member rows users (n, dim); the groups as a CSR: g_off (n_grp + 1) ascending offsets into g_mem, g_mem row
+ *                         indices into users.  A row listed twice counts twice.
+ *   s(m, j)               exactly poi_score_rank's s(r, j): users[m] . items[j] in float32 from the same product routine and k order
+ *                         (f32 matrix pipe, exact products); with wd non-NULL plus wd * sts[m][bin(last_poi[m], j)] for bin < n_dist - the
+ *                         arguments and the rule of poi_score_topk_geo (sts (n, n_dist + 1)).  A member with last_poi[m] < 0 has no distance
+ *                         term.  wd NULL: the plain score; sts / coords / cphi / thr / last_poi are then ignored.
+ *   a(g, j), agg = 1      least misery: the minimum of s(m, j) over the group's list.  Exact: permuting the list changes no bit of the
+ *                         output (a zero comes out as +0 whichever sign the members' zeros have).
+ *   a(g, j), agg = 0      mean: the float32 sum of s(m, j) over the list divided by float(M), one IEEE division.  ORDER OF THE ADDITIONS: a
+ *                         left-to-right chain in list order, ((s(m_0) + s(m_1)) + s(m_2)) + ... - a function of the members' positions in
+ *                         the group's list alone, not of the grid, of how the item range is cut, of the group's place in the call or of
+ *                         the other groups.
+ *   NaN                   a POI for which any member's score is NaN is never selected.
+ *   C(g)                  [0, n_item) minus ex[ex_off[g] .. ex_off[g + 1]): ONE exclusion list per group, the conventions of
+ *                         poi_score_topk_near (ascending unique ids; both pointers NULL = none).
+ *   outputs               idx_out (n_grp, k), k <= 32, by descending a, ties by ascending id; -1 ids and -inf scores where |C(g)| < k;
+ *                         score_out (n_grp, k) or NULL; count_out (n_grp) or NULL = |C(g)|.
+ *   bad groups            a member outside [0, n), descending g_off, an exclusion id outside [0, n_item) or a list that is not ascending:
+ *                         the group is all -1 / -inf / count 0 and is counted once (poi_ctx_take_bad_ids).
+ *   empty group           all -1 / -inf, count 0, not counted.  n_grp = 0 is a no-op.  Any group size: a list longer than the 32 rows of a
+ *                         tile is walked in chunks and the aggregate carried from chunk to chunk.
+ *   items                 float32 or a registered half table; rows >= n_item (the padding row) are never read.  dim: a multiple of 4, <= 256.
+ * No float atomics: identical calls give bitwise identical outputs, every grid and split gives the same outputs as every other, and a
+ * group gives the same outputs alone as inside a larger call.
+ * Two launch regimes: calls of at most "group_split_max" groups (poi_ctx_set_option, default 256: live traffic, often one party) cut
+ * the item range into "group_grid" slices, one workgroup each, and merge the slices' lists in a second kernel; larger calls run one
+ * workgroup per 8 groups, which it packs whole into passes of at most 32 member rows.  poi_ctx_last_plan: "group_path" (0 tile, 1 split),
+ * "group_splits" (slices, 0 on the tile path), "group_split_max" (the switch point in force).  Timing name: "group_topk". */
+int poi_group_topk(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                   const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                   int32_t n_dist, double dd,
+                   const int32_t* g_off, const int32_t* g_mem, int32_t n_grp, int32_t agg, const int32_t* ex_off, const int32_t* ex,
+                   int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+/* The same definition on explicit score rows scores (n, n_item), g_mem indexing its rows - to poi_group_topk what poi_rank_scores is to
+ * poi_score_rank: for the models whose score is not users . items, and an independent check of the aggregation and the selection.
+ * One workgroup per group.  Timing name: "group_topk_scores". */
+int poi_group_topk_scores(poi_ctx* ctx, const float* scores, int32_t n, int32_t n_item,
+                          const int32_t* g_off, const int32_t* g_mem, int32_t n_grp, int32_t agg, const int32_t* ex_off, const int32_t* ex,
+                          int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
 
 /* ---- fold-in (additive to 9): a user row of OboBpr / OboVBpr for a check-in history the model never trained on -------------------------------
  * The factorisation family's only user representation is a trained row of ux (and ue).  Fold-in freezes the item side and runs the

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libpoi_hip.so")
 SOURCES = ["abi.hip", "seq_engine.hip", "exact_engine.hip", "tile_engine.hip", "te_scatter.hip", "te_xfwd.hip", "bpr.hip", "score_topk.hip", "score_filter.hip",
-           "misc.hip", "sync.hip", "carnn.hip", "fpmc.hip", "prme.hip", "geoie.hip", "geoie_score.hip", "poi2vec.hip", "cells.hip", "session.hip", "session_cells.hip", "vbpr.hip", "near.hip", "rank.hip", "foldin.hip", "foldin_seq.hip", "foldin_p2v.hip"]
+           "misc.hip", "sync.hip", "carnn.hip", "fpmc.hip", "prme.hip", "geoie.hip", "geoie_score.hip", "poi2vec.hip", "cells.hip", "session.hip", "session_cells.hip", "vbpr.hip", "near.hip", "rank.hip", "group.hip", "foldin.hip", "foldin_seq.hip", "foldin_p2v.hip"]
 HEADERS = ["poi_common.h", "poi_kernels.h", "seq_common.h", "geoie_pair.h", "topk_list.h", "session_common.h", os.path.join("..", "..", "include", "poi_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 

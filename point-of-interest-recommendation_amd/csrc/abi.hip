@@ -79,7 +79,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR
@@ -113,6 +113,10 @@ struct poi_ctx {
   // exact target ranks (rank.hip): the targets' scores and ids, pass 1 -> pass 2
   DevBuf rank_ws;
   int rank_grid = 0;        // option "rank_grid": cap of the item ranges a 32-row tile is split into (0: by the row count and the CUs)
+  // group recommendation (group.hip): per (group, slice) partial lists of the split path
+  DevBuf group_ws;
+  int group_split_max = 256; // option "group_split_max": poi_group_topk calls of at most this many groups cut the item range into slices, a workgroup each
+  int group_grid = 0;       // option "group_grid": slices on the split path (0: by the group count and the CUs)
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)
@@ -248,7 +252,7 @@ int poi_ctx_destroy(poi_ctx* c) {
   if (!c) return POI_OK;
   DevBuf* all[] = {&c->ex_ws, &c->ex_slab, &c->ex_glt, &c->ex_gdi, &c->ws, &c->slab, &c->te_ws, &c->hslab, &c->zrow, &c->g_lt, &c->mult_lt, &c->nseq_lt, &c->g_di, &c->mult_di, &c->nseq_di, &c->seg_s, &c->seg_e, &c->pmark, &c->xc, &c->kc_dev, &c->uidx_stage, &c->out_stage, &c->ptab, &c->iota, &c->xw, &c->xg, &c->xflag, &c->bad_ids,
                    &c->g_wd, &c->mult_wd, &c->nseq_wd, &c->ca_ws, &c->ca_slab, &c->ca_scr, &c->ca2, &c->g_ux, &c->cnt_ux, &c->g_blt, &c->cnt_blt, &c->cand_s, &c->cand_i, &c->items_pk, &c->gbound, &c->st,
-                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->pv_fold, &c->cell_ws, &c->vb_ws, &c->rank_ws, &c->sess_wrs, &c->geo_ws};
+                   &c->items_pk16, &c->inorm, &c->surv_cnt, &c->surv_idx, &c->surv_sc, &c->tflag, &c->pre_idx, &c->pre_sc, &c->users_pk16, &c->ubound, &c->ugeo, &c->fp_ws, &c->pr_ws, &c->ge_ws, &c->pv_ws, &c->pv_sc, &c->pv_fold, &c->cell_ws, &c->vb_ws, &c->rank_ws, &c->sess_wrs, &c->geo_ws, &c->group_ws};
   (void)hipDeviceSynchronize();
   c->tm.clear();
   drop_graphs(c);
@@ -1974,6 +1978,80 @@ int poi_rank_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// group recommendation (group.hip)
+static int group_check_args(poi_ctx* c, const char* who, int32_t n, int32_t n_item, const int32_t* g_off, const int32_t* g_mem, int32_t n_grp,
+                            int32_t agg, const int32_t* ex_off, const int32_t* ex, int32_t k, const int32_t* idx_out) {
+  if (!g_off || !g_mem || !idx_out) return fail(c, POI_EINVAL, "%s: NULL g_off / g_mem / idx_out", who);
+  if (k <= 0 || k > GROUP_K_MAX) return fail(c, POI_ENOTSUP, "%s supports 1 <= k <= %d (got %d)", who, GROUP_K_MAX, k);
+  if (agg < 0 || agg > 1) return fail(c, POI_EINVAL, "%s: agg must be 0 (mean) or 1 (least misery) (got %d)", who, agg);
+  if (n < 0 || n_item <= 0 || n_grp < 0) return fail(c, POI_EINVAL, "%s: n < 0, n_item <= 0 or n_grp < 0", who);
+  if ((ex_off == nullptr) != (ex == nullptr)) return fail(c, POI_EINVAL, "%s: ex_off and ex go together", who);
+  return POI_OK;
+}
+
+int poi_group_topk(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                   const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                   const int32_t* g_off, const int32_t* g_mem, int32_t n_grp, int32_t agg, const int32_t* ex_off, const int32_t* ex, int32_t k,
+                   int32_t* idx_out, float* score_out, int32_t* count_out, void* stream) {
+  if (!c || !items || (!users && n > 0)) return fail(c, POI_EINVAL, "poi_group_topk: NULL ctx / users / items");
+  int rc;
+  if ((rc = group_check_args(c, "poi_group_topk", n, n_item, g_off, g_mem, n_grp, agg, ex_off, ex, k, idx_out))) return rc;
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_group_topk: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  const bool geo = wd != nullptr;
+  if (geo && (!sts || !coords || !cphi || !thr || !last_poi)) return fail(c, POI_EINVAL, "poi_group_topk: the distance term needs sts / coords / cphi / thr / last_poi");
+  if (geo && (n_dist <= 0 || !(dd > 0))) return fail(c, POI_EINVAL, "poi_group_topk: the distance term needs n_dist > 0 and dd > 0");
+  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "poi_group_topk: users must be float32");
+  if (n_grp == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::GroupArgs A = {};
+  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
+  A.n = n; A.n_item = n_item; A.dim = dim; A.k = k; A.n_grp = n_grp; A.agg = agg;
+  if (geo) { A.wd = wd; A.sts = sts; A.coords = coords; A.cphi = cphi; A.thr = thr; A.last_poi = last_poi; A.n_dist = n_dist; A.bin_scale = (float)(12742.0 * 1000.0 / dd); }
+  A.g_off = g_off; A.g_mem = g_mem; A.ex_off = ex_off; A.ex = ex;
+  A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  // few groups (live traffic): the item range is cut into slices so that the call fills the CUs; many groups: one workgroup per GROUP_GPT groups
+  const int split = n_grp <= c->group_split_max;
+  const int n_gtile = (n_grp + GROUP_GPT - 1) / GROUP_GPT, ntile = (n_item + 31) / 32;
+  A.n_split = 1;
+  if (split) {
+    int s = c->group_grid > 0 ? c->group_grid : 2 * c->num_cu / n_gtile;
+    if (c->group_grid <= 0 && s > ntile / 16) s = ntile / 16;      // (at least four item tiles per wave)
+    if (c->group_grid <= 0 && s < 2) s = 2;
+    A.n_split = s > GROUP_SPLIT_LIMIT ? GROUP_SPLIT_LIMIT : s;
+    const size_t lists = (size_t)n_grp * A.n_split;
+    if ((rc = ensure(c, c->group_ws, lists * (GROUP_K_MAX * (sizeof(float) + sizeof(int)) + sizeof(int)), st))) return rc;
+    A.part_s = (float*)c->group_ws.p;
+    A.part_i = (int*)(A.part_s + lists * GROUP_K_MAX);
+    A.part_cnt = A.part_i + lists * GROUP_K_MAX;
+  }
+  c->plan.valid = 1; c->plan.group_path = split; c->plan.group_splits = split ? A.n_split : 0; c->plan.group_split_max = c->group_split_max;
+  HIPCHK(c, poi::launch_group(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_group_topk_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, const int32_t* g_off, const int32_t* g_mem, int32_t n_grp,
+                          int32_t agg, const int32_t* ex_off, const int32_t* ex, int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out,
+                          void* stream) {
+  if (!c || (!scores && n > 0)) return fail(c, POI_EINVAL, "poi_group_topk_scores: NULL ctx / scores");
+  int rc;
+  if ((rc = group_check_args(c, "poi_group_topk_scores", n, n_item, g_off, g_mem, n_grp, agg, ex_off, ex, k, idx_out))) return rc;
+  if (n_grp == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::GroupArgs A = {};
+  A.n = n; A.n_item = n_item; A.k = k; A.n_grp = n_grp; A.agg = agg; A.n_split = 1;
+  A.g_off = g_off; A.g_mem = g_mem; A.ex_off = ex_off; A.ex = ex;
+  A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
+  if ((rc = ensure(c, c->bad_ids, 64, st))) return rc;
+  A.bad = (int*)c->bad_ids.p;
+  HIPCHK(c, poi::launch_group_scores(scores, A, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // fold-in of new users (foldin.hip)
 int poi_foldin_bpr(poi_ctx* c, const float* items, int32_t n_item, int32_t dim, const int32_t* off, const int32_t* p, const int32_t* q,
                    int64_t q_epoch_stride, int32_t n, int32_t epochs, float alpha, float lambda, const float* w0, float* w_out,
@@ -2203,7 +2281,8 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
                       {"early_bins", &c->early_bins, 0, 1}, {"hot_bins", &c->hot_bins, 0, 1}, {"hybrid", &c->hybrid, 0, 1}, {"hybrid_min", &c->hyb_min, 0, 1 << 30}, {"hybrid_max", &c->hyb_max, 0, 1 << 30}, {"hybrid_force", &c->hyb_force, 0, 1 << 30},
                       {"cell_grid", &c->cell_grid, 0, 1 << 30}, {"vbpr_grid", &c->vbpr_grid, 0, 1 << 30}, {"session_tile_min", &c->sess_tile_min, 1, 1 << 30},
                       {"near_split_max", &c->near_split_max, 0, 1 << 30}, {"near_grid", &c->near_grid, 0, NEAR_SPLIT_LIMIT},
-                      {"rank_grid", &c->rank_grid, 0, 1 << 30}, {"geoie_score_span", &c->geo_span, 0, 1 << 30}};
+                      {"rank_grid", &c->rank_grid, 0, 1 << 30}, {"geoie_score_span", &c->geo_span, 0, 1 << 30},
+                      {"group_split_max", &c->group_split_max, 0, 1 << 30}, {"group_grid", &c->group_grid, 0, GROUP_SPLIT_LIMIT}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);
@@ -2285,7 +2364,8 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"session_tile_min", &poi_ctx::LastPlan::session_tile_min}, {"near_path", &poi_ctx::LastPlan::near_path},
       {"near_splits", &poi_ctx::LastPlan::near_splits}, {"near_split_max", &poi_ctx::LastPlan::near_split_max},
       {"rank_splits", &poi_ctx::LastPlan::rank_splits}, {"geoie_score_span", &poi_ctx::LastPlan::geoie_score_span},
-      {"geoie_score_splits", &poi_ctx::LastPlan::geoie_score_splits}};
+      {"geoie_score_splits", &poi_ctx::LastPlan::geoie_score_splits}, {"group_path", &poi_ctx::LastPlan::group_path},
+      {"group_splits", &poi_ctx::LastPlan::group_splits}, {"group_split_max", &poi_ctx::LastPlan::group_split_max}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

@@ -616,6 +616,24 @@ hipError_t launch_rank(const RankArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_rank_scores(const float* scores, int n, int n_item, const int* tgt, const int* tmask, int len_t, const int* ex_off,
                               const int* ex, int* rank_out, int* count_out, int* bad, hipStream_t st);
 
+// Group recommendation (group.hip): top-K of an aggregate (mean / least misery) of the members' scores
+#define GROUP_K_MAX 32                      // list length (one half wave)
+#define GROUP_GPT 8                         // groups a workgroup owns; it packs them into passes of at most 32 member rows
+#define GROUP_SPLIT_LIMIT 64                // workgroups the item range may be split over
+struct GroupArgs {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim, k, n_grp, agg;                          // agg: 0 mean, 1 least misery
+  const float *wd, *sts; const double *coords, *cphi, *thr; const int* last_poi; int n_dist; float bin_scale;      // distance term, or wd null
+  const int *g_off, *g_mem;                                   // CSR of the groups' member rows
+  const int *ex_off, *ex;                                     // per-group exclusion lists (ascending ids), or both null
+  int n_split;                                                // item slices, one workgroup each (1 on the tile path)
+  float* part_s; int *part_i, *part_cnt;                      // split path: (n_grp, n_split, GROUP_K_MAX) partial lists, (n_grp, n_split) counts
+  int* idx_out; float* score_out; int* count_out;             // score_out / count_out may be null
+  int* bad;                                                   // device counter of rejected groups (poi_ctx_take_bad_ids)
+};
+hipError_t launch_group(GroupArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_group_scores(const float* scores, GroupArgs& A, hipStream_t st, Timing* tm);
+
 // Fold-in of new users for the factorisation family (foldin.hip)
 #define FOLDIN_USERS_PER_WAVE 4             // one 16-lane DPP row per user
 struct FoldinArgs {

@@ -7,7 +7,7 @@
 //
 // Pass 1 (rank_targets_kernel, one wave per 32-row tile): the scores of the row's targets.  The B operand of the tile product is the
 // gathered item rows of the 32 rows' i-th targets, the row's own score is the diagonal of the 32x32 result: the SAME product routine
-// (tile_product: v_mfma_f32_32x32x2_f32 in one k order) and the same distance-term expression as pass 2, so a POI whose item row equals
+// (tile_product, tile_product.h: v_mfma_f32_32x32x2_f32 in one k order) and the same distance-term expression as pass 2, so a POI whose item row equals
 // the target's ties bit for bit and the index rule decides.  The pass also validates: a masked position, a target outside [0, n_item)
 // (counted), an excluded target and every target of a row with a malformed exclusion list (counted once) get rank -1 and take no part
 // in pass 2; the other ranks start at 0.
@@ -27,57 +27,10 @@
 // rank_scores_kernel applies the same definition to explicit score rows (poi_rank_scores: the counterpart of poi_topk).
 #include "poi_common.h"
 #include "poi_kernels.h"
+#include "tile_product.h"
 #include <limits.h>
 
 namespace poi {
-
-namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// row `row` of a (rows, D) table in fragment order: lane half h holds the k-columns 8m + 4h .. 8m + 4h + 3, one float4 per m
-template <int D8>
-__device__ __forceinline__ void load_frag(float4 (&f)[D8], const void* base, int f16, size_t row, int D, int h) {
-#pragma unroll
-  for (int m = 0; m < D8; ++m) {
-    const int k0 = 8 * m + 4 * h;
-    f[m] = k0 < D ? ld4t(base, row * D + k0, f16) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-
-// THE product of both passes: acc[item = lane & 31][row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)], one fixed k order
-template <int D8>
-__device__ __forceinline__ f32x16 tile_product(const float4 (&a)[D8], const float4 (&b)[D8]) {
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-  for (int m = 0; m < D8; ++m) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].x, b[m].x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].y, b[m].y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].z, b[m].z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].w, b[m].w, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// the distance term's probability of (row, item): sts[row][bin] for bin < n_dist, the bin from the float64 Haversine term through thr
-__device__ __forceinline__ float geo_prob(const RankArgs& A, const double* thr, int row, double ulat, double ulon, double ucp, double jlat,
-                                          double jlon, double jcp) {
-  const int bin = bin_of_c(haversine_c(ulat, ulon, ucp, jlat, jlon, jcp), thr, A.n_dist, A.bin_scale);
-  return bin < A.n_dist ? A.sts[(size_t)row * (A.n_dist + 1) + bin] : 0.f;
-}
-
-// ascending list ex[a .. b): does it hold id?
-__device__ __forceinline__ bool listed(const int* ex, int a, int b, int id) {
-  const int e1 = b;
-  while (a < b) { const int md = (a + b) >> 1; if (ex[md] < id) a = md + 1; else b = md; }
-  return a < e1 && ex[a] == id;
-}
-
-__device__ __forceinline__ float pos_inf() { return __builtin_huge_valf(); }
-
-}  // namespace
 
 template <int D8, bool GEO>
 __global__ __launch_bounds__(64) void rank_targets_kernel(RankArgs A) {

@@ -152,6 +152,31 @@ def train_exclusion_csr(off, p_flat, n_item):
     return eo, (key % (n_item + 1)).astype(np.int32)
 
 
+def group_exclusion_csr(ex_off, ex_ids, g_off, g_mem, n_item):
+    """One exclusion list per GROUP from per-user lists: the sorted union of the members' lists, as a CSR (off int64 (n_grp + 1), ids
+    int32) - with (ex_off, ex_ids) = train_exclusion_csr(...) the exclude="train" lists of recommend_group: a POI any member has visited
+    leaves the group's ranking.  g_off (n_grp + 1) ascending offsets from 0 into g_mem (ValueError), g_mem user ids inside the per-user
+    CSR (IndexError); a user listed twice counts once, an empty group gets an empty list."""
+    eo = np.asarray(ex_off, np.int64).reshape(-1)
+    ex = np.asarray(ex_ids, np.int64).reshape(-1)
+    go = np.asarray(g_off, np.int64).reshape(-1)
+    gm = np.asarray(g_mem, np.int64).reshape(-1)
+    if len(go) < 1 or go[0] != 0 or go[-1] != len(gm) or np.any(np.diff(go) < 0):
+        raise ValueError("g_off must hold ascending offsets from 0 to len(g_mem) = %d" % len(gm))
+    if gm.size and (gm.min() < 0 or gm.max() >= len(eo) - 1):
+        raise IndexError("group members must lie in [0, %d) (found %d..%d)" % (len(eo) - 1, int(gm.min()), int(gm.max())))
+    n_grp = len(go) - 1
+    grp = np.repeat(np.arange(n_grp), np.diff(go))                        # the group of every member occurrence
+    beg, ln = eo[gm], eo[gm + 1] - eo[gm]
+    pos = np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln - beg, ln)
+    key = np.unique(np.repeat(grp, ln) * (n_item + 1) + ex[pos])          # sorted by (group, POI), duplicates dropped
+    off = np.zeros(n_grp + 1, np.int64)
+    np.cumsum(np.bincount(key // (n_item + 1), minlength=n_grp), out=off[1:])
+    if off[-1] >= 1 << 31:
+        raise ValueError("the group exclusion lists hold %d ids: above 2^31" % off[-1])
+    return off, (key % (n_item + 1)).astype(np.int32)
+
+
 def last_exclusion_csr(anchor):
     """exclude="last" as a CSR: row r lists anchor[r] alone; a row without an anchor (-1) excludes nothing."""
     a = np.asarray(anchor, np.int64).reshape(-1)

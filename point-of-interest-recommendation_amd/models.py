@@ -678,6 +678,159 @@ class _Base:
         return self._rank_launch(users, items, self._rank_term(ids, lo), tgt, tm, ex, return_scores, return_counts, sync)
 
 
+    # ---- group recommendation (poi_group_topk / poi_group_topk_scores): the top-K of an aggregate of the members' scores ---------------
+    _GROUP_AGG = {"mean": 0, "min": 1}
+
+    @staticmethod
+    def _group_csr(groups, hi, what):
+        """groups -> (off, ids, on_device): int64 host arrays.  A tuple (off, ids) is a CSR, anything else a list of id lists.  Host data
+        is checked here (ValueError / IndexError before any launch).  Of a device CSR only the offsets' range is checked (they address
+        memory; reading them is one sync): the order of its offsets and its ids are left to the kernel."""
+        on_device = False
+        if isinstance(groups, tuple) and len(groups) == 2:
+            off, ids = groups
+            on_device = isinstance(off, torch.Tensor) and isinstance(ids, torch.Tensor) and (off.is_cuda or ids.is_cuda)
+            off = np.asarray(off.cpu().numpy() if isinstance(off, torch.Tensor) else off, np.int64).reshape(-1)
+            ids = np.asarray(ids.cpu().numpy() if isinstance(ids, torch.Tensor) else ids, np.int64).reshape(-1)
+            if len(off) < 1 or off.min() < 0 or off.max() > len(ids):
+                raise ValueError("%s=(off, ids): the offsets must lie in [0, len(ids) = %d]" % (what, len(ids)))
+            if not on_device and (off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0)):
+                raise ValueError("%s=(off, ids): off must hold ascending offsets from 0 to len(ids) = %d" % (what, len(ids)))
+        else:
+            lists = [np.atleast_1d(np.asarray(g, np.int64)).reshape(-1) for g in groups]
+            off = np.zeros(len(lists) + 1, np.int64)
+            np.cumsum([len(g) for g in lists], out=off[1:])
+            ids = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+        if not on_device and ids.size and (ids.min() < 0 or ids.max() >= hi):
+            raise IndexError("%s: ids must lie in [0, %d) (found %d..%d)" % (what, hi, int(ids.min()), int(ids.max())))
+        return off, ids, on_device
+
+    @staticmethod
+    def _group_members(ids, hi):
+        """(distinct valid ids ascending, member -> index into them; -1 for an id outside [0, hi): the kernel rejects that group)."""
+        valid = (ids >= 0) & (ids < hi)
+        uniq, inv = np.unique(ids[valid], return_inverse=True)
+        mem = np.full(len(ids), -1, np.int32)
+        mem[valid] = inv.astype(np.int32)
+        return uniq, mem
+
+    def _group_args(self, k, agg):
+        k = int(k)
+        if not 1 <= k <= 32:
+            raise _lib.PoiError("group recommendation supports 1 <= k <= 32 (got %d)" % k)
+        if agg not in self._GROUP_AGG:
+            raise ValueError("agg must be 'mean' or 'min' (got %r)" % (agg,))
+        return k, self._GROUP_AGG[agg]
+
+    def _group_exclusion(self, exclude, off, ids, n_grp, kinds=("train",)):
+        """exclude -> (ex_off (n_grp + 1), ex) int32 device tensors, or (None, None): ONE list per group."""
+        if isinstance(exclude, str) and exclude == "train" and "train" in kinds:
+            from .data import group_exclusion_csr
+            host = self.__dict__.get("_near_train_host")
+            if host is None:
+                host = self._near_train_host = tuple(t.cpu().numpy() for t in self.train_exclusion())
+            eo, ex = group_exclusion_csr(host[0], host[1], off, ids, self.n_item)      # (checks the lists on the host, device tensors included)
+            i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+            return i32(eo), (i32(ex) if len(ex) else torch.zeros(1, dtype=torch.int32, device=self.device))
+        return self._near_exclusion(exclude, n_grp, None, kinds=())
+
+    def _group_out(self, idx, sc, cnt, return_scores, return_counts, sync):
+        if sync:
+            bad = self.ctx.take_bad_ids(self._stream().value)
+            if bad:
+                raise IndexError("%d group(s) with a member out of range, descending offsets or a malformed exclusion list: their lists are all -1" % bad)
+        out = (idx,) + ((sc,) if return_scores else ()) + ((cnt,) if return_counts else ())
+        return out if len(out) > 1 else idx
+
+    def _group_launch(self, users, items, term, g_off, g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync):
+        """One poi_group_topk call -> idx[, scores][, counts] (device tensors).  term: (wd, sts rows, last POI rows) or None."""
+        idx = torch.empty((n_grp, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n_grp, k), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n_grp, dtype=torch.int32, device=self.device) if return_counts else None
+        wd = sts = lp = coords = cphi = thr = None
+        n_dist, dd_m = 0, 0.0
+        if term is not None:
+            wd, sts, lp = term
+            coords, cphi, thr, n_dist, dd_m = self.coords, self._cphi, self._binthr, self.n_dist, self.dd * 1000.0
+        self.ctx.check(self.lib.poi_group_topk(self.ctx.handle, _ptr(users), _ptr(items), users.shape[0], self.n_item, self.kdim, _ptr(wd), _ptr(sts),
+                                               _ptr(coords), _ptr(cphi), _ptr(thr), _ptr(lp), int(n_dist), float(dd_m), _ptr(g_off), _ptr(g_mem), n_grp,
+                                               agg, _ptr(ex[0]), _ptr(ex[1]), k, _ptr(idx), _ptr(sc), _ptr(cnt), self._stream()))
+        return self._group_out(idx, sc, cnt, return_scores, return_counts, sync)
+
+    def _group_from_scores(self, off, ids, agg, ex, k, return_scores, return_counts, sync):
+        """Explicit score rows (_rank_score_rows), whole groups at a time within the _rank_chunk budget of rows, + poi_group_topk_scores."""
+        n_grp = len(off) - 1
+        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+        idx = torch.empty((n_grp, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n_grp, k), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n_grp, dtype=torch.int32, device=self.device) if return_counts else None
+        valid = (ids >= 0) & (ids < self.n_user)
+        budget = self._rank_chunk(max(int(np.unique(ids[valid]).size), 1))
+        rows_of = lambda g: ids[off[g]:off[g + 1]][valid[off[g]:off[g + 1]]] if off[g + 1] > off[g] else ids[:0]
+        g = 0
+        while g < n_grp:
+            seen = set(rows_of(g).tolist())
+            if len(seen) > budget:
+                raise _lib.PoiError("group %d has %d distinct members: above the %d score rows one call may build" % (g, len(seen), budget))
+            g2 = g + 1
+            while g2 < n_grp:
+                more = seen | set(rows_of(g2).tolist())
+                if len(more) > budget:
+                    break
+                seen, g2 = more, g2 + 1
+            a = np.array(sorted(seen), np.int64)
+            full = None
+            if len(a):
+                full, per = self._rank_score_rows(a)
+                if per > 1:                                  # (user, position) rows: the user's next POI is position 0
+                    full = full.view(len(a), per, self.n_item)[:, 0].contiguous()
+            lo_, hi_ = int(off[g]), int(max(off[g2], off[g]))
+            sub, ok = ids[lo_:hi_], valid[lo_:hi_]
+            mem = np.full(hi_ - lo_, -1, np.int32)
+            mem[ok] = np.searchsorted(a, sub[ok]).astype(np.int32)
+            g_off, g_mem = i32(off[g:g2 + 1] - off[g]), (i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=self.device))
+            eo = ex[0][g:g2 + 1].contiguous() if ex[0] is not None else None
+            at = lambda t, w: ctypes.c_void_p(t.data_ptr() + 4 * g * w) if t is not None else None
+            self.ctx.check(self.lib.poi_group_topk_scores(self.ctx.handle, _ptr(full), len(a), self.n_item, _ptr(g_off), _ptr(g_mem), g2 - g, agg,
+                                                          _ptr(eo), _ptr(ex[1]), k, at(idx, k), at(sc, k), at(cnt, 1), self._stream()))
+            g = g2
+        return self._group_out(idx, sc, cnt, return_scores, return_counts, sync)
+
+    def recommend_group(self, groups, k, agg="mean", exclude=None, return_scores=False, return_counts=False, sync=True):
+        """Top-K for PARTIES of users (include/poi_hip.h, poi_group_topk): every POI is scored for every member with the model's own rule
+        and the members' scores are aggregated - agg="mean" (the float32 sum in list order divided by the group size) or agg="min" (least
+        misery: the score of the unhappiest member) - without the (members, n_item) score matrix.  groups: a list of lists of user ids,
+        or a CSR pair (off, ids); a user listed twice counts twice.  exclude: None, "train" (the sorted union of the members' distinct
+        train POIs leaves the ranking: data.group_exclusion_csr) or CSR lists (off, ids), ONE list per group, ids ascending and unique.
+        Returns (n_grp, k) int32 ids by descending aggregate (k <= 32), ties by ascending id, -1 where a group has fewer than k
+        candidates (scores -inf); with return_counts the candidate count of every group.  An empty group is all -1, count 0.
+        Host arguments are checked before the launch; device tensors are checked by the kernel: an offending group comes out all -1
+        and - with sync - raises IndexError (sync=False leaves the count to ctx.take_bad_ids()).  The models that score by
+        users . items gather each distinct member's row once and take the fused kernel; CA-RNN, PRME, POI2Vec (the score of the
+        user's next position) and GeoIE under rule="geo" go through their own score rows, whole groups at a time, and
+        poi_group_topk_scores."""
+        k, agg = self._group_args(k, agg)
+        off, ids, on_device = self._group_csr(groups, self.n_user, "groups")
+        n_grp = len(off) - 1
+        ex = self._group_exclusion(exclude, off, ids, n_grp)
+        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+        fused = self._rank_fused
+        if n_grp == 0:
+            return self._group_out(torch.empty((0, k), dtype=torch.int32, device=self.device), torch.empty((0, k), dtype=torch.float32, device=self.device),
+                                   torch.empty(0, dtype=torch.int32, device=self.device), return_scores, return_counts, False)
+        if not fused:
+            return self._group_from_scores(off, ids, agg, ex, k, return_scores, return_counts, sync)
+        uniq, mem = self._group_members(ids, self.n_user)
+        if len(uniq):
+            uid, users, lo = self._users_rows(uniq)
+            term = self._rank_term(uid, lo)
+        else:                                            # no valid member anywhere: nothing is gathered, every group is empty or rejected
+            users, term = torch.zeros((0, self.kdim), dtype=torch.float32, device=self.device), None
+        items = self._items() if hasattr(self, "_items") else self.trained_items.t
+        g_mem = i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._group_launch(users.contiguous(), items, term, i32(off), g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync)
+
+
 # =================================================================================================
 class GruBasic(_Base):
     """public/GRU.py:32-205."""
@@ -1593,6 +1746,31 @@ class Session:
         return m._rank_launch(users, m.trained_items.t, term, tgt, tm, ex, return_scores, return_counts, sync)
 
 
+    def recommend_group(self, slot_groups, k, agg="mean", exclude=None, return_scores=False, return_counts=False, sync=True):
+        """model.recommend_group over the slots' CURRENT states (h, sts, last_poi, as `rank_of` assembles them): slot_groups is a list of
+        lists of slot ids or a CSR pair (off, ids); agg "mean" or "min"; exclude None or CSR lists (off, ids), one per group.  A slot
+        without a check-in has no distance term."""
+        m = self.m
+        k, agg = m._group_args(k, agg)
+        off, ids, on_device = m._group_csr(slot_groups, self.n_slot, "slot_groups")
+        n_grp = len(off) - 1
+        if n_grp == 0:
+            return m._group_out(torch.empty((0, k), dtype=torch.int32, device=m.device), torch.empty((0, k), dtype=torch.float32, device=m.device),
+                                torch.empty(0, dtype=torch.int32, device=m.device), return_scores, return_counts, False)
+        ex = m._group_exclusion(exclude, off, ids, n_grp, kinds=())
+        uniq, mem = m._group_members(ids, self.n_slot)
+        sl = torch.as_tensor(uniq).to(m.device)
+        users = self.h.index_select(0, sl).float().contiguous()
+        term = None
+        if self.spatial and len(uniq):
+            lpr = self.last_poi.index_select(0, sl).contiguous()
+            st = (self.sts.index_select(0, sl) * (lpr >= 0).float()[:, None]).contiguous()
+            st[:, m.n_dist] = 0.0
+            term = (m.wd.t, st, lpr)
+        g_mem = self._i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=m.device)
+        return m._group_launch(users, m.trained_items.t, term, self._i32(off), g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync)
+
+
 class CellSession(Session):
     """Online sessions of the baselines `Lstm`, `Rnn` and `OboCARNN` (model.cell_session()): the slot bookkeeping, `advance`, `replay`
     and the repeated-slot rule of `Session` over the cell steps of poi_session_cell_advance / poi_session_carnn_advance
@@ -1728,6 +1906,13 @@ class CellSession(Session):
         if sc is not None:
             sc = torch.where(has[:, None], sc, torch.full_like(sc, float("nan")))
         return (idx, sc) if return_scores else idx
+
+    def recommend_group(self, slot_groups, k, agg="mean", exclude=None, return_scores=False, return_counts=False, sync=True):
+        """Lstm / Rnn: `Session.recommend_group`'s plain rule.  CA-RNN ranks by a rule of its own and is refused."""
+        if self.carnn:
+            raise _lib.PoiError("OboCARNN ranks by a score rule of its own, not users . items: recommend_group is not supported on its sessions "
+                                "(model.recommend_group covers the trained users)")
+        return super().recommend_group(slot_groups, k, agg, exclude, return_scores, return_counts, sync)
 
     def rank_of(self, slots, pois, exclude=None, return_scores=False, return_counts=False, sync=True):
         """Exact 0-based rank of pois[i] (one POI per slot, or (n, len_t <= 8)) among all POIs under the slot's CURRENT state and the
