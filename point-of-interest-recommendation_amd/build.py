@@ -12,9 +12,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libpoi_hip.so")
-SOURCES = ["abi.hip", "seq_engine.hip", "exact_engine.hip", "tile_engine.hip", "te_scatter.hip", "te_xfwd.hip", "bpr.hip", "score_topk.hip", "score_filter.hip",
+SOURCES = ["abi.hip", "abi_train.hip", "abi_serve.hip", "seq_engine.hip", "exact_engine.hip", "tile_engine.hip", "te_scatter.hip", "te_xfwd.hip", "bpr.hip", "score_topk.hip", "score_filter.hip",
            "misc.hip", "sync.hip", "carnn.hip", "fpmc.hip", "prme.hip", "geoie.hip", "geoie_score.hip", "poi2vec.hip", "cells.hip", "session.hip", "session_cells.hip", "vbpr.hip", "near.hip", "rank.hip", "group.hip", "foldin.hip", "foldin_seq.hip", "foldin_p2v.hip"]
-HEADERS = ["poi_common.h", "poi_kernels.h", "seq_common.h", "geoie_pair.h", "topk_list.h", "session_common.h", os.path.join("..", "..", "include", "poi_hip.h")]
+# every header next to the sources, and the public one: a unit is rebuilt when any of them changes
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "poi_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 
@@ -60,7 +61,7 @@ def build_lib(force=False, verbose=True):
     extra = os.environ.get("POI_HIPCC_FLAGS", "").split()
     os.makedirs(OBJ, exist_ok=True)
     srcs = _sources()
-    with cf.ThreadPoolExecutor(max(1, min(len(srcs), os.cpu_count() or 1))) as ex:
+    with cf.ThreadPoolExecutor(max(1, min(len(srcs), os.cpu_count() or 1, 16))) as ex:
         objs = list(ex.map(lambda s: _compile_one(hipcc, s, extra, force and not os.environ.get("POI_BUILD_INCREMENTAL"), verbose), srcs))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB + ".tmp"] + objs + ["-ldl"]
     if verbose:

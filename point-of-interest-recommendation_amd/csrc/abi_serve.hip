@@ -1,0 +1,912 @@
+// C-ABI of libpoi_hip.so (see include/poi_hip.h): everything that answers a query - scoring, top-K, ranks, sessions, fold-ins, metrics, samplers, deltas.
+#include "abi_internal.h"
+
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+extern "C" {
+
+int poi_carnn_score_all(poi_ctx* c, const float* users, const float* items, const float* M, const float* dists, const double* coords,
+                        const double* cphi, const double* thr, const int32_t* last_poi, int32_t n, int32_t n_item, int32_t n_dist, int32_t dim,
+                        double dd, float* scores_out, void* stream) {
+  if (!c || !users || !items || !M || !dists || !coords || !cphi || !thr || !last_poi || !scores_out) return fail(c, POI_EINVAL, "poi_carnn_score_all: NULL argument");
+  if (n < 0 || n_item <= 0 || n_dist <= 0 || dim <= 0 || !(dd > 0)) return fail(c, POI_EINVAL, "bad sizes");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure(c, c->ca_scr, sizeof(float) * ((size_t)(n_dist + 1) * dim + (size_t)n_item + 2048), st))) return rc;
+  for (int32_t o = 0; o < n; o += 32768) {
+    const int32_t m = n - o < 32768 ? n - o : 32768;
+    HIPCHK(c, poi::launch_carnn_score(users + (size_t)o * dim, items, M, dists, coords, cphi, thr, last_poi + o, m, n_item, n_dist, dim, dd,
+                                      (float*)c->ca_scr.p, scores_out + (size_t)o * n_item, st, &c->tm));
+  }
+  return POI_OK;
+}
+
+// PRME scoring (prme.hip)
+static int prme_score_common(poi_ctx* c, const poi_prme_params* P, const double* coords, const int32_t* users, const int32_t* qpoi, int32_t n_rows,
+                             float cw, int32_t k, float* out, int32_t* idx_out, float* score_out, void* stream) {
+  const char* who = k > 0 ? "poi_prme_score_topk" : "poi_prme_score_all";
+  int rc = prme_check(c, P, who);
+  if (rc) return rc;
+  if (!coords || !users || !qpoi || (k > 0 ? !idx_out : !out)) return fail(c, POI_EINVAL, "%s: NULL argument", who);
+  if (n_rows < 0) return fail(c, POI_EINVAL, "%s: n_rows < 0", who);
+  if (k > 0 && (k > 64 || k > P->n_item)) return fail(c, POI_EINVAL, "%s: k must lie in [1, min(64, n_item)] (got %d)", who, k);
+  if (n_rows == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::PrmeScoreArgs A;
+  memset(&A, 0, sizeof A);
+  A.du = P->du; A.dp = P->dp; A.ds = P->ds; A.coords = coords; A.users = users; A.qpoi = qpoi;
+  A.n_rows = n_rows; A.n_user = P->n_user; A.n_item = P->n_item; A.dim = P->dim; A.k = k > 0 ? k : 0; A.cw = cw;
+  A.out = out; A.idx_out = idx_out; A.sc_out = score_out;
+  c->tm.begin(k > 0 ? "prme_score_topk" : "prme_score_all", st);
+  HIPCHK(c, poi::launch_prme_score(A, st));
+  c->tm.end(st);
+  return POI_OK;
+}
+
+int poi_prme_score_all(poi_ctx* c, const poi_prme_params* P, const double* coords, const int32_t* users, const int32_t* qpoi, int32_t n_rows,
+                       float cw, float* out, void* stream) {
+  return prme_score_common(c, P, coords, users, qpoi, n_rows, cw, 0, out, nullptr, nullptr, stream);
+}
+
+int poi_prme_score_topk(poi_ctx* c, const poi_prme_params* P, const double* coords, const int32_t* users, const int32_t* qpoi,
+                        int32_t n_rows, float cw, int32_t k, int32_t* idx_out, float* score_out, void* stream) {
+  if (k <= 0) return fail(c, POI_EINVAL, "poi_prme_score_topk: k must be positive (got %d)", k);
+  return prme_score_common(c, P, coords, users, qpoi, n_rows, cw, k, nullptr, idx_out, score_out, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// scoring under the trained rule (geoie_score.hip): k == 0 writes the (n_rows, n_item) matrix, k > 0 the lists
+static int geoie_score_common(poi_ctx* c, const char* who, const poi_geoie_params* P, const int32_t* off, const int32_t* p, const int32_t* mult,
+                              const float* tu, const int32_t* rows, int32_t n_rows, const double* coords, const double* cphi, double d_min,
+                              float* out, const int32_t* ex_off, const int32_t* ex, int32_t k, int32_t* idx_out, float* score_out,
+                              int32_t* count_out, void* stream) {
+  int rc = geoie_check(c, P, who);
+  if (rc) return rc;
+  if (n_rows < 0) return fail(c, POI_EINVAL, "%s: n_rows < 0", who);
+  if (!(d_min >= 0.0)) return fail(c, POI_EINVAL, "%s: d_min must be >= 0", who);
+  if (int r = check_ex_pair(c, who, ex_off, ex)) return r;
+  if (tu && is_f16(c, tu)) return fail(c, POI_ENOTSUP, "%s: tu must be float32", who);
+  if (n_rows == 0) return POI_OK;
+  if (!off || !p || !coords || !cphi) return fail(c, POI_EINVAL, "%s: NULL off / p / coords / cphi", who);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::GeoScoreArgs A = {};
+  A.g = P->g; A.h = P->h; A.z = P->z; A.ab = P->ab; A.n_item = P->n_item; A.dim = P->dim;
+  A.off = off; A.p = p; A.mult = mult; A.rows = rows; A.tu = tu; A.n_rows = n_rows;
+  A.coords = coords; A.cphi = cphi; A.d_min = d_min;
+  A.out = out; A.k = k; A.ex_off = ex_off; A.ex = ex; A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  // candidates per workgroup: "geoie_score_span", or - so that a call of one history still fills the chip - about 4 workgroups per CU
+  // over the call, at least 256 candidates each
+  int64_t span = c->geo_span;
+  if (span <= 0) {
+    const int64_t want = ((int64_t)4 * c->num_cu + n_rows - 1) / n_rows;
+    span = ((int64_t)P->n_item + want - 1) / want;
+    if (span < 256) span = 256;
+  }
+  span = (span + 15) & ~(int64_t)15;
+  if (span > (int64_t)1 << 30) span = (int64_t)1 << 30;
+  A.span = (int)span;
+  A.n_split = (int)(((int64_t)P->n_item + span - 1) / span);
+  if ((int64_t)n_rows * A.n_split >= ((int64_t)1 << 31) - 1) return fail(c, POI_ENOTSUP, "%s: n_rows x spans per row must stay below 2^31", who);
+  if (k > 0 && A.n_split > 1) {
+    if ((rc = carve_lists(c, c->geo_ws, st, A, (size_t)n_rows * A.n_split, GEO_K_MAX))) return rc;
+  }
+  c->plan.valid = 1; c->plan.geoie_score_span = A.span; c->plan.geoie_score_splits = A.n_split;
+  HIPCHK(c, poi::launch_geoie_score(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_geoie_score_all_geo(poi_ctx* c, const poi_geoie_params* P, const int32_t* off, const int32_t* p, const int32_t* mult, const float* tu,
+                            const int32_t* rows, int32_t n_rows, const double* coords, const double* cphi, double d_min, float* out,
+                            void* stream) {
+  if (c && n_rows > 0 && !out) return fail(c, POI_EINVAL, "poi_geoie_score_all_geo: NULL out");
+  return geoie_score_common(c, "poi_geoie_score_all_geo", P, off, p, mult, tu, rows, n_rows, coords, cphi, d_min, out, nullptr, nullptr, 0, nullptr,
+                            nullptr, nullptr, stream);
+}
+
+int poi_geoie_score_topk_geo(poi_ctx* c, const poi_geoie_params* P, const int32_t* off, const int32_t* p, const int32_t* mult, const float* tu,
+                             const int32_t* rows, int32_t n_rows, const double* coords, const double* cphi, double d_min, const int32_t* ex_off,
+                             const int32_t* ex, int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out, void* stream) {
+  if (k <= 0 || k > GEO_K_MAX) return fail(c, POI_ENOTSUP, "poi_geoie_score_topk_geo supports 1 <= k <= %d (got %d)", GEO_K_MAX, k);
+  if (c && n_rows > 0 && !idx_out) return fail(c, POI_EINVAL, "poi_geoie_score_topk_geo: NULL idx_out");
+  return geoie_score_common(c, "poi_geoie_score_topk_geo", P, off, p, mult, tu, rows, n_rows, coords, cphi, d_min, nullptr, ex_off, ex, k, idx_out,
+                            score_out, count_out, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// online sessions (session.hip)
+// ---------------------------------------------------------------------------------------------
+static int session_check(poi_ctx* c, const poi_gru_params* P, bool spatial, const char* who) {
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, P->dim);
+  if (P->n_item <= 0) return fail(c, POI_EINVAL, "%s: n_item must be positive", who);
+  if (spatial && (!P->di || !P->vs || !P->bs || P->n_dist <= 0)) return fail(c, POI_EINVAL, "%s: the spatial cell needs di / vs / bs and n_dist > 0", who);
+  if (!spatial && (P->di || P->vs || P->bs || P->n_dist != 0)) return fail(c, POI_EINVAL, "%s: the plain cell takes di / vs / bs NULL and n_dist 0", who);
+  if (spatial && P->n_dist + 1 > 4096) return fail(c, POI_ENOTSUP, "%s: at most 4095 distance bins", who);
+  if (spatial && is_f16(c, P->di)) return fail(c, POI_ENOTSUP, "%s: the distance table must be float32 (only the POI snapshot may be a half table)", who);
+  return POI_OK;
+}
+
+static void session_fill(poi_ctx* c, poi::SessArgs& A, const poi_gru_params* P, bool spatial) {
+  A = poi::SessArgs{};
+  A.lt = P->lt; A.lt_f16 = is_f16(c, P->lt);
+  A.di = P->di; A.ui = P->ui; A.wh = P->wh; A.bi = P->bi; A.vs = P->vs; A.bs = P->bs;
+  A.n_item = P->n_item; A.n_dist = spatial ? P->n_dist : 0; A.dim = P->dim; A.xw = spatial ? 2 * P->dim : P->dim; A.spatial = spatial ? 1 : 0;
+}
+
+int poi_session_advance(poi_ctx* c, const poi_gru_params* P, const double* coords, const double* cphi, const double* thr, double dd,
+                        double* h, float* sts, int32_t* last_poi, int32_t* steps, int32_t n_slot, const int32_t* slot,
+                        const int32_t* poi, int32_t n, float* hts_out, float* sts_out, void* stream) {
+  if (!c || !P) return fail(c, POI_EINVAL, "poi_session_advance: NULL ctx/params");
+  if (!P->lt || !P->ui || !P->wh || !P->bi) return fail(c, POI_EINVAL, "poi_session_advance: lt/ui/wh/bi must be non-NULL");
+  const bool spatial = P->di != nullptr || P->n_dist != 0;
+  int rc = session_check(c, P, spatial, "poi_session_advance");
+  if (rc) return rc;
+  if (spatial && (!coords || !cphi || !thr || !sts || !(dd > 0))) return fail(c, POI_EINVAL, "poi_session_advance: the spatial cell needs coords / cphi / thr / sts and dd > 0");
+  if (!h || !last_poi || !steps || n_slot <= 0) return fail(c, POI_EINVAL, "poi_session_advance: h / last_poi / steps NULL or n_slot <= 0");
+  if (!slot || !poi || n < 0) return fail(c, POI_EINVAL, "poi_session_advance: slot / poi NULL or n < 0");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::SessArgs A;
+  session_fill(c, A, P, spatial);
+  A.coords = coords; A.cphi = cphi; A.thr = thr; A.dd = dd;
+  A.h = h; A.sts = sts; A.last_poi = last_poi; A.steps = steps; A.n_slot = n_slot;
+  A.slot = slot; A.poi = poi; A.n = n; A.hts_out = hts_out; A.sts_out = sts_out;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  const int tile = n >= c->sess_tile_min && poi::sess_tile_supported(A.dim, A.xw, A.n_dist + 1, A.spatial);
+  // repeated slots: one event needs no check, small event launches scan the call inside the kernel, everything else claims the slots
+  if (n > 1 && (tile || n > SESS_SCAN_MAX)) {
+    if ((rc = ensure(c, c->sess_owner, sizeof(int) * (size_t)n_slot, st))) return rc;
+    A.owner = (int*)c->sess_owner.p;
+  }
+  c->plan.valid = 1; c->plan.session_path = tile; c->plan.session_tiles = tile ? (n + 15) / 16 : 0; c->plan.session_tile_min = c->sess_tile_min;
+  HIPCHK(c, poi::launch_session(A, tile, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_session_sts(poi_ctx* c, const poi_gru_params* P, const double* h, int32_t n_slot, const int32_t* slot, int32_t n, float* sts_out,
+                    void* stream) {
+  if (!c || !P) return fail(c, POI_EINVAL, "poi_session_sts: NULL ctx/params");
+  int rc = session_check(c, P, true, "poi_session_sts");
+  if (rc) return rc;
+  if (!h || !slot || !sts_out || n < 0 || n_slot <= 0) return fail(c, POI_EINVAL, "poi_session_sts: h / slot / sts_out NULL, n < 0 or n_slot <= 0");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::SessArgs A;
+  session_fill(c, A, P, true);
+  A.h = const_cast<double*>(h); A.n_slot = n_slot; A.slot = slot; A.n = n; A.sts_out = sts_out; A.head_only = 1;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  HIPCHK(c, poi::launch_session(A, 0, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// online sessions of Lstm / Rnn / CA-RNN (session_cells.hip)
+// ---------------------------------------------------------------------------------------------
+static int session_cells_run(poi_ctx* c, poi::SessCellArgs& A, const char* who, void* stream) {
+  if (A.dim <= 0 || A.dim % 4 != 0 || A.dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, A.dim);
+  if (is_f16(c, A.lt)) return fail(c, POI_ENOTSUP, "%s: float32 tables only", who);
+  if (A.n_item <= 0) return fail(c, POI_EINVAL, "%s: n_item must be positive", who);
+  if (!A.h || !A.last_poi || !A.steps || A.n_slot <= 0) return fail(c, POI_EINVAL, "%s: h / last_poi / steps NULL or n_slot <= 0", who);
+  if (!A.slot || !A.poi || A.n < 0) return fail(c, POI_EINVAL, "%s: slot / poi NULL or n < 0", who);
+  if (A.n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  const int tile = A.n >= c->sess_tile_min && poi::sess_cell_tile_supported(A.G, A.dim);
+  // repeated slots: as poi_session_advance - one event needs no check, small event launches scan the call inside the kernel
+  if (A.n > 1 && (tile || A.n > SESS_SCAN_MAX)) {
+    if ((rc = ensure(c, c->sess_owner, sizeof(int) * (size_t)A.n_slot, st))) return rc;
+    A.owner = (int*)c->sess_owner.p;
+  }
+  if (tile && A.G == 0) {
+    if ((rc = ensure(c, c->sess_wrs, sizeof(double) * (size_t)(A.n_dist + 1) * A.dim, st))) return rc;
+    A.wrs = (const double*)c->sess_wrs.p;
+  }
+  c->plan.valid = 1; c->plan.session_path = tile; c->plan.session_tiles = tile ? (A.n + 15) / 16 : 0; c->plan.session_tile_min = c->sess_tile_min;
+  HIPCHK(c, poi::launch_session_cells(A, tile, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_session_cell_advance(poi_ctx* c, const poi_cell_params* P, double* h, double* cst, int32_t* last_poi, int32_t* steps, int32_t n_slot,
+                             const int32_t* slot, const int32_t* poi, int32_t n, float* hts_out, void* stream) {
+  if (!c || !P) return fail(c, POI_EINVAL, "poi_session_cell_advance: NULL ctx/params");
+  if (P->cell != POI_CELL_RNN && P->cell != POI_CELL_LSTM) return fail(c, POI_EINVAL, "poi_session_cell_advance: cell must be POI_CELL_RNN or POI_CELL_LSTM (got %d)", P->cell);
+  if (!P->lt || !P->ui || !P->wh || !P->bi) return fail(c, POI_EINVAL, "poi_session_cell_advance: lt/ui/wh/bi must be non-NULL");
+  if (P->cell == POI_CELL_LSTM && !cst) return fail(c, POI_EINVAL, "poi_session_cell_advance: the Lstm cell needs c");
+  poi::SessCellArgs A = poi::SessCellArgs{};
+  A.G = P->cell; A.lt = P->lt; A.ui = P->ui; A.wh = P->wh; A.bi = P->bi; A.n_item = P->n_item; A.dim = P->dim;
+  A.h = h; A.c = P->cell == POI_CELL_LSTM ? cst : nullptr; A.last_poi = last_poi; A.steps = steps; A.n_slot = n_slot;
+  A.slot = slot; A.poi = poi; A.n = n; A.hts_out = hts_out;
+  return session_cells_run(c, A, "poi_session_cell_advance", stream);
+}
+
+int poi_session_carnn_advance(poi_ctx* c, const poi_carnn_params* P, const double* coords, const double* cphi, const double* thr, double dd,
+                              double* h, int32_t* last_poi, int32_t* steps, int32_t n_slot, const int32_t* slot, const int32_t* poi, int32_t n,
+                              float* hts_out, void* stream) {
+  if (!c || !P) return fail(c, POI_EINVAL, "poi_session_carnn_advance: NULL ctx/params");
+  if (!P->lt || !P->wd || !P->M || P->n_dist <= 0) return fail(c, POI_EINVAL, "poi_session_carnn_advance: CA-RNN needs lt / wd / M and n_dist > 0");
+  if (!coords || !cphi || !thr || !(dd > 0)) return fail(c, POI_EINVAL, "poi_session_carnn_advance: coords / cphi / thr NULL or dd <= 0");
+  poi::SessCellArgs A = poi::SessCellArgs{};
+  A.G = 0; A.lt = P->lt; A.ui = P->M; A.wh = P->wd; A.n_item = P->n_item; A.n_dist = P->n_dist; A.dim = P->dim;
+  A.coords = coords; A.cphi = cphi; A.thr = thr; A.dd = dd;
+  A.h = h; A.last_poi = last_poi; A.steps = steps; A.n_slot = n_slot;
+  A.slot = slot; A.poi = poi; A.n = n; A.hts_out = hts_out;
+  return session_cells_run(c, A, "poi_session_carnn_advance", stream);
+}
+
+// POI2Vec scoring (poi2vec.hip)
+static int poi2vec_score_common(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch,
+                                int32_t length, const int32_t* coff, const int32_t* cidx, int32_t axis, int32_t k, float* out, int32_t* idx_out,
+                                float* score_out, void* stream, const char* who, const int32_t* ex_off = nullptr, const int32_t* ex = nullptr,
+                                int32_t* count_out = nullptr) {
+  int rc = poi2vec_check(c, P, who);
+  if (rc) return rc;
+  if (!leaf_nodes || !users || !coff || !cidx) return fail(c, POI_EINVAL, "%s: NULL argument", who);
+  if (n_batch < 0 || length < 0 || (axis != 0 && axis != 1)) return fail(c, POI_EINVAL, "%s: bad sizes or softmax_axis", who);
+  if ((int64_t)n_batch * length >= ((int64_t)1 << 31) / 4) return fail(c, POI_ENOTSUP, "%s: too many rows", who);
+  if (n_batch == 0 || length == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::P2vScoreArgs A;
+  memset(&A, 0, sizeof A);
+  A.xu = P->xu; A.wl = P->wl; A.pb = P->pb; A.probs = P->probs; A.rid = P->rid; A.leaf_nodes = leaf_nodes; A.users = users; A.coff = coff; A.cidx = cidx;
+  A.n_user = P->n_user; A.n_item = P->n_item; A.n_node = P->n_node; A.depth = P->depth; A.dim = P->dim;
+  A.n_batch = n_batch; A.length = length; A.n_rows = n_batch * length; A.axis = axis; A.k = k;
+  const size_t rows = (size_t)A.n_rows, NL = (size_t)1 << (P->depth - 1);
+  const size_t ns = (size_t)(axis == 0 ? P->n_item : n_batch);
+  if ((rc = carve(c, c->pv_sc, st, [&](Carver& W) {
+        A.cl = (double*)W.bytes(sizeof(double) * (rows * P->dim)); A.zf = (double*)W.bytes(sizeof(double) * (rows * P->n_node)); A.rp = (double*)W.bytes(sizeof(double) * (rows * NL));
+        A.ssum = (double*)W.bytes(sizeof(double) * (ns)); A.smax = (float*)W.bytes(sizeof(float) * (ns)); A.logit = (float*)W.bytes(sizeof(float) * ((size_t)n_batch * P->n_item));
+      }))) return rc;
+  A.out = out;                                     // NULL for the top-K: the scores are not stored
+  A.idx_out = idx_out; A.score_out = score_out;
+  A.ex_off = ex_off; A.ex = ex; A.count_out = count_out;
+  HIPCHK(c, poi::launch_poi2vec_scores(A, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_poi2vec_scores(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch, int32_t length,
+                       const int32_t* coff, const int32_t* cidx, int32_t softmax_axis, float* out, void* stream) {
+  if (c && !out) return fail(c, POI_EINVAL, "poi_poi2vec_scores: NULL argument");
+  return poi2vec_score_common(c, P, leaf_nodes, users, n_batch, length, coff, cidx, softmax_axis, 0, out, nullptr, nullptr, stream, "poi_poi2vec_scores");
+}
+
+int poi_poi2vec_topk(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch, int32_t length,
+                     const int32_t* coff, const int32_t* cidx, int32_t softmax_axis, int32_t k, int32_t* idx_out, float* score_out, void* stream) {
+  if (c && !idx_out) return fail(c, POI_EINVAL, "poi_poi2vec_topk: NULL argument");
+  if (c && P && (k < 1 || k > 64 || k > P->n_item)) return fail(c, POI_EINVAL, "poi_poi2vec_topk: k must lie in [1, min(64, n_item)]");
+  return poi2vec_score_common(c, P, leaf_nodes, users, n_batch, length, coff, cidx, softmax_axis, k, nullptr, idx_out, score_out, stream, "poi_poi2vec_topk");
+}
+
+int poi_poi2vec_topk_ex(poi_ctx* c, const poi_poi2vec_params* P, const int32_t* leaf_nodes, const int32_t* users, int32_t n_batch, int32_t length,
+                        const int32_t* coff, const int32_t* cidx, int32_t softmax_axis, const int32_t* ex_off, const int32_t* ex, int32_t k,
+                        int32_t* idx_out, float* score_out, int32_t* count_out, void* stream) {
+  if (c && !idx_out) return fail(c, POI_EINVAL, "poi_poi2vec_topk_ex: NULL argument");
+  if (c) if (int r = check_ex_pair(c, "poi_poi2vec_topk_ex", ex_off, ex, "come")) return r;
+  if (c && P && (k < 1 || k > 64 || k > P->n_item)) return fail(c, POI_EINVAL, "poi_poi2vec_topk_ex: k must lie in [1, min(64, n_item)]");
+  return poi2vec_score_common(c, P, leaf_nodes, users, n_batch, length, coff, cidx, softmax_axis, k, nullptr, idx_out, score_out, stream,
+                              "poi_poi2vec_topk_ex", ex_off, ex, count_out);
+}
+
+// fold-in of new users for POI2Vec (foldin_p2v.hip).  The partials grow with users x spans x (dim + 2): the call is cut into user
+// chunks that keep them within P2V_FOLD_PART_BYTES (a user's bits do not depend on the chunking)
+#define P2V_FOLD_PART_BYTES ((size_t)64 << 20)
+int poi_foldin_p2v_span(void) { return P2V_FOLD_SPAN; }
+
+int poi_foldin_p2v(poi_ctx* c, const float* wl, int32_t n_item, int32_t dim, const int32_t* off, const int32_t* tgt, int32_t n, int32_t epochs,
+                   float alpha, float lambda, const float* w0, float* w_out, float* loss_out, void* stream) {
+  if (!c || !wl || !w_out) return fail(c, POI_EINVAL, "poi_foldin_p2v: NULL ctx / wl / w_out");
+  if (dim <= 0 || dim % 4 != 0 || dim > 128) return fail(c, POI_ENOTSUP, "poi_foldin_p2v: dim must be a multiple of 4 in [4, 128] (got %d)", dim);
+  if (n < 0 || n_item <= 0 || epochs < 0) return fail(c, POI_EINVAL, "poi_foldin_p2v: n < 0, n_item <= 0 or epochs < 0");
+  if (n == 0) return POI_OK;
+  if (!off || !tgt) return fail(c, POI_EINVAL, "poi_foldin_p2v: NULL off / tgt");
+  if (is_f16(c, wl) || (w0 && is_f16(c, w0)) || is_f16(c, w_out)) return fail(c, POI_ENOTSUP, "poi_foldin_p2v: wl / w0 / w_out must be float32");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  int* bad;
+  if ((rc = bad_counter(c, st, &bad))) return rc;
+  const int n_span = (n_item + P2V_FOLD_SPAN - 1) / P2V_FOLD_SPAN;
+  const size_t per_user = sizeof(double) * (size_t)n_span * (size_t)(dim + 2);
+  size_t uc = P2V_FOLD_PART_BYTES / per_user / P2V_FOLD_USERS * P2V_FOLD_USERS;
+  if (uc < P2V_FOLD_USERS) uc = P2V_FOLD_USERS;
+  if (uc > (size_t)n) uc = (size_t)n;
+  poi::FoldP2vArgs A = {};
+  if ((rc = carve(c, c->pv_fold, st, [&](Carver& W) {
+        A.w = (double*)W.bytes(sizeof(double) * uc * dim); A.tbar = (double*)W.bytes(sizeof(double) * uc * dim);
+        A.flag = (int*)W.bytes(sizeof(int) * uc); A.part = (double*)W.bytes(per_user * uc);
+      }))) return rc;
+  A.wl = wl; A.n_item = n_item; A.dim = dim; A.epochs = epochs; A.n_span = n_span; A.tgt = tgt; A.alpha = alpha; A.lambda = lambda; A.bad = bad;
+  for (size_t r0 = 0; r0 < (size_t)n; r0 += uc) {
+    A.n = (int)((size_t)n - r0 < uc ? (size_t)n - r0 : uc);
+    A.off = off + r0;
+    A.w0 = w0 ? w0 + r0 * dim : nullptr; A.w_out = w_out + r0 * dim; A.loss_out = loss_out ? loss_out + r0 * epochs : nullptr;
+    HIPCHK(c, poi::launch_foldin_p2v(A, st, &c->tm));
+  }
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+struct UlptaiArg { const void* bins; int bin_bytes; const float* sts; int n_dist; const double *coords, *cphi, *thr; const int* last_poi; double dd; };
+
+static int score_common(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                        const float* wd, const float* prob, float* scores, int32_t k, int32_t* idx_out, float* score_out,
+                        void* stream, const UlptaiArg* U = nullptr) {
+  // the top-K seed is "consumed by the next call" whatever that call does: taken (and cleared) before any early return, so a failed or
+  // empty call can never leave a stale pointer - sized for another n - armed for a later one
+  const int32_t* seed_idx = c ? c->seed_idx : nullptr; const int seed_k = c ? c->seed_k : 0;
+  if (c) { c->seed_idx = nullptr; c->seed_k = 0; }
+  if (!c || !users || !items) return fail(c, POI_EINVAL, "score: NULL argument");
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "bad sizes");
+  if (prob && !wd) return fail(c, POI_EINVAL, "prob given without wd");
+  if (k < 0 || k > 32 || (k > 0 && k > n_item)) return fail(c, POI_ENOTSUP, "top-K supports 1 <= k <= min(32, n_item) (got %d)", k);
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::ScoreArgs A;
+  memset(&A, 0, sizeof A);
+  A.users = users; A.items = items; A.items_f16 = is_f16(c, items); A.n = n; A.n_item = n_item; A.dim = dim; A.wd = wd; A.prob = prob;
+  A.scores = scores; A.k = k; A.idx_out = idx_out; A.score_out = score_out;
+  if (U) { A.ulptai = U->bins; A.bin_bytes = U->bin_bytes; A.sts = U->sts; A.n_dist = U->n_dist; }
+  if (U && !U->bins) { A.geo = 1; A.coords = U->coords; A.cphi = U->cphi; A.thr = U->thr; A.last_poi = U->last_poi; A.dd = U->dd; }
+  if (const char* e = getenv("POI_SCORE_DBG")) A.dbg = atoi(e);
+  const int ntile = (n_item + 31) / 32;
+  // variant: 0 = one item stream per wave (row-per-lane loads; small n or dim > 128), 1 = packed item
+  // stream per wave with the user tile's A fragments in LDS (default for n >= 128)
+  int variant = (n >= 128 && dim <= 128) ? 1 : 0;
+  if (c->score_variant >= 0 && dim <= 128) variant = c->score_variant;
+  if (U && U->bins) variant = 1;      // the bin matrix is laid out for the packed-stream kernel
+  if (U && !U->bins) variant = 0;     // bins on the fly: the row-per-lane kernel (any dim <= 256)
+  // ... or, for enough users to fill the chip with eight-wave workgroups and a wide model, the packed-stream GEO kernel
+  if (U && !U->bins && k > 0 && n >= 1024 && dim >= 128 && poi::score_geo_stream_lds(dim, U->n_dist) <= 160 * 1024 && c->score_variant != 0) variant = 2;
+  const int n_utile = (n + 31) / 32;
+  // item ranges per user tile for a table of nt item tiles: long item streams keep per-user thresholds high (few top-K compactions)
+  auto splits_for = [&](int nt) {
+    int want = (c->num_cu * 8 + n_utile - 1) / n_utile;   // 8 waves per CU
+    if (want > nt / 8) want = nt / 8;          // >= 8 tiles per stream: amortise the per-wave top-K epilogue
+    if (want < 1) want = 1;
+    if (want < (nt + 2046) / 2047) want = (nt + 2046) / 2047;      // candidate lists hold 16-bit item offsets: < 65536 items per range
+    return variant == 2 ? ((want + 7) / 8) * 8 : ((want + 3) / 4) * 4;
+  };
+  const int n_split = splits_for(ntile);
+  A.n_split = n_split;
+  const int n_pad = n_utile * 32;
+  int rc;
+  // one-stage kernel of the chosen variant + merge of the per-range lists, on the item table X describes
+  auto one_stage = [&](poi::ScoreArgs& X) -> int {
+    const int nt = (X.n_item + 31) / 32;
+    if (variant == 2) {
+      const int d8 = dim <= 128 ? 16 : 32;
+      int r2 = ensure(c, c->items_pk, sizeof(float) * 4 * (size_t)nt * d8 * 64, st);
+      if (r2) return r2;
+      X.items_packed = (float4*)c->items_pk.p;
+      HIPCHK(c, poi::launch_score_geo_stream(X, st, &c->tm));
+    } else if (variant == 1) {
+      const int d8 = dim <= 32 ? 4 : dim <= 64 ? 8 : 16;
+      int r2 = ensure(c, c->items_pk, sizeof(float) * 4 * (size_t)nt * d8 * 64, st);
+      if (r2) return r2;
+      X.items_packed = (float4*)c->items_pk.p;
+      HIPCHK(c, poi::launch_score_packed(X, st, &c->tm));
+    } else {
+      HIPCHK(c, poi::launch_score(X, st, &c->tm));
+    }
+    if (k > 0) HIPCHK(c, poi::launch_topk_merge(X, X.n_split, n_pad, st));
+    return POI_OK;
+  };
+  bool two_stage = false, use_maxpass = false;
+  if (k > 0) {
+    const size_t cand = (size_t)n_split * n_pad * k;
+    if ((rc = ensure(c, c->cand_s, sizeof(float) * cand, st))) return rc;
+    if ((rc = ensure(c, c->cand_i, sizeof(int) * cand, st))) return rc;
+    A.cand_score = (float*)c->cand_s.p; A.cand_idx = (int*)c->cand_i.p;
+    const bool seeded = seed_idx && seed_k >= k && seed_k <= 64;
+    {
+      poi::ScoreArgs probe = A; probe.seeded = 1;
+      two_stage = c->topk_filter && (variant == 1 || A.geo) && poi::score_two_stage_supported(probe);
+    }
+    // SELF-SEEDING pre-pass of the two-stage path: the one-stage kernel on the first 1/16 of the item tiles (1/64 when the caller's
+    // seed already gave bounds) - the K-th best EXACT score of any subset is a lower bound of the final K-th best, so the filter pass
+    // starts from thresholds that leave ~16 K (64 K) survivors per user whatever the seed holds: an unseeded call (the first evaluation
+    // of a run) or a useless seed (a model that moved a lot) no longer sends its tiles to the one-stage kernel.  Unseeded calls always
+    // take it; seeded ones when the table has >= 2^20 items (there it costs < 2 % of the call).
+    const int sub_tiles = !two_stage ? 0 : !seeded ? (ntile >= 256 ? ntile / 16 : 0) : (n_item >= (1 << 20) ? ntile / 64 : 0);
+    if (two_stage && !seeded && sub_tiles == 0) two_stage = false;      // (a small table and no seed: one-stage)
+    if (n_split > 1 || seeded || two_stage) {
+      if ((rc = ensure(c, c->gbound, sizeof(unsigned) * (size_t)n_pad, st))) return rc;
+      HIPCHK(c, hipMemsetAsync(c->gbound.p, 0, sizeof(unsigned) * (size_t)n_pad, st));
+      A.gbound = (unsigned*)c->gbound.p;
+    }
+    if (seeded) {
+      c->tm.begin("topk_seed", st);
+      HIPCHK(c, poi::launch_topk_seed(A, seed_idx, seed_k, st));
+      c->tm.end(st);
+      A.seeded = 1;
+    }
+    // unseeded, resident bin matrix / no distance term, dims 64 / 128: thresholds from the block maxima of the f16 lower bounds instead
+    // (score_filter.hip, MAXP: one f16 pass over ALL items, ~1.3 K survivors per user against ~17 K of the float32 prefix pre-pass)
+    use_maxpass = two_stage && !seeded && sub_tiles > 0 && poi::score_maxpass_supported(A);
+    if (const char* e = getenv("POI_SF_MAXPASS")) use_maxpass = use_maxpass && atoi(e) != 0;
+    if (two_stage && sub_tiles > 0 && !use_maxpass) {
+      if ((rc = ensure(c, c->pre_idx, sizeof(int) * (size_t)n_pad * k, st)) || (rc = ensure(c, c->pre_sc, sizeof(float) * (size_t)n_pad * k, st))) return rc;
+      poi::ScoreArgs S = A;
+      S.n_item = sub_tiles * 32; S.bins_ntile = ntile; S.n_split = splits_for(sub_tiles);
+      S.idx_out = (int*)c->pre_idx.p; S.score_out = (float*)c->pre_sc.p;
+      if ((size_t)S.n_split * n_pad * k > cand) {
+        if ((rc = ensure(c, c->cand_s, sizeof(float) * (size_t)S.n_split * n_pad * k, st)) || (rc = ensure(c, c->cand_i, sizeof(int) * (size_t)S.n_split * n_pad * k, st))) return rc;
+        A.cand_score = S.cand_score = (float*)c->cand_s.p; A.cand_idx = S.cand_idx = (int*)c->cand_i.p;
+      }
+      if ((rc = one_stage(S))) return rc;
+      HIPCHK(c, poi::launch_topk_bound(S.score_out, n, k, A.gbound, st));
+      A.seeded = 1;
+    }
+  }
+  if (two_stage) {
+    // two-stage: f16 filter pass + exact float32 rescoring of the survivors (score_filter.hip); the one-stage kernel below then only
+    // runs the user tiles whose survivor lists overflowed (A.tile_flag)
+    const int kg = dim / 16, cap = poi::score_filter_cap();
+    if ((rc = ensure(c, c->items_pk16, sizeof(uint4) * (size_t)ntile * kg * 64, st)) || (rc = ensure(c, c->inorm, sizeof(float2) * (size_t)ntile * 32, st)) ||
+        (rc = ensure(c, c->surv_cnt, sizeof(int) * (size_t)n_pad, st)) || (rc = ensure(c, c->surv_idx, sizeof(int) * (size_t)n_pad * cap, st)) ||
+        (rc = ensure(c, c->surv_sc, sizeof(float) * (size_t)n_pad * cap, st)) ||
+        (rc = ensure(c, c->tflag, sizeof(int) * (size_t)n_utile, st))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->surv_cnt.p, 0, sizeof(int) * (size_t)n_pad, st));
+    HIPCHK(c, hipMemsetAsync(c->tflag.p, 0, sizeof(int) * (size_t)n_utile, st));
+    A.items_packed16 = (const uint4*)c->items_pk16.p; A.inorm = (const float2*)c->inorm.p;
+    A.surv_cnt = (int*)c->surv_cnt.p; A.surv_idx = (int*)c->surv_idx.p; A.surv_sc = (float*)c->surv_sc.p; A.tile_flag = (int*)c->tflag.p;
+    // GEO with a huge item table and few users (config X's evaluation): the item-stationary filter - every user tile's own pass over the
+    // item table is 1.3 TB at 8192 users x 10 M POIs; forced (2) / forbidden (0) by POI_SF_ITEMS for tests and A/B runs
+    A.n_cu = c->num_cu;
+    {
+      int items_mode = (A.geo && n_item >= (1 << 20) && n_utile <= 4096) ? 1 : 0;
+      if (const char* e = getenv("POI_SF_ITEMS")) items_mode = A.geo ? (atoi(e) != 0) : 0;
+      if (c->sf_items >= 0) items_mode = A.geo ? c->sf_items : 0;
+      if (items_mode) {
+        if ((rc = ensure(c, c->users_pk16, sizeof(uint4) * (size_t)n_utile * kg * 64, st)) || (rc = ensure(c, c->ubound, sizeof(float) * 4 * (size_t)n_pad, st)) ||
+            (rc = ensure(c, c->ugeo, sizeof(double) * 3 * (size_t)n_pad, st))) return rc;
+        A.users_packed16 = (uint4*)c->users_pk16.p; A.ubound = (float4*)c->ubound.p; A.ugeo = (double*)c->ugeo.p;
+      }
+    }
+    int nsf = ((4 * c->num_cu + n_utile - 1) / n_utile) * 4;      // >= 4 workgroups (16 waves) per CU
+    if (nsf < 16) nsf = 16;      // (swept at the Gowalla shape: 8 / 16 / 32 / 64 / 128 ranges -> 3.09 / 2.84 / 2.80 / 2.86 / 3.21 ms of filter time)
+    if (const char* e = getenv("POI_SF_NSPLIT")) { const int v = atoi(e); if (v >= 4) nsf = (v / 4) * 4; }      // tuning switch
+    if (nsf > (ntile / 4) * 4) nsf = (ntile / 4) * 4;
+    if (nsf < 4) nsf = 4;
+    if (use_maxpass) {
+      HIPCHK(c, poi::launch_score_maxpass(A, nsf, st, &c->tm));
+      A.seeded = 1;
+    }
+    HIPCHK(c, poi::launch_score_two_stage(A, nsf, st, &c->tm));
+    c->last_two_n = n; c->last_two_tiles = n_utile;
+  }
+  return one_stage(A);
+}
+
+int poi_score_all(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                  const float* wd, const float* prob, float* scores_out, void* stream) {
+  if (!scores_out) return fail(c, POI_EINVAL, "scores_out is NULL");
+  return score_common(c, users, items, n, n_item, dim, wd, prob, scores_out, 0, nullptr, nullptr, stream);
+}
+
+int poi_score_topk(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                   const float* wd, const float* prob, int32_t k, int32_t* idx_out, float* score_out, void* stream) {
+  if (!idx_out || k <= 0) return fail(c, POI_EINVAL, "idx_out NULL or k <= 0");
+  return score_common(c, users, items, n, n_item, dim, wd, prob, nullptr, k, idx_out, score_out, stream);
+}
+
+int poi_ulptai_build(poi_ctx* c, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                     int32_t n_user, int32_t n_item, int32_t n_dist, double dd, void* out, int32_t bin_bytes, void* stream) {
+  if (!c || !coords || !cphi || !thr || !last_poi || !out) return fail(c, POI_EINVAL, "poi_ulptai_build: NULL argument");
+  if (n_user <= 0 || n_item <= 0 || n_dist <= 0 || !(dd > 0)) return fail(c, POI_EINVAL, "bad sizes");
+  if (bin_bytes != 1 && bin_bytes != 2) return fail(c, POI_EINVAL, "bin_bytes must be 1 or 2");
+  if ((bin_bytes == 1 && n_dist > 255) || n_dist > 65535) return fail(c, POI_EINVAL, "n_dist %d does not fit %d-byte bins", n_dist, bin_bytes);
+  HIPCHK(c, hipSetDevice(c->device));
+  c->tm.begin("ulptai_build", (hipStream_t)stream);
+  HIPCHK(c, poi::launch_ulptai(coords, cphi, thr, last_poi, n_user, n_item, n_dist, dd, out, bin_bytes, (hipStream_t)stream));
+  c->tm.end((hipStream_t)stream);
+  return POI_OK;
+}
+
+int poi_score_topk_ulptai(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                          const float* wd, const float* sts, const void* ulptai, int32_t bin_bytes, int32_t n_dist,
+                          int32_t k, int32_t* idx_out, float* score_out, void* stream) {
+  if (!idx_out || k <= 0) return fail(c, POI_EINVAL, "idx_out NULL or k <= 0");
+  if (!wd || !sts || !ulptai) return fail(c, POI_EINVAL, "poi_score_topk_ulptai: wd / sts / ulptai NULL");
+  if (bin_bytes != 1 && bin_bytes != 2) return fail(c, POI_EINVAL, "bin_bytes must be 1 or 2");
+  if (dim > 128) return fail(c, POI_ENOTSUP, "the bin-matrix path supports dim <= 128 (got %d)", dim);
+  if (n_dist <= 0 || (int64_t)n * (n_dist + 1) >= (int64_t)1 << 31) return fail(c, POI_EINVAL, "n * (n_dist + 1) must stay below 2^31: score in batches");
+  const UlptaiArg U{ulptai, bin_bytes, sts, n_dist, nullptr, nullptr, nullptr, nullptr, 0.0};
+  return score_common(c, users, items, n, n_item, dim, wd, nullptr, nullptr, k, idx_out, score_out, stream, &U);
+}
+
+int poi_score_topk_geo(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                       const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                       int32_t k, int32_t* idx_out, float* score_out, void* stream) {
+  if (!idx_out || k <= 0) return fail(c, POI_EINVAL, "idx_out NULL or k <= 0");
+  if (!wd || !sts || !coords || !cphi || !thr || !last_poi) return fail(c, POI_EINVAL, "poi_score_topk_geo: NULL argument");
+  if (n_dist <= 0 || !(dd > 0)) return fail(c, POI_EINVAL, "bad n_dist / dd");
+  const UlptaiArg U{nullptr, 0, sts, n_dist, coords, cphi, thr, last_poi, dd};
+  return score_common(c, users, items, n, n_item, dim, wd, nullptr, nullptr, k, idx_out, score_out, stream, &U);
+}
+
+// ---------------------------------------------------------------------------------------------
+// restricted top-K (near.hip)
+int poi_score_topk_near(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const double* coords,
+                        const double* cphi, const int32_t* lat_order, const int32_t* anchor, double c_r, const int32_t* ex_off, const int32_t* ex,
+                        const float* wd, const float* sts, const double* thr, int32_t n_dist, double dd, int32_t k, int32_t* idx_out,
+                        float* score_out, int32_t* count_out, void* stream) {
+  if (!c || !users || !items || !idx_out) return fail(c, POI_EINVAL, "poi_score_topk_near: NULL ctx / users / items / idx_out");
+  if (k <= 0 || k > NEAR_K_MAX) return fail(c, POI_ENOTSUP, "poi_score_topk_near supports 1 <= k <= %d (got %d)", NEAR_K_MAX, k);
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_score_topk_near: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "poi_score_topk_near: n < 0 or n_item <= 0");
+  if (!(c_r >= 0.0)) return fail(c, POI_EINVAL, "poi_score_topk_near: c_r must be >= 0 (+inf: no radius test)");
+  const bool radius = c_r < HUGE_VAL, geo = wd != nullptr;
+  float bin_scale;
+  int rc;
+  if ((rc = check_ex_pair(c, "poi_score_topk_near", ex_off, ex))) return rc;
+  if ((rc = check_geo_term(c, "poi_score_topk_near", geo, geo == (sts != nullptr) && geo == (thr != nullptr), "wd, sts and thr go together", n_dist, dd, &bin_scale))) return rc;
+  if ((radius || geo) && (!coords || !cphi || !anchor)) return fail(c, POI_EINVAL, "poi_score_topk_near: a radius or a distance term needs coords / cphi / anchor");
+  if (radius && !lat_order) return fail(c, POI_EINVAL, "poi_score_topk_near: a radius needs lat_order");
+  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "poi_score_topk_near: users must be float32");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::NearArgs A = {};
+  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
+  A.n = n; A.n_item = n_item; A.dim = dim; A.k = k;
+  A.coords = coords; A.cphi = cphi; A.order = lat_order; A.anchor = anchor; A.c_r = c_r; A.band_deg = radius ? lat_band_deg(c_r) : 0.0;
+  A.ex_off = ex_off; A.ex = ex;
+  A.wd = wd; A.sts = sts; A.thr = thr; A.n_dist = geo ? n_dist : 0; A.bin_scale = bin_scale;
+  A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  // few rows (live traffic): every row's band is cut into slices so that the call fills the CUs; many rows: one workgroup per row
+  const int split = n <= c->near_split_max;
+  A.n_split = 1;
+  if (split) {
+    int s = c->near_grid > 0 ? c->near_grid : 4 * c->num_cu / n;
+    if (c->near_grid <= 0 && s < 2) s = 2;
+    A.n_split = s > NEAR_SPLIT_LIMIT ? NEAR_SPLIT_LIMIT : s;
+    if ((rc = carve_lists(c, c->near_ws, st, A, (size_t)n * A.n_split, NEAR_K_MAX))) return rc;
+  }
+  c->plan.valid = 1; c->plan.near_path = split; c->plan.near_splits = split ? A.n_split : 0; c->plan.near_split_max = c->near_split_max;
+  HIPCHK(c, poi::launch_near(A, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// exact target ranks (rank.hip)
+static int rank_check(poi_ctx* c, const char* who, int32_t n, int32_t n_item, const int32_t* tgt, const int32_t* tmask, int32_t len_t,
+                      const int32_t* ex_off, const int32_t* ex, const int32_t* rank_out) {
+  if (!tgt || !tmask || !rank_out) return fail(c, POI_EINVAL, "%s: NULL tgt / tmask / rank_out", who);
+  if (len_t <= 0 || len_t > RANK_LT_MAX) return fail(c, POI_ENOTSUP, "%s supports 1 <= len_t <= %d (got %d)", who, RANK_LT_MAX, len_t);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "%s: n < 0 or n_item <= 0", who);
+  if (int r = check_ex_pair(c, who, ex_off, ex)) return r;
+  return POI_OK;
+}
+
+int poi_score_rank(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                   const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                   const int32_t* tgt, const int32_t* tmask, int32_t len_t, const int32_t* ex_off, const int32_t* ex, int32_t* rank_out,
+                   float* score_out, int32_t* count_out, void* stream) {
+  if (!c || !users || !items) return fail(c, POI_EINVAL, "poi_score_rank: NULL ctx / users / items");
+  int rc;
+  if ((rc = rank_check(c, "poi_score_rank", n, n_item, tgt, tmask, len_t, ex_off, ex, rank_out))) return rc;
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_score_rank: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  const bool geo = wd != nullptr;
+  float bin_scale;
+  if ((rc = check_geo_term(c, "poi_score_rank", geo, !geo || (sts && coords && cphi && thr && last_poi), "the distance term needs sts / coords / cphi / thr / last_poi", n_dist, dd, &bin_scale))) return rc;
+  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "poi_score_rank: users must be float32");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::RankArgs A = {};
+  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
+  A.n = n; A.n_item = n_item; A.dim = dim; A.len_t = len_t;
+  if (geo) { A.wd = wd; A.sts = sts; A.coords = coords; A.cphi = cphi; A.thr = thr; A.last_poi = last_poi; A.n_dist = n_dist; A.bin_scale = bin_scale; }
+  A.tgt = tgt; A.tmask = tmask; A.ex_off = ex_off; A.ex = ex;
+  A.rank_out = rank_out; A.score_out = score_out; A.count_out = count_out;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
+  if ((rc = ensure(c, c->rank_ws, sizeof(poi::RankTgt) * (size_t)n_utile * 32 * RANK_LT_MAX, st))) return rc;
+  A.tl = (poi::RankTgt*)c->rank_ws.p;
+  // item ranges per 32-row tile, one wave each: 8 waves per CU over the call, at least 8 tiles per range; "rank_grid" caps it; the 16-bit
+  // per-lane counters set the floor
+  int want = (c->num_cu * 8 + n_utile - 1) / n_utile;
+  if (want > ntile / 8) want = ntile / 8;
+  if (c->rank_grid > 0 && want > c->rank_grid) want = c->rank_grid;
+  if (want < 1) want = 1;
+  if (want < (ntile + RANK_TILES_MAX - 1) / RANK_TILES_MAX) want = (ntile + RANK_TILES_MAX - 1) / RANK_TILES_MAX;
+  A.n_split = want;
+  c->plan.valid = 1; c->plan.rank_splits = want;
+  HIPCHK(c, poi::launch_rank(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_rank_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, const int32_t* tgt, const int32_t* tmask, int32_t len_t,
+                    const int32_t* ex_off, const int32_t* ex, int32_t* rank_out, int32_t* count_out, void* stream) {
+  if (!c || !scores) return fail(c, POI_EINVAL, "poi_rank_scores: NULL ctx / scores");
+  int rc;
+  if ((rc = rank_check(c, "poi_rank_scores", n, n_item, tgt, tmask, len_t, ex_off, ex, rank_out))) return rc;
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  int* bad;
+  if ((rc = bad_counter(c, st, &bad))) return rc;
+  c->tm.begin("rank_scores", st);
+  HIPCHK(c, poi::launch_rank_scores(scores, n, n_item, tgt, tmask, len_t, ex_off, ex, rank_out, count_out, bad, st));
+  c->tm.end(st);
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// group recommendation (group.hip)
+static int group_check_args(poi_ctx* c, const char* who, int32_t n, int32_t n_item, const int32_t* g_off, const int32_t* g_mem, int32_t n_grp,
+                            int32_t agg, const int32_t* ex_off, const int32_t* ex, int32_t k, const int32_t* idx_out) {
+  if (!g_off || !g_mem || !idx_out) return fail(c, POI_EINVAL, "%s: NULL g_off / g_mem / idx_out", who);
+  if (k <= 0 || k > GROUP_K_MAX) return fail(c, POI_ENOTSUP, "%s supports 1 <= k <= %d (got %d)", who, GROUP_K_MAX, k);
+  if (agg < 0 || agg > 1) return fail(c, POI_EINVAL, "%s: agg must be 0 (mean) or 1 (least misery) (got %d)", who, agg);
+  if (n < 0 || n_item <= 0 || n_grp < 0) return fail(c, POI_EINVAL, "%s: n < 0, n_item <= 0 or n_grp < 0", who);
+  if (int r = check_ex_pair(c, who, ex_off, ex)) return r;
+  return POI_OK;
+}
+
+int poi_group_topk(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                   const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                   const int32_t* g_off, const int32_t* g_mem, int32_t n_grp, int32_t agg, const int32_t* ex_off, const int32_t* ex, int32_t k,
+                   int32_t* idx_out, float* score_out, int32_t* count_out, void* stream) {
+  if (!c || !items || (!users && n > 0)) return fail(c, POI_EINVAL, "poi_group_topk: NULL ctx / users / items");
+  int rc;
+  if ((rc = group_check_args(c, "poi_group_topk", n, n_item, g_off, g_mem, n_grp, agg, ex_off, ex, k, idx_out))) return rc;
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_group_topk: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  const bool geo = wd != nullptr;
+  float bin_scale;
+  if ((rc = check_geo_term(c, "poi_group_topk", geo, !geo || (sts && coords && cphi && thr && last_poi), "the distance term needs sts / coords / cphi / thr / last_poi", n_dist, dd, &bin_scale))) return rc;
+  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "poi_group_topk: users must be float32");
+  if (n_grp == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::GroupArgs A = {};
+  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
+  A.n = n; A.n_item = n_item; A.dim = dim; A.k = k; A.n_grp = n_grp; A.agg = agg;
+  if (geo) { A.wd = wd; A.sts = sts; A.coords = coords; A.cphi = cphi; A.thr = thr; A.last_poi = last_poi; A.n_dist = n_dist; A.bin_scale = bin_scale; }
+  A.g_off = g_off; A.g_mem = g_mem; A.ex_off = ex_off; A.ex = ex;
+  A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  // few groups (live traffic): the item range is cut into slices so that the call fills the CUs; many groups: one workgroup per GROUP_GPT groups
+  const int split = n_grp <= c->group_split_max;
+  const int n_gtile = (n_grp + GROUP_GPT - 1) / GROUP_GPT, ntile = (n_item + 31) / 32;
+  A.n_split = 1;
+  if (split) {
+    int s = c->group_grid > 0 ? c->group_grid : 2 * c->num_cu / n_gtile;
+    if (c->group_grid <= 0 && s > ntile / 16) s = ntile / 16;      // (at least four item tiles per wave)
+    if (c->group_grid <= 0 && s < 2) s = 2;
+    A.n_split = s > GROUP_SPLIT_LIMIT ? GROUP_SPLIT_LIMIT : s;
+    if ((rc = carve_lists(c, c->group_ws, st, A, (size_t)n_grp * A.n_split, GROUP_K_MAX))) return rc;
+  }
+  c->plan.valid = 1; c->plan.group_path = split; c->plan.group_splits = split ? A.n_split : 0; c->plan.group_split_max = c->group_split_max;
+  HIPCHK(c, poi::launch_group(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_group_topk_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, const int32_t* g_off, const int32_t* g_mem, int32_t n_grp,
+                          int32_t agg, const int32_t* ex_off, const int32_t* ex, int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out,
+                          void* stream) {
+  if (!c || (!scores && n > 0)) return fail(c, POI_EINVAL, "poi_group_topk_scores: NULL ctx / scores");
+  int rc;
+  if ((rc = group_check_args(c, "poi_group_topk_scores", n, n_item, g_off, g_mem, n_grp, agg, ex_off, ex, k, idx_out))) return rc;
+  if (n_grp == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::GroupArgs A = {};
+  A.n = n; A.n_item = n_item; A.k = k; A.n_grp = n_grp; A.agg = agg; A.n_split = 1;
+  A.g_off = g_off; A.g_mem = g_mem; A.ex_off = ex_off; A.ex = ex;
+  A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  HIPCHK(c, poi::launch_group_scores(scores, A, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// fold-in of new users (foldin.hip)
+int poi_foldin_bpr(poi_ctx* c, const float* items, int32_t n_item, int32_t dim, const int32_t* off, const int32_t* p, const int32_t* q,
+                   int64_t q_epoch_stride, int32_t n, int32_t epochs, float alpha, float lambda, const float* w0, float* w_out,
+                   float* loss_out, void* stream) {
+  if (!c || !items || !w_out) return fail(c, POI_EINVAL, "poi_foldin_bpr: NULL ctx / items / w_out");
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_foldin_bpr: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  if (n < 0 || n_item <= 0 || epochs < 0 || q_epoch_stride < 0) return fail(c, POI_EINVAL, "poi_foldin_bpr: n < 0, n_item <= 0, epochs < 0 or q_epoch_stride < 0");
+  if (n == 0) return POI_OK;
+  if (!off || !p || !q) return fail(c, POI_EINVAL, "poi_foldin_bpr: NULL off / p / q");
+  if ((w0 && is_f16(c, w0)) || is_f16(c, w_out)) return fail(c, POI_ENOTSUP, "poi_foldin_bpr: w0 / w_out must be float32");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::FoldinArgs A = {};
+  A.items = items; A.items_f16 = is_f16(c, items);
+  A.n = n; A.n_item = n_item; A.dim = dim; A.epochs = epochs;
+  A.off = off; A.p = p; A.q = q; A.q_epoch_stride = q_epoch_stride;
+  A.alpha = alpha; A.lambda = lambda;
+  A.w0 = w0; A.w_out = w_out; A.loss_out = loss_out;
+  int rc;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  HIPCHK(c, poi::launch_foldin(A, st, &c->tm));
+  return POI_OK;
+}
+
+// fold-in for the successive-POI models (foldin_seq.hip): the per-step scalars, then the generalised chain
+static int foldin_terms_common(poi_ctx* c, const char* who, const int32_t* off, const int32_t* p, const int32_t* q, int64_t q_epoch_stride, int32_t n,
+                               int64_t total, int32_t epochs, const double* c_out, poi::FoldinTermsArgs& A) {
+  if (n < 0 || total < 0 || epochs < 0 || q_epoch_stride < 0) return fail(c, POI_EINVAL, "%s: n < 0, total < 0, epochs < 0 or q_epoch_stride < 0", who);
+  if (total >= ((int64_t)1 << 31)) return fail(c, POI_ENOTSUP, "%s: at most 2^31 - 1 check-ins per call", who);
+  if (q_epoch_stride != 0 && q_epoch_stride < total) return fail(c, POI_EINVAL, "%s: q_epoch_stride must be 0 or at least total", who);
+  if (n == 0 || total == 0 || epochs == 0) return POI_OK;
+  if (!off || !p || !q || !c_out) return fail(c, POI_EINVAL, "%s: NULL off / p / q / c_out", who);
+  A.off = off; A.p = p; A.q = q; A.q_epoch_stride = q_epoch_stride; A.n = n; A.total = total;
+  A.n_epoch = q_epoch_stride ? epochs : 1;
+  return POI_OK;
+}
+
+int poi_foldin_terms_fpmc(poi_ctx* c, const poi_fpmc_params* P, const int32_t* off, const int32_t* p, const int32_t* q, int64_t q_epoch_stride,
+                          int32_t n, int64_t total, int32_t epochs, double* c_out, void* stream) {
+  if (!c || !P || !P->ia || !P->ai) return fail(c, POI_EINVAL, "poi_foldin_terms_fpmc: NULL ctx / params / ia / ai");
+  if (is_f16(c, P->ia) || is_f16(c, P->ai)) return fail(c, POI_ENOTSUP, "FPMC-LR tables are float32 only");
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 256) return fail(c, POI_ENOTSUP, "poi_foldin_terms_fpmc: dim must be a multiple of 4 in [4, 256] (got %d)", P->dim);
+  if (P->n_item <= 0) return fail(c, POI_EINVAL, "poi_foldin_terms_fpmc: n_item <= 0");
+  poi::FoldinTermsArgs A = {};
+  int rc = foldin_terms_common(c, "poi_foldin_terms_fpmc", off, p, q, q_epoch_stride, n, total, epochs, c_out, A);
+  if (rc || !A.off) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  A.tab_pq = P->ia; A.tab_prev = P->ai; A.n_item = P->n_item; A.dim = P->dim; A.c_out = c_out;
+  HIPCHK(c, poi::launch_foldin_terms(A, false, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_foldin_terms_prme(poi_ctx* c, const poi_prme_params* P, const double* cordi, const int32_t* off, const int32_t* p, const int32_t* q,
+                          int64_t q_epoch_stride, const int32_t* gap, const double* dist, int32_t n, int64_t total, int32_t epochs, int32_t threshold,
+                          float cw, double* a_out, double* c_out, void* stream) {
+  if (!c || !P || !P->ds) return fail(c, POI_EINVAL, "poi_foldin_terms_prme: NULL ctx / params / ds");
+  if (is_f16(c, P->ds)) return fail(c, POI_ENOTSUP, "PRME tables are float32 only");
+  if (P->dim <= 0 || P->dim % 4 != 0 || P->dim > 256) return fail(c, POI_ENOTSUP, "poi_foldin_terms_prme: dim must be a multiple of 4 in [4, 256] (got %d)", P->dim);
+  if (P->n_item <= 0) return fail(c, POI_EINVAL, "poi_foldin_terms_prme: n_item <= 0");
+  poi::FoldinTermsArgs A = {};
+  int rc = foldin_terms_common(c, "poi_foldin_terms_prme", off, p, q, q_epoch_stride, n, total, epochs, c_out, A);
+  if (rc || !A.off) return rc;
+  if (!gap || !a_out || (!dist && !cordi)) return fail(c, POI_EINVAL, "poi_foldin_terms_prme: NULL gap / a_out, or neither dist nor cordi");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  A.tab_pq = P->ds; A.tab_prev = P->ds; A.n_item = P->n_item; A.dim = P->dim; A.c_out = c_out; A.a_out = a_out;
+  A.gap = gap; A.dist = dist; A.cordi = cordi; A.thd = threshold; A.cw = cw;
+  HIPCHK(c, poi::launch_foldin_terms(A, true, c->num_cu, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_foldin_pair(poi_ctx* c, const float* items, int32_t n_item, int32_t dim, int32_t form, int32_t first, const int32_t* off, const int32_t* p,
+                    const int32_t* q, int64_t q_epoch_stride, const double* a, const double* cterm, int64_t c_epoch_stride, int32_t n, int32_t epochs,
+                    float alpha, float lambda, const float* w0, float* w_out, float* loss_out, void* stream) {
+  if (!c || !items || !w_out) return fail(c, POI_EINVAL, "poi_foldin_pair: NULL ctx / items / w_out");
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_foldin_pair: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  if (form != FOLDIN_FORM_DOT && form != FOLDIN_FORM_METRIC) return fail(c, POI_EINVAL, "poi_foldin_pair: form must be POI_FOLDIN_DOT or POI_FOLDIN_METRIC (got %d)", form);
+  if (first != 0 && first != 1) return fail(c, POI_EINVAL, "poi_foldin_pair: first must be 0 or 1 (got %d)", first);
+  if (n < 0 || n_item <= 0 || epochs < 0 || q_epoch_stride < 0 || c_epoch_stride < 0)
+    return fail(c, POI_EINVAL, "poi_foldin_pair: n < 0, n_item <= 0, epochs < 0 or a negative epoch stride");
+  if (n == 0) return POI_OK;
+  if (!off || !p || !q) return fail(c, POI_EINVAL, "poi_foldin_pair: NULL off / p / q");
+  if (is_f16(c, items) || (w0 && is_f16(c, w0)) || is_f16(c, w_out)) return fail(c, POI_ENOTSUP, "poi_foldin_pair: items / w0 / w_out must be float32");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::FoldinPairArgs A = {};
+  A.items = items; A.n = n; A.n_item = n_item; A.dim = dim; A.epochs = epochs; A.form = form; A.first = first;
+  A.off = off; A.p = p; A.q = q; A.q_epoch_stride = q_epoch_stride;
+  A.a = form == FOLDIN_FORM_METRIC ? a : nullptr; A.c = cterm; A.c_epoch_stride = c_epoch_stride;
+  A.alpha = alpha; A.lambda = lambda;
+  A.w0 = w0; A.w_out = w_out; A.loss_out = loss_out;
+  int rc;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  A.dummy = (const double*)(A.bad + 8);      // (bytes 32 .. 39 of the counter's buffer: never written)
+  HIPCHK(c, poi::launch_foldin_pair(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_topk(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, int32_t k, int32_t* idx_out, float* score_out,
+             void* stream) {
+  if (!c || !scores || !idx_out) return fail(c, POI_EINVAL, "poi_topk: NULL argument");
+  if (k <= 0 || k > 64 || k > n_item) return fail(c, POI_ENOTSUP, "poi_topk supports 1 <= k <= min(64, n_item) (got %d)", k);
+  if (n < 0) return fail(c, POI_EINVAL, "n < 0");
+  if (n == 0) return POI_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, poi::launch_topk_rows(scores, n, n_item, k, idx_out, score_out, (hipStream_t)stream));
+  return POI_OK;
+}
+
+int poi_auc_preference(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t dim,
+                       const int32_t* tp, const int32_t* tq, const int32_t* tm, int32_t len, uint8_t* out, void* stream) {
+  if (!c || !users || !items || !tp || !tq || !tm || !out) return fail(c, POI_EINVAL, "poi_auc_preference: NULL argument");
+  if (dim <= 0 || dim % 4 != 0) return fail(c, POI_ENOTSUP, "dim must be a positive multiple of 4");
+  if (n < 0 || len < 0) return fail(c, POI_EINVAL, "bad sizes");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, poi::launch_auc(users, items, is_f16(c, items), n, dim, tp, tq, tm, len, out, (hipStream_t)stream));
+  return POI_OK;
+}
+
+int poi_sumsq(poi_ctx* c, const float* x, int64_t n, double* out, void* stream) {
+  if (!c || !x || !out || n < 0) return fail(c, POI_EINVAL, "poi_sumsq: bad argument");
+  if (n == 0) return POI_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (is_f16(c, x)) HIPCHK(c, poi::launch_sumsq_f16(x, n, out, (hipStream_t)stream));
+  else HIPCHK(c, poi::launch_sumsq(x, n, out, (hipStream_t)stream));
+  return POI_OK;
+}
+
+int poi_dist_prob(poi_ctx* c, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                  const float* sts, int32_t n, int32_t n_item, int32_t n_dist, double dd, float* prob_out, void* stream) {
+  if (!c || !coords || !last_poi || !sts || !prob_out) return fail(c, POI_EINVAL, "poi_dist_prob: NULL argument");
+  if ((cphi == nullptr) != (thr == nullptr)) return fail(c, POI_EINVAL, "poi_dist_prob: cphi and thr go together");
+  if (n < 0 || n_item <= 0 || n_dist <= 0 || !(dd > 0)) return fail(c, POI_EINVAL, "bad sizes");
+  HIPCHK(c, hipSetDevice(c->device));
+  for (int32_t o = 0; o < n; o += 32768) {
+    const int32_t m = n - o < 32768 ? n - o : 32768;
+    c->tm.begin("dist_prob", (hipStream_t)stream);
+    HIPCHK(c, poi::launch_dist_prob(coords, cphi, thr, last_poi + o, sts + (size_t)o * (n_dist + 1), m, n_item, n_dist, dd,
+                                    prob_out + (size_t)o * n_item, (hipStream_t)stream));
+    c->tm.end((hipStream_t)stream);
+  }
+  return POI_OK;
+}
+
+int poi_rank_metrics(poi_ctx* c, const int32_t* ranks, int32_t n, int32_t k, const int32_t* tes_p, const int32_t* tes_mask,
+                     int32_t len_tes, const int32_t* at_nums, int32_t n_at, double* acc, void* stream) {
+  if (!c || !ranks || !tes_p || !tes_mask || !at_nums || !acc) return fail(c, POI_EINVAL, "poi_rank_metrics: NULL argument");
+  if (n < 0 || k <= 0 || len_tes <= 0 || n_at <= 0 || n_at > 8) return fail(c, POI_EINVAL, "poi_rank_metrics: bad sizes (n_at <= 8)");
+  if (n == 0) return POI_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, poi::launch_rank_metrics(ranks, n, k, tes_p, tes_mask, len_tes, at_nums, n_at, acc, (hipStream_t)stream));
+  return POI_OK;
+}
+
+int poi_sample_negatives(poi_ctx* c, const int32_t* off, const int32_t* p, int32_t n_user, int32_t n_item, const int32_t* tes_p,
+                         const int32_t* tes_mask, int32_t len_tes, uint64_t seed, int32_t* q_out, int32_t* tes_q_out, void* stream) {
+  if (!c || !off || !p || !q_out) return fail(c, POI_EINVAL, "poi_sample_negatives: NULL argument");
+  if (tes_q_out && (!tes_p || !tes_mask || len_tes <= 0)) return fail(c, POI_EINVAL, "poi_sample_negatives: test tables missing");
+  if (n_user < 0 || n_item <= 0) return fail(c, POI_EINVAL, "bad sizes");
+  if (n_user == 0) return POI_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->tm.begin("sample_neg", (hipStream_t)stream);
+  HIPCHK(c, poi::launch_sample_neg(off, p, n_user, n_item, tes_p, tes_mask, len_tes, seed, q_out, tes_q_out, (hipStream_t)stream));
+  c->tm.end((hipStream_t)stream);
+  return POI_OK;
+}
+
+int poi_neg_dist_bins(poi_ctx* c, const int32_t* off, const int32_t* p, const int32_t* q, int32_t n_user, const double* coords,
+                      const double* cphi, const double* thr, int32_t n_dist, double dd, int32_t* dq_out, void* stream) {
+  if (!c || !off || !p || !q || !coords || !cphi || !thr || !dq_out) return fail(c, POI_EINVAL, "poi_neg_dist_bins: NULL argument");
+  if (n_user < 0 || n_dist <= 0 || !(dd > 0)) return fail(c, POI_EINVAL, "bad sizes");
+  if (n_user == 0) return POI_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->tm.begin("neg_dist", (hipStream_t)stream);
+  HIPCHK(c, poi::launch_neg_dist(off, p, q, n_user, coords, cphi, thr, n_dist, dd, dq_out, (hipStream_t)stream));
+  c->tm.end((hipStream_t)stream);
+  return POI_OK;
+}
+
+int poi_delta_make(poi_ctx* c, const float* cur, const float* base, float* delta, int64_t n, void* stream) {
+  if (!c || !cur || !base || !delta || n < 0) return fail(c, POI_EINVAL, "poi_delta_make: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, poi::launch_delta_make(cur, base, delta, n, (hipStream_t)stream));
+  return POI_OK;
+}
+
+int poi_delta_apply(poi_ctx* c, float* cur, const float* base, const float* delta_sum, int64_t n, void* stream) {
+  if (!c || !cur || !base || !delta_sum || n < 0) return fail(c, POI_EINVAL, "poi_delta_apply: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, poi::launch_delta_apply(cur, base, delta_sum, n, (hipStream_t)stream));
+  return POI_OK;
+}
+
+}  // extern "C"

@@ -327,13 +327,6 @@ static hipError_t launch_bpr_hogwild_t(const BprArgs& A, hipStream_t st, Timing*
   return hipGetLastError();
 }
 
-// workspace of a snapshot launch of n triples (see abi.hip poi_bpr_step): ints, floats
-void bpr_ws_sizes(int n, int dim, size_t* n_int, size_t* n_float) {
-  const size_t chunks = (size_t)(n + 63) / 64 + (size_t)(2 * (size_t)n + 63) / 64 + 2;
-  *n_int = 4 * (3 * (size_t)n + 64) + RS_HIST_INTS + RS_MAXBIN + 64 + 4 * chunks;
-  *n_float = (((size_t)n + 64 + 3) & ~(size_t)3) + 2 * chunks * (size_t)dim;
-}
-
 hipError_t launch_bpr(BprArgs& A, int mode, int num_cu, hipStream_t st, Timing* tm) {
   if (mode == 1) {
     if (A.lt_f16) return hipErrorInvalidValue;

@@ -278,12 +278,6 @@ __global__ __launch_bounds__(256) void fpmc_commit_kernel(FpmcArgs A) {
   }
 }
 
-void fpmc_ws_sizes(int n, int dim, size_t* n_int, size_t* n_float) {
-  const size_t chunks = ((size_t)6 * n + 63) / 64 + 2;
-  *n_int = 4 * (6 * (size_t)n + 64) + RS_HIST_INTS + RS_MAXBIN + 64 + 4 * chunks;
-  *n_float = (((size_t)n + 64 + 3) & ~(size_t)3) + 2 * chunks * (size_t)dim + 6 * (size_t)n * dim;
-}
-
 template <int LPR>
 static hipError_t launch_fpmc_step_t(FpmcArgs& A, int num_cu, hipStream_t st, Timing* tm) {
   const int n = A.n;

@@ -342,7 +342,6 @@ struct BprArgs {
   float *lead, *trail;    // per window: partial sum of its opening / closing run
 };
 hipError_t launch_bpr(BprArgs& A, int mode, int num_cu, hipStream_t st, Timing* tm);
-void bpr_ws_sizes(int n, int dim, size_t* n_int, size_t* n_float);
 
 // FPMC-LR (fpmc.hip)
 struct FpmcNbrArgs {
@@ -371,7 +370,6 @@ struct FpmcArgs {
   float *s, *lead, *trail, *slot;   // per transition sigmoid(-x); per-window partial sums; (6 n, D) new rows at a run's first position
 };
 hipError_t launch_fpmc_step(FpmcArgs& A, int num_cu, hipStream_t st, Timing* tm);
-void fpmc_ws_sizes(int n, int dim, size_t* n_int, size_t* n_float);
 
 // PRME (prme.hip)
 struct PrmeArgs {
@@ -390,7 +388,6 @@ struct PrmeArgs {
   float *ga, *gb, *lead, *trail, *slot;   // per transition 2 a g, 2 b g; per-window partial sums; (7 n, D) new rows at a run's first position
 };
 hipError_t launch_prme_step(PrmeArgs& A, int num_cu, hipStream_t st, Timing* tm);
-void prme_ws_sizes(int n, int dim, size_t* n_int, size_t* n_float);
 struct PrmeScoreArgs {
   const float *du, *dp, *ds;        // (n_user, D), (>= n_item, D), (n_item + 1, D)
   const double* coords;             // (n_item + 1, 2) lat, lon (row n_item: the pad POI)
@@ -533,7 +530,6 @@ struct VbprArgs {
   float* out; int n_rows;           // items: (n_rows, 2 D) output over the n_rows = n_item + 1 table rows
 };
 void vbpr_chunking(int n, int* ch_rows, int* n_chunk);
-void vbpr_ws_sizes(int n, int dim, int n_img, size_t* n_int, size_t* n_float, size_t* n_double);
 hipError_t launch_vbpr_step(VbprArgs& A, int num_cu, hipStream_t st, Timing* tm);
 hipError_t launch_vbpr_items(VbprArgs& A, int num_cu, hipStream_t st, Timing* tm);
 hipError_t launch_vbpr_users(const float* ux, const float* ue, int n_user, int dim, float* out, int num_cu, hipStream_t st, Timing* tm);

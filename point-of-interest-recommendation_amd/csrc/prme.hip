@@ -202,12 +202,6 @@ __global__ __launch_bounds__(256) void prme_commit_kernel(PrmeArgs A) {
   }
 }
 
-void prme_ws_sizes(int n, int dim, size_t* n_int, size_t* n_float) {
-  const size_t chunks = ((size_t)7 * n + 63) / 64 + 2, nt = ((size_t)n + 64 + 3) & ~(size_t)3;
-  *n_int = 4 * (7 * (size_t)n + 64) + RS_HIST_INTS + RS_MAXBIN + 64 + 4 * chunks;
-  *n_float = 2 * nt + 2 * chunks * (size_t)dim + 7 * (size_t)n * dim;
-}
-
 template <int LPR>
 static hipError_t launch_prme_step_t(PrmeArgs& A, int num_cu, hipStream_t st, Timing* tm) {
   const int n = A.n;

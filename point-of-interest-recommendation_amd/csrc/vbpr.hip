@@ -370,15 +370,6 @@ void vbpr_chunking(int n, int* ch_rows, int* n_chunk) {
   *n_chunk = (int)(leaves < 1 ? 1 : (leaves + per - 1) / (per < 1 ? 1 : per));
 }
 
-void vbpr_ws_sizes(int n, int dim, int n_img, size_t* n_int, size_t* n_float, size_t* n_double) {
-  int ch_rows = 0, n_chunk = 0;
-  vbpr_chunking(n, &ch_rows, &n_chunk);
-  const size_t chunks = ((size_t)4 * n + 63) / 64 + 2, nt = ((size_t)n + 64 + 3) & ~(size_t)3;
-  *n_int = 4 * (4 * (size_t)n + 64) + RS_HIST_INTS + RS_MAXBIN + 64 + 4 * chunks + 2 * nt;
-  *n_float = nt + (size_t)n * dim + 2 * chunks * (size_t)dim + 4 * (size_t)n * dim;
-  *n_double = (size_t)n_chunk * dim * n_img;
-}
-
 static int vbpr_grid(const VbprArgs& A, long long items, int num_cu, int per_cu) {
   long long g = items < 1 ? 1 : items;
   if (g > (long long)num_cu * per_cu) g = (long long)num_cu * per_cu;

@@ -241,3 +241,35 @@ def test_sequence_file_round_trip(tmp_path):
     assert np.array_equal(ds.coords, coords[[back[a] for a in range(ds.n_item)]])
     with pytest.raises(IndexError):
         D.load_sequence_file(path, split=-13)
+
+
+def _csrc():
+    return os.path.join(ROOT, "point-of-interest-recommendation_amd", "csrc")
+
+
+def test_every_included_header_is_a_build_dependency():
+    """A header that build.HEADERS does not name can change without any object being rebuilt: the library goes stale silently."""
+    csrc = _csrc()
+    files = list(poi_amd.build.SOURCES) + [f for f in os.listdir(csrc) if f.endswith(".h")]
+    for fn in files:
+        for name in re.findall(r'^\s*#\s*include\s+"([^"/]+\.h)"', open(os.path.join(csrc, fn)).read(), flags=re.M):
+            assert name in poi_amd.build.HEADERS, "%s includes %s, which is not in build.HEADERS" % (fn, name)
+    assert os.path.join("..", "..", "include", "poi_hip.h") in poi_amd.build.HEADERS
+
+
+def test_sources_are_the_translation_units_of_the_tree():
+    csrc = _csrc()
+    for s in poi_amd.build.SOURCES:
+        assert os.path.exists(os.path.join(csrc, s)), s
+    assert len(set(poi_amd.build.SOURCES)) == len(poi_amd.build.SOURCES)
+    for fn in os.listdir(csrc):
+        if fn.endswith(".hip"):
+            assert fn in poi_amd.build.SOURCES, "%s would be left out of the library" % fn
+
+
+def test_no_workspace_size_function_remains():
+    """The workspaces are sized by the dry pass of their own carving (abi_internal.h Carver): no second description of a layout."""
+    csrc = _csrc()
+    for fn in os.listdir(csrc):
+        if fn.endswith((".hip", ".h")):
+            assert "_ws_sizes" not in open(os.path.join(csrc, fn)).read(), fn
