@@ -80,6 +80,8 @@ extern "C" {
  * included, unchanged). */
 /* additive to 9: group recommendation - new entry points poi_group_topk and poi_group_topk_scores, options "group_split_max" / "group_grid",
  * plan keys "group_path" / "group_splits" / "group_split_max", timing names "group_topk" / "group_topk_scores" (existing entries unchanged). */
+/* additive to 9: route recommendation - new entry points poi_route_expand and poi_route_merge, options "route_split_max" / "route_grid",
+ * plan keys "route_path" / "route_splits", timing names "route_expand" / "route_merge" (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -165,7 +167,8 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * Additive to 9: "near_path", "near_splits", "near_split_max" - written by poi_score_topk_near in the same way.
  * Additive to 9: "rank_splits" - written by poi_score_rank in the same way.
  * Additive to 9: "geoie_score_span", "geoie_score_splits" - written by poi_geoie_score_all_geo / poi_geoie_score_topk_geo in the same way.
- * Additive to 9: "group_path", "group_splits", "group_split_max" - written by poi_group_topk in the same way. */
+ * Additive to 9: "group_path", "group_splits", "group_split_max" - written by poi_group_topk in the same way.
+ * Additive to 9: "route_path", "route_splits" - written by poi_route_expand in the same way. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -241,7 +244,11 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *   "group_split_max" n (default 256): poi_group_topk calls of at most n groups cut the item range into slices, a workgroup each, and merge
  *       the slices' lists (0: never); larger calls run one workgroup per 8 groups;
  *   "group_grid" n (default 0 = by the group count and the CUs; at most 64): slices on that split path - bitwise the same result for
- *       every n and on either path. */
+ *       every n and on either path.
+ *   "route_split_max" n (default 8192 = 32 rows for each of 256 CUs): poi_route_expand calls of at most n rows cut the item range of every
+ *       32-row tile over several workgroups and finish the rows in a second kernel (0: never); larger calls run one workgroup per tile;
+ *   "route_grid" n (default 0 = by the row count and the CUs; at most 64): workgroups per 32-row tile on that split path - bitwise the
+ *       same result for every n and on either path. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -946,6 +953,68 @@ int poi_group_topk(poi_ctx* ctx, const float* users, const float* items, int32_t
 int poi_group_topk_scores(poi_ctx* ctx, const float* scores, int32_t n, int32_t n_item,
                           const int32_t* g_off, const int32_t* g_mem, int32_t n_grp, int32_t agg, const int32_t* ex_off, const int32_t* ex,
                           int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+
+/* ---- route recommendation (additive to 9): beam search over a session's next N POIs ---------------------------------------------------------
+ * Every other serving entry stops at one hop: the best next place for a state that exists.  A route - "plan my afternoon" - is not the
+ * top-N of one ranking: the second stop depends on the first, the recurrent state moves, and under the distance term the next hop is
+ * measured from the stop before it.  These two entries are one step of a beam search; the state gathering between steps is the caller's
+ * (index_select) and the advance is poi_session_advance / poi_session_cell_advance on a scratch session.
+ *
+ * DEFINITION.  Route of a slot under its current state, beam width B (1 <= B <= 8), T steps (1 <= T <= 16).  A hypothesis is (path,
+ * total, state).  Start: one live hypothesis - empty path, total 0.0 (float64), the slot's state.  At step t, for every live hypothesis r:
+ *   s(r, j)       exactly poi_score_rank's s(r, j): float(h_r) . items[j] in float32 from the same product routine, fragment loader and k
+ *                 order; with wd non-NULL plus wd * sts[r][bin(last_poi[r], j)] for bin < n_dist.  A hypothesis with last_poi[r] < 0 (a fresh
+ *                 slot at step 0) has no distance term.  A candidate's score is bit-equal to poi_score_rank's score_out for the same row
+ *                 and POI.
+ *   lse(r)        log sum_{j in [0, n_item)} exp(s(r, j)) over ALL POIs, excluded ones included: the model's distribution; exclusion only
+ *                 limits what may be chosen.  float64: every float32 score is widened before exp; the result is max + log(float64 sum).
+ *                 ORDER OF THE SUM - a function of the row's scores alone, not of the grid, the regime or the row's place in the call:
+ *                 the POIs are cut into ITEM BLOCKS of 512 consecutive ids.  Inside a block, residue class l = j mod 32 (l = 0 .. 31) is
+ *                 one chain in ascending j: a running maximum m and sum, sum = sum * exp(m - s) + 1 when s > m (m := s), else
+ *                 sum += exp(s - m).  The 32 chains are rescaled to the block's maximum, sum_l * exp(m_l - M_b), and added by a
+ *                 butterfly over l (partners l xor 16, 8, 4, 2, 1).  Over the blocks: M = the maximum of the M_b, then the terms
+ *                 S_b * exp(M_b - M) are added in ASCENDING BLOCK ORDER, one serial chain from block 0; lse = M + log(S).  Scores are
+ *                 expected finite (-inf is accepted and adds nothing).
+ *   C(r)          [0, n_item) minus the slot's exclusion list minus the hypothesis's own path (the caller passes path_len = 0 to allow
+ *                 revisits).
+ *   NaN           a NaN score is never selected and adds nothing to the sum.
+ *   expansion     r proposes its best min(B, |C(r)|) candidates by the tie rule of every top-K entry (higher score, then lower id), each
+ *                 with total_r + (double(s) - lse(r)).
+ *   merge         the slot keeps the best B of its at most B * B proposals: higher total, then lower parent beam index, then lower POI
+ *                 id.  A survivor inherits its parent's state and path, appends the POI and is advanced by it.
+ *   dead beams    fewer than B proposals leave dead beams: POI -1 from that step on, total -inf; they never come back and never propose.
+ *                 A dead beam's parent_out is its own place (capped to n_par - 1), so that a gather stays in range.
+ *
+ * poi_route_expand - score + normaliser + top-b with exclusion, one pass over the item table for n hypothesis rows:
+ *   users ... dd          poi_score_rank's arguments (users float32, items float32 or a registered half table, dim a multiple of 4 <= 256).
+ *   path                  (n, path_stride) int32, path_len <= 16 valid ids per row (unsorted), or path_len = 0.
+ *   ex_off, ex            exclusion lists in the conventions of poi_score_topk_near; row r uses list r / rows_per_list, so that the B rows of
+ *                         a slot share one list (rows_per_list = 1: a list per row).  Both NULL = none.
+ *   live                  (n) int32 or NULL: a row with live[r] == 0 is dead - it is not read and costs nothing.
+ *   outputs               idx_out (n, b) by descending score, ties by ascending id, -1 where |C(r)| < b; score_out (n, b), -inf there;
+ *                         lse_out (n) float64; count_out (n) or NULL = |C(r)|.
+ *   bad rows              an exclusion list that is not ascending or leaves [0, n_item), or a path id outside [0, n_item): the row is
+ *                         -1 / -inf / NaN lse / count 0 and is counted once (poi_ctx_take_bad_ids).  A dead row gives the same and is not counted.
+ * No float atomics: identical calls give bitwise identical outputs, every grid and both regimes give the same outputs as every other, and
+ * a row gives the same outputs alone as inside a larger call.  Two launch regimes: calls of at most "route_split_max" rows (a single
+ * user's 1 .. 8 hypotheses is the live-traffic case) cut the item range of every 32-row tile over "route_grid" workgroups and finish the
+ * rows in a second kernel; larger calls run one workgroup per 32-row tile, which finishes its own rows.  poi_ctx_last_plan: "route_path"
+ * (0 tile, 1 split), "route_splits" (workgroups per tile, 0 on the tile path).  Timing name: "route_expand".  n = 0 is a no-op. */
+int poi_route_expand(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                     const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                     int32_t n_dist, double dd,
+                     const int32_t* path, int32_t path_stride, int32_t path_len, const int32_t* ex_off, const int32_t* ex, int32_t rows_per_list,
+                     const int32_t* live, int32_t b,
+                     int32_t* idx_out, float* score_out, double* lse_out, int32_t* count_out, void* stream);
+/* The merge of one step: n_slot slots, n_par parent rows each (1 at step 0, B afterwards), b proposals per parent (n_par * b <= 64); idx /
+ * score (n_slot * n_par, b) and lse (n_slot * n_par) are the expand outputs, total_in (n_slot, n_par) float64 the parents' totals, n_live
+ * (n_slot) the number of live parents (a prefix of the slot's rows), NULL = all.  Outputs (n_slot, b) by the order above: parent_out,
+ * poi_out (-1: dead), total_out (-inf: dead), steplp_out or NULL = double(score) - lse of the step (-inf: dead); nlive_out (n_slot) or NULL =
+ * the live survivors.  Proposals with a -inf or NaN total sort last and come out dead.  One wavefront per slot, one proposal per lane.
+ * Timing name: "route_merge". */
+int poi_route_merge(poi_ctx* ctx, const int32_t* idx, const float* score, const double* lse, const double* total_in, const int32_t* n_live,
+                    int32_t n_slot, int32_t n_par, int32_t b,
+                    int32_t* parent_out, int32_t* poi_out, double* total_out, double* steplp_out, int32_t* nlive_out, void* stream);
 
 /* ---- fold-in (additive to 9): a user row of OboBpr / OboVBpr for a check-in history the model never trained on -------------------------------
  * The factorisation family's only user representation is a trained row of ux (and ue).  Fold-in freezes the item side and runs the

@@ -715,6 +715,81 @@ int poi_group_topk_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_
 }
 
 // ---------------------------------------------------------------------------------------------
+// route recommendation (route.hip)
+int poi_route_expand(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                     const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                     const int32_t* path, int32_t path_stride, int32_t path_len, const int32_t* ex_off, const int32_t* ex, int32_t rows_per_list,
+                     const int32_t* live, int32_t b, int32_t* idx_out, float* score_out, double* lse_out, int32_t* count_out, void* stream) {
+  if (!c || !users || !items || !idx_out || !score_out || !lse_out) return fail(c, POI_EINVAL, "poi_route_expand: NULL ctx / users / items / idx_out / score_out / lse_out");
+  if (b <= 0 || b > ROUTE_B_MAX) return fail(c, POI_ENOTSUP, "poi_route_expand supports 1 <= b <= %d (got %d)", ROUTE_B_MAX, b);
+  if (path_len < 0 || path_len > ROUTE_T_MAX) return fail(c, POI_ENOTSUP, "poi_route_expand supports 0 <= path_len <= %d (got %d)", ROUTE_T_MAX, path_len);
+  if (path_len > 0 && (!path || path_stride < path_len)) return fail(c, POI_EINVAL, "poi_route_expand: path_len > 0 needs path and path_stride >= path_len");
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_route_expand: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "poi_route_expand: n < 0 or n_item <= 0");
+  if (rows_per_list <= 0) return fail(c, POI_EINVAL, "poi_route_expand: rows_per_list must be positive (got %d)", rows_per_list);
+  const bool geo = wd != nullptr;
+  float bin_scale;
+  int rc;
+  if ((rc = check_ex_pair(c, "poi_route_expand", ex_off, ex))) return rc;
+  if ((rc = check_geo_term(c, "poi_route_expand", geo, !geo || (sts && coords && cphi && thr && last_poi), "the distance term needs sts / coords / cphi / thr / last_poi", n_dist, dd, &bin_scale))) return rc;
+  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "poi_route_expand: users must be float32");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::RouteArgs A = {};
+  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
+  A.n = n; A.n_item = n_item; A.dim = dim; A.b = b;
+  if (geo) { A.wd = wd; A.sts = sts; A.coords = coords; A.cphi = cphi; A.thr = thr; A.last_poi = last_poi; A.n_dist = n_dist; A.bin_scale = bin_scale; }
+  A.path = path; A.path_stride = path_stride; A.path_len = path_len;
+  A.ex_off = ex_off; A.ex = ex; A.rows_per_list = rows_per_list; A.live = live;
+  A.idx_out = idx_out; A.score_out = score_out; A.lse_out = lse_out; A.count_out = count_out;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  // few rows (live traffic: one user's 1 .. 8 hypotheses): the item range is cut over workgroups so that the call fills the CUs, and a
+  // second kernel finishes the rows; many rows: one workgroup per 32-row tile, which finishes its own rows
+  const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
+  A.n_blk = (ntile + ROUTE_LSE_TILES - 1) / ROUTE_LSE_TILES;
+  const int split = n <= c->route_split_max;
+  A.n_split = 1; A.finish = 1;
+  if (split) {
+    int s = c->route_grid > 0 ? c->route_grid : 2 * c->num_cu / n_utile;
+    if (c->route_grid <= 0 && s > (A.n_blk + ROUTE_NWAVE - 1) / ROUTE_NWAVE) s = (A.n_blk + ROUTE_NWAVE - 1) / ROUTE_NWAVE;      // (a wave walks whole item blocks)
+    if (s < 1) s = 1;
+    A.n_split = s > ROUTE_SPLIT_LIMIT ? ROUTE_SPLIT_LIMIT : s;
+    A.finish = 0;
+  }
+  const size_t rows = (size_t)n_utile * 32, lists = rows * A.n_split * ROUTE_NWAVE;
+  if ((rc = carve(c, c->route_ws, st, [&](Carver& W) {
+        A.part_s = (float*)W.bytes(sizeof(float) * lists * ROUTE_B_MAX);
+        A.part_i = (int*)W.bytes(sizeof(int) * lists * ROUTE_B_MAX);
+        A.part_lse = (double*)W.bytes(sizeof(double) * rows * A.n_blk * 2);
+        A.row_st = (int*)W.bytes(sizeof(int) * rows);
+        A.row_cnt = (int*)W.bytes(sizeof(int) * rows);
+      })))
+    return rc;
+  c->plan.valid = 1; c->plan.route_path = split; c->plan.route_splits = split ? A.n_split : 0;
+  HIPCHK(c, poi::launch_route_expand(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_route_merge(poi_ctx* c, const int32_t* idx, const float* score, const double* lse, const double* total_in, const int32_t* n_live,
+                    int32_t n_slot, int32_t n_par, int32_t b, int32_t* parent_out, int32_t* poi_out, double* total_out, double* steplp_out,
+                    int32_t* nlive_out, void* stream) {
+  if (!c || !idx || !score || !lse || !total_in || !parent_out || !poi_out || !total_out)
+    return fail(c, POI_EINVAL, "poi_route_merge: NULL ctx / idx / score / lse / total_in / parent_out / poi_out / total_out");
+  if (b <= 0 || b > ROUTE_B_MAX || n_par <= 0 || n_par > ROUTE_B_MAX) return fail(c, POI_ENOTSUP, "poi_route_merge supports 1 <= b, n_par <= %d (got %d, %d)", ROUTE_B_MAX, b, n_par);
+  if (n_slot < 0) return fail(c, POI_EINVAL, "poi_route_merge: n_slot < 0");
+  if (n_slot == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::RouteMergeArgs A = {};
+  A.idx = idx; A.score = score; A.lse = lse; A.total_in = total_in; A.n_live = n_live;
+  A.n_slot = n_slot; A.n_par = n_par; A.b = b;
+  A.parent_out = parent_out; A.poi_out = poi_out; A.total_out = total_out; A.steplp_out = steplp_out; A.nlive_out = nlive_out;
+  HIPCHK(c, poi::launch_route_merge(A, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // fold-in of new users (foldin.hip)
 int poi_foldin_bpr(poi_ctx* c, const float* items, int32_t n_item, int32_t dim, const int32_t* off, const int32_t* p, const int32_t* q,
                    int64_t q_epoch_stride, int32_t n, int32_t epochs, float alpha, float lambda, const float* w0, float* w_out,

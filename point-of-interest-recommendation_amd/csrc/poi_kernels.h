@@ -630,6 +630,35 @@ struct GroupArgs {
 hipError_t launch_group(GroupArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_group_scores(const float* scores, GroupArgs& A, hipStream_t st, Timing* tm);
 
+// Route recommendation (route.hip): one beam-search step - per row the best b candidates and the normaliser over all POIs; the merge
+#define ROUTE_B_MAX 8                       // beam width: list length, and parents x b <= 64 proposals meet in one wave
+#define ROUTE_T_MAX 16                      // steps: the longest path a row may carry
+#define ROUTE_SPLIT_LIMIT 64                // workgroups the item range of a 32-row tile may be split over
+#define ROUTE_NWAVE 4                       // waves of a workgroup (POI_NWAVE): the item ranges of a tile are n_split * ROUTE_NWAVE
+#define ROUTE_LSE_TILES 16                  // 32-item tiles per ITEM BLOCK of the normaliser (512 POIs): the unit of its summation order
+struct RouteArgs {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim, b;
+  const float *wd, *sts; const double *coords, *cphi, *thr; const int* last_poi; int n_dist; float bin_scale;      // distance term, or wd null
+  const int* path; int path_stride, path_len;                 // (n, path_stride): path_len ids per row that leave the candidates
+  const int *ex_off, *ex; int rows_per_list;                  // exclusion lists (ascending ids), list row / rows_per_list; or both null
+  const int* live;                                            // (n) 0: the row is dead and costs nothing; null: every row is live
+  int n_split, finish, n_blk;                                 // workgroups per 32-row tile; 1: the tile path (n_split 1) finishes its rows itself; item blocks
+  float* part_s; int* part_i;                                 // (rows padded to 32, 4 n_split, ROUTE_B_MAX) partial lists
+  double* part_lse;                                           // (rows padded to 32, n_blk, 2): max and rescaled float64 sum of every item block
+  int *row_st, *row_cnt;                                      // (rows padded to 32): 0 dead, 1 live, 2 rejected; |C(r)|
+  int* idx_out; float* score_out; double* lse_out; int* count_out;      // count_out may be null
+  int* bad;                                                   // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+struct RouteMergeArgs {
+  const int* idx; const float* score; const double* lse;      // the expand outputs of n_slot * n_par rows
+  const double* total_in; const int* n_live;                  // (n_slot, n_par); (n_slot) live parents (a prefix), or null: all
+  int n_slot, n_par, b;
+  int *parent_out, *poi_out; double *total_out, *steplp_out; int* nlive_out;      // (n_slot, b); steplp_out / nlive_out may be null
+};
+hipError_t launch_route_expand(const RouteArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_route_merge(const RouteMergeArgs& A, hipStream_t st, Timing* tm);
+
 // Fold-in of new users for the factorisation family (foldin.hip)
 #define FOLDIN_USERS_PER_WAVE 4             // one 16-lane DPP row per user
 struct FoldinArgs {

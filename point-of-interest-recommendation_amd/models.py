@@ -1770,6 +1770,109 @@ class Session:
         g_mem = self._i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=m.device)
         return m._group_launch(users, m.trained_items.t, term, self._i32(off), g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync)
 
+    # ---- routes ---------------------------------------------------------------------------------
+    ROUTE_BEAM_MAX, ROUTE_STEPS_MAX = 8, 16
+
+    @classmethod
+    def _route_args(cls, steps, beam):
+        steps, beam = int(steps), int(beam)
+        if not 1 <= beam <= cls.ROUTE_BEAM_MAX:
+            raise _lib.PoiError("route recommendation supports 1 <= beam <= %d (got %d)" % (cls.ROUTE_BEAM_MAX, beam))
+        if not 1 <= steps <= cls.ROUTE_STEPS_MAX:
+            raise _lib.PoiError("route recommendation supports 1 <= steps <= %d (got %d)" % (cls.ROUTE_STEPS_MAX, steps))
+        return steps, beam
+
+    def _route_expand(self, users, sts, last_poi, path, path_len, ex, rows_per_list, live, b, return_counts=False):
+        """One poi_route_expand call on explicit rows -> (idx (n, b), score (n, b), lse (n) float64[, counts]) device tensors.  sts /
+        last_poi: the rows' distance-term state (spatial sessions) or None."""
+        m = self.m
+        n = users.shape[0]
+        idx = torch.empty((n, b), dtype=torch.int32, device=m.device)
+        sc = torch.empty((n, b), dtype=torch.float32, device=m.device)
+        lse = torch.empty(n, dtype=torch.float64, device=m.device)
+        cnt = torch.empty(n, dtype=torch.int32, device=m.device) if return_counts else None
+        wd = coords = cphi = thr = None
+        n_dist, dd_m = 0, 0.0
+        if sts is not None:
+            wd, coords, cphi, thr, n_dist, dd_m = m.wd.t, m.coords, m._cphi, m._binthr, m.n_dist, m.dd * 1000.0
+        m.ctx.check(m.lib.poi_route_expand(m.ctx.handle, _ptr(users), _ptr(m.trained_items.t), n, m.n_item, users.shape[1], _ptr(wd), _ptr(sts), _ptr(coords),
+                                           _ptr(cphi), _ptr(thr), _ptr(last_poi), int(n_dist), float(dd_m), _ptr(path), path.shape[1] if path is not None else 0,
+                                           int(path_len), _ptr(ex[0]), _ptr(ex[1]), int(rows_per_list), _ptr(live), int(b), _ptr(idx), _ptr(sc), _ptr(lse),
+                                           _ptr(cnt), m._stream()))
+        return (idx, sc, lse, cnt) if return_counts else (idx, sc, lse)
+
+    def _route_merge(self, idx, sc, lse, total, n_live, n_slot, n_par, b, return_step_scores=False):
+        """One poi_route_merge call -> (parent, poi, total (n_slot, b), steplp | None, n_live (n_slot)) device tensors."""
+        m = self.m
+        parent = torch.empty((n_slot, b), dtype=torch.int32, device=m.device)
+        poi = torch.empty((n_slot, b), dtype=torch.int32, device=m.device)
+        tot = torch.empty((n_slot, b), dtype=torch.float64, device=m.device)
+        slp = torch.empty((n_slot, b), dtype=torch.float64, device=m.device) if return_step_scores else None
+        nl = torch.empty(n_slot, dtype=torch.int32, device=m.device)
+        m.ctx.check(m.lib.poi_route_merge(m.ctx.handle, _ptr(idx), _ptr(sc), _ptr(lse), _ptr(total), _ptr(n_live), n_slot, n_par, b, _ptr(parent), _ptr(poi),
+                                          _ptr(tot), _ptr(slp), _ptr(nl), m._stream()))
+        return parent, poi, tot, slp, nl
+
+    _ROUTE_STATE = ("h", "c", "sts", "last_poi", "steps")      # what a hypothesis inherits from its parent (c: an Lstm's cell state)
+
+    def recommend_route(self, slots, steps, beam=4, exclude="last", revisit=False, return_step_scores=False, sync=True):
+        """The best `beam` routes of `steps` next POIs for every slot under its CURRENT state (include/poi_hip.h, route recommendation):
+        a beam search whose step score is the log-softmax over all POIs of the score rule of `recommend`.  At every step each live
+        hypothesis proposes its best `beam` POIs outside exclude and - unless revisit - outside its own path (poi_route_expand), the
+        slot keeps the best `beam` of the proposals by total log-probability (poi_route_merge), and the survivors are advanced by their
+        POI on a scratch session of n * beam slots.  exclude: None, "last" (the slot's last_poi at the call) or CSR lists (off, ids) per
+        slot.  Returns paths (n, beam, steps) int32 and logp (n, beam) float64 device tensors, beams by descending logp (-1 / -inf: a
+        dead beam - fewer candidates than beams); with return_step_scores also the per-step log-probabilities (n, beam, steps) float64.
+        The session's own slots are only read (they may repeat): a route is a what-if.  The loop issues no host synchronisation;
+        sync=True raises IndexError at the end when a device exclusion list was malformed."""
+        m = self.m
+        T, B = self._route_args(steps, beam)
+        ids = self._slot_tensor(slots)
+        n = ids.numel()
+        dev = m.device
+        paths = torch.full((n * B, T), -1, dtype=torch.int32, device=dev)
+        total = torch.zeros((n, 1), dtype=torch.float64, device=dev)
+        slp = torch.full((n * B, T), float("-inf"), dtype=torch.float64, device=dev) if return_step_scores else None
+        if n == 0:
+            out = (paths.view(0, B, T), total.new_zeros((0, B)))
+            return out + (slp.view(0, B, T),) if return_step_scores else out
+        src = {k: getattr(self, k).index_select(0, ids) for k in self._ROUTE_STATE if getattr(self, k, None) is not None}
+        ex = m._near_exclusion(exclude, n, src["last_poi"].contiguous(), kinds=("last",))
+        scratch = type(self)(m, n_slot=n * B)
+        all_rows = torch.arange(n * B, dtype=torch.int32, device=dev)
+        base = torch.arange(n, device=dev)[:, None]
+        beam_no = torch.arange(B, dtype=torch.int32, device=dev)[None, :]
+        P, nlive, live = 1, None, None
+        for t in range(T):
+            users = src["h"].float().contiguous()
+            sts = src["sts"].contiguous() if self.spatial else None
+            lp = src["last_poi"].contiguous() if self.spatial else None
+            idx, sc, lse = self._route_expand(users, sts, lp, None if revisit or t == 0 else paths, 0 if revisit else t, ex, P, live, B)
+            parent, poi, total, step_lp, nlive = self._route_merge(idx, sc, lse, total, nlive, n, P, B, return_step_scores)
+            flat = (base * P + parent.long()).reshape(-1)
+            if t > 0:
+                paths = paths.index_select(0, flat)
+            paths[:, t] = poi.reshape(-1)
+            if slp is not None:
+                if t > 0:
+                    slp = slp.index_select(0, flat)
+                slp[:, t] = step_lp.reshape(-1)
+            if t + 1 == T:
+                break
+            for k in src:                                # the survivors' states, then one check-in each (a dead row: POI 0, it stays dead)
+                setattr(scratch, k, src[k].index_select(0, flat).contiguous())
+            nxt = poi.clamp(min=0).reshape(-1).contiguous()
+            scratch._launch(all_rows.data_ptr(), nxt.data_ptr(), n * B)
+            src = {k: getattr(scratch, k) for k in src}
+            live = (beam_no < nlive[:, None]).int().contiguous()
+            P = B
+        if sync:
+            bad = m.ctx.take_bad_ids(m._stream().value)
+            if bad:
+                raise IndexError("%d hypothesis row(s) with an exclusion id outside [0, %d) or a list that is not ascending: their routes are dead" % (bad, m.n_item))
+        out = (paths.view(n, B, T), total)
+        return out + (slp.view(n, B, T),) if return_step_scores else out
+
 
 class CellSession(Session):
     """Online sessions of the baselines `Lstm`, `Rnn` and `OboCARNN` (model.cell_session()): the slot bookkeeping, `advance`, `replay`
@@ -1913,6 +2016,13 @@ class CellSession(Session):
             raise _lib.PoiError("OboCARNN ranks by a score rule of its own, not users . items: recommend_group is not supported on its sessions "
                                 "(model.recommend_group covers the trained users)")
         return super().recommend_group(slot_groups, k, agg, exclude, return_scores, return_counts, sync)
+
+    def recommend_route(self, slots, steps, beam=4, exclude="last", revisit=False, return_step_scores=False, sync=True):
+        """Lstm / Rnn: `Session.recommend_route` over the plain rule (the Lstm's c travels with h).  CA-RNN ranks by a rule of its own
+        and is refused."""
+        if self.carnn:
+            raise _lib.PoiError("OboCARNN ranks by a score rule of its own, not users . items: recommend_route is not supported on its sessions")
+        return super().recommend_route(slots, steps, beam, exclude, revisit, return_step_scores, sync)
 
     def rank_of(self, slots, pois, exclude=None, return_scores=False, return_counts=False, sync=True):
         """Exact 0-based rank of pois[i] (one POI per slot, or (n, len_t <= 8)) among all POIs under the slot's CURRENT state and the
