@@ -82,6 +82,9 @@ extern "C" {
  * plan keys "group_path" / "group_splits" / "group_split_max", timing names "group_topk" / "group_topk_scores" (existing entries unchanged). */
 /* additive to 9: route recommendation - new entry points poi_route_expand and poi_route_merge, options "route_split_max" / "route_grid",
  * plan keys "route_path" / "route_splits", timing names "route_expand" / "route_merge" (existing entries unchanged). */
+/* additive to 9: diversified recommendation - new entry points poi_diverse_pool, poi_diverse_rerank and poi_diverse_topk, options
+ * "diverse_split_max" / "diverse_grid", plan keys "diverse_path" / "diverse_splits" / "diverse_split_max", timing names "diverse_pool" /
+ * "diverse_rerank" (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -168,7 +171,8 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * Additive to 9: "rank_splits" - written by poi_score_rank in the same way.
  * Additive to 9: "geoie_score_span", "geoie_score_splits" - written by poi_geoie_score_all_geo / poi_geoie_score_topk_geo in the same way.
  * Additive to 9: "group_path", "group_splits", "group_split_max" - written by poi_group_topk in the same way.
- * Additive to 9: "route_path", "route_splits" - written by poi_route_expand in the same way. */
+ * Additive to 9: "route_path", "route_splits" - written by poi_route_expand in the same way.
+ * Additive to 9: "diverse_path", "diverse_splits", "diverse_split_max" - written by poi_diverse_pool / poi_diverse_topk in the same way. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -248,7 +252,11 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *   "route_split_max" n (default 8192 = 32 rows for each of 256 CUs): poi_route_expand calls of at most n rows cut the item range of every
  *       32-row tile over several workgroups and finish the rows in a second kernel (0: never); larger calls run one workgroup per tile;
  *   "route_grid" n (default 0 = by the row count and the CUs; at most 64): workgroups per 32-row tile on that split path - bitwise the
- *       same result for every n and on either path. */
+ *       same result for every n and on either path.
+ *   "diverse_split_max" n (default 256): poi_diverse_pool / poi_diverse_topk calls of at most n rows cut the item range of every 32-row tile
+ *       into slices, a workgroup each, and merge the slices' lists (0: never); larger calls run one workgroup per tile;
+ *   "diverse_grid" n (default 0 = by the row count and the CUs; at most 64): slices on that split path - bitwise the same result for
+ *       every n and on either path. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -1015,6 +1023,72 @@ int poi_route_expand(poi_ctx* ctx, const float* users, const float* items, int32
 int poi_route_merge(poi_ctx* ctx, const int32_t* idx, const float* score, const double* lse, const double* total_in, const int32_t* n_live,
                     int32_t n_slot, int32_t n_par, int32_t b,
                     int32_t* parent_out, int32_t* poi_out, double* total_out, double* steplp_out, int32_t* nlive_out, void* stream);
+
+/* ---- diversified recommendation (additive to 9): a fused pool of up to 64 candidates and its MMR re-ranking ------------------------------
+ * Every other ranking entry answers "the K best POIs by score", and the K highest scores of an embedding model are routinely K
+ * near-duplicates: the score is smooth in the item embedding and in the distance to the last check-in.  Re-ranking a candidate pool for
+ * relevance against redundancy (maximal marginal relevance, MMR) is the serving step that fixes it.  Two stages, each an entry of its
+ * own - the second also serves pools that come from elsewhere (poi_topk over explicit score rows) - and poi_diverse_topk, which runs both.
+ *
+ * Stage 1, the pool (poi_diverse_pool).
+ *   C(r)          [0, n_item) minus ex[ex_off[r] .. ex_off[r + 1]): the conventions of poi_score_rank (ascending unique ids; both NULL = none).
+ *   s(r, j)       exactly poi_score_rank's s(r, j): users[r] . items[j] in float32 from the same product routine and k order; with wd
+ *                 non-NULL plus wd * sts[r][bin(last_poi[r], j)] for bin < n_dist (n_dist <= 4096).  A row with last_poi[r] < 0 has no
+ *                 distance term.  wd NULL: the plain score; sts / thr / last_poi are then ignored.
+ *   P(r)          the best m = min(pool, |selectable C(r)|) candidates by descending score, ties by ascending id.  NaN, -inf and +inf
+ *                 scores are never pooled.  (+inf IS selected by poi_score_topk: a deviation, needed because stage 2 normalises the scores.)
+ *   outputs       pool_idx (n, pool) int32 and pool_score (n, pool) float32, 1 <= pool <= 64, filled with -1 / -inf behind the m entries;
+ *                 count_out (n) or NULL = |C(r)|.
+ *   bad rows      as in poi_score_rank: a list that is not ascending or leaves [0, n_item) - the row is all -1 / -inf, count 0, counted
+ *                 once (poi_ctx_take_bad_ids).
+ *   items         float32 or a registered half table; rows >= n_item are never read.  dim: a multiple of 4, <= 256.  n = 0 is a no-op.
+ * The walk of poi_score_rank / poi_group_topk: a workgroup owns a 32-row tile, the item tiles stream past on the f32 matrix pipe, every
+ * wave keeps a sorted 64-entry list per row in LDS, exact to its last entry.  Two launch regimes: calls of at most "diverse_split_max"
+ * rows (default 256) cut the item range into "diverse_grid" slices, a workgroup each, and merge the slices' lists in a second kernel;
+ * larger calls run one workgroup per row tile.  poi_ctx_last_plan: "diverse_path" (0 tile, 1 split), "diverse_splits" (slices, 0 on the
+ * tile path), "diverse_split_max" (the switch point in force).  Timing name: "diverse_pool".
+ *
+ * Stage 2, the re-rank (poi_diverse_rerank).  Per row a pool as above: position i is the i-th best, m = the entries before the first -1
+ * (an id >= n_item among them rejects the row: all -1, counted once).  Everything below is float64.
+ *   rel_i         (s_i - s_{m-1}) / (s_0 - s_{m-1}); every rel_i = 1 when s_0 == s_{m-1} (m == 1 included).
+ *   d(i, l)       12742 * asin(min(1, sqrt(sin^2(dlat * pi/360) + cos(lat_i) cos(lat_l) sin^2(dlon * pi/360)))) km, cos(lat) from cphi.  This
+ *                 is NOT the (1 - cos) / 2 form of cal_dis that the distance bins use: that form loses the relative accuracy of nearby
+ *                 pairs to cancellation - harmless for the bins, whose thresholds are compared with the same term, but the similarity
+ *                 is most sensitive exactly where POIs are metres apart.
+ *   geo(i, l)     exp(-d(i, l) / scale_km), scale_km > 0.
+ *   emb(i, l)     x_i . x_l / (|x_i| |x_l|), 0 if either norm is 0; x = the rows of items (float32 or a registered half table: the table
+ *                 the score was taken with), dim a multiple of 4, <= 256.  One summation order per dim.
+ *   sim           g * geo + (1 - g) * emb, g = geo_weight in [0, 1].  A part with zero weight is not evaluated: coords / cphi may be NULL
+ *                 with g = 0, items with g = 1.
+ *   selection     the first pick is position 0.  After the first pick l_0, pen_i = sim(i, l_0); after each further pick l,
+ *                 pen_i = max(pen_i, sim(i, l)).  Step t >= 1 picks the unselected i with the largest
+ *                 obj_i = trade * rel_i - (1 - trade) * pen_i, ties to the lower position; min(k, m) picks.  trade in [0, 1]; trade = 1
+ *                 returns the pool's first k entries unchanged (and evaluates no similarity).
+ *   outputs       idx_out (n, k) the POI ids, -1 fill, 1 <= k <= 32, k <= pool <= 64; score_out (n, k) or NULL: the ORIGINAL float32
+ *                 scores, -inf fill; pos_out (n, k) or NULL: the pool positions, -1 fill; obj_out (n, k) float64 or NULL: the objective
+ *                 at selection (trade * rel_0 for the first pick), -inf fill.
+ * One wavefront per row, one pool position per lane.  No atomics touch a result: a row's bits do not depend on the grid, on its place
+ * in the call or on the other rows.  Timing name: "diverse_rerank".  n = 0 is a no-op.
+ *
+ * poi_diverse_topk runs both: the arguments are the union of the two, coords / cphi serve the distance term and the geo part alike,
+ * items the score and the embedding part.  pool_idx / pool_score (both or neither) receive the pool; NULL keeps it in a context-owned
+ * workspace.  No host synchronisation between the stages.  Its output equals the two calls' bit for bit. */
+int poi_diverse_pool(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                     const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                     int32_t n_dist, double dd,
+                     const int32_t* ex_off, const int32_t* ex, int32_t pool,
+                     int32_t* pool_idx, float* pool_score, int32_t* count_out, void* stream);
+int poi_diverse_rerank(poi_ctx* ctx, const int32_t* pool_idx, const float* pool_score, int32_t n, int32_t pool,
+                       const float* items, int32_t n_item, int32_t dim, const double* coords, const double* cphi,
+                       int32_t k, double trade, double geo_weight, double scale_km,
+                       int32_t* idx_out, float* score_out, int32_t* pos_out, double* obj_out, void* stream);
+int poi_diverse_topk(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                     const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                     int32_t n_dist, double dd,
+                     const int32_t* ex_off, const int32_t* ex, int32_t pool,
+                     int32_t k, double trade, double geo_weight, double scale_km,
+                     int32_t* idx_out, float* score_out, int32_t* pos_out, double* obj_out,
+                     int32_t* pool_idx, float* pool_score, int32_t* count_out, void* stream);
 
 /* ---- fold-in (additive to 9): a user row of OboBpr / OboVBpr for a check-in history the model never trained on -------------------------------
  * The factorisation family's only user representation is a trained row of ux (and ue).  Fold-in freezes the item side and runs the

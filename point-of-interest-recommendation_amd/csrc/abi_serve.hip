@@ -790,6 +790,148 @@ int poi_route_merge(poi_ctx* c, const int32_t* idx, const float* score, const do
 }
 
 // ---------------------------------------------------------------------------------------------
+// diversified recommendation (diverse.hip)
+static int diverse_pool_check(poi_ctx* c, const char* who, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                              const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr,
+                              const int32_t* last_poi, int32_t n_dist, double dd, const int32_t* ex_off, const int32_t* ex, int32_t pool,
+                              float* bin_scale) {
+  if (!c || !users || !items) return fail(c, POI_EINVAL, "%s: NULL ctx / users / items", who);
+  if (pool <= 0 || pool > DIVERSE_POOL_MAX) return fail(c, POI_ENOTSUP, "%s supports 1 <= pool <= %d (got %d)", who, DIVERSE_POOL_MAX, pool);
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, dim);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "%s: n < 0 or n_item <= 0", who);
+  const bool geo = wd != nullptr;
+  int rc;
+  if ((rc = check_ex_pair(c, who, ex_off, ex))) return rc;
+  if ((rc = check_geo_term(c, who, geo, !geo || (sts && coords && cphi && thr && last_poi), "the distance term needs sts / coords / cphi / thr / last_poi", n_dist, dd, bin_scale))) return rc;
+  if (geo && n_dist > DIVERSE_NDIST_MAX) return fail(c, POI_ENOTSUP, "%s supports n_dist <= %d (got %d)", who, DIVERSE_NDIST_MAX, n_dist);
+  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "%s: users must be float32", who);
+  return POI_OK;
+}
+
+static int diverse_rerank_check(poi_ctx* c, const char* who, int32_t n, int32_t pool, const void* items, int32_t n_item, int32_t dim,
+                                const double* coords, const double* cphi, int32_t k, double trade, double geo_weight, double scale_km,
+                                const int32_t* idx_out) {
+  if (!c || !idx_out) return fail(c, POI_EINVAL, "%s: NULL ctx / idx_out", who);
+  if (k <= 0 || k > DIVERSE_K_MAX) return fail(c, POI_ENOTSUP, "%s supports 1 <= k <= %d (got %d)", who, DIVERSE_K_MAX, k);
+  if (pool < k || pool > DIVERSE_POOL_MAX) return fail(c, POI_ENOTSUP, "%s supports k <= pool <= %d (got pool %d, k %d)", who, DIVERSE_POOL_MAX, pool, k);
+  if (!(trade >= 0.0 && trade <= 1.0)) return fail(c, POI_EINVAL, "%s: trade must lie in [0, 1] (got %g)", who, trade);
+  if (!(geo_weight >= 0.0 && geo_weight <= 1.0)) return fail(c, POI_EINVAL, "%s: geo_weight must lie in [0, 1] (got %g)", who, geo_weight);
+  if (!(scale_km > 0.0)) return fail(c, POI_EINVAL, "%s: scale_km must be positive (got %g)", who, scale_km);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "%s: n < 0 or n_item <= 0", who);
+  if (geo_weight > 0.0 && (!coords || !cphi)) return fail(c, POI_EINVAL, "%s: geo_weight > 0 needs coords / cphi", who);
+  if (geo_weight < 1.0) {
+    if (!items) return fail(c, POI_EINVAL, "%s: geo_weight < 1 needs items", who);
+    if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, dim);
+  }
+  return POI_OK;
+}
+
+// stage 1 into (pool_idx, pool_score), or - both null - into the context's workspace, whose pieces come back through the same pointers
+static int diverse_pool_run(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd,
+                            const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                            int32_t n_dist, float bin_scale, const int32_t* ex_off, const int32_t* ex, int32_t pool, int32_t** pool_idx,
+                            float** pool_score, int32_t* count_out, hipStream_t st) {
+  poi::DiverseArgs A = {};
+  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
+  A.n = n; A.n_item = n_item; A.dim = dim; A.k = pool;
+  if (wd) { A.wd = wd; A.sts = sts; A.coords = coords; A.cphi = cphi; A.thr = thr; A.last_poi = last_poi; A.n_dist = n_dist; A.bin_scale = bin_scale; }
+  A.ex_off = ex_off; A.ex = ex; A.count_out = count_out;
+  int rc;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  // few rows (live traffic): the item range of every 32-row tile is cut into slices so that the call fills the CUs; many rows: one workgroup per tile
+  const int split = n <= c->diverse_split_max;
+  const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
+  A.n_split = 1;
+  if (split) {
+    int s = c->diverse_grid > 0 ? c->diverse_grid : 2 * c->num_cu / n_utile;
+    if (c->diverse_grid <= 0 && s > ntile / 16) s = ntile / 16;      // (at least four item tiles per wave)
+    if (c->diverse_grid <= 0 && s < 2) s = 2;
+    A.n_split = s > DIVERSE_SPLIT_LIMIT ? DIVERSE_SPLIT_LIMIT : s;
+  }
+  const bool own = *pool_idx == nullptr;
+  const size_t lists = split ? (size_t)n * A.n_split : 0;
+  if ((rc = carve(c, c->diverse_ws, st, [&](Carver& W) {
+        if (own) { *pool_idx = (int32_t*)W.bytes(sizeof(int32_t) * (size_t)n * pool); *pool_score = (float*)W.bytes(sizeof(float) * (size_t)n * pool); }
+        if (split) {
+          A.part_s = (float*)W.bytes(sizeof(float) * lists * DIVERSE_POOL_MAX);
+          A.part_i = (int*)W.bytes(sizeof(int) * lists * DIVERSE_POOL_MAX);
+          A.part_cnt = (int*)W.bytes(sizeof(int) * lists);
+        }
+      })))
+    return rc;
+  A.idx_out = *pool_idx; A.score_out = *pool_score;
+  c->plan.valid = 1; c->plan.diverse_path = split; c->plan.diverse_splits = split ? A.n_split : 0; c->plan.diverse_split_max = c->diverse_split_max;
+  HIPCHK(c, poi::launch_diverse_pool(A, st, &c->tm));
+  return POI_OK;
+}
+
+static int diverse_rerank_run(poi_ctx* c, const int32_t* pool_idx, const float* pool_score, int32_t n, int32_t pool, const void* items,
+                              int32_t n_item, int32_t dim, const double* coords, const double* cphi, int32_t k, double trade,
+                              double geo_weight, double scale_km, int32_t* idx_out, float* score_out, int32_t* pos_out, double* obj_out,
+                              hipStream_t st) {
+  poi::RerankArgs R = {};
+  R.pool_idx = pool_idx; R.pool_score = pool_score; R.n = n; R.pool = pool;
+  R.n_item = n_item; R.k = k; R.trade = trade; R.geo_weight = geo_weight; R.scale_km = scale_km;
+  if (geo_weight < 1.0) { R.items = items; R.items_f16 = is_f16(c, items); R.dim = dim; }
+  if (geo_weight > 0.0) { R.coords = coords; R.cphi = cphi; }
+  R.idx_out = idx_out; R.score_out = score_out; R.pos_out = pos_out; R.obj_out = obj_out;
+  if (int rc = bad_counter(c, st, &R.bad)) return rc;
+  HIPCHK(c, poi::launch_diverse_rerank(R, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_diverse_pool(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                     const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                     const int32_t* ex_off, const int32_t* ex, int32_t pool, int32_t* pool_idx, float* pool_score, int32_t* count_out,
+                     void* stream) {
+  float bin_scale;
+  if (int rc = diverse_pool_check(c, "poi_diverse_pool", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, ex_off, ex,
+                                  pool, &bin_scale))
+    return rc;
+  if (!pool_idx || !pool_score) return fail(c, POI_EINVAL, "poi_diverse_pool: NULL pool_idx / pool_score");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  return diverse_pool_run(c, users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, bin_scale, ex_off, ex, pool, &pool_idx,
+                          &pool_score, count_out, st);
+}
+
+int poi_diverse_rerank(poi_ctx* c, const int32_t* pool_idx, const float* pool_score, int32_t n, int32_t pool, const float* items, int32_t n_item,
+                       int32_t dim, const double* coords, const double* cphi, int32_t k, double trade, double geo_weight, double scale_km,
+                       int32_t* idx_out, float* score_out, int32_t* pos_out, double* obj_out, void* stream) {
+  if (int rc = diverse_rerank_check(c, "poi_diverse_rerank", n, pool, items, n_item, dim, coords, cphi, k, trade, geo_weight, scale_km, idx_out))
+    return rc;
+  if (!pool_idx || !pool_score) return fail(c, POI_EINVAL, "poi_diverse_rerank: NULL pool_idx / pool_score");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  return diverse_rerank_run(c, pool_idx, pool_score, n, pool, items, n_item, dim, coords, cphi, k, trade, geo_weight, scale_km, idx_out, score_out,
+                            pos_out, obj_out, st);
+}
+
+int poi_diverse_topk(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                     const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                     const int32_t* ex_off, const int32_t* ex, int32_t pool, int32_t k, double trade, double geo_weight, double scale_km,
+                     int32_t* idx_out, float* score_out, int32_t* pos_out, double* obj_out, int32_t* pool_idx, float* pool_score,
+                     int32_t* count_out, void* stream) {
+  float bin_scale;
+  int rc;
+  if ((rc = diverse_pool_check(c, "poi_diverse_topk", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, ex_off, ex, pool,
+                               &bin_scale)))
+    return rc;
+  if ((rc = diverse_rerank_check(c, "poi_diverse_topk", n, pool, items, n_item, dim, coords, cphi, k, trade, geo_weight, scale_km, idx_out))) return rc;
+  if ((pool_idx == nullptr) != (pool_score == nullptr)) return fail(c, POI_EINVAL, "poi_diverse_topk: pool_idx and pool_score go together");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = diverse_pool_run(c, users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, bin_scale, ex_off, ex, pool, &pool_idx,
+                             &pool_score, count_out, st)))
+    return rc;
+  return diverse_rerank_run(c, pool_idx, pool_score, n, pool, items, n_item, dim, coords, cphi, k, trade, geo_weight, scale_km, idx_out, score_out,
+                            pos_out, obj_out, st);
+}
+
+// ---------------------------------------------------------------------------------------------
 // fold-in of new users (foldin.hip)
 int poi_foldin_bpr(poi_ctx* c, const float* items, int32_t n_item, int32_t dim, const int32_t* off, const int32_t* p, const int32_t* q,
                    int64_t q_epoch_stride, int32_t n, int32_t epochs, float alpha, float lambda, const float* w0, float* w_out,

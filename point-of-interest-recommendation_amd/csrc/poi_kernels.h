@@ -659,6 +659,32 @@ struct RouteMergeArgs {
 hipError_t launch_route_expand(const RouteArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_route_merge(const RouteMergeArgs& A, hipStream_t st, Timing* tm);
 
+// Diversified recommendation (diverse.hip): a pool of the best <= 64 candidates per row, and its MMR re-ranking
+#define DIVERSE_POOL_MAX 64                 // pool length (one wave: lane i owns pool position i)
+#define DIVERSE_K_MAX 32                    // re-ranked list length
+#define DIVERSE_SPLIT_LIMIT 64              // workgroups the item range of a 32-row tile may be split over
+#define DIVERSE_NDIST_MAX 4096              // distance bins whose thresholds fit the pool kernel's LDS beside its lists
+struct DiverseArgs {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim, k;                                      // k: the pool length
+  const float *wd, *sts; const double *coords, *cphi, *thr; const int* last_poi; int n_dist; float bin_scale;      // distance term, or wd null
+  const int *ex_off, *ex;                                     // per-row exclusion lists (ascending ids), or both null
+  int n_split;                                                // item slices, one workgroup each per 32-row tile (1 on the tile path)
+  float* part_s; int *part_i, *part_cnt;                      // split path: (n, n_split, DIVERSE_POOL_MAX) partial lists, (n, n_split) counts
+  int* idx_out; float* score_out; int* count_out;             // (n, k) pool ids / scores; count_out may be null
+  int* bad;                                                   // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+struct RerankArgs {
+  const int* pool_idx; const float* pool_score; int n, pool;  // (n, pool): position i = the i-th best, -1 ends a row's pool
+  const void* items; int items_f16; int n_item, dim;          // the item rows of the embedding part (null with geo_weight 1)
+  const double *coords, *cphi;                                // (n_item, 2) lat, lon; cos(lat) (null with geo_weight 0)
+  int k; double trade, geo_weight, scale_km;
+  int* idx_out; float* score_out; int* pos_out; double* obj_out;      // (n, k); all but idx_out may be null
+  int* bad;                                                   // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+hipError_t launch_diverse_pool(DiverseArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_diverse_rerank(const RerankArgs& A, hipStream_t st, Timing* tm);
+
 // Fold-in of new users for the factorisation family (foldin.hip)
 #define FOLDIN_USERS_PER_WAVE 4             // one 16-lane DPP row per user
 struct FoldinArgs {

@@ -202,3 +202,30 @@ def fun_predict_auc_recall_map_ndcg(p, model, best, epoch, starts_ends_auc, star
                 cur[i] = m[k][key]
                 getattr(best, "best_epoch_" + name)[i] = epoch
     return dict(auc=auc, at=m, ranks=all_ranks)
+
+
+def intra_list_distance_km(idx, coords):
+    """Mean pairwise great-circle distance (km) within each recommendation list: idx (n, k) POI ids with -1 for an empty place (ignored),
+    coords (n_item, 2) lat, lon.  Returns (n) float64, NaN for a list of fewer than two POIs.  The distance is the sin^2 Haversine form
+    of the re-ranking (include/poi_hip.h, poi_diverse_rerank).  With catalogue_coverage, the number that shows what diversification did."""
+    idx = np.asarray(idx.cpu().numpy() if hasattr(idx, "cpu") else idx, np.int64)
+    xy = np.asarray(coords.cpu().numpy() if hasattr(coords, "cpu") else coords, np.float64)
+    idx = idx.reshape(len(idx), -1)
+    ok = idx >= 0
+    g = np.where(ok, idx, 0)
+    lat, lon = xy[g, 0], xy[g, 1]
+    cp = np.cos(lat * (np.pi / 180.0))
+    sa = np.sin((lat[:, :, None] - lat[:, None, :]) * (np.pi / 360.0))
+    sb = np.sin((lon[:, :, None] - lon[:, None, :]) * (np.pi / 360.0))
+    d = 12742.0 * np.arcsin(np.minimum(1.0, np.sqrt(sa * sa + cp[:, :, None] * cp[:, None, :] * (sb * sb))))
+    pair = ok[:, :, None] & ok[:, None, :] & np.triu(np.ones((idx.shape[1], idx.shape[1]), bool), 1)[None]
+    cnt = pair.sum(axis=(1, 2))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(cnt > 0, (d * pair).sum(axis=(1, 2)) / cnt, np.nan)
+
+
+def catalogue_coverage(idx, n_item):
+    """Fraction of the catalogue's n_item POIs that appear on at least one of the lists idx (n, k); -1 places are ignored."""
+    idx = np.asarray(idx.cpu().numpy() if hasattr(idx, "cpu") else idx, np.int64).reshape(-1)
+    idx = idx[(idx >= 0) & (idx < n_item)]
+    return float(np.unique(idx).size) / float(n_item)

@@ -830,6 +830,160 @@ class _Base:
         g_mem = i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=self.device)
         return self._group_launch(users.contiguous(), items, term, i32(off), g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync)
 
+    # ---- diversified recommendation (poi_diverse_topk / poi_diverse_rerank): a pool of the best candidates, re-ranked by MMR --------------
+    def _diverse_items(self):
+        """The POI rows the embedding similarity is taken between: the table the model scores with.  None: the model has no single POI
+        table that means anything (geo_weight < 1 is then refused)."""
+        return self._items() if hasattr(self, "_items") else self.trained_items.t
+
+    @staticmethod
+    def _diverse_args(k, pool, trade, geo_weight, scale_km):
+        k, pool, trade, geo_weight, scale_km = int(k), int(pool), float(trade), float(geo_weight), float(scale_km)
+        if not 1 <= k <= 32:
+            raise ValueError("diversified recommendation supports 1 <= k <= 32 (got %d)" % k)
+        if not k <= pool <= 64:
+            raise ValueError("pool must lie in [k, 64] (got pool %d, k %d)" % (pool, k))
+        if not 0.0 <= trade <= 1.0:
+            raise ValueError("trade must lie in [0, 1] (got %r)" % (trade,))
+        if not 0.0 <= geo_weight <= 1.0:
+            raise ValueError("geo_weight must lie in [0, 1] (got %r)" % (geo_weight,))
+        if not scale_km > 0.0:
+            raise ValueError("scale_km must be positive (got %r)" % (scale_km,))
+        return k, pool, trade, geo_weight, scale_km
+
+    def _diverse_sim(self, geo_weight, items):
+        """(items, kdim, coords, cphi) of the similarity's two parts; a part with zero weight is not handed over."""
+        coords = cphi = None
+        if geo_weight > 0.0:
+            coords, cphi, _ = self._near_geo(False)
+        if geo_weight < 1.0:
+            if items is None:
+                raise ValueError("%s has no single POI table for an embedding similarity: use geo_weight=1" % type(self).__name__)
+            items = items.contiguous()
+            if items.shape[1] % 4 or items.shape[1] > 256:
+                raise _lib.PoiError("the embedding similarity supports item rows of a multiple of 4 up to 256 columns (got %d)" % items.shape[1])
+            return items, items.shape[1], coords, cphi
+        return None, 0, coords, cphi
+
+    def _diverse_out(self, idx, sc, obj, pool, cnt, return_scores, return_objective, return_pool, return_counts, sync):
+        if sync:
+            bad = self.ctx.take_bad_ids(self._stream().value)
+            if bad:
+                raise IndexError("%d row(s) with a malformed exclusion list or a pool id outside [0, %d): their lists are all -1" % (bad, self.n_item))
+        out = (idx,) + ((sc,) if return_scores else ()) + ((obj,) if return_objective else ()) + ((pool,) if return_pool else ()) \
+            + ((cnt,) if return_counts else ())
+        return out if len(out) > 1 else idx
+
+    def _diverse_buffers(self, n, k, pool, return_scores, return_objective, return_pool, return_counts):
+        dev = self.device
+        idx = torch.empty((n, k), dtype=torch.int32, device=dev)
+        sc = torch.empty((n, k), dtype=torch.float32, device=dev) if return_scores else None
+        obj = torch.empty((n, k), dtype=torch.float64, device=dev) if return_objective else None
+        pl = (torch.empty((n, pool), dtype=torch.int32, device=dev), torch.empty((n, pool), dtype=torch.float32, device=dev)) if return_pool else (None, None)
+        cnt = torch.empty(n, dtype=torch.int32, device=dev) if return_counts else None
+        return idx, sc, obj, pl, cnt
+
+    def _diverse_launch(self, users, items, kdim, term, ex, k, pool, trade, geo_weight, scale_km, return_scores, return_objective, return_pool,
+                        return_counts, sync):
+        """One poi_diverse_topk call.  term: (wd, sts rows, last POI rows) or None."""
+        n = users.shape[0]
+        idx, sc, obj, pl, cnt = self._diverse_buffers(n, k, pool, return_scores, return_objective, return_pool, return_counts)
+        wd = sts = lp = coords = cphi = thr = None
+        n_dist, dd_m = 0, 0.0
+        if term is not None:
+            wd, sts, lp = term
+            coords, cphi, thr, n_dist, dd_m = self.coords, self._cphi, self._binthr, self.n_dist, self.dd * 1000.0
+        if geo_weight > 0.0:
+            coords, cphi, _ = self._near_geo(False)
+        self.ctx.check(self.lib.poi_diverse_topk(self.ctx.handle, _ptr(users), _ptr(items), n, self.n_item, kdim, _ptr(wd), _ptr(sts), _ptr(coords),
+                                                 _ptr(cphi), _ptr(thr), _ptr(lp), int(n_dist), float(dd_m), _ptr(ex[0]), _ptr(ex[1]), pool, k, trade,
+                                                 geo_weight, scale_km, _ptr(idx), _ptr(sc), None, _ptr(obj), _ptr(pl[0]), _ptr(pl[1]), _ptr(cnt),
+                                                 self._stream()))
+        return self._diverse_out(idx, sc, obj, pl, cnt, return_scores, return_objective, return_pool, return_counts, sync)
+
+    def _diverse_host_exclusion(self, ex, n):
+        """The explicit-score path masks score rows with the lists: device lists are read back and checked like host lists."""
+        if ex[0] is None:
+            return ex
+        from .data import check_exclusion_csr
+        eo, ei = ex[0].cpu().numpy().astype(np.int64), ex[1].cpu().numpy()
+        if len(eo) and 0 <= eo[0] <= eo[-1] <= len(ei):      # the rows' window of a longer id list (exclude="train" over a user range)
+            eo, ei = eo - eo[0], ei[int(eo[0]):int(eo[-1])]
+        eo, ei = check_exclusion_csr(eo, ei, n, self.n_item)
+        return torch.as_tensor(eo).to(self.device), torch.as_tensor(ei).to(self.device)
+
+    def _diverse_from_scores(self, score_rows, n, ex, sim, k, pool, trade, geo_weight, scale_km, return_scores, return_objective, return_pool,
+                             return_counts, sync):
+        """Explicit score rows, a bounded number of rows at a time: the exclusions masked to -inf, the pool from poi_topk, then
+        poi_diverse_rerank.  score_rows(o, c) -> (c, n_item) float32 scores of rows o .. o + c - 1."""
+        items, kdim, coords, cphi = sim
+        N = self.n_item
+        idx, sc, obj, pl, cnt = self._diverse_buffers(n, k, pool, return_scores, return_objective, True, return_counts)
+        ex = self._diverse_host_exclusion(ex, n)
+        kk = min(pool, N)
+        step = self._rank_chunk(max(n, 1))
+        ninf = float("-inf")
+        at = lambda t, o, w, b=4: ctypes.c_void_p(t.data_ptr() + b * o * w) if t is not None else None
+        for o in range(0, n, step):
+            c = min(step, n - o)
+            full = score_rows(o, c)
+            full = torch.where(torch.isfinite(full), full, torch.full_like(full, ninf))      # NaN and +-inf are never pooled
+            if ex[0] is not None:
+                eo = ex[0][o:o + c + 1].long()
+                ln = eo[1:] - eo[:-1]
+                full[torch.repeat_interleave(torch.arange(c, device=self.device), ln), ex[1][int(eo[0]):int(eo[-1])].long()] = ninf
+                if cnt is not None:
+                    cnt[o:o + c] = (N - ln).int()
+            elif cnt is not None:
+                cnt[o:o + c] = N
+            ti = torch.full((c, kk), -1, dtype=torch.int32, device=self.device)
+            ts = torch.full((c, kk), ninf, dtype=torch.float32, device=self.device)
+            self.ctx.check(self.lib.poi_topk(self.ctx.handle, _ptr(full.contiguous()), c, N, kk, _ptr(ti), _ptr(ts), self._stream()))
+            dead = ~torch.isfinite(ts)
+            ti[dead] = -1; ts[dead] = ninf
+            pl[0][o:o + c] = -1; pl[1][o:o + c] = ninf
+            pl[0][o:o + c, :kk] = ti; pl[1][o:o + c, :kk] = ts
+            self.ctx.check(self.lib.poi_diverse_rerank(self.ctx.handle, at(pl[0], o, pool), at(pl[1], o, pool), c, pool, _ptr(items), N, kdim, _ptr(coords),
+                                                       _ptr(cphi), k, trade, geo_weight, scale_km, at(idx, o, k), at(sc, o, k), None, at(obj, o, k, 8),
+                                                       self._stream()))
+        return self._diverse_out(idx, sc, obj, pl, cnt, return_scores, return_objective, return_pool, return_counts, sync)
+
+    def compute_sub_topk_diverse(self, start_end, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
+                                 return_objective=False, return_pool=False, return_counts=False, sync=True):
+        """DIVERSIFIED top-K (include/poi_hip.h, poi_diverse_topk): the `pool` best candidates of every row under the model's own score
+        (k <= pool <= 64; exclude as compute_sub_topk_near: None, "train", "last" or CSR lists (off, ids)), re-ranked greedily for
+        relevance against redundancy (maximal marginal relevance): the first pick is the best candidate, every further pick maximises
+        trade * rel - (1 - trade) * (the largest similarity to a POI already picked), rel the pool's scores scaled to [0, 1].  The
+        similarity is geo_weight * exp(-distance / scale_km) + (1 - geo_weight) * (cosine of the two item rows); a part with zero weight
+        is not evaluated (geo_weight > 0 needs POI coordinates: set_coords).  trade = 1 is the plain top-K.  Returns (n, k) int32 ids
+        (k <= 32), -1 where fewer candidates exist; with return_scores the picks' ORIGINAL scores, with return_objective the float64
+        objective at selection, with return_pool the pair (pool ids, pool scores), with return_counts the candidate count of every row.
+        No (n, n_item) matrix is built for the models that score by users . items; CA-RNN, PRME, POI2Vec and GeoIE under rule="geo" go
+        through their own score rows, a bounded number at a time, poi_topk and poi_diverse_rerank.  Host arguments are checked before
+        the launch (ValueError / IndexError)."""
+        k, pool, trade, geo_weight, scale_km = self._diverse_args(k, pool, trade, geo_weight, scale_km)
+        sim = self._diverse_sim(geo_weight, self._diverse_items() if geo_weight < 1.0 else None)
+        flags = (return_scores, return_objective, return_pool, return_counts, sync)
+        if not self._rank_fused:
+            a = start_end if isinstance(start_end, torch.Tensor) else np.atleast_1d(np.asarray(start_end))
+            n = len(a)
+            ids, lo = self._ids(a)
+            anc = self._rows(self._last_train_poi(), ids, lo) if exclude == "last" else None
+            ex = self._near_exclusion(exclude, n, anc, ids, lo)
+
+            def score_rows(o, c):
+                full, per = self._rank_score_rows(a[o:o + c])
+                return full.view(c, per, self.n_item)[:, 0] if per > 1 else full      # (user, position) rows: the user's next POI is position 0
+            return self._diverse_from_scores(score_rows, n, ex, sim, k, pool, trade, geo_weight, scale_km, *flags)
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        anc = self._rows(self._last_train_poi(), ids, lo) if exclude == "last" else None
+        ex = self._near_exclusion(exclude, n, anc, ids, lo)
+        items = self._items() if hasattr(self, "_items") else self.trained_items.t
+        if n == 0:
+            return self._diverse_out(*self._diverse_buffers(0, k, pool, True, True, True, True), *flags[:4], False)
+        return self._diverse_launch(users.contiguous(), items, self.kdim, self._rank_term(ids, lo), ex, k, pool, trade, geo_weight, scale_km, *flags)
+
 
 # =================================================================================================
 class GruBasic(_Base):
@@ -1770,6 +1924,29 @@ class Session:
         g_mem = self._i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=m.device)
         return m._group_launch(users, m.trained_items.t, term, self._i32(off), g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync)
 
+    def recommend_diverse(self, slots, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
+                          return_objective=False, return_pool=False, return_counts=False, sync=True):
+        """model.compute_sub_topk_diverse over the slots' CURRENT states (h, sts, last_poi, as `rank_of` assembles them): the `pool`
+        best POIs of every slot, re-ranked for relevance against redundancy.  exclude: None, "last" or CSR lists (off, ids).  A slot
+        without a check-in has no distance term."""
+        m = self.m
+        k, pool, trade, geo_weight, scale_km = m._diverse_args(k, pool, trade, geo_weight, scale_km)
+        items, kdim, _, _ = m._diverse_sim(geo_weight, m.trained_items.t if geo_weight < 1.0 else None)
+        ids = self._slot_tensor(slots)
+        n = ids.numel()
+        flags = (return_scores, return_objective, return_pool, return_counts)
+        if n == 0:
+            return m._diverse_out(*m._diverse_buffers(0, k, pool, True, True, True, True), *flags, False)
+        users = self.h.index_select(0, ids).float().contiguous()
+        lpr = self.last_poi.index_select(0, ids).contiguous()
+        term = None
+        if self.spatial:
+            st = (self.sts.index_select(0, ids) * (lpr >= 0).float()[:, None]).contiguous()
+            st[:, m.n_dist] = 0.0
+            term = (m.wd.t, st, lpr)
+        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
+        return m._diverse_launch(users, m.trained_items.t, m.kdim, term, ex, k, pool, trade, geo_weight, scale_km, *flags, sync)
+
     # ---- routes ---------------------------------------------------------------------------------
     ROUTE_BEAM_MAX, ROUTE_STEPS_MAX = 8, 16
 
@@ -2009,6 +2186,31 @@ class CellSession(Session):
         if sc is not None:
             sc = torch.where(has[:, None], sc, torch.full_like(sc, float("nan")))
         return (idx, sc) if return_scores else idx
+
+    def recommend_diverse(self, slots, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
+                          return_objective=False, return_pool=False, return_counts=False, sync=True):
+        """Lstm / Rnn: `Session.recommend_diverse`'s plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi, the
+        exclusions masked, the pool from poi_topk, then poi_diverse_rerank; a slot without a check-in gives -1 ids (count 0)."""
+        if not self.carnn:
+            return super().recommend_diverse(slots, k, pool, trade, geo_weight, scale_km, exclude, return_scores, return_objective, return_pool,
+                                             return_counts, sync)
+        m = self.m
+        k, pool, trade, geo_weight, scale_km = m._diverse_args(k, pool, trade, geo_weight, scale_km)
+        sim = m._diverse_sim(geo_weight, m.trained_items.t if geo_weight < 1.0 else None)
+        n, users, lp, has = self._carnn_rows(slots)
+        lpr = torch.where(has, lp, torch.full_like(lp, -1))
+        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
+
+        def score_rows(o, c):
+            full = self._carnn_scores(users, lp, o, c)
+            return torch.where(has[o:o + c, None], full, torch.full_like(full, float("-inf")))      # no check-in: nothing is pooled
+        out = m._diverse_from_scores(score_rows, n, ex, sim, k, pool, trade, geo_weight, scale_km, return_scores, return_objective, return_pool,
+                                     True, sync)
+        out = list(out) if isinstance(out, tuple) else [out]
+        out[-1] = torch.where(has, out[-1], torch.zeros_like(out[-1]))
+        if not return_counts:
+            out.pop()
+        return tuple(out) if len(out) > 1 else out[0]
 
     def recommend_group(self, slot_groups, k, agg="mean", exclude=None, return_scores=False, return_counts=False, sync=True):
         """Lstm / Rnn: `Session.recommend_group`'s plain rule.  CA-RNN ranks by a rule of its own and is refused."""
@@ -2880,6 +3082,9 @@ class OboPrme(_SeqFoldin, _Base):
 
     _rank_fused = False
 
+    def _diverse_items(self):
+        return None                               # two POI tables (preference and sequential space): no single row stands for a POI
+
     def _rank_score_rows(self, a):
         """The rows compute_sub_topk ranks: every user from its row 0 (query = the last train POI)."""
         ids, lo = self._ids(a)
@@ -3575,6 +3780,9 @@ class OboPoi2vec(_Base):
         return self._score_call(start_end, k=int(k), return_scores=return_scores, **kw)
 
     _rank_fused = False
+
+    def _diverse_items(self):
+        return self._trained["wl"]
 
     def _rank_score_rows(self, a):
         """The rows compute_sub_topk ranks: (user, position) for position < the longest test sequence of the users."""

@@ -1,0 +1,176 @@
+"""CPU tests of the diversified recommendation's host side: the oracle (tests/diverse_oracle.py) against an independent brute force,
+its two fixed points, the declarations, the host argument checks, and the conditions on the fixtures of tests/test_gpu_diverse.py.
+
+The conditions, with the oracle's own pools: every non-planted row of every fixture has min_gap >= 1e-9 (the smallest difference
+between the best and the second-best objective of a step), and at least 90 % of the rows have clear top-(pool + 1) score gaps by
+near_oracle.qualifying.  Why 1e-9: the GPU and numpy differ by a few ulp in sin / asin / sqrt / exp and in the order of a float64
+dot product - an objective error of order 1e-14; 1e-9 is five orders above that.  Checked on the CPU only (random tables, 3000 POIs,
+70 rows, dims 20 .. 256, pools 20 / 33 / 64): the reference alone stays inside both conditions; if a seed does not, pick another.
+No GPU."""
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+from poi_amd import _lib, build, evaluate, models as M
+from tests import diverse_cases as DC
+from tests import diverse_oracle as DO
+from tests import near_oracle as NO
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def brute_dist(xy, a, b):
+    sa = math.sin((xy[a][0] - xy[b][0]) * math.pi / 360.0)
+    sb = math.sin((xy[a][1] - xy[b][1]) * math.pi / 360.0)
+    q = sa * sa + math.cos(xy[a][0] * math.pi / 180.0) * math.cos(xy[b][0] * math.pi / 180.0) * sb * sb
+    return 12742.0 * math.asin(min(1.0, math.sqrt(q)))
+
+
+def brute_rerank(ids, s, items, xy, k, trade, g, scale):
+    """One row, Python loops, every max-similarity recomputed from scratch against the whole selected set."""
+    m = len(ids)
+
+    def sim(i, l):
+        v = 0.0
+        if g > 0.0:
+            v += g * math.exp(-brute_dist(xy, ids[i], ids[l]) / scale)
+        if g < 1.0:
+            xi, xl = items[ids[i]], items[ids[l]]
+            ni, nl = math.sqrt(sum(float(a) * float(a) for a in xi)), math.sqrt(sum(float(a) * float(a) for a in xl))
+            v += (1.0 - g) * (sum(float(a) * float(b) for a, b in zip(xi, xl)) / (ni * nl) if ni > 0 and nl > 0 else 0.0)
+        return v
+    rel = [1.0 if s[0] == s[m - 1] else (s[i] - s[m - 1]) / (s[0] - s[m - 1]) for i in range(m)]
+    picked, objs = [0], [trade * rel[0]]
+    while len(picked) < min(k, m):
+        best, best_o = None, None
+        for i in range(m):
+            if i in picked:
+                continue
+            o = trade * rel[i] - (1.0 - trade) * max(sim(i, l) for l in picked)
+            if best is None or o > best_o:
+                best, best_o = i, o
+        picked.append(best); objs.append(best_o)
+    return picked, objs
+
+
+def test_oracle_matches_a_brute_force():
+    rng = np.random.default_rng(3)
+    N, dim = 40, 5
+    items = rng.normal(0, 0.3, (N + 1, dim)); items[7] = 0.0                 # (a zero row: its cosine is 0)
+    xy = np.stack((30.0 + rng.uniform(0, 0.1, N), 120.0 + rng.uniform(0, 0.1, N)), axis=1)
+    sc = rng.normal(0, 1, (6, N)); sc[2, 5] = np.nan; sc[2, 6] = np.inf; sc[2, 8] = -np.inf
+    mask = np.ones((6, N), bool); mask[1, :30] = False; mask[4] = False; mask[5, 1:] = False
+    pi, ps, cnt = DO.pool(sc, mask, 12)
+    assert cnt.tolist() == [N, 10, N, N, 0, 1] and DO.pool_size(pi).tolist() == [12, 10, 12, 12, 0, 1]
+    assert not {5, 6, 8} & set(pi[2].tolist()) and np.all(pi[4] == -1) and np.all(np.isneginf(ps[4])) and 7 in set(pi.reshape(-1).tolist())
+    for r in range(6):
+        cand = [j for j in range(N) if mask[r, j] and np.isfinite(sc[r, j])]
+        want = sorted(cand, key=lambda j: (-sc[r, j], j))[:12]
+        assert pi[r, :len(want)].tolist() == want
+    for trade, g in ((0.7, 1.0), (0.3, 0.5), (0.5, 0.0), (0.0, 1.0), (1.0, 0.5)):
+        idx, pos, obj, gap = DO.rerank(pi, ps, items, xy, 8, trade, g, 1.5)
+        for r in range(6):
+            m = int(DO.pool_size(pi)[r])
+            if m == 0:
+                assert np.all(idx[r] == -1) and np.all(pos[r] == -1) and np.all(np.isneginf(obj[r]))
+                continue
+            picked, objs = brute_rerank(pi[r, :m].tolist(), ps[r, :m].tolist(), items, xy, 8, trade, g, 1.5)
+            t = len(picked)
+            assert pos[r, :t].tolist() == picked and idx[r, :t].tolist() == [int(pi[r, p]) for p in picked] and np.all(idx[r, t:] == -1)
+            assert np.allclose(obj[r, :t], objs, rtol=0, atol=1e-13) and np.all(np.isneginf(obj[r, t:]))
+    a, b = np.array([0, 3, 9]), np.array([1, 3, 20])
+    assert np.allclose(DO.dist_km(xy, a, b), [brute_dist(xy, i, j) for i, j in zip(a, b)], rtol=1e-13, atol=0) and DO.dist_km(xy, 3, 3) == 0.0
+
+
+def test_trade_one_is_the_identity_and_trade_zero_takes_the_farthest():
+    P = DC.explicit_pools(20)
+    for g in (0.0, 0.5, 1.0):
+        idx, pos, obj, gap = DO.rerank(P["idx"], P["score"], P["items"], P["coords"], 20, 1.0, g, DC.SCALE_KM)
+        for r, m in enumerate(P["m"]):
+            t = min(20, m)
+            assert np.array_equal(idx[r, :t], P["idx"][r, :t]) and np.array_equal(pos[r, :t], np.arange(t)) and np.all(idx[r, t:] == -1)
+    idx, pos, obj, gap = DO.rerank(P["idx"], P["score"], P["items"], P["coords"], 2, 0.0, 1.0, DC.SCALE_KM)
+    for r, m in enumerate(P["m"]):
+        if m >= 2:
+            d = DO.dist_km(P["coords"], P["idx"][r, :m], P["idx"][r, 0])
+            assert pos[r, 1] == int(np.argmax(d)) and obj[r, 1] == -np.exp(-d.max() / DC.SCALE_KM)
+
+
+def test_declarations():
+    header = open(os.path.join(ROOT, "include", "poi_hip.h")).read()
+    for name in ("poi_diverse_pool", "poi_diverse_rerank", "poi_diverse_topk"):
+        assert re.search(r"\bint %s\(poi_ctx\* ctx" % name, header), name
+    for word in ("diverse_split_max", "diverse_grid", "diverse_path", "diverse_splits", "\"diverse_pool\"", "\"diverse_rerank\"", "additive to 9: diversified"):
+        assert word in header, word
+    assert "(1 - cos) / 2" in header[header.index("diversified recommendation (additive to 9)"):]
+    assert "diverse.hip" in build.SOURCES
+    assert {"diverse_path", "diverse_splits", "diverse_split_max"} <= set(_lib.PLAN_KEYS)
+    src = open(os.path.join(ROOT, "point-of-interest-recommendation_amd", "_lib.py")).read()
+    for name, n_args in (("poi_diverse_pool", 21), ("poi_diverse_rerank", 19), ("poi_diverse_topk", 29)):
+        sig = re.search(r'"%s": \(c_int, \[(.*?)\]\)' % name, src, re.S).group(1)
+        assert len([a for a in sig.replace("\n", " ").split(",") if a.strip()]) == n_args, name
+        proto = re.search(r"\bint %s\((.*?)\);" % name, header, re.S).group(1)
+        assert len(proto.split(",")) == n_args, name
+    for fn in ("compute_sub_topk_diverse", "_diverse_items"):
+        assert hasattr(M._Base, fn)
+    assert hasattr(M.Session, "recommend_diverse") and M.CellSession.recommend_diverse is not M.Session.recommend_diverse
+    assert M.OboPrme._diverse_items(None) is None
+
+
+def test_host_argument_checks():
+    args = M._Base._diverse_args
+    assert args(20, 64, 0.7, 1.0, 1.0) == (20, 64, 0.7, 1.0, 1.0) and args(32, 32, 0, 0, 0.5) == (32, 32, 0.0, 0.0, 0.5)
+    for bad in ((0, 64, 0.7, 1.0, 1.0), (33, 64, 0.7, 1.0, 1.0), (20, 19, 0.7, 1.0, 1.0), (20, 65, 0.7, 1.0, 1.0), (20, 64, -0.1, 1.0, 1.0),
+                (20, 64, 1.1, 1.0, 1.0), (20, 64, float("nan"), 1.0, 1.0), (20, 64, 0.7, -0.5, 1.0), (20, 64, 0.7, 1.5, 1.0), (20, 64, 0.7, 1.0, 0.0),
+                (20, 64, 0.7, 1.0, -1.0), (20, 64, 0.7, 1.0, float("nan"))):
+        with pytest.raises(ValueError):
+            args(*bad)
+    from poi_amd import data as D
+    with pytest.raises(IndexError):
+        D.check_exclusion_csr([0, 1], [DC.N_ITEM], 1, DC.N_ITEM)
+    with pytest.raises(ValueError):
+        D.check_exclusion_csr([0, 2], [4, 4], 1, DC.N_ITEM)
+
+
+def test_evaluate_helpers():
+    xy = np.array([[30.0, 120.0], [30.0, 120.01], [30.01, 120.0], [30.5, 120.5]])
+    idx = np.array([[0, 1, 2], [0, -1, 1], [3, -1, -1], [-1, -1, -1]])
+    d = evaluate.intra_list_distance_km(idx, xy)
+    pair = lambda a, b: float(DO.dist_km(xy, a, b))
+    assert np.isclose(d[0], (pair(0, 1) + pair(0, 2) + pair(1, 2)) / 3, rtol=1e-12) and np.isclose(d[1], pair(0, 1), rtol=1e-12)
+    assert np.isnan(d[2]) and np.isnan(d[3])
+    assert evaluate.catalogue_coverage(idx, 4) == 1.0 and evaluate.catalogue_coverage(idx[1:2], 4) == 0.5 and evaluate.catalogue_coverage(idx[3:], 4) == 0.0
+
+
+# ---- the conditions on the fixtures --------------------------------------------------------------------------------------------------
+def test_fixtures_have_clear_gaps_under_the_oracle_alone():
+    for name, sc, ex, items, coords, planted in DC.rank_fixtures():
+        if planted:
+            continue                                 # (the twins tie by construction: tests/test_gpu_diverse.py holds them to the tie rule)
+        mask = DC.mask_of(len(sc), sc.shape[1], ex)
+        for pool in DC.POOLS:
+            ok = NO.qualifying(sc, mask, pool)
+            assert ok.mean() >= 0.9, "%s pool %d: only %.1f %% of the rows have clear top-(pool + 1) gaps: pick another seed" % (name, pool, 100 * ok.mean())
+    worst = np.inf
+    for (name, sc, ex, items, coords, planted), pool, trade, g in DC.e2e_runs():
+        if planted:
+            continue
+        gap = DC.oracle_run(sc, ex, items, coords, DC.K, pool, trade, g)[-1]
+        worst = min(worst, gap.min())
+        assert gap.min() >= DC.GAP, "%s pool %d trade %g geo %g: min_gap %.3g: pick another seed" % (name, pool, trade, g, gap.min())
+    print("smallest min_gap over the end-to-end fixtures: %.3g" % worst)
+
+
+@pytest.mark.parametrize("dim", [20, 256])
+def test_explicit_pools_have_clear_gaps(dim):
+    P = DC.explicit_pools(dim)
+    assert sorted(set(P["m"].tolist())) == sorted(DC.POOL_M)
+    worst = np.inf
+    for k, trade, g in DC.RERANK_GRID:
+        gap = DO.rerank(P["idx"], P["score"], P["items"], P["coords"], k, trade, g, DC.SCALE_KM)[3]
+        worst = min(worst, gap.min())
+        assert gap.min() >= DC.GAP, (k, trade, g, gap.min())
+    print("dim %d: smallest min_gap over the explicit pools %.3g" % (dim, worst))
