@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/poi_hip.h"
 #include "poi_kernels.h"
+#include "split_plan.h"
 
 #include <string>
 #include <utility>
@@ -191,6 +192,14 @@ int carve_lists(poi_ctx* c, DevBuf& b, hipStream_t st, Args& A, size_t lists, in
     A.part_i = (int*)W.bytes(sizeof(int) * lists * k_max);
     A.part_cnt = (int*)W.bytes(sizeof(int) * lists);
   });
+}
+
+// The operand block tile_operands() (abi_serve.hip) has filled, into a family's argument struct: the same members under the same names.
+template <class Args>
+void put_operands(Args& A, const poi::TileOperands& T) {
+  A.users = T.users; A.items = T.items; A.items_f16 = T.items_f16; A.n = T.n; A.n_item = T.n_item; A.dim = T.dim;
+  A.wd = T.wd; A.sts = T.sts; A.coords = T.coords; A.cphi = T.cphi; A.thr = T.thr; A.last_poi = T.last_poi; A.n_dist = T.n_dist; A.bin_scale = T.bin_scale;
+  A.ex_off = T.ex_off; A.ex = T.ex; A.bad = T.bad;
 }
 
 // Argument checks shared by the entry points (defined in abi.hip).  Each returns POI_OK or the code it has recorded with fail().

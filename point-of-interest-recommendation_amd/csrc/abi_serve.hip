@@ -1,6 +1,7 @@
 // C-ABI of libpoi_hip.so (see include/poi_hip.h): everything that answers a query - scoring, top-K, ranks, sessions, fold-ins, metrics, samplers, deltas.
 #include "abi_internal.h"
 
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -568,17 +569,37 @@ int poi_score_topk_near(poi_ctx* c, const float* users, const float* items, int3
   A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
   if ((rc = bad_counter(c, st, &A.bad))) return rc;
   // few rows (live traffic): every row's band is cut into slices so that the call fills the CUs; many rows: one workgroup per row
-  const int split = n <= c->near_split_max;
-  A.n_split = 1;
-  if (split) {
-    int s = c->near_grid > 0 ? c->near_grid : 4 * c->num_cu / n;
-    if (c->near_grid <= 0 && s < 2) s = 2;
-    A.n_split = s > NEAR_SPLIT_LIMIT ? NEAR_SPLIT_LIMIT : s;
-    if ((rc = carve_lists(c, c->near_ws, st, A, (size_t)n * A.n_split, NEAR_K_MAX))) return rc;
-  }
-  c->plan.valid = 1; c->plan.near_path = split; c->plan.near_splits = split ? A.n_split : 0; c->plan.near_split_max = c->near_split_max;
+  const SplitPlan sp = plan_split(n, n, c->near_split_max, c->near_grid, 4, c->num_cu, INT_MAX, 2, NEAR_SPLIT_LIMIT);
+  A.n_split = sp.n_split;
+  if (sp.split && (rc = carve_lists(c, c->near_ws, st, A, (size_t)n * A.n_split, NEAR_K_MAX))) return rc;
+  c->plan.valid = 1; c->plan.near_path = sp.split; c->plan.near_splits = sp.split ? A.n_split : 0; c->plan.near_split_max = c->near_split_max;
   HIPCHK(c, poi::launch_near(A, st, &c->tm));
   return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The operand block of the families that walk tiles of users . items (poi::TileOperands: rank.hip, group.hip, route.hip, diverse.hip):
+// the checks each of them makes on the users / items / distance-term arguments and the exclusion pair, then the block itself, the
+// half-table flag, the metres-per-bin factor and the context's counter of rejected rows included.  Selects the context's device.
+static int tile_operands(poi_ctx* c, const char* who, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd,
+                         const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist,
+                         double dd, const int32_t* ex_off, const int32_t* ex, hipStream_t st, poi::TileOperands* out) {
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, dim);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "%s: n < 0 or n_item <= 0", who);
+  const bool geo = wd != nullptr;
+  float bin_scale;
+  int rc;
+  if ((rc = check_ex_pair(c, who, ex_off, ex))) return rc;
+  if ((rc = check_geo_term(c, who, geo, !geo || (sts && coords && cphi && thr && last_poi), "the distance term needs sts / coords / cphi / thr / last_poi", n_dist, dd, &bin_scale))) return rc;
+  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "%s: users must be float32", who);
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::TileOperands& T = *out;
+  T = poi::TileOperands{};
+  T.users = users; T.items = items; T.items_f16 = is_f16(c, items);
+  T.n = n; T.n_item = n_item; T.dim = dim;
+  if (geo) { T.wd = wd; T.sts = sts; T.coords = coords; T.cphi = cphi; T.thr = thr; T.last_poi = last_poi; T.n_dist = n_dist; T.bin_scale = bin_scale; }
+  T.ex_off = ex_off; T.ex = ex;
+  return bad_counter(c, st, &T.bad);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -599,21 +620,14 @@ int poi_score_rank(poi_ctx* c, const float* users, const float* items, int32_t n
   if (!c || !users || !items) return fail(c, POI_EINVAL, "poi_score_rank: NULL ctx / users / items");
   int rc;
   if ((rc = rank_check(c, "poi_score_rank", n, n_item, tgt, tmask, len_t, ex_off, ex, rank_out))) return rc;
-  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_score_rank: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
-  const bool geo = wd != nullptr;
-  float bin_scale;
-  if ((rc = check_geo_term(c, "poi_score_rank", geo, !geo || (sts && coords && cphi && thr && last_poi), "the distance term needs sts / coords / cphi / thr / last_poi", n_dist, dd, &bin_scale))) return rc;
-  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "poi_score_rank: users must be float32");
-  if (n == 0) return POI_OK;
   hipStream_t st = (hipStream_t)stream;
-  HIPCHK(c, hipSetDevice(c->device));
+  poi::TileOperands T;
+  if ((rc = tile_operands(c, "poi_score_rank", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, ex_off, ex, st, &T))) return rc;
+  if (n == 0) return POI_OK;
   poi::RankArgs A = {};
-  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
-  A.n = n; A.n_item = n_item; A.dim = dim; A.len_t = len_t;
-  if (geo) { A.wd = wd; A.sts = sts; A.coords = coords; A.cphi = cphi; A.thr = thr; A.last_poi = last_poi; A.n_dist = n_dist; A.bin_scale = bin_scale; }
-  A.tgt = tgt; A.tmask = tmask; A.ex_off = ex_off; A.ex = ex;
+  put_operands(A, T);
+  A.len_t = len_t; A.tgt = tgt; A.tmask = tmask;
   A.rank_out = rank_out; A.score_out = score_out; A.count_out = count_out;
-  if ((rc = bad_counter(c, st, &A.bad))) return rc;
   const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
   if ((rc = ensure(c, c->rank_ws, sizeof(poi::RankTgt) * (size_t)n_utile * 32 * RANK_LT_MAX, st))) return rc;
   A.tl = (poi::RankTgt*)c->rank_ws.p;
@@ -665,33 +679,21 @@ int poi_group_topk(poi_ctx* c, const float* users, const float* items, int32_t n
   if (!c || !items || (!users && n > 0)) return fail(c, POI_EINVAL, "poi_group_topk: NULL ctx / users / items");
   int rc;
   if ((rc = group_check_args(c, "poi_group_topk", n, n_item, g_off, g_mem, n_grp, agg, ex_off, ex, k, idx_out))) return rc;
-  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_group_topk: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
-  const bool geo = wd != nullptr;
-  float bin_scale;
-  if ((rc = check_geo_term(c, "poi_group_topk", geo, !geo || (sts && coords && cphi && thr && last_poi), "the distance term needs sts / coords / cphi / thr / last_poi", n_dist, dd, &bin_scale))) return rc;
-  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "poi_group_topk: users must be float32");
-  if (n_grp == 0) return POI_OK;
   hipStream_t st = (hipStream_t)stream;
-  HIPCHK(c, hipSetDevice(c->device));
+  poi::TileOperands T;
+  if ((rc = tile_operands(c, "poi_group_topk", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, ex_off, ex, st, &T))) return rc;
+  if (n_grp == 0) return POI_OK;
   poi::GroupArgs A = {};
-  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
-  A.n = n; A.n_item = n_item; A.dim = dim; A.k = k; A.n_grp = n_grp; A.agg = agg;
-  if (geo) { A.wd = wd; A.sts = sts; A.coords = coords; A.cphi = cphi; A.thr = thr; A.last_poi = last_poi; A.n_dist = n_dist; A.bin_scale = bin_scale; }
-  A.g_off = g_off; A.g_mem = g_mem; A.ex_off = ex_off; A.ex = ex;
+  put_operands(A, T);
+  A.k = k; A.n_grp = n_grp; A.agg = agg; A.g_off = g_off; A.g_mem = g_mem;
   A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
-  if ((rc = bad_counter(c, st, &A.bad))) return rc;
-  // few groups (live traffic): the item range is cut into slices so that the call fills the CUs; many groups: one workgroup per GROUP_GPT groups
-  const int split = n_grp <= c->group_split_max;
+  // few groups (live traffic): the item range is cut into slices so that the call fills the CUs (at least four item tiles per wave);
+  // many groups: one workgroup per GROUP_GPT groups
   const int n_gtile = (n_grp + GROUP_GPT - 1) / GROUP_GPT, ntile = (n_item + 31) / 32;
-  A.n_split = 1;
-  if (split) {
-    int s = c->group_grid > 0 ? c->group_grid : 2 * c->num_cu / n_gtile;
-    if (c->group_grid <= 0 && s > ntile / 16) s = ntile / 16;      // (at least four item tiles per wave)
-    if (c->group_grid <= 0 && s < 2) s = 2;
-    A.n_split = s > GROUP_SPLIT_LIMIT ? GROUP_SPLIT_LIMIT : s;
-    if ((rc = carve_lists(c, c->group_ws, st, A, (size_t)n_grp * A.n_split, GROUP_K_MAX))) return rc;
-  }
-  c->plan.valid = 1; c->plan.group_path = split; c->plan.group_splits = split ? A.n_split : 0; c->plan.group_split_max = c->group_split_max;
+  const SplitPlan sp = plan_split(n_grp, n_gtile, c->group_split_max, c->group_grid, 2, c->num_cu, ntile / 16, 2, GROUP_SPLIT_LIMIT);
+  A.n_split = sp.n_split;
+  if (sp.split && (rc = carve_lists(c, c->group_ws, st, A, (size_t)n_grp * A.n_split, GROUP_K_MAX))) return rc;
+  c->plan.valid = 1; c->plan.group_path = sp.split; c->plan.group_splits = sp.split ? A.n_split : 0; c->plan.group_split_max = c->group_split_max;
   HIPCHK(c, poi::launch_group(A, st, &c->tm));
   return POI_OK;
 }
@@ -724,39 +726,23 @@ int poi_route_expand(poi_ctx* c, const float* users, const float* items, int32_t
   if (b <= 0 || b > ROUTE_B_MAX) return fail(c, POI_ENOTSUP, "poi_route_expand supports 1 <= b <= %d (got %d)", ROUTE_B_MAX, b);
   if (path_len < 0 || path_len > ROUTE_T_MAX) return fail(c, POI_ENOTSUP, "poi_route_expand supports 0 <= path_len <= %d (got %d)", ROUTE_T_MAX, path_len);
   if (path_len > 0 && (!path || path_stride < path_len)) return fail(c, POI_EINVAL, "poi_route_expand: path_len > 0 needs path and path_stride >= path_len");
-  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_route_expand: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
-  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "poi_route_expand: n < 0 or n_item <= 0");
   if (rows_per_list <= 0) return fail(c, POI_EINVAL, "poi_route_expand: rows_per_list must be positive (got %d)", rows_per_list);
-  const bool geo = wd != nullptr;
-  float bin_scale;
-  int rc;
-  if ((rc = check_ex_pair(c, "poi_route_expand", ex_off, ex))) return rc;
-  if ((rc = check_geo_term(c, "poi_route_expand", geo, !geo || (sts && coords && cphi && thr && last_poi), "the distance term needs sts / coords / cphi / thr / last_poi", n_dist, dd, &bin_scale))) return rc;
-  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "poi_route_expand: users must be float32");
-  if (n == 0) return POI_OK;
   hipStream_t st = (hipStream_t)stream;
-  HIPCHK(c, hipSetDevice(c->device));
+  poi::TileOperands T;
+  int rc;
+  if ((rc = tile_operands(c, "poi_route_expand", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, ex_off, ex, st, &T))) return rc;
+  if (n == 0) return POI_OK;
   poi::RouteArgs A = {};
-  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
-  A.n = n; A.n_item = n_item; A.dim = dim; A.b = b;
-  if (geo) { A.wd = wd; A.sts = sts; A.coords = coords; A.cphi = cphi; A.thr = thr; A.last_poi = last_poi; A.n_dist = n_dist; A.bin_scale = bin_scale; }
-  A.path = path; A.path_stride = path_stride; A.path_len = path_len;
-  A.ex_off = ex_off; A.ex = ex; A.rows_per_list = rows_per_list; A.live = live;
+  put_operands(A, T);
+  A.b = b; A.path = path; A.path_stride = path_stride; A.path_len = path_len;
+  A.rows_per_list = rows_per_list; A.live = live;
   A.idx_out = idx_out; A.score_out = score_out; A.lse_out = lse_out; A.count_out = count_out;
-  if ((rc = bad_counter(c, st, &A.bad))) return rc;
   // few rows (live traffic: one user's 1 .. 8 hypotheses): the item range is cut over workgroups so that the call fills the CUs, and a
-  // second kernel finishes the rows; many rows: one workgroup per 32-row tile, which finishes its own rows
+  // second kernel finishes the rows; many rows: one workgroup per 32-row tile, which finishes its own rows.  (A wave walks whole item blocks.)
   const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
   A.n_blk = (ntile + ROUTE_LSE_TILES - 1) / ROUTE_LSE_TILES;
-  const int split = n <= c->route_split_max;
-  A.n_split = 1; A.finish = 1;
-  if (split) {
-    int s = c->route_grid > 0 ? c->route_grid : 2 * c->num_cu / n_utile;
-    if (c->route_grid <= 0 && s > (A.n_blk + ROUTE_NWAVE - 1) / ROUTE_NWAVE) s = (A.n_blk + ROUTE_NWAVE - 1) / ROUTE_NWAVE;      // (a wave walks whole item blocks)
-    if (s < 1) s = 1;
-    A.n_split = s > ROUTE_SPLIT_LIMIT ? ROUTE_SPLIT_LIMIT : s;
-    A.finish = 0;
-  }
+  const SplitPlan sp = plan_split(n, n_utile, c->route_split_max, c->route_grid, 2, c->num_cu, (A.n_blk + ROUTE_NWAVE - 1) / ROUTE_NWAVE, 1, ROUTE_SPLIT_LIMIT);
+  A.n_split = sp.n_split; A.finish = !sp.split;
   const size_t rows = (size_t)n_utile * 32, lists = rows * A.n_split * ROUTE_NWAVE;
   if ((rc = carve(c, c->route_ws, st, [&](Carver& W) {
         A.part_s = (float*)W.bytes(sizeof(float) * lists * ROUTE_B_MAX);
@@ -766,7 +752,7 @@ int poi_route_expand(poi_ctx* c, const float* users, const float* items, int32_t
         A.row_cnt = (int*)W.bytes(sizeof(int) * rows);
       })))
     return rc;
-  c->plan.valid = 1; c->plan.route_path = split; c->plan.route_splits = split ? A.n_split : 0;
+  c->plan.valid = 1; c->plan.route_path = sp.split; c->plan.route_splits = sp.split ? A.n_split : 0;
   HIPCHK(c, poi::launch_route_expand(A, st, &c->tm));
   return POI_OK;
 }
@@ -791,20 +777,15 @@ int poi_route_merge(poi_ctx* c, const int32_t* idx, const float* score, const do
 
 // ---------------------------------------------------------------------------------------------
 // diversified recommendation (diverse.hip)
+// stage 1's arguments: its own limits around the operand block
 static int diverse_pool_check(poi_ctx* c, const char* who, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
                               const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr,
                               const int32_t* last_poi, int32_t n_dist, double dd, const int32_t* ex_off, const int32_t* ex, int32_t pool,
-                              float* bin_scale) {
+                              hipStream_t st, poi::TileOperands* T) {
   if (!c || !users || !items) return fail(c, POI_EINVAL, "%s: NULL ctx / users / items", who);
   if (pool <= 0 || pool > DIVERSE_POOL_MAX) return fail(c, POI_ENOTSUP, "%s supports 1 <= pool <= %d (got %d)", who, DIVERSE_POOL_MAX, pool);
-  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, dim);
-  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "%s: n < 0 or n_item <= 0", who);
-  const bool geo = wd != nullptr;
-  int rc;
-  if ((rc = check_ex_pair(c, who, ex_off, ex))) return rc;
-  if ((rc = check_geo_term(c, who, geo, !geo || (sts && coords && cphi && thr && last_poi), "the distance term needs sts / coords / cphi / thr / last_poi", n_dist, dd, bin_scale))) return rc;
-  if (geo && n_dist > DIVERSE_NDIST_MAX) return fail(c, POI_ENOTSUP, "%s supports n_dist <= %d (got %d)", who, DIVERSE_NDIST_MAX, n_dist);
-  if (is_f16(c, users)) return fail(c, POI_ENOTSUP, "%s: users must be float32", who);
+  if (int rc = tile_operands(c, who, users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, ex_off, ex, st, T)) return rc;
+  if (wd && n_dist > DIVERSE_NDIST_MAX) return fail(c, POI_ENOTSUP, "%s supports n_dist <= %d (got %d)", who, DIVERSE_NDIST_MAX, n_dist);
   return POI_OK;
 }
 
@@ -827,27 +808,19 @@ static int diverse_rerank_check(poi_ctx* c, const char* who, int32_t n, int32_t 
 }
 
 // stage 1 into (pool_idx, pool_score), or - both null - into the context's workspace, whose pieces come back through the same pointers
-static int diverse_pool_run(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd,
-                            const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
-                            int32_t n_dist, float bin_scale, const int32_t* ex_off, const int32_t* ex, int32_t pool, int32_t** pool_idx,
-                            float** pool_score, int32_t* count_out, hipStream_t st) {
+static int diverse_pool_run(poi_ctx* c, const poi::TileOperands& T, int32_t pool, int32_t** pool_idx, float** pool_score, int32_t* count_out,
+                            hipStream_t st) {
   poi::DiverseArgs A = {};
-  A.users = users; A.items = items; A.items_f16 = is_f16(c, items);
-  A.n = n; A.n_item = n_item; A.dim = dim; A.k = pool;
-  if (wd) { A.wd = wd; A.sts = sts; A.coords = coords; A.cphi = cphi; A.thr = thr; A.last_poi = last_poi; A.n_dist = n_dist; A.bin_scale = bin_scale; }
-  A.ex_off = ex_off; A.ex = ex; A.count_out = count_out;
+  put_operands(A, T);
+  A.k = pool; A.count_out = count_out;
+  const int n = T.n;
+  // few rows (live traffic): the item range of every 32-row tile is cut into slices so that the call fills the CUs (at least four item
+  // tiles per wave); many rows: one workgroup per tile
+  const int n_utile = (n + 31) / 32, ntile = (T.n_item + 31) / 32;
+  const SplitPlan sp = plan_split(n, n_utile, c->diverse_split_max, c->diverse_grid, 2, c->num_cu, ntile / 16, 2, DIVERSE_SPLIT_LIMIT);
+  const int split = sp.split;
+  A.n_split = sp.n_split;
   int rc;
-  if ((rc = bad_counter(c, st, &A.bad))) return rc;
-  // few rows (live traffic): the item range of every 32-row tile is cut into slices so that the call fills the CUs; many rows: one workgroup per tile
-  const int split = n <= c->diverse_split_max;
-  const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
-  A.n_split = 1;
-  if (split) {
-    int s = c->diverse_grid > 0 ? c->diverse_grid : 2 * c->num_cu / n_utile;
-    if (c->diverse_grid <= 0 && s > ntile / 16) s = ntile / 16;      // (at least four item tiles per wave)
-    if (c->diverse_grid <= 0 && s < 2) s = 2;
-    A.n_split = s > DIVERSE_SPLIT_LIMIT ? DIVERSE_SPLIT_LIMIT : s;
-  }
   const bool own = *pool_idx == nullptr;
   const size_t lists = split ? (size_t)n * A.n_split : 0;
   if ((rc = carve(c, c->diverse_ws, st, [&](Carver& W) {
@@ -884,16 +857,14 @@ int poi_diverse_pool(poi_ctx* c, const float* users, const float* items, int32_t
                      const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
                      const int32_t* ex_off, const int32_t* ex, int32_t pool, int32_t* pool_idx, float* pool_score, int32_t* count_out,
                      void* stream) {
-  float bin_scale;
+  hipStream_t st = (hipStream_t)stream;
+  poi::TileOperands T;
   if (int rc = diverse_pool_check(c, "poi_diverse_pool", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, ex_off, ex,
-                                  pool, &bin_scale))
+                                  pool, st, &T))
     return rc;
   if (!pool_idx || !pool_score) return fail(c, POI_EINVAL, "poi_diverse_pool: NULL pool_idx / pool_score");
   if (n == 0) return POI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(c, hipSetDevice(c->device));
-  return diverse_pool_run(c, users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, bin_scale, ex_off, ex, pool, &pool_idx,
-                          &pool_score, count_out, st);
+  return diverse_pool_run(c, T, pool, &pool_idx, &pool_score, count_out, st);
 }
 
 int poi_diverse_rerank(poi_ctx* c, const int32_t* pool_idx, const float* pool_score, int32_t n, int32_t pool, const float* items, int32_t n_item,
@@ -914,19 +885,16 @@ int poi_diverse_topk(poi_ctx* c, const float* users, const float* items, int32_t
                      const int32_t* ex_off, const int32_t* ex, int32_t pool, int32_t k, double trade, double geo_weight, double scale_km,
                      int32_t* idx_out, float* score_out, int32_t* pos_out, double* obj_out, int32_t* pool_idx, float* pool_score,
                      int32_t* count_out, void* stream) {
-  float bin_scale;
+  hipStream_t st = (hipStream_t)stream;
+  poi::TileOperands T;
   int rc;
   if ((rc = diverse_pool_check(c, "poi_diverse_topk", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, ex_off, ex, pool,
-                               &bin_scale)))
+                               st, &T)))
     return rc;
   if ((rc = diverse_rerank_check(c, "poi_diverse_topk", n, pool, items, n_item, dim, coords, cphi, k, trade, geo_weight, scale_km, idx_out))) return rc;
   if ((pool_idx == nullptr) != (pool_score == nullptr)) return fail(c, POI_EINVAL, "poi_diverse_topk: pool_idx and pool_score go together");
   if (n == 0) return POI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = diverse_pool_run(c, users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, bin_scale, ex_off, ex, pool, &pool_idx,
-                             &pool_score, count_out, st)))
-    return rc;
+  if ((rc = diverse_pool_run(c, T, pool, &pool_idx, &pool_score, count_out, st))) return rc;
   return diverse_rerank_run(c, pool_idx, pool_score, n, pool, items, n_item, dim, coords, cphi, k, trade, geo_weight, scale_km, idx_out, score_out,
                             pos_out, obj_out, st);
 }

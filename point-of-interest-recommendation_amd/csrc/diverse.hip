@@ -15,7 +15,7 @@
 // in front of the newcomer are a prefix of the sorted list, the others move down one lane), many - the first tiles - through
 // lds_list_merge's sort.  Either way the list is the best 64 of everything offered, and everything that beats the list's K-th entry is
 // offered: with K = pool <= 64 entries 0 .. K - 1 are exact, to the last one.  The four waves' lists meet in LDS (top64_merge); on the
-// split path they go to per-slice partial lists of 64 entries that diverse_merge_kernel folds.  The order is total and a pair's score
+// split path they go to per-slice partial lists of 64 entries that topk_slices_merge_kernel folds.  The order is total and a pair's score
 // does not depend on the slice or the wave: every grid gives the same bits, a row gives the same bits alone as in a call of thousands.
 //
 // Stage 2, the re-rank (everything in float64).  Pool position i = the i-th best, m = the entries before the first -1.
@@ -48,29 +48,6 @@ constexpr int RERANK_LDS_MAX = DIVERSE_POOL_MAX * (256 + 4) * 4;
 
 __device__ __forceinline__ bool finite_f(float s) { return (__float_as_uint(s) & 0x7f800000u) != 0x7f800000u; }
 
-// the lanes of `bal` hold candidates (v, j) for the sorted 64-entry list (ls, lx), entry l on lane l (group.hip's list_take)
-__device__ __forceinline__ void pool_take(float* ls, int* lx, unsigned long long bal, bool cand, float v, int j, int K) {
-  if (__popcll(bal) > 8) { lds_list_merge(ls, lx, cand ? v : neg_inf(), cand ? j : PAD_ID, K); return; }
-  const int lane = lane_id();
-  __builtin_amdgcn_wave_barrier();
-  float cs = ls[lane];
-  int ci = lx[lane];
-  while (bal) {
-    const int src = __ffsll((long long)bal) - 1;
-    bal &= bal - 1;
-    const float nv = readlane_f(v, src);
-    const int nj = __builtin_amdgcn_readlane(j, src);
-    const int pos = __popcll(__ballot(better(cs, ci, nv, nj)));
-    const float us = __shfl_up(cs, 1, 64);
-    const int ui = __shfl_up(ci, 1, 64);
-    if (lane == pos) { cs = nv; ci = nj; }
-    else if (lane > pos) { cs = us; ci = ui; }
-  }
-  __builtin_amdgcn_wave_barrier();
-  ls[lane] = cs; lx[lane] = ci;
-  wave_fence();
-}
-
 }  // namespace
 
 template <int D8, bool DB, bool GEO>
@@ -89,22 +66,12 @@ __global__ __launch_bounds__(POI_BLOCK) void diverse_pool_kernel(DiverseArgs A) 
   for (int i = w; i < 32; i += POI_NWAVE) {
     const int r = ut * 32 + i;
     int bad = 0, e0 = 0, e1 = 0;
-    if (r < A.n && A.ex) {
-      e0 = A.ex_off[r]; e1 = A.ex_off[r + 1];
-      bad = e0 < 0 || e1 < e0;
-      if (!bad)
-        for (int p = e0 + lane; p < e1; p += 64) { const int v = A.ex[p]; bad |= (unsigned)v >= (unsigned)N || (p > e0 && A.ex[p - 1] >= v); }
-    }
+    if (r < A.n && A.ex) bad = check_ex_row(A.ex_off, A.ex, r, N, lane, e0, e1);
     bad = __any(bad) ? 1 : 0;
     if (lane == 0) {
       s_ok[i] = r < A.n && !bad; s_e0[i] = bad ? 0 : e0; s_e1[i] = bad ? 0 : e1;
       if (bad && sl == 0) atomicAdd(A.bad, 1);
-      if (GEO) {
-        const int lp = r < A.n ? A.last_poi[r] : -1;
-        const int lc = min(max(lp, 0), N - 1);                  // (an id outside the table reads no memory outside it)
-        s_has[i] = lp >= 0;
-        s_ulat[i] = A.coords[2 * (size_t)lc]; s_ulon[i] = A.coords[2 * (size_t)lc + 1]; s_ucp[i] = A.cphi[lc];
-      }
+      if (GEO) load_row_geo(A, r < A.n ? r : -1, N, s_has[i], s_ulat[i], s_ulon[i], s_ucp[i]);
     }
   }
   if (GEO)
@@ -161,7 +128,7 @@ __global__ __launch_bounds__(POI_BLOCK) void diverse_pool_kernel(DiverseArgs A) 
         const int e0 = s_e0[row], e1 = s_e1[row];
         if (cand && e1 > e0) cand = !listed(A.ex, e0, e1, j);
         const unsigned long long bal = __ballot(cand);
-        if (bal) pool_take(ls + row * DIVERSE_POOL_MAX, lx + row * DIVERSE_POOL_MAX, bal, cand, v, j, K);
+        if (bal) list_take(ls + row * DIVERSE_POOL_MAX, lx + row * DIVERSE_POOL_MAX, bal, cand, v, j, K);
       }
     }
     if constexpr (DB) {
@@ -184,26 +151,6 @@ __global__ __launch_bounds__(POI_BLOCK) void diverse_pool_kernel(DiverseArgs A) 
     const int cnt = (s_ok[i] && sl == 0) ? N - (s_e1[i] - s_e0[i]) : 0;
     list_emit<DIVERSE_POOL_MAX>(A, A.part_s != nullptr, row, sl, cs, ci, cnt);
   }
-}
-
-// split path: one wave per row folds the row's slice lists in slice order
-__global__ __launch_bounds__(64) void diverse_merge_kernel(DiverseArgs A) {
-  const int r = blockIdx.x, lane = lane_id(), S = A.n_split;
-  const size_t base = (size_t)r * S;
-  float cs = neg_inf();
-  int ci = PAD_ID, cnt = 0;
-  for (int s = 0; s < S; ++s) {
-    const size_t at = (base + s) * DIVERSE_POOL_MAX + lane;
-    top64_merge(cs, ci, A.part_s[at], A.part_i[at]);
-  }
-  for (int s = lane; s < S; s += 64) cnt += A.part_cnt[base + s];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if (lane < A.k) {
-    A.idx_out[(size_t)r * A.k + lane] = ci == PAD_ID ? -1 : ci;
-    A.score_out[(size_t)r * A.k + lane] = ci == PAD_ID ? neg_inf() : cs;
-  }
-  if (lane == 0 && A.count_out) A.count_out[r] = cnt;
 }
 
 template <bool GEO, bool EMB>
@@ -340,7 +287,7 @@ hipError_t launch_diverse_pool(DiverseArgs& A, hipStream_t st, Timing* tm) {
   tm->begin("diverse_pool", st);
   const hipError_t e = A.wd ? launch_pool_g<true>(A, st) : launch_pool_g<false>(A, st);
   if (e != hipSuccess) return e;
-  if (A.part_s) hipLaunchKernelGGL(diverse_merge_kernel, dim3((unsigned)A.n), dim3(64), 0, st, A);
+  if (A.part_s) launch_topk_slices_merge(slice_lists(A), DIVERSE_POOL_MAX, A.n, st);
   tm->end(st);
   return hipGetLastError();
 }

@@ -180,37 +180,12 @@ __global__ __launch_bounds__(256) void geoie_score_kernel(GeoScoreArgs A) {
     if (lane == 0) m_cnt[w] = count;
     __syncthreads();
     if (w == 0) {
-      const int ll = lane & (GEO_K_MAX - 1), hw = lane >> 5;
-      float as = m_s[hw][ll], bs = m_s[2 + hw][ll];
-      int ai = m_i[hw][ll], bi = m_i[2 + hw][ll];
-      wave_sort_desc(as, ai);
-      top64_merge(as, ai, bs, bi);
+      float as;
+      int ai;
+      block_lists_fold<GEO_K_MAX>(&m_s[0][0], &m_i[0][0], GEO_K_MAX, as, ai);
       list_emit<GEO_K_MAX>(A, A.n_split > 1, r, s, as, ai, (m_cnt[0] + m_cnt[1]) + (m_cnt[2] + m_cnt[3]));
     }
   }
-}
-
-// several spans per row: one wave per row folds the row's span lists, two at a time, in span order (near_merge_kernel's text: see there)
-__global__ __launch_bounds__(64) void geoie_score_merge_kernel(GeoScoreArgs A) {
-  const int r = blockIdx.x, lane = lane_id(), S = A.n_split;
-  const size_t base = (size_t)r * S;
-  float cs = neg_inf();
-  int ci = PAD_ID, cnt = 0;
-  for (int s0 = 0; s0 < S; s0 += 2) {
-    const int sl = s0 + (lane >> 5);
-    const size_t at = (base + sl) * GEO_K_MAX + (lane & (GEO_K_MAX - 1));
-    const float ns = sl < S ? A.part_s[at] : neg_inf();
-    const int ni = sl < S ? A.part_i[at] : PAD_ID;
-    top64_merge(cs, ci, ns, ni);
-  }
-  for (int s = lane; s < S; s += 64) cnt += A.part_cnt[base + s];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if (lane < A.k) {
-    A.idx_out[(size_t)r * A.k + lane] = ci == PAD_ID ? -1 : ci;
-    if (A.score_out) A.score_out[(size_t)r * A.k + lane] = ci == PAD_ID ? neg_inf() : cs;
-  }
-  if (lane == 0 && A.count_out) A.count_out[r] = cnt;
 }
 
 template <int MAXD>
@@ -219,7 +194,7 @@ static hipError_t launch_geoie_score_t(GeoScoreArgs& A, hipStream_t st, Timing* 
   if (A.k > 0) {
     tm->begin("geoie_topk_geo", st);
     hipLaunchKernelGGL((geoie_score_kernel<MAXD, true>), grid, dim3(256), 0, st, A);
-    if (A.n_split > 1) hipLaunchKernelGGL(geoie_score_merge_kernel, dim3((unsigned)A.n_rows), dim3(64), 0, st, A);
+    if (A.n_split > 1) launch_topk_slices_merge(slice_lists(A), GEO_K_MAX, A.n_rows, st);
   } else {
     tm->begin("geoie_score_geo", st);
     hipLaunchKernelGGL((geoie_score_kernel<MAXD, false>), grid, dim3(256), 0, st, A);

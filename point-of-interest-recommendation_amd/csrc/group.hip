@@ -16,7 +16,7 @@
 // Every pair's aggregate is first compared with the K-th entry of its group's list (LDS reads only; one ballot for the common tile);
 // the survivors are looked up in the exclusion list and inserted into the wave's sorted LDS list, one at a time (list_take; many at
 // once, as in the first tiles, through lds_list_merge's sort).  The waves' lists meet in LDS; on the split path they go to per-slice
-// partial lists that group_merge_kernel folds.  The order (descending a, ascending id) is total, the aggregate of a pair
+// partial lists that topk_slices_merge_kernel (topk_merge.hip) folds.  The order (descending a, ascending id) is total, the aggregate of a pair
 // does not depend on the slice, the wave or the pass: every grid gives the same bits, and a group gives the same bits alone as in a
 // call of thousands.  No float atomics; a rejected group is counted with one integer atomic.
 //
@@ -58,31 +58,6 @@ __device__ __forceinline__ int group_check(const GroupArgs& A, int g, int& a, in
       for (int p = e0 + tid; p < e1; p += POI_BLOCK) { const int v = A.ex[p]; bad |= (unsigned)v >= (unsigned)A.n_item || (p > e0 && A.ex[p - 1] >= v); }
   }
   return __syncthreads_or(bad);
-}
-
-// the lanes of `bal` hold candidates (v, j) for the sorted 64-entry list (ls, lx), entry l on lane l.  A few (the common tile, once the
-// list has warmed up): one at a time - the entries in front of the newcomer are a prefix of the sorted list, the others move down one
-// lane.  Many (the first tiles): lds_list_merge's sort.  The list is the best 64 of everything offered either way: the same bits.
-__device__ __forceinline__ void list_take(float* ls, int* lx, unsigned long long bal, bool cand, float v, int j, int K) {
-  if (__popcll(bal) > 8) { lds_list_merge(ls, lx, cand ? v : neg_inf(), cand ? j : PAD_ID, K); return; }
-  const int lane = lane_id();
-  __builtin_amdgcn_wave_barrier();
-  float cs = ls[lane];
-  int ci = lx[lane];
-  while (bal) {
-    const int src = __ffsll((long long)bal) - 1;
-    bal &= bal - 1;
-    const float nv = readlane_f(v, src);
-    const int nj = __builtin_amdgcn_readlane(j, src);
-    const int pos = __popcll(__ballot(better(cs, ci, nv, nj)));
-    const float us = __shfl_up(cs, 1, 64);
-    const int ui = __shfl_up(ci, 1, 64);
-    if (lane == pos) { cs = nv; ci = nj; }
-    else if (lane > pos) { cs = us; ci = ui; }
-  }
-  __builtin_amdgcn_wave_barrier();
-  ls[lane] = cs; lx[lane] = ci;
-  __builtin_amdgcn_wave_barrier();
 }
 
 // lanes with `mine` offer (v, j) to the sorted list (ls, lx) of a group whose exclusion list is ex[e0 .. e1)
@@ -169,7 +144,7 @@ __global__ __launch_bounds__(POI_BLOCK) void group_kernel(GroupArgs A) {
           }
         }
         s_mem[w][lane] = member;
-        if (GEO) {
+        if (GEO) {                                    // (load_row_geo's text, and block_lists_fold's below: through the helpers this kernel compiles to other code)
           const int lp = member >= 0 ? A.last_poi[member] : -1;
           const int lc = min(max(lp, 0), N - 1);                 // (an id outside the table reads no memory outside it)
           s_has[w][lane] = lp >= 0;
@@ -262,11 +237,11 @@ __global__ __launch_bounds__(POI_BLOCK) void group_kernel(GroupArgs A) {
 
   __syncthreads();
   if (w == 0) {
-    const int l = lane & (GROUP_K_MAX - 1), hw = lane >> 5;
     for (int p = 0; p < GPT; ++p) {
       const int g = gt * GPT + p;
       if (g >= A.n_grp) break;
       if (!BIG && s_gm[p] > 32) continue;           // (the other kernel's)
+      const int l = lane & (GROUP_K_MAX - 1), hw = lane >> 5;
       float as = l_s[hw][p][l], bs = l_s[2 + hw][p][l];
       int ai = l_i[hw][p][l], bi = l_i[2 + hw][p][l];
       wave_sort_desc(as, ai);
@@ -275,29 +250,6 @@ __global__ __launch_bounds__(POI_BLOCK) void group_kernel(GroupArgs A) {
       list_emit<GROUP_K_MAX>(A, A.part_s != nullptr, g, sl, as, ai, cnt);
     }
   }
-}
-
-// split path: one wave per group folds the group's slice lists, two at a time, in slice order (the text of near_merge_kernel)
-__global__ __launch_bounds__(64) void group_merge_kernel(GroupArgs A) {
-  const int g = blockIdx.x, lane = lane_id(), S = A.n_split;
-  const size_t base = (size_t)g * S;
-  float cs = neg_inf();
-  int ci = PAD_ID, cnt = 0;
-  for (int s0 = 0; s0 < S; s0 += 2) {
-    const int sl = s0 + (lane >> 5);
-    const size_t at = (base + sl) * GROUP_K_MAX + (lane & (GROUP_K_MAX - 1));
-    const float ns = sl < S ? A.part_s[at] : neg_inf();
-    const int ni = sl < S ? A.part_i[at] : PAD_ID;
-    top64_merge(cs, ci, ns, ni);
-  }
-  for (int s = lane; s < S; s += 64) cnt += A.part_cnt[base + s];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if (lane < A.k) {
-    A.idx_out[(size_t)g * A.k + lane] = ci == PAD_ID ? -1 : ci;
-    if (A.score_out) A.score_out[(size_t)g * A.k + lane] = ci == PAD_ID ? neg_inf() : cs;
-  }
-  if (lane == 0 && A.count_out) A.count_out[g] = cnt;
 }
 
 // The definition on explicit score rows: one workgroup per group, a wave takes 64 POIs per round and reads the members' rows in list order.
@@ -325,11 +277,9 @@ __global__ __launch_bounds__(POI_BLOCK) void group_scores_kernel(const float* __
   }
   __syncthreads();
   if (w == 0) {
-    const int l = lane & (GROUP_K_MAX - 1), hw = lane >> 5;
-    float as = l_s[hw][l], bs = l_s[2 + hw][l];
-    int ai = l_i[hw][l], bi = l_i[2 + hw][l];
-    wave_sort_desc(as, ai);
-    top64_merge(as, ai, bs, bi);
+    float as;
+    int ai;
+    block_lists_fold<GROUP_K_MAX>(&l_s[0][0], &l_i[0][0], 64, as, ai);
     list_emit<GROUP_K_MAX>(A, false, g, 0, as, ai, M > 0 ? N - (e1 - e0) : 0);
   }
 }
@@ -356,7 +306,7 @@ hipError_t launch_group(GroupArgs& A, hipStream_t st, Timing* tm) {
   tm->begin("group_topk", st);
   const hipError_t e = A.wd ? launch_group_g<true>(A, st) : launch_group_g<false>(A, st);
   if (e != hipSuccess) return e;
-  if (A.part_s) hipLaunchKernelGGL(group_merge_kernel, dim3((unsigned)A.n_grp), dim3(64), 0, st, A);
+  if (A.part_s) launch_topk_slices_merge(slice_lists(A), GROUP_K_MAX, A.n_grp, st);
   tm->end(st);
   return hipGetLastError();
 }

@@ -15,7 +15,7 @@
 //   pair, whatever the slice, the wave or the grid - plus wd * sts[r][bin] for bin < n_dist when the row has an anchor.
 // Each wave keeps its best 64 sorted over its lanes (top64_merge, topk_list.h: sort the batch, keep the better of cur[l] / new[63 - l], sort); a batch
 // without an entry above the K-th best so far is dropped after one ballot.  The four waves' lists meet in LDS.  Row path: that list is
-// the answer.  Split path: it goes to a (row, slice) partial list and a one-wave merge kernel per row combines the slices.  The order
+// the answer.  Split path: it goes to a (row, slice) partial list and a one-wave merge kernel per row (topk_merge.hip) combines the slices.  The order
 // (descending score, ascending id) is total over distinct ids, so the result does not depend on how a band was cut: every grid gives the
 // same bits.  No atomics touch a result; a rejected row is counted with one integer atomic.
 //
@@ -158,37 +158,11 @@ __global__ __launch_bounds__(256) void near_kernel(NearArgs A) {
   if (lane == 0) m_cnt[w] = count;
   __syncthreads();
   if (w == 0) {
-    const int l = lane & (NEAR_K_MAX - 1), hw = lane >> 5;
-    float as = m_s[hw][l], bs = m_s[2 + hw][l];
-    int ai = m_i[hw][l], bi = m_i[2 + hw][l];
-    wave_sort_desc(as, ai);
-    top64_merge(as, ai, bs, bi);
+    float as;
+    int ai;
+    block_lists_fold<NEAR_K_MAX>(&m_s[0][0], &m_i[0][0], NEAR_K_MAX, as, ai);
     list_emit<NEAR_K_MAX>(A, A.part_s != nullptr, r, s, as, ai, (m_cnt[0] + m_cnt[1]) + (m_cnt[2] + m_cnt[3]));
   }
-}
-
-// split path: one wave per row folds the row's slice lists, two at a time, in slice order.  (geoie_score_merge_kernel has the same text:
-// behind one shared device function the compiler ordered both kernels' instructions differently, so each keeps its own.)
-__global__ __launch_bounds__(64) void near_merge_kernel(NearArgs A) {
-  const int r = blockIdx.x, lane = lane_id(), S = A.n_split;
-  const size_t base = (size_t)r * S;
-  float cs = neg_inf();
-  int ci = PAD_ID, cnt = 0;
-  for (int s0 = 0; s0 < S; s0 += 2) {
-    const int sl = s0 + (lane >> 5);
-    const size_t at = (base + sl) * NEAR_K_MAX + (lane & (NEAR_K_MAX - 1));
-    const float ns = sl < S ? A.part_s[at] : neg_inf();
-    const int ni = sl < S ? A.part_i[at] : PAD_ID;
-    top64_merge(cs, ci, ns, ni);
-  }
-  for (int s = lane; s < S; s += 64) cnt += A.part_cnt[base + s];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if (lane < A.k) {
-    A.idx_out[(size_t)r * A.k + lane] = ci == PAD_ID ? -1 : ci;
-    if (A.score_out) A.score_out[(size_t)r * A.k + lane] = ci == PAD_ID ? neg_inf() : cs;
-  }
-  if (lane == 0 && A.count_out) A.count_out[r] = cnt;
 }
 
 hipError_t launch_near(NearArgs& A, hipStream_t st, Timing* tm) {
@@ -201,7 +175,7 @@ hipError_t launch_near(NearArgs& A, hipStream_t st, Timing* tm) {
     case 4: hipLaunchKernelGGL(near_kernel<4>, grid, dim3(256), 0, st, A); break;
     default: return hipErrorInvalidValue;
   }
-  if (A.part_s) hipLaunchKernelGGL(near_merge_kernel, dim3((unsigned)A.n), dim3(64), 0, st, A);
+  if (A.part_s) launch_topk_slices_merge(slice_lists(A), NEAR_K_MAX, A.n, st);
   tm->end(st);
   return hipGetLastError();
 }

@@ -592,6 +592,26 @@ struct NearArgs {
 };
 hipError_t launch_near(NearArgs& A, hipStream_t st, Timing* tm);
 
+// What every kernel that walks 32-row x 32-item tiles of users . items takes (rank.hip, group.hip, route.hip, diverse.hip).  The host
+// checks and fills it in one place (tile_operands, abi_serve.hip) and copies it into the family's argument struct, which holds the same
+// members in an order of its own: behind a common base the tile walks compiled to slower code (route's distance-term walk by 3 - 4 %)
+struct TileOperands {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim;
+  const float *wd, *sts; const double *coords, *cphi, *thr; const int* last_poi; int n_dist; float bin_scale;      // distance term, or wd null
+  const int *ex_off, *ex;                                     // per-row (group, list) exclusion lists (ascending ids), or both null
+  int* bad;                                                   // device counter of rejected rows / groups / targets (poi_ctx_take_bad_ids)
+};
+
+// The partial top-K lists of a split path and where their fold goes (topk_merge.hip): row r owns the lists r n_split .. of k_max entries
+struct SliceLists {
+  const float* part_s; const int *part_i, *part_cnt; int n_split, k;
+  int* idx_out; float* score_out; int* count_out;             // (rows, k); score_out / count_out may be null
+};
+void launch_topk_slices_merge(const SliceLists& L, int k_max, int n_rows, hipStream_t st);      // k_max (the lists' length): 32 or 64
+template <class Args>
+inline SliceLists slice_lists(const Args& A) { return SliceLists{A.part_s, A.part_i, A.part_cnt, A.n_split, A.k, A.idx_out, A.score_out, A.count_out}; }
+
 // Exact rank of target POIs among all POIs (rank.hip)
 #define RANK_LT_MAX 8                       // targets per row
 #define RANK_TILES_MAX 65535                // item tiles one wave may walk: its per-lane counters are 16 bits wide

@@ -43,7 +43,7 @@ namespace {
 __device__ __forceinline__ double neg_inf_d() { return -__builtin_huge_val(); }
 
 // the lanes of `bal` hold candidates (v, j) for the sorted ROUTE_B_MAX-entry list (ls, lx) in LDS: one at a time - the entries in front of
-// the newcomer are a prefix of the sorted list, the others move down one lane (group.hip's list_take on a short list)
+// the newcomer are a prefix of the sorted list, the others move down one lane (topk_list.h's list_take on a short list)
 __device__ __forceinline__ void list8_take(float* ls, int* lx, unsigned long long bal, float v, int j) {
   const int lane = lane_id();
   float cs = lane < ROUTE_B_MAX ? ls[lane] : neg_inf();
@@ -72,15 +72,9 @@ __device__ __forceinline__ void route_finish_row(const RouteArgs& A, int row, in
     if (lane == 0) { A.lse_out[row] = __builtin_nan(""); if (A.count_out) A.count_out[row] = 0; }
     return;
   }
-  float cs = neg_inf();
-  int ci = PAD_ID;
-  for (int w0 = 0; w0 < W; w0 += 64 / ROUTE_B_MAX) {
-    const int wv = w0 + lane / ROUTE_B_MAX;
-    const size_t at = ((size_t)row * W + wv) * ROUTE_B_MAX + (lane & (ROUTE_B_MAX - 1));
-    const float ns = wv < W ? A.part_s[at] : neg_inf();
-    const int ni = wv < W ? A.part_i[at] : PAD_ID;
-    top64_merge(cs, ci, ns, ni);
-  }
+  float cs;
+  int ci;
+  fold_slice_lists<ROUTE_B_MAX>(A.part_s, A.part_i, (size_t)row * W, W, cs, ci);
   if (lane < b) {
     A.idx_out[(size_t)row * b + lane] = ci == PAD_ID ? -1 : ci;
     A.score_out[(size_t)row * b + lane] = ci == PAD_ID ? neg_inf() : cs;
@@ -126,13 +120,7 @@ __global__ __launch_bounds__(POI_BLOCK) void route_expand_kernel(RouteArgs A) {
     int st = 0, e0 = 0, e1 = 0, cnt = 0, pv = -1;
     if (row < A.n && (!A.live || A.live[row] != 0)) {      // (wave-uniform)
       int bad = 0;
-      if (A.ex) {
-        const int lst = row / A.rows_per_list;
-        e0 = A.ex_off[lst]; e1 = A.ex_off[lst + 1];
-        bad = e0 < 0 || e1 < e0;
-        if (!bad)
-          for (int p = e0 + lane; p < e1; p += 64) { const int v = A.ex[p]; bad |= (unsigned)v >= (unsigned)N || (p > e0 && A.ex[p - 1] >= v); }
-      }
+      if (A.ex) bad = check_ex_row(A.ex_off, A.ex, row / A.rows_per_list, N, lane, e0, e1);
       if (lane < PL) { pv = A.path[(size_t)row * A.path_stride + lane]; bad |= (unsigned)pv >= (unsigned)N; }
       bad = __any(bad) ? 1 : 0;
       st = bad ? 2 : 1;
@@ -153,12 +141,7 @@ __global__ __launch_bounds__(POI_BLOCK) void route_expand_kernel(RouteArgs A) {
         A.row_st[row] = st; A.row_cnt[row] = cnt;
         if (st == 2) atomicAdd(A.bad, 1);
       }
-      if (GEO) {
-        const int lp = row < A.n ? A.last_poi[row] : -1;
-        const int lc = min(max(lp, 0), N - 1);      // (an id outside the table reads no memory outside it)
-        s_has[i] = lp >= 0;
-        s_ulat[i] = A.coords[2 * (size_t)lc]; s_ulon[i] = A.coords[2 * (size_t)lc + 1]; s_ucp[i] = A.cphi[lc];
-      }
+      if (GEO) load_row_geo(A, row < A.n ? row : -1, N, s_has[i], s_ulat[i], s_ulon[i], s_ucp[i]);
     }
   }
   if (GEO)

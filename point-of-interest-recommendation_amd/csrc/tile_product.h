@@ -1,5 +1,5 @@
-// The 32 x 32 float32 tile product of the item-stationary serving kernels (rank.hip, group.hip) and the helpers that go with it: the
-// fragment loader, the distance term's probability and the exclusion-list search.  One routine for every kernel that must score a
+// The 32 x 32 float32 tile product of the item-stationary serving kernels (rank.hip, group.hip, route.hip, diverse.hip) and the helpers
+// that go with it: the fragment loader, the distance term's probability, the exclusion-list search and what a tile row's prologue reads.  One routine for every kernel that must score a
 // (row, item) pair to the same bits as the others.
 #pragma once
 #include "poi_common.h"
@@ -47,6 +47,25 @@ __device__ __forceinline__ bool listed(const int* ex, int a, int b, int id) {
   const int e1 = b;
   while (a < b) { const int md = (a + b) >> 1; if (ex[md] < id) a = md + 1; else b = md; }
   return a < e1 && ex[a] == id;
+}
+
+// one wave: exclusion list `list` of (ex_off, ex) into [e0, e1).  Nonzero on a lane that saw it broken - offsets out of order, an id
+// outside [0, N) or not above the one before it; the caller joins the lanes
+__device__ __forceinline__ int check_ex_row(const int* ex_off, const int* ex, int list, int N, int lane, int& e0, int& e1) {
+  e0 = ex_off[list]; e1 = ex_off[list + 1];
+  int bad = e0 < 0 || e1 < e0;
+  if (!bad)
+    for (int p = e0 + lane; p < e1; p += 64) { const int v = ex[p]; bad |= (unsigned)v >= (unsigned)N || (p > e0 && ex[p - 1] >= v); }
+  return bad;
+}
+
+// the distance term's row side: has row `row` (-1: no such row) a last POI, and that POI's latitude, longitude and cos(latitude)
+template <class Args>
+__device__ __forceinline__ void load_row_geo(const Args& A, int row, int N, int& has, double& lat, double& lon, double& cp) {
+  const int lp = row >= 0 ? A.last_poi[row] : -1;
+  const int lc = min(max(lp, 0), N - 1);            // (an id outside the table reads no memory outside it)
+  has = lp >= 0;
+  lat = A.coords[2 * (size_t)lc]; lon = A.coords[2 * (size_t)lc + 1]; cp = A.cphi[lc];
 }
 
 __device__ __forceinline__ float pos_inf() { return __builtin_huge_valf(); }

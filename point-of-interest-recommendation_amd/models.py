@@ -485,6 +485,27 @@ class _Base:
         eo, ex = (torch.as_tensor(v).to(self.device) for v in check_exclusion_csr(off, lst, n, self.n_item))
         return eo, (ex if ex.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
 
+    def _tile_operands(self, users, items, kdim, term):
+        """The 13 arguments that follow the context handle in poi_score_rank / poi_group_topk / poi_route_expand / poi_diverse_topk
+        (users .. dd).  term: (wd, sts rows, last POI rows) of the model's distance term, or None."""
+        wd = sts = lp = coords = cphi = thr = None
+        n_dist, dd_m = 0, 0.0
+        if term is not None:
+            wd, sts, lp = term
+            coords, cphi, thr, n_dist, dd_m = self.coords, self._cphi, self._binthr, self.n_dist, self.dd * 1000.0
+        return [_ptr(users), _ptr(items), users.shape[0], self.n_item, kdim, _ptr(wd), _ptr(sts), _ptr(coords), _ptr(cphi), _ptr(thr), _ptr(lp),
+                int(n_dist), float(dd_m)]
+
+    def _serve_out(self, first, optional_pairs, sync, message):
+        """What a serving call returns: `first`, then every (tensor, wanted) pair that is wanted; alone, `first` itself.  With sync the
+        kernels' count of rejected rows is read first and raises IndexError("<count> <message>")."""
+        if sync:
+            bad = self.ctx.take_bad_ids(self._stream().value)
+            if bad:
+                raise IndexError("%d %s" % (bad, message))
+        out = (first,) + tuple(t for t, wanted in optional_pairs if wanted)
+        return out if len(out) > 1 else first
+
     def _near_launch(self, users, items, anchor, c_r, ex, term, k, return_scores, return_counts, sync):
         """One poi_score_topk_near call -> idx[, scores][, counts] (device tensors)."""
         n, k = users.shape[0], int(k)
@@ -499,13 +520,8 @@ class _Base:
         self.ctx.check(self.lib.poi_score_topk_near(self.ctx.handle, _ptr(users), _ptr(items), n, self.n_item, self.kdim, _ptr(coords), _ptr(cphi),
                                                     _ptr(order), _ptr(anchor), c_r, _ptr(ex[0]), _ptr(ex[1]), _ptr(wd), _ptr(sts), _ptr(thr),
                                                     int(n_dist), float(dd_m), k, _ptr(idx), _ptr(sc), _ptr(cnt), self._stream()))
-        if sync:
-            bad = self.ctx.take_bad_ids(self._stream().value)
-            if bad:
-                raise IndexError("%d row(s) with an anchor outside [-1, %d) or an exclusion id outside [0, %d): their lists are all -1"
-                                 % (bad, self.n_item, self.n_item))
-        out = (idx,) + ((sc,) if return_scores else ()) + ((cnt,) if return_counts else ())
-        return out if len(out) > 1 else idx
+        return self._serve_out(idx, ((sc, return_scores), (cnt, return_counts)), sync,
+                               "row(s) with an anchor outside [-1, %d) or an exclusion id outside [0, %d): their lists are all -1" % (self.n_item, self.n_item))
 
     def _near_anchor(self, anchor, n, default):
         """anchor argument -> (n) int32 device tensor; host arrays are range-checked ([-1, n_item), -1 = no anchor) before any launch."""
@@ -571,12 +587,8 @@ class _Base:
         return tgt.contiguous(), tm.contiguous()
 
     def _rank_out(self, rank, sc, cnt, return_scores, return_counts, sync):
-        if sync:
-            bad = self.ctx.take_bad_ids(self._stream().value)
-            if bad:
-                raise IndexError("%d target(s) outside [0, %d) or row(s) with a malformed exclusion list: their ranks are -1" % (bad, self.n_item))
-        out = (rank,) + ((sc,) if return_scores else ()) + ((cnt,) if return_counts else ())
-        return out if len(out) > 1 else rank
+        return self._serve_out(rank, ((sc, return_scores), (cnt, return_counts)), sync,
+                               "target(s) outside [0, %d) or row(s) with a malformed exclusion list: their ranks are -1" % self.n_item)
 
     def _rank_launch(self, users, items, term, tgt, tm, ex, return_scores, return_counts, sync):
         """One poi_score_rank call -> rank[, scores][, counts] (device tensors)."""
@@ -584,14 +596,8 @@ class _Base:
         rank = torch.empty((n, lt), dtype=torch.int32, device=self.device)
         sc = torch.empty((n, lt), dtype=torch.float32, device=self.device) if return_scores else None
         cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
-        wd = sts = lp = coords = cphi = thr = None
-        n_dist, dd_m = 0, 0.0
-        if term is not None:
-            wd, sts, lp = term
-            coords, cphi, thr, n_dist, dd_m = self.coords, self._cphi, self._binthr, self.n_dist, self.dd * 1000.0
-        self.ctx.check(self.lib.poi_score_rank(self.ctx.handle, _ptr(users), _ptr(items), n, self.n_item, self.kdim, _ptr(wd), _ptr(sts), _ptr(coords),
-                                               _ptr(cphi), _ptr(thr), _ptr(lp), int(n_dist), float(dd_m), _ptr(tgt), _ptr(tm), lt, _ptr(ex[0]), _ptr(ex[1]),
-                                               _ptr(rank), _ptr(sc), _ptr(cnt), self._stream()))
+        self.ctx.check(self.lib.poi_score_rank(self.ctx.handle, *self._tile_operands(users, items, self.kdim, term), _ptr(tgt), _ptr(tm), lt,
+                                               _ptr(ex[0]), _ptr(ex[1]), _ptr(rank), _ptr(sc), _ptr(cnt), self._stream()))
         return self._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
 
     def _rank_score_rows(self, a):
@@ -735,25 +741,15 @@ class _Base:
         return self._near_exclusion(exclude, n_grp, None, kinds=())
 
     def _group_out(self, idx, sc, cnt, return_scores, return_counts, sync):
-        if sync:
-            bad = self.ctx.take_bad_ids(self._stream().value)
-            if bad:
-                raise IndexError("%d group(s) with a member out of range, descending offsets or a malformed exclusion list: their lists are all -1" % bad)
-        out = (idx,) + ((sc,) if return_scores else ()) + ((cnt,) if return_counts else ())
-        return out if len(out) > 1 else idx
+        return self._serve_out(idx, ((sc, return_scores), (cnt, return_counts)), sync,
+                               "group(s) with a member out of range, descending offsets or a malformed exclusion list: their lists are all -1")
 
     def _group_launch(self, users, items, term, g_off, g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync):
         """One poi_group_topk call -> idx[, scores][, counts] (device tensors).  term: (wd, sts rows, last POI rows) or None."""
         idx = torch.empty((n_grp, k), dtype=torch.int32, device=self.device)
         sc = torch.empty((n_grp, k), dtype=torch.float32, device=self.device) if return_scores else None
         cnt = torch.empty(n_grp, dtype=torch.int32, device=self.device) if return_counts else None
-        wd = sts = lp = coords = cphi = thr = None
-        n_dist, dd_m = 0, 0.0
-        if term is not None:
-            wd, sts, lp = term
-            coords, cphi, thr, n_dist, dd_m = self.coords, self._cphi, self._binthr, self.n_dist, self.dd * 1000.0
-        self.ctx.check(self.lib.poi_group_topk(self.ctx.handle, _ptr(users), _ptr(items), users.shape[0], self.n_item, self.kdim, _ptr(wd), _ptr(sts),
-                                               _ptr(coords), _ptr(cphi), _ptr(thr), _ptr(lp), int(n_dist), float(dd_m), _ptr(g_off), _ptr(g_mem), n_grp,
+        self.ctx.check(self.lib.poi_group_topk(self.ctx.handle, *self._tile_operands(users, items, self.kdim, term), _ptr(g_off), _ptr(g_mem), n_grp,
                                                agg, _ptr(ex[0]), _ptr(ex[1]), k, _ptr(idx), _ptr(sc), _ptr(cnt), self._stream()))
         return self._group_out(idx, sc, cnt, return_scores, return_counts, sync)
 
@@ -866,13 +862,8 @@ class _Base:
         return None, 0, coords, cphi
 
     def _diverse_out(self, idx, sc, obj, pool, cnt, return_scores, return_objective, return_pool, return_counts, sync):
-        if sync:
-            bad = self.ctx.take_bad_ids(self._stream().value)
-            if bad:
-                raise IndexError("%d row(s) with a malformed exclusion list or a pool id outside [0, %d): their lists are all -1" % (bad, self.n_item))
-        out = (idx,) + ((sc,) if return_scores else ()) + ((obj,) if return_objective else ()) + ((pool,) if return_pool else ()) \
-            + ((cnt,) if return_counts else ())
-        return out if len(out) > 1 else idx
+        return self._serve_out(idx, ((sc, return_scores), (obj, return_objective), (pool, return_pool), (cnt, return_counts)), sync,
+                               "row(s) with a malformed exclusion list or a pool id outside [0, %d): their lists are all -1" % self.n_item)
 
     def _diverse_buffers(self, n, k, pool, return_scores, return_objective, return_pool, return_counts):
         dev = self.device
@@ -888,17 +879,11 @@ class _Base:
         """One poi_diverse_topk call.  term: (wd, sts rows, last POI rows) or None."""
         n = users.shape[0]
         idx, sc, obj, pl, cnt = self._diverse_buffers(n, k, pool, return_scores, return_objective, return_pool, return_counts)
-        wd = sts = lp = coords = cphi = thr = None
-        n_dist, dd_m = 0, 0.0
-        if term is not None:
-            wd, sts, lp = term
-            coords, cphi, thr, n_dist, dd_m = self.coords, self._cphi, self._binthr, self.n_dist, self.dd * 1000.0
-        if geo_weight > 0.0:
-            coords, cphi, _ = self._near_geo(False)
-        self.ctx.check(self.lib.poi_diverse_topk(self.ctx.handle, _ptr(users), _ptr(items), n, self.n_item, kdim, _ptr(wd), _ptr(sts), _ptr(coords),
-                                                 _ptr(cphi), _ptr(thr), _ptr(lp), int(n_dist), float(dd_m), _ptr(ex[0]), _ptr(ex[1]), pool, k, trade,
-                                                 geo_weight, scale_km, _ptr(idx), _ptr(sc), None, _ptr(obj), _ptr(pl[0]), _ptr(pl[1]), _ptr(cnt),
-                                                 self._stream()))
+        ops = self._tile_operands(users, items, kdim, term)
+        if geo_weight > 0.0:                             # the re-ranking's geographic similarity needs coords / cphi without the term, too
+            ops[7:9] = [_ptr(v) for v in self._near_geo(False)[:2]]
+        self.ctx.check(self.lib.poi_diverse_topk(self.ctx.handle, *ops, _ptr(ex[0]), _ptr(ex[1]), pool, k, trade, geo_weight, scale_km, _ptr(idx),
+                                                 _ptr(sc), None, _ptr(obj), _ptr(pl[0]), _ptr(pl[1]), _ptr(cnt), self._stream()))
         return self._diverse_out(idx, sc, obj, pl, cnt, return_scores, return_objective, return_pool, return_counts, sync)
 
     def _diverse_host_exclusion(self, ex, n):
@@ -1968,14 +1953,10 @@ class Session:
         sc = torch.empty((n, b), dtype=torch.float32, device=m.device)
         lse = torch.empty(n, dtype=torch.float64, device=m.device)
         cnt = torch.empty(n, dtype=torch.int32, device=m.device) if return_counts else None
-        wd = coords = cphi = thr = None
-        n_dist, dd_m = 0, 0.0
-        if sts is not None:
-            wd, coords, cphi, thr, n_dist, dd_m = m.wd.t, m.coords, m._cphi, m._binthr, m.n_dist, m.dd * 1000.0
-        m.ctx.check(m.lib.poi_route_expand(m.ctx.handle, _ptr(users), _ptr(m.trained_items.t), n, m.n_item, users.shape[1], _ptr(wd), _ptr(sts), _ptr(coords),
-                                           _ptr(cphi), _ptr(thr), _ptr(last_poi), int(n_dist), float(dd_m), _ptr(path), path.shape[1] if path is not None else 0,
-                                           int(path_len), _ptr(ex[0]), _ptr(ex[1]), int(rows_per_list), _ptr(live), int(b), _ptr(idx), _ptr(sc), _ptr(lse),
-                                           _ptr(cnt), m._stream()))
+        term = (m.wd.t, sts, last_poi) if sts is not None else None
+        m.ctx.check(m.lib.poi_route_expand(m.ctx.handle, *m._tile_operands(users, m.trained_items.t, users.shape[1], term), _ptr(path),
+                                           path.shape[1] if path is not None else 0, int(path_len), _ptr(ex[0]), _ptr(ex[1]), int(rows_per_list), _ptr(live),
+                                           int(b), _ptr(idx), _ptr(sc), _ptr(lse), _ptr(cnt), m._stream()))
         return (idx, sc, lse, cnt) if return_counts else (idx, sc, lse)
 
     def _route_merge(self, idx, sc, lse, total, n_live, n_slot, n_par, b, return_step_scores=False):

@@ -273,3 +273,88 @@ def test_no_workspace_size_function_remains():
     for fn in os.listdir(csrc):
         if fn.endswith((".hip", ".h")):
             assert "_ws_sizes" not in open(os.path.join(csrc, fn)).read(), fn
+
+
+# ---- the split planner of the serving paths (csrc/split_plan.h): the table the formulas it replaced give -------------------------------
+_PLAN_MAIN = r"""
+#include "split_plan.h"
+#include <stdio.h>
+int main() {
+  int a[9];
+  while (scanf("%d %d %d %d %d %d %d %d %d", a, a + 1, a + 2, a + 3, a + 4, a + 5, a + 6, a + 7, a + 8) == 9) {
+    const SplitPlan p = plan_split(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]);
+    printf("%d %d\n", p.split, p.n_split);
+  }
+  return 0;
+}
+"""
+_INT_MAX = 2 ** 31 - 1
+
+
+def _c_div(a, b):
+    return a // b      # (every operand below is positive: C's division)
+
+
+def _plan_before(family, n, num_cu, n_item, grid):
+    """(path, n_split) as the four entry points spelled the decision out before plan_split, with the default split_max of each; n_split
+    is the kernels' A.n_split: 1 on the other path."""
+    ntile = (n_item + 31) // 32
+    if family == "near":
+        if not n <= 256:
+            return 0, 1
+        s = grid if grid > 0 else _c_div(4 * num_cu, n)
+        if grid <= 0 and s < 2:
+            s = 2
+        return 1, min(s, 64)
+    if family in ("group", "diverse"):
+        if not n <= 256:
+            return 0, 1
+        units = (n + 7) // 8 if family == "group" else (n + 31) // 32
+        s = grid if grid > 0 else _c_div(2 * num_cu, units)
+        if grid <= 0 and s > ntile // 16:
+            s = ntile // 16
+        if grid <= 0 and s < 2:
+            s = 2
+        return 1, min(s, 64)
+    assert family == "route"
+    if not n <= 8192:
+        return 0, 1
+    n_blk = (ntile + 15) // 16
+    s = grid if grid > 0 else _c_div(2 * num_cu, (n + 31) // 32)
+    if grid <= 0 and s > (n_blk + 3) // 4:
+        s = (n_blk + 3) // 4
+    if s < 1:
+        s = 1
+    return 1, min(s, 64)
+
+
+def _plan_call(family, n, num_cu, n_item, grid):
+    """The arguments abi_serve.hip hands plan_split for the same call: rows, units, split_max, grid option, per-CU factor, CUs, cap, floor, limit."""
+    ntile = (n_item + 31) // 32
+    if family == "near":
+        return n, n, 256, grid, 4, num_cu, _INT_MAX, 2, 64
+    if family == "group":
+        return n, (n + 7) // 8, 256, grid, 2, num_cu, ntile // 16, 2, 64
+    if family == "diverse":
+        return n, (n + 31) // 32, 256, grid, 2, num_cu, ntile // 16, 2, 64
+    return n, (n + 31) // 32, 8192, grid, 2, num_cu, ((ntile + 15) // 16 + 3) // 4, 1, 64
+
+
+def test_plan_split_reproduces_the_four_decisions(tmp_path):
+    import shutil
+    import subprocess
+    cxx = shutil.which("c++") or shutil.which("g++") or poi_amd.build._hipcc()
+    src, exe = str(tmp_path / "plan_main.cpp"), str(tmp_path / "plan_main")
+    open(src, "w").write(_PLAN_MAIN)
+    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O1", "-I", _csrc(), src, "-o", exe], check=True)
+    cases = [(f, n, cu, ni, g) for f in ("near", "group", "route", "diverse") for n in (1, 2, 31, 32, 33, 256, 257, 8192, 8193) for cu in (8, 256)
+             for ni in (40, 5000, 200000) for g in (0, 1, 64, 100)]
+    text = "".join("%d %d %d %d %d %d %d %d %d\n" % _plan_call(*c) for c in cases)
+    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
+    got = [tuple(int(v) for v in line.split()) for line in out if line]
+    assert len(got) == len(cases)
+    for c, g in zip(cases, got):
+        assert g == _plan_before(*c), (c, g, _plan_before(*c))
+    # every branch is in the table: both paths, the cap, the floor, the limit, the grid option taken as given
+    want = [_plan_before(*c) for c in cases]
+    assert {w[0] for w in want} == {0, 1} and {1, 2, 64} <= {w[1] for w in want}

@@ -1,6 +1,6 @@
 """Static guard on the diversified recommendation kernels (csrc/diverse.hip): the pool kernel keeps the rows' and the item tile's
 fragments in registers beside the 32 x 32 accumulator, as group_kernel does, and is only worth having while none of that lives in scratch
-memory; the merge and re-rank kernels are held to the same.  Reads every template instance's private segment size and spill count from
+memory; the split path's merge (csrc/topk_merge.hip) and the re-rank kernel are held to the same.  Reads every template instance's private segment size and spill count from
 the library's gfx950 code objects (tools/scan_waits.py, as tests/test_static_group.py does): sizes only, no instruction is searched for.
 Skipped when the ROCm binary tools are not installed."""
 import importlib.util
@@ -16,7 +16,7 @@ scan_waits = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(scan_waits)
 
 KERNELS = (["diverse_pool_kernel<%s, %s>" % (d8, geo) for d8 in ("4, true", "8, true", "16, false", "32, false") for geo in ("true", "false")]
-           + ["diverse_merge_kernel"] + ["diverse_rerank_kernel<%s>" % ge for ge in ("true, true", "true, false", "false, true")])
+           + ["topk_slices_merge_kernel<64>"] + ["diverse_rerank_kernel<%s>" % ge for ge in ("true, true", "true, false", "false, true")])
 
 
 @pytest.fixture(scope="module")
@@ -26,7 +26,7 @@ def found(tmp_path_factory):
     if not scan_waits.available():
         pytest.skip("llvm-objdump / clang-offload-bundler not installed")
     tmp = str(tmp_path_factory.mktemp("scan"))
-    recs = {r["kernel"]: r for r in scan_waits.scan(["diverse_pool_kernel", "diverse_merge_kernel", "diverse_rerank_kernel"], tmp=tmp) if "loop" not in r}
+    recs = {r["kernel"]: r for r in scan_waits.scan(["diverse_pool_kernel", "topk_slices_merge_kernel", "diverse_rerank_kernel"], tmp=tmp) if "loop" not in r}
     scratch = {}
     for co in scan_waits.code_objects(tmp):
         notes = subprocess.run([scan_waits.LLVM + "/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout

@@ -15,7 +15,7 @@ scan_waits = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(scan_waits)
 
 KERNELS = ["group_kernel<%s, %s, %s>" % (d8, geo, big) for d8 in ("4, true", "8, true", "16, false", "32, false") for geo in ("true", "false")
-           for big in ("true", "false")] + ["group_merge_kernel"]
+           for big in ("true", "false")] + ["topk_slices_merge_kernel<32>"]      # (the split path's merge: csrc/topk_merge.hip)
 
 
 @pytest.fixture(scope="module")
@@ -25,7 +25,7 @@ def found(tmp_path_factory):
     if not scan_waits.available():
         pytest.skip("llvm-objdump / clang-offload-bundler not installed")
     tmp = str(tmp_path_factory.mktemp("scan"))
-    recs = {r["kernel"]: r for r in scan_waits.scan(["group_kernel", "group_merge_kernel"], tmp=tmp) if "loop" not in r}
+    recs = {r["kernel"]: r for r in scan_waits.scan(["group_kernel", "topk_slices_merge_kernel"], tmp=tmp) if "loop" not in r}
     scratch = {}
     for co in scan_waits.code_objects(tmp):
         notes = subprocess.run([scan_waits.LLVM + "/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
