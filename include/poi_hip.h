@@ -85,6 +85,9 @@ extern "C" {
 /* additive to 9: diversified recommendation - new entry points poi_diverse_pool, poi_diverse_rerank and poi_diverse_topk, options
  * "diverse_split_max" / "diverse_grid", plan keys "diverse_path" / "diverse_splits" / "diverse_split_max", timing names "diverse_pool" /
  * "diverse_rerank" (existing entries unchanged). */
+/* additive to 9: candidate generation - new entry points poi_score_rows, poi_topk_select and poi_score_candidates, options
+ * "select_split_max" / "select_grid" / "select_chunk_mb", plan keys "select_rows_per_chunk" / "select_chunks" / "select_path" /
+ * "select_splits", timing names "score_rows" / "topk_select" / "score_candidates" (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -172,7 +175,9 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * Additive to 9: "geoie_score_span", "geoie_score_splits" - written by poi_geoie_score_all_geo / poi_geoie_score_topk_geo in the same way.
  * Additive to 9: "group_path", "group_splits", "group_split_max" - written by poi_group_topk in the same way.
  * Additive to 9: "route_path", "route_splits" - written by poi_route_expand in the same way.
- * Additive to 9: "diverse_path", "diverse_splits", "diverse_split_max" - written by poi_diverse_pool / poi_diverse_topk in the same way. */
+ * Additive to 9: "diverse_path", "diverse_splits", "diverse_split_max" - written by poi_diverse_pool / poi_diverse_topk in the same way.
+ * Additive to 9: "select_rows_per_chunk", "select_chunks" - the chunking poi_score_candidates took (rows of score rows held at a time,
+ * number of chunks); "select_path", "select_splits" - written by poi_topk_select / poi_score_candidates in the same way. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -256,7 +261,13 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *   "diverse_split_max" n (default 256): poi_diverse_pool / poi_diverse_topk calls of at most n rows cut the item range of every 32-row tile
  *       into slices, a workgroup each, and merge the slices' lists (0: never); larger calls run one workgroup per tile;
  *   "diverse_grid" n (default 0 = by the row count and the CUs; at most 64): slices on that split path - bitwise the same result for
- *       every n and on either path. */
+ *       every n and on either path.
+ *   "select_split_max" n (default 256): poi_topk_select / poi_score_candidates calls of at most n rows cut each row's id range into
+ *       slices, a workgroup each (0: never); larger calls run one workgroup per row;
+ *   "select_grid" n (default 0 = by the row count and the CUs; at most 64): slices on that split path - bitwise the same result for
+ *       every n and on either path;
+ *   "select_chunk_mb" n (default 1024, at least 1): poi_score_candidates keeps at most n MiB of score rows at a time (a whole number
+ *       of 32-row tiles, at least one) - bitwise the same result for every n. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -1089,6 +1100,61 @@ int poi_diverse_topk(poi_ctx* ctx, const float* users, const float* items, int32
                      int32_t k, double trade, double geo_weight, double scale_km,
                      int32_t* idx_out, float* score_out, int32_t* pos_out, double* obj_out,
                      int32_t* pool_idx, float* pool_score, int32_t* count_out, void* stream);
+
+/* ---- candidate generation (additive to 9): the exact top-K of every row for K up to 4096 ---------------------------------------------------
+ * Every other ranking entry stops at a short list (k <= 32 fused, k <= 64 in poi_topk): each keeps a sorted list with one entry per
+ * lane of a wavefront.  The retrieval stage of a two-stage recommender hands hundreds to thousands of candidates per user to a
+ * downstream ranker, and "recall of the retrieval stage at K" is the number such a system is tuned on.  These entries SELECT (radix
+ * selection over explicit score rows) instead of inserting into a sorted list.
+ *   C(r)          [0, n_item) minus ex[ex_off[r] .. ex_off[r + 1]): the conventions of poi_score_rank / poi_score_topk_near (ascending
+ *                 unique ids; both NULL = none).
+ *   selectable    an entry of C(r) is selectable unless its score is NaN or -inf.  +inf IS selectable, as in poi_score_topk.
+ *   order         the result of row r is the best K' = min(k, |selectable|) entries under the tie rule of every top-K entry: higher
+ *                 score first, then the lower id.  idx_out (n, k) is sorted best first, -1 ids and -inf scores (score_out (n, k) or
+ *                 NULL) behind the K' entries.
+ *   count_out     (n) or NULL: |C(r)|, not clipped to k and not reduced by the scores that are not selectable.
+ *   limits        1 <= k <= min(4096, n_item), otherwise POI_ENOTSUP.
+ *   signed zeros  -0.0 and +0.0 are the SAME score and the id decides - poi_score_rank compares with float > / ==, and the two entries
+ *                 agree on every row.  A selected zero is written to score_out as +0.0 whichever sign it had.  (poi_topk leaves the
+ *                 order of -0.0 against +0.0 unspecified.)
+ *   bad rows      the rule of poi_score_rank: a row whose list is not ascending or leaves [0, n_item) is rejected - all -1 / -inf,
+ *                 count 0, counted once (poi_ctx_take_bad_ids).
+ *   determinism   the selected set follows from integer counts and the order from a total order: identical bits on every grid, in
+ *                 both launch regimes, for any chunking, and for a row alone or in a call of thousands.  No float atomics.
+ *
+ * poi_score_rows writes s(r, j) of poi_score_rank for every pair into scores_out[r * ld + j] (ld >= n_item; the columns beyond n_item
+ * are not written): users[r] . items[j] from the same product routine and k order, with wd non-NULL plus wd * sts[r][bin(last_poi[r], j)]
+ * for bin < n_dist by the same expression; a row with last_poi[r] < 0 has no distance term.  The bits are poi_score_rank's score_out.
+ * users .. dd are poi_score_rank's arguments (items float32 or a registered half table; dim a multiple of 4, <= 256).  A store-epilogue
+ * instance of poi_score_rank's tile walk: unlike poi_score_all it needs no (n, n_item) probability matrix for the distance term.
+ * Timing name: "score_rows".  n = 0 is a no-op.
+ *
+ * poi_topk_select is the definition above on explicit float32 score rows scores (n, ld), the first n_item columns of a row being its
+ * scores: the large-K counterpart of poi_topk for the models whose score is not users . items, and an independent check of the
+ * selection.  Three digit passes (11 / 11 / 10 bits of the order-preserving integer image of the score) count the entries that share
+ * the prefix found so far - per (row, slice) in LDS, summed per row with integer atomic adds - and fix the exact K'-th key; everything
+ * above it is collected in any order, of the entries equal to it exactly the lowest ids; one workgroup per row sorts the K' entries.
+ * Two launch regimes: calls of at most "select_split_max" rows (poi_ctx_set_option, default 256) cut each row's id range into
+ * "select_grid" slices (0: by the row count and the CUs; at most 64), a workgroup each; larger calls run one workgroup per row.
+ * poi_ctx_last_plan: "select_path" (0 row, 1 split), "select_splits" (slices, 0 on the row path).  Timing name: "topk_select" (its
+ * stages: "select_pass0" / "select_pass1" / "select_pass2" / "select_collect" / "select_sort").  n = 0 is a no-op.
+ *
+ * poi_score_candidates runs both with the score rows in a context-owned workspace: a whole number of 32-row tiles at a time, as many
+ * as fit "select_chunk_mb" MiB (default 1024; at least one tile), no host synchronisation between the chunks.  Its output equals
+ * poi_score_rows + poi_topk_select bit for bit, whatever the chunk.  poi_ctx_last_plan: "select_rows_per_chunk", "select_chunks",
+ * "select_path", "select_splits".  Timing name: "score_candidates" (around "score_rows" and "topk_select" of every chunk). */
+int poi_score_rows(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                   const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                   int32_t n_dist, double dd,
+                   float* scores_out, int64_t ld, void* stream);
+int poi_topk_select(poi_ctx* ctx, const float* scores, int32_t n, int32_t n_item, int64_t ld, int32_t k,
+                    const int32_t* ex_off, const int32_t* ex,
+                    int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+int poi_score_candidates(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                         const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                         int32_t n_dist, double dd,
+                         int32_t k, const int32_t* ex_off, const int32_t* ex,
+                         int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
 
 /* ---- fold-in (additive to 9): a user row of OboBpr / OboVBpr for a check-in history the model never trained on -------------------------------
  * The factorisation family's only user representation is a trained row of ux (and ue).  Fold-in freezes the item side and runs the

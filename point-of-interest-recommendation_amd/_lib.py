@@ -186,6 +186,11 @@ SIGNATURES = {
     "poi_diverse_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_int32, c_double, c_void_p, c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_score_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_int32, c_double, c_void_p, c_int64, c_void_p]),
+    "poi_topk_select": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_score_candidates": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int32, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_foldin_bpr": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float, c_float,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_foldin_terms_fpmc": (c_int, [c_void_p, POINTER(FpmcParams), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p]),
@@ -252,7 +257,8 @@ PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", 
              "fork", "hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg", "cell_kernel", "cell_grid", "session_path", "session_tiles", "session_tile_min",
              "near_path", "near_splits", "near_split_max", "rank_splits", "geoie_score_span", "geoie_score_splits",
              "group_path", "group_splits", "group_split_max", "route_path", "route_splits",
-             "diverse_path", "diverse_splits", "diverse_split_max")
+             "diverse_path", "diverse_splits", "diverse_split_max",
+             "select_rows_per_chunk", "select_chunks", "select_path", "select_splits")
 
 
 class Context:
@@ -345,7 +351,8 @@ class Context:
         "early_bins", "hot_bins", "hybrid", "hybrid_min", "hybrid_max", "hybrid_force"; "cell_grid" of poi_cell_step; "session_tile_min" of poi_session_advance;
         "near_split_max" / "near_grid" of poi_score_topk_near; "rank_grid" of poi_score_rank; "geoie_score_span" of
         poi_geoie_score_all_geo / poi_geoie_score_topk_geo; "group_split_max" / "group_grid" of poi_group_topk; "route_split_max" / "route_grid" of
-        poi_route_expand; "diverse_split_max" / "diverse_grid" of poi_diverse_pool / poi_diverse_topk)."""
+        poi_route_expand; "diverse_split_max" / "diverse_grid" of poi_diverse_pool / poi_diverse_topk; "select_split_max" /
+        "select_grid" / "select_chunk_mb" of poi_topk_select / poi_score_candidates)."""
         self.check(self.lib.poi_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def set_small_launch(self, max_sequences=1800):

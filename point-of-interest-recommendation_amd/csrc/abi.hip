@@ -734,7 +734,9 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
                       {"rank_grid", &c->rank_grid, 0, 1 << 30}, {"geoie_score_span", &c->geo_span, 0, 1 << 30},
                       {"group_split_max", &c->group_split_max, 0, 1 << 30}, {"group_grid", &c->group_grid, 0, GROUP_SPLIT_LIMIT},
                       {"route_split_max", &c->route_split_max, 0, 1 << 30}, {"route_grid", &c->route_grid, 0, ROUTE_SPLIT_LIMIT},
-                      {"diverse_split_max", &c->diverse_split_max, 0, 1 << 30}, {"diverse_grid", &c->diverse_grid, 0, DIVERSE_SPLIT_LIMIT}};
+                      {"diverse_split_max", &c->diverse_split_max, 0, 1 << 30}, {"diverse_grid", &c->diverse_grid, 0, DIVERSE_SPLIT_LIMIT},
+                      {"select_split_max", &c->select_split_max, 0, 1 << 30}, {"select_grid", &c->select_grid, 0, SELECT_SPLIT_LIMIT},
+                      {"select_chunk_mb", &c->select_chunk_mb, 1, 1 << 20}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);
@@ -820,7 +822,9 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"group_splits", &poi_ctx::LastPlan::group_splits}, {"group_split_max", &poi_ctx::LastPlan::group_split_max},
       {"route_path", &poi_ctx::LastPlan::route_path}, {"route_splits", &poi_ctx::LastPlan::route_splits},
       {"diverse_path", &poi_ctx::LastPlan::diverse_path}, {"diverse_splits", &poi_ctx::LastPlan::diverse_splits},
-      {"diverse_split_max", &poi_ctx::LastPlan::diverse_split_max}};
+      {"diverse_split_max", &poi_ctx::LastPlan::diverse_split_max},
+      {"select_rows_per_chunk", &poi_ctx::LastPlan::select_rows_per_chunk}, {"select_chunks", &poi_ctx::LastPlan::select_chunks},
+      {"select_path", &poi_ctx::LastPlan::select_path}, {"select_splits", &poi_ctx::LastPlan::select_splits}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

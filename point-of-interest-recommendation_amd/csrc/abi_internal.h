@@ -79,7 +79,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max, select_rows_per_chunk, select_chunks, select_path, select_splits; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR
@@ -125,6 +125,11 @@ struct poi_ctx {
   DevBuf diverse_ws;
   int diverse_split_max = 256; // option "diverse_split_max": poi_diverse_pool calls of at most this many rows cut the item range of every 32-row tile into slices, a workgroup each
   int diverse_grid = 0;     // option "diverse_grid": slices on the split path (0: by the row count and the CUs)
+  // candidate generation (select.hip): the score rows of a chunk (poi_score_candidates); per-row histograms, state and candidate slots
+  DevBuf select_sc, select_ws;
+  int select_split_max = 256; // option "select_split_max": calls of at most this many rows cut each row's id range into slices, a workgroup each
+  int select_grid = 0;      // option "select_grid": slices on the split path (0: by the row count and the CUs)
+  int select_chunk_mb = 1024; // option "select_chunk_mb": poi_score_candidates keeps at most this many MiB of score rows at a time
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)

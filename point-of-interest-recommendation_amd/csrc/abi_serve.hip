@@ -661,6 +661,140 @@ int poi_rank_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// candidate generation (select.hip)
+static int select_check(poi_ctx* c, const char* who, int32_t n, int32_t n_item, int32_t k, const int32_t* ex_off, const int32_t* ex,
+                        const int32_t* idx_out) {
+  if (!idx_out) return fail(c, POI_EINVAL, "%s: NULL idx_out", who);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "%s: n < 0 or n_item <= 0", who);
+  if (k <= 0 || k > SELECT_K_MAX || k > n_item)
+    return fail(c, POI_ENOTSUP, "%s supports 1 <= k <= min(%d, n_item = %d) (got %d)", who, SELECT_K_MAX, n_item, k);
+  return check_ex_pair(c, who, ex_off, ex);
+}
+
+// the slices of a call of n rows: few rows cut each row's id range so that the call fills the CUs (a slice keeps >= 2048 ids)
+static SplitPlan select_plan(const poi_ctx* c, int n, int n_item) {
+  return plan_split(n, n, c->select_split_max, c->select_grid, 4, c->num_cu, n_item / 2048 > 1 ? n_item / 2048 : 1, 1, SELECT_SPLIT_LIMIT);
+}
+
+// the workspace of `per` rows: histograms, state, candidate slots
+static int select_carve(poi_ctx* c, poi::SelectArgs& A, int per, int k, hipStream_t st) {
+  return carve(c, c->select_ws, st, [&](Carver& W) {
+    A.hist = (int*)W.bytes(sizeof(int) * (size_t)per * SELECT_BINS);
+    A.state = (int*)W.bytes(sizeof(int) * (size_t)per * SELECT_STATE_INTS);
+    A.cand = (unsigned long long*)W.bytes(sizeof(unsigned long long) * (size_t)per * k);
+  });
+}
+
+// the selection over score rows that are on the device, SELECT_ROWS_MAX rows per launch sequence; no host synchronisation in between
+static int select_run(poi_ctx* c, const float* scores, int n, int n_item, int64_t ld, int k, const int32_t* ex_off, const int32_t* ex,
+                      int32_t* idx_out, float* score_out, int32_t* count_out, int n_split, int* bad, hipStream_t st) {
+  poi::SelectArgs A = {};
+  A.n_item = n_item; A.ld = ld; A.k = k; A.n_split = n_split; A.ex = ex; A.bad = bad;
+  const int per = n < SELECT_ROWS_MAX ? n : SELECT_ROWS_MAX;
+  if (int rc = select_carve(c, A, per, k, st)) return rc;
+  for (int o = 0; o < n; o += per) {
+    A.n = n - o < per ? n - o : per;
+    A.scores = scores + (size_t)o * (size_t)ld;
+    A.ex_off = ex_off ? ex_off + o : nullptr;
+    A.idx_out = idx_out + (size_t)o * k;
+    A.score_out = score_out ? score_out + (size_t)o * k : nullptr;
+    A.count_out = count_out ? count_out + o : nullptr;
+    HIPCHK(c, poi::launch_select(A, st, &c->tm));
+  }
+  return POI_OK;
+}
+
+static int score_rows_split(const poi_ctx* c, int n, int n_item) {
+  // item ranges per 32-row tile, one wave each: 8 waves per CU over the call, at least 8 tiles per range (poi_score_rank's rule)
+  const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
+  int want = (c->num_cu * 8 + n_utile - 1) / n_utile;
+  if (want > ntile / 8) want = ntile / 8;
+  return want < 1 ? 1 : want;
+}
+
+int poi_score_rows(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                   const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                   float* scores_out, int64_t ld, void* stream) {
+  if (!c || !users || !items || !scores_out) return fail(c, POI_EINVAL, "poi_score_rows: NULL ctx / users / items / scores_out");
+  if (ld < n_item) return fail(c, POI_EINVAL, "poi_score_rows: ld must be >= n_item");
+  hipStream_t st = (hipStream_t)stream;
+  poi::TileOperands T;
+  int rc;
+  if ((rc = tile_operands(c, "poi_score_rows", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, nullptr, nullptr, st, &T))) return rc;
+  if (n == 0) return POI_OK;
+  poi::ScoreRowsArgs A = {};
+  put_operands(A, T);
+  A.out = scores_out; A.ld = ld; A.n_split = score_rows_split(c, n, n_item);
+  HIPCHK(c, poi::launch_score_rows(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_topk_select(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, int64_t ld, int32_t k, const int32_t* ex_off, const int32_t* ex,
+                    int32_t* idx_out, float* score_out, int32_t* count_out, void* stream) {
+  if (!c || !scores) return fail(c, POI_EINVAL, "poi_topk_select: NULL ctx / scores");
+  int rc;
+  if ((rc = select_check(c, "poi_topk_select", n, n_item, k, ex_off, ex, idx_out))) return rc;
+  if (ld < n_item) return fail(c, POI_EINVAL, "poi_topk_select: ld must be >= n_item");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  int* bad;
+  if ((rc = bad_counter(c, st, &bad))) return rc;
+  const SplitPlan sp = select_plan(c, n, n_item);
+  c->plan.valid = 1; c->plan.select_path = sp.split; c->plan.select_splits = sp.split ? sp.n_split : 0;
+  c->plan.select_rows_per_chunk = n; c->plan.select_chunks = 1;
+  const long span = c->tm.span_begin("topk_select", st);
+  rc = select_run(c, scores, n, n_item, ld, k, ex_off, ex, idx_out, score_out, count_out, sp.n_split, bad, st);
+  c->tm.span_end(span, st);
+  return rc;
+}
+
+int poi_score_candidates(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd,
+                         const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist,
+                         double dd, int32_t k, const int32_t* ex_off, const int32_t* ex, int32_t* idx_out, float* score_out, int32_t* count_out,
+                         void* stream) {
+  if (!c || !users || !items) return fail(c, POI_EINVAL, "poi_score_candidates: NULL ctx / users / items");
+  int rc;
+  if ((rc = select_check(c, "poi_score_candidates", n, n_item, k, ex_off, ex, idx_out))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  poi::TileOperands T;
+  if ((rc = tile_operands(c, "poi_score_candidates", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, ex_off, ex, st, &T))) return rc;
+  if (n == 0) return POI_OK;
+  // a whole number of 32-row tiles at a time, as many as fit "select_chunk_mb" (at least one tile)
+  const int64_t ld = ((int64_t)n_item + 31) / 32 * 32;
+  int64_t fit = ((int64_t)c->select_chunk_mb << 20) / (ld * 4) / 32 * 32;
+  if (fit < 32) fit = 32;
+  const int rows = (int)(fit < ((int64_t)n + 31) / 32 * 32 ? fit : ((int64_t)n + 31) / 32 * 32);
+  float* sc_rows = nullptr;
+  if ((rc = carve(c, c->select_sc, st, [&](Carver& W) { sc_rows = (float*)W.bytes(sizeof(float) * (size_t)rows * (size_t)ld); }))) return rc;
+  {                                                 // both workspaces grow (and synchronise) before the first launch, not between chunks
+    poi::SelectArgs S = {};
+    const int top = rows < n ? rows : n;
+    if ((rc = select_carve(c, S, top < SELECT_ROWS_MAX ? top : SELECT_ROWS_MAX, k, st))) return rc;
+  }
+  const SplitPlan sp = select_plan(c, n, n_item);
+  c->plan.valid = 1; c->plan.select_path = sp.split; c->plan.select_splits = sp.split ? sp.n_split : 0;
+  c->plan.select_rows_per_chunk = rows; c->plan.select_chunks = (n + rows - 1) / rows;
+  const long span = c->tm.span_begin("score_candidates", st);
+  for (int o = 0; o < n; o += rows) {
+    const int m = n - o < rows ? n - o : rows;
+    poi::ScoreRowsArgs A = {};
+    put_operands(A, T);
+    A.users = users + (size_t)o * dim; A.n = m;
+    if (wd) { A.sts = sts + (size_t)o * (n_dist + 1); A.last_poi = last_poi + o; }
+    A.out = sc_rows; A.ld = ld; A.n_split = score_rows_split(c, m, n_item);
+    HIPCHK(c, poi::launch_score_rows(A, st, &c->tm));
+    const long sel = c->tm.span_begin("topk_select", st);
+    rc = select_run(c, sc_rows, m, n_item, ld, k, ex_off ? ex_off + o : nullptr, ex, idx_out + (size_t)o * k,
+                    score_out ? score_out + (size_t)o * k : nullptr, count_out ? count_out + o : nullptr, sp.n_split, T.bad, st);
+    c->tm.span_end(sel, st);
+    if (rc) return rc;
+  }
+  c->tm.span_end(span, st);
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // group recommendation (group.hip)
 static int group_check_args(poi_ctx* c, const char* who, int32_t n, int32_t n_item, const int32_t* g_off, const int32_t* g_mem, int32_t n_grp,
                             int32_t agg, const int32_t* ex_off, const int32_t* ex, int32_t k, const int32_t* idx_out) {

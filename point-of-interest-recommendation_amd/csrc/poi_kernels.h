@@ -705,6 +705,31 @@ struct RerankArgs {
 hipError_t launch_diverse_pool(DiverseArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_diverse_rerank(const RerankArgs& A, hipStream_t st, Timing* tm);
 
+// Candidate generation (select.hip): explicit score rows from the tile walk, and the exact top-K of score rows for K up to 4096
+#define SELECT_K_MAX 4096                   // list length: the sort's 4096 x 8 bytes fit one workgroup's LDS
+#define SELECT_SPLIT_LIMIT 64               // slices a row's id range may be cut into
+#define SELECT_BINS 2048                    // histogram bins per row (digits of 11 / 11 / 10 bits)
+#define SELECT_STATE_INTS 8                 // per-row state between the kernels
+#define SELECT_ROWS_MAX 4096                // rows one launch sequence takes (bounds the histogram / candidate workspace)
+struct ScoreRowsArgs {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim;
+  const float *wd, *sts; const double *coords, *cphi, *thr; const int* last_poi; int n_dist; float bin_scale;      // distance term, or wd null
+  const int *ex_off, *ex; int* bad;                           // (the operand block's members: not read)
+  int n_split;                                                // item ranges (one per wave) of a 32-row tile
+  float* out; long long ld;                                   // out[r * ld + j], ld >= n_item
+};
+struct SelectArgs {
+  const float* scores; long long ld; int n, n_item, k;        // (n, ld) float32 score rows, the first n_item of each row are read
+  const int *ex_off, *ex;                                     // per-row exclusion lists (ascending ids), or both null
+  int n_split;                                                // slices of a row's id range, a workgroup each
+  int* hist; int* state; unsigned long long* cand;            // workspace: (n, SELECT_BINS), (n, SELECT_STATE_INTS), (n, k)
+  int* idx_out; float* score_out; int* count_out;             // (n, k); score_out / count_out may be null
+  int* bad;                                                   // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+hipError_t launch_score_rows(const ScoreRowsArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_select(const SelectArgs& A, hipStream_t st, Timing* tm);
+
 // Fold-in of new users for the factorisation family (foldin.hip)
 #define FOLDIN_USERS_PER_WAVE 4             // one 16-lane DPP row per user
 struct FoldinArgs {

@@ -133,6 +133,44 @@ def full_rank_metrics(model, starts_ends_tes, at_nums, exclude=None):
     return _metrics_of_ranks(model, batches, at_nums, model.tes_masks.shape[1], model.n_user)
 
 
+def candidate_recall(model, starts_ends_tes, ks, exclude="train"):
+    """Recall of the retrieval stage: the share of the held-out POIs (tes_buys_masks under tes_masks) that lie inside the top-k
+    candidates of model.compute_sub_candidates, for every k in ks (strictly ascending, 1 <= k <= min(4096, n_item)).  All cut-offs come
+    from ONE call at max(ks): the list is sorted, so the top-k is its first k columns.  exclude as compute_sub_candidates; a held-out POI
+    that is excluded (or lies outside [0, n_item)) is not a candidate and leaves the mean, as in full_rank_metrics - whose recall at
+    the same cut-offs this equals.  Returns {k: recall}; the reductions are torch ops on the device."""
+    import torch
+    ks = [int(k) for k in ks]
+    if not ks or any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] <= 0:
+        raise ValueError("ks must be strictly ascending cut-offs >= 1 (got %r)" % (ks,))
+    N = model.n_item
+    hits = torch.zeros(len(ks), dtype=torch.float64, device=model.device)
+    total = torch.zeros((), dtype=torch.float64, device=model.device)
+    for se in coalesce_ranges(starts_ends_tes):
+        idx = model.compute_sub_candidates(se, ks[-1], exclude=exclude)
+        ids, lo = model._ids(se)
+        n = ids.numel()
+        tgt = model._rows(model.tes_buys_masks, ids, lo).long()
+        ok = (model._rows(model.tes_masks, ids, lo) != 0) & (tgt >= 0) & (tgt < N)
+        eo, ex = model._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+        if eo is not None and n:                                     # a target on its row's list: sorted keys row * n_item + id
+            eo = eo.long()
+            rows = torch.repeat_interleave(torch.arange(n, device=model.device), eo[1:] - eo[:-1])
+            keys = rows * N + ex[int(eo[0]):int(eo[-1])].long()
+            want = torch.arange(n, device=model.device)[:, None] * N + tgt.clamp(0, N - 1)
+            at = torch.searchsorted(keys, want.reshape(-1)).clamp(max=max(keys.numel() - 1, 0)).reshape(want.shape)
+            ok &= ~((keys[at] == want) if keys.numel() else torch.zeros_like(ok))
+        total += ok.sum()
+        for o in range(0, n, 2048):                                  # (rows, targets, k) comparisons, 2048 rows at a time
+            eq = idx[o:o + 2048, None, :] == tgt[o:o + 2048, :, None].int()
+            found = eq.any(2) & ok[o:o + 2048]
+            pos = eq.int().argmax(2)
+            for i, k in enumerate(ks):
+                hits[i] += (found & (pos < k)).sum()
+    h, t = hits.cpu().numpy(), float(total.item())
+    return {k: (float(h[i]) / t if t else 0.0) for i, k in enumerate(ks)}
+
+
 def foldin_rank_metrics(model, histories, targets, at_nums, exclude="history", **fold_in_kwargs):
     """full_rank_metrics for HELD-OUT users of the factorisation family, of the successive-POI models OboFpmc_lr / OboPrme and of
     OboPoi2vec (strong generalisation): every history is folded in (model.rank_new: fold_in, then the exact rank of its targets among all POIs) and the

@@ -684,6 +684,77 @@ class _Base:
         return self._rank_launch(users, items, self._rank_term(ids, lo), tgt, tm, ex, return_scores, return_counts, sync)
 
 
+    # ---- candidate generation (poi_score_candidates / poi_topk_select): the exact top-K of every row for K up to 4096 ----------------------
+    CANDIDATES_K_MAX = 4096
+
+    def _candidates_k(self, k):
+        k = int(k)
+        if not 1 <= k <= min(self.CANDIDATES_K_MAX, self.n_item):
+            raise ValueError("candidate generation supports 1 <= k <= min(%d, n_item = %d) (got %d)" % (self.CANDIDATES_K_MAX, self.n_item, k))
+        return k
+
+    def _candidates_buffers(self, n, k, return_scores, return_counts):
+        idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        return idx, sc, cnt
+
+    def _candidates_out(self, idx, sc, cnt, return_scores, return_counts, sync):
+        return self._serve_out(idx, ((sc, return_scores), (cnt, return_counts)), sync,
+                               "row(s) with a malformed exclusion list: their candidate lists are all -1")
+
+    def _candidates_launch(self, users, items, term, ex, k, return_scores, return_counts, sync):
+        """One poi_score_candidates call -> idx[, scores][, counts] (device tensors).  term: (wd, sts rows, last POI rows) or None."""
+        n = users.shape[0]
+        idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
+        if n:
+            self.ctx.check(self.lib.poi_score_candidates(self.ctx.handle, *self._tile_operands(users, items, self.kdim, term), k, _ptr(ex[0]), _ptr(ex[1]),
+                                                         _ptr(idx), _ptr(sc), _ptr(cnt), self._stream()))
+        return self._candidates_out(idx, sc, cnt, return_scores, return_counts, sync and n > 0)
+
+    def _candidates_from_scores(self, score_rows, n, ex, k, return_scores, return_counts, sync):
+        """Explicit score rows, a bounded number of rows at a time, + poi_topk_select, which takes the exclusion lists itself (the rows
+        are not masked on the host).  score_rows(o, c) -> (c, n_item) float32 scores of rows o .. o + c - 1."""
+        N = self.n_item
+        idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
+        at = lambda t, o, w: ctypes.c_void_p(t.data_ptr() + 4 * o * w) if t is not None else None
+        step = self._rank_chunk(max(n, 1))
+        for o in range(0, n, step):
+            c = min(step, n - o)
+            full = score_rows(o, c).contiguous()
+            self.ctx.check(self.lib.poi_topk_select(self.ctx.handle, _ptr(full), c, N, N, k, at(ex[0], o, 1), _ptr(ex[1]), at(idx, o, k), at(sc, o, k),
+                                                    at(cnt, o, 1), self._stream()))
+        return self._candidates_out(idx, sc, cnt, return_scores, return_counts, sync and n > 0)
+
+    def compute_sub_candidates(self, start_end, k, exclude=None, return_scores=False, return_counts=False, sync=True):
+        """CANDIDATE GENERATION (include/poi_hip.h, poi_score_candidates): the exact top-k of every row under the model's own score for
+        1 <= k <= min(4096, n_item) - the hand-over of a retrieval stage to a downstream ranker, where compute_sub_topk stops at a short
+        list.  exclude: None, "train" (the user's distinct train POIs) or CSR lists (off, ids), ids ascending and unique per row.
+        Returns (n, k) int32 ids on the device by descending score, ties by ascending id (-0.0 and +0.0 are one score), -1 where a row
+        has fewer than k selectable POIs (NaN and -inf scores are never selected; scores -inf); with return_scores the scores, with
+        return_counts the candidate count of every row.  The models that score by users . items make one fused call (the score rows
+        live in a bounded workspace of the context, option "select_chunk_mb"); CA-RNN, PRME, POI2Vec and GeoIE under rule="geo" go
+        through their own score rows, a bounded number at a time, and poi_topk_select.  Host arguments are checked before the launch
+        (ValueError / IndexError); device lists are checked by the kernel: an offending row comes out all -1 and - with sync - raises
+        IndexError."""
+        k = self._candidates_k(k)
+        if not self._rank_fused:
+            a = start_end if isinstance(start_end, torch.Tensor) else np.atleast_1d(np.asarray(start_end))
+            n = len(a)
+            ids, lo = self._ids(a)
+            ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+
+            def score_rows(o, c):
+                full, per = self._rank_score_rows(a[o:o + c])
+                return full.view(c, per, self.n_item)[:, 0] if per > 1 else full      # (user, position) rows: the user's next POI is position 0
+            return self._candidates_from_scores(score_rows, n, ex, k, return_scores, return_counts, sync)
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+        items = self._items() if hasattr(self, "_items") else self.trained_items.t
+        return self._candidates_launch(users.contiguous(), items, self._rank_term(ids, lo), ex, k, return_scores, return_counts, sync)
+
+
     # ---- group recommendation (poi_group_topk / poi_group_topk_scores): the top-K of an aggregate of the members' scores ---------------
     _GROUP_AGG = {"mean": 0, "min": 1}
 
@@ -1885,6 +1956,24 @@ class Session:
         return m._rank_launch(users, m.trained_items.t, term, tgt, tm, ex, return_scores, return_counts, sync)
 
 
+    def candidates(self, slots, k, exclude=None, return_scores=False, return_counts=False, sync=True):
+        """model.compute_sub_candidates over the slots' CURRENT states (h, sts, last_poi, as `rank_of` assembles them): the exact top-k
+        of every slot for 1 <= k <= min(4096, n_item).  exclude: None, "last" or CSR lists (off, ids).  A slot without a check-in has no
+        distance term."""
+        m = self.m
+        k = m._candidates_k(k)
+        ids = self._slot_tensor(slots)
+        n = ids.numel()
+        users = self.h.index_select(0, ids).float().contiguous()
+        lpr = self.last_poi.index_select(0, ids).contiguous()
+        term = None
+        if self.spatial:
+            st = (self.sts.index_select(0, ids) * (lpr >= 0).float()[:, None]).contiguous()
+            st[:, m.n_dist] = 0.0
+            term = (m.wd.t, st, lpr)
+        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
+        return m._candidates_launch(users, m.trained_items.t, term, ex, k, return_scores, return_counts, sync)
+
     def recommend_group(self, slot_groups, k, agg="mean", exclude=None, return_scores=False, return_counts=False, sync=True):
         """model.recommend_group over the slots' CURRENT states (h, sts, last_poi, as `rank_of` assembles them): slot_groups is a list of
         lists of slot ids or a CSR pair (off, ids); agg "mean" or "min"; exclude None or CSR lists (off, ids), one per group.  A slot
@@ -2187,6 +2276,27 @@ class CellSession(Session):
             return torch.where(has[o:o + c, None], full, torch.full_like(full, float("-inf")))      # no check-in: nothing is pooled
         out = m._diverse_from_scores(score_rows, n, ex, sim, k, pool, trade, geo_weight, scale_km, return_scores, return_objective, return_pool,
                                      True, sync)
+        out = list(out) if isinstance(out, tuple) else [out]
+        out[-1] = torch.where(has, out[-1], torch.zeros_like(out[-1]))
+        if not return_counts:
+            out.pop()
+        return tuple(out) if len(out) > 1 else out[0]
+
+    def candidates(self, slots, k, exclude=None, return_scores=False, return_counts=False, sync=True):
+        """Lstm / Rnn: `Session.candidates`' plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi +
+        poi_topk_select; a slot without a check-in gives -1 ids (count 0)."""
+        if not self.carnn:
+            return super().candidates(slots, k, exclude, return_scores, return_counts, sync)
+        m = self.m
+        k = m._candidates_k(k)
+        n, users, lp, has = self._carnn_rows(slots)
+        lpr = torch.where(has, lp, torch.full_like(lp, -1))
+        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
+
+        def score_rows(o, c):
+            full = self._carnn_scores(users, lp, o, c)
+            return torch.where(has[o:o + c, None], full, torch.full_like(full, float("-inf")))      # no check-in: nothing is selectable
+        out = m._candidates_from_scores(score_rows, n, ex, k, return_scores, True, sync)
         out = list(out) if isinstance(out, tuple) else [out]
         out[-1] = torch.where(has, out[-1], torch.zeros_like(out[-1]))
         if not return_counts:
