@@ -177,7 +177,10 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * Additive to 9: "route_path", "route_splits" - written by poi_route_expand in the same way.
  * Additive to 9: "diverse_path", "diverse_splits", "diverse_split_max" - written by poi_diverse_pool / poi_diverse_topk in the same way.
  * Additive to 9: "select_rows_per_chunk", "select_chunks" - the chunking poi_score_candidates took (rows of score rows held at a time,
- * number of chunks); "select_path", "select_splits" - written by poi_topk_select / poi_score_candidates in the same way. */
+ * number of chunks); "select_path", "select_splits" - written by poi_topk_select / poi_score_candidates in the same way.
+ * Additive to 9: "xfwd_ids_lds" - 1 when the launch took the table form of the exact forward recurrence with its row ids staged in LDS
+ * (option of the same name), 0 with the ids loaded inside the step loop or without the table form; poi_gru_predict records its own value
+ * of this one key. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -226,6 +229,10 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *   "forward_table_compact" 0|1 (default 1): the exact forward pass forms its float64 input table over the POIs that are step inputs
  *       of the launch only (ranked on the device) instead of over every row of the POI table - bitwise the same update;
  *   "forward_table_compact_min" n (default 1536): ... for launches of at least n sequences;
+ *   "xfwd_ids_lds" 0|1 (default 1): the table-form recurrences of the exact forward pass (forward table / compact table: te_rec_fwdxi, te_rec_fwddi,
+ *       te_rec_fwd1xi) stage the table-row ids of their sequences' steps in LDS once per tile / sequence instead of loading them inside the step
+ *       loop, where the wait for them also drained the step's stores - bitwise the same update; 0, or an id table that does not fit the
+ *       kernel's LDS (16-sequence tiles at dim 128: more than 133 steps), takes the in-loop loads;
  *   "head_split" 0|1 (default 1): the training head (public/GRU_Spatial.py:180-200, <= 256 bins) on bf16 split products (te_head3)
  *       instead of float32-input matrix instructions;
  *   "early_bins" 0|1 (default 1): the distance-bin rows' write-back chain starts next to the d x product instead of at the tail;

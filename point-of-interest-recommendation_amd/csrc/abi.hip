@@ -124,6 +124,7 @@ int poi_ctx_create(poi_ctx** out, int device) {
   if (const char* e = getenv("POI_TE_HEAD3")) c->head3 = atoi(e) != 0;
   if (const char* e = getenv("POI_TE_EFUSE")) c->efuse = atoi(e) != 0;
   if (const char* e = getenv("POI_TE_XCOMP")) c->xcomp = atoi(e) != 0;
+  if (const char* e = getenv("POI_TE_XIDS_LDS")) c->xids_lds = atoi(e) != 0;
   if (const char* e = getenv("POI_TE_XCOMP_MIN")) c->xcomp_min = atoi(e);
   if (const char* e = getenv("POI_TE_REC1")) c->rec1_max = atoi(e);
   if (const char* e = getenv("POI_TE_ONE")) c->one_path = atoi(e) != 0;
@@ -274,6 +275,8 @@ static int te_setup(poi_ctx* c, poi::TeArgs& A, const poi_gru_params* P, const p
     const size_t frag = (size_t)3 * D * D * 5, nz = (size_t)(spatial ? n_dist + 1 : 1) * 3 * D;      // five int8 digit planes per weight
     if ((rc = ensure(c, c->xw, 2 * frag + 64 + sizeof(double) * (6 * (size_t)D + nz + 8) + 64, st))) return rc;
     A.xcomp = (A.xft && want_xc) ? 1 : 0;
+    // (the ids of a sequence's steps in LDS: the step capacity Tcap was sized with; 0 - in-loop loads - when switched off or when the table does not fit)
+    A.xid_cap = (A.xft && c->xids_lds) ? poi::te_xfwd_ids_cap(D, predict ? T->max_len : (T->max_len > 1 ? T->max_len - 1 : 1), A.xrec1 != 0) : 0;
     const size_t xrows = A.xcomp ? std::min((size_t)P->n_item + 1, Tcap) + 2 : A.xft ? (size_t)P->n_item + 1 + 2 : Tcap;
     if ((rc = ensure(c, c->xg, sizeof(double) * xrows * 3 * D, st))) return rc;
     char* xp = (char*)c->xw.p;
@@ -462,7 +465,7 @@ static int seq_step(poi_ctx* c, const poi_gru_params* P, const poi_seq_tables* T
     {
       poi_ctx::LastPlan& R = c->plan;
       R.tile = 1; R.one = one; R.rec1 = E.rec1; R.xrec1 = E.xrec1; R.hyb = E.hyb; R.bintab = E.bintab; R.ppoi = E.ppoi; R.listed = E.urow != nullptr;
-      R.fwd_tab = E.fwd_tab; R.xft = E.xft; R.xcomp = E.xcomp; R.head_split = E.head_split; R.efuse = one ? 0 : E.efuse; R.early_bins = E.early_bins;
+      R.fwd_tab = E.fwd_tab; R.xft = E.xft; R.xcomp = E.xcomp; R.xfwd_ids_lds = E.xid_cap > 0; R.head_split = E.head_split; R.efuse = one ? 0 : E.efuse; R.early_bins = E.early_bins;
       R.hyb_dev = E.hyb_dev; R.st = st; R.ws_gen = c->te_ws_gen;      // (fork: launch_te_scatter)
     }
     // captured: a replay re-issues the launch id this launch got when it was captured - atomicMax against whatever a LATER launch left in xflag
@@ -507,7 +510,7 @@ static int seq_step(poi_ctx* c, const poi_gru_params* P, const poi_seq_tables* T
       // word they overlapped and early_min was missing), plus what te_setup derived from them for THIS launch
       const uint64_t sw[] = {(uint64_t)c->fwd_tab, (uint64_t)c->rec_split, (uint64_t)c->one_path, (uint64_t)(unsigned)c->rec1_max, (uint64_t)(unsigned)c->bintab_min,
                              (uint64_t)c->early_bins, (uint64_t)(unsigned)c->early_min, (uint64_t)c->xfwd, (uint64_t)E.early_bins, (uint64_t)E.bintab, (uint64_t)E.rec1,
-                             (uint64_t)E.fwd_tab, (uint64_t)E.xfwd, (uint64_t)E.xft, (uint64_t)E.xrec1, (uint64_t)E.xcomp, (uint64_t)(unsigned)c->xcomp_min, (uint64_t)E.head_split, (uint64_t)(unsigned)c->xrec1_max, (uint64_t)E.ppoi, (uint64_t)one, (uint64_t)E.hyb, (uint64_t)E.efuse, (uint64_t)E.hot_early};
+                             (uint64_t)E.fwd_tab, (uint64_t)E.xfwd, (uint64_t)E.xft, (uint64_t)E.xrec1, (uint64_t)E.xcomp, (uint64_t)(unsigned)E.xid_cap, (uint64_t)(unsigned)c->xcomp_min, (uint64_t)E.head_split, (uint64_t)(unsigned)c->xrec1_max, (uint64_t)E.ppoi, (uint64_t)one, (uint64_t)E.hyb, (uint64_t)E.efuse, (uint64_t)E.hot_early};
       add(sw, sizeof sw);
     }
     poi_ctx::StepGraph* g = nullptr;
@@ -583,6 +586,7 @@ int poi_gru_predict(poi_ctx* c, const poi_gru_params* P, const poi_seq_tables* T
     poi::TeArgs E;
     if ((rc = te_setup(c, E, P, T, uidx, n, true, spatial, (hipStream_t)stream))) return rc;
     E.hts = hts; E.sts = sts; E.out_row = out_row;
+    c->plan.valid = 1; c->plan.xfwd_ids_lds = E.xid_cap > 0;      // (the one plan value a predict launch records)
     HIPCHK(c, poi::launch_te_predict(E, c->num_cu, (hipStream_t)stream, &c->tm));
     return POI_OK;
   }
@@ -727,7 +731,7 @@ int poi_ctx_set_exact_forward(poi_ctx* c, int on, int per_sequence_max) {
 int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
   if (!c || !name) return fail(c, POI_EINVAL, "poi_ctx_set_option: null argument");
   struct Opt { const char* name; int* p; int lo, hi; };
-  const Opt opts[] = {{"forward_table_compact", &c->xcomp, 0, 1}, {"forward_table_compact_min", &c->xcomp_min, 0, 1 << 30}, {"head_split", &c->head3, 0, 1},
+  const Opt opts[] = {{"forward_table_compact", &c->xcomp, 0, 1}, {"forward_table_compact_min", &c->xcomp_min, 0, 1 << 30}, {"xfwd_ids_lds", &c->xids_lds, 0, 1}, {"head_split", &c->head3, 0, 1},
                       {"early_bins", &c->early_bins, 0, 1}, {"hot_bins", &c->hot_bins, 0, 1}, {"hybrid", &c->hybrid, 0, 1}, {"hybrid_min", &c->hyb_min, 0, 1 << 30}, {"hybrid_max", &c->hyb_max, 0, 1 << 30}, {"hybrid_force", &c->hyb_force, 0, 1 << 30},
                       {"cell_grid", &c->cell_grid, 0, 1 << 30}, {"vbpr_grid", &c->vbpr_grid, 0, 1 << 30}, {"session_tile_min", &c->sess_tile_min, 1, 1 << 30},
                       {"near_split_max", &c->near_split_max, 0, 1 << 30}, {"near_grid", &c->near_grid, 0, NEAR_SPLIT_LIMIT},
@@ -811,7 +815,7 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
   static const struct { const char* name; int poi_ctx::LastPlan::*f; } flags[] = {
       {"tile", &poi_ctx::LastPlan::tile}, {"one", &poi_ctx::LastPlan::one}, {"rec1", &poi_ctx::LastPlan::rec1}, {"xrec1", &poi_ctx::LastPlan::xrec1},
       {"hyb", &poi_ctx::LastPlan::hyb}, {"bintab", &poi_ctx::LastPlan::bintab}, {"ppoi", &poi_ctx::LastPlan::ppoi}, {"listed", &poi_ctx::LastPlan::listed},
-      {"fwd_tab", &poi_ctx::LastPlan::fwd_tab}, {"xft", &poi_ctx::LastPlan::xft}, {"xcomp", &poi_ctx::LastPlan::xcomp},
+      {"fwd_tab", &poi_ctx::LastPlan::fwd_tab}, {"xft", &poi_ctx::LastPlan::xft}, {"xcomp", &poi_ctx::LastPlan::xcomp}, {"xfwd_ids_lds", &poi_ctx::LastPlan::xfwd_ids_lds},
       {"head_split", &poi_ctx::LastPlan::head_split}, {"efuse", &poi_ctx::LastPlan::efuse}, {"early_bins", &poi_ctx::LastPlan::early_bins},
       {"fork", &poi_ctx::LastPlan::fork}, {"cell_kernel", &poi_ctx::LastPlan::cell_kernel}, {"cell_grid", &poi_ctx::LastPlan::cell_grid},
       {"session_path", &poi_ctx::LastPlan::session_path}, {"session_tiles", &poi_ctx::LastPlan::session_tiles},

@@ -61,6 +61,7 @@ struct poi_ctx {
   int xfwd = 1;             // exact forward (te_xfwd.hip: fixed point on the int8 matrix cores / float64 MFMA + float64 gates) for dims 64 / 128 / 256; POI_TE_XFWD=0 / poi_ctx_set_exact_forward
   int xcomp = 1;            // exact forward table over the step-input POIs only; POI_TE_XCOMP=0: every row of the POI table (A/B)
   int xcomp_min = 1536;     // ... for launches of at least this many sequences (below: one row per step - the table form of te_rec_fwdx costs 0.6 us more per step of the latency chain than the ranking saves in te_gemmx; 1300 / 1563 / 2048 / 3125 users: +9 / -6 / -38 / -45 us); POI_TE_XCOMP_MIN
+  int xids_lds = 1;         // option "xfwd_ids_lds": the table-form recurrences of the exact forward stage their table-row ids in LDS (TeArgs.xid_cap) instead of loading them inside the step loop; POI_TE_XIDS_LDS=0 (A/B)
   int efuse = 1;            // E = lt[p'] - lt[q'] gathered inside te_head3 (dim 128) instead of written by te_gather and read back twice; POI_TE_EFUSE
   int head3 = 1;            // training head on split products for <= 256 bins (te_head3); POI_TE_HEAD3
   int xrec1_max = 1100;     // ... launches of at most this many sequences run its recurrence per sequence in float64 on the vector ALUs (te_rec_fwd1x); POI_TE_XREC1
@@ -79,7 +80,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max, select_rows_per_chunk, select_chunks, select_path, select_splits; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, xfwd_ids_lds, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max, select_rows_per_chunk, select_chunks, select_path, select_splits; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR

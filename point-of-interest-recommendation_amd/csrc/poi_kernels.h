@@ -207,6 +207,7 @@ struct TeArgs {
   int2* row_pq;
   int xrec1;                          // the recurrence of every sequence in its own workgroup on the float64 vector ALUs (te_rec_fwd1x): small launches
   int xfwd, xft;                      // on; pre-activations from the forward table ptabx[p_t] + ztabx[dp_t] (else gx[row])
+  int xid_cap;                        // xft: the recurrence stages the table-row ids of its sequences' steps in LDS, xid_cap steps per sequence (0: it loads them inside the step loop); te_xfwd_ids_cap
   double *gx, *ptabx, *ztabx;         // (T + spare) x 3D per step | (n_item + 1 + spare) x 3D | (n_dist + 1) x 3D, gate-major columns (g D + unit)
   uint4 *xWh8, *xUi8; double *xWhS, *xUiS;      // digit fragments + row scales of wh (16x16x64 order) and of ui's POI half (32x32x32 order)
   int x_rows_est;                     // host-side bound of the packed row count (grid sizing of te_gemmx)
@@ -250,6 +251,7 @@ bool te_one_supported(int D, bool spatial, int max_len);
 hipError_t launch_te_train(TeArgs& A, int num_cu, hipStream_t st, Timing* tm);
 hipError_t launch_te_predict(TeArgs& A, int num_cu, hipStream_t st, Timing* tm);
 bool te_xfwd_supported(int D);
+int te_xfwd_ids_cap(int D, int steps, bool per_sequence);      // TeArgs.xid_cap for sequences of at most `steps` steps: steps + 1, or 0 when the id table does not fit the kernel's LDS
 hipError_t launch_te_xfwd(const TeArgs& A, int num_cu, hipStream_t st, Timing* tm, int phase);      // te_xfwd.hip: phase 0 = input product, 1 = recurrence
 hipError_t launch_rows_apply(const SeqArgs& A, bool spatial, int grid, float alpha, float lambda, hipStream_t st, Timing* tm);
 hipError_t launch_dense_apply(const SeqArgs& A, bool spatial, int n_slab, int n_slab_head, float alpha, float lambda, hipStream_t st, Timing* tm);

@@ -33,6 +33,7 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 
 #define XS 5                       // signed base-256 digits per operand
 #define XQB (8 * XS - 2)           // |Q| <= 2^XQB: the leading digit stays inside [-64, 64] (+ carry)
+#define X1_ID_CAP 512              // te_rec_fwd1xi: steps of its (static) id list in LDS
 
 __device__ __forceinline__ double x_pow2(int e) { return __longlong_as_double((long long)(1023 + e) << 52); }
 // exponent e with |m| < 2^e (m = 0 and subnormals: -126)
@@ -360,9 +361,19 @@ __device__ unsigned long long g_xprof[8][10];
 // columns, 96 bytes per lane, made every 16-byte load instruction of a wave touch 48 lines: the kernel was bound by the address path.)
 struct XG12 { double v[12]; };
 
-template <int D, bool FT, bool PRED = false>      // PRED: poi_gru_predict - all L positions, no per-step stores, the final state -> hts
-__global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel(TeArgs A) {
+// IDL (FT only; TeArgs.xid_cap steps): the table-row ids of the tile's steps are staged ONCE into LDS behind the digit planes and the low
+// fragments - s_id[t * 16 + q] = {POI row, bin row, packed row} of step t of sequence q, the ids clamped as rows() clamps them, the spare
+// row and its ids past the sequence's end - and the step loop reads the ids of step t + 1 and the packed row of step t from there (the
+// packed row in the table frees the two registers of the sequence's first row and length: the loop has none to spare).
+// With the ids loaded from memory inside the loop (IDL = false: option "xfwd_ids_lds" 0, or a table that does not fit the LDS opt-in) the
+// loop header is `s_waitcnt vmcnt(0)`: the id loads sit behind the A.spatial branch, the compiler merges the counter state of the two arms
+// and of the peeled first step pessimistically, and the write acknowledgement of the step's five 16-byte stores stands in front of the next
+// step's table-row loads (rule 2).  Without a vector-memory result at the loop top every wait of the loop is counted and the
+// stores stay in flight across the step boundary.
+template <int D, bool FT, bool PRED, bool IDL>      // PRED: poi_gru_predict - all L positions, no per-step stores, the final state -> hts
+__device__ __forceinline__ void te_rec_fwdx_body(const TeArgs& A) {
   constexpr int KB = D / 64, NW = D / 16, SR = 3, SL = XS - SR, LDP = D + 16, PSZ = 16 * LDP;
+  static_assert(FT || !IDL, "te_rec_fwdx: the per-step-row form has no ids");
   static_assert(D <= 128 && D % 64 == 0, "te_rec_fwdx: resident digit fragments and x_combine's int32 merge are sized for K <= 128");
   extern __shared__ __align__(16) unsigned char xlds[];
   unsigned char* Hq = xlds;                          // XS planes x 16 rows x LDP bytes
@@ -385,6 +396,25 @@ __global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel(TeArgs A) {
   if (tid >= 64 && tid < 128) s_t64[tid - 64] = exp2((double)(tid - 64) * (1.0 / 64.0));
   for (int e = tid; e < 3 * D; e += blockDim.x) s_cn[e] = A.xWhS[e] * 0x1p-8;
   for (int e = tid; e < 2 * XS * PSZ / 4; e += blockDim.x) reinterpret_cast<unsigned*>(xlds)[e] = 0u;      // h_0 = 0: all digits zero
+  // IDL: D / 4 threads per sequence stage its ids, coalesced along the steps.  The first two passes (64 steps at dim 128) are requested
+  // here, in front of the weight fragments, and land in LDS behind them: one load latency per tile instead of two.
+  constexpr int TPS = D / 4;
+  int4* const s_id = reinterpret_cast<int4*>(xlds + 2 * XS * PSZ + (size_t)NW * 3 * KB * SL * 64 * 16);
+  const int id_q = tid / TPS, id_t = tid % TPS, id_cap = A.xid_cap;
+  int id_r0 = 0, id_ns = 0;
+  const int id_sp = IDL ? A.soff[A.n_seq] : 0;       // (the spare packed row)
+  auto id_of = [&](int t) {
+    const int* __restrict__ xrow = A.xcomp ? A.row_pc : A.row_p;      // (compact table: te_gather translated the ids)
+    const int rr = t < id_ns ? id_r0 + t : id_sp;
+    return make_int4((int)min((unsigned)xrow[rr], (unsigned)A.n_item), A.spatial ? (int)min((unsigned)A.row_dp[rr], (unsigned)A.n_dist) : 0, rr, 0);
+  };
+  int4 id_pre[2] = {make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0)};
+  if constexpr (IDL) {
+    const int k = k_lo + tile * 16 + id_q;
+    if (k < A.n_seq) { id_r0 = A.soff[k]; id_ns = A.soff[k + 1] - id_r0; }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) id_pre[j] = id_of(id_t + j * TPS);
+  }
   i32x4 bw[3][KB][SR];
 #pragma unroll
   for (int gt = 0; gt < 3; ++gt) {
@@ -398,9 +428,16 @@ __global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel(TeArgs A) {
         else Bl[((gt * KB + kb) * SL + (s - SR)) * 64 + lane] = v;
       }
   }
+  if constexpr (IDL) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      if (id_t + j * TPS < id_cap) s_id[(id_t + j * TPS) * 16 + id_q] = id_pre[j];
+    for (int t = id_t + 2 * TPS; t < id_cap; t += TPS) s_id[t * 16 + id_q] = id_of(t);
+  }
   __syncthreads();
   int ns_max = 0;
   for (int q = 0; q < 16; ++q) ns_max = max(ns_max, s_ns[q]);
+  if constexpr (IDL) ns_max = min(ns_max, id_cap - 1);      // (te_xfwd_ids_cap: never the smaller - the loop reads the entry of step t + 1 unclamped)
   const int rowb = s_r0[i], nsr = s_ns[i];
   const int Tsp = A.soff[A.n_seq];                   // spare packed row: finished sequences read / write it unconditionally
   // (a launch whose weights / input rows hold a NaN or inf - x_flag_bad - starts from h_0 = NaN: the digits of a state cannot carry it)
@@ -457,10 +494,13 @@ __global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel(TeArgs A) {
   };
   // one step: z | r products (they share the state's digit fragments: one LDS read) -> r gate, r * h digits -> barrier -> c products,
   // z gate (off the chain: behind the c products' issue), c gate, h, h digits -> barrier
+  const int* const idp = reinterpret_cast<const int*>(s_id + i);      // IDL: this lane's sequence in the id table, 64 ints per step
   auto compute = [&](int t) {
     i32x4 azr[2][XS], ac[1][XS];
-    const bool on = t < nsr;
-    const size_t row = (size_t)(on ? rowb + t : Tsp);
+    bool on;
+    size_t row;      // the step's packed row, the spare one when the sequence has ended
+    if constexpr (IDL) { const int r = idp[t * 64 + 2]; on = r != Tsp; row = (size_t)r; }
+    else { on = t < nsr; row = (size_t)(on ? rowb + t : Tsp); }
     XP(0)
     mma(azr, hrow, 0, std::integral_constant<int, 2>());
     XP(1)
@@ -520,6 +560,30 @@ __global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel(TeArgs A) {
         gc.v[q] = nx.v[q];
       }
     }
+  } else if constexpr (IDL) {
+    // forward table, ids in LDS: the table rows of step t + 1 are requested at the top of step t from the ids staged above (the last
+    // request, for step ns_max, is never used; ns_max < xid_cap keeps it inside the table).  Straight-line: no branch, no memory result needed
+    // before the end-of-step wait, which is counted behind the step's stores.
+    auto rows = [&](int t, XG12& pp, XG12& zz) {
+      const int2 id = *reinterpret_cast<const int2*>(idp + t * 64);
+      load3(pp, A.ptabx + (size_t)id.x * 3 * D);
+      load3(zz, A.ztabx + (size_t)id.y * 3 * D);
+    };
+    XG12 pn, zn;
+    rows(0, pn, zn);
+#pragma unroll
+    for (int q = 0; q < 12; ++q) gc.v[q] = pn.v[q] + zn.v[q];
+    for (int t = 0; t < ns_max; ++t) {
+      rows(t + 1, pn, zn);
+      __builtin_amdgcn_sched_barrier(0);      // (the two fences: without them the scheduler stretches the live ranges of a step over the
+      compute(t);                             //  loop's edge and, at dim 128, spills - a spill reload is a scratch load and `vmcnt(0)` again;
+      __builtin_amdgcn_sched_barrier(0);      //  with them 224 registers, no scratch)
+#pragma unroll
+      for (int q = 0; q < 12; ++q) {
+        asm volatile("" : "+v"(pn.v[q]), "+v"(zn.v[q]));
+        gc.v[q] = pn.v[q] + zn.v[q];
+      }
+    }
   } else {
     // forward table: the row ids of step t + 2 and the table rows of step t + 1 are requested at the top of step t.  (Measured and not
     // kept: touching the lines of the row of step t + 3 - one dword per 128-byte line, at the top or at the very end of a step - to bring
@@ -555,6 +619,10 @@ __global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel(TeArgs A) {
   }
   XP_END
 }
+template <int D, bool FT, bool PRED = false>
+__global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel(TeArgs A) { te_rec_fwdx_body<D, FT, PRED, false>(A); }
+template <int D, bool PRED = false>      // the forward-table form with the tile's ids in LDS
+__global__ __launch_bounds__(D * 4) void te_rec_fwdxi_kernel(TeArgs A) { te_rec_fwdx_body<D, true, PRED, true>(A); }
 
 // -------------------------------------------------------------------------------------------------
 // te_rec_fwd1x: the exact forward recurrence of ONE sequence per workgroup on the vector ALUs, in float64 - small launches (at most one
@@ -577,11 +645,15 @@ __device__ __forceinline__ double x_pick4(const double (&a)[4], int o) { return 
 // order over the length-sorted launch: every workgroup gets one sequence of each length class) with its weights loaded ONCE: a launch of
 // 1563 sequences was six rounds of workgroups, each paying the longest sequence of its round and a 196 KB weight fetch (te_rec_fwd 217 us;
 // the 16-row tiles: 221 us), now ~113 steps per CU.  FT: pre-activations from the forward table (ptabx[p_t] + ztabx[dp_t]) instead of gx.
-template <int D, bool PRED = false, bool FT = false>
-__global__ __launch_bounds__(4 * D) void te_rec_fwd1x_kernel(TeArgs A) {
+// IDL (FT only): the table-row ids of the sequence's steps are staged into LDS when the workgroup takes the sequence up (te_rec_fwdx: the
+// loop top needs no memory result; here the id -> row chain of a step loses its first link).
+template <int D, bool PRED, bool FT, bool IDL>
+__device__ __forceinline__ void te_rec_fwd1x_body(const TeArgs& A) {
   constexpr int LZ = D / 8, LC = D / 16;
+  static_assert(FT || !IDL, "te_rec_fwd1x: the per-step-row form has no ids");
   __shared__ __align__(16) double hs[D], rhs[D], zs[D];
   __shared__ double s_t64[64];
+  __shared__ int2 s_id[IDL ? X1_ID_CAP : 1];      // {POI row, bin row} of the current sequence's steps (te_xfwd_ids_cap: the launch's steps fit)
   const int tid = threadIdx.x;
   // hybrid recurrences (TeArgs.hyb, training): the leading hyb_dev[0] sequences on hyb_dev[1] workgroups, the rest in tiles (te_rec_fwdx) at the same time
   const int n1 = (!PRED && A.hyb) ? A.hyb_dev[0] : A.n_seq, G = (!PRED && A.hyb) ? A.hyb_dev[1] : (int)gridDim.x, bq = blockIdx.x;
@@ -614,9 +686,13 @@ __global__ __launch_bounds__(4 * D) void te_rec_fwd1x_kernel(TeArgs A) {
   float* const dH = A.H + Tsp * D + (tid % D);
   float* const dR = A.RH + Tsp * D + (tid % D);
   const int* __restrict__ xrow = A.xcomp ? A.row_pc : A.row_p;
-  // pre-activations of packed row rr, columns jz (z | r) and 2 D + jc (c)
-  auto pre = [&](size_t rr, double& ozr, double& oc) {
-    if constexpr (FT) {
+  // pre-activations of packed row rr (step ts of the sequence), columns jz (z | r) and 2 D + jc (c)
+  auto pre = [&](size_t rr, int ts, double& ozr, double& oc) {
+    if constexpr (IDL) {
+      const int2 id = s_id[min(ts, X1_ID_CAP - 1)];
+      const size_t p1 = (size_t)id.x * 3 * D, z1 = (size_t)id.y * 3 * D;
+      ozr = A.ptabx[p1 + jz] + A.ztabx[z1 + jz]; oc = A.ptabx[p1 + 2 * D + jc] + A.ztabx[z1 + 2 * D + jc];
+    } else if constexpr (FT) {
       const size_t p1 = (size_t)min((unsigned)xrow[rr], (unsigned)A.n_item) * 3 * D, z1 = (size_t)(A.spatial ? min((unsigned)A.row_dp[rr], (unsigned)A.n_dist) : 0u) * 3 * D;
       ozr = A.ptabx[p1 + jz] + A.ztabx[z1 + jz]; oc = A.ptabx[p1 + 2 * D + jc] + A.ztabx[z1 + 2 * D + jc];
     } else { ozr = A.gx[rr * 3 * D + jz]; oc = A.gx[rr * 3 * D + 2 * D + jc]; }
@@ -626,13 +702,17 @@ __global__ __launch_bounds__(4 * D) void te_rec_fwd1x_kernel(TeArgs A) {
     if (k >= n1) break;                      // (workgroup-uniform; the snake's odd legs run downwards: a later even leg may still exist)
     if (tid < D) hs[tid] = 0.0;
     const int r0 = A.soff[k], ns = A.soff[k + 1] - r0;
+    if constexpr (IDL)      // (the last sequence's steps have all been read: the barrier that closes a sequence)
+      for (int t = tid; t < min(ns, X1_ID_CAP); t += 4 * D)
+        s_id[t] = make_int2((int)min((unsigned)xrow[r0 + t], (unsigned)A.n_item), A.spatial ? (int)min((unsigned)A.row_dp[r0 + t], (unsigned)A.n_dist) : 0);
     __syncthreads();
     double gzr = 0.0, gcc = 0.0;
-    if (ns > 0) pre((size_t)r0, gzr, gcc);
+    if (ns > 0) pre((size_t)r0, 0, gzr, gcc);
     for (int t = 0; t < ns; ++t) {
-      const size_t row = (size_t)(r0 + t), rn = (size_t)(r0 + min(t + 1, ns - 1));
+      const int tn = min(t + 1, ns - 1);
+      const size_t row = (size_t)(r0 + t), rn = (size_t)(r0 + tn);
       double nzr, nc;
-      pre(rn, nzr, nc);
+      pre(rn, tn, nzr, nc);
       double a[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int i = 0; i < LZ; i += 2) {
@@ -681,6 +761,10 @@ __global__ __launch_bounds__(4 * D) void te_rec_fwd1x_kernel(TeArgs A) {
     __syncthreads();                         // hs is reset for the next sequence: every lane has read its last values
   }
 }
+template <int D, bool PRED = false, bool FT = false>
+__global__ __launch_bounds__(4 * D) void te_rec_fwd1x_kernel(TeArgs A) { te_rec_fwd1x_body<D, PRED, FT, false>(A); }
+template <int D, bool PRED = false>      // the forward-table form with the sequence's ids in LDS
+__global__ __launch_bounds__(4 * D) void te_rec_fwd1xi_kernel(TeArgs A) { te_rec_fwd1x_body<D, PRED, true, true>(A); }
 
 // -------------------------------------------------------------------------------------------------
 // te_rec_fwdd: the exact forward recurrence for D = 256 (config X) - the recurrent products in FLOAT64 on the matrix cores
@@ -716,9 +800,10 @@ __global__ __launch_bounds__(256) void te_xwpackd_kernel(const float* __restrict
   }
 }
 
-template <int D, bool FT, bool PRED = false>
-__global__ __launch_bounds__(D * 2) void te_rec_fwdd_kernel(TeArgs A) {
+template <int D, bool FT, bool PRED, bool IDL>      // IDL: the tile's table-row ids staged in LDS behind the state (te_rec_fwdx)
+__device__ __forceinline__ void te_rec_fwdd_body(const TeArgs& A) {
   constexpr int NW = D / 32, NT = D / 16, KQ = D / 16;
+  static_assert(FT || !IDL, "te_rec_fwdd: the per-step-row form has no ids");
   static_assert(D % 32 == 0 && D >= 64, "te_rec_fwdd: a wave owns 32 units of every gate");
   extern __shared__ __align__(16) unsigned char xlds[];
   double* hT = reinterpret_cast<double*>(xlds);      // [D][16]
@@ -735,11 +820,24 @@ __global__ __launch_bounds__(D * 2) void te_rec_fwdd_kernel(TeArgs A) {
   }
   if (tid >= 64 && tid < 128) s_t64[tid - 64] = exp2((double)(tid - 64) * (1.0 / 64.0));
   for (int e = tid; e < 2 * D * 16; e += blockDim.x) hT[e] = 0.0;      // h_0 = 0
+  const int Tsp = A.soff[A.n_seq];                   // spare packed row: finished sequences read / write it unconditionally
+  const int* __restrict__ xrow = A.xcomp ? A.row_pc : A.row_p;
+  int2* const s_id = reinterpret_cast<int2*>(rhT + D * 16);      // [xid_cap][16] {POI row, bin row}, clamped; the spare row's past a sequence's end
+  const int id_cap = A.xid_cap;
+  if constexpr (IDL) {      // D / 8 threads per sequence, coalesced along its steps
+    constexpr int TPS = D / 8;
+    const int q = tid / TPS, k = tile * 16 + q;
+    int r0 = 0, ns = 0;
+    if (k < A.n_seq) { r0 = A.soff[k]; ns = A.soff[k + 1] - r0; }
+    for (int t = tid % TPS; t < id_cap; t += TPS) {
+      const int rr = t < ns ? r0 + t : Tsp;
+      s_id[t * 16 + q] = make_int2((int)min((unsigned)xrow[rr], (unsigned)A.n_item), A.spatial ? (int)min((unsigned)A.row_dp[rr], (unsigned)A.n_dist) : 0);
+    }
+  }
   __syncthreads();
   int ns_max = 0;
   for (int q = 0; q < 16; ++q) ns_max = max(ns_max, s_ns[q]);
   const int rowb = s_r0[i], nsr = s_ns[i];
-  const int Tsp = A.soff[A.n_seq];                   // spare packed row: finished sequences read / write it unconditionally
   const float4* __restrict__ Wp = reinterpret_cast<const float4*>(A.xWh8);
   // this lane: units ub[u] .. ub[u] + 3 (u = 0, 1: the wave's two unit tiles) of sequence i
   int ub[2];
@@ -801,12 +899,14 @@ __global__ __launch_bounds__(D * 2) void te_rec_fwdd_kernel(TeArgs A) {
       }
     }
   };
-  const int* __restrict__ xrow = A.xcomp ? A.row_pc : A.row_p;
   for (int t = 0; t < ns_max; ++t) {
     const bool on = t < nsr;
     const size_t row = (size_t)(on ? rowb + t : Tsp);
     int p1 = 0, z1 = 0;
-    if constexpr (FT) {
+    if constexpr (IDL) {
+      const int2 id = s_id[min(t, id_cap - 1) * 16 + i];
+      p1 = id.x; z1 = id.y;
+    } else if constexpr (FT) {
       p1 = (int)min((unsigned)xrow[row], (unsigned)A.n_item);
       z1 = A.spatial ? (int)min((unsigned)A.row_dp[row], (unsigned)A.n_dist) : 0;
     }
@@ -863,15 +963,23 @@ __global__ __launch_bounds__(D * 2) void te_rec_fwdd_kernel(TeArgs A) {
             make_float4((float)hcur[u][0], (float)hcur[u][1], (float)hcur[u][2], (float)hcur[u][3]);
   }
 }
+template <int D, bool FT, bool PRED = false>
+__global__ __launch_bounds__(D * 2) void te_rec_fwdd_kernel(TeArgs A) { te_rec_fwdd_body<D, FT, PRED, false>(A); }
+template <int D, bool PRED = false>      // the forward-table form with the tile's ids in LDS
+__global__ __launch_bounds__(D * 2) void te_rec_fwddi_kernel(TeArgs A) { te_rec_fwdd_body<D, true, PRED, true>(A); }
 
 // -------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------
 bool te_xfwd_supported(int D) { return D == 64 || D == 128 || D == 256; }
 
-size_t te_xfwd_lds(int D) {
+#define XLDS_OPT_IN (152 * 1024)      // dynamic LDS the recurrence kernels may ask for (hipFuncAttributeMaxDynamicSharedMemorySize)
+
+// id_steps: step capacity of the id table behind the kernel's own LDS (TeArgs.xid_cap; 16 sequences x {POI row, bin row, packed row, -})
+size_t te_xfwd_lds(int D, int id_steps = 0) {
   const int KB = D / 64, NW = D / 16, SL = XS - 3;
-  return (size_t)2 * XS * 16 * (D + 16) + (size_t)NW * 3 * KB * SL * 64 * 16;
+  return (size_t)2 * XS * 16 * (D + 16) + (size_t)NW * 3 * KB * SL * 64 * 16
+         + (size_t)id_steps * 16 * sizeof(int4);
 }
 
 // bytes of the digit fragments / doubles of the scales for a (rows x K) operand
@@ -880,18 +988,37 @@ size_t te_xfrag_bytes(int rows, int K) { return (size_t)rows * K * XS; }
 // D <= 128: te_rec_fwdx (int8 digit products, resident fragments); D = 256: te_rec_fwdd (float64 MFMA, streamed float32 fragments)
 template <int D> struct XRec {
   static constexpr bool F64 = D > 128;
-  static size_t lds() { return F64 ? sizeof(double) * 2 * D * 16 : te_xfwd_lds(D <= 128 ? D : 128); }
+  static size_t lds(int id_steps = 0) { return F64 ? sizeof(double) * 2 * D * 16 + (size_t)id_steps * 16 * sizeof(int2) : te_xfwd_lds(D <= 128 ? D : 128, id_steps); }
   static dim3 block() { return dim3(F64 ? D * 2 : D * 4); }
   template <bool FT, bool PRED> static const void* fn() {
     if constexpr (F64) return reinterpret_cast<const void*>(&te_rec_fwdd_kernel<D, FT, PRED>);
     else return reinterpret_cast<const void*>(&te_rec_fwdx_kernel<D, FT, PRED>);
   }
+  template <bool PRED> static const void* fn_ids() {      // the forward-table form with the ids in LDS
+    if constexpr (F64) return reinterpret_cast<const void*>(&te_rec_fwddi_kernel<D, PRED>);
+    else return reinterpret_cast<const void*>(&te_rec_fwdxi_kernel<D, PRED>);
+  }
   template <bool FT, bool PRED> static void launch(const TeArgs& A, hipStream_t st) {
     const dim3 grid((A.n_seq + 15) / 16);
-    if constexpr (F64) hipLaunchKernelGGL((te_rec_fwdd_kernel<D, FT, PRED>), grid, block(), lds(), st, A);
+    if (FT && A.xid_cap > 0) {
+      if constexpr (F64) hipLaunchKernelGGL((te_rec_fwddi_kernel<D, PRED>), grid, block(), lds(A.xid_cap), st, A);
+      else hipLaunchKernelGGL((te_rec_fwdxi_kernel<D, PRED>), grid, block(), lds(A.xid_cap), st, A);
+    }
+    else if constexpr (F64) hipLaunchKernelGGL((te_rec_fwdd_kernel<D, FT, PRED>), grid, block(), lds(), st, A);
     else hipLaunchKernelGGL((te_rec_fwdx_kernel<D, FT, PRED>), grid, block(), lds(), st, A);
   }
 };
+
+// The step capacity of the id table (TeArgs.xid_cap) for a launch whose sequences have at most `steps` steps: one entry more than the
+// steps (the loop requests the rows of step t + 1), or 0 - ids loaded inside the step loop - when the table does not fit: behind the
+// tile kernels' own dynamic LDS under the opt-in, or in the per-sequence kernel's static list.
+int te_xfwd_ids_cap(int D, int steps, bool per_sequence) {
+  if (steps < 1 || steps >= (1 << 20)) return 0;
+  const int cap = steps + 1;
+  if (per_sequence) return cap <= X1_ID_CAP ? cap : 0;
+  const size_t need = D == 64 ? XRec<64>::lds(cap) : D == 128 ? XRec<128>::lds(cap) : XRec<256>::lds(cap);
+  return need <= (size_t)XLDS_OPT_IN ? cap : 0;
+}
 
 template <int D>
 static hipError_t te_xfwd_t(const TeArgs& A, int num_cu, hipStream_t st, Timing* tm, int phase) {
@@ -899,10 +1026,10 @@ static hipError_t te_xfwd_t(const TeArgs& A, int num_cu, hipStream_t st, Timing*
   static DeviceOnce once;
   {
     const hipError_t oe = once.run([&]() -> hipError_t {
-      const void* fns[5] = {XRec<D>::template fn<false, false>(), XRec<D>::template fn<true, false>(), XRec<D>::template fn<false, true>(), XRec<D>::template fn<true, true>(),
-                            reinterpret_cast<const void*>(&te_gemmx_kernel<D>)};
+      const void* fns[7] = {XRec<D>::template fn<false, false>(), XRec<D>::template fn<true, false>(), XRec<D>::template fn<false, true>(), XRec<D>::template fn<true, true>(),
+                            XRec<D>::template fn_ids<false>(), XRec<D>::template fn_ids<true>(), reinterpret_cast<const void*>(&te_gemmx_kernel<D>)};
       for (const void* f : fns) {
-        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, XLDS_OPT_IN);
         if (e != hipSuccess) return e;
       }
       return hipSuccess;
@@ -977,7 +1104,8 @@ static hipError_t te_xfwd_t(const TeArgs& A, int num_cu, hipStream_t st, Timing*
   if (A.predict) {      // (inside the caller's te_predict region)
     if constexpr (!XRec<D>::F64) {
       if (A.xrec1) {
-        if (A.xft) hipLaunchKernelGGL((te_rec_fwd1x_kernel<D, true, true>), dim3(min(n, num_cu * (D <= 64 ? 3 : 1))), dim3(4 * D), 0, st, A);
+        if (A.xft && A.xid_cap > 0) hipLaunchKernelGGL((te_rec_fwd1xi_kernel<D, true>), dim3(min(n, num_cu * (D <= 64 ? 3 : 1))), dim3(4 * D), 0, st, A);
+        else if (A.xft) hipLaunchKernelGGL((te_rec_fwd1x_kernel<D, true, true>), dim3(min(n, num_cu * (D <= 64 ? 3 : 1))), dim3(4 * D), 0, st, A);
         else hipLaunchKernelGGL((te_rec_fwd1x_kernel<D, true, false>), dim3(min(n, num_cu * (D <= 64 ? 3 : 1))), dim3(4 * D), 0, st, A);
         return hipGetLastError();
       }
@@ -1000,7 +1128,8 @@ static hipError_t te_xfwd_t(const TeArgs& A, int num_cu, hipStream_t st, Timing*
       done = true;
     } else
     if (A.xrec1) {      // persistent: one workgroup per CU walks the launch's sequences
-      if (A.xft) hipLaunchKernelGGL((te_rec_fwd1x_kernel<D, false, true>), dim3(min(n, num_cu * (D <= 64 ? 3 : 1))), dim3(4 * D), 0, st, A);
+      if (A.xft && A.xid_cap > 0) hipLaunchKernelGGL((te_rec_fwd1xi_kernel<D, false>), dim3(min(n, num_cu * (D <= 64 ? 3 : 1))), dim3(4 * D), 0, st, A);
+      else if (A.xft) hipLaunchKernelGGL((te_rec_fwd1x_kernel<D, false, true>), dim3(min(n, num_cu * (D <= 64 ? 3 : 1))), dim3(4 * D), 0, st, A);
       else hipLaunchKernelGGL((te_rec_fwd1x_kernel<D, false, false>), dim3(min(n, num_cu * (D <= 64 ? 3 : 1))), dim3(4 * D), 0, st, A);
       done = true;
     }

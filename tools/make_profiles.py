@@ -83,7 +83,7 @@ fa, fc = counters("fetch")
 wa, wc = counters("write")
 # timed regions of bench.py -> kernels
 REGION = {"te_gather": ["te_gather_kernel"], "te_gemm_ax": ["te_gemm_nt_kernel<true", "te_gemm_ntk_kernel<true", "te_gemm_ntk_kernel<false, true", "te_ptab_s3_kernel", "te_ztab_kernel", "te_xpack_kernel", "te_xwpackd_kernel", "te_xztab_kernel", "te_gemmx_kernel", "te_xcount_kernel", "te_xassign_kernel"], "te_gemm_dx": ["te_gemm_nt_kernel<false", "te_gemm_ntk_kernel<false, false"],
-          "te_rec_fwd": ["te_rec_fwd16_kernel", "te_rec_fwdx_kernel", "te_rec_fwd1x_kernel", "te_rec_fwd1_kernel", "te_rec_fwd32_kernel", "te_rec_fwdd_kernel"],
+          "te_rec_fwd": ["te_rec_fwd16_kernel", "te_rec_fwdx_kernel", "te_rec_fwdxi_kernel", "te_rec_fwd1x_kernel", "te_rec_fwd1xi_kernel", "te_rec_fwd1_kernel", "te_rec_fwd32_kernel", "te_rec_fwdd_kernel", "te_rec_fwddi_kernel"],
           "te_rec_bwd": ["te_rec_bwd16_kernel", "te_rec_bwd16t_kernel", "te_rec_bwd1_kernel", "te_rec_bwd32_kernel"],
           # the TRAINING head (te_head3 / te_head_big3 on split products; te_head_kernel<.., 0> when split products are off); the predict head is its own row
           "te_head": ["te_head3_kernel", "te_head_big3_kernel", "te_bpr_head_kernel"], "te_predict_head": ["te_head_kernel", "te_head_big_kernel"],
