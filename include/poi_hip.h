@@ -88,6 +88,10 @@ extern "C" {
 /* additive to 9: candidate generation - new entry points poi_score_rows, poi_topk_select and poi_score_candidates, options
  * "select_split_max" / "select_grid" / "select_chunk_mb", plan keys "select_rows_per_chunk" / "select_chunks" / "select_path" /
  * "select_splits", timing names "score_rows" / "topk_select" / "score_candidates" (existing entries unchanged). */
+/* additive to 9: filtered recommendation - new entry points poi_filter_build, poi_score_topk_filtered and poi_topk_filtered_scores, the
+ * POI_FILTER_* path constants, options "filter_split_max" / "filter_grid" / "filter_gather_cost", plan keys "filter_path" /
+ * "filter_splits" / "filter_split_max", timing names "filter_build" / "score_topk_filtered" / "topk_filtered_scores" (existing entries
+ * unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -180,7 +184,9 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * number of chunks); "select_path", "select_splits" - written by poi_topk_select / poi_score_candidates in the same way.
  * Additive to 9: "xfwd_ids_lds" - 1 when the launch took the table form of the exact forward recurrence with its row ids staged in LDS
  * (option of the same name), 0 with the ids loaded inside the step loop or without the table form; poi_gru_predict records its own value
- * of this one key. */
+ * of this one key.
+ * Additive to 9: "filter_path" (1 walk, 2 gather), "filter_splits" (slices, 0 outside the split regime), "filter_split_max" - written
+ * by poi_score_topk_filtered. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -1162,6 +1168,77 @@ int poi_score_candidates(poi_ctx* ctx, const float* users, const float* items, i
                          int32_t n_dist, double dd,
                          int32_t k, const int32_t* ex_off, const int32_t* ex,
                          int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+
+/* ---- filtered recommendation (additive to 9): the top-K among the POIs that pass an attribute predicate -----------------------------------
+ * "The best restaurants for this user", "the best museums open now", "the best cafes within 2 km": a top-K over the POIs that pass a
+ * predicate on the CALLER'S attributes (the reference data carries ids, times and coordinates only).  Passing the complement as an
+ * exclusion list costs a binary search per id over a list as long as the table; these entries take a pass BITMAP instead.
+ *
+ * Attributes, per POI, both optional:  cat (n_item) int32 in [0, n_cat), 1 <= n_cat <= 4096;  flags (n_item) uint32, whose meaning is
+ * the application's (price tier, open now, ...).  A NULL flags reads as all-zero words.
+ * Predicate q of a table of P:  a category list pc[pc_off[q] .. pc_off[q + 1]) (ids ascending and unique; EMPTY = any category) and
+ * three words need[q] / any[q] / forbid[q]:
+ *   pass(q, j) = (list empty or cat[j] in list) and (flags[j] & need) == need and (any == 0 or (flags[j] & any) != 0)
+ *                and (flags[j] & forbid) == 0
+ * A NULL cat (or pc) with a non-empty list is POI_EINVAL.  A POI whose cat[j] lies outside [0, n_cat) passes no predicate that has a
+ * list and is counted once per POI (poi_ctx_take_bad_ids).
+ *
+ * poi_filter_build writes bits_out (P, ldw) uint32, ldw >= W = ceil(n_item / 32): POI j is bit j & 31 of word j >> 5 of its
+ * predicate's row; the bits at j >= n_item (the pad words included) are written as 0.  count_out (P) int32 or NULL: the popcounts.
+ * All arrays are device memory.  One small kernel, integer work only.  Timing name: "filter_build".  P = 0 is a no-op.  The ranking
+ * entries take ONLY the bitmap: a caller with a predicate of its own (opening hours evaluated at query time) packs a mask itself.
+ *
+ * The ranking entries:
+ *   C(r)          { j in [0, n_item) : bit j of row pred[r] of bits
+ *                   and (anchor[r] < 0 or c_r == +inf or c(anchor[r], j) < c_r or j == anchor[r])
+ *                   and j not in ex[ex_off[r] .. ex_off[r + 1]) }
+ *                 c, c_r, anchor and lat_order as poi_score_topk_near - with ONE difference: the anchor is a candidate only if it
+ *                 passes the predicate too.  pred (n) int32, or NULL: every row uses predicate 0.  bits is (n_pred, ldw); its bits
+ *                 at j >= n_item are ignored, never trusted.
+ *   score         poi_score_rank's s(r, j), BIT FOR BIT, on every path: users[r] . items[j] from the same product routine and k
+ *                 order; with wd non-NULL plus wd * sts[r][bin(anchor[r], j)] for bin < n_dist by the same expression (the anchor
+ *                 doubles as last_poi; a row with anchor[r] < 0 has no distance term).  poi_score_topk_near sums in another order,
+ *                 which is why it was not extended.  One score definition: the path taken changes no bit of the result.
+ *   order, fill, selectable, signed zeros, determinism: as poi_score_candidates - higher score first, then the lower id; -1 ids and
+ *                 -inf scores behind the K' = min(k, |selectable|) entries; NaN and -inf are not selectable, +inf is; -0.0 and +0.0
+ *                 are one score, written as +0.0; identical bits on every grid, in both regimes, alone or in a call of thousands.
+ *   count_out     (n) or NULL: |C(r)|, not clipped to k and not reduced by the scores that are not selectable.
+ *   bad rows      pred[r] outside [0, n_pred), an anchor outside [-1, n_item), an exclusion list that is not ascending or leaves
+ *                 [0, n_item): all -1 / -inf, count 0, counted once (poi_ctx_take_bad_ids).
+ *   limits        1 <= k <= 32; dim a multiple of 4, <= 256; items float32 or a registered half table; n_dist <= 4096 with the
+ *                 distance term.  Otherwise POI_ENOTSUP.  No float atomics on any result.
+ *
+ * poi_score_topk_filtered - users .. dd are poi_score_rank's arguments with anchor in last_poi's place.  path:
+ *   POI_FILTER_WALK    the tile walk of poi_diverse_pool with lists of k <= 32.  A 32-item tile is one bitmap word per row; a tile
+ *                      whose 32 words are all zero costs neither a product nor an item-row load, so the walk scales with the
+ *                      selectivity when the rows of a tile share a predicate.  A finite radius is POI_ENOTSUP here.
+ *   POI_FILTER_GATHER  one workgroup per row and slice: the set bits (without a radius) or the latitude band (with one: the exact
+ *                      Haversine test, then the bit) are compacted into a queue, and the queue is scored by the walk's product
+ *                      routine on gathered item rows.  Cost per CANDIDATE, not per POI.
+ *   POI_FILTER_AUTO    gather when c_r is finite, or when cand_hint > 0 and n * cand_hint * G < ceil(n / 32) * n_item; otherwise
+ *                      walk.  cand_hint: the caller's upper bound on the pass count of the predicates the call uses, 0 = unknown.
+ *                      G: option "filter_gather_cost" (DESIGN.md section 27 has the table it is read from).
+ * Calls of at most "filter_split_max" rows (default 256) cut the item range / every row's candidates into "filter_grid" slices (0: by
+ * the row count and the CUs; at most 64), a workgroup each, and merge.  poi_ctx_last_plan: "filter_path" (1 walk, 2 gather),
+ * "filter_splits" (0 outside the split regime), "filter_split_max".  Timing name: "score_topk_filtered".  n = 0 is a no-op.
+ *
+ * poi_topk_filtered_scores is the definition (without a radius) on explicit float32 score rows scores (n, ld), ld >= n_item, one
+ * workgroup per row: the counterpart of poi_topk / poi_rank_scores for the models whose score is not users . items, and an independent
+ * check of the fused paths.  Timing name: "topk_filtered_scores".  n = 0 is a no-op. */
+enum { POI_FILTER_AUTO = 0, POI_FILTER_WALK = 1, POI_FILTER_GATHER = 2 };
+int poi_filter_build(poi_ctx* ctx, const int32_t* cat, const uint32_t* flags, int32_t n_item, int32_t n_cat,
+                     const int32_t* pc_off, const int32_t* pc, const uint32_t* need, const uint32_t* any, const uint32_t* forbid, int32_t P,
+                     uint32_t* bits_out, int64_t ldw, int32_t* count_out, void* stream);
+int poi_score_topk_filtered(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                            const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* anchor,
+                            int32_t n_dist, double dd,
+                            const uint32_t* bits, int64_t ldw, int32_t n_pred, const int32_t* pred, int64_t cand_hint,
+                            const int32_t* lat_order, double c_r, const int32_t* ex_off, const int32_t* ex, int32_t k, int32_t path,
+                            int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+int poi_topk_filtered_scores(poi_ctx* ctx, const float* scores, int32_t n, int32_t n_item, int64_t ld,
+                             const uint32_t* bits, int64_t ldw, int32_t n_pred, const int32_t* pred,
+                             const int32_t* ex_off, const int32_t* ex, int32_t k,
+                             int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
 
 /* ---- fold-in (additive to 9): a user row of OboBpr / OboVBpr for a check-in history the model never trained on -------------------------------
  * The factorisation family's only user representation is a trained row of ux (and ue).  Fold-in freezes the item side and runs the

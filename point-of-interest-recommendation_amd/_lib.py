@@ -191,6 +191,13 @@ SIGNATURES = {
     "poi_topk_select": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_score_candidates": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int32, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_filter_build": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                 c_int64, c_void_p, c_void_p]),
+    "poi_score_topk_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_int32, c_double, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_double, c_void_p, c_void_p, c_int32,
+                                        c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_topk_filtered_scores": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_foldin_bpr": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float, c_float,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_foldin_terms_fpmc": (c_int, [c_void_p, POINTER(FpmcParams), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p]),
@@ -258,7 +265,8 @@ PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", 
              "near_path", "near_splits", "near_split_max", "rank_splits", "geoie_score_span", "geoie_score_splits",
              "group_path", "group_splits", "group_split_max", "route_path", "route_splits",
              "diverse_path", "diverse_splits", "diverse_split_max",
-             "select_rows_per_chunk", "select_chunks", "select_path", "select_splits", "xfwd_ids_lds")
+             "select_rows_per_chunk", "select_chunks", "select_path", "select_splits", "xfwd_ids_lds",
+             "filter_path", "filter_splits", "filter_split_max")
 
 
 class Context:
@@ -352,7 +360,8 @@ class Context:
         "near_split_max" / "near_grid" of poi_score_topk_near; "rank_grid" of poi_score_rank; "geoie_score_span" of
         poi_geoie_score_all_geo / poi_geoie_score_topk_geo; "group_split_max" / "group_grid" of poi_group_topk; "route_split_max" / "route_grid" of
         poi_route_expand; "diverse_split_max" / "diverse_grid" of poi_diverse_pool / poi_diverse_topk; "select_split_max" /
-        "select_grid" / "select_chunk_mb" of poi_topk_select / poi_score_candidates)."""
+        "select_grid" / "select_chunk_mb" of poi_topk_select / poi_score_candidates; "filter_split_max" / "filter_grid" / "filter_gather_cost" of
+        poi_score_topk_filtered)."""
         self.check(self.lib.poi_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def set_small_launch(self, max_sequences=1800):

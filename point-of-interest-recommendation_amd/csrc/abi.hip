@@ -740,7 +740,9 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
                       {"route_split_max", &c->route_split_max, 0, 1 << 30}, {"route_grid", &c->route_grid, 0, ROUTE_SPLIT_LIMIT},
                       {"diverse_split_max", &c->diverse_split_max, 0, 1 << 30}, {"diverse_grid", &c->diverse_grid, 0, DIVERSE_SPLIT_LIMIT},
                       {"select_split_max", &c->select_split_max, 0, 1 << 30}, {"select_grid", &c->select_grid, 0, SELECT_SPLIT_LIMIT},
-                      {"select_chunk_mb", &c->select_chunk_mb, 1, 1 << 20}};
+                      {"select_chunk_mb", &c->select_chunk_mb, 1, 1 << 20},
+                      {"filter_split_max", &c->filter_split_max, 0, 1 << 30}, {"filter_grid", &c->filter_grid, 0, FILTER_SPLIT_LIMIT},
+                      {"filter_gather_cost", &c->filter_gather_cost, 1, 1 << 20}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);
@@ -828,7 +830,9 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"diverse_path", &poi_ctx::LastPlan::diverse_path}, {"diverse_splits", &poi_ctx::LastPlan::diverse_splits},
       {"diverse_split_max", &poi_ctx::LastPlan::diverse_split_max},
       {"select_rows_per_chunk", &poi_ctx::LastPlan::select_rows_per_chunk}, {"select_chunks", &poi_ctx::LastPlan::select_chunks},
-      {"select_path", &poi_ctx::LastPlan::select_path}, {"select_splits", &poi_ctx::LastPlan::select_splits}};
+      {"select_path", &poi_ctx::LastPlan::select_path}, {"select_splits", &poi_ctx::LastPlan::select_splits},
+      {"filter_path", &poi_ctx::LastPlan::filter_path}, {"filter_splits", &poi_ctx::LastPlan::filter_splits},
+      {"filter_split_max", &poi_ctx::LastPlan::filter_split_max}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

@@ -4,6 +4,7 @@
 #include "../../include/poi_hip.h"
 #include "poi_kernels.h"
 #include "split_plan.h"
+#include "filter_plan.h"
 
 #include <string>
 #include <utility>
@@ -80,7 +81,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, xfwd_ids_lds, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max, select_rows_per_chunk, select_chunks, select_path, select_splits; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, xfwd_ids_lds, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max, select_rows_per_chunk, select_chunks, select_path, select_splits, filter_path, filter_splits, filter_split_max; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR
@@ -131,6 +132,11 @@ struct poi_ctx {
   int select_split_max = 256; // option "select_split_max": calls of at most this many rows cut each row's id range into slices, a workgroup each
   int select_grid = 0;      // option "select_grid": slices on the split path (0: by the row count and the CUs)
   int select_chunk_mb = 1024; // option "select_chunk_mb": poi_score_candidates keeps at most this many MiB of score rows at a time
+  // filtered recommendation (filter.hip): per (row, slice) partial lists of the split regime
+  DevBuf filter_ws;
+  int filter_split_max = 256; // option "filter_split_max": poi_score_topk_filtered calls of at most this many rows cut the item range (walk) / every row's candidates (gather) into slices, a workgroup each
+  int filter_grid = 0;      // option "filter_grid": slices in the split regime (0: by the row count and the CUs)
+  int filter_gather_cost = FILTER_GATHER_COST_DEFAULT;      // option "filter_gather_cost": POI_FILTER_AUTO's price of a gathered candidate in walk cells (filter_plan.h)
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)

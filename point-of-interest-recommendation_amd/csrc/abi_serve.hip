@@ -1034,6 +1034,106 @@ int poi_diverse_topk(poi_ctx* c, const float* users, const float* items, int32_t
 }
 
 // ---------------------------------------------------------------------------------------------
+// filtered recommendation (filter.hip)
+int poi_filter_build(poi_ctx* c, const int32_t* cat, const uint32_t* flags, int32_t n_item, int32_t n_cat, const int32_t* pc_off, const int32_t* pc,
+                     const uint32_t* need, const uint32_t* any, const uint32_t* forbid, int32_t n_pred, uint32_t* bits_out, int64_t ldw,
+                     int32_t* count_out, void* stream) {
+  if (!c) return fail(c, POI_EINVAL, "poi_filter_build: NULL ctx");
+  if (n_item <= 0 || n_pred < 0) return fail(c, POI_EINVAL, "poi_filter_build: n_item <= 0 or P < 0");
+  if (n_cat < 1 || n_cat > FILTER_NCAT_MAX) return fail(c, POI_EINVAL, "poi_filter_build: n_cat must lie in [1, %d] (got %d)", FILTER_NCAT_MAX, n_cat);
+  if (ldw < ((int64_t)n_item + 31) / 32) return fail(c, POI_EINVAL, "poi_filter_build: ldw must be >= ceil(n_item / 32) = %d (got %lld)", (n_item + 31) / 32, (long long)ldw);
+  if (n_pred == 0) return POI_OK;
+  if (!pc_off || !need || !any || !forbid || !bits_out) return fail(c, POI_EINVAL, "poi_filter_build: NULL pc_off / need / any / forbid / bits_out");
+  if (n_pred > 65535) return fail(c, POI_ENOTSUP, "poi_filter_build supports at most 65535 predicates per call (got %d)", n_pred);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!cat || !pc) {      // a category list needs both: the offsets are the caller's device array, one look at the last one settles it
+    int32_t total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, pc_off + n_pred, sizeof(total), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (total > 0) return fail(c, POI_EINVAL, "poi_filter_build: a predicate with a category list needs cat and pc");
+  }
+  poi::FilterBuildArgs A = {};
+  A.cat = cat; A.flags = flags; A.n_item = n_item; A.n_cat = n_cat;
+  A.pc_off = pc_off; A.pc = pc; A.need = need; A.any = any; A.forbid = forbid; A.n_pred = n_pred;
+  A.bits = bits_out; A.ldw = ldw; A.count = count_out;
+  if (int rc = bad_counter(c, st, &A.bad)) return rc;
+  HIPCHK(c, poi::launch_filter_build(A, st, &c->tm));
+  return POI_OK;
+}
+
+// what the two ranking entries check alike: k, the bitmap and the per-row predicate index
+static int filter_check(poi_ctx* c, const char* who, int32_t n, int32_t n_item, const uint32_t* bits, int64_t ldw, int32_t n_pred, int32_t k,
+                        const int32_t* idx_out) {
+  if (!bits || !idx_out) return fail(c, POI_EINVAL, "%s: NULL bits / idx_out", who);
+  if (k <= 0 || k > FILTER_K_MAX) return fail(c, POI_ENOTSUP, "%s supports 1 <= k <= %d (got %d)", who, FILTER_K_MAX, k);
+  if (n < 0 || n_item <= 0 || n_pred <= 0) return fail(c, POI_EINVAL, "%s: n < 0, n_item <= 0 or n_pred <= 0", who);
+  if (ldw < ((int64_t)n_item + 31) / 32) return fail(c, POI_EINVAL, "%s: ldw must be >= ceil(n_item / 32) = %d (got %lld)", who, (n_item + 31) / 32, (long long)ldw);
+  return POI_OK;
+}
+
+int poi_score_topk_filtered(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd,
+                            const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* anchor, int32_t n_dist,
+                            double dd, const uint32_t* bits, int64_t ldw, int32_t n_pred, const int32_t* pred, int64_t cand_hint,
+                            const int32_t* lat_order, double c_r, const int32_t* ex_off, const int32_t* ex, int32_t k, int32_t path,
+                            int32_t* idx_out, float* score_out, int32_t* count_out, void* stream) {
+  const char* who = "poi_score_topk_filtered";
+  if (!c || !users || !items) return fail(c, POI_EINVAL, "%s: NULL ctx / users / items", who);
+  int rc;
+  if ((rc = filter_check(c, who, n, n_item, bits, ldw, n_pred, k, idx_out))) return rc;
+  if (path != POI_FILTER_AUTO && path != POI_FILTER_WALK && path != POI_FILTER_GATHER) return fail(c, POI_EINVAL, "%s: unknown path %d", who, path);
+  if (!(c_r >= 0.0)) return fail(c, POI_EINVAL, "%s: c_r must be >= 0 (+inf: no radius test)", who);
+  if (cand_hint < 0) return fail(c, POI_EINVAL, "%s: cand_hint must be >= 0 (0: unknown)", who);
+  const bool radius = c_r < HUGE_VAL;
+  if (radius && path == POI_FILTER_WALK) return fail(c, POI_ENOTSUP, "%s: the walk path takes no radius", who);
+  if (radius && (!coords || !cphi || !anchor || !lat_order)) return fail(c, POI_EINVAL, "%s: a radius needs coords / cphi / anchor / lat_order", who);
+  hipStream_t st = (hipStream_t)stream;
+  poi::TileOperands T;
+  if ((rc = tile_operands(c, who, users, items, n, n_item, dim, wd, sts, coords, cphi, thr, anchor, n_dist, dd, ex_off, ex, st, &T))) return rc;
+  if (wd && n_dist > FILTER_NDIST_MAX) return fail(c, POI_ENOTSUP, "%s supports n_dist <= %d (got %d)", who, FILTER_NDIST_MAX, n_dist);
+  if (n == 0) return POI_OK;
+  poi::FilterArgs A = {};
+  put_operands(A, T);
+  A.last_poi = anchor; A.coords = coords; A.cphi = cphi;      // (the anchor is range-checked with or without a distance term)
+  A.k = k; A.bits = bits; A.ldw = ldw; A.n_pred = n_pred; A.pred = pred;
+  A.order = lat_order; A.c_r = c_r; A.band_deg = radius ? lat_band_deg(c_r) : 0.0;
+  A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
+  const int way = plan_filter_path(path, radius, n, n_item, cand_hint, c->filter_gather_cost);
+  // few rows (live traffic): the item range of every 32-row tile (walk) / every row's candidates (gather) are cut into slices so that
+  // the call fills the CUs; many rows: one workgroup per tile / row
+  const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
+  const SplitPlan sp = way == FILTER_PATH_WALK
+                           ? plan_split(n, n_utile, c->filter_split_max, c->filter_grid, 2, c->num_cu, ntile / 16, 2, FILTER_SPLIT_LIMIT)
+                           : plan_split(n, n, c->filter_split_max, c->filter_grid, 4, c->num_cu, INT_MAX, 2, FILTER_SPLIT_LIMIT);
+  A.n_split = sp.n_split;
+  if (sp.split && (rc = carve_lists(c, c->filter_ws, st, A, (size_t)n * A.n_split, FILTER_K_MAX))) return rc;
+  c->plan.valid = 1; c->plan.filter_path = way; c->plan.filter_splits = sp.split ? A.n_split : 0; c->plan.filter_split_max = c->filter_split_max;
+  HIPCHK(c, way == FILTER_PATH_WALK ? poi::launch_filter_walk(A, st, &c->tm) : poi::launch_filter_gather(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_topk_filtered_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, int64_t ld, const uint32_t* bits, int64_t ldw,
+                             int32_t n_pred, const int32_t* pred, const int32_t* ex_off, const int32_t* ex, int32_t k, int32_t* idx_out,
+                             float* score_out, int32_t* count_out, void* stream) {
+  const char* who = "poi_topk_filtered_scores";
+  if (!c || !scores) return fail(c, POI_EINVAL, "%s: NULL ctx / scores", who);
+  int rc;
+  if ((rc = filter_check(c, who, n, n_item, bits, ldw, n_pred, k, idx_out))) return rc;
+  if (ld < n_item) return fail(c, POI_EINVAL, "%s: ld must be >= n_item", who);
+  if ((rc = check_ex_pair(c, who, ex_off, ex))) return rc;
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::FilterScoresArgs A = {};
+  A.scores = scores; A.ld = ld; A.n = n; A.n_item = n_item; A.k = k;
+  A.ex_off = ex_off; A.ex = ex; A.bits = bits; A.ldw = ldw; A.n_pred = n_pred; A.pred = pred; A.n_split = 1;
+  A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  HIPCHK(c, poi::launch_filter_scores(A, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // fold-in of new users (foldin.hip)
 int poi_foldin_bpr(poi_ctx* c, const float* items, int32_t n_item, int32_t dim, const int32_t* off, const int32_t* p, const int32_t* q,
                    int64_t q_epoch_stride, int32_t n, int32_t epochs, float alpha, float lambda, const float* w0, float* w_out,

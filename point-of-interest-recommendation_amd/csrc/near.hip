@@ -29,17 +29,6 @@ namespace poi {
 
 namespace {
 
-// position of the t-th (0-based) set bit of m; m has more than t bits set
-__device__ __forceinline__ int nth_bit(unsigned long long m, int t) {
-  int pos = 0;
-#pragma unroll
-  for (int w = 32; w > 0; w >>= 1) {
-    const int c = __popcll((m >> pos) & ((1ull << w) - 1ull));
-    if (t >= c) { t -= c; pos += w; }
-  }
-  return pos;
-}
-
 // scores the queue (lane l: candidate q_id, PAD_ID = none; m = entries in use) and folds it into the wave's list
 template <int NJ>
 __device__ __forceinline__ void near_score(const NearArgs& A, int r, const float4 (&u)[NJ], float wd, int q_id, int q_bin, int m, float& cs, int& ci) {

@@ -732,6 +732,43 @@ struct SelectArgs {
 hipError_t launch_score_rows(const ScoreRowsArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_select(const SelectArgs& A, hipStream_t st, Timing* tm);
 
+// Filtered recommendation (filter.hip): pass bitmaps of attribute predicates, and the top-K among the POIs whose bit is set
+#define FILTER_K_MAX NEAR_K_MAX             // list length (one half wave)
+#define FILTER_SPLIT_LIMIT 64               // slices a row's (a 32-row tile's) item range may be cut into
+#define FILTER_NCAT_MAX 4096                // categories: the predicate's list is a bit set of this many bits in LDS
+#define FILTER_NDIST_MAX 4096               // distance bins whose thresholds fit the walk kernel's LDS beside its lists
+struct FilterBuildArgs {
+  const int* cat; const unsigned* flags; int n_item, n_cat;   // per POI; either may be null (flags: all-zero words)
+  const int *pc_off, *pc; const unsigned *need, *any, *forbid; int n_pred;      // predicate q: categories pc[pc_off[q] .. pc_off[q + 1]) (empty: any), flag words
+  unsigned* bits; long long ldw; int* count;                  // (n_pred, ldw) words, bit j & 31 of word j >> 5; (n_pred) popcounts or null
+  int* bad;                                                   // device counter: POIs whose category lies outside [0, n_cat) (poi_ctx_take_bad_ids)
+};
+struct FilterArgs {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim, k;
+  const float *wd, *sts; const double *coords, *cphi, *thr; const int* last_poi; int n_dist; float bin_scale;      // distance term, or wd null; last_poi = the anchor (null: none)
+  const int *ex_off, *ex;                                     // per-row exclusion lists (ascending ids), or both null
+  const unsigned* bits; long long ldw; int n_pred; const int* pred;             // pass bitmaps; per-row predicate (null: predicate 0)
+  const int* order; double c_r, band_deg;                     // gather path: latitude order, radius (c_r = +inf: none), band half-width
+  int n_split;                                                // slices (1 on the tile / row path)
+  float* part_s; int *part_i, *part_cnt;                      // split path: (n, n_split, FILTER_K_MAX) partial lists, (n, n_split) counts
+  int* idx_out; float* score_out; int* count_out;             // (n, k); score_out / count_out may be null
+  int* bad;                                                   // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+struct FilterScoresArgs {
+  const float* scores; long long ld; int n, n_item, k;        // (n, ld) float32 score rows, the first n_item of each row are read
+  const int *ex_off, *ex;
+  const unsigned* bits; long long ldw; int n_pred; const int* pred;
+  int n_split;                                                // (1: list_emit's member)
+  float* part_s; int *part_i, *part_cnt;                      // (null: list_emit's members)
+  int* idx_out; float* score_out; int* count_out;
+  int* bad;
+};
+hipError_t launch_filter_build(const FilterBuildArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_filter_walk(FilterArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_filter_gather(FilterArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_filter_scores(const FilterScoresArgs& A, hipStream_t st, Timing* tm);
+
 // Fold-in of new users for the factorisation family (foldin.hip)
 #define FOLDIN_USERS_PER_WAVE 4             // one 16-lane DPP row per user
 struct FoldinArgs {

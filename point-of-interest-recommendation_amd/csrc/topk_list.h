@@ -1,12 +1,23 @@
 // 64-entry top-K lists sorted by better() (poi_common.h: higher score, then lower id), held one entry per lane of a wave or in LDS:
-// the pad entry, the merges and the insertion, the fold of a workgroup's four lists, and the emit and the fold of the kernels that cut
-// a row into slices (near.hip, geoie_score.hip, group.hip, diverse.hip, route.hip; the merge kernel itself is topk_merge.hip).
+// the pad entry, the bit rank of the queue compactions, the merges and the insertion, the fold of a workgroup's four lists, and the emit and the fold of the kernels that cut
+// a row into slices (near.hip, geoie_score.hip, group.hip, diverse.hip, route.hip, filter.hip; the merge kernel itself is topk_merge.hip).
 #pragma once
 #include "poi_common.h"
 
 namespace poi {
 
 constexpr int PAD_ID = 0x7fffffff;      // an empty list entry: sorts behind every POI of the same score
+
+// position of the t-th (0-based) set bit of m; m has more than t bits set
+__device__ __forceinline__ int nth_bit(unsigned long long m, int t) {
+  int pos = 0;
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) {
+    const int c = __popcll((m >> pos) & ((1ull << w) - 1ull));
+    if (t >= c) { t -= c; pos += w; }
+  }
+  return pos;
+}
 
 // (cs, ci) sorted best-first over the lanes, (ns, ni) in any order -> the best 64 of the 128, sorted
 __device__ __forceinline__ void top64_merge(float& cs, int& ci, float ns, int ni) {

@@ -935,3 +935,49 @@ def synthetic_features(n_item, n_img, seed, scale=None):
     out = np.zeros((n_item + 1, n_img), np.float32)
     out[:n_item] = x
     return out
+
+
+# ---- filtered recommendation: POI attributes and pass bitmaps (include/poi_hip.h, poi_filter_build) ---------------------------------
+def synthetic_attributes(n_item, n_cat, seed):
+    """(categories (n_item) int32 in [0, n_cat), flags (n_item) uint32) for tests and benchmarks - nothing in the reference carries
+    attributes.  Category sizes are very unequal (Zipf over a shuffled category order: a few categories hold most POIs, many hold a
+    handful or none); flag bit 0 is set on about half of the POIs ("open now"), bit 1 on a tenth ("wheelchair access"), bits 2-3 hold a
+    price tier 0 .. 3, bit 4 is set on about one POI in a hundred."""
+    rng = np.random.default_rng(seed)
+    w = 1.0 / np.arange(1, n_cat + 1) ** 1.2
+    cats = rng.permutation(n_cat)[rng.choice(n_cat, n_item, p=w / w.sum())].astype(np.int32)
+    flags = ((rng.random(n_item) < 0.5).astype(np.uint32) | ((rng.random(n_item) < 0.1).astype(np.uint32) << 1)
+             | (rng.integers(0, 4, n_item).astype(np.uint32) << 2) | ((rng.random(n_item) < 0.01).astype(np.uint32) << 4))
+    return cats, flags.astype(np.uint32)
+
+
+def pack_pass_bits(masks, ldw=None):
+    """Boolean pass masks (P, n_item) (or (n_item): one predicate) -> the (P, ldw) uint32 bitmap the filtered top-K entries read: POI j
+    is bit j & 31 of word j >> 5; the bits at j >= n_item are 0.  ldw defaults to ceil(n_item / 32).  numpy in, numpy out; a torch
+    tensor in, a torch tensor (int32 storage of the same bits, on the tensor's device) out."""
+    try:
+        import torch
+    except ImportError:      # pragma: no cover - torch is a hard dependency of the package, numpy callers do not need it here
+        torch = None
+    if torch is not None and isinstance(masks, torch.Tensor):
+        m = masks.reshape(1, -1) if masks.dim() == 1 else masks
+        P, N = m.shape
+        W = (N + 31) // 32
+        ldw = W if ldw is None else int(ldw)
+        if ldw < W:
+            raise ValueError("ldw must be >= ceil(n_item / 32) = %d (got %d)" % (W, ldw))
+        b = torch.zeros((P, ldw * 32), dtype=torch.int64, device=m.device)
+        b[:, :N] = m != 0
+        sh = torch.arange(32, dtype=torch.int64, device=m.device)
+        words = (b.view(P, ldw, 32) << sh).sum(dim=2)                                   # < 2^32, exact in int64
+        return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)   # the same 32 bits
+    m = np.asarray(masks)
+    m = m.reshape(1, -1) if m.ndim == 1 else m
+    P, N = m.shape
+    W = (N + 31) // 32
+    ldw = W if ldw is None else int(ldw)
+    if ldw < W:
+        raise ValueError("ldw must be >= ceil(n_item / 32) = %d (got %d)" % (W, ldw))
+    b = np.zeros((P, ldw * 32), np.uint8)
+    b[:, :N] = m != 0
+    return np.ascontiguousarray(np.packbits(b, axis=1, bitorder="little")).view("<u4").reshape(P, ldw)

@@ -66,6 +66,30 @@ class _L2:
         return 0.5 * m.alpha_lambda[1] * float(acc.item())
 
 
+class PoiFilter:
+    """Pass bitmaps of P predicates over a model's POIs (include/poi_hip.h, poi_filter_build): `bits` (P, W = ceil(n_item / 32)) int32
+    on the device - POI j is bit j & 31 of word j >> 5 of its predicate's row - and `counts` (P) on the host, the POIs each predicate
+    passes.  Built by model.poi_filter(predicates) from the model's attributes, or from boolean masks of the caller's own
+    (from_masks: a predicate the attribute words cannot express, such as opening hours evaluated at query time)."""
+
+    def __init__(self, model, bits, counts):
+        self.n_item, self.bits, self.counts = model.n_item, bits, np.asarray(counts, np.int64)
+        self.n_pred, self.ldw = int(bits.shape[0]), int(bits.shape[1])
+
+    @classmethod
+    def from_masks(cls, model, masks):
+        """masks: boolean (P, n_item) (or (n_item)), numpy or torch - packed by data.pack_pass_bits."""
+        from .data import pack_pass_bits
+        m = masks if isinstance(masks, torch.Tensor) else np.asarray(masks)
+        m = m.reshape(1, -1) if m.ndim == 1 else m
+        if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] != model.n_item:
+            raise ValueError("masks must be (P >= 1, n_item = %d) (got %s)" % (model.n_item, tuple(m.shape)))
+        if isinstance(m, torch.Tensor):
+            return cls(model, pack_pass_bits(m).to(model.device).contiguous(), (m != 0).sum(dim=1).cpu().numpy())
+        bits = torch.as_tensor(pack_pass_bits(m).view(np.int32)).to(model.device).contiguous()
+        return cls(model, bits, (m != 0).sum(axis=1))
+
+
 class _Base:
     def _setup(self, device, alpha_lambda):
         if not torch.cuda.is_available():
@@ -753,6 +777,162 @@ class _Base:
         ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
         items = self._items() if hasattr(self, "_items") else self.trained_items.t
         return self._candidates_launch(users.contiguous(), items, self._rank_term(ids, lo), ex, k, return_scores, return_counts, sync)
+
+
+    # ---- filtered recommendation (poi_filter_build / poi_score_topk_filtered / poi_topk_filtered_scores): top-K among the POIs that pass a predicate
+    FILTER_K_MAX = 32
+    _FILTER_PATH = {"auto": 0, "walk": 1, "gather": 2}
+
+    def set_attributes(self, categories=None, flags=None, n_cat=None):
+        """POI attributes for poi_filter - the caller's, as VBPR's feature table and set_coords are (the reference data has none).
+        categories: (n_item) ints in [0, n_cat), n_cat <= 4096 (default: the largest category + 1); flags: (n_item) uint32 words whose
+        bits mean what the application says (price tier, open now, ...).  Either may be None."""
+        cat = fl = None
+        if categories is not None:
+            c = categories.cpu().numpy() if isinstance(categories, torch.Tensor) else np.asarray(categories)
+            if c.shape != (self.n_item,):
+                raise ValueError("categories must hold one id per POI (%s vs n_item = %d)" % (c.shape, self.n_item))
+            n_cat = int(c.max()) + 1 if n_cat is None else int(n_cat)
+            cat = torch.as_tensor(np.ascontiguousarray(c, dtype=np.int32)).to(self.device)
+        n_cat = 1 if n_cat is None else int(n_cat)
+        if not 1 <= n_cat <= 4096:
+            raise ValueError("n_cat must lie in [1, 4096] (got %d)" % n_cat)
+        if flags is not None:
+            f = flags.cpu().numpy() if isinstance(flags, torch.Tensor) else np.asarray(flags)
+            if f.shape != (self.n_item,):
+                raise ValueError("flags must hold one word per POI (%s vs n_item = %d)" % (f.shape, self.n_item))
+            fl = torch.as_tensor(np.ascontiguousarray(f.astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32).view(np.int32)).to(self.device)
+        self._attr = (cat, fl, n_cat)
+
+    def poi_filter(self, predicates):
+        """predicates: a list of dicts with any of "categories" (ids; absent or empty: any category), "need" (flag bits that must all
+        be set), "any" (at least one of them set; 0: no condition) and "forbid" (none of them set) -> a PoiFilter over the model's
+        attributes (set_attributes).  One kernel and one synchronisation (the counts come to the host): a set-up step, like
+        set_coords.  A POI whose category lies outside [0, n_cat) passes no predicate with a category list and raises IndexError."""
+        cat, fl, n_cat = self.__dict__.get("_attr", (None, None, 1))
+        preds = list(predicates)
+        if not preds:
+            raise ValueError("poi_filter needs at least one predicate")
+        off, pcs, words = [0], [], []
+        for q, d in enumerate(preds):
+            extra = set(d) - {"categories", "need", "any", "forbid"}
+            if extra:
+                raise ValueError("predicate %d: unknown key(s) %s" % (q, sorted(extra)))
+            c = np.unique(np.asarray(list(d.get("categories") or ()), np.int64))
+            if c.size:
+                if cat is None:
+                    raise _lib.PoiError("predicate %d lists categories but the model holds none: call set_attributes(categories=...)" % q)
+                if c.min() < 0 or c.max() >= n_cat:
+                    raise ValueError("predicate %d: category ids must lie in [0, %d)" % (q, n_cat))
+            pcs.append(c); off.append(off[-1] + c.size)
+            w = [int(d.get(key, 0)) for key in ("need", "any", "forbid")]
+            if any(not 0 <= v <= 0xFFFFFFFF for v in w):
+                raise ValueError("predicate %d: need / any / forbid are 32-bit words" % q)
+            words.append(w)
+        P, W = len(preds), (self.n_item + 31) // 32
+        i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+        u32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).to(self.device)
+        pc = np.concatenate(pcs) if off[-1] else np.zeros(1, np.int64)
+        wd = np.asarray(words, np.uint32)
+        t_off, t_pc, t_need, t_any, t_forbid = i32(off), i32(pc), u32(wd[:, 0]), u32(wd[:, 1]), u32(wd[:, 2])
+        bits = torch.empty((P, W), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(P, dtype=torch.int32, device=self.device)
+        self.ctx.check(self.lib.poi_filter_build(self.ctx.handle, _ptr(cat), _ptr(fl), self.n_item, n_cat, _ptr(t_off), _ptr(t_pc), _ptr(t_need), _ptr(t_any),
+                                                 _ptr(t_forbid), P, _ptr(bits), W, _ptr(cnt), self._stream()))
+        counts = cnt.cpu().numpy()
+        bad = self.ctx.take_bad_ids(self._stream().value)
+        if bad:
+            raise IndexError("%d POI(s) with a category outside [0, %d): they pass no predicate that lists categories" % (bad, n_cat))
+        return PoiFilter(self, bits, counts)
+
+    def _filtered_args(self, k, filt, which, n, path):
+        """(k, per-row predicate tensor or None, cand_hint, path code) of a filtered call, host arguments checked."""
+        k = int(k)
+        if not 1 <= k <= self.FILTER_K_MAX:
+            raise ValueError("filtered recommendation supports 1 <= k <= %d (got %d)" % (self.FILTER_K_MAX, k))
+        if not isinstance(filt, PoiFilter) or filt.n_item != self.n_item or filt.bits.device != self.device:
+            raise ValueError("filt must be a PoiFilter built for this model (model.poi_filter / PoiFilter.from_masks)")
+        if path not in self._FILTER_PATH:
+            raise ValueError("path must be one of %s (got %r)" % (", ".join(repr(p) for p in self._FILTER_PATH), path))
+        if which is None:
+            pred, hint = None, int(filt.counts[0])
+        elif isinstance(which, torch.Tensor):      # a device tensor is checked by the kernel
+            pred, hint = which.to(self.device, torch.int32).contiguous().reshape(-1), int(filt.counts.max())
+        else:
+            w = np.atleast_1d(np.asarray(which)).astype(np.int64)
+            if w.size and (w.min() < 0 or w.max() >= filt.n_pred):
+                raise IndexError("which must index the filter's %d predicate(s) (found %d..%d)" % (filt.n_pred, int(w.min()), int(w.max())))
+            pred, hint = torch.as_tensor(w.astype(np.int32)).to(self.device), int(filt.counts[w].max()) if w.size else 0
+        if pred is not None and pred.numel() != n:
+            raise ValueError("which must hold one predicate index per row (%d vs %d)" % (pred.numel(), n))
+        return k, pred, hint, self._FILTER_PATH[path]
+
+    def _filtered_out(self, idx, sc, cnt, return_scores, return_counts, sync):
+        return self._serve_out(idx, ((sc, return_scores), (cnt, return_counts)), sync,
+                               "row(s) with a predicate index, an anchor or an exclusion id out of range: their lists are all -1")
+
+    def _filtered_launch(self, users, items, anchor, c_r, ex, term, filt, pred, hint, k, path, return_scores, return_counts, sync):
+        """One poi_score_topk_filtered call -> idx[, scores][, counts] (device tensors).  term: compute_sub_topk_near's."""
+        n = users.shape[0]
+        radius = c_r < float("inf")
+        coords = cphi = order = None
+        if radius or term is not None:
+            coords, cphi, order = self._near_geo(radius)
+        wd, sts, thr, n_dist, dd_m = term if term is not None else (None, None, None, 0, 0.0)
+        idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
+        if n:
+            self.ctx.check(self.lib.poi_score_topk_filtered(self.ctx.handle, _ptr(users), _ptr(items), n, self.n_item, self.kdim, _ptr(wd), _ptr(sts),
+                                                            _ptr(coords), _ptr(cphi), _ptr(thr), _ptr(anchor), int(n_dist), float(dd_m), _ptr(filt.bits),
+                                                            filt.ldw, filt.n_pred, _ptr(pred), hint, _ptr(order), c_r, _ptr(ex[0]), _ptr(ex[1]), k, path,
+                                                            _ptr(idx), _ptr(sc), _ptr(cnt), self._stream()))
+        return self._filtered_out(idx, sc, cnt, return_scores, return_counts, sync and n > 0)
+
+    def _filtered_from_scores(self, score_rows, n, ex, filt, pred, k, return_scores, return_counts, sync):
+        """Explicit score rows, a bounded number of rows at a time, + poi_topk_filtered_scores.  score_rows(o, c) -> (c, n_item)
+        float32 scores of rows o .. o + c - 1."""
+        N = self.n_item
+        idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
+        at = lambda t, o, w: ctypes.c_void_p(t.data_ptr() + 4 * o * w) if t is not None else None
+        step = self._rank_chunk(max(n, 1))
+        for o in range(0, n, step):
+            c = min(step, n - o)
+            full = score_rows(o, c).contiguous()
+            self.ctx.check(self.lib.poi_topk_filtered_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(filt.bits), filt.ldw, filt.n_pred, at(pred, o, 1),
+                                                             at(ex[0], o, 1), _ptr(ex[1]), k, at(idx, o, k), at(sc, o, k), at(cnt, o, 1), self._stream()))
+        return self._filtered_out(idx, sc, cnt, return_scores, return_counts, sync and n > 0)
+
+    def compute_sub_topk_filtered(self, start_end, k, filt, which=None, within_km=None, exclude=None, anchor=None, path="auto",
+                                  return_scores=False, return_counts=False, sync=True):
+        """FILTERED top-K (include/poi_hip.h, poi_score_topk_filtered): compute_sub_topk over the POIs that pass a predicate of `filt`
+        (model.poi_filter / PoiFilter.from_masks) - "the best restaurants for this user".  which: the predicate index of every row
+        (default: predicate 0).  within_km / exclude / anchor as compute_sub_topk_near (default anchor: the user's last train POI; the
+        anchor is a candidate only if it passes the predicate too); the spatial model's distance term is taken at the anchor.  path:
+        "auto" (by the radius and the predicates' pass counts), "walk" or "gather" - the result is the same bits on either.  Returns
+        (n, k) int32 ids (k <= 32) by descending score, ties by ascending id, -1 where fewer POIs pass (scores -inf; NaN and -inf
+        scores are never listed, -0.0 is +0.0); with return_counts the number of passing candidates of every row.  CA-RNN, PRME, GeoIE
+        and POI2Vec go through their own score rows, a bounded number at a time, and poi_topk_filtered_scores; a radius is not
+        defined for them.  Host arguments are checked before the launch; device tensors by the kernel: an offending row comes out all
+        -1 and - with sync - raises IndexError."""
+        if not (self._near_ok and self._rank_fused):
+            if within_km is not None or anchor is not None:
+                raise _lib.PoiError("%s ranks by a score rule of its own, not users . items: within_km / anchor are not defined for it" % type(self).__name__)
+            a = start_end if isinstance(start_end, torch.Tensor) else np.atleast_1d(np.asarray(start_end))
+            n = len(a)
+            k, pred, _, _ = self._filtered_args(k, filt, which, n, path)
+            ids, lo = self._ids(a)
+            ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+
+            def score_rows(o, c):
+                full, per = self._rank_score_rows(a[o:o + c])
+                return full.view(c, per, self.n_item)[:, 0] if per > 1 else full      # (user, position) rows: the user's next POI is position 0
+            return self._filtered_from_scores(score_rows, n, ex, filt, pred, k, return_scores, return_counts, sync)
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        k, pred, hint, pathc = self._filtered_args(k, filt, which, n, path)
+        anc = self._near_anchor(anchor, n, lambda: self._rows(self._last_train_poi(), ids, lo))
+        ex = self._near_exclusion(exclude, n, anc, ids, lo)
+        return self._filtered_launch(users.contiguous(), self._near_items(), anc.contiguous(), self._near_radius(within_km), ex, self._near_term(ids, lo),
+                                     filt, pred, hint, k, pathc, return_scores, return_counts, sync)
 
 
     # ---- group recommendation (poi_group_topk / poi_group_topk_scores): the top-K of an aggregate of the members' scores ---------------
@@ -1937,6 +2117,23 @@ class Session:
         return (idx, sc) if return_scores else idx
 
 
+    def recommend_filtered(self, slots, k, filt, which=None, within_km=None, exclude=None, path="auto", return_scores=False, return_counts=False,
+                           sync=True):
+        """model.compute_sub_topk_filtered over the slots' CURRENT states: the top-k (k <= 32) among the POIs that pass a predicate of
+        `filt` (which: the predicate index of every slot, default predicate 0), the slot's last_poi as the anchor of the radius and of
+        the spatial distance term (a slot without a check-in has neither).  exclude: None, "last" or CSR lists (off, ids)."""
+        m = self.m
+        ids = self._slot_tensor(slots)
+        n = ids.numel()
+        k, pred, hint, pathc = m._filtered_args(k, filt, which, n, path)
+        users = self.h.index_select(0, ids).float().contiguous()
+        anc = self.last_poi.index_select(0, ids).contiguous()
+        term = (m.wd.t, self.sts.index_select(0, ids).contiguous(), m._binthr, m.n_dist, m.dd * 1000.0) if self.spatial else None
+        ex = m._near_exclusion(exclude, n, anc, kinds=("last",))
+        return m._filtered_launch(users, m.trained_items.t, anc, m._near_radius(within_km), ex, term, filt, pred, hint, k, pathc, return_scores,
+                                  return_counts, sync)
+
+
     def rank_of(self, slots, pois, exclude=None, return_scores=False, return_counts=False, sync=True):
         """Exact 0-based rank of pois[i] (one POI per slot, or (n, len_t <= 8)) among all POIs under the slot's CURRENT state - the score
         rule of `recommend` (h . trained_items[:-1]^T, plus the spatial distance term at last_poi; none before the first check-in):
@@ -2256,6 +2453,30 @@ class CellSession(Session):
         if sc is not None:
             sc = torch.where(has[:, None], sc, torch.full_like(sc, float("nan")))
         return (idx, sc) if return_scores else idx
+
+    def recommend_filtered(self, slots, k, filt, which=None, within_km=None, exclude=None, path="auto", return_scores=False, return_counts=False,
+                           sync=True):
+        """Lstm / Rnn: `Session.recommend_filtered`'s plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi +
+        poi_topk_filtered_scores; a slot without a check-in gives -1 ids (count 0); within_km is not defined for its score rule."""
+        if not self.carnn:
+            return super().recommend_filtered(slots, k, filt, which, within_km, exclude, path, return_scores, return_counts, sync)
+        m = self.m
+        if within_km is not None:
+            raise _lib.PoiError("OboCARNN ranks by a score rule of its own: within_km is not supported on its sessions")
+        n, users, lp, has = self._carnn_rows(slots)
+        k, pred, _, _ = m._filtered_args(k, filt, which, n, path)
+        lpr = torch.where(has, lp, torch.full_like(lp, -1))
+        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
+
+        def score_rows(o, c):
+            full = self._carnn_scores(users, lp, o, c)
+            return torch.where(has[o:o + c, None], full, torch.full_like(full, float("-inf")))      # no check-in: nothing is selectable
+        out = m._filtered_from_scores(score_rows, n, ex, filt, pred, k, return_scores, True, sync)
+        out = list(out) if isinstance(out, tuple) else [out]
+        out[-1] = torch.where(has, out[-1], torch.zeros_like(out[-1]))
+        if not return_counts:
+            out.pop()
+        return tuple(out) if len(out) > 1 else out[0]
 
     def recommend_diverse(self, slots, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
                           return_objective=False, return_pool=False, return_counts=False, sync=True):
