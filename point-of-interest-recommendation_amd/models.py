@@ -332,6 +332,10 @@ class _Base:
         ids, lo = self._ids(start_end)
         return ids, self._rows(self.trained_users.t, ids, lo), lo
 
+    def _items(self):
+        """The POI rows the fused serving kernels take the product users . items with."""
+        return self.trained_items.t
+
     def _prob_rows(self, ids, lo):
         return None, None
 
@@ -393,21 +397,51 @@ class _Base:
             filled[lo:lo + n] = True
 
 
-    def _topk_from_scores(self, start_end, k, return_scores=False, scores=None):
-        """Cut-offs beyond the fused kernels' k <= 32 (e.g. at_nums = [5, 10, 15, 20, 30, 50], public/Valuate.py:126):
-        explicit score rows (compute_sub_all_scores_device or `scores`, <= 1 GiB at a time) + poi_topk (k <= 64)."""
+    # ---- explicit score rows: the models and sessions that rank by a rule of their own build (rows, n_item) float32 scores, a bounded
+    # number of rows at a time, and hand them to poi_topk / poi_rank_scores / poi_topk_select / ... ------------------------------------
+    SCORE_ROWS_BYTES = 1 << 30      # of score rows alive at a time (an instance may set its own)
+
+    def _rank_chunk(self, n):
+        return max(1, min(n, self.SCORE_ROWS_BYTES // (4 * max(self.n_item, 1))))
+
+    def _row_chunks(self, n, step=None):
+        """(o, c): rows o .. o + c - 1 of n, _rank_chunk rows at a time."""
+        step = step or self._rank_chunk(max(n, 1))
+        for o in range(0, n, step):
+            yield o, min(step, n - o)
+
+    @staticmethod
+    def _id_list(start_end):
+        return start_end if isinstance(start_end, torch.Tensor) else np.atleast_1d(np.asarray(start_end))
+
+    def _own_score_rows(self, a, positions=False):
+        """score_rows(o, c) -> the model's own score rows (_rank_score_rows) of the users a[o : o + c]: one row per user - of (user,
+        position) rows position 0, the user's next POI - or, with `positions`, all of them, user-major."""
+        def score_rows(o, c):
+            full, per = self._rank_score_rows(a[o:o + c])
+            return full.view(c, per, self.n_item)[:, 0] if per > 1 and not positions else full
+        return score_rows
+
+    def _topk_from_rows(self, score_rows, n, k, return_scores):
+        """Explicit score rows, a bounded number at a time, + poi_topk (k <= 64).  score_rows(o, c) -> (c, n_item) float32 scores of
+        rows o .. o + c - 1."""
+        k = int(k)
         if k > 64:
             raise _lib.PoiError("top-K supports k <= 64 (got %d)" % k)
-        a = start_end if isinstance(start_end, torch.Tensor) else np.atleast_1d(np.asarray(start_end))
-        n = len(a)
         idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
         sc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_scores else None
-        step = max(1, min(n, (1 << 28) // max(self.n_item, 1)))
-        for o in range(0, n, step):
-            full = (scores or self.compute_sub_all_scores_device)(a[o:o + step])
-            self.ctx.check(self.lib.poi_topk(self.ctx.handle, _ptr(full), full.shape[0], self.n_item, int(k), ctypes.c_void_p(idx.data_ptr() + 4 * o * k),
+        for o, c in self._row_chunks(n):
+            full = score_rows(o, c)
+            self.ctx.check(self.lib.poi_topk(self.ctx.handle, _ptr(full), full.shape[0], self.n_item, k, ctypes.c_void_p(idx.data_ptr() + 4 * o * k),
                                              ctypes.c_void_p(sc.data_ptr() + 4 * o * k) if sc is not None else None, self._stream()))
         return (idx, sc) if return_scores else idx
+
+    def _topk_from_scores(self, start_end, k, return_scores=False, scores=None):
+        """Cut-offs beyond the fused kernels' k <= 32 (e.g. at_nums = [5, 10, 15, 20, 30, 50], public/Valuate.py:126): the rows of
+        compute_sub_all_scores_device (or `scores`) through _topk_from_rows."""
+        a = self._id_list(start_end)
+        rows = scores or self.compute_sub_all_scores_device
+        return self._topk_from_rows(lambda o, c: rows(a[o:o + c]), len(a), k, return_scores)
 
 
     # ---- restricted recommendation (poi_score_topk_near): top-K within a radius of an anchor POI, skipping listed POIs -----------------
@@ -628,21 +662,16 @@ class _Base:
         """Fallback models: (score rows (m, n_item) ranked by descending value, rows per user) for the users `a`."""
         return self.compute_sub_all_scores_device(a), 1
 
-    def _rank_from_scores(self, start_end, exclude, targets, return_scores, return_counts, sync):
-        """Explicit score rows, a bounded number of users at a time, + poi_rank_scores."""
-        a = start_end if isinstance(start_end, torch.Tensor) else np.atleast_1d(np.asarray(start_end))
-        n = len(a)
-        ids, lo = self._ids(a)
-        tgt, tm = self._rank_targets(targets, n, ids, lo)
-        ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+    def _rank_from_scores(self, score_rows, n, tgt, tm, ex, return_scores, return_counts, sync, step=None):
+        """Explicit score rows, a bounded number of rows at a time (`step`: not the model's _rank_chunk), + poi_rank_scores.
+        score_rows(o, c) -> (c, n_item) float32 scores of rows o .. o + c - 1, or (c * per, n_item) rows (row, position), row-major."""
         lt = tgt.shape[1]
-        rank = torch.full((n, lt), -1, dtype=torch.int32, device=self.device)
-        sc = torch.full((n, lt), float("-inf"), dtype=torch.float32, device=self.device) if return_scores else None
+        rank = torch.empty((n, lt), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, lt), dtype=torch.float32, device=self.device) if return_scores else None
         cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
-        step = self._rank_chunk(n)
-        for o in range(0, n, step):
-            c = min(step, n - o)
-            full, per = self._rank_score_rows(a[o:o + c])
+        for o, c in self._row_chunks(n, step):
+            full = score_rows(o, c)
+            per = full.shape[0] // c
             t_c, m_c = tgt[o:o + c], tm[o:o + c]
             eo = ex[0][o:o + c + 1].contiguous() if ex[0] is not None else None
             if per == 1:
@@ -686,9 +715,6 @@ class _Base:
                 sc[o:o + c] = torch.where(ok, v, torch.full_like(v, float("-inf")))
         return self._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
 
-    def _rank_chunk(self, n):
-        return max(1, min(n, (1 << 28) // max(self.n_item, 1)))      # <= 1 GiB of score rows at a time
-
     def compute_sub_target_rank(self, start_end, exclude=None, targets=None, return_scores=False, return_counts=False, sync=True):
         """Exact 0-based rank of each target POI among ALL POIs under the model's own score (include/poi_hip.h, poi_score_rank): the
         number of POIs with a higher score, or an equal score and a lower id - the position the target would have in an endless
@@ -699,13 +725,17 @@ class _Base:
         ranked POIs per row.  No (n, n_item) matrix is built for the models that score by users . items; CA-RNN, PRME and POI2Vec go
         through their own score rows, a bounded number of users at a time, and poi_rank_scores."""
         if not self._rank_fused:
-            return self._rank_from_scores(start_end, exclude, targets, return_scores, return_counts, sync)
+            a = self._id_list(start_end)
+            n = len(a)
+            ids, lo = self._ids(a)
+            tgt, tm = self._rank_targets(targets, n, ids, lo)
+            ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+            return self._rank_from_scores(self._own_score_rows(a, positions=True), n, tgt, tm, ex, return_scores, return_counts, sync)
         ids, users, lo = self._users_rows(start_end)
         n = ids.numel()
         tgt, tm = self._rank_targets(targets, n, ids, lo)
         ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-        items = self._items() if hasattr(self, "_items") else self.trained_items.t
-        return self._rank_launch(users, items, self._rank_term(ids, lo), tgt, tm, ex, return_scores, return_counts, sync)
+        return self._rank_launch(users, self._items(), self._rank_term(ids, lo), tgt, tm, ex, return_scores, return_counts, sync)
 
 
     # ---- candidate generation (poi_score_candidates / poi_topk_select): the exact top-K of every row for K up to 4096 ----------------------
@@ -742,9 +772,7 @@ class _Base:
         N = self.n_item
         idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
         at = lambda t, o, w: ctypes.c_void_p(t.data_ptr() + 4 * o * w) if t is not None else None
-        step = self._rank_chunk(max(n, 1))
-        for o in range(0, n, step):
-            c = min(step, n - o)
+        for o, c in self._row_chunks(n):
             full = score_rows(o, c).contiguous()
             self.ctx.check(self.lib.poi_topk_select(self.ctx.handle, _ptr(full), c, N, N, k, at(ex[0], o, 1), _ptr(ex[1]), at(idx, o, k), at(sc, o, k),
                                                     at(cnt, o, 1), self._stream()))
@@ -763,20 +791,15 @@ class _Base:
         IndexError."""
         k = self._candidates_k(k)
         if not self._rank_fused:
-            a = start_end if isinstance(start_end, torch.Tensor) else np.atleast_1d(np.asarray(start_end))
+            a = self._id_list(start_end)
             n = len(a)
             ids, lo = self._ids(a)
             ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-
-            def score_rows(o, c):
-                full, per = self._rank_score_rows(a[o:o + c])
-                return full.view(c, per, self.n_item)[:, 0] if per > 1 else full      # (user, position) rows: the user's next POI is position 0
-            return self._candidates_from_scores(score_rows, n, ex, k, return_scores, return_counts, sync)
+            return self._candidates_from_scores(self._own_score_rows(a), n, ex, k, return_scores, return_counts, sync)
         ids, users, lo = self._users_rows(start_end)
         n = ids.numel()
         ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-        items = self._items() if hasattr(self, "_items") else self.trained_items.t
-        return self._candidates_launch(users.contiguous(), items, self._rank_term(ids, lo), ex, k, return_scores, return_counts, sync)
+        return self._candidates_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), ex, k, return_scores, return_counts, sync)
 
 
     # ---- filtered recommendation (poi_filter_build / poi_score_topk_filtered / poi_topk_filtered_scores): top-K among the POIs that pass a predicate
@@ -893,9 +916,7 @@ class _Base:
         N = self.n_item
         idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
         at = lambda t, o, w: ctypes.c_void_p(t.data_ptr() + 4 * o * w) if t is not None else None
-        step = self._rank_chunk(max(n, 1))
-        for o in range(0, n, step):
-            c = min(step, n - o)
+        for o, c in self._row_chunks(n):
             full = score_rows(o, c).contiguous()
             self.ctx.check(self.lib.poi_topk_filtered_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(filt.bits), filt.ldw, filt.n_pred, at(pred, o, 1),
                                                              at(ex[0], o, 1), _ptr(ex[1]), k, at(idx, o, k), at(sc, o, k), at(cnt, o, 1), self._stream()))
@@ -916,16 +937,12 @@ class _Base:
         if not (self._near_ok and self._rank_fused):
             if within_km is not None or anchor is not None:
                 raise _lib.PoiError("%s ranks by a score rule of its own, not users . items: within_km / anchor are not defined for it" % type(self).__name__)
-            a = start_end if isinstance(start_end, torch.Tensor) else np.atleast_1d(np.asarray(start_end))
+            a = self._id_list(start_end)
             n = len(a)
             k, pred, _, _ = self._filtered_args(k, filt, which, n, path)
             ids, lo = self._ids(a)
             ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-
-            def score_rows(o, c):
-                full, per = self._rank_score_rows(a[o:o + c])
-                return full.view(c, per, self.n_item)[:, 0] if per > 1 else full      # (user, position) rows: the user's next POI is position 0
-            return self._filtered_from_scores(score_rows, n, ex, filt, pred, k, return_scores, return_counts, sync)
+            return self._filtered_from_scores(self._own_score_rows(a), n, ex, filt, pred, k, return_scores, return_counts, sync)
         ids, users, lo = self._users_rows(start_end)
         n = ids.numel()
         k, pred, hint, pathc = self._filtered_args(k, filt, which, n, path)
@@ -1026,11 +1043,7 @@ class _Base:
                     break
                 seen, g2 = more, g2 + 1
             a = np.array(sorted(seen), np.int64)
-            full = None
-            if len(a):
-                full, per = self._rank_score_rows(a)
-                if per > 1:                                  # (user, position) rows: the user's next POI is position 0
-                    full = full.view(len(a), per, self.n_item)[:, 0].contiguous()
+            full = self._own_score_rows(a)(0, len(a)).contiguous() if len(a) else None
             lo_, hi_ = int(off[g]), int(max(off[g2], off[g]))
             sub, ok = ids[lo_:hi_], valid[lo_:hi_]
             mem = np.full(hi_ - lo_, -1, np.int32)
@@ -1073,15 +1086,14 @@ class _Base:
             term = self._rank_term(uid, lo)
         else:                                            # no valid member anywhere: nothing is gathered, every group is empty or rejected
             users, term = torch.zeros((0, self.kdim), dtype=torch.float32, device=self.device), None
-        items = self._items() if hasattr(self, "_items") else self.trained_items.t
         g_mem = i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=self.device)
-        return self._group_launch(users.contiguous(), items, term, i32(off), g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync)
+        return self._group_launch(users.contiguous(), self._items(), term, i32(off), g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync)
 
     # ---- diversified recommendation (poi_diverse_topk / poi_diverse_rerank): a pool of the best candidates, re-ranked by MMR --------------
     def _diverse_items(self):
         """The POI rows the embedding similarity is taken between: the table the model scores with.  None: the model has no single POI
         table that means anything (geo_weight < 1 is then refused)."""
-        return self._items() if hasattr(self, "_items") else self.trained_items.t
+        return self._items()
 
     @staticmethod
     def _diverse_args(k, pool, trade, geo_weight, scale_km):
@@ -1157,11 +1169,9 @@ class _Base:
         idx, sc, obj, pl, cnt = self._diverse_buffers(n, k, pool, return_scores, return_objective, True, return_counts)
         ex = self._diverse_host_exclusion(ex, n)
         kk = min(pool, N)
-        step = self._rank_chunk(max(n, 1))
         ninf = float("-inf")
         at = lambda t, o, w, b=4: ctypes.c_void_p(t.data_ptr() + b * o * w) if t is not None else None
-        for o in range(0, n, step):
-            c = min(step, n - o)
+        for o, c in self._row_chunks(n):
             full = score_rows(o, c)
             full = torch.where(torch.isfinite(full), full, torch.full_like(full, ninf))      # NaN and +-inf are never pooled
             if ex[0] is not None:
@@ -1201,24 +1211,19 @@ class _Base:
         sim = self._diverse_sim(geo_weight, self._diverse_items() if geo_weight < 1.0 else None)
         flags = (return_scores, return_objective, return_pool, return_counts, sync)
         if not self._rank_fused:
-            a = start_end if isinstance(start_end, torch.Tensor) else np.atleast_1d(np.asarray(start_end))
+            a = self._id_list(start_end)
             n = len(a)
             ids, lo = self._ids(a)
             anc = self._rows(self._last_train_poi(), ids, lo) if exclude == "last" else None
             ex = self._near_exclusion(exclude, n, anc, ids, lo)
-
-            def score_rows(o, c):
-                full, per = self._rank_score_rows(a[o:o + c])
-                return full.view(c, per, self.n_item)[:, 0] if per > 1 else full      # (user, position) rows: the user's next POI is position 0
-            return self._diverse_from_scores(score_rows, n, ex, sim, k, pool, trade, geo_weight, scale_km, *flags)
+            return self._diverse_from_scores(self._own_score_rows(a), n, ex, sim, k, pool, trade, geo_weight, scale_km, *flags)
         ids, users, lo = self._users_rows(start_end)
         n = ids.numel()
         anc = self._rows(self._last_train_poi(), ids, lo) if exclude == "last" else None
         ex = self._near_exclusion(exclude, n, anc, ids, lo)
-        items = self._items() if hasattr(self, "_items") else self.trained_items.t
         if n == 0:
             return self._diverse_out(*self._diverse_buffers(0, k, pool, True, True, True, True), *flags[:4], False)
-        return self._diverse_launch(users.contiguous(), items, self.kdim, self._rank_term(ids, lo), ex, k, pool, trade, geo_weight, scale_km, *flags)
+        return self._diverse_launch(users.contiguous(), self._items(), self.kdim, self._rank_term(ids, lo), ex, k, pool, trade, geo_weight, scale_km, *flags)
 
 
 # =================================================================================================
@@ -2062,6 +2067,33 @@ class Session:
             self._raise_bad()
 
     # ---- recommend ------------------------------------------------------------------------------
+    def _tile_rows(self, ids, clamp=False, pad=False):
+        """(users (n, kdim) float32, last POI rows (n), term) of the slots `ids` for the kernels that take _tile_operands: term = (wd,
+        sts rows, last POI rows) or None (not spatial).  A slot without a check-in (last POI -1) has no distance term: its sts row is
+        zero, and so is column n_dist ("too far") of every row.  The term's last POI rows are the slots' own - the kernels read -1 as
+        "no term" - unless `clamp`: rank.hip and poi_score_topk_geo clamp the row to POI 0 and rely on the zero sts row, so rank_of and
+        the unrestricted recommend hand over rows clamped to 0 (the sign of a zero score depends on it).  pad: the sts rows are padded
+        with zero rows to whole 32-row tiles (poi_score_topk_geo reads whole tiles)."""
+        m = self.m
+        users = self.h.index_select(0, ids).float().contiguous()
+        lpr = self.last_poi.index_select(0, ids).contiguous()
+        if not self.spatial:
+            return users, lpr, None
+        n = ids.numel()
+        st = torch.zeros((((n + 31) // 32) * 32 if pad else n, self.nb), dtype=torch.float32, device=m.device)
+        st[:n] = self.sts.index_select(0, ids) * (lpr >= 0).float()[:, None]
+        st[:, m.n_dist] = 0.0
+        return users, lpr, (m.wd.t, st, lpr.clamp(min=0).contiguous() if clamp else lpr)
+
+    def _near_rows(self, ids):
+        """(users (n, kdim) float32, anchor = last POI rows (n), term) of the slots `ids` for the kernels that take _near_launch's term:
+        (wd, sts rows, thr, n_dist, dd in metres) or None (not spatial); the kernels skip the term of an anchor -1 themselves."""
+        m = self.m
+        users = self.h.index_select(0, ids).float().contiguous()
+        anc = self.last_poi.index_select(0, ids).contiguous()
+        term = (m.wd.t, self.sts.index_select(0, ids).contiguous(), m._binthr, m.n_dist, m.dd * 1000.0) if self.spatial else None
+        return users, anc, term
+
     def recommend(self, slots, k, return_scores=False, within_km=None, exclude=None, return_counts=False, sync=True):
         """(n, k) int32 device indices by descending score, ties by ascending index: h . trained_items[:-1]^T, plus - spatial -
         wd * sts[bin(last_poi, .)] for bins below n_dist.  A slot without a check-in has no distance term.
@@ -2073,24 +2105,14 @@ class Session:
         ids = self._slot_tensor(slots)
         n, k = ids.numel(), int(k)
         if within_km is not None or exclude is not None or return_counts:
-            users = self.h.index_select(0, ids).float().contiguous()
-            anc = self.last_poi.index_select(0, ids).contiguous()
-            term = (m.wd.t, self.sts.index_select(0, ids).contiguous(), m._binthr, m.n_dist, m.dd * 1000.0) if self.spatial else None
+            users, anc, term = self._near_rows(ids)
             ex = m._near_exclusion(exclude, n, anc, kinds=("last",))
             return m._near_launch(users, m.trained_items.t, anc, m._near_radius(within_km), ex, term, k, return_scores, return_counts, sync)
-        users = self.h.index_select(0, ids).float().contiguous()
-        idx = torch.empty((n, k), dtype=torch.int32, device=m.device)
-        sc = torch.empty((n, k), dtype=torch.float32, device=m.device) if return_scores else None
-        wd = st = lp = None
-        if self.spatial:
-            pad = ((n + 31) // 32) * 32                  # whole 32-row tiles must be readable, column n_dist ("too far") is zero
-            lpr = self.last_poi.index_select(0, ids)
-            st = torch.zeros((pad, self.nb), dtype=torch.float32, device=m.device)
-            st[:n] = self.sts.index_select(0, ids) * (lpr >= 0).float()[:, None]
-            st[:, m.n_dist] = 0.0
-            lp = lpr.clamp(min=0).contiguous()
-            wd = m.wd.t
+        users, _, term = self._tile_rows(ids, clamp=True, pad=True)
+        wd, st, lp = term or (None, None, None)
         if k <= 32:
+            idx = torch.empty((n, k), dtype=torch.int32, device=m.device)
+            sc = torch.empty((n, k), dtype=torch.float32, device=m.device) if return_scores else None
             if self.spatial:
                 m.ctx.check(m.lib.poi_score_topk_geo(m.ctx.handle, _ptr(users), _ptr(m.trained_items.t), n, m.n_item, m.kdim, _ptr(wd), _ptr(st),
                                                      _ptr(m.coords), _ptr(m._cphi), _ptr(m._binthr), _ptr(lp), m.n_dist, m.dd * 1000.0, k,
@@ -2099,11 +2121,8 @@ class Session:
                 m.ctx.check(m.lib.poi_score_topk(m.ctx.handle, _ptr(users), _ptr(m.trained_items.t), n, m.n_item, m.kdim, None, None, k,
                                                  _ptr(idx), _ptr(sc), m._stream()))
             return (idx, sc) if return_scores else idx
-        if k > 64:
-            raise _lib.PoiError("top-K supports k <= 64 (got %d)" % k)
-        step = max(1, min(n, (1 << 28) // max(m.n_item, 1)))      # explicit score rows, <= 1 GiB at a time, + poi_topk
-        for o in range(0, n, step):
-            c = min(step, n - o)
+
+        def score_rows(o, c):
             prob = None
             if self.spatial:
                 prob = torch.empty((c, m.n_item), dtype=torch.float32, device=m.device)
@@ -2112,10 +2131,8 @@ class Session:
             full = torch.empty((c, m.n_item), dtype=torch.float32, device=m.device)
             m.ctx.check(m.lib.poi_score_all(m.ctx.handle, _ptr(users[o:o + c]), _ptr(m.trained_items.t), c, m.n_item, m.kdim, _ptr(wd), _ptr(prob),
                                             _ptr(full), m._stream()))
-            m.ctx.check(m.lib.poi_topk(m.ctx.handle, _ptr(full), c, m.n_item, k, ctypes.c_void_p(idx.data_ptr() + 4 * o * k),
-                                       ctypes.c_void_p(sc.data_ptr() + 4 * o * k) if sc is not None else None, m._stream()))
-        return (idx, sc) if return_scores else idx
-
+            return full
+        return m._topk_from_rows(score_rows, n, k, return_scores)
 
     def recommend_filtered(self, slots, k, filt, which=None, within_km=None, exclude=None, path="auto", return_scores=False, return_counts=False,
                            sync=True):
@@ -2126,13 +2143,10 @@ class Session:
         ids = self._slot_tensor(slots)
         n = ids.numel()
         k, pred, hint, pathc = m._filtered_args(k, filt, which, n, path)
-        users = self.h.index_select(0, ids).float().contiguous()
-        anc = self.last_poi.index_select(0, ids).contiguous()
-        term = (m.wd.t, self.sts.index_select(0, ids).contiguous(), m._binthr, m.n_dist, m.dd * 1000.0) if self.spatial else None
+        users, anc, term = self._near_rows(ids)
         ex = m._near_exclusion(exclude, n, anc, kinds=("last",))
         return m._filtered_launch(users, m.trained_items.t, anc, m._near_radius(within_km), ex, term, filt, pred, hint, k, pathc, return_scores,
                                   return_counts, sync)
-
 
     def rank_of(self, slots, pois, exclude=None, return_scores=False, return_counts=False, sync=True):
         """Exact 0-based rank of pois[i] (one POI per slot, or (n, len_t <= 8)) among all POIs under the slot's CURRENT state - the score
@@ -2141,17 +2155,10 @@ class Session:
         m = self.m
         ids = self._slot_tensor(slots)
         n = ids.numel()
-        users = self.h.index_select(0, ids).float().contiguous()
-        lpr = self.last_poi.index_select(0, ids).contiguous()
+        users, lpr, term = self._tile_rows(ids, clamp=True)
         tgt, tm = m._rank_targets(pois.reshape(n, -1) if isinstance(pois, torch.Tensor) else np.asarray(pois).reshape(n, -1), n)
-        term = None
-        if self.spatial:
-            st = (self.sts.index_select(0, ids) * (lpr >= 0).float()[:, None]).contiguous()
-            st[:, m.n_dist] = 0.0
-            term = (m.wd.t, st, lpr.clamp(min=0).contiguous())
         ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
         return m._rank_launch(users, m.trained_items.t, term, tgt, tm, ex, return_scores, return_counts, sync)
-
 
     def candidates(self, slots, k, exclude=None, return_scores=False, return_counts=False, sync=True):
         """model.compute_sub_candidates over the slots' CURRENT states (h, sts, last_poi, as `rank_of` assembles them): the exact top-k
@@ -2161,13 +2168,7 @@ class Session:
         k = m._candidates_k(k)
         ids = self._slot_tensor(slots)
         n = ids.numel()
-        users = self.h.index_select(0, ids).float().contiguous()
-        lpr = self.last_poi.index_select(0, ids).contiguous()
-        term = None
-        if self.spatial:
-            st = (self.sts.index_select(0, ids) * (lpr >= 0).float()[:, None]).contiguous()
-            st[:, m.n_dist] = 0.0
-            term = (m.wd.t, st, lpr)
+        users, lpr, term = self._tile_rows(ids)
         ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
         return m._candidates_launch(users, m.trained_items.t, term, ex, k, return_scores, return_counts, sync)
 
@@ -2184,16 +2185,10 @@ class Session:
                                 torch.empty(0, dtype=torch.int32, device=m.device), return_scores, return_counts, False)
         ex = m._group_exclusion(exclude, off, ids, n_grp, kinds=())
         uniq, mem = m._group_members(ids, self.n_slot)
-        sl = torch.as_tensor(uniq).to(m.device)
-        users = self.h.index_select(0, sl).float().contiguous()
-        term = None
-        if self.spatial and len(uniq):
-            lpr = self.last_poi.index_select(0, sl).contiguous()
-            st = (self.sts.index_select(0, sl) * (lpr >= 0).float()[:, None]).contiguous()
-            st[:, m.n_dist] = 0.0
-            term = (m.wd.t, st, lpr)
+        users, _, term = self._tile_rows(torch.as_tensor(uniq).to(m.device))
         g_mem = self._i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=m.device)
-        return m._group_launch(users, m.trained_items.t, term, self._i32(off), g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync)
+        return m._group_launch(users, m.trained_items.t, term if len(uniq) else None, self._i32(off), g_mem, n_grp, agg, ex, k, return_scores,
+                               return_counts, sync)
 
     def recommend_diverse(self, slots, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
                           return_objective=False, return_pool=False, return_counts=False, sync=True):
@@ -2208,13 +2203,7 @@ class Session:
         flags = (return_scores, return_objective, return_pool, return_counts)
         if n == 0:
             return m._diverse_out(*m._diverse_buffers(0, k, pool, True, True, True, True), *flags, False)
-        users = self.h.index_select(0, ids).float().contiguous()
-        lpr = self.last_poi.index_select(0, ids).contiguous()
-        term = None
-        if self.spatial:
-            st = (self.sts.index_select(0, ids) * (lpr >= 0).float()[:, None]).contiguous()
-            st[:, m.n_dist] = 0.0
-            term = (m.wd.t, st, lpr)
+        users, lpr, term = self._tile_rows(ids)
         ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
         return m._diverse_launch(users, m.trained_items.t, m.kdim, term, ex, k, pool, trade, geo_weight, scale_km, *flags, sync)
 
@@ -2413,19 +2402,37 @@ class CellSession(Session):
                                                        m._stream()))
 
     # ---- ranking: CA-RNN's own rule ---------------------------------------------------------------
-    def _carnn_rows(self, slots):
-        """(n, users (n, dim) float32, last POI clamped to 0, has-a-check-in mask) of the slots."""
-        ids = self._slot_tensor(slots)
-        lpr = self.last_poi.index_select(0, ids)
-        return ids.numel(), self.h.index_select(0, ids).float().contiguous(), lpr.clamp(min=0).contiguous(), lpr >= 0
-
-    def _carnn_scores(self, users, lp, o, c):
+    def _carnn_rows(self, slots, exclude=None):
+        """(n, score_rows, has, ex) of the slots: score_rows(o, c) -> poi_carnn_score_all on the CURRENT h and last POI of slots
+        o .. o + c - 1, has (n) = the slot has a check-in, ex = the exclusion lists.  A slot without a check-in has no last POI: it is
+        scored at POI 0 and its row masked to -inf, so nothing of it is selectable."""
         m = self.m
-        full = torch.empty((c, m.n_item), dtype=torch.float32, device=m.device)
-        m.ctx.check(m.lib.poi_carnn_score_all(m.ctx.handle, _ptr(users[o:o + c]), _ptr(m.trained_items.t), _ptr(m.M.t), _ptr(m.trained_dists.t),
-                                              _ptr(m.coords), _ptr(m._cphi), _ptr(m._binthr), _ptr(lp[o:o + c]), c, m.n_item, m.n_dist, m.dim,
-                                              m.dd * 1000.0, _ptr(full), m._stream()))
-        return full
+        ids = self._slot_tensor(slots)
+        n = ids.numel()
+        users = self.h.index_select(0, ids).float().contiguous()
+        lpr = self.last_poi.index_select(0, ids)
+        lp, has = lpr.clamp(min=0).contiguous(), lpr >= 0
+
+        def score_rows(o, c):
+            full = torch.empty((c, m.n_item), dtype=torch.float32, device=m.device)
+            m.ctx.check(m.lib.poi_carnn_score_all(m.ctx.handle, _ptr(users[o:o + c]), _ptr(m.trained_items.t), _ptr(m.M.t), _ptr(m.trained_dists.t),
+                                                  _ptr(m.coords), _ptr(m._cphi), _ptr(m._binthr), _ptr(lp[o:o + c]), c, m.n_item, m.n_dist, m.dim,
+                                                  m.dd * 1000.0, _ptr(full), m._stream()))
+            return torch.where(has[o:o + c, None], full, torch.full_like(full, float("-inf")))
+        return n, score_rows, has, m._near_exclusion(exclude, n, torch.where(has, lp, torch.full_like(lp, -1)), kinds=("last",))
+
+    @staticmethod
+    def _carnn_out(out, has, return_scores, return_counts, ranked=False):
+        """The no-check-in rule on a result ids-or-ranks[, scores][, ...][, counts] of _carnn_rows' rows: such a slot counts 0
+        candidates; `ranked` (recommend, rank_of: the kernel ranks the masked row all the same) also gives it -1 and a NaN score."""
+        out = list(out) if isinstance(out, tuple) else [out]
+        if ranked:
+            out[0] = torch.where(has[:, None], out[0], torch.full_like(out[0], -1))
+            if return_scores:
+                out[1] = torch.where(has[:, None], out[1], torch.full_like(out[1], float("nan")))
+        if return_counts:
+            out[-1] = torch.where(has, out[-1], torch.zeros_like(out[-1]))
+        return tuple(out) if len(out) > 1 else out[0]
 
     def recommend(self, slots, k, return_scores=False, within_km=None, exclude=None, return_counts=False, sync=True):
         """(n, k) int32 device indices by descending score, ties by ascending index.  Lstm / Rnn: `Session.recommend`'s plain rule and
@@ -2434,25 +2441,10 @@ class CellSession(Session):
         not defined for its score rule and raise."""
         if not self.carnn:
             return super().recommend(slots, k, return_scores, within_km, exclude, return_counts, sync)
-        m = self.m
         if within_km is not None or exclude is not None or return_counts:
             raise _lib.PoiError("OboCARNN ranks by a score rule of its own: within_km / exclude / return_counts are not supported on its sessions")
-        k = int(k)
-        if k > 64:
-            raise _lib.PoiError("top-K supports k <= 64 (got %d)" % k)
-        n, users, lp, has = self._carnn_rows(slots)
-        idx = torch.empty((n, k), dtype=torch.int32, device=m.device)
-        sc = torch.empty((n, k), dtype=torch.float32, device=m.device) if return_scores else None
-        step = max(1, min(n, (1 << 28) // max(m.n_item, 1)))
-        for o in range(0, n, step):
-            c = min(step, n - o)
-            full = self._carnn_scores(users, lp, o, c)
-            m.ctx.check(m.lib.poi_topk(m.ctx.handle, _ptr(full), c, m.n_item, k, ctypes.c_void_p(idx.data_ptr() + 4 * o * k),
-                                       ctypes.c_void_p(sc.data_ptr() + 4 * o * k) if sc is not None else None, m._stream()))
-        idx = torch.where(has[:, None], idx, torch.full_like(idx, -1))
-        if sc is not None:
-            sc = torch.where(has[:, None], sc, torch.full_like(sc, float("nan")))
-        return (idx, sc) if return_scores else idx
+        n, score_rows, has, _ = self._carnn_rows(slots)
+        return self._carnn_out(self.m._topk_from_rows(score_rows, n, k, return_scores), has, return_scores, False, ranked=True)
 
     def recommend_filtered(self, slots, k, filt, which=None, within_km=None, exclude=None, path="auto", return_scores=False, return_counts=False,
                            sync=True):
@@ -2463,20 +2455,11 @@ class CellSession(Session):
         m = self.m
         if within_km is not None:
             raise _lib.PoiError("OboCARNN ranks by a score rule of its own: within_km is not supported on its sessions")
-        n, users, lp, has = self._carnn_rows(slots)
-        k, pred, _, _ = m._filtered_args(k, filt, which, n, path)
-        lpr = torch.where(has, lp, torch.full_like(lp, -1))
-        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
-
-        def score_rows(o, c):
-            full = self._carnn_scores(users, lp, o, c)
-            return torch.where(has[o:o + c, None], full, torch.full_like(full, float("-inf")))      # no check-in: nothing is selectable
-        out = m._filtered_from_scores(score_rows, n, ex, filt, pred, k, return_scores, True, sync)
-        out = list(out) if isinstance(out, tuple) else [out]
-        out[-1] = torch.where(has, out[-1], torch.zeros_like(out[-1]))
-        if not return_counts:
-            out.pop()
-        return tuple(out) if len(out) > 1 else out[0]
+        ids = self._slot_tensor(slots)
+        k, pred, _, _ = m._filtered_args(k, filt, which, ids.numel(), path)
+        n, score_rows, has, ex = self._carnn_rows(ids, exclude)
+        return self._carnn_out(m._filtered_from_scores(score_rows, n, ex, filt, pred, k, return_scores, return_counts, sync), has, return_scores,
+                               return_counts)
 
     def recommend_diverse(self, slots, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
                           return_objective=False, return_pool=False, return_counts=False, sync=True):
@@ -2488,20 +2471,10 @@ class CellSession(Session):
         m = self.m
         k, pool, trade, geo_weight, scale_km = m._diverse_args(k, pool, trade, geo_weight, scale_km)
         sim = m._diverse_sim(geo_weight, m.trained_items.t if geo_weight < 1.0 else None)
-        n, users, lp, has = self._carnn_rows(slots)
-        lpr = torch.where(has, lp, torch.full_like(lp, -1))
-        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
-
-        def score_rows(o, c):
-            full = self._carnn_scores(users, lp, o, c)
-            return torch.where(has[o:o + c, None], full, torch.full_like(full, float("-inf")))      # no check-in: nothing is pooled
+        n, score_rows, has, ex = self._carnn_rows(slots, exclude)
         out = m._diverse_from_scores(score_rows, n, ex, sim, k, pool, trade, geo_weight, scale_km, return_scores, return_objective, return_pool,
-                                     True, sync)
-        out = list(out) if isinstance(out, tuple) else [out]
-        out[-1] = torch.where(has, out[-1], torch.zeros_like(out[-1]))
-        if not return_counts:
-            out.pop()
-        return tuple(out) if len(out) > 1 else out[0]
+                                     return_counts, sync)
+        return self._carnn_out(out, has, return_scores, return_counts)
 
     def candidates(self, slots, k, exclude=None, return_scores=False, return_counts=False, sync=True):
         """Lstm / Rnn: `Session.candidates`' plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi +
@@ -2510,19 +2483,8 @@ class CellSession(Session):
             return super().candidates(slots, k, exclude, return_scores, return_counts, sync)
         m = self.m
         k = m._candidates_k(k)
-        n, users, lp, has = self._carnn_rows(slots)
-        lpr = torch.where(has, lp, torch.full_like(lp, -1))
-        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
-
-        def score_rows(o, c):
-            full = self._carnn_scores(users, lp, o, c)
-            return torch.where(has[o:o + c, None], full, torch.full_like(full, float("-inf")))      # no check-in: nothing is selectable
-        out = m._candidates_from_scores(score_rows, n, ex, k, return_scores, True, sync)
-        out = list(out) if isinstance(out, tuple) else [out]
-        out[-1] = torch.where(has, out[-1], torch.zeros_like(out[-1]))
-        if not return_counts:
-            out.pop()
-        return tuple(out) if len(out) > 1 else out[0]
+        n, score_rows, has, ex = self._carnn_rows(slots, exclude)
+        return self._carnn_out(m._candidates_from_scores(score_rows, n, ex, k, return_scores, return_counts, sync), has, return_scores, return_counts)
 
     def recommend_group(self, slot_groups, k, agg="mean", exclude=None, return_scores=False, return_counts=False, sync=True):
         """Lstm / Rnn: `Session.recommend_group`'s plain rule.  CA-RNN ranks by a rule of its own and is refused."""
@@ -2545,35 +2507,12 @@ class CellSession(Session):
         if not self.carnn:
             return super().rank_of(slots, pois, exclude, return_scores, return_counts, sync)
         m = self.m
-        n, users, lp, has = self._carnn_rows(slots)
+        ids = self._slot_tensor(slots)
+        n = ids.numel()
         tgt, tm = m._rank_targets(pois.reshape(n, -1) if isinstance(pois, torch.Tensor) else np.asarray(pois).reshape(n, -1), n)
-        lpr = torch.where(has, lp, torch.full_like(lp, -1))
-        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
-        lt = tgt.shape[1]
-        rank = torch.empty((n, lt), dtype=torch.int32, device=m.device)
-        sc = torch.empty((n, lt), dtype=torch.float32, device=m.device) if return_scores else None
-        cnt = torch.empty(n, dtype=torch.int32, device=m.device) if return_counts else None
-        step = max(1, min(n, (1 << 28) // max(m.n_item, 1)))
-        for o in range(0, n, step):
-            c = min(step, n - o)
-            full = self._carnn_scores(users, lp, o, c)
-            eo = ex[0][o:o + c + 1].contiguous() if ex[0] is not None else None
-            r_c = torch.empty((c, lt), dtype=torch.int32, device=m.device)
-            k_c = torch.empty(c, dtype=torch.int32, device=m.device) if cnt is not None else None
-            m.ctx.check(m.lib.poi_rank_scores(m.ctx.handle, _ptr(full), c, m.n_item, _ptr(tgt[o:o + c].contiguous()), _ptr(tm[o:o + c].contiguous()), lt,
-                                              _ptr(eo), _ptr(ex[1]), _ptr(r_c), _ptr(k_c), m._stream()))
-            rank[o:o + c] = r_c
-            if cnt is not None:
-                cnt[o:o + c] = k_c
-            if sc is not None:
-                v = full.gather(1, tgt[o:o + c].long().clamp(0, m.n_item - 1))
-                sc[o:o + c] = torch.where(r_c >= 0, v, torch.full_like(v, float("-inf")))
-        rank = torch.where(has[:, None], rank, torch.full_like(rank, -1))
-        if sc is not None:
-            sc = torch.where(has[:, None], sc, torch.full_like(sc, float("nan")))
-        if cnt is not None:
-            cnt = torch.where(has, cnt, torch.zeros_like(cnt))
-        return m._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
+        n, score_rows, has, ex = self._carnn_rows(ids, exclude)
+        return self._carnn_out(m._rank_from_scores(score_rows, n, tgt, tm, ex, return_scores, return_counts, sync), has, return_scores,
+                               return_counts, ranked=True)
 
 
 # =================================================================================================
@@ -3477,19 +3416,16 @@ class OboPrme(_SeqFoldin, _Base):
                                                                         torch.empty((0, k), dtype=torch.float32, device=self.device))
             cnt = torch.full((n,), self.n_item, dtype=torch.int32, device=self.device)
         else:
-            idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
-            sc = torch.empty((n, k), dtype=torch.float32, device=self.device)
             eo64 = eo.long()
             row = torch.repeat_interleave(torch.arange(n, device=self.device), eo64[1:] - eo64[:-1])
             ids = ex[:row.numel()].long()
-            step = self._rank_chunk(n)
-            for o in range(0, n, step):
-                c = min(step, n - o)
+
+            def score_rows(o, c):
                 full = self._foldin_score(w, last, o, c)
                 sel = (row >= o) & (row < o + c)
                 full[row[sel] - o, ids[sel]] = float("-inf")
-                self.ctx.check(self.lib.poi_topk(self.ctx.handle, _ptr(full), c, self.n_item, k, ctypes.c_void_p(idx.data_ptr() + 4 * o * k),
-                                                 ctypes.c_void_p(sc.data_ptr() + 4 * o * k), self._stream()))
+                return full
+            idx, sc = self._topk_from_rows(score_rows, n, k, True)
             idx = torch.where(sc == float("-inf"), torch.full_like(idx, -1), idx)
             cnt = (self.n_item - (eo64[1:] - eo64[:-1])).int()
         out = (idx,) + ((sc,) if return_scores else ()) + ((cnt,) if return_counts else ())
@@ -3503,27 +3439,8 @@ class OboPrme(_SeqFoldin, _Base):
             raise ValueError("rank_new needs gaps and targets")
         w, off, p, n, total, last = self._foldin_rows(histories, fold_in_kwargs, gaps=gaps)
         tgt, tm = self._rank_targets(targets, n)
-        eo, ex = self._foldin_ex(exclude, off, p, n, total)
-        lt = tgt.shape[1]
-        rank = torch.empty((n, lt), dtype=torch.int32, device=self.device)
-        sc = torch.empty((n, lt), dtype=torch.float32, device=self.device) if return_scores else None
-        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
-        step = self._rank_chunk(n)
-        for o in range(0, n, step):
-            c = min(step, n - o)
-            full = self._foldin_score(w, last, o, c)
-            eo_c = eo[o:o + c + 1].contiguous() if eo is not None else None
-            r_c = torch.empty((c, lt), dtype=torch.int32, device=self.device)
-            k_c = torch.empty(c, dtype=torch.int32, device=self.device) if cnt is not None else None
-            self.ctx.check(self.lib.poi_rank_scores(self.ctx.handle, _ptr(full), c, self.n_item, _ptr(tgt[o:o + c].contiguous()),
-                                                    _ptr(tm[o:o + c].contiguous()), lt, _ptr(eo_c), _ptr(ex), _ptr(r_c), _ptr(k_c), self._stream()))
-            rank[o:o + c] = r_c
-            if cnt is not None:
-                cnt[o:o + c] = k_c
-            if sc is not None:
-                v = full.gather(1, tgt[o:o + c].long().clamp(0, self.n_item - 1))
-                sc[o:o + c] = torch.where(r_c >= 0, v, torch.full_like(v, float("-inf")))
-        return self._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
+        ex = self._foldin_ex(exclude, off, p, n, total)
+        return self._rank_from_scores(lambda o, c: self._foldin_score(w, last, o, c), n, tgt, tm, ex, return_scores, return_counts, sync)
 
     def compute_sub_auc_preference(self, start_end):
         """PRME.py:141-159 returns zeros (the AUC code is commented out there): AUC is always 0."""
@@ -3859,28 +3776,12 @@ class OboGeoIE(_Base):
         excluded target is not ranked (-1); a NaN score counts below every target."""
         csr, off, p, n, total, tu = self._geo_new(histories, user_term)
         tgt, tm = self._rank_targets(targets, n)
-        eo, ex = self._foldin_exclusion(exclude, off, p, n, total)
-        lt = tgt.shape[1]
-        rank = torch.empty((n, lt), dtype=torch.int32, device=self.device)
-        sc = torch.empty((n, lt), dtype=torch.float32, device=self.device) if return_scores else None
-        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
-        step = self._rank_chunk(n)
-        for o in range(0, n, step):
-            c = min(step, n - o)
+        ex = self._foldin_exclusion(exclude, off, p, n, total)
+
+        def score_rows(o, c):                            # (with sync a bad history raises here, before its rows are ranked)
             rows = torch.arange(o, o + c, dtype=torch.int32, device=self.device)
-            full = self._geo_call(csr, rows, tu[o:o + c].contiguous() if tu is not None else None, c, sync=sync)
-            eo_c = eo[o:o + c + 1].contiguous() if eo is not None else None
-            r_c = torch.empty((c, lt), dtype=torch.int32, device=self.device)
-            k_c = torch.empty(c, dtype=torch.int32, device=self.device) if cnt is not None else None
-            self.ctx.check(self.lib.poi_rank_scores(self.ctx.handle, _ptr(full), c, self.n_item, _ptr(tgt[o:o + c].contiguous()),
-                                                    _ptr(tm[o:o + c].contiguous()), lt, _ptr(eo_c), _ptr(ex), _ptr(r_c), _ptr(k_c), self._stream()))
-            rank[o:o + c] = r_c
-            if cnt is not None:
-                cnt[o:o + c] = k_c
-            if sc is not None:
-                v = full.gather(1, tgt[o:o + c].long().clamp(0, self.n_item - 1))
-                sc[o:o + c] = torch.where(r_c >= 0, v, torch.full_like(v, float("-inf")))
-        return self._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
+            return self._geo_call(csr, rows, tu[o:o + c].contiguous() if tu is not None else None, c, sync=sync)
+        return self._rank_from_scores(score_rows, n, tgt, tm, ex, return_scores, return_counts, sync)
 
     def compute_sub_auc_preference(self, start_end):
         """GeoIE.py:114-115 returns zeros: AUC is always 0."""
@@ -4102,7 +4003,9 @@ class OboPoi2vec(_Base):
         return full, (full.shape[0] // max(len(a), 1) if len(a) else 1)
 
     def _rank_chunk(self, n):
-        return max(n, 1)                          # the reference softmax runs over the USERS of a call: the call is not cut
+        if self.softmax_axis == "reference":
+            return max(n, 1)                      # the reference softmax runs over the USERS of a call: the call is not cut
+        return super()._rank_chunk(n)             # softmax over the POIs: a row does not depend on the other users of its call
 
     # ---- unseen users (poi_foldin_p2v) ---------------------------------------------------------------------------------
     # paths_i of Poi2vec.seq_train (POI2Vec.py:140-163) depends on wl, pb and the contexts, never on xu: with the item side frozen the
@@ -4239,27 +4142,10 @@ class OboPoi2vec(_Base):
             raise _lib.PoiError("%s ranks by a score rule of its own, not users . items: compute_sub_topk_near does not cover it" % type(self).__name__)
         w, (rc, flat), off, p, n, total = self._foldin_rows(histories, contexts, fold_in_kwargs)
         tgt, tm = self._rank_targets(targets, n)
-        eo, ex = self._foldin_exclusion(exclude, off, p, n, total)
-        lt = tgt.shape[1]
-        rank = torch.empty((n, lt), dtype=torch.int32, device=self.device)
-        sc = torch.empty((n, lt), dtype=torch.float32, device=self.device) if return_scores else None
-        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
-        step = max(1, min(max(n, 1), (1 << 28) // max(self.n_item, 1)))
-        for o in range(0, n, step):
-            c = min(step, n - o)
-            full = self._score_rows_new(w, rc, flat, o, c)
-            eo_c = eo[o:o + c + 1].contiguous() if eo is not None else None
-            r_c = torch.empty((c, lt), dtype=torch.int32, device=self.device)
-            k_c = torch.empty(c, dtype=torch.int32, device=self.device) if cnt is not None else None
-            self.ctx.check(self.lib.poi_rank_scores(self.ctx.handle, _ptr(full), c, self.n_item, _ptr(tgt[o:o + c].contiguous()),
-                                                    _ptr(tm[o:o + c].contiguous()), lt, _ptr(eo_c), _ptr(ex), _ptr(r_c), _ptr(k_c), self._stream()))
-            rank[o:o + c] = r_c
-            if cnt is not None:
-                cnt[o:o + c] = k_c
-            if sc is not None:
-                v = full.gather(1, tgt[o:o + c].long().clamp(0, self.n_item - 1))
-                sc[o:o + c] = torch.where(r_c >= 0, v, torch.full_like(v, float("-inf")))
-        return self._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
+        ex = self._foldin_exclusion(exclude, off, p, n, total)
+        # (the folded rows are scored with the softmax over the POIs whatever softmax_axis says: they are cut like any other model's)
+        return self._rank_from_scores(lambda o, c: self._score_rows_new(w, rc, flat, o, c), n, tgt, tm, ex, return_scores, return_counts, sync,
+                                      step=_Base._rank_chunk(self, max(n, 1)))
 
     def compute_sub_auc_preference(self, start_end):
         """POI2Vec.py:111-112 returns zeros: AUC is always 0."""
