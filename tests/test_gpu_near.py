@@ -30,9 +30,12 @@ def last_of(T):
     return T["train"][0][np.arange(T["n_user"]), T["lens"] - 1]
 
 
-def make_case(kind, dim, seed, n_user=70, n_item=300, coords=None, twins=None):
+def make_case(kind, dim, seed, n_user=70, n_item=300, coords=None, twins=None, table_dtype="f32"):
     """dict(T, users, items (float64 views of the float32 tables, logical width), term, build(pa) -> model).  coords: replaces the
-    generator's; twins (a, b): item row b is a copy of row a in every item table."""
+    generator's; twins (a, b): item row b is a copy of row a in every item table.  table_dtype="f16" (bpr / gru / spatial): the model
+    stores its POI table as IEEE half, built from the same unrounded float32 `items` (tests/half_cases.py rounds them for the oracle)."""
+    assert table_dtype == "f32" or kind in ("bpr", "gru", "spatial"), "%s stores float32 tables only" % kind
+    kw = {} if table_dtype == "f32" else dict(table_dtype=table_dtype)
     T = geo_problem(seed, n_user=n_user, n_item=n_item, n_dist=11, dim=dim, len_min=4, len_max=8)
     if coords is not None:
         T["coords"] = coords
@@ -54,7 +57,7 @@ def make_case(kind, dim, seed, n_user=70, n_item=300, coords=None, twins=None):
             term = (float(P["wd"]), sts)
 
         def build(pa):
-            m = plain_model(pa, T, P) if kind == "gru" else spatial_model(pa, T, P)
+            m = plain_model(pa, T, P, **kw) if kind == "gru" else spatial_model(pa, T, P, **kw)
             m.update_trained_users(users)
             if kind == "gru":
                 m.set_coords(T["coords"])
@@ -66,7 +69,7 @@ def make_case(kind, dim, seed, n_user=70, n_item=300, coords=None, twins=None):
 
         def build(pa):
             m = pa.models.OboBpr(train=T["train"], test=T["test"], alpha_lambda=AL, n_user=n_user, n_item=n_item, n_in=dim, n_hidden=dim,
-                                 init=dict(ux=users, lt=items))
+                                 init=dict(ux=users, lt=items), **kw)
             m.update_trained_items(); m.update_trained_users(); m.set_coords(T["coords"])
             return m
     elif kind == "vbpr":
