@@ -158,8 +158,10 @@ int poi_ctx_set_engine(poi_ctx* ctx, int engine);
 int poi_ctx_set_graph(poi_ctx* ctx, int on, int min_n, int max_n);
 int64_t poi_ctx_graph_replays(const poi_ctx* ctx);
 /* ABI 6.  Out-of-range ids in poi_bpr_step (the reference - a Theano gather, public/BPR.py:214-218 - raises IndexError): the kernels never touch
- * memory outside the tables; a triple with a user id outside [0, n_user) or a POI id outside [0, n_item] contributes NO gradient, its loss is NaN,
- * and it is counted on the device.  poi_ctx_take_bad_ids synchronises `stream`, returns the count since the last call and clears it - the Python
+ * memory outside the tables; a triple with a user id outside [0, n_user) or a POI id outside [0, n_item] is REJECTED: it adds no gradient, no L2
+ * decay and no multiplicity to any row - the rows its valid ids name included - its loss is NaN, and it is counted on the device, once per triple
+ * however many of its ids are bad, in both modes.  Removal rule: in snapshot mode the launch equals the launch without its rejected triples, bit
+ * for bit (tables and kept losses).  poi_ctx_take_bad_ids synchronises `stream`, returns the count since the last call and clears it - the Python
  * mirror raises IndexError from OboBpr.train / train_batch(sync=True), as the reference does.  ABI 7: poi_fpmc_step counts its rejected
  * transitions (an id outside its table, or i == j) in the same counter, one per transition.  ABI 8: so does poi_prme_step. */
 int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
@@ -341,7 +343,9 @@ int poi_ctx_set_batch_cap(poi_ctx* ctx, float cap);
  * bitwise identical tables; ABI 5); lt may be a registered IEEE-half table (float32 arithmetic, poi_ctx_set_f16_rounding
  * applies), ux stays float32; dim a multiple of 4 up to 1024.
  * POI_BPR_HOGWILD = in-place racy update (one pass over the three rows; identical to the
- * reference whenever no row is shared inside the launch, e.g. n == 1; float32 tables only). */
+ * reference whenever no row is shared inside the launch, e.g. n == 1; float32 tables only).
+ * A triple with an id outside its table is rejected (ABI 6): NaN loss, counted once per triple, and - snapshot mode - the launch
+ * equals the launch without it bit for bit: no gradient, no L2 decay, no multiplicity on any row. */
 enum { POI_BPR_SNAPSHOT = 0, POI_BPR_HOGWILD = 1 };
 int poi_bpr_step(poi_ctx* ctx, float* ux, float* lt, int32_t n_user, int32_t n_item, int32_t dim,
                  const int32_t* uidx, const int32_t* p, const int32_t* q, int32_t n,

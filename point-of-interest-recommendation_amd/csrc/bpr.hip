@@ -16,6 +16,12 @@
 //   bpr_commit        shadow rows -> ux.
 // Rows moved: 2 per triple (user pass) + 2 per triple (POI pass) + every touched row read and written once: ~4.4 rows per triple at the
 // Gowalla shape against the 6 of the per-triple formulation - the user row of a run and the target rows are not re-read per triple.
+// REJECTED TRIPLES (an id outside its table; include/poi_hip.h, ABI 6): the launch equals the launch without them, bit for bit.  The sorted
+// array is split at fixed positions - user touches [0, n), POI touches [n, 3 n) - so there is ONE SENTINEL PER PART: the user touch of a
+// rejected triple is keyed n_user (after every user row, before every POI key) and its two POI touches n_user + n_item + 2 (after every
+// POI key; POI row r is keyed n_user + 1 + r).  Each part still holds exactly its n / 2 n touches, its sentinel run sorts last, and
+// bpr_chunk stops at it: no gradient, no L2 decay, no multiplicity on any row, the rows the triple's valid ids name included.  bpr_keys
+// counts the triple once and writes its NaN loss; bpr_commit skips the sentinel (it has no shadow row).
 // HOGWILD mode: the round-1 in-place kernel (racy by definition; identical to the reference whenever no row is shared inside the launch).
 #include "poi_common.h"
 #include "poi_kernels.h"
@@ -69,18 +75,24 @@ __global__ __launch_bounds__(POI_BLOCK) void bpr_hogwild_kernel(BprArgs A) {
 // -------------------------------------------------------------------------------------------------
 // SNAPSHOT mode
 // -------------------------------------------------------------------------------------------------
-// touch e < 3 n: e / n = 0 user, 1 positive, 2 negative row of triple e % n; key = row in the unified space [users | POI rows]
+// touch e < 3 n: e / n = 0 user, 1 positive, 2 negative row of triple e % n.  Keys: [users 0 .. n_user - 1 | user sentinel n_user |
+// POI rows n_user + 1 .. n_user + 1 + n_item | POI sentinel n_user + n_item + 2] - see REJECTED TRIPLES in the header.
+__device__ __forceinline__ int bpr_user_sentinel(const BprArgs& A) { return A.n_user; }
+__device__ __forceinline__ int bpr_poi_base(const BprArgs& A) { return A.n_user + 1; }
+__device__ __forceinline__ int bpr_poi_sentinel(const BprArgs& A) { return A.n_user + A.n_item + 2; }
+// one thread per triple: its three ids are read once and its three keys written (touch kind * n + i)
 __global__ __launch_bounds__(256) void bpr_keys_kernel(BprArgs A) {
   const int n = A.n;
   if (blockIdx.x == 0 && threadIdx.x == 0) A.cnt[0] = 3 * n;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < 3 * n; e += gridDim.x * 256) {
-    const int kind = e >= 2 * n ? 2 : e >= n ? 1 : 0, i = e - kind * n;
-    // (ids clamped into their tables: the reference raises IndexError on a bad id, a device kernel must not write outside; the triple of a bad id
-    // gets g = 0 and a NaN loss in bpr_chunk<users> and is counted here: poi_ctx_take_bad_ids)
-    const unsigned raw = kind == 0 ? (unsigned)A.uidx[i] : (unsigned)(kind == 1 ? A.p[i] : A.q[i]);
-    if (kind == 0 ? raw >= (unsigned)A.n_user : raw > (unsigned)A.n_item) atomicAdd(A.bad, 1);
-    A.keys0[e] = kind == 0 ? (int)min((unsigned)A.uidx[i], (unsigned)(A.n_user - 1))
-                           : A.n_user + (int)min((unsigned)(kind == 1 ? A.p[i] : A.q[i]), (unsigned)A.n_item);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const int u = A.uidx[i], p = A.p[i], q = A.q[i];
+    // (the reference raises IndexError on a bad id; here all three touches of the triple get their part's sentinel, the triple is counted once
+    // and its NaN loss written: poi_ctx_take_bad_ids)
+    const bool bad = (unsigned)u >= (unsigned)A.n_user || (unsigned)p > (unsigned)A.n_item || (unsigned)q > (unsigned)A.n_item;
+    if (bad) { atomicAdd(A.bad, 1); A.loss[i] = __int_as_float(0x7fc00000); }
+    A.keys0[i] = bad ? bpr_user_sentinel(A) : u;
+    A.keys0[n + i] = bad ? bpr_poi_sentinel(A) : bpr_poi_base(A) + p;
+    A.keys0[2 * n + i] = bad ? bpr_poi_sentinel(A) : bpr_poi_base(A) + q;
   }
 }
 
@@ -108,7 +120,7 @@ __device__ __forceinline__ void bpr_apply(const BprArgs& A, int key, const BprVe
       const size_t off = (size_t)key * D + col;
       *reinterpret_cast<float4*>(A.shadow + off) = bpr_rule(*reinterpret_cast<const float4*>(A.ux + off), sum.v[t], sc, inv, A.lambda);
     } else {
-      const size_t off = (size_t)(key - A.n_user) * D + col;
+      const size_t off = (size_t)(key - bpr_poi_base(A)) * D + col;
       st4t_sr(A.lt, off, A.lt_f16, bpr_rule(ld4t(A.lt, off, A.lt_f16), sum.v[t], sc, inv, A.lambda), A.sr_salt, off);
     }
   }
@@ -124,6 +136,7 @@ __global__ __launch_bounds__(256) void bpr_chunk_kernel(BprArgs A) {
   const int part_b = PART ? n : 0, part_e = PART ? 3 * n : n;
   const int n_chunk = (part_e - part_b + 63) / 64;
   const int chunk0 = PART ? (n + 63) / 64 : 0;
+  const int sentinel = PART ? bpr_poi_sentinel(A) : bpr_user_sentinel(A);
   for (int c = blockIdx.x * 4 + wave_id(); c < n_chunk; c += gridDim.x * 4) {
     const int j0 = part_b + 64 * c, nv = min(64, part_e - j0);
     const bool valid = lane < nv;
@@ -139,6 +152,7 @@ __global__ __launch_bounds__(256) void bpr_chunk_kernel(BprArgs A) {
       const unsigned long long above = a + 1 < 64 ? (starts >> (a + 1)) << (a + 1) : 0ull;
       const int b = above ? min(nv, (int)__builtin_ctzll(above)) : nv;
       const int row = __builtin_amdgcn_readfirstlane(__shfl(key, a, 64));
+      if (row == sentinel) break;      // rejected triples sort last in their part: nothing after them
       const bool cont_before = a == 0 && !(starts & 1ull);
       const bool cont_after = b == nv && nextk == row;
       BprVec<NT> acc; bpr_zero<LPR, NT>(acc);
@@ -188,9 +202,8 @@ __global__ __launch_bounds__(256) void bpr_chunk_kernel(BprArgs A) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) dot += dot4(ur.v[t], x[u].v[t]);
             dot = xor_group_sum<LPR>(dot);
-            const bool bad = (unsigned)A.uidx[tri[u]] >= (unsigned)A.n_user || (unsigned)A.p[tri[u]] > (unsigned)A.n_item || (unsigned)A.q[tri[u]] > (unsigned)A.n_item;
-            sg[u] = (ok[u] && !bad) ? -sigmoidf_(-dot) : 0.f;      // (a triple with an id outside its table moves nothing)
-            if (ok[u] && gl == 0) { A.g[tri[u]] = sg[u]; A.loss[tri[u]] = bad ? __int_as_float(0x7fc00000) : -log_sigmoidf_(dot); }
+            sg[u] = ok[u] ? -sigmoidf_(-dot) : 0.f;      // (every touch in a run belongs to a triple with all three ids inside their tables)
+            if (ok[u] && gl == 0) { A.g[tri[u]] = sg[u]; A.loss[tri[u]] = -log_sigmoidf_(dot); }
           }
         }
 #pragma unroll
@@ -276,7 +289,7 @@ __global__ __launch_bounds__(256) void bpr_commit_kernel(BprArgs A) {
     const int key = valid ? A.ks[j0 + lane] : -1;
     const int up = __shfl_up(key, 1, 64);
     const int prev = lane == 0 ? (c > 0 ? A.ks[j0 - 1] : -2) : up;
-    const int st = (valid && key != prev) ? key : -1;
+    const int st = (valid && key != prev && key != bpr_user_sentinel(A)) ? key : -1;      // (the sentinel has no shadow row)
     for (int l0 = 0; l0 < nv; l0 += EPW) {
       const int row = __shfl(st, (l0 + grp) & 63, 64);
       if (l0 + grp >= nv || row < 0) continue;
@@ -293,9 +306,9 @@ template <int LPR, int NT>
 static hipError_t launch_bpr_snapshot_t(BprArgs& A, int num_cu, hipStream_t st, Timing* tm) {
   const int n = A.n;
   tm->begin("bpr_sort", st);
-  hipLaunchKernelGGL(bpr_keys_kernel, dim3(min(num_cu * 8, (3 * n + 255) / 256)), dim3(256), 0, st, A);
+  hipLaunchKernelGGL(bpr_keys_kernel, dim3(min(num_cu * 8, (n + 255) / 256)), dim3(256), 0, st, A);
   int bits = 1;
-  while ((1ll << bits) < (long long)A.n_user + A.n_item + 2) ++bits;
+  while ((1ll << bits) <= (long long)A.n_user + A.n_item + 2) ++bits;      // (largest key: the POI sentinel)
   const int *ks = nullptr, *vs = nullptr;
   hipError_t e = launch_radix_sort(A.keys0, A.keys1, A.vals0, A.vals1, A.cnt, bits, A.hist, st, &ks, &vs);
   if (e != hipSuccess) return e;

@@ -172,7 +172,8 @@ def test_bpr_snapshot_fuzz_sizes_and_dims(pa):
 @pytest.mark.parametrize("mode", ["snapshot", "hogwild"])
 def test_out_of_range_ids_raise_like_the_reference_and_move_nothing(pa, mode):
     """ADVICE r5 / include/poi_hip.h ABI 6: the reference's gather raises IndexError on an id outside its table (public/BPR.py:214-218).  Here the
-    triple gets no gradient and a NaN loss, nothing is written outside the tables, the device counts it and the Python mirror raises IndexError."""
+    triple gets no gradient and a NaN loss, nothing is written outside the tables, the device counts it ONCE and the Python mirror raises IndexError;
+    in snapshot mode the launch equals the launch without the triple, bit for bit (every placement and kind: tests/test_gpu_rejected.py)."""
     import torch
     n_user, n_item, D = 40, 90, 64
     T = toy_problem(3, n_user=n_user, n_item=n_item, n_dist=10, dim=D, len_max=6)
@@ -188,7 +189,15 @@ def test_out_of_range_ids_raise_like_the_reference_and_move_nothing(pa, mode):
         loss = loss.cpu().numpy()
         assert np.isnan(loss[bad[0]]) and np.isfinite(np.delete(loss, bad[0])).all()
         assert torch.isfinite(m.ux.t).all() and torch.isfinite(m.lt.t).all()
-        assert m.ctx.take_bad_ids() >= 1 and m.ctx.take_bad_ids() == 0          # counted, then cleared
+        assert m.ctx.take_bad_ids() == 1 and m.ctx.take_bad_ids() == 0          # counted once per triple, then cleared
+        if mode == "snapshot":      # the launch equals the launch without the triple, bit for bit (hogwild is racy on this fixture's shared rows)
+            with_bad = (m.ux.t.clone(), m.lt.t.clone())
+            m.ux.t.copy_(guard_u); m.lt.t.copy_(guard_i)
+            keep = np.delete(np.arange(len(u)), bad[0])
+            clean = m.train_batch(u[keep], p[keep], q[keep], mode=mode, sync=False).cpu().numpy()
+            assert m.ctx.take_bad_ids() == 0
+            assert torch.equal(with_bad[0], m.ux.t) and torch.equal(with_bad[1], m.lt.t), bad
+            assert np.array_equal(loss[keep].view(np.uint32), clean.view(np.uint32))
         m.ux.t.copy_(guard_u); m.lt.t.copy_(guard_i)
         with pytest.raises(IndexError):
             m.train_batch(ub, pb, qb, mode=mode)
