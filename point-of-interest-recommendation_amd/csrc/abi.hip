@@ -132,6 +132,9 @@ int poi_ctx_create(poi_ctx** out, int device) {
   if (const char* e = getenv("POI_CARNN_FAST")) c->carnn_fast = atoi(e) != 0;
   if (const char* e = getenv("POI_GRAPH")) c->graph_mode = atoi(e) != 0;
   if (const char* e = getenv("POI_TOPK_FILTER")) c->topk_filter = atoi(e) != 0;
+  if (const char* e = getenv("POI_SF_ITEMS")) c->sf_items_env = atoi(e) != 0;
+  if (const char* e = getenv("POI_SF_NSPLIT")) c->sf_nsplit = atoi(e);
+  if (const char* e = getenv("POI_SCORE_DBG")) c->score_dbg = atoi(e);
   if (const char* e = getenv("POI_ENGINE")) { if (!strcmp(e, "seq")) c->engine = 1; else if (!strcmp(e, "tile")) c->engine = 2; else if (!strcmp(e, "exact")) c->engine = 4; }
   if (hipSetDevice(device) != hipSuccess) { delete c; return fail(nullptr, POI_EHIP, "hipSetDevice failed"); }
   const char* sd = getenv("POI_TE_SIDE");

@@ -141,7 +141,10 @@ struct poi_ctx {
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)
   DevBuf users_pk16, ubound, ugeo;      // item-stationary GEO filter: users' half fragments, per-user bound terms, last-POI coordinates
-  int sf_items = -1;        // poi_ctx_set_topk_filter(ctx, 2 / 3): force / forbid the item-stationary GEO filter (-1: by shape)
+  int sf_items = -1;        // poi_ctx_set_topk_filter(ctx, 2 / 3): force / forbid the item-stationary GEO filter (-1: POI_SF_ITEMS, then by shape)
+  int sf_items_env = -1;    // POI_SF_ITEMS=1|0: the same, for A/B runs (-1: by shape)
+  int sf_nsplit = 0;        // POI_SF_NSPLIT=<n>: item ranges of the filter pass (tuning; below 4: by shape)
+  int score_dbg = 0;        // POI_SCORE_DBG: ScoreArgs.dbg (tuning, 0 in production)
   int f16_rounding = 0;     // poi_ctx_set_f16_rounding: 0 nearest, 1 stochastic (write-back of a half POI table)
   unsigned sr_counter = 0;  // launches so far (salt of the stochastic rounding)
   int topk_filter = 1;      // poi_ctx_set_topk_filter / POI_TOPK_FILTER=0: one-stage float32 kernel only

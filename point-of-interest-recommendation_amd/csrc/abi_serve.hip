@@ -1,5 +1,6 @@
 // C-ABI of libpoi_hip.so (see include/poi_hip.h): everything that answers a query - scoring, top-K, ranks, sessions, fold-ins, metrics, samplers, deltas.
 #include "abi_internal.h"
+#include "score_plan.h"
 
 #include <limits.h>
 #include <math.h>
@@ -354,138 +355,74 @@ static int score_common(poi_ctx* c, const float* users, const float* items, int3
   if (n == 0) return POI_OK;
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(c, hipSetDevice(c->device));
+  // plan: every decision of the call (score_plan.h), from its shape and the context's settings alone
+  ScoreShape S = {};
+  S.n = n; S.n_item = n_item; S.dim = dim; S.k = k; S.all_scores = scores != nullptr; S.seed_k = seed_idx ? seed_k : 0;
+  S.dist = U ? (!U->bins ? SCORE_DIST_GEO : U->bin_bytes == 1 ? SCORE_DIST_BINS8 : SCORE_DIST_BINS16) : prob ? SCORE_DIST_PROB : SCORE_DIST_NONE;
+  S.n_dist = U ? U->n_dist : 0;
+  // (item-stationary filter: poi_ctx_set_topk_filter(2 / 3) first, then POI_SF_ITEMS, then the shape)
+  const ScoreSettings C = {c->num_cu, c->score_variant, c->topk_filter, c->sf_items >= 0 ? c->sf_items : c->sf_items_env, c->sf_nsplit};
+  const ScorePlan P = plan_score(S, C);
+  // allocate: all of the call's buffers, before the first launch
+  struct { DevBuf& b; size_t bytes; } const need[] = {
+      {c->items_pk, P.b_items_pk}, {c->cand_s, P.b_cand_s}, {c->cand_i, P.b_cand_i}, {c->gbound, P.b_gbound}, {c->pre_idx, P.b_pre_idx}, {c->pre_sc, P.b_pre_sc},
+      {c->items_pk16, P.b_items_pk16}, {c->inorm, P.b_inorm}, {c->surv_cnt, P.b_surv_cnt}, {c->surv_idx, P.b_surv_idx}, {c->surv_sc, P.b_surv_sc}, {c->tflag, P.b_tflag},
+      {c->users_pk16, P.b_users_pk16}, {c->ubound, P.b_ubound}, {c->ugeo, P.b_ugeo}};
+  for (const auto& e : need) if (int rc = ensure(c, e.b, e.bytes, st)) return rc;
+  // launch
+  const int n_utile = (n + 31) / 32, n_pad = n_utile * 32, ntile = (n_item + 31) / 32;
   poi::ScoreArgs A;
   memset(&A, 0, sizeof A);
   A.users = users; A.items = items; A.items_f16 = is_f16(c, items); A.n = n; A.n_item = n_item; A.dim = dim; A.wd = wd; A.prob = prob;
   A.scores = scores; A.k = k; A.idx_out = idx_out; A.score_out = score_out;
   if (U) { A.ulptai = U->bins; A.bin_bytes = U->bin_bytes; A.sts = U->sts; A.n_dist = U->n_dist; }
   if (U && !U->bins) { A.geo = 1; A.coords = U->coords; A.cphi = U->cphi; A.thr = U->thr; A.last_poi = U->last_poi; A.dd = U->dd; }
-  if (const char* e = getenv("POI_SCORE_DBG")) A.dbg = atoi(e);
-  const int ntile = (n_item + 31) / 32;
-  // variant: 0 = one item stream per wave (row-per-lane loads; small n or dim > 128), 1 = packed item
-  // stream per wave with the user tile's A fragments in LDS (default for n >= 128)
-  int variant = (n >= 128 && dim <= 128) ? 1 : 0;
-  if (c->score_variant >= 0 && dim <= 128) variant = c->score_variant;
-  if (U && U->bins) variant = 1;      // the bin matrix is laid out for the packed-stream kernel
-  if (U && !U->bins) variant = 0;     // bins on the fly: the row-per-lane kernel (any dim <= 256)
-  // ... or, for enough users to fill the chip with eight-wave workgroups and a wide model, the packed-stream GEO kernel
-  if (U && !U->bins && k > 0 && n >= 1024 && dim >= 128 && poi::score_geo_stream_lds(dim, U->n_dist) <= 160 * 1024 && c->score_variant != 0) variant = 2;
-  const int n_utile = (n + 31) / 32;
-  // item ranges per user tile for a table of nt item tiles: long item streams keep per-user thresholds high (few top-K compactions)
-  auto splits_for = [&](int nt) {
-    int want = (c->num_cu * 8 + n_utile - 1) / n_utile;   // 8 waves per CU
-    if (want > nt / 8) want = nt / 8;          // >= 8 tiles per stream: amortise the per-wave top-K epilogue
-    if (want < 1) want = 1;
-    if (want < (nt + 2046) / 2047) want = (nt + 2046) / 2047;      // candidate lists hold 16-bit item offsets: < 65536 items per range
-    return variant == 2 ? ((want + 7) / 8) * 8 : ((want + 3) / 4) * 4;
-  };
-  const int n_split = splits_for(ntile);
-  A.n_split = n_split;
-  const int n_pad = n_utile * 32;
-  int rc;
-  // one-stage kernel of the chosen variant + merge of the per-range lists, on the item table X describes
-  auto one_stage = [&](poi::ScoreArgs& X) -> int {
-    const int nt = (X.n_item + 31) / 32;
-    if (variant == 2) {
-      const int d8 = dim <= 128 ? 16 : 32;
-      int r2 = ensure(c, c->items_pk, sizeof(float) * 4 * (size_t)nt * d8 * 64, st);
-      if (r2) return r2;
-      X.items_packed = (float4*)c->items_pk.p;
-      HIPCHK(c, poi::launch_score_geo_stream(X, st, &c->tm));
-    } else if (variant == 1) {
-      const int d8 = dim <= 32 ? 4 : dim <= 64 ? 8 : 16;
-      int r2 = ensure(c, c->items_pk, sizeof(float) * 4 * (size_t)nt * d8 * 64, st);
-      if (r2) return r2;
-      X.items_packed = (float4*)c->items_pk.p;
-      HIPCHK(c, poi::launch_score_packed(X, st, &c->tm));
-    } else {
-      HIPCHK(c, poi::launch_score(X, st, &c->tm));
-    }
+  A.dbg = c->score_dbg;
+  A.n_split = P.n_split;
+  if (P.variant) A.items_packed = (float4*)c->items_pk.p;
+  // one-stage kernel of the plan's variant + merge of the per-range lists, on the item table X describes
+  auto one_stage = [&](const poi::ScoreArgs& X) -> int {
+    if (P.variant == 2) HIPCHK(c, poi::launch_score_geo_stream(X, st, &c->tm));
+    else if (P.variant == 1) HIPCHK(c, poi::launch_score_packed(X, st, &c->tm));
+    else HIPCHK(c, poi::launch_score(X, st, &c->tm));
     if (k > 0) HIPCHK(c, poi::launch_topk_merge(X, X.n_split, n_pad, st));
     return POI_OK;
   };
-  bool two_stage = false, use_maxpass = false;
-  if (k > 0) {
-    const size_t cand = (size_t)n_split * n_pad * k;
-    if ((rc = ensure(c, c->cand_s, sizeof(float) * cand, st))) return rc;
-    if ((rc = ensure(c, c->cand_i, sizeof(int) * cand, st))) return rc;
-    A.cand_score = (float*)c->cand_s.p; A.cand_idx = (int*)c->cand_i.p;
-    const bool seeded = seed_idx && seed_k >= k && seed_k <= 64;
-    {
-      poi::ScoreArgs probe = A; probe.seeded = 1;
-      two_stage = c->topk_filter && (variant == 1 || A.geo) && poi::score_two_stage_supported(probe);
-    }
-    // SELF-SEEDING pre-pass of the two-stage path: the one-stage kernel on the first 1/16 of the item tiles (1/64 when the caller's
-    // seed already gave bounds) - the K-th best EXACT score of any subset is a lower bound of the final K-th best, so the filter pass
-    // starts from thresholds that leave ~16 K (64 K) survivors per user whatever the seed holds: an unseeded call (the first evaluation
-    // of a run) or a useless seed (a model that moved a lot) no longer sends its tiles to the one-stage kernel.  Unseeded calls always
-    // take it; seeded ones when the table has >= 2^20 items (there it costs < 2 % of the call).
-    const int sub_tiles = !two_stage ? 0 : !seeded ? (ntile >= 256 ? ntile / 16 : 0) : (n_item >= (1 << 20) ? ntile / 64 : 0);
-    if (two_stage && !seeded && sub_tiles == 0) two_stage = false;      // (a small table and no seed: one-stage)
-    if (n_split > 1 || seeded || two_stage) {
-      if ((rc = ensure(c, c->gbound, sizeof(unsigned) * (size_t)n_pad, st))) return rc;
-      HIPCHK(c, hipMemsetAsync(c->gbound.p, 0, sizeof(unsigned) * (size_t)n_pad, st));
-      A.gbound = (unsigned*)c->gbound.p;
-    }
-    if (seeded) {
-      c->tm.begin("topk_seed", st);
-      HIPCHK(c, poi::launch_topk_seed(A, seed_idx, seed_k, st));
-      c->tm.end(st);
-      A.seeded = 1;
-    }
-    // unseeded, resident bin matrix / no distance term, dims 64 / 128: thresholds from the block maxima of the f16 lower bounds instead
-    // (score_filter.hip, MAXP: one f16 pass over ALL items, ~1.3 K survivors per user against ~17 K of the float32 prefix pre-pass)
-    use_maxpass = two_stage && !seeded && sub_tiles > 0 && poi::score_maxpass_supported(A);
-    if (const char* e = getenv("POI_SF_MAXPASS")) use_maxpass = use_maxpass && atoi(e) != 0;
-    if (two_stage && sub_tiles > 0 && !use_maxpass) {
-      if ((rc = ensure(c, c->pre_idx, sizeof(int) * (size_t)n_pad * k, st)) || (rc = ensure(c, c->pre_sc, sizeof(float) * (size_t)n_pad * k, st))) return rc;
-      poi::ScoreArgs S = A;
-      S.n_item = sub_tiles * 32; S.bins_ntile = ntile; S.n_split = splits_for(sub_tiles);
-      S.idx_out = (int*)c->pre_idx.p; S.score_out = (float*)c->pre_sc.p;
-      if ((size_t)S.n_split * n_pad * k > cand) {
-        if ((rc = ensure(c, c->cand_s, sizeof(float) * (size_t)S.n_split * n_pad * k, st)) || (rc = ensure(c, c->cand_i, sizeof(int) * (size_t)S.n_split * n_pad * k, st))) return rc;
-        A.cand_score = S.cand_score = (float*)c->cand_s.p; A.cand_idx = S.cand_idx = (int*)c->cand_i.p;
-      }
-      if ((rc = one_stage(S))) return rc;
-      HIPCHK(c, poi::launch_topk_bound(S.score_out, n, k, A.gbound, st));
-      A.seeded = 1;
-    }
+  if (k > 0) { A.cand_score = (float*)c->cand_s.p; A.cand_idx = (int*)c->cand_i.p; }
+  if (P.gbound) {
+    HIPCHK(c, hipMemsetAsync(c->gbound.p, 0, sizeof(unsigned) * (size_t)n_pad, st));
+    A.gbound = (unsigned*)c->gbound.p;
   }
-  if (two_stage) {
-    // two-stage: f16 filter pass + exact float32 rescoring of the survivors (score_filter.hip); the one-stage kernel below then only
-    // runs the user tiles whose survivor lists overflowed (A.tile_flag)
-    const int kg = dim / 16, cap = poi::score_filter_cap();
-    if ((rc = ensure(c, c->items_pk16, sizeof(uint4) * (size_t)ntile * kg * 64, st)) || (rc = ensure(c, c->inorm, sizeof(float2) * (size_t)ntile * 32, st)) ||
-        (rc = ensure(c, c->surv_cnt, sizeof(int) * (size_t)n_pad, st)) || (rc = ensure(c, c->surv_idx, sizeof(int) * (size_t)n_pad * cap, st)) ||
-        (rc = ensure(c, c->surv_sc, sizeof(float) * (size_t)n_pad * cap, st)) ||
-        (rc = ensure(c, c->tflag, sizeof(int) * (size_t)n_utile, st))) return rc;
+  if (P.seeded) {
+    c->tm.begin("topk_seed", st);
+    HIPCHK(c, poi::launch_topk_seed(A, seed_idx, seed_k, st));
+    c->tm.end(st);
+    A.seeded = 1;
+  }
+  if (P.pre == SCORE_PRE_PREFIX) {
+    // the one-stage kernel on a prefix of the table -> bounds.  (X is taken before A learns of the two-stage buffers: with a tile_flag the
+    // one-stage kernel would only run flagged tiles)
+    poi::ScoreArgs X = A;
+    X.n_item = P.sub_tiles * 32; X.bins_ntile = ntile; X.n_split = P.pre_split;
+    X.idx_out = (int*)c->pre_idx.p; X.score_out = (float*)c->pre_sc.p;
+    if (int rc = one_stage(X)) return rc;
+    HIPCHK(c, poi::launch_topk_bound(X.score_out, n, k, A.gbound, st));
+    A.seeded = 1;
+  }
+  if (P.two_stage) {
+    // f16 filter pass + exact float32 rescoring of the survivors (score_filter.hip); the one-stage kernel below then only runs the user
+    // tiles whose survivor lists overflowed (A.tile_flag)
     HIPCHK(c, hipMemsetAsync(c->surv_cnt.p, 0, sizeof(int) * (size_t)n_pad, st));
     HIPCHK(c, hipMemsetAsync(c->tflag.p, 0, sizeof(int) * (size_t)n_utile, st));
     A.items_packed16 = (const uint4*)c->items_pk16.p; A.inorm = (const float2*)c->inorm.p;
     A.surv_cnt = (int*)c->surv_cnt.p; A.surv_idx = (int*)c->surv_idx.p; A.surv_sc = (float*)c->surv_sc.p; A.tile_flag = (int*)c->tflag.p;
-    // GEO with a huge item table and few users (config X's evaluation): the item-stationary filter - every user tile's own pass over the
-    // item table is 1.3 TB at 8192 users x 10 M POIs; forced (2) / forbidden (0) by POI_SF_ITEMS for tests and A/B runs
     A.n_cu = c->num_cu;
-    {
-      int items_mode = (A.geo && n_item >= (1 << 20) && n_utile <= 4096) ? 1 : 0;
-      if (const char* e = getenv("POI_SF_ITEMS")) items_mode = A.geo ? (atoi(e) != 0) : 0;
-      if (c->sf_items >= 0) items_mode = A.geo ? c->sf_items : 0;
-      if (items_mode) {
-        if ((rc = ensure(c, c->users_pk16, sizeof(uint4) * (size_t)n_utile * kg * 64, st)) || (rc = ensure(c, c->ubound, sizeof(float) * 4 * (size_t)n_pad, st)) ||
-            (rc = ensure(c, c->ugeo, sizeof(double) * 3 * (size_t)n_pad, st))) return rc;
-        A.users_packed16 = (uint4*)c->users_pk16.p; A.ubound = (float4*)c->ubound.p; A.ugeo = (double*)c->ugeo.p;
-      }
-    }
-    int nsf = ((4 * c->num_cu + n_utile - 1) / n_utile) * 4;      // >= 4 workgroups (16 waves) per CU
-    if (nsf < 16) nsf = 16;      // (swept at the Gowalla shape: 8 / 16 / 32 / 64 / 128 ranges -> 3.09 / 2.84 / 2.80 / 2.86 / 3.21 ms of filter time)
-    if (const char* e = getenv("POI_SF_NSPLIT")) { const int v = atoi(e); if (v >= 4) nsf = (v / 4) * 4; }      // tuning switch
-    if (nsf > (ntile / 4) * 4) nsf = (ntile / 4) * 4;
-    if (nsf < 4) nsf = 4;
-    if (use_maxpass) {
-      HIPCHK(c, poi::launch_score_maxpass(A, nsf, st, &c->tm));
+    if (P.items) { A.users_packed16 = (uint4*)c->users_pk16.p; A.ubound = (float4*)c->ubound.p; A.ugeo = (double*)c->ugeo.p; }
+    if (P.pre == SCORE_PRE_MAXPASS) {
+      HIPCHK(c, poi::launch_score_maxpass(A, P, st, &c->tm));
       A.seeded = 1;
     }
-    HIPCHK(c, poi::launch_score_two_stage(A, nsf, st, &c->tm));
+    HIPCHK(c, poi::launch_score_two_stage(A, P, st, &c->tm));
     c->last_two_n = n; c->last_two_tiles = n_utile;
   }
   return one_stage(A);

@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+struct ScorePlan;      // score_plan.h
+
 namespace poi {
 
 // Optional per-kernel timing with HIP events recorded on the launch stream (bench.py's live
@@ -850,11 +852,9 @@ struct ScoreArgs {
   uint4* users_packed16; float4* ubound; double* ugeo; int n_cu;
   int bins_ntile;           // item tiles per user-tile row of the bin matrix when the call scores only a PREFIX of the item table (0: = tiles of n_item)
 };
-bool score_two_stage_supported(const ScoreArgs& A);
-hipError_t launch_score_two_stage(const ScoreArgs& A, int n_split_f, hipStream_t st, Timing* tm);
-bool score_maxpass_supported(const ScoreArgs& A);
-hipError_t launch_score_maxpass(const ScoreArgs& A, int n_split_f, hipStream_t st, Timing* tm);      // unseeded calls: thresholds from block maxima of the f16 lower bounds
-int score_filter_cap();
+// two-stage path (score_filter.hip); every grid, LDS size and kernel choice comes from the call's plan (score_plan.h)
+hipError_t launch_score_two_stage(const ScoreArgs& A, const ScorePlan& P, hipStream_t st, Timing* tm);
+hipError_t launch_score_maxpass(const ScoreArgs& A, const ScorePlan& P, hipStream_t st, Timing* tm);      // unseeded calls: thresholds from block maxima of the f16 lower bounds
 hipError_t launch_topk_bound(const float* score_k, int n, int k, unsigned* gbound, hipStream_t st);
 hipError_t launch_ulptai(const double* coords, const double* cphi, const double* thr, const int* last_poi, int n, int n_item,
                          int n_dist, double dd, void* out, int bin_bytes, hipStream_t st);
@@ -862,7 +862,6 @@ hipError_t launch_score(const ScoreArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_score_packed(const ScoreArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_topk_seed(const ScoreArgs& A, const int* seed, int k_seed, hipStream_t st);
 hipError_t launch_score_geo_stream(const ScoreArgs& A, hipStream_t st, Timing* tm);
-size_t score_geo_stream_lds(int dim, int n_dist);
 hipError_t launch_topk_merge(const ScoreArgs& A, int n_lists, int n_pad, hipStream_t st);
 hipError_t launch_topk_rows(const float* scores, int n, int n_item, int k, int* idx_out, float* score_out, hipStream_t st);
 

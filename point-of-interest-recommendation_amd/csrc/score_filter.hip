@@ -20,8 +20,8 @@
 // overflowing tiles take the exact path.  tests: test_gpu_parity.py (two-stage == one-stage, ids AND scores), tools/fuzz_score.py.
 #include "poi_common.h"
 #include "poi_kernels.h"
+#include "score_plan.h"
 #include <limits.h>
-#include <stdlib.h>
 
 namespace poi {
 
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void pack_items_f16_kernel(const float* __rest
   if (s == 0 && valid) inorm[gi] = make_float2(bad ? INFINITY : sqrtf(n2) * 1.000002f, n1 * (2.98023224e-8f * 1.01f));
 }
 
-#define SF_CAP 4096       // survivor slots per user in global memory (good seeds leave ~K + 1 of them, the self-seeding pre-pass ~16 K; an overflow flags the tile).  8 bytes per slot: a 65536-user call pins 2 GB of grow-only context memory
+// SF_CAP, the survivor slots per user in global memory: score_plan.h
 
 // stage 1.  BINS: 0 = no distance term, 1 / 2 = resident bin matrix (uint8 / uint16, misc.hip::ulptai_kernel) + the users' bin probabilities,
 // 3 = GEO: bins computed on the fly from the coordinates (poi_score_topk_geo: no U x N matrix; config X) - only for the pairs whose
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(256, 2) void score_filter_items_kernel(ScoreArgs A,
   // Work unit = (chunk of user tiles, group of four item tiles), the chunk the SLOW index: every workgroup of the chip is on the same ~1 MB
   // of user fragments at a time, which then live in the 4 MB L2 of every XCD; the item table is re-read once per chunk (x 4 at 8192 users:
   // 20 GB from HBM).
-  const int uc = max(1, (1 << 20) / (KG * 1024)), n_chunk = (n_utile + uc - 1) / uc;
+  const int uc = max(1, score_items_chunk(D)), n_chunk = (n_utile + uc - 1) / uc;
   for (long long work = blockIdx.x; work < (long long)groups * n_chunk; work += gridDim.x) {
     const int g = (int)(work % groups), u_lo = (int)(work / groups) * uc, u_hi = min(n_utile, u_lo + uc);
     const int tile = min(4 * g + w, ntile - 1);
@@ -691,74 +691,53 @@ __global__ __launch_bounds__(256) void score_rescore_kernel(ScoreArgs A) {
   }
 }
 
-bool score_two_stage_supported(const ScoreArgs& A) {
-  if (!(A.k > 0 && A.seeded && !A.prob && !A.scores && A.n >= 128 && A.n_dist + 1 <= 1024)) return false;
-  return A.geo ? (A.dim == 64 || A.dim == 128 || A.dim == 256) : (A.dim == 64 || A.dim == 128);      // (the users' bin probabilities live in LDS: 32 x (n_dist + 1) floats)
+// score_filter_kernel<D, BINS, UT, MAXP> on `n_split` item ranges.  The (BINS, UT) pairs that exist: GEO with one user tile per workgroup,
+// a resident bin matrix with one or two, no distance term with two (score_plan.h::score_filter_ut); MAXP and dim 256 are not GEO's / GEO's alone
+template <int D, int BINS, int UT, bool MAXP>
+static hipError_t launch_filter_as(const ScoreArgs& F, const ScorePlan& P, hipStream_t st) {
+  static DeviceOnce once;      // (per device: poi_common.h)
+  const hipError_t oe = once.run([]() { return hipFuncSetAttribute(reinterpret_cast<const void*>(&score_filter_kernel<D, BINS, UT, MAXP>), hipFuncAttributeMaxDynamicSharedMemorySize, SCORE_LDS_MAX); });
+  if (oe != hipSuccess) return oe;
+  const dim3 grid(((F.n + 31) / 32 + UT - 1) / UT, F.n_split / POI_NWAVE);
+  hipLaunchKernelGGL((score_filter_kernel<D, BINS, UT, MAXP>), grid, dim3(256), P.lds_filter, st, F);
+  return hipSuccess;
 }
-
-// user tiles per workgroup: two while both fit twice into a CU's LDS (two workgroups per CU), else one
-static int score_filter_ut(int dim, int n_dist, bool bins, bool geo) {
-  const size_t per_tile = sizeof(float) * ((size_t)(dim / 16) * 64 * 4 + 128 + (bins ? ((32 * (size_t)(n_dist + 1) + 3) & ~(size_t)3) : 0));
-  return (!geo && 2 * per_tile <= 79 * 1024) ? 2 : 1;
-}
-size_t score_filter_lds(int dim, int n_dist, bool bins, bool geo) {
-  const size_t per_tile = sizeof(float) * ((size_t)(dim / 16) * 64 * 4 + 128 + (bins ? ((32 * (size_t)(n_dist + 1) + 3) & ~(size_t)3) : 0));
-  return score_filter_ut(dim, n_dist, bins, geo) * per_tile + (geo ? sizeof(double) * (size_t)(n_dist + 96) + sizeof(float) * 32 : 0);
+template <int D, bool MAXP>
+static hipError_t launch_filter(const ScoreArgs& F, const ScorePlan& P, hipStream_t st) {
+  if constexpr (!MAXP) if (P.bins == 3 && P.ut == 1) return launch_filter_as<D, 3, 1, false>(F, P, st);
+  if constexpr (D <= 128) {
+    if (P.bins == 1) return P.ut == 2 ? launch_filter_as<D, 1, 2, MAXP>(F, P, st) : launch_filter_as<D, 1, 1, MAXP>(F, P, st);
+    if (P.bins == 2) return P.ut == 2 ? launch_filter_as<D, 2, 2, MAXP>(F, P, st) : launch_filter_as<D, 2, 1, MAXP>(F, P, st);
+    if (P.bins == 0 && P.ut == 2) return launch_filter_as<D, 0, 2, MAXP>(F, P, st);
+  }
+  return hipErrorInvalidValue;
 }
 
 template <int D>
-static hipError_t launch_two_stage_t(const ScoreArgs& A, int n_split_f, hipStream_t st, Timing* tm) {
+static hipError_t launch_two_stage_t(const ScoreArgs& A, const ScorePlan& P, hipStream_t st, Timing* tm) {
   const int ntile = (A.n_item + 31) / 32, n_utile = (A.n + 31) / 32;
-  const int bins = A.geo ? 3 : A.ulptai ? (A.bin_bytes == 1 ? 1 : 2) : 0;
   tm->begin("pack_items", st);
   hipLaunchKernelGGL(pack_items_f16_kernel<D>, dim3(ntile), dim3(256), 0, st, A.items, A.items_f16, A.n_item, const_cast<uint4*>(A.items_packed16), const_cast<float2*>(A.inorm));
   tm->end(st);
-  ScoreArgs F = A; F.n_split = n_split_f;
-  const size_t lds = score_filter_lds(D, A.n_dist, bins != 0, bins == 3);
-  const int ut = score_filter_ut(D, A.n_dist, bins != 0, bins == 3);
-  const dim3 grid((n_utile + ut - 1) / ut, n_split_f / POI_NWAVE);
-  static DeviceOnce once;      // (per device: poi_common.h)
-  {
-    const hipError_t oe = once.run([&]() -> hipError_t {
-    hipError_t e = hipSuccess;
-    auto big = [&](const void* f) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
-    big(reinterpret_cast<const void*>(&score_filter_kernel<D, 3, 1>));
-    if constexpr (D <= 128) {
-      big(reinterpret_cast<const void*>(&score_filter_kernel<D, 2, 1>)); big(reinterpret_cast<const void*>(&score_filter_kernel<D, 1, 1>));
-      big(reinterpret_cast<const void*>(&score_filter_kernel<D, 2, 2>)); big(reinterpret_cast<const void*>(&score_filter_kernel<D, 1, 2>));
-      big(reinterpret_cast<const void*>(&score_filter_kernel<D, 0, 2>));
-    }
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&score_rescore_kernel<D / 8, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    return e;
-    });
-    if (oe != hipSuccess) return oe;
-  }
+  ScoreArgs F = A; F.n_split = P.nsf;
+  hipError_t e = hipSuccess;
   tm->begin("score_filter", st);
-  if (bins == 3 && A.users_packed16) {        // item-stationary (huge item table, few users): see score_filter_items_kernel
+  if (P.items) {        // item-stationary (huge item table, few users): see score_filter_items_kernel
     hipLaunchKernelGGL(sf_users_prep_kernel<D>, dim3(n_utile), dim3(256), 0, st, F, A.users_packed16, A.ubound, A.ugeo);
-    const size_t ldsi = sizeof(uint4) * 2 * (D / 16) * 64 + sizeof(float) * (64 + 4) + sizeof(double) * (2 * 96 + (size_t)A.n_dist + 2) + sizeof(int) * ((size_t)n_utile + 4);
-    const int groups = (ntile + 3) / 4;
-    const long long units = (long long)groups * ((n_utile + ((1 << 20) / ((D / 16) * 1024)) - 1) / ((1 << 20) / ((D / 16) * 1024)));
-    const int gridi = units < A.n_cu * 2 ? (int)units : A.n_cu * 2;
-    hipLaunchKernelGGL(score_filter_items_kernel<D>, dim3(gridi), dim3(256), ldsi, st, F, A.users_packed16, A.ubound, A.ugeo, n_utile);
-  } else
-  if (bins == 3) hipLaunchKernelGGL((score_filter_kernel<D, 3, 1>), grid, dim3(256), lds, st, F);
-  else if constexpr (D <= 128) {
-    if (bins == 1 && ut == 2) hipLaunchKernelGGL((score_filter_kernel<D, 1, 2>), grid, dim3(256), lds, st, F);
-    else if (bins == 1) hipLaunchKernelGGL((score_filter_kernel<D, 1, 1>), grid, dim3(256), lds, st, F);
-    else if (bins == 2 && ut == 2) hipLaunchKernelGGL((score_filter_kernel<D, 2, 2>), grid, dim3(256), lds, st, F);
-    else if (bins == 2) hipLaunchKernelGGL((score_filter_kernel<D, 2, 1>), grid, dim3(256), lds, st, F);
-    else hipLaunchKernelGGL((score_filter_kernel<D, 0, 2>), grid, dim3(256), lds, st, F);
-  } else return hipErrorInvalidValue;
+    hipLaunchKernelGGL(score_filter_items_kernel<D>, dim3(P.items_grid), dim3(256), P.lds_items, st, F, A.users_packed16, A.ubound, A.ugeo, n_utile);
+  } else e = launch_filter<D, false>(F, P, st);
   tm->end(st);
+  if (e != hipSuccess) return e;
   constexpr int D8 = D / 8;
-  const size_t lds2 = sizeof(float) * ((size_t)D8 * 64 * 4);
+  static DeviceOnce once;      // (per device: poi_common.h)
+  e = once.run([]() { return hipFuncSetAttribute(reinterpret_cast<const void*>(&score_rescore_kernel<D8, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); });
+  if (e != hipSuccess) return e;
   tm->begin("score_rescore", st);
-  if (bins == 3) hipLaunchKernelGGL((score_rescore_kernel<D8, 3>), dim3(n_utile), dim3(256), lds2, st, A);
+  if (P.bins == 3) hipLaunchKernelGGL((score_rescore_kernel<D8, 3>), dim3(n_utile), dim3(256), P.lds_rescore, st, A);
   else if constexpr (D <= 128) {
-    if (bins == 1) hipLaunchKernelGGL((score_rescore_kernel<D8, 1>), dim3(n_utile), dim3(256), lds2, st, A);
-    else if (bins == 2) hipLaunchKernelGGL((score_rescore_kernel<D8, 2>), dim3(n_utile), dim3(256), lds2, st, A);
-    else hipLaunchKernelGGL((score_rescore_kernel<D8, 0>), dim3(n_utile), dim3(256), lds2, st, A);
+    if (P.bins == 1) hipLaunchKernelGGL((score_rescore_kernel<D8, 1>), dim3(n_utile), dim3(256), P.lds_rescore, st, A);
+    else if (P.bins == 2) hipLaunchKernelGGL((score_rescore_kernel<D8, 2>), dim3(n_utile), dim3(256), P.lds_rescore, st, A);
+    else hipLaunchKernelGGL((score_rescore_kernel<D8, 0>), dim3(n_utile), dim3(256), P.lds_rescore, st, A);
   }
   tm->end(st);
   return hipGetLastError();
@@ -767,65 +746,36 @@ static hipError_t launch_two_stage_t(const ScoreArgs& A, int n_split_f, hipStrea
 // self-seeding of an unseeded call (resident bin matrix or no distance term, dims 64 / 128): block maxima of the approximate lower bounds +
 // K-th largest per user -> gbound.  Uses surv_sc as scratch and leaves the packed items / norms for the filter pass.
 template <int D>
-static hipError_t launch_maxpass_t(const ScoreArgs& A, int n_split_f, hipStream_t st, Timing* tm) {
-  if constexpr (D > 128) { return hipErrorInvalidValue; } else {
-  const int ntile = (A.n_item + 31) / 32, n_utile = (A.n + 31) / 32;
-  const int bins = A.ulptai ? (A.bin_bytes == 1 ? 1 : 2) : 0;
-  int nsm = n_split_f >= 64 ? 64 : n_split_f >= 32 ? 32 : 16;      // 512 .. 2048 blocks per user
-  if (const char* e = getenv("POI_SF_NSM")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64) nsm = v; }      // tuning switch
+static hipError_t launch_maxpass_t(const ScoreArgs& A, const ScorePlan& P, hipStream_t st, Timing* tm) {
+  const int ntile = (A.n_item + 31) / 32;
   tm->begin("pack_items", st);
   hipLaunchKernelGGL(pack_items_f16_kernel<D>, dim3(ntile), dim3(256), 0, st, A.items, A.items_f16, A.n_item, const_cast<uint4*>(A.items_packed16), const_cast<float2*>(A.inorm));
   tm->end(st);
-  ScoreArgs F = A; F.n_split = nsm;
-  // every second item tile: the K-th largest block maximum over half of the items is about the 2 K-th best score - 40 survivors per user
-  // instead of 21 for half of this pass (measured at the Gowalla shape, strides 1 / 2 / 4 / 8: 6.5 / 5.2 / 5.3 / 6.6 ms per unseeded call)
-  F.max_stride = ntile >= 64 * 8 ? 2 : 1;
-  if (const char* e = getenv("POI_SF_MAXSTRIDE")) { const int v = atoi(e); if (v >= 1 && v <= 16) F.max_stride = v; }      // tuning switch
-  const size_t lds = score_filter_lds(D, A.n_dist, bins != 0, false);
-  const int ut = score_filter_ut(D, A.n_dist, bins != 0, false);
-  const dim3 grid((n_utile + ut - 1) / ut, nsm / POI_NWAVE);
-  static DeviceOnce once;
-  {
-    const hipError_t oe = once.run([&]() -> hipError_t {
-    hipError_t e = hipSuccess;
-    auto big = [&](const void* f) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
-    big(reinterpret_cast<const void*>(&score_filter_kernel<D, 2, 1, true>)); big(reinterpret_cast<const void*>(&score_filter_kernel<D, 1, 1, true>));
-    big(reinterpret_cast<const void*>(&score_filter_kernel<D, 2, 2, true>)); big(reinterpret_cast<const void*>(&score_filter_kernel<D, 1, 2, true>));
-    big(reinterpret_cast<const void*>(&score_filter_kernel<D, 0, 2, true>));
-    return e;
-    });
-    if (oe != hipSuccess) return oe;
-  }
+  ScoreArgs F = A; F.n_split = P.nsm; F.max_stride = P.max_stride;
   tm->begin("score_maxpass", st);
-  if (bins == 1 && ut == 2) hipLaunchKernelGGL((score_filter_kernel<D, 1, 2, true>), grid, dim3(256), lds, st, F);
-  else if (bins == 1) hipLaunchKernelGGL((score_filter_kernel<D, 1, 1, true>), grid, dim3(256), lds, st, F);
-  else if (bins == 2 && ut == 2) hipLaunchKernelGGL((score_filter_kernel<D, 2, 2, true>), grid, dim3(256), lds, st, F);
-  else if (bins == 2) hipLaunchKernelGGL((score_filter_kernel<D, 2, 1, true>), grid, dim3(256), lds, st, F);
-  else hipLaunchKernelGGL((score_filter_kernel<D, 0, 2, true>), grid, dim3(256), lds, st, F);
-  const dim3 gs((A.n + POI_NWAVE - 1) / POI_NWAVE);
-  if (nsm == 64) hipLaunchKernelGGL(sf_select_kernel<32>, gs, dim3(256), 0, st, F, A.k);
-  else if (nsm == 32) hipLaunchKernelGGL(sf_select_kernel<16>, gs, dim3(256), 0, st, F, A.k);
-  else hipLaunchKernelGGL(sf_select_kernel<8>, gs, dim3(256), 0, st, F, A.k);
-  tm->end(st);
-  return hipGetLastError();
+  const hipError_t e = launch_filter<D, true>(F, P, st);
+  if (e == hipSuccess) {
+    const dim3 gs((A.n + POI_NWAVE - 1) / POI_NWAVE);
+    if (P.nsm == 64) hipLaunchKernelGGL(sf_select_kernel<32>, gs, dim3(256), 0, st, F, A.k);
+    else if (P.nsm == 32) hipLaunchKernelGGL(sf_select_kernel<16>, gs, dim3(256), 0, st, F, A.k);
+    else hipLaunchKernelGGL(sf_select_kernel<8>, gs, dim3(256), 0, st, F, A.k);
   }
+  tm->end(st);
+  return e != hipSuccess ? e : hipGetLastError();
 }
-bool score_maxpass_supported(const ScoreArgs& A) { return !A.geo && (A.dim == 64 || A.dim == 128) && A.k > 0 && A.k <= 64 && (A.n_item + 31) / 32 >= 64 * 4; }
-hipError_t launch_score_maxpass(const ScoreArgs& A, int n_split_f, hipStream_t st, Timing* tm) {
-  if (A.dim == 64) return launch_maxpass_t<64>(A, n_split_f, st, tm);
-  if (A.dim == 128) return launch_maxpass_t<128>(A, n_split_f, st, tm);
+hipError_t launch_score_maxpass(const ScoreArgs& A, const ScorePlan& P, hipStream_t st, Timing* tm) {
+  if (A.dim == 64) return launch_maxpass_t<64>(A, P, st, tm);
+  if (A.dim == 128) return launch_maxpass_t<128>(A, P, st, tm);
   return hipErrorInvalidValue;
 }
 
 // stage 1 + stage 2; the caller then runs the one-stage kernel + merge with A.tile_flag set (they skip every tile that is not flagged)
-hipError_t launch_score_two_stage(const ScoreArgs& A, int n_split_f, hipStream_t st, Timing* tm) {
-  if (A.dim == 64) return launch_two_stage_t<64>(A, n_split_f, st, tm);
-  if (A.dim == 128) return launch_two_stage_t<128>(A, n_split_f, st, tm);
-  if (A.dim == 256) return launch_two_stage_t<256>(A, n_split_f, st, tm);
+hipError_t launch_score_two_stage(const ScoreArgs& A, const ScorePlan& P, hipStream_t st, Timing* tm) {
+  if (A.dim == 64) return launch_two_stage_t<64>(A, P, st, tm);
+  if (A.dim == 128) return launch_two_stage_t<128>(A, P, st, tm);
+  if (A.dim == 256) return launch_two_stage_t<256>(A, P, st, tm);
   return hipErrorInvalidValue;
 }
-
-int score_filter_cap() { return SF_CAP; }
 
 // gbound[u] = max(gbound[u], order-mapped (K-th best score of the pre-pass list - 1 ulp)): the K-th best exact score of a SUBSET of the items
 // bounds the final K-th best from below (`score > bound` keeps ties, as compact_user publishes)

@@ -14,14 +14,14 @@
 // item offset), compacted by rank counting over v_readlane whenever a list could overflow.
 #include "poi_common.h"
 #include "poi_kernels.h"
+#include "score_plan.h"
 #include <limits.h>
 
 namespace poi {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#define TK_CAP 80   // candidate slots per user per wave (>= K + 32; compaction when cnt > TK_CAP - 32).
-                    // 4 waves x 32 users x 80 x 6 B = 61 KB per workgroup (+ 16 KB of A fragments: two workgroups per CU)
+// TK_CAP, SG_NW: score_plan.h (the launch planner sizes the LDS from them)
 
 // better() / wave_sort_desc() / wave_fence() / f2ord() / ord2f(): poi_common.h
 
@@ -33,6 +33,7 @@ struct WaveTopk {   // LDS state of one wavefront
   unsigned gseen[32];   // last global bound seen / published per user (order-mapped)
   unsigned gtmp[32];    // staging of a bound refresh
 };
+static_assert(sizeof(WaveTopk) == SCORE_WAVETOPK_BYTES, "score_plan.h sizes the LDS of the one-stage kernels from this");
 
 __device__ __forceinline__ int popc64(unsigned long long m) { return __builtin_popcountll(m); }
 
@@ -578,7 +579,6 @@ __global__ __launch_bounds__(POI_BLOCK, 2) void score_kernel_packed(ScoreArgs A)
 //    items into a range) almost no pair passes: the float64 block runs for a handful of (tile, row) pairs.
 // LDS: 8 candidate-list blocks (124 KB) + A fragments (32 KB at dim 256) + thresholds / user coordinates: one workgroup per CU.
 // -------------------------------------------------------------------------------------------------
-#define SG_NW 8
 template <int D8>
 __global__ __launch_bounds__(SG_NW * 64) void score_kernel_geo_stream(ScoreArgs A) {
   extern __shared__ __align__(16) float dyn[];
@@ -784,7 +784,7 @@ static hipError_t launch_score_t(const ScoreArgs& A, hipStream_t st, Timing* tm)
     static DeviceOnce once;      // (per device: poi_common.h)
     const hipError_t oe = once.run([]() { return hipFuncSetAttribute(reinterpret_cast<const void*>(&score_kernel<D8, DB, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); });
     if (oe != hipSuccess) return oe;
-    hipLaunchKernelGGL((score_kernel<D8, DB, true>), grid, dim3(POI_BLOCK), sizeof(double) * (A.n_dist + 96), st, A);
+    hipLaunchKernelGGL((score_kernel<D8, DB, true>), grid, dim3(POI_BLOCK), score_one_stage_lds(0, A.dim, true, A.n_dist), st, A);
   }
   else hipLaunchKernelGGL((score_kernel<D8, DB, false>), grid, dim3(POI_BLOCK), 0, st, A);
   tm->end(st);
@@ -799,9 +799,10 @@ static hipError_t launch_score_packed_t(const ScoreArgs& A, hipStream_t st, Timi
   tm->end(st);
   dim3 grid((A.n + 31) / 32, A.n_split / POI_NWAVE);
   tm->begin(A.k > 0 ? "score_topk" : "score_all", st);
-  if (A.ulptai && A.bin_bytes == 1) hipLaunchKernelGGL((score_kernel_packed<D8, 1>), grid, dim3(POI_BLOCK), sizeof(WaveTopk) * POI_NWAVE + sizeof(float4) * D8 * 64, st, A);
-  else if (A.ulptai) hipLaunchKernelGGL((score_kernel_packed<D8, 2>), grid, dim3(POI_BLOCK), sizeof(WaveTopk) * POI_NWAVE + sizeof(float4) * D8 * 64, st, A);
-  else hipLaunchKernelGGL((score_kernel_packed<D8, 0>), grid, dim3(POI_BLOCK), sizeof(WaveTopk) * POI_NWAVE + sizeof(float4) * D8 * 64, st, A);
+  const size_t lds = score_one_stage_lds(1, A.dim, false, 0);
+  if (A.ulptai && A.bin_bytes == 1) hipLaunchKernelGGL((score_kernel_packed<D8, 1>), grid, dim3(POI_BLOCK), lds, st, A);
+  else if (A.ulptai) hipLaunchKernelGGL((score_kernel_packed<D8, 2>), grid, dim3(POI_BLOCK), lds, st, A);
+  else hipLaunchKernelGGL((score_kernel_packed<D8, 0>), grid, dim3(POI_BLOCK), lds, st, A);
   tm->end(st);
   return hipGetLastError();
 }
@@ -811,12 +812,6 @@ hipError_t launch_score_packed(const ScoreArgs& A, hipStream_t st, Timing* tm) {
   if (A.dim <= 64) return launch_score_packed_t<8>(A, st, tm);
   if (A.dim <= 128) return launch_score_packed_t<16>(A, st, tm);
   return hipErrorInvalidValue;
-}
-
-
-size_t score_geo_stream_lds(int dim, int n_dist) {
-  const int d8 = dim <= 128 ? 16 : 32;
-  return sizeof(WaveTopk) * SG_NW + sizeof(float4) * d8 * 64 + sizeof(double) * (n_dist + 96) + sizeof(float) * 32;
 }
 
 template <int D8>
