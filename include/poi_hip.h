@@ -92,6 +92,9 @@ extern "C" {
  * POI_FILTER_* path constants, options "filter_split_max" / "filter_grid" / "filter_gather_cost", plan keys "filter_path" /
  * "filter_splits" / "filter_split_max", timing names "filter_build" / "score_topk_filtered" / "topk_filtered_scores" (existing entries
  * unchanged). */
+/* additive to 9: audience recommendation - new entry points poi_score_audience and poi_audience_rows, options "audience_split_max" /
+ * "audience_grid", plan keys "audience_path" / "audience_splits" / "audience_split_max", timing names "score_audience" (with
+ * "audience_walk" / "audience_merge" inside it) / "audience_rows" (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -188,7 +191,9 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * (option of the same name), 0 with the ids loaded inside the step loop or without the table form; poi_gru_predict records its own value
  * of this one key.
  * Additive to 9: "filter_path" (1 walk, 2 gather), "filter_splits" (slices, 0 outside the split regime), "filter_split_max" - written
- * by poi_score_topk_filtered. */
+ * by poi_score_topk_filtered.
+ * Additive to 9: "audience_path" (0 one workgroup per query block, 1 slices), "audience_splits" (slices, 0 outside the split regime),
+ * "audience_split_max" - written by poi_score_audience / poi_audience_rows. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -282,7 +287,12 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *   "select_grid" n (default 0 = by the row count and the CUs; at most 64): slices on that split path - bitwise the same result for
  *       every n and on either path;
  *   "select_chunk_mb" n (default 1024, at least 1): poi_score_candidates keeps at most n MiB of score rows at a time (a whole number
- *       of 32-row tiles, at least one) - bitwise the same result for every n. */
+ *       of 32-row tiles, at least one) - bitwise the same result for every n;
+ *   "audience_split_max" n (default 256): poi_score_audience / poi_audience_rows calls of at most n query POIs cut the candidate rows
+ *       into slices, one workgroup per (32-query block, slice), and merge the slices' lists (0: never); larger calls run one workgroup
+ *       per query block;
+ *   "audience_grid" n (default 0 = by the query-block count and the CUs; at most 64): slices in that split regime - bitwise the same
+ *       result for every n and in either regime. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -1243,6 +1253,40 @@ int poi_topk_filtered_scores(poi_ctx* ctx, const float* scores, int32_t n, int32
                              const uint32_t* bits, int64_t ldw, int32_t n_pred, const int32_t* pred,
                              const int32_t* ex_off, const int32_t* ex, int32_t k,
                              int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+
+/* ---- audience recommendation (additive to 9): given a POI, which users? -------------------------------------------------------------------
+ * Every entry above ranks POIs for a row.  poi_score_audience ranks ROWS for a POI: for query POIs pois[q] (q < n_q) and the candidate
+ * rows users (n, dim) it returns per query the best rows under the score and the order of poi_score_rank / poi_score_rows:
+ *   s(u, j)  = users[u] . items[j] (+ wd * sts[u][bin(last_poi[u], j)] with wd non-NULL, for a row with last_poi[u] >= 0), to the bit;
+ *   C(q)     = [0, n) minus ex[ex_off[q] .. ex_off[q + 1]) - ascending unique ROW INDICES, typically the rows that already visited the
+ *              POI; both pointers NULL: no exclusion;
+ *   result   = the best min(k, |C(q)|) rows of C(q) by descending score, ties by ascending row index, into idx_out / score_out (n_q, k);
+ *              -1 ids and -inf scores behind them; count_out[q] = |C(q)|, not clipped to k.  A NaN score is never listed.
+ * The first 13 arguments are poi_score_rank's: items float32 or a registered half table, dim a multiple of 4 up to 256, sts
+ * (n, n_dist + 1), last_poi (n); n_dist at most 1024 with the distance term.  1 <= k <= 32 (POI_ENOTSUP beyond: poi_audience_rows +
+ * poi_topk_select is the route for a larger k).  A query id outside [0, n_item), or a list that is not ascending or leaves [0, n), rejects the
+ * query: -1 / -inf, count 0, counted once (poi_ctx_take_bad_ids) - poi_score_rank's rule.  The same POI may be queried twice: two
+ * identical rows.  n_q = 0 is a no-op; n = 0 with n_q > 0 writes the empty lists.
+ * A workgroup keeps a block of 32 query POIs resident and streams the user table past them: per query block the user table is read
+ * once.  Two launch regimes: calls of at most "audience_split_max" queries (poi_ctx_set_option, default 256: live traffic, a few POIs
+ * against every user) cut the rows into "audience_grid" slices, one workgroup per (query block, slice), and merge the slices' lists in
+ * a second kernel; larger calls run one workgroup per query block.  The output is bitwise the same on every grid and in both regimes,
+ * for a query alone or among thousands, wherever it stands in its block; no float atomics.  poi_ctx_last_plan: "audience_path",
+ * "audience_splits", "audience_split_max".  Timing names: "score_audience" (the call), and inside it "audience_walk" and - split regime -
+ * "audience_merge".
+ *
+ * poi_audience_rows is the same walk with a store epilogue: scores_out[q * ld + u] = s(u, pois[q]) for u < n (ld >= n; the columns beyond
+ * n are not written); the row of a rejected query (id outside [0, n_item)) is -inf.  The large-k route (with poi_topk_select: there n is
+ * n_q and n_item the candidate count) and an independent check of poi_score_audience.  Timing name: "audience_rows". */
+int poi_score_audience(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                       const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                       int32_t n_dist, double dd,
+                       const int32_t* pois, int32_t n_q, const int32_t* ex_off, const int32_t* ex, int32_t k,
+                       int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+int poi_audience_rows(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                      const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                      int32_t n_dist, double dd,
+                      const int32_t* pois, int32_t n_q, float* scores_out, int64_t ld, void* stream);
 
 /* ---- fold-in (additive to 9): a user row of OboBpr / OboVBpr for a check-in history the model never trained on -------------------------------
  * The factorisation family's only user representation is a trained row of ux (and ue).  Fold-in freezes the item side and runs the

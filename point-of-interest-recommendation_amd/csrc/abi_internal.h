@@ -5,6 +5,7 @@
 #include "poi_kernels.h"
 #include "split_plan.h"
 #include "filter_plan.h"
+#include "audience_plan.h"
 
 #include <string>
 #include <utility>
@@ -81,7 +82,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, xfwd_ids_lds, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max, select_rows_per_chunk, select_chunks, select_path, select_splits, filter_path, filter_splits, filter_split_max; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, xfwd_ids_lds, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max, select_rows_per_chunk, select_chunks, select_path, select_splits, filter_path, filter_splits, filter_split_max, audience_path, audience_splits, audience_split_max; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR
@@ -137,6 +138,10 @@ struct poi_ctx {
   int filter_split_max = 256; // option "filter_split_max": poi_score_topk_filtered calls of at most this many rows cut the item range (walk) / every row's candidates (gather) into slices, a workgroup each
   int filter_grid = 0;      // option "filter_grid": slices in the split regime (0: by the row count and the CUs)
   int filter_gather_cost = FILTER_GATHER_COST_DEFAULT;      // option "filter_gather_cost": POI_FILTER_AUTO's price of a gathered candidate in walk cells (filter_plan.h)
+  // audience recommendation (audience.hip): per (query, slice) partial lists of the split regime
+  DevBuf audience_ws;
+  int audience_split_max = 256; // option "audience_split_max": poi_score_audience / poi_audience_rows calls of at most this many queries cut the candidate rows into slices, a workgroup each per query block
+  int audience_grid = 0;    // option "audience_grid": slices in the split regime (0: by the query-block count and the CUs)
   // scoring
   DevBuf cand_s, cand_i, items_pk, gbound;
   DevBuf items_pk16, inorm, surv_cnt, surv_idx, surv_sc, tflag, pre_idx, pre_sc;      // two-stage fused top-K (score_filter.hip)

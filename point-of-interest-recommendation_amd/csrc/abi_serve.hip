@@ -788,6 +788,64 @@ int poi_group_topk_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_
 }
 
 // ---------------------------------------------------------------------------------------------
+// audience recommendation (audience.hip)
+static int audience_operands(poi_ctx* c, const char* who, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                             const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr,
+                             const int32_t* last_poi, int32_t n_dist, double dd, const int32_t* pois, int32_t n_q, const int32_t* ex_off,
+                             const int32_t* ex, hipStream_t st, poi::AudienceArgs* A) {
+  if (!c || !items || (!users && n > 0)) return fail(c, POI_EINVAL, "%s: NULL ctx / users / items", who);
+  if (n_q < 0 || (!pois && n_q > 0)) return fail(c, POI_EINVAL, "%s: n_q < 0 or NULL pois", who);
+  if (wd && n_dist > AUDIENCE_NDIST_MAX) return fail(c, POI_ENOTSUP, "%s supports n_dist <= %d with the distance term (got %d)", who, AUDIENCE_NDIST_MAX, n_dist);
+  poi::TileOperands T;
+  if (int rc = tile_operands(c, who, users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, ex_off, ex, st, &T)) return rc;
+  *A = poi::AudienceArgs{};
+  put_operands(*A, T);
+  A->pois = pois; A->n_q = n_q;
+  // few queries (live traffic: a few POIs against every user): the rows are cut into slices so that the call fills the CUs; many: one
+  // workgroup per 32-query block
+  const SplitPlan sp = audience_plan(n_q, n, c->audience_split_max, c->audience_grid, c->num_cu);
+  A->n_split = sp.n_split;
+  if (n_q > 0) {
+    c->plan.valid = 1; c->plan.audience_path = sp.split; c->plan.audience_splits = sp.split ? sp.n_split : 0;
+    c->plan.audience_split_max = c->audience_split_max;
+  }
+  return POI_OK;
+}
+
+int poi_score_audience(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                       const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                       const int32_t* pois, int32_t n_q, const int32_t* ex_off, const int32_t* ex, int32_t k, int32_t* idx_out, float* score_out,
+                       int32_t* count_out, void* stream) {
+  if (c && !idx_out) return fail(c, POI_EINVAL, "poi_score_audience: NULL idx_out");
+  if (c && (k <= 0 || k > AUDIENCE_K_MAX)) return fail(c, POI_ENOTSUP, "poi_score_audience supports 1 <= k <= %d (got %d)", AUDIENCE_K_MAX, k);
+  hipStream_t st = (hipStream_t)stream;
+  poi::AudienceArgs A;
+  int rc;
+  if ((rc = audience_operands(c, "poi_score_audience", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, pois, n_q,
+                              ex_off, ex, st, &A))) return rc;
+  if (n_q == 0) return POI_OK;
+  A.k = k; A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
+  if (c->plan.audience_path && (rc = carve_lists(c, c->audience_ws, st, A, (size_t)n_q * A.n_split, AUDIENCE_K_MAX))) return rc;
+  HIPCHK(c, poi::launch_audience(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_audience_rows(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                      const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                      const int32_t* pois, int32_t n_q, float* scores_out, int64_t ld, void* stream) {
+  if (c && !scores_out && n_q > 0 && n > 0) return fail(c, POI_EINVAL, "poi_audience_rows: NULL scores_out");
+  if (c && ld < n) return fail(c, POI_EINVAL, "poi_audience_rows: ld must be >= n");
+  hipStream_t st = (hipStream_t)stream;
+  poi::AudienceArgs A;
+  if (int rc = audience_operands(c, "poi_audience_rows", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, pois, n_q,
+                                 nullptr, nullptr, st, &A)) return rc;
+  if (n_q == 0 || n == 0) return POI_OK;
+  A.rows_out = scores_out; A.ld = ld;
+  HIPCHK(c, poi::launch_audience_rows(A, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // route recommendation (route.hip)
 int poi_route_expand(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
                      const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,

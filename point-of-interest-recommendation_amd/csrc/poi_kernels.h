@@ -654,6 +654,24 @@ struct GroupArgs {
 hipError_t launch_group(GroupArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_group_scores(const float* scores, GroupArgs& A, hipStream_t st, Timing* tm);
 
+// Audience recommendation (audience.hip): the top-K candidate rows (users) of each query POI - rank.hip's walk with the axes swapped
+#define AUDIENCE_K_MAX 32                   // list length (one half wave)
+#define AUDIENCE_NDIST_MAX 1024             // distance bins whose thresholds fit the walk kernel's LDS beside its lists
+struct AudienceArgs {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim, k;
+  const float *wd, *sts; const double *coords, *cphi, *thr; const int* last_poi; int n_dist; float bin_scale;      // distance term, or wd null
+  const int* pois; int n_q;                                   // the query POIs
+  const int *ex_off, *ex;                                     // per-query exclusion lists (ascending row indices), or both null
+  int n_split;                                                // slices of the user range, one workgroup each per 32-query block
+  float* part_s; int *part_i, *part_cnt;                      // split regime: (n_q, n_split, AUDIENCE_K_MAX) partial lists, (n_q, n_split) counts
+  int* idx_out; float* score_out; int* count_out;             // (n_q, k); score_out / count_out may be null
+  float* rows_out; long long ld;                              // poi_audience_rows: rows_out[q * ld + u], ld >= n
+  int* bad;                                                   // device counter of rejected queries (poi_ctx_take_bad_ids)
+};
+hipError_t launch_audience(const AudienceArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_audience_rows(const AudienceArgs& A, hipStream_t st, Timing* tm);
+
 // Route recommendation (route.hip): one beam-search step - per row the best b candidates and the normaliser over all POIs; the merge
 #define ROUTE_B_MAX 8                       // beam width: list length, and parents x b <= 64 proposals meet in one wave
 #define ROUTE_T_MAX 16                      // steps: the longest path a row may carry

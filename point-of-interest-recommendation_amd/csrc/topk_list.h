@@ -29,7 +29,9 @@ __device__ __forceinline__ void top64_merge(float& cs, int& ci, float ns, int ni
 }
 
 // merge a wave's 64 (unsorted) new candidates of one row into the row's LDS list (sorted, best first; entries 0 .. K-1 exact): the
-// wave sorts only when one candidate beats the list's K-th entry, then the half-cleaner merge of two sorted lists
+// wave sorts only when one candidate beats the list's K-th entry, then the half-cleaner merge of two sorted lists.  LEN: the entries the
+// LDS list holds (64, or 32: audience.hip keeps 32 lists per wave) - the lanes behind it hold pads and write nothing back
+template <int LEN = 64>
 __device__ __forceinline__ void lds_list_merge(float* ls, int* li, float s, int i, int K) {
   const int lane = lane_id();
   const bool cand = better(s, i, ls[K - 1], li[K - 1]);
@@ -38,8 +40,8 @@ __device__ __forceinline__ void lds_list_merge(float* ls, int* li, float s, int 
   wave_sort_desc(s, i);
   float rs = __shfl(s, 63 - lane, 64);
   int ri = __shfl(i, 63 - lane, 64);
-  const float cs = ls[lane];
-  const int ci = li[lane];
+  const float cs = (LEN == 64 || lane < LEN) ? ls[lane] : neg_inf();
+  const int ci = (LEN == 64 || lane < LEN) ? li[lane] : PAD_ID;
   if (better(cs, ci, rs, ri)) { rs = cs; ri = ci; }      // best 64 of the union: a bitonic sequence
 #pragma unroll
   for (int j = 32; j > 0; j >>= 1) {
@@ -49,19 +51,20 @@ __device__ __forceinline__ void lds_list_merge(float* ls, int* li, float s, int 
     if (((lane & j) == 0) != mine) { rs = ps; ri = pi; }
   }
   __builtin_amdgcn_wave_barrier();
-  ls[lane] = rs; li[lane] = ri;
+  if (LEN == 64 || lane < LEN) { ls[lane] = rs; li[lane] = ri; }
   __builtin_amdgcn_wave_barrier();
 }
 
 // the lanes of `bal` hold candidates (v, j) for the sorted 64-entry list (ls, lx), entry l on lane l.  A few (the common tile, once the
 // list has warmed up): one at a time - the entries in front of the newcomer are a prefix of the sorted list, the others move down one
 // lane.  Many (the first tiles): lds_list_merge's sort.  The list is the best 64 of everything offered either way: the same bits.
+template <int LEN = 64>
 __device__ __forceinline__ void list_take(float* ls, int* lx, unsigned long long bal, bool cand, float v, int j, int K) {
-  if (__popcll(bal) > 8) { lds_list_merge(ls, lx, cand ? v : neg_inf(), cand ? j : PAD_ID, K); return; }
+  if (__popcll(bal) > 8) { lds_list_merge<LEN>(ls, lx, cand ? v : neg_inf(), cand ? j : PAD_ID, K); return; }
   const int lane = lane_id();
   __builtin_amdgcn_wave_barrier();
-  float cs = ls[lane];
-  int ci = lx[lane];
+  float cs = (LEN == 64 || lane < LEN) ? ls[lane] : neg_inf();
+  int ci = (LEN == 64 || lane < LEN) ? lx[lane] : PAD_ID;
   while (bal) {
     const int src = __ffsll((long long)bal) - 1;
     bal &= bal - 1;
@@ -74,7 +77,7 @@ __device__ __forceinline__ void list_take(float* ls, int* lx, unsigned long long
     else if (lane > pos) { cs = us; ci = ui; }
   }
   __builtin_amdgcn_wave_barrier();
-  ls[lane] = cs; lx[lane] = ci;
+  if (LEN == 64 || lane < LEN) { ls[lane] = cs; lx[lane] = ci; }
   __builtin_amdgcn_wave_barrier();                  // (a wave's LDS accesses complete in order: the next read needs no wait, only this place in the code)
 }
 

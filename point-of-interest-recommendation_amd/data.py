@@ -152,6 +152,22 @@ def train_exclusion_csr(off, p_flat, n_item):
     return eo, (key % (n_item + 1)).astype(np.int32)
 
 
+def visitors_csr(off, p_flat, n_item):
+    """Every POI's DISTINCT train visitors as a CSR (voff int64 (n_item + 1), users int32), user ids ascending within a POI: the inverse
+    of train_exclusion_csr and the exclude="train" lists of recommend_audience.  A padding id (>= n_item) is no visit."""
+    off = np.asarray(off, np.int64)
+    p = np.asarray(p_flat, np.int64)
+    n_user = len(off) - 1
+    user = np.repeat(np.arange(n_user), np.diff(off))
+    keep = (p >= 0) & (p < n_item)
+    key = np.unique(p[keep] * max(n_user, 1) + user[keep])                # sorted by (POI, user), duplicates dropped
+    voff = np.zeros(n_item + 1, np.int64)
+    np.cumsum(np.bincount(key // max(n_user, 1), minlength=n_item), out=voff[1:])
+    if voff[-1] >= 1 << 31:
+        raise ValueError("the visitor lists hold %d ids: above 2^31" % voff[-1])
+    return voff, (key % max(n_user, 1)).astype(np.int32)
+
+
 def group_exclusion_csr(ex_off, ex_ids, g_off, g_mem, n_item):
     """One exclusion list per GROUP from per-user lists: the sorted union of the members' lists, as a CSR (off int64 (n_grp + 1), ids
     int32) - with (ex_off, ex_ids) = train_exclusion_csr(...) the exclude="train" lists of recommend_group: a POI any member has visited

@@ -171,6 +171,48 @@ def candidate_recall(model, starts_ends_tes, ks, exclude="train"):
     return {k: (float(h[i]) / t if t else 0.0) for i, k in enumerate(ks)}
 
 
+def audience_recall(model, ks, exclude="train"):
+    """Recall of the audience direction: over the held-out (user, test POI) pairs (tes_buys_masks under tes_masks), the share of pairs
+    whose user lies inside the top-k audience of the POI (model.recommend_audience), for every k in ks (strictly ascending).  ONE call
+    over the distinct test POIs at max(ks): the lists are sorted, so the top-k is their first k columns.  exclude as recommend_audience;
+    a pair whose user is excluded from its POI (or whose POI lies outside [0, n_item)) is no candidate and leaves the mean.  Returns
+    {k: recall}; the reductions are torch ops on the device."""
+    import torch
+    ks = [int(k) for k in ks]
+    if not ks or any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] <= 0:
+        raise ValueError("ks must be strictly ascending cut-offs >= 1 (got %r)" % (ks,))
+    N, U, dev = model.n_item, model.n_user, model.device
+    tgt = model.tes_buys_masks.long()
+    ok = (model.tes_masks != 0) & (tgt >= 0) & (tgt < N)
+    u, c = torch.nonzero(ok, as_tuple=True)
+    j = tgt[u, c]
+    pois = torch.unique(j)                                           # sorted: a pair's query is its POI's position
+    qpos = torch.searchsorted(pois, j)
+    if not pois.numel():
+        return {k: 0.0 for k in ks}
+    q32 = pois.int()
+    idx = model.recommend_audience(q32, ks[-1], exclude=exclude).long()
+    keep = torch.ones_like(u, dtype=torch.bool)
+    eo, ex = model._audience_exclusion(exclude, q32, None, U)
+    if eo is not None:                                               # a pair on its query's list: sorted keys query * n_user + user
+        eo = eo.long()
+        rows = torch.repeat_interleave(torch.arange(pois.numel(), device=dev), eo[1:] - eo[:-1])
+        keys = rows * U + ex[int(eo[0]):int(eo[-1])].long()
+        want = qpos * U + u
+        at = torch.searchsorted(keys, want).clamp(max=max(keys.numel() - 1, 0))
+        if keys.numel():
+            keep &= keys[at] != want
+    hits = torch.zeros(len(ks), dtype=torch.float64, device=dev)
+    for o in range(0, u.numel(), 4096):                              # (pairs, k) comparisons, 4096 pairs at a time
+        eq = idx[qpos[o:o + 4096]] == u[o:o + 4096, None]
+        found = eq.any(1) & keep[o:o + 4096]
+        pos = eq.int().argmax(1)
+        for i, k in enumerate(ks):
+            hits[i] += (found & (pos < k)).sum()
+    h, t = hits.cpu().numpy(), float(keep.sum().item())
+    return {k: (float(h[i]) / t if t else 0.0) for i, k in enumerate(ks)}
+
+
 def foldin_rank_metrics(model, histories, targets, at_nums, exclude="history", **fold_in_kwargs):
     """full_rank_metrics for HELD-OUT users of the factorisation family, of the successive-POI models OboFpmc_lr / OboPrme and of
     OboPoi2vec (strong generalisation): every history is folded in (model.rank_new: fold_in, then the exact rank of its targets among all POIs) and the

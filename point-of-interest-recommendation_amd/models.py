@@ -1089,6 +1089,184 @@ class _Base:
         g_mem = i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=self.device)
         return self._group_launch(users.contiguous(), self._items(), term, i32(off), g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync)
 
+
+    # ---- audience recommendation (poi_score_audience / poi_audience_rows): given a POI, which users? -----------------------------------
+    AUDIENCE_K_FUSED = 32       # the fused walk's list length; beyond it: score rows + poi_topk_select
+
+    def train_visitors(self):
+        """Every POI's DISTINCT train visitors as a sorted CSR (voff (n_item + 1) int32, user ids int32) on the device - built once and
+        cached (data.visitors_csr): the exclude="train" lists of recommend_audience."""
+        t = self.__dict__.get("_audience_train")
+        if t is None:
+            if getattr(self, "_off_host", None) is None or getattr(self, "p", None) is None:
+                raise _lib.PoiError("%s keeps no (off, p) train table: pass the visitor lists as exclude=(off, ids)" % type(self).__name__)
+            from .data import visitors_csr
+            vo, us = visitors_csr(self._off_host, self.p.cpu().numpy(), self.n_item)
+            self._audience_train_host = (vo, us)
+            i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+            t = self._audience_train = (i32(vo), i32(us) if len(us) else torch.zeros(1, dtype=torch.int32, device=self.device))
+        return t
+
+    def _audience_k(self, k, n, fused):
+        k = int(k)
+        if not (1 <= k <= min(self.CANDIDATES_K_MAX, n) or (fused and 1 <= k <= self.AUDIENCE_K_FUSED)):
+            raise ValueError("audience recommendation supports 1 <= k <= min(%d, candidates = %d)%s (got %d)"
+                             % (self.CANDIDATES_K_MAX, n, ", or k <= 32 whatever the candidate count" if fused else "", k))
+        return k
+
+    def _audience_queries(self, pois, host=False):
+        """pois -> int32 device tensor (n_q).  Host ids are range-checked (IndexError before any launch); a device tensor is left to the
+        kernel - unless `host`: the caller gathers with the ids on the host side of things and needs them checked."""
+        if isinstance(pois, torch.Tensor) and pois.is_cuda and not host:
+            return pois.to(self.device, torch.int32).reshape(-1).contiguous()
+        a = np.atleast_1d(np.asarray(pois.cpu().numpy() if isinstance(pois, torch.Tensor) else pois)).astype(np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= self.n_item):
+            raise IndexError("pois must lie in [0, %d) (found %d..%d)" % (self.n_item, int(a.min()), int(a.max())))
+        return torch.as_tensor(a.astype(np.int32)).to(self.device)
+
+    @staticmethod
+    def _audience_segment(users, hi, what="users"):
+        """users -> None (every row) or the ascending unique int64 host id list of a segment (ValueError / IndexError)."""
+        if users is None:
+            return None
+        a = np.atleast_1d(np.asarray(users.cpu().numpy() if isinstance(users, torch.Tensor) else users)).astype(np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= hi):
+            raise IndexError("%s must lie in [0, %d) (found %d..%d)" % (what, hi, int(a.min()), int(a.max())))
+        if a.size > 1 and np.any(np.diff(a) <= 0):
+            raise ValueError("%s must be strictly ascending (sorted, unique)" % what)
+        return a
+
+    def _audience_exclusion(self, exclude, q, seg, n_all, kinds=("train",)):
+        """exclude -> (ex_off (n_q + 1), ex) int32 device tensors of ROW INDICES per query, or (None, None).  seg: the segment's ids
+        (the lists are restricted to it and re-indexed), or None (row index = id)."""
+        n_q = q.numel()
+        empty = lambda: torch.zeros(1, dtype=torch.int32, device=self.device)
+        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+        if exclude is None:
+            return None, None
+        if isinstance(exclude, str):
+            if exclude not in kinds:
+                raise ValueError("exclude must be None, %s or a pair (off, ids) (got %r)" % (", ".join(repr(k) for k in kinds) or "-", exclude))
+            vo, us = self.train_visitors()
+            if seg is None:                                     # gather the queried POIs' lists on the device (a bad id lists nothing)
+                ok = (q >= 0) & (q < self.n_item)
+                qc = q.long().clamp(0, self.n_item - 1)
+                beg, ln = vo[qc].long(), (vo[qc + 1] - vo[qc]).long() * ok.long()
+                no = torch.zeros(n_q + 1, dtype=torch.int64, device=self.device)
+                no[1:] = torch.cumsum(ln, 0)
+                pos = torch.arange(int(no[-1].item()), device=self.device) - torch.repeat_interleave(no[:-1] - beg, ln)
+                return no.int(), (us[pos].contiguous() if pos.numel() else empty())
+            off, lst = self._audience_train_host
+            qh = q.cpu().numpy().astype(np.int64)
+            okh = (qh >= 0) & (qh < self.n_item)
+            qh = np.clip(qh, 0, self.n_item - 1)
+            ln = (off[qh + 1] - off[qh]) * okh
+            pos = np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln - off[qh], ln)
+            off, lst = np.concatenate(([0], np.cumsum(ln))), lst[pos].astype(np.int64)
+        else:
+            off, lst = exclude
+            if isinstance(off, torch.Tensor) and isinstance(lst, torch.Tensor) and seg is None:      # device lists are checked by the kernel
+                if off.numel() != n_q + 1:
+                    raise ValueError("exclude=(off, ids): off must hold n_q + 1 = %d offsets" % (n_q + 1))
+                lst = lst.to(self.device, torch.int32).contiguous()
+                return off.to(self.device, torch.int32).contiguous(), (lst if lst.numel() else empty())
+            off = off.cpu().numpy() if isinstance(off, torch.Tensor) else off
+            lst = lst.cpu().numpy() if isinstance(lst, torch.Tensor) else lst
+            from .data import check_exclusion_csr
+            off, lst = (np.asarray(v, np.int64) for v in check_exclusion_csr(off, lst, n_q, n_all))
+            if seg is None:
+                return i32(off), (i32(lst) if len(lst) else empty())
+        # restricted to the segment and re-indexed: the rows keep the lists' ascending order
+        at = np.searchsorted(seg, lst)
+        keep = (at < len(seg)) & (seg[np.minimum(at, max(len(seg) - 1, 0))] == lst) if len(seg) else np.zeros(len(lst), bool)
+        row = np.repeat(np.arange(n_q), np.diff(off))
+        no = np.zeros(n_q + 1, np.int64)
+        np.cumsum(np.bincount(row[keep], minlength=n_q), out=no[1:])
+        return i32(no), (i32(at[keep]) if keep.any() else empty())
+
+    def _audience_out(self, idx, sc, cnt, seg_dev, return_scores, return_counts, sync):
+        if seg_dev is not None and idx.numel():                 # row indices -> ids; -1 stays -1
+            idx = torch.where(idx >= 0, seg_dev[idx.clamp(min=0).long()], idx)
+        return self._serve_out(idx, ((sc, return_scores), (cnt, return_counts)), sync,
+                               "query POI(s) outside [0, %d) or with a malformed exclusion list: their lists are all -1" % self.n_item)
+
+    def _audience_select(self, buf, c, n, ld, k, ex, o, idx, sc, cnt):
+        """poi_topk_select over the (c, ld) score rows of queries o .. o + c - 1: there the rows are the queries, the "items" the n candidates."""
+        at = lambda t, w: ctypes.c_void_p(t.data_ptr() + 4 * o * w) if t is not None else None
+        self.ctx.check(self.lib.poi_topk_select(self.ctx.handle, _ptr(buf), c, n, ld, k, at(ex[0], 1), _ptr(ex[1]), at(idx, k), at(sc, k), at(cnt, 1),
+                                                self._stream()))
+
+    def _audience_launch(self, users, items, kdim, term, q, ex, k, seg_dev, return_scores, return_counts, sync):
+        """The fused paths on explicit candidate rows `users` (n, kdim): one poi_score_audience call for k <= 32, poi_audience_rows into a
+        bounded buffer + poi_topk_select beyond.  term: (wd, sts rows, last POI rows) or None."""
+        n, n_q = users.shape[0], q.numel()
+        idx = torch.empty((n_q, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n_q, k), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n_q, dtype=torch.int32, device=self.device) if return_counts else None
+        ops = self._tile_operands(users, items, kdim, term)
+        if n_q and k <= self.AUDIENCE_K_FUSED:
+            self.ctx.check(self.lib.poi_score_audience(self.ctx.handle, *ops, _ptr(q), n_q, _ptr(ex[0]), _ptr(ex[1]), k, _ptr(idx), _ptr(sc), _ptr(cnt),
+                                                       self._stream()))
+        elif n_q:
+            ld = (n + 31) // 32 * 32
+            per = max(1, min(n_q, self.SCORE_ROWS_BYTES // (4 * ld)))
+            buf = torch.empty((per, ld), dtype=torch.float32, device=self.device)
+            for o in range(0, n_q, per):                        # (no host synchronisation between the chunks)
+                c = min(per, n_q - o)
+                self.ctx.check(self.lib.poi_audience_rows(self.ctx.handle, *ops, ctypes.c_void_p(q.data_ptr() + 4 * o), c, _ptr(buf), ld, self._stream()))
+                self._audience_select(buf, c, n, ld, k, ex, o, idx, sc, cnt)
+            if cnt is not None:                                 # a rejected query's row is -inf: nothing is listed, and nothing counted
+                cnt = torch.where((q >= 0) & (q < self.n_item), cnt, torch.zeros_like(cnt))
+        return self._audience_out(idx, sc, cnt, seg_dev, return_scores, return_counts, sync and n_q > 0)
+
+    def _audience_from_scores(self, a, q, ex, k, seg_dev, return_scores, return_counts, sync):
+        """The models that rank by a rule of their own: their score rows (_own_score_rows) of the users `a`, _rank_chunk users at a time;
+        the queried columns are gathered and transposed into the (queries, n) buffer, then poi_topk_select."""
+        n, n_q = len(a), q.numel()
+        idx = torch.empty((n_q, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n_q, k), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n_q, dtype=torch.int32, device=self.device) if return_counts else None
+        ld = (n + 31) // 32 * 32
+        per = max(1, min(max(n_q, 1), self.SCORE_ROWS_BYTES // (4 * ld)))
+        score_rows = self._own_score_rows(a)
+        buf = torch.empty((per, ld), dtype=torch.float32, device=self.device)
+        for o in range(0, n_q, per):
+            c = min(per, n_q - o)
+            ql = q[o:o + c].long()
+            for uo, uc in self._row_chunks(n):
+                buf[:c, uo:uo + uc] = score_rows(uo, uc).index_select(1, ql).t()
+            self._audience_select(buf, c, n, ld, k, ex, o, idx, sc, cnt)
+        return self._audience_out(idx, sc, cnt, seg_dev, return_scores, return_counts, sync and n_q > 0)
+
+    def recommend_audience(self, pois, k, users=None, exclude=None, return_scores=False, return_counts=False, sync=True):
+        """AUDIENCE recommendation (include/poi_hip.h, poi_score_audience): given a POI, which users?  For every query POI the top-k
+        users under the model's own score - the score compute_sub_target_rank ranks POIs with, read along the other axis - without the
+        (n_user, n_item) score matrix.  users: None = every user, or an ascending unique id list = that segment only.  exclude: None,
+        "train" (the POI's distinct train visitors leave the ranking: data.visitors_csr, restricted to the segment) or a CSR pair
+        (off, ids) of user ids per query, ascending and unique.  Returns (n_q, k) int32 USER IDS on the device by descending score, ties by
+        ascending id, -1 where a POI has fewer than k candidates (scores -inf); with return_counts the candidate count of every query.
+        The same POI may be queried twice.  1 <= k <= 32 is one fused call; 32 < k <= min(4096, candidates) goes through
+        poi_audience_rows, a bounded number of queries at a time, and poi_topk_select.  Host arguments are checked before the launch
+        (ValueError / IndexError); device tensors are checked by the kernel: an offending query comes out all -1 and - with sync -
+        raises IndexError (sync=False leaves the count to ctx.take_bad_ids()).  CA-RNN, PRME / PRPRM, POI2Vec and GeoIE go through
+        their own score rows (the score of the user's next position), _rank_chunk users at a time, and poi_topk_select for any k."""
+        fused = bool(self._rank_fused)
+        seg = self._audience_segment(users, self.n_user)
+        n = self.n_user if seg is None else len(seg)
+        k = self._audience_k(k, n, fused)
+        q = self._audience_queries(pois, host=not fused)
+        ex = self._audience_exclusion(exclude, q, seg, self.n_user)
+        seg_dev = None if seg is None else torch.as_tensor(seg.astype(np.int32)).to(self.device)
+        a = np.arange(self.n_user) if seg is None else seg
+        if not fused:
+            return self._audience_from_scores(a, q, ex, k, seg_dev, return_scores, return_counts, sync)
+        if n:
+            ids, rows, lo = self._users_rows(a)
+            term = self._rank_term(ids, lo)
+        else:
+            rows, term = torch.zeros((0, self.kdim), dtype=torch.float32, device=self.device), None
+        return self._audience_launch(rows.contiguous(), self._items(), self.kdim, term, q, ex, k, seg_dev, return_scores, return_counts, sync)
+
     # ---- diversified recommendation (poi_diverse_topk / poi_diverse_rerank): a pool of the best candidates, re-ranked by MMR --------------
     def _diverse_items(self):
         """The POI rows the embedding similarity is taken between: the table the model scores with.  None: the model has no single POI
@@ -2190,6 +2368,21 @@ class Session:
         return m._group_launch(users, m.trained_items.t, term if len(uniq) else None, self._i32(off), g_mem, n_grp, agg, ex, k, return_scores,
                                return_counts, sync)
 
+    def audience(self, pois, k, slots=None, exclude=None, return_scores=False, return_counts=False, sync=True):
+        """model.recommend_audience over the slots' CURRENT states (h, sts, last_poi, as `candidates` assembles them): which live
+        sessions should hear about this POI?  slots: None = every slot, or an ascending unique list of slot ids.  exclude: None or a
+        CSR pair (off, ids) of slot ids per query.  Returns (n_q, k) int32 SLOT ids by descending score, ties by ascending id, -1 fill
+        [, scores][, candidate counts].  A slot without a check-in has no distance term."""
+        m = self.m
+        seg = m._audience_segment(slots, self.n_slot, "slots")
+        n = self.n_slot if seg is None else len(seg)
+        k = m._audience_k(k, n, True)
+        q = m._audience_queries(pois)
+        ex = m._audience_exclusion(exclude, q, seg, self.n_slot, kinds=())
+        users, _, term = self._tile_rows(self._slot_tensor(seg))
+        return m._audience_launch(users, m.trained_items.t, m.kdim, term if n else None, q, ex, k, None if seg is None else self._i32(seg),
+                                  return_scores, return_counts, sync)
+
     def recommend_diverse(self, slots, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
                           return_objective=False, return_pool=False, return_counts=False, sync=True):
         """model.compute_sub_topk_diverse over the slots' CURRENT states (h, sts, last_poi, as `rank_of` assembles them): the `pool`
@@ -2492,6 +2685,13 @@ class CellSession(Session):
             raise _lib.PoiError("OboCARNN ranks by a score rule of its own, not users . items: recommend_group is not supported on its sessions "
                                 "(model.recommend_group covers the trained users)")
         return super().recommend_group(slot_groups, k, agg, exclude, return_scores, return_counts, sync)
+
+    def audience(self, pois, k, slots=None, exclude=None, return_scores=False, return_counts=False, sync=True):
+        """Lstm / Rnn: `Session.audience`'s plain rule.  CA-RNN ranks by a rule of its own and is refused."""
+        if self.carnn:
+            raise _lib.PoiError("OboCARNN ranks by a score rule of its own, not users . items: audience is not supported on its sessions "
+                                "(model.recommend_audience covers the trained users)")
+        return super().audience(pois, k, slots, exclude, return_scores, return_counts, sync)
 
     def recommend_route(self, slots, steps, beam=4, exclude="last", revisit=False, return_step_scores=False, sync=True):
         """Lstm / Rnn: `Session.recommend_route` over the plain rule (the Lstm's c travels with h).  CA-RNN ranks by a rule of its own
