@@ -95,6 +95,10 @@ extern "C" {
 /* additive to 9: audience recommendation - new entry points poi_score_audience and poi_audience_rows, options "audience_split_max" /
  * "audience_grid", plan keys "audience_path" / "audience_splits" / "audience_split_max", timing names "score_audience" (with
  * "audience_walk" / "audience_merge" inside it) / "audience_rows" (existing entries unchanged). */
+/* additive to 9: similar POIs and users - new entry points poi_row_inv_norms, poi_similar_topk, poi_similar_rows and
+ * poi_similar_nearest, options "similar_split_max" / "similar_grid" / "similar_rows_max", plan keys "similar_path" / "similar_splits" /
+ * "similar_split_max", timing names "similar_topk" (with "similar_norms" / "similar_walk" / "similar_merge" or "similar_rows" /
+ * "topk_select" inside it) / "similar_rows" / "similar_nearest" (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -193,7 +197,9 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * Additive to 9: "filter_path" (1 walk, 2 gather), "filter_splits" (slices, 0 outside the split regime), "filter_split_max" - written
  * by poi_score_topk_filtered.
  * Additive to 9: "audience_path" (0 one workgroup per query block, 1 slices), "audience_splits" (slices, 0 outside the split regime),
- * "audience_split_max" - written by poi_score_audience / poi_audience_rows. */
+ * "audience_split_max" - written by poi_score_audience / poi_audience_rows.
+ * Additive to 9: "similar_path" (0 one workgroup per query block, 1 slices, 2 score rows + selection), "similar_splits" (slices of the
+ * walk, 0 with one workgroup per query block), "similar_split_max" - written by poi_similar_topk / poi_similar_rows. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -292,7 +298,14 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *       into slices, one workgroup per (32-query block, slice), and merge the slices' lists (0: never); larger calls run one workgroup
  *       per query block;
  *   "audience_grid" n (default 0 = by the query-block count and the CUs; at most 64): slices in that split regime - bitwise the same
- *       result for every n and in either regime. */
+ *       result for every n and in either regime;
+ *   "similar_split_max" n (default 16384) / "similar_grid" n (default 0; at most 64): the same two for poi_similar_topk /
+ *       poi_similar_rows - queries in the query POIs' place, the table's own rows in the candidate rows'.  The default is where two
+ *       workgroups per CU leave one slice anyway: one workgroup per query block walks the whole table alone, which costs the
+ *       same few milliseconds for 257 queries as for 8192;
+ *   "similar_rows_max" n (default 1024, at most 4096): poi_similar_topk calls of at most n queries write their score rows
+ *       (poi_similar_rows' walk) and select from them (poi_topk_select's kernels) instead of keeping fused lists - for few queries the
+ *       faster route; 0: never.  Bitwise the same result for every n. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -1287,6 +1300,66 @@ int poi_audience_rows(poi_ctx* ctx, const float* users, const float* items, int3
                       const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
                       int32_t n_dist, double dd,
                       const int32_t* pois, int32_t n_q, float* scores_out, int64_t ld, void* stream);
+
+/* ---- similar POIs and users (additive to 9): places like this one, users like this one, "because you visited X" ------------------------------
+ * Every entry above starts from a user row or ranks rows for a POI.  These rank the rows of ONE table x (n, dim) - the POI table, or a
+ * table of user rows - by their similarity to a query row of the same table, without an (n, n) matrix and without a normalised copy of
+ * the table.  dim a multiple of 4 up to 256; x float32 or a registered half table.
+ *   inv[i]    = 1 / sqrt(sum_c x[i][c]^2) in float64, 0 for a zero row.  Summation order: poi_diverse_rerank's - four interleaved fma
+ *               chains over the float4 columns (chain q takes the columns 4 i + q), closed as (a0 + a1) + (a2 + a3): one order per dim.
+ *   emb(i, j) = (double)dot32(i, j) * (inv[i] * inv[j]);  dot32 = the float32 product of poi_score_rows for row x[i] against item x[j],
+ *               to the bit.  Not clamped; 0 for a zero row.
+ *   geo(i, j) = exp(-d(i, j) / scale_km), d = poi_diverse_rerank's sin^2 Haversine distance (km), operation for operation, in float64,
+ *               cos(lat) from cphi.
+ *   sim(i, j) = (float)(g geo + (1 - g) emb), g = geo_weight in [0, 1) (g = 1 is POI_EINVAL), scale_km > 0: formed in float64 without
+ *               contraction, rounded once to float32; -0.0 is written as +0.0.  With g = 0 nothing of geo is evaluated and coords / cphi
+ *               may be NULL.  sim(i, j) and sim(j, i) are the same bits.
+ *   C(q)      = [0, n) minus the query's own row queries[q], minus ex[ex_off[q] .. ex_off[q + 1]) (ascending unique row indices; both
+ *               NULL: none).  A list that names the query row itself does not subtract it twice.
+ *   result    = the best min(k, |C(q)|) rows of C(q) by descending sim, ties by ascending row, into idx_out / score_out (n_q, k); -1 ids
+ *               and -inf scores behind them; count_out[q] = |C(q)|, not clipped to k.  A NaN is never listed.
+ * A query outside [0, n), or a list that is not ascending or leaves [0, n), rejects the query: -1 / -inf, count 0, counted once
+ * (poi_ctx_take_bad_ids) - poi_score_audience's rule.  The same row may be queried twice.  n_q = 0 is a no-op; n > 0.
+ * This is a similarity of the model's rows, nothing more: it is not a decomposition of any model score.
+ *
+ * poi_row_inv_norms writes inv_out (n) float64: one read of the table, no atomics.  Timing name: "similar_norms".
+ *
+ * poi_similar_topk: 1 <= k <= 32 (POI_ENOTSUP beyond: poi_similar_rows + poi_topk_select is the route for a larger k).  inv_norm (n)
+ * from poi_row_inv_norms, or NULL: computed into the context's workspace inside the call - no cache is kept, so none can go stale.  A
+ * workgroup keeps 32 query rows resident and streams the table's 32-row tiles past them (audience's walk); with g > 0 a pair whose
+ * bound g + (1 - g) emb cannot enter its query's list is not given its distance - the listed bits do not depend on that.  Launch
+ * regimes: at most "similar_rows_max" queries (default 1024) write their score rows into the context's workspace and select from them
+ * (k <= n, the rows within "select_chunk_mb"); otherwise at most "similar_split_max" queries (default 16384) cut the rows into "similar_grid" slices
+ * and merge, larger calls run one workgroup per query block.  The output is bitwise the same on every route, grid and regime, for a
+ * query alone or among thousands; no float atomics.  poi_ctx_last_plan: "similar_path", "similar_splits", "similar_split_max".
+ * Timing names: "similar_topk" (the call), inside it "similar_norms", "similar_walk" and "similar_merge", or "similar_rows" and
+ * "topk_select".
+ *
+ * poi_similar_rows is the same walk with a store epilogue: scores_out[q * ld + j] = sim(queries[q], j) for j < n (ld >= n; the columns
+ * beyond n are not written), -inf at the query's own column and in the whole row of a rejected query (counted once).  The large-k
+ * route - poi_topk_select with k up to 4096 takes the exclusion lists itself; its count_out still counts the query's own row - and an
+ * independent check of the fused entry.  Timing name: "similar_rows".
+ *
+ * poi_similar_nearest - "because you visited X": for every POI lists[r][i] >= 0 of row r (lists (n, k) int32 with -1 fill, k <= 32)
+ * the POI of the row's history h_ids[h_off[r] .. h_off[r + 1]) (in the order given, duplicates allowed) it is most similar to.  The
+ * similarity is poi_diverse_rerank's, in float64 throughout: sim = g geo + (1 - g) x_i . x_l / (|x_i| |x_l|) with float64 row
+ * products and sqrt norms, 0 for a zero row; g in [0, 1] (a part with zero weight is not evaluated: its inputs may be NULL).  pos_out
+ * (n, k) int32: the position INSIDE the row's history with the largest similarity, ties to the lower position; -1 for a -1 entry or
+ * an empty history.  sim_out (n, k) float64 or NULL: that similarity, -inf there.  A listed id outside [-1, n_item), offsets out of
+ * order or a history id outside [0, n_item) rejects the row: -1 / -inf, counted once.  It attributes a recommendation to the most
+ * similar visited POI; it does not decompose the model's score.  One wave per row.  Timing name: "similar_nearest".  n = 0 is a no-op. */
+int poi_row_inv_norms(poi_ctx* ctx, const float* x, int32_t n, int32_t dim, double* inv_out, void* stream);
+int poi_similar_topk(poi_ctx* ctx, const float* x, int32_t n, int32_t dim, const double* coords, const double* cphi,
+                     double geo_weight, double scale_km, const double* inv_norm,
+                     const int32_t* queries, int32_t n_q, const int32_t* ex_off, const int32_t* ex, int32_t k,
+                     int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+int poi_similar_rows(poi_ctx* ctx, const float* x, int32_t n, int32_t dim, const double* coords, const double* cphi,
+                     double geo_weight, double scale_km, const double* inv_norm,
+                     const int32_t* queries, int32_t n_q, float* scores_out, int64_t ld, void* stream);
+int poi_similar_nearest(poi_ctx* ctx, const float* items, int32_t n_item, int32_t dim, const double* coords, const double* cphi,
+                        double geo_weight, double scale_km,
+                        const int32_t* lists, int32_t n, int32_t k, const int32_t* h_off, const int32_t* h_ids,
+                        int32_t* pos_out, double* sim_out, void* stream);
 
 /* ---- fold-in (additive to 9): a user row of OboBpr / OboVBpr for a check-in history the model never trained on -------------------------------
  * The factorisation family's only user representation is a trained row of ux (and ue).  Fold-in freezes the item side and runs the

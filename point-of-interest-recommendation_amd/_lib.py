@@ -193,6 +193,13 @@ SIGNATURES = {
                                    c_int32, c_double, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_audience_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_int32, c_double, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    "poi_row_inv_norms": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "poi_similar_topk": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_int32, c_void_p,
+                                 c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_similar_rows": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_int32, c_void_p,
+                                 c_int64, c_void_p]),
+    "poi_similar_nearest": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_double, c_double, c_void_p, c_int32, c_int32, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_score_candidates": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int32, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_filter_build": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
@@ -270,7 +277,8 @@ PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", 
              "group_path", "group_splits", "group_split_max", "route_path", "route_splits",
              "diverse_path", "diverse_splits", "diverse_split_max",
              "select_rows_per_chunk", "select_chunks", "select_path", "select_splits", "xfwd_ids_lds",
-             "filter_path", "filter_splits", "filter_split_max", "audience_path", "audience_splits", "audience_split_max")
+             "filter_path", "filter_splits", "filter_split_max", "audience_path", "audience_splits", "audience_split_max",
+             "similar_path", "similar_splits", "similar_split_max")
 
 
 class Context:
@@ -365,7 +373,8 @@ class Context:
         poi_geoie_score_all_geo / poi_geoie_score_topk_geo; "group_split_max" / "group_grid" of poi_group_topk; "route_split_max" / "route_grid" of
         poi_route_expand; "diverse_split_max" / "diverse_grid" of poi_diverse_pool / poi_diverse_topk; "select_split_max" /
         "select_grid" / "select_chunk_mb" of poi_topk_select / poi_score_candidates; "filter_split_max" / "filter_grid" / "filter_gather_cost" of
-        poi_score_topk_filtered; "audience_split_max" / "audience_grid" of poi_score_audience / poi_audience_rows)."""
+        poi_score_topk_filtered; "audience_split_max" / "audience_grid" of poi_score_audience / poi_audience_rows; "similar_split_max" /
+        "similar_grid" / "similar_rows_max" of poi_similar_topk / poi_similar_rows)."""
         self.check(self.lib.poi_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def set_small_launch(self, max_sequences=1800):

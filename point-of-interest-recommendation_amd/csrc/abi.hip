@@ -746,7 +746,9 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
                       {"select_chunk_mb", &c->select_chunk_mb, 1, 1 << 20},
                       {"filter_split_max", &c->filter_split_max, 0, 1 << 30}, {"filter_grid", &c->filter_grid, 0, FILTER_SPLIT_LIMIT},
                       {"filter_gather_cost", &c->filter_gather_cost, 1, 1 << 20},
-                      {"audience_split_max", &c->audience_split_max, 0, 1 << 30}, {"audience_grid", &c->audience_grid, 0, AUDIENCE_SPLIT_LIMIT}};
+                      {"audience_split_max", &c->audience_split_max, 0, 1 << 30}, {"audience_grid", &c->audience_grid, 0, AUDIENCE_SPLIT_LIMIT},
+                      {"similar_split_max", &c->similar_split_max, 0, 1 << 30}, {"similar_grid", &c->similar_grid, 0, SIMILAR_SPLIT_LIMIT},
+                      {"similar_rows_max", &c->similar_rows_max, 0, SIMILAR_ROWS_MAX_LIMIT}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);
@@ -838,7 +840,9 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"filter_path", &poi_ctx::LastPlan::filter_path}, {"filter_splits", &poi_ctx::LastPlan::filter_splits},
       {"filter_split_max", &poi_ctx::LastPlan::filter_split_max},
       {"audience_path", &poi_ctx::LastPlan::audience_path}, {"audience_splits", &poi_ctx::LastPlan::audience_splits},
-      {"audience_split_max", &poi_ctx::LastPlan::audience_split_max}};
+      {"audience_split_max", &poi_ctx::LastPlan::audience_split_max},
+      {"similar_path", &poi_ctx::LastPlan::similar_path}, {"similar_splits", &poi_ctx::LastPlan::similar_splits},
+      {"similar_split_max", &poi_ctx::LastPlan::similar_split_max}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

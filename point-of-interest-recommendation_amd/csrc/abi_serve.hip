@@ -846,6 +846,135 @@ int poi_audience_rows(poi_ctx* c, const float* users, const float* items, int32_
 }
 
 // ---------------------------------------------------------------------------------------------
+// similar rows (similar.hip)
+int poi_row_inv_norms(poi_ctx* c, const float* x, int32_t n, int32_t dim, double* inv_out, void* stream) {
+  if (!c || !x || (!inv_out && n > 0)) return fail(c, POI_EINVAL, "poi_row_inv_norms: NULL ctx / x / inv_out");
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_row_inv_norms: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  if (n < 0) return fail(c, POI_EINVAL, "poi_row_inv_norms: n < 0");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, poi::launch_row_inv_norms(x, is_f16(c, x), n, dim, inv_out, st, &c->tm));
+  return POI_OK;
+}
+
+// the checks and the argument block poi_similar_topk and poi_similar_rows share; inv_norm NULL: the norms go to the context's workspace
+static int similar_operands(poi_ctx* c, const char* who, const float* x, int32_t n, int32_t dim, const double* coords, const double* cphi,
+                            double geo_weight, double scale_km, const double* inv_norm, const int32_t* queries, int32_t n_q, const int32_t* ex_off,
+                            const int32_t* ex, hipStream_t st, poi::SimilarArgs* A, long* span = nullptr) {
+  if (!c || !x) return fail(c, POI_EINVAL, "%s: NULL ctx / x", who);
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, dim);
+  if (n <= 0) return fail(c, POI_EINVAL, "%s: n <= 0", who);
+  if (n_q < 0 || (!queries && n_q > 0)) return fail(c, POI_EINVAL, "%s: n_q < 0 or NULL queries", who);
+  if (!(geo_weight >= 0.0 && geo_weight < 1.0)) return fail(c, POI_EINVAL, "%s: geo_weight must lie in [0, 1) (got %g)", who, geo_weight);
+  if (!(scale_km > 0.0)) return fail(c, POI_EINVAL, "%s: scale_km must be positive (got %g)", who, scale_km);
+  if (geo_weight > 0.0 && (!coords || !cphi)) return fail(c, POI_EINVAL, "%s: geo_weight > 0 needs coords / cphi", who);
+  if (int rc = check_ex_pair(c, who, ex_off, ex)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  *A = poi::SimilarArgs{};
+  A->x = x; A->x_f16 = is_f16(c, x); A->n = n; A->dim = dim;
+  if (geo_weight > 0.0) { A->coords = coords; A->cphi = cphi; }
+  A->g = geo_weight; A->omg = 1.0 - geo_weight; A->scale_km = scale_km;
+  A->queries = queries; A->n_q = n_q; A->ex_off = ex_off; A->ex = ex; A->count_bad = 1; A->n_split = 1;
+  if (int rc = bad_counter(c, st, &A->bad)) return rc;
+  if (n_q == 0) return POI_OK;
+  if (span) *span = c->tm.span_begin("similar_topk", st);      // the call; inside it the norms, the walk and the merge / the rows and the selection
+  if (!inv_norm) {                                  // (no cache is kept: none can go stale)
+    if (int rc = ensure(c, c->similar_inv, sizeof(double) * (size_t)n, st)) return rc;
+    HIPCHK(c, poi::launch_row_inv_norms(x, A->x_f16, n, dim, (double*)c->similar_inv.p, st, &c->tm));
+    inv_norm = (const double*)c->similar_inv.p;
+  }
+  A->inv = inv_norm;
+  return POI_OK;
+}
+
+int poi_similar_topk(poi_ctx* c, const float* x, int32_t n, int32_t dim, const double* coords, const double* cphi, double geo_weight,
+                     double scale_km, const double* inv_norm, const int32_t* queries, int32_t n_q, const int32_t* ex_off, const int32_t* ex,
+                     int32_t k, int32_t* idx_out, float* score_out, int32_t* count_out, void* stream) {
+  if (c && !idx_out) return fail(c, POI_EINVAL, "poi_similar_topk: NULL idx_out");
+  if (c && (k <= 0 || k > SIMILAR_K_MAX)) return fail(c, POI_ENOTSUP, "poi_similar_topk supports 1 <= k <= %d (got %d)", SIMILAR_K_MAX, k);
+  hipStream_t st = (hipStream_t)stream;
+  // the plan first: the workspaces grow (and may synchronise) before the first launch
+  const int64_t ld = ((int64_t)(n > 0 ? n : 1) + 31) / 32 * 32;
+  const long long rows_fit = c ? ((long long)c->select_chunk_mb << 20) / (ld * 4) : 0;
+  const SimilarPlan P = c ? similar_plan(n_q, n, k, c->similar_rows_max, rows_fit, c->similar_split_max, c->similar_grid, c->num_cu) : SimilarPlan{0, 1};
+  float* sc_rows = nullptr;
+  poi::SimilarArgs A;
+  int rc;
+  if (c && n > 0 && n_q > 0) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (P.path == 2) {
+      if ((rc = carve(c, c->similar_sc, st, [&](Carver& W) { sc_rows = (float*)W.bytes(sizeof(float) * (size_t)n_q * (size_t)ld); }))) return rc;
+      poi::SelectArgs S = {};
+      if ((rc = select_carve(c, S, n_q < SELECT_ROWS_MAX ? n_q : SELECT_ROWS_MAX, k, st))) return rc;
+    }
+  }
+  long span = -1;
+  if ((rc = similar_operands(c, "poi_similar_topk", x, n, dim, coords, cphi, geo_weight, scale_km, inv_norm, queries, n_q, ex_off, ex, st, &A, &span))) return rc;
+  if (n_q == 0) return POI_OK;
+  A.k = k; A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out; A.n_split = P.n_split;
+  c->plan.valid = 1; c->plan.similar_path = P.path; c->plan.similar_splits = P.n_split > 1 || P.path == 1 ? P.n_split : 0;
+  c->plan.similar_split_max = c->similar_split_max;
+  if (P.path == 2) {
+    A.rows_out = sc_rows; A.ld = ld; A.count_bad = 0;
+    HIPCHK(c, poi::launch_similar_rows(A, st, &c->tm));
+    const SplitPlan sp = select_plan(c, n_q, n);
+    const long sel = c->tm.span_begin("topk_select", st);
+    rc = select_run(c, sc_rows, n_q, n, ld, k, ex_off, ex, idx_out, score_out, count_out, sp.n_split, A.bad, st);
+    c->tm.span_end(sel, st);
+    if (rc) return rc;
+    HIPCHK(c, poi::launch_similar_fix_counts(A, st));
+  } else {
+    if (P.path == 1 && (rc = carve_lists(c, c->similar_ws, st, A, (size_t)n_q * A.n_split, SIMILAR_K_MAX))) return rc;
+    HIPCHK(c, poi::launch_similar(A, st, &c->tm));
+  }
+  c->tm.span_end(span, st);
+  return POI_OK;
+}
+
+int poi_similar_rows(poi_ctx* c, const float* x, int32_t n, int32_t dim, const double* coords, const double* cphi, double geo_weight,
+                     double scale_km, const double* inv_norm, const int32_t* queries, int32_t n_q, float* scores_out, int64_t ld, void* stream) {
+  if (c && !scores_out && n_q > 0) return fail(c, POI_EINVAL, "poi_similar_rows: NULL scores_out");
+  if (c && ld < n) return fail(c, POI_EINVAL, "poi_similar_rows: ld must be >= n");
+  hipStream_t st = (hipStream_t)stream;
+  poi::SimilarArgs A;
+  if (int rc = similar_operands(c, "poi_similar_rows", x, n, dim, coords, cphi, geo_weight, scale_km, inv_norm, queries, n_q, nullptr, nullptr, st, &A)) return rc;
+  if (n_q == 0) return POI_OK;
+  const SplitPlan sp = similar_split(n_q, n, c->similar_split_max, c->similar_grid, c->num_cu);
+  A.n_split = sp.n_split; A.rows_out = scores_out; A.ld = ld;
+  c->plan.valid = 1; c->plan.similar_path = sp.split; c->plan.similar_splits = sp.split ? sp.n_split : 0; c->plan.similar_split_max = c->similar_split_max;
+  HIPCHK(c, poi::launch_similar_rows(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_similar_nearest(poi_ctx* c, const float* items, int32_t n_item, int32_t dim, const double* coords, const double* cphi, double geo_weight,
+                        double scale_km, const int32_t* lists, int32_t n, int32_t k, const int32_t* h_off, const int32_t* h_ids, int32_t* pos_out,
+                        double* sim_out, void* stream) {
+  if (!c) return fail(c, POI_EINVAL, "poi_similar_nearest: NULL ctx");
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "poi_similar_nearest: n < 0 or n_item <= 0");
+  if (k <= 0 || k > SIMILAR_K_MAX) return fail(c, POI_ENOTSUP, "poi_similar_nearest supports 1 <= k <= %d (got %d)", SIMILAR_K_MAX, k);
+  if (!(geo_weight >= 0.0 && geo_weight <= 1.0)) return fail(c, POI_EINVAL, "poi_similar_nearest: geo_weight must lie in [0, 1] (got %g)", geo_weight);
+  if (!(scale_km > 0.0)) return fail(c, POI_EINVAL, "poi_similar_nearest: scale_km must be positive (got %g)", scale_km);
+  if (geo_weight > 0.0 && (!coords || !cphi)) return fail(c, POI_EINVAL, "poi_similar_nearest: geo_weight > 0 needs coords / cphi");
+  if (geo_weight < 1.0) {
+    if (!items) return fail(c, POI_EINVAL, "poi_similar_nearest: geo_weight < 1 needs items");
+    if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "poi_similar_nearest: dim must be a multiple of 4 in [4, 256] (got %d)", dim);
+  }
+  if (n > 0 && (!lists || !h_off || !h_ids || !pos_out)) return fail(c, POI_EINVAL, "poi_similar_nearest: NULL lists / h_off / h_ids / pos_out");
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::NearestArgs A = {};
+  if (geo_weight < 1.0) { A.items = items; A.items_f16 = is_f16(c, items); A.dim = dim; }
+  if (geo_weight > 0.0) { A.coords = coords; A.cphi = cphi; }
+  A.n_item = n_item; A.geo_weight = geo_weight; A.scale_km = scale_km;
+  A.lists = lists; A.n = n; A.k = k; A.h_off = h_off; A.h_ids = h_ids; A.pos_out = pos_out; A.sim_out = sim_out;
+  if (int rc = bad_counter(c, st, &A.bad)) return rc;
+  HIPCHK(c, poi::launch_similar_nearest(A, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // route recommendation (route.hip)
 int poi_route_expand(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
                      const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,

@@ -36,6 +36,7 @@
 // similarity at all.  No atomics on a result; a rejected row is counted with one integer atomic.
 #include "poi_common.h"
 #include "poi_kernels.h"
+#include "pair_sim.h"
 #include "tile_product.h"
 #include "topk_list.h"
 
@@ -181,18 +182,8 @@ __global__ __launch_bounds__(64) void diverse_rerank_kernel(RerankArgs A) {
   }
   double lat = 0.0, lon = 0.0, cp = 0.0, nrm = 0.0;
   if (GEO && need_sim) { lat = A.coords[2 * (size_t)idc]; lon = A.coords[2 * (size_t)idc + 1]; cp = A.cphi[idc]; }
-  // one order per dim: four interleaved chains over the float4 columns, closed pairwise
-  auto dot_rows = [&](int a, int b) {
-    const float* xa = s_x + a * LD;
-    const float* xb = s_x + b * LD;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    for (int c = 0; c < D; c += 4) {
-      const float4 u = *reinterpret_cast<const float4*>(xa + c), v = *reinterpret_cast<const float4*>(xb + c);
-      a0 = fma((double)u.x, (double)v.x, a0); a1 = fma((double)u.y, (double)v.y, a1);
-      a2 = fma((double)u.z, (double)v.z, a2); a3 = fma((double)u.w, (double)v.w, a3);
-    }
-    return (a0 + a1) + (a2 + a3);
-  };
+  // one order per dim: four interleaved chains over the float4 columns, closed pairwise (pair_sim.h)
+  auto dot_rows = [&](int a, int b) { return dot_rows_f64(s_x + a * LD, s_x + b * LD, D); };
   if (EMB && need_sim) {
     // 16 lanes per row, four rows at a time
     const int grp = lane >> 4, gl = lane & 15;
@@ -233,20 +224,17 @@ __global__ __launch_bounds__(64) void diverse_rerank_kernel(RerankArgs A) {
     if (lane == t) { o_id = wid; o_pos = win; o_sc = wsc; o_obj = wobj; }
     if (lane == win) taken = true;
     if (need_sim && t + 1 < steps) {
-      double sim = 0.0;
+      double sim = 0.0, e = 0.0;
       if (GEO) {
         const double wlat = __shfl(lat, win, 64), wlon = __shfl(lon, win, 64), wcp = __shfl(cp, win, 64);
-        const double sa = sin((lat - wlat) * 0.008726646259971648), sb = sin((lon - wlon) * 0.008726646259971648);      // pi / 360
-        const double q = sa * sa + cp * wcp * (sb * sb);
-        const double d = 12742.0 * asin(fmin(1.0, sqrt(q)));
-        sim = g * exp(-d / A.scale_km);
+        sim = geo_part(g, sin2_dist_km(lat, lon, cp, wlat, wlon, wcp), A.scale_km);
       }
       if (EMB) {
         const double wn = __shfl(nrm, win, 64);
         const double dt = dot_rows(lane, win);
-        const double e = (nrm == 0.0 || wn == 0.0) ? 0.0 : dt / (nrm * wn);
-        sim = GEO ? sim + omg * e : omg * e;
+        e = (nrm == 0.0 || wn == 0.0) ? 0.0 : dt / (nrm * wn);
       }
+      sim = sim_mix<GEO, EMB>(sim, omg, e);
       pen = t == 0 ? sim : fmax(pen, sim);
     }
   }

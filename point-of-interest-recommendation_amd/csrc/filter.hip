@@ -71,6 +71,7 @@ __global__ __launch_bounds__(POI_BLOCK) void filter_build_kernel(FilterBuildArgs
   }
   __syncthreads();
   const unsigned need = A.need[q], any = A.any[q], forbid = A.forbid[q];
+  const bool flagged = A.flags && (need | any | forbid) != 0u;      // (a predicate without flag words reads no flags: every word passes it)
   const long long span = A.ldw * 32;                // bit positions of a row, the pad words included
   unsigned* const out = A.bits + (size_t)q * A.ldw;
   int cnt = 0, nbad = 0;
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(POI_BLOCK) void filter_build_kernel(FilterBuildArgs
     const long long j = j0 + lane;
     bool pass = false, stray = false;
     if (j < A.n_item) {
-      const unsigned f = A.flags ? A.flags[j] : 0u;
+      const unsigned f = flagged ? A.flags[j] : 0u;
       pass = (f & need) == need && (any == 0u || (f & any) != 0u) && (f & forbid) == 0u;
       if (A.cat) {
         const int c = A.cat[j];

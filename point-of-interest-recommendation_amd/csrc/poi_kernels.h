@@ -672,6 +672,38 @@ struct AudienceArgs {
 hipError_t launch_audience(const AudienceArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_audience_rows(const AudienceArgs& A, hipStream_t st, Timing* tm);
 
+// Similar rows (similar.hip): the top-K rows of ONE table most similar to each query row - audience.hip's walk with the table on both
+// sides and a float64 similarity epilogue; the nearest history POI of every listed POI
+#define SIMILAR_K_MAX 32                    // list length (one half wave)
+struct SimilarArgs {
+  const void* x; int x_f16;                                   // (n, dim) float32 or IEEE half: the table, on both sides
+  int n, dim, k;
+  const double* inv;                                          // (n) 1 / |x_i|, 0 for a zero row (row_inv_norms_kernel)
+  const double *coords, *cphi; double g, omg, scale_km;       // geographic part (coords null: g == 0); omg = 1 - g
+  const int* queries; int n_q;                                // the query rows
+  const int *ex_off, *ex;                                     // per-query exclusion lists (ascending row indices), or both null
+  int n_split;                                                // slices of the row range, one workgroup each per 32-query block
+  float* part_s; int *part_i, *part_cnt;                      // split regime: (n_q, n_split, SIMILAR_K_MAX) partial lists, (n_q, n_split) counts
+  int* idx_out; float* score_out; int* count_out;             // (n_q, k); score_out / count_out may be null
+  float* rows_out; long long ld;                              // poi_similar_rows: rows_out[q * ld + j], ld >= n
+  int count_bad;                                              // 0: the caller counts the rejected queries itself (rows + select route)
+  int* bad;                                                   // device counter of rejected queries (poi_ctx_take_bad_ids)
+};
+struct NearestArgs {
+  const void* items; int items_f16; int n_item, dim;          // the item rows of the embedding part (null with geo_weight 1)
+  const double *coords, *cphi; double geo_weight, scale_km;   // (n_item, 2) lat, lon; cos(lat) (null with geo_weight 0)
+  const int* lists; int n, k;                                 // (n, k) listed POIs, -1 fill
+  const int *h_off, *h_ids;                                   // CSR of the rows' history POIs, in the order given
+  int* pos_out; double* sim_out;                              // (n, k); sim_out may be null
+  int* bad;                                                   // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+hipError_t launch_row_inv_norms(const void* x, int x_f16, int n, int dim, double* inv_out, hipStream_t st, Timing* tm);
+hipError_t launch_similar(const SimilarArgs& A, hipStream_t st, Timing* tm);         // the fused walk (+ the slices' merge)
+hipError_t launch_similar_rows(const SimilarArgs& A, hipStream_t st, Timing* tm);    // the store epilogue
+// after poi_topk_select over rows_out: count_out loses the query's own row, a rejected query is counted once and lists nothing
+hipError_t launch_similar_fix_counts(const SimilarArgs& A, hipStream_t st);
+hipError_t launch_similar_nearest(const NearestArgs& A, hipStream_t st, Timing* tm);
+
 // Route recommendation (route.hip): one beam-search step - per row the best b candidates and the normaliser over all POIs; the merge
 #define ROUTE_B_MAX 8                       // beam width: list length, and parents x b <= 64 proposals meet in one wave
 #define ROUTE_T_MAX 16                      // steps: the longest path a row may carry

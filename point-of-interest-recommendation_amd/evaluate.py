@@ -213,6 +213,44 @@ def audience_recall(model, ks, exclude="train"):
     return {k: (float(h[i]) / t if t else 0.0) for i, k in enumerate(ks)}
 
 
+def _covisit_share(voff, vus, a, b):
+    """The share of the POI pairs (a[i], b[i]) that share at least one visitor.  (voff, vus): data.visitors_csr - per POI its distinct
+    visitors, ascending, so poi * n_user + user is one sorted key array; every visitor of a[i] is looked up among the visitors of b[i]."""
+    voff, vus = np.asarray(voff, np.int64), np.asarray(vus, np.int64)
+    a, b = np.asarray(a, np.int64).reshape(-1), np.asarray(b, np.int64).reshape(-1)
+    if not len(a):
+        return 0.0
+    if not len(vus):
+        return 0.0
+    stride = int(vus.max()) + 1
+    keys = np.repeat(np.arange(len(voff) - 1), np.diff(voff)) * stride + vus
+    ln = voff[a + 1] - voff[a]
+    pair = np.repeat(np.arange(len(a)), ln)
+    pos = np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln - voff[a], ln)
+    want = b[pair] * stride + vus[pos]
+    at = np.minimum(np.searchsorted(keys, want), len(keys) - 1)
+    hit = np.zeros(len(a), bool)
+    hit[pair[keys[at] == want]] = True
+    return float(hit.mean())
+
+
+def similar_covisit_rate(model, k, geo_weight=0.0, scale_km=1.0, seed=0):
+    """Do the similar-POI lists mean something?  Over every POI as a query: the share of (POI, similar POI) pairs
+    (model.similar_pois at k) that share at least one TRAIN visitor (data.visitors_csr), and beside it the same share for k random
+    other POIs per query, drawn under a fixed seed.  Returns dict(similar=, random=, pairs= the listed pairs)."""
+    from .data import visitors_csr
+    n = model.n_item
+    voff, vus = visitors_csr(model._off_host, model.p.cpu().numpy(), n)
+    pois = np.arange(n)
+    idx = model.similar_pois(pois, k, geo_weight=geo_weight, scale_km=scale_km).cpu().numpy().astype(np.int64)
+    q = np.repeat(pois, idx.shape[1]).reshape(idx.shape)
+    listed = idx >= 0
+    rnd = np.random.default_rng(seed).integers(0, max(n - 1, 1), idx.shape)
+    rnd = np.minimum(rnd + (rnd >= q), n - 1)                       # (any POI but the query itself)
+    return dict(similar=_covisit_share(voff, vus, q[listed], idx[listed]), random=_covisit_share(voff, vus, q[listed], rnd[listed]),
+                pairs=int(listed.sum()))
+
+
 def foldin_rank_metrics(model, histories, targets, at_nums, exclude="history", **fold_in_kwargs):
     """full_rank_metrics for HELD-OUT users of the factorisation family, of the successive-POI models OboFpmc_lr / OboPrme and of
     OboPoi2vec (strong generalisation): every history is folded in (model.rank_new: fold_in, then the exact rank of its targets among all POIs) and the

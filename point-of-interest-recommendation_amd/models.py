@@ -1267,6 +1267,172 @@ class _Base:
             rows, term = torch.zeros((0, self.kdim), dtype=torch.float32, device=self.device), None
         return self._audience_launch(rows.contiguous(), self._items(), self.kdim, term, q, ex, k, seg_dev, return_scores, return_counts, sync)
 
+    # ---- similar POIs and users (poi_similar_topk / poi_similar_rows / poi_similar_nearest): rows like this one ---------------------------
+    SIMILAR_K_FUSED = 32        # the fused entry's list length; beyond it: similarity rows + poi_topk_select
+
+    def _similar_args(self, k, n, geo_weight, scale_km):
+        k, geo_weight, scale_km = int(k), float(geo_weight), float(scale_km)
+        if not (1 <= k <= min(self.CANDIDATES_K_MAX, n - 1) or 1 <= k <= self.SIMILAR_K_FUSED):
+            raise ValueError("similar rows support 1 <= k <= min(%d, rows - 1 = %d), or k <= 32 whatever the row count (got %d)"
+                             % (self.CANDIDATES_K_MAX, n - 1, k))
+        if not 0.0 <= geo_weight < 1.0:
+            raise ValueError("geo_weight must lie in [0, 1) (got %r)" % (geo_weight,))
+        if not scale_km > 0.0:
+            raise ValueError("scale_km must be positive (got %r)" % (scale_km,))
+        return k, geo_weight, scale_km
+
+    def _similar_queries(self, ids, n, what):
+        """ids -> int32 device tensor (n_q).  Host ids are range-checked (IndexError before any launch); a device tensor is left to the kernel."""
+        if isinstance(ids, torch.Tensor) and ids.is_cuda:
+            return ids.to(self.device, torch.int32).reshape(-1).contiguous()
+        a = np.atleast_1d(np.asarray(ids.cpu().numpy() if isinstance(ids, torch.Tensor) else ids)).astype(np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= n):
+            raise IndexError("%s must lie in [0, %d) (found %d..%d)" % (what, n, int(a.min()), int(a.max())))
+        return torch.as_tensor(a.astype(np.int32)).to(self.device)
+
+    def _similar_launch(self, x, n, coords, cphi, q, ex, k, geo_weight, scale_km, what, return_scores, return_counts, sync):
+        """The rows of x[:n] most similar to x[q]: one poi_similar_topk call for k <= 32; beyond, poi_similar_rows into a bounded buffer, a
+        number of queries at a time, + poi_topk_select (no host synchronisation between the chunks)."""
+        n_q, dim = q.numel(), x.shape[1]
+        if dim % 4 or dim > 256:
+            raise _lib.PoiError("the similarity supports rows of a multiple of 4 up to 256 columns (got %d)" % dim)
+        idx = torch.empty((n_q, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n_q, k), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n_q, dtype=torch.int32, device=self.device) if return_counts else None
+        head = [self.ctx.handle, _ptr(x), n, dim, _ptr(coords), _ptr(cphi), geo_weight, scale_km]
+        if n_q and k <= self.SIMILAR_K_FUSED:
+            self.ctx.check(self.lib.poi_similar_topk(*head, None, _ptr(q), n_q, _ptr(ex[0]), _ptr(ex[1]), k, _ptr(idx), _ptr(sc), _ptr(cnt), self._stream()))
+        elif n_q:
+            inv = torch.empty(n, dtype=torch.float64, device=self.device)
+            self.ctx.check(self.lib.poi_row_inv_norms(self.ctx.handle, _ptr(x), n, dim, _ptr(inv), self._stream()))
+            ld = (n + 31) // 32 * 32
+            per = max(1, min(n_q, self.SCORE_ROWS_BYTES // (4 * ld)))
+            buf = torch.empty((per, ld), dtype=torch.float32, device=self.device)
+            for o in range(0, n_q, per):
+                c = min(per, n_q - o)
+                self.ctx.check(self.lib.poi_similar_rows(*head, _ptr(inv), ctypes.c_void_p(q.data_ptr() + 4 * o), c, _ptr(buf), ld, self._stream()))
+                self._audience_select(buf, c, n, ld, k, ex, o, idx, sc, cnt)
+            if cnt is not None:
+                # the selection counted [0, n) minus the list: the query's own row leaves the count unless the list named it; a rejected
+                # query's row is -inf: nothing is listed, and nothing counted
+                named = torch.zeros(n_q + 1, dtype=torch.int32, device=self.device)
+                if ex[0] is not None:
+                    row = torch.bucketize(torch.arange(ex[1].numel(), device=self.device), ex[0][1:].long(), right=True)
+                    hit = (row < n_q) & (ex[1] == q[row.clamp(max=n_q - 1)])
+                    named.index_add_(0, row, hit.int())
+                valid = (q >= 0) & (q < n)
+                cnt = torch.where(valid, (cnt - 1 + named[:n_q].clamp(max=1)).clamp(min=0), torch.zeros_like(cnt))
+        return self._serve_out(idx, ((sc, return_scores), (cnt, return_counts)), sync and n_q > 0,
+                               "%s outside [0, %d) or with a malformed exclusion list: their lists are all -1" % (what, n))
+
+    def similar_pois(self, pois, k, geo_weight=0.0, scale_km=1.0, exclude=None, return_scores=False, return_counts=False, sync=True):
+        """PLACES LIKE THIS ONE (include/poi_hip.h, poi_similar_topk): for every query POI the k POIs most similar to it under
+        sim = geo_weight * exp(-distance_km / scale_km) + (1 - geo_weight) * cosine(item rows) - the similarity of the MMR re-ranking
+        (compute_sub_topk_diverse), taken over the whole catalogue, on the table the model scores with.  The query itself is no
+        candidate; exclude: None or a CSR pair (off, ids) of POI ids per query, ascending and unique.  0 <= geo_weight < 1.  Returns
+        (n_q, k) int32 POI ids on the device by descending similarity, ties by ascending id, -1 where a query has fewer than k candidates
+        (scores -inf); with return_counts the candidate count of every query.  1 <= k <= 32 is one fused call; 32 < k <=
+        min(4096, n_item - 1) goes through poi_similar_rows, a bounded number of queries at a time, and poi_topk_select.  It is a
+        similarity of the model's POI rows, not a decomposition of any score.  Host arguments are checked before the launch
+        (ValueError / IndexError); device tensors are checked by the kernel: an offending query comes out all -1 and - with sync -
+        raises IndexError (sync=False leaves the count to ctx.take_bad_ids()).  Models without a single POI table refuse it."""
+        n = self.n_item
+        k, geo_weight, scale_km = self._similar_args(k, n, geo_weight, scale_km)
+        items, _, coords, cphi = self._diverse_sim(geo_weight, self._diverse_items())
+        q = self._similar_queries(pois, n, "pois")
+        ex = self._audience_exclusion(exclude, q, None, n, kinds=())
+        return self._similar_launch(items, n, coords, cphi, q, ex, k, geo_weight, scale_km, "query POI(s)", return_scores, return_counts, sync)
+
+    def similar_users(self, users, k, exclude=None, return_scores=False, return_counts=False, sync=True):
+        """USERS LIKE THIS ONE: similar_pois over the user rows the model scores with (_users_rows of every user), by the cosine alone.
+        Offered by the models whose score is users . items; the others raise ValueError."""
+        if not self._rank_fused:
+            raise ValueError("%s ranks by a score rule of its own, not users . items: its user rows carry no cosine similarity" % type(self).__name__)
+        n = self.n_user
+        k, _, _ = self._similar_args(k, n, 0.0, 1.0)
+        rows = self._users_rows(np.arange(n))[1].contiguous()
+        q = self._similar_queries(users, n, "users")
+        ex = self._audience_exclusion(exclude, q, None, n, kinds=())
+        return self._similar_launch(rows, n, None, None, q, ex, k, 0.0, 1.0, "query user(s)", return_scores, return_counts, sync)
+
+    def _similar_train(self):
+        """Every user's train sequence as a CSR (off host int64, off int32, ids int32 on the device), padding ids (>= n_item) dropped; built once."""
+        t = self.__dict__.get("_similar_train_csr")
+        if t is None:
+            if getattr(self, "_off_host", None) is None or getattr(self, "p", None) is None:
+                raise _lib.PoiError("%s keeps no (off, p) train table: pass the histories as (off, ids)" % type(self).__name__)
+            off, p = self._off_host.astype(np.int64), self.p.cpu().numpy().astype(np.int64)
+            keep = (p >= 0) & (p < self.n_item)
+            no = np.concatenate(([0], np.cumsum(keep)))[off]
+            i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+            ids = p[keep]
+            t = self._similar_train_csr = (no, ids, i32(no), i32(ids) if len(ids) else torch.zeros(1, dtype=torch.int32, device=self.device))
+        return t
+
+    def nearest_visited(self, start_end, lists, histories="train", geo_weight=0.0, scale_km=1.0, return_sims=False, sync=True):
+        """BECAUSE YOU VISITED X (include/poi_hip.h, poi_similar_nearest): for every POI on a row's list - lists (n, k <= 32), -1 fill,
+        typically the row's recommendations - the POI of the row's history it is most similar to, under compute_sub_topk_diverse's
+        float64 similarity (0 <= geo_weight <= 1).  histories: "train" (the rows' train sequences) or a CSR pair (off, ids) of POI ids per
+        row, in any order, duplicates allowed.  Returns (n, k) int32 history POI ids on the device, -1 where there is none (a -1 entry,
+        an empty history)[, the (n, k) float64 similarities, -inf there]; ties go to the earlier history position.  This attributes a
+        recommendation to the most similar visited POI - it does NOT decompose the model's score.  Host arguments are checked before the
+        launch; device tensors by the kernel (an offending row comes out all -1 and - with sync - raises IndexError)."""
+        geo_weight, scale_km = float(geo_weight), float(scale_km)
+        if not 0.0 <= geo_weight <= 1.0:
+            raise ValueError("geo_weight must lie in [0, 1] (got %r)" % (geo_weight,))
+        if not scale_km > 0.0:
+            raise ValueError("scale_km must be positive (got %r)" % (scale_km,))
+        items, kdim, coords, cphi = self._diverse_sim(geo_weight, self._diverse_items() if geo_weight < 1.0 else None)
+        ids, lo = self._ids(start_end)
+        n = ids.numel()
+        if isinstance(lists, torch.Tensor) and lists.is_cuda:
+            lt = lists.to(self.device, torch.int32)
+        else:
+            a = np.asarray(lists.cpu().numpy() if isinstance(lists, torch.Tensor) else lists).astype(np.int64)
+            if a.size and (a.min() < -1 or a.max() >= self.n_item):
+                raise IndexError("listed POIs must lie in [-1, %d) (found %d..%d)" % (self.n_item, int(a.min()), int(a.max())))
+            lt = torch.as_tensor(a.astype(np.int32)).to(self.device)
+        if lt.dim() != 2 or lt.shape[0] != n or not 1 <= lt.shape[1] <= 32:
+            raise ValueError("lists must be (%d rows, 1 <= k <= 32) (got %s)" % (n, tuple(lt.shape)))
+        lt, k = lt.contiguous(), lt.shape[1]
+        i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+        if isinstance(histories, str):
+            if histories != "train":
+                raise ValueError("histories must be 'train' or a pair (off, ids) (got %r)" % (histories,))
+            off_h, ids_h, off_d, ids_d = self._similar_train()
+            if lo is not None:                                  # a contiguous user range: its offsets index the cached ids as they are
+                h_off, h_ids = off_d[lo:lo + n + 1], ids_d
+            else:
+                a = ids.cpu().numpy().astype(np.int64)
+                ln = off_h[a + 1] - off_h[a]
+                pos = np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln - off_h[a], ln)
+                h_off, h_ids = i32(np.concatenate(([0], np.cumsum(ln)))), (i32(ids_h[pos]) if len(pos) else torch.zeros(1, dtype=torch.int32, device=self.device))
+        else:
+            off, hid = histories
+            if isinstance(off, torch.Tensor) and off.is_cuda and isinstance(hid, torch.Tensor) and hid.is_cuda:
+                h_off, h_ids = off.to(self.device, torch.int32).contiguous(), hid.to(self.device, torch.int32).contiguous()
+            else:
+                off = np.asarray(off.cpu().numpy() if isinstance(off, torch.Tensor) else off).astype(np.int64).reshape(-1)
+                hid = np.asarray(hid.cpu().numpy() if isinstance(hid, torch.Tensor) else hid).astype(np.int64).reshape(-1)
+                if len(off) == 0 or off[0] < 0 or np.any(np.diff(off) < 0) or off[-1] > len(hid):
+                    raise ValueError("histories=(off, ids): off must ascend from >= 0 to at most len(ids)")
+                if hid.size and (hid.min() < 0 or hid.max() >= self.n_item):
+                    raise IndexError("history POIs must lie in [0, %d) (found %d..%d)" % (self.n_item, int(hid.min()), int(hid.max())))
+                h_off, h_ids = i32(off), i32(hid)
+            if h_off.numel() != n + 1:
+                raise ValueError("histories=(off, ids): off must hold n + 1 = %d offsets" % (n + 1))
+            if not h_ids.numel():
+                h_ids = torch.zeros(1, dtype=torch.int32, device=self.device)
+        pos = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        sim = torch.empty((n, k), dtype=torch.float64, device=self.device) if return_sims else None
+        if n:
+            self.ctx.check(self.lib.poi_similar_nearest(self.ctx.handle, _ptr(items), self.n_item, kdim, _ptr(coords), _ptr(cphi), geo_weight, scale_km,
+                                                        _ptr(lt), n, k, _ptr(h_off), _ptr(h_ids), _ptr(pos), _ptr(sim), self._stream()))
+        at = (h_off[:-1].long()[:, None] + pos.clamp(min=0).long()).clamp(max=h_ids.numel() - 1)
+        out = torch.where(pos >= 0, h_ids[at], torch.full_like(pos, -1))
+        return self._serve_out(out, ((sim, return_sims),), sync and n > 0,
+                               "row(s) with a listed or history POI outside [0, %d): their entries are all -1" % self.n_item)
+
     # ---- diversified recommendation (poi_diverse_topk / poi_diverse_rerank): a pool of the best candidates, re-ranked by MMR --------------
     def _diverse_items(self):
         """The POI rows the embedding similarity is taken between: the table the model scores with.  None: the model has no single POI
