@@ -99,6 +99,9 @@ extern "C" {
  * poi_similar_nearest, options "similar_split_max" / "similar_grid" / "similar_rows_max", plan keys "similar_path" / "similar_splits" /
  * "similar_split_max", timing names "similar_topk" (with "similar_norms" / "similar_walk" / "similar_merge" or "similar_rows" /
  * "topk_select" inside it) / "similar_rows" / "similar_nearest" (existing entries unchanged). */
+/* additive to 9: capped recommendation - new entry points poi_labels_build, poi_score_topk_capped and poi_topk_capped_scores, options
+ * "capped_split_max" / "capped_grid" / "capped_hist_kb", plan keys "capped_splits" / "capped_split_max", timing names "labels_build" / "score_topk_capped"
+ * (with "capped_walk" / "capped_merge" inside it) / "topk_capped_scores" (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -199,7 +202,8 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * Additive to 9: "audience_path" (0 one workgroup per query block, 1 slices), "audience_splits" (slices, 0 outside the split regime),
  * "audience_split_max" - written by poi_score_audience / poi_audience_rows.
  * Additive to 9: "similar_path" (0 one workgroup per query block, 1 slices, 2 score rows + selection), "similar_splits" (slices of the
- * walk, 0 with one workgroup per query block), "similar_split_max" - written by poi_similar_topk / poi_similar_rows. */
+ * walk, 0 with one workgroup per query block), "similar_split_max" - written by poi_similar_topk / poi_similar_rows.
+ * Additive to 9: "capped_splits" (slices, 0 outside the split regime), "capped_split_max" - written by poi_score_topk_capped. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -305,7 +309,13 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *       same few milliseconds for 257 queries as for 8192;
  *   "similar_rows_max" n (default 1024, at most 4096): poi_similar_topk calls of at most n queries write their score rows
  *       (poi_similar_rows' walk) and select from them (poi_topk_select's kernels) instead of keeping fused lists - for few queries the
- *       faster route; 0: never.  Bitwise the same result for every n. */
+ *       faster route; 0: never.  Bitwise the same result for every n;
+ *   "capped_split_max" n (default 256) / "capped_grid" n (default 0 = by the row count and the CUs; at most 64): the split regime
+ *       of poi_score_topk_capped and its slices, as "filter_split_max" / "filter_grid" are the walk path's of
+ *       poi_score_topk_filtered - bitwise the same result for every n and in either regime;
+ *   "capped_hist_kb" n (default 262144 = 256 MiB): poi_labels_build keeps at most n KiB of per-predicate label histograms
+ *       ((n_label + 1) ints per predicate) in the context's workspace at a time - whole predicates, at least one; more predicates go
+ *       through it in chunks.  The same tables for every n. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -1212,7 +1222,8 @@ int poi_score_candidates(poi_ctx* ctx, const float* users, const float* items, i
  *
  * poi_filter_build writes bits_out (P, ldw) uint32, ldw >= W = ceil(n_item / 32): POI j is bit j & 31 of word j >> 5 of its
  * predicate's row; the bits at j >= n_item (the pad words included) are written as 0.  count_out (P) int32 or NULL: the popcounts.
- * All arrays are device memory.  One small kernel, integer work only.  Timing name: "filter_build".  P = 0 is a no-op.  The ranking
+ * All arrays are device memory.  One small kernel, integer work only; the predicate words are copied aside before it runs, so
+ * bits_out may overlap them.  Timing name: "filter_build".  P = 0 is a no-op.  The ranking
  * entries take ONLY the bitmap: a caller with a predicate of its own (opening hours evaluated at query time) packs a mask itself.
  *
  * The ranking entries:
@@ -1266,6 +1277,74 @@ int poi_topk_filtered_scores(poi_ctx* ctx, const float* scores, int32_t n, int32
                              const uint32_t* bits, int64_t ldw, int32_t n_pred, const int32_t* pred,
                              const int32_t* ex_off, const int32_t* ex, int32_t k,
                              int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+
+/* ---- capped recommendation (additive to 9): the top-K with at most `per` POIs of one label -------------------------------------------------
+ * "The best 20 places, but no more than 2 of the same category" (or chain, or neighbourhood) - the hard cap of a carousel; with a cap of
+ * 1, "which kinds of place for this user, and the best one of each".  poi_diverse_topk trades relevance against similarity softly
+ * inside a pool of 64 and can promise no cap; poi_score_topk_filtered restricts to one predicate and does not spread over labels.
+ *
+ *   labels        (n_item) int32, device.  labels[j] >= 0 names POI j's group; labels[j] < 0 means unlabelled: the POI is a group of
+ *                 its own and is never capped.  The ranking entries index nothing by a label: any non-negative value is a group.
+ *   cap           1 <= per <= 32, and 1 <= k <= 32.
+ *   C(r)          poi_score_topk_filtered's candidate set without a radius: bit j of row pred[r] of bits (bits == NULL: every POI
+ *                 passes, and ldw / n_pred / pred are ignored) minus ex[ex_off[r] .. ex_off[r + 1]).
+ *   score         poi_score_rank's s(r, j), BIT FOR BIT: users[r] . items[j] from the same product routine and k order, plus - with
+ *                 wd non-NULL - wd * sts[r][bin(anchor[r], j)] for bin < n_dist (the anchor in last_poi's place; a row with
+ *                 anchor[r] < 0 has no distance term), exactly as poi_score_topk_filtered has it.
+ *   order, zeros  higher score first, then the lower id; -0.0 and +0.0 are one score, written as +0.0; NaN and -inf are not
+ *                 selectable, +inf is.
+ *   result        walk the selectable members of C(r) in that order; take j unless labels[j] >= 0 and `per` entries already taken
+ *                 carry labels[j]; stop at k.  Equivalently: j is kept iff fewer than `per` selectable candidates of its label
+ *                 precede it, and the list is the first k kept.  -1 ids and -inf scores behind them, as poi_score_candidates.
+ *   outputs       idx_out (n, k); score_out (n, k) or NULL; label_out (n, k) or NULL: labels[idx], -1 on the fill; count_out (n) or
+ *                 NULL: |C(r)|, neither clipped to k nor reduced by the cap.
+ *   bad rows      as poi_score_topk_filtered: pred[r] outside [0, n_pred), an anchor outside [-1, n_item), an exclusion list that is
+ *                 not ascending or leaves [0, n_item): all -1 / -inf, count 0, counted once (poi_ctx_take_bad_ids).
+ *   limits        dim a multiple of 4, <= 256; items float32 or a registered half table; n_dist <= 4096 with the distance term; no
+ *                 radius.  k, per or dim outside their range: POI_ENOTSUP.  NULL labels: POI_EINVAL.  n = 0 is a no-op.
+ *   determinism   no float atomics; identical bits on every grid, in both launch regimes, for a row alone or in a call of thousands.
+ * It follows that the list for k' < k is a prefix of the list for k; that with per >= k, with all labels distinct or with all labels
+ * negative the result is poi_score_topk_filtered's / poi_topk_filtered_scores' bit for bit; and that with one label for every POI the
+ * list is the plain top-`per`.
+ *
+ * The fill gate.  The kernels skip a candidate that does not beat entry g - 1 of its row's list.  Under a cap the list may never reach
+ * k entries (five labels with per = 2 fill 10), so g = min(k, fill[pred[r]][per]) with fill (max(n_pred, 1), 33) int32 from
+ * poi_labels_build:  fill[q][m] = #(unlabelled POIs passing q) + sum over the labels of min(m, #POIs of the label passing q),  the
+ * longest list predicate q can give under the cap m.  fill == NULL means g = k: correct, but every (row, POI) pair of a row whose list
+ * cannot fill takes the serial path.  Any value at or above the true one is safe, only slower; a value BELOW it is a caller error that
+ * yields lists cut at that value.  Exclusion lists are not in fill: a row whose list empties a label stays correct and slow.
+ *
+ * poi_labels_build - labels, and bits (n_pred, ldw) or NULL with n_pred = 0 (one row: every POI passes).  Requires
+ * 1 <= n_label <= n_item.  Writes fill_out (max(n_pred, 1), 33) and, if not NULL, count_out (n_label): the POIs of every label in
+ * [0, n_label), whatever they pass.  A label >= n_label is counted once per POI (poi_ctx_take_bad_ids) and entered as unlabelled, which
+ * keeps fill an upper bound.  Integer atomics on a context-owned histogram only, at most "capped_hist_kb" KiB of it at a time.
+ * Timing name: "labels_build" (once per chunk of predicates).
+ *
+ * poi_score_topk_capped - the counterpart of poi_score_topk_filtered(path = POI_FILTER_WALK): users .. dd are poi_score_rank's
+ * arguments with anchor in last_poi's place; the same tile walk with 32-entry lists that carry the label of every entry, a cap-aware
+ * insertion, and pairwise merges of the waves' and the slices' lists with the cap re-applied after each (DESIGN.md section 30 says why
+ * a plain best-64 followed by one cap is wrong).  Calls of at most "capped_split_max" rows (default 256) cut the item range of every
+ * 32-row tile into "capped_grid" slices (0: by the row count and the CUs; at most 64), a workgroup each, and merge.
+ * poi_ctx_last_plan: "capped_splits" (0 outside the split regime), "capped_split_max".  Timing name: "score_topk_capped", with
+ * "capped_walk" and "capped_merge" inside it.
+ *
+ * poi_topk_capped_scores - the counterpart of poi_topk_filtered_scores: the definition on explicit float32 score rows scores (n, ld),
+ * ld >= n_item, one workgroup per row, for the models whose score is not users . items, and an independent check of the walk.  Timing
+ * name: "topk_capped_scores". */
+int poi_labels_build(poi_ctx* ctx, const int32_t* labels, int32_t n_item, int32_t n_label,
+                     const uint32_t* bits, int64_t ldw, int32_t n_pred, int32_t* count_out, int32_t* fill_out, void* stream);
+int poi_score_topk_capped(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                          const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* anchor,
+                          int32_t n_dist, double dd,
+                          const int32_t* labels, int32_t per, const int32_t* fill,
+                          const uint32_t* bits, int64_t ldw, int32_t n_pred, const int32_t* pred,
+                          const int32_t* ex_off, const int32_t* ex, int32_t k,
+                          int32_t* idx_out, float* score_out, int32_t* label_out, int32_t* count_out, void* stream);
+int poi_topk_capped_scores(poi_ctx* ctx, const float* scores, int32_t n, int32_t n_item, int64_t ld,
+                           const int32_t* labels, int32_t per, const int32_t* fill,
+                           const uint32_t* bits, int64_t ldw, int32_t n_pred, const int32_t* pred,
+                           const int32_t* ex_off, const int32_t* ex, int32_t k,
+                           int32_t* idx_out, float* score_out, int32_t* label_out, int32_t* count_out, void* stream);
 
 /* ---- audience recommendation (additive to 9): given a POI, which users? -------------------------------------------------------------------
  * Every entry above ranks POIs for a row.  poi_score_audience ranks ROWS for a POI: for query POIs pois[q] (q < n_q) and the candidate

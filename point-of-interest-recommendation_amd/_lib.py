@@ -209,6 +209,12 @@ SIGNATURES = {
                                         c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_topk_filtered_scores": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_labels_build": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "poi_score_topk_capped": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int32, c_double, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_topk_capped_scores": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                       c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_foldin_bpr": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float, c_float,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_foldin_terms_fpmc": (c_int, [c_void_p, POINTER(FpmcParams), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p]),
@@ -278,7 +284,7 @@ PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", 
              "diverse_path", "diverse_splits", "diverse_split_max",
              "select_rows_per_chunk", "select_chunks", "select_path", "select_splits", "xfwd_ids_lds",
              "filter_path", "filter_splits", "filter_split_max", "audience_path", "audience_splits", "audience_split_max",
-             "similar_path", "similar_splits", "similar_split_max")
+             "similar_path", "similar_splits", "similar_split_max", "capped_splits", "capped_split_max")
 
 
 class Context:
@@ -374,7 +380,8 @@ class Context:
         poi_route_expand; "diverse_split_max" / "diverse_grid" of poi_diverse_pool / poi_diverse_topk; "select_split_max" /
         "select_grid" / "select_chunk_mb" of poi_topk_select / poi_score_candidates; "filter_split_max" / "filter_grid" / "filter_gather_cost" of
         poi_score_topk_filtered; "audience_split_max" / "audience_grid" of poi_score_audience / poi_audience_rows; "similar_split_max" /
-        "similar_grid" / "similar_rows_max" of poi_similar_topk / poi_similar_rows)."""
+        "similar_grid" / "similar_rows_max" of poi_similar_topk / poi_similar_rows; "capped_split_max" / "capped_grid" of
+        poi_score_topk_capped, "capped_hist_kb" of poi_labels_build)."""
         self.check(self.lib.poi_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def set_small_launch(self, max_sequences=1800):

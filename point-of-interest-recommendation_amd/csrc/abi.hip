@@ -748,7 +748,9 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
                       {"filter_gather_cost", &c->filter_gather_cost, 1, 1 << 20},
                       {"audience_split_max", &c->audience_split_max, 0, 1 << 30}, {"audience_grid", &c->audience_grid, 0, AUDIENCE_SPLIT_LIMIT},
                       {"similar_split_max", &c->similar_split_max, 0, 1 << 30}, {"similar_grid", &c->similar_grid, 0, SIMILAR_SPLIT_LIMIT},
-                      {"similar_rows_max", &c->similar_rows_max, 0, SIMILAR_ROWS_MAX_LIMIT}};
+                      {"similar_rows_max", &c->similar_rows_max, 0, SIMILAR_ROWS_MAX_LIMIT},
+                      {"capped_split_max", &c->capped_split_max, 0, 1 << 30}, {"capped_grid", &c->capped_grid, 0, CAPPED_SPLIT_LIMIT},
+                      {"capped_hist_kb", &c->capped_hist_kb, 1, 1 << 21}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);
@@ -842,7 +844,8 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"audience_path", &poi_ctx::LastPlan::audience_path}, {"audience_splits", &poi_ctx::LastPlan::audience_splits},
       {"audience_split_max", &poi_ctx::LastPlan::audience_split_max},
       {"similar_path", &poi_ctx::LastPlan::similar_path}, {"similar_splits", &poi_ctx::LastPlan::similar_splits},
-      {"similar_split_max", &poi_ctx::LastPlan::similar_split_max}};
+      {"similar_split_max", &poi_ctx::LastPlan::similar_split_max},
+      {"capped_splits", &poi_ctx::LastPlan::capped_splits}, {"capped_split_max", &poi_ctx::LastPlan::capped_split_max}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

@@ -1182,6 +1182,14 @@ int poi_filter_build(poi_ctx* c, const int32_t* cat, const uint32_t* flags, int3
   A.pc_off = pc_off; A.pc = pc; A.need = need; A.any = any; A.forbid = forbid; A.n_pred = n_pred;
   A.bits = bits_out; A.ldw = ldw; A.count = count_out;
   if (int rc = bad_counter(c, st, &A.bad)) return rc;
+  // The kernel's workgroups read the predicate words while others already write bits_out: a caller whose bits_out overlaps need /
+  // any / forbid (one scratch array handed for all of them) would have a late workgroup see a written word as its flag condition and read flags[j] for every POI - beyond a flags array that the all-zero words promised nobody would
+  // read.  The words are copied aside first; the stream orders the copies before the kernel.
+  uint32_t* words = nullptr;
+  if (int rc = carve(c, c->filter_ws, st, [&](Carver& W) { words = (uint32_t*)W.bytes(sizeof(uint32_t) * 3 * (size_t)n_pred); })) return rc;
+  const uint32_t* const src[3] = {need, any, forbid};
+  for (int i = 0; i < 3; ++i) HIPCHK(c, hipMemcpyAsync(words + (size_t)i * n_pred, src[i], sizeof(uint32_t) * (size_t)n_pred, hipMemcpyDeviceToDevice, st));
+  A.need = words; A.any = words + n_pred; A.forbid = words + 2 * (size_t)n_pred;
   HIPCHK(c, poi::launch_filter_build(A, st, &c->tm));
   return POI_OK;
 }
@@ -1254,6 +1262,110 @@ int poi_topk_filtered_scores(poi_ctx* c, const float* scores, int32_t n, int32_t
   A.idx_out = idx_out; A.score_out = score_out; A.count_out = count_out;
   if ((rc = bad_counter(c, st, &A.bad))) return rc;
   HIPCHK(c, poi::launch_filter_scores(A, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// capped recommendation (capped.hip)
+int poi_labels_build(poi_ctx* c, const int32_t* labels, int32_t n_item, int32_t n_label, const uint32_t* bits, int64_t ldw, int32_t n_pred,
+                     int32_t* count_out, int32_t* fill_out, void* stream) {
+  const char* who = "poi_labels_build";
+  if (!c || !labels || !fill_out) return fail(c, POI_EINVAL, "%s: NULL ctx / labels / fill_out", who);
+  if (n_item <= 0 || n_label < 1 || n_label > n_item) return fail(c, POI_EINVAL, "%s: needs n_item > 0 and 1 <= n_label <= n_item (got %d, %d)", who, n_item, n_label);
+  if (bits ? n_pred <= 0 : n_pred != 0) return fail(c, POI_EINVAL, "%s: n_pred must be > 0 with bits and 0 without (got %d)", who, n_pred);
+  if (bits && ldw < ((int64_t)n_item + 31) / 32) return fail(c, POI_EINVAL, "%s: ldw must be >= ceil(n_item / 32) = %d (got %lld)", who, (n_item + 31) / 32, (long long)ldw);
+  if (n_pred > 65535) return fail(c, POI_ENOTSUP, "%s supports at most 65535 predicates per call (got %d)", who, n_pred);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::LabelsBuildArgs A = {};
+  A.labels = labels; A.n_item = n_item; A.n_label = n_label; A.bits = bits; A.ldw = ldw; A.n_pred = n_pred;
+  const size_t rows = n_pred > 0 ? n_pred : 1;
+  // the histogram is (predicates, n_label + 1) ints: many predicates over thousands of labels go through it "capped_hist_kb" KiB at a
+  // time, the stream ordering one chunk's kernels before the next chunk's memset
+  const size_t per_row = sizeof(int) * ((size_t)n_label + 1);
+  size_t chunk = ((size_t)c->capped_hist_kb << 10) / per_row;
+  chunk = chunk < 1 ? 1 : (chunk > rows ? rows : chunk);
+  int rc;
+  if ((rc = carve(c, c->capped_ws, st, [&](Carver& W) { A.hist = (int*)W.bytes(per_row * chunk); }))) return rc;
+  int* bad = nullptr;
+  if ((rc = bad_counter(c, st, &bad))) return rc;
+  for (size_t q0 = 0; q0 < rows; q0 += chunk) {
+    const size_t m = rows - q0 < chunk ? rows - q0 : chunk;
+    A.bits = bits ? bits + q0 * (size_t)ldw : nullptr;
+    A.n_pred = bits ? (int)m : 0;
+    A.unl = A.hist + m * n_label;
+    A.fill = fill_out + q0 * CAPPED_FILL_LD;
+    A.count = q0 == 0 ? count_out : nullptr;             // the per-label counts and the stray labels do not depend on the predicate:
+    A.bad = q0 == 0 ? bad : nullptr;                     // the first chunk reports them
+    HIPCHK(c, poi::launch_labels_build(A, st, &c->tm));
+  }
+  return POI_OK;
+}
+
+// what the two ranking entries check alike: k, the cap, the labels, the optional bitmap
+static int capped_check(poi_ctx* c, const char* who, int32_t n, int32_t n_item, const int32_t* labels, int32_t per, const uint32_t* bits,
+                        int64_t ldw, int32_t n_pred, int32_t k, const int32_t* idx_out) {
+  if (k <= 0 || k > CAPPED_K_MAX) return fail(c, POI_ENOTSUP, "%s supports 1 <= k <= %d (got %d)", who, CAPPED_K_MAX, k);
+  if (per <= 0 || per > CAPPED_PER_MAX) return fail(c, POI_ENOTSUP, "%s supports 1 <= per <= %d (got %d)", who, CAPPED_PER_MAX, per);
+  if (!labels || !idx_out) return fail(c, POI_EINVAL, "%s: NULL labels / idx_out", who);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "%s: n < 0 or n_item <= 0", who);
+  if (bits && n_pred <= 0) return fail(c, POI_EINVAL, "%s: n_pred must be > 0 with bits", who);
+  if (bits && ldw < ((int64_t)n_item + 31) / 32) return fail(c, POI_EINVAL, "%s: ldw must be >= ceil(n_item / 32) = %d (got %lld)", who, (n_item + 31) / 32, (long long)ldw);
+  return POI_OK;
+}
+
+int poi_score_topk_capped(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd,
+                          const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* anchor, int32_t n_dist,
+                          double dd, const int32_t* labels, int32_t per, const int32_t* fill, const uint32_t* bits, int64_t ldw, int32_t n_pred,
+                          const int32_t* pred, const int32_t* ex_off, const int32_t* ex, int32_t k, int32_t* idx_out, float* score_out,
+                          int32_t* label_out, int32_t* count_out, void* stream) {
+  const char* who = "poi_score_topk_capped";
+  if (!c || !users || !items) return fail(c, POI_EINVAL, "%s: NULL ctx / users / items", who);
+  int rc;
+  hipStream_t st = (hipStream_t)stream;
+  poi::TileOperands T;
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, dim);
+  if ((rc = capped_check(c, who, n, n_item, labels, per, bits, ldw, n_pred, k, idx_out))) return rc;
+  if ((rc = tile_operands(c, who, users, items, n, n_item, dim, wd, sts, coords, cphi, thr, anchor, n_dist, dd, ex_off, ex, st, &T))) return rc;
+  if (wd && n_dist > CAPPED_NDIST_MAX) return fail(c, POI_ENOTSUP, "%s supports n_dist <= %d (got %d)", who, CAPPED_NDIST_MAX, n_dist);
+  if (n == 0) return POI_OK;
+  poi::CappedArgs A = {};
+  put_operands(A, T);
+  A.last_poi = anchor; A.coords = coords; A.cphi = cphi;      // (the anchor is range-checked with or without a distance term)
+  A.k = k; A.labels = labels; A.per = per; A.fill = fill;
+  A.bits = bits; A.ldw = bits ? ldw : 0; A.n_pred = bits ? n_pred : 1; A.pred = bits ? pred : nullptr;
+  A.idx_out = idx_out; A.score_out = score_out; A.label_out = label_out; A.count_out = count_out;
+  // few rows (live traffic): the item range of every 32-row tile is cut into slices so that the call fills the CUs; many rows: one
+  // workgroup per tile
+  const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
+  const SplitPlan sp = plan_split(n, n_utile, c->capped_split_max, c->capped_grid, 2, c->num_cu, ntile / 16, 2, CAPPED_SPLIT_LIMIT);
+  A.n_split = sp.n_split;
+  if (sp.split && (rc = carve_lists(c, c->capped_ws, st, A, (size_t)n * A.n_split, CAPPED_K_MAX))) return rc;
+  c->plan.valid = 1; c->plan.capped_splits = sp.split ? A.n_split : 0; c->plan.capped_split_max = c->capped_split_max;
+  HIPCHK(c, poi::launch_capped_walk(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_topk_capped_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, int64_t ld, const int32_t* labels, int32_t per,
+                           const int32_t* fill, const uint32_t* bits, int64_t ldw, int32_t n_pred, const int32_t* pred, const int32_t* ex_off,
+                           const int32_t* ex, int32_t k, int32_t* idx_out, float* score_out, int32_t* label_out, int32_t* count_out,
+                           void* stream) {
+  const char* who = "poi_topk_capped_scores";
+  if (!c || !scores) return fail(c, POI_EINVAL, "%s: NULL ctx / scores", who);
+  int rc;
+  if ((rc = capped_check(c, who, n, n_item, labels, per, bits, ldw, n_pred, k, idx_out))) return rc;
+  if (ld < n_item) return fail(c, POI_EINVAL, "%s: ld must be >= n_item", who);
+  if ((rc = check_ex_pair(c, who, ex_off, ex))) return rc;
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::CappedScoresArgs A = {};
+  A.scores = scores; A.ld = ld; A.n = n; A.n_item = n_item; A.k = k;
+  A.ex_off = ex_off; A.ex = ex; A.labels = labels; A.per = per; A.fill = fill;
+  A.bits = bits; A.ldw = bits ? ldw : 0; A.n_pred = bits ? n_pred : 1; A.pred = bits ? pred : nullptr;
+  A.idx_out = idx_out; A.score_out = score_out; A.label_out = label_out; A.count_out = count_out;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  HIPCHK(c, poi::launch_capped_scores(A, st, &c->tm));
   return POI_OK;
 }
 

@@ -36,6 +36,7 @@
 #include "poi_kernels.h"
 #include "tile_product.h"
 #include "topk_list.h"
+#include "walk_common.h"
 
 namespace poi {
 
@@ -43,18 +44,6 @@ namespace {
 
 constexpr int WALK_LIST = 64;                                                // list stride: list_take works on one entry per lane
 constexpr int WALK_LISTS_BYTES = POI_NWAVE * 32 * WALK_LIST * 8;             // the waves' per-row lists: scores, then ids
-
-// the score every path ranks: one zero, and is it selectable (neither NaN nor -inf)
-__device__ __forceinline__ float one_zero(float s) { return s == 0.f ? 0.f : s; }
-__device__ __forceinline__ bool selectable(float s) { return s > neg_inf(); }
-__device__ __forceinline__ unsigned tail_mask(int N) { return (N & 31) ? (1u << (N & 31)) - 1u : ~0u; }
-
-// one thread of a workgroup: the part of [e0, e1) it checks - ids inside [0, N) and strictly ascending
-__device__ __forceinline__ int ex_slice_bad(const int* ex, int e0, int e1, int N, int tid, int nthr) {
-  int bad = 0;
-  for (int i = e0 + tid; i < e1; i += nthr) { const int v = ex[i]; bad |= (unsigned)v >= (unsigned)N || (i > e0 && ex[i - 1] >= v); }
-  return bad;
-}
 
 }  // namespace
 

@@ -821,6 +821,43 @@ hipError_t launch_filter_walk(FilterArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_filter_gather(FilterArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_filter_scores(const FilterScoresArgs& A, hipStream_t st, Timing* tm);
 
+// Capped recommendation (capped.hip): the top-K with at most `per` POIs of one label
+#define CAPPED_K_MAX 32                     // list length (one half wave)
+#define CAPPED_PER_MAX 32                   // the largest cap; fill tables hold the caps 0 .. CAPPED_PER_MAX
+#define CAPPED_FILL_LD (CAPPED_PER_MAX + 1) // ints per predicate of a fill table
+#define CAPPED_SPLIT_LIMIT 64               // slices a 32-row tile's item range may be cut into
+#define CAPPED_NDIST_MAX 4096               // distance bins whose thresholds fit the walk kernel's LDS beside its lists
+struct LabelsBuildArgs {
+  const int* labels; int n_item, n_label;                     // per POI: >= 0 a group, < 0 unlabelled; >= n_label: a bad id, entered as unlabelled
+  const unsigned* bits; long long ldw; int n_pred;            // pass bitmaps, or null (one row: every POI passes)
+  int *hist, *unl;                                            // workspace: (rows, n_label) passing POIs per label, (rows) unlabelled ones; unl = hist + rows * n_label
+  int* count; int* fill;                                      // (n_label) POIs per label or null; (rows, CAPPED_FILL_LD)
+  int* bad;                                                   // device counter: POIs whose label is >= n_label (poi_ctx_take_bad_ids)
+};
+struct CappedArgs {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim, k;
+  const float *wd, *sts; const double *coords, *cphi, *thr; const int* last_poi; int n_dist; float bin_scale;      // distance term, or wd null; last_poi = the anchor (null: none)
+  const int *ex_off, *ex;                                     // per-row exclusion lists (ascending ids), or both null
+  const int* labels; int per; const int* fill;                // labels (n_item); the cap; fill table (n_pred or 1, CAPPED_FILL_LD) or null
+  const unsigned* bits; long long ldw; int n_pred; const int* pred;             // pass bitmaps or null (then n_pred = 1); per-row predicate (null: predicate 0)
+  int n_split;                                                // slices (1 in the block regime)
+  float* part_s; int *part_i, *part_cnt;                      // split regime: (n, n_split, CAPPED_K_MAX) partial lists, (n, n_split) counts
+  int* idx_out; float* score_out; int* label_out; int* count_out;               // (n, k); score_out / label_out / count_out may be null
+  int* bad;                                                   // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+struct CappedScoresArgs {
+  const float* scores; long long ld; int n, n_item, k;        // (n, ld) float32 score rows, the first n_item of each row are read
+  const int *ex_off, *ex;
+  const int* labels; int per; const int* fill;
+  const unsigned* bits; long long ldw; int n_pred; const int* pred;
+  int* idx_out; float* score_out; int* label_out; int* count_out;
+  int* bad;
+};
+hipError_t launch_labels_build(const LabelsBuildArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_capped_walk(const CappedArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_capped_scores(const CappedScoresArgs& A, hipStream_t st, Timing* tm);
+
 // Fold-in of new users for the factorisation family (foldin.hip)
 #define FOLDIN_USERS_PER_WAVE 4             // one 16-lane DPP row per user
 struct FoldinArgs {

@@ -997,3 +997,27 @@ def pack_pass_bits(masks, ldw=None):
     b = np.zeros((P, ldw * 32), np.uint8)
     b[:, :N] = m != 0
     return np.ascontiguousarray(np.packbits(b, axis=1, bitorder="little")).view("<u4").reshape(P, ldw)
+
+
+def grid_labels(coords, cell_km):
+    """Grid cells as labels for the capped top-K (models.poi_labels): coords (n_item, 2) lat, lon in degrees -> (labels (n_item) int32,
+    n_label, centres (n_label, 2) float64).  Cells are equal-angle: cell_km kilometres of latitude (EARTH_D pi / 360 km per degree) by
+    the same length of longitude at the table's MEAN latitude (the step is divided by its cosine), indexed by floor(lat / step) and
+    floor(lon / step) - a cell never straddles the equator or the 0 degree meridian.  The occupied cells are numbered 0 .. n_label - 1 in
+    the order of their first POI by ascending id; centres holds every cell's mid point.  Host numpy."""
+    xy = np.asarray(coords.cpu().numpy() if hasattr(coords, "cpu") else coords, np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 2 or len(xy) == 0:
+        raise ValueError("coords must be (n_item >= 1, 2) lat, lon (got %s)" % (xy.shape,))
+    if not float(cell_km) > 0.0:
+        raise ValueError("cell_km must be > 0 (got %r)" % (cell_km,))
+    km_per_deg = EARTH_D * np.pi / 360.0
+    dlat = float(cell_km) / km_per_deg
+    dlon = dlat / max(np.cos(xy[:, 0].mean() * DEG), 1e-6)
+    cell = np.stack([np.floor(xy[:, 0] / dlat), np.floor(xy[:, 1] / dlon)], axis=1).astype(np.int64)
+    _, first, inv = np.unique(cell, axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")                   # unique() sorts by cell: renumber by first appearance
+    rank = np.empty(len(order), np.int64)
+    rank[order] = np.arange(len(order))
+    labels = rank[np.asarray(inv).reshape(-1)].astype(np.int32)
+    centres = (cell[first[order]] + 0.5) * np.array([dlat, dlon])
+    return labels, int(len(order)), centres

@@ -347,3 +347,23 @@ def catalogue_coverage(idx, n_item):
     idx = np.asarray(idx.cpu().numpy() if hasattr(idx, "cpu") else idx, np.int64).reshape(-1)
     idx = idx[(idx >= 0) & (idx < n_item)]
     return float(np.unique(idx).size) / float(n_item)
+
+
+def label_spread(idx, labels):
+    """What a cap did to recommendation lists: idx (n, k) POI ids with -1 for an empty place (ignored), labels (n_item) ints (< 0:
+    unlabelled, every such POI a group of its own) -> (distinct (n) int64: the number of distinct labels on each list; share (n)
+    float64: the largest fraction of a list that one label holds, NaN for an empty list).  A per = 1 list has share 1 / its length.
+    With intra_list_distance_km and catalogue_coverage, the figures of the re-ranked and the capped lists."""
+    idx = np.asarray(idx.cpu().numpy() if hasattr(idx, "cpu") else idx, np.int64)
+    lab = np.asarray(labels.cpu().numpy() if hasattr(labels, "cpu") else labels, np.int64)
+    idx = idx.reshape(len(idx), -1)
+    distinct, share = np.zeros(len(idx), np.int64), np.full(len(idx), np.nan)
+    for r, row in enumerate(idx):
+        ids = row[row >= 0]
+        if not ids.size:
+            continue
+        l = lab[ids]
+        groups = np.where(l >= 0, l, -1 - ids)                  # an unlabelled POI: a group of its own
+        _, cnt = np.unique(groups, return_counts=True)
+        distinct[r], share[r] = cnt.size, cnt.max() / ids.size
+    return distinct, share

@@ -90,6 +90,25 @@ class PoiFilter:
         return cls(model, bits, (m != 0).sum(axis=1))
 
 
+class PoiLabels:
+    """A labelling of a model's POIs for the capped top-K (include/poi_hip.h, poi_labels_build): `labels` (n_item) int32 on the device
+    (>= 0: the POI's group; < 0: unlabelled, a group of its own that is never capped), `fill` (P, 33) int32 on the device - the longest
+    list predicate q of `filt` (one row without a filter) can give under a cap of m, the gate of compute_sub_topk_capped - and
+    `counts` (n_label) on the host, the POIs of every label.  Built by model.poi_labels(labels) or from_categories(model)."""
+
+    def __init__(self, model, labels, n_label, fill, counts, filt=None):
+        self.n_item, self.labels, self.n_label, self.fill, self.filt = model.n_item, labels, int(n_label), fill, filt
+        self.counts = np.asarray(counts, np.int64)
+
+    @classmethod
+    def from_categories(cls, model, filt=None):
+        """The categories of model.set_attributes as the labels (n_label = n_cat)."""
+        cat, _, n_cat = model.__dict__.get("_attr", (None, None, 1))
+        if cat is None:
+            raise _lib.PoiError("the model holds no categories: call set_attributes(categories=...) first")
+        return model.poi_labels(cat, n_cat, filt)
+
+
 class _Base:
     def _setup(self, device, alpha_lambda):
         if not torch.cuda.is_available():
@@ -950,6 +969,135 @@ class _Base:
         ex = self._near_exclusion(exclude, n, anc, ids, lo)
         return self._filtered_launch(users.contiguous(), self._near_items(), anc.contiguous(), self._near_radius(within_km), ex, self._near_term(ids, lo),
                                      filt, pred, hint, k, pathc, return_scores, return_counts, sync)
+
+
+    # ---- capped recommendation (poi_labels_build / poi_score_topk_capped / poi_topk_capped_scores): top-K with at most `per` POIs per label
+    CAPPED_K_MAX = 32
+    CAPPED_PER_MAX = 32
+
+    def poi_labels(self, labels, n_label=None, filt=None):
+        """labels: (n_item) ints, numpy or torch - >= 0 the POI's group (a category, a chain, a grid cell of data.grid_labels), < 0
+        unlabelled -> a PoiLabels.  n_label: labels lie below it (default: the largest label + 1); 1 <= n_label <= n_item.  filt: the
+        PoiFilter the capped calls will use, so that the gate knows how long each predicate's lists can get.  One launch and one
+        synchronisation (the per-label counts come to the host): a set-up step, like poi_filter.  Labels that arrive as a DEVICE
+        tensor without n_label cost a second one, for their maximum; host labels give it on the host.  A label >= n_label raises
+        IndexError."""
+        host = None if isinstance(labels, torch.Tensor) else np.ascontiguousarray(np.asarray(labels).astype(np.int64))
+        lab = labels if host is None else torch.as_tensor(host)
+        if tuple(lab.shape) != (self.n_item,):
+            raise ValueError("labels must hold one id per POI (%s vs n_item = %d)" % (tuple(lab.shape), self.n_item))
+        if n_label is None:
+            n_label = max(int(lab.max().item() if host is None else host.max()) + 1, 1)
+        n_label = int(n_label)
+        if not 1 <= n_label <= self.n_item:
+            raise ValueError("n_label must lie in [1, n_item = %d] (got %d)" % (self.n_item, n_label))
+        if filt is not None and (not isinstance(filt, PoiFilter) or filt.n_item != self.n_item or filt.bits.device != self.device):
+            raise ValueError("filt must be a PoiFilter built for this model (model.poi_filter / PoiFilter.from_masks)")
+        lab = lab.to(device=self.device, dtype=torch.int32).contiguous()
+        rows = filt.n_pred if filt is not None else 1
+        fill = torch.empty((rows, self.CAPPED_PER_MAX + 1), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(n_label, dtype=torch.int32, device=self.device)
+        self.ctx.check(self.lib.poi_labels_build(self.ctx.handle, _ptr(lab), self.n_item, n_label, _ptr(filt.bits) if filt is not None else None,
+                                                 filt.ldw if filt is not None else 0, filt.n_pred if filt is not None else 0, _ptr(cnt), _ptr(fill),
+                                                 self._stream()))
+        counts = cnt.cpu().numpy()
+        bad = self.ctx.take_bad_ids(self._stream().value)
+        if bad:
+            raise IndexError("%d POI(s) with a label outside [.., %d): they would be ranked as unlabelled" % (bad, n_label))
+        return PoiLabels(self, lab, n_label, fill, counts, filt)
+
+    def _capped_args(self, k, labels, per, filt, which, n):
+        """(k, per, PoiLabels, per-row predicate tensor or None, fill tensor or None) of a capped call, host arguments checked."""
+        k, per = int(k), int(per)
+        if not 1 <= k <= self.CAPPED_K_MAX:
+            raise ValueError("capped recommendation supports 1 <= k <= %d (got %d)" % (self.CAPPED_K_MAX, k))
+        if not 1 <= per <= self.CAPPED_PER_MAX:
+            raise ValueError("capped recommendation supports 1 <= per <= %d (got %d)" % (self.CAPPED_PER_MAX, per))
+        if filt is not None and (not isinstance(filt, PoiFilter) or filt.n_item != self.n_item or filt.bits.device != self.device):
+            raise ValueError("filt must be a PoiFilter built for this model (model.poi_filter / PoiFilter.from_masks)")
+        if not isinstance(labels, PoiLabels):
+            labels = self.poi_labels(labels, filt=filt)
+        if labels.n_item != self.n_item or labels.labels.device != self.device:
+            raise ValueError("labels must be a PoiLabels built for this model (model.poi_labels / PoiLabels.from_categories)")
+        pred = None
+        if filt is None:
+            if which is not None:
+                raise ValueError("which indexes the predicates of filt: it needs one")
+        elif isinstance(which, torch.Tensor):      # a device tensor is checked by the kernel
+            pred = which.to(self.device, torch.int32).contiguous().reshape(-1)
+        elif which is not None:
+            w = np.atleast_1d(np.asarray(which)).astype(np.int64)
+            if w.size and (w.min() < 0 or w.max() >= filt.n_pred):
+                raise IndexError("which must index the filter's %d predicate(s) (found %d..%d)" % (filt.n_pred, int(w.min()), int(w.max())))
+            pred = torch.as_tensor(w.astype(np.int32)).to(self.device)
+        if pred is not None and pred.numel() != n:
+            raise ValueError("which must hold one predicate index per row (%d vs %d)" % (pred.numel(), n))
+        # the fill table gates by predicate row: it serves the filter it was built with (without one: the call without a filter)
+        fill = labels.fill if labels.filt is filt else None
+        return k, per, labels, pred, fill
+
+    def _capped_buffers(self, n, k, return_scores, return_labels, return_counts):
+        idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
+        return idx, sc, (torch.empty((n, k), dtype=torch.int32, device=self.device) if return_labels else None), cnt
+
+    def _capped_out(self, idx, sc, lab, cnt, return_scores, return_labels, return_counts, sync):
+        return self._serve_out(idx, ((sc, return_scores), (lab, return_labels), (cnt, return_counts)), sync,
+                               "row(s) with a predicate index, an anchor or an exclusion id out of range: their lists are all -1")
+
+    def _capped_launch(self, users, items, term, ex, labels, per, fill, filt, pred, k, return_scores, return_labels, return_counts, sync):
+        """One poi_score_topk_capped call -> idx[, scores][, labels][, counts] (device tensors).  term: (wd, sts rows, last POI rows) or
+        None, as _candidates_launch takes it."""
+        n = users.shape[0]
+        idx, sc, lab, cnt = self._capped_buffers(n, k, return_scores, return_labels, return_counts)
+        if n:
+            bits, ldw, n_pred = (_ptr(filt.bits), filt.ldw, filt.n_pred) if filt is not None else (None, 0, 0)
+            self.ctx.check(self.lib.poi_score_topk_capped(self.ctx.handle, *self._tile_operands(users, items, self.kdim, term), _ptr(labels.labels), per,
+                                                          _ptr(fill), bits, ldw, n_pred, _ptr(pred), _ptr(ex[0]), _ptr(ex[1]), k, _ptr(idx), _ptr(sc),
+                                                          _ptr(lab), _ptr(cnt), self._stream()))
+        return self._capped_out(idx, sc, lab, cnt, return_scores, return_labels, return_counts, sync and n > 0)
+
+    def _capped_from_scores(self, score_rows, n, ex, labels, per, fill, filt, pred, k, return_scores, return_labels, return_counts, sync):
+        """Explicit score rows, a bounded number of rows at a time, + poi_topk_capped_scores.  score_rows(o, c) -> (c, n_item) float32
+        scores of rows o .. o + c - 1."""
+        N = self.n_item
+        idx, sc, lab, cnt = self._capped_buffers(n, k, return_scores, return_labels, return_counts)
+        at = lambda t, o, w: ctypes.c_void_p(t.data_ptr() + 4 * o * w) if t is not None else None
+        bits, ldw, n_pred = (_ptr(filt.bits), filt.ldw, filt.n_pred) if filt is not None else (None, 0, 0)
+        for o, c in self._row_chunks(n):
+            full = score_rows(o, c).contiguous()
+            self.ctx.check(self.lib.poi_topk_capped_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(labels.labels), per, _ptr(fill), bits, ldw, n_pred,
+                                                           at(pred, o, 1), at(ex[0], o, 1), _ptr(ex[1]), k, at(idx, o, k), at(sc, o, k), at(lab, o, k),
+                                                           at(cnt, o, 1), self._stream()))
+        return self._capped_out(idx, sc, lab, cnt, return_scores, return_labels, return_counts, sync and n > 0)
+
+    def compute_sub_topk_capped(self, start_end, k, labels, per=1, filt=None, which=None, exclude=None, return_scores=False, return_labels=False,
+                                return_counts=False, sync=True):
+        """CAPPED top-K (include/poi_hip.h, poi_score_topk_capped): compute_sub_topk with at most `per` POIs of one label - "the best 20
+        places, but no more than 2 of a category"; with per = 1, the best POI of each of the k best labels.  labels: a PoiLabels
+        (model.poi_labels / PoiLabels.from_categories; a plain array is turned into one, at the price of a synchronisation).
+        Unlabelled POIs (label < 0) are never capped.  filt / which: restrict the candidates to a predicate per row as
+        compute_sub_topk_filtered does; build the PoiLabels with the same filt, or the gate falls back to k (correct, slower where
+        lists cannot fill).  exclude: None, "train" or CSR lists (off, ids) as compute_sub_candidates.  Returns (n, k) int32 ids
+        (k <= 32, per <= 32) by descending score under the model's own score (the spatial model's distance term at the user's last
+        POI), ties by ascending id, -1 where the cap or the candidates leave fewer; with return_scores the scores (-inf on the fill),
+        with return_labels the entries' labels (-1 on the fill), with return_counts the candidates of every row, not reduced by the
+        cap.  CA-RNN, PRME, POI2Vec and GeoIE under rule="geo" go through their own score rows, a bounded number at a time, and
+        poi_topk_capped_scores.  Host arguments are checked before the launch (ValueError / IndexError); device tensors by the
+        kernel: an offending row comes out all -1 and - with sync - raises IndexError."""
+        if not self._rank_fused:
+            a = self._id_list(start_end)
+            n = len(a)
+            k, per, labels, pred, fill = self._capped_args(k, labels, per, filt, which, n)
+            ids, lo = self._ids(a)
+            ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+            return self._capped_from_scores(self._own_score_rows(a), n, ex, labels, per, fill, filt, pred, k, return_scores, return_labels,
+                                            return_counts, sync)
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        k, per, labels, pred, fill = self._capped_args(k, labels, per, filt, which, n)
+        ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+        return self._capped_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), ex, labels, per, fill, filt, pred, k, return_scores,
+                                   return_labels, return_counts, sync)
 
 
     # ---- group recommendation (poi_group_topk / poi_group_topk_scores): the top-K of an aggregate of the members' scores ---------------
@@ -2492,6 +2640,19 @@ class Session:
         return m._filtered_launch(users, m.trained_items.t, anc, m._near_radius(within_km), ex, term, filt, pred, hint, k, pathc, return_scores,
                                   return_counts, sync)
 
+    def recommend_capped(self, slots, k, labels, per=1, filt=None, which=None, exclude=None, return_scores=False, return_labels=False,
+                         return_counts=False, sync=True):
+        """model.compute_sub_topk_capped over the slots' CURRENT states (h, sts, last_poi, as `candidates` assembles them): the top-k
+        (k <= 32) with at most `per` POIs of one label of `labels` (a PoiLabels).  exclude: None, "last" or CSR lists (off, ids).  A
+        slot without a check-in has no distance term."""
+        m = self.m
+        ids = self._slot_tensor(slots)
+        n = ids.numel()
+        k, per, labels, pred, fill = m._capped_args(k, labels, per, filt, which, n)
+        users, lpr, term = self._tile_rows(ids)
+        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
+        return m._capped_launch(users, m.trained_items.t, term, ex, labels, per, fill, filt, pred, k, return_scores, return_labels, return_counts, sync)
+
     def rank_of(self, slots, pois, exclude=None, return_scores=False, return_counts=False, sync=True):
         """Exact 0-based rank of pois[i] (one POI per slot, or (n, len_t <= 8)) among all POIs under the slot's CURRENT state - the score
         rule of `recommend` (h . trained_items[:-1]^T, plus the spatial distance term at last_poi; none before the first check-in):
@@ -2819,6 +2980,19 @@ class CellSession(Session):
         n, score_rows, has, ex = self._carnn_rows(ids, exclude)
         return self._carnn_out(m._filtered_from_scores(score_rows, n, ex, filt, pred, k, return_scores, return_counts, sync), has, return_scores,
                                return_counts)
+
+    def recommend_capped(self, slots, k, labels, per=1, filt=None, which=None, exclude=None, return_scores=False, return_labels=False,
+                         return_counts=False, sync=True):
+        """Lstm / Rnn: `Session.recommend_capped`'s plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi +
+        poi_topk_capped_scores; a slot without a check-in gives -1 ids (count 0)."""
+        if not self.carnn:
+            return super().recommend_capped(slots, k, labels, per, filt, which, exclude, return_scores, return_labels, return_counts, sync)
+        m = self.m
+        ids = self._slot_tensor(slots)
+        k, per, labels, pred, fill = m._capped_args(k, labels, per, filt, which, ids.numel())
+        n, score_rows, has, ex = self._carnn_rows(ids, exclude)
+        out = m._capped_from_scores(score_rows, n, ex, labels, per, fill, filt, pred, k, return_scores, return_labels, return_counts, sync)
+        return self._carnn_out(out, has, return_scores, return_counts)
 
     def recommend_diverse(self, slots, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
                           return_objective=False, return_pool=False, return_counts=False, sync=True):
