@@ -176,3 +176,199 @@ def test_predict_runs_every_position():
     for t in range(2):
         hh, cc, _ = C.cell_step(P, "lstm", P["lt"][pm[1, t]], hh, cc)
     assert np.array_equal(h[1], hh) and h.shape == (2, 4)
+
+
+# ---- the batched oracle and the launch-size cases (tests/cells_cases.py, tests/test_gpu_cells_launch_sizes.py) -------------------------
+from tests import cells_cases as K                                                 # noqa: E402
+from tests.gpu_util import delta_excess                                            # noqa: E402
+
+RAGGED = [("ragged", [9, 1, 2, 5, 7, 3, 2, 9], 9), ("short_only", [1, 2, 1, 2], 5), ("one_user_len1", [1], 4), ("padded_beyond_longest", [6, 2, 4], 8)]
+
+
+def _rel(a, b):
+    return float(np.max(np.abs(np.asarray(a) - np.asarray(b))) / max(np.max(np.abs(b)), 1e-300))
+
+
+@pytest.mark.parametrize("cell", C.CELLS)
+@pytest.mark.parametrize("dim", [4, 20])
+@pytest.mark.parametrize("name,lens,len_max", RAGGED, ids=[c[0] for c in RAGGED])
+def test_batched_oracle_equals_the_loop(cell, dim, name, lens, len_max):
+    """Float64 against float64, the users' terms added in another order: the new tables, what the step changed and the loss agree to
+    1e-12 relative (measured: below 1e-15 on the tables, at most 8.2e-14 on the updates, which are a hundredth of the tables)."""
+    n_item = 17
+    P = _params(21, n_item, dim, cell)
+    pm, qm, mm = _batch(6, len(lens), n_item, len_max, lens)
+    ref, ref_loss = C.minibatch_step(P, pm, qm, mm, ALPHA, LAM, cell)
+    got, loss = C.minibatch_step_batched(P, pm, qm, mm, ALPHA, LAM, cell)
+    assert abs(loss - ref_loss) <= 1e-12 * abs(ref_loss), (loss, ref_loss)
+    worst = 0.0
+    for k in ("lt", "ui", "wh", "bi"):
+        assert got[k].shape == ref[k].shape
+        e_w, e_d = _rel(got[k], ref[k]), _rel(got[k] - P[k], ref[k] - P[k])
+        worst = max(worst, e_d)
+        assert e_w <= 1e-12 and e_d <= 1e-12, (k, e_w, e_d)
+    print("batched vs loop %s dim %d %s: worst update error %.2e" % (cell, dim, name, worst))
+    assert np.array_equal(got["lt"] != P["lt"], ref["lt"] != P["lt"])            # the same rows move
+    h_ref, h_got = C.predict(P, pm, mm, cell), C.predict_batched(P, pm, mm, cell)
+    assert h_got.shape == h_ref.shape and _rel(h_got, h_ref) <= 1e-12
+
+
+def test_sort_passes_mirror_and_case_preconditions():
+    assert [K.sort_passes(v) for v in K.A_N_ITEM] == list(K.A_PASSES)
+    assert [K.sort_passes(v) for v in (1, 70, 100_000, (1 << 27) - 2, (1 << 27) - 1)] == [1, 1, 2, 3, 4]
+    assert [K.chunk_rows(n, m) for n, m in ((1, 1), (64, 50), (257, 11), (5300, 50))] == [8, 56, 48, 4144]
+    for n_item in K.A_N_ITEM:
+        rag, full = K.case_a(n_item, False), K.case_a(n_item, True)
+        u = np.arange(40)
+        assert K.pad_multiplicity(rag, u) > 0 and K.pad_multiplicity(full, u) == 0
+        for c in (rag, full):
+            pm, mm, qm = c["train"]
+            assert pm[mm > 0].min() == 0 and qm[mm > 0].max() >= n_item - 1 and max(pm.max(), qm.max()) <= n_item
+        assert (full["train"][0] == n_item).sum() == 0 and (full["train"][2] == n_item).sum() == 0
+        assert (rag["train"][2][rag["train"][1] > 0] == n_item).sum() == 1      # the pad row as a real negative
+    b = K.case_b()
+    for n in K.B_SIZES:
+        lens = b["lens"][K.b_users(b, n)]
+        assert lens[255 if n > 255 else 0] == (1 if n > 255 else lens[0]) and (n <= 256 or lens[256] == 1)
+    assert K.position_rows(b, K.b_users(b, 257)) % K.chunk_rows(257, K.max_len(b)) != 0
+    assert K.pad_multiplicity(b, K.b_users(b, 769)) < 3000
+    c1 = K.case_c1()
+    assert K.sort_entries(c1, np.arange(513)) > K.COMMIT_GRID_MAX
+    c2 = K.case_c2()
+    assert K.max_len(c2) == 50 and K.position_rows(c2, np.arange(64)) < 2 * K.chunk_rows(64, 50)
+    lens = np.full(K.D_N_USER, 50); lens[-1] = 49                               # case D without building its tables
+    assert lens.sum() > 262144 and -(-(2 * lens.sum() + 1) // 64) > K.WINDOW_GRID_MAX and K.sort_passes(K.D_N_ITEM) == 3
+    assert -(-(2 * (lens.sum() - 100 * 50) + 1) // 64) <= K.WINDOW_GRID_MAX     # 5200 users stay under the cap
+
+
+def _verdict(got_lt, exp_lt, old_lt, touched):
+    """What tests/test_gpu_cells_launch_sizes.py asserts on lt: (delta excess, rows the oracle leaves alone that moved)."""
+    return delta_excess(got_lt, exp_lt, old_lt)[0], int((got_lt[~touched] != old_lt[~touched]).any(axis=1).sum())
+
+
+def _flagged(v):
+    return v[0] > 1.0 or v[1] > 0
+
+
+@pytest.fixture(scope="module", params=C.CELLS)
+def replica(request):
+    """Case D reduced to 530 users (three plan blocks, three sort passes, the same 50-position users and 262 143 POIs) and its gradients."""
+    cell = request.param
+    case = K.case_d(530)
+    P = K.params(90, K.D_N_ITEM, 8, cell)
+    pm, qm, mm = K.tables(case, np.arange(530))
+    losses, G, rows, vecs, ent = C.batch_grads(P, pm, qm, mm, cell)
+    mult = C.multiplicities(pm, qm, P["lt"].shape[0])
+    exp = C.apply_grads(P, G, rows, vecs, mult, ALPHA, LAM)["lt"]
+    return dict(P=P, G=G, rows=rows, vecs=vecs, ent=ent, mult=mult, exp=exp, touched=mult > 0, pm=pm, qm=qm, case=case)
+
+
+def _corrupt(R, rows=None, vecs=None, mult=None):
+    lt = C.apply_grads(R["P"], R["G"], R["rows"] if rows is None else rows, R["vecs"] if vecs is None else vecs,
+                       R["mult"] if mult is None else mult, ALPHA, LAM)["lt"]
+    return _verdict(lt, R["exp"], R["P"]["lt"], R["touched"])
+
+
+def _single_touch_entries(R, side):
+    """Sorted entries (of the positives: side 0, the negatives: side 1) that are the only touch of their row, weakest gradient first."""
+    keep = np.flatnonzero((R["mult"][R["rows"]] == 1) & (R["ent"] % 2 == side))
+    mass = np.zeros(int(R["ent"].max()) + 1)
+    np.maximum.at(mass, R["ent"][keep], np.abs(R["vecs"][keep]).max(axis=1))
+    ents = np.unique(R["ent"][keep])
+    return ents[np.argsort(mass[ents], kind="stable")]
+
+
+def test_replica_is_sparse_and_clean(replica):
+    R = replica
+    assert (R["mult"][R["touched"]] == 1).mean() > 0.8                          # most touched rows hold one sorted entry
+    assert R["mult"][R["case"]["hot"]].min() > 4 * K.WINDOW                    # the planted hot POIs cross several windows each
+    assert R["mult"][0] >= 1 and R["mult"][K.D_N_ITEM - 1] >= 1 and R["mult"][K.D_N_ITEM] == 3      # 2 analytic + the planted negative
+    assert _corrupt(R) == (0.0, 0)
+
+
+@pytest.mark.parametrize("pick", ["weakest", "median", "strongest"])
+def test_a_dropped_single_touch_entry_is_flagged(replica, pick):
+    """(a) one sorted entry lost from a row it alone touches: its gradient and its unit of L2 multiplicity are gone, the row stays put.
+    Also for the weakest such entry, a negative at t = 0 whose gradient is exactly zero (h_{-1} = 0): its L2 term alone is 40x over."""
+    R = replica
+    ents = _single_touch_entries(R, 1)
+    e = ents[{"weakest": 0, "median": len(ents) // 2, "strongest": -1}[pick]]
+    keep = R["ent"] != e
+    mult = R["mult"].copy()
+    mult[R["rows"][~keep][0]] -= 1
+    v = _corrupt(R, R["rows"][keep], R["vecs"][keep], mult)
+    print("(a) %s entry dropped: excess %.1f" % (pick, v[0]))
+    assert v[0] > 1.0
+
+
+def test_an_entry_credited_to_the_next_row_is_flagged(replica):
+    """(b) a positive's entry (gam h and ui^T da) lands on row r + 1: row r loses its update, row r + 1 - untouched in the oracle - moves."""
+    R = replica
+    for e in _single_touch_entries(R, 0):
+        sel = R["ent"] == e
+        r = int(R["rows"][sel][0])
+        if r + 1 < K.D_N_ITEM and R["mult"][r + 1] == 0:
+            break
+    rows, mult = R["rows"].copy(), R["mult"].copy()
+    rows[sel] += 1
+    mult[r] -= 1; mult[r + 1] += 1
+    v = _corrupt(R, rows=rows, mult=mult)
+    print("(b) entry on row r + 1: excess %.1f, untouched rows moved %d" % v)
+    assert v[0] > 1.0 and v[1] == 1
+
+
+def test_a_user_of_the_second_plan_block_contributing_nothing_is_flagged(replica):
+    """(d) user 300 of the launch (second block of 256 of cell_plan_kernel's scan) leaves no row entry."""
+    R = replica
+    user = R["ent"] // (2 * R["case"]["len_max"])
+    keep = user != 300
+    mult = R["mult"] - np.bincount(np.concatenate((R["pm"][300], R["qm"][300])), minlength=len(R["mult"]))
+    v = _corrupt(R, R["rows"][keep], R["vecs"][keep], mult)
+    print("(d) user 300 silent: excess %.1f" % v[0])
+    assert v[0] > 1.0
+
+
+def _pad_off_by_one(case, idxs, cell, seed):
+    P = K.params(seed, case["n_item"], case["dim"], cell)
+    pm, qm, mm = K.tables(case, idxs)
+    losses, G, rows, vecs, _ = C.batch_grads(P, pm, qm, mm, cell)
+    mult = C.multiplicities(pm, qm, P["lt"].shape[0])
+    exp = C.apply_grads(P, G, rows, vecs, mult, ALPHA, LAM)["lt"]
+    out = []
+    for d in (1, -1):
+        bad = mult.copy()
+        bad[case["n_item"]] += d
+        if bad[case["n_item"]] >= 0:
+            out.append(_verdict(C.apply_grads(P, G, rows, vecs, bad, ALPHA, LAM)["lt"], exp, P["lt"], mult > 0))
+    return mult[case["n_item"]], out
+
+
+def _assert_flagged(seen):
+    for what, m, v in seen:
+        print("(c) %s, pad multiplicity %d off by one: excess %.2f, untouched rows moved %d" % (what, m, v[0], v[1]))
+        assert m < 1e4 and _flagged(v), (what, m, v)
+
+
+@pytest.mark.parametrize("cell", C.CELLS)
+def test_pad_multiplicity_off_by_one_is_flagged(cell):
+    """(c) on case A (ragged: the delta bar; full length: the pad row is untouched and must not move) and on case B's largest launch,
+    where the multiplicity is largest and the bar weakest: 1e-4 of an update of alpha lambda mult |row| against a shift of
+    alpha lambda |row| - the excess falls as 1e4 / mult, so the cases keep mult well below 1e4."""
+    seen = []
+    for n_item in (K.A_N_ITEM[0], K.A_N_ITEM[-1]):
+        for full in (False, True):
+            m, vs = _pad_off_by_one(K.case_a(n_item, full), np.arange(40), cell, 1)
+            assert (m == 0) == full
+            seen += [("A %d %s" % (n_item, "full" if full else "ragged"), m, v) for v in vs]
+    b = K.case_b()
+    m, vs = _pad_off_by_one(b, K.b_users(b, 769), cell, 2)
+    _assert_flagged(seen + [("B 769", m, v) for v in vs])
+
+
+def test_pad_multiplicity_off_by_one_is_flagged_on_the_replica(replica):
+    R, seen = replica, []
+    for d in (1, -1):
+        bad = R["mult"].copy()
+        bad[K.D_N_ITEM] += d
+        seen.append(("D replica %+d" % d, R["mult"][K.D_N_ITEM], _corrupt(R, mult=bad)))
+    _assert_flagged(seen)
