@@ -102,6 +102,8 @@ extern "C" {
 /* additive to 9: capped recommendation - new entry points poi_labels_build, poi_score_topk_capped and poi_topk_capped_scores, options
  * "capped_split_max" / "capped_grid" / "capped_hist_kb", plan keys "capped_splits" / "capped_split_max", timing names "labels_build" / "score_topk_capped"
  * (with "capped_walk" / "capped_merge" inside it) / "topk_capped_scores" (existing entries unchanged). */
+/* additive to 9: re-ranking - new entry points poi_score_lists, poi_rerank_lists and poi_rerank (and poi_score_lists_chunk), plan key
+ * "lists_path", timing names "score_lists" / "rerank_lists" / "rerank"; no new option (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -203,7 +205,8 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * "audience_split_max" - written by poi_score_audience / poi_audience_rows.
  * Additive to 9: "similar_path" (0 one workgroup per query block, 1 slices, 2 score rows + selection), "similar_splits" (slices of the
  * walk, 0 with one workgroup per query block), "similar_split_max" - written by poi_similar_topk / poi_similar_rows.
- * Additive to 9: "capped_splits" (slices, 0 outside the split regime), "capped_split_max" - written by poi_score_topk_capped. */
+ * Additive to 9: "capped_splits" (slices, 0 outside the split regime), "capped_split_max" - written by poi_score_topk_capped.
+ * Additive to 9: "lists_path" (0 ragged lists, 1 one shared list) - written by poi_score_lists / poi_rerank. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -1205,6 +1208,60 @@ int poi_score_candidates(poi_ctx* ctx, const float* users, const float* items, i
                          int32_t n_dist, double dd,
                          int32_t k, const int32_t* ex_off, const int32_t* ex,
                          int32_t* idx_out, float* score_out, int32_t* count_out, void* stream);
+
+/* ---- re-ranking (additive to 9): score explicit candidate lists, blend with a prior, exact top-K ---------------------------------------------
+ * The second stage of a two-stage recommender: a cheap model (or a campaign, a geofence, "open now") has produced candidate POIs per
+ * row - e.g. the idx_out of poi_score_candidates - and THIS model scores exactly those and returns them in order.  No (n, n_item) matrix.
+ *   lists         ragged (cand_off non-NULL): row r owns cand[cand_off[r] .. cand_off[r + 1]), cand holds n_cand ids in all; scores
+ *                 and priors are flat and parallel to cand.  Shared (cand_off NULL): ONE list cand[0 .. n_cand) for every row; scores
+ *                 and priors are (n, n_cand) row-major.
+ *   ids           an id in [0, n_item) is scored; duplicates are allowed and get identical bits.  A NEGATIVE id is padding: its score
+ *                 is -inf and it is never selected - the (n, k) idx_out of poi_score_candidates with its -1 fill is a ragged list with
+ *                 cand_off[r] = r k.
+ *   score         s(r, j) of poi_score_rows / poi_score_rank, bit for bit: users[r] . items[j] from the same product routine and k
+ *                 order, with wd non-NULL plus wd * sts[r][bin(last_poi[r], j)] for rows with last_poi[r] >= 0.  users .. dd are
+ *                 poi_score_rank's arguments (items float32 or a registered half table; dim a multiple of 4, <= 256).
+ *   bad rows      a ragged row whose offsets are negative, descending or end beyond n_cand, or that holds an id >= n_item, is
+ *                 rejected: the entries it owns (where its offsets say so at all) are -inf, it is counted once
+ *                 (poi_ctx_take_bad_ids), and nothing outside cand[0 .. n_cand) or the tables is read.  A shared list that holds an
+ *                 id >= n_item rejects every row of the call, counted once.  Entries of cand that no accepted row owns get -inf.
+ *
+ * poi_score_lists writes the scores: score_out (n_cand) ragged, (n, n_cand) shared.  Ragged lists go through one workgroup per (row,
+ * chunk of poi_score_lists_chunk() entries) - the row's fragment against 32 gathered item rows per product, one item row of
+ * 4 dim bytes per entry; a shared list through a real 32 x 32 tile product, each item row fetched once per 32-row tile.  An output
+ * element depends on its own (row, id) only: every grid gives the same bits.  poi_ctx_last_plan: "lists_path" (0 ragged, 1 shared).
+ * Timing name: "score_lists".  n = 0 or n_cand = 0 is a no-op.
+ *
+ * poi_rerank_lists orders every list under EXPLICIT scores.  The key of entry i of row r is
+ *   t = score[i]                                                          prior == NULL (the weights are ignored)
+ *   t = (float)(w_score * (double)score[i] + w_prior * (double)prior[i])  otherwise; both products and the sum are rounded to double
+ *                                                                          one by one (no contraction), the result once to float
+ * An entry is selectable unless its id is negative or t is NaN or -inf (+inf is selectable; -0.0 and +0.0 are ONE key, written as +0.0:
+ * the rules of poi_score_candidates).  Total order: higher t, then the lower id, then the lower position in the list; duplicates are
+ * kept.  Outputs for 1 <= k <= 4096, the best K' = min(k, selectable) entries sorted best first: idx_out (n, k), -1 beyond K';
+ * score_out (n, k) or NULL: the key t, -inf beyond K'; pos_out (n, k) or NULL: the entry's position inside its row's list (-1 beyond
+ * K') - what a caller gathers side data with, and how far an entry moved; count_out (n) or NULL: the number of selectable entries, not
+ * clipped to k.  One workgroup per row, a bitonic network over the next power of two in LDS; integer and compare work only: the same
+ * bits for a row alone or in a call of thousands.  A ragged row with malformed offsets or more than 4096 entries is rejected (all
+ * -1 / -inf, count 0, counted once); ids are not checked against a table here.  A shared n_cand > 4096 or k outside [1, 4096] is
+ * POI_ENOTSUP.  Timing name: "rerank_lists".  n = 0 is a no-op.
+ *
+ * poi_rerank runs both with the scores in a context-owned workspace, no host synchronisation in between; its output equals
+ * poi_score_lists + poi_rerank_lists bit for bit, and a row either stage rejects is counted once.  Timing name: "rerank" (around
+ * "score_lists" and "rerank_lists"). */
+int poi_score_lists_chunk(void);      /* entries of a ragged row per workgroup step (a compile-time constant; tests straddle it) */
+int poi_score_lists(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                    const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+                    int32_t n_dist, double dd,
+                    const int32_t* cand_off, const int32_t* cand, int32_t n_cand, float* score_out, void* stream);
+int poi_rerank_lists(poi_ctx* ctx, const int32_t* cand_off, const int32_t* cand, int32_t n, int32_t n_cand,
+                     const float* score, const float* prior, double w_score, double w_prior, int32_t k,
+                     int32_t* idx_out, float* score_out, int32_t* pos_out, int32_t* count_out, void* stream);
+int poi_rerank(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+               const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* last_poi,
+               int32_t n_dist, double dd,
+               const int32_t* cand_off, const int32_t* cand, int32_t n_cand, const float* prior, double w_score, double w_prior, int32_t k,
+               int32_t* idx_out, float* score_out, int32_t* pos_out, int32_t* count_out, void* stream);
 
 /* ---- filtered recommendation (additive to 9): the top-K among the POIs that pass an attribute predicate -----------------------------------
  * "The best restaurants for this user", "the best museums open now", "the best cafes within 2 km": a top-K over the POIs that pass a

@@ -202,6 +202,14 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_score_candidates": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int32, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_score_lists_chunk": (c_int, []),
+    "poi_score_lists": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_int32, c_double, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "poi_rerank_lists": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_double, c_double, c_int32, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "poi_rerank": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_int32, c_double, c_void_p, c_void_p, c_int32, c_void_p, c_double, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p]),
     "poi_filter_build": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
                                  c_int64, c_void_p, c_void_p]),
     "poi_score_topk_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -284,7 +292,7 @@ PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", 
              "diverse_path", "diverse_splits", "diverse_split_max",
              "select_rows_per_chunk", "select_chunks", "select_path", "select_splits", "xfwd_ids_lds",
              "filter_path", "filter_splits", "filter_split_max", "audience_path", "audience_splits", "audience_split_max",
-             "similar_path", "similar_splits", "similar_split_max", "capped_splits", "capped_split_max")
+             "similar_path", "similar_splits", "similar_split_max", "capped_splits", "capped_split_max", "lists_path")
 
 
 class Context:

@@ -845,7 +845,8 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"audience_split_max", &poi_ctx::LastPlan::audience_split_max},
       {"similar_path", &poi_ctx::LastPlan::similar_path}, {"similar_splits", &poi_ctx::LastPlan::similar_splits},
       {"similar_split_max", &poi_ctx::LastPlan::similar_split_max},
-      {"capped_splits", &poi_ctx::LastPlan::capped_splits}, {"capped_split_max", &poi_ctx::LastPlan::capped_split_max}};
+      {"capped_splits", &poi_ctx::LastPlan::capped_splits}, {"capped_split_max", &poi_ctx::LastPlan::capped_split_max},
+      {"lists_path", &poi_ctx::LastPlan::lists_path}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

@@ -732,6 +732,122 @@ int poi_score_candidates(poi_ctx* c, const float* users, const float* items, int
 }
 
 // ---------------------------------------------------------------------------------------------
+// re-ranking (rerank.hip)
+int poi_score_lists_chunk(void) { return RERANK_CHUNK; }
+
+static int lists_check(poi_ctx* c, const char* who, int32_t n, const int32_t* cand, int32_t n_cand) {
+  if (!cand) return fail(c, POI_EINVAL, "%s: NULL cand", who);
+  if (n < 0 || n_cand < 0) return fail(c, POI_EINVAL, "%s: n < 0 or n_cand < 0", who);
+  return POI_OK;
+}
+
+// the scoring launch of a call whose workspace is carved: the grid, the plan record
+static int score_lists_run(poi_ctx* c, const poi::TileOperands& T, const int32_t* cand_off, const int32_t* cand, int32_t n_cand, int* flag, float* out,
+                           hipStream_t st) {
+  poi::ScoreListsArgs A = {};
+  put_operands(A, T);
+  A.cand_off = cand_off; A.cand = cand; A.n_cand = n_cand; A.flag = flag; A.out = out;
+  if (cand_off) {
+    // workgroups per row: 16 per CU over the call, no more than the chunks of the call's entries; a row's further chunks go round
+    const int chunks = (n_cand + RERANK_CHUNK - 1) / RERANK_CHUNK;
+    int want = (c->num_cu * 16 + T.n - 1) / T.n;
+    if (want > chunks) want = chunks;
+    A.n_split = want < 1 ? 1 : want;
+  } else {
+    // list ranges per 32-row tile, one wave each: 8 waves per CU over the call (poi_score_rows' rule), at least one 32-candidate tile each
+    const int n_utile = (T.n + 31) / 32, ntile = (n_cand + 31) / 32;
+    int want = (c->num_cu * 8 + n_utile - 1) / n_utile;
+    if (want > ntile) want = ntile;
+    A.n_split = want < 1 ? 1 : want;
+  }
+  c->plan.valid = 1; c->plan.lists_path = cand_off ? 0 : 1;
+  HIPCHK(c, poi::launch_score_lists(A, st, &c->tm));
+  return POI_OK;
+}
+
+static int rerank_check(poi_ctx* c, const char* who, const int32_t* cand_off, int32_t n_cand, int32_t k, const int32_t* idx_out) {
+  if (!idx_out) return fail(c, POI_EINVAL, "%s: NULL idx_out", who);
+  if (k <= 0 || k > RERANK_LEN_MAX) return fail(c, POI_ENOTSUP, "%s supports 1 <= k <= %d (got %d)", who, RERANK_LEN_MAX, k);
+  if (!cand_off && n_cand > RERANK_LEN_MAX) return fail(c, POI_ENOTSUP, "%s supports a shared list of at most %d entries (got %d)", who, RERANK_LEN_MAX, n_cand);
+  return POI_OK;
+}
+
+static int rerank_run(poi_ctx* c, const int32_t* cand_off, const int32_t* cand, int32_t n, int32_t n_cand, const float* score, const float* prior,
+                      double w_score, double w_prior, const int* flag, int32_t k, int32_t* idx_out, float* score_out, int32_t* pos_out,
+                      int32_t* count_out, int* bad, hipStream_t st) {
+  poi::RerankListsArgs A = {};
+  A.cand_off = cand_off; A.cand = cand; A.n = n; A.n_cand = n_cand; A.score = score; A.prior = prior; A.w_score = w_score; A.w_prior = w_prior;
+  A.flag = flag; A.k = k; A.idx_out = idx_out; A.score_out = score_out; A.pos_out = pos_out; A.count_out = count_out; A.bad = bad;
+  const int longest = n_cand < RERANK_LEN_MAX ? n_cand : RERANK_LEN_MAX;
+  A.p_max = 1;
+  while (A.p_max < longest) A.p_max <<= 1;
+  HIPCHK(c, poi::launch_rerank_lists(A, st, &c->tm));
+  return POI_OK;
+}
+
+int poi_score_lists(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                    const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+                    const int32_t* cand_off, const int32_t* cand, int32_t n_cand, float* score_out, void* stream) {
+  if (!c || !users || !items || !score_out) return fail(c, POI_EINVAL, "poi_score_lists: NULL ctx / users / items / score_out");
+  int rc;
+  if ((rc = lists_check(c, "poi_score_lists", n, cand, n_cand))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  poi::TileOperands T;
+  if ((rc = tile_operands(c, "poi_score_lists", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, nullptr, nullptr, st, &T))) return rc;
+  if (n == 0 || n_cand == 0) return POI_OK;
+  int* flag = nullptr;
+  if ((rc = carve(c, c->rerank_ws, st, [&](Carver& W) { flag = (int*)W.bytes(sizeof(int) * (size_t)(cand_off ? n : 1)); }))) return rc;
+  return score_lists_run(c, T, cand_off, cand, n_cand, flag, score_out, st);
+}
+
+int poi_rerank_lists(poi_ctx* c, const int32_t* cand_off, const int32_t* cand, int32_t n, int32_t n_cand, const float* score, const float* prior,
+                     double w_score, double w_prior, int32_t k, int32_t* idx_out, float* score_out, int32_t* pos_out, int32_t* count_out,
+                     void* stream) {
+  if (!c || !score) return fail(c, POI_EINVAL, "poi_rerank_lists: NULL ctx / score");
+  int rc;
+  if ((rc = lists_check(c, "poi_rerank_lists", n, cand, n_cand))) return rc;
+  if ((rc = rerank_check(c, "poi_rerank_lists", cand_off, n_cand, k, idx_out))) return rc;
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  int* bad;
+  if ((rc = bad_counter(c, st, &bad))) return rc;
+  return rerank_run(c, cand_off, cand, n, n_cand, score, prior, w_score, w_prior, nullptr, k, idx_out, score_out, pos_out, count_out, bad, st);
+}
+
+int poi_rerank(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+               const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,
+               const int32_t* cand_off, const int32_t* cand, int32_t n_cand, const float* prior, double w_score, double w_prior, int32_t k,
+               int32_t* idx_out, float* score_out, int32_t* pos_out, int32_t* count_out, void* stream) {
+  if (!c || !users || !items) return fail(c, POI_EINVAL, "poi_rerank: NULL ctx / users / items");
+  int rc;
+  if ((rc = lists_check(c, "poi_rerank", n, cand, n_cand))) return rc;
+  if ((rc = rerank_check(c, "poi_rerank", cand_off, n_cand, k, idx_out))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  poi::TileOperands T;
+  if ((rc = tile_operands(c, "poi_rerank", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, last_poi, n_dist, dd, nullptr, nullptr, st, &T))) return rc;
+  if (n == 0) return POI_OK;
+  // the scores between the two stages live in the context; the stages follow each other on the stream, the host does not wait in between
+  int* flag = nullptr;
+  float* sc = nullptr;
+  const size_t n_sc = cand_off ? (size_t)n_cand : (size_t)n * (size_t)n_cand;
+  if ((rc = carve(c, c->rerank_ws, st, [&](Carver& W) {
+         flag = (int*)W.bytes(sizeof(int) * (size_t)(cand_off ? n : 1));
+         sc = (float*)W.bytes(sizeof(float) * (n_sc ? n_sc : 1));
+       })))
+    return rc;
+  const long span = c->tm.span_begin("rerank", st);
+  if (n_cand > 0) {
+    if ((rc = score_lists_run(c, T, cand_off, cand, n_cand, flag, sc, st))) return rc;
+  } else {
+    c->plan.valid = 1; c->plan.lists_path = cand_off ? 0 : 1;
+  }
+  rc = rerank_run(c, cand_off, cand, n, n_cand, sc, prior, w_score, w_prior, n_cand > 0 ? flag : nullptr, k, idx_out, score_out, pos_out, count_out, T.bad, st);
+  c->tm.span_end(span, st);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
 // group recommendation (group.hip)
 static int group_check_args(poi_ctx* c, const char* who, int32_t n, int32_t n_item, const int32_t* g_off, const int32_t* g_mem, int32_t n_grp,
                             int32_t agg, const int32_t* ex_off, const int32_t* ex, int32_t k, const int32_t* idx_out) {

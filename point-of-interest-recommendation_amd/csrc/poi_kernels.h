@@ -784,6 +784,31 @@ struct SelectArgs {
 hipError_t launch_score_rows(const ScoreRowsArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_select(const SelectArgs& A, hipStream_t st, Timing* tm);
 
+// Re-ranking (rerank.hip): the scores of explicit candidate lists, and the best k of every list under explicit (blended) scores
+#define RERANK_CHUNK 256                    // entries of a ragged row one workgroup scores at a time (poi_score_lists_chunk)
+#define RERANK_LEN_MAX 4096                 // list length / k of the sort: 4096 x 12 bytes fit one workgroup's LDS
+#define RERANK_SORT_BLOCK 1024              // threads of the sort's workgroup at lists beyond 2048 entries
+struct ScoreListsArgs {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim;
+  const float *wd, *sts; const double *coords, *cphi, *thr; const int* last_poi; int n_dist; float bin_scale;      // distance term, or wd null
+  const int *ex_off, *ex; int* bad;                           // (ex_off / ex: the operand block's members, not read); bad: device counter of rejected rows
+  const int *cand_off, *cand; int n_cand;                     // ragged: row r owns cand[cand_off[r] .. cand_off[r + 1]); cand_off null: one list for all rows
+  int* flag;                                                  // workspace: (n) ragged / (1) shared, 1 = rejected
+  int n_split;                                                // ragged: workgroups per row (gridDim.y); shared: list ranges (one per wave) of a 32-row tile
+  float* out;                                                 // ragged: (n_cand), parallel to cand; shared: (n, n_cand)
+};
+struct RerankListsArgs {
+  const int *cand_off, *cand; int n, n_cand;                  // the lists, as above
+  const float *score, *prior; double w_score, w_prior;        // parallel to cand (ragged) / (n, n_cand) (shared); prior may be null
+  const int* flag;                                            // rows the scoring stage of poi_rerank has rejected and counted (not counted again), or null
+  int k, p_max;                                               // p_max: the power of two the longest admissible list sorts in
+  int* idx_out; float* score_out; int* pos_out; int* count_out;      // (n, k), (n); all but idx_out may be null
+  int* bad;                                                   // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+hipError_t launch_score_lists(const ScoreListsArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_rerank_lists(const RerankListsArgs& A, hipStream_t st, Timing* tm);
+
 // Filtered recommendation (filter.hip): pass bitmaps of attribute predicates, and the top-K among the POIs whose bit is set
 #define FILTER_K_MAX NEAR_K_MAX             // list length (one half wave)
 #define FILTER_SPLIT_LIMIT 64               // slices a row's (a 32-row tile's) item range may be cut into

@@ -171,6 +171,72 @@ def candidate_recall(model, starts_ends_tes, ks, exclude="train"):
     return {k: (float(h[i]) / t if t else 0.0) for i, k in enumerate(ks)}
 
 
+def two_stage_metrics(retriever, ranker, starts_ends_tes, cands=(100, 1000), ks=(5, 10, 20), exclude="train"):
+    """What a two-stage recommender loses against its ranker run over ALL POIs: `retriever` hands its top-c candidates
+    (compute_sub_candidates) to `ranker`, which scores exactly those and orders them (rerank).  For every candidate cut c in cands
+    (strictly ascending, <= min(4096, n_item)) and cut-off k in ks (strictly ascending, k <= cands[0]) the result holds
+      out[c]["retriever"] / ["ranker"]   dict(mrr, recall={k: ..}) of each model alone, from the exact ranks of the held-out POIs among
+                                         all POIs (compute_sub_target_rank) - the same numbers under every c
+      out[c]["two_stage"]                the same for retrieve-then-rerank: a held-out POI outside the c candidates is a miss
+                                         (reciprocal rank 0), one inside has the rank of its place in the re-ranked list
+      out[c]["agreement"]                {k: share of rows whose two-stage top-k IS the ranker's own top-k over all POIs}
+    ONE compute_sub_candidates call of the retriever at max(cands): the smaller cuts are prefixes of its sorted lists.  The held-out
+    POIs are the ranker's test rows; one that is excluded (or masked) is not ranked and leaves every mean.  Both models must agree on
+    n_item and n_user (ValueError).  The reductions are torch ops on the models' device; scalars reach the host."""
+    import torch
+    cands, ks = [int(c) for c in cands], [int(k) for k in ks]
+    for name, v in (("cands", cands), ("ks", ks)):
+        if not v or any(b <= a for a, b in zip(v, v[1:])) or v[0] <= 0:
+            raise ValueError("%s must be strictly ascending and >= 1 (got %r)" % (name, v))
+    if ks[-1] > cands[0]:
+        raise ValueError("every cut-off of ks must be <= the smallest candidate cut (%d > %d)" % (ks[-1], cands[0]))
+    if retriever.n_item != ranker.n_item or retriever.n_user != ranker.n_user:
+        raise ValueError("retriever and ranker must share the POI table and the user ids (n_item %d vs %d, n_user %d vs %d)"
+                         % (retriever.n_item, ranker.n_item, retriever.n_user, ranker.n_user))
+    dev = ranker.device
+    z = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
+    acc = {c: dict(rr=z(), hit=z(len(ks)), same=z(len(ks))) for c in cands}
+    alone = {who: dict(rr=z(), hit=z(len(ks))) for who in ("retriever", "ranker")}
+    total, rows = z(), 0
+    for se in coalesce_ranges(starts_ends_tes):
+        ids, lo = ranker._ids(se)
+        n = ids.numel()
+        if not n:
+            continue
+        rows += n
+        tgt, tm = ranker._rows(ranker.tes_buys_masks, ids, lo), ranker._rows(ranker.tes_masks, ids, lo)
+        r_rank = ranker.compute_sub_target_rank(se, exclude=exclude, targets=(tgt, tm)).long()
+        ok = r_rank >= 0
+        total += ok.sum()
+        for who, rk in (("retriever", retriever.compute_sub_target_rank(se, exclude=exclude, targets=(tgt, tm)).long()), ("ranker", r_rank)):
+            alone[who]["rr"] += torch.where(ok & (rk >= 0), 1.0 / (rk.clamp(min=0).double() + 1.0), z()).sum()
+            for i, k in enumerate(ks):
+                alone[who]["hit"][i] += (ok & (rk >= 0) & (rk < k)).sum()
+        pool = retriever.compute_sub_candidates(se, cands[-1], exclude=exclude)
+        own = ranker.compute_sub_candidates(se, ks[-1], exclude=exclude)
+        for c in cands:
+            two = ranker.rerank(se, pool[:, :c].contiguous(), c)
+            for o in range(0, n, 2048):                              # (rows, targets, c) comparisons, 2048 rows at a time
+                eq = two[o:o + 2048, None, :] == tgt[o:o + 2048, :, None].int()
+                found = eq.any(2) & ok[o:o + 2048]
+                pos = eq.int().argmax(2)
+                acc[c]["rr"] += torch.where(found, 1.0 / (pos.double() + 1.0), z()).sum()
+                for i, k in enumerate(ks):
+                    acc[c]["hit"][i] += (found & (pos < k)).sum()
+            for i, k in enumerate(ks):
+                acc[c]["same"][i] += (two[:, :k] == own[:, :k]).all(1).sum()
+    t = float(total.item())
+    share = lambda v, d: float(v) / d if d else 0.0
+    single = {who: dict(mrr=share(a["rr"].item(), t), recall={k: share(a["hit"][i].item(), t) for i, k in enumerate(ks)}) for who, a in alone.items()}
+    out = {}
+    for c in cands:
+        a = acc[c]
+        out[c] = dict(retriever=single["retriever"], ranker=single["ranker"],
+                      two_stage=dict(mrr=share(a["rr"].item(), t), recall={k: share(a["hit"][i].item(), t) for i, k in enumerate(ks)}),
+                      agreement={k: share(a["same"][i].item(), rows) for i, k in enumerate(ks)})
+    return out
+
+
 def audience_recall(model, ks, exclude="train"):
     """Recall of the audience direction: over the held-out (user, test POI) pairs (tes_buys_masks under tes_masks), the share of pairs
     whose user lies inside the top-k audience of the POI (model.recommend_audience), for every k in ks (strictly ascending).  ONE call

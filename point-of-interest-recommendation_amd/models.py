@@ -821,6 +821,185 @@ class _Base:
         return self._candidates_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), ex, k, return_scores, return_counts, sync)
 
 
+    # ---- re-ranking (poi_score_lists / poi_rerank_lists / poi_rerank): score explicit candidate lists, blend with a prior, exact top-K -----
+    RERANK_LEN_MAX = 4096
+    _RERANK_MESSAGE = ("row(s) with malformed candidate offsets, more than %d candidates or a candidate id beyond the table: "
+                       "their scores are -inf, their lists all -1" % RERANK_LEN_MAX)
+
+    def _rerank_lists_arg(self, lists, n, host_check=False):
+        """lists -> dict(off, ids (device int32; off None = one shared list), n_cand, shape): an (n, C) array or tensor padded with -1
+        (shape (n, C): a ragged list with off[r] = r C), a CSR pair (off, ids) (shape None: flat) or a 1-D array, one list shared by
+        every row (shape (n, C)).  Host arrays are checked before the launch - offsets ascending inside the ids (ValueError), ids below
+        n_item (IndexError; negative ids are padding); device tensors are left to the kernel, unless `host_check` copies them back."""
+        def host(a):
+            if isinstance(a, torch.Tensor):
+                return a.cpu().numpy() if host_check or not a.is_cuda else None
+            return np.asarray(a)
+
+        def ids_dev(a, h):
+            if h is not None:
+                h = np.ascontiguousarray(h).reshape(-1).astype(np.int64)
+                if h.size and h.max() >= self.n_item:
+                    raise IndexError("candidate ids must lie below n_item = %d (found %d); negative ids are padding" % (self.n_item, int(h.max())))
+                t = torch.as_tensor(h.astype(np.int32)).to(self.device)
+            else:
+                t = a.to(self.device, torch.int32).contiguous().reshape(-1)
+            return t if t.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)
+
+        if isinstance(lists, tuple):
+            if len(lists) != 2:
+                raise ValueError("lists=(off, ids): a CSR pair")
+            off, ids = lists
+            n_cand = int(ids.numel() if isinstance(ids, torch.Tensor) else np.asarray(ids).size)
+            if (off.numel() if isinstance(off, torch.Tensor) else np.asarray(off).size) != n + 1:
+                raise ValueError("lists=(off, ids): off must hold n + 1 = %d offsets" % (n + 1))
+            ho = host(off)
+            if ho is not None:
+                ho = ho.reshape(-1).astype(np.int64)
+                if ho[0] < 0 or np.any(np.diff(ho) < 0) or ho[-1] > n_cand:
+                    raise ValueError("lists=(off, ids): the offsets must ascend inside [0, %d]" % n_cand)
+                off_t = torch.as_tensor(ho.astype(np.int32)).to(self.device)
+            else:
+                off_t = off.to(self.device, torch.int32).contiguous().reshape(-1)
+            return dict(off=off_t, ids=ids_dev(ids, host(ids)), n_cand=n_cand, shape=None, host_off=ho)
+        h = host(lists)
+        shape = tuple(lists.shape) if isinstance(lists, torch.Tensor) else h.shape
+        if len(shape) == 1:
+            return dict(off=None, ids=ids_dev(lists, h), n_cand=int(shape[0]), shape=(n, int(shape[0])), host_off=None)
+        if len(shape) != 2 or shape[0] != n:
+            raise ValueError("lists must be (n = %d, C) padded with -1, a CSR pair (off, ids) or one 1-D shared list (got shape %s)" % (n, shape))
+        C = int(shape[1])
+        ho = np.arange(n + 1, dtype=np.int64) * C
+        if ho[-1] >= 2 ** 31:
+            raise ValueError("lists: n * C must stay below 2^31")
+        off_t = torch.arange(n + 1, dtype=torch.int32, device=self.device) * C      # (built on the device: no copy in front of the launch)
+        return dict(off=off_t, ids=ids_dev(lists, h), n_cand=n * C, shape=(n, C), host_off=ho)
+
+    def _rerank_args(self, L, n, k, prior, weights):
+        """k, the prior as a device float32 tensor laid out like the scores (or None), the two weights."""
+        k = int(k)
+        if not 1 <= k <= self.RERANK_LEN_MAX:
+            raise ValueError("re-ranking supports 1 <= k <= %d (got %d)" % (self.RERANK_LEN_MAX, k))
+        longest = L["n_cand"] if L["off"] is None else L["shape"][1] if L["shape"] else int(np.diff(L["host_off"]).max()) if L["host_off"] is not None and n else 0
+        if longest > self.RERANK_LEN_MAX:
+            raise ValueError("re-ranking supports lists of at most %d candidates (got %d)" % (self.RERANK_LEN_MAX, longest))
+        w = tuple(float(x) for x in weights)
+        if len(w) != 2:
+            raise ValueError("weights = (w_score, w_prior)")
+        if prior is not None:
+            prior = self._dev(prior, torch.float32).reshape(-1)
+            want = L["n_cand"] if L["off"] is not None else n * L["n_cand"]
+            if prior.numel() != want:
+                raise ValueError("prior must hold one value per candidate entry (%d vs %d)" % (prior.numel(), want))
+            if not prior.numel():
+                prior = torch.zeros(1, dtype=torch.float32, device=self.device)
+        return k, prior, w
+
+    def _rerank_buffers(self, n, k, return_scores, return_positions, return_counts):
+        idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_scores else None
+        pos = torch.empty((n, k), dtype=torch.int32, device=self.device) if return_positions else None
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        return idx, sc, pos, cnt
+
+    def _lists_scores_buffer(self, L, n):
+        numel = L["n_cand"] if L["off"] is not None else n * L["n_cand"]
+        return torch.empty(max(numel, 1), dtype=torch.float32, device=self.device), numel
+
+    def _lists_scores_out(self, buf, numel, L):
+        out = buf[:numel]
+        return out.view(L["shape"]) if L["shape"] is not None else out
+
+    def _score_lists_launch(self, users, items, term, L, sync):
+        """One poi_score_lists call -> the scores, laid out like the lists."""
+        n = users.shape[0]
+        buf, numel = self._lists_scores_buffer(L, n)
+        if n and numel:
+            self.ctx.check(self.lib.poi_score_lists(self.ctx.handle, *self._tile_operands(users, items, self.kdim, term), _ptr(L["off"]), _ptr(L["ids"]),
+                                                    L["n_cand"], _ptr(buf), self._stream()))
+        return self._serve_out(self._lists_scores_out(buf, numel, L), (), sync and n > 0 and numel > 0, self._RERANK_MESSAGE)
+
+    def _rerank_launch(self, users, items, term, L, k, prior, w, return_scores, return_positions, return_counts, sync):
+        """One poi_rerank call -> idx[, keys][, positions][, counts] (device tensors)."""
+        n = users.shape[0]
+        idx, sc, pos, cnt = self._rerank_buffers(n, k, return_scores, return_positions, return_counts)
+        if n:
+            self.ctx.check(self.lib.poi_rerank(self.ctx.handle, *self._tile_operands(users, items, self.kdim, term), _ptr(L["off"]), _ptr(L["ids"]),
+                                               L["n_cand"], _ptr(prior), w[0], w[1], k, _ptr(idx), _ptr(sc), _ptr(pos), _ptr(cnt), self._stream()))
+        return self._serve_out(idx, ((sc, return_scores), (pos, return_positions), (cnt, return_counts)), sync and n > 0, self._RERANK_MESSAGE)
+
+    def _lists_from_rows(self, score_rows, n, L):
+        """The listed columns of explicit score rows, a bounded number of rows at a time (score_rows(o, c) -> (c, n_item)): a torch
+        gather.  The lists have been checked on the host (_rerank_lists_arg(host_check=True)); padding gets -inf."""
+        buf, numel = self._lists_scores_buffer(L, n)
+        ids = L["ids"][:L["n_cand"]].long()
+        col, pad = ids.clamp(min=0), ids < 0
+        for o, c in self._row_chunks(n):
+            full = score_rows(o, c)
+            if L["off"] is None:
+                part = full.index_select(1, col).masked_fill(pad[None, :], float("-inf"))
+                buf[o * L["n_cand"]:(o + c) * L["n_cand"]] = part.reshape(-1)
+            else:
+                e0, e1 = int(L["host_off"][o]), int(L["host_off"][o + c])
+                lens = torch.as_tensor(np.diff(L["host_off"][o:o + c + 1])).to(self.device)
+                row = torch.repeat_interleave(torch.arange(c, device=self.device), lens)
+                buf[e0:e1] = full[row, col[e0:e1]].masked_fill(pad[e0:e1], float("-inf"))
+        if L["off"] is not None and numel:                       # entries no row owns
+            own = torch.zeros(numel, dtype=torch.bool, device=self.device)
+            own[int(L["host_off"][0]):int(L["host_off"][-1])] = True
+            buf[:numel].masked_fill_(~own, float("-inf"))
+        return buf, numel
+
+    def _rerank_from_scores(self, score_rows, n, L, k, prior, w, return_scores, return_positions, return_counts, sync):
+        """Explicit score rows + a gather of the listed columns + poi_rerank_lists."""
+        idx, sc, pos, cnt = self._rerank_buffers(n, k, return_scores, return_positions, return_counts)
+        if n:
+            buf, _ = self._lists_from_rows(score_rows, n, L)
+            self.ctx.check(self.lib.poi_rerank_lists(self.ctx.handle, _ptr(L["off"]), _ptr(L["ids"]), n, L["n_cand"], _ptr(buf), _ptr(prior), w[0], w[1], k,
+                                                     _ptr(idx), _ptr(sc), _ptr(pos), _ptr(cnt), self._stream()))
+        return self._serve_out(idx, ((sc, return_scores), (pos, return_positions), (cnt, return_counts)), sync and n > 0, self._RERANK_MESSAGE)
+
+    def score_lists(self, start_end, lists, sync=True):
+        """The model's own score of EXPLICIT candidates (include/poi_hip.h, poi_score_lists): `lists` is an (n, C) array or tensor
+        padded with -1, a CSR pair (off, ids) or a 1-D array - one list shared by every row.  Returns float32 scores on the device
+        laid out like the lists ((n, C), flat, (n, C)); padding gets -inf.  The scores are compute_sub_all_scores' at the listed
+        columns - for the models that score by users . items bit for bit poi_score_rows', without the (n, n_item) matrix."""
+        if not self._rank_fused:
+            a = self._id_list(start_end)
+            L = self._rerank_lists_arg(lists, len(a), host_check=True)
+            buf, numel = self._lists_from_rows(self._own_score_rows(a), len(a), L) if len(a) else self._lists_scores_buffer(L, 0)
+            return self._lists_scores_out(buf, numel, L)
+        ids, users, lo = self._users_rows(start_end)
+        L = self._rerank_lists_arg(lists, ids.numel())
+        return self._score_lists_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), L, sync)
+
+    def rerank(self, start_end, lists, k, prior=None, weights=(1.0, 0.0), return_scores=False, return_positions=False, return_counts=False,
+               sync=True):
+        """RE-RANKING (include/poi_hip.h, poi_rerank): the second stage of a two-stage recommender.  Every row brings its candidate POIs
+        (`lists`, as score_lists takes them: e.g. another model's compute_sub_candidates output); they are scored under THIS model and
+        the best k <= 4096 come back in order.  With a prior (one float per candidate entry, laid out like the lists) the key is
+        weights[0] * score + weights[1] * prior in float64, rounded once to float32; without one the key is the score.  Returns (n, k)
+        int32 ids on the device by descending key, ties by ascending id, then by position in the list (duplicates are kept), -1
+        where a list has fewer than k selectable entries (padding, NaN and -inf keys are never selected); with return_scores the keys,
+        with return_positions each entry's position inside its list (gather side data with it), with return_counts the number of
+        selectable entries per row.  The models that score by users . items make one fused call; CA-RNN, PRME, POI2Vec and GeoIE under
+        rule="geo" go through their own score rows, a bounded number at a time, a gather and poi_rerank_lists.  Host arguments are
+        checked before the launch (ValueError / IndexError); device lists are checked by the kernel: an offending row comes out all
+        -1 and - with sync - raises IndexError."""
+        if not self._rank_fused:
+            a = self._id_list(start_end)
+            n = len(a)
+            L = self._rerank_lists_arg(lists, n, host_check=True)
+            k, prior, w = self._rerank_args(L, n, k, prior, weights)
+            return self._rerank_from_scores(self._own_score_rows(a), n, L, k, prior, w, return_scores, return_positions, return_counts, sync)
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        L = self._rerank_lists_arg(lists, n)
+        k, prior, w = self._rerank_args(L, n, k, prior, weights)
+        return self._rerank_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), L, k, prior, w, return_scores, return_positions,
+                                   return_counts, sync)
+
+
     # ---- filtered recommendation (poi_filter_build / poi_score_topk_filtered / poi_topk_filtered_scores): top-K among the POIs that pass a predicate
     FILTER_K_MAX = 32
     _FILTER_PATH = {"auto": 0, "walk": 1, "gather": 2}
@@ -2677,6 +2856,25 @@ class Session:
         ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
         return m._candidates_launch(users, m.trained_items.t, term, ex, k, return_scores, return_counts, sync)
 
+    def score_lists(self, slots, lists, sync=True):
+        """model.score_lists over the slots' CURRENT states (h, sts, last_poi, as `candidates` assembles them): the scores of explicit
+        candidate lists.  A slot without a check-in has no distance term."""
+        m = self.m
+        ids = self._slot_tensor(slots)
+        users, _, term = self._tile_rows(ids)
+        return m._score_lists_launch(users, m.trained_items.t, term, m._rerank_lists_arg(lists, ids.numel()), sync)
+
+    def rerank(self, slots, lists, k, prior=None, weights=(1.0, 0.0), return_scores=False, return_positions=False, return_counts=False, sync=True):
+        """model.rerank over the slots' CURRENT states: every slot's candidate list scored under its state and returned in order
+        (k <= 4096; optionally blended with a prior)."""
+        m = self.m
+        ids = self._slot_tensor(slots)
+        n = ids.numel()
+        users, _, term = self._tile_rows(ids)
+        L = m._rerank_lists_arg(lists, n)
+        k, prior, w = m._rerank_args(L, n, k, prior, weights)
+        return m._rerank_launch(users, m.trained_items.t, term, L, k, prior, w, return_scores, return_positions, return_counts, sync)
+
     def recommend_group(self, slot_groups, k, agg="mean", exclude=None, return_scores=False, return_counts=False, sync=True):
         """model.recommend_group over the slots' CURRENT states (h, sts, last_poi, as `rank_of` assembles them): slot_groups is a list of
         lists of slot ids or a CSR pair (off, ids); agg "mean" or "min"; exclude None or CSR lists (off, ids), one per group.  A slot
@@ -3018,6 +3216,28 @@ class CellSession(Session):
         k = m._candidates_k(k)
         n, score_rows, has, ex = self._carnn_rows(slots, exclude)
         return self._carnn_out(m._candidates_from_scores(score_rows, n, ex, k, return_scores, return_counts, sync), has, return_scores, return_counts)
+
+    def score_lists(self, slots, lists, sync=True):
+        """Lstm / Rnn: `Session.score_lists`' plain rule.  CA-RNN: the listed columns of its own score rows on the slots' CURRENT h and
+        last_poi; a slot without a check-in scores -inf everywhere."""
+        if not self.carnn:
+            return super().score_lists(slots, lists, sync)
+        m = self.m
+        n, score_rows, _, _ = self._carnn_rows(slots)
+        L = m._rerank_lists_arg(lists, n, host_check=True)
+        buf, numel = m._lists_from_rows(score_rows, n, L) if n else m._lists_scores_buffer(L, 0)
+        return m._lists_scores_out(buf, numel, L)
+
+    def rerank(self, slots, lists, k, prior=None, weights=(1.0, 0.0), return_scores=False, return_positions=False, return_counts=False, sync=True):
+        """Lstm / Rnn: `Session.rerank`'s plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi, a gather of the
+        listed columns and poi_rerank_lists; a slot without a check-in gives -1 ids (count 0)."""
+        if not self.carnn:
+            return super().rerank(slots, lists, k, prior, weights, return_scores, return_positions, return_counts, sync)
+        m = self.m
+        n, score_rows, _, _ = self._carnn_rows(slots)
+        L = m._rerank_lists_arg(lists, n, host_check=True)
+        k, prior, w = m._rerank_args(L, n, k, prior, weights)
+        return m._rerank_from_scores(score_rows, n, L, k, prior, w, return_scores, return_positions, return_counts, sync)
 
     def recommend_group(self, slot_groups, k, agg="mean", exclude=None, return_scores=False, return_counts=False, sync=True):
         """Lstm / Rnn: `Session.recommend_group`'s plain rule.  CA-RNN ranks by a rule of its own and is refused."""
