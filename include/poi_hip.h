@@ -104,6 +104,10 @@ extern "C" {
  * (with "capped_walk" / "capped_merge" inside it) / "topk_capped_scores" (existing entries unchanged). */
 /* additive to 9: re-ranking - new entry points poi_score_lists, poi_rerank_lists and poi_rerank (and poi_score_lists_chunk), plan key
  * "lists_path", timing names "score_lists" / "rerank_lists" / "rerank"; no new option (existing entries unchanged). */
+/* additive to 9: label recommendation - new entry points poi_score_labels, poi_score_topk_labels and poi_labels_scores, options
+ * "labels_split_max" / "labels_grid" / "labels_lds_kb" / "labels_ws_kb", plan keys "labels_splits" / "labels_split_max" / "labels_home" /
+ * "labels_chunks" / "labels_rows_per_chunk", timing names "score_labels" / "score_topk_labels" / "labels_scores_call" (with "labels_max" /
+ * "labels_walk" or "labels_scores", and "labels_finish" inside them) (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -206,7 +210,11 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * Additive to 9: "similar_path" (0 one workgroup per query block, 1 slices, 2 score rows + selection), "similar_splits" (slices of the
  * walk, 0 with one workgroup per query block), "similar_split_max" - written by poi_similar_topk / poi_similar_rows.
  * Additive to 9: "capped_splits" (slices, 0 outside the split regime), "capped_split_max" - written by poi_score_topk_capped.
- * Additive to 9: "lists_path" (0 ragged lists, 1 one shared list) - written by poi_score_lists / poi_rerank. */
+ * Additive to 9: "lists_path" (0 ragged lists, 1 one shared list) - written by poi_score_lists / poi_rerank.
+ * Additive to 9: "labels_splits" (slices, 0 outside the split regime), "labels_split_max", "labels_home" (where the label accumulators of
+ * the call lived: 1 the workgroup's LDS, 2 the context's global accumulator), "labels_chunks" / "labels_rows_per_chunk" (the rows went
+ * through the accumulator workspace in this many chunks of this many rows) - written by poi_score_labels / poi_score_topk_labels /
+ * poi_labels_scores. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -318,7 +326,14 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *       poi_score_topk_filtered - bitwise the same result for every n and in either regime;
  *   "capped_hist_kb" n (default 262144 = 256 MiB): poi_labels_build keeps at most n KiB of per-predicate label histograms
  *       ((n_label + 1) ints per predicate) in the context's workspace at a time - whole predicates, at least one; more predicates go
- *       through it in chunks.  The same tables for every n. */
+ *       through it in chunks.  The same tables for every n;
+ *   "labels_split_max" n (default 256) / "labels_grid" n (default 0 = by the row count and the CUs; at most 64): the split regime of
+ *       poi_score_labels / poi_score_topk_labels and its slices, as "capped_split_max" / "capped_grid" - bitwise the same result;
+ *   "labels_lds_kb" n (default 40, at most 120; 0: never): the label accumulators of a workgroup (32 rows x (n_label + 1) buckets x 20
+ *       bytes; poi_labels_scores: one row) live in LDS and are flushed once while they fit n KiB, otherwise every candidate goes to the
+ *       context's global accumulator with integer atomics - bitwise the same result on either side;
+ *   "labels_ws_kb" n (default 262144 = 256 MiB): the global accumulator holds at most n KiB (whole 32-row tiles, at least one); more
+ *       rows go through it in chunks.  Bitwise the same result for every n. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -1402,6 +1417,72 @@ int poi_topk_capped_scores(poi_ctx* ctx, const float* scores, int32_t n, int32_t
                            const uint32_t* bits, int64_t ldw, int32_t n_pred, const int32_t* pred,
                            const int32_t* ex_off, const int32_t* ex, int32_t k,
                            int32_t* idx_out, float* score_out, int32_t* label_out, int32_t* count_out, void* stream);
+
+/* ---- label recommendation (additive to 9): which category / district comes next, by probability mass ---------------------------------------
+ * The level above the POI lists: the probability that the next check-in falls in label l is the softmax mass of the label's POIs,
+ *   p(l | r) = sum over j in l of exp(s(r, j)) / sum over j of exp(s(r, j)),
+ * computed in one fused pass without the (n, n_item) score matrix.  poi_score_topk_capped(per = 1) ranks labels by their single best POI;
+ * a label with 400 decent POIs can outweigh one with a single excellent POI, and only the mass says so.
+ *
+ *   rows, s(r, j)  exactly poi_score_rank's: the same product routine, fragment loader and k order, the same distance term at the row's
+ *                  `anchor` (no term while anchor < 0), one zero; float32 and half item tables
+ *   labels         (n_item) int32, a PoiLabels' device array: a value in [0, n_label) is POI j's label, anything else (< 0) is unlabelled
+ *                  and goes to the extra bucket n_label.  1 <= n_label <= n_item
+ *   C(r)           every POI minus the row's exclusion list (ex_off (n + 1), ex: CSR, ascending ids, both NULL = none; the checks of
+ *                  poi_score_topk_capped).  A NaN or -inf score is no candidate and adds nothing
+ *   M(r)           the maximum of s(r, j) over ALL j in [0, n_item) with a non-NaN score: it does not depend on the exclusion list
+ *   q(r, j)        round_to_nearest_uint64(exp(double(s(r, j)) - double(M(r))) * 2^36), per candidate
+ *   per bucket     mass_q = the uint64 sum of q over the bucket's candidates; best = the candidate that wins under the top-K tie rule
+ *                  (higher score, then lower id); count = its candidates.  An integer sum, a maximum under a total order, an integer
+ *                  count: their bits do not depend on the grid, the regime, the accumulator's home, the chunking of the rows or on whether
+ *                  a row is served alone or with thousands of others.  n_item < 2^27 keeps the sum below 2^63 (larger: POI_ENOTSUP)
+ *   resolution     one q unit is 2^-36 of the row's best POI: rounding each term to it leaves an ABSOLUTE ERROR FLOOR of 2^-37 of the best
+ *                  POI's weight per candidate of a label's mass (a candidate more than 25.6 below M(r) adds nothing)
+ *   total_q        the sum over all n_label + 1 buckets;  logp(r, l) = log(double(mass_q)) - log(double(total_q)) in float64, -inf for a
+ *                  label without mass;  the log-normaliser over the candidates is lognorm = M + log(total_q * 2^-36), -inf without mass
+ *   fill           a row with non-finite M(r) (no scorable POI, all NaN, a +inf score) has no candidates: masses and counts 0, ids -1,
+ *                  scores and log values -inf.  A rejected row (anchor outside [-1, n_item), malformed exclusion list) is counted once
+ *                  in the context's bad-id counter, comes out the same way and reports M = -inf
+ *
+ * poi_score_labels - the dense result for n rows: mass_out (n, n_label + 1) uint64, best_id_out / best_score_out / count_out of the
+ * same shape (id -1 and score -inf for an empty bucket), m_out (n) float32, lognorm_out (n) float64; every output may be NULL and is
+ * then skipped.  The category distribution as a feature for a downstream ranker.
+ *
+ * poi_score_topk_labels - the best k labels (1 <= k <= 32, otherwise POI_ENOTSUP) per row among the labels with count > 0; the
+ * unlabelled bucket is never listed, its share is rest_logp_out (n).  by = POI_LABELS_BY_MASS: higher mass_q first, then the lower
+ * label id; POI_LABELS_BY_MAX: by the label's best POI under the top-K tie rule - the labels, ids and scores of
+ * poi_score_topk_capped(per = 1) on labellings without unlabelled POIs.  label_out (n, k) int32 (-1 fill), logp_out (n, k) float64
+ * (-inf fill), best_id_out / best_score_out (n, k) the listed labels' best POIs; n_listed_out, rest_logp_out, m_out, lognorm_out (n).
+ * All but label_out may be NULL.
+ *
+ * poi_labels_scores - the same definition on explicit float32 score rows scores (n, ld), ld >= n_item, one workgroup per row, for the
+ * models whose score is not users . items, and an independent check of the walk: the dense outputs, and with 1 <= k <= 32 the top-K
+ * outputs (k = 0: none).
+ *
+ * Kernels (labels.hip): a max-only instance of the tile walk gives M(r) ("labels_max"), a second walk accumulates ("labels_walk") with
+ * integer atomics only - in the workgroup's LDS while the accumulators fit "labels_lds_kb", else on the context's global accumulator -
+ * and a finish kernel ("labels_finish") takes logs and selects the k labels.  Few rows cut every tile's item range into slices
+ * ("labels_split_max" / "labels_grid").  poi_ctx_last_plan: "labels_splits" (0 outside the split regime), "labels_split_max",
+ * "labels_home" (1 LDS, 2 global), "labels_chunks", "labels_rows_per_chunk". */
+#define POI_LABELS_BY_MASS 0
+#define POI_LABELS_BY_MAX 1
+int poi_score_labels(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                     const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* anchor,
+                     int32_t n_dist, double dd,
+                     const int32_t* labels, int32_t n_label, const int32_t* ex_off, const int32_t* ex,
+                     uint64_t* mass_out, int32_t* best_id_out, float* best_score_out, int32_t* count_out, float* m_out, double* lognorm_out,
+                     void* stream);
+int poi_score_topk_labels(poi_ctx* ctx, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim,
+                          const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* anchor,
+                          int32_t n_dist, double dd,
+                          const int32_t* labels, int32_t n_label, const int32_t* ex_off, const int32_t* ex, int32_t by, int32_t k,
+                          int32_t* label_out, double* logp_out, int32_t* best_id_out, float* best_score_out, int32_t* n_listed_out,
+                          double* rest_logp_out, float* m_out, double* lognorm_out, void* stream);
+int poi_labels_scores(poi_ctx* ctx, const float* scores, int32_t n, int32_t n_item, int64_t ld,
+                      const int32_t* labels, int32_t n_label, const int32_t* ex_off, const int32_t* ex, int32_t by, int32_t k,
+                      uint64_t* mass_out, int32_t* best_id_out, float* best_score_out, int32_t* count_out,
+                      int32_t* label_out, double* logp_out, int32_t* top_id_out, float* top_score_out, int32_t* n_listed_out,
+                      double* rest_logp_out, float* m_out, double* lognorm_out, void* stream);
 
 /* ---- audience recommendation (additive to 9): given a POI, which users? -------------------------------------------------------------------
  * Every entry above ranks POIs for a row.  poi_score_audience ranks ROWS for a POI: for query POIs pois[q] (q < n_q) and the candidate

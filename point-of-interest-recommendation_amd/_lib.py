@@ -223,6 +223,15 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_topk_capped_scores": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                        c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_score_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int32, c_double, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
+    "poi_score_topk_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int32, c_double, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "poi_labels_scores": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     "poi_foldin_bpr": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float, c_float,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "poi_foldin_terms_fpmc": (c_int, [c_void_p, POINTER(FpmcParams), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p]),
@@ -292,7 +301,8 @@ PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", 
              "diverse_path", "diverse_splits", "diverse_split_max",
              "select_rows_per_chunk", "select_chunks", "select_path", "select_splits", "xfwd_ids_lds",
              "filter_path", "filter_splits", "filter_split_max", "audience_path", "audience_splits", "audience_split_max",
-             "similar_path", "similar_splits", "similar_split_max", "capped_splits", "capped_split_max", "lists_path")
+             "similar_path", "similar_splits", "similar_split_max", "capped_splits", "capped_split_max", "lists_path",
+             "labels_splits", "labels_split_max", "labels_home", "labels_chunks", "labels_rows_per_chunk")
 
 
 class Context:
@@ -389,7 +399,8 @@ class Context:
         "select_grid" / "select_chunk_mb" of poi_topk_select / poi_score_candidates; "filter_split_max" / "filter_grid" / "filter_gather_cost" of
         poi_score_topk_filtered; "audience_split_max" / "audience_grid" of poi_score_audience / poi_audience_rows; "similar_split_max" /
         "similar_grid" / "similar_rows_max" of poi_similar_topk / poi_similar_rows; "capped_split_max" / "capped_grid" of
-        poi_score_topk_capped, "capped_hist_kb" of poi_labels_build)."""
+        poi_score_topk_capped, "capped_hist_kb" of poi_labels_build; "labels_split_max" / "labels_grid" / "labels_lds_kb" / "labels_ws_kb" of
+        poi_score_labels / poi_score_topk_labels / poi_labels_scores)."""
         self.check(self.lib.poi_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def set_small_launch(self, max_sequences=1800):

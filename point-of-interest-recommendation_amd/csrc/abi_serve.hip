@@ -7,6 +7,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <functional>
+
 extern "C" {
 
 int poi_carnn_score_all(poi_ctx* c, const float* users, const float* items, const float* M, const float* dists, const double* coords,
@@ -1483,6 +1485,157 @@ int poi_topk_capped_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n
   if ((rc = bad_counter(c, st, &A.bad))) return rc;
   HIPCHK(c, poi::launch_capped_scores(A, st, &c->tm));
   return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// label recommendation (labels.hip)
+struct LabelsOut {      // what a call asks of the finish kernel: pointers at row 0
+  uint64_t* mass; int32_t* best_id; float* best_score; int32_t* count;      // dense (n, n_label + 1)
+  float* m; double* lognorm;                                                // (n)
+  int32_t* label; double* logp; int32_t* top_id; float* top_score;          // (n, k)
+  int32_t* n_listed; double* rest_logp;                                     // (n)
+};
+
+// what the three entries check alike
+static int labels_check(poi_ctx* c, const char* who, int32_t n, int32_t n_item, const int32_t* labels, int32_t n_label, int32_t by, int32_t k,
+                        bool topk_required, const int32_t* label_out) {
+  if (k > LABELS_K_MAX || k < (topk_required ? 1 : 0))
+    return fail(c, POI_ENOTSUP, "%s supports %d <= k <= %d (got %d)", who, topk_required ? 1 : 0, LABELS_K_MAX, k);
+  if (!labels) return fail(c, POI_EINVAL, "%s: NULL labels", who);
+  if (k > 0 && !label_out) return fail(c, POI_EINVAL, "%s: NULL label_out", who);
+  if (k > 0 && by != LABELS_BY_MASS && by != LABELS_BY_MAX) return fail(c, POI_EINVAL, "%s: by must be POI_LABELS_BY_MASS or POI_LABELS_BY_MAX (got %d)", who, by);
+  if (n < 0 || n_item <= 0) return fail(c, POI_EINVAL, "%s: n < 0 or n_item <= 0", who);
+  if (n_item >= (1 << 27)) return fail(c, POI_ENOTSUP, "%s supports n_item < 2^27: the 64-bit mass of a label must stay below 2^63 (got %d)", who, n_item);
+  if (n_label < 1 || n_label > n_item) return fail(c, POI_EINVAL, "%s: needs 1 <= n_label <= n_item (got %d, %d)", who, n_label, n_item);
+  return POI_OK;
+}
+
+// The rows of a call through the accumulator workspace, "labels_ws_kb" KiB of whole 32-row tiles at a time: per chunk the memset, the
+// accumulation (`accumulate(row0, rows, acc)`: the max pass and the walk, or the explicit-rows kernel) and the finish kernel.
+static int labels_run(poi_ctx* c, int n, int n_label, int by, int k, const LabelsOut& O, hipStream_t st,
+                      const std::function<int(int, int, const poi::LabelsAcc&)>& accumulate) {
+  const size_t L1 = (size_t)n_label + 1, per_row = LABELS_ROW_BYTES * L1 + 8;
+  size_t fit = ((size_t)c->labels_ws_kb << 10) / per_row / 32 * 32;
+  if (fit < 32) fit = 32;
+  const size_t n_pad = ((size_t)n + 31) / 32 * 32;
+  const size_t chunk = fit < n_pad ? fit : n_pad;
+  poi::LabelsAcc acc = {};
+  void* block = nullptr;
+  const size_t bytes = chunk * per_row;
+  int rc;
+  if ((rc = carve(c, c->labels_ws, st, [&](Carver& W) { block = W.bytes(bytes); }))) return rc;
+  acc.mass = (unsigned long long*)block; acc.best = acc.mass + chunk * L1; acc.cnt = (unsigned*)(acc.best + chunk * L1);
+  acc.mkey = acc.cnt + chunk * L1; acc.status = (int*)(acc.mkey + chunk);
+  c->plan.valid = 1; c->plan.labels_rows_per_chunk = (int)chunk; c->plan.labels_chunks = (int)((n_pad + chunk - 1) / chunk);
+  for (size_t r0 = 0; r0 < (size_t)n; r0 += chunk) {
+    const int m = (int)((size_t)n - r0 < chunk ? (size_t)n - r0 : chunk);
+    HIPCHK(c, hipMemsetAsync(block, 0, bytes, st));      // (the stream orders it behind the finish kernel of the chunk before)
+    if ((rc = accumulate((int)r0, m, acc))) return rc;
+    poi::LabelsFinishArgs F = {};
+    F.n = m; F.n_label = n_label; F.k = k; F.by = by; F.acc = acc;
+    F.mass_out = O.mass ? (unsigned long long*)O.mass + r0 * L1 : nullptr; F.best_id_out = O.best_id ? O.best_id + r0 * L1 : nullptr;
+    F.best_score_out = O.best_score ? O.best_score + r0 * L1 : nullptr; F.count_out = O.count ? O.count + r0 * L1 : nullptr;
+    F.m_out = O.m ? O.m + r0 : nullptr; F.lognorm_out = O.lognorm ? O.lognorm + r0 : nullptr;
+    F.label_out = O.label ? O.label + r0 * k : nullptr; F.logp_out = O.logp ? O.logp + r0 * k : nullptr;
+    F.top_id_out = O.top_id ? O.top_id + r0 * k : nullptr; F.top_score_out = O.top_score ? O.top_score + r0 * k : nullptr;
+    F.n_listed_out = O.n_listed ? O.n_listed + r0 : nullptr; F.rest_logp_out = O.rest_logp ? O.rest_logp + r0 : nullptr;
+    HIPCHK(c, poi::launch_labels_finish(F, st, &c->tm));
+  }
+  return POI_OK;
+}
+
+// the fused entries: the tile walk over users . items
+static int labels_fused(poi_ctx* c, const char* who, const char* span_name, const float* users, const float* items, int32_t n, int32_t n_item,
+                        int32_t dim, const float* wd, const float* sts, const double* coords, const double* cphi, const double* thr,
+                        const int32_t* anchor, int32_t n_dist, double dd, const int32_t* labels, int32_t n_label, const int32_t* ex_off,
+                        const int32_t* ex, int32_t by, int32_t k, bool topk_required, const LabelsOut& O, void* stream) {
+  if (!c || !users || !items) return fail(c, POI_EINVAL, "%s: NULL ctx / users / items", who);
+  int rc;
+  hipStream_t st = (hipStream_t)stream;
+  poi::TileOperands T;
+  if (dim <= 0 || dim % 4 != 0 || dim > 256) return fail(c, POI_ENOTSUP, "%s: dim must be a multiple of 4 in [4, 256] (got %d)", who, dim);
+  if ((rc = labels_check(c, who, n, n_item, labels, n_label, by, k, topk_required, O.label))) return rc;
+  if ((rc = tile_operands(c, who, users, items, n, n_item, dim, wd, sts, coords, cphi, thr, anchor, n_dist, dd, ex_off, ex, st, &T))) return rc;
+  if (wd && n_dist > LABELS_NDIST_MAX) return fail(c, POI_ENOTSUP, "%s supports n_dist <= %d (got %d)", who, LABELS_NDIST_MAX, n_dist);
+  if (n == 0) return POI_OK;
+  const bool lds_home = poi::labels_lds_bytes(32, n_label) <= ((size_t)c->labels_lds_kb << 10);
+  const int ntile = (n_item + 31) / 32;
+  c->plan.labels_home = lds_home ? 1 : 2; c->plan.labels_split_max = c->labels_split_max;
+  const long span = c->tm.span_begin(span_name, st);      // the call; inside it the max pass, the walk and the finish on their own
+  rc = labels_run(c, n, n_label, by, k, O, st, [&](int r0, int m, const poi::LabelsAcc& acc) -> int {
+    poi::LabelsArgs A = {};
+    put_operands(A, T);
+    A.users = users + (size_t)r0 * dim; A.n = m;
+    A.last_poi = anchor ? anchor + r0 : nullptr; A.coords = coords; A.cphi = cphi;      // (the anchor is range-checked with or without a distance term)
+    if (A.sts) A.sts = sts + (size_t)r0 * ((size_t)n_dist + 1);
+    if (A.ex_off) A.ex_off = ex_off + r0;
+    A.labels = labels; A.n_label = n_label; A.lds_home = lds_home; A.acc = acc;
+    // few rows (live traffic): the item range of every 32-row tile is cut into slices so that the call fills the CUs; many rows: one
+    // workgroup per tile
+    const SplitPlan sp = plan_split(m, (m + 31) / 32, c->labels_split_max, c->labels_grid, 2, c->num_cu, ntile / 16, 2, LABELS_SPLIT_LIMIT);
+    A.n_split = sp.n_split;
+    c->plan.labels_splits = sp.split ? A.n_split : 0;
+    HIPCHK(c, poi::launch_labels_max(A, st, &c->tm));
+    HIPCHK(c, poi::launch_labels_walk(A, st, &c->tm));
+    return POI_OK;
+  });
+  c->tm.span_end(span, st);
+  return rc;
+}
+
+int poi_score_labels(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
+                     const double* coords, const double* cphi, const double* thr, const int32_t* anchor, int32_t n_dist, double dd,
+                     const int32_t* labels, int32_t n_label, const int32_t* ex_off, const int32_t* ex, uint64_t* mass_out, int32_t* best_id_out,
+                     float* best_score_out, int32_t* count_out, float* m_out, double* lognorm_out, void* stream) {
+  LabelsOut O = {};
+  O.mass = mass_out; O.best_id = best_id_out; O.best_score = best_score_out; O.count = count_out; O.m = m_out; O.lognorm = lognorm_out;
+  return labels_fused(c, "poi_score_labels", "score_labels", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, anchor, n_dist, dd, labels,
+                      n_label, ex_off, ex, LABELS_BY_MASS, 0, false, O, stream);
+}
+
+int poi_score_topk_labels(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd,
+                          const float* sts, const double* coords, const double* cphi, const double* thr, const int32_t* anchor, int32_t n_dist,
+                          double dd, const int32_t* labels, int32_t n_label, const int32_t* ex_off, const int32_t* ex, int32_t by, int32_t k,
+                          int32_t* label_out, double* logp_out, int32_t* best_id_out, float* best_score_out, int32_t* n_listed_out,
+                          double* rest_logp_out, float* m_out, double* lognorm_out, void* stream) {
+  LabelsOut O = {};
+  O.label = label_out; O.logp = logp_out; O.top_id = best_id_out; O.top_score = best_score_out; O.n_listed = n_listed_out;
+  O.rest_logp = rest_logp_out; O.m = m_out; O.lognorm = lognorm_out;
+  return labels_fused(c, "poi_score_topk_labels", "score_topk_labels", users, items, n, n_item, dim, wd, sts, coords, cphi, thr, anchor, n_dist, dd,
+                      labels, n_label, ex_off, ex, by, k, true, O, stream);
+}
+
+int poi_labels_scores(poi_ctx* c, const float* scores, int32_t n, int32_t n_item, int64_t ld, const int32_t* labels, int32_t n_label,
+                      const int32_t* ex_off, const int32_t* ex, int32_t by, int32_t k, uint64_t* mass_out, int32_t* best_id_out,
+                      float* best_score_out, int32_t* count_out, int32_t* label_out, double* logp_out, int32_t* top_id_out, float* top_score_out,
+                      int32_t* n_listed_out, double* rest_logp_out, float* m_out, double* lognorm_out, void* stream) {
+  const char* who = "poi_labels_scores";
+  if (!c || !scores) return fail(c, POI_EINVAL, "%s: NULL ctx / scores", who);
+  int rc;
+  if ((rc = labels_check(c, who, n, n_item, labels, n_label, by, k, false, label_out))) return rc;
+  if (ld < n_item) return fail(c, POI_EINVAL, "%s: ld must be >= n_item", who);
+  if ((rc = check_ex_pair(c, who, ex_off, ex))) return rc;
+  if (n == 0) return POI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  int* bad = nullptr;
+  if ((rc = bad_counter(c, st, &bad))) return rc;
+  LabelsOut O = {};
+  O.mass = mass_out; O.best_id = best_id_out; O.best_score = best_score_out; O.count = count_out; O.m = m_out; O.lognorm = lognorm_out;
+  O.label = label_out; O.logp = logp_out; O.top_id = top_id_out; O.top_score = top_score_out; O.n_listed = n_listed_out; O.rest_logp = rest_logp_out;
+  // one row per workgroup: its accumulators take 1 / 32 of a tile's - the same budget holds 32 times the labels
+  const bool lds_home = poi::labels_lds_bytes(1, n_label) <= ((size_t)c->labels_lds_kb << 10);
+  c->plan.labels_home = lds_home ? 1 : 2; c->plan.labels_splits = 0; c->plan.labels_split_max = c->labels_split_max;
+  const long span = c->tm.span_begin("labels_scores_call", st);
+  rc = labels_run(c, n, n_label, by, k, O, st, [&](int r0, int m, const poi::LabelsAcc& acc) -> int {
+    poi::LabelsScoresArgs A = {};
+    A.scores = scores + (size_t)r0 * (size_t)ld; A.ld = ld; A.n = m; A.n_item = n_item;
+    A.ex_off = ex_off ? ex_off + r0 : nullptr; A.ex = ex; A.labels = labels; A.n_label = n_label; A.lds_home = lds_home; A.acc = acc; A.bad = bad;
+    HIPCHK(c, poi::launch_labels_scores(A, st, &c->tm));
+    return POI_OK;
+  });
+  c->tm.span_end(span, st);
+  return rc;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -883,6 +883,52 @@ hipError_t launch_labels_build(const LabelsBuildArgs& A, hipStream_t st, Timing*
 hipError_t launch_capped_walk(const CappedArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_capped_scores(const CappedScoresArgs& A, hipStream_t st, Timing* tm);
 
+// Label recommendation (labels.hip): per row and label the softmax mass, the best POI and the number of the candidates
+#define LABELS_K_MAX 32                     // labels a top-K call lists per row
+#define LABELS_SPLIT_LIMIT 64               // slices a 32-row tile's item range may be cut into
+#define LABELS_NDIST_MAX 4096               // distance bins whose thresholds fit the walk kernel's LDS beside its accumulators
+#define LABELS_LDS_KB_MAX 120               // the most LDS (KiB) the accumulators of a workgroup may take (option "labels_lds_kb")
+#define LABELS_ROW_BYTES 20                 // accumulator bytes per (row, bucket): 64-bit mass, 64-bit best key, 32-bit count
+#define LABELS_Q_BITS 36                    // q = round(exp(s - M) 2^36)
+#define LABELS_BY_MASS 0
+#define LABELS_BY_MAX 1
+struct LabelsAcc {                                            // context workspace of one chunk of rows, zero before the walk
+  unsigned long long *mass, *best; unsigned* cnt;             // (rows, n_label + 1): bucket n_label holds the unlabelled POIs
+  unsigned* mkey; int* status;                                // (rows): f2ord(M(r)), 0 = none; 1 = the row was rejected
+};
+struct LabelsArgs {
+  const float* users; const void* items; int items_f16;      // (n, dim) float32; (n_item [+ 1], dim) float32 or IEEE half
+  int n, n_item, dim;
+  const float *wd, *sts; const double *coords, *cphi, *thr; const int* last_poi; int n_dist; float bin_scale;      // distance term, or wd null; last_poi = the anchor (null: none)
+  const int *ex_off, *ex;                                     // per-row exclusion lists (ascending ids), or both null
+  const int* labels; int n_label;                             // labels (n_item): [0, n_label) a label, anything else unlabelled
+  int n_split;                                                // slices (1 in the tile regime)
+  int lds_home;                                               // the accumulators of a workgroup live in LDS and are flushed once (else: atomics on acc)
+  LabelsAcc acc;
+  int* bad;                                                   // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+struct LabelsScoresArgs {
+  const float* scores; long long ld; int n, n_item;           // (n, ld) float32 score rows, the first n_item of each row are read
+  const int *ex_off, *ex;
+  const int* labels; int n_label;
+  int lds_home;
+  LabelsAcc acc;
+  int* bad;
+};
+struct LabelsFinishArgs {
+  int n, n_label, k, by;                                      // k = 0: no top-K part
+  LabelsAcc acc;
+  unsigned long long* mass_out; int* best_id_out; float* best_score_out; int* count_out;      // dense (n, n_label + 1), each may be null
+  float* m_out; double* lognorm_out;                          // (n), may be null
+  int* label_out; double* logp_out; int* top_id_out; float* top_score_out;      // (n, k); all but label_out may be null
+  int* n_listed_out; double* rest_logp_out;                   // (n), may be null
+};
+hipError_t launch_labels_max(const LabelsArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_labels_walk(const LabelsArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_labels_scores(const LabelsScoresArgs& A, hipStream_t st, Timing* tm);
+hipError_t launch_labels_finish(const LabelsFinishArgs& A, hipStream_t st, Timing* tm);
+size_t labels_lds_bytes(int rows, int n_label);              // LDS the accumulators of `rows` rows take
+
 // Fold-in of new users for the factorisation family (foldin.hip)
 #define FOLDIN_USERS_PER_WAVE 4             // one 16-lane DPP row per user
 struct FoldinArgs {

@@ -171,6 +171,35 @@ def candidate_recall(model, starts_ends_tes, ks, exclude="train"):
     return {k: (float(h[i]) / t if t else 0.0) for i, k in enumerate(ks)}
 
 
+def label_hit_rate(model, labels, starts_ends_tes, ks, by="mass", exclude=None):
+    """Next-category / next-region accuracy: the share of the held-out check-ins (tes_buys_masks under tes_masks) whose LABEL is among
+    the top-k labels of model.recommend_labels, for every k in ks (strictly ascending, 1 <= k <= 32).  labels: a PoiLabels; by: "mass"
+    (the label's softmax mass) or "max" (its single best POI) - run both to see what the mass buys.  A held-out POI outside [0, n_item)
+    or without a label leaves the mean.  All cut-offs come from ONE call at max(ks).  Returns {k: hit rate}."""
+    import torch
+    ks = [int(k) for k in ks]
+    if not ks or any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] <= 0:
+        raise ValueError("ks must be strictly ascending cut-offs >= 1 (got %r)" % (ks,))
+    N = model.n_item
+    hits = torch.zeros(len(ks), dtype=torch.float64, device=model.device)
+    total = torch.zeros((), dtype=torch.float64, device=model.device)
+    for se in coalesce_ranges(starts_ends_tes):
+        top = model.recommend_labels(se, ks[-1], labels, by=by, exclude=exclude)[0]
+        ids, lo = model._ids(se)
+        tgt = model._rows(model.tes_buys_masks, ids, lo).long()
+        ok = (model._rows(model.tes_masks, ids, lo) != 0) & (tgt >= 0) & (tgt < N)
+        want = labels.labels[tgt.clamp(0, N - 1)]                    # (n, len_t) labels of the held-out POIs
+        ok &= (want >= 0) & (want < labels.n_label)
+        total += ok.sum()
+        eq = top[:, None, :] == want[:, :, None]
+        found = eq.any(2) & ok
+        pos = eq.int().argmax(2)
+        for i, k in enumerate(ks):
+            hits[i] += (found & (pos < k)).sum()
+    h, t = hits.cpu().numpy(), float(total.item())
+    return {k: (float(h[i]) / t if t else 0.0) for i, k in enumerate(ks)}
+
+
 def two_stage_metrics(retriever, ranker, starts_ends_tes, cands=(100, 1000), ks=(5, 10, 20), exclude="train"):
     """What a two-stage recommender loses against its ranker run over ALL POIs: `retriever` hands its top-c candidates
     (compute_sub_candidates) to `ranker`, which scores exactly those and orders them (rerank).  For every candidate cut c in cands

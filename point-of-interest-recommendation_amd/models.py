@@ -1278,6 +1278,121 @@ class _Base:
         return self._capped_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), ex, labels, per, fill, filt, pred, k, return_scores,
                                    return_labels, return_counts, sync)
 
+    # ---- label recommendation (poi_score_labels / poi_score_topk_labels / poi_labels_scores): the next category / district by probability mass
+    LABELS_K_MAX = 32
+    _LABELS_BY = {"mass": 0, "max": 1}
+    _LABELS_BAD = "row(s) with an anchor or an exclusion id out of range: their label lists are all -1"
+
+    def _labels_args(self, k, labels, by):
+        """(k, PoiLabels, the library's code of `by`) of a label call, host arguments checked; k None: the dense call."""
+        if k is not None:
+            k = int(k)
+            if not 1 <= k <= self.LABELS_K_MAX:
+                raise ValueError("label recommendation supports 1 <= k <= %d (got %d)" % (self.LABELS_K_MAX, k))
+        if by not in self._LABELS_BY:
+            raise ValueError("by must be 'mass' or 'max' (got %r)" % (by,))
+        if not isinstance(labels, PoiLabels):
+            labels = self.poi_labels(labels)
+        if labels.n_item != self.n_item or labels.labels.device != self.device:
+            raise ValueError("labels must be a PoiLabels built for this model (model.poi_labels / PoiLabels.from_categories)")
+        if self.n_item >= 1 << 27:
+            raise ValueError("label recommendation supports n_item < 2^27 (got %d)" % self.n_item)
+        return k, labels, self._LABELS_BY[by]
+
+    def _labels_buffers(self, n, k, return_best):
+        lab = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        logp = torch.empty((n, k), dtype=torch.float64, device=self.device)
+        bid = torch.empty((n, k), dtype=torch.int32, device=self.device) if return_best else None
+        bsc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_best else None
+        return lab, logp, bid, bsc
+
+    def _labels_launch(self, users, items, term, ex, labels, by, k, return_best, sync):
+        """One poi_score_topk_labels call -> labels, logp[, best ids, best scores] (device tensors).  term: (wd, sts rows, last POI rows)
+        or None, as _candidates_launch takes it."""
+        n = users.shape[0]
+        lab, logp, bid, bsc = self._labels_buffers(n, k, return_best)
+        if n:
+            self.ctx.check(self.lib.poi_score_topk_labels(self.ctx.handle, *self._tile_operands(users, items, self.kdim, term), _ptr(labels.labels),
+                                                          labels.n_label, _ptr(ex[0]), _ptr(ex[1]), by, k, _ptr(lab), _ptr(logp), _ptr(bid), _ptr(bsc),
+                                                          None, None, None, None, self._stream()))
+        return self._serve_out(lab, ((logp, True), (bid, return_best), (bsc, return_best)), sync and n > 0, self._LABELS_BAD)
+
+    def _labels_from_scores(self, score_rows, n, ex, labels, by, k, return_best, sync):
+        """Explicit score rows, a bounded number of rows at a time, + poi_labels_scores.  score_rows(o, c) -> (c, n_item) float32 scores
+        of rows o .. o + c - 1."""
+        N = self.n_item
+        lab, logp, bid, bsc = self._labels_buffers(n, k, return_best)
+        at = lambda t, o, w: ctypes.c_void_p(t.data_ptr() + t.element_size() * o * w) if t is not None else None
+        for o, c in self._row_chunks(n):
+            full = score_rows(o, c).contiguous()
+            self.ctx.check(self.lib.poi_labels_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(labels.labels), labels.n_label, at(ex[0], o, 1),
+                                                      _ptr(ex[1]), by, k, None, None, None, None, at(lab, o, k), at(logp, o, k), at(bid, o, k),
+                                                      at(bsc, o, k), None, None, None, None, self._stream()))
+        return self._serve_out(lab, ((logp, True), (bid, return_best), (bsc, return_best)), sync and n > 0, self._LABELS_BAD)
+
+    def _labels_dense(self, n, n_label, call):
+        """The dense mass of n rows through call(o, c, mass rows o ..) -> ((n, n_label) float64 probabilities, (n) unlabelled rest)."""
+        mass = torch.zeros((n, n_label + 1), dtype=torch.int64, device=self.device)      # (uint64 below 2^63: the same bits)
+        call(mass)
+        if n and self.ctx.take_bad_ids(self._stream().value):
+            raise IndexError("label_distribution: " + self._LABELS_BAD)
+        m = mass.double()
+        prob = m / m.sum(dim=1, keepdim=True).clamp(min=1.0)
+        return prob[:, :n_label].contiguous(), prob[:, n_label].contiguous()
+
+    def recommend_labels(self, start_end, k, labels, by="mass", exclude=None, return_best=False, sync=True):
+        """The next LABELS (include/poi_hip.h, poi_score_topk_labels): the k (<= 32) categories / districts of `labels` (a PoiLabels:
+        model.poi_labels / PoiLabels.from_categories / data.grid_labels) the next check-in most likely falls in.  by="mass": by the
+        softmax mass of the label's POIs under the model's own score (the spatial model's distance term at the user's last POI) - the
+        probability of the label; by="max": by the label's single best POI, the order of compute_sub_topk_capped(per=1).  exclude:
+        None, "train" or CSR lists (off, ids): excluded POIs leave the masses and the normaliser.  Returns (labels (n, k) int32 with -1
+        where fewer labels have a candidate, log-probabilities (n, k) float64 with -inf on the fill) and, with return_best, the listed
+        labels' best POI ids and scores.  The unlabelled POIs are never listed; their mass is part of the normaliser.  CA-RNN, PRME,
+        POI2Vec and GeoIE under rule="geo" go through their own score rows, a bounded number at a time, and poi_labels_scores.  Host
+        arguments are checked before the launch (ValueError / IndexError); device tensors by the kernel: an offending row comes out
+        all -1 and - with sync - raises IndexError."""
+        k, labels, byc = self._labels_args(k, labels, by)
+        if not self._rank_fused:
+            a = self._id_list(start_end)
+            ids, lo = self._ids(a)
+            ex = self._near_exclusion(exclude, len(a), None, ids, lo, kinds=("train",))
+            return self._labels_from_scores(self._own_score_rows(a), len(a), ex, labels, byc, k, return_best, sync)
+        ids, users, lo = self._users_rows(start_end)
+        ex = self._near_exclusion(exclude, ids.numel(), None, ids, lo, kinds=("train",))
+        return self._labels_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), ex, labels, byc, k, return_best, sync)
+
+    def label_distribution(self, start_end, labels, exclude=None):
+        """The whole label distribution (poi_score_labels): ((n, n_label) float64 probabilities that the next check-in falls in each
+        label, (n) float64 share of the unlabelled POIs) - the rows sum to 1 with the rest (a row without candidates is all zero).
+        Arguments as recommend_labels; synchronises for the rejected-row count."""
+        _, labels, _ = self._labels_args(None, labels, "mass")
+        L = labels.n_label
+        if not self._rank_fused:
+            a = self._id_list(start_end)
+            n, N = len(a), self.n_item
+            ids, lo = self._ids(a)
+            ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+            score_rows = self._own_score_rows(a)
+
+            def call(mass):
+                for o, c in self._row_chunks(n):
+                    full = score_rows(o, c).contiguous()
+                    self.ctx.check(self.lib.poi_labels_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(labels.labels), L,
+                                                              ctypes.c_void_p(ex[0].data_ptr() + 4 * o) if ex[0] is not None else None, _ptr(ex[1]), 0, 0,
+                                                              ctypes.c_void_p(mass.data_ptr() + 8 * o * (L + 1)), None, None, None, None, None, None,
+                                                              None, None, None, None, None, self._stream()))
+            return self._labels_dense(n, L, call)
+        ids, users, lo = self._users_rows(start_end)
+        n = ids.numel()
+        ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
+        users, term = users.contiguous(), self._rank_term(ids, lo)
+
+        def call(mass):
+            if n:
+                self.ctx.check(self.lib.poi_score_labels(self.ctx.handle, *self._tile_operands(users, self._items(), self.kdim, term), _ptr(labels.labels),
+                                                         L, _ptr(ex[0]), _ptr(ex[1]), _ptr(mass), None, None, None, None, None, self._stream()))
+        return self._labels_dense(n, L, call)
+
 
     # ---- group recommendation (poi_group_topk / poi_group_topk_scores): the top-K of an aggregate of the members' scores ---------------
     _GROUP_AGG = {"mean": 0, "min": 1}
@@ -2832,6 +2947,18 @@ class Session:
         ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
         return m._capped_launch(users, m.trained_items.t, term, ex, labels, per, fill, filt, pred, k, return_scores, return_labels, return_counts, sync)
 
+    def recommend_labels(self, slots, k, labels, by="mass", exclude=None, return_best=False, sync=True):
+        """model.recommend_labels over the slots' CURRENT states (h, sts, last_poi, as `candidates` assembles them): the k (<= 32) labels
+        of `labels` (a PoiLabels) the next check-in most likely falls in, by softmax mass (by="mass") or by the label's best POI
+        (by="max"), with their log-probabilities.  exclude: None, "last" or CSR lists (off, ids).  A slot without a check-in has no
+        distance term."""
+        m = self.m
+        ids = self._slot_tensor(slots)
+        k, labels, byc = m._labels_args(k, labels, by)
+        users, lpr, term = self._tile_rows(ids)
+        ex = m._near_exclusion(exclude, ids.numel(), lpr, kinds=("last",))
+        return m._labels_launch(users, m.trained_items.t, term, ex, labels, byc, k, return_best, sync)
+
     def rank_of(self, slots, pois, exclude=None, return_scores=False, return_counts=False, sync=True):
         """Exact 0-based rank of pois[i] (one POI per slot, or (n, len_t <= 8)) among all POIs under the slot's CURRENT state - the score
         rule of `recommend` (h . trained_items[:-1]^T, plus the spatial distance term at last_poi; none before the first check-in):
@@ -3191,6 +3318,17 @@ class CellSession(Session):
         n, score_rows, has, ex = self._carnn_rows(ids, exclude)
         out = m._capped_from_scores(score_rows, n, ex, labels, per, fill, filt, pred, k, return_scores, return_labels, return_counts, sync)
         return self._carnn_out(out, has, return_scores, return_counts)
+
+    def recommend_labels(self, slots, k, labels, by="mass", exclude=None, return_best=False, sync=True):
+        """Lstm / Rnn: `Session.recommend_labels`'s plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi +
+        poi_labels_scores; a slot without a check-in has no scorable POI: labels -1, log-probabilities -inf."""
+        if not self.carnn:
+            return super().recommend_labels(slots, k, labels, by, exclude, return_best, sync)
+        m = self.m
+        ids = self._slot_tensor(slots)
+        k, labels, byc = m._labels_args(k, labels, by)
+        n, score_rows, _, ex = self._carnn_rows(ids, exclude)
+        return m._labels_from_scores(score_rows, n, ex, labels, byc, k, return_best, sync)
 
     def recommend_diverse(self, slots, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
                           return_objective=False, return_pool=False, return_counts=False, sync=True):
