@@ -29,6 +29,70 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def _at(t, o, w):
+    """Row o of a row-major tensor of w columns as a pointer (None stays None): where a chunk of rows writes its part of an output."""
+    return ctypes.c_void_p(t.data_ptr() + t.element_size() * o * w) if t is not None else None
+
+
+class ScoreSource:
+    """What a per-row serving call ranks - n rows, each with a score for every POI - and nothing else.  A FUSED source scores by
+    users . items (+ the spatial distance term) inside the serving kernels; any other one hands out explicit score rows, a bounded
+    number at a time.  Three producers: _Base._source (trained users), Session._source (live slots), CellSession._source (CA-RNN's
+    own rule).  The per-row families (_Base._serve_*) are written once over a source.
+
+    fused sources:  users (n, kdim) float32 contiguous, items, kdim, tile_term(clamp, pad) -> (wd, sts rows, last POI rows) | None as
+                    _tile_operands takes it, near_term() -> (wd, sts rows, thr, n_dist, dd_m) | None as _near_launch takes it - each
+                    built when it is asked for.
+    other sources:  score_rows(positions=False) -> rows(o, c), the (c, n_item) scores of rows o .. o + c - 1 (positions: every
+                    (row, position) row of a model that scores them, row-major).
+    every source:   anchor() -> the default anchor rows (the last train POI / the slot's last_poi, -1: none); exclusion(exclude);
+                    finish(out, ...); need_fused(family)."""
+
+    def __init__(self, model, n, kinds, anchor, refusals, ids=None, lo=None, users=None, items=None, tile_term=None, near_term=None,
+                 score_rows=None, has=None):
+        self.m, self.n, self.kinds, self.anchor, self.refusals, self.ids, self.lo = model, n, kinds, anchor, refusals, ids, lo
+        self.fused = users is not None
+        self.users, self.items, self.kdim = users, items, (model.kdim if self.fused else None)
+        self._tile_term, self._near_term, self.score_rows, self.has = tile_term, near_term, score_rows, has
+
+    def tile_term(self, clamp=False, pad=False):
+        """clamp: the last POI rows clamped to 0 (the kernel relies on the zero sts row: target ranks, the unrestricted top-K);
+        pad: sts rows padded to whole 32-row tiles (poi_score_topk_geo alone).  Both mean something to a session only."""
+        return self._tile_term(clamp, pad)
+
+    def near_term(self):
+        return self._near_term()
+
+    def need_fused(self, family):
+        """A call that needs users . items on a source that ranks by a rule of its own: PoiError, the producer's text."""
+        if not self.fused:
+            raise _lib.PoiError(self.refusals()[family])
+
+    def exclusion(self, exclude, anchor=None):
+        """exclude -> (off (n + 1), ids) int32 device tensors or (None, None): None, one of the source's names - "train" (the users'
+        distinct train POIs: a contiguous user range windows the cached CSR), "last" (`anchor`, default the source's own) - or CSR
+        lists (off, ids).  Any other name raises ValueError with the names this source accepts."""
+        if anchor is None and isinstance(exclude, str) and exclude == "last" and "last" in self.kinds:
+            anchor = self.anchor()
+        return self.m._near_exclusion(exclude, self.n, anchor, self.ids, self.lo, self.kinds)
+
+    def finish(self, out, return_scores, return_counts, ranked=False):
+        """ids-or-ranks[, scores][, ...][, counts] as the caller gets them: the identity, except for a CA-RNN session - a slot without
+        a check-in (`has` false; its row was scored at POI 0 and masked to -inf) counts 0 candidates, and `ranked` (recommend,
+        rank_of: the kernel ranks the masked row all the same) also gives it -1 and a NaN score."""
+        has = self.has
+        if has is None:
+            return out
+        out = list(out) if isinstance(out, tuple) else [out]
+        if ranked:
+            out[0] = torch.where(has[:, None], out[0], torch.full_like(out[0], -1))
+            if return_scores:
+                out[1] = torch.where(has[:, None], out[1], torch.full_like(out[1], float("nan")))
+        if return_counts:
+            out[-1] = torch.where(has, out[-1], torch.zeros_like(out[-1]))
+        return tuple(out) if len(out) > 1 else out[0]
+
+
 class Shared:
     """Stand-in for a Theano shared variable: .get_value() / .set_value() on a device tensor."""
 
@@ -260,7 +324,7 @@ class _Base:
         else:
             raise ValueError("negatives must hold total = %d or epochs x total = %d ids (got %d)" % (total, epochs * total, q.numel()))
         if not q.numel():
-            q = torch.zeros(1, dtype=torch.int32, device=self.device)
+            q = self._some_ids()
         return q, stride
 
     def _load_tables(self, train, test):
@@ -441,18 +505,53 @@ class _Base:
             return full.view(c, per, self.n_item)[:, 0] if per > 1 and not positions else full
         return score_rows
 
+    def _refusals(self):
+        """What a call that needs users . items says to a model that ranks by a rule of its own (ScoreSource.need_fused)."""
+        own = "%s ranks by a score rule of its own, not users . items: " % type(self).__name__
+        return {"near": own + "compute_sub_topk_near does not cover it", "filtered": own + "within_km / anchor are not defined for it"}
+
+    def _source(self, start_end, kinds=("train",), fused=None):
+        """The ScoreSource of the trained users `start_end`: fused (trained_users rows . _items(), the distance term of _rank_term /
+        _near_term) where the model scores by users . items - _rank_fused, read per call: GeoIE's follows its rule - and the model's
+        own score rows otherwise.  kinds: the exclude= names the calling family accepts; fused: the family's own condition."""
+        refusals = self._refusals                                # (the texts are built when one is raised)
+        if not (self._rank_fused if fused is None else fused):
+            a = self._id_list(start_end)
+            ids, lo = self._ids(a)
+            anchor, rows = (lambda: self._rows(self._last_train_poi(), ids, lo)), (lambda positions=False: self._own_score_rows(a, positions))
+            return ScoreSource(self, len(a), kinds, anchor, refusals, ids, lo, score_rows=rows)
+        ids, users, lo = self._users_rows(start_end)
+        return ScoreSource(self, ids.numel(), kinds, lambda: self._rows(self._last_train_poi(), ids, lo), refusals, ids, lo, users.contiguous(),
+                           self._items(), lambda clamp, pad: self._rank_term(ids, lo), lambda: self._near_term(ids, lo))
+
+    def _topk_buffers(self, n, k, return_scores, return_counts):
+        """(idx (n, k) int32, scores (n, k) float32 | None, counts (n) int32 | None): the outputs of a top-K or rank call."""
+        idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_scores else None
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        return idx, sc, cnt
+
+    def _some_ids(self, t=None):
+        """An int32 id list as the library takes it: `t` itself, a one-element placeholder for an empty (or no) list."""
+        return t if t is not None and t.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def _csr_take(self, ids, beg, ln):
+        """The lists ids[beg[r] : beg[r] + ln[r]] (int64 device rows) as a CSR of their own: (off (rows + 1) int32, ids)."""
+        off = torch.zeros(ln.numel() + 1, dtype=torch.int64, device=self.device)
+        off[1:] = torch.cumsum(ln, 0)
+        pos = torch.arange(int(off[-1].item()), device=self.device) - torch.repeat_interleave(off[:-1] - beg, ln)
+        return off.int(), self._some_ids(ids[pos].contiguous())
+
     def _topk_from_rows(self, score_rows, n, k, return_scores):
         """Explicit score rows, a bounded number at a time, + poi_topk (k <= 64).  score_rows(o, c) -> (c, n_item) float32 scores of
         rows o .. o + c - 1."""
         k = int(k)
         if k > 64:
             raise _lib.PoiError("top-K supports k <= 64 (got %d)" % k)
-        idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
-        sc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_scores else None
+        idx, sc, _ = self._topk_buffers(n, k, return_scores, False)
         for o, c in self._row_chunks(n):
             full = score_rows(o, c)
-            self.ctx.check(self.lib.poi_topk(self.ctx.handle, _ptr(full), full.shape[0], self.n_item, k, ctypes.c_void_p(idx.data_ptr() + 4 * o * k),
-                                             ctypes.c_void_p(sc.data_ptr() + 4 * o * k) if sc is not None else None, self._stream()))
+            self.ctx.check(self.lib.poi_topk(self.ctx.handle, _ptr(full), full.shape[0], self.n_item, k, _at(idx, o, k), _at(sc, o, k), self._stream()))
         return (idx, sc) if return_scores else idx
 
     def _topk_from_scores(self, start_end, k, return_scores=False, scores=None):
@@ -501,7 +600,7 @@ class _Base:
         return cache[r]
 
     def _near_items(self):
-        return self.trained_items.t
+        return self._items()
 
     def _near_term(self, ids, lo):
         """(wd, sts rows (n, n_dist + 1), thr, n_dist, dd in metres) of the model's distance term, or None."""
@@ -539,28 +638,22 @@ class _Base:
                 has = (anchor >= 0)
                 eo = torch.zeros(n + 1, dtype=torch.int32, device=self.device)
                 eo[1:] = torch.cumsum(has.int(), 0)
-                ex = anchor[has].contiguous()
-                return eo, (ex if ex.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+                return eo, self._some_ids(anchor[has].contiguous())
             eo, ex = self.train_exclusion()
             if lo is not None:                                  # a contiguous user range: its offsets index the cached ids as they are
                 return eo[lo:lo + n + 1], ex
             u = ids.long()
-            beg, ln = eo[u].long(), (eo[u + 1] - eo[u]).long()
-            no = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
-            no[1:] = torch.cumsum(ln, 0)
-            pos = torch.arange(int(no[-1].item()), device=self.device) - torch.repeat_interleave(no[:-1] - beg, ln)
-            return no.int(), (ex[pos].contiguous() if pos.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+            return self._csr_take(ex, eo[u].long(), (eo[u + 1] - eo[u]).long())
         off, lst = exclude
         if isinstance(off, torch.Tensor) and isinstance(lst, torch.Tensor):      # device lists are checked by the kernel
             if off.numel() != n + 1:
                 raise ValueError("exclude=(off, ids): off must hold n + 1 = %d offsets" % (n + 1))
-            lst = lst.to(self.device, torch.int32).contiguous()
-            return off.to(self.device, torch.int32).contiguous(), (lst if lst.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+            return off.to(self.device, torch.int32).contiguous(), self._some_ids(lst.to(self.device, torch.int32).contiguous())
         off = off.cpu().numpy() if isinstance(off, torch.Tensor) else off
         lst = lst.cpu().numpy() if isinstance(lst, torch.Tensor) else lst
         from .data import check_exclusion_csr
         eo, ex = (torch.as_tensor(v).to(self.device) for v in check_exclusion_csr(off, lst, n, self.n_item))
-        return eo, (ex if ex.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+        return eo, self._some_ids(ex)
 
     def _tile_operands(self, users, items, kdim, term):
         """The 13 arguments that follow the context handle in poi_score_rank / poi_group_topk / poi_route_expand / poi_diverse_topk
@@ -591,9 +684,7 @@ class _Base:
         if radius or term is not None:
             coords, cphi, order = self._near_geo(radius)
         wd, sts, thr, n_dist, dd_m = term if term is not None else (None, None, None, 0, 0.0)
-        idx = torch.empty((n, max(k, 0)), dtype=torch.int32, device=self.device)
-        sc = torch.empty((n, max(k, 0)), dtype=torch.float32, device=self.device) if return_scores else None
-        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        idx, sc, cnt = self._topk_buffers(n, max(k, 0), return_scores, return_counts)
         self.ctx.check(self.lib.poi_score_topk_near(self.ctx.handle, _ptr(users), _ptr(items), n, self.n_item, self.kdim, _ptr(coords), _ptr(cphi),
                                                     _ptr(order), _ptr(anchor), c_r, _ptr(ex[0]), _ptr(ex[1]), _ptr(wd), _ptr(sts), _ptr(thr),
                                                     int(n_dist), float(dd_m), k, _ptr(idx), _ptr(sc), _ptr(cnt), self._stream()))
@@ -625,8 +716,8 @@ class _Base:
         within_km=None and exclude=None this is compute_sub_topk.  Host arguments are checked before the launch; device tensors are
         checked by the kernel: an offending row comes out all -1 and - with sync - raises IndexError (sync=False leaves the count to
         ctx.take_bad_ids())."""
-        if not self._near_ok:
-            raise _lib.PoiError("%s ranks by a score rule of its own, not users . items: compute_sub_topk_near does not cover it" % type(self).__name__)
+        if not self._near_ok:                                    # (before anything of the model is read)
+            raise _lib.PoiError(self._refusals()["near"])
         if within_km is None and exclude is None and anchor is None:
             out = self.compute_sub_topk(start_end, k, return_scores)
             if return_counts:
@@ -634,12 +725,14 @@ class _Base:
                 cnt = torch.full((n,), self.n_item, dtype=torch.int32, device=self.device)
                 out = (out + (cnt,)) if return_scores else (out, cnt)
             return out
-        ids, users, lo = self._users_rows(start_end)
-        n = ids.numel()
-        anc = self._near_anchor(anchor, n, lambda: self._rows(self._last_train_poi(), ids, lo))
-        ex = self._near_exclusion(exclude, n, anc, ids, lo)
-        return self._near_launch(users, self._near_items(), anc, self._near_radius(within_km), ex, self._near_term(ids, lo), k,
-                                 return_scores, return_counts, sync)
+        return self._serve_near(self._source(start_end, ("train", "last"), True), k, within_km, exclude, anchor, return_scores, return_counts, sync)
+
+    def _serve_near(self, src, k, within_km, exclude, anchor, return_scores, return_counts, sync):
+        """The restricted top-K of a source's rows: anchor (default the source's), exclusion lists, one poi_score_topk_near call."""
+        src.need_fused("near")
+        anc = self._near_anchor(anchor, src.n, src.anchor)
+        ex = src.exclusion(exclude, anc)
+        return self._near_launch(src.users, src.items, anc, self._near_radius(within_km), ex, src.near_term(), k, return_scores, return_counts, sync)
 
     # ---- exact target ranks (poi_score_rank / poi_rank_scores): where the held-out POIs stand among ALL POIs ---------------------------
     _rank_fused = True      # False: the model's score is not users . items - explicit score rows + poi_rank_scores
@@ -648,15 +741,12 @@ class _Base:
         """(wd, sts rows (n, n_dist + 1), last POI rows (n)) of the model's distance term, or None."""
         return None
 
-    def _rank_targets(self, targets, n, ids=None, lo=None):
-        """targets -> (tgt, tmask) int32 device tensors (n, len_t): None = the model's test rows, an (n, len_t) array of POI ids (all
-        valid), or a pair (ids, mask)."""
-        if targets is None:
-            tgt, tm = self._rows(self.tes_buys_masks, ids, lo), self._rows(self.tes_masks, ids, lo)
-        else:
-            tgt, tm = targets if isinstance(targets, tuple) and len(targets) == 2 else (targets, None)
-            tgt = self._dev(tgt, torch.int32).reshape(n, -1)
-            tm = torch.ones_like(tgt) if tm is None else self._dev(tm, torch.int32).reshape(n, -1)
+    def _rank_targets(self, targets, n):
+        """targets -> (tgt, tmask) int32 device tensors (n, len_t): an (n, len_t) array of POI ids (all valid), or a pair (ids, mask)."""
+        tgt, tm = targets if isinstance(targets, tuple) and len(targets) == 2 else (targets, None)
+        rows = lambda t: t if t.dim() == 2 and t.shape[0] == n else t.reshape(n, -1)      # ((0, len_t) rows cannot be reshaped)
+        tgt = rows(self._dev(tgt, torch.int32))
+        tm = torch.ones_like(tgt) if tm is None else rows(self._dev(tm, torch.int32))
         if tgt.shape != tm.shape:
             raise ValueError("targets and their mask must have the same shape (%s vs %s)" % (tuple(tgt.shape), tuple(tm.shape)))
         if not 1 <= tgt.shape[1] <= 8:
@@ -670,9 +760,7 @@ class _Base:
     def _rank_launch(self, users, items, term, tgt, tm, ex, return_scores, return_counts, sync):
         """One poi_score_rank call -> rank[, scores][, counts] (device tensors)."""
         n, lt = users.shape[0], tgt.shape[1]
-        rank = torch.empty((n, lt), dtype=torch.int32, device=self.device)
-        sc = torch.empty((n, lt), dtype=torch.float32, device=self.device) if return_scores else None
-        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        rank, sc, cnt = self._topk_buffers(n, lt, return_scores, return_counts)
         self.ctx.check(self.lib.poi_score_rank(self.ctx.handle, *self._tile_operands(users, items, self.kdim, term), _ptr(tgt), _ptr(tm), lt,
                                                _ptr(ex[0]), _ptr(ex[1]), _ptr(rank), _ptr(sc), _ptr(cnt), self._stream()))
         return self._rank_out(rank, sc, cnt, return_scores, return_counts, sync)
@@ -685,9 +773,7 @@ class _Base:
         """Explicit score rows, a bounded number of rows at a time (`step`: not the model's _rank_chunk), + poi_rank_scores.
         score_rows(o, c) -> (c, n_item) float32 scores of rows o .. o + c - 1, or (c * per, n_item) rows (row, position), row-major."""
         lt = tgt.shape[1]
-        rank = torch.empty((n, lt), dtype=torch.int32, device=self.device)
-        sc = torch.empty((n, lt), dtype=torch.float32, device=self.device) if return_scores else None
-        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
+        rank, sc, cnt = self._topk_buffers(n, lt, return_scores, return_counts)
         for o, c in self._row_chunks(n, step):
             full = score_rows(o, c)
             per = full.shape[0] // c
@@ -704,11 +790,7 @@ class _Base:
                 t_r = torch.zeros((c, per), dtype=torch.int32, device=self.device); m_r = torch.zeros_like(t_r)
                 t_r[:, :w] = t_c[:, :w]; m_r[:, :w] = m_c[:, :w]
                 if eo is not None:                               # every position of a user shares the user's list
-                    b, l = eo[:-1].long(), (eo[1:] - eo[:-1]).long()
-                    l_r = l.repeat_interleave(per)
-                    o_r = torch.zeros(c * per + 1, dtype=torch.int64, device=self.device); o_r[1:] = torch.cumsum(l_r, 0)
-                    pos = torch.arange(int(o_r[-1].item()), device=self.device) - torch.repeat_interleave(o_r[:-1] - b.repeat_interleave(per), l_r)
-                    e_r = (o_r.int(), ex[1][pos].contiguous() if pos.numel() else torch.zeros(1, dtype=torch.int32, device=self.device))
+                    e_r = self._csr_take(ex[1], eo[:-1].long().repeat_interleave(per), (eo[1:] - eo[:-1]).long().repeat_interleave(per))
                 else:
                     e_r = (None, None)
                 r_r = torch.empty((c * per, 1), dtype=torch.int32, device=self.device)
@@ -743,18 +825,21 @@ class _Base:
         [0, n_item) (which - with sync - raises IndexError); with return_scores the targets' scores, with return_counts the number of
         ranked POIs per row.  No (n, n_item) matrix is built for the models that score by users . items; CA-RNN, PRME and POI2Vec go
         through their own score rows, a bounded number of users at a time, and poi_rank_scores."""
-        if not self._rank_fused:
-            a = self._id_list(start_end)
-            n = len(a)
-            ids, lo = self._ids(a)
-            tgt, tm = self._rank_targets(targets, n, ids, lo)
-            ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-            return self._rank_from_scores(self._own_score_rows(a, positions=True), n, tgt, tm, ex, return_scores, return_counts, sync)
-        ids, users, lo = self._users_rows(start_end)
-        n = ids.numel()
-        tgt, tm = self._rank_targets(targets, n, ids, lo)
-        ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-        return self._rank_launch(users, self._items(), self._rank_term(ids, lo), tgt, tm, ex, return_scores, return_counts, sync)
+        src = self._source(start_end)
+        if targets is None:
+            targets = self._rows(self.tes_buys_masks, src.ids, src.lo), self._rows(self.tes_masks, src.ids, src.lo)
+        return self._serve_rank(src, targets, exclude, return_scores, return_counts, sync)
+
+    def _serve_rank(self, src, targets, exclude, return_scores, return_counts, sync):
+        """The exact ranks of a source's rows: poi_score_rank on the last POI rows clamped to 0, or every (row, position) score row +
+        poi_rank_scores."""
+        tgt, tm = self._rank_targets(targets, src.n)
+        ex = src.exclusion(exclude)
+        if src.fused:
+            out = self._rank_launch(src.users, src.items, src.tile_term(clamp=True), tgt, tm, ex, return_scores, return_counts, sync)
+        else:
+            out = self._rank_from_scores(src.score_rows(positions=True), src.n, tgt, tm, ex, return_scores, return_counts, sync)
+        return src.finish(out, return_scores, return_counts, ranked=True)
 
 
     # ---- candidate generation (poi_score_candidates / poi_topk_select): the exact top-K of every row for K up to 4096 ----------------------
@@ -766,12 +851,6 @@ class _Base:
             raise ValueError("candidate generation supports 1 <= k <= min(%d, n_item = %d) (got %d)" % (self.CANDIDATES_K_MAX, self.n_item, k))
         return k
 
-    def _candidates_buffers(self, n, k, return_scores, return_counts):
-        idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
-        sc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_scores else None
-        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
-        return idx, sc, cnt
-
     def _candidates_out(self, idx, sc, cnt, return_scores, return_counts, sync):
         return self._serve_out(idx, ((sc, return_scores), (cnt, return_counts)), sync,
                                "row(s) with a malformed exclusion list: their candidate lists are all -1")
@@ -779,7 +858,7 @@ class _Base:
     def _candidates_launch(self, users, items, term, ex, k, return_scores, return_counts, sync):
         """One poi_score_candidates call -> idx[, scores][, counts] (device tensors).  term: (wd, sts rows, last POI rows) or None."""
         n = users.shape[0]
-        idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
+        idx, sc, cnt = self._topk_buffers(n, k, return_scores, return_counts)
         if n:
             self.ctx.check(self.lib.poi_score_candidates(self.ctx.handle, *self._tile_operands(users, items, self.kdim, term), k, _ptr(ex[0]), _ptr(ex[1]),
                                                          _ptr(idx), _ptr(sc), _ptr(cnt), self._stream()))
@@ -789,12 +868,11 @@ class _Base:
         """Explicit score rows, a bounded number of rows at a time, + poi_topk_select, which takes the exclusion lists itself (the rows
         are not masked on the host).  score_rows(o, c) -> (c, n_item) float32 scores of rows o .. o + c - 1."""
         N = self.n_item
-        idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
-        at = lambda t, o, w: ctypes.c_void_p(t.data_ptr() + 4 * o * w) if t is not None else None
+        idx, sc, cnt = self._topk_buffers(n, k, return_scores, return_counts)
         for o, c in self._row_chunks(n):
             full = score_rows(o, c).contiguous()
-            self.ctx.check(self.lib.poi_topk_select(self.ctx.handle, _ptr(full), c, N, N, k, at(ex[0], o, 1), _ptr(ex[1]), at(idx, o, k), at(sc, o, k),
-                                                    at(cnt, o, 1), self._stream()))
+            self.ctx.check(self.lib.poi_topk_select(self.ctx.handle, _ptr(full), c, N, N, k, _at(ex[0], o, 1), _ptr(ex[1]), _at(idx, o, k), _at(sc, o, k),
+                                                    _at(cnt, o, 1), self._stream()))
         return self._candidates_out(idx, sc, cnt, return_scores, return_counts, sync and n > 0)
 
     def compute_sub_candidates(self, start_end, k, exclude=None, return_scores=False, return_counts=False, sync=True):
@@ -808,17 +886,17 @@ class _Base:
         through their own score rows, a bounded number at a time, and poi_topk_select.  Host arguments are checked before the launch
         (ValueError / IndexError); device lists are checked by the kernel: an offending row comes out all -1 and - with sync - raises
         IndexError."""
+        return self._serve_candidates(self._source(start_end), k, exclude, return_scores, return_counts, sync)
+
+    def _serve_candidates(self, src, k, exclude, return_scores, return_counts, sync):
+        """The exact top-k <= 4096 of a source's rows: poi_score_candidates, or its score rows + poi_topk_select."""
         k = self._candidates_k(k)
-        if not self._rank_fused:
-            a = self._id_list(start_end)
-            n = len(a)
-            ids, lo = self._ids(a)
-            ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-            return self._candidates_from_scores(self._own_score_rows(a), n, ex, k, return_scores, return_counts, sync)
-        ids, users, lo = self._users_rows(start_end)
-        n = ids.numel()
-        ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-        return self._candidates_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), ex, k, return_scores, return_counts, sync)
+        ex = src.exclusion(exclude)
+        if src.fused:
+            out = self._candidates_launch(src.users, src.items, src.tile_term(), ex, k, return_scores, return_counts, sync)
+        else:
+            out = self._candidates_from_scores(src.score_rows(), src.n, ex, k, return_scores, return_counts, sync)
+        return src.finish(out, return_scores, return_counts)
 
 
     # ---- re-ranking (poi_score_lists / poi_rerank_lists / poi_rerank): score explicit candidate lists, blend with a prior, exact top-K -----
@@ -844,7 +922,7 @@ class _Base:
                 t = torch.as_tensor(h.astype(np.int32)).to(self.device)
             else:
                 t = a.to(self.device, torch.int32).contiguous().reshape(-1)
-            return t if t.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)
+            return self._some_ids(t)
 
         if isinstance(lists, tuple):
             if len(lists) != 2:
@@ -896,11 +974,8 @@ class _Base:
         return k, prior, w
 
     def _rerank_buffers(self, n, k, return_scores, return_positions, return_counts):
-        idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
-        sc = torch.empty((n, k), dtype=torch.float32, device=self.device) if return_scores else None
-        pos = torch.empty((n, k), dtype=torch.int32, device=self.device) if return_positions else None
-        cnt = torch.empty(n, dtype=torch.int32, device=self.device) if return_counts else None
-        return idx, sc, pos, cnt
+        idx, sc, cnt = self._topk_buffers(n, k, return_scores, return_counts)
+        return idx, sc, (torch.empty((n, k), dtype=torch.int32, device=self.device) if return_positions else None), cnt
 
     def _lists_scores_buffer(self, L, n):
         numel = L["n_cand"] if L["off"] is not None else n * L["n_cand"]
@@ -964,14 +1039,16 @@ class _Base:
         padded with -1, a CSR pair (off, ids) or a 1-D array - one list shared by every row.  Returns float32 scores on the device
         laid out like the lists ((n, C), flat, (n, C)); padding gets -inf.  The scores are compute_sub_all_scores' at the listed
         columns - for the models that score by users . items bit for bit poi_score_rows', without the (n, n_item) matrix."""
-        if not self._rank_fused:
-            a = self._id_list(start_end)
-            L = self._rerank_lists_arg(lists, len(a), host_check=True)
-            buf, numel = self._lists_from_rows(self._own_score_rows(a), len(a), L) if len(a) else self._lists_scores_buffer(L, 0)
-            return self._lists_scores_out(buf, numel, L)
-        ids, users, lo = self._users_rows(start_end)
-        L = self._rerank_lists_arg(lists, ids.numel())
-        return self._score_lists_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), L, sync)
+        return self._serve_score_lists(self._source(start_end), lists, sync)
+
+    def _serve_score_lists(self, src, lists, sync):
+        """The scores of explicit candidate lists under a source's rows: poi_score_lists, or the listed columns of its score rows (the
+        lists then checked on the host, device lists too)."""
+        L = self._rerank_lists_arg(lists, src.n, host_check=not src.fused)
+        if src.fused:
+            return self._score_lists_launch(src.users, src.items, src.tile_term(), L, sync)
+        buf, numel = self._lists_from_rows(src.score_rows(), src.n, L) if src.n else self._lists_scores_buffer(L, 0)
+        return self._lists_scores_out(buf, numel, L)
 
     def rerank(self, start_end, lists, k, prior=None, weights=(1.0, 0.0), return_scores=False, return_positions=False, return_counts=False,
                sync=True):
@@ -986,18 +1063,15 @@ class _Base:
         rule="geo" go through their own score rows, a bounded number at a time, a gather and poi_rerank_lists.  Host arguments are
         checked before the launch (ValueError / IndexError); device lists are checked by the kernel: an offending row comes out all
         -1 and - with sync - raises IndexError."""
-        if not self._rank_fused:
-            a = self._id_list(start_end)
-            n = len(a)
-            L = self._rerank_lists_arg(lists, n, host_check=True)
-            k, prior, w = self._rerank_args(L, n, k, prior, weights)
-            return self._rerank_from_scores(self._own_score_rows(a), n, L, k, prior, w, return_scores, return_positions, return_counts, sync)
-        ids, users, lo = self._users_rows(start_end)
-        n = ids.numel()
-        L = self._rerank_lists_arg(lists, n)
-        k, prior, w = self._rerank_args(L, n, k, prior, weights)
-        return self._rerank_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), L, k, prior, w, return_scores, return_positions,
-                                   return_counts, sync)
+        return self._serve_rerank(self._source(start_end), lists, k, prior, weights, return_scores, return_positions, return_counts, sync)
+
+    def _serve_rerank(self, src, lists, k, prior, weights, return_scores, return_positions, return_counts, sync):
+        """A source's rows re-rank their candidate lists: poi_rerank, or the listed columns of its score rows + poi_rerank_lists."""
+        L = self._rerank_lists_arg(lists, src.n, host_check=not src.fused)
+        k, prior, w = self._rerank_args(L, src.n, k, prior, weights)
+        if src.fused:
+            return self._rerank_launch(src.users, src.items, src.tile_term(), L, k, prior, w, return_scores, return_positions, return_counts, sync)
+        return self._rerank_from_scores(src.score_rows(), src.n, L, k, prior, w, return_scores, return_positions, return_counts, sync)
 
 
     # ---- filtered recommendation (poi_filter_build / poi_score_topk_filtered / poi_topk_filtered_scores): top-K among the POIs that pass a predicate
@@ -1071,22 +1145,30 @@ class _Base:
         k = int(k)
         if not 1 <= k <= self.FILTER_K_MAX:
             raise ValueError("filtered recommendation supports 1 <= k <= %d (got %d)" % (self.FILTER_K_MAX, k))
-        if not isinstance(filt, PoiFilter) or filt.n_item != self.n_item or filt.bits.device != self.device:
-            raise ValueError("filt must be a PoiFilter built for this model (model.poi_filter / PoiFilter.from_masks)")
+        self._check_filter(filt)
         if path not in self._FILTER_PATH:
             raise ValueError("path must be one of %s (got %r)" % (", ".join(repr(p) for p in self._FILTER_PATH), path))
+        pred, hint = self._which_arg(filt, which, n)
+        return k, pred, hint, self._FILTER_PATH[path]
+
+    def _check_filter(self, filt):
+        if not isinstance(filt, PoiFilter) or filt.n_item != self.n_item or filt.bits.device != self.device:
+            raise ValueError("filt must be a PoiFilter built for this model (model.poi_filter / PoiFilter.from_masks)")
+
+    def _which_arg(self, filt, which, n):
+        """which -> (the per-row predicate tensor, or None: predicate 0; the most POIs a named predicate passes)."""
         if which is None:
-            pred, hint = None, int(filt.counts[0])
-        elif isinstance(which, torch.Tensor):      # a device tensor is checked by the kernel
+            return None, int(filt.counts[0])
+        if isinstance(which, torch.Tensor):      # a device tensor is checked by the kernel
             pred, hint = which.to(self.device, torch.int32).contiguous().reshape(-1), int(filt.counts.max())
         else:
             w = np.atleast_1d(np.asarray(which)).astype(np.int64)
             if w.size and (w.min() < 0 or w.max() >= filt.n_pred):
                 raise IndexError("which must index the filter's %d predicate(s) (found %d..%d)" % (filt.n_pred, int(w.min()), int(w.max())))
             pred, hint = torch.as_tensor(w.astype(np.int32)).to(self.device), int(filt.counts[w].max()) if w.size else 0
-        if pred is not None and pred.numel() != n:
+        if pred.numel() != n:
             raise ValueError("which must hold one predicate index per row (%d vs %d)" % (pred.numel(), n))
-        return k, pred, hint, self._FILTER_PATH[path]
+        return pred, hint
 
     def _filtered_out(self, idx, sc, cnt, return_scores, return_counts, sync):
         return self._serve_out(idx, ((sc, return_scores), (cnt, return_counts)), sync,
@@ -1100,7 +1182,7 @@ class _Base:
         if radius or term is not None:
             coords, cphi, order = self._near_geo(radius)
         wd, sts, thr, n_dist, dd_m = term if term is not None else (None, None, None, 0, 0.0)
-        idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
+        idx, sc, cnt = self._topk_buffers(n, k, return_scores, return_counts)
         if n:
             self.ctx.check(self.lib.poi_score_topk_filtered(self.ctx.handle, _ptr(users), _ptr(items), n, self.n_item, self.kdim, _ptr(wd), _ptr(sts),
                                                             _ptr(coords), _ptr(cphi), _ptr(thr), _ptr(anchor), int(n_dist), float(dd_m), _ptr(filt.bits),
@@ -1112,12 +1194,11 @@ class _Base:
         """Explicit score rows, a bounded number of rows at a time, + poi_topk_filtered_scores.  score_rows(o, c) -> (c, n_item)
         float32 scores of rows o .. o + c - 1."""
         N = self.n_item
-        idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
-        at = lambda t, o, w: ctypes.c_void_p(t.data_ptr() + 4 * o * w) if t is not None else None
+        idx, sc, cnt = self._topk_buffers(n, k, return_scores, return_counts)
         for o, c in self._row_chunks(n):
             full = score_rows(o, c).contiguous()
-            self.ctx.check(self.lib.poi_topk_filtered_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(filt.bits), filt.ldw, filt.n_pred, at(pred, o, 1),
-                                                             at(ex[0], o, 1), _ptr(ex[1]), k, at(idx, o, k), at(sc, o, k), at(cnt, o, 1), self._stream()))
+            self.ctx.check(self.lib.poi_topk_filtered_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(filt.bits), filt.ldw, filt.n_pred, _at(pred, o, 1),
+                                                             _at(ex[0], o, 1), _ptr(ex[1]), k, _at(idx, o, k), _at(sc, o, k), _at(cnt, o, 1), self._stream()))
         return self._filtered_out(idx, sc, cnt, return_scores, return_counts, sync and n > 0)
 
     def compute_sub_topk_filtered(self, start_end, k, filt, which=None, within_km=None, exclude=None, anchor=None, path="auto",
@@ -1132,22 +1213,24 @@ class _Base:
         and POI2Vec go through their own score rows, a bounded number at a time, and poi_topk_filtered_scores; a radius is not
         defined for them.  Host arguments are checked before the launch; device tensors by the kernel: an offending row comes out all
         -1 and - with sync - raises IndexError."""
-        if not (self._near_ok and self._rank_fused):
-            if within_km is not None or anchor is not None:
-                raise _lib.PoiError("%s ranks by a score rule of its own, not users . items: within_km / anchor are not defined for it" % type(self).__name__)
-            a = self._id_list(start_end)
-            n = len(a)
-            k, pred, _, _ = self._filtered_args(k, filt, which, n, path)
-            ids, lo = self._ids(a)
-            ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-            return self._filtered_from_scores(self._own_score_rows(a), n, ex, filt, pred, k, return_scores, return_counts, sync)
-        ids, users, lo = self._users_rows(start_end)
-        n = ids.numel()
-        k, pred, hint, pathc = self._filtered_args(k, filt, which, n, path)
-        anc = self._near_anchor(anchor, n, lambda: self._rows(self._last_train_poi(), ids, lo))
-        ex = self._near_exclusion(exclude, n, anc, ids, lo)
-        return self._filtered_launch(users.contiguous(), self._near_items(), anc.contiguous(), self._near_radius(within_km), ex, self._near_term(ids, lo),
-                                     filt, pred, hint, k, pathc, return_scores, return_counts, sync)
+        fused = self._near_ok and self._rank_fused
+        src = self._source(start_end, ("train", "last") if fused else ("train",), fused)
+        return self._serve_filtered(src, k, filt, which, within_km, exclude, anchor, path, return_scores, return_counts, sync)
+
+    def _serve_filtered(self, src, k, filt, which, within_km, exclude, anchor, path, return_scores, return_counts, sync):
+        """The filtered top-K of a source's rows: poi_score_topk_filtered around the anchor, or - no radius and no anchor there - its
+        score rows + poi_topk_filtered_scores."""
+        if within_km is not None or anchor is not None:
+            src.need_fused("filtered")
+        k, pred, hint, pathc = self._filtered_args(k, filt, which, src.n, path)
+        if src.fused:
+            anc = self._near_anchor(anchor, src.n, src.anchor)
+            ex = src.exclusion(exclude, anc)
+            out = self._filtered_launch(src.users, src.items, anc.contiguous(), self._near_radius(within_km), ex, src.near_term(), filt, pred, hint, k,
+                                        pathc, return_scores, return_counts, sync)
+        else:
+            out = self._filtered_from_scores(src.score_rows(), src.n, src.exclusion(exclude), filt, pred, k, return_scores, return_counts, sync)
+        return src.finish(out, return_scores, return_counts)
 
 
     # ---- capped recommendation (poi_labels_build / poi_score_topk_capped / poi_topk_capped_scores): top-K with at most `per` POIs per label
@@ -1170,8 +1253,8 @@ class _Base:
         n_label = int(n_label)
         if not 1 <= n_label <= self.n_item:
             raise ValueError("n_label must lie in [1, n_item = %d] (got %d)" % (self.n_item, n_label))
-        if filt is not None and (not isinstance(filt, PoiFilter) or filt.n_item != self.n_item or filt.bits.device != self.device):
-            raise ValueError("filt must be a PoiFilter built for this model (model.poi_filter / PoiFilter.from_masks)")
+        if filt is not None:
+            self._check_filter(filt)
         lab = lab.to(device=self.device, dtype=torch.int32).contiguous()
         rows = filt.n_pred if filt is not None else 1
         fill = torch.empty((rows, self.CAPPED_PER_MAX + 1), dtype=torch.int32, device=self.device)
@@ -1192,31 +1275,21 @@ class _Base:
             raise ValueError("capped recommendation supports 1 <= k <= %d (got %d)" % (self.CAPPED_K_MAX, k))
         if not 1 <= per <= self.CAPPED_PER_MAX:
             raise ValueError("capped recommendation supports 1 <= per <= %d (got %d)" % (self.CAPPED_PER_MAX, per))
-        if filt is not None and (not isinstance(filt, PoiFilter) or filt.n_item != self.n_item or filt.bits.device != self.device):
-            raise ValueError("filt must be a PoiFilter built for this model (model.poi_filter / PoiFilter.from_masks)")
+        if filt is not None:
+            self._check_filter(filt)
         if not isinstance(labels, PoiLabels):
             labels = self.poi_labels(labels, filt=filt)
         if labels.n_item != self.n_item or labels.labels.device != self.device:
             raise ValueError("labels must be a PoiLabels built for this model (model.poi_labels / PoiLabels.from_categories)")
-        pred = None
-        if filt is None:
-            if which is not None:
-                raise ValueError("which indexes the predicates of filt: it needs one")
-        elif isinstance(which, torch.Tensor):      # a device tensor is checked by the kernel
-            pred = which.to(self.device, torch.int32).contiguous().reshape(-1)
-        elif which is not None:
-            w = np.atleast_1d(np.asarray(which)).astype(np.int64)
-            if w.size and (w.min() < 0 or w.max() >= filt.n_pred):
-                raise IndexError("which must index the filter's %d predicate(s) (found %d..%d)" % (filt.n_pred, int(w.min()), int(w.max())))
-            pred = torch.as_tensor(w.astype(np.int32)).to(self.device)
-        if pred is not None and pred.numel() != n:
-            raise ValueError("which must hold one predicate index per row (%d vs %d)" % (pred.numel(), n))
+        if filt is None and which is not None:
+            raise ValueError("which indexes the predicates of filt: it needs one")
+        pred = self._which_arg(filt, which, n)[0] if filt is not None else None
         # the fill table gates by predicate row: it serves the filter it was built with (without one: the call without a filter)
         fill = labels.fill if labels.filt is filt else None
         return k, per, labels, pred, fill
 
     def _capped_buffers(self, n, k, return_scores, return_labels, return_counts):
-        idx, sc, cnt = self._candidates_buffers(n, k, return_scores, return_counts)
+        idx, sc, cnt = self._topk_buffers(n, k, return_scores, return_counts)
         return idx, sc, (torch.empty((n, k), dtype=torch.int32, device=self.device) if return_labels else None), cnt
 
     def _capped_out(self, idx, sc, lab, cnt, return_scores, return_labels, return_counts, sync):
@@ -1240,13 +1313,12 @@ class _Base:
         scores of rows o .. o + c - 1."""
         N = self.n_item
         idx, sc, lab, cnt = self._capped_buffers(n, k, return_scores, return_labels, return_counts)
-        at = lambda t, o, w: ctypes.c_void_p(t.data_ptr() + 4 * o * w) if t is not None else None
         bits, ldw, n_pred = (_ptr(filt.bits), filt.ldw, filt.n_pred) if filt is not None else (None, 0, 0)
         for o, c in self._row_chunks(n):
             full = score_rows(o, c).contiguous()
             self.ctx.check(self.lib.poi_topk_capped_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(labels.labels), per, _ptr(fill), bits, ldw, n_pred,
-                                                           at(pred, o, 1), at(ex[0], o, 1), _ptr(ex[1]), k, at(idx, o, k), at(sc, o, k), at(lab, o, k),
-                                                           at(cnt, o, 1), self._stream()))
+                                                           _at(pred, o, 1), _at(ex[0], o, 1), _ptr(ex[1]), k, _at(idx, o, k), _at(sc, o, k), _at(lab, o, k),
+                                                           _at(cnt, o, 1), self._stream()))
         return self._capped_out(idx, sc, lab, cnt, return_scores, return_labels, return_counts, sync and n > 0)
 
     def compute_sub_topk_capped(self, start_end, k, labels, per=1, filt=None, which=None, exclude=None, return_scores=False, return_labels=False,
@@ -1263,20 +1335,19 @@ class _Base:
         cap.  CA-RNN, PRME, POI2Vec and GeoIE under rule="geo" go through their own score rows, a bounded number at a time, and
         poi_topk_capped_scores.  Host arguments are checked before the launch (ValueError / IndexError); device tensors by the
         kernel: an offending row comes out all -1 and - with sync - raises IndexError."""
-        if not self._rank_fused:
-            a = self._id_list(start_end)
-            n = len(a)
-            k, per, labels, pred, fill = self._capped_args(k, labels, per, filt, which, n)
-            ids, lo = self._ids(a)
-            ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-            return self._capped_from_scores(self._own_score_rows(a), n, ex, labels, per, fill, filt, pred, k, return_scores, return_labels,
-                                            return_counts, sync)
-        ids, users, lo = self._users_rows(start_end)
-        n = ids.numel()
-        k, per, labels, pred, fill = self._capped_args(k, labels, per, filt, which, n)
-        ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-        return self._capped_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), ex, labels, per, fill, filt, pred, k, return_scores,
-                                   return_labels, return_counts, sync)
+        return self._serve_capped(self._source(start_end), k, labels, per, filt, which, exclude, return_scores, return_labels, return_counts, sync)
+
+    def _serve_capped(self, src, k, labels, per, filt, which, exclude, return_scores, return_labels, return_counts, sync):
+        """The capped top-K of a source's rows: poi_score_topk_capped, or its score rows + poi_topk_capped_scores."""
+        k, per, labels, pred, fill = self._capped_args(k, labels, per, filt, which, src.n)
+        ex = src.exclusion(exclude)
+        if src.fused:
+            out = self._capped_launch(src.users, src.items, src.tile_term(), ex, labels, per, fill, filt, pred, k, return_scores, return_labels,
+                                      return_counts, sync)
+        else:
+            out = self._capped_from_scores(src.score_rows(), src.n, ex, labels, per, fill, filt, pred, k, return_scores, return_labels,
+                                           return_counts, sync)
+        return src.finish(out, return_scores, return_counts)
 
     # ---- label recommendation (poi_score_labels / poi_score_topk_labels / poi_labels_scores): the next category / district by probability mass
     LABELS_K_MAX = 32
@@ -1322,23 +1393,12 @@ class _Base:
         of rows o .. o + c - 1."""
         N = self.n_item
         lab, logp, bid, bsc = self._labels_buffers(n, k, return_best)
-        at = lambda t, o, w: ctypes.c_void_p(t.data_ptr() + t.element_size() * o * w) if t is not None else None
         for o, c in self._row_chunks(n):
             full = score_rows(o, c).contiguous()
-            self.ctx.check(self.lib.poi_labels_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(labels.labels), labels.n_label, at(ex[0], o, 1),
-                                                      _ptr(ex[1]), by, k, None, None, None, None, at(lab, o, k), at(logp, o, k), at(bid, o, k),
-                                                      at(bsc, o, k), None, None, None, None, self._stream()))
+            self.ctx.check(self.lib.poi_labels_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(labels.labels), labels.n_label, _at(ex[0], o, 1),
+                                                      _ptr(ex[1]), by, k, None, None, None, None, _at(lab, o, k), _at(logp, o, k), _at(bid, o, k),
+                                                      _at(bsc, o, k), None, None, None, None, self._stream()))
         return self._serve_out(lab, ((logp, True), (bid, return_best), (bsc, return_best)), sync and n > 0, self._LABELS_BAD)
-
-    def _labels_dense(self, n, n_label, call):
-        """The dense mass of n rows through call(o, c, mass rows o ..) -> ((n, n_label) float64 probabilities, (n) unlabelled rest)."""
-        mass = torch.zeros((n, n_label + 1), dtype=torch.int64, device=self.device)      # (uint64 below 2^63: the same bits)
-        call(mass)
-        if n and self.ctx.take_bad_ids(self._stream().value):
-            raise IndexError("label_distribution: " + self._LABELS_BAD)
-        m = mass.double()
-        prob = m / m.sum(dim=1, keepdim=True).clamp(min=1.0)
-        return prob[:, :n_label].contiguous(), prob[:, n_label].contiguous()
 
     def recommend_labels(self, start_end, k, labels, by="mass", exclude=None, return_best=False, sync=True):
         """The next LABELS (include/poi_hip.h, poi_score_topk_labels): the k (<= 32) categories / districts of `labels` (a PoiLabels:
@@ -1351,47 +1411,45 @@ class _Base:
         POI2Vec and GeoIE under rule="geo" go through their own score rows, a bounded number at a time, and poi_labels_scores.  Host
         arguments are checked before the launch (ValueError / IndexError); device tensors by the kernel: an offending row comes out
         all -1 and - with sync - raises IndexError."""
+        return self._serve_labels(self._source(start_end), k, labels, by, exclude, return_best, sync)
+
+    def _serve_labels(self, src, k, labels, by, exclude, return_best, sync):
+        """The next labels of a source's rows: poi_score_topk_labels, or its score rows + poi_labels_scores."""
         k, labels, byc = self._labels_args(k, labels, by)
-        if not self._rank_fused:
-            a = self._id_list(start_end)
-            ids, lo = self._ids(a)
-            ex = self._near_exclusion(exclude, len(a), None, ids, lo, kinds=("train",))
-            return self._labels_from_scores(self._own_score_rows(a), len(a), ex, labels, byc, k, return_best, sync)
-        ids, users, lo = self._users_rows(start_end)
-        ex = self._near_exclusion(exclude, ids.numel(), None, ids, lo, kinds=("train",))
-        return self._labels_launch(users.contiguous(), self._items(), self._rank_term(ids, lo), ex, labels, byc, k, return_best, sync)
+        ex = src.exclusion(exclude)
+        if src.fused:
+            return self._labels_launch(src.users, src.items, src.tile_term(), ex, labels, byc, k, return_best, sync)
+        return self._labels_from_scores(src.score_rows(), src.n, ex, labels, byc, k, return_best, sync)
 
     def label_distribution(self, start_end, labels, exclude=None):
         """The whole label distribution (poi_score_labels): ((n, n_label) float64 probabilities that the next check-in falls in each
         label, (n) float64 share of the unlabelled POIs) - the rows sum to 1 with the rest (a row without candidates is all zero).
         Arguments as recommend_labels; synchronises for the rejected-row count."""
+        return self._serve_label_distribution(self._source(start_end), labels, exclude)
+
+    def _serve_label_distribution(self, src, labels, exclude):
+        """The dense label mass of a source's rows (poi_score_labels, or its score rows + poi_labels_scores) -> ((n, n_label) float64
+        probabilities, (n) unlabelled rest)."""
         _, labels, _ = self._labels_args(None, labels, "mass")
-        L = labels.n_label
-        if not self._rank_fused:
-            a = self._id_list(start_end)
-            n, N = len(a), self.n_item
-            ids, lo = self._ids(a)
-            ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-            score_rows = self._own_score_rows(a)
-
-            def call(mass):
-                for o, c in self._row_chunks(n):
-                    full = score_rows(o, c).contiguous()
-                    self.ctx.check(self.lib.poi_labels_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(labels.labels), L,
-                                                              ctypes.c_void_p(ex[0].data_ptr() + 4 * o) if ex[0] is not None else None, _ptr(ex[1]), 0, 0,
-                                                              ctypes.c_void_p(mass.data_ptr() + 8 * o * (L + 1)), None, None, None, None, None, None,
-                                                              None, None, None, None, None, self._stream()))
-            return self._labels_dense(n, L, call)
-        ids, users, lo = self._users_rows(start_end)
-        n = ids.numel()
-        ex = self._near_exclusion(exclude, n, None, ids, lo, kinds=("train",))
-        users, term = users.contiguous(), self._rank_term(ids, lo)
-
-        def call(mass):
-            if n:
-                self.ctx.check(self.lib.poi_score_labels(self.ctx.handle, *self._tile_operands(users, self._items(), self.kdim, term), _ptr(labels.labels),
-                                                         L, _ptr(ex[0]), _ptr(ex[1]), _ptr(mass), None, None, None, None, None, self._stream()))
-        return self._labels_dense(n, L, call)
+        n, N, L = src.n, self.n_item, labels.n_label
+        ex = src.exclusion(exclude)
+        mass = torch.zeros((n, L + 1), dtype=torch.int64, device=self.device)      # (uint64 below 2^63: the same bits)
+        if not src.fused:
+            score_rows = src.score_rows()
+            for o, c in self._row_chunks(n):
+                full = score_rows(o, c).contiguous()
+                self.ctx.check(self.lib.poi_labels_scores(self.ctx.handle, _ptr(full), c, N, N, _ptr(labels.labels), L, _at(ex[0], o, 1), _ptr(ex[1]), 0, 0,
+                                                          _at(mass, o, L + 1), None, None, None, None, None, None, None, None, None, None, None,
+                                                          self._stream()))
+        elif n:
+            self.ctx.check(self.lib.poi_score_labels(self.ctx.handle, *self._tile_operands(src.users, src.items, self.kdim, src.tile_term()),
+                                                     _ptr(labels.labels), L, _ptr(ex[0]), _ptr(ex[1]), _ptr(mass), None, None, None, None, None,
+                                                     self._stream()))
+        if n and self.ctx.take_bad_ids(self._stream().value):
+            raise IndexError("label_distribution: " + self._LABELS_BAD)
+        m = mass.double()
+        prob = m / m.sum(dim=1, keepdim=True).clamp(min=1.0)
+        return prob[:, :L].contiguous(), prob[:, L].contiguous()
 
 
     # ---- group recommendation (poi_group_topk / poi_group_topk_scores): the top-K of an aggregate of the members' scores ---------------
@@ -1447,7 +1505,7 @@ class _Base:
                 host = self._near_train_host = tuple(t.cpu().numpy() for t in self.train_exclusion())
             eo, ex = group_exclusion_csr(host[0], host[1], off, ids, self.n_item)      # (checks the lists on the host, device tensors included)
             i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
-            return i32(eo), (i32(ex) if len(ex) else torch.zeros(1, dtype=torch.int32, device=self.device))
+            return i32(eo), self._some_ids(i32(ex))
         return self._near_exclusion(exclude, n_grp, None, kinds=())
 
     def _group_out(self, idx, sc, cnt, return_scores, return_counts, sync):
@@ -1490,11 +1548,10 @@ class _Base:
             sub, ok = ids[lo_:hi_], valid[lo_:hi_]
             mem = np.full(hi_ - lo_, -1, np.int32)
             mem[ok] = np.searchsorted(a, sub[ok]).astype(np.int32)
-            g_off, g_mem = i32(off[g:g2 + 1] - off[g]), (i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=self.device))
+            g_off, g_mem = i32(off[g:g2 + 1] - off[g]), self._some_ids(i32(mem))
             eo = ex[0][g:g2 + 1].contiguous() if ex[0] is not None else None
-            at = lambda t, w: ctypes.c_void_p(t.data_ptr() + 4 * g * w) if t is not None else None
             self.ctx.check(self.lib.poi_group_topk_scores(self.ctx.handle, _ptr(full), len(a), self.n_item, _ptr(g_off), _ptr(g_mem), g2 - g, agg,
-                                                          _ptr(eo), _ptr(ex[1]), k, at(idx, k), at(sc, k), at(cnt, 1), self._stream()))
+                                                          _ptr(eo), _ptr(ex[1]), k, _at(idx, g, k), _at(sc, g, k), _at(cnt, g, 1), self._stream()))
             g = g2
         return self._group_out(idx, sc, cnt, return_scores, return_counts, sync)
 
@@ -1528,7 +1585,7 @@ class _Base:
             term = self._rank_term(uid, lo)
         else:                                            # no valid member anywhere: nothing is gathered, every group is empty or rejected
             users, term = torch.zeros((0, self.kdim), dtype=torch.float32, device=self.device), None
-        g_mem = i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=self.device)
+        g_mem = self._some_ids(i32(mem))
         return self._group_launch(users.contiguous(), self._items(), term, i32(off), g_mem, n_grp, agg, ex, k, return_scores, return_counts, sync)
 
 
@@ -1546,7 +1603,7 @@ class _Base:
             vo, us = visitors_csr(self._off_host, self.p.cpu().numpy(), self.n_item)
             self._audience_train_host = (vo, us)
             i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
-            t = self._audience_train = (i32(vo), i32(us) if len(us) else torch.zeros(1, dtype=torch.int32, device=self.device))
+            t = self._audience_train = (i32(vo), self._some_ids(i32(us)))
         return t
 
     def _audience_k(self, k, n, fused):
@@ -1582,7 +1639,7 @@ class _Base:
         """exclude -> (ex_off (n_q + 1), ex) int32 device tensors of ROW INDICES per query, or (None, None).  seg: the segment's ids
         (the lists are restricted to it and re-indexed), or None (row index = id)."""
         n_q = q.numel()
-        empty = lambda: torch.zeros(1, dtype=torch.int32, device=self.device)
+        empty = self._some_ids
         i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
         if exclude is None:
             return None, None
@@ -1634,8 +1691,7 @@ class _Base:
 
     def _audience_select(self, buf, c, n, ld, k, ex, o, idx, sc, cnt):
         """poi_topk_select over the (c, ld) score rows of queries o .. o + c - 1: there the rows are the queries, the "items" the n candidates."""
-        at = lambda t, w: ctypes.c_void_p(t.data_ptr() + 4 * o * w) if t is not None else None
-        self.ctx.check(self.lib.poi_topk_select(self.ctx.handle, _ptr(buf), c, n, ld, k, at(ex[0], 1), _ptr(ex[1]), at(idx, k), at(sc, k), at(cnt, 1),
+        self.ctx.check(self.lib.poi_topk_select(self.ctx.handle, _ptr(buf), c, n, ld, k, _at(ex[0], o, 1), _ptr(ex[1]), _at(idx, o, k), _at(sc, o, k), _at(cnt, o, 1),
                                                 self._stream()))
 
     def _audience_launch(self, users, items, kdim, term, q, ex, k, seg_dev, return_scores, return_counts, sync):
@@ -1808,7 +1864,7 @@ class _Base:
             no = np.concatenate(([0], np.cumsum(keep)))[off]
             i32 = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
             ids = p[keep]
-            t = self._similar_train_csr = (no, ids, i32(no), i32(ids) if len(ids) else torch.zeros(1, dtype=torch.int32, device=self.device))
+            t = self._similar_train_csr = (no, ids, i32(no), self._some_ids(i32(ids)))
         return t
 
     def nearest_visited(self, start_end, lists, histories="train", geo_weight=0.0, scale_km=1.0, return_sims=False, sync=True):
@@ -1848,7 +1904,7 @@ class _Base:
                 a = ids.cpu().numpy().astype(np.int64)
                 ln = off_h[a + 1] - off_h[a]
                 pos = np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln - off_h[a], ln)
-                h_off, h_ids = i32(np.concatenate(([0], np.cumsum(ln)))), (i32(ids_h[pos]) if len(pos) else torch.zeros(1, dtype=torch.int32, device=self.device))
+                h_off, h_ids = i32(np.concatenate(([0], np.cumsum(ln)))), self._some_ids(i32(ids_h[pos]))
         else:
             off, hid = histories
             if isinstance(off, torch.Tensor) and off.is_cuda and isinstance(hid, torch.Tensor) and hid.is_cuda:
@@ -1864,7 +1920,7 @@ class _Base:
             if h_off.numel() != n + 1:
                 raise ValueError("histories=(off, ids): off must hold n + 1 = %d offsets" % (n + 1))
             if not h_ids.numel():
-                h_ids = torch.zeros(1, dtype=torch.int32, device=self.device)
+                h_ids = self._some_ids()
         pos = torch.empty((n, k), dtype=torch.int32, device=self.device)
         sim = torch.empty((n, k), dtype=torch.float64, device=self.device) if return_sims else None
         if n:
@@ -1956,7 +2012,6 @@ class _Base:
         ex = self._diverse_host_exclusion(ex, n)
         kk = min(pool, N)
         ninf = float("-inf")
-        at = lambda t, o, w, b=4: ctypes.c_void_p(t.data_ptr() + b * o * w) if t is not None else None
         for o, c in self._row_chunks(n):
             full = score_rows(o, c)
             full = torch.where(torch.isfinite(full), full, torch.full_like(full, ninf))      # NaN and +-inf are never pooled
@@ -1975,8 +2030,8 @@ class _Base:
             ti[dead] = -1; ts[dead] = ninf
             pl[0][o:o + c] = -1; pl[1][o:o + c] = ninf
             pl[0][o:o + c, :kk] = ti; pl[1][o:o + c, :kk] = ts
-            self.ctx.check(self.lib.poi_diverse_rerank(self.ctx.handle, at(pl[0], o, pool), at(pl[1], o, pool), c, pool, _ptr(items), N, kdim, _ptr(coords),
-                                                       _ptr(cphi), k, trade, geo_weight, scale_km, at(idx, o, k), at(sc, o, k), None, at(obj, o, k, 8),
+            self.ctx.check(self.lib.poi_diverse_rerank(self.ctx.handle, _at(pl[0], o, pool), _at(pl[1], o, pool), c, pool, _ptr(items), N, kdim, _ptr(coords),
+                                                       _ptr(cphi), k, trade, geo_weight, scale_km, _at(idx, o, k), _at(sc, o, k), None, _at(obj, o, k),
                                                        self._stream()))
         return self._diverse_out(idx, sc, obj, pl, cnt, return_scores, return_objective, return_pool, return_counts, sync)
 
@@ -1993,23 +2048,22 @@ class _Base:
         No (n, n_item) matrix is built for the models that score by users . items; CA-RNN, PRME, POI2Vec and GeoIE under rule="geo" go
         through their own score rows, a bounded number at a time, poi_topk and poi_diverse_rerank.  Host arguments are checked before
         the launch (ValueError / IndexError)."""
+        return self._serve_diverse(self._source(start_end, ("train", "last")), k, pool, trade, geo_weight, scale_km, exclude, return_scores,
+                                   return_objective, return_pool, return_counts, sync)
+
+    def _serve_diverse(self, src, k, pool, trade, geo_weight, scale_km, exclude, return_scores, return_objective, return_pool, return_counts, sync):
+        """The diversified top-K of a source's rows: poi_diverse_topk, or its score rows + poi_topk + poi_diverse_rerank."""
         k, pool, trade, geo_weight, scale_km = self._diverse_args(k, pool, trade, geo_weight, scale_km)
         sim = self._diverse_sim(geo_weight, self._diverse_items() if geo_weight < 1.0 else None)
-        flags = (return_scores, return_objective, return_pool, return_counts, sync)
-        if not self._rank_fused:
-            a = self._id_list(start_end)
-            n = len(a)
-            ids, lo = self._ids(a)
-            anc = self._rows(self._last_train_poi(), ids, lo) if exclude == "last" else None
-            ex = self._near_exclusion(exclude, n, anc, ids, lo)
-            return self._diverse_from_scores(self._own_score_rows(a), n, ex, sim, k, pool, trade, geo_weight, scale_km, *flags)
-        ids, users, lo = self._users_rows(start_end)
-        n = ids.numel()
-        anc = self._rows(self._last_train_poi(), ids, lo) if exclude == "last" else None
-        ex = self._near_exclusion(exclude, n, anc, ids, lo)
-        if n == 0:
-            return self._diverse_out(*self._diverse_buffers(0, k, pool, True, True, True, True), *flags[:4], False)
-        return self._diverse_launch(users.contiguous(), self._items(), self.kdim, self._rank_term(ids, lo), ex, k, pool, trade, geo_weight, scale_km, *flags)
+        flags = (return_scores, return_objective, return_pool, return_counts)
+        ex = src.exclusion(exclude)
+        if not src.fused:
+            out = self._diverse_from_scores(src.score_rows(), src.n, ex, sim, k, pool, trade, geo_weight, scale_km, *flags, sync)
+        elif src.n == 0:
+            out = self._diverse_out(*self._diverse_buffers(0, k, pool, True, True, True, True), *flags, False)
+        else:
+            out = self._diverse_launch(src.users, src.items, src.kdim, src.tile_term(), ex, k, pool, trade, geo_weight, scale_km, *flags, sync)
+        return src.finish(out, return_scores, return_counts)
 
 
 # =================================================================================================
@@ -2853,32 +2907,37 @@ class Session:
             self._raise_bad()
 
     # ---- recommend ------------------------------------------------------------------------------
-    def _tile_rows(self, ids, clamp=False, pad=False):
-        """(users (n, kdim) float32, last POI rows (n), term) of the slots `ids` for the kernels that take _tile_operands: term = (wd,
-        sts rows, last POI rows) or None (not spatial).  A slot without a check-in (last POI -1) has no distance term: its sts row is
-        zero, and so is column n_dist ("too far") of every row.  The term's last POI rows are the slots' own - the kernels read -1 as
-        "no term" - unless `clamp`: rank.hip and poi_score_topk_geo clamp the row to POI 0 and rely on the zero sts row, so rank_of and
-        the unrestricted recommend hand over rows clamped to 0 (the sign of a zero score depends on it).  pad: the sts rows are padded
-        with zero rows to whole 32-row tiles (poi_score_topk_geo reads whole tiles)."""
+    # Every serving call below is "make the slots' ScoreSource, call the model's family function".  A CellSession of Lstm / Rnn ranks by
+    # the plain rule, as a session of the plain GRU does.  A CA-RNN CellSession ranks by its own score rows (CellSession._carnn_rows):
+    # a slot without a check-in has no scorable POI and gives -1 ids (NaN scores from recommend / rank_of, count 0, labels -1 with
+    # log-probability -inf, list scores -inf), and what needs users . items is refused (CellSession._refusals).
+    def _need_fused(self, family):
+        """Group, audience and route do not rank one score row per slot: they take users . items from the slots' fused source and
+        refuse a session whose rows are not fused before anything is looked at.  These sessions' rows always are; CellSession's may
+        not be."""
+
+    def _source(self, slots):
+        """The fused ScoreSource of the slots' CURRENT states: users = h as float32, the anchor = last_poi (-1: no check-in yet), and
+        - spatial - the distance term of the slots' sts rows.  tile_term: a slot without a check-in has no term - its sts row is zero,
+        and so is column n_dist ("too far") of every row; the last POI rows are the slots' own (the kernels read -1 as "no term")
+        unless clamped to 0.  near_term: the sts rows as they are; the kernels skip the term of an anchor -1 themselves."""
         m = self.m
+        ids = self._slot_tensor(slots)
+        n = ids.numel()
         users = self.h.index_select(0, ids).float().contiguous()
         lpr = self.last_poi.index_select(0, ids).contiguous()
-        if not self.spatial:
-            return users, lpr, None
-        n = ids.numel()
-        st = torch.zeros((((n + 31) // 32) * 32 if pad else n, self.nb), dtype=torch.float32, device=m.device)
-        st[:n] = self.sts.index_select(0, ids) * (lpr >= 0).float()[:, None]
-        st[:, m.n_dist] = 0.0
-        return users, lpr, (m.wd.t, st, lpr.clamp(min=0).contiguous() if clamp else lpr)
 
-    def _near_rows(self, ids):
-        """(users (n, kdim) float32, anchor = last POI rows (n), term) of the slots `ids` for the kernels that take _near_launch's term:
-        (wd, sts rows, thr, n_dist, dd in metres) or None (not spatial); the kernels skip the term of an anchor -1 themselves."""
-        m = self.m
-        users = self.h.index_select(0, ids).float().contiguous()
-        anc = self.last_poi.index_select(0, ids).contiguous()
-        term = (m.wd.t, self.sts.index_select(0, ids).contiguous(), m._binthr, m.n_dist, m.dd * 1000.0) if self.spatial else None
-        return users, anc, term
+        def tile_term(clamp, pad):
+            if not self.spatial:
+                return None
+            st = torch.zeros((((n + 31) // 32) * 32 if pad else n, self.nb), dtype=torch.float32, device=m.device)
+            st[:n] = self.sts.index_select(0, ids) * (lpr >= 0).float()[:, None]
+            st[:, m.n_dist] = 0.0
+            return m.wd.t, st, lpr.clamp(min=0).contiguous() if clamp else lpr
+
+        def near_term():
+            return (m.wd.t, self.sts.index_select(0, ids).contiguous(), m._binthr, m.n_dist, m.dd * 1000.0) if self.spatial else None
+        return ScoreSource(m, n, ("last",), lambda: lpr, None, users=users, items=m.trained_items.t, tile_term=tile_term, near_term=near_term)
 
     def recommend(self, slots, k, return_scores=False, within_km=None, exclude=None, return_counts=False, sync=True):
         """(n, k) int32 device indices by descending score, ties by ascending index: h . trained_items[:-1]^T, plus - spatial -
@@ -2886,19 +2945,19 @@ class Session:
         within_km / exclude / return_counts rank over restricted candidates instead (poi_score_topk_near, k <= 32): the POIs within
         within_km km of the slot's last_poi (a slot without a check-in ignores the radius), minus exclude = "last" (the last_poi) or CSR
         lists (off, ids); -1 ids where fewer than k candidates remain.  Plain models need set_coords() for a radius.  The defaults
-        keep the unrestricted path."""
+        keep the unrestricted path.  CA-RNN: compute_sub_all_scores' rule on the slots' CURRENT h and last_poi (explicit score rows,
+        <= 1 GiB at a time, + poi_topk, k <= 64); within_km / exclude / return_counts are not defined for its score rule and raise."""
         m = self.m
-        ids = self._slot_tensor(slots)
-        n, k = ids.numel(), int(k)
+        src = self._source(slots)
+        n, k = src.n, int(k)
         if within_km is not None or exclude is not None or return_counts:
-            users, anc, term = self._near_rows(ids)
-            ex = m._near_exclusion(exclude, n, anc, kinds=("last",))
-            return m._near_launch(users, m.trained_items.t, anc, m._near_radius(within_km), ex, term, k, return_scores, return_counts, sync)
-        users, _, term = self._tile_rows(ids, clamp=True, pad=True)
-        wd, st, lp = term or (None, None, None)
+            return m._serve_near(src, k, within_km, exclude, None, return_scores, return_counts, sync)
+        if not src.fused:
+            return src.finish(m._topk_from_rows(src.score_rows(), n, k, return_scores), return_scores, False, ranked=True)
+        users = src.users
+        wd, st, lp = src.tile_term(clamp=True, pad=True) or (None, None, None)
         if k <= 32:
-            idx = torch.empty((n, k), dtype=torch.int32, device=m.device)
-            sc = torch.empty((n, k), dtype=torch.float32, device=m.device) if return_scores else None
+            idx, sc, _ = m._topk_buffers(n, k, return_scores, False)
             if self.spatial:
                 m.ctx.check(m.lib.poi_score_topk_geo(m.ctx.handle, _ptr(users), _ptr(m.trained_items.t), n, m.n_item, m.kdim, _ptr(wd), _ptr(st),
                                                      _ptr(m.coords), _ptr(m._cphi), _ptr(m._binthr), _ptr(lp), m.n_dist, m.dd * 1000.0, k,
@@ -2924,133 +2983,92 @@ class Session:
                            sync=True):
         """model.compute_sub_topk_filtered over the slots' CURRENT states: the top-k (k <= 32) among the POIs that pass a predicate of
         `filt` (which: the predicate index of every slot, default predicate 0), the slot's last_poi as the anchor of the radius and of
-        the spatial distance term (a slot without a check-in has neither).  exclude: None, "last" or CSR lists (off, ids)."""
-        m = self.m
-        ids = self._slot_tensor(slots)
-        n = ids.numel()
-        k, pred, hint, pathc = m._filtered_args(k, filt, which, n, path)
-        users, anc, term = self._near_rows(ids)
-        ex = m._near_exclusion(exclude, n, anc, kinds=("last",))
-        return m._filtered_launch(users, m.trained_items.t, anc, m._near_radius(within_km), ex, term, filt, pred, hint, k, pathc, return_scores,
-                                  return_counts, sync)
+        the spatial distance term (a slot without a check-in has neither).  exclude: None, "last" or CSR lists (off, ids).  CA-RNN: its
+        own score rows + poi_topk_filtered_scores; within_km is not defined for its score rule."""
+        return self.m._serve_filtered(self._source(slots), k, filt, which, within_km, exclude, None, path, return_scores, return_counts, sync)
 
     def recommend_capped(self, slots, k, labels, per=1, filt=None, which=None, exclude=None, return_scores=False, return_labels=False,
                          return_counts=False, sync=True):
         """model.compute_sub_topk_capped over the slots' CURRENT states (h, sts, last_poi, as `candidates` assembles them): the top-k
         (k <= 32) with at most `per` POIs of one label of `labels` (a PoiLabels).  exclude: None, "last" or CSR lists (off, ids).  A
-        slot without a check-in has no distance term."""
-        m = self.m
-        ids = self._slot_tensor(slots)
-        n = ids.numel()
-        k, per, labels, pred, fill = m._capped_args(k, labels, per, filt, which, n)
-        users, lpr, term = self._tile_rows(ids)
-        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
-        return m._capped_launch(users, m.trained_items.t, term, ex, labels, per, fill, filt, pred, k, return_scores, return_labels, return_counts, sync)
+        slot without a check-in has no distance term.  CA-RNN: its own score rows + poi_topk_capped_scores."""
+        return self.m._serve_capped(self._source(slots), k, labels, per, filt, which, exclude, return_scores, return_labels, return_counts, sync)
 
     def recommend_labels(self, slots, k, labels, by="mass", exclude=None, return_best=False, sync=True):
         """model.recommend_labels over the slots' CURRENT states (h, sts, last_poi, as `candidates` assembles them): the k (<= 32) labels
         of `labels` (a PoiLabels) the next check-in most likely falls in, by softmax mass (by="mass") or by the label's best POI
         (by="max"), with their log-probabilities.  exclude: None, "last" or CSR lists (off, ids).  A slot without a check-in has no
-        distance term."""
-        m = self.m
-        ids = self._slot_tensor(slots)
-        k, labels, byc = m._labels_args(k, labels, by)
-        users, lpr, term = self._tile_rows(ids)
-        ex = m._near_exclusion(exclude, ids.numel(), lpr, kinds=("last",))
-        return m._labels_launch(users, m.trained_items.t, term, ex, labels, byc, k, return_best, sync)
+        distance term.  CA-RNN: its own score rows + poi_labels_scores."""
+        return self.m._serve_labels(self._source(slots), k, labels, by, exclude, return_best, sync)
 
     def rank_of(self, slots, pois, exclude=None, return_scores=False, return_counts=False, sync=True):
         """Exact 0-based rank of pois[i] (one POI per slot, or (n, len_t <= 8)) among all POIs under the slot's CURRENT state - the score
         rule of `recommend` (h . trained_items[:-1]^T, plus the spatial distance term at last_poi; none before the first check-in):
-        model.compute_sub_target_rank through the session's h / sts / last_poi.  exclude: None, "last" or CSR lists (off, ids)."""
-        m = self.m
-        ids = self._slot_tensor(slots)
-        n = ids.numel()
-        users, lpr, term = self._tile_rows(ids, clamp=True)
-        tgt, tm = m._rank_targets(pois.reshape(n, -1) if isinstance(pois, torch.Tensor) else np.asarray(pois).reshape(n, -1), n)
-        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
-        return m._rank_launch(users, m.trained_items.t, term, tgt, tm, ex, return_scores, return_counts, sync)
+        model.compute_sub_target_rank through the session's h / sts / last_poi.  exclude: None, "last" or CSR lists (off, ids).  CA-RNN
+        goes through its score rows and poi_rank_scores; a slot without a check-in gives rank -1 (NaN score, count 0)."""
+        src = self._source(slots)
+        pois = pois.reshape(src.n, -1) if isinstance(pois, torch.Tensor) else np.asarray(pois).reshape(src.n, -1)
+        return self.m._serve_rank(src, pois, exclude, return_scores, return_counts, sync)
 
     def candidates(self, slots, k, exclude=None, return_scores=False, return_counts=False, sync=True):
         """model.compute_sub_candidates over the slots' CURRENT states (h, sts, last_poi, as `rank_of` assembles them): the exact top-k
         of every slot for 1 <= k <= min(4096, n_item).  exclude: None, "last" or CSR lists (off, ids).  A slot without a check-in has no
-        distance term."""
-        m = self.m
-        k = m._candidates_k(k)
-        ids = self._slot_tensor(slots)
-        n = ids.numel()
-        users, lpr, term = self._tile_rows(ids)
-        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
-        return m._candidates_launch(users, m.trained_items.t, term, ex, k, return_scores, return_counts, sync)
+        distance term.  CA-RNN: its own score rows + poi_topk_select."""
+        return self.m._serve_candidates(self._source(slots), k, exclude, return_scores, return_counts, sync)
 
     def score_lists(self, slots, lists, sync=True):
         """model.score_lists over the slots' CURRENT states (h, sts, last_poi, as `candidates` assembles them): the scores of explicit
-        candidate lists.  A slot without a check-in has no distance term."""
-        m = self.m
-        ids = self._slot_tensor(slots)
-        users, _, term = self._tile_rows(ids)
-        return m._score_lists_launch(users, m.trained_items.t, term, m._rerank_lists_arg(lists, ids.numel()), sync)
+        candidate lists.  A slot without a check-in has no distance term.  CA-RNN: the listed columns of its own score rows."""
+        return self.m._serve_score_lists(self._source(slots), lists, sync)
 
     def rerank(self, slots, lists, k, prior=None, weights=(1.0, 0.0), return_scores=False, return_positions=False, return_counts=False, sync=True):
         """model.rerank over the slots' CURRENT states: every slot's candidate list scored under its state and returned in order
-        (k <= 4096; optionally blended with a prior)."""
-        m = self.m
-        ids = self._slot_tensor(slots)
-        n = ids.numel()
-        users, _, term = self._tile_rows(ids)
-        L = m._rerank_lists_arg(lists, n)
-        k, prior, w = m._rerank_args(L, n, k, prior, weights)
-        return m._rerank_launch(users, m.trained_items.t, term, L, k, prior, w, return_scores, return_positions, return_counts, sync)
+        (k <= 4096; optionally blended with a prior).  CA-RNN: its own score rows, a gather of the listed columns and
+        poi_rerank_lists."""
+        return self.m._serve_rerank(self._source(slots), lists, k, prior, weights, return_scores, return_positions, return_counts, sync)
+
+    def recommend_diverse(self, slots, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
+                          return_objective=False, return_pool=False, return_counts=False, sync=True):
+        """model.compute_sub_topk_diverse over the slots' CURRENT states (h, sts, last_poi, as `rank_of` assembles them): the `pool`
+        best POIs of every slot, re-ranked for relevance against redundancy.  exclude: None, "last" or CSR lists (off, ids).  A slot
+        without a check-in has no distance term.  CA-RNN: its own score rows, the exclusions masked, the pool from poi_topk, then
+        poi_diverse_rerank."""
+        return self.m._serve_diverse(self._source(slots), k, pool, trade, geo_weight, scale_km, exclude, return_scores, return_objective, return_pool,
+                                     return_counts, sync)
 
     def recommend_group(self, slot_groups, k, agg="mean", exclude=None, return_scores=False, return_counts=False, sync=True):
         """model.recommend_group over the slots' CURRENT states (h, sts, last_poi, as `rank_of` assembles them): slot_groups is a list of
         lists of slot ids or a CSR pair (off, ids); agg "mean" or "min"; exclude None or CSR lists (off, ids), one per group.  A slot
-        without a check-in has no distance term."""
+        without a check-in has no distance term.  CA-RNN ranks by a rule of its own and is refused."""
+        self._need_fused("group")
         m = self.m
         k, agg = m._group_args(k, agg)
         off, ids, on_device = m._group_csr(slot_groups, self.n_slot, "slot_groups")
         n_grp = len(off) - 1
         if n_grp == 0:
-            return m._group_out(torch.empty((0, k), dtype=torch.int32, device=m.device), torch.empty((0, k), dtype=torch.float32, device=m.device),
-                                torch.empty(0, dtype=torch.int32, device=m.device), return_scores, return_counts, False)
+            return m._group_out(*m._topk_buffers(0, k, True, True), return_scores, return_counts, False)
         ex = m._group_exclusion(exclude, off, ids, n_grp, kinds=())
         uniq, mem = m._group_members(ids, self.n_slot)
-        users, _, term = self._tile_rows(torch.as_tensor(uniq).to(m.device))
-        g_mem = self._i32(mem) if len(mem) else torch.zeros(1, dtype=torch.int32, device=m.device)
-        return m._group_launch(users, m.trained_items.t, term if len(uniq) else None, self._i32(off), g_mem, n_grp, agg, ex, k, return_scores,
-                               return_counts, sync)
+        src = self._source(torch.as_tensor(uniq).to(m.device))
+        return m._group_launch(src.users, src.items, src.tile_term() if len(uniq) else None, self._i32(off), m._some_ids(self._i32(mem)), n_grp, agg,
+                               ex, k, return_scores, return_counts, sync)
 
     def audience(self, pois, k, slots=None, exclude=None, return_scores=False, return_counts=False, sync=True):
         """model.recommend_audience over the slots' CURRENT states (h, sts, last_poi, as `candidates` assembles them): which live
         sessions should hear about this POI?  slots: None = every slot, or an ascending unique list of slot ids.  exclude: None or a
         CSR pair (off, ids) of slot ids per query.  Returns (n_q, k) int32 SLOT ids by descending score, ties by ascending id, -1 fill
-        [, scores][, candidate counts].  A slot without a check-in has no distance term."""
+        [, scores][, candidate counts].  A slot without a check-in has no distance term.  CA-RNN ranks by a rule of its own and is
+        refused."""
+        self._need_fused("audience")
         m = self.m
         seg = m._audience_segment(slots, self.n_slot, "slots")
         n = self.n_slot if seg is None else len(seg)
         k = m._audience_k(k, n, True)
         q = m._audience_queries(pois)
         ex = m._audience_exclusion(exclude, q, seg, self.n_slot, kinds=())
-        users, _, term = self._tile_rows(self._slot_tensor(seg))
-        return m._audience_launch(users, m.trained_items.t, m.kdim, term if n else None, q, ex, k, None if seg is None else self._i32(seg),
+        src = self._source(seg)
+        return m._audience_launch(src.users, src.items, m.kdim, src.tile_term() if n else None, q, ex, k, None if seg is None else self._i32(seg),
                                   return_scores, return_counts, sync)
-
-    def recommend_diverse(self, slots, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
-                          return_objective=False, return_pool=False, return_counts=False, sync=True):
-        """model.compute_sub_topk_diverse over the slots' CURRENT states (h, sts, last_poi, as `rank_of` assembles them): the `pool`
-        best POIs of every slot, re-ranked for relevance against redundancy.  exclude: None, "last" or CSR lists (off, ids).  A slot
-        without a check-in has no distance term."""
-        m = self.m
-        k, pool, trade, geo_weight, scale_km = m._diverse_args(k, pool, trade, geo_weight, scale_km)
-        items, kdim, _, _ = m._diverse_sim(geo_weight, m.trained_items.t if geo_weight < 1.0 else None)
-        ids = self._slot_tensor(slots)
-        n = ids.numel()
-        flags = (return_scores, return_objective, return_pool, return_counts)
-        if n == 0:
-            return m._diverse_out(*m._diverse_buffers(0, k, pool, True, True, True, True), *flags, False)
-        users, lpr, term = self._tile_rows(ids)
-        ex = m._near_exclusion(exclude, n, lpr, kinds=("last",))
-        return m._diverse_launch(users, m.trained_items.t, m.kdim, term, ex, k, pool, trade, geo_weight, scale_km, *flags, sync)
 
     # ---- routes ---------------------------------------------------------------------------------
     ROUTE_BEAM_MAX, ROUTE_STEPS_MAX = 8, 16
@@ -3102,7 +3120,9 @@ class Session:
         slot.  Returns paths (n, beam, steps) int32 and logp (n, beam) float64 device tensors, beams by descending logp (-1 / -inf: a
         dead beam - fewer candidates than beams); with return_step_scores also the per-step log-probabilities (n, beam, steps) float64.
         The session's own slots are only read (they may repeat): a route is a what-if.  The loop issues no host synchronisation;
-        sync=True raises IndexError at the end when a device exclusion list was malformed."""
+        sync=True raises IndexError at the end when a device exclusion list was malformed.  CA-RNN ranks by a rule of its own and is
+        refused."""
+        self._need_fused("route")
         m = self.m
         T, B = self._route_args(steps, beam)
         ids = self._slot_tensor(slots)
@@ -3115,7 +3135,7 @@ class Session:
             out = (paths.view(0, B, T), total.new_zeros((0, B)))
             return out + (slp.view(0, B, T),) if return_step_scores else out
         src = {k: getattr(self, k).index_select(0, ids) for k in self._ROUTE_STATE if getattr(self, k, None) is not None}
-        ex = m._near_exclusion(exclude, n, src["last_poi"].contiguous(), kinds=("last",))
+        ex = m._near_exclusion(exclude, n, src["last_poi"].contiguous(), kinds=("last",))      # (the rows are in hand: no source)
         scratch = type(self)(m, n_slot=n * B)
         all_rows = torch.arange(n * B, dtype=torch.int32, device=dev)
         base = torch.arange(n, device=dev)[:, None]
@@ -3247,13 +3267,12 @@ class CellSession(Session):
                                                        m._stream()))
 
     # ---- ranking: CA-RNN's own rule ---------------------------------------------------------------
-    def _carnn_rows(self, slots, exclude=None):
-        """(n, score_rows, has, ex) of the slots: score_rows(o, c) -> poi_carnn_score_all on the CURRENT h and last POI of slots
-        o .. o + c - 1, has (n) = the slot has a check-in, ex = the exclusion lists.  A slot without a check-in has no last POI: it is
-        scored at POI 0 and its row masked to -inf, so nothing of it is selectable."""
+    def _carnn_rows(self, slots):
+        """(n, score_rows, has, last POI rows) of the slots: score_rows(o, c) -> poi_carnn_score_all on the CURRENT h and last POI of
+        slots o .. o + c - 1, has (n) = the slot has a check-in.  A slot without a check-in has no last POI: it is scored at POI 0 and
+        its row masked to -inf, so nothing of it is selectable."""
         m = self.m
         ids = self._slot_tensor(slots)
-        n = ids.numel()
         users = self.h.index_select(0, ids).float().contiguous()
         lpr = self.last_poi.index_select(0, ids)
         lp, has = lpr.clamp(min=0).contiguous(), lpr >= 0
@@ -3264,153 +3283,30 @@ class CellSession(Session):
                                                   _ptr(m.coords), _ptr(m._cphi), _ptr(m._binthr), _ptr(lp[o:o + c]), c, m.n_item, m.n_dist, m.dim,
                                                   m.dd * 1000.0, _ptr(full), m._stream()))
             return torch.where(has[o:o + c, None], full, torch.full_like(full, float("-inf")))
-        return n, score_rows, has, m._near_exclusion(exclude, n, torch.where(has, lp, torch.full_like(lp, -1)), kinds=("last",))
+        return ids.numel(), score_rows, has, lpr
+
+    def _source(self, slots):
+        """Lstm / Rnn: Session's fused source (no sts, no distance term).  CA-RNN: its own score rows; what comes out for a slot
+        without a check-in is settled by ScoreSource.finish."""
+        if not self.carnn:
+            return super()._source(slots)
+        n, score_rows, has, lpr = self._carnn_rows(slots)
+        return ScoreSource(self.m, n, ("last",), lambda: lpr, self._refusals, score_rows=lambda positions=False: score_rows, has=has)
 
     @staticmethod
-    def _carnn_out(out, has, return_scores, return_counts, ranked=False):
-        """The no-check-in rule on a result ids-or-ranks[, scores][, ...][, counts] of _carnn_rows' rows: such a slot counts 0
-        candidates; `ranked` (recommend, rank_of: the kernel ranks the masked row all the same) also gives it -1 and a NaN score."""
-        out = list(out) if isinstance(out, tuple) else [out]
-        if ranked:
-            out[0] = torch.where(has[:, None], out[0], torch.full_like(out[0], -1))
-            if return_scores:
-                out[1] = torch.where(has[:, None], out[1], torch.full_like(out[1], float("nan")))
-        if return_counts:
-            out[-1] = torch.where(has, out[-1], torch.zeros_like(out[-1]))
-        return tuple(out) if len(out) > 1 else out[0]
+    def _refusals():
+        """What a call that needs users . items says to a CA-RNN session (ScoreSource.need_fused, _need_fused)."""
+        own = "OboCARNN ranks by a score rule of its own"
+        dot = own + ", not users . items: "
+        return {"near": own + ": within_km / exclude / return_counts are not supported on its sessions",
+                "filtered": own + ": within_km is not supported on its sessions",
+                "group": dot + "recommend_group is not supported on its sessions (model.recommend_group covers the trained users)",
+                "audience": dot + "audience is not supported on its sessions (model.recommend_audience covers the trained users)",
+                "route": dot + "recommend_route is not supported on its sessions"}
 
-    def recommend(self, slots, k, return_scores=False, within_km=None, exclude=None, return_counts=False, sync=True):
-        """(n, k) int32 device indices by descending score, ties by ascending index.  Lstm / Rnn: `Session.recommend`'s plain rule and
-        its restricted form.  CA-RNN: compute_sub_all_scores' rule on the slots' CURRENT h and last_poi (explicit score rows, <= 1 GiB
-        at a time, + poi_topk, k <= 64); a slot without a check-in gives -1 ids (NaN scores); within_km / exclude / return_counts are
-        not defined for its score rule and raise."""
-        if not self.carnn:
-            return super().recommend(slots, k, return_scores, within_km, exclude, return_counts, sync)
-        if within_km is not None or exclude is not None or return_counts:
-            raise _lib.PoiError("OboCARNN ranks by a score rule of its own: within_km / exclude / return_counts are not supported on its sessions")
-        n, score_rows, has, _ = self._carnn_rows(slots)
-        return self._carnn_out(self.m._topk_from_rows(score_rows, n, k, return_scores), has, return_scores, False, ranked=True)
-
-    def recommend_filtered(self, slots, k, filt, which=None, within_km=None, exclude=None, path="auto", return_scores=False, return_counts=False,
-                           sync=True):
-        """Lstm / Rnn: `Session.recommend_filtered`'s plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi +
-        poi_topk_filtered_scores; a slot without a check-in gives -1 ids (count 0); within_km is not defined for its score rule."""
-        if not self.carnn:
-            return super().recommend_filtered(slots, k, filt, which, within_km, exclude, path, return_scores, return_counts, sync)
-        m = self.m
-        if within_km is not None:
-            raise _lib.PoiError("OboCARNN ranks by a score rule of its own: within_km is not supported on its sessions")
-        ids = self._slot_tensor(slots)
-        k, pred, _, _ = m._filtered_args(k, filt, which, ids.numel(), path)
-        n, score_rows, has, ex = self._carnn_rows(ids, exclude)
-        return self._carnn_out(m._filtered_from_scores(score_rows, n, ex, filt, pred, k, return_scores, return_counts, sync), has, return_scores,
-                               return_counts)
-
-    def recommend_capped(self, slots, k, labels, per=1, filt=None, which=None, exclude=None, return_scores=False, return_labels=False,
-                         return_counts=False, sync=True):
-        """Lstm / Rnn: `Session.recommend_capped`'s plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi +
-        poi_topk_capped_scores; a slot without a check-in gives -1 ids (count 0)."""
-        if not self.carnn:
-            return super().recommend_capped(slots, k, labels, per, filt, which, exclude, return_scores, return_labels, return_counts, sync)
-        m = self.m
-        ids = self._slot_tensor(slots)
-        k, per, labels, pred, fill = m._capped_args(k, labels, per, filt, which, ids.numel())
-        n, score_rows, has, ex = self._carnn_rows(ids, exclude)
-        out = m._capped_from_scores(score_rows, n, ex, labels, per, fill, filt, pred, k, return_scores, return_labels, return_counts, sync)
-        return self._carnn_out(out, has, return_scores, return_counts)
-
-    def recommend_labels(self, slots, k, labels, by="mass", exclude=None, return_best=False, sync=True):
-        """Lstm / Rnn: `Session.recommend_labels`'s plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi +
-        poi_labels_scores; a slot without a check-in has no scorable POI: labels -1, log-probabilities -inf."""
-        if not self.carnn:
-            return super().recommend_labels(slots, k, labels, by, exclude, return_best, sync)
-        m = self.m
-        ids = self._slot_tensor(slots)
-        k, labels, byc = m._labels_args(k, labels, by)
-        n, score_rows, _, ex = self._carnn_rows(ids, exclude)
-        return m._labels_from_scores(score_rows, n, ex, labels, byc, k, return_best, sync)
-
-    def recommend_diverse(self, slots, k, pool=64, trade=0.7, geo_weight=1.0, scale_km=1.0, exclude=None, return_scores=False,
-                          return_objective=False, return_pool=False, return_counts=False, sync=True):
-        """Lstm / Rnn: `Session.recommend_diverse`'s plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi, the
-        exclusions masked, the pool from poi_topk, then poi_diverse_rerank; a slot without a check-in gives -1 ids (count 0)."""
-        if not self.carnn:
-            return super().recommend_diverse(slots, k, pool, trade, geo_weight, scale_km, exclude, return_scores, return_objective, return_pool,
-                                             return_counts, sync)
-        m = self.m
-        k, pool, trade, geo_weight, scale_km = m._diverse_args(k, pool, trade, geo_weight, scale_km)
-        sim = m._diverse_sim(geo_weight, m.trained_items.t if geo_weight < 1.0 else None)
-        n, score_rows, has, ex = self._carnn_rows(slots, exclude)
-        out = m._diverse_from_scores(score_rows, n, ex, sim, k, pool, trade, geo_weight, scale_km, return_scores, return_objective, return_pool,
-                                     return_counts, sync)
-        return self._carnn_out(out, has, return_scores, return_counts)
-
-    def candidates(self, slots, k, exclude=None, return_scores=False, return_counts=False, sync=True):
-        """Lstm / Rnn: `Session.candidates`' plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi +
-        poi_topk_select; a slot without a check-in gives -1 ids (count 0)."""
-        if not self.carnn:
-            return super().candidates(slots, k, exclude, return_scores, return_counts, sync)
-        m = self.m
-        k = m._candidates_k(k)
-        n, score_rows, has, ex = self._carnn_rows(slots, exclude)
-        return self._carnn_out(m._candidates_from_scores(score_rows, n, ex, k, return_scores, return_counts, sync), has, return_scores, return_counts)
-
-    def score_lists(self, slots, lists, sync=True):
-        """Lstm / Rnn: `Session.score_lists`' plain rule.  CA-RNN: the listed columns of its own score rows on the slots' CURRENT h and
-        last_poi; a slot without a check-in scores -inf everywhere."""
-        if not self.carnn:
-            return super().score_lists(slots, lists, sync)
-        m = self.m
-        n, score_rows, _, _ = self._carnn_rows(slots)
-        L = m._rerank_lists_arg(lists, n, host_check=True)
-        buf, numel = m._lists_from_rows(score_rows, n, L) if n else m._lists_scores_buffer(L, 0)
-        return m._lists_scores_out(buf, numel, L)
-
-    def rerank(self, slots, lists, k, prior=None, weights=(1.0, 0.0), return_scores=False, return_positions=False, return_counts=False, sync=True):
-        """Lstm / Rnn: `Session.rerank`'s plain rule.  CA-RNN: its own score rows on the slots' CURRENT h and last_poi, a gather of the
-        listed columns and poi_rerank_lists; a slot without a check-in gives -1 ids (count 0)."""
-        if not self.carnn:
-            return super().rerank(slots, lists, k, prior, weights, return_scores, return_positions, return_counts, sync)
-        m = self.m
-        n, score_rows, _, _ = self._carnn_rows(slots)
-        L = m._rerank_lists_arg(lists, n, host_check=True)
-        k, prior, w = m._rerank_args(L, n, k, prior, weights)
-        return m._rerank_from_scores(score_rows, n, L, k, prior, w, return_scores, return_positions, return_counts, sync)
-
-    def recommend_group(self, slot_groups, k, agg="mean", exclude=None, return_scores=False, return_counts=False, sync=True):
-        """Lstm / Rnn: `Session.recommend_group`'s plain rule.  CA-RNN ranks by a rule of its own and is refused."""
+    def _need_fused(self, family):
         if self.carnn:
-            raise _lib.PoiError("OboCARNN ranks by a score rule of its own, not users . items: recommend_group is not supported on its sessions "
-                                "(model.recommend_group covers the trained users)")
-        return super().recommend_group(slot_groups, k, agg, exclude, return_scores, return_counts, sync)
-
-    def audience(self, pois, k, slots=None, exclude=None, return_scores=False, return_counts=False, sync=True):
-        """Lstm / Rnn: `Session.audience`'s plain rule.  CA-RNN ranks by a rule of its own and is refused."""
-        if self.carnn:
-            raise _lib.PoiError("OboCARNN ranks by a score rule of its own, not users . items: audience is not supported on its sessions "
-                                "(model.recommend_audience covers the trained users)")
-        return super().audience(pois, k, slots, exclude, return_scores, return_counts, sync)
-
-    def recommend_route(self, slots, steps, beam=4, exclude="last", revisit=False, return_step_scores=False, sync=True):
-        """Lstm / Rnn: `Session.recommend_route` over the plain rule (the Lstm's c travels with h).  CA-RNN ranks by a rule of its own
-        and is refused."""
-        if self.carnn:
-            raise _lib.PoiError("OboCARNN ranks by a score rule of its own, not users . items: recommend_route is not supported on its sessions")
-        return super().recommend_route(slots, steps, beam, exclude, revisit, return_step_scores, sync)
-
-    def rank_of(self, slots, pois, exclude=None, return_scores=False, return_counts=False, sync=True):
-        """Exact 0-based rank of pois[i] (one POI per slot, or (n, len_t <= 8)) among all POIs under the slot's CURRENT state and the
-        score rule of `recommend`.  exclude: None, "last" or CSR lists (off, ids).  CA-RNN goes through its score rows and
-        poi_rank_scores; a slot without a check-in gives rank -1 (NaN score, count 0)."""
-        if not self.carnn:
-            return super().rank_of(slots, pois, exclude, return_scores, return_counts, sync)
-        m = self.m
-        ids = self._slot_tensor(slots)
-        n = ids.numel()
-        tgt, tm = m._rank_targets(pois.reshape(n, -1) if isinstance(pois, torch.Tensor) else np.asarray(pois).reshape(n, -1), n)
-        n, score_rows, has, ex = self._carnn_rows(ids, exclude)
-        return self._carnn_out(m._rank_from_scores(score_rows, n, tgt, tm, ex, return_scores, return_counts, sync), has, return_scores,
-                               return_counts, ranked=True)
+            raise _lib.PoiError(self._refusals()[family])
 
 
 # =================================================================================================
@@ -3953,9 +3849,6 @@ class OboFpmc_lr(_SeqFoldin, _Base):
                                                _ptr(idx), _ptr(sc), self._stream()))
         self._seed_end(seed, idx)
         return (idx, sc) if return_scores else idx
-
-    def _near_items(self):
-        return self._items()
 
     def _last_train_poi(self):
         return self.tra_last_poi
@@ -4603,7 +4496,7 @@ class OboGeoIE(_Base):
         keys, cnt = torch.unique((row * w + ids)[ids != self.n_item], return_counts=True)      # sorted: by row, then by id
         co = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
         co[1:] = torch.cumsum(torch.bincount(keys // w, minlength=n), 0)
-        pad = lambda t: t.int().contiguous() if t.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)
+        pad = lambda t: self._some_ids(t.int().contiguous())
         return co.int(), pad(keys % w), pad(cnt)
 
     def _geo_train_csr(self):
@@ -4957,7 +4850,7 @@ class OboPoi2vec(_Base):
             rc = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
             rc[1:] = torch.cumsum(has.long(), 0)
             flat = p[(o[1:] - 1).clamp(min=0)][has]
-            pad = flat.int().contiguous() if flat.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)
+            pad = self._some_ids(flat.int().contiguous())
             return rc.int(), pad
         rows = [np.asarray(c, np.int64).reshape(-1) for c in contexts]
         if len(rows) != n:
@@ -4990,7 +4883,7 @@ class OboPoi2vec(_Base):
             wc = w[o:o + c].contiguous()
             rcc = (rc[o:o + c + 1] - rc[o]).contiguous()
             fl = flat[int(rc[o]):] if o else flat
-            fl = fl if fl.numel() else torch.zeros(1, dtype=torch.int32, device=self.device)
+            fl = self._some_ids(fl)
             users = torch.arange(c, dtype=torch.int32, device=self.device)
             P = self._new_params(wc)
             self.ctx.check(self.lib.poi_poi2vec_scores(self.ctx.handle, ctypes.byref(P), _ptr(self.leaf_nodes), _ptr(users), c, 1, _ptr(rcc),

@@ -116,7 +116,8 @@ def test_declarations():
         assert len(proto.split(",")) == n_args, name
     for fn in ("compute_sub_topk_diverse", "_diverse_items"):
         assert hasattr(M._Base, fn)
-    assert hasattr(M.Session, "recommend_diverse") and M.CellSession.recommend_diverse is not M.Session.recommend_diverse
+    assert hasattr(M.Session, "recommend_diverse") and hasattr(M.CellSession, "recommend_diverse")
+    assert M.CellSession._source is not M.Session._source                # (CA-RNN's own score rows reach the call through its source)
     assert M.OboPrme._diverse_items(None) is None
 
 

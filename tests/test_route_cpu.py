@@ -70,7 +70,6 @@ def test_host_argument_checks():
     for steps, beam in ((4, 9), (4, 0), (17, 4), (0, 4), (-1, 4)):
         with pytest.raises(M._lib.PoiError):
             M.Session._route_args(steps, beam)
-    assert M.CellSession.recommend_route is not M.Session.recommend_route
     carnn = M.CellSession.__new__(M.CellSession)                        # (no device: the refusal comes before anything is touched)
     carnn.carnn = True
     with pytest.raises(M._lib.PoiError, match="OboCARNN"):
