@@ -570,15 +570,9 @@ int poi_score_rank(poi_ctx* c, const float* users, const float* items, int32_t n
   const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
   if ((rc = ensure(c, c->rank_ws, sizeof(poi::RankTgt) * (size_t)n_utile * 32 * RANK_LT_MAX, st))) return rc;
   A.tl = (poi::RankTgt*)c->rank_ws.p;
-  // item ranges per 32-row tile, one wave each: 8 waves per CU over the call, at least 8 tiles per range; "rank_grid" caps it; the 16-bit
-  // per-lane counters set the floor
-  int want = (c->num_cu * 8 + n_utile - 1) / n_utile;
-  if (want > ntile / 8) want = ntile / 8;
-  if (c->rank_grid > 0 && want > c->rank_grid) want = c->rank_grid;
-  if (want < 1) want = 1;
-  if (want < (ntile + RANK_TILES_MAX - 1) / RANK_TILES_MAX) want = (ntile + RANK_TILES_MAX - 1) / RANK_TILES_MAX;
-  A.n_split = want;
-  c->plan.valid = 1; c->plan.rank_splits = want;
+  // item ranges, one wave each (split_plan.h): "rank_grid" caps them, the 16-bit per-lane counters set the floor
+  A.n_split = plan_wave_ranges(n_utile, ntile, c->num_cu, c->rank_grid, RANK_TILES_MAX);
+  c->plan.valid = 1; c->plan.rank_splits = A.n_split;
   HIPCHK(c, poi::launch_rank(A, st, &c->tm));
   return POI_OK;
 }
@@ -643,13 +637,8 @@ static int select_run(poi_ctx* c, const float* scores, int n, int n_item, int64_
   return POI_OK;
 }
 
-static int score_rows_split(const poi_ctx* c, int n, int n_item) {
-  // item ranges per 32-row tile, one wave each: 8 waves per CU over the call, at least 8 tiles per range (poi_score_rank's rule)
-  const int n_utile = (n + 31) / 32, ntile = (n_item + 31) / 32;
-  int want = (c->num_cu * 8 + n_utile - 1) / n_utile;
-  if (want > ntile / 8) want = ntile / 8;
-  return want < 1 ? 1 : want;
-}
+// item ranges, one wave each: poi_score_rank's rule (split_plan.h) without its cap and floor
+static int score_rows_split(const poi_ctx* c, int n, int n_item) { return plan_wave_ranges((n + 31) / 32, (n_item + 31) / 32, c->num_cu, 0, 0); }
 
 int poi_score_rows(poi_ctx* c, const float* users, const float* items, int32_t n, int32_t n_item, int32_t dim, const float* wd, const float* sts,
                    const double* coords, const double* cphi, const double* thr, const int32_t* last_poi, int32_t n_dist, double dd,

@@ -5,7 +5,8 @@
 //              wd * sts[u][bin(last_poi[u], j)] for a row with a last POI
 //   C(q)     = [0, n) minus the query's exclusion list (ascending row indices);  the list is C(q) by descending s, ties by ascending row.
 //
-// audience_kernel is rank.hip's walk with the axes swapped.  A workgroup owns a block of 32 query POIs and one slice of the user range;
+// audience_kernel is the tile walk of tile_walk.h with the axes swapped (wave_tile_range over the USER tiles).  A workgroup owns a block
+// of 32 query POIs and one slice of the user range;
 // its four waves take a quarter of the slice each.  The queries' item rows are gathered once (b fragments in registers, a half table
 // through items_f16), their coordinates and cos(lat) too; the 32-row user tiles stream past as the a fragments.  In tile_product's
 // accumulator a lane then holds 16 user rows of ITS OWN query (item = lane & 31): a query's 32 candidates of a tile sit in the registers
@@ -28,7 +29,8 @@
 // the distance term; flops 2 * 32 * n * dim per query block on the f32 matrix pipe.
 #include "poi_common.h"
 #include "poi_kernels.h"
-#include "tile_product.h"
+#include "launch_common.h"
+#include "tile_walk.h"
 #include "topk_list.h"
 #include <limits.h>
 
@@ -75,9 +77,8 @@ __global__ __launch_bounds__(POI_BLOCK) void audience_kernel(AudienceArgs A) {
     for (int i = tid; i < A.n_dist; i += POI_BLOCK) s_thr[i] = A.thr[i];
   __syncthreads();
 
-  const int ntile = (n + 31) / 32;
-  const int t0 = (int)((long long)ntile * sl / S), t1 = (int)((long long)ntile * (sl + 1) / S);
-  const int tb = t0 + (int)((long long)(t1 - t0) * w / POI_NWAVE), te = t0 + (int)((long long)(t1 - t0) * (w + 1) / POI_NWAVE);
+  int ntile, tb, te;
+  wave_tile_range(n, sl, S, w, ntile, tb, te);
   const float wd = GEO ? A.wd[0] : 0.f;
   const int myq = s_q[li];
   const bool qlive = myq >= 0;
@@ -126,6 +127,7 @@ __global__ __launch_bounds__(POI_BLOCK) void audience_kernel(AudienceArgs A) {
         n_lat = A.coords[2 * (size_t)lc]; n_lon = A.coords[2 * (size_t)lc + 1]; n_cp = A.cphi[lc];
         lp_n2 = row_lp(tile + 2);
       }
+      // (tile_walk.h: the walk's contract - not met here, the mask branch stands behind the product: DESIGN.md section 1)
       const f32x16 acc = tile_product<D8>(a0, bf);
       // one buffer: the next tile's rows are requested as soon as the product has read this tile's, behind them the whole epilogue
       if constexpr (!DB) { if (tile + 1 < te) load_frag<D8>(a0, A.users, 0, (size_t)min((tile + 1) * 32 + li, n - 1), D, h); }
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(POI_BLOCK) void audience_kernel(AudienceArgs A) {
       unsigned cm = 0u;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ul = (r & 3) + 8 * (r >> 2) + 4 * h, u = tile * 32 + ul;
+        const int ul = acc_tile_row(r, 4 * h), u = tile * 32 + ul;
         float s = acc[r];
         if (GEO) {
           if (s_has[w][ul]) s = __fmaf_rn(wd, geo_prob(A, s_thr, u, s_ulat[w][ul], s_ulon[w][ul], s_ucp[w][ul], jlat, jlon, jcp), s);
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(POI_BLOCK) void audience_kernel(AudienceArgs A) {
       }
       if (ROWS) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) s_sc[w][((r & 3) + 8 * (r >> 2) + 4 * h) * AUD_LD + li] = sv[r];
+        for (int r = 0; r < 16; ++r) s_sc[w][acc_tile_row(r, 4 * h) * AUD_LD + li] = sv[r];
         wave_fence();
         const int u = tile * 32 + li;
 #pragma unroll
@@ -179,7 +181,7 @@ __global__ __launch_bounds__(POI_BLOCK) void audience_kernel(AudienceArgs A) {
         const unsigned long long offers = __ballot(cm != 0u);
         if (offers) {                               // (wave-uniform; rare once the lists have warmed up)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) s_sc[w][((r & 3) + 8 * (r >> 2) + 4 * h) * AUD_LD + li] = sv[r];
+          for (int r = 0; r < 16; ++r) s_sc[w][acc_tile_row(r, 4 * h) * AUD_LD + li] = sv[r];
           wave_fence();
           unsigned qs = (unsigned)(offers | (offers >> 32));
           const int u = tile * 32 + li;
@@ -224,21 +226,14 @@ __global__ __launch_bounds__(POI_BLOCK) void audience_kernel(AudienceArgs A) {
   }
 }
 
-template <int D8, bool DB, bool GEO, bool ROWS>
-static void launch_audience_t(const AudienceArgs& A, hipStream_t st) {
-  const unsigned n_qblock = (unsigned)((A.n_q + 31) / 32);
-  const size_t lds = GEO ? sizeof(double) * A.n_dist : 0;
-  hipLaunchKernelGGL((audience_kernel<D8, DB, GEO, ROWS>), dim3(n_qblock * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
-}
-
 template <bool GEO, bool ROWS>
 static hipError_t launch_audience_g(const AudienceArgs& A, hipStream_t st) {
-  if (A.dim <= 32) launch_audience_t<4, true, GEO, ROWS>(A, st);
-  else if (A.dim <= 64) launch_audience_t<8, true, GEO, ROWS>(A, st);
-  else if (A.dim <= 128) launch_audience_t<16, false, GEO, ROWS>(A, st);
-  else if (A.dim <= 256) launch_audience_t<32, false, GEO, ROWS>(A, st);
-  else return hipErrorInvalidValue;
-  return hipSuccess;
+  return by_dim<64>(A.dim, [&](auto d8, auto db) -> hipError_t {
+    const unsigned n_qblock = (unsigned)((A.n_q + 31) / 32);
+    const size_t lds = GEO ? sizeof(double) * A.n_dist : 0;
+    hipLaunchKernelGGL((audience_kernel<decltype(d8)::value, decltype(db)::value, GEO, ROWS>), dim3(n_qblock * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
+    return hipSuccess;
+  });
 }
 
 hipError_t launch_audience(const AudienceArgs& A, hipStream_t st, Timing* tm) {
@@ -246,7 +241,7 @@ hipError_t launch_audience(const AudienceArgs& A, hipStream_t st, Timing* tm) {
   tm->begin("audience_walk", st);
   const hipError_t e = A.wd ? launch_audience_g<true, false>(A, st) : launch_audience_g<false, false>(A, st);
   tm->end(st);
-  if (e != hipSuccess) return e;
+  if (e != hipSuccess) { tm->span_end(span, st); return e; }
   if (A.part_s) {
     tm->begin("audience_merge", st);
     launch_topk_slices_merge(slice_lists(A), AUDIENCE_K_MAX, A.n_q, st);
@@ -257,11 +252,10 @@ hipError_t launch_audience(const AudienceArgs& A, hipStream_t st, Timing* tm) {
 }
 
 hipError_t launch_audience_rows(const AudienceArgs& A, hipStream_t st, Timing* tm) {
-  tm->begin("audience_rows", st);
+  Timing::Scope rec(tm, "audience_rows", st);
   const hipError_t e = A.wd ? launch_audience_g<true, true>(A, st) : launch_audience_g<false, true>(A, st);
   if (e != hipSuccess) return e;
-  tm->end(st);
-  return hipGetLastError();
+  return rec.close();
 }
 
 }  // namespace poi

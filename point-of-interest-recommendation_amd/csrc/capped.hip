@@ -28,17 +28,18 @@
 // labels_hist_kernel / labels_fill_kernel: per predicate the histogram of the passing POIs' labels (integer atomics) and from it
 // fill[q][m] = #(unlabelled passing POIs) + sum over labels of min(m, #passing POIs of the label), m = 0 .. 32.
 //
-// capped_walk_kernel: filter_walk_kernel's tile walk (a workgroup owns a 32-row tile and an item slice, its waves a quarter of the
-// slice each, A fragments in registers, one bitmap word per row and tile fetched two tiles ahead, zero-word tiles skipped) with lists
-// of 32 entries that carry the label beside score and id.  capped_slices_merge_kernel folds the slices' lists of the split regime in
+// capped_walk_kernel: the item-stationary tile walk in tile_walk.h's steps (wave_tile_range: a workgroup owns a 32-row tile and an item
+// slice, its waves a quarter of the slice each; load_row_tile / load_item_tile; the distance term through geo_add; the rare part row
+// by row through rare_row / acc_row) with filter.hip's bitmap pipeline (one word per row and tile fetched two tiles ahead, zero-word
+// tiles skipped) and lists of 32 entries that carry the label beside score and id.  capped_slices_merge_kernel folds the slices' lists of the split regime in
 // slice order.  capped_scores_kernel applies the definition to explicit float32 score rows, one workgroup per row.
 //
 // No float atomics; the same bits on every grid, in both regimes, a row alone or among thousands.
 #include "poi_common.h"
 #include "poi_kernels.h"
-#include "tile_product.h"
+#include "launch_common.h"
+#include "tile_walk.h"
 #include "topk_list.h"
-#include "walk_common.h"
 
 namespace poi {
 
@@ -226,7 +227,7 @@ __global__ __launch_bounds__(POI_BLOCK) void capped_walk_kernel(CappedArgs A) {
   double* const s_thr = reinterpret_cast<double*>(s_dyn + CAP_LISTS_BYTES);
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id(), li = lane & 31, h = lane >> 5;
   const int S = A.n_split, ut = blockIdx.x / S, sl = blockIdx.x - ut * S;
-  const int D = A.dim, N = A.n_item, per = A.per;
+  const int N = A.n_item, per = A.per;
 
   // the tile's rows: predicate index and anchor in range, exclusion lists with offsets in order and ids ascending inside [0, N)
   for (int i = w; i < 32; i += POI_NWAVE) {
@@ -252,9 +253,8 @@ __global__ __launch_bounds__(POI_BLOCK) void capped_walk_kernel(CappedArgs A) {
   for (int e = tid; e < POI_NWAVE * 32 * CAP_LIST; e += POI_BLOCK) { l_s[e] = neg_inf(); l_i[e] = PAD_ID; l_l[e] = -1; }
   __syncthreads();
 
-  const int ntile = (N + 31) / 32;
-  const int t0 = (int)((long long)ntile * sl / S), t1 = (int)((long long)ntile * (sl + 1) / S);
-  const int tb = t0 + (int)((long long)(t1 - t0) * w / POI_NWAVE), te = t0 + (int)((long long)(t1 - t0) * (w + 1) / POI_NWAVE);
+  int ntile, tb, te;
+  wave_tile_range(N, sl, S, w, ntile, tb, te);
   const float wd = GEO ? A.wd[0] : 0.f;
   float* const ls = l_s + w * 32 * CAP_LIST;
   int* const lx = l_i + w * 32 * CAP_LIST;
@@ -272,16 +272,16 @@ __global__ __launch_bounds__(POI_BLOCK) void capped_walk_kernel(CappedArgs A) {
   };
 
   float4 af[D8];
-  load_frag<D8>(af, A.users, 0, (size_t)min(ut * 32 + li, A.n - 1), D, h);
+  load_row_tile<D8>(af, A, ut, li, h);
   float4 b0[D8], b1[DB ? D8 : 1];
   unsigned w0 = word(tb), w1 = word(tb + 1);
   bool live = __ballot(w0 != 0u) != 0ull;           // (wave-uniform) some row of the tile wants this item tile
-  if (live) load_frag<D8>(b0, A.items, A.items_f16, (size_t)min(tb * 32 + li, N - 1), D, h);
+  if (live) load_item_tile<D8>(b0, A, tb, li, h);
   int pc = 0;                                       // passing POIs of row li in this wave's tiles
   for (int tile = tb; tile < te; ++tile) {
     const unsigned w2 = word(tile + 2);
     const bool live1 = __ballot(w1 != 0u) != 0ull;
-    if constexpr (DB) { if (live1) load_frag<D8>(b1, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h); }
+    if constexpr (DB) { if (live1) load_item_tile<D8>(b1, A, tile + 1, li, h); }
     pc += __popc(w0);
     if (live) {
       const int j = tile * 32 + li;
@@ -289,20 +289,18 @@ __global__ __launch_bounds__(POI_BLOCK) void capped_walk_kernel(CappedArgs A) {
       __builtin_amdgcn_wave_barrier();
       s_word[w][li] = w0;
       __builtin_amdgcn_wave_barrier();              // (a wave's LDS accesses complete in order: the reads below see it)
-      f32x16 acc = tile_product<D8>(af, b0);
-      double jlat = 0.0, jlon = 0.0, jcp = 0.0;
-      if (GEO) { const int jc = min(j, N - 1); jlat = A.coords[2 * (size_t)jc]; jlon = A.coords[2 * (size_t)jc + 1]; jcp = A.cphi[jc]; }
-      // the half wave's row base, opaque per tile (rank.hip: otherwise the loop-invariant LDS reads of the 16 rows are hoisted)
-      int hb = 4 * h;
-      asm volatile("" : "+v"(hb));
+      f32x16 acc = tile_product<D8>(af, b0);       // (tile_walk.h: the walk's contract)
+      double jlat, jlon, jcp;
+      item_tile_coords<GEO>(A, j, jlat, jlon, jcp);
+      const int hb = opaque_half_base(h);
       unsigned cm = 0u;                             // bit r: acc[r] passes and beats the gate entry of its row's list
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ul = (r & 3) + 8 * (r >> 2) + hb;
+        const int ul = acc_tile_row(r, hb);
         const bool bit = (s_word[w][ul] >> li) & 1u;
         float s = acc[r];
         if (GEO) {
-          if (bit && s_has[ul]) s = __fmaf_rn(wd, geo_prob(A, s_thr, min(ut * 32 + ul, A.n - 1), s_ulat[ul], s_ulon[ul], s_ucp[ul], jlat, jlon, jcp), s);
+          if (bit && s_has[ul]) s = geo_add(A, wd, s_thr, ut, ul, s_ulat, s_ulon, s_ucp, jlat, jlon, jcp, s);
         }
         s = one_zero(s);
         acc[r] = s;
@@ -313,12 +311,10 @@ __global__ __launch_bounds__(POI_BLOCK) void capped_walk_kernel(CappedArgs A) {
       if (__ballot(cm != 0u)) {
         // the rare part: row by row, the exclusion lookup and the cap-aware insertions
         for (int row = 0; row < 32; ++row) {
-          const int rr = (row & 3) + 4 * (row >> 3), hh = (row >> 2) & 1;
-          bool cand = h == hh && ((cm >> rr) & 1u);
+          int rr;
+          bool cand = rare_row(row, h, cm, rr);
           if (!__ballot(cand)) continue;            // (wave-uniform)
-          float v = acc[0];
-#pragma unroll
-          for (int r = 1; r < 16; ++r) v = rr == r ? acc[r] : v;
+          const float v = acc_row(acc, rr);
           const int e0 = s_e0[row], e1 = s_e1[row];
           if (cand && e1 > e0) cand = !listed(A.ex, e0, e1, j);
           const unsigned long long bal = __ballot(cand);
@@ -342,7 +338,7 @@ __global__ __launch_bounds__(POI_BLOCK) void capped_walk_kernel(CappedArgs A) {
         for (int m = 0; m < D8; ++m) b0[m] = b1[m];
       }
     } else {
-      if (live1) load_frag<D8>(b0, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h);
+      if (live1) load_item_tile<D8>(b0, A, tile + 1, li, h);
     }
     w0 = w1; w1 = w2; live = live1;
   }
@@ -403,7 +399,7 @@ __global__ __launch_bounds__(64) void capped_slices_merge_kernel(CappedArgs A) {
 }
 
 hipError_t launch_labels_build(const LabelsBuildArgs& A, hipStream_t st, Timing* tm) {
-  tm->begin("labels_build", st);
+  Timing::Scope rec(tm, "labels_build", st);
   const int rows = A.n_pred > 0 ? A.n_pred : 1;
   hipError_t e = hipMemsetAsync(A.hist, 0, sizeof(int) * ((size_t)rows * A.n_label + rows), st);      // (unl lies right behind hist)
   if (e != hipSuccess) return e;
@@ -411,8 +407,7 @@ hipError_t launch_labels_build(const LabelsBuildArgs& A, hipStream_t st, Timing*
   const long long rounds = ((long long)A.n_item + POI_BLOCK - 1) / POI_BLOCK;
   hipLaunchKernelGGL(labels_hist_kernel, dim3((unsigned)(rounds < 1024 ? rounds : 1024), (unsigned)rows), dim3(POI_BLOCK), 0, st, A);
   hipLaunchKernelGGL(labels_fill_kernel, dim3((unsigned)rows), dim3(POI_BLOCK), 0, st, A);
-  tm->end(st);
-  return hipGetLastError();
+  return rec.close();
 }
 
 hipError_t launch_capped_scores(const CappedScoresArgs& A, hipStream_t st, Timing* tm) {
@@ -422,27 +417,17 @@ hipError_t launch_capped_scores(const CappedScoresArgs& A, hipStream_t st, Timin
   return hipGetLastError();
 }
 
-template <int D8, bool DB, bool GEO>
-static hipError_t launch_walk_t(const CappedArgs& A, hipStream_t st) {
-  static DeviceOnce once;      // the LDS opt-in is a per-device attribute of the function
-  const hipError_t oe = once.run([&]() -> hipError_t {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&capped_walk_kernel<D8, DB, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               CAP_LISTS_BYTES + (int)sizeof(double) * CAPPED_NDIST_MAX);
-  });
-  if (oe != hipSuccess) return oe;
-  const unsigned n_utile = (unsigned)((A.n + 31) / 32);
-  const size_t lds = CAP_LISTS_BYTES + (GEO ? sizeof(double) * A.n_dist : 0);
-  hipLaunchKernelGGL((capped_walk_kernel<D8, DB, GEO>), dim3(n_utile * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
-  return hipGetLastError();
-}
-
 template <bool GEO>
 static hipError_t launch_walk_g(const CappedArgs& A, hipStream_t st) {
-  if (A.dim <= 32) return launch_walk_t<4, true, GEO>(A, st);
-  if (A.dim <= 64) return launch_walk_t<8, true, GEO>(A, st);
-  if (A.dim <= 128) return launch_walk_t<16, false, GEO>(A, st);
-  if (A.dim <= 256) return launch_walk_t<32, false, GEO>(A, st);
-  return hipErrorInvalidValue;
+  return by_dim<64>(A.dim, [&](auto d8, auto db) -> hipError_t {
+    constexpr auto kernel = &capped_walk_kernel<decltype(d8)::value, decltype(db)::value, GEO>;
+    const hipError_t oe = lds_opt_in<kernel>(CAP_LISTS_BYTES + (int)sizeof(double) * CAPPED_NDIST_MAX);
+    if (oe != hipSuccess) return oe;
+    const unsigned n_utile = (unsigned)((A.n + 31) / 32);
+    const size_t lds = CAP_LISTS_BYTES + (GEO ? sizeof(double) * A.n_dist : 0);
+    hipLaunchKernelGGL(kernel, dim3(n_utile * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_capped_walk(const CappedArgs& A, hipStream_t st, Timing* tm) {

@@ -8,7 +8,8 @@
 //   P(r)     = the best min(pool, |selectable C(r)|) candidates by better() (descending score, ascending id).  NaN, -inf and +inf scores
 //              are never pooled (+inf is pooled by poi_score_topk: stage 2 normalises the scores, so it must stay out here).
 // diverse_pool_kernel: a workgroup owns a 32-row tile and one slice of the item range, its four waves a quarter of the slice each - the
-// walk of rank.hip / group.hip: the rows' A fragments in registers, the slice's 32-item tiles streamed past them on the f32 matrix pipe,
+// item-stationary tile walk in tile_walk.h's steps: the rows' A fragments in registers, the slice's 32-item tiles streamed past them on
+// the f32 matrix pipe,
 // the distance term added in the accumulator registers.  Every wave keeps one sorted 64-entry list per row in LDS (topk_list.h).  Per tile
 // each of the lane's 16 scores is compared with the K-th entry of its row's list (LDS broadcast reads, one ballot for the common
 // tile); only the survivors are looked up in the exclusion list and inserted, a row at a time: a few by single insertion (the entries
@@ -37,7 +38,8 @@
 #include "poi_common.h"
 #include "poi_kernels.h"
 #include "pair_sim.h"
-#include "tile_product.h"
+#include "launch_common.h"
+#include "tile_walk.h"
 #include "topk_list.h"
 
 namespace poi {
@@ -61,7 +63,7 @@ __global__ __launch_bounds__(POI_BLOCK) void diverse_pool_kernel(DiverseArgs A) 
   double* const s_thr = reinterpret_cast<double*>(s_dyn + POOL_LISTS_BYTES);
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id(), li = lane & 31, h = lane >> 5;
   const int S = A.n_split, ut = blockIdx.x / S, sl = blockIdx.x - ut * S;
-  const int D = A.dim, N = A.n_item, K = A.k;
+  const int N = A.n_item, K = A.k;
 
   // the tile's rows: exclusion lists with offsets in order, ids ascending inside [0, N)
   for (int i = w; i < 32; i += POI_NWAVE) {
@@ -80,37 +82,34 @@ __global__ __launch_bounds__(POI_BLOCK) void diverse_pool_kernel(DiverseArgs A) 
   for (int e = tid; e < POI_NWAVE * 32 * DIVERSE_POOL_MAX; e += POI_BLOCK) { l_s[e] = neg_inf(); l_i[e] = PAD_ID; }
   __syncthreads();
 
-  const int ntile = (N + 31) / 32;
-  const int t0 = (int)((long long)ntile * sl / S), t1 = (int)((long long)ntile * (sl + 1) / S);
-  const int tb = t0 + (int)((long long)(t1 - t0) * w / POI_NWAVE), te = t0 + (int)((long long)(t1 - t0) * (w + 1) / POI_NWAVE);
+  int ntile, tb, te;
+  wave_tile_range(N, sl, S, w, ntile, tb, te);
   const float wd = GEO ? A.wd[0] : 0.f;
   float* const ls = l_s + w * 32 * DIVERSE_POOL_MAX;
   int* const lx = l_i + w * 32 * DIVERSE_POOL_MAX;
 
   unsigned rok = 0u;                                // the lane's 16 accumulator rows that are ranked
 #pragma unroll
-  for (int r = 0; r < 16; ++r) rok |= s_ok[(r & 3) + 8 * (r >> 2) + 4 * h] ? 1u << r : 0u;
+  for (int r = 0; r < 16; ++r) rok |= s_ok[acc_tile_row(r, 4 * h)] ? 1u << r : 0u;
 
   float4 af[D8];
-  load_frag<D8>(af, A.users, 0, (size_t)min(ut * 32 + li, A.n - 1), D, h);
+  load_row_tile<D8>(af, A, ut, li, h);
   float4 b0[D8], b1[DB ? D8 : 1];
-  load_frag<D8>(b0, A.items, A.items_f16, (size_t)min(tb * 32 + li, N - 1), D, h);
+  load_item_tile<D8>(b0, A, tb, li, h);
   for (int tile = tb; tile < te; ++tile) {
-    if constexpr (DB) { if (tile + 1 < te) load_frag<D8>(b1, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h); }
-    f32x16 acc = tile_product<D8>(af, b0);
+    if constexpr (DB) { if (tile + 1 < te) load_item_tile<D8>(b1, A, tile + 1, li, h); }
+    f32x16 acc = tile_product<D8>(af, b0);         // (tile_walk.h: the walk's contract)
     const int j = tile * 32 + li;
-    double jlat = 0.0, jlon = 0.0, jcp = 0.0;
-    if (GEO) { const int jc = min(j, N - 1); jlat = A.coords[2 * (size_t)jc]; jlon = A.coords[2 * (size_t)jc + 1]; jcp = A.cphi[jc]; }
-    // the half wave's row base, opaque per tile (rank.hip: otherwise the loop-invariant LDS reads of the 16 rows are hoisted - 100+ registers)
-    int hb = 4 * h;
-    asm volatile("" : "+v"(hb));
+    double jlat, jlon, jcp;
+    item_tile_coords<GEO>(A, j, jlat, jlon, jcp);
+    const int hb = opaque_half_base(h);
     unsigned cm = 0u;                               // bit r: acc[r] beats the K-th entry of its row's list
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int ul = (r & 3) + 8 * (r >> 2) + hb;
+      const int ul = acc_tile_row(r, hb);
       float s = acc[r];
       if (GEO) {
-        if (s_has[ul]) s = __fmaf_rn(wd, geo_prob(A, s_thr, min(ut * 32 + ul, A.n - 1), s_ulat[ul], s_ulon[ul], s_ucp[ul], jlat, jlon, jcp), s);
+        if (s_has[ul]) s = geo_add(A, wd, s_thr, ut, ul, s_ulat, s_ulon, s_ucp, jlat, jlon, jcp, s);
         acc[r] = s;
       }
       if (finite_f(s) && better(s, j, ls[ul * DIVERSE_POOL_MAX + K - 1], lx[ul * DIVERSE_POOL_MAX + K - 1])) cm |= 1u << r;
@@ -120,12 +119,10 @@ __global__ __launch_bounds__(POI_BLOCK) void diverse_pool_kernel(DiverseArgs A) 
     if (__ballot(cm != 0u)) {
       // the rare part: row by row, the exclusion lookup and the insertions
       for (int row = 0; row < 32; ++row) {
-        const int rr = (row & 3) + 4 * (row >> 3), hh = (row >> 2) & 1;
-        bool cand = h == hh && ((cm >> rr) & 1u);
+        int rr;
+        bool cand = rare_row(row, h, cm, rr);
         if (!__ballot(cand)) continue;              // (wave-uniform)
-        float v = acc[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) v = rr == r ? acc[r] : v;
+        const float v = acc_row(acc, rr);
         const int e0 = s_e0[row], e1 = s_e1[row];
         if (cand && e1 > e0) cand = !listed(A.ex, e0, e1, j);
         const unsigned long long bal = __ballot(cand);
@@ -136,7 +133,7 @@ __global__ __launch_bounds__(POI_BLOCK) void diverse_pool_kernel(DiverseArgs A) 
 #pragma unroll
       for (int m = 0; m < D8; ++m) b0[m] = b1[m];
     } else {
-      if (tile + 1 < te) load_frag<D8>(b0, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h);
+      if (tile + 1 < te) load_item_tile<D8>(b0, A, tile + 1, li, h);
     }
   }
 
@@ -247,45 +244,31 @@ __global__ __launch_bounds__(64) void diverse_rerank_kernel(RerankArgs A) {
   }
 }
 
-template <int D8, bool DB, bool GEO>
-static hipError_t launch_pool_t(const DiverseArgs& A, hipStream_t st) {
-  static DeviceOnce once;      // the LDS opt-in is a per-device attribute of the function
-  const hipError_t oe = once.run([&]() -> hipError_t {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&diverse_pool_kernel<D8, DB, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               POOL_LISTS_BYTES + (int)sizeof(double) * DIVERSE_NDIST_MAX);
-  });
-  if (oe != hipSuccess) return oe;
-  const unsigned n_utile = (unsigned)((A.n + 31) / 32);
-  const size_t lds = POOL_LISTS_BYTES + (GEO ? sizeof(double) * A.n_dist : 0);
-  hipLaunchKernelGGL((diverse_pool_kernel<D8, DB, GEO>), dim3(n_utile * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
-  return hipGetLastError();
-}
-
 template <bool GEO>
 static hipError_t launch_pool_g(const DiverseArgs& A, hipStream_t st) {
-  if (A.dim <= 32) return launch_pool_t<4, true, GEO>(A, st);
-  if (A.dim <= 64) return launch_pool_t<8, true, GEO>(A, st);
-  if (A.dim <= 128) return launch_pool_t<16, false, GEO>(A, st);
-  if (A.dim <= 256) return launch_pool_t<32, false, GEO>(A, st);
-  return hipErrorInvalidValue;
+  return by_dim<64>(A.dim, [&](auto d8, auto db) -> hipError_t {
+    constexpr auto kernel = &diverse_pool_kernel<decltype(d8)::value, decltype(db)::value, GEO>;
+    const hipError_t oe = lds_opt_in<kernel>(POOL_LISTS_BYTES + (int)sizeof(double) * DIVERSE_NDIST_MAX);
+    if (oe != hipSuccess) return oe;
+    const unsigned n_utile = (unsigned)((A.n + 31) / 32);
+    const size_t lds = POOL_LISTS_BYTES + (GEO ? sizeof(double) * A.n_dist : 0);
+    hipLaunchKernelGGL(kernel, dim3(n_utile * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_diverse_pool(DiverseArgs& A, hipStream_t st, Timing* tm) {
   if (A.wd && A.n_dist > DIVERSE_NDIST_MAX) return hipErrorInvalidValue;
-  tm->begin("diverse_pool", st);
+  Timing::Scope rec(tm, "diverse_pool", st);
   const hipError_t e = A.wd ? launch_pool_g<true>(A, st) : launch_pool_g<false>(A, st);
   if (e != hipSuccess) return e;
   if (A.part_s) launch_topk_slices_merge(slice_lists(A), DIVERSE_POOL_MAX, A.n, st);
-  tm->end(st);
-  return hipGetLastError();
+  return rec.close();
 }
 
 template <bool GEO, bool EMB>
 static hipError_t launch_rerank_t(const RerankArgs& A, hipStream_t st) {
-  static DeviceOnce once;
-  const hipError_t oe = once.run([&]() -> hipError_t {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&diverse_rerank_kernel<GEO, EMB>), hipFuncAttributeMaxDynamicSharedMemorySize, RERANK_LDS_MAX);
-  });
+  const hipError_t oe = lds_opt_in<&diverse_rerank_kernel<GEO, EMB>>(RERANK_LDS_MAX);
   if (oe != hipSuccess) return oe;
   const size_t lds = EMB ? sizeof(float) * DIVERSE_POOL_MAX * (size_t)(A.dim + 4) : 0;
   hipLaunchKernelGGL((diverse_rerank_kernel<GEO, EMB>), dim3((unsigned)A.n), dim3(64), lds, st, A);

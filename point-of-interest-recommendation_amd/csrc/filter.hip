@@ -13,8 +13,9 @@
 // filter_build_kernel: one predicate per blockIdx.y, its category list as an n_cat-bit set in LDS, one POI per lane, a ballot forms two
 // words.  Integer work only.
 //
-// filter_walk_kernel: the tile walk of diverse.hip / rank.hip - a workgroup owns a 32-row tile and a slice of the item range, its waves
-// a quarter of the slice each, the rows' A fragments in registers, one sorted list per (wave, row) in LDS (topk_list.h).  A 32-item
+// filter_walk_kernel: the item-stationary tile walk in tile_walk.h's steps - a workgroup owns a 32-row tile and a slice of the item range,
+// its waves a quarter of the slice each (wave_tile_range), the rows' A fragments in registers (load_row_tile), the item tiles streamed
+// past them (load_item_tile), one sorted list per (wave, row) in LDS (topk_list.h).  A 32-item
 // tile is exactly one bitmap word per row: lane li fetches row li's word two tiles ahead, so that one ballot decides BEFORE the item
 // rows of a tile are requested whether any row wants it - a tile whose 32 words are zero costs neither a load nor a product.  Bit li of
 // the row's word (a broadcast read from LDS) gates the distance term and the compare against the row's K-th entry; the exclusion lookup
@@ -34,9 +35,9 @@
 // filter_scores_kernel applies the definition to explicit float32 score rows, one workgroup per row.
 #include "poi_common.h"
 #include "poi_kernels.h"
-#include "tile_product.h"
+#include "launch_common.h"
+#include "tile_walk.h"
 #include "topk_list.h"
-#include "walk_common.h"
 
 namespace poi {
 
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(POI_BLOCK) void filter_walk_kernel(FilterArgs A) {
   double* const s_thr = reinterpret_cast<double*>(s_dyn + WALK_LISTS_BYTES);
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id(), li = lane & 31, h = lane >> 5;
   const int S = A.n_split, ut = blockIdx.x / S, sl = blockIdx.x - ut * S;
-  const int D = A.dim, N = A.n_item, K = A.k;
+  const int N = A.n_item, K = A.k;
 
   // the tile's rows: predicate index and anchor in range, exclusion lists with offsets in order and ids ascending inside [0, N)
   for (int i = w; i < 32; i += POI_NWAVE) {
@@ -170,9 +171,8 @@ __global__ __launch_bounds__(POI_BLOCK) void filter_walk_kernel(FilterArgs A) {
   for (int e = tid; e < POI_NWAVE * 32 * WALK_LIST; e += POI_BLOCK) { l_s[e] = neg_inf(); l_i[e] = PAD_ID; }
   __syncthreads();
 
-  const int ntile = (N + 31) / 32;
-  const int t0 = (int)((long long)ntile * sl / S), t1 = (int)((long long)ntile * (sl + 1) / S);
-  const int tb = t0 + (int)((long long)(t1 - t0) * w / POI_NWAVE), te = t0 + (int)((long long)(t1 - t0) * (w + 1) / POI_NWAVE);
+  int ntile, tb, te;
+  wave_tile_range(N, sl, S, w, ntile, tb, te);
   const float wd = GEO ? A.wd[0] : 0.f;
   float* const ls = l_s + w * 32 * WALK_LIST;
   int* const lx = l_i + w * 32 * WALK_LIST;
@@ -188,36 +188,34 @@ __global__ __launch_bounds__(POI_BLOCK) void filter_walk_kernel(FilterArgs A) {
   };
 
   float4 af[D8];
-  load_frag<D8>(af, A.users, 0, (size_t)min(ut * 32 + li, A.n - 1), D, h);
+  load_row_tile<D8>(af, A, ut, li, h);
   float4 b0[D8], b1[DB ? D8 : 1];
   unsigned w0 = word(tb), w1 = word(tb + 1);
   bool live = __ballot(w0 != 0u) != 0ull;           // (wave-uniform) some row of the tile wants this item tile
-  if (live) load_frag<D8>(b0, A.items, A.items_f16, (size_t)min(tb * 32 + li, N - 1), D, h);
+  if (live) load_item_tile<D8>(b0, A, tb, li, h);
   int pc = 0;                                       // passing POIs of row li in this wave's tiles
   for (int tile = tb; tile < te; ++tile) {
     const unsigned w2 = word(tile + 2);
     const bool live1 = __ballot(w1 != 0u) != 0ull;
-    if constexpr (DB) { if (live1) load_frag<D8>(b1, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h); }
+    if constexpr (DB) { if (live1) load_item_tile<D8>(b1, A, tile + 1, li, h); }
     pc += __popc(w0);
     if (live) {
       __builtin_amdgcn_wave_barrier();
       s_word[w][li] = w0;
       __builtin_amdgcn_wave_barrier();              // (a wave's LDS accesses complete in order: the reads below see it)
-      f32x16 acc = tile_product<D8>(af, b0);
+      f32x16 acc = tile_product<D8>(af, b0);       // (tile_walk.h: the walk's contract)
       const int j = tile * 32 + li;
-      double jlat = 0.0, jlon = 0.0, jcp = 0.0;
-      if (GEO) { const int jc = min(j, N - 1); jlat = A.coords[2 * (size_t)jc]; jlon = A.coords[2 * (size_t)jc + 1]; jcp = A.cphi[jc]; }
-      // the half wave's row base, opaque per tile (rank.hip: otherwise the loop-invariant LDS reads of the 16 rows are hoisted - 100+ registers)
-      int hb = 4 * h;
-      asm volatile("" : "+v"(hb));
+      double jlat, jlon, jcp;
+      item_tile_coords<GEO>(A, j, jlat, jlon, jcp);
+      const int hb = opaque_half_base(h);
       unsigned cm = 0u;                             // bit r: acc[r] passes and beats the K-th entry of its row's list
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ul = (r & 3) + 8 * (r >> 2) + hb;
+        const int ul = acc_tile_row(r, hb);
         const bool bit = (s_word[w][ul] >> li) & 1u;
         float s = acc[r];
         if (GEO) {
-          if (bit && s_has[ul]) s = __fmaf_rn(wd, geo_prob(A, s_thr, min(ut * 32 + ul, A.n - 1), s_ulat[ul], s_ulon[ul], s_ucp[ul], jlat, jlon, jcp), s);
+          if (bit && s_has[ul]) s = geo_add(A, wd, s_thr, ut, ul, s_ulat, s_ulon, s_ucp, jlat, jlon, jcp, s);
         }
         s = one_zero(s);
         acc[r] = s;
@@ -227,12 +225,10 @@ __global__ __launch_bounds__(POI_BLOCK) void filter_walk_kernel(FilterArgs A) {
       if (__ballot(cm != 0u)) {
         // the rare part: row by row, the exclusion lookup and the insertions
         for (int row = 0; row < 32; ++row) {
-          const int rr = (row & 3) + 4 * (row >> 3), hh = (row >> 2) & 1;
-          bool cand = h == hh && ((cm >> rr) & 1u);
+          int rr;
+          bool cand = rare_row(row, h, cm, rr);
           if (!__ballot(cand)) continue;            // (wave-uniform)
-          float v = acc[0];
-#pragma unroll
-          for (int r = 1; r < 16; ++r) v = rr == r ? acc[r] : v;
+          const float v = acc_row(acc, rr);
           const int e0 = s_e0[row], e1 = s_e1[row];
           if (cand && e1 > e0) cand = !listed(A.ex, e0, e1, j);
           const unsigned long long bal = __ballot(cand);
@@ -246,7 +242,7 @@ __global__ __launch_bounds__(POI_BLOCK) void filter_walk_kernel(FilterArgs A) {
         for (int m = 0; m < D8; ++m) b0[m] = b1[m];
       }
     } else {
-      if (live1) load_frag<D8>(b0, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h);
+      if (live1) load_item_tile<D8>(b0, A, tile + 1, li, h);
     }
     w0 = w1; w1 = w2; live = live1;
   }
@@ -413,15 +409,14 @@ __global__ __launch_bounds__(256) void filter_gather_kernel(FilterArgs A) {
 }
 
 hipError_t launch_filter_build(const FilterBuildArgs& A, hipStream_t st, Timing* tm) {
-  tm->begin("filter_build", st);
+  Timing::Scope rec(tm, "filter_build", st);
   if (A.count) {
     const hipError_t e = hipMemsetAsync(A.count, 0, sizeof(int) * (size_t)A.n_pred, st);
     if (e != hipSuccess) return e;
   }
   const long long rounds = (A.ldw * 32 + POI_BLOCK - 1) / POI_BLOCK;
   hipLaunchKernelGGL(filter_build_kernel, dim3((unsigned)(rounds < 4096 ? rounds : 4096), (unsigned)A.n_pred), dim3(POI_BLOCK), 0, st, A);
-  tm->end(st);
-  return hipGetLastError();
+  return rec.close();
 }
 
 hipError_t launch_filter_scores(const FilterScoresArgs& A, hipStream_t st, Timing* tm) {
@@ -431,57 +426,42 @@ hipError_t launch_filter_scores(const FilterScoresArgs& A, hipStream_t st, Timin
   return hipGetLastError();
 }
 
-template <int D8, bool DB, bool GEO>
-static hipError_t launch_walk_t(const FilterArgs& A, hipStream_t st) {
-  static DeviceOnce once;      // the LDS opt-in is a per-device attribute of the function
-  const hipError_t oe = once.run([&]() -> hipError_t {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&filter_walk_kernel<D8, DB, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               WALK_LISTS_BYTES + (int)sizeof(double) * FILTER_NDIST_MAX);
-  });
-  if (oe != hipSuccess) return oe;
-  const unsigned n_utile = (unsigned)((A.n + 31) / 32);
-  const size_t lds = WALK_LISTS_BYTES + (GEO ? sizeof(double) * A.n_dist : 0);
-  hipLaunchKernelGGL((filter_walk_kernel<D8, DB, GEO>), dim3(n_utile * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
-  return hipGetLastError();
-}
-
 template <bool GEO>
 static hipError_t launch_walk_g(const FilterArgs& A, hipStream_t st) {
-  if (A.dim <= 32) return launch_walk_t<4, true, GEO>(A, st);
-  if (A.dim <= 64) return launch_walk_t<8, true, GEO>(A, st);
-  if (A.dim <= 128) return launch_walk_t<16, false, GEO>(A, st);
-  if (A.dim <= 256) return launch_walk_t<32, false, GEO>(A, st);
-  return hipErrorInvalidValue;
+  return by_dim<64>(A.dim, [&](auto d8, auto db) -> hipError_t {
+    constexpr auto kernel = &filter_walk_kernel<decltype(d8)::value, decltype(db)::value, GEO>;
+    const hipError_t oe = lds_opt_in<kernel>(WALK_LISTS_BYTES + (int)sizeof(double) * FILTER_NDIST_MAX);
+    if (oe != hipSuccess) return oe;
+    const unsigned n_utile = (unsigned)((A.n + 31) / 32);
+    const size_t lds = WALK_LISTS_BYTES + (GEO ? sizeof(double) * A.n_dist : 0);
+    hipLaunchKernelGGL(kernel, dim3(n_utile * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_filter_walk(FilterArgs& A, hipStream_t st, Timing* tm) {
   if (A.wd && A.n_dist > FILTER_NDIST_MAX) return hipErrorInvalidValue;
-  tm->begin("score_topk_filtered", st);
+  Timing::Scope rec(tm, "score_topk_filtered", st);
   const hipError_t e = A.wd ? launch_walk_g<true>(A, st) : launch_walk_g<false>(A, st);
   if (e != hipSuccess) return e;
   if (A.part_s) launch_topk_slices_merge(slice_lists(A), FILTER_K_MAX, A.n, st);
-  tm->end(st);
-  return hipGetLastError();
+  return rec.close();
 }
 
 template <bool GEO>
 static hipError_t launch_gather_g(const FilterArgs& A, hipStream_t st) {
-  const dim3 grid((unsigned)A.n * (unsigned)A.n_split);
-  if (A.dim <= 32) hipLaunchKernelGGL((filter_gather_kernel<4, GEO>), grid, dim3(256), 0, st, A);
-  else if (A.dim <= 64) hipLaunchKernelGGL((filter_gather_kernel<8, GEO>), grid, dim3(256), 0, st, A);
-  else if (A.dim <= 128) hipLaunchKernelGGL((filter_gather_kernel<16, GEO>), grid, dim3(256), 0, st, A);
-  else if (A.dim <= 256) hipLaunchKernelGGL((filter_gather_kernel<32, GEO>), grid, dim3(256), 0, st, A);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  return by_dim<64>(A.dim, [&](auto d8, auto) -> hipError_t {
+    hipLaunchKernelGGL((filter_gather_kernel<decltype(d8)::value, GEO>), dim3((unsigned)A.n * (unsigned)A.n_split), dim3(256), 0, st, A);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_filter_gather(FilterArgs& A, hipStream_t st, Timing* tm) {
-  tm->begin("score_topk_filtered", st);
+  Timing::Scope rec(tm, "score_topk_filtered", st);
   const hipError_t e = A.wd ? launch_gather_g<true>(A, st) : launch_gather_g<false>(A, st);
   if (e != hipSuccess) return e;
   if (A.part_s) launch_topk_slices_merge(slice_lists(A), FILTER_K_MAX, A.n, st);
-  tm->end(st);
-  return hipGetLastError();
+  return rec.close();
 }
 
 }  // namespace poi

@@ -26,7 +26,8 @@
 // group_scores_kernel applies the same definition to explicit score rows (one workgroup per group, coalesced reads of the members' rows).
 #include "poi_common.h"
 #include "poi_kernels.h"
-#include "tile_product.h"
+#include "launch_common.h"
+#include "tile_walk.h"
 #include "topk_list.h"
 
 namespace poi {
@@ -106,9 +107,8 @@ __global__ __launch_bounds__(POI_BLOCK) void group_kernel(GroupArgs A) {
   for (int q = 0; q < GPT; ++q) { l_s[w][q][lane] = neg_inf(); l_i[w][q][lane] = PAD_ID; }
   __syncthreads();
 
-  const int ntile = (N + 31) / 32;
-  const int t0 = (int)((long long)ntile * sl / S), t1 = (int)((long long)ntile * (sl + 1) / S);
-  const int tb = t0 + (int)((long long)(t1 - t0) * w / POI_NWAVE), te = t0 + (int)((long long)(t1 - t0) * (w + 1) / POI_NWAVE);
+  int ntile, tb, te;
+  wave_tile_range(N, sl, S, w, ntile, tb, te);
   const float wd = GEO ? A.wd[0] : 0.f;
 
   int q = 0;
@@ -159,23 +159,23 @@ __global__ __launch_bounds__(POI_BLOCK) void group_kernel(GroupArgs A) {
     if (!BIG) load_frag<D8>(af, A.users, 0, (size_t)max(s_mem[w][li], 0), D, h);
 
     float4 b0[D8], b1[DB ? D8 : 1];
-    load_frag<D8>(b0, A.items, A.items_f16, (size_t)min(tb * 32 + li, N - 1), D, h);
+    load_item_tile<D8>(b0, A, tb, li, h);
     for (int tile = tb; tile < te; ++tile) {
-      if constexpr (DB) { if (tile + 1 < te) load_frag<D8>(b1, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h); }
+      if constexpr (DB) { if (tile + 1 < te) load_item_tile<D8>(b1, A, tile + 1, li, h); }
       const int j = tile * 32 + li;
       const bool jvalid = j < N;
-      double jlat = 0.0, jlon = 0.0, jcp = 0.0;
-      if (GEO) { const int jc = min(j, N - 1); jlat = A.coords[2 * (size_t)jc]; jlon = A.coords[2 * (size_t)jc + 1]; jcp = A.cphi[jc]; }
+      double jlat, jlon, jcp;
+      item_tile_coords<GEO>(A, j, jlat, jlon, jcp);
       float carry = 0.f;                            // BIG: the group's chain, from chunk to chunk
       for (int c = 0; c < nch; ++c) {
         if (BIG) {
           if (c > 0 || tile > tb) setup_rows(c);
           load_frag<D8>(af, A.users, 0, (size_t)max(s_mem[w][li], 0), D, h);
         }
-        const f32x16 acc = tile_product<D8>(af, b0);
+        const f32x16 acc = tile_product<D8>(af, b0);      // (tile_walk.h: the walk's contract)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int ul = (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int ul = acc_tile_row(r, 4 * h);
           float s = acc[r];
           if (GEO) {
             if (s_has[w][ul]) s = __fmaf_rn(wd, geo_prob(A, s_thr, s_mem[w][ul], s_ulat[w][ul], s_ulon[w][ul], s_ucp[w][ul], jlat, jlon, jcp), s);
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(POI_BLOCK) void group_kernel(GroupArgs A) {
 #pragma unroll
         for (int m = 0; m < D8; ++m) b0[m] = b1[m];
       } else {
-        if (tile + 1 < te) load_frag<D8>(b0, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h);
+        if (tile + 1 < te) load_item_tile<D8>(b0, A, tile + 1, li, h);
       }
     }
   }
@@ -284,31 +284,25 @@ __global__ __launch_bounds__(POI_BLOCK) void group_scores_kernel(const float* __
   }
 }
 
-template <int D8, bool DB, bool GEO>
-static void launch_group_t(const GroupArgs& A, hipStream_t st) {
-  const unsigned n_gtile = (unsigned)((A.n_grp + GROUP_GPT - 1) / GROUP_GPT), S = (unsigned)A.n_split;
-  const size_t lds = GEO ? sizeof(double) * A.n_dist : 0;
-  hipLaunchKernelGGL((group_kernel<D8, DB, GEO, false>), dim3(n_gtile * S), dim3(POI_BLOCK), lds, st, A);
-  hipLaunchKernelGGL((group_kernel<D8, DB, GEO, true>), dim3((unsigned)A.n_grp * S), dim3(POI_BLOCK), lds, st, A);
-}
-
 template <bool GEO>
 static hipError_t launch_group_g(const GroupArgs& A, hipStream_t st) {
-  if (A.dim <= 32) launch_group_t<4, true, GEO>(A, st);
-  else if (A.dim <= 64) launch_group_t<8, true, GEO>(A, st);
-  else if (A.dim <= 128) launch_group_t<16, false, GEO>(A, st);
-  else if (A.dim <= 256) launch_group_t<32, false, GEO>(A, st);
-  else return hipErrorInvalidValue;
-  return hipSuccess;
+  return by_dim<64>(A.dim, [&](auto d8, auto db) -> hipError_t {
+    constexpr int D8 = decltype(d8)::value;
+    constexpr bool DB = decltype(db)::value;
+    const unsigned n_gtile = (unsigned)((A.n_grp + GROUP_GPT - 1) / GROUP_GPT), S = (unsigned)A.n_split;
+    const size_t lds = GEO ? sizeof(double) * A.n_dist : 0;
+    hipLaunchKernelGGL((group_kernel<D8, DB, GEO, false>), dim3(n_gtile * S), dim3(POI_BLOCK), lds, st, A);
+    hipLaunchKernelGGL((group_kernel<D8, DB, GEO, true>), dim3((unsigned)A.n_grp * S), dim3(POI_BLOCK), lds, st, A);
+    return hipSuccess;
+  });
 }
 
 hipError_t launch_group(GroupArgs& A, hipStream_t st, Timing* tm) {
-  tm->begin("group_topk", st);
+  Timing::Scope rec(tm, "group_topk", st);
   const hipError_t e = A.wd ? launch_group_g<true>(A, st) : launch_group_g<false>(A, st);
   if (e != hipSuccess) return e;
   if (A.part_s) launch_topk_slices_merge(slice_lists(A), GROUP_K_MAX, A.n_grp, st);
-  tm->end(st);
-  return hipGetLastError();
+  return rec.close();
 }
 
 hipError_t launch_group_scores(const float* scores, GroupArgs& A, hipStream_t st, Timing* tm) {

@@ -14,9 +14,10 @@
 // (f2ord(score) << 32) | (0xFFFFFFFF - id), a 32-bit add.  Whatever the grid, the regime, the accumulator's home or the chunking of
 // the rows, the bits are the same.  No float atomics.
 //
-// labels_walk_kernel<.., MODE>: capped.hip's item-stationary tile walk without the bitmap (a workgroup owns a 32-row tile and an item
-// slice, its waves a quarter of the slice each, A fragments in registers, labels[j] fetched with the tile) and rank.hip's exclusion
-// cursors (lane r walks row r's list, a tile with listed ids gets one mask per row through LDS).
+// labels_walk_kernel<.., MODE>: the item-stationary tile walk in tile_walk.h's steps (wave_tile_range: a workgroup owns a 32-row tile
+// and an item slice, its waves a quarter of the slice each; load_row_tile / load_item_tile, labels[j] fetched with the tile; the
+// distance term through geo_add), no bitmap, and exclusion cursors in the kernel's own text (lane r walks row r's list, a tile with
+// listed ids gets one mask per row through LDS - BEFORE the product: tile_walk.h's contract came from this kernel).
 //   MODE 0   the max pass: M(r) alone - per-lane running maxima, one butterfly and one integer atomicMax per row and wave
 //   MODE 1   accumulators of the workgroup's 32 rows in LDS (few labels: 32 (n_label + 1) 20 bytes), flushed once with global atomics
 //   MODE 2   atomics straight on the context's global accumulator (many labels)
@@ -25,8 +26,8 @@
 // a block-wide arg-max under "higher key, then lower label id": by mass the key is mass_q, by max the packed best key).
 #include "poi_common.h"
 #include "poi_kernels.h"
-#include "tile_product.h"
-#include "walk_common.h"
+#include "launch_common.h"
+#include "tile_walk.h"
 #include <limits.h>
 
 namespace poi {
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(POI_BLOCK) void labels_walk_kernel(LabelsArgs A) {
   double* const s_thr = reinterpret_cast<double*>(s_dyn + (MODE == 1 ? (size_t)cells * LABELS_ROW_BYTES : 0));
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id(), li = lane & 31, h = lane >> 5;
   const int S = A.n_split, ut = blockIdx.x / S, sl = blockIdx.x - ut * S;
-  const int D = A.dim, N = A.n_item;
+  const int N = A.n_item;
 
   // the tile's rows: anchor in range, exclusion lists with offsets in order and ids ascending inside [0, N); M(r) finite
   for (int i = w; i < 32; i += POI_NWAVE) {
@@ -106,9 +107,8 @@ __global__ __launch_bounds__(POI_BLOCK) void labels_walk_kernel(LabelsArgs A) {
     for (int e = tid; e < cells; e += POI_BLOCK) { l_mass[e] = 0ull; l_best[e] = 0ull; l_cnt[e] = 0u; }
   __syncthreads();
 
-  const int ntile = (N + 31) / 32;
-  const int t0 = (int)((long long)ntile * sl / S), t1 = (int)((long long)ntile * (sl + 1) / S);
-  const int tb = t0 + (int)((long long)(t1 - t0) * w / POI_NWAVE), te = t0 + (int)((long long)(t1 - t0) * (w + 1) / POI_NWAVE);
+  int ntile, tb, te;
+  wave_tile_range(N, sl, S, w, ntile, tb, te);
   const float wd = GEO ? A.wd[0] : 0.f;
 
   if (tb < te) {                                    // (wave-uniform)
@@ -130,11 +130,11 @@ __global__ __launch_bounds__(POI_BLOCK) void labels_walk_kernel(LabelsArgs A) {
     for (int r = 0; r < (MODE == 0 ? 16 : 1); ++r) mx[r] = neg_inf();
 
     float4 af[D8];
-    load_frag<D8>(af, A.users, 0, (size_t)min(ut * 32 + li, A.n - 1), D, h);
+    load_row_tile<D8>(af, A, ut, li, h);
     float4 b0[D8], b1[DB ? D8 : 1];
-    load_frag<D8>(b0, A.items, A.items_f16, (size_t)min(tb * 32 + li, N - 1), D, h);
+    load_item_tile<D8>(b0, A, tb, li, h);
     for (int tile = tb; tile < te; ++tile) {
-      if constexpr (DB) { if (tile + 1 < te) load_frag<D8>(b1, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h); }
+      if constexpr (DB) { if (tile + 1 < te) load_item_tile<D8>(b1, A, tile + 1, li, h); }
       const int j = tile * 32 + li;
       const bool jvalid = j < N;
       const int lab = MODE != 0 ? A.labels[min(j, N - 1)] : 0;      // lane li: the label of its item column, fetched with the tile
@@ -154,22 +154,17 @@ __global__ __launch_bounds__(POI_BLOCK) void labels_walk_kernel(LabelsArgs A) {
           exdirty = anyex;
         }
       }
-      double jlat = 0.0, jlon = 0.0, jcp = 0.0;
-      if (GEO) { const int jc = min(j, N - 1); jlat = A.coords[2 * (size_t)jc]; jlon = A.coords[2 * (size_t)jc + 1]; jcp = A.cphi[jc]; }
+      double jlat, jlon, jcp;
+      item_tile_coords<GEO>(A, j, jlat, jlon, jcp);
       const int bk = bucket_of(lab, A.n_label);
-      // the product LAST before the epilogue, in one basic block with the first read of its result: with the mask branch between the
-      // two, the taken path reached the read of accumulator register 15 some ten wait states behind the last MFMA instead of eighteen
-      // (hipcc, ROCm 7: the wait count of a 16-pass MFMA is not carried across the branch) and rows 27 / 31 of a tile read a stale value
-      f32x16 acc = tile_product<D8>(af, b0);
-      // the half wave's row base, opaque per tile (rank.hip: otherwise the loop-invariant LDS reads of the 16 rows are hoisted)
-      int hb = 4 * h;
-      asm volatile("" : "+v"(hb));
+      f32x16 acc = tile_product<D8>(af, b0);       // (tile_walk.h: the walk's contract)
+      const int hb = opaque_half_base(h);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ul = (r & 3) + 8 * (r >> 2) + hb;
+        const int ul = acc_tile_row(r, hb);
         float s = acc[r];
         if (GEO) {
-          if (s_has[ul]) s = __fmaf_rn(wd, geo_prob(A, s_thr, min(ut * 32 + ul, A.n - 1), s_ulat[ul], s_ulon[ul], s_ucp[ul], jlat, jlon, jcp), s);
+          if (s_has[ul]) s = geo_add(A, wd, s_thr, ut, ul, s_ulat, s_ulon, s_ucp, jlat, jlon, jcp, s);
         }
         s = one_zero(s);
         if constexpr (MODE == 0) {
@@ -191,7 +186,7 @@ __global__ __launch_bounds__(POI_BLOCK) void labels_walk_kernel(LabelsArgs A) {
           for (int m = 0; m < D8; ++m) b0[m] = b1[m];
         }
       } else {
-        if (tile + 1 < te) load_frag<D8>(b0, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h);
+        if (tile + 1 < te) load_item_tile<D8>(b0, A, tile + 1, li, h);
       }
     }
 
@@ -199,7 +194,7 @@ __global__ __launch_bounds__(POI_BLOCK) void labels_walk_kernel(LabelsArgs A) {
       // one butterfly per row over the 32 lanes of the half wave, one integer atomic each
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = ut * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int row = ut * 32 + acc_tile_row(r, 4 * h);
         float v = mx[r];
 #pragma unroll
         for (int o = 16; o > 0; o >>= 1) { const float u = __shfl_xor(v, o, 64); v = u > v ? u : v; }
@@ -342,27 +337,17 @@ __global__ __launch_bounds__(256) void labels_finish_kernel(LabelsFinishArgs A) 
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------------------------
-template <int D8, bool DB, bool GEO, int MODE>
-static hipError_t launch_walk_t(const LabelsArgs& A, hipStream_t st) {
-  static DeviceOnce once;      // the LDS opt-in is a per-device attribute of the function
-  const hipError_t oe = once.run([&]() -> hipError_t {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&labels_walk_kernel<D8, DB, GEO, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (MODE == 1 ? LABELS_LDS_KB_MAX << 10 : 0) + (int)sizeof(double) * LABELS_NDIST_MAX);
-  });
-  if (oe != hipSuccess) return oe;
-  const unsigned n_utile = (unsigned)((A.n + 31) / 32);
-  const size_t lds = (MODE == 1 ? labels_lds_bytes(32, A.n_label) : 0) + (GEO ? sizeof(double) * A.n_dist : 0);
-  hipLaunchKernelGGL((labels_walk_kernel<D8, DB, GEO, MODE>), dim3(n_utile * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
-  return hipGetLastError();
-}
-
 template <bool GEO, int MODE>
 static hipError_t launch_walk_g(const LabelsArgs& A, hipStream_t st) {
-  if (A.dim <= 32) return launch_walk_t<4, true, GEO, MODE>(A, st);
-  if (A.dim <= 64) return launch_walk_t<8, true, GEO, MODE>(A, st);
-  if (A.dim <= 128) return launch_walk_t<16, false, GEO, MODE>(A, st);
-  if (A.dim <= 256) return launch_walk_t<32, false, GEO, MODE>(A, st);
-  return hipErrorInvalidValue;
+  return by_dim<64>(A.dim, [&](auto d8, auto db) -> hipError_t {
+    constexpr auto kernel = &labels_walk_kernel<decltype(d8)::value, decltype(db)::value, GEO, MODE>;
+    const hipError_t oe = lds_opt_in<kernel>((MODE == 1 ? LABELS_LDS_KB_MAX << 10 : 0) + (int)sizeof(double) * LABELS_NDIST_MAX);
+    if (oe != hipSuccess) return oe;
+    const unsigned n_utile = (unsigned)((A.n + 31) / 32);
+    const size_t lds = (MODE == 1 ? labels_lds_bytes(32, A.n_label) : 0) + (GEO ? sizeof(double) * A.n_dist : 0);
+    hipLaunchKernelGGL(kernel, dim3(n_utile * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_labels_max(const LabelsArgs& A, hipStream_t st, Timing* tm) {
@@ -386,19 +371,15 @@ hipError_t launch_labels_walk(const LabelsArgs& A, hipStream_t st, Timing* tm) {
 
 hipError_t launch_labels_scores(const LabelsScoresArgs& A, hipStream_t st, Timing* tm) {
   if (A.lds_home && labels_lds_bytes(1, A.n_label) > ((size_t)LABELS_LDS_KB_MAX << 10)) return hipErrorInvalidValue;
-  tm->begin("labels_scores", st);
+  Timing::Scope rec(tm, "labels_scores", st);
   if (A.lds_home) {
-    static DeviceOnce once;
-    const hipError_t oe = once.run([&]() -> hipError_t {
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(&labels_scores_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LABELS_LDS_KB_MAX << 10);
-    });
+    const hipError_t oe = lds_opt_in<&labels_scores_kernel<true>>(LABELS_LDS_KB_MAX << 10);
     if (oe != hipSuccess) return oe;
     hipLaunchKernelGGL(labels_scores_kernel<true>, dim3((unsigned)A.n), dim3(256), labels_lds_bytes(1, A.n_label), st, A);
   } else {
     hipLaunchKernelGGL(labels_scores_kernel<false>, dim3((unsigned)A.n), dim3(256), 0, st, A);
   }
-  tm->end(st);
-  return hipGetLastError();
+  return rec.close();
 }
 
 hipError_t launch_labels_finish(const LabelsFinishArgs& A, hipStream_t st, Timing* tm) {

@@ -43,6 +43,17 @@ struct Timing {
   }
   void span_end(long idx, hipStream_t st) { if (idx >= 0 && (size_t)idx < recs.size()) (void)hipEventRecord(recs[(size_t)idx].b, st); }
   void clear() { for (auto& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); } recs.clear(); }
+  // a launcher's record: begun here, closed on every way out - close() on the normal one (the record ends before the launch status is
+  // read), the destructor on an early `return e`.  Both call end(): it is a no-op on a record that is already closed (open_), and must stay one
+  struct Scope {
+    Scope(Timing* tm, const char* name, hipStream_t st) : tm_(tm), st_(st) { tm_->begin(name, st_); }
+    ~Scope() { tm_->end(st_); }
+    Scope(const Scope&) = delete;
+    Scope& operator=(const Scope&) = delete;
+    hipError_t close() { tm_->end(st_); return hipGetLastError(); }
+   private:
+    Timing* tm_; hipStream_t st_;
+  };
  private:
   bool open_ = false;
 };
@@ -654,7 +665,7 @@ struct GroupArgs {
 hipError_t launch_group(GroupArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_group_scores(const float* scores, GroupArgs& A, hipStream_t st, Timing* tm);
 
-// Audience recommendation (audience.hip): the top-K candidate rows (users) of each query POI - rank.hip's walk with the axes swapped
+// Audience recommendation (audience.hip): the top-K candidate rows (users) of each query POI - tile_walk.h's walk with the axes swapped
 #define AUDIENCE_K_MAX 32                   // list length (one half wave)
 #define AUDIENCE_NDIST_MAX 1024             // distance bins whose thresholds fit the walk kernel's LDS beside its lists
 struct AudienceArgs {
@@ -672,7 +683,7 @@ struct AudienceArgs {
 hipError_t launch_audience(const AudienceArgs& A, hipStream_t st, Timing* tm);
 hipError_t launch_audience_rows(const AudienceArgs& A, hipStream_t st, Timing* tm);
 
-// Similar rows (similar.hip): the top-K rows of ONE table most similar to each query row - audience.hip's walk with the table on both
+// Similar rows (similar.hip): the top-K rows of ONE table most similar to each query row - tile_walk.h's walk along the streamed rows, the table on both
 // sides and a float64 similarity epilogue; the nearest history POI of every listed POI
 #define SIMILAR_K_MAX 32                    // list length (one half wave)
 struct SimilarArgs {

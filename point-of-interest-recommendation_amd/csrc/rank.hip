@@ -27,7 +27,8 @@
 // rank_scores_kernel applies the same definition to explicit score rows (poi_rank_scores: the counterpart of poi_topk).
 #include "poi_common.h"
 #include "poi_kernels.h"
-#include "tile_product.h"
+#include "launch_common.h"
+#include "tile_walk.h"
 #include <limits.h>
 
 namespace poi {
@@ -100,11 +101,10 @@ __global__ __launch_bounds__(POI_BLOCK) void rank_kernel(RankArgs A) {
   __shared__ unsigned s_exm[POI_NWAVE][32];
   extern __shared__ __align__(16) double s_geo[];   // GEO: thr[n_dist] | row lat[32] | lon[32] | cos(lat)[32]
   const int lane = lane_id(), w = wave_id(), li = lane & 31, h = lane >> 5;
-  const int D = A.dim, N = A.n_item, ut = blockIdx.x;
+  const int N = A.n_item, ut = blockIdx.x;
   const int split = blockIdx.y * POI_NWAVE + w;
-  const int ntile = (N + 31) / 32;
-  const int tps = (ntile + A.n_split - 1) / A.n_split;
-  const int t_begin = min(ntile, split * tps), t_end = min(ntile, t_begin + tps);
+  int t_begin, t_end;
+  wave_tile_chunk(N, A.n_split, split, t_begin, t_end);
   for (int e = threadIdx.x; e < 32 * LT; e += POI_BLOCK) s_t[e / LT][e % LT] = A.tl[(size_t)(ut * 32 + e / LT) * RANK_LT_MAX + A.t_off + e % LT];
   double* s_ulat = s_geo + A.n_dist; double* s_ulon = s_ulat + 32; double* s_ucp = s_ulon + 32;
   if (GEO) {
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(POI_BLOCK) void rank_kernel(RankArgs A) {
   const float wd = GEO ? A.wd[0] : 0.f;
 
   float4 af[D8];
-  load_frag<D8>(af, A.users, 0, (size_t)min(ut * 32 + li, A.n - 1), D, h);
+  load_row_tile<D8>(af, A, ut, li, h);
 
   // lane r < 32: cursor into row r's exclusion list, at the first id of this wave's item range
   int xpos = 0, xend = 0, xnext = INT_MAX;
@@ -144,10 +144,11 @@ __global__ __launch_bounds__(POI_BLOCK) void rank_kernel(RankArgs A) {
     for (int p = 0; p < NP; ++p) cnt[r][p] = 0u;
 
   float4 b0[D8], b1[DB ? D8 : 1];
-  load_frag<D8>(b0, A.items, A.items_f16, (size_t)min(t_begin * 32 + li, N - 1), D, h);
+  load_item_tile<D8>(b0, A, t_begin, li, h);
 
   for (int tile = t_begin; tile < t_end; ++tile) {
-    if constexpr (DB) { if (tile + 1 < t_end) load_frag<D8>(b1, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h); }
+    if constexpr (DB) { if (tile + 1 < t_end) load_item_tile<D8>(b1, A, tile + 1, li, h); }
+    // (tile_walk.h: the walk's contract - not met here, the mask branch stands behind the product: DESIGN.md section 1)
     const f32x16 acc = tile_product<D8>(af, b0);
     const int j = tile * 32 + li;
     const bool jvalid = j < N;
@@ -165,17 +166,14 @@ __global__ __launch_bounds__(POI_BLOCK) void rank_kernel(RankArgs A) {
       wave_fence();
       exdirty = anyex;
     }
-    double jlat = 0.0, jlon = 0.0, jcp = 0.0;
-    if (GEO) { const int jc = min(j, N - 1); jlat = A.coords[2 * (size_t)jc]; jlon = A.coords[2 * (size_t)jc + 1]; jcp = A.cphi[jc]; }
-    // the half wave's row base, opaque per tile: otherwise the compiler hoists the loop-invariant LDS reads of the 16 rows' targets
-    // (and coordinates) out of the tile loop - 256 registers and more
-    int hb = 4 * h;
-    asm volatile("" : "+v"(hb));
+    double jlat, jlon, jcp;
+    item_tile_coords<GEO>(A, j, jlat, jlon, jcp);
+    const int hb = opaque_half_base(h);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int ul = (r & 3) + 8 * (r >> 2) + hb;
+      const int ul = acc_tile_row(r, hb);
       float s = acc[r];
-      if (GEO) s = __fmaf_rn(wd, geo_prob(A, s_geo, min(ut * 32 + ul, A.n - 1), s_ulat[ul], s_ulon[ul], s_ucp[ul], jlat, jlon, jcp), s);
+      if (GEO) s = geo_add(A, wd, s_geo, ut, ul, s_ulat, s_ulon, s_ucp, jlat, jlon, jcp, s);      // (unguarded: every ranked row has a last POI)
       const bool live = jvalid & !((s_exm[w][ul] >> li) & 1u);
       s = live ? s : __builtin_nanf("");            // compares false with everything: contributes nothing
 #pragma unroll
@@ -195,14 +193,14 @@ __global__ __launch_bounds__(POI_BLOCK) void rank_kernel(RankArgs A) {
 #pragma unroll
       for (int m = 0; m < D8; ++m) b0[m] = b1[m];
     } else {
-      if (tile + 1 < t_end) load_frag<D8>(b0, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h);
+      if (tile + 1 < t_end) load_item_tile<D8>(b0, A, tile + 1, li, h);
     }
   }
 
   // one reduction per (row, target) over the 32 lanes of the half wave, one integer atomic each
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int ul = (r & 3) + 8 * (r >> 2) + 4 * h, row = ut * 32 + ul;
+    const int ul = acc_tile_row(r, 4 * h), row = ut * 32 + ul;
     int mine = 0;                                   // lane li = i of the half wave keeps target i's sum
 #pragma unroll
     for (int i = 0; i < LT; ++i) {
@@ -269,28 +267,23 @@ __global__ __launch_bounds__(POI_BLOCK) void rank_scores_kernel(const float* __r
   if (tid == 0 && count_out) count_out[row] = badrow ? 0 : N - (e1 - e0);
 }
 
-template <int D8, bool DB, bool GEO>
-static hipError_t launch_rank_t(const RankArgs& A, hipStream_t st) {
-  const int n_utile = (A.n + 31) / 32;
-  const size_t lds = GEO ? sizeof(double) * (A.n_dist + 96) : 0;
-  hipLaunchKernelGGL((rank_targets_kernel<D8, GEO>), dim3(n_utile), dim3(64), 0, st, A);
-  const dim3 grid(n_utile, (A.n_split + POI_NWAVE - 1) / POI_NWAVE);
-  if (A.len_t <= 1) hipLaunchKernelGGL((rank_kernel<D8, DB, GEO, 1>), grid, dim3(POI_BLOCK), lds, st, A);
-  else {
-    // four targets per walk (their counters and the product's operands fit the register file without scratch); more take a second walk
-    RankArgs B = A;
-    for (B.t_off = 0; B.t_off < A.len_t; B.t_off += 4) hipLaunchKernelGGL((rank_kernel<D8, DB, GEO, 4>), grid, dim3(POI_BLOCK), lds, st, B);
-  }
-  return hipGetLastError();
-}
-
 template <bool GEO>
 static hipError_t launch_rank_g(const RankArgs& A, hipStream_t st) {
-  if (A.dim <= 32) return launch_rank_t<4, true, GEO>(A, st);
-  if (A.dim <= 64) return launch_rank_t<8, true, GEO>(A, st);
-  if (A.dim <= 128) return launch_rank_t<16, true, GEO>(A, st);
-  if (A.dim <= 256) return launch_rank_t<32, false, GEO>(A, st);
-  return hipErrorInvalidValue;
+  return by_dim<128>(A.dim, [&](auto d8, auto db) -> hipError_t {
+    constexpr int D8 = decltype(d8)::value;
+    constexpr bool DB = decltype(db)::value;
+    const int n_utile = (A.n + 31) / 32;
+    const size_t lds = GEO ? sizeof(double) * (A.n_dist + 96) : 0;
+    hipLaunchKernelGGL((rank_targets_kernel<D8, GEO>), dim3(n_utile), dim3(64), 0, st, A);
+    const dim3 grid(n_utile, (A.n_split + POI_NWAVE - 1) / POI_NWAVE);
+    if (A.len_t <= 1) hipLaunchKernelGGL((rank_kernel<D8, DB, GEO, 1>), grid, dim3(POI_BLOCK), lds, st, A);
+    else {
+      // four targets per walk (their counters and the product's operands fit the register file without scratch); more take a second walk
+      RankArgs B = A;
+      for (B.t_off = 0; B.t_off < A.len_t; B.t_off += 4) hipLaunchKernelGGL((rank_kernel<D8, DB, GEO, 4>), grid, dim3(POI_BLOCK), lds, st, B);
+    }
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_rank(const RankArgs& A, hipStream_t st, Timing* tm) {

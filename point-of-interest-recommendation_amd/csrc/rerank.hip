@@ -26,8 +26,8 @@
 // No float atomics, vector stores only.
 #include "poi_common.h"
 #include "poi_kernels.h"
-#include "tile_product.h"
-#include "walk_common.h"
+#include "launch_common.h"
+#include "tile_walk.h"
 
 namespace poi {
 
@@ -103,9 +103,8 @@ __global__ __launch_bounds__(POI_BLOCK) void score_lists_shared_kernel(ScoreList
   const int lane = lane_id(), w = wave_id(), li = lane & 31, h = lane >> 5;
   const int D = A.dim, N = A.n_item, C = A.n_cand, ut = blockIdx.x;
   const int split = blockIdx.y * POI_NWAVE + w;
-  const int ntile = (C + 31) / 32;
-  const int tps = (ntile + A.n_split - 1) / A.n_split;
-  const int t_begin = min(ntile, split * tps), t_end = min(ntile, t_begin + tps);
+  int t_begin, t_end;
+  wave_tile_chunk(C, A.n_split, split, t_begin, t_end);
   const bool rejected = A.flag[0] != 0;             // (workgroup-uniform)
   if (GEO && !rejected) {
     for (int i = threadIdx.x; i < A.n_dist; i += POI_BLOCK) s_thr[i] = A.thr[i];
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(POI_BLOCK) void score_lists_shared_kernel(ScoreList
   const float wd = GEO ? A.wd[0] : 0.f;
 
   float4 af[D8];
-  load_frag<D8>(af, A.users, 0, (size_t)min(ut * 32 + li, A.n - 1), D, h);
+  load_row_tile<D8>(af, A, ut, li, h);
   // the id of list position c, -1 behind the list; what is read of the tables: padding reads row 0
   auto id_at = [&](int c) { return c < C ? A.cand[c] : -1; };
   int id0 = id_at(t_begin * 32 + li), id1 = -1;
@@ -136,19 +135,17 @@ __global__ __launch_bounds__(POI_BLOCK) void score_lists_shared_kernel(ScoreList
   for (int tile = t_begin; tile < t_end; ++tile) {
     if (tile + 1 < t_end) id1 = id_at((tile + 1) * 32 + li);
     if constexpr (DB) { if (tile + 1 < t_end) load_frag<D8>(b1, A.items, A.items_f16, (size_t)min(max(id1, 0), N - 1), D, h); }
-    const f32x16 acc = tile_product<D8>(af, b0);
+    const f32x16 acc = tile_product<D8>(af, b0);   // (tile_walk.h: the walk's contract)
     const int c = tile * 32 + li, jc = min(max(id0, 0), N - 1);
     double jlat = 0.0, jlon = 0.0, jcp = 0.0;
     if (GEO) { jlat = A.coords[2 * (size_t)jc]; jlon = A.coords[2 * (size_t)jc + 1]; jcp = A.cphi[jc]; }
-    // the half wave's row base, opaque per tile (rank.hip: otherwise the loop-invariant LDS reads of the 16 rows are hoisted)
-    int hb = 4 * h;
-    asm volatile("" : "+v"(hb));
+    const int hb = opaque_half_base(h);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int ul = (r & 3) + 8 * (r >> 2) + hb, row = ut * 32 + ul;
+      const int ul = acc_tile_row(r, hb), row = ut * 32 + ul;
       float s = acc[r];
       if (GEO) {
-        if (s_has[ul]) s = __fmaf_rn(wd, geo_prob(A, s_thr, min(row, A.n - 1), s_ulat[ul], s_ulon[ul], s_ucp[ul], jlat, jlon, jcp), s);
+        if (s_has[ul]) s = geo_add(A, wd, s_thr, ut, ul, s_ulat, s_ulon, s_ucp, jlat, jlon, jcp, s);
       }
       s = one_zero(s);
       if (row < A.n && c < C) A.out[(size_t)row * (size_t)C + c] = id0 >= 0 ? s : neg_inf();      // 32 consecutive floats per row
@@ -225,36 +222,28 @@ __global__ __launch_bounds__(RERANK_SORT_BLOCK) void rerank_sort_kernel(RerankLi
   if (tid == 0 && A.count_out) A.count_out[row] = count;
 }
 
-template <int D8, bool DB, bool GEO>
-static hipError_t launch_score_lists_t(const ScoreListsArgs& A, hipStream_t st) {
-  if (A.cand_off) {
-    hipLaunchKernelGGL((score_lists_ragged_kernel<D8, GEO>), dim3((unsigned)A.n, (unsigned)A.n_split), dim3(POI_BLOCK), 0, st, A);
-  } else {
-    const dim3 grid((A.n + 31) / 32, (A.n_split + POI_NWAVE - 1) / POI_NWAVE);
-    hipLaunchKernelGGL((score_lists_shared_kernel<D8, DB, GEO>), grid, dim3(POI_BLOCK), GEO ? sizeof(double) * A.n_dist : 0, st, A);
-  }
-  return hipGetLastError();
-}
-
 template <bool GEO>
 static hipError_t launch_score_lists_g(const ScoreListsArgs& A, hipStream_t st) {
-  if (A.dim <= 32) return launch_score_lists_t<4, true, GEO>(A, st);
-  if (A.dim <= 64) return launch_score_lists_t<8, true, GEO>(A, st);
-  if (A.dim <= 128) return launch_score_lists_t<16, true, GEO>(A, st);
-  if (A.dim <= 256) return launch_score_lists_t<32, false, GEO>(A, st);
-  return hipErrorInvalidValue;
+  return by_dim<128>(A.dim, [&](auto d8, auto db) -> hipError_t {
+    constexpr int D8 = decltype(d8)::value;
+    if (A.cand_off) {
+      hipLaunchKernelGGL((score_lists_ragged_kernel<D8, GEO>), dim3((unsigned)A.n, (unsigned)A.n_split), dim3(POI_BLOCK), 0, st, A);
+    } else {
+      const dim3 grid((A.n + 31) / 32, (A.n_split + POI_NWAVE - 1) / POI_NWAVE);
+      hipLaunchKernelGGL((score_lists_shared_kernel<D8, decltype(db)::value, GEO>), grid, dim3(POI_BLOCK), GEO ? sizeof(double) * A.n_dist : 0, st, A);
+    }
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_score_lists(const ScoreListsArgs& A, hipStream_t st, Timing* tm) {
-  tm->begin("score_lists", st);
+  Timing::Scope rec(tm, "score_lists", st);
   hipLaunchKernelGGL(lists_check_kernel, dim3(A.cand_off ? (unsigned)A.n : 1u), dim3(POI_BLOCK), 0, st, A.cand_off, A.cand, A.n_cand, A.n_item, A.flag, A.bad);
   if (A.cand_off) {                                 // a rejected ragged row writes nothing: its -inf is this fill's
     const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)A.out, (int)0xff800000u, (size_t)A.n_cand, st);
     if (e != hipSuccess) return e;
   }
-  const hipError_t e = A.wd ? launch_score_lists_g<true>(A, st) : launch_score_lists_g<false>(A, st);
-  tm->end(st);
-  return e;
+  return A.wd ? launch_score_lists_g<true>(A, st) : launch_score_lists_g<false>(A, st);
 }
 
 hipError_t launch_rerank_lists(const RerankListsArgs& A, hipStream_t st, Timing* tm) {

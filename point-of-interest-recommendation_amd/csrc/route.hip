@@ -8,7 +8,8 @@
 //   C(r)     = [0, n_item) minus the exclusion list of the row's slot (list row / rows_per_list) minus the row's own path
 //   list     = the best min(b, |C(r)|) of C(r) by better() (higher score, then lower id)
 //
-// route_expand_kernel: the item-stationary tile walk of rank.hip.  A workgroup owns a 32-row tile and one slice of the item range; each
+// route_expand_kernel: the item-stationary tile walk in tile_walk.h's steps (load_row_tile / load_item_tile, item_tile_coords, geo_add;
+// the item BLOCK ranges are its own).  A workgroup owns a 32-row tile and one slice of the item range; each
 // of its four waves walks a contiguous range of ITEM BLOCKS (ROUTE_LSE_TILES tiles = 512 POIs) with the rows' A fragments in registers.
 // Epilogue per 32 x 32 tile and accumulator register (one (row, item) pair per lane):
 //   normaliser  a per-lane running (max, float64 sum) of the pairs this lane has seen in the current block - lane `li` of the half wave
@@ -30,7 +31,8 @@
 // by (higher total, lower parent, lower POI id) with a 64-step all-pairs count; the best b survive.
 #include "poi_common.h"
 #include "poi_kernels.h"
-#include "tile_product.h"
+#include "launch_common.h"
+#include "tile_walk.h"
 #include "topk_list.h"
 #include <limits.h>
 
@@ -112,7 +114,7 @@ __global__ __launch_bounds__(POI_BLOCK) void route_expand_kernel(RouteArgs A) {
   extern __shared__ __align__(16) double s_thr[];   // GEO: thr[n_dist]
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id(), li = lane & 31, h = lane >> 5;
   const int S = A.n_split, ut = blockIdx.x / S, sl = blockIdx.x - ut * S;
-  const int D = A.dim, N = A.n_item, b = A.b, PL = A.path_len;
+  const int N = A.n_item, b = A.b, PL = A.path_len;
 
   // the tile's rows: live? exclusion list ascending inside [0, N), path ids inside [0, N); |C(r)|
   for (int i = w; i < 32; i += POI_NWAVE) {
@@ -158,31 +160,29 @@ __global__ __launch_bounds__(POI_BLOCK) void route_expand_kernel(RouteArgs A) {
   if (any_live && t_begin < t_end) {                // (wave-uniform)
     const float wd = GEO ? A.wd[0] : 0.f;
     float4 af[D8];
-    load_frag<D8>(af, A.users, 0, (size_t)min(ut * 32 + li, A.n - 1), D, h);
+    load_row_tile<D8>(af, A, ut, li, h);
     float mx[16];
     double sm[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { mx[r] = neg_inf(); sm[r] = 0.0; }
 
     float4 b0[D8], b1[DB ? D8 : 1];
-    load_frag<D8>(b0, A.items, A.items_f16, (size_t)min(t_begin * 32 + li, N - 1), D, h);
+    load_item_tile<D8>(b0, A, t_begin, li, h);
     for (int tile = t_begin; tile < t_end; ++tile) {
-      if constexpr (DB) { if (tile + 1 < t_end) load_frag<D8>(b1, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h); }
-      f32x16 acc = tile_product<D8>(af, b0);
+      if constexpr (DB) { if (tile + 1 < t_end) load_item_tile<D8>(b1, A, tile + 1, li, h); }
+      f32x16 acc = tile_product<D8>(af, b0);       // (tile_walk.h: the walk's contract)
       const int j = tile * 32 + li;
       const bool jvalid = j < N;
-      double jlat = 0.0, jlon = 0.0, jcp = 0.0;
-      if (GEO) { const int jc = min(j, N - 1); jlat = A.coords[2 * (size_t)jc]; jlon = A.coords[2 * (size_t)jc + 1]; jcp = A.cphi[jc]; }
-      // the half wave's row base, opaque per tile: otherwise the loop-invariant LDS reads of the 16 rows are hoisted out of the tile loop
-      int hb = 4 * h;
-      asm volatile("" : "+v"(hb));
+      double jlat, jlon, jcp;
+      item_tile_coords<GEO>(A, j, jlat, jlon, jcp);
+      const int hb = opaque_half_base(h);
       unsigned cm = 0u;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ul = (r & 3) + 8 * (r >> 2) + hb;
+        const int ul = acc_tile_row(r, hb);
         float s = acc[r];
         if (GEO) {
-          if (s_has[ul]) s = __fmaf_rn(wd, geo_prob(A, s_thr, min(ut * 32 + ul, A.n - 1), s_ulat[ul], s_ulon[ul], s_ucp[ul], jlat, jlon, jcp), s);
+          if (s_has[ul]) s = geo_add(A, wd, s_thr, ut, ul, s_ulat, s_ulon, s_ucp, jlat, jlon, jcp, s);
           acc[r] = s;
         }
         if (jvalid && s == s) {                     // (a NaN adds nothing)
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(POI_BLOCK) void route_expand_kernel(RouteArgs A) {
           for (int hh = 0; hh < 2; ++hh) {
             bool cand = h == hh && ((cm >> r) & 1u);
             if (!__ballot(cand)) continue;          // (wave-uniform)
-            const int ul = (r & 3) + 8 * (r >> 2) + 4 * hh;
+            const int ul = acc_tile_row(r, 4 * hh);
             if (cand) {
               bool out = s_e1[ul] > s_e0[ul] && listed(A.ex, s_e0[ul], s_e1[ul], j);
               for (int q = 0; q < PL; ++q) out |= s_path[ul][q] == j;
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(POI_BLOCK) void route_expand_kernel(RouteArgs A) {
         const int blk = tile / ROUTE_LSE_TILES;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int ul = (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int ul = acc_tile_row(r, 4 * h);
           float M = mx[r];
 #pragma unroll
           for (int o = 16; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o, 64));
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(POI_BLOCK) void route_expand_kernel(RouteArgs A) {
 #pragma unroll
         for (int m = 0; m < D8; ++m) b0[m] = b1[m];
       } else {
-        if (tile + 1 < t_end) load_frag<D8>(b0, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h);
+        if (tile + 1 < t_end) load_item_tile<D8>(b0, A, tile + 1, li, h);
       }
     }
   }
@@ -293,30 +293,22 @@ __global__ __launch_bounds__(64) void route_merge_kernel(RouteMergeArgs A) {
   if (lane == 0 && A.nlive_out) A.nlive_out[s] = min(n_valid, B);
 }
 
-template <int D8, bool DB, bool GEO>
-static void launch_route_t(const RouteArgs& A, hipStream_t st) {
-  const unsigned n_utile = (unsigned)((A.n + 31) / 32);
-  const size_t lds = GEO ? sizeof(double) * A.n_dist : 0;
-  hipLaunchKernelGGL((route_expand_kernel<D8, DB, GEO>), dim3(n_utile * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
-}
-
 template <bool GEO>
 static hipError_t launch_route_g(const RouteArgs& A, hipStream_t st) {
-  if (A.dim <= 32) launch_route_t<4, true, GEO>(A, st);
-  else if (A.dim <= 64) launch_route_t<8, true, GEO>(A, st);
-  else if (A.dim <= 128) launch_route_t<16, false, GEO>(A, st);
-  else if (A.dim <= 256) launch_route_t<32, false, GEO>(A, st);
-  else return hipErrorInvalidValue;
-  return hipSuccess;
+  return by_dim<64>(A.dim, [&](auto d8, auto db) -> hipError_t {
+    const unsigned n_utile = (unsigned)((A.n + 31) / 32);
+    const size_t lds = GEO ? sizeof(double) * A.n_dist : 0;
+    hipLaunchKernelGGL((route_expand_kernel<decltype(d8)::value, decltype(db)::value, GEO>), dim3(n_utile * (unsigned)A.n_split), dim3(POI_BLOCK), lds, st, A);
+    return hipSuccess;
+  });
 }
 
 hipError_t launch_route_expand(const RouteArgs& A, hipStream_t st, Timing* tm) {
-  tm->begin("route_expand", st);
+  Timing::Scope rec(tm, "route_expand", st);
   const hipError_t e = A.wd ? launch_route_g<true>(A, st) : launch_route_g<false>(A, st);
   if (e != hipSuccess) return e;
   if (!A.finish) hipLaunchKernelGGL(route_finish_kernel, dim3((unsigned)A.n), dim3(64), 0, st, A);
-  tm->end(st);
-  return hipGetLastError();
+  return rec.close();
 }
 
 hipError_t launch_route_merge(const RouteMergeArgs& A, hipStream_t st, Timing* tm) {

@@ -7,7 +7,8 @@
 //   result      = the best K' = min(k, |selectable|) entries under better() (descending score, ascending id), sorted best first,
 //                 -1 ids and -inf scores behind; -0.0 and +0.0 are the SAME score (the id decides) and come out as +0.0
 //
-// score_rows_kernel: the tile walk of rank.hip with a store epilogue - a wave owns a 32-row tile and a range of 32-item tiles, the
+// score_rows_kernel: the item-stationary tile walk in tile_walk.h's steps (wave_tile_chunk, load_row_tile / load_item_tile, geo_add) with
+// a store epilogue - a wave owns a 32-row tile and a range of 32-item tiles, the
 // accumulator register of a row holds 32 consecutive items and goes to scores_out[r * ld + j] as it is.  The same tile_product and the
 // same distance-term expression as rank.hip: a pair's score has the bits of poi_score_rank's score_out.
 //
@@ -33,7 +34,8 @@
 // chunking, for a row alone or in a call of thousands.  No float atomics, vector stores only.
 #include "poi_common.h"
 #include "poi_kernels.h"
-#include "tile_product.h"
+#include "launch_common.h"
+#include "tile_walk.h"
 
 namespace poi {
 
@@ -95,11 +97,10 @@ __global__ __launch_bounds__(POI_BLOCK) void score_rows_kernel(ScoreRowsArgs A) 
   __shared__ double s_ulat[32], s_ulon[32], s_ucp[32];
   extern __shared__ __align__(16) double s_thr[];   // GEO: thr[n_dist]
   const int lane = lane_id(), w = wave_id(), li = lane & 31, h = lane >> 5;
-  const int D = A.dim, N = A.n_item, ut = blockIdx.x;
+  const int N = A.n_item, ut = blockIdx.x;
   const int split = blockIdx.y * POI_NWAVE + w;
-  const int ntile = (N + 31) / 32;
-  const int tps = (ntile + A.n_split - 1) / A.n_split;
-  const int t_begin = min(ntile, split * tps), t_end = min(ntile, t_begin + tps);
+  int t_begin, t_end;
+  wave_tile_chunk(N, A.n_split, split, t_begin, t_end);
   if (GEO) {
     for (int i = threadIdx.x; i < A.n_dist; i += POI_BLOCK) s_thr[i] = A.thr[i];
     if (threadIdx.x < 32) {
@@ -112,24 +113,22 @@ __global__ __launch_bounds__(POI_BLOCK) void score_rows_kernel(ScoreRowsArgs A) 
   const float wd = GEO ? A.wd[0] : 0.f;
 
   float4 af[D8];
-  load_frag<D8>(af, A.users, 0, (size_t)min(ut * 32 + li, A.n - 1), D, h);
+  load_row_tile<D8>(af, A, ut, li, h);
   float4 b0[D8], b1[DB ? D8 : 1];
-  load_frag<D8>(b0, A.items, A.items_f16, (size_t)min(t_begin * 32 + li, N - 1), D, h);
+  load_item_tile<D8>(b0, A, t_begin, li, h);
   for (int tile = t_begin; tile < t_end; ++tile) {
-    if constexpr (DB) { if (tile + 1 < t_end) load_frag<D8>(b1, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h); }
-    const f32x16 acc = tile_product<D8>(af, b0);
+    if constexpr (DB) { if (tile + 1 < t_end) load_item_tile<D8>(b1, A, tile + 1, li, h); }
+    const f32x16 acc = tile_product<D8>(af, b0);   // (tile_walk.h: the walk's contract)
     const int j = tile * 32 + li;
-    double jlat = 0.0, jlon = 0.0, jcp = 0.0;
-    if (GEO) { const int jc = min(j, N - 1); jlat = A.coords[2 * (size_t)jc]; jlon = A.coords[2 * (size_t)jc + 1]; jcp = A.cphi[jc]; }
-    // the half wave's row base, opaque per tile (rank.hip: otherwise the loop-invariant LDS reads of the 16 rows are hoisted)
-    int hb = 4 * h;
-    asm volatile("" : "+v"(hb));
+    double jlat, jlon, jcp;
+    item_tile_coords<GEO>(A, j, jlat, jlon, jcp);
+    const int hb = opaque_half_base(h);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int ul = (r & 3) + 8 * (r >> 2) + hb, row = ut * 32 + ul;
+      const int ul = acc_tile_row(r, hb), row = ut * 32 + ul;
       float s = acc[r];
       if (GEO) {
-        if (s_has[ul]) s = __fmaf_rn(wd, geo_prob(A, s_thr, min(row, A.n - 1), s_ulat[ul], s_ulon[ul], s_ucp[ul], jlat, jlon, jcp), s);
+        if (s_has[ul]) s = geo_add(A, wd, s_thr, ut, ul, s_ulat, s_ulon, s_ucp, jlat, jlon, jcp, s);
       }
       if (row < A.n && j < N) A.out[(size_t)row * (size_t)A.ld + j] = s;      // 32 consecutive floats per row: one 128-byte segment
       if (GEO) __builtin_amdgcn_sched_barrier(0);   // one row's distance term in flight at a time
@@ -138,7 +137,7 @@ __global__ __launch_bounds__(POI_BLOCK) void score_rows_kernel(ScoreRowsArgs A) 
 #pragma unroll
       for (int m = 0; m < D8; ++m) b0[m] = b1[m];
     } else {
-      if (tile + 1 < t_end) load_frag<D8>(b0, A.items, A.items_f16, (size_t)min((tile + 1) * 32 + li, N - 1), D, h);
+      if (tile + 1 < t_end) load_item_tile<D8>(b0, A, tile + 1, li, h);
     }
   }
 }
@@ -312,20 +311,13 @@ __global__ __launch_bounds__(SELECT_SORT_BLOCK) void select_sort_kernel(SelectAr
   }
 }
 
-template <int D8, bool DB, bool GEO>
-static hipError_t launch_score_rows_t(const ScoreRowsArgs& A, hipStream_t st) {
-  const dim3 grid((A.n + 31) / 32, (A.n_split + POI_NWAVE - 1) / POI_NWAVE);
-  hipLaunchKernelGGL((score_rows_kernel<D8, DB, GEO>), grid, dim3(POI_BLOCK), GEO ? sizeof(double) * A.n_dist : 0, st, A);
-  return hipGetLastError();
-}
-
 template <bool GEO>
 static hipError_t launch_score_rows_g(const ScoreRowsArgs& A, hipStream_t st) {
-  if (A.dim <= 32) return launch_score_rows_t<4, true, GEO>(A, st);
-  if (A.dim <= 64) return launch_score_rows_t<8, true, GEO>(A, st);
-  if (A.dim <= 128) return launch_score_rows_t<16, true, GEO>(A, st);
-  if (A.dim <= 256) return launch_score_rows_t<32, false, GEO>(A, st);
-  return hipErrorInvalidValue;
+  return by_dim<128>(A.dim, [&](auto d8, auto db) -> hipError_t {
+    const dim3 grid((A.n + 31) / 32, (A.n_split + POI_NWAVE - 1) / POI_NWAVE);
+    hipLaunchKernelGGL((score_rows_kernel<decltype(d8)::value, decltype(db)::value, GEO>), grid, dim3(POI_BLOCK), GEO ? sizeof(double) * A.n_dist : 0, st, A);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_score_rows(const ScoreRowsArgs& A, hipStream_t st, Timing* tm) {

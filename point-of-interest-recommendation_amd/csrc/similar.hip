@@ -8,7 +8,8 @@
 //   sim(i,j) = (float)(g geo + (1 - g) emb), formed in float64 without contraction, rounded once; -0.0 is written as +0.0
 //   C(q)     = [0, n) minus the query's own row minus its exclusion list;  the list is C(q) by descending sim, ties by ascending row.
 //
-// similar_kernel is audience.hip's walk with the table on both sides.  A workgroup owns a block of 32 query rows and one slice of the
+// similar_kernel is the tile walk of tile_walk.h along the streamed rows (wave_tile_range, acc_tile_row), as in audience.hip, with the
+// table on both sides.  A workgroup owns a block of 32 query rows and one slice of the
 // row range; its four waves take a quarter of the slice each.  The queries' fragments, inv, coordinates and cos(lat) stay in registers;
 // the 32-row tiles of the same table stream past as the a fragments.  In tile_product's accumulator a lane holds 16 streamed rows of
 // ITS OWN query (lane & 31).  The streamed rows' inv and coordinates are direct loads by tile (no dependent gather), requested a tile
@@ -34,7 +35,8 @@
 #include "poi_common.h"
 #include "poi_kernels.h"
 #include "pair_sim.h"
-#include "tile_product.h"
+#include "launch_common.h"
+#include "tile_walk.h"
 #include "topk_list.h"
 #include <limits.h>
 
@@ -110,9 +112,8 @@ __global__ __launch_bounds__(POI_BLOCK) void similar_kernel(SimilarArgs A) {
   }
   __syncthreads();
 
-  const int ntile = (n + 31) / 32;
-  const int t0 = (int)((long long)ntile * sl / S), t1 = (int)((long long)ntile * (sl + 1) / S);
-  const int tb = t0 + (int)((long long)(t1 - t0) * w / POI_NWAVE), te = t0 + (int)((long long)(t1 - t0) * (w + 1) / POI_NWAVE);
+  int ntile, tb, te;
+  wave_tile_range(n, sl, S, w, ntile, tb, te);
   const int myq = s_q[li];
   const bool qlive = myq >= 0;
   const double g = A.g, omg = A.omg, scale_km = A.scale_km;
@@ -160,6 +161,7 @@ __global__ __launch_bounds__(POI_BLOCK) void similar_kernel(SimilarArgs A) {
         n_inv = A.inv[u];
         if (GEO) { n_lat = A.coords[2 * u]; n_lon = A.coords[2 * u + 1]; n_cp = A.cphi[u]; }
       }
+      // (tile_walk.h: the walk's contract - not met here, the mask branch stands behind the product: DESIGN.md section 1)
       const f32x16 acc = tile_product<D8>(a0, bf);
       // one buffer: the next tile's rows are requested as soon as the product has read this tile's, behind them the whole epilogue
       if constexpr (!DB) { if (tile + 1 < te) load_frag<D8>(a0, A.x, A.x_f16, (size_t)min((tile + 1) * 32 + li, n - 1), D, h); }
@@ -185,7 +187,7 @@ __global__ __launch_bounds__(POI_BLOCK) void similar_kernel(SimilarArgs A) {
       unsigned cm = 0u;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ul = (r & 3) + 8 * (r >> 2) + 4 * h, u = tile * 32 + ul;
+        const int ul = acc_tile_row(r, 4 * h), u = tile * 32 + ul;
         const double e = (double)acc[r] * (s_uinv[w][ul] * qinv);
         const bool live = ROWS || (qlive && u < n && u != myq && !((xm >> ul) & 1u));
         float s = quiet_nan();                      // compares false with everything: never offered
@@ -205,7 +207,7 @@ __global__ __launch_bounds__(POI_BLOCK) void similar_kernel(SimilarArgs A) {
       }
       if (ROWS) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) s_sc[w][((r & 3) + 8 * (r >> 2) + 4 * h) * SIM_LD + li] = sv[r];
+        for (int r = 0; r < 16; ++r) s_sc[w][acc_tile_row(r, 4 * h) * SIM_LD + li] = sv[r];
         wave_fence();
         const int u = tile * 32 + li;
 #pragma unroll
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(POI_BLOCK) void similar_kernel(SimilarArgs A) {
         const unsigned long long offers = __ballot(cm != 0u);
         if (offers) {                               // (wave-uniform; rare once the lists have warmed up)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) s_sc[w][((r & 3) + 8 * (r >> 2) + 4 * h) * SIM_LD + li] = sv[r];
+          for (int r = 0; r < 16; ++r) s_sc[w][acc_tile_row(r, 4 * h) * SIM_LD + li] = sv[r];
           wave_fence();
           unsigned qs = (unsigned)(offers | (offers >> 32));
           const int u = tile * 32 + li;
@@ -371,20 +373,13 @@ hipError_t launch_row_inv_norms(const void* x, int x_f16, int n, int dim, double
   return hipGetLastError();
 }
 
-template <int D8, bool DB, bool GEO, bool ROWS>
-static void launch_similar_t(const SimilarArgs& A, hipStream_t st) {
-  const unsigned n_qblock = (unsigned)((A.n_q + 31) / 32);
-  hipLaunchKernelGGL((similar_kernel<D8, DB, GEO, ROWS>), dim3(n_qblock * (unsigned)A.n_split), dim3(POI_BLOCK), 0, st, A);
-}
-
 template <bool GEO, bool ROWS>
 static hipError_t launch_similar_g(const SimilarArgs& A, hipStream_t st) {
-  if (A.dim <= 32) launch_similar_t<4, true, GEO, ROWS>(A, st);
-  else if (A.dim <= 64) launch_similar_t<8, true, GEO, ROWS>(A, st);
-  else if (A.dim <= 128) launch_similar_t<16, false, GEO, ROWS>(A, st);
-  else if (A.dim <= 256) launch_similar_t<32, false, GEO, ROWS>(A, st);
-  else return hipErrorInvalidValue;
-  return hipSuccess;
+  return by_dim<64>(A.dim, [&](auto d8, auto db) -> hipError_t {
+    const unsigned n_qblock = (unsigned)((A.n_q + 31) / 32);
+    hipLaunchKernelGGL((similar_kernel<decltype(d8)::value, decltype(db)::value, GEO, ROWS>), dim3(n_qblock * (unsigned)A.n_split), dim3(POI_BLOCK), 0, st, A);
+    return hipSuccess;
+  });
 }
 
 hipError_t launch_similar(const SimilarArgs& A, hipStream_t st, Timing* tm) {
@@ -401,11 +396,10 @@ hipError_t launch_similar(const SimilarArgs& A, hipStream_t st, Timing* tm) {
 }
 
 hipError_t launch_similar_rows(const SimilarArgs& A, hipStream_t st, Timing* tm) {
-  tm->begin("similar_rows", st);
+  Timing::Scope rec(tm, "similar_rows", st);
   const hipError_t e = A.coords ? launch_similar_g<true, true>(A, st) : launch_similar_g<false, true>(A, st);
   if (e != hipSuccess) return e;
-  tm->end(st);
-  return hipGetLastError();
+  return rec.close();
 }
 
 hipError_t launch_similar_fix_counts(const SimilarArgs& A, hipStream_t st) {

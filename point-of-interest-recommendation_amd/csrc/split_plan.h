@@ -17,3 +17,15 @@ inline SplitPlan plan_split(int rows, int units, int split_max, int grid_opt, in
   }
   return SplitPlan{1, s > limit ? limit : s};
 }
+
+// The item ranges of the walks that give every WAVE a range of its own (rank.hip, select.hip's score_rows): 8 waves per CU over the call's
+// `n_utile` 32-row tiles, at least 8 of the `ntile` item tiles per range, at least one range.  `cap` > 0 (poi_score_rank's "rank_grid")
+// caps the count; `tiles_max` > 0 (rank.hip's 16-bit per-lane counters) is the most tiles a range may hold, and wins over the cap.
+inline int plan_wave_ranges(int n_utile, int ntile, int num_cu, int cap, int tiles_max) {
+  int want = (num_cu * 8 + n_utile - 1) / n_utile;
+  if (want > ntile / 8) want = ntile / 8;
+  if (cap > 0 && want > cap) want = cap;
+  if (want < 1) want = 1;
+  if (tiles_max > 0 && want < (ntile + tiles_max - 1) / tiles_max) want = (ntile + tiles_max - 1) / tiles_max;
+  return want;
+}

@@ -79,7 +79,8 @@ def check_against_oracle(got, orc, what=""):
 # ---- the fused entry against the oracle ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n_item,n,dim,len_t,spatial", [
     (31, 31, 8, 1, False), (32, 31, 20, 3, True), (33, 33, 64, 1, True), (50, 70, 128, 3, False), (300, 33, 64, 3, True),
-    (300, 1, 20, 1, True), (2049, 70, 128, 1, True), (2049, 31, 8, 3, False), (2049, 33, 20, 3, True), (50, 31, 64, 1, False)])
+    (300, 1, 20, 1, True), (2049, 70, 128, 1, True), (2049, 31, 8, 3, False), (2049, 33, 20, 3, True), (50, 31, 64, 1, False),
+    (200, 33, 160, 1, True)])        # (the fourth dim bracket, 129 .. 256: one full row tile and a row, six item tiles and a tail)
 def test_rank_matches_the_oracle(pa, n_item, n, dim, len_t, spatial):
     seed = 7 * n_item + n + dim
     T, P, m, hts, sts, last = build(pa, seed, n, n_item, dim, spatial)

@@ -340,21 +340,91 @@ def _plan_call(family, n, num_cu, n_item, grid):
     return n, (n + 31) // 32, 8192, grid, 2, num_cu, ((ntile + 15) // 16 + 3) // 4, 1, 64
 
 
-def test_plan_split_reproduces_the_four_decisions(tmp_path):
+# the wave-range rule of poi_score_rank and poi_score_rows (plan_wave_ranges), and csrc/launch_common.h's dim brackets
+_WAVE_MAIN = r"""
+#include "split_plan.h"
+#include <stdio.h>
+int main() {
+  int a[5];
+  while (scanf("%d %d %d %d %d", a, a + 1, a + 2, a + 3, a + 4) == 5) printf("%d\n", plan_wave_ranges(a[0], a[1], a[2], a[3], a[4]));
+  return 0;
+}
+"""
+_BRACKET_MAIN = r"""
+#include "launch_common.h"
+#include <stdio.h>
+int main() {
+  int dim;
+  while (scanf("%d", &dim) == 1) {
+    const int b = dim_bracket(dim);
+    printf("%d %d %d\n", b, b < 0 ? -1 : (int)two_buffers(b, 64), b < 0 ? -1 : (int)two_buffers(b, 128));
+  }
+  return 0;
+}
+"""
+_RANK_TILES_MAX = 65535
+
+
+def _run_host(tmp_path, name, main_src, text):
+    """Compile a host program against csrc's headers with the plain C++ compiler and run it on `text`: the integers of every output line."""
     import shutil
     import subprocess
     cxx = shutil.which("c++") or shutil.which("g++") or poi_amd.build._hipcc()
-    src, exe = str(tmp_path / "plan_main.cpp"), str(tmp_path / "plan_main")
-    open(src, "w").write(_PLAN_MAIN)
+    src, exe = str(tmp_path / (name + ".cpp")), str(tmp_path / name)
+    open(src, "w").write(main_src)
     subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O1", "-I", _csrc(), src, "-o", exe], check=True)
+    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
+    return [tuple(int(v) for v in line.split()) for line in out if line]
+
+
+def _wave_ranges_before(entry, n, num_cu, n_item, rank_grid):
+    """n_split as poi_score_rank and score_rows_split spelled it out before plan_wave_ranges."""
+    n_utile, ntile = (n + 31) // 32, (n_item + 31) // 32
+    want = _c_div(num_cu * 8 + n_utile - 1, n_utile)
+    if want > ntile // 8:
+        want = ntile // 8
+    if entry == "rows":
+        return 1 if want < 1 else want
+    if rank_grid > 0 and want > rank_grid:
+        want = rank_grid
+    if want < 1:
+        want = 1
+    if want < (ntile + _RANK_TILES_MAX - 1) // _RANK_TILES_MAX:
+        want = (ntile + _RANK_TILES_MAX - 1) // _RANK_TILES_MAX
+    return want
+
+
+def test_plan_split_reproduces_the_four_decisions(tmp_path):
     cases = [(f, n, cu, ni, g) for f in ("near", "group", "route", "diverse") for n in (1, 2, 31, 32, 33, 256, 257, 8192, 8193) for cu in (8, 256)
              for ni in (40, 5000, 200000) for g in (0, 1, 64, 100)]
     text = "".join("%d %d %d %d %d %d %d %d %d\n" % _plan_call(*c) for c in cases)
-    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
-    got = [tuple(int(v) for v in line.split()) for line in out if line]
+    got = _run_host(tmp_path, "plan_main", _PLAN_MAIN, text)
     assert len(got) == len(cases)
     for c, g in zip(cases, got):
         assert g == _plan_before(*c), (c, g, _plan_before(*c))
     # every branch is in the table: both paths, the cap, the floor, the limit, the grid option taken as given
     want = [_plan_before(*c) for c in cases]
     assert {w[0] for w in want} == {0, 1} and {1, 2, 64} <= {w[1] for w in want}
+
+    # the wave ranges of rank and score_rows: one rule, rank's "rank_grid" cap and counter floor as arguments
+    wcases = [(e, n, cu, ni, g) for e in ("rank", "rows") for n in (1, 32, 33, 4096, 100000) for cu in (8, 256)
+              for ni in (40, 256, 5000, 200000, 3000000) for g in ((0, 1, 7, 4096) if e == "rank" else (0,))]
+    text = "".join("%d %d %d %d %d\n" % ((n + 31) // 32, (ni + 31) // 32, cu, g, _RANK_TILES_MAX if e == "rank" else 0) for e, n, cu, ni, g in wcases)
+    got = _run_host(tmp_path, "wave_main", _WAVE_MAIN, text)
+    assert len(got) == len(wcases)
+    for c, g in zip(wcases, got):
+        assert g == (_wave_ranges_before(*c),), (c, g, _wave_ranges_before(*c))
+    # the 8-tile cap, the grid cap, the floor of one range and the counter floor (above the grid cap) are all in the table
+    wwant = {c: _wave_ranges_before(*c) for c in wcases}
+    assert wwant[("rank", 1, 256, 40, 0)] == 1 and wwant[("rank", 1, 256, 5000, 0)] == 19 and wwant[("rank", 1, 256, 200000, 7)] == 7
+    assert wwant[("rank", 1, 8, 3000000, 1)] == 2 and wwant[("rows", 1, 8, 3000000, 0)] == 64
+
+
+def test_dim_bracket_table(tmp_path):
+    """Every launcher of the tile-walk families picks its <D8, DB> instantiation through dim_bracket and two_buffers."""
+    dims = (4, 32, 36, 64, 68, 128, 132, 256, 260, 0)
+    got = _run_host(tmp_path, "bracket_main", _BRACKET_MAIN, "".join("%d\n" % d for d in dims))
+    assert [g[0] for g in got] == [0, 0, 1, 1, 2, 2, 3, 3, -1, -1]
+    # two buffers up to dim 64 (most families) / up to dim 128 (rank, score_rows, score_lists)
+    assert [g[1] for g in got[:8]] == [1, 1, 1, 1, 0, 0, 0, 0]
+    assert [g[2] for g in got[:8]] == [1, 1, 1, 1, 1, 1, 0, 0]
