@@ -203,6 +203,8 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * Additive to 9: "xfwd_ids_lds" - 1 when the launch took the table form of the exact forward recurrence with its row ids staged in LDS
  * (option of the same name), 0 with the ids loaded inside the step loop or without the table form; poi_gru_predict records its own value
  * of this one key.
+ * Additive to 9: "stream_hints" - 1 when the 16-sequence tiles of the launch's exact forward recurrence stored G, H and RH non-temporally
+ * (option of the same name), 0 otherwise.
  * Additive to 9: "filter_path" (1 walk, 2 gather), "filter_splits" (slices, 0 outside the split regime), "filter_split_max" - written
  * by poi_score_topk_filtered.
  * Additive to 9: "audience_path" (0 one workgroup per query block, 1 slices), "audience_splits" (slices, 0 outside the split regime),
@@ -267,6 +269,10 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *       te_rec_fwd1xi) stage the table-row ids of their sequences' steps in LDS once per tile / sequence instead of loading them inside the step
  *       loop, where the wait for them also drained the step's stores - bitwise the same update; 0, or an id table that does not fit the
  *       kernel's LDS (16-sequence tiles at dim 128: more than 133 steps), takes the in-loop loads;
+ *   "stream_hints" 0|1 (default 1), "stream_hints_min" n (default 2560): in training launches of at least n sequences (dim 128; 2 n at dim 64:
+ *       the bound is one of bytes) the 16-sequence tiles of the exact forward recurrence store the per-step rows G, H and RH - written once, read by later kernels only - with the
+ *       non-temporal policy, so that they do not displace the forward table's rows from the caches - bitwise the same update; smaller launches
+ *       keep plain stores (their rows stay on-die for the backward recurrence);
  *   "head_split" 0|1 (default 1): the training head (public/GRU_Spatial.py:180-200, <= 256 bins) on bf16 split products (te_head3)
  *       instead of float32-input matrix instructions;
  *   "early_bins" 0|1 (default 1): the distance-bin rows' write-back chain starts next to the d x product instead of at the tail;

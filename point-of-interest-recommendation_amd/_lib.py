@@ -299,7 +299,7 @@ PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", 
              "near_path", "near_splits", "near_split_max", "rank_splits", "geoie_score_span", "geoie_score_splits",
              "group_path", "group_splits", "group_split_max", "route_path", "route_splits",
              "diverse_path", "diverse_splits", "diverse_split_max",
-             "select_rows_per_chunk", "select_chunks", "select_path", "select_splits", "xfwd_ids_lds",
+             "select_rows_per_chunk", "select_chunks", "select_path", "select_splits", "xfwd_ids_lds", "stream_hints",
              "filter_path", "filter_splits", "filter_split_max", "audience_path", "audience_splits", "audience_split_max",
              "similar_path", "similar_splits", "similar_split_max", "capped_splits", "capped_split_max", "lists_path",
              "labels_splits", "labels_split_max", "labels_home", "labels_chunks", "labels_rows_per_chunk")
@@ -391,7 +391,7 @@ class Context:
         self.check(self.lib.poi_ctx_set_exact_forward(self.handle, 1 if on else 0, int(per_sequence_max)))
 
     def set_option(self, name, value):
-        """Named tuning switch of the tile engine (poi_ctx_set_option: "forward_table_compact", "forward_table_compact_min", "xfwd_ids_lds", "head_split",
+        """Named tuning switch of the tile engine (poi_ctx_set_option: "forward_table_compact", "forward_table_compact_min", "xfwd_ids_lds", "stream_hints", "stream_hints_min", "head_split",
         "early_bins", "hot_bins", "hybrid", "hybrid_min", "hybrid_max", "hybrid_force"; "cell_grid" of poi_cell_step; "session_tile_min" of poi_session_advance;
         "near_split_max" / "near_grid" of poi_score_topk_near; "rank_grid" of poi_score_rank; "geoie_score_span" of
         poi_geoie_score_all_geo / poi_geoie_score_topk_geo; "group_split_max" / "group_grid" of poi_group_topk; "route_split_max" / "route_grid" of

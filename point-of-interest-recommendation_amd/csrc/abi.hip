@@ -111,6 +111,7 @@ int poi_ctx_create(poi_ctx** out, int device) {
   if (const char* e = getenv("POI_TE_PPOI")) c->ppoi = atoi(e) != 0;
   if (const char* e = getenv("POI_TE_EARLY_BINS")) c->early_bins = atoi(e) != 0;
   if (const char* e = getenv("POI_TE_HOTBINS")) c->hot_bins = atoi(e) != 0;
+  if (const char* e = getenv("POI_TE_STREAM")) c->stream_hints = atoi(e) != 0;
   if (const char* e = getenv("POI_TE_HYBRID")) c->hybrid = atoi(e) != 0;
   if (const char* e = getenv("POI_TE_HOT_EARLY")) c->hot_early = atoi(e) != 0;
   if (const char* e = getenv("POI_TE_HYB_MIN")) c->hyb_min = atoi(e);
@@ -261,6 +262,9 @@ static int te_setup(poi_ctx* c, poi::TeArgs& A, const poi_gru_params* P, const p
   const bool want_ft = c->fwd_tab && !A.rec32 && 2 * (size_t)(P->n_item + 1) <= Tcap;
   A.fwd_tab = (!A.xfwd && want_ft && A.bintab && !A.rec1) ? 1 : 0;      // (the per-sequence kernels read G)
   A.xrec1 = (A.xfwd && D <= 128 && n <= c->xrec1_max && !A.hyb) ? 1 : 0;      // one workgroup per sequence, float64 on the vector ALUs (te_rec_fwd1x)
+  // (the 16-sequence tiles of te_rec_fwdx store G, H, RH non-temporally - large launches only: a small launch's rows stay on-die for te_rec_bwd, and a
+  // row of dim 64 is half the bytes: stream_min counts sequences of dim 128; POI_TE_DBG bit 16384: plain stores, for A/B runs)
+  A.stream_hints = (c->stream_hints && A.xfwd && D <= 128 && !A.xrec1 && !predict && (size_t)n * D >= (size_t)c->stream_min * 128 && !(A.dbg & 16384)) ? 1 : 0;
   // (the table over the launch's step-input POIs only - te_slots marks them for the per-POI regrouping - never has more rows than the launch has steps)
   const bool want_xc = c->xcomp && A.ppoi && P->n_item + 1 <= (1 << 22) && n >= c->xcomp_min;
   A.xft = (A.xfwd && (want_ft || want_xc) && n > 1) ? 1 : 0;      // (n == 1: the one-sequence path writes gx itself, te_one_in; the per-sequence kernel has a table variant too)
@@ -468,7 +472,7 @@ static int seq_step(poi_ctx* c, const poi_gru_params* P, const poi_seq_tables* T
     {
       poi_ctx::LastPlan& R = c->plan;
       R.tile = 1; R.one = one; R.rec1 = E.rec1; R.xrec1 = E.xrec1; R.hyb = E.hyb; R.bintab = E.bintab; R.ppoi = E.ppoi; R.listed = E.urow != nullptr;
-      R.fwd_tab = E.fwd_tab; R.xft = E.xft; R.xcomp = E.xcomp; R.xfwd_ids_lds = E.xid_cap > 0; R.head_split = E.head_split; R.efuse = one ? 0 : E.efuse; R.early_bins = E.early_bins;
+      R.fwd_tab = E.fwd_tab; R.xft = E.xft; R.xcomp = E.xcomp; R.xfwd_ids_lds = E.xid_cap > 0; R.stream_hints = one ? 0 : E.stream_hints; R.head_split = E.head_split; R.efuse = one ? 0 : E.efuse; R.early_bins = E.early_bins;
       R.hyb_dev = E.hyb_dev; R.st = st; R.ws_gen = c->te_ws_gen;      // (fork: launch_te_scatter)
     }
     // captured: a replay re-issues the launch id this launch got when it was captured - atomicMax against whatever a LATER launch left in xflag
@@ -513,7 +517,7 @@ static int seq_step(poi_ctx* c, const poi_gru_params* P, const poi_seq_tables* T
       // word they overlapped and early_min was missing), plus what te_setup derived from them for THIS launch
       const uint64_t sw[] = {(uint64_t)c->fwd_tab, (uint64_t)c->rec_split, (uint64_t)c->one_path, (uint64_t)(unsigned)c->rec1_max, (uint64_t)(unsigned)c->bintab_min,
                              (uint64_t)c->early_bins, (uint64_t)(unsigned)c->early_min, (uint64_t)c->xfwd, (uint64_t)E.early_bins, (uint64_t)E.bintab, (uint64_t)E.rec1,
-                             (uint64_t)E.fwd_tab, (uint64_t)E.xfwd, (uint64_t)E.xft, (uint64_t)E.xrec1, (uint64_t)E.xcomp, (uint64_t)(unsigned)E.xid_cap, (uint64_t)(unsigned)c->xcomp_min, (uint64_t)E.head_split, (uint64_t)(unsigned)c->xrec1_max, (uint64_t)E.ppoi, (uint64_t)one, (uint64_t)E.hyb, (uint64_t)E.efuse, (uint64_t)E.hot_early};
+                             (uint64_t)E.fwd_tab, (uint64_t)E.xfwd, (uint64_t)E.xft, (uint64_t)E.xrec1, (uint64_t)E.xcomp, (uint64_t)(unsigned)E.xid_cap, (uint64_t)(unsigned)c->xcomp_min, (uint64_t)E.head_split, (uint64_t)(unsigned)c->xrec1_max, (uint64_t)E.ppoi, (uint64_t)one, (uint64_t)E.hyb, (uint64_t)E.efuse, (uint64_t)E.hot_early, (uint64_t)E.stream_hints};
       add(sw, sizeof sw);
     }
     poi_ctx::StepGraph* g = nullptr;
@@ -735,7 +739,7 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
   if (!c || !name) return fail(c, POI_EINVAL, "poi_ctx_set_option: null argument");
   struct Opt { const char* name; int* p; int lo, hi; };
   const Opt opts[] = {{"forward_table_compact", &c->xcomp, 0, 1}, {"forward_table_compact_min", &c->xcomp_min, 0, 1 << 30}, {"xfwd_ids_lds", &c->xids_lds, 0, 1}, {"head_split", &c->head3, 0, 1},
-                      {"early_bins", &c->early_bins, 0, 1}, {"hot_bins", &c->hot_bins, 0, 1}, {"hybrid", &c->hybrid, 0, 1}, {"hybrid_min", &c->hyb_min, 0, 1 << 30}, {"hybrid_max", &c->hyb_max, 0, 1 << 30}, {"hybrid_force", &c->hyb_force, 0, 1 << 30},
+                      {"early_bins", &c->early_bins, 0, 1}, {"hot_bins", &c->hot_bins, 0, 1}, {"stream_hints", &c->stream_hints, 0, 1}, {"stream_hints_min", &c->stream_min, 0, 1 << 30}, {"hybrid", &c->hybrid, 0, 1}, {"hybrid_min", &c->hyb_min, 0, 1 << 30}, {"hybrid_max", &c->hyb_max, 0, 1 << 30}, {"hybrid_force", &c->hyb_force, 0, 1 << 30},
                       {"cell_grid", &c->cell_grid, 0, 1 << 30}, {"vbpr_grid", &c->vbpr_grid, 0, 1 << 30}, {"session_tile_min", &c->sess_tile_min, 1, 1 << 30},
                       {"near_split_max", &c->near_split_max, 0, 1 << 30}, {"near_grid", &c->near_grid, 0, NEAR_SPLIT_LIMIT},
                       {"rank_grid", &c->rank_grid, 0, 1 << 30}, {"geoie_score_span", &c->geo_span, 0, 1 << 30},
@@ -827,7 +831,7 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
   static const struct { const char* name; int poi_ctx::LastPlan::*f; } flags[] = {
       {"tile", &poi_ctx::LastPlan::tile}, {"one", &poi_ctx::LastPlan::one}, {"rec1", &poi_ctx::LastPlan::rec1}, {"xrec1", &poi_ctx::LastPlan::xrec1},
       {"hyb", &poi_ctx::LastPlan::hyb}, {"bintab", &poi_ctx::LastPlan::bintab}, {"ppoi", &poi_ctx::LastPlan::ppoi}, {"listed", &poi_ctx::LastPlan::listed},
-      {"fwd_tab", &poi_ctx::LastPlan::fwd_tab}, {"xft", &poi_ctx::LastPlan::xft}, {"xcomp", &poi_ctx::LastPlan::xcomp}, {"xfwd_ids_lds", &poi_ctx::LastPlan::xfwd_ids_lds},
+      {"fwd_tab", &poi_ctx::LastPlan::fwd_tab}, {"xft", &poi_ctx::LastPlan::xft}, {"xcomp", &poi_ctx::LastPlan::xcomp}, {"xfwd_ids_lds", &poi_ctx::LastPlan::xfwd_ids_lds}, {"stream_hints", &poi_ctx::LastPlan::stream_hints},
       {"head_split", &poi_ctx::LastPlan::head_split}, {"efuse", &poi_ctx::LastPlan::efuse}, {"early_bins", &poi_ctx::LastPlan::early_bins},
       {"fork", &poi_ctx::LastPlan::fork}, {"cell_kernel", &poi_ctx::LastPlan::cell_kernel}, {"cell_grid", &poi_ctx::LastPlan::cell_grid},
       {"session_path", &poi_ctx::LastPlan::session_path}, {"session_tiles", &poi_ctx::LastPlan::session_tiles},

@@ -65,6 +65,8 @@ struct poi_ctx {
   int xcomp = 1;            // exact forward table over the step-input POIs only; POI_TE_XCOMP=0: every row of the POI table (A/B)
   int xcomp_min = 1536;     // ... for launches of at least this many sequences (below: one row per step - the table form of te_rec_fwdx costs 0.6 us more per step of the latency chain than the ranking saves in te_gemmx; 1300 / 1563 / 2048 / 3125 users: +9 / -6 / -38 / -45 us); POI_TE_XCOMP_MIN
   int xids_lds = 1;         // option "xfwd_ids_lds": the table-form recurrences of the exact forward stage their table-row ids in LDS (TeArgs.xid_cap) instead of loading them inside the step loop; POI_TE_XIDS_LDS=0 (A/B)
+  int stream_hints = 1;     // option "stream_hints": the forward recurrence's tiles store the write-once rows G, H, RH non-temporally (TeArgs.stream_hints); POI_TE_STREAM=0 / POI_TE_DBG bit 16384 (A/B)
+  int stream_min = 2560;    // ... in launches of at least this many sequences at dim 128, twice as many at dim 64 (option "stream_hints_min"; dim 128, 12500 / 4096 / 2560 users: -38 / -10 / -5 us per launch, 2304 / 1563: +8 / +3 - the rows of a small launch stay on-die for te_rec_bwd; dim 64, 12500 / 4096 / 2560: -36 / +4 / +9)
   int efuse = 1;            // E = lt[p'] - lt[q'] gathered inside te_head3 (dim 128) instead of written by te_gather and read back twice; POI_TE_EFUSE
   int head3 = 1;            // training head on split products for <= 256 bins (te_head3); POI_TE_HEAD3
   int xrec1_max = 1100;     // ... launches of at most this many sequences run its recurrence per sequence in float64 on the vector ALUs (te_rec_fwd1x); POI_TE_XREC1
@@ -83,7 +85,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, xfwd_ids_lds, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max, select_rows_per_chunk, select_chunks, select_path, select_splits, filter_path, filter_splits, filter_split_max, audience_path, audience_splits, audience_split_max, similar_path, similar_splits, similar_split_max, capped_splits, capped_split_max, lists_path, labels_splits, labels_split_max, labels_home, labels_chunks, labels_rows_per_chunk; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, xfwd_ids_lds, stream_hints, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max, select_rows_per_chunk, select_chunks, select_path, select_splits, filter_path, filter_splits, filter_split_max, audience_path, audience_splits, audience_split_max, similar_path, similar_splits, similar_split_max, capped_splits, capped_split_max, lists_path, labels_splits, labels_split_max, labels_home, labels_chunks, labels_rows_per_chunk; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR

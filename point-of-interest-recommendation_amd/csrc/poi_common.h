@@ -88,6 +88,17 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// ---- streaming stores of the training chain (TeArgs.stream_hints; DESIGN.md section 5, "Stream, reused, handoff") ---------------------
+// A packed row that a kernel writes once and never reads back is stored with the non-temporal policy (`nt` on the instruction), so that
+// its lines do not displace the table rows the same kernel gathers at random.  NT is a template parameter of the kernel (the launcher
+// chooses the instance): false is the plain store, the code there was before.  A hint moves no value and reorders no sum.
+typedef float st_f32x4 __attribute__((ext_vector_type(4)));
+template <bool NT>
+__device__ __forceinline__ void st_store4(float* p, float a, float b, float c, float d) {
+  if constexpr (NT) __builtin_nontemporal_store(st_f32x4{a, b, c, d}, reinterpret_cast<st_f32x4*>(p));
+  else *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
+}
+
 // Block-wide (256 threads) reductions; `red` is an LDS array of >= POI_NWAVE floats.  Contains barriers.
 __device__ __forceinline__ float block_sum(float v, float* red) {
   v = wave_sum(v);

@@ -147,6 +147,7 @@ struct TeArgs {
   int* dcc0;                          // exclusive scan of the COLD bins' chunk counts (+ total): te_dsum's work list
   float* dpart2; int *dnf, *dnf2, *dbn;   // super-chunk partial sums; distinct-sequence counts per chunk / super-chunk / bin
   int dbg;                            // tuning switch (POI_TE_DBG), 0 in production
+  int stream_hints;                   // 1: the tile kernels of the exact forward recurrence (dims 64 / 128) store G, H and RH non-temporally (te_rec_fwdx(i)_kernel_nt); option "stream_hints" / POI_TE_DBG bit 16384 (A/B)
   int early_bins; float bin_alpha, bin_lambda;      // the distance-bin chain of the write-back starts on the side stream behind te_wgrad (launch_te_train)
   // packed-row workspace
   int *soff, *row_src, *row_t, *row_p, *row_dp, *row_ab;   // packed row -> CSR position, step index, input table rows (lt, di)
@@ -232,7 +233,7 @@ struct TeArgs {
 #define TE_ENT_GH 0x20000000      // + g[row-1] * h[row-1]
 #define TE_ENT_NEG 0x40000000     // the g*h term enters with a minus sign (negative sample)
 #define TE_ENT_FIRST 0x80000000u  // first entry of its sequence within the row segment
-#define TE_HYB_NMAX 4096          // hybrid recurrences: te_scan keeps the launch's step counts in LDS for the split
+#define TE_HYB_NMAX 4096         // hybrid recurrences: te_scan keeps the launch's step counts in LDS for the split
 #define TE_PSUM_WG 1024          // workgroups of te_psum = chunk partials of a hot bin: device-independent (was num_cu * 4)
 #define TE_HB 4                   // hot distance bins summed by te_psum (TeArgs.dhot)
 #define TE_HOT_BIN_MIN 4096       // ... when they hold at least this many steps of the launch

@@ -370,7 +370,9 @@ struct XG12 { double v[12]; };
 // and of the peeled first step pessimistically, and the write acknowledgement of the step's five 16-byte stores stands in front of the next
 // step's table-row loads (rule 2).  Without a vector-memory result at the loop top every wait of the loop is counted and the
 // stores stay in flight across the step boundary.
-template <int D, bool FT, bool PRED, bool IDL>      // PRED: poi_gru_predict - all L positions, no per-step stores, the final state -> hts
+// NT (training only; TeArgs.stream_hints): the step's five 16-byte stores of G, H and RH - rows nothing in this kernel reads back - are
+// non-temporal (poi_common.h st_store4); same instructions in the same places otherwise, the counted waits of the loop do not move.
+template <int D, bool FT, bool PRED, bool IDL, bool NT = false>      // PRED: poi_gru_predict - all L positions, no per-step stores, the final state -> hts
 __device__ __forceinline__ void te_rec_fwdx_body(const TeArgs& A) {
   constexpr int KB = D / 64, NW = D / 16, SR = 3, SL = XS - SR, LDP = D + 16, PSZ = 16 * LDP;
   static_assert(FT || !IDL, "te_rec_fwdx: the per-step-row form has no ids");
@@ -515,8 +517,8 @@ __device__ __forceinline__ void te_rec_fwdx_body(const TeArgs& A) {
       }
       put_digits(RHq, rh);
       if constexpr (!PRED) {
-        *reinterpret_cast<float4*>(A.G + row * 3 * D + D + u0) = make_float4(rv4[0], rv4[1], rv4[2], rv4[3]);
-        *reinterpret_cast<float4*>(A.RH + row * D + u0) = make_float4(rh4[0], rh4[1], rh4[2], rh4[3]);
+        st_store4<NT>(A.G + row * 3 * D + D + u0, rv4[0], rv4[1], rv4[2], rv4[3]);
+        st_store4<NT>(A.RH + row * D + u0, rh4[0], rh4[1], rh4[2], rh4[3]);
       }
     }
     XP(2)
@@ -538,9 +540,9 @@ __device__ __forceinline__ void te_rec_fwdx_body(const TeArgs& A) {
     }
     put_digits(Hq, hcur);
     if constexpr (!PRED) {
-      *reinterpret_cast<float4*>(A.G + row * 3 * D + u0) = make_float4(z4[0], z4[1], z4[2], z4[3]);
-      *reinterpret_cast<float4*>(A.G + row * 3 * D + 2 * D + u0) = make_float4(c4[0], c4[1], c4[2], c4[3]);
-      *reinterpret_cast<float4*>(A.H + row * D + u0) = make_float4(h4[0], h4[1], h4[2], h4[3]);
+      st_store4<NT>(A.G + row * 3 * D + u0, z4[0], z4[1], z4[2], z4[3]);
+      st_store4<NT>(A.G + row * 3 * D + 2 * D + u0, c4[0], c4[1], c4[2], c4[3]);
+      st_store4<NT>(A.H + row * D + u0, h4[0], h4[1], h4[2], h4[3]);
     }
     XP(6)
     lds_barrier();
@@ -623,6 +625,11 @@ template <int D, bool FT, bool PRED = false>
 __global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel(TeArgs A) { te_rec_fwdx_body<D, FT, PRED, false>(A); }
 template <int D, bool PRED = false>      // the forward-table form with the tile's ids in LDS
 __global__ __launch_bounds__(D * 4) void te_rec_fwdxi_kernel(TeArgs A) { te_rec_fwdx_body<D, true, PRED, true>(A); }
+// the training instances with non-temporal stores (kernels of their own names: the plain ones keep theirs)
+template <int D, bool FT>
+__global__ __launch_bounds__(D * 4) void te_rec_fwdx_kernel_nt(TeArgs A) { te_rec_fwdx_body<D, FT, false, false, true>(A); }
+template <int D>
+__global__ __launch_bounds__(D * 4) void te_rec_fwdxi_kernel_nt(TeArgs A) { te_rec_fwdx_body<D, true, false, true, true>(A); }
 
 // -------------------------------------------------------------------------------------------------
 // te_rec_fwd1x: the exact forward recurrence of ONE sequence per workgroup on the vector ALUs, in float64 - small launches (at most one
@@ -1000,6 +1007,13 @@ template <int D> struct XRec {
   }
   template <bool FT, bool PRED> static void launch(const TeArgs& A, hipStream_t st) {
     const dim3 grid((A.n_seq + 15) / 16);
+    if constexpr (!F64 && !PRED) {      // non-temporal G / H / RH stores (dims 64 / 128; dim 256 stays plain: DESIGN.md section 5)
+      if (A.stream_hints) {
+        if (FT && A.xid_cap > 0) hipLaunchKernelGGL((te_rec_fwdxi_kernel_nt<D>), grid, block(), lds(A.xid_cap), st, A);
+        else hipLaunchKernelGGL((te_rec_fwdx_kernel_nt<D, FT>), grid, block(), lds(), st, A);
+        return;
+      }
+    }
     if (FT && A.xid_cap > 0) {
       if constexpr (F64) hipLaunchKernelGGL((te_rec_fwddi_kernel<D, PRED>), grid, block(), lds(A.xid_cap), st, A);
       else hipLaunchKernelGGL((te_rec_fwdxi_kernel<D, PRED>), grid, block(), lds(A.xid_cap), st, A);
@@ -1026,9 +1040,14 @@ static hipError_t te_xfwd_t(const TeArgs& A, int num_cu, hipStream_t st, Timing*
   static DeviceOnce once;
   {
     const hipError_t oe = once.run([&]() -> hipError_t {
-      const void* fns[7] = {XRec<D>::template fn<false, false>(), XRec<D>::template fn<true, false>(), XRec<D>::template fn<false, true>(), XRec<D>::template fn<true, true>(),
-                            XRec<D>::template fn_ids<false>(), XRec<D>::template fn_ids<true>(), reinterpret_cast<const void*>(&te_gemmx_kernel<D>)};
+      const void* fns[10] = {XRec<D>::template fn<false, false>(), XRec<D>::template fn<true, false>(), XRec<D>::template fn<false, true>(), XRec<D>::template fn<true, true>(),
+                             XRec<D>::template fn_ids<false>(), XRec<D>::template fn_ids<true>(), reinterpret_cast<const void*>(&te_gemmx_kernel<D>), nullptr, nullptr, nullptr};
+      if constexpr (!XRec<D>::F64) {
+        fns[7] = reinterpret_cast<const void*>(&te_rec_fwdx_kernel_nt<D, false>); fns[8] = reinterpret_cast<const void*>(&te_rec_fwdx_kernel_nt<D, true>);
+        fns[9] = reinterpret_cast<const void*>(&te_rec_fwdxi_kernel_nt<D>);
+      }
       for (const void* f : fns) {
+        if (!f) continue;
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, XLDS_OPT_IN);
         if (e != hipSuccess) return e;
       }
