@@ -267,6 +267,7 @@ hipError_t launch_te_predict(TeArgs& A, int num_cu, hipStream_t st, Timing* tm);
 bool te_xfwd_supported(int D);
 int te_xfwd_ids_cap(int D, int steps, bool per_sequence);      // TeArgs.xid_cap for sequences of at most `steps` steps: steps + 1, or 0 when the id table does not fit the kernel's LDS
 hipError_t launch_te_xfwd(const TeArgs& A, int num_cu, hipStream_t st, Timing* tm, int phase);      // te_xfwd.hip: phase 0 = input product, 1 = recurrence
+hipError_t launch_te_xsts(const TeArgs& A, int num_cu, hipStream_t st);      // te_xfwd.hip: predict's sts = softmax(vs . hts + bs) in float64 (exact forward)
 hipError_t launch_rows_apply(const SeqArgs& A, bool spatial, int grid, float alpha, float lambda, hipStream_t st, Timing* tm);
 hipError_t launch_dense_apply(const SeqArgs& A, bool spatial, int n_slab, int n_slab_head, float alpha, float lambda, hipStream_t st, Timing* tm);
 

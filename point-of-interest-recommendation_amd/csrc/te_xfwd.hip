@@ -19,7 +19,8 @@
 //
 // Kernels: te_xpack (weights -> digit planes in MFMA fragment order + per-row scales, once per launch), te_xztab (distance-bin half
 // of the input product + bias per bin, float64 FMAs), te_gemmx (POI half of the input product: table rows or gathered step rows),
-// te_rec_fwdx (the recurrence, 16-sequence tiles as te_rec_fwd16; same outputs: G := z | r | c, H, RH in float32 for the head and BPTT).
+// te_rec_fwdx (the recurrence, 16-sequence tiles as te_rec_fwd16; same outputs: G := z | r | c, H, RH in float32 for the head and BPTT),
+// te_xsts (predict: the bin probabilities from the final states, float64).
 #include "poi_common.h"
 #include "poi_kernels.h"
 
@@ -974,6 +975,89 @@ template <int D, bool FT, bool PRED = false>
 __global__ __launch_bounds__(D * 2) void te_rec_fwdd_kernel(TeArgs A) { te_rec_fwdd_body<D, FT, PRED, false>(A); }
 template <int D, bool PRED = false>      // the forward-table form with the tile's ids in LDS
 __global__ __launch_bounds__(D * 2) void te_rec_fwddi_kernel(TeArgs A) { te_rec_fwdd_body<D, true, PRED, true>(A); }
+
+// -------------------------------------------------------------------------------------------------
+// te_xsts: the bin probabilities of predict, sts[r] = softmax(vs . hts[r] + bs), in float64 from the float32 final states the exact
+// recurrence stored.  The float32 head of predict (te_head, mode 1) accumulates the D-term logits in float32: with saturated states
+// (|h| ~ 1, |logit| ~ 14) at dim 256 that alone is 2e-6 .. 3e-6 of the largest probability - more than the whole exact forward pass
+// leaves (3e-8 on hts; tests/test_gpu_xfwd_ranges.py).  Here: a workgroup takes R sequences; a wave takes a bin, its lanes the
+// k-slices of the bin's vs row (one coalesced row read for R sequences), float64 FMAs (products of float32 values are exact), the
+// logits of the R rows in LDS, max / sum / exp (libm) in float64, one float32 rounding at the store.  What is left is the float32
+// rounding of hts itself (~6e-8).  A NaN state (a flagged launch) comes out as NaN probabilities.
+// -------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double x_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <int R>
+__global__ __launch_bounds__(256) void te_xsts_kernel(TeArgs A) {
+  extern __shared__ __align__(16) double xs_lg[];      // R x NB logits -> exponentials
+  __shared__ float s_h[R][256];
+  __shared__ double s_red[R][4];
+  const int D = A.dim, NB = A.n_dist + 1, n = A.n_seq;
+  const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
+  for (int r0 = blockIdx.x * R; r0 < n; r0 += gridDim.x * R) {
+#pragma unroll
+    for (int q = 0; q < R; ++q) s_h[q][tid] = (tid < D && r0 + q < n) ? A.hts[(size_t)(r0 + q) * D + tid] : 0.f;
+    __syncthreads();
+    for (int b = w; b < NB; b += 4) {
+      const float* __restrict__ v = A.vs + (size_t)b * D;
+      double a[R];
+#pragma unroll
+      for (int q = 0; q < R; ++q) a[q] = 0.0;
+      for (int k = lane; k < D; k += 64) {
+        const double vk = (double)v[k];
+#pragma unroll
+        for (int q = 0; q < R; ++q) a[q] = __builtin_fma(vk, (double)s_h[q][k], a[q]);
+      }
+      const double bb = (double)A.bs[b];
+#pragma unroll
+      for (int q = 0; q < R; ++q) {
+        const double t = x_wave_sum(a[q]);
+        if (lane == 0) xs_lg[q * NB + b] = t + bb;
+      }
+    }
+    __syncthreads();
+    double m[R], sm[R];
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      double t = -__builtin_inf();
+      for (int b = tid; b < NB; b += 256) t = __builtin_fmax(t, xs_lg[q * NB + b]);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) t = __builtin_fmax(t, __shfl_xor(t, o, 64));
+      if (lane == 0) s_red[q][w] = t;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < R; ++q) m[q] = __builtin_fmax(__builtin_fmax(s_red[q][0], s_red[q][1]), __builtin_fmax(s_red[q][2], s_red[q][3]));
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      double t = 0.0;
+      for (int b = tid; b < NB; b += 256) { const double e = exp(xs_lg[q * NB + b] - m[q]); xs_lg[q * NB + b] = e; t += e; }      // (own entries: no barrier in between)
+      t = x_wave_sum(t);
+      if (lane == 0) s_red[q][w] = t;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      sm[q] = (s_red[q][0] + s_red[q][1]) + (s_red[q][2] + s_red[q][3]);
+      if (r0 + q < n)
+        for (int b = tid; b < NB; b += 256) A.sts[(size_t)(r0 + q) * NB + b] = (float)(xs_lg[q * NB + b] / sm[q]);
+    }
+    __syncthreads();      // s_h, s_red and the logits are free for the next rows
+  }
+}
+// (four sequences per workgroup up to 1024 bins - 32 KB of logits -, one beyond: 2048 bins are 16 KB)
+hipError_t launch_te_xsts(const TeArgs& A, int num_cu, hipStream_t st) {
+  if (!A.sts || !A.spatial || A.n_seq <= 0) return hipSuccess;
+  if (A.dim > 256) return hipErrorInvalidValue;
+  const int NB = A.n_dist + 1;
+  if (NB <= 1024) hipLaunchKernelGGL(te_xsts_kernel<4>, dim3(min((A.n_seq + 3) / 4, num_cu * 8)), dim3(256), sizeof(double) * 4 * NB, st, A);
+  else hipLaunchKernelGGL(te_xsts_kernel<1>, dim3(min(A.n_seq, num_cu * 8)), dim3(256), sizeof(double) * NB, st, A);
+  return hipGetLastError();
+}
 
 // -------------------------------------------------------------------------------------------------
 // host side

@@ -4243,7 +4243,9 @@ static hipError_t te_predict_t(TeArgs& A, int num_cu, hipStream_t st, Timing* tm
   }
   }
   hipError_t e = hipSuccess;
-  if (A.sts) e = te_head_dispatch<D>(A, 1, num_cu * 2 < tiles ? num_cu * 2 : tiles, st);
+  // (exact forward: the final states are good to 3e-8 - the bin probabilities from them in float64, te_xsts; the float32 head's logits alone cost 3e-6 at dim 256)
+  if (A.sts && A.xfwd) e = launch_te_xsts(A, num_cu, st);
+  else if (A.sts) e = te_head_dispatch<D>(A, 1, num_cu * 2 < tiles ? num_cu * 2 : tiles, st);
   tm->end(st);
   return e != hipSuccess ? e : hipGetLastError();
 }
