@@ -108,6 +108,8 @@ extern "C" {
  * "labels_split_max" / "labels_grid" / "labels_lds_kb" / "labels_ws_kb", plan keys "labels_splits" / "labels_split_max" / "labels_home" /
  * "labels_chunks" / "labels_rows_per_chunk", timing names "score_labels" / "score_topk_labels" / "labels_scores_call" (with "labels_max" /
  * "labels_walk" or "labels_scores", and "labels_finish" inside them) (existing entries unchanged). */
+/* additive to 9: leave-one-out attribution - new entry point poi_explain_loo, option "explain_start", plan keys "explain_columns" /
+ * "explain_tiles" / "explain_start", timing names "explain_base" / "explain_walk" (existing entries unchanged). */
 #define POI_ABI_VERSION 9
 
 enum {
@@ -216,7 +218,9 @@ int64_t poi_ctx_take_bad_ids(poi_ctx* ctx, void* stream);
  * Additive to 9: "labels_splits" (slices, 0 outside the split regime), "labels_split_max", "labels_home" (where the label accumulators of
  * the call lived: 1 the workgroup's LDS, 2 the context's global accumulator), "labels_chunks" / "labels_rows_per_chunk" (the rows went
  * through the accumulator workspace in this many chunks of this many rows) - written by poi_score_labels / poi_score_topk_labels /
- * poi_labels_scores. */
+ * poi_labels_scores.
+ * Additive to 9: "explain_columns" (base + variant columns of the call), "explain_tiles" (16-column workgroups of its two launches),
+ * "explain_start" (the start mode in force) - written by poi_explain_loo. */
 int poi_ctx_last_plan(poi_ctx* ctx, const char* key, int64_t* value);
 /* fp16 POI tables: declare that the device buffer [ptr, ptr + bytes) holds IEEE half elements.  From then on every entry point that is
  * handed a pointer INSIDE a registered buffer as its POI table (`lt` of poi_gru_params for poi_spatial_step / poi_gru_step /
@@ -339,7 +343,9 @@ int poi_ctx_set_exact_forward(poi_ctx* ctx, int on, int per_sequence_max);
  *       bytes; poi_labels_scores: one row) live in LDS and are flushed once while they fit n KiB, otherwise every candidate goes to the
  *       context's global accumulator with integer atomics - bitwise the same result on either side;
  *   "labels_ws_kb" n (default 262144 = 256 MiB): the global accumulator holds at most n KiB (whole 32-row tiles, at least one); more
- *       rows go through it in chunks.  Bitwise the same result for every n. */
+ *       rows go through it in chunks.  Bitwise the same result for every n;
+ *   "explain_start" 0 | 1 (default 1): poi_explain_loo starts a variant from the base walk's checkpoint before its first removed
+ *       position (1) or at position 0 from h = 0 (0).  Bitwise the same result on either side. */
 int poi_ctx_set_option(poi_ctx* ctx, const char* name, int value);
 /* Small launches: launches of at most max_sequences sequences (default 1800; 0 disables; dim 64 / 128) run the recurrence of every
  * sequence per workgroup on the vector ALUs (te_rec_fwd1 / bwd1, weights resident in registers; persistent since round 5: one workgroup per
@@ -902,6 +908,37 @@ int poi_session_advance(poi_ctx* ctx, const poi_gru_params* prm, const double* c
                         const int32_t* poi, int32_t n, float* hts_out, float* sts_out, void* stream);
 int poi_session_sts(poi_ctx* ctx, const poi_gru_params* prm, const double* h, int32_t n_slot, const int32_t* slot, int32_t n,
                     float* sts_out, void* stream);
+
+/* ---- leave-one-out attribution (additive to 9) ----------------------------------------------------------------------------------------
+ * WHY was POI j recommended: the score of j under the row's whole history minus its score with one check-in (or every visit of one
+ * POI) taken out.  prm / coords / cphi / thr / dd as poi_session_advance takes them (the evaluation snapshots; prm->wd is read by the
+ * spatial model).  Row r of n has the history h_ids[h_off[r] .. h_off[r + 1]) (total ids in all) and the list lists[r][0 .. n_list),
+ * n_list <= 32, -1 = no entry.  grp[t] is the GROUP of position t within its row (one per check-in: its index; one per distinct POI:
+ * the POI's rank by first occurrence); row r has the groups 0 .. g_off[r + 1] - g_off[r] - 1, and group g of row r is row
+ * g_off[r] + g of delta (n_group rows in all).
+ *   A VARIANT is the history without the positions of one group.  Its state is what a fresh poi_session_advance slot holds after the
+ * kept positions in order: the step after a removed check-in is binned against the last KEPT POI (n_dist without one), last_poi is
+ * the last kept POI (-1 without one), sts = softmax(vs h + bs).  score(v, j) = h_v . lt[j] + wd sts_v[bin(last_v, j)] (the term only
+ * for bins below n_dist and last_v >= 0, spatial only).  State, head, softmax and the dot product over the float32 / half row are
+ * float64.  base[r][c] = score(whole history, lists[r][c]); delta[g_off[r] + g][c] = base[r][c] - score(variant g, lists[r][c]):
+ * positive - the check-in pushed the POI up.  A -1 entry gives NaN in both.  A row without history has no variant; its base is the
+ * score of h = 0 without the distance term.  Optional h_out (n_group, dim), sts_out (n_group, n_dist + 1), last_out (n_group): the
+ * state of every variant.
+ *   Columns.  One persistent kernel walks 16 COLUMNS per workgroup with their states in LDS for all steps; a column is an int32
+ * quadruple (row, key, start, 0).  base_cols: n of them, key -1, one per row - walked first, they write base and keep h after every
+ * 16th position in a context workspace (n x floor((max_len - 1) / 16) x dim float64; max_len >= the longest history).  var_cols:
+ * n_var of them, key = the group removed, start = 16 floor(f / 16) for a group that first occurs at position f: the column starts
+ * there from the checkpoint (option "explain_start" 0: every column at 0 from h = 0 - the same bits).  Order both longest remaining
+ * walk first; columns of different rows share a workgroup.  A column outside these rules writes nothing.  The bits of a column do
+ * not depend on its workgroup, its neighbours or the start mode.
+ *   dim must be a multiple of 16 in [16, 256] (the shapes of the session tile kernel; every pad_dim model) - POI_ENOTSUP otherwise.
+ * A row with a history POI outside [0, n_item), a listed id outside [-1, n_item) or offsets outside [0, total] gives NaN in base, its
+ * deltas and its states and is counted once (poi_ctx_take_bad_ids).  poi_ctx_last_plan: "explain_columns", "explain_tiles",
+ * "explain_start".  Timing names: "explain_base", "explain_walk". */
+int poi_explain_loo(poi_ctx* ctx, const poi_gru_params* prm, const double* coords, const double* cphi, const double* thr, double dd,
+                    const int32_t* h_off, const int32_t* h_ids, int64_t total, const int32_t* grp, const int32_t* g_off, int32_t n_group,
+                    int32_t n, int32_t max_len, const int32_t* base_cols, const int32_t* var_cols, int32_t n_var, const int32_t* lists,
+                    int32_t n_list, double* base, double* delta, double* h_out, double* sts_out, int32_t* last_out, void* stream);
 
 /* ---- online sessions of the baselines Lstm / Rnn / CA-RNN (additive to 9) ------------------------------------------------------------
  * The same per-slot state, owned by the caller, for the three recurrent classes poi_session_advance does not cover: h (n_slot, D)

@@ -161,6 +161,9 @@ SIGNATURES = {
     "poi_session_advance": (c_int, [c_void_p, POINTER(GruParams), c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                     c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "poi_session_sts": (c_int, [c_void_p, POINTER(GruParams), c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "poi_explain_loo": (c_int, [c_void_p, POINTER(GruParams), c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
     "poi_session_cell_advance": (c_int, [c_void_p, POINTER(CellParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
                                          c_void_p]),
     "poi_session_carnn_advance": (c_int, [c_void_p, POINTER(CarnnParams), c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int32,
@@ -302,7 +305,8 @@ PLAN_KEYS = ("tile", "one", "rec1", "xrec1", "hyb", "bintab", "ppoi", "listed", 
              "select_rows_per_chunk", "select_chunks", "select_path", "select_splits", "xfwd_ids_lds", "stream_hints",
              "filter_path", "filter_splits", "filter_split_max", "audience_path", "audience_splits", "audience_split_max",
              "similar_path", "similar_splits", "similar_split_max", "capped_splits", "capped_split_max", "lists_path",
-             "labels_splits", "labels_split_max", "labels_home", "labels_chunks", "labels_rows_per_chunk")
+             "labels_splits", "labels_split_max", "labels_home", "labels_chunks", "labels_rows_per_chunk",
+             "explain_columns", "explain_tiles", "explain_start")
 
 
 class Context:
@@ -316,6 +320,7 @@ class Context:
             raise PoiError("poi_ctx_create(%d) failed: %s" % (device, self.lib.poi_last_error(None).decode()))
         self.handle = h
         self.device = int(device)
+        self.options = {}           # name -> value of every set_option() so far
 
     def check(self, rc):
         if rc != 0:
@@ -400,8 +405,9 @@ class Context:
         poi_score_topk_filtered; "audience_split_max" / "audience_grid" of poi_score_audience / poi_audience_rows; "similar_split_max" /
         "similar_grid" / "similar_rows_max" of poi_similar_topk / poi_similar_rows; "capped_split_max" / "capped_grid" of
         poi_score_topk_capped, "capped_hist_kb" of poi_labels_build; "labels_split_max" / "labels_grid" / "labels_lds_kb" / "labels_ws_kb" of
-        poi_score_labels / poi_score_topk_labels / poi_labels_scores)."""
+        poi_score_labels / poi_score_topk_labels / poi_labels_scores; "explain_start" of poi_explain_loo).  `options` keeps what was set."""
         self.check(self.lib.poi_ctx_set_option(self.handle, name.encode(), int(value)))
+        self.options[name] = int(value)
 
     def set_small_launch(self, max_sequences=1800):
         """Launches of at most this many sequences use the per-sequence recurrent kernels (poi_ctx_set_small_launch; 0 disables)."""

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libpoi_hip.so")
 SOURCES = ["abi.hip", "abi_train.hip", "abi_serve.hip", "seq_engine.hip", "exact_engine.hip", "tile_engine.hip", "te_scatter.hip", "te_xfwd.hip", "bpr.hip", "score_topk.hip", "score_filter.hip",
-           "misc.hip", "sync.hip", "carnn.hip", "fpmc.hip", "prme.hip", "geoie.hip", "geoie_score.hip", "poi2vec.hip", "cells.hip", "session.hip", "session_cells.hip", "vbpr.hip", "near.hip", "rank.hip", "group.hip", "route.hip", "diverse.hip", "select.hip", "filter.hip", "capped.hip", "labels.hip", "rerank.hip", "audience.hip", "similar.hip", "foldin.hip", "foldin_seq.hip", "foldin_p2v.hip", "topk_merge.hip"]
+           "misc.hip", "sync.hip", "carnn.hip", "fpmc.hip", "prme.hip", "geoie.hip", "geoie_score.hip", "poi2vec.hip", "cells.hip", "session.hip", "session_cells.hip", "explain.hip", "vbpr.hip", "near.hip", "rank.hip", "group.hip", "route.hip", "diverse.hip", "select.hip", "filter.hip", "capped.hip", "labels.hip", "rerank.hip", "audience.hip", "similar.hip", "foldin.hip", "foldin_seq.hip", "foldin_p2v.hip", "topk_merge.hip"]
 # every header next to the sources, and the public one: a unit is rebuilt when any of them changes
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "poi_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]

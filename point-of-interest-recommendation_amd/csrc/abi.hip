@@ -756,7 +756,8 @@ int poi_ctx_set_option(poi_ctx* c, const char* name, int value) {
                       {"capped_split_max", &c->capped_split_max, 0, 1 << 30}, {"capped_grid", &c->capped_grid, 0, CAPPED_SPLIT_LIMIT},
                       {"capped_hist_kb", &c->capped_hist_kb, 1, 1 << 21},
                       {"labels_split_max", &c->labels_split_max, 0, 1 << 30}, {"labels_grid", &c->labels_grid, 0, LABELS_SPLIT_LIMIT},
-                      {"labels_lds_kb", &c->labels_lds_kb, 0, LABELS_LDS_KB_MAX}, {"labels_ws_kb", &c->labels_ws_kb, 1, 1 << 30}};
+                      {"labels_lds_kb", &c->labels_lds_kb, 0, LABELS_LDS_KB_MAX}, {"labels_ws_kb", &c->labels_ws_kb, 1, 1 << 30},
+                      {"explain_start", &c->explain_start, 0, 1}};
   for (const Opt& o : opts)
     if (!strcmp(name, o.name)) {
       if (value < o.lo || value > o.hi) return fail(c, POI_EINVAL, "poi_ctx_set_option: %s must be in [%d, %d] (got %d)", name, o.lo, o.hi, value);
@@ -855,7 +856,9 @@ int poi_ctx_last_plan(poi_ctx* c, const char* key, int64_t* value) {
       {"lists_path", &poi_ctx::LastPlan::lists_path},
       {"labels_splits", &poi_ctx::LastPlan::labels_splits}, {"labels_split_max", &poi_ctx::LastPlan::labels_split_max},
       {"labels_home", &poi_ctx::LastPlan::labels_home}, {"labels_chunks", &poi_ctx::LastPlan::labels_chunks},
-      {"labels_rows_per_chunk", &poi_ctx::LastPlan::labels_rows_per_chunk}};
+      {"labels_rows_per_chunk", &poi_ctx::LastPlan::labels_rows_per_chunk},
+      {"explain_columns", &poi_ctx::LastPlan::explain_columns}, {"explain_tiles", &poi_ctx::LastPlan::explain_tiles},
+      {"explain_start", &poi_ctx::LastPlan::explain_start}};
   for (const auto& e : flags)
     if (!strcmp(key, e.name)) { *value = R.*e.f; return POI_OK; }
   static const char* const hyb_keys[] = {"hyb_fwd_seq", "hyb_fwd_wg", "hyb_bwd_seq", "hyb_bwd_wg"};      // the order of TeArgs.hyb_dev

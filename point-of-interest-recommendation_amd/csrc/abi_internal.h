@@ -85,7 +85,7 @@ struct poi_ctx {
   hipStream_t cap = nullptr;   // capture stream (the caller's stream may be the null stream, which cannot capture)
   DevBuf uidx_stage, out_stage;
   // the plan of the last training launch (poi_ctx_last_plan): host fields, stored where the launch decides them
-  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, xfwd_ids_lds, stream_hints, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max, select_rows_per_chunk, select_chunks, select_path, select_splits, filter_path, filter_splits, filter_split_max, audience_path, audience_splits, audience_split_max, similar_path, similar_splits, similar_split_max, capped_splits, capped_split_max, lists_path, labels_splits, labels_split_max, labels_home, labels_chunks, labels_rows_per_chunk; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
+  struct LastPlan { int valid, tile, one, rec1, xrec1, hyb, bintab, ppoi, listed, fwd_tab, xft, xcomp, xfwd_ids_lds, stream_hints, head_split, efuse, early_bins, fork, cell_kernel, cell_grid, session_path, session_tiles, session_tile_min, near_path, near_splits, near_split_max, rank_splits, geoie_score_span, geoie_score_splits, group_path, group_splits, group_split_max, route_path, route_splits, diverse_path, diverse_splits, diverse_split_max, select_rows_per_chunk, select_chunks, select_path, select_splits, filter_path, filter_splits, filter_split_max, audience_path, audience_splits, audience_split_max, similar_path, similar_splits, similar_split_max, capped_splits, capped_split_max, lists_path, labels_splits, labels_split_max, labels_home, labels_chunks, labels_rows_per_chunk, explain_columns, explain_tiles, explain_start; const int* hyb_dev; hipStream_t st; uint64_t ws_gen; };
   LastPlan plan = {};
   uint64_t te_ws_gen = 0;   // te_setup calls so far: a later one may reuse the workspace that holds plan.hyb_dev
   // BPR
@@ -161,6 +161,9 @@ struct poi_ctx {
   int labels_grid = 0;      // option "labels_grid": slices in the split regime (0: by the row count and the CUs)
   int labels_lds_kb = 40;   // option "labels_lds_kb": the accumulators of a workgroup live in LDS while 32 (n_label + 1) 20 bytes fit this many KiB (0: always in global memory); not measured yet
   int labels_ws_kb = 256 << 10; // option "labels_ws_kb": the accumulator workspace holds at most this many KiB (whole 32-row tiles, at least one); more rows go through it in chunks
+  // leave-one-out attribution (explain.hip): the rows' bad-id flags and the base states after every 16th position
+  DevBuf explain_ws;
+  int explain_start = 1;    // option "explain_start": 1 - a variant starts from the base walk's checkpoint before its first removed position; 0 - at position 0 from h = 0
   // re-ranking (rerank.hip): the rejected-row flags of poi_score_lists; poi_rerank's scores between its two stages
   DevBuf rerank_ws;
   // scoring

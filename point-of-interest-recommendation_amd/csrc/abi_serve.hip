@@ -192,6 +192,49 @@ int poi_session_sts(poi_ctx* c, const poi_gru_params* P, const double* h, int32_
 }
 
 // ---------------------------------------------------------------------------------------------
+// leave-one-out attribution (explain.hip)
+// ---------------------------------------------------------------------------------------------
+int poi_explain_loo(poi_ctx* c, const poi_gru_params* P, const double* coords, const double* cphi, const double* thr, double dd,
+                    const int32_t* h_off, const int32_t* h_ids, int64_t total, const int32_t* grp, const int32_t* g_off, int32_t n_group,
+                    int32_t n, int32_t max_len, const int32_t* base_cols, const int32_t* var_cols, int32_t n_var, const int32_t* lists,
+                    int32_t n_list, double* base, double* delta, double* h_out, double* sts_out, int32_t* last_out, void* stream) {
+  if (!c || !P) return fail(c, POI_EINVAL, "poi_explain_loo: NULL ctx/params");
+  if (!P->lt || !P->ui || !P->wh || !P->bi) return fail(c, POI_EINVAL, "poi_explain_loo: lt/ui/wh/bi must be non-NULL");
+  const bool spatial = P->di != nullptr || P->n_dist != 0;
+  int rc = session_check(c, P, spatial, "poi_explain_loo");
+  if (rc) return rc;
+  if (spatial && (!coords || !cphi || !thr || !P->wd || !(dd > 0))) return fail(c, POI_EINVAL, "poi_explain_loo: the spatial cell needs coords / cphi / thr / wd and dd > 0");
+  if (n < 0 || n_group < 0 || n_var < 0 || total < 0 || max_len < 0) return fail(c, POI_EINVAL, "poi_explain_loo: n / n_group / n_var / total / max_len < 0");
+  if (n_list <= 0 || n_list > EXPLAIN_C_MAX) return fail(c, POI_ENOTSUP, "poi_explain_loo supports 1 <= n_list <= %d (got %d)", EXPLAIN_C_MAX, n_list);
+  const int xw = spatial ? 2 * P->dim : P->dim, NB = spatial ? P->n_dist + 1 : 1;
+  if (!poi::explain_supported(P->dim, xw, NB, spatial ? 1 : 0))
+    return fail(c, POI_ENOTSUP, "poi_explain_loo: dim must be a multiple of 16 in [16, 256] (got %d) and the tile must fit the LDS - build the model with pad_dim=True", P->dim);
+  if (n == 0) return POI_OK;
+  if (!h_off || !h_ids || !grp || !g_off || !base_cols || !lists || !base) return fail(c, POI_EINVAL, "poi_explain_loo: NULL h_off / h_ids / grp / g_off / base_cols / lists / base");
+  if (n_var > 0 && (!var_cols || !delta || n_group <= 0)) return fail(c, POI_EINVAL, "poi_explain_loo: variants need var_cols / delta and n_group > 0");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  poi::ExplainArgs A = poi::ExplainArgs{};
+  A.lt = P->lt; A.lt_f16 = is_f16(c, P->lt);
+  A.di = P->di; A.ui = P->ui; A.wh = P->wh; A.bi = P->bi; A.vs = P->vs; A.bs = P->bs; A.wd = P->wd;
+  A.n_item = P->n_item; A.n_dist = spatial ? P->n_dist : 0; A.dim = P->dim; A.xw = xw; A.spatial = spatial ? 1 : 0;
+  A.coords = coords; A.cphi = cphi; A.thr = thr; A.dd = dd;
+  A.h_off = h_off; A.h_ids = h_ids; A.total = total; A.grp = grp; A.g_off = g_off; A.n_group = n_group; A.n = n;
+  A.base_cols = base_cols; A.var_cols = var_cols; A.n_var = n_var; A.start_mode = c->explain_start;
+  A.nck = max_len > 16 ? (max_len - 1) / 16 : 0;
+  A.lists = lists; A.C = n_list; A.base = base; A.delta = delta; A.h_out = h_out; A.sts_out = sts_out; A.last_out = last_out;
+  if ((rc = bad_counter(c, st, &A.bad))) return rc;
+  if ((rc = carve(c, c->explain_ws, st, [&](Carver& W) {
+         A.rowbad = (int*)W.bytes(sizeof(int) * (size_t)n);
+         A.ck = (double*)W.bytes(sizeof(double) * (size_t)n * (size_t)A.nck * (size_t)A.dim);
+       })))
+    return rc;
+  c->plan.valid = 1; c->plan.explain_columns = n + n_var; c->plan.explain_tiles = (n + 15) / 16 + (n_var + 15) / 16; c->plan.explain_start = c->explain_start;
+  HIPCHK(c, poi::launch_explain(A, st, &c->tm));
+  return POI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // online sessions of Lstm / Rnn / CA-RNN (session_cells.hip)
 // ---------------------------------------------------------------------------------------------
 static int session_cells_run(poi_ctx* c, poi::SessCellArgs& A, const char* who, void* stream) {

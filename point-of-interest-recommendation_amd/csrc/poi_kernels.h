@@ -574,6 +574,28 @@ hipError_t launch_session(SessArgs& A, int tile, hipStream_t st, Timing* tm);
 // the repeated-slot claims alone (sess_claim_kernel + sess_mark_kernel): owner[s] = the one event that names slot s, or -1
 hipError_t launch_session_claims(const int* slot, int n, int n_slot, int* owner, hipStream_t st);
 
+// Leave-one-out attribution (explain.hip): base and per-variant scores of listed POIs, 16 (row, key) columns per workgroup
+#define EXPLAIN_C_MAX 32                    // listed POIs per row
+struct ExplainArgs {
+  const void* lt; int lt_f16;               // POI snapshot: float32, or IEEE half when lt_f16 (step inputs and the scored rows)
+  const float *di, *ui, *wh, *bi, *vs, *bs, *wd;      // di / vs / bs / wd null: the plain cell
+  int n_item, n_dist, dim, xw, spatial;
+  const double *coords, *cphi, *thr; double dd;
+  const int *h_off, *h_ids; long long total;          // histories: row r = h_ids[h_off[r] .. h_off[r + 1]), total ids
+  const int *grp, *g_off; int n_group;      // group of every position within its row; rows of delta per row: g_off[r] .. g_off[r + 1]
+  int n;
+  const int *base_cols, *var_cols; int n_var;         // int4 (row, key, start, 0) per column: n base columns (key -1), n_var variants
+  int start_mode;                           // 1: a variant starts at its column's start from the checkpoint; 0: at position 0 from h = 0
+  double* ck; int nck;                      // (n, nck, D) base states after positions 16, 32, ..., 16 nck
+  int* rowbad;                              // (n) rows with an id out of range
+  const int* lists; int C;                  // (n, C), -1: no entry
+  double *base, *delta;                     // (n, C), (n_group, C)
+  double *h_out, *sts_out; int* last_out;   // optional per variant: (n_group, D), (n_group, n_dist + 1), (n_group)
+  int* bad;                                 // device counter of rejected rows (poi_ctx_take_bad_ids)
+};
+bool explain_supported(int D, int xw, int NB, int spatial);
+hipError_t launch_explain(ExplainArgs& A, hipStream_t st, Timing* tm);
+
 // Online sessions of Lstm / Rnn / CA-RNN (session_cells.hip): the same state and launch regimes, templated on the cell
 struct SessCellArgs {
   int G;                                    // gate blocks: 1 Rnn, 4 Lstm, 0 CA-RNN

@@ -27,10 +27,6 @@ namespace poi {
 
 namespace {
 
-__device__ __forceinline__ float ld_tab(const void* base, size_t off, int f16) {
-  return f16 ? __half2float(reinterpret_cast<const __half*>(base)[off]) : reinterpret_cast<const float*>(base)[off];
-}
-
 // softmax(vs . hs + bs) of one event by the whole workgroup: float32 rows to st (state, may be null) and out (may be null)
 __device__ __forceinline__ void event_head(const SessArgs& A, const double* hs, double* lg, double* red, float* st, float* out) {
   const int D = A.dim, NB = A.n_dist + 1, lane = lane_id(), w = wave_id(), tid = threadIdx.x;
@@ -155,30 +151,7 @@ __global__ __launch_bounds__(256) void sess_event_kernel(SessArgs A) {
   }
 }
 
-// ---- tile path: 16 events per workgroup, float64 MFMA ---------------------------------------------------------------------------------
-namespace {
-// acc[q] += W_q[16 rows][K] . S[K][16 events]: wrow[q] = this lane's row of W_q at column 4 g; S k-major in LDS at the swizzled rows
-// (not merged with session_cells.hip's sc_mma, which prefetches the next k-block: unifying them would change one kernel's schedule)
-template <int NG, class T>
-__device__ __forceinline__ void sess_mma(f64x4 (&acc)[NG], const float* const (&wrow)[NG], int K, const T* sT, int i, int g) {
-  for (int kq = 0; kq < (K >> 4); ++kq) {
-    float4 a[NG];
-#pragma unroll
-    for (int q = 0; q < NG; ++q) a[q] = ld4(wrow[q] + 16 * kq);
-    const T* bp = sT + (size_t)(16 * kq + g) * RS + i;
-    const double b0 = (double)bp[0], b1 = (double)bp[4 * RS], b2 = (double)bp[8 * RS], b3 = (double)bp[12 * RS];
-#pragma unroll
-    for (int q = 0; q < NG; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[q].x, b0, acc[q], 0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < NG; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[q].y, b1, acc[q], 0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < NG; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[q].z, b2, acc[q], 0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < NG; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[q].w, b3, acc[q], 0, 0, 0);
-  }
-}
-}  // namespace
-
+// ---- tile path: 16 events per workgroup, float64 MFMA (sess_mma and the gate expressions: session_common.h) ---------------------------
 size_t sess_tile_lds(int D, int xw, int NB, int spatial) {
   size_t r0 = sizeof(float) * RS * (size_t)xw;
   if (spatial && sizeof(double) * RS * (size_t)NB > r0) r0 = sizeof(double) * RS * (size_t)NB;

@@ -24,6 +24,32 @@ __device__ __forceinline__ int pos_bin(const Args& A, int cur, int prev) {
   return bin_of_c(c, A.thr, A.n_dist, (float)(12742.0 * 1000.0 / A.dd));
 }
 
+__device__ __forceinline__ float ld_tab(const void* base, size_t off, int f16) {
+  return f16 ? __half2float(reinterpret_cast<const __half*>(base)[off]) : reinterpret_cast<const float*>(base)[off];
+}
+
+// ---- the 16-column float64 matrix-core cell step (session.hip's tile kernel, explain.hip's walk) ------------------------------------
+// acc[q] += W_q[16 rows][K] . S[K][16 events]: wrow[q] = this lane's row of W_q at column 4 g; S k-major in LDS at the swizzled rows
+// (not merged with session_cells.hip's sc_mma, which prefetches the next k-block: unifying them would change one kernel's schedule)
+template <int NG, class T>
+__device__ __forceinline__ void sess_mma(f64x4 (&acc)[NG], const float* const (&wrow)[NG], int K, const T* sT, int i, int g) {
+  for (int kq = 0; kq < (K >> 4); ++kq) {
+    float4 a[NG];
+#pragma unroll
+    for (int q = 0; q < NG; ++q) a[q] = ld4(wrow[q] + 16 * kq);
+    const T* bp = sT + (size_t)(16 * kq + g) * RS + i;
+    const double b0 = (double)bp[0], b1 = (double)bp[4 * RS], b2 = (double)bp[8 * RS], b3 = (double)bp[12 * RS];
+#pragma unroll
+    for (int q = 0; q < NG; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[q].x, b0, acc[q], 0, 0, 0);
+#pragma unroll
+    for (int q = 0; q < NG; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[q].y, b1, acc[q], 0, 0, 0);
+#pragma unroll
+    for (int q = 0; q < NG; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[q].z, b2, acc[q], 0, 0, 0);
+#pragma unroll
+    for (int q = 0; q < NG; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[q].w, b3, acc[q], 0, 0, 0);
+  }
+}
+
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -346,6 +346,34 @@ def similar_covisit_rate(model, k, geo_weight=0.0, scale_km=1.0, seed=0):
                 pairs=int(listed.sum()))
 
 
+def attribution_by_recency(model, starts_ends, k, explain=None):
+    """How far back does a recommendation look?  Every user's own top-k is attributed to their train check-ins (models.Explainer(model).explain
+    - or the callable `explain` of the same form - leave-one-out, by="checkin"); check-in t of a history of length L gets the share sum_c |delta[t, c]| / sum_{t', c} |delta[t', c]|
+    of the user's attribution.  Returns dict(share= the mean share by position counted from the END (share[0]: the last check-in),
+    over the users who have that position, count= those users per position, rows= the users counted: the ones with a history and
+    any attribution at all)."""
+    if explain is None:
+        from .models import Explainer
+        explain = Explainer(model).explain
+    tot, cnt, rows = np.zeros(0), np.zeros(0, np.int64), 0
+    for se in coalesce_ranges(starts_ends):
+        out = explain(se, model.compute_sub_topk(se, k))
+        delta, off = (np.asarray(t.cpu().numpy()) for t in out[1:3])
+        if not len(delta):
+            continue
+        mass = np.nansum(np.abs(delta), axis=1)
+        row = np.repeat(np.arange(len(off) - 1), np.diff(off))
+        whole = np.bincount(row, weights=mass, minlength=len(off) - 1)
+        live = whole[row] > 0
+        from_end = (off[1:][row] - 1 - np.arange(len(mass)))[live]
+        n_pos = max(len(tot), int(from_end.max()) + 1 if live.any() else 0)
+        tot, cnt = np.pad(tot, (0, n_pos - len(tot))), np.pad(cnt, (0, n_pos - len(cnt)))
+        tot += np.bincount(from_end, weights=(mass / np.maximum(whole[row], 1e-300))[live], minlength=n_pos)
+        cnt += np.bincount(from_end, minlength=n_pos)
+        rows += int((whole > 0).sum())
+    return dict(share=tot / np.maximum(cnt, 1), count=cnt, rows=rows)
+
+
 def foldin_rank_metrics(model, histories, targets, at_nums, exclude="history", **fold_in_kwargs):
     """full_rank_metrics for HELD-OUT users of the factorisation family, of the successive-POI models OboFpmc_lr / OboPrme and of
     OboPoi2vec (strong generalisation): every history is folded in (model.rank_new: fold_in, then the exact rank of its targets among all POIs) and the

@@ -1873,7 +1873,7 @@ class _Base:
         float64 similarity (0 <= geo_weight <= 1).  histories: "train" (the rows' train sequences) or a CSR pair (off, ids) of POI ids per
         row, in any order, duplicates allowed.  Returns (n, k) int32 history POI ids on the device, -1 where there is none (a -1 entry,
         an empty history)[, the (n, k) float64 similarities, -inf there]; ties go to the earlier history position.  This attributes a
-        recommendation to the most similar visited POI - it does NOT decompose the model's score.  Host arguments are checked before the
+        recommendation to the most similar visited POI - it does NOT decompose the model's score (Explainer.explain does).  Host arguments are checked before the
         launch; device tensors by the kernel (an offending row comes out all -1 and - with sync - raises IndexError)."""
         geo_weight, scale_km = float(geo_weight), float(scale_km)
         if not 0.0 <= geo_weight <= 1.0:
@@ -2067,6 +2067,52 @@ class _Base:
 
 
 # =================================================================================================
+# ---- leave-one-out attribution (poi_explain_loo): the groups a history is cut into and the kernel's column tables ------------------------
+def explain_groups(off, p, by):
+    """The groups of GruBasic.explain over the CSR histories (off (n + 1) int64 from 0, p (total) ids; tensors of one device, torch ops
+    only).  by="checkin": one group per position; by="poi": one per distinct POI of a row, numbered by first occurrence.  Returns
+    (grp (total) int32 - the group of every position within its row, g_off (n + 1) int64 - row r owns the delta rows g_off[r] ..
+    g_off[r + 1], keys (G) int32 - the POI every group removes, first (G) int64 - the group's first position within its row,
+    row (G) int64)."""
+    if by not in ("checkin", "poi"):
+        raise ValueError("by must be 'checkin' or 'poi' (got %r)" % (by,))
+    dev, n, total = p.device, off.numel() - 1, int(p.numel())
+    off = off.to(dev, torch.int64)
+    pos = torch.arange(total, device=dev)
+    row = torch.repeat_interleave(torch.arange(n, device=dev), off[1:] - off[:-1])
+    local = pos - off[:-1][row]
+    if by == "checkin":
+        return local.int(), off.clone(), p.int(), local, row
+    uniq, inv = torch.unique(row * (1 << 32) + (p.long() & 0xFFFFFFFF), return_inverse=True)      # (row, POI) pairs
+    first = torch.full((uniq.numel(),), total, dtype=torch.int64, device=dev).scatter_reduce_(0, inv, pos, "amin")
+    order = torch.argsort(first)                                # first positions are distinct: row-major, first occurrence within a row
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(order.numel(), device=dev)
+    at = first[order]
+    g_row = row[at]
+    g_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    g_off[1:] = torch.cumsum(torch.bincount(g_row, minlength=n), 0)
+    return (rank[inv] - g_off[:-1][row]).int(), g_off, p[at].int(), local[at], g_row
+
+
+def explain_columns(lens, g_off, first, row, start_mode=1):
+    """The column tables of poi_explain_loo (include/poi_hip.h) for n rows of lengths `lens` and their groups (explain_groups; `row`
+    counts from the first of these rows): int32 quadruples (row, key, start, 0).  base (n, 4): key -1, longest history first.
+    variants (G, 4): key = the group within its row, start = 16 floor(first / 16) (start_mode 0: 0), longest remaining walk
+    lens[row] - start first; equal lengths keep their order."""
+    dev, n = lens.device, lens.numel()
+    lens = lens.long()
+    z = lambda k: torch.zeros(k, dtype=torch.int64, device=dev)
+    b_order = torch.sort(-lens, stable=True)[1]
+    base = torch.stack((b_order, z(n) - 1, z(n), z(n)), 1).int().contiguous()
+    G = first.numel()
+    key = torch.arange(G, device=dev) - g_off[:-1].long()[row]
+    start = (first // 16) * 16 if start_mode else z(G)
+    v_order = torch.sort(-(lens[row] - start), stable=True)[1]
+    var = torch.stack((row, key, start, z(G)), 1)[v_order].int().contiguous()
+    return base, var
+
+
 class GruBasic(_Base):
     """public/GRU.py:32-205."""
 
@@ -2706,6 +2752,110 @@ class OboCARNN(GruBasic):
         return self._topk_from_scores(start_end, k, return_scores)
 
     _rank_fused = False
+
+
+# =================================================================================================
+class Explainer:
+    """Leave-one-out attribution for the GRU family (OboSpatialGru, OboGru, Gru; include/poi_hip.h, poi_explain_loo): which past
+    check-ins drove a recommendation.  `Explainer(model).explain(...)`; like a Session it reads the evaluation SNAPSHOTS trained_items /
+    trained_dists as they are at the call and never changes a model parameter.  (A class of its own rather than a method of GruBasic:
+    the recorded public signatures of the model classes - tests/golden/signatures.json - do not move.)"""
+
+    EXPLAIN_C_MAX = 32
+    EXPLAIN_WS_BYTES = 256 << 20      # of checkpoint states alive at a time: more rows go through the kernel in chunks
+
+    def __init__(self, model):
+        if not isinstance(model, GruBasic) or isinstance(model, (_CellModel, OboCARNN)):
+            raise _lib.PoiError("explain covers the GRU family (OboSpatialGru, OboGru, Gru): %s is out of scope" % type(model).__name__)
+        if model.spatial and model.coords is None:
+            raise _lib.PoiError("explain on the spatial model needs coords= at construction")
+        if model.kdim % 16 or not 16 <= model.kdim <= 256:
+            raise _lib.PoiError("explain needs a stored dim that is a multiple of 16 in [16, 256] (got %d): build the model with pad_dim=True" % model.kdim)
+        self.m = model
+
+    def _explain_lists(self, lists, n):
+        """lists -> (n, C <= 32) int32 device tensor; host lists are range-checked as nearest_visited checks them."""
+        m = self.m
+        if isinstance(lists, torch.Tensor) and lists.is_cuda:
+            lt = lists.to(m.device, torch.int32)
+        else:
+            a = np.asarray(lists.cpu().numpy() if isinstance(lists, torch.Tensor) else lists).astype(np.int64)
+            if a.size and (a.min() < -1 or a.max() >= m.n_item):
+                raise IndexError("listed POIs must lie in [-1, %d) (found %d..%d)" % (m.n_item, int(a.min()), int(a.max())))
+            lt = torch.as_tensor(a.astype(np.int32)).to(m.device)
+        if lt.dim() != 2 or lt.shape[0] != n or not 1 <= lt.shape[1] <= self.EXPLAIN_C_MAX:
+            raise ValueError("lists must be (%d rows, 1 <= C <= %d) (got %s)" % (n, self.EXPLAIN_C_MAX, tuple(lt.shape)))
+        return lt.contiguous()
+
+    def explain(self, start_end, lists, histories="train", by="checkin", return_states=False, sync=True):
+        """WHY these POIs (include/poi_hip.h, poi_explain_loo): the leave-one-out attribution of listed POIs to a row's history.  For
+        every row of start_end and every POI of its list - lists (n, C <= 32), -1 fill, typically the row's recommendations - the
+        model's score with the whole history (base) and, per group g of the history, base minus the score with the group taken out
+        (delta): positive - those check-ins pushed the POI up.  by="checkin": a group is one position; by="poi": every visit of one
+        POI, groups in first-occurrence order.  The history without a group runs through the cell as a fresh session would, the step
+        after a gap binned against the last kept POI; state, head and scores are float64.  histories: "train" (the rows' train
+        sequences) or what fold_in takes (a CSR pair (off, p_flat), a list of sequences), one per row.
+        Returns (base (n, C) float64, delta (G, C) float64, off (n + 1) int64: row r owns delta[off[r] : off[r + 1]], keys (G) int32:
+        the POI every delta row removed) on the device[, dict(h (G, dim), sts (G, n_dist + 1) - spatial, last_poi (G)): the state of
+        every variant].  A -1 entry gives NaN.  Host arguments are checked before the launch; device tensors by the kernel: a row
+        with a POI out of range comes out NaN and - with sync - raises IndexError."""
+        if by not in ("checkin", "poi"):
+            raise ValueError("by must be 'checkin' or 'poi' (got %r)" % (by,))
+        m = self.m
+        ids, _ = m._ids(start_end)
+        n = ids.numel()
+        lt = self._explain_lists(lists, n)
+        C = lt.shape[1]
+        dev = m.device
+        if isinstance(histories, str):
+            if histories != "train":
+                raise ValueError("histories must be 'train' or what fold_in takes (got %r)" % (histories,))
+            off_h, ids_h = m._similar_train()[:2]
+            a = ids.cpu().numpy().astype(np.int64)
+            ln = off_h[a + 1] - off_h[a]
+            o = np.concatenate(([0], np.cumsum(ln)))
+            take = np.arange(int(o[-1])) - np.repeat(o[:-1] - off_h[a], ln)
+            histories = (o, ids_h[take])
+        on_device = isinstance(histories, tuple) and len(histories) == 2 and isinstance(histories[1], torch.Tensor) and histories[1].is_cuda
+        off_t, p, n_h, total = m._foldin_csr(histories)
+        if n_h != n:
+            raise ValueError("explain: %d rows but %d histories" % (n, n_h))
+        if not on_device and total and int(p[:total].max()) >= m.n_item:      # (fold_in admits the padding id n_item; a walk cannot)
+            raise IndexError("history POIs must lie in [0, %d) (found %d)" % (m.n_item, int(p[:total].max())))
+        off = off_t.cpu().numpy().astype(np.int64)
+        lens = np.diff(off)
+        if lens.size and lens.min() < 0:
+            raise ValueError("histories=(off, p_flat): off must ascend")
+        grp, g_off, keys, first, g_row = explain_groups(off_t.long(), p[:total], by)
+        g_host = g_off.cpu().numpy()
+        G = int(g_host[-1])
+        base = torch.empty((n, C), dtype=torch.float64, device=dev)
+        delta = torch.empty((G, C), dtype=torch.float64, device=dev)
+        NB = m.n_dist + 1 if m.spatial else 0
+        h_out = torch.empty((G, m.kdim), dtype=torch.float64, device=dev) if return_states else None
+        s_out = torch.empty((G, NB), dtype=torch.float64, device=dev) if return_states and m.spatial else None
+        l_out = torch.empty(G, dtype=torch.int32, device=dev) if return_states else None
+        P, sp = m._params(snapshot=True), m.spatial
+        mode = int(m.ctx.options.get("explain_start", 1))
+        g32, lens_t = g_off.int().contiguous(), torch.as_tensor(lens).to(dev)
+        grp = m._some_ids(grp.contiguous())
+        per_row = max(1, (int(lens.max()) - 1) // 16 if n else 1) * m.kdim * 8
+        for o, c in m._row_chunks(n, max(1, self.EXPLAIN_WS_BYTES // per_row)):
+            g0, g1 = int(g_host[o]), int(g_host[o + c])
+            bc, vc = explain_columns(lens_t[o:o + c], g_off[o:o + c + 1] - g0, first[g0:g1], g_row[g0:g1] - o, mode)
+            m.ctx.check(m.lib.poi_explain_loo(
+                m.ctx.handle, ctypes.byref(P), _ptr(m.coords if sp else None), _ptr(m._cphi if sp else None),
+                _ptr(m._binthr if sp else None), m.dd * 1000.0 if sp else 0.0, _ptr(off_t[o:]), _ptr(p), total, _ptr(grp), _ptr(g32[o:]), G,
+                c, int(lens[o:o + c].max()), _ptr(bc), _ptr(vc) if g1 > g0 else None, g1 - g0, _ptr(lt[o:]), C, _ptr(base[o:]), _ptr(delta),
+                _ptr(h_out), _ptr(s_out), _ptr(l_out), m._stream()))
+        states = None
+        if return_states:
+            states = dict(h=h_out[:, :m.dim], last_poi=l_out)
+            if sp:
+                states["sts"] = s_out
+        return m._serve_out(base, ((delta, True), (g_off, True), (keys, True), (states, return_states)), sync and n > 0,
+                               "row(s) with a history POI outside [0, %d) or a listed POI outside [-1, %d): their base, deltas and states are NaN"
+                               % (m.n_item, m.n_item))
 
 
 # =================================================================================================
